@@ -15,7 +15,7 @@ pocket and ~89 % of the per-block edge work becomes dead (and is skipped): that 
 reported beside the headline as `config.drifted_shipped_schedule_chain`, never as `value`.  The headline model is the
 same architecture and weight generator with noise_precision 0.1, norm_values [1, 0.25] (1/alpha_T = 3.2, max|x| ~ 17 A).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--timesteps T]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--timesteps T] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Both forms work: started WITHOUT a torch.distributed environment and with --gpus N > 1, this process touches no
@@ -108,7 +108,29 @@ def parse(argv=None):
                         '(tests/test_hip_rccl.py); needs RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT in the environment')
     p.add_argument('--dry-run-launch', action='store_true',
                    help='launch logic only (CPU, gloo, no sampling): used by tests/test_bench_launch.py')
-    return p.parse_args(argv)
+    p.add_argument('--dump-outputs', default=None, metavar='DIR',
+                   help='after the timed steps, write what the last timed chain returned (xh_phar, xh_pocket) as DIR/<name>.npy in float32 '
+                        '(ranks other than 0 add _rank<r>); the inputs are seeded, so two builds can be compared output for output')
+    args = p.parse_args(argv)
+    if args.steps < 1:
+        p.error('--steps must be >= 1')
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, suffix=''):
+    """--dump-outputs: one float32 .npy per array; past DUMP_LIMIT_BYTES in all, every array keeps a fixed, seeded sample of its rows."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        frac = DUMP_LIMIT_BYTES / total
+        rng = np.random.Generator(np.random.PCG64(0))
+        arrays = {k: a[np.sort(rng.choice(len(a), max(1, int(len(a) * frac)), replace=False))] for k, a in arrays.items()}
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + suffix + '.npy'), a)
 
 
 # --------------------------------------------------------------------------------------------- launching N ranks
@@ -485,6 +507,9 @@ def main(argv=None):
         elapsed = time.perf_counter() - t0
         cnt = h.counters()
         st = h.chain_status()
+        if args.dump_outputs:                 # (outside the timed region) what a caller of the timed path receives from its last step
+            dump_outputs(args.dump_outputs, {'xh_phar': out[0].cpu().numpy(), 'xh_pocket': out[1].cpu().numpy()},
+                         suffix=f'_rank{rank}' if rank else '')
     if dist is not None:
         tmax = torch.tensor([elapsed], device=cdev, dtype=torch.float64)
         wait_collective(dist.all_reduce(tmax, op=dist.ReduceOp.MAX, async_op=True))

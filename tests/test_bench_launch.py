@@ -89,3 +89,26 @@ def test_scale_day_one_script_dry_run(tmp_path):
         assert weak['n_gpus'] == n and weak['scaling'] == 'weak' and len(weak['pocket_blocks']) == n
         assert strong['n_gpus'] == n and strong['scaling'] == 'strong'
         assert strong['pocket_blocks'][0][0] == 0 and strong['pocket_blocks'][-1][1] == 512
+
+
+def test_dump_outputs_writes_float32_within_the_size_limit(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per returned array; past the size limit every array keeps a fixed, seeded row sample."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    a, b = np.arange(40.0).reshape(20, 2), np.ones((20, 3), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / 'full'), {'a': a, 'b': b})
+    got = np.load(tmp_path / 'full' / 'a.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, a)
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 200)
+    for d in ('s1', 's2'):
+        bench.dump_outputs(str(tmp_path / d), {'a': a, 'b': b}, suffix='_rank1')
+    s1, s2 = np.load(tmp_path / 's1' / 'a_rank1.npy'), np.load(tmp_path / 's2' / 'a_rank1.npy')
+    assert np.array_equal(s1, s2) and 0 < len(s1) < 20
+    assert sum(os.path.getsize(tmp_path / 's1' / f) - 128 for f in ('a_rank1.npy', 'b_rank1.npy')) <= 200
+
+
+def test_steps_must_be_positive():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--dry-run-launch', '--steps', '0'],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode != 0 and '--steps' in r.stderr
