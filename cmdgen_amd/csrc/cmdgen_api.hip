@@ -1320,7 +1320,7 @@ extern "C" int cmdgen_get_counters(cmdgen_handle* h, cmdgen_counters* out, cmdge
     HIPCHK(h, hipMemcpy(cnt, h->work.counters, sizeof cnt, hipMemcpyDeviceToHost));
     memset(out, 0, sizeof *out);
     out->evaluations = cnt[0]; out->edges = cnt[1]; out->edges_phar = cnt[2]; out->nodes = cnt[3]; out->nan_resets = cnt[4];
-    out->edges_skipped = cnt[6]; out->node_rows_skipped = cnt[7];
+    out->edges_skipped = cnt[6]; out->node_rows_skipped = cnt[7]; out->half_low_range = cnt[HALF_LOW_SLOT];
     return CMDGEN_OK;
 }
 

@@ -79,6 +79,42 @@ __device__ __forceinline__ float4 pos_mat(const Layout& lay, const Work& w, int 
     return layer == 0 ? w.X0[n] : w.XL[(size_t)layer * lay.Nm + n];
 }
 
+// The half engine's low-range flags (cmdgen_split.h: HALF_LOW_TAU) of the tile's rows, taken on ONE QUARTER of K (64 of 256 columns): the last,
+// whose planes stay in LDS until the tile loop's next barrier - read back at the end of the tile, outside the pipelined build and GEMM, whose
+// registers are spoken for.  A row whose max |a| over all of K lies below tau has it below tau on that quarter too, so no such row is missed; a row flagged on its
+// quarter alone costs a repeated call, never a wrong result (the random-init models keep their smallest one-quarter row max, 0.07, a binade
+// above tau).  The planes hold a0 = fp16(a): tau is a power of two, so |a0| >= tau exactly when |a| >= tau, up to the rounding at tau itself.
+// Per thread: its four columns of row slot sl (rows 16 sl + tid / 16) -> bit sl: some |a0| reaches tau.
+__device__ __forceinline__ unsigned low_range_slot(const unsigned short* p4, int sl) {
+    const uint2 p = *reinterpret_cast<const uint2*>(p4);
+    const unsigned tb = __builtin_bit_cast(unsigned short, (_Float16)HALF_LOW_TAU);
+    const unsigned m = max(max(p.x & 0x7fffu, (p.x >> 16) & 0x7fffu), max(p.y & 0x7fffu, (p.y >> 16) & 0x7fffu));   // fp16 magnitudes order as their bits
+    return (m >= tb ? 1u : 0u) << sl;
+}
+__device__ __forceinline__ unsigned low_range_flags(const E128Lds& L, const int tid, const int nslots) {
+    const int c4 = tid & 15, rsub = tid >> 4;
+    unsigned bits = 0u;
+    for (int sl = 0; sl < nslots; ++sl) {
+        if constexpr (FUSED) {          // quarter 3 in plane buffer 1, 16-byte chunks XOR-swizzled by row (x_main's wofs)
+            const int wofs = (rsub * KQ + ((((c4 >> 1) ^ (rsub & 7)) << 3) | ((c4 & 1) << 2))) * 2;
+            bits |= low_range_slot(reinterpret_cast<const unsigned short*>(reinterpret_cast<const unsigned char*>(L.planes) + 4 * PLF + sl * (16 * KQ * 2) + wofs), sl);
+        } else {
+            bits |= low_range_slot(L.planes + (16 * sl + rsub) * PLDA + 4 * c4, sl);
+        }
+    }
+    return bits;
+}
+// the tile's valid rows (16 sl + tid / 16 < ne) whose max |a| (last quarter) lies below HALF_LOW_TAU: the thread's flags ORed over the 16 lanes
+// of its rows, counted by the lane tid % 16 == 0 (rows past ne repeat the tile's last row and are not counted)
+__device__ __forceinline__ unsigned low_range_rows(unsigned range, const int tid, const int ne, const int nslots) {
+#define LR_OR(CTRL) range |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)range, CTRL, 0xf, 0xf, true);
+    LR_OR(0xb1) LR_OR(0x4e) LR_OR(0x141) LR_OR(0x140)             // quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror: the 16 lanes of a row
+#undef LR_OR
+    const int nv = min(max((ne - (tid >> 4) + 15) >> 4, 0), nslots);
+    const unsigned flagged = ~range & ((1u << nv) - 1u);
+    return (tid & 15) == 0 ? (unsigned)__builtin_popcount(flagged) : 0u;
+}
+
 // ---- tile build: columns [64 q, 64 q + 64) of SiLU(P[row] + Q[col] + w_r r + w_d d0) as three bf16 planes, in two batches of 64 rows
 // (8 gathered float4 per thread and batch: with the 128 accumulators and the weight fragments a whole tile's 16 would spill).  The
 // gather of a batch and its use are separate calls so that a batch can be in flight during the GEMM over the previous quarter.
@@ -124,7 +160,8 @@ __device__ __forceinline__ void store_half(E128Lds& L, const int tid, const int 
             const float4 a = make_float4(silu_f(G_F(g.p, 0) + G_F(g.q, 0) + wr4.x * r + wd4.x * d0), silu_f(G_F(g.p, 1) + G_F(g.q, 1) + wr4.y * r + wd4.y * d0),
                                          silu_f(G_F(g.p, 2) + G_F(g.q, 2) + wr4.z * r + wd4.z * d0), silu_f(G_F(g.p, 3) + G_F(g.q, 3) + wr4.w * r + wd4.w * d0));
 #undef G_F
-            if constexpr (NPL == 3) split_store4(L.planes, PE, e * PLDA + 4 * c4, a); else split_store4_half(L.planes, PE, e * PLDA + 4 * c4, a);
+            if constexpr (NPL == 3) split_store4(L.planes, PE, e * PLDA + 4 * c4, a);
+            else split_store4_half(L.planes, PE, e * PLDA + 4 * c4, a);
         }
 }
 
@@ -560,6 +597,13 @@ __device__ __forceinline__ void tile_compute(E128Lds& L, const Layout& lay, cons
                 }
             }
         flush();                                                         // the tile's last segment when it ends with the tile's last row
+    }
+    // half engine: the rows below the engine's range, from the last quarter's planes - intact until the tile loop's next barrier; here, after
+    // the epilogue, the accumulators are free (low_range_flags)
+    if constexpr (NPL == 2) {
+        // (the thread index formed anew - the wave's index in a scalar register, the lane by mbcnt - so that no vector register is held across the tile for it)
+        const int t = 64 * wave + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        half_low_count(w.counters, low_range_rows(low_range_flags(L, t, 2 * NMT), t, ne, 2 * NMT));
     }
 #undef STAMP
 #undef STAMPB

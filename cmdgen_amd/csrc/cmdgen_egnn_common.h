@@ -190,13 +190,16 @@ __device__ __forceinline__ void build_edge_half(unsigned short* planes, int half
 // Full-K tile build for 32-row tiles (cmdgen_split.h, tile_gemm_planes_swz32): all 256 columns of the tile at once - 16 gathered rows
 // per thread in flight together, ONE round trip per tile - into the swizzled, unpadded plane image.  Thread -> columns 4 c4 .. 4 c4 + 3
 // (c4 = tid % 64) of rows pass * 4 + tid / 64; wr4 / wd4: the thread's four radial / d0 weights (fixed columns: registers, no LDS).
+// Half engine (NPC = 2): returns the wave's count of valid rows (e < ne) whose max |a| over all of K lies below HALF_LOW_TAU (cmdgen_split.h) -
+// a row is one wave's 64 lanes in one pass, so one ballot decides it.  Wave-uniform; 0 on the bf16 split.
 template <int NPC>
-__device__ __forceinline__ void build_edge_full32(unsigned short* planes, const int* s_row, const int* s_col, const float* s_r, const float* s_d0,
+__device__ __forceinline__ int build_edge_full32(unsigned short* planes, const int* s_row, const int* s_col, const float* s_r, const float* s_d0,
                                                   int ne, const float* __restrict__ P, const float* __restrict__ Q, const float4& wr4, const float4& wd4,
                                                   float* __restrict__ pre_out = nullptr, float* __restrict__ act_out = nullptr) {
     // pre_out / act_out (training forward): the tile's first row of the stored pre-activations / activations (whole 1 KB rows per wave)
     constexpr int H = 256, MT = 32;
     const int c4 = threadIdx.x & 63, rsub = threadIdx.x >> 6;
+    int low = 0;
     float4 p[MT / 4], q[MT / 4];
 #pragma unroll
     for (int pass = 0; pass < MT / 4; ++pass) {
@@ -221,8 +224,14 @@ __device__ __forceinline__ void build_edge_full32(unsigned short* planes, const 
                 if (act_out) reinterpret_cast<float4*>(act_out + (size_t)e * H)[c4] = a;
             }
         }
-        if constexpr (NPC == 3) split_store4_swz(planes, e, c4, a); else split_store4_swz_half(planes, e, c4, a);
+        if constexpr (NPC == 3) split_store4_swz(planes, e, c4, a);
+        else {
+            split_store4_swz_half(planes, e, c4, a);
+            const float m = absmax4(a);
+            low += (e < ne && __ballot(m >= HALF_LOW_TAU) == 0ull) ? 1 : 0;          // (e: wave-uniform)
+        }
     }
+    return low;
 }
 
 // Training save hook: the LDS tile holds PRE-activations.  They and their SiLU leave for HBM as whole rows (16 bytes per

@@ -238,6 +238,15 @@ __global__ __launch_bounds__(512) void k_node16w(Layout lay, Work w, Dims d, Lay
     nw_zero(acc);
     const NwFrag fc = skip_pc ? fnp : want_pc ? fcp : fcq;                   // the GEMM behind W4
     nw_gemm<KB>(buf1, f4, fc, acc, ring);
+    if constexpr (NPL == 2) {
+        // T is the half engine's A operand of the W4 product: its valid rows whose max |t| lies below HALF_LOW_TAU (cmdgen_split.h) are counted -
+        // wave w reads rows 2 w (lanes 0-31) and 2 w + 1, eight columns per lane (rows past nvalid hold SiLU(b3) and are not counted)
+        const int row = tid >> 5, c8 = (tid & 31) * 8;
+        const float m = fmaxf(absmax4(*reinterpret_cast<const float4*>(buf1 + row * NW_LD + c8)), absmax4(*reinterpret_cast<const float4*>(buf1 + row * NW_LD + c8 + 4)));
+        const unsigned long long big = __ballot(m >= HALF_LOW_TAU);
+        const int r0 = 2 * wave;
+        if ((tid & 63) == 0) half_low_count(w.counters, (r0 < nvalid && (unsigned)big == 0u ? 1u : 0u) + (r0 + 1 < nvalid && (big >> 32) == 0ull ? 1u : 0u));
+    }
     NSTAMP(3);
     nw_barrier();
     nw_foreach(acc, wave, [&](int row, int col, int n, float v) {

@@ -182,9 +182,11 @@ __device__ __forceinline__ float4 n64_node_pos(const Layout& lay, const Work& w,
 // sequence: the tile-in and agg hand-over phases took 12k cycles each; profiles/r05_q).  Only a layout's last tile takes the general path.
 // NCT: 32-column tiles per wave - 2: four waves (256 threads); 1: eight waves (512 threads), each with half the columns and half the epilogue work.
 // LEAN: the 64-row four-wave tile sized for TWO workgroups per CU - ring of four k-blocks, no fp32 h tile in LDS (68 KB, <= 256 registers).
+// low_big (half engine): two LDS words, the tile's rows (bit = row) of T = SiLU(pre3) whose max |a| over K reaches HALF_LOW_TAU (cmdgen_split.h)
 template <int NROWS, bool FULL, int NCT, bool LEAN>
 __device__ __forceinline__ void node_planes_tile_body(unsigned short* planes, const Layout& lay, const Work& w, const Dims& d, const LayerW& lw,
-                                                 const LayerW& lw_next, const int layer, const int has_next_arg, const int row0, const int row_end) {
+                                                 const LayerW& lw_next, const int layer, const int has_next_arg, const int row0, const int row_end,
+                                                 unsigned* low_big) {
     constexpr int H = 256, LPR = H / 4, NMT = NROWS / 32, NPE = NROWS * NPLD;
     constexpr int NW = 8 / NCT, NPASS = NROWS / NW;        // waves = rows per pass of the row-wise phases (64 threads per row)
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -240,6 +242,7 @@ __device__ __forceinline__ void node_planes_tile_body(unsigned short* planes, co
     float b3c[NCT], b4c[NCT];
 #pragma unroll
     for (int n = 0; n < NCT; ++n) { b3c[n] = lw.b3[colw + 32 * n] * sc3; b4c[n] = lw.b4[colw + 32 * n]; }
+    if (NPL == 2 && tid < 2) low_big[tid] = 0u;                                // (ordered before the waves' ORs by the barriers in between)
     if (layer >= 1 && tid < NROWS) {                                           // materialise the coordinates entering this block
         const int n = row0 + tid;
         if (tid < nvalid && n < lay.Nm) w.XL[(size_t)layer * lay.Nm + n] = n64_node_pos(lay, w, d, n, layer);
@@ -326,16 +329,40 @@ __device__ __forceinline__ void node_planes_tile_body(unsigned short* planes, co
     NSTAMP(1);
     n64_lds_barrier();                                                         // every wave is done reading agg
     // ---- T = SiLU(pre3): from the accumulators straight into the planes (register pairs r, r + 1 = two rows of one column)
+    // half engine: T is the A operand of the W4 product - the rows of it that some value of this wave's columns keeps in range (|t| >= HALF_LOW_TAU)
+    // collect in a wave-uniform mask (one ballot per register: its two 32-lane halves are rows N64_ROW(m, r) and that + 4), ORed over the waves in LDS.
+    // Only the waves of the first quarter of K (columns 0 - 63) test, as the edge tiles do (cmdgen_edge128_body.h, low_range_rows): a row below tau
+    // over all of K is below it there too; the other waves' epilogue stays as it was (the random-init models' smallest first-quarter row max is 0.059)
+    const bool low_test = NCT * wave < 2;                                     // wave-uniform
+    unsigned long long big = 0ull;
 #pragma unroll
     for (int m = 0; m < NMT; ++m)
 #pragma unroll
-        for (int n = 0; n < NCT; ++n)
+        for (int r = 0; r < 16; r += 2) {
+            float ma = 0.f, mb = 0.f;
 #pragma unroll
-            for (int r = 0; r < 16; r += 2) {
+            for (int n = 0; n < NCT; ++n) {
                 const float bb = b3c[n];
                 const int col = colw + 32 * n;
-                n64_split_store2(planes, NPE, N64_ROW(m, r) * NPLD + col, N64_ROW(m, r + 1) * NPLD + col, n64_silu_scaled(acc[m][n][r] + bb, c13, sc3), n64_silu_scaled(acc[m][n][r + 1] + bb, c13, sc3));
+                const float ta = n64_silu_scaled(acc[m][n][r] + bb, c13, sc3), tb = n64_silu_scaled(acc[m][n][r + 1] + bb, c13, sc3);
+                n64_split_store2(planes, NPE, N64_ROW(m, r) * NPLD + col, N64_ROW(m, r + 1) * NPLD + col, ta, tb);
+                ma = fmaxf(ma, fabsf(ta)); mb = fmaxf(mb, fabsf(tb));
             }
+            if (NPL == 2 && low_test) {
+                const int row = m * 32 + (r & 3) + 8 * (r >> 2);            // N64_ROW(m, r) of lanes 0-31; lanes 32-63: row + 4
+                const unsigned long long ka = __ballot(ma >= HALF_LOW_TAU), kb = __ballot(mb >= HALF_LOW_TAU);
+                if ((unsigned)ka) big |= 1ull << row;
+                if (ka >> 32) big |= 1ull << (row + 4);
+                if ((unsigned)kb) big |= 1ull << (row + 1);
+                if (kb >> 32) big |= 1ull << (row + 5);
+            }
+        }
+    if constexpr (NPL == 2) {
+        if (lane == 0 && low_test) {
+            if ((unsigned)big) atomicOr(&low_big[0], (unsigned)big);
+            if (big >> 32) atomicOr(&low_big[1], (unsigned)(big >> 32));
+        }
+    }
     // the residual's h, in the accumulator layout, requested now (L2) and consumed after the W4 product (two images: fetched above)
 #pragma unroll
     for (int m = 0; m < NMT; ++m)
@@ -348,6 +375,11 @@ __device__ __forceinline__ void node_planes_tile_body(unsigned short* planes, co
             }
     n64_lds_barrier();
     NSTAMP(2);
+    if (NPL == 2 && tid == 0) {             // the valid rows no wave kept in range (a valid row of T is never all zero: SiLU(x) = 0 only at x = 0)
+        const unsigned long long big = (unsigned long long)low_big[0] | ((unsigned long long)low_big[1] << 32);
+        const unsigned long long valid = nvalid >= 64 ? ~0ull : (1ull << nvalid) - 1ull;
+        half_low_count(w.counters, (unsigned)__builtin_popcountll(valid & ~big));
+    }
     N64_ZERO(acc)
     {
         const N64Tiles<NCT> nxt = job_tiles(job0);
@@ -476,8 +508,9 @@ __device__ __forceinline__ void node_planes_tile_body(unsigned short* planes, co
 template <int NROWS, int NCT = 2, bool LEAN = false>
 __device__ __forceinline__ void node_planes_tile(unsigned short* planes, const Layout& lay, const Work& w, const Dims& d, const LayerW& lw,
                                                  const LayerW& lw_next, const int layer, const int has_next_arg, const int row0, const int row_end) {
-    if (row_end - row0 >= NROWS) node_planes_tile_body<NROWS, true, NCT, LEAN>(planes, lay, w, d, lw, lw_next, layer, has_next_arg, row0, row_end);
-    else node_planes_tile_body<NROWS, false, NCT, LEAN>(planes, lay, w, d, lw, lw_next, layer, has_next_arg, row0, row_end);
+    __shared__ unsigned low_big[2];
+    if (row_end - row0 >= NROWS) node_planes_tile_body<NROWS, true, NCT, LEAN>(planes, lay, w, d, lw, lw_next, layer, has_next_arg, row0, row_end, low_big);
+    else node_planes_tile_body<NROWS, false, NCT, LEAN>(planes, lay, w, d, lw, lw_next, layer, has_next_arg, row0, row_end, low_big);
 }
 
 

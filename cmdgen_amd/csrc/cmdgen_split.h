@@ -62,7 +62,30 @@ __device__ __forceinline__ void split3_pair(float a, float b, uint32_t& p0, uint
 // both pieces are normal numbers, and the epilogue folds 1 / wh_scale into constants it multiplies by anyway.  An ACTIVATION above 65504
 // becomes Inf and its second piece NaN: the evaluation's NaN guard then resets the step (dynamics.py:129-131), as for an infinite
 // activation on the bf16 split; no fixture or chain of this repository comes within three orders of magnitude of that.
+// The LOW end is not a NaN: activations are not scaled, and below 2^-3 the second piece a1 ~ 2^-11 a falls under fp16's smallest normal
+// 2^-14.  From there a product keeps an ABSOLUTE error of ~2^-25 |w| instead of a relative one, so a row whose activations are all small
+// loses accuracy against its own result (emulated: 2e-6 at max |a| = 2^-4, 2e-5 at 2^-7, against 1e-6 for an fp32 sgemm) - silently.
+// The producers of the SiLU-output A operands - the edge and coordinate tile builds (edge_mlp.0 / coord_mlp.0 activations feeding the second
+// layer) and the node tiles' T = SiLU(node_mlp.0) feeding W4 - therefore flag every VALID row (rows past a tile's end are not counted) whose
+// max |a| lies below HALF_LOW_TAU = 2^-5 and count it on the device in cmdgen_counters.half_low_range; the Python guard
+// (hip_backend.Handle.run_range_guarded) repeats such a call on the three-piece bf16 split engine, as it does for an overflow.  The max is
+// taken over all of K by the 32-row full-K edge tiles and k_node16w, over ONE quarter of K (64 columns) by the 128-row edge tiles (the last
+// quarter, read back from its planes) and the plane node tiles (the first): a row below tau over all of K is below it on any quarter, so no
+// low row is missed, and a row low on its quarter alone costs a repeated call, never a wrong result.  Not covered: the other half-engine
+// A operands - h and agg / nf into the W3 product, h_new into the projections (sums of messages and residuals, not single SiLU layers).
+// The GEMMs' arithmetic does not change.  tests/test_hip_half_range.py drives both ends.
 // ---------------------------------------------------------------------------------------------
+// 2^-5: emulated (tests/test_half_split_range.py), a row's worst error relative to its own result is ~4e-6 there - a fifth of the evaluation
+// tolerance 2e-5 - and doubles with every binade below (2e-5 at 2^-7).  It cannot sit at 2^-3, where a1 of the largest activation turns
+// subnormal: the fp32 oracle run on this repository's random-init models gives the node tiles' SiLU output rows at max |a| 0.067 - 0.2 in
+// normal operation - 57 % of the node rows of a K = 20 chain of bench.py's model lie below 2^-3, none below 2^-4 - and with tau = 2^-2 the
+// guard fired on every fixture and bench chain; 2^-5 leaves one binade below the smallest such row (a quarter of K: 0.059).
+#define HALF_LOW_TAU 0.03125f
+#define HALF_LOW_SLOT 5                 // cmdgen_counters.half_low_range: index in the device counter array (Work::counters)
+__device__ __forceinline__ float absmax4(const float4& v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); }
+__device__ __forceinline__ void half_low_count(unsigned long long* counters, unsigned n) {
+    if (n) atomicAdd(&counters[HALF_LOW_SLOT], (unsigned long long)n);
+}
 typedef _Float16 sf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 sf16x2 __attribute__((ext_vector_type(2)));
 // two floats -> packed fp16 pair (round to nearest even; v_cvt_pk_f16_f32)

@@ -73,11 +73,12 @@ __device__ __forceinline__ void edge_coord_body(EdgeLds<H, MT, FK>& L, const Lay
         acc_zero<MT>(acc);
         if constexpr (FK) {
             unsigned short* planes = reinterpret_cast<unsigned short*>(buf);
-            build_edge_full32<FK>(planes, s_row, s_col, s_r, s_d0, ne, w.Pc, w.Qc, wr4, wd4,
+            const int low = build_edge_full32<FK>(planes, s_row, s_col, s_r, s_d0, ne, w.Pc, w.Qc, wr4, wd4,
                                   SAVE ? sv.pre6 + ((size_t)layer * sv.eccap + e0) * H : nullptr,
                                   (SAVE && sv.act6) ? sv.act6 + ((size_t)layer * sv.eccap + e0) * H : nullptr);
             lds_barrier();
             G::gemm(planes, fw, acc.a, carry);
+            if ((threadIdx.x & 63) == 0) half_low_count(w.counters, (unsigned)low);      // (half engine: rows below its range)
         } else if constexpr (PL) {
             unsigned short* planes = reinterpret_cast<unsigned short*>(buf);
             constexpr int PLDA = SPLIT_PLANE_LDA(H / 2), PE = MT * PLDA;

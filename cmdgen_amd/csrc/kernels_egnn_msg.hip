@@ -99,12 +99,14 @@ __device__ __forceinline__ void edge_msg_body(EdgeLds<H, MT, FK>& L, const Layou
         acc_zero<MT>(acc);
         if constexpr (FK) {
             unsigned short* planes = reinterpret_cast<unsigned short*>(buf);
-            if (!(ablate & 2)) build_edge_full32<FK>(planes, s_row, s_col, s_r, s_d0, ne, w.P, w.Q, wr4, wd4,
+            int low = 0;
+            if (!(ablate & 2)) low = build_edge_full32<FK>(planes, s_row, s_col, s_r, s_d0, ne, w.P, w.Q, wr4, wd4,
                                                      SAVE ? sv.pre1 + ((size_t)sv.slot * sv.ecap + e0) * H : nullptr,
                                                      (SAVE && sv.act1) ? sv.act1 + ((size_t)sv.slot * sv.ecap + e0) * H : nullptr);
             lds_barrier();
             STAMP(1);
             if (!(ablate & 4)) G::gemm(planes, fw, acc.a, carry);
+            if ((threadIdx.x & 63) == 0) half_low_count(w.counters, (unsigned)low);      // (half engine: rows below its range)
         } else if constexpr (PL) {
             // two half-K passes: build columns [0,128) as bf16 planes -> GEMM over k 0..127 -> build [128,256) -> GEMM over the rest
             unsigned short* planes = reinterpret_cast<unsigned short*>(buf);

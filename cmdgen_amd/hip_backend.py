@@ -30,7 +30,7 @@ class Config(C.Structure):
 class Counters(C.Structure):
     _fields_ = [('evaluations', C.c_uint64), ('edges', C.c_uint64), ('edges_phar', C.c_uint64),
                 ('nodes', C.c_uint64), ('nan_resets', C.c_uint64), ('edges_skipped', C.c_uint64), ('node_rows_skipped', C.c_uint64),
-                ('reserved', C.c_uint64 * 1)]
+                ('half_low_range', C.c_uint64)]
 
 
 class KernelTimes(C.Structure):
@@ -531,27 +531,43 @@ class Handle:
         return out
 
     def chain_status(self):
-        """Deferred checks of the last chain.  `nan_resets` counts the NaN reset steps since the previous call (the library's counter is
-        cumulative: `nan_resets_total`)."""
+        """Deferred checks of the last chain.  `nan_resets` / `half_low_range` count the NaN reset steps / the half engine's low-range rows
+        since the previous call (the library's counters are cumulative: `nan_resets_total`, `half_low_range_total`; run_range_guarded
+        replaces both deltas by those of its own run)."""
         a, b, n = C.c_float(0), C.c_float(0), C.c_int64(0)
         self._check(self.lib.cmdgen_chain_status(self.h, C.byref(a), C.byref(b), C.byref(n), self._stream()),
                     'cmdgen_chain_status')
-        seen = getattr(self, '_nan_seen', 0)
-        self._nan_seen = n.value
-        return {'max_rel_com_error': a.value, 'max_cog': b.value, 'nan_resets': max(n.value - seen, 0), 'nan_resets_total': n.value}
+        low = self.counters()['half_low_range']
+        seen, low_seen = getattr(self, '_nan_seen', 0), getattr(self, '_low_seen', 0)
+        self._nan_seen, self._low_seen = n.value, low
+        return {'max_rel_com_error': a.value, 'max_cog': b.value, 'nan_resets': max(n.value - seen, 0), 'nan_resets_total': n.value,
+                'half_low_range': max(low - low_seen, 0), 'half_low_range_total': low}
 
-    # ---- the half engine's range (two fp16 pieces per operand: an activation beyond 65504 becomes Inf -> NaN -> a reset step the fp32 reference
-    # does not take).  A NaN reset on a half-engine handle is therefore never accepted as it stands: the call is repeated on the three-piece bf16
-    # split engine (fp32's exponent range) with the same inputs and draws.  If that run is clean, its result is returned (and a warning names the
-    # cause); if it resets too, the NaN is the model's own - the reference resets there as well (dynamics.py:129-131) - and that run is returned.
+    # ---- the half engine's range (two fp16 pieces per operand).  At the top an activation beyond 65504 becomes Inf -> NaN -> a reset step the
+    # fp32 reference does not take; at the bottom a row of activations all below 2^-5 has subnormal second pieces and loses fp32 accuracy without
+    # any NaN (cmdgen_split.h: the tile producers count such rows in the counter half_low_range).  A half-engine call with either is therefore never
+    # accepted as it stands: it is repeated on the three-piece bf16 split engine (fp32's exponent range and precision) with the same inputs and
+    # draws, and a warning names the cause.  If that run resets too, the NaN is the model's own - the reference resets there as well
+    # (dynamics.py:129-131) - and that run is returned.
     def half_engine_active(self) -> bool:
         return bool(self.query('half_engine'))
 
     def run_range_guarded(self, run, status):
-        """run() queues the work and returns its outputs; status() -> dict with 'nan_resets' of that run.  -> (outputs, status dict)."""
+        """run() queues the work and returns its outputs; status() -> dict of that run's checks (h.chain_status for a chain, or {}).
+        -> (outputs, status dict with 'nan_resets' and 'half_low_range' of the run returned; 'half_engine_fallback' if it was repeated).
+        The counters are read before and after each run, so what an earlier call on this handle counted is not charged to this one (the read
+        after the first run is the one before the repeat; chain_status's own read serves as the read after a chain)."""
+        def after(st):
+            if 'nan_resets_total' in st and 'half_low_range_total' in st:
+                return {'nan_resets': st['nan_resets_total'], 'half_low_range': st['half_low_range_total']}
+            return self.counters()
+        c0 = self.counters()
         out = run()
         st = status()
-        if not st['nan_resets'] or not self.half_engine_active():
+        c1 = after(st)
+        st['nan_resets'] = c1['nan_resets'] - c0['nan_resets']
+        st['half_low_range'] = low = c1['half_low_range'] - c0['half_low_range']
+        if not (st['nan_resets'] or low) or not self.half_engine_active():
             return out, st
         import warnings
         prev = self.get_option('half_engine')
@@ -561,8 +577,16 @@ class Handle:
             st2 = status()
         finally:
             self.set_option('half_engine', prev)
+        c2 = after(st2)
+        st2['nan_resets'] = c2['nan_resets'] - c1['nan_resets']
+        st2['half_low_range'] = c2['half_low_range'] - c1['half_low_range']
         st2['half_engine_fallback'] = True
-        if not st2['nan_resets']:
+        if low:
+            warnings.warn('activations of this call lay below the half matrix engine\'s precision range (%d rows flagged: max |a| below 2^-5 on '
+                          'the part of K their kernel checks): it was repeated on the three-piece bf16 engine (set option half_engine=0 on this '
+                          'handle to run there from the start)' % low,
+                          RuntimeWarning, stacklevel=3)
+        elif not st2['nan_resets']:
             warnings.warn('an activation left the half matrix engine\'s range (|a| > 65504): this call was repeated on the three-piece bf16 engine '
                           '(set option half_engine=0 on this handle to run there from the start)', RuntimeWarning, stacklevel=3)
         return out2, st2
@@ -574,11 +598,11 @@ class Handle:
     def counters(self) -> Dict[str, int]:
         c = Counters()
         self._check(self.lib.cmdgen_get_counters(self.h, C.byref(c), self._stream()), 'cmdgen_get_counters')
-        return {k: int(getattr(c, k)) for k in ('evaluations', 'edges', 'edges_phar', 'nodes', 'nan_resets', 'edges_skipped', 'node_rows_skipped')}
+        return {k: int(getattr(c, k)) for k, _ in Counters._fields_}
 
     def reset_counters(self):
         self._check(self.lib.cmdgen_reset_counters(self.h, self._stream()), 'cmdgen_reset_counters')
-        self._nan_seen = 0
+        self._nan_seen = self._low_seen = 0
 
     def profile_evaluation(self, xh_phar, xh_pocket, t):
         import torch

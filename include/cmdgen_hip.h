@@ -90,7 +90,11 @@ typedef struct cmdgen_counters {
     uint64_t edges_skipped;        /* edges of k_edge_msg tiles that were skipped as dead work (last block of a conditional evaluation: no receiver
                                       of the tile is still read), summed over launches: the executed edge work is edges * n_layers - this */
     uint64_t node_rows_skipped;    /* rows of k_node tiles skipped for the same reason, summed over launches */
-    uint64_t reserved[1];
+    uint64_t half_low_range;       /* valid rows of the half matrix engine's SiLU-output A operands (edge / coordinate MLP first layers, the
+                                      node MLP's hidden layer) whose max |a| lies below 2^-5 (over all of K, or over one quarter of K in the
+                                      128-row edge and the plane node tiles): there the products lose fp32 accuracy silently (cmdgen_split.h,
+                                      HALF_LOW_TAU); replayed graphs included.  A non-zero delta over a call: repeat it on the three-piece
+                                      bf16 split ("half_engine" = 0) */
 } cmdgen_counters;
 
 /* Per-kernel timing of one profiled evaluation (hipEvent pairs on the launch stream). */
