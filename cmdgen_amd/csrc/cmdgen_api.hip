@@ -510,6 +510,7 @@ static int set_layout_impl(cmdgen_handle* h, int64_t batch, const int64_t* nph, 
         memcmp(h->cur_nphar.data(), nph, batch * sizeof(int64_t)) == 0 &&
         memcmp(h->cur_npocket.data(), npk, batch * sizeof(int64_t)) == 0)
         return CMDGEN_OK;
+    ++h->eval_gen;
     hipSetDevice(h->device);
     const Dims& d = h->dims;
     const int B = (int)batch;
@@ -786,6 +787,7 @@ extern "C" int cmdgen_dynamics_forward(cmdgen_handle* h, const float* xh_phar, c
     hipStream_t s = (hipStream_t)stream;
     rc = begin_work(h, s); if (rc) return rc;
     EvalLaunch a = make_launch(h);
+    ++h->eval_gen;
     cmdgen_launch_eval(a, xh_phar, xh_pocket, t, nullptr, nullptr, eps_phar, eps_pocket, s, nullptr);
     if (!h->dims.joint) cmdgen_launch_nan_fix(a, eps_phar, s);     // joint: k_vel_com applied the reset already
     HIPCHK(h, hipGetLastError());
@@ -800,6 +802,7 @@ extern "C" int cmdgen_debug_eval_prefix(cmdgen_handle* h, const float* xh_phar, 
     hipStream_t s = (hipStream_t)stream;
     rc = begin_work(h, s); if (rc) return rc;
     EvalLaunch a = make_launch(h);
+    ++h->eval_gen;
     a.stop_block = block; a.stop_stage = stage;
     cmdgen_launch_eval(a, xh_phar, xh_pocket, t, nullptr, nullptr, h->work.eps_tmp, nullptr, s, nullptr);
     h->agg_dirty = true;                               // stage 1 leaves the segment sums in agg
@@ -1010,6 +1013,7 @@ extern "C" int cmdgen_sample_chain(cmdgen_handle* h, const float* pocket_x, cons
     HIPCHK(h, hipMemsetAsync(h->d_cog, 0, 4 * sizeof(unsigned int), s));
     HIPCHK(h, hipStreamSynchronize(s));              // st0 is on the stack
     EvalLaunch a = make_launch(h);
+    ++h->eval_gen;
     if (h->kernel_profiling && !use_graph) a.prof_events = h->prof_events;
     cmdgen_launch_chain_init(h->lay, d, c, pocket_x, pocket_onehot, s);
     // One denoising step = the posterior update fused with pass 1 of the next radius graph (k_step_count), then the
@@ -1246,6 +1250,7 @@ extern "C" int cmdgen_joint_chain(cmdgen_handle* h, const float* phar_x, const f
     HIPCHK(h, hipMemsetAsync(h->joint_cog, 0, 4 * sizeof(unsigned int), s));
     HIPCHK(h, hipStreamSynchronize(s));
     EvalLaunch a = make_launch(h);
+    ++h->eval_gen;
     if (h->kernel_profiling && !use_graph) a.prof_events = h->prof_events;
     cmdgen_launch_joint_init(h->lay, d, c, phar_x, phar_onehot, pocket_x, pocket_onehot, s);
     auto one_step = [&](hipStream_t ss) {
@@ -1344,6 +1349,7 @@ extern "C" int cmdgen_profile_evaluation(cmdgen_handle* h, const float* xh_phar,
     std::vector<hipEvent_t> ev(nev);
     for (auto& e : ev) HIPCHK(h, hipEventCreate(&e));
     EvalLaunch a = make_launch(h);
+    ++h->eval_gen;
     cmdgen_launch_eval(a, xh_phar, xh_pocket, t, nullptr, nullptr, eps_phar, nullptr, s, ev.data());
     cmdgen_launch_nan_fix(a, eps_phar, s);
     HIPCHK(h, hipStreamSynchronize(s));
@@ -1411,6 +1417,8 @@ extern "C" int cmdgen_query(cmdgen_handle* h, const char* key, int64_t* value) {
     else if (k == "node16w") *value = a.node16w;
     else if (k == "edge_fullk") *value = a.edge_fullk;
     else if (k == "dead_skip") *value = a.dead_skip;
+    else if (k == "eval_gen") *value = h->eval_gen;
+    else if (k == "train_half_ran") *value = h->train_fwd_half;
     else if (k == "train_edges") *value = h->train_E;
     else if (k == "train_coord_edges") *value = h->train_Ec;
     else return fail(h, CMDGEN_EINVAL, "unknown query '%s'", key);
@@ -1434,6 +1442,7 @@ extern "C" int cmdgen_time_evaluation(cmdgen_handle* h, const float* xh_phar, co
     }
     rc = begin_work(h, s); if (rc) return rc;
     EvalLaunch a = make_launch(h);
+    ++h->eval_gen;
     hipGraph_t g = nullptr; hipGraphExec_t ge = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     // every exit below releases what it holds: a failure between Begin- and EndCapture must still end the capture (the
@@ -1474,6 +1483,7 @@ extern "C" int cmdgen_time_edge_kernel(cmdgen_handle* h, int32_t layer, int32_t 
     hipEvent_t e0, e1;
     HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1));
     EvalLaunch a = make_launch(h);
+    ++h->eval_gen;
     a.ablate = (layer >> 8) & 0xff;                                 // bits 8.. of `layer`: phase-ablation mask (timing only)
     layer &= 0xff;
     cmdgen_launch_edge_msg_only(a, layer, s);                       // warm

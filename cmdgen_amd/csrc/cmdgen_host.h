@@ -81,6 +81,10 @@ struct cmdgen_handle {
     TrainState* train = nullptr;           // training workspace (cmdgen_train.hip)
     float* h_norm = nullptr; hipEvent_t norm_ev = nullptr; bool norm_pending = false;   // deferred gradient-norm readback (pinned host float)
     int train_E = 0, train_Ec = 0;         // message / coordinate edges of the last cmdgen_train_forward (cmdgen_query)
+    int64_t eval_gen = 0;                  // bumped by every call that rewrites the evaluation workspace (edge lists, flags) or the layout:
+                                           // cmdgen_train_backward_inputs refuses activations whose graph is no longer the handle's
+    int64_t train_gen = -1;                // eval_gen of the last cmdgen_train_forward
+    int train_fwd_half = 0;                // the last cmdgen_train_forward's tile kernels ran on the half engine (cmdgen_query "train_half_ran")
     bool train_bf16 = false;               // GEMM operand precision of the training step (cmdgen_train_set_precision)
     bool agg_dirty = false;                // cmdgen_debug_eval_prefix left segment sums in work.agg
     hipStream_t last_stream = nullptr;     // stream most recently handed to this handle (ordering contract of cmdgen_set_layout)

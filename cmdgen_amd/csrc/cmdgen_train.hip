@@ -41,11 +41,16 @@ void tr_coord_out_bwd(int E, const int* row, const int* col, const float4* X, co
                       float nc, const float* dacc, float dacc_div, int n_moving, float* dphi, float4* dcd, hipStream_t s, const float* adiv = nullptr);
 void tr_edge_tail_bwd(int E, int H, const int* row, const int* col, const float* g, const float* d0, const float* Wcol, int ldw,
                       const float4* X, float nc, const float4* dcd, int n_moving, float* dP, float* dQ, float* dWcol, float* dX,
-                      float* scratch, hipStream_t s);
+                      float* scratch, hipStream_t s, const float* Wd = nullptr, float* dd0 = nullptr);
 size_t tr_edge_tail_scratch_floats(size_t E, size_t H);
 void cmdgen_dgrad_tail(int E, const float* dY, const void* Wt, const float* pre1, const int* row, const int* col, const float* d0,
                        const float* Wcol, int ldw, const float4* X, float nc, const float4* dcd, int n_moving, float* dP, float* dQ,
-                       float* dWcol, float* dX, float* scratch, int pieces, hipStream_t s, bool defer_reduce = false);
+                       float* dWcol, float* dX, float* scratch, int pieces, hipStream_t s, bool defer_reduce = false,
+                       const float* Wd = nullptr, float* dd0 = nullptr);
+void tr_d0_adjoint(int E, const int* row, const int* col, const float4* X0, const float* dd0, float* dX, hipStream_t s);
+void tr_zero_if_flag(float* v, size_t n, const int* flag, hipStream_t s);
+void tr_input_x(int Nl, int N, int ldp, int ldq, const float* dX, const float* dvel0, const int* nan_flag, float* dxp, float* dxq, hipStream_t s);
+void tr_dt(const Layout& lay, const float* dhdyn, int dyn, float* dt, hipStream_t s);
 size_t tr_partial_scratch_floats(size_t E, size_t H);
 void tr_gate_bwd(int E, int H, const int* row, const float* pre2, const float* wa, const float* z, int attention, const float* dagg,
                  float* dpre2, float* scratch, float* d_wa, float* d_ba, float* zero, size_t zero_floats, hipStream_t s,
@@ -171,11 +176,16 @@ struct TrainState {
     float *emb_wT = nullptr, *embo_wT = nullptr;
     void *frag_tab = nullptr, *misc_tab = nullptr, *split_tab = nullptr, *half_tab = nullptr, *half16_tab = nullptr;
     int n_frag = 0, n_misc = 0, max_frag4 = 0, max_misc = 0, n_split = 0, n_half = 0, n_half_fwd = 0, n_half16 = 0, max_half16 = 0;
+    // input gradients (cmdgen_train_backward_inputs only; allocated by its first call): dL/dvel after the projection's adjoint, the per-edge
+    // d0 adjoints of the message and the coordinate list, and a flat gradient for callers that want no weight gradients
+    std::vector<void*> inp_allocs;
+    float *dvel0 = nullptr, *dd0_e = nullptr, *dd0_c = nullptr, *grad_tmp = nullptr;
+    size_t inp_ecap = 0, inp_eccap = 0;
 };
 
 void cmdgen_train_free(TrainState* t) {
     if (!t) return;
-    free_pool(t->node_allocs); free_pool(t->edge_allocs); free_pool(t->pack_allocs);
+    free_pool(t->node_allocs); free_pool(t->edge_allocs); free_pool(t->pack_allocs); free_pool(t->inp_allocs);
     for (hipEvent_t e : t->evs) hipEventDestroy(e);
     for (hipEvent_t e : t->evs2) hipEventDestroy(e);
     if (t->h_tot) hipHostFree(t->h_tot);
@@ -445,6 +455,7 @@ extern "C" int cmdgen_train_forward(cmdgen_handle* h, const float* theta, const 
     // radius graph (same compact lists as the sampler), then the edge counts come to the host: grids and the
     // activation store are sized from them
     EvalLaunch a = make_launch(h);
+    ++h->eval_gen;                                                          // the graph pass below rewrites the evaluation workspace
     a.dead_skip = 0; a.w.need_qc = nullptr; a.w.ehop = nullptr; a.w.hop_levels = 1;       // the training forward skips nothing: no hop levels in its graph pass
     cmdgen_launch_edges(a, xh_phar, xh_pocket, s);
     // the list lengths come to the host through pinned memory and an event of their own: the re-packs below depend on the parameters only
@@ -547,6 +558,8 @@ extern "C" int cmdgen_train_forward(cmdgen_handle* h, const float* theta, const 
     // actually ran: a generic (fragment-reading) tile launch here would have multiplied with the weights of an earlier step - refuse the step
     // instead of training on them (the conditions above and in launch_msg_fullk / launch_coord_fullk / cmdgen_launch_node16w must agree).
     t->fwd_on_half = fwd_half;
+    h->train_fwd_half = fwd_half ? 1 : 0;
+    h->train_gen = h->eval_gen;
     if (frag_partial && a.frag_launches > 0) {
         t->have_forward = false;
         return fail(h, CMDGEN_ESTATE, "internal: %d tile launches of the training forward read fp32 weight fragments this step did not re-pack (set option train_half=0)", a.frag_launches);
@@ -561,8 +574,9 @@ extern "C" int cmdgen_train_forward(cmdgen_handle* h, const float* theta, const 
 // (stage k is block L-k), L+1 = embedding and encoders.  The gradient regions of the flat buffer therefore complete
 // from the back: after stage k every tensor of blocks >= L-k is final, so the caller can start the all-reduce of that
 // (contiguous) tail while the earlier blocks are still being differentiated.
+struct InputGrads { float* d_xh_phar; float* d_xh_pocket; float* d_t; };
 static int train_backward_stages(cmdgen_handle* h, const float* d_eps_phar, const float* d_eps_pocket, float* grad,
-                                 int first_stage, int last_stage, cmdgen_stream stream);
+                                 int first_stage, int last_stage, cmdgen_stream stream, const InputGrads* ig = nullptr);
 
 extern "C" int cmdgen_train_backward(cmdgen_handle* h, const float* d_eps_phar, const float* d_eps_pocket, float* grad,
                                      cmdgen_stream stream) {
@@ -578,8 +592,52 @@ extern "C" int cmdgen_train_backward_stages(cmdgen_handle* h, const float* d_eps
     return train_backward_stages(h, d_eps_phar, d_eps_pocket, grad, first_stage, last_stage, stream);
 }
 
+// The backward pass of the last cmdgen_train_forward to its INPUTS as well: the same pass as cmdgen_train_backward (same kernels, same
+// parameter gradient) with the input-gradient forms of the two edge tails (k_edge_tail_bwd<true>, k_dgrad_tail<., true>: position gradients
+// of every row, d0 adjoints per edge) and a few launches after the last stage (d0 geometry, the direct term of vel = x_final - x, the
+// encoders' first layers, the time column).  grad null: the parameter gradient goes to a buffer of the handle and is dropped.
+extern "C" int cmdgen_train_backward_inputs(cmdgen_handle* h, const float* d_eps_phar, const float* d_eps_pocket, float* grad,
+                                            float* d_xh_phar, float* d_xh_pocket, float* d_t, cmdgen_stream stream) {
+    if (!h) return CMDGEN_EINVAL;
+    if (!h->train || !h->train->have_forward) return fail(h, CMDGEN_ESTATE, "cmdgen_train_backward_inputs needs a preceding cmdgen_train_forward");
+    if (h->train_gen != h->eval_gen)
+        return fail(h, CMDGEN_ESTATE, "cmdgen_train_backward_inputs: an evaluation or a new layout replaced the graph of the last cmdgen_train_forward "
+                                      "(run the forward again)");
+    if (!d_eps_phar) return fail(h, CMDGEN_EINVAL, "null device pointer");
+    if (d_t && !h->dims.condition_time) return fail(h, CMDGEN_EINVAL, "d_t: this model has condition_time False (t is not an input)");
+    hipSetDevice(h->device);
+    TrainState* t = h->train;
+    const size_t N = h->cap_N;
+    if (!t->dvel0 || t->inp_ecap != t->ecap || t->inp_eccap != t->eccap) {     // sized as the edge store (ensure_edges) and the node capacity
+        hipDeviceSynchronize();
+        free_pool(t->inp_allocs);
+        t->dvel0 = t->dd0_e = t->dd0_c = t->grad_tmp = nullptr;
+        void* p; int rc;
+        if ((rc = dev_alloc(h, t->inp_allocs, &p, N * 4 * sizeof(float), false))) return rc;
+        t->dvel0 = (float*)p;
+        if ((rc = dev_alloc(h, t->inp_allocs, &p, t->ecap * sizeof(float), false))) return rc;
+        t->dd0_e = (float*)p;
+        if ((rc = dev_alloc(h, t->inp_allocs, &p, t->eccap * sizeof(float), false))) return rc;
+        t->dd0_c = (float*)p;
+        t->inp_ecap = t->ecap; t->inp_eccap = t->eccap;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (!grad) {
+        if (!t->grad_tmp) {
+            void* p; int rc = dev_alloc(h, t->inp_allocs, &p, t->tab.total * sizeof(float), false); if (rc) return rc;
+            t->grad_tmp = (float*)p;
+        }
+        grad = t->grad_tmp;
+        HIPCHK(h, hipMemsetAsync(grad, 0, t->tab.total * sizeof(float), s));
+    }
+    HIPCHK(h, hipMemsetAsync(t->dd0_e, 0, (size_t)std::max(t->E, 1) * sizeof(float), s));
+    HIPCHK(h, hipMemsetAsync(t->dd0_c, 0, (size_t)std::max(t->Ec, 1) * sizeof(float), s));
+    const InputGrads ig{d_xh_phar, d_xh_pocket, d_t};
+    return train_backward_stages(h, d_eps_phar, d_eps_pocket, grad, 0, h->dims.L + 1, stream, &ig);
+}
+
 static int train_backward_stages(cmdgen_handle* h, const float* d_eps_phar, const float* d_eps_pocket, float* grad,
-                                 int first_stage, int last_stage, cmdgen_stream stream) {
+                                 int first_stage, int last_stage, cmdgen_stream stream, const InputGrads* ig) {
     if (!h || !h->train || !h->train->have_forward) return fail(h, CMDGEN_ESTATE, "cmdgen_train_backward needs a preceding cmdgen_train_forward");
     if (!d_eps_phar || !grad) return fail(h, CMDGEN_EINVAL, "null device pointer");
     hipSetDevice(h->device);
@@ -695,7 +753,14 @@ static int train_backward_stages(cmdgen_handle* h, const float* d_eps_phar, cons
     small_wgrad(tb.embo, H, N, t->dhfin, d.dyn, t->h + (size_t)L * d.S * NH, H);
     linear_dgrad(theta, tb.embo, 0, H, N, t->dhfin, d.dyn, dh0, H, false, s);
     flush_side();           // (none of what these read is written again in this pass)
+    if (ig) {
+        tr_zero_if_flag(t->dX, (size_t)N * 4, (const int*)w.nan_flag, s);      // a NaN reset: vel is a constant (zero) of the inputs
+        HIPCHK(h, hipMemcpyAsync(t->dvel0, t->dX, (size_t)N * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));    // dL/dvel: the direct term
     }
+    }
+    // input gradients: every row's position gradient is accumulated (pocket rows that do not move still enter every radial and coord_diff)
+    const int n_rows_dx = ig ? N : Nm;
+    float* dd0_e = ig ? t->dd0_e : nullptr; float* dd0_c = ig ? t->dd0_c : nullptr;
     const int S = d.S, U = L * S;
     const float* rowdiv = d.agg_mean ? w.adiv : nullptr;              // aggregation 'mean': sums were divided by the receiver's edge count (egnn_new.py:288-292)
     for (int l = L - 1; l >= 0; --l) {
@@ -741,14 +806,15 @@ static int train_backward_stages(cmdgen_handle* h, const float* d_eps_phar, cons
         edge_wgrad(bc.c2, actB, (t->wsilu & 2) ? pre6 : t->act6 + (size_t)l * t->eccap * H, Ec, (t->wsilu & 2) ? 1 : 0);      // weight and bias gradient of coord_mlp.2 (c1 = SiLU(pre6))
         if (tail_fused)     // dpre6 = (dpre7 W7) SiLU'(pre6) and everything done with it, in one kernel: it never reaches HBM
             cmdgen_dgrad_tail(Ec, actB, pkc.t_c2, pre6, w.crow, w.ccol, w.cd0, pair ? pkc.rd_c : theta + bc.c0.w + 2 * H /* radial column: the forward's contiguous copy */, pair ? 1 : ld1, Xl,
-                              d.norm_constant, t->dcd, Nm, dPc, dQc, grad + bc.c0.w + 2 * H, t->dX, tail_c, pcs, s, pair);
+                              d.norm_constant, t->dcd, n_rows_dx, dPc, dQc, grad + bc.c0.w + 2 * H, t->dX, tail_c, pcs, s, pair,
+                              pair ? pkc.rd_c + H : theta + bc.c0.w + 2 * H + 1 /* d0 column */, dd0_c);
         if (pair) { float* gw = grad + bc.c4.w; float* gc = grad + bc.c0.w + 2 * H; defer([=](hipStream_t q) { tr_reduce_pair(Ec, H, part_c, gw, nullptr, tail_c, gc, ld1, q); }); }
         else {
             if (sp) cmdgen_dgrad_split(Ec, actB, pkc.t_c2, nullptr, nullptr, t->actA, false, 1.0f, pre6, s, pcs);
             else linear_dgrad(theta, bc.c2, 0, H, Ec, actB, H, t->actA, H, false, s, pre6);  // actA <- dc1 * SiLU'(pre6) = dpre6
             // adjoints of the gathers, the radial / d0 column gradients, d radial and the geometry adjoint: one pass over dpre6
-            tr_edge_tail_bwd(Ec, H, w.crow, w.ccol, t->actA, w.cd0, theta + bc.c0.w + 2 * H, ld1, Xl, d.norm_constant, t->dcd, Nm,
-                             dPc, dQc, grad + bc.c0.w + 2 * H, t->dX, t->tail_scratch, s);
+            tr_edge_tail_bwd(Ec, H, w.crow, w.ccol, t->actA, w.cd0, theta + bc.c0.w + 2 * H, ld1, Xl, d.norm_constant, t->dcd, n_rows_dx,
+                             dPc, dQc, grad + bc.c0.w + 2 * H, t->dX, t->tail_scratch, s, theta + bc.c0.w + 2 * H + 1, dd0_c);
         }
         if (sp) cmdgen_dgrad_split(N, dPc, pkc.t_c0a, dQc, pkc.t_c0b, dh_in, true, 1.0f, nullptr, s, pcs);
         else {
@@ -780,8 +846,8 @@ static int train_backward_stages(cmdgen_handle* h, const float* d_eps_phar, cons
                     d.attention ? grad + b.att.w : nullptr, d.attention ? grad + b.att.b : nullptr, dPe, pq_floats, s, pair);
         edge_wgrad(b.e2, actA, (t->wsilu & 1) ? pre1 : t->act1 + (size_t)u * t->ecap * H, E, (t->wsilu & 1) ? 1 : 0);            // weight and bias gradient of edge_mlp.2 (m1 = SiLU(pre1))
         if (tail_fused)
-            cmdgen_dgrad_tail(E, actA, pk.t_e2, pre1, w.erow, w.ecol, w.ed0, pair ? pk.rd_e : theta + b.e0.w + 2 * H, pair ? 1 : ld1, Xl, d.norm_constant, nullptr, Nm,
-                              dPe, dQe, grad + b.e0.w + 2 * H, t->dX, tail_e, pcs, s, pair);
+            cmdgen_dgrad_tail(E, actA, pk.t_e2, pre1, w.erow, w.ecol, w.ed0, pair ? pk.rd_e : theta + b.e0.w + 2 * H, pair ? 1 : ld1, Xl, d.norm_constant, nullptr, n_rows_dx,
+                              dPe, dQe, grad + b.e0.w + 2 * H, t->dX, tail_e, pcs, s, pair, pair ? pk.rd_e + H : theta + b.e0.w + 2 * H + 1, dd0_e);
         if (pair) {
             float* gaw = d.attention ? grad + b.att.w : nullptr; float* gab = d.attention ? grad + b.att.b : nullptr; float* ge = grad + b.e0.w + 2 * H;
             defer([=](hipStream_t q) { tr_reduce_pair(E, H, part_e, gaw, gab, tail_e, ge, ld1, q); });
@@ -789,8 +855,8 @@ static int train_backward_stages(cmdgen_handle* h, const float* d_eps_phar, cons
         else {
             if (sp) cmdgen_dgrad_split(E, actA, pk.t_e2, nullptr, nullptr, t->actB, false, 1.0f, pre1, s, pcs);
             else linear_dgrad(theta, b.e2, 0, H, E, actA, H, t->actB, H, false, s, pre1);   // actB <- dm1 * SiLU'(pre1) = dpre1
-            tr_edge_tail_bwd(E, H, w.erow, w.ecol, t->actB, w.ed0, theta + b.e0.w + 2 * H, ld1, Xl, d.norm_constant, nullptr, Nm,
-                             dPe, dQe, grad + b.e0.w + 2 * H, t->dX, t->tail_scratch, s);
+            tr_edge_tail_bwd(E, H, w.erow, w.ecol, t->actB, w.ed0, theta + b.e0.w + 2 * H, ld1, Xl, d.norm_constant, nullptr, n_rows_dx,
+                             dPe, dQe, grad + b.e0.w + 2 * H, t->dX, t->tail_scratch, s, theta + b.e0.w + 2 * H + 1, dd0_e);
         }
         // node_mlp.0 (both halves) and edge_mlp.0 (both halves): the second grouped launch of the GCL
         defer_wgrad(b.n0, 0, H, dn, hl, true);
@@ -826,6 +892,14 @@ static int train_backward_stages(cmdgen_handle* h, const float* d_eps_phar, cons
     linear_dgrad(theta, tb.re2, 0, 2 * R, Np, dq, d.dyn, t->denca_p, 2 * R, false, s);
     tr_silu_bwd(t->denca_p, t->enc1_p, (size_t)Np * 2 * R, s);
     small_wgrad(tb.re0, R, Np, t->denca_p, 2 * R, t->xh_pocket + 3, ldq);
+    if (ig) {       // the input gradients, on the main stream behind the data-gradient chain
+        if (ig->d_xh_phar && Nl) linear_dgrad(theta, tb.pe0, 0, P, Nl, t->denca_l, 2 * P, ig->d_xh_phar + 3, ldp, false, s);
+        if (ig->d_xh_pocket && Np) linear_dgrad(theta, tb.re0, 0, R, Np, t->denca_p, 2 * R, ig->d_xh_pocket + 3, ldq, false, s);
+        if (ig->d_t) tr_dt(h->lay, t->dhdyn, d.dyn, ig->d_t, s);
+        tr_d0_adjoint(E, w.erow, w.ecol, t->X, t->dd0_e, t->dX, s);
+        tr_d0_adjoint(Ec, w.crow, w.ccol, t->X, t->dd0_c, t->dX, s);
+        tr_input_x(Nl, N, ldp, ldq, t->dX, t->dvel0, (const int*)w.nan_flag, ig->d_xh_phar, ig->d_xh_pocket, s);
+    }
     flush_side();
     ss3.join();
     ss.join();

@@ -1215,15 +1215,19 @@ __global__ void k_coord_out_bwd(int E, const int* __restrict__ row, const int* _
 //   once per run), dQ[col] += g (atomics), dW[:, 2H] += sum_e r_e g_e and dW[:, 2H+1] += sum_e d0_e g_e (the radial /
 //   d0 columns of the Linear, strided by ldw), dr_e = g_e . w_r, and the geometry adjoint of k_geom_bwd for that dr_e
 //   (plus dcd_e for the coordinate list) into dX.  A wave takes TAIL_EPW consecutive edges (a workgroup 4 x that).
+//   INP (input gradients, cmdgen_train_backward_inputs only): also dd0[e] += g_e . w_d, the adjoint of the edge's d0 feature (its geometry
+//   adjoint into the input positions runs once after the last block: k_d0_adjoint); the caller passes n_moving = N there.
 // ------------------------------------------------------------------------------------
 #define TAIL_EPW 8              // edges per wave: short serial runs, thousands of waves in flight
+template <bool INP = false>
 __global__ __launch_bounds__(256) void k_edge_tail_bwd(int E, int H, const int* __restrict__ row, const int* __restrict__ col,
                                                        const float* __restrict__ g, const float* __restrict__ d0,
                                                        const float* __restrict__ Wcol /* W + 2H, stride ldw */, int ldw,
                                                        const float4* __restrict__ X, float norm_constant,
                                                        const float4* __restrict__ dcd, int n_moving,
                                                        float* __restrict__ dP, float* __restrict__ dQ,
-                                                       float* __restrict__ scratch /* [workgroups][2][H] */, float* __restrict__ dX) {
+                                                       float* __restrict__ scratch /* [workgroups][2][H] */, float* __restrict__ dX,
+                                                       const float* __restrict__ Wd /* d0 column, stride ldw */, float* __restrict__ dd0) {
     __shared__ float red[2][4][256];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // a lane owns columns lane, lane + 64, lane + 128, lane + 192: every load / atomic of the wave is one contiguous
@@ -1231,11 +1235,12 @@ __global__ __launch_bounds__(256) void k_edge_tail_bwd(int E, int H, const int* 
     const int NC = (H + 63) / 64;
     const int e0 = blockIdx.x * (4 * TAIL_EPW) + wave * TAIL_EPW, e1 = min(E, e0 + TAIL_EPW);
     const int ne = max(e1 - e0, 0);
-    float wr[4], accR[4], accD[4], run[4];
+    float wr[4], wd[4], accR[4], accD[4], run[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int c = lane + 64 * q;
         wr[q] = (q < NC && c < H) ? Wcol[(size_t)c * ldw] : 0.f;
+        wd[q] = (INP && q < NC && c < H) ? Wd[(size_t)c * ldw] : 0.f;
         accR[q] = accD[q] = run[q] = 0.f;
     }
     // lane l < ne owns edge e0 + l for the per-edge scalars: indices, geometry, and later the geometry adjoint
@@ -1246,7 +1251,7 @@ __global__ __launch_bounds__(256) void k_edge_tail_bwd(int E, int H, const int* 
         dxl = a.x - b.x; dyl = a.y - b.y; dzl = a.z - b.z;
         my_r = dxl * dxl + dyl * dyl + dzl * dzl;
     }
-    float my_gr = 0.f;
+    float my_gr = 0.f, my_gd = 0.f;
     int cur = __shfl(my_i, 0);
 #pragma unroll
     for (int k = 0; k < TAIL_EPW; ++k) {
@@ -1262,17 +1267,20 @@ __global__ __launch_bounds__(256) void k_edge_tail_bwd(int E, int H, const int* 
                 for (int q = 0; q < 4; ++q) { const int c = lane + 64 * q; if (c < H) atomicAdd(dP + (size_t)cur * H + c, run[q]); run[q] = 0.f; }
                 cur = i;
             }
-            float dot = 0.f;
+            float dot = 0.f, dotd = 0.f;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int c = lane + 64 * q;
                 accR[q] += r * v[q]; accD[q] += dd * v[q]; run[q] += v[q]; dot += v[q] * wr[q];
+                if (INP) dotd += v[q] * wd[q];
                 if (c < H) atomicAdd(dQ + (size_t)j * H + c, v[q]);
             }
             const float gr = wave_sum(dot);                  // dL/d radial of this edge
             if (lane == k) my_gr = gr;
+            if (INP) { const float gd = wave_sum(dotd); if (lane == k) my_gd = gd; }      // dL/d d0 of this edge
         }
     }
+    if (INP && lane < ne) dd0[e0 + lane] += my_gd;        // one lane per edge: every block's list launch adds in stream order
     if (ne > 0) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) { const int c = lane + 64 * q; if (c < H) atomicAdd(dP + (size_t)cur * H + c, run[q]); }
@@ -1319,8 +1327,9 @@ struct TailArgs {
     const float4* X; float norm_constant; const float4* dcd; int n_moving;
     float* dP; float* dQ; float* scratch; float* dX;
     unsigned long long* dbg;      // diagnostic build (-DCMDGEN_TAIL_STAMPS=1): per-phase cycle sums [wave][8], [32 + wave] lifetimes, [40] workgroups; else unused
+    const float* Wd; float* dd0;  // INP only: the d0 column (stride ldw) and the per-edge d0 adjoint it adds into (as k_edge_tail_bwd<true>)
 };
-template <int NPC>
+template <int NPC, bool INP = false>
 __global__ __launch_bounds__(256, 3) void k_dgrad_tail(int M, const float* __restrict__ A0, const void* __restrict__ W0,
                                                        const float* __restrict__ pre, TailArgs ta) {
     constexpr int MT = 32, HH = 256, PLDA = SPLIT_PLANE_LDA(HH / 2), PE = MT * PLDA;
@@ -1341,9 +1350,13 @@ __global__ __launch_bounds__(256, 3) void k_dgrad_tail(int M, const float* __res
     // their difference stood in every tile's critical path; profiles/r05_ah_tail_stamps.txt)
     int my_i = -1, my_j = -1; float my_r = 0.f, my_d0 = 0.f, dxl = 0.f, dyl = 0.f, dzl = 0.f;
     if (lane < ne) { my_i = ta.row[e0 + lane]; my_j = ta.col[e0 + lane]; my_d0 = ta.d0[e0 + lane]; }
-    float wr[4];
+    float wr[4], wd[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int q = 0; q < 4; ++q) wr[q] = ta.Wcol[(size_t)(lane + 64 * q) * ta.ldw];
+    if (INP) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) wd[q] = ta.Wd[(size_t)(lane + 64 * q) * ta.ldw];
+    }
     sf32x16 acc[1][2];
     TSTAMP(0);
     dgrad_tile_gemm<MT, NPC>(reinterpret_cast<unsigned short*>(smem), M, row0, A0, W0, nullptr, nullptr, acc);
@@ -1376,7 +1389,7 @@ __global__ __launch_bounds__(256, 3) void k_dgrad_tail(int M, const float* __res
     }
     TSTAMP(3);
     float accR[4] = {0.f, 0.f, 0.f, 0.f}, accD[4] = {0.f, 0.f, 0.f, 0.f}, run[4] = {0.f, 0.f, 0.f, 0.f};
-    float my_gr = 0.f;
+    float my_gr = 0.f, my_gd = 0.f;
     int cur = __shfl(my_i, 0);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -1391,18 +1404,21 @@ __global__ __launch_bounds__(256, 3) void k_dgrad_tail(int M, const float* __res
                 for (int q = 0; q < 4; ++q) { atomicAdd(ta.dP + (size_t)cur * HH + lane + 64 * q, run[q]); run[q] = 0.f; }
                 cur = i;
             }
-            float dot = 0.f;
+            float dot = 0.f, dotd = 0.f;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 accR[q] += r * v[q]; accD[q] += dd * v[q]; run[q] += v[q]; dot += v[q] * wr[q];
+                if (INP) dotd += v[q] * wd[q];
 #if CMDGEN_TAIL_EXP != 1
                 atomicAdd(ta.dQ + (size_t)j * HH + lane + 64 * q, v[q]);
 #endif
             }
             const float gr = wave_sum(dot);                  // dL/d radial of this edge
             if (lane == k) my_gr = gr;
+            if (INP) { const float gd = wave_sum(dotd); if (lane == k) my_gd = gd; }      // dL/d d0 of this edge
         }
     }
+    if (INP && lane < ne) ta.dd0[e0 + lane] += my_gd;
     TSTAMP(4);
     if (ne > 0) {
 #pragma unroll
@@ -1529,6 +1545,52 @@ __global__ void k_eps_bwd(int n_rows, int F, int row0, const float* __restrict__
     if (i >= n_rows * (3 + F)) return;
     const int n = i / (3 + F), k = i - n * (3 + F);
     if (k < 3) dvel[(size_t)(row0 + n) * 4 + k] = deps[i]; else ddec[(size_t)n * F + k - 3] = deps[i];
+}
+
+// ------------------------------------------------------------------------------------
+// input gradients (cmdgen_train_backward_inputs): what the parameter pass does not form
+// ------------------------------------------------------------------------------------
+// geometry adjoint of the d0 edge feature, d0 = |x_i - x_j|^2 of the INPUT positions X0 (egnn_new.py:194): dX[i] += 2 (x_i - x_j) dd0,
+// dX[j] -= the same.  One thread per edge of a list (the message list and the coordinate list are launched one after the other).
+__global__ void k_d0_adjoint(int E, const int* __restrict__ row, const int* __restrict__ col, const float4* __restrict__ X0,
+                             const float* __restrict__ dd0, float* __restrict__ dX) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    const int i = row[e], j = col[e];
+    if (i == j) return;
+    const float4 a = X0[i], b = X0[j];
+    const float g = 2.0f * dd0[e];
+    const float gx = (a.x - b.x) * g, gy = (a.y - b.y) * g, gz = (a.z - b.z) * g;
+    float* p = dX + (size_t)i * 4; atomicAdd(p, gx); atomicAdd(p + 1, gy); atomicAdd(p + 2, gz);
+    float* q = dX + (size_t)j * 4; atomicAdd(q, -gx); atomicAdd(q + 1, -gy); atomicAdd(q + 2, -gz);
+}
+// the batch-global NaN guard reset vel to zeros (dynamics.py:129-131): no gradient flows through vel at all - neither the direct term nor
+// the network's path through x_final - so the input pass starts from dL/dvel = 0 (the parameter pass keeps its seed: the trainer's norm guard)
+__global__ void k_zero_if_flag(float* __restrict__ v, size_t n, const int* __restrict__ flag) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && *flag) v[i] = 0.f;
+}
+// position columns of the input gradients: dL/dx_in = dL/dx_0 (through the network, dX) - dL/dvel (the direct term of vel = x_final - x,
+// dvel0: after the projection's adjoint; zero where the batch-global NaN guard reset vel).  Rows < Nl -> d_xh_phar, the rest -> d_xh_pocket.
+__global__ void k_input_x(int Nl, int N, int ldp, int ldq, const float* __restrict__ dX, const float* __restrict__ dvel0,
+                          const int* __restrict__ nan_flag, float* __restrict__ dxp, float* __restrict__ dxq) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N * 3) return;
+    const int n = i / 3, k = i - n * 3;
+    const float direct = *nan_flag ? 0.f : dvel0[(size_t)n * 4 + k];
+    const float v = dX[(size_t)n * 4 + k] - direct;
+    if (n < Nl) { if (dxp) dxp[(size_t)n * ldp + k] = v; }
+    else if (dxq) dxq[(size_t)(n - Nl) * ldq + k] = v;
+}
+// d_t[b] = sum over the nodes of sample b of the time column of dL/d[enc_out | t] (condition_time: h_time = t[mask], dynamics.py:96-98).
+// One wave per sample, phar rows then pocket rows.
+__global__ __launch_bounds__(64) void k_dt(Layout lay, const float* __restrict__ dhdyn, int dyn, float* __restrict__ dt) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int nl = lay.num_phar[b], np = lay.num_pocket[b], pb = lay.phar_base[b], qb = lay.Nl + lay.pocket_base[b];
+    float sum = 0.f;
+    for (int i = lane; i < nl + np; i += 64) sum += dhdyn[(size_t)(i < nl ? pb + i : qb + i - nl) * dyn + dyn - 1];
+    sum = wave_sum(sum);
+    if (lane == 0) dt[b] = sum;
 }
 
 // ------------------------------------------------------------------------------------
@@ -2005,21 +2067,28 @@ void tr_coord_out_bwd(int E, const int* row, const int* col, const float4* X, co
 }
 void tr_edge_tail_bwd(int E, int H, const int* row, const int* col, const float* g, const float* d0, const float* Wcol, int ldw,
                       const float4* X, float nc, const float4* dcd, int n_moving, float* dP, float* dQ, float* dWcol, float* dX,
-                      float* scratch, hipStream_t s) {
+                      float* scratch, hipStream_t s, const float* Wd = nullptr, float* dd0 = nullptr) {
     if (!E) return;
     const int nwg = (E + 4 * TAIL_EPW - 1) / (4 * TAIL_EPW);
-    hipLaunchKernelGGL(k_edge_tail_bwd, dim3(nwg), dim3(256), 0, s, E, H, row, col, g, d0, Wcol, ldw, X, nc, dcd, n_moving, dP, dQ,
-                       scratch, dX);
+    if (dd0) hipLaunchKernelGGL(k_edge_tail_bwd<true>, dim3(nwg), dim3(256), 0, s, E, H, row, col, g, d0, Wcol, ldw, X, nc, dcd, n_moving,
+                                dP, dQ, scratch, dX, Wd, dd0);
+    else hipLaunchKernelGGL(k_edge_tail_bwd<false>, dim3(nwg), dim3(256), 0, s, E, H, row, col, g, d0, Wcol, ldw, X, nc, dcd, n_moving,
+                            dP, dQ, scratch, dX, (const float*)nullptr, (float*)nullptr);
     hipLaunchKernelGGL(k_tail_colsum_reduce, dim3((H + 63) / 64, 2, min(32, (nwg + 15) / 16)), dim3(256), 0, s, nwg, H, scratch, dWcol, ldw);
 }
 // fused: g = (dY W2^T-pack) * SiLU'(pre1) and its whole tail (H = 256; W = split pack of the transposed weight)
 void cmdgen_dgrad_tail(int E, const float* dY, const void* Wt, const float* pre1, const int* row, const int* col, const float* d0,
                        const float* Wcol, int ldw, const float4* X, float nc, const float4* dcd, int n_moving, float* dP, float* dQ,
-                       float* dWcol, float* dX, float* scratch, int pieces, hipStream_t s, bool defer_reduce = false) {
+                       float* dWcol, float* dX, float* scratch, int pieces, hipStream_t s, bool defer_reduce = false,
+                       const float* Wd = nullptr, float* dd0 = nullptr) {
     if (E <= 0) return;
     const int nwg = (E + 31) / 32;
-    const TailArgs ta{row, col, d0, Wcol, ldw, X, nc, dcd, n_moving, dP, dQ, scratch, dX, g_train_tune.dbg};
-    if (pieces == 3) hipLaunchKernelGGL((k_dgrad_tail<3>), dim3(nwg), dim3(256), 0, s, E, dY, Wt, pre1, ta);
+    const TailArgs ta{row, col, d0, Wcol, ldw, X, nc, dcd, n_moving, dP, dQ, scratch, dX, g_train_tune.dbg, Wd, dd0};
+    if (dd0) {
+        if (pieces == 3) hipLaunchKernelGGL((k_dgrad_tail<3, true>), dim3(nwg), dim3(256), 0, s, E, dY, Wt, pre1, ta);
+        else hipLaunchKernelGGL((k_dgrad_tail<1, true>), dim3(nwg), dim3(256), 0, s, E, dY, Wt, pre1, ta);
+    }
+    else if (pieces == 3) hipLaunchKernelGGL((k_dgrad_tail<3>), dim3(nwg), dim3(256), 0, s, E, dY, Wt, pre1, ta);
     else hipLaunchKernelGGL((k_dgrad_tail<1>), dim3(nwg), dim3(256), 0, s, E, dY, Wt, pre1, ta);
     if (!defer_reduce) hipLaunchKernelGGL(k_tail_colsum_reduce, dim3(4, 2, min(32, (nwg + 15) / 16)), dim3(256), 0, s, nwg, 256, scratch, dWcol, ldw);
 }
@@ -2049,6 +2118,18 @@ __global__ void k_bwd_init(int Nl, int N, int P, int dyn, const float* __restric
 void tr_bwd_init(int Nl, int N, int P, int dyn, const float* deps, float* dX, float* ddec, float* dhfin, hipStream_t s) {
     const size_t n = (size_t)N * (dyn > 4 ? dyn : 4) > (size_t)Nl * P ? (size_t)N * (dyn > 4 ? dyn : 4) : (size_t)Nl * P;
     if (n) hipLaunchKernelGGL(k_bwd_init, EW_GRID(n), 0, s, Nl, N, P, dyn, deps, dX, ddec, dhfin);
+}
+void tr_zero_if_flag(float* v, size_t n, const int* flag, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_zero_if_flag, EW_GRID(n), 0, s, v, n, flag);
+}
+void tr_d0_adjoint(int E, const int* row, const int* col, const float4* X0, const float* dd0, float* dX, hipStream_t s) {
+    if (E) hipLaunchKernelGGL(k_d0_adjoint, EW_GRID(E), 0, s, E, row, col, X0, dd0, dX);
+}
+void tr_input_x(int Nl, int N, int ldp, int ldq, const float* dX, const float* dvel0, const int* nan_flag, float* dxp, float* dxq, hipStream_t s) {
+    if (N) hipLaunchKernelGGL(k_input_x, EW_GRID((size_t)N * 3), 0, s, Nl, N, ldp, ldq, dX, dvel0, nan_flag, dxp, dxq);
+}
+void tr_dt(const Layout& lay, const float* dhdyn, int dyn, float* dt, hipStream_t s) {
+    if (lay.B) hipLaunchKernelGGL(k_dt, dim3(lay.B), dim3(64), 0, s, lay, dhdyn, dyn, dt);
 }
 void tr_adamw(size_t n, float* theta, const float* grad, float* m, float* v, float* vmax, float lr, float b1, float b2,
               float eps, float wd, float bias1, float bias2_sqrt, float clip, hipStream_t s, const float* sqnorm = nullptr,

@@ -13,7 +13,7 @@ import math
 import numpy as np
 import torch
 
-from .en_diffusion import EnVariationalDiffusion, fresh_seed
+from .en_diffusion import EnVariationalDiffusion, fresh_seed, no_grad_unless_differentiable
 from .. import utils
 
 
@@ -34,9 +34,10 @@ class ConditionalDDPM(EnVariationalDiffusion):
     def sample(self, *args):
         raise NotImplementedError('Conditional model does not support sampling without given pocket.')
 
-    # ---- loss terms (conditional_model.py:20-106, :158-320) as VALUES: the network evaluation runs in the HIP
-    # library and no autograd graph is built here.  Training uses training.HipTrainer: the activation-saving forward
-    # (``_net``) plus the library's own backward pass with the analytic gradient of these terms.
+    # ---- loss terms (conditional_model.py:20-106, :158-320): the network evaluation runs in the HIP library.  By default
+    # they are VALUES (no autograd graph): training.HipTrainer trains with the activation-saving forward (``_net``) plus the
+    # library's own backward pass and the analytic gradient of these terms.  With the dynamics in differentiable mode
+    # (EGNNDynamics.set_differentiable) and grad mode on they are built with autograd, as in the reference.
     def noised_representation(self, xh_phar, xh0_pocket, phar_mask, pocket_mask, gamma_t, eps=None):
         alpha_t, sigma_t = self.alpha(gamma_t, xh_phar), self.sigma(gamma_t, xh_phar)
         eps_phar = self.sample_gaussian((len(phar_mask), self.n_dims + self.phar_nf), phar_mask.device) \
@@ -72,9 +73,10 @@ class ConditionalDDPM(EnVariationalDiffusion):
     def log_pN(self, N_phar, N_pocket):
         return self.size_distribution.log_prob_n1_given_n2(N_phar, N_pocket)
 
-    @torch.no_grad()
+    @no_grad_unless_differentiable
     def forward(self, phar, pocket, return_info=False, t_int=None, eps=None, _net=None):
-        """The 12 loss terms (+ info) of conditional_model.py:198-320 as VALUES (no autograd graph).
+        """The 12 loss terms (+ info) of conditional_model.py:198-320 - VALUES (no autograd graph) unless the dynamics are in
+        differentiable mode and grad mode is on (then with autograd, as in the reference).
 
         t_int [B,1] and eps (list of the Gaussian draws, one per noised_representation call) may be
         supplied for reproducibility; otherwise they are drawn like the reference does.  ``_net`` replaces the
@@ -232,7 +234,7 @@ class SimpleConditionalDDPM(ConditionalDDPM):
             0, m, torch.ones(len(m), dtype=x.dtype, device=x.device)).clamp(min=1)
         return tot / cnt[:, None]
 
-    @torch.no_grad()
+    @no_grad_unless_differentiable
     def forward(self, phar, pocket, return_info=False, t_int=None, eps=None, _net=None):
         phar, pocket = dict(phar), dict(pocket)
         com = self._pocket_com(pocket)

@@ -51,6 +51,14 @@ class EGNNDynamics(nn.Module):
         self._handle = None
         self._weights_sig = None
         self._mask_cache = None
+        self.differentiable = False
+
+    def set_differentiable(self, on: bool = True):
+        """Opt in to autograd (default off): in grad mode forward() then returns tensors with a grad_fn, and backward gives the reference's
+        gradients to the weights and to xh_phars / xh_residues / t (cmdgen_amd.autograd; the radius graph is a constant, as in the
+        reference).  Off: forward() is the plain evaluation it always was (no grad_fn)."""
+        self.differentiable = bool(on)
+        return self
 
     # -- wiring from the diffusion module (schedule table and normalisation live in the same handle)
     def attach_diffusion(self, timesteps, gamma_table, norm_values, norm_biases, no_com_projection=False):
@@ -62,8 +70,9 @@ class EGNNDynamics(nn.Module):
     def _signature(self):
         return tuple((p.data_ptr(), p._version) for p in self.parameters())
 
-    def hip_handle(self) -> "hip_backend.Handle":
-        """The cmdgen handle for this module's device, with the current weights uploaded."""
+    def hip_handle(self, upload: bool = True) -> "hip_backend.Handle":
+        """The cmdgen handle for this module's device, with the current weights uploaded (upload False: uploaded once, not refreshed - the
+        differentiable path hands the library its parameters itself, and the next evaluation that needs the uploaded copy refreshes it)."""
         p0 = next(self.parameters())
         if p0.device.type != 'cuda':
             raise hip_backend.CmdgenError(
@@ -72,7 +81,7 @@ class EGNNDynamics(nn.Module):
         if self._handle is None or self._handle.device_index != idx:
             self._handle = hip_backend.Handle(self._cfg, idx)
             self._weights_sig = None
-        sig = self._signature()
+        sig = self._signature() if (upload or self._weights_sig is None) else self._weights_sig
         if sig != self._weights_sig:
             state = {'ddpm.dynamics.' + k: v for k, v in self.state_dict().items()}
             state['ddpm.gamma.gamma'] = self._gamma
@@ -89,10 +98,14 @@ class EGNNDynamics(nn.Module):
 
     def forward(self, xh_phars, xh_residues, t, mask_phars, mask_residues):
         """-> (eps_phar [Nl, 3+phar_nf], eps_pocket [Np, 3+residue_nf]); dynamics.py:75-139."""
-        h = self.hip_handle()
+        diff = self.differentiable and torch.is_grad_enabled()
+        h = self.hip_handle(upload=not diff)
         batch = int(t.numel()) if t.numel() > 1 else int(max(int(mask_phars.max()), int(mask_residues.max())) + 1)
         nph, npk = self._layout_from_masks(mask_phars, mask_residues, batch)
         h.set_layout(nph, npk)
+        if diff:
+            from ..autograd import dynamics_apply
+            return dynamics_apply(self, xh_phars, xh_residues, t)
         xp = xh_phars.detach().to(torch.float32).contiguous()
         xr = xh_residues.detach().to(torch.float32).contiguous()
         # one evaluation: the NaN guard's counter tells whether a reset happened (the reference syncs here too: `torch.any(torch.isnan(vel))`,

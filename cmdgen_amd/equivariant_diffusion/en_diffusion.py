@@ -9,6 +9,7 @@ and never sit on the per-step critical path.
 """
 from __future__ import annotations
 
+import functools
 import math
 from typing import Dict
 
@@ -19,6 +20,18 @@ from torch import nn
 
 from .. import utils
 from ..synthetic import gamma_table
+
+
+def no_grad_unless_differentiable(fn):
+    """torch.no_grad() around a loss entry point, unless its dynamics module is in differentiable mode (EGNNDynamics.set_differentiable)
+    and grad mode is on: then the loss is built with autograd, as the reference's forward is."""
+    @functools.wraps(fn)
+    def wrapper(self, *args, **kwargs):
+        if getattr(self.dynamics, 'differentiable', False) and torch.is_grad_enabled():
+            return fn(self, *args, **kwargs)
+        with torch.no_grad():
+            return fn(self, *args, **kwargs)
+    return wrapper
 
 
 class PredefinedNoiseSchedule(nn.Module):
@@ -363,10 +376,16 @@ class EnVariationalDiffusion(nn.Module):
     def log_pN(self, N_phar, N_pocket):
         return self.size_distribution.log_prob(N_phar, N_pocket)
 
-    @torch.no_grad()
+    def set_differentiable(self, on: bool = True):
+        """Opt in to autograd through the loss (EGNNDynamics.set_differentiable): forward() then runs with grad mode as the caller has
+        it, so `nll.mean().backward()` fills the dynamics' .grad.  Sampling entries stay no_grad."""
+        self.dynamics.set_differentiable(on)
+        return self
+
+    @no_grad_unless_differentiable
     def forward(self, phar, pocket, return_info=False, t_int=None, eps=None, _net=None):
-        """The joint model's 12 loss terms (+ info) of en_diffusion.py:332-465 as VALUES (no autograd graph: the
-        HIP evaluation has no backward pass).  ``t_int`` [B,1] and ``eps`` (list of combined draws, each a pair of
+        """The joint model's 12 loss terms (+ info) of en_diffusion.py:332-465 - VALUES (no autograd graph) unless the
+        dynamics are in differentiable mode and grad mode is on (then with autograd, as in the reference).  ``t_int`` [B,1] and ``eps`` (list of combined draws, each a pair of
         raw blocks, see sample_combined_position_feature_noise) may be supplied for reproducibility."""
         phar, pocket = dict(phar), dict(pocket)
         phar, pocket = self.normalize(phar, pocket)

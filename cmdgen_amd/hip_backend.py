@@ -66,6 +66,7 @@ SYMBOLS = [
     ('cmdgen_train_forward', C.c_int, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),
     ('cmdgen_train_backward', C.c_int, [_vp, _fp, _fp, _fp, _vp]),
     ('cmdgen_train_backward_stages', C.c_int, [_vp, _fp, _fp, _fp, C.c_int32, C.c_int32, _vp]),
+    ('cmdgen_train_backward_inputs', C.c_int, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),
     ('cmdgen_train_set_precision', C.c_int, [_vp, C.c_int32]),
     ('cmdgen_train_noise', C.c_int, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),
     ('cmdgen_train_loss', C.c_int, [_vp, C.c_int32, C.c_float, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),
@@ -404,6 +405,20 @@ class Handle:
         assert grad.is_cuda and grad.dtype == torch.float32 and grad.is_contiguous() and grad.numel() == self.param_count()
         self._check(self.lib.cmdgen_train_backward(self.h, _ptr(d_eps), _ptr(d_eps_pocket), _ptr(grad), self._stream()),
                     'cmdgen_train_backward')
+
+    def train_backward_inputs(self, d_eps, grad=None, d_eps_pocket=None, d_xh_phar=None, d_xh_pocket=None, d_t=None):
+        """The backward pass of the last train_forward to its inputs as well (cmdgen_train_backward_inputs).  grad (optional) is accumulated
+        as train_backward accumulates it; d_xh_phar [Nl, 3+phar_nf], d_xh_pocket [Np, 3+residue_nf] and d_t [batch] (each optional) are
+        written."""
+        import torch
+        assert d_eps.is_cuda and d_eps.dtype == torch.float32 and d_eps.is_contiguous()
+        assert d_eps_pocket is None or (d_eps_pocket.is_cuda and d_eps_pocket.dtype == torch.float32 and d_eps_pocket.is_contiguous())
+        assert grad is None or (grad.is_cuda and grad.dtype == torch.float32 and grad.is_contiguous() and grad.numel() == self.param_count())
+        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
+        for out, shape in ((d_xh_phar, (self.n_phar, 3 + P)), (d_xh_pocket, (self.n_pocket, 3 + R)), (d_t, (self.batch,))):
+            assert out is None or (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape), shape
+        self._check(self.lib.cmdgen_train_backward_inputs(self.h, _ptr(d_eps), _ptr(d_eps_pocket), _ptr(grad), _ptr(d_xh_phar),
+                                                          _ptr(d_xh_pocket), _ptr(d_t), self._stream()), 'cmdgen_train_backward_inputs')
 
     def train_backward_stages(self, d_eps, grad, first_stage: int, last_stage: int, d_eps_pocket=None):
         """Stages first..last of the backward pass (0 readout, k = block L-k, L+1 embedding / encoders)."""

@@ -132,10 +132,17 @@ class PharPocketDDPM(nn.Module):
                   'mask': data['pocket_mask'].to(self.device, INT_TYPE)}
         return phar, pocket
 
+    def set_differentiable(self, on: bool = True):
+        """Opt in to autograd (default off): with it on, `nll, _ = model(data); nll.mean().backward()` leaves the reference's
+        gradients in the dynamics' .grad - the reference's training_step with any torch optimizer (cmdgen_amd.autograd)."""
+        self.ddpm.set_differentiable(on)
+        return self
+
     def forward(self, data, t_int=None, eps=None, _net=None):
-        """-> (nll [B], info) as lightning_modules.py:188-239.  Loss VALUES (evaluation / monitoring) - no autograd
-        graph is built; the optimizer is driven by training.HipTrainer, which runs the HIP library's own backward
-        pass (cmdgen_train_forward / cmdgen_train_backward) with the analytic gradient of this loss."""
+        """-> (nll [B], info) as lightning_modules.py:188-239.  By default loss VALUES (evaluation / monitoring, no
+        autograd graph): training.HipTrainer drives the optimizer with the HIP library's own backward pass
+        (cmdgen_train_forward / cmdgen_train_backward) and the analytic gradient of this loss.  After
+        set_differentiable(True), in grad mode, nll carries a graph and nll.mean().backward() fills the .grads."""
         phar, pocket = self.get_phar_and_pocket(data)
         delta_log_px, error_t_phar, error_t_pocket, SNR_weight, loss_0_x_phar, loss_0_x_pocket, loss_0_h, \
             neg_log_const_0, kl_prior, log_pN, t_int_, xh_phar_hat, info = \

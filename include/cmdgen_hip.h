@@ -282,6 +282,22 @@ int cmdgen_train_backward(cmdgen_handle* h, const float* d_eps_phar, const float
 int cmdgen_train_backward_stages(cmdgen_handle* h, const float* d_eps_phar, const float* d_eps_pocket, float* grad,
                                  int32_t first_stage, int32_t last_stage, cmdgen_stream stream);
 
+/* The backward pass of the last cmdgen_train_forward to its INPUTS as well as to the parameters: the reference's autograd
+ * gradients of EGNNDynamics.forward (dynamics.py:75-139) with respect to xh_phar, xh_pocket and t.  grad (may be NULL: no
+ * parameter gradient is wanted) is accumulated exactly as cmdgen_train_backward accumulates it; the input gradients are
+ * WRITTEN (not accumulated), each only where its pointer is non-NULL:
+ *   d_xh_phar [Nl,3+phar_nf], d_xh_pocket [Np,3+residue_nf]: position columns through every radial, coord_diff and d0
+ *     term of every row (pocket rows that do not move included), the direct term of vel = x_final - x (and its centre-of-mass
+ *     projection when update_pocket_coords; zero where the NaN guard reset vel), feature columns through the encoders;
+ *   d_t [batch]: per-sample sum of the time column (condition_time; refused without it).
+ * The radius graph is a constant of the pass (as in the reference, whose edge set carries no gradient).  After a NaN reset of
+ * the forward's velocity (dynamics.py:129-131) no gradient flows through vel.  Any evaluation, chain or new layout on the handle
+ * since the forward replaces the graph the pass reads: the call then fails with CMDGEN_ESTATE (run the forward again;
+ * cmdgen_query "eval_gen" counts such calls).  The call changes nothing cmdgen_train_backward does: same kernels, same
+ * parameter gradient (both up to the order of float atomics). */
+int cmdgen_train_backward_inputs(cmdgen_handle* h, const float* d_eps_phar, const float* d_eps_pocket, float* grad,
+                                 float* d_xh_phar, float* d_xh_pocket, float* d_t, cmdgen_stream stream);
+
 /* The loss side of ConditionalDDPM.forward in training mode (conditional_model.py:198-320) and of
  * PharPocketDDPM.forward (lightning_modules.py:188-239), fused: three launches per step instead of a few hundred
  * small tensor operations.  Per-sample scalars that depend only on t and on the node counts are made by the host
