@@ -15,15 +15,18 @@ pocket and ~89 % of the per-block edge work becomes dead (and is skipped): that 
 reported beside the headline as `config.drifted_shipped_schedule_chain`, never as `value`.  The headline model is the
 same architecture and weight generator with noise_precision 0.1, norm_values [1, 0.25] (1/alpha_T = 3.2, max|x| ~ 17 A).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--timesteps T] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--timesteps T] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Both forms work: started WITHOUT a torch.distributed environment and with --gpus N > 1, this process touches no
 GPU, starts the N ranks itself (torch.distributed.run, one rank per GPU over RCCL) and relays rank 0's JSON line.
 
-Prints ONE JSON line (rank 0).  Also reported: the algorithmic-FLOP roofline of the dominant kernel measured live
-with HIP events on the launch stream, the north-star shape (256 pockets) next to the headline, and the oracle's CPU
-rate on the host cores (a baseline, not the target).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the
+headline with what the timed steps' own device counters give; no GPU or CPU work follows the timed steps.  --full also
+reports what takes runs of its own: the algorithmic-FLOP roofline of the dominant kernel measured live with HIP events
+on the launch stream, one evaluation's kernel breakdown, the steady-state micro-benchmark, the other shapes at N = 1
+(north star, full-atom, drifted chain, fp32 engine, training step, driver shapes) and the oracle's CPU rate on the
+host cores (a baseline, not the target).
 """
 import argparse
 import glob
@@ -82,10 +85,13 @@ def parse(argv=None):
     p.add_argument('--representation', default='CA', choices=['CA', 'full-atom'])
     p.add_argument('--n_phar', type=int, default=15)
     p.add_argument('--no-graph', action='store_true')
-    p.add_argument('--no-cpu-baseline', action='store_true')
-    p.add_argument('--cpu-seconds', type=float, default=12.0)
+    p.add_argument('--full', action='store_true',
+                   help='after the timed steps, also measure the records that take runs of their own: roofline and kernel breakdown, steady-state '
+                        'evaluation, the other shapes and the CPU baseline (a plain run reports the headline alone)')
+    p.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+    p.add_argument('--cpu-seconds', type=float, default=12.0, help='--full: time budget of the CPU baseline')
     p.add_argument('--north-star-batch', type=int, default=256,
-                   help='also time one chain at the north-star shape (pockets on one GPU; 0 = skip; N=1 only)')
+                   help='--full: also time one chain at the north-star shape (pockets on one GPU; 0 = skip; N=1 only)')
     p.add_argument('--gemm', default=None, choices=['split', 'fp32'],
                    help="matrix engine of tiles of >= 32 rows: 'split' (default of the library: fp32-accurate, six bf16 MFMAs "
                         "per fp32 product) or 'fp32' (v_mfma_f32_32x32x2_f32)")
@@ -95,9 +101,9 @@ def parse(argv=None):
     p.add_argument('--global-batch', type=int, default=512)
     p.add_argument('--shipped-schedule', action='store_true',
                    help='time the chain of the shipped schedule (noise_precision 1e-5, norm_values [1, 4]) as the headline: with untrained weights '
-                        'it drifts out of the pocket and most of its edge work is dead (diagnostic; the default line carries it as a side record)')
+                        'it drifts out of the pocket and most of its edge work is dead (diagnostic; the --full line carries it as a side record)')
     p.add_argument('--no-extra-shapes', action='store_true',
-                   help='skip the other records of the default line (trained-geometry chain, full-atom shape, training step)')
+                   help='--full without the other shapes (north star, full-atom shape, drifted chain, fp32 engine, training step, driver shapes)')
     p.add_argument('--rehearse-on-one-gpu', action='store_true',
                    help='N > 1 ranks that all use cuda:0 and rendezvous over gloo: runs the whole multi-rank path (sharded pockets, '
                         'barriers, MAX-over-ranks timing, rank count) on a one-GPU box; the number is NOT a scaling result')
@@ -254,6 +260,12 @@ def cpu_baseline(cfg, sd, batch, rep, n_phar, budget_s):
 
 
 # --------------------------------------------------------------------------------------------- the other records of the line
+def launch_config(h):
+    """The launch choices the library resolves for the handle's layout and options (host-side queries, no device work)."""
+    return {k: h.query(k) for k in ('node_mt', 'edge_mt', 'coord_mt', 'edge_grid', 'coord_grid', 'gemm_split', 'half_engine', 'node16_split', 'node16w', 'node64',
+                                    'msg_mfmas_per_product', 'node_mfmas_per_product', 'coord_mfmas_per_product')}
+
+
 def kernel_table(h, prof, pc, H, L, nl_tot):
     """Per-kernel roofline entries from one profiled eager chain: prof = {kernel: (total ms, launches)} (every launch carried its own
     HIP start / stop events), pc = device counters of that chain.  -> (per_kernel, dominant kernel, launch config, units per launch)."""
@@ -265,8 +277,7 @@ def kernel_table(h, prof, pc, H, L, nl_tot):
     flop_launch = {'edge_msg': 2.0 * (H * H + H) * units['edge_msg'],
                    'node': node_flop_per_launch(H, L, units['node'], nl_tot, False),
                    'edge_coord': coord_flop_per_launch(H, L, units['edge_coord'], pc['nodes'] / ev, False)}
-    launch_cfg = {k: h.query(k) for k in ('node_mt', 'edge_mt', 'coord_mt', 'edge_grid', 'coord_grid', 'gemm_split', 'half_engine', 'node16_split', 'node16w', 'node64',
-                                           'msg_mfmas_per_product', 'node_mfmas_per_product', 'coord_mfmas_per_product')}
+    launch_cfg = launch_config(h)
     # node64: the 64-row planes node kernel took the launches (kernels_node64.hip; chosen per layout by tile count)
     mt_of = {'edge_msg': launch_cfg['edge_mt'], 'node': 32 if launch_cfg['node64'] == 32 else 64 if launch_cfg['node64'] else launch_cfg['node_mt'], 'edge_coord': launch_cfg['coord_mt']}
     # the matrix engine each kernel ran on, as the library's launchers resolve it: MFMAs per fp32 product (1 / 6 / 3)
@@ -522,71 +533,11 @@ def main(argv=None):
     if rank == 0:
         H, L, dyn = cfg.hidden_nf, cfg.n_layers, cfg.joint_nf + 1
         nl_tot = int(pb.num_nodes_phar.sum())
-        # ---- roofline of the dominant kernel: EVERY launch of the three MFMA kernels during one more chain of the same
-        # workload carries its own start / stop HIP events (hipExtLaunchKernelGGL on the launch stream: the dispatch's own
-        # begin / end timestamps, what rocprofv3 --kernel-trace reports; eager launches: a graph replay has no per-kernel events).
-        # Algorithmic FLOP per launch: edge kernels 2(H^2+H) per listed edge (device counters); node kernel see
-        # node_flop_per_launch (what each launch needs, not 14 H^2 on every row).
-        with torch.cuda.stream(stream):
-            h.reset_counters()
-            h.set_kernel_profiling(True)
-            h.sample_chain(px, poh, T, noise=None, seed=0, pocket_ids=pb.pocket_index, use_graph=False)
-            prof = h.kernel_profile()
-            h.set_kernel_profiling(False)
-            pc = h.counters()
-            # whole-evaluation kernel breakdown on the final chain state
-            z = out[0].clone(); z[:, 3:] = 0
-            kt = h.profile_evaluation(z.contiguous(), torch.cat([out[1][:, :3], out[1][:, 3:] / cfg.norm_values[1]], 1).contiguous(),
-                                      torch.full((B,), 0.5, device=dev))
-        # ---- steady-state micro-benchmark: one evaluation at the geometry a TRAINED model holds -
-        # phar points uniform in a 5 A ball at the pocket centre (random-init weights let the chain drift away,
-        # which roughly halves the edge count).  Graph-replayed, timed with HIP events on the launch stream.
-        with torch.cuda.stream(stream):
-            rng = np.random.Generator(np.random.PCG64(12345 + rank))
-            pm_np = np.repeat(np.arange(B), pb.num_nodes_phar)
-            com = np.stack([pb.x[pb.mask == b].mean(0) for b in range(B)])
-            v = rng.normal(size=(nl_tot, 3)); v /= np.linalg.norm(v, axis=1, keepdims=True)
-            xin = (com[pm_np] + v * 5.0 * np.cbrt(rng.uniform(size=(nl_tot, 1)))).astype(np.float32)
-            xh_in = torch.from_numpy(np.concatenate([xin, rng.normal(size=(nl_tot, cfg.phar_nf)).astype(np.float32)], 1)).to(dev)
-            xq_in = torch.from_numpy(np.concatenate([pb.x, pb.one_hot / cfg.norm_values[1]], 1).astype(np.float32)).to(dev)
-            t_in = torch.full((B,), 0.5, device=dev)
-            h.reset_counters()
-            ms_eval = h.time_evaluation(xh_in, xq_in, t_in, graph_len=10, replays=20 if rep == 'CA' else 3)
-            mc = h.counters()
-        dt_micro = ms_eval * 1e-3
-        m_ev = max(mc['evaluations'], 1)
-        steady = {'us_per_evaluation': 1e3 * ms_eval, 'pocket_evaluations_per_s': B / dt_micro,
-                  'edges_per_pocket': mc['edges'] / m_ev / B, 'coord_edges_per_pocket': mc['edges_phar'] / m_ev / B,
-                  'edges_per_s': mc['edges'] / m_ev / dt_micro,
-                  'alg_tflops': whole_job_flop(H, L, dyn, mc['edges'], mc['edges_phar'], mc['nodes'], m_ev * nl_tot) / m_ev / dt_micro / 1e12,
-                  'timing': 'hipGraph of 10 evaluations replayed, HIP events on the launch stream'}
-        per_kernel, dom, launch_cfg, units = kernel_table(h, prof, pc, H, L, nl_tot)
-        kname = KERNEL_NAMES
-        achieved = per_kernel[dom]['tflops']
-        avg_ms, launches, flop_per_launch = per_kernel[dom]['avg_launch_ms'], per_kernel[dom]['launches'], per_kernel[dom]['flop_per_launch']
-        p_ev = max(pc['evaluations'], 1)
-        reference_flop_per_launch = {'edge_msg': 2.0 * (H * H + H) * pc['edges'] / p_ev, 'node': node_flop_per_launch(H, L, pc['nodes'] / p_ev, nl_tot, False),
-                                     'edge_coord': per_kernel['edge_coord']['flop_per_launch'] if 'edge_coord' in per_kernel else 0.0}[dom]
+        launch_cfg = launch_config(h)
         # whole-job algorithmic FLOP for the timed region
         f_ref = whole_job_flop(H, L, dyn, cnt['edges'], cnt['edges_phar'], cnt['nodes'], cnt['evaluations'] * nl_tot)            # what the reference computes
         f_alg = whole_job_flop(H, L, dyn, executed(cnt, L)[0], cnt['edges_phar'], executed(cnt, L)[1], cnt['evaluations'] * nl_tot)   # what ran
-        # HBM-side bytes per launch from the PMC passes (tools/collect_traffic.py), only when they were taken on
-        # exactly these kernel sources
-        traffic, traffic_note = None, 'no profiles/kernel_traffic.json'
-        tpath = os.path.join(ROOT, 'profiles', 'kernel_traffic.json')
         sha = kernel_source_sha()
-        if os.path.exists(tpath):
-            try:
-                tj = json.load(open(tpath))
-                if tj.get('kernel_source_sha') != sha:
-                    traffic_note = f"stale: measured on kernel sources {tj.get('kernel_source_sha')}, these are {sha}"
-                elif tj.get('workload_batch') != B or tj.get('representation') != rep:
-                    traffic_note = 'measured on another workload'
-                else:
-                    traffic = tj.get('hbm_bytes_per_launch', {}).get(dom)
-                    traffic_note = tj.get('source')
-            except Exception as e:          # noqa: BLE001
-                traffic_note = f'unreadable: {e}'
         result = {
             'metric': 'denoising steps/sec', 'value': value, 'unit': 'pocket-steps/s',
             'n_gpus': n_gpus, 'steps': args.steps, 'warmup': args.warmup,
@@ -616,8 +567,6 @@ def main(argv=None):
                 'edges_per_s': n_gpus * cnt['edges'] / elapsed,
                 'whole_step_alg_tflops': f_alg / elapsed / 1e12,
                 'chain_status': st,
-                'kernel_ms_one_evaluation': kt,
-                'steady_state_evaluation': steady,
                 'kernel_source_sha': sha,
                 'launch': launch_cfg,
                 # north_star: "sampled coords within 1e-4 RMS of reference".  Where it is asserted as an ABSOLUTE bound: the reference's
@@ -627,7 +576,72 @@ def main(argv=None):
                 'parity': 'coordinate RMS vs the reference <= 1e-4 A absolute at this size in the bounded-|x| regime (G14: 7.7e-5 A, types exact); '
                           'per-step z of the shipped schedule pinned by G15 (K = T = 500) relative to |x|',
             },
-            'roofline': {
+        }
+        if args.full:
+            # ---- roofline of the dominant kernel: EVERY launch of the three MFMA kernels during one more chain of the same
+            # workload carries its own start / stop HIP events (hipExtLaunchKernelGGL on the launch stream: the dispatch's own
+            # begin / end timestamps, what rocprofv3 --kernel-trace reports; eager launches: a graph replay has no per-kernel events).
+            # Algorithmic FLOP per launch: edge kernels 2(H^2+H) per listed edge (device counters); node kernel see
+            # node_flop_per_launch (what each launch needs, not 14 H^2 on every row).
+            with torch.cuda.stream(stream):
+                h.reset_counters()
+                h.set_kernel_profiling(True)
+                h.sample_chain(px, poh, T, noise=None, seed=0, pocket_ids=pb.pocket_index, use_graph=False)
+                prof = h.kernel_profile()
+                h.set_kernel_profiling(False)
+                pc = h.counters()
+                # whole-evaluation kernel breakdown on the final chain state
+                z = out[0].clone(); z[:, 3:] = 0
+                kt = h.profile_evaluation(z.contiguous(), torch.cat([out[1][:, :3], out[1][:, 3:] / cfg.norm_values[1]], 1).contiguous(),
+                                          torch.full((B,), 0.5, device=dev))
+            # ---- steady-state micro-benchmark: one evaluation at the geometry a TRAINED model holds -
+            # phar points uniform in a 5 A ball at the pocket centre (random-init weights let the chain drift away,
+            # which roughly halves the edge count).  Graph-replayed, timed with HIP events on the launch stream.
+            with torch.cuda.stream(stream):
+                rng = np.random.Generator(np.random.PCG64(12345 + rank))
+                pm_np = np.repeat(np.arange(B), pb.num_nodes_phar)
+                com = np.stack([pb.x[pb.mask == b].mean(0) for b in range(B)])
+                v = rng.normal(size=(nl_tot, 3)); v /= np.linalg.norm(v, axis=1, keepdims=True)
+                xin = (com[pm_np] + v * 5.0 * np.cbrt(rng.uniform(size=(nl_tot, 1)))).astype(np.float32)
+                xh_in = torch.from_numpy(np.concatenate([xin, rng.normal(size=(nl_tot, cfg.phar_nf)).astype(np.float32)], 1)).to(dev)
+                xq_in = torch.from_numpy(np.concatenate([pb.x, pb.one_hot / cfg.norm_values[1]], 1).astype(np.float32)).to(dev)
+                t_in = torch.full((B,), 0.5, device=dev)
+                h.reset_counters()
+                ms_eval = h.time_evaluation(xh_in, xq_in, t_in, graph_len=10, replays=20 if rep == 'CA' else 3)
+                mc = h.counters()
+            dt_micro = ms_eval * 1e-3
+            m_ev = max(mc['evaluations'], 1)
+            steady = {'us_per_evaluation': 1e3 * ms_eval, 'pocket_evaluations_per_s': B / dt_micro,
+                      'edges_per_pocket': mc['edges'] / m_ev / B, 'coord_edges_per_pocket': mc['edges_phar'] / m_ev / B,
+                      'edges_per_s': mc['edges'] / m_ev / dt_micro,
+                      'alg_tflops': whole_job_flop(H, L, dyn, mc['edges'], mc['edges_phar'], mc['nodes'], m_ev * nl_tot) / m_ev / dt_micro / 1e12,
+                      'timing': 'hipGraph of 10 evaluations replayed, HIP events on the launch stream'}
+            per_kernel, dom, _, units = kernel_table(h, prof, pc, H, L, nl_tot)
+            kname = KERNEL_NAMES
+            achieved = per_kernel[dom]['tflops']
+            avg_ms, launches, flop_per_launch = per_kernel[dom]['avg_launch_ms'], per_kernel[dom]['launches'], per_kernel[dom]['flop_per_launch']
+            p_ev = max(pc['evaluations'], 1)
+            reference_flop_per_launch = {'edge_msg': 2.0 * (H * H + H) * pc['edges'] / p_ev, 'node': node_flop_per_launch(H, L, pc['nodes'] / p_ev, nl_tot, False),
+                                         'edge_coord': per_kernel['edge_coord']['flop_per_launch'] if 'edge_coord' in per_kernel else 0.0}[dom]
+            # HBM-side bytes per launch from the PMC passes (tools/collect_traffic.py), only when they were taken on
+            # exactly these kernel sources
+            traffic, traffic_note = None, 'no profiles/kernel_traffic.json'
+            tpath = os.path.join(ROOT, 'profiles', 'kernel_traffic.json')
+            if os.path.exists(tpath):
+                try:
+                    tj = json.load(open(tpath))
+                    if tj.get('kernel_source_sha') != sha:
+                        traffic_note = f"stale: measured on kernel sources {tj.get('kernel_source_sha')}, these are {sha}"
+                    elif tj.get('workload_batch') != B or tj.get('representation') != rep:
+                        traffic_note = 'measured on another workload'
+                    else:
+                        traffic = tj.get('hbm_bytes_per_launch', {}).get(dom)
+                        traffic_note = tj.get('source')
+                except Exception as e:          # noqa: BLE001
+                    traffic_note = f'unreadable: {e}'
+            result['config']['kernel_ms_one_evaluation'] = kt
+            result['config']['steady_state_evaluation'] = steady
+            result['roofline'] = {
                 'bound': 'mfma', 'kernel': kname[dom],
                 'achieved': achieved, 'peak': per_kernel[dom]['peak'], 'unit': 'TFLOP/s',
                 'frac': per_kernel[dom]['frac'], 'traffic': traffic, 'traffic_note': traffic_note,
@@ -664,10 +678,9 @@ def main(argv=None):
                 # the north-star also asks for the HBM view: PMC bytes per launch / launch time / 8 TB/s (not the binding roofline)
                 'hbm_frac_from_pmc': (traffic / (avg_ms * 1e-3) / (PEAK_HBM_TBS * 1e12)) if traffic else None,
                 'per_kernel': {k: {kk: v[kk] for kk in PER_KERNEL_KEYS} for k, v in per_kernel.items()},
-            },
-        }
-        # ---- the other records of the default line (N = 1): every chain below keeps the phar points inside the pocket unless its name says "drifted"
-        if n_gpus == 1 and not args.no_extra_shapes and not args.strong and rep == 'CA' and not args.shipped_schedule:
+            }
+        # ---- the other records of the --full line (N = 1): every chain below keeps the phar points inside the pocket unless its name says "drifted"
+        if args.full and n_gpus == 1 and not args.no_extra_shapes and not args.strong and rep == 'CA' and not args.shipped_schedule:
             # north_star: a 256-pocket CrossDocked batch on one GPU, same model, K = T
             ns = chain_record(cfg, sd, make_pockets(args.north_star_batch, 'CA', n_phar=args.n_phar), T, dev, stream, use_graph, prof_steps=16, gemm=args.gemm) \
                 if args.north_star_batch and args.north_star_batch != B else None
@@ -725,7 +738,7 @@ def main(argv=None):
                 flat[tag + '_value'] = round(r['value'], 1)
             flat['launches_per_step'] = 3 + 3 * cfg_d.n_layers
             flat['driver_shapes'] = shapes
-        if not args.no_cpu_baseline and n_gpus == 1:      # timed on rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and n_gpus == 1:      # timed on rank 0 at N=1 only
             result['cpu_baseline'] = cpu_baseline(cfg, sd, B, rep, args.n_phar, args.cpu_seconds)
             cpu_v = result['cpu_baseline']['value']
             result['config']['gpu_over_cpu'] = value / cpu_v           # same model, same geometry (phar points inside the pocket)

@@ -108,6 +108,14 @@ def test_dump_outputs_writes_float32_within_the_size_limit(tmp_path, monkeypatch
     assert sum(os.path.getsize(tmp_path / 's1' / f) - 128 for f in ('a_rank1.npy', 'b_rank1.npy')) <= 200
 
 
+def test_full_is_an_option_off_by_default():
+    """A plain run times the headline alone; the records that take runs of their own need --full."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse([]).full is False and bench.parse(['--full']).full is True
+    assert _run(['--full'])['n_gpus'] == 1
+
+
 def test_steps_must_be_positive():
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--dry-run-launch', '--steps', '0'],
                        capture_output=True, text=True, timeout=600)

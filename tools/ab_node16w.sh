@@ -7,7 +7,7 @@ for rep in 1 2; do
 for o in node16w=1 node16w=0; do
   for b in 32 64; do
     echo -n "[$o B=$b] "
-    timeout -k 10 300 python bench.py --batch $b --steps 3 --warmup 1 --no-extra-shapes --no-cpu-baseline --option $o 2>/dev/null | tail -1 | python -c "
+    timeout -k 10 300 python bench.py --full --batch $b --steps 3 --warmup 1 --no-extra-shapes --no-cpu-baseline --option $o 2>/dev/null | tail -1 | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); print('%.1f pocket-steps/s' % d['value'], [(k['kernel'][:24], round(k['avg_us'],1)) for k in d['roofline'].get('kernels', [])][:3] if isinstance(d.get('roofline'), dict) else '')"
   done

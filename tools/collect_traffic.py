@@ -3,9 +3,9 @@
 
 The passes (separate runs, TCC slots do not hold both counters; program directly after `--`):
 
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --north-star-batch 0
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_write -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --north-star-batch 0
-    python3 tools/collect_traffic.py gpurun_out/pmc_fetch gpurun_out/pmc_write --out gpurun_out/kernel_traffic.json [--sq gpurun_out/pmc_sq]
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d OUT/pmc_fetch -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --north-star-batch 0
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d OUT/pmc_write -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --north-star-batch 0
+    python3 tools/collect_traffic.py OUT/pmc_fetch OUT/pmc_write --out OUT/kernel_traffic.json [--sq OUT/pmc_sq]
 
 HBM-side bytes per launch = (2 x FETCH_SIZE + WRITE_SIZE) x 1024 (MI355X_MICROARCH.md, HBM: on gfx950 FETCH_SIZE reports
 half the bytes of 16 B/lane reads, WRITE_SIZE is exact; both in KiB; Infinity-Cache hits are counted, so this is an upper
@@ -58,7 +58,7 @@ def main():
     ap.add_argument('--out', default=os.path.join(ROOT, 'gpurun_out', 'kernel_traffic.json'))
     ap.add_argument('--batch', type=int, default=64)
     ap.add_argument('--representation', default='CA')
-    ap.add_argument('--command', default='python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --north-star-batch 0')
+    ap.add_argument('--command', default='python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --north-star-batch 0')
     a = ap.parse_args()
     from bench import kernel_source_sha
     fetch = read_counters(a.fetch_dir).get('FETCH_SIZE', {})

@@ -10,10 +10,10 @@ run() { echo "== $*" >&2; timeout -k 10 "$@"; rc=$?; if [ $rc -eq 124 ] || [ $rc
 if [ $part != b ]; then
 run 900 python -m pytest tests -m gpu -q > $o/${tag}_gpu_tests.log 2>&1; tail -3 $o/${tag}_gpu_tests.log
 run 120 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee $o/${tag}_smoke.txt
-# rocprofv3 kernel stats of the headline command alone (no other record of the default line), then the PMC passes (separate runs; 200-step chains)
-run 400 rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_stats -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --north-star-batch 0 --no-extra-shapes > /dev/null 2>&1
+# rocprofv3 kernel stats of the headline command and its roofline passes (none of the other shapes of the --full line), then the PMC passes (separate runs; 200-step chains)
+run 400 rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_stats -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --north-star-batch 0 --no-extra-shapes > /dev/null 2>&1
 cp $(find $o/${tag}_stats -name "*kernel_stats.csv" | head -1) $o/${tag}_kernel_stats_b64_T1000.csv; rm -rf $o/${tag}_stats
-BARGS="--steps 1 --warmup 0 --timesteps 200 --no-cpu-baseline --north-star-batch 0 --no-extra-shapes"
+BARGS="--full --steps 1 --warmup 0 --timesteps 200 --no-cpu-baseline --north-star-batch 0 --no-extra-shapes"
 run 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $o/pmc_fetch -- python3 bench.py $BARGS > /dev/null 2> $o/pmc_fetch.err
 run 400 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $o/pmc_write -- python3 bench.py $BARGS > /dev/null 2> $o/pmc_write.err
 run 400 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_LDS --output-format csv -d $o/pmc_sq -- python3 bench.py $BARGS > /dev/null 2> $o/pmc_sq.err
@@ -21,13 +21,13 @@ run 100 python3 tools/collect_traffic.py $o/pmc_fetch $o/pmc_write --sq $o/pmc_s
 rm -rf $o/pmc_fetch $o/pmc_write $o/pmc_sq
 # the traffic file belongs to these sources (stamped with their hash): the default line below reads it from profiles/
 cp $o/kernel_traffic.json profiles/kernel_traffic.json
-# the default line: headline (64 pockets, phar points inside the pocket), north_star_trained, fullatom_trained, drifted chain, fp32 engine, training step, cpu_baseline
-run 900 python bench.py --steps 5 --warmup 2 > $o/${tag}_bench_b64.json 2> $o/${tag}_bench_b64.err
+# the --full line: headline (64 pockets, phar points inside the pocket), north_star_trained, fullatom_trained, drifted chain, fp32 engine, training step, cpu_baseline
+run 900 python bench.py --full --steps 5 --warmup 2 > $o/${tag}_bench_b64.json 2> $o/${tag}_bench_b64.err
 fi
 if [ $part = a ]; then echo done part a; exit 0; fi
 # the same counters and kernel stats at the north-star batch (256 pockets: 128-row edge kernels, 64-row node kernel), 100-step chains
-B256="--batch 256 --steps 1 --warmup 0 --timesteps 100 --no-cpu-baseline --north-star-batch 0 --no-extra-shapes"
-run 400 rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_stats256 -- python3 bench.py --batch 256 --steps 1 --warmup 1 --timesteps 300 --no-cpu-baseline --north-star-batch 0 --no-extra-shapes > /dev/null 2>&1
+B256="--full --batch 256 --steps 1 --warmup 0 --timesteps 100 --no-cpu-baseline --north-star-batch 0 --no-extra-shapes"
+run 400 rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_stats256 -- python3 bench.py --full --batch 256 --steps 1 --warmup 1 --timesteps 300 --no-cpu-baseline --north-star-batch 0 --no-extra-shapes > /dev/null 2>&1
 cp $(find $o/${tag}_stats256 -name "*kernel_stats.csv" | head -1) $o/${tag}_kernel_stats_b256_T300.csv; rm -rf $o/${tag}_stats256
 run 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $o/pmc_fetch -- python3 bench.py $B256 > /dev/null 2> $o/pmc_fetch.err
 run 400 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $o/pmc_write -- python3 bench.py $B256 > /dev/null 2> $o/pmc_write.err

@@ -3,7 +3,7 @@
 tag=${1:-r04_w}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 o=gpurun_out
-FA="--batch 64 --representation full-atom --steps 1 --warmup 0 --timesteps 20 --no-cpu-baseline --north-star-batch 0 --no-extra-shapes"
+FA="--full --batch 64 --representation full-atom --steps 1 --warmup 0 --timesteps 20 --no-cpu-baseline --north-star-batch 0 --no-extra-shapes"
 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_fa_stats -- python3 bench.py $FA > /dev/null 2>&1
 cp $(find $o/${tag}_fa_stats -name "*kernel_stats.csv" | head -1) $o/${tag}_kernel_stats_fullatom_b64_T20.csv; rm -rf $o/${tag}_fa_stats
 timeout -k 10 500 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_LDS --output-format csv -d $o/pmc_sq -- python3 bench.py $FA > /dev/null 2> $o/pmc_sq.err

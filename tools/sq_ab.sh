@@ -3,8 +3,8 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 o=gpurun_out
 PMC="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES"
-FA="--representation full-atom --batch 64 --timesteps 20 --steps 1 --warmup 0 --north-star-batch 0 --no-cpu-baseline --no-extra-shapes"
-CA="--batch 256 --timesteps 50 --steps 1 --warmup 0 --north-star-batch 0 --no-cpu-baseline --no-extra-shapes"
+FA="--full --representation full-atom --batch 64 --timesteps 20 --steps 1 --warmup 0 --north-star-batch 0 --no-cpu-baseline --no-extra-shapes"
+CA="--full --batch 256 --timesteps 50 --steps 1 --warmup 0 --north-star-batch 0 --no-cpu-baseline --no-extra-shapes"
 unset CMDGEN_LIB
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc $PMC --output-format csv -d $o/sq_fa_pin -- python3 bench.py $FA > /dev/null 2>&1; echo rc=$?
 export CMDGEN_LIB=build/libcmdgen_hip_burst.so
