@@ -34,6 +34,10 @@ void cmdgen_launch_debug_noise(unsigned long long seed, long long pocket_id, int
 void cmdgen_launch_chain_final(const Layout& lay, const Dims& d, const ChainBuf& c, const Work& w,
                                const float* eps, float* xo, float* po, unsigned int* cog, hipStream_t s);
 
+void cmdgen_launch_inpaint_prep(const Layout& lay, const Dims& d, const ChainBuf& c, const InpaintBuf& ip, const float* phx,
+                                const float* phoh, const float* fix, const float* px, hipStream_t s);
+void cmdgen_launch_inpaint_step_count(const Layout& lay, const Dims& d, const ChainBuf& c, const InpaintBuf& ip, const Work& w,
+                                      const float* eps, hipStream_t s);
 void cmdgen_launch_joint_init(const Layout& lay, const Dims& d, const JointBuf& c, const float* phx, const float* phoh,
                               const float* px, const float* poh, hipStream_t s);
 void cmdgen_launch_joint_step(const Layout& lay, const Dims& d, const JointBuf& c, const float* ep, const float* eq, hipStream_t s);
@@ -100,10 +104,11 @@ extern "C" void cmdgen_destroy(cmdgen_handle* h) {
     hipSetDevice(h->device);
     if (h->step_graph) hipGraphExecDestroy(h->step_graph);
     if (h->joint_graph) hipGraphExecDestroy(h->joint_graph);
+    if (h->inpaint_graph) hipGraphExecDestroy(h->inpaint_graph);
     if (h->own_stream) hipStreamDestroy(h->own_stream);
     if (h->ev_in) hipEventDestroy(h->ev_in);
     if (h->ev_out) hipEventDestroy(h->ev_out);
-    free_pool(h->weight_allocs); free_pool(h->layout_allocs); free_pool(h->chain_allocs); free_pool(h->joint_allocs);
+    free_pool(h->weight_allocs); free_pool(h->layout_allocs); free_pool(h->chain_allocs); free_pool(h->joint_allocs); free_pool(h->inp_allocs);
     for (int i = 0; i < 2; ++i) { if (h->idx_stage[i]) hipHostFree(h->idx_stage[i]); if (h->idx_ev[i]) hipEventDestroy(h->idx_ev[i]); }
     if (h->h_norm) hipHostFree(h->h_norm);
     if (h->norm_ev) hipEventDestroy(h->norm_ev);
@@ -296,6 +301,7 @@ extern "C" int cmdgen_finalize_weights(cmdgen_handle* h) {
     hipSetDevice(h->device);
     if (h->step_graph) { hipGraphExecDestroy(h->step_graph); h->step_graph = nullptr; }
     if (h->joint_graph) { hipGraphExecDestroy(h->joint_graph); h->joint_graph = nullptr; }
+    if (h->inpaint_graph) { hipGraphExecDestroy(h->inpaint_graph); h->inpaint_graph = nullptr; }
     free_pool(h->weight_allocs);
     h->layers.clear();
     const Dims& d = h->dims;
@@ -401,6 +407,7 @@ extern "C" int cmdgen_finalize_weights(cmdgen_handle* h) {
     h->finalized = true;
     h->user_coef_K = -1; h->chain_K = -1;      // a new gamma table invalidates any step table
     h->joint_steps = -1; h->joint_key.clear();
+    h->inp_steps = -1;
     return CMDGEN_OK;
 }
 
@@ -543,7 +550,7 @@ static int set_layout_impl(cmdgen_handle* h, int64_t batch, const int64_t* nph, 
     // are still running on `stream` keep reading theirs)
     const bool fits_now = h->cap_B >= B && h->cap_Nl >= Nl && h->cap_Np >= Np && h->cap_N >= N && h->cap_e >= ecap && h->cap_ec >= eccap;
     const bool no_wait = on_stream && fits_now && h->have_layout && h->chain_allocs.empty() && h->joint_allocs.empty() &&
-                         (h->last_stream == stream) && !h->step_graph && !h->joint_graph;
+                         h->inp_allocs.empty() && (h->last_stream == stream) && !h->step_graph && !h->joint_graph && !h->inpaint_graph;
     if (!no_wait) {
         if (h->own_stream) hipStreamSynchronize(h->own_stream);
         if (h->have_layout) hipStreamSynchronize(h->last_stream);
@@ -551,6 +558,7 @@ static int set_layout_impl(cmdgen_handle* h, int64_t batch, const int64_t* nph, 
     }
     if (h->step_graph) { hipGraphExecDestroy(h->step_graph); h->step_graph = nullptr; }
     if (h->joint_graph) { hipGraphExecDestroy(h->joint_graph); h->joint_graph = nullptr; }
+    if (h->inpaint_graph) { hipGraphExecDestroy(h->inpaint_graph); h->inpaint_graph = nullptr; }
     int rc; void* p;
     Layout& L = h->lay; Work& w = h->work;
     // Workspaces are capacity-based: a new batch that fits the current capacities (every training step and every
@@ -560,6 +568,7 @@ static int set_layout_impl(cmdgen_handle* h, int64_t batch, const int64_t* nph, 
         hipDeviceSynchronize();
         free_pool(h->layout_allocs); free_pool(h->chain_allocs); h->chain_K = -1;
         free_pool(h->joint_allocs); h->joint_steps = -1; h->joint_key.clear();
+        free_pool(h->inp_allocs); h->inp_steps = -1;
         cmdgen_train_free(h->train); h->train = nullptr;
         h->have_layout = false;
         auto grow = [](int64_t v) { return v + v / 4 + 64; };
@@ -597,6 +606,7 @@ static int set_layout_impl(cmdgen_handle* h, int64_t batch, const int64_t* nph, 
         // chain / joint buffers are sized by the exact layout and cheap: rebuilt on the next chain
         free_pool(h->chain_allocs); h->chain_K = -1;
         free_pool(h->joint_allocs); h->joint_steps = -1; h->joint_key.clear();
+        free_pool(h->inp_allocs); h->inp_steps = -1;
     }
     if (edge_lds_bytes(max_n) > 64 * 1024) cmdgen_edge_kernels_allow_lds(edge_lds_bytes(max_n));
     L.B = B; L.Nl = (int)Nl; L.Np = (int)Np; L.N = (int)N; L.max_n = max_n;
@@ -744,6 +754,7 @@ static void drop_graphs(cmdgen_handle* h) {
     if (h->have_layout) hipStreamSynchronize(h->last_stream);
     if (h->step_graph) { hipGraphExecDestroy(h->step_graph); h->step_graph = nullptr; }
     if (h->joint_graph) { hipGraphExecDestroy(h->joint_graph); h->joint_graph = nullptr; }
+    if (h->inpaint_graph) { hipGraphExecDestroy(h->inpaint_graph); h->inpaint_graph = nullptr; }
 }
 static void refresh_tune(cmdgen_handle* h) {
     TrainTune t;
@@ -978,7 +989,7 @@ extern "C" int cmdgen_sample_chain(cmdgen_handle* h, const float* pocket_x, cons
     const int K = timesteps;
     if (K < 1 || K > h->cfg.timesteps) return fail(h, CMDGEN_EINVAL, "timesteps=%d must be in [1, %d]", K, h->cfg.timesteps);
     if (h->dims.joint) return fail(h, CMDGEN_ESTATE, "this handle is the joint model (update_pocket_coords=1): use cmdgen_joint_chain");
-    h->last_chain_joint = false;
+    h->last_chain_joint = false; h->last_chain_inpaint = false;
     hipSetDevice(h->device);
     hipStream_t caller = (hipStream_t)stream;
     hipStream_t s = caller;
@@ -1168,6 +1179,7 @@ static int prepare_joint(cmdgen_handle* h, int K, int resamplings, int jump, boo
     if (h->joint_steps >= 0 && h->joint_key == key) return 0;
     hipDeviceSynchronize();
     if (h->joint_graph) { hipGraphExecDestroy(h->joint_graph); h->joint_graph = nullptr; }
+    if (h->inpaint_graph) { hipGraphExecDestroy(h->inpaint_graph); h->inpaint_graph = nullptr; }
     free_pool(h->joint_allocs);
     h->joint_steps = -1;
     const Dims& d = h->dims;
@@ -1233,7 +1245,7 @@ extern "C" int cmdgen_joint_chain(cmdgen_handle* h, const float* phar_x, const f
         cmdgen_joint_plan(h, timesteps, resamplings, jump_length, inpaint ? 1 : 0, nullptr, &need);
         if (n_draws < need) return fail(h, CMDGEN_EINVAL, "noise holds %lld combined draws, the schedule needs %lld", (long long)n_draws, (long long)need);
     }
-    h->last_chain_joint = true;
+    h->last_chain_joint = true; h->last_chain_inpaint = false;
     const Dims& d = h->dims;
     {
         std::vector<int64_t> gid(h->lay.B);
@@ -1290,14 +1302,227 @@ extern "C" int cmdgen_joint_chain(cmdgen_handle* h, const float* phar_x, const f
     return CMDGEN_OK;
 }
 
+// ---------------------------------------------------------------------------------
+// conditional RePaint: ConditionalDDPM.inpaint (kernels_inpaint.hip; the op semantics and the draw scheme are in
+// include/cmdgen_hip.h)
+// ---------------------------------------------------------------------------------
+struct InpaintPlan {
+    std::vector<float> coef, coef2;     // [n_steps+1][4] (last: decode row), [n_steps][4]
+    std::vector<int> iop;               // [n_steps][4]
+    int n_steps = 0, n_draws = 0;
+};
+
+// One row per op in execution order.  The posterior rows are the step table's (the caller's, when it supplied one for K:
+// then an op at step s uses exactly the scalars cmdgen_sample_chain uses there).
+static InpaintPlan build_inpaint_plan(const cmdgen_handle* h, int K, int resamplings, int jump) {
+    InpaintPlan p;
+    std::vector<float> tab;
+    if (h->user_coef_K == K) tab = h->user_coef; else build_step_table(h->gamma, h->cfg.timesteps, K, tab);
+    const int T = h->cfg.timesteps;
+    auto g_at = [&](int step) { return h->gamma[(size_t)lrintf(((float)step / (float)K) * (float)T)]; };
+    const std::vector<int> sched = repaint_schedule(resamplings, jump, K);
+    int draw = 1;                       // row 0 = z_T
+    int s = K - 1;
+    for (size_t i = 0; i < sched.size(); ++i) {
+        for (int j = 0; j < sched[i]; ++j) {
+            p.coef.insert(p.coef.end(), tab.begin() + (size_t)(K - 1 - s) * 4, tab.begin() + (size_t)(K - s) * 4);
+            const float g_s = g_at(s);
+            const int rowA = draw++, rowB = draw++;
+            float re_a = 0.f, re_s = 0.f; int flags = 0, rowC = 0;
+            if (j == sched[i] - 1 && i + 1 < sched.size()) {      // jump back s -> s + jump_length
+                const float g_t2 = g_at(s + jump);
+                re_s = sqrtf(-expm1f(softplus_f(g_s) - softplus_f(g_t2)));
+                re_a = expf(0.5f * (logsigmoid_f(-g_t2) - logsigmoid_f(-g_s)));
+                flags = 1; rowC = draw++;
+                s = s + jump;
+            }
+            p.coef2.insert(p.coef2.end(), {sqrtf(sigmoid_h(-g_s)), sqrtf(sigmoid_h(g_s)), re_a, re_s});
+            p.iop.insert(p.iop.end(), {flags, rowA, rowB, rowC});
+            s -= 1;
+            p.n_steps += 1;
+        }
+    }
+    p.coef.insert(p.coef.end(), tab.begin() + (size_t)K * 4, tab.begin() + (size_t)(K + 1) * 4);
+    p.n_draws = draw + 1;               // + the decode draw
+    return p;
+}
+
+static int check_inpaint_args(cmdgen_handle* h, int K, int resamplings, int jump) {
+    if (h->dims.joint) return fail(h, CMDGEN_ESTATE, "this handle is the joint model (update_pocket_coords=1): use cmdgen_joint_chain");
+    if (h->dims.no_com) return fail(h, CMDGEN_ESTATE, "inpainting is not supported for no_com_projection handles (SimpleConditionalDDPM)");
+    if (K < 1 || K > h->cfg.timesteps) return fail(h, CMDGEN_EINVAL, "timesteps=%d must be in [1, %d]", K, h->cfg.timesteps);
+    if (resamplings < 1 || jump < 1) return fail(h, CMDGEN_EINVAL, "resamplings and jump_length must be >= 1");
+    return 0;
+}
+
+extern "C" int cmdgen_inpaint_plan(cmdgen_handle* h, int32_t timesteps, int32_t resamplings, int32_t jump_length,
+                                   int64_t* n_steps, int64_t* n_draws) {
+    if (!h) return CMDGEN_EINVAL;
+    if (!h->finalized) return fail(h, CMDGEN_ESTATE, "weights not finalised (cmdgen_finalize_weights)");
+    int rc = check_inpaint_args(h, timesteps, resamplings, jump_length); if (rc) return rc;
+    const InpaintPlan p = build_inpaint_plan(h, timesteps, resamplings, jump_length);
+    if (n_steps) *n_steps = p.n_steps;
+    if (n_draws) *n_draws = p.n_draws;
+    return CMDGEN_OK;
+}
+
+// buffers of the inpainting chain for the current layout, and the plan's tables (re-uploaded only when they change)
+static int prepare_inpaint(cmdgen_handle* h, const InpaintPlan& p) {
+    std::vector<float> tables(p.coef);
+    tables.insert(tables.end(), p.coef2.begin(), p.coef2.end());
+    for (int v : p.iop) { float f; memcpy(&f, &v, 4); tables.push_back(f); }
+    if (h->inp_steps >= 0 && tables.size() == h->inp_tables.size() &&
+        memcmp(tables.data(), h->inp_tables.data(), tables.size() * sizeof(float)) == 0)
+        return 0;
+    hipDeviceSynchronize();
+    if (h->inpaint_graph) { hipGraphExecDestroy(h->inpaint_graph); h->inpaint_graph = nullptr; }
+    free_pool(h->inp_allocs);
+    h->inp_steps = -1;
+    const Dims& d = h->dims;
+    const Layout& L = h->lay;
+    void* q; int rc;
+    auto up = [&](const void* src, size_t bytes) -> void* {
+        if (dev_alloc(h, h->inp_allocs, &q, bytes, false)) return nullptr;
+        if (hipMemcpy(q, src, bytes, hipMemcpyHostToDevice) != hipSuccess) { fail(h, CMDGEN_EHIP, "hipMemcpy H2D failed"); return nullptr; }
+        return q;
+    };
+    ChainBuf& c = h->inp_chain;
+    InpaintBuf& ip = h->inp;
+    if (!(c.coef = (const float4*)up(p.coef.data(), p.coef.size() * sizeof(float)))) return CMDGEN_EHIP;
+    if (!(ip.coef2 = (const float4*)up(p.coef2.data(), p.coef2.size() * sizeof(float)))) return CMDGEN_EHIP;
+    if (!(ip.iop = (const int4*)up(p.iop.data(), p.iop.size() * sizeof(int)))) return CMDGEN_EHIP;
+#define IALLOC(dst, type, bytes) do { rc = dev_alloc(h, h->inp_allocs, &q, bytes, true); if (rc) return rc; dst = (type)q; } while (0)
+    const size_t nl_ = (size_t)L.Nl * (3 + d.P) * sizeof(float);
+    IALLOC(c.z_phar, float*, nl_);
+    IALLOC(c.xh_pocket, float*, (size_t)L.Np * (3 + d.R) * sizeof(float));
+    IALLOC(c.check, unsigned int*, (size_t)(p.n_steps + 3) * 2 * sizeof(unsigned int));
+    IALLOC(c.state, ChainState*, sizeof(ChainState));
+    IALLOC(h->inp_cog, unsigned int*, 4 * sizeof(unsigned int));
+    IALLOC(ip.known, const float*, nl_);
+    IALLOC(ip.fix, float*, (size_t)L.Nl * sizeof(float));
+    IALLOC(ip.poff, float4*, (size_t)L.B * sizeof(float4));
+    for (int i = 0; i < 3; ++i) IALLOC(h->inp_pk[i], float*, (size_t)L.Np * d.H * sizeof(float));      // PocketCache c, P0, Q0
+    for (int i = 3; i < 6; ++i) IALLOC(h->inp_pk[i], float*, (size_t)d.H * sizeof(float));             // dh, dP, dQ
+#undef IALLOC
+    std::vector<float> t01((size_t)2 * L.B, 0.f);
+    for (int b = 0; b < L.B; ++b) t01[L.B + b] = 1.f;
+    if (!(h->inp_pk[6] = (float*)up(t01.data(), t01.size() * sizeof(float)))) return CMDGEN_EHIP;
+    ip.n_steps = p.n_steps;
+    h->inp_steps = p.n_steps;
+    h->inp_tables.swap(tables);
+    return 0;
+}
+
+extern "C" int cmdgen_inpaint_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
+                                    const float* phar_x, const float* phar_onehot, const float* phar_fixed,
+                                    int32_t timesteps, int32_t resamplings, int32_t jump_length,
+                                    const float* noise, int64_t n_draws, uint64_t seed, const int64_t* pocket_ids_host,
+                                    float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                                    int32_t use_graph, cmdgen_stream stream) {
+    int rc = check_ready(h); if (rc) return rc;
+    rc = check_inpaint_args(h, timesteps, resamplings, jump_length); if (rc) return rc;
+    if (!pocket_x || !pocket_onehot || !phar_x || !phar_onehot || !phar_fixed || !xh_phar_out || !xh_pocket_out)
+        return fail(h, CMDGEN_EINVAL, "null device pointer");
+    const InpaintPlan plan = build_inpaint_plan(h, timesteps, resamplings, jump_length);
+    if (noise && n_draws < plan.n_draws)
+        return fail(h, CMDGEN_EINVAL, "noise holds %lld draws, the schedule needs %lld", (long long)n_draws, (long long)plan.n_draws);
+    hipSetDevice(h->device);
+    hipStream_t caller = (hipStream_t)stream;
+    hipStream_t s = caller;
+    if (use_graph && caller == nullptr) {       // as cmdgen_sample_chain: the legacy default stream cannot be captured
+        if (!h->own_stream) {
+            HIPCHK(h, hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
+            HIPCHK(h, hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
+            HIPCHK(h, hipEventCreateWithFlags(&h->ev_out, hipEventDisableTiming));
+        }
+        HIPCHK(h, hipEventRecord(h->ev_in, caller));
+        HIPCHK(h, hipStreamWaitEvent(h->own_stream, h->ev_in, 0));
+        s = h->own_stream;
+    }
+    rc = prepare_inpaint(h, plan); if (rc) return rc;
+    rc = begin_work(h, s); if (rc) return rc;
+    h->last_stream = caller;
+    h->last_chain_joint = false; h->last_chain_inpaint = true;
+    const Dims& d = h->dims;
+    const int n_steps = plan.n_steps;
+    {
+        std::vector<int64_t> gid(h->lay.B);
+        for (int b = 0; b < h->lay.B; ++b) gid[b] = pocket_ids_host ? pocket_ids_host[b] : b;
+        HIPCHK(h, hipMemcpyAsync(h->d_gid, gid.data(), gid.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipStreamSynchronize(s));          // gid is a stack vector
+    }
+    ChainBuf c = h->inp_chain;
+    c.noise = noise; c.seed = seed; c.z_steps = z_steps_out; c.pocket_steps = pocket_steps_out;
+    const InpaintBuf ip = h->inp;
+    const ChainState st0{0, n_steps, 0, 0};
+    HIPCHK(h, hipMemcpyAsync(c.state, &st0, sizeof st0, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemsetAsync(c.check, 0, (size_t)(n_steps + 3) * 2 * sizeof(unsigned int), s));
+    HIPCHK(h, hipMemsetAsync(h->inp_cog, 0, 4 * sizeof(unsigned int), s));
+    HIPCHK(h, hipStreamSynchronize(s));              // st0 is on the stack
+    EvalLaunch a = make_launch(h);
+    ++h->eval_gen;
+    if (h->kernel_profiling && !use_graph) a.prof_events = h->prof_events;
+    cmdgen_launch_chain_init(h->lay, d, c, pocket_x, pocket_onehot, s);
+    cmdgen_launch_inpaint_prep(h->lay, d, c, ip, phar_x, phar_onehot, phar_fixed, pocket_x, s);
+    if (opt_of(h, "pocket_cache", 1) != 0 && h->lay.Np > 0) {
+        float* const* k = h->inp_pk;
+        cmdgen_build_pocket_cache(a, c.z_phar, c.xh_pocket, k[6], k[0], k[1], k[2], k[3], k[4], k[5], s);
+        a.pcache = PocketCache{k[0], k[1], k[2], k[3], k[4], k[5]};
+    }
+    EvalLaunch a2 = a;
+    a2.skip_count = 1;                               // k_inpaint_step_count ran pass 1 of the graph
+    cmdgen_launch_eval(a, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, s, nullptr);   // evaluation 0 (t = 1)
+    auto one_step = [&](hipStream_t ss) {
+        cmdgen_launch_inpaint_step_count(h->lay, d, c, ip, h->work, h->work.eps_tmp, ss);
+        cmdgen_launch_eval(a2, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, ss, nullptr);
+    };
+    if (use_graph) {
+        // a graph of its own (the plain chain's step_graph stays valid); the op index lives on the device, so G captured
+        // ops replay anywhere in the schedule.  The tables, the known rows and the mask are handle buffers: a new plan
+        // re-instantiates it (prepare_inpaint), the caller's pointers below are its key.
+        const void* key[4] = {noise, z_steps_out, pocket_steps_out, (const void*)s};
+        int G = (int)opt_of(h, "graph_steps", 8);
+        if (G < 1) G = 1;
+        if (G > n_steps) G = n_steps;
+        if (h->inpaint_graph && (memcmp(key, h->ig_key, sizeof key) != 0 || h->ig_seed != seed || h->ig_steps != G)) {
+            hipGraphExecDestroy(h->inpaint_graph); h->inpaint_graph = nullptr;
+        }
+        if (!h->inpaint_graph) {
+            hipGraph_t g = nullptr;
+            HIPCHK(h, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+            for (int i = 0; i < G; ++i) one_step(s);
+            HIPCHK(h, hipStreamEndCapture(s, &g));
+            HIPCHK(h, hipGraphInstantiate(&h->inpaint_graph, g, nullptr, nullptr, 0));
+            hipGraphDestroy(g);
+            memcpy(h->ig_key, key, sizeof key); h->ig_seed = seed; h->ig_steps = G;
+        }
+        for (int i = 0; i < n_steps / G; ++i) HIPCHK(h, hipGraphLaunch(h->inpaint_graph, s));
+        for (int i = 0; i < n_steps % G; ++i) one_step(s);
+    } else {
+        for (int i = 0; i < n_steps; ++i) one_step(s);
+    }
+    // decode: k_chain_final reads its draw from row 1 + K of `noise` (K = n_steps here); the decode draw is the plan's last row
+    ChainBuf cf = c;
+    if (noise) cf.noise = noise + (size_t)(plan.n_draws - 1 - (1 + n_steps)) * h->lay.Nl * (3 + d.P);
+    cmdgen_launch_chain_final(h->lay, d, cf, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, h->inp_cog, s);
+    HIPCHK(h, hipGetLastError());
+    if (s != caller) {
+        HIPCHK(h, hipEventRecord(h->ev_out, s));
+        HIPCHK(h, hipStreamWaitEvent(caller, h->ev_out, 0));
+    }
+    return CMDGEN_OK;
+}
+
 extern "C" int cmdgen_chain_status(cmdgen_handle* h, float* max_rel, float* max_cog, int64_t* nan_resets, cmdgen_stream stream) {
     int rc = check_ready(h); if (rc) return rc;
-    if (h->last_chain_joint ? h->joint_steps < 0 : h->chain_K < 0) return fail(h, CMDGEN_ESTATE, "no chain has run");
+    const int K = h->last_chain_inpaint ? h->inp_steps : h->last_chain_joint ? h->joint_steps : h->chain_K;
+    if (K < 0) return fail(h, CMDGEN_ESTATE, "no chain has run");
+    const unsigned int* check = h->last_chain_inpaint ? h->inp_chain.check : h->last_chain_joint ? h->joint.check : h->chain.check;
+    const unsigned int* cog_slot = h->last_chain_inpaint ? h->inp_cog : h->last_chain_joint ? h->joint_cog : h->d_cog;
     hipSetDevice(h->device);
     HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
-    const int K = h->last_chain_joint ? h->joint_steps : h->chain_K;
     std::vector<unsigned int> chk((size_t)(K + 3) * 2);
-    HIPCHK(h, hipMemcpy(chk.data(), h->last_chain_joint ? h->joint.check : h->chain.check, chk.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(chk.data(), check, chk.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
     float worst = 0.f;
     for (int i = 0; i < K + 2 && worst == worst; ++i) {
         float largest, err;
@@ -1306,7 +1531,7 @@ extern "C" int cmdgen_chain_status(cmdgen_handle* h, float* max_rel, float* max_
         if (rel > worst || rel != rel) worst = rel;      // a NaN sticks: the reference's `assert rel_error < 1e-2` fails on it
     }
     if (max_rel) *max_rel = worst;
-    unsigned int cog; HIPCHK(h, hipMemcpy(&cog, h->last_chain_joint ? h->joint_cog : h->d_cog, 4, hipMemcpyDeviceToHost));
+    unsigned int cog; HIPCHK(h, hipMemcpy(&cog, cog_slot, 4, hipMemcpyDeviceToHost));
     if (max_cog) memcpy(max_cog, &cog, 4);
     unsigned long long cnt[8];
     HIPCHK(h, hipMemcpy(cnt, h->work.counters, sizeof cnt, hipMemcpyDeviceToHost));

@@ -78,6 +78,18 @@ struct cmdgen_handle {
     hipGraphExec_t joint_graph = nullptr;
     const void* jg_key[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     unsigned long long jg_seed = 0; int jg_steps = 0;
+    // conditional RePaint chain (cmdgen_inpaint_chain): buffers of its own, so plain and inpainting chains can alternate on a handle
+    std::vector<void*> inp_allocs;
+    ChainBuf inp_chain{};                  // z, pocket, op tables' posterior rows (coef), checks and state of the inpainting chain
+    InpaintBuf inp{};
+    unsigned int* inp_cog = nullptr;
+    float* inp_pk[7] = {};                 // its PocketCache storage (c, P0, Q0, dh, dP, dQ) and the pinned time pair
+    int inp_steps = -1;                    // ops of the prepared plan (-1: nothing prepared)
+    std::vector<float> inp_tables;         // the uploaded tables (coef | coef2 | iop bits), compared to decide a re-upload
+    bool last_chain_inpaint = false;
+    hipGraphExec_t inpaint_graph = nullptr;
+    const void* ig_key[4] = {nullptr, nullptr, nullptr, nullptr};
+    unsigned long long ig_seed = 0; int ig_steps = 0;
     TrainState* train = nullptr;           // training workspace (cmdgen_train.hip)
     float* h_norm = nullptr; hipEvent_t norm_ev = nullptr; bool norm_pending = false;   // deferred gradient-norm readback (pinned host float)
     int train_E = 0, train_Ec = 0;         // message / coordinate edges of the last cmdgen_train_forward (cmdgen_query)

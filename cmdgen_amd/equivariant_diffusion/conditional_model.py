@@ -208,6 +208,98 @@ class ConditionalDDPM(EnVariationalDiffusion):
         return out_phar, out_pocket, phar_mask, pocket['mask']
 
 
+    @torch.no_grad()
+    def inpaint(self, phar, pocket, phar_fixed, resamplings=1, jump_length=1, return_frames=1, timesteps=None,
+                noise=None, seed=None, pocket_ids=None):
+        """Sample given pockets while holding some pharmacophore points: RePaint (the joint model's loop,
+        en_diffusion.py:672-831) on this model's own steps.  An op of get_repaint_schedule(resamplings, jump_length,
+        timesteps) is sample_p_zs_given_zt, then the given rows noised to the op's s by q(z_s | x) and moved into the
+        current frame by the pocket's shift replace the fixed rows, then the phar COM projection; before a jump back,
+        sample_p_zt_given_zs re-noises.  The frame is the one of sample_given_pocket (phar COM at zero, the pocket a
+        translated copy); both inputs are normalised here (unlike the joint model's inpaint, quirk Q14).
+        The whole chain runs on the device (cmdgen_inpaint_chain; its header gives the op and the draw layout).
+
+        phar: dict(x [Nl,3], one_hot [Nl,P], size [B], mask [Nl]) - only rows with phar_fixed set are read;
+        pocket: as in sample_given_pocket; phar_fixed: [Nl] or [Nl,1] floats or bools.
+        noise [n_draws, Nl, 3+P] (Handle.inpaint_plan), seed and pocket_ids as in sample_given_pocket.
+        Returns (xh_phar, xh_pocket, phar_mask, pocket_mask) like sample_given_pocket; with return_frames > 1
+        (jump_length 1 only) the frames are the states at the end of each resample cycle, frame 0 the final sample.
+        """
+        timesteps = self.T if timesteps is None else timesteps
+        assert 0 < return_frames <= timesteps
+        assert timesteps % return_frames == 0
+        if return_frames > 1 and jump_length != 1:
+            raise ValueError('return_frames > 1 is only implemented for jump_length=1 (as in the joint model\'s inpaint)')
+        device = pocket['x'].device
+        n_samples = len(pocket['size'])
+        sizes = pocket['size'].detach().to('cpu', torch.int64).numpy()
+        nph = phar['size'].detach().to('cpu', torch.int64).numpy()
+        if len(nph) != n_samples:
+            raise ValueError(f'phar has {len(nph)} samples, pocket {n_samples}')
+        for m in (phar['mask'], pocket['mask']):
+            if m.numel() > 1 and bool((m[1:] < m[:-1]).any()):
+                raise ValueError('batch masks must be ascending and contiguous')
+        n_phar = int(nph.sum())
+        fixed = torch.as_tensor(phar_fixed).detach().to(device, torch.float32)
+        if fixed.dim() == 2 and fixed.shape[1] == 1:
+            fixed = fixed[:, 0]
+        if fixed.dim() != 1 or fixed.numel() != n_phar:
+            raise ValueError(f'phar_fixed has shape {tuple(torch.as_tensor(phar_fixed).shape)}: expected [{n_phar}] or [{n_phar}, 1]')
+        self.refresh_learned_schedule()
+        h = self.dynamics.hip_handle()
+        h.set_layout(nph, sizes)
+        h.set_step_table(timesteps, self.step_table(timesteps))
+        n_steps, n_draws = h.inpaint_plan(timesteps, resamplings, jump_length)
+        f32 = lambda t: t.detach().to(device, torch.float32).contiguous()
+        if noise is not None:
+            noise = f32(noise)
+            if noise.dim() != 3 or noise.shape[0] < n_draws:
+                raise ValueError(f'noise has shape {tuple(noise.shape)}: this schedule needs {n_draws} draws of [{n_phar}, {3 + self.phar_nf}]')
+        if seed is None:
+            seed = fresh_seed()
+        phar_mask = utils.num_nodes_to_batch_mask(n_samples, torch.as_tensor(nph), device)
+        args = (f32(pocket['x']), f32(pocket['one_hot']), f32(phar['x']), f32(phar['one_hot']), fixed.contiguous())
+        want_steps = return_frames > 1
+        (xh_phar, xh_pocket, z_steps), st = h.run_range_guarded(
+            lambda: h.inpaint_chain(*args, timesteps, resamplings=resamplings, jump_length=jump_length, noise=noise, seed=seed,
+                                    pocket_ids=pocket_ids, want_steps=want_steps, use_graph=self.use_hip_graph),
+            h.chain_status)
+        self.last_chain_status = st
+        assert st['max_rel_com_error'] < 1e-2, f"Mean is not zero, relative_error {st['max_rel_com_error']}"
+        if st['nan_resets']:
+            print('Warning: detected nan, resetting EGNN output to zero.')
+        if st['max_cog'] > 5e-2 and return_frames == 1:
+            print(f"Warning CoG drift with error {st['max_cog']:.3f}. Projecting the positions down.")
+        if return_frames == 1:
+            return xh_phar, xh_pocket, phar_mask, pocket['mask']
+        out_phar = torch.zeros((return_frames,) + tuple(xh_phar.shape), device=device)
+        out_pocket = torch.zeros((return_frames,) + tuple(xh_pocket.shape), device=device)
+        p_steps = h.last_pocket_steps
+        nd = self.n_dims
+        for step, idx in self.inpaint_frames(resamplings, jump_length, timesteps, return_frames):
+            zs, ps = z_steps[step], p_steps[step]
+            out_phar[idx] = torch.cat([zs[:, :nd] * self.norm_values[0],
+                                       zs[:, nd:] * self.norm_values[1] + self.norm_biases[1]], dim=1)
+            out_pocket[idx] = torch.cat([ps * self.norm_values[0], xh_pocket[:, nd:]], dim=1)
+        out_phar[0], out_pocket[0] = xh_phar, xh_pocket
+        return out_phar, out_pocket, phar_mask, pocket['mask']
+
+    def inpaint_frames(self, resamplings, jump_length, timesteps, return_frames):
+        """[(op index, frame index)]: the ops after which inpaint records a frame - the schedule walked as
+        en_diffusion.py:723-813 do, a frame at the end of a resample cycle whose s falls on the frame grid."""
+        schedule = self.get_repaint_schedule(resamplings, jump_length, timesteps)
+        frames, s, step = [], timesteps - 1, 0
+        for i, n_denoise_steps in enumerate(schedule):
+            for j in range(n_denoise_steps):
+                if (n_denoise_steps > jump_length or i == len(schedule) - 1) and (s * return_frames) % timesteps == 0:
+                    frames.append((step, (s * return_frames) // timesteps))
+                if j == n_denoise_steps - 1 and i < len(schedule) - 1:
+                    s = s + jump_length
+                s -= 1
+                step += 1
+        return frames
+
+
 class SimpleConditionalDDPM(ConditionalDDPM):
     """The same model without the subspace trick (conditional_model.py:481-525): the context (pocket) is
     centred once and samples are not projected to the COM-free subspace; translation equivariance comes from
@@ -243,3 +335,7 @@ class SimpleConditionalDDPM(ConditionalDDPM):
         return super().forward(phar, pocket, return_info, t_int=t_int, eps=eps, _net=_net)
 
     # sample_given_pocket: the library centres the pocket itself when no_com_projection is set
+
+    def inpaint(self, *args, **kwargs):
+        raise NotImplementedError('inpainting is not implemented for SimpleConditionalDDPM (no centre-of-mass projection); '
+                                  'use ConditionalDDPM')

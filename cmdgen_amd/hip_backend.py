@@ -61,6 +61,9 @@ SYMBOLS = [
     ('cmdgen_joint_chain', C.c_int, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int64,
                                      C.c_uint64, _i64p, _fp, _fp, _fp, C.c_int32, _vp]),
     ('cmdgen_joint_plan', C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i64p, _i64p]),
+    ('cmdgen_inpaint_plan', C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _i64p, _i64p]),
+    ('cmdgen_inpaint_chain', C.c_int, [_vp, _fp, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int64,
+                                       C.c_uint64, _i64p, _fp, _fp, _fp, _fp, C.c_int32, _vp]),
     ('cmdgen_param_count', C.c_int, [_vp, _i64p]),
     ('cmdgen_param_offset', C.c_int, [_vp, C.c_char_p, _i64p, _i64p]),
     ('cmdgen_train_forward', C.c_int, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),
@@ -370,6 +373,45 @@ class Handle:
             int(noise.shape[0]) if noise is not None else 0, C.c_uint64(seed & (2 ** 64 - 1)),
             ids.ctypes.data_as(_i64p) if ids is not None else None, _ptr(xh_phar), _ptr(xh_pocket), _ptr(z_steps),
             int(bool(use_graph)), self._stream()), 'cmdgen_joint_chain')
+        return xh_phar, xh_pocket, z_steps
+
+    def inpaint_plan(self, timesteps: int, resamplings: int = 1, jump_length: int = 1):
+        """(denoising ops, noise draws) of a conditional inpainting chain (cmdgen_inpaint_plan)."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._check(self.lib.cmdgen_inpaint_plan(self.h, int(timesteps), int(resamplings), int(jump_length), C.byref(a), C.byref(b)),
+                    'cmdgen_inpaint_plan')
+        return a.value, b.value
+
+    def inpaint_chain(self, pocket_x, pocket_onehot, phar_x, phar_onehot, phar_fixed, timesteps: int, resamplings: int = 1,
+                      jump_length: int = 1, noise=None, seed: int = 0, pocket_ids: Optional[Sequence[int]] = None,
+                      want_steps: bool = False, use_graph: bool = True):
+        """ConditionalDDPM.inpaint on the device (cmdgen_inpaint_chain).  Raw pocket_x [Np,3], pocket_onehot [Np,R], phar_x [Nl,3],
+        phar_onehot [Nl,P] and phar_fixed float [Nl] device tensors; noise [n_draws, Nl, 3+P] or None.  -> (xh_phar, xh_pocket, z_steps);
+        with want_steps the pocket after every op is left in last_pocket_steps, as sample_chain does."""
+        import torch
+        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
+        shapes = [(self.n_pocket, 3), (self.n_pocket, R), (self.n_phar, 3), (self.n_phar, P), (self.n_phar,)]
+        for t, sh in zip((pocket_x, pocket_onehot, phar_x, phar_onehot, phar_fixed), shapes):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == sh, (tuple(t.shape), sh)
+        n_steps, n_draws = self.inpaint_plan(timesteps, resamplings, jump_length)
+        if noise is not None:
+            assert noise.is_cuda and noise.dtype == torch.float32 and noise.is_contiguous()
+            assert noise.dim() == 3 and tuple(noise.shape[1:]) == (self.n_phar, 3 + P), noise.shape
+        dev = pocket_x.device
+        xh_phar = torch.empty((self.n_phar, 3 + P), dtype=torch.float32, device=dev)
+        xh_pocket = torch.empty((self.n_pocket, 3 + R), dtype=torch.float32, device=dev)
+        z_steps = torch.empty((n_steps, self.n_phar, 3 + P), dtype=torch.float32, device=dev) if want_steps else None
+        p_steps = torch.empty((n_steps, self.n_pocket, 3), dtype=torch.float32, device=dev) if want_steps else None
+        self.last_pocket_steps = p_steps
+        ids = None
+        if pocket_ids is not None:
+            ids = np.ascontiguousarray(np.asarray(pocket_ids, dtype=np.int64))
+            assert len(ids) == self.batch
+        self._check(self.lib.cmdgen_inpaint_chain(
+            self.h, _ptr(pocket_x), _ptr(pocket_onehot), _ptr(phar_x), _ptr(phar_onehot), _ptr(phar_fixed), int(timesteps),
+            int(resamplings), int(jump_length), _ptr(noise), int(noise.shape[0]) if noise is not None else 0,
+            C.c_uint64(seed & (2 ** 64 - 1)), ids.ctypes.data_as(_i64p) if ids is not None else None, _ptr(xh_phar),
+            _ptr(xh_pocket), _ptr(z_steps), _ptr(p_steps), int(bool(use_graph)), self._stream()), 'cmdgen_inpaint_chain')
         return xh_phar, xh_pocket, z_steps
 
     # ---- training step (flat parameter / gradient buffers are torch tensors owned by the caller)

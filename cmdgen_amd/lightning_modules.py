@@ -266,16 +266,9 @@ class PharPocketDDPM(nn.Module):
         pm = phar_mask.cpu()
         return list(zip(utils.batch_to_list(x, pm), utils.batch_to_list(phar_type, pm)))
 
-    def generate_phars(self, pdb_file, n_samples, pocket_ids=None, ref_ligand=None, num_nodes_phar=None,
-                       sanitize=False, largest_frag=False, relax_iter=0, timesteps=None, **kwargs):
-        """Generate pharmacophore point clouds inside a pocket (lightning_modules.py:385-541).
-
-        pocket_ids: residues as '<chain>:<resi>'; ref_ligand: '<chain>:<resi>' alternative.
-        sanitize / largest_frag / relax_iter and the inpainting kwargs are accepted and have no
-        effect in conditional mode, as in the reference (quirk Q10); in mode 'joint' the kwargs
-        (resamplings, jump_length) go to EnVariationalDiffusion.inpaint (lightning_modules.py:466-486)."""
-        assert (pocket_ids is None) ^ (ref_ligand is None)
-        sampler_kw = {k: kwargs.pop(k) for k in ('noise', 'seed') if k in kwargs}
+    def _pdb_pocket(self, pdb_file, n_samples, pocket_ids, ref_ligand):
+        """The pocket of a PDB file (residues '<chain>:<resi>' or those around ref_ligand), repeated n_samples times as a
+        batch dict (lightning_modules.py:400-441)."""
         pdb_struct = utils.parse_pdb(pdb_file)
         if pocket_ids is not None:
             residues = [pdb_struct[x.split(':')[0]][(' ', int(x.split(':')[1]), ' ')] for x in pocket_ids]
@@ -298,6 +291,19 @@ class PharPocketDDPM(nn.Module):
                                               len(pocket_coord))
         pocket = {'x': pocket_coord.repeat(n_samples, 1), 'one_hot': pocket_one_hot.repeat(n_samples, 1),
                   'size': pocket_size, 'mask': pocket_mask}
+        return pocket
+
+    def generate_phars(self, pdb_file, n_samples, pocket_ids=None, ref_ligand=None, num_nodes_phar=None,
+                       sanitize=False, largest_frag=False, relax_iter=0, timesteps=None, **kwargs):
+        """Generate pharmacophore point clouds inside a pocket (lightning_modules.py:385-541).
+
+        pocket_ids: residues as '<chain>:<resi>'; ref_ligand: '<chain>:<resi>' alternative.
+        sanitize / largest_frag / relax_iter and the inpainting kwargs are accepted and have no
+        effect in conditional mode, as in the reference (quirk Q10); in mode 'joint' the kwargs
+        (resamplings, jump_length) go to EnVariationalDiffusion.inpaint (lightning_modules.py:466-486)."""
+        assert (pocket_ids is None) ^ (ref_ligand is None)
+        sampler_kw = {k: kwargs.pop(k) for k in ('noise', 'seed') if k in kwargs}
+        pocket = self._pdb_pocket(pdb_file, n_samples, pocket_ids, ref_ligand)
         pocket_com_before = _scatter_mean(pocket['x'], pocket['mask'], n_samples)
         if num_nodes_phar is None:
             num_nodes_phar = self.ddpm.size_distribution.sample_conditional(n1=None, n2=pocket['size'])
@@ -329,6 +335,61 @@ class PharPocketDDPM(nn.Module):
         phar_to_coords = {}
         for coords_batch, types in zip(utils.batch_to_list(x, phar_mask), utils.batch_to_list(phar_type, phar_mask)):
             names = [self.dataset_info['phar_decoder'][int(t)] for t in types]
+            for k, (name, coords) in enumerate(zip(names, coords_batch), start=1):
+                phar_to_coords.setdefault(f'Molecule_{k}', {}).setdefault(name, []).append(coords)
+        return phar_to_coords
+
+    def inpaint_phars(self, pdb_file, n_samples, fixed_phars, pocket_ids=None, ref_ligand=None, num_nodes_phar=None,
+                      timesteps=None, resamplings=1, jump_length=1, seed=None):
+        """Generate pharmacophores inside a pocket around given points (ConditionalDDPM.inpaint).
+
+        fixed_phars: [(type name of dataset_info['phar_decoder'], (x, y, z) in Angstrom in the PDB's frame)]; they are the
+        first rows of every sample.  num_nodes_phar: points per sample, default the size prior given the pocket, at least
+        len(fixed_phars).  The pocket, the output format and the move back to the pocket's position are generate_phars'."""
+        assert (pocket_ids is None) ^ (ref_ligand is None)
+        if not isinstance(self.ddpm, ConditionalDDPM):
+            raise NotImplementedError('inpaint_phars needs the conditional model (mode pocket_conditioning)')
+        n_fix = len(fixed_phars)
+        decoder = list(self.dataset_info['phar_decoder'])
+        for name, _ in fixed_phars:
+            if name not in decoder:
+                raise ValueError(f'unknown pharmacophore type {name!r}: expected one of {decoder}')
+        pocket = self._pdb_pocket(pdb_file, n_samples, pocket_ids, ref_ligand)
+        pocket_com_before = _scatter_mean(pocket['x'], pocket['mask'], n_samples)
+        if num_nodes_phar is None:
+            num_nodes_phar = self.ddpm.size_distribution.sample_conditional(n1=None, n2=pocket['size'])
+            num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device).clamp(min=n_fix)
+        else:
+            num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device).reshape(-1)
+            if num_nodes_phar.numel() == 1:
+                num_nodes_phar = num_nodes_phar.expand(n_samples)
+            if bool((num_nodes_phar < n_fix).any()):
+                raise ValueError(f'num_nodes_phar must be at least len(fixed_phars) = {n_fix}')
+        num_nodes_phar = num_nodes_phar.to(INT_TYPE)
+        phar_mask = utils.num_nodes_to_batch_mask(n_samples, num_nodes_phar, self.device)
+        first = torch.cumsum(num_nodes_phar, 0) - num_nodes_phar                 # first row of every sample
+        rows = (first[:, None] + torch.arange(n_fix, device=self.device)[None, :]).reshape(-1)
+        fx = torch.tensor([list(map(float, xyz)) for _, xyz in fixed_phars], device=self.device, dtype=FLOAT_TYPE).reshape(n_fix, 3)
+        ft = torch.tensor([decoder.index(name) for name, _ in fixed_phars], device=self.device, dtype=torch.int64)
+        x = torch.zeros((len(phar_mask), self.x_dims), device=self.device, dtype=FLOAT_TYPE)
+        one_hot = torch.zeros((len(phar_mask), self.phar_nf), device=self.device, dtype=FLOAT_TYPE)
+        fixed = torch.zeros(len(phar_mask), device=self.device, dtype=FLOAT_TYPE)
+        x[rows] = fx.repeat(n_samples, 1)
+        one_hot[rows] = F.one_hot(ft, self.phar_nf).to(FLOAT_TYPE).repeat(n_samples, 1)
+        fixed[rows] = 1.0
+        phar = {'x': x, 'one_hot': one_hot, 'size': num_nodes_phar, 'mask': phar_mask}
+        xh_phar, xh_pocket, phar_mask, pocket_mask = self.ddpm.inpaint(
+            phar, pocket, fixed, resamplings=resamplings, jump_length=jump_length, timesteps=timesteps, seed=seed)
+        # move the generated points back to the original pocket position (as generate_phars)
+        pocket_com_after = _scatter_mean(xh_pocket[:, :self.x_dims], pocket_mask, n_samples)
+        xh_pocket[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[pocket_mask]
+        xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
+        phar_mask = phar_mask.cpu()
+        x = xh_phar[:, :self.x_dims].detach().cpu()
+        phar_type = xh_phar[:, self.x_dims:].argmax(1).detach().cpu()
+        phar_to_coords = {}
+        for coords_batch, types in zip(utils.batch_to_list(x, phar_mask), utils.batch_to_list(phar_type, phar_mask)):
+            names = [decoder[int(t)] for t in types]
             for k, (name, coords) in enumerate(zip(names, coords_batch), start=1):
                 phar_to_coords.setdefault(f'Molecule_{k}', {}).setdefault(name, []).append(coords)
         return phar_to_coords

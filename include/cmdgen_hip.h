@@ -243,6 +243,36 @@ int cmdgen_joint_chain(cmdgen_handle* h, const float* phar_x, const float* phar_
 int cmdgen_joint_plan(cmdgen_handle* h, int32_t timesteps, int32_t resamplings, int32_t jump_length,
                       int32_t inpaint, int64_t* n_steps, int64_t* n_draws);
 
+/* RePaint for the CONDITIONAL model (ConditionalDDPM.inpaint): sample_given_pocket's chain with the rows of phar_fixed
+ * held at a noised copy of the given rows.  The schedule is get_repaint_schedule(resamplings, jump_length, timesteps)
+ * (en_diffusion.py:649-670), walked as en_diffusion.py:723-813 do; one op going from t to s, in the normalised space:
+ *   A  (z_u, P_u) = sample_p_zs_given_zt(s, t, z, P)                                 (conditional_model.py:342-374)
+ *   B  z_k = alpha_s K + sigma_s eps_B over all phar rows; z_k.x += com(P_u) - com(P0) per sample;
+ *      z = phar_fixed ? z_k : z_u; (z.x, P.x) = remove_mean_batch(z.x, P_u.x)        (skipped for a sample with no fixed row)
+ *   C  after the last op before a jump back: (z, P) = sample_p_zt_given_zs(z, P, gamma(s + jump_length), gamma(s))
+ * K = the normalised phar input rows, P0 = the normalised input pocket, P = its translated copy (the phar COM stays at 0).
+ * z_T and the final decode (with the CoG-drift projection) are sample_given_pocket's.  With resamplings = jump_length = 1
+ * a sample without fixed rows follows cmdgen_sample_chain's trajectory bit for bit (same seed, device draws).
+ *   pocket_x, pocket_onehot      as cmdgen_sample_chain (raw; normalised on the device)
+ *   phar_x dev [Nl,3], phar_onehot dev [Nl,phar_nf]: raw input phar rows (only fixed rows are read)
+ *   phar_fixed dev [Nl]: nonzero = fixed row
+ *   noise  dev [n_draws][Nl][3+phar_nf] or NULL, in call order: draw 0 (z_T); per op draw A, draw B, and draw C if the op
+ *          jumps back; the decode draw.  n_draws = 2 + 2 n_steps + n_jumps (cmdgen_inpaint_plan); fewer rows are refused.
+ *   Device draws (noise == NULL): Philox keyed by (seed, global pocket id) as cmdgen_sample_chain, with the draw counter
+ *          z_T: 0, A of op i: 1 + i, decode: 1 + n_steps, B of op i: 2 + n_steps + i, C of op i: 2 + 2 n_steps + i.
+ *   outputs as cmdgen_sample_chain; z_steps_out [n_steps][Nl][3+phar_nf] and pocket_steps_out [n_steps][Np][3] hold z and
+ *          P after step B of every op (before a jump back).
+ * The joint model (use cmdgen_joint_chain) and no_com_projection handles (SimpleConditionalDDPM) are refused.
+ * Asynchronous on `stream`; cmdgen_chain_status reports this run's checks, drift and NaN resets. */
+int cmdgen_inpaint_plan(cmdgen_handle* h, int32_t timesteps, int32_t resamplings, int32_t jump_length,
+                        int64_t* n_steps, int64_t* n_draws);
+int cmdgen_inpaint_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
+                         const float* phar_x, const float* phar_onehot, const float* phar_fixed,
+                         int32_t timesteps, int32_t resamplings, int32_t jump_length,
+                         const float* noise, int64_t n_draws, uint64_t seed, const int64_t* pocket_ids_host,
+                         float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                         int32_t use_graph, cmdgen_stream stream);
+
 /* ---- training step (conditional model) -------------------------------------------------- */
 /* The trainable tensors of EGNNDynamics live in ONE flat fp32 device buffer owned by the caller, in the
  * reference's registration order (the state_dict order below 'ddpm.dynamics.': weight then bias of every
