@@ -25,8 +25,6 @@ void cmdgen_build_pocket_cache(const EvalLaunch& a, const float* xh_phar, const 
 void cmdgen_launch_edge_msg_only(const EvalLaunch& a, int layer, hipStream_t s);
 void cmdgen_launch_chain_init(const Layout& lay, const Dims& d, const ChainBuf& c, const float* px,
                               const float* poh, hipStream_t s);
-void cmdgen_launch_ddpm_step(const Layout& lay, const Dims& d, const ChainBuf& c, const Work& w,
-                             const float* eps, hipStream_t s);
 void cmdgen_launch_step_count(const Layout& lay, const Dims& d, const ChainBuf& c, const Work& w,
                               const float* eps, hipStream_t s);
 void cmdgen_launch_debug_noise(unsigned long long seed, long long pocket_id, int draw, int n_nodes, int width,
@@ -99,16 +97,26 @@ extern "C" int cmdgen_create(const cmdgen_config* cfg, int device, cmdgen_handle
     return CMDGEN_OK;
 }
 
+// every kind's captured steps (they bake in the kernel choice, the layout and the weights)
+static void drop_chain_graphs(cmdgen_handle* h) {
+    for (ChainSlot& k : h->chains)
+        if (k.graph) { hipGraphExecDestroy(k.graph); k.graph = nullptr; }
+}
+
+// every kind's buffers: the next chain of each kind prepares its slot again
+static void release_chains(cmdgen_handle* h) {
+    for (ChainSlot& k : h->chains) { free_pool(k.allocs); k.n_steps = -1; k.tables.clear(); }
+}
+
 extern "C" void cmdgen_destroy(cmdgen_handle* h) {
     if (!h) return;
     hipSetDevice(h->device);
-    if (h->step_graph) hipGraphExecDestroy(h->step_graph);
-    if (h->joint_graph) hipGraphExecDestroy(h->joint_graph);
-    if (h->inpaint_graph) hipGraphExecDestroy(h->inpaint_graph);
+    drop_chain_graphs(h);
     if (h->own_stream) hipStreamDestroy(h->own_stream);
     if (h->ev_in) hipEventDestroy(h->ev_in);
     if (h->ev_out) hipEventDestroy(h->ev_out);
-    free_pool(h->weight_allocs); free_pool(h->layout_allocs); free_pool(h->chain_allocs); free_pool(h->joint_allocs); free_pool(h->inp_allocs);
+    release_chains(h);
+    free_pool(h->weight_allocs); free_pool(h->layout_allocs);
     for (int i = 0; i < 2; ++i) { if (h->idx_stage[i]) hipHostFree(h->idx_stage[i]); if (h->idx_ev[i]) hipEventDestroy(h->idx_ev[i]); }
     if (h->h_norm) hipHostFree(h->h_norm);
     if (h->norm_ev) hipEventDestroy(h->norm_ev);
@@ -299,9 +307,7 @@ static int upload_pack(cmdgen_handle* h, const float* W, int out, int in, WPack*
 extern "C" int cmdgen_finalize_weights(cmdgen_handle* h) {
     if (!h) return CMDGEN_EINVAL;
     hipSetDevice(h->device);
-    if (h->step_graph) { hipGraphExecDestroy(h->step_graph); h->step_graph = nullptr; }
-    if (h->joint_graph) { hipGraphExecDestroy(h->joint_graph); h->joint_graph = nullptr; }
-    if (h->inpaint_graph) { hipGraphExecDestroy(h->inpaint_graph); h->inpaint_graph = nullptr; }
+    drop_chain_graphs(h);
     free_pool(h->weight_allocs);
     h->layers.clear();
     const Dims& d = h->dims;
@@ -405,9 +411,8 @@ extern "C" int cmdgen_finalize_weights(cmdgen_handle* h) {
 #undef GET
 #undef UP
     h->finalized = true;
-    h->user_coef_K = -1; h->chain_K = -1;      // a new gamma table invalidates any step table
-    h->joint_steps = -1; h->joint_key.clear();
-    h->inp_steps = -1;
+    h->user_coef_K = -1;                       // a new gamma table invalidates any step table
+    release_chains(h);
     return CMDGEN_OK;
 }
 
@@ -549,16 +554,15 @@ static int set_layout_impl(cmdgen_handle* h, int64_t batch, const int64_t* nph, 
     // the OTHER of two device blocks, copied from pinned staging in stream order, so kernels of the previous layout that
     // are still running on `stream` keep reading theirs)
     const bool fits_now = h->cap_B >= B && h->cap_Nl >= Nl && h->cap_Np >= Np && h->cap_N >= N && h->cap_e >= ecap && h->cap_ec >= eccap;
-    const bool no_wait = on_stream && fits_now && h->have_layout && h->chain_allocs.empty() && h->joint_allocs.empty() &&
-                         h->inp_allocs.empty() && (h->last_stream == stream) && !h->step_graph && !h->joint_graph && !h->inpaint_graph;
+    bool chains_idle = true;
+    for (const ChainSlot& k : h->chains) chains_idle = chains_idle && k.allocs.empty() && !k.graph;
+    const bool no_wait = on_stream && fits_now && h->have_layout && chains_idle && (h->last_stream == stream);
     if (!no_wait) {
         if (h->own_stream) hipStreamSynchronize(h->own_stream);
         if (h->have_layout) hipStreamSynchronize(h->last_stream);
         if (on_stream) hipStreamSynchronize(stream);
     }
-    if (h->step_graph) { hipGraphExecDestroy(h->step_graph); h->step_graph = nullptr; }
-    if (h->joint_graph) { hipGraphExecDestroy(h->joint_graph); h->joint_graph = nullptr; }
-    if (h->inpaint_graph) { hipGraphExecDestroy(h->inpaint_graph); h->inpaint_graph = nullptr; }
+    drop_chain_graphs(h);
     int rc; void* p;
     Layout& L = h->lay; Work& w = h->work;
     // Workspaces are capacity-based: a new batch that fits the current capacities (every training step and every
@@ -566,9 +570,7 @@ static int set_layout_impl(cmdgen_handle* h, int64_t batch, const int64_t* nph, 
     const bool fits = h->cap_B >= B && h->cap_Nl >= Nl && h->cap_Np >= Np && h->cap_N >= N && h->cap_e >= ecap && h->cap_ec >= eccap;
     if (!fits) {
         hipDeviceSynchronize();
-        free_pool(h->layout_allocs); free_pool(h->chain_allocs); h->chain_K = -1;
-        free_pool(h->joint_allocs); h->joint_steps = -1; h->joint_key.clear();
-        free_pool(h->inp_allocs); h->inp_steps = -1;
+        free_pool(h->layout_allocs); release_chains(h);
         cmdgen_train_free(h->train); h->train = nullptr;
         h->have_layout = false;
         auto grow = [](int64_t v) { return v + v / 4 + 64; };
@@ -603,10 +605,8 @@ static int set_layout_impl(cmdgen_handle* h, int64_t batch, const int64_t* nph, 
 #undef ALLOC
         h->cap_B = cB; h->cap_Nl = cNl; h->cap_Np = cNp; h->cap_N = cN; h->cap_e = ce; h->cap_ec = cec;
     } else {
-        // chain / joint buffers are sized by the exact layout and cheap: rebuilt on the next chain
-        free_pool(h->chain_allocs); h->chain_K = -1;
-        free_pool(h->joint_allocs); h->joint_steps = -1; h->joint_key.clear();
-        free_pool(h->inp_allocs); h->inp_steps = -1;
+        // chain buffers are sized by the exact layout and cheap: rebuilt on the next chain
+        release_chains(h);
     }
     if (edge_lds_bytes(max_n) > 64 * 1024) cmdgen_edge_kernels_allow_lds(edge_lds_bytes(max_n));
     L.B = B; L.Nl = (int)Nl; L.Np = (int)Np; L.N = (int)N; L.max_n = max_n;
@@ -744,7 +744,7 @@ EvalLaunch make_launch(cmdgen_handle* h) {
 // ---------------------------------------------------------------------------------
 static const char* const kOptionKeys[] = {
     "node_mt", "edge_mt", "coord_mt", "embed_mt", "edge_wgs_per_cu", "coord_wgs_per_cu", "e128_wgs_per_cu", "e128_fused", "half_engine", "edge_fullk", "node64", "node16_split", "node16w",
-    "dead_skip", "write_embed", "fused_step", "pocket_cache", "graph_steps",
+    "dead_skip", "write_embed", "graph_steps",
     "wgrad_split", "wgrad_tile", "wgrad_split_wgs128", "wgrad_split_wgs64", "wgrad_wgs", "dgrad_mt", "dgrad_tail", "wgrad_stream", "train_half", "wgrad_silu", "train_node16", "wgrad_k128"};
 
 static void drop_graphs(cmdgen_handle* h) {
@@ -752,9 +752,7 @@ static void drop_graphs(cmdgen_handle* h) {
     hipSetDevice(h->device);
     if (h->own_stream) hipStreamSynchronize(h->own_stream);
     if (h->have_layout) hipStreamSynchronize(h->last_stream);
-    if (h->step_graph) { hipGraphExecDestroy(h->step_graph); h->step_graph = nullptr; }
-    if (h->joint_graph) { hipGraphExecDestroy(h->joint_graph); h->joint_graph = nullptr; }
-    if (h->inpaint_graph) { hipGraphExecDestroy(h->inpaint_graph); h->inpaint_graph = nullptr; }
+    drop_chain_graphs(h);
 }
 static void refresh_tune(cmdgen_handle* h) {
     TrainTune t;
@@ -934,51 +932,178 @@ static void build_step_table(const std::vector<float>& gamma, int T, int K, std:
 // math so that it matches the reference's torch ops bit for bit.
 extern "C" int cmdgen_set_step_table(cmdgen_handle* h, int32_t K, const float* coef_host) {
     if (!h || K < 1 || !coef_host) return fail(h, CMDGEN_EINVAL, "bad step table");
-    const size_t n = (size_t)(K + 1) * 4;
-    // the Python API hands the table over on every sampling call: an unchanged table keeps the chain buffers and
-    // the captured step graph (re-capture + re-instantiate cost more than a short chain)
-    if (h->user_coef_K == K && h->user_coef.size() == n && memcmp(h->user_coef.data(), coef_host, n * sizeof(float)) == 0)
-        return CMDGEN_OK;
-    h->user_coef.assign(coef_host, coef_host + n);
+    h->user_coef.assign(coef_host, coef_host + (size_t)(K + 1) * 4);
     h->user_coef_K = K;
-    h->chain_K = -1;
     return CMDGEN_OK;
 }
 
-static int prepare_chain(cmdgen_handle* h, int K, bool want_steps) {
-    if (h->chain_K == K) return 0;
+// the step table of K steps: the caller's when it supplied one for K
+static std::vector<float> step_table(const cmdgen_handle* h, int K) {
+    std::vector<float> tab;
+    if (h->user_coef_K == K) tab = h->user_coef; else build_step_table(h->gamma, h->cfg.timesteps, K, tab);
+    return tab;
+}
+
+// ---------------------------------------------------------------------------------
+// the denoising chains: what cmdgen_sample_chain, cmdgen_joint_chain and cmdgen_inpaint_chain share
+// ---------------------------------------------------------------------------------
+// a plan's tables as one upload: coef | coef2 | iop bits
+static std::vector<float> plan_tables(const std::vector<float>& coef, const std::vector<float>& coef2, const std::vector<int>& iop) {
+    std::vector<float> t(coef);
+    t.insert(t.end(), coef2.begin(), coef2.end());
+    t.resize(t.size() + iop.size());
+    memcpy(t.data() + coef.size() + coef2.size(), iop.data(), iop.size() * sizeof(int));
+    return t;
+}
+
+// the kind's own buffers in its slot's pool, pointed at the uploaded tables
+typedef int (*ChainAlloc)(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps);
+
+// A slot that holds exactly `tables` for the current layout is used as it is, with its captured graph.  Otherwise it is
+// prepared again: the tables, the check buffer, the loop state and the CoG slot, then the kind's buffers (alloc).
+static int prepare_slot(cmdgen_handle* h, ChainSlot& k, std::vector<float>& tables, int n_steps, ChainAlloc alloc) {
+    if (k.n_steps >= 0 && k.tables.size() == tables.size() &&
+        memcmp(k.tables.data(), tables.data(), tables.size() * sizeof(float)) == 0)
+        return 0;
     hipDeviceSynchronize();
-    if (h->step_graph) { hipGraphExecDestroy(h->step_graph); h->step_graph = nullptr; }
-    free_pool(h->chain_allocs);
-    const Dims& d = h->dims;
+    if (k.graph) { hipGraphExecDestroy(k.graph); k.graph = nullptr; }
+    free_pool(k.allocs);
+    k.n_steps = -1;
     void* p; int rc;
-    std::vector<float> coef;
-    if (h->user_coef_K == K) coef = h->user_coef; else build_step_table(h->gamma, h->cfg.timesteps, K, coef);
-    rc = dev_alloc(h, h->chain_allocs, &p, coef.size() * sizeof(float), false); if (rc) return rc;
-    HIPCHK(h, hipMemcpy(p, coef.data(), coef.size() * sizeof(float), hipMemcpyHostToDevice));
-    h->chain.coef = (const float4*)p;
-    rc = dev_alloc(h, h->chain_allocs, &p, (size_t)h->lay.Nl * (3 + d.P) * sizeof(float), true); if (rc) return rc; h->chain.z_phar = (float*)p;
-    rc = dev_alloc(h, h->chain_allocs, &p, (size_t)h->lay.Np * (3 + d.R) * sizeof(float), true); if (rc) return rc; h->chain.xh_pocket = (float*)p;
-    rc = dev_alloc(h, h->chain_allocs, &p, (size_t)(K + 3) * 2 * sizeof(unsigned int), true); if (rc) return rc; h->chain.check = (unsigned int*)p;
-    rc = dev_alloc(h, h->chain_allocs, &p, sizeof(ChainState), true); if (rc) return rc; h->chain.state = (ChainState*)p;
-    rc = dev_alloc(h, h->chain_allocs, &p, 4 * sizeof(unsigned int), true); if (rc) return rc; h->d_cog = (unsigned int*)p;
-    {   // storage of the chain-invariant pocket rows of k_embed (PocketCache) and the two pinned time arrays used to build it
-        const size_t nq = (size_t)h->lay.Np * d.H * sizeof(float), nh = (size_t)d.H * sizeof(float);
-        rc = dev_alloc(h, h->chain_allocs, &p, nq, true); if (rc) return rc; h->pk_c = (float*)p;
-        rc = dev_alloc(h, h->chain_allocs, &p, nq, true); if (rc) return rc; h->pk_P0 = (float*)p;
-        rc = dev_alloc(h, h->chain_allocs, &p, nq, true); if (rc) return rc; h->pk_Q0 = (float*)p;
-        rc = dev_alloc(h, h->chain_allocs, &p, nh, true); if (rc) return rc; h->pk_dh = (float*)p;
-        rc = dev_alloc(h, h->chain_allocs, &p, nh, true); if (rc) return rc; h->pk_dP = (float*)p;
-        rc = dev_alloc(h, h->chain_allocs, &p, nh, true); if (rc) return rc; h->pk_dQ = (float*)p;
-        std::vector<float> t01((size_t)2 * h->lay.B, 0.f);
-        for (int b = 0; b < h->lay.B; ++b) t01[h->lay.B + b] = 1.f;
-        rc = dev_alloc(h, h->chain_allocs, &p, t01.size() * sizeof(float), false); if (rc) return rc; h->pk_t01 = (float*)p;
-        HIPCHK(h, hipMemcpy(p, t01.data(), t01.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    h->chain_K = K;
-    (void)want_steps;
+    rc = dev_alloc(h, k.allocs, &p, tables.size() * sizeof(float), false); if (rc) return rc;
+    HIPCHK(h, hipMemcpy(p, tables.data(), tables.size() * sizeof(float), hipMemcpyHostToDevice));
+    const float* tab = (const float*)p;
+    rc = dev_alloc(h, k.allocs, &p, (size_t)(n_steps + 3) * 2 * sizeof(unsigned int), true); if (rc) return rc; k.check = (unsigned int*)p;
+    rc = dev_alloc(h, k.allocs, &p, sizeof(ChainState), true); if (rc) return rc; k.state = (ChainState*)p;
+    rc = dev_alloc(h, k.allocs, &p, 4 * sizeof(unsigned int), true); if (rc) return rc; k.cog = (unsigned int*)p;
+    rc = alloc(h, k, tab, n_steps); if (rc) return rc;
+    k.n_steps = n_steps;
+    k.tables.swap(tables);
     return 0;
 }
+
+// storage of the chain-invariant pocket rows of k_embed (PocketCache) and the time pair (t = 0, t = 1) that builds it
+static int alloc_pocket_cache(cmdgen_handle* h, ChainSlot& k) {
+    const Layout& L = h->lay;
+    void* p; int rc;
+    for (int i = 0; i < 6; ++i) {            // c, P0, Q0: [Np][H]; dh, dP, dQ: [H]
+        rc = dev_alloc(h, k.allocs, &p, (size_t)(i < 3 ? L.Np : 1) * h->dims.H * sizeof(float), true); if (rc) return rc;
+        k.pk[i] = (float*)p;
+    }
+    std::vector<float> t01((size_t)2 * L.B, 0.f);
+    for (int b = 0; b < L.B; ++b) t01[L.B + b] = 1.f;
+    rc = dev_alloc(h, k.allocs, &p, t01.size() * sizeof(float), false); if (rc) return rc;
+    HIPCHK(h, hipMemcpy(p, t01.data(), t01.size() * sizeof(float), hipMemcpyHostToDevice));
+    k.pk[6] = (float*)p;
+    return 0;
+}
+
+// chain-invariant work once per chain: the pocket's features are fixed, so k_embed's output for pocket rows is affine in the
+// time feature - two embed-only passes (t = 0, t = 1) give the cache every later evaluation of `a` reads
+static void build_pocket_cache(cmdgen_handle* h, const ChainSlot& k, const ChainBuf& c, EvalLaunch& a, hipStream_t s) {
+    if (h->lay.Np <= 0) return;
+    float* const* pk = k.pk;
+    cmdgen_build_pocket_cache(a, c.z_phar, c.xh_pocket, pk[6], pk[0], pk[1], pk[2], pk[3], pk[4], pk[5], s);
+    a.pcache = PocketCache{pk[0], pk[1], pk[2], pk[3], pk[4], pk[5]};
+}
+
+// the handle's own stream, for work the caller queues on the legacy default stream (which cannot be captured)
+static int own_stream(cmdgen_handle* h) {
+    if (h->own_stream) return 0;
+    HIPCHK(h, hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
+    HIPCHK(h, hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
+    HIPCHK(h, hipEventCreateWithFlags(&h->ev_out, hipEventDisableTiming));
+    return 0;
+}
+
+// The start of a chain of `kind` with n_steps denoising steps: the stream it runs on (*s; with use_graph on the legacy default
+// stream, the handle's own stream ordered after the caller's pending work), its slot prepared for `tables`, the per-call reset
+// (pocket ids of the Philox draws, loop state, check buffer, CoG slot) and the launch description of its evaluations (*a).
+static int begin_chain(cmdgen_handle* h, ChainKind kind, std::vector<float>& tables, int n_steps, ChainAlloc alloc,
+                       const int64_t* pocket_ids_host, bool use_graph, hipStream_t caller, hipStream_t* s, EvalLaunch* a) {
+    h->last_chain = kind;
+    hipSetDevice(h->device);
+    int rc;
+    *s = caller;
+    if (use_graph && caller == nullptr) {
+        rc = own_stream(h); if (rc) return rc;
+        HIPCHK(h, hipEventRecord(h->ev_in, caller));
+        HIPCHK(h, hipStreamWaitEvent(h->own_stream, h->ev_in, 0));
+        *s = h->own_stream;
+    }
+    ChainSlot& k = h->chains[kind];
+    rc = prepare_slot(h, k, tables, n_steps, alloc); if (rc) return rc;
+    rc = begin_work(h, *s); if (rc) return rc;
+    h->last_stream = caller;
+    std::vector<int64_t> gid(h->lay.B);                  // global pocket ids for the Philox key
+    for (int b = 0; b < h->lay.B; ++b) gid[b] = pocket_ids_host ? pocket_ids_host[b] : b;
+    HIPCHK(h, hipMemcpyAsync(h->d_gid, gid.data(), gid.size() * sizeof(int64_t), hipMemcpyHostToDevice, *s));
+    HIPCHK(h, hipStreamSynchronize(*s));                 // gid is a stack vector
+    const ChainState st0{0, n_steps, 0, 0};
+    HIPCHK(h, hipMemcpyAsync(k.state, &st0, sizeof st0, hipMemcpyHostToDevice, *s));
+    HIPCHK(h, hipMemsetAsync(k.check, 0, (size_t)(n_steps + 3) * 2 * sizeof(unsigned int), *s));
+    HIPCHK(h, hipMemsetAsync(k.cog, 0, 4 * sizeof(unsigned int), *s));
+    HIPCHK(h, hipStreamSynchronize(*s));                 // st0 is on the stack
+    *a = make_launch(h);
+    ++h->eval_gen;
+    if (h->kernel_profiling && !use_graph) a->prof_events = h->prof_events;
+    return 0;
+}
+
+// The n denoising steps of a chain.  The step is identical every iteration (the step index lives on the device), so with
+// use_graph G of them (option "graph_steps", default 8: they amortise the per-replay floor of ~10-16 us) are captured once
+// and replayed n / G times, and the other n % G run eagerly.  The graph stays valid while its slot keeps its plan
+// (prepare_slot) and `key` (the caller's pointers and the stream), the seed and G stay the same.
+template <class Step>
+static int run_steps(cmdgen_handle* h, ChainSlot& k, const void* const* key, unsigned long long seed, int n, bool use_graph,
+                     hipStream_t s, Step one_step) {
+    if (!use_graph) {
+        for (int i = 0; i < n; ++i) one_step(s);
+        return 0;
+    }
+    int G = (int)opt_of(h, "graph_steps", 8);
+    if (G < 1) G = 1;
+    if (G > n) G = n;
+    if (k.graph && (memcmp(key, k.key, sizeof k.key) != 0 || k.seed != seed || k.graph_steps != G)) {
+        hipGraphExecDestroy(k.graph); k.graph = nullptr;
+    }
+    if (!k.graph) {
+        hipGraph_t g = nullptr;
+        hipError_t err = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
+        if (err != hipSuccess) return fail(h, CMDGEN_EHIP, "hipStreamBeginCapture: %s", hipGetErrorString(err));
+        for (int i = 0; i < G; ++i) one_step(s);
+        err = hipStreamEndCapture(s, &g);                // always: a capture left open poisons every later launch on s
+        if (err == hipSuccess) err = hipGraphInstantiate(&k.graph, g, nullptr, nullptr, 0);
+        if (g) hipGraphDestroy(g);
+        if (err != hipSuccess) { k.graph = nullptr; return fail(h, CMDGEN_EHIP, "capturing the chain's steps: %s", hipGetErrorString(err)); }
+        memcpy(k.key, key, sizeof k.key); k.seed = seed; k.graph_steps = G;
+    }
+    for (int i = 0; i < n / G; ++i) HIPCHK(h, hipGraphLaunch(k.graph, s));
+    for (int i = 0; i < n % G; ++i) one_step(s);
+    return 0;
+}
+
+// the end of a chain: its launch errors, and the caller's later work ordered after it when it ran on the handle's own stream
+static int end_chain(cmdgen_handle* h, hipStream_t caller, hipStream_t s) {
+    HIPCHK(h, hipGetLastError());
+    if (s != caller) {
+        HIPCHK(h, hipEventRecord(h->ev_out, s));
+        HIPCHK(h, hipStreamWaitEvent(caller, h->ev_out, 0));
+    }
+    return CMDGEN_OK;
+}
+
+// a conditional chain's z and pocket (ChainBuf) and its pocket cache; coef: its posterior rows
+static int alloc_chain_buf(cmdgen_handle* h, ChainSlot& k, ChainBuf& c, const float* coef) {
+    const Dims& d = h->dims;
+    void* p; int rc;
+    c.coef = (const float4*)coef; c.check = k.check; c.state = k.state;
+    rc = dev_alloc(h, k.allocs, &p, (size_t)h->lay.Nl * (3 + d.P) * sizeof(float), true); if (rc) return rc; c.z_phar = (float*)p;
+    rc = dev_alloc(h, k.allocs, &p, (size_t)h->lay.Np * (3 + d.R) * sizeof(float), true); if (rc) return rc; c.xh_pocket = (float*)p;
+    return alloc_pocket_cache(h, k);
+}
+
+static int alloc_plain(cmdgen_handle* h, ChainSlot& k, const float* tables, int) { return alloc_chain_buf(h, k, h->chain, tables); }
 
 extern "C" int cmdgen_sample_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
                                    int32_t timesteps, const float* noise, uint64_t seed,
@@ -989,101 +1114,33 @@ extern "C" int cmdgen_sample_chain(cmdgen_handle* h, const float* pocket_x, cons
     const int K = timesteps;
     if (K < 1 || K > h->cfg.timesteps) return fail(h, CMDGEN_EINVAL, "timesteps=%d must be in [1, %d]", K, h->cfg.timesteps);
     if (h->dims.joint) return fail(h, CMDGEN_ESTATE, "this handle is the joint model (update_pocket_coords=1): use cmdgen_joint_chain");
-    h->last_chain_joint = false; h->last_chain_inpaint = false;
-    hipSetDevice(h->device);
-    hipStream_t caller = (hipStream_t)stream;
-    hipStream_t s = caller;
-    if (use_graph && caller == nullptr) {
-        // the legacy default stream cannot be captured: run the chain on a stream of our own,
-        // ordered after the caller's pending work and before its later work by events
-        if (!h->own_stream) {
-            HIPCHK(h, hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-            HIPCHK(h, hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
-            HIPCHK(h, hipEventCreateWithFlags(&h->ev_out, hipEventDisableTiming));
-        }
-        HIPCHK(h, hipEventRecord(h->ev_in, caller));
-        HIPCHK(h, hipStreamWaitEvent(h->own_stream, h->ev_in, 0));
-        s = h->own_stream;
-    }
-    rc = prepare_chain(h, K, z_steps_out != nullptr); if (rc) return rc;
-    rc = begin_work(h, s); if (rc) return rc;
-    h->last_stream = caller;
+    std::vector<float> tables = step_table(h, K);
+    const hipStream_t caller = (hipStream_t)stream;
+    hipStream_t s; EvalLaunch a;
+    rc = begin_chain(h, CHAIN_PLAIN, tables, K, alloc_plain, pocket_ids_host, use_graph, caller, &s, &a); if (rc) return rc;
+    ChainSlot& k = h->chains[CHAIN_PLAIN];
     const Dims& d = h->dims;
-    // global pocket ids for the Philox key
-    {
-        std::vector<int64_t> gid(h->lay.B);
-        for (int b = 0; b < h->lay.B; ++b) gid[b] = pocket_ids_host ? pocket_ids_host[b] : b;
-        HIPCHK(h, hipMemcpyAsync(h->d_gid, gid.data(), gid.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        HIPCHK(h, hipStreamSynchronize(s));          // gid is a stack vector
-    }
     ChainBuf c = h->chain;
     c.noise = noise; c.seed = seed; c.z_steps = z_steps_out; c.pocket_steps = pocket_steps_out;
-    const ChainState st0{0, K, 0, 0};
-    HIPCHK(h, hipMemcpyAsync(c.state, &st0, sizeof st0, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemsetAsync(c.check, 0, (size_t)(K + 3) * 2 * sizeof(unsigned int), s));
-    HIPCHK(h, hipMemsetAsync(h->d_cog, 0, 4 * sizeof(unsigned int), s));
-    HIPCHK(h, hipStreamSynchronize(s));              // st0 is on the stack
-    EvalLaunch a = make_launch(h);
-    ++h->eval_gen;
-    if (h->kernel_profiling && !use_graph) a.prof_events = h->prof_events;
     cmdgen_launch_chain_init(h->lay, d, c, pocket_x, pocket_onehot, s);
+    build_pocket_cache(h, k, c, a, s);
     // One denoising step = the posterior update fused with pass 1 of the next radius graph (k_step_count), then the
     // evaluation at the new state: pass 2 of the graph (k_edge_write), k_embed, the L blocks,
-    // k_readout.  The chain is: evaluation 0, K x (step + evaluation), decode.  Option "fused_step" = 0 restores the
-    // separate k_ddpm_step / k_edge_count launches on one stream (A/B measurements).
-    const bool fused = opt_of(h, "fused_step", 1) != 0;
-    if (opt_of(h, "pocket_cache", 1) != 0 && h->lay.Np > 0) {
-        // chain-invariant work once per chain: the pocket's features are fixed, so k_embed's output for pocket rows is
-        // affine in the time feature - two embed-only passes (t = 0, t = 1) give the cache every later evaluation reads
-        cmdgen_build_pocket_cache(a, c.z_phar, c.xh_pocket, h->pk_t01, h->pk_c, h->pk_P0, h->pk_Q0, h->pk_dh, h->pk_dP, h->pk_dQ, s);
-        a.pcache = PocketCache{h->pk_c, h->pk_P0, h->pk_Q0, h->pk_dh, h->pk_dP, h->pk_dQ};
-    }
+    // k_readout.  The chain is: evaluation 0, K x (step + evaluation), decode.
     EvalLaunch a2 = a;
-    if (fused) { a2 = a; a2.skip_count = 1; }         // (pass 2 of the graph on a side stream was measured and dropped: the fork / join costs ~23 us per
-                                                      // step inside the replayed graph, far more than the 10 us it hides; profiles/r02_b_step_fusion.txt)
+    a2.skip_count = 1;                               // (pass 2 of the graph on a side stream was measured and dropped: the fork / join costs ~23 us per
+                                                     // step inside the replayed graph, far more than the 10 us it hides; profiles/r02_b_step_fusion.txt)
     cmdgen_launch_eval(a, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, s, nullptr);   // evaluation 0 (t = 1)
-    auto one_step = [&](hipStream_t ss) {
-        if (fused) cmdgen_launch_step_count(h->lay, d, c, h->work, h->work.eps_tmp, ss);
-        else cmdgen_launch_ddpm_step(h->lay, d, c, h->work, h->work.eps_tmp, ss);
+    const void* key[6] = {noise, z_steps_out, pocket_steps_out, nullptr, nullptr, s};
+    rc = run_steps(h, k, key, seed, K, use_graph, s, [&](hipStream_t ss) {
+        cmdgen_launch_step_count(h->lay, d, c, h->work, h->work.eps_tmp, ss);
         cmdgen_launch_eval(a2, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, ss, nullptr);
-    };
-    if (use_graph) {
-        // The step is identical every iteration (the step index lives on the device), so it is
-        // captured once per (layout, K, noise/z_steps pointers, stream) and replayed K times.
-        if (h->step_graph && (h->graph_noise != noise || h->graph_zsteps != z_steps_out || h->graph_psteps != pocket_steps_out || h->graph_stream != s || h->graph_seed != seed)) {
-            hipGraphExecDestroy(h->step_graph); h->step_graph = nullptr;
-        }
-        // G identical steps per graph launch amortise the per-replay floor (~10-16 us host side, a few us of
-        // device idle): the step index lives on the device, so a G-step graph is just G copies of the step.
-        int G = (int)opt_of(h, "graph_steps", 8);
-        if (G < 1) G = 1;
-        if (G > K) G = K;
-        if (h->step_graph && h->graph_steps != G) { hipGraphExecDestroy(h->step_graph); h->step_graph = nullptr; }
-        if (!h->step_graph) {
-            hipGraph_t g = nullptr;
-            HIPCHK(h, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            for (int i = 0; i < G; ++i) one_step(s);
-            HIPCHK(h, hipStreamEndCapture(s, &g));
-            HIPCHK(h, hipGraphInstantiate(&h->step_graph, g, nullptr, nullptr, 0));
-            hipGraphDestroy(g);
-            h->graph_noise = noise; h->graph_zsteps = z_steps_out; h->graph_psteps = pocket_steps_out; h->graph_stream = s; h->graph_seed = seed;
-            h->graph_steps = G;
-        }
-        for (int i = 0; i < K / G; ++i) HIPCHK(h, hipGraphLaunch(h->step_graph, s));
-        for (int i = 0; i < K % G; ++i) one_step(s);
-    } else {
-        for (int i = 0; i < K; ++i) one_step(s);
-    }
+    });
+    if (rc) return rc;
     // final p(x, h | z0): the last evaluation above ran at t = 0 (coef[K].w); decode
-    cmdgen_launch_chain_final(h->lay, d, c, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, h->d_cog, s);
-    HIPCHK(h, hipGetLastError());
-    if (s != caller) {
-        HIPCHK(h, hipEventRecord(h->ev_out, s));
-        HIPCHK(h, hipStreamWaitEvent(caller, h->ev_out, 0));
-    }
-    return CMDGEN_OK;
+    cmdgen_launch_chain_final(h->lay, d, c, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, k.cog, s);
+    return end_chain(h, caller, s);
 }
-
 
 // ---------------------------------------------------------------------------------
 // joint model: EnVariationalDiffusion.sample / .inpaint (en_diffusion.py:576-831)
@@ -1174,39 +1231,23 @@ extern "C" int cmdgen_joint_plan(cmdgen_handle* h, int32_t timesteps, int32_t re
     return CMDGEN_OK;
 }
 
-static int prepare_joint(cmdgen_handle* h, int K, int resamplings, int jump, bool inpaint) {
-    const std::vector<int> key{K, resamplings, jump, inpaint ? 1 : 0};
-    if (h->joint_steps >= 0 && h->joint_key == key) return 0;
-    hipDeviceSynchronize();
-    if (h->joint_graph) { hipGraphExecDestroy(h->joint_graph); h->joint_graph = nullptr; }
-    if (h->inpaint_graph) { hipGraphExecDestroy(h->inpaint_graph); h->inpaint_graph = nullptr; }
-    free_pool(h->joint_allocs);
-    h->joint_steps = -1;
+// JointBuf: the plan's rows (coef, coef2, iop: n_steps + 1 each), the state, and the scratch of the combined draws
+static int alloc_joint(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
     const Dims& d = h->dims;
-    const JointPlan p = build_joint_plan(h->gamma, h->cfg.timesteps, K, resamplings, jump, inpaint);
-    void* q; int rc;
-    auto up = [&](const void* src, size_t bytes, const void** dst) -> int {
-        int r = dev_alloc(h, h->joint_allocs, &q, bytes, false); if (r) return r;
-        if (hipMemcpy(q, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(h, CMDGEN_EHIP, "hipMemcpy H2D failed");
-        *dst = q; return 0;
-    };
-    const void* dp;
-    rc = up(p.coef.data(), p.coef.size() * sizeof(float), &dp); if (rc) return rc; h->joint.coef = (const float4*)dp;
-    rc = up(p.coef2.data(), p.coef2.size() * sizeof(float), &dp); if (rc) return rc; h->joint.coef2 = (const float4*)dp;
-    rc = up(p.iop.data(), p.iop.size() * sizeof(int), &dp); if (rc) return rc; h->joint.iop = (const int4*)dp;
+    JointBuf& c = h->joint;
+    c.coef = (const float4*)tables;
+    c.coef2 = (const float4*)(tables + (size_t)(n_steps + 1) * 4);
+    c.iop = (const int4*)(tables + (size_t)(n_steps + 1) * 8);
+    c.check = k.check; c.state = k.state;
     const size_t np_ = (size_t)h->lay.Nl * (3 + d.P) * sizeof(float), nq_ = (size_t)h->lay.Np * (3 + d.R) * sizeof(float);
-#define JALLOC(dst, bytes) do { rc = dev_alloc(h, h->joint_allocs, &q, bytes, true); if (rc) return rc; dst = (float*)q; } while (0)
-    JALLOC(h->joint.z_phar, np_); JALLOC(h->joint.z_pocket, nq_);
-    JALLOC(h->joint.e_phar, np_); JALLOC(h->joint.e_pocket, nq_);
-    JALLOC(h->joint.zk_phar, np_); JALLOC(h->joint.zk_pocket, nq_);
-    JALLOC(h->joint.x0_phar, np_); JALLOC(h->joint.x0_pocket, nq_);
+    void* q; int rc;
+#define JALLOC(dst, bytes) do { rc = dev_alloc(h, k.allocs, &q, bytes, true); if (rc) return rc; dst = (float*)q; } while (0)
+    JALLOC(c.z_phar, np_); JALLOC(c.z_pocket, nq_);
+    JALLOC(c.e_phar, np_); JALLOC(c.e_pocket, nq_);
+    JALLOC(c.zk_phar, np_); JALLOC(c.zk_pocket, nq_);
+    JALLOC(c.x0_phar, np_); JALLOC(c.x0_pocket, nq_);
     JALLOC(h->eps_pocket_tmp, nq_);
 #undef JALLOC
-    rc = dev_alloc(h, h->joint_allocs, &q, (size_t)(p.n_steps + 3) * 2 * sizeof(unsigned int), true); if (rc) return rc; h->joint.check = (unsigned int*)q;
-    rc = dev_alloc(h, h->joint_allocs, &q, sizeof(ChainState), true); if (rc) return rc; h->joint.state = (ChainState*)q;
-    rc = dev_alloc(h, h->joint_allocs, &q, 4 * sizeof(unsigned int), true); if (rc) return rc; h->joint_cog = (unsigned int*)q;
-    h->joint_steps = p.n_steps;
-    h->joint_key = key;
     return 0;
 }
 
@@ -1223,83 +1264,29 @@ extern "C" int cmdgen_joint_chain(cmdgen_handle* h, const float* phar_x, const f
     const bool inpaint = phar_fixed != nullptr || pocket_fixed != nullptr;
     if (inpaint && (!phar_fixed || !pocket_fixed || !phar_x || !phar_onehot || !pocket_x || !pocket_onehot))
         return fail(h, CMDGEN_EINVAL, "inpainting needs phar_x, phar_onehot, pocket_x, pocket_onehot and both fixed masks");
-    hipSetDevice(h->device);
-    hipStream_t caller = (hipStream_t)stream;
-    hipStream_t s = caller;
-    if (use_graph && caller == nullptr) {
-        if (!h->own_stream) {
-            HIPCHK(h, hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-            HIPCHK(h, hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
-            HIPCHK(h, hipEventCreateWithFlags(&h->ev_out, hipEventDisableTiming));
-        }
-        HIPCHK(h, hipEventRecord(h->ev_in, caller));
-        HIPCHK(h, hipStreamWaitEvent(h->own_stream, h->ev_in, 0));
-        s = h->own_stream;
-    }
-    rc = prepare_joint(h, timesteps, resamplings, jump_length, inpaint); if (rc) return rc;
-    rc = begin_work(h, s); if (rc) return rc;
-    h->last_stream = caller;
-    const int n_steps = h->joint_steps;
-    if (noise) {
-        int64_t need = 0;
-        cmdgen_joint_plan(h, timesteps, resamplings, jump_length, inpaint ? 1 : 0, nullptr, &need);
-        if (n_draws < need) return fail(h, CMDGEN_EINVAL, "noise holds %lld combined draws, the schedule needs %lld", (long long)n_draws, (long long)need);
-    }
-    h->last_chain_joint = true; h->last_chain_inpaint = false;
+    const JointPlan plan = build_joint_plan(h->gamma, h->cfg.timesteps, timesteps, resamplings, jump_length, inpaint);
+    if (noise && n_draws < plan.n_draws)
+        return fail(h, CMDGEN_EINVAL, "noise holds %lld combined draws, the schedule needs %lld", (long long)n_draws, (long long)plan.n_draws);
+    const int n_steps = plan.n_steps;
+    std::vector<float> tables = plan_tables(plan.coef, plan.coef2, plan.iop);
+    const hipStream_t caller = (hipStream_t)stream;
+    hipStream_t s; EvalLaunch a;
+    rc = begin_chain(h, CHAIN_JOINT, tables, n_steps, alloc_joint, pocket_ids_host, use_graph, caller, &s, &a); if (rc) return rc;
+    ChainSlot& k = h->chains[CHAIN_JOINT];
     const Dims& d = h->dims;
-    {
-        std::vector<int64_t> gid(h->lay.B);
-        for (int b = 0; b < h->lay.B; ++b) gid[b] = pocket_ids_host ? pocket_ids_host[b] : b;
-        HIPCHK(h, hipMemcpyAsync(h->d_gid, gid.data(), gid.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-    }
     JointBuf c = h->joint;
-    c.fix_phar = inpaint ? phar_fixed : nullptr; c.fix_pocket = inpaint ? pocket_fixed : nullptr;
+    c.fix_phar = phar_fixed; c.fix_pocket = pocket_fixed;
     c.noise = noise; c.seed = seed; c.z_steps = z_steps_out;
-    const ChainState st0{0, n_steps, 0, 0};
-    HIPCHK(h, hipMemcpyAsync(c.state, &st0, sizeof st0, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemsetAsync(c.check, 0, (size_t)(n_steps + 3) * 2 * sizeof(unsigned int), s));
-    HIPCHK(h, hipMemsetAsync(h->joint_cog, 0, 4 * sizeof(unsigned int), s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    EvalLaunch a = make_launch(h);
-    ++h->eval_gen;
-    if (h->kernel_profiling && !use_graph) a.prof_events = h->prof_events;
     cmdgen_launch_joint_init(h->lay, d, c, phar_x, phar_onehot, pocket_x, pocket_onehot, s);
-    auto one_step = [&](hipStream_t ss) {
+    const void* key[6] = {noise, z_steps_out, nullptr, phar_fixed, pocket_fixed, s};
+    rc = run_steps(h, k, key, seed, n_steps, use_graph, s, [&](hipStream_t ss) {
         cmdgen_launch_eval(a, c.z_phar, c.z_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, h->eps_pocket_tmp, ss, nullptr);
         cmdgen_launch_joint_step(h->lay, d, c, h->work.eps_tmp, h->eps_pocket_tmp, ss);
-    };
-    if (use_graph) {
-        // as in cmdgen_sample_chain: the op index lives on the device, so G captured steps replay for any position
-        const void* key[6] = {noise, z_steps_out, (const void*)s, phar_fixed, pocket_fixed, nullptr};
-        int G = (int)opt_of(h, "graph_steps", 8);
-        if (G < 1) G = 1;
-        if (G > n_steps) G = n_steps;
-        if (h->joint_graph && (memcmp(key, h->jg_key, sizeof key) != 0 || h->jg_seed != seed || h->jg_steps != G)) {
-            hipGraphExecDestroy(h->joint_graph); h->joint_graph = nullptr;
-        }
-        if (!h->joint_graph) {
-            hipGraph_t g = nullptr;
-            HIPCHK(h, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            for (int i = 0; i < G; ++i) one_step(s);
-            HIPCHK(h, hipStreamEndCapture(s, &g));
-            HIPCHK(h, hipGraphInstantiate(&h->joint_graph, g, nullptr, nullptr, 0));
-            hipGraphDestroy(g);
-            memcpy(h->jg_key, key, sizeof key); h->jg_seed = seed; h->jg_steps = G;
-        }
-        for (int i = 0; i < n_steps / G; ++i) HIPCHK(h, hipGraphLaunch(h->joint_graph, s));
-        for (int i = 0; i < n_steps % G; ++i) one_step(s);
-    } else {
-        for (int i = 0; i < n_steps; ++i) one_step(s);
-    }
+    });
+    if (rc) return rc;
     cmdgen_launch_eval(a, c.z_phar, c.z_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, h->eps_pocket_tmp, s, nullptr);
-    cmdgen_launch_joint_final(h->lay, d, c, h->work.eps_tmp, h->eps_pocket_tmp, xh_phar_out, xh_pocket_out, h->joint_cog, s);
-    HIPCHK(h, hipGetLastError());
-    if (s != caller) {
-        HIPCHK(h, hipEventRecord(h->ev_out, s));
-        HIPCHK(h, hipStreamWaitEvent(caller, h->ev_out, 0));
-    }
-    return CMDGEN_OK;
+    cmdgen_launch_joint_final(h->lay, d, c, h->work.eps_tmp, h->eps_pocket_tmp, xh_phar_out, xh_pocket_out, k.cog, s);
+    return end_chain(h, caller, s);
 }
 
 // ---------------------------------------------------------------------------------
@@ -1316,8 +1303,7 @@ struct InpaintPlan {
 // then an op at step s uses exactly the scalars cmdgen_sample_chain uses there).
 static InpaintPlan build_inpaint_plan(const cmdgen_handle* h, int K, int resamplings, int jump) {
     InpaintPlan p;
-    std::vector<float> tab;
-    if (h->user_coef_K == K) tab = h->user_coef; else build_step_table(h->gamma, h->cfg.timesteps, K, tab);
+    const std::vector<float> tab = step_table(h, K);
     const int T = h->cfg.timesteps;
     auto g_at = [&](int step) { return h->gamma[(size_t)lrintf(((float)step / (float)K) * (float)T)]; };
     const std::vector<int> sched = repaint_schedule(resamplings, jump, K);
@@ -1366,50 +1352,21 @@ extern "C" int cmdgen_inpaint_plan(cmdgen_handle* h, int32_t timesteps, int32_t 
     return CMDGEN_OK;
 }
 
-// buffers of the inpainting chain for the current layout, and the plan's tables (re-uploaded only when they change)
-static int prepare_inpaint(cmdgen_handle* h, const InpaintPlan& p) {
-    std::vector<float> tables(p.coef);
-    tables.insert(tables.end(), p.coef2.begin(), p.coef2.end());
-    for (int v : p.iop) { float f; memcpy(&f, &v, 4); tables.push_back(f); }
-    if (h->inp_steps >= 0 && tables.size() == h->inp_tables.size() &&
-        memcmp(tables.data(), h->inp_tables.data(), tables.size() * sizeof(float)) == 0)
-        return 0;
-    hipDeviceSynchronize();
-    if (h->inpaint_graph) { hipGraphExecDestroy(h->inpaint_graph); h->inpaint_graph = nullptr; }
-    free_pool(h->inp_allocs);
-    h->inp_steps = -1;
+// the inpainting chain's ChainBuf (posterior rows: coef, n_steps + 1) and InpaintBuf (coef2, iop: n_steps each; the known part)
+static int alloc_inpaint(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
+    int rc = alloc_chain_buf(h, k, h->inp_chain, tables); if (rc) return rc;
     const Dims& d = h->dims;
     const Layout& L = h->lay;
-    void* q; int rc;
-    auto up = [&](const void* src, size_t bytes) -> void* {
-        if (dev_alloc(h, h->inp_allocs, &q, bytes, false)) return nullptr;
-        if (hipMemcpy(q, src, bytes, hipMemcpyHostToDevice) != hipSuccess) { fail(h, CMDGEN_EHIP, "hipMemcpy H2D failed"); return nullptr; }
-        return q;
-    };
-    ChainBuf& c = h->inp_chain;
     InpaintBuf& ip = h->inp;
-    if (!(c.coef = (const float4*)up(p.coef.data(), p.coef.size() * sizeof(float)))) return CMDGEN_EHIP;
-    if (!(ip.coef2 = (const float4*)up(p.coef2.data(), p.coef2.size() * sizeof(float)))) return CMDGEN_EHIP;
-    if (!(ip.iop = (const int4*)up(p.iop.data(), p.iop.size() * sizeof(int)))) return CMDGEN_EHIP;
-#define IALLOC(dst, type, bytes) do { rc = dev_alloc(h, h->inp_allocs, &q, bytes, true); if (rc) return rc; dst = (type)q; } while (0)
-    const size_t nl_ = (size_t)L.Nl * (3 + d.P) * sizeof(float);
-    IALLOC(c.z_phar, float*, nl_);
-    IALLOC(c.xh_pocket, float*, (size_t)L.Np * (3 + d.R) * sizeof(float));
-    IALLOC(c.check, unsigned int*, (size_t)(p.n_steps + 3) * 2 * sizeof(unsigned int));
-    IALLOC(c.state, ChainState*, sizeof(ChainState));
-    IALLOC(h->inp_cog, unsigned int*, 4 * sizeof(unsigned int));
-    IALLOC(ip.known, const float*, nl_);
+    ip.coef2 = (const float4*)(tables + (size_t)(n_steps + 1) * 4);
+    ip.iop = (const int4*)(tables + (size_t)(2 * n_steps + 1) * 4);
+    ip.n_steps = n_steps;
+    void* q;
+#define IALLOC(dst, type, bytes) do { rc = dev_alloc(h, k.allocs, &q, bytes, true); if (rc) return rc; dst = (type)q; } while (0)
+    IALLOC(ip.known, const float*, (size_t)L.Nl * (3 + d.P) * sizeof(float));
     IALLOC(ip.fix, float*, (size_t)L.Nl * sizeof(float));
     IALLOC(ip.poff, float4*, (size_t)L.B * sizeof(float4));
-    for (int i = 0; i < 3; ++i) IALLOC(h->inp_pk[i], float*, (size_t)L.Np * d.H * sizeof(float));      // PocketCache c, P0, Q0
-    for (int i = 3; i < 6; ++i) IALLOC(h->inp_pk[i], float*, (size_t)d.H * sizeof(float));             // dh, dP, dQ
 #undef IALLOC
-    std::vector<float> t01((size_t)2 * L.B, 0.f);
-    for (int b = 0; b < L.B; ++b) t01[L.B + b] = 1.f;
-    if (!(h->inp_pk[6] = (float*)up(t01.data(), t01.size() * sizeof(float)))) return CMDGEN_EHIP;
-    ip.n_steps = p.n_steps;
-    h->inp_steps = p.n_steps;
-    h->inp_tables.swap(tables);
     return 0;
 }
 
@@ -1426,103 +1383,45 @@ extern "C" int cmdgen_inpaint_chain(cmdgen_handle* h, const float* pocket_x, con
     const InpaintPlan plan = build_inpaint_plan(h, timesteps, resamplings, jump_length);
     if (noise && n_draws < plan.n_draws)
         return fail(h, CMDGEN_EINVAL, "noise holds %lld draws, the schedule needs %lld", (long long)n_draws, (long long)plan.n_draws);
-    hipSetDevice(h->device);
-    hipStream_t caller = (hipStream_t)stream;
-    hipStream_t s = caller;
-    if (use_graph && caller == nullptr) {       // as cmdgen_sample_chain: the legacy default stream cannot be captured
-        if (!h->own_stream) {
-            HIPCHK(h, hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-            HIPCHK(h, hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
-            HIPCHK(h, hipEventCreateWithFlags(&h->ev_out, hipEventDisableTiming));
-        }
-        HIPCHK(h, hipEventRecord(h->ev_in, caller));
-        HIPCHK(h, hipStreamWaitEvent(h->own_stream, h->ev_in, 0));
-        s = h->own_stream;
-    }
-    rc = prepare_inpaint(h, plan); if (rc) return rc;
-    rc = begin_work(h, s); if (rc) return rc;
-    h->last_stream = caller;
-    h->last_chain_joint = false; h->last_chain_inpaint = true;
-    const Dims& d = h->dims;
     const int n_steps = plan.n_steps;
-    {
-        std::vector<int64_t> gid(h->lay.B);
-        for (int b = 0; b < h->lay.B; ++b) gid[b] = pocket_ids_host ? pocket_ids_host[b] : b;
-        HIPCHK(h, hipMemcpyAsync(h->d_gid, gid.data(), gid.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        HIPCHK(h, hipStreamSynchronize(s));          // gid is a stack vector
-    }
+    std::vector<float> tables = plan_tables(plan.coef, plan.coef2, plan.iop);
+    const hipStream_t caller = (hipStream_t)stream;
+    hipStream_t s; EvalLaunch a;
+    rc = begin_chain(h, CHAIN_INPAINT, tables, n_steps, alloc_inpaint, pocket_ids_host, use_graph, caller, &s, &a); if (rc) return rc;
+    ChainSlot& k = h->chains[CHAIN_INPAINT];
+    const Dims& d = h->dims;
     ChainBuf c = h->inp_chain;
     c.noise = noise; c.seed = seed; c.z_steps = z_steps_out; c.pocket_steps = pocket_steps_out;
     const InpaintBuf ip = h->inp;
-    const ChainState st0{0, n_steps, 0, 0};
-    HIPCHK(h, hipMemcpyAsync(c.state, &st0, sizeof st0, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemsetAsync(c.check, 0, (size_t)(n_steps + 3) * 2 * sizeof(unsigned int), s));
-    HIPCHK(h, hipMemsetAsync(h->inp_cog, 0, 4 * sizeof(unsigned int), s));
-    HIPCHK(h, hipStreamSynchronize(s));              // st0 is on the stack
-    EvalLaunch a = make_launch(h);
-    ++h->eval_gen;
-    if (h->kernel_profiling && !use_graph) a.prof_events = h->prof_events;
     cmdgen_launch_chain_init(h->lay, d, c, pocket_x, pocket_onehot, s);
     cmdgen_launch_inpaint_prep(h->lay, d, c, ip, phar_x, phar_onehot, phar_fixed, pocket_x, s);
-    if (opt_of(h, "pocket_cache", 1) != 0 && h->lay.Np > 0) {
-        float* const* k = h->inp_pk;
-        cmdgen_build_pocket_cache(a, c.z_phar, c.xh_pocket, k[6], k[0], k[1], k[2], k[3], k[4], k[5], s);
-        a.pcache = PocketCache{k[0], k[1], k[2], k[3], k[4], k[5]};
-    }
+    build_pocket_cache(h, k, c, a, s);
     EvalLaunch a2 = a;
     a2.skip_count = 1;                               // k_inpaint_step_count ran pass 1 of the graph
     cmdgen_launch_eval(a, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, s, nullptr);   // evaluation 0 (t = 1)
-    auto one_step = [&](hipStream_t ss) {
+    // the tables, the known rows and the mask are slot buffers (a new plan prepares the slot again); the caller's pointers are the key
+    const void* key[6] = {noise, z_steps_out, pocket_steps_out, nullptr, nullptr, s};
+    rc = run_steps(h, k, key, seed, n_steps, use_graph, s, [&](hipStream_t ss) {
         cmdgen_launch_inpaint_step_count(h->lay, d, c, ip, h->work, h->work.eps_tmp, ss);
         cmdgen_launch_eval(a2, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, ss, nullptr);
-    };
-    if (use_graph) {
-        // a graph of its own (the plain chain's step_graph stays valid); the op index lives on the device, so G captured
-        // ops replay anywhere in the schedule.  The tables, the known rows and the mask are handle buffers: a new plan
-        // re-instantiates it (prepare_inpaint), the caller's pointers below are its key.
-        const void* key[4] = {noise, z_steps_out, pocket_steps_out, (const void*)s};
-        int G = (int)opt_of(h, "graph_steps", 8);
-        if (G < 1) G = 1;
-        if (G > n_steps) G = n_steps;
-        if (h->inpaint_graph && (memcmp(key, h->ig_key, sizeof key) != 0 || h->ig_seed != seed || h->ig_steps != G)) {
-            hipGraphExecDestroy(h->inpaint_graph); h->inpaint_graph = nullptr;
-        }
-        if (!h->inpaint_graph) {
-            hipGraph_t g = nullptr;
-            HIPCHK(h, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            for (int i = 0; i < G; ++i) one_step(s);
-            HIPCHK(h, hipStreamEndCapture(s, &g));
-            HIPCHK(h, hipGraphInstantiate(&h->inpaint_graph, g, nullptr, nullptr, 0));
-            hipGraphDestroy(g);
-            memcpy(h->ig_key, key, sizeof key); h->ig_seed = seed; h->ig_steps = G;
-        }
-        for (int i = 0; i < n_steps / G; ++i) HIPCHK(h, hipGraphLaunch(h->inpaint_graph, s));
-        for (int i = 0; i < n_steps % G; ++i) one_step(s);
-    } else {
-        for (int i = 0; i < n_steps; ++i) one_step(s);
-    }
+    });
+    if (rc) return rc;
     // decode: k_chain_final reads its draw from row 1 + K of `noise` (K = n_steps here); the decode draw is the plan's last row
     ChainBuf cf = c;
     if (noise) cf.noise = noise + (size_t)(plan.n_draws - 1 - (1 + n_steps)) * h->lay.Nl * (3 + d.P);
-    cmdgen_launch_chain_final(h->lay, d, cf, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, h->inp_cog, s);
-    HIPCHK(h, hipGetLastError());
-    if (s != caller) {
-        HIPCHK(h, hipEventRecord(h->ev_out, s));
-        HIPCHK(h, hipStreamWaitEvent(caller, h->ev_out, 0));
-    }
-    return CMDGEN_OK;
+    cmdgen_launch_chain_final(h->lay, d, cf, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, k.cog, s);
+    return end_chain(h, caller, s);
 }
 
 extern "C" int cmdgen_chain_status(cmdgen_handle* h, float* max_rel, float* max_cog, int64_t* nan_resets, cmdgen_stream stream) {
     int rc = check_ready(h); if (rc) return rc;
-    const int K = h->last_chain_inpaint ? h->inp_steps : h->last_chain_joint ? h->joint_steps : h->chain_K;
+    const ChainSlot& k = h->chains[h->last_chain];
+    const int K = k.n_steps;
     if (K < 0) return fail(h, CMDGEN_ESTATE, "no chain has run");
-    const unsigned int* check = h->last_chain_inpaint ? h->inp_chain.check : h->last_chain_joint ? h->joint.check : h->chain.check;
-    const unsigned int* cog_slot = h->last_chain_inpaint ? h->inp_cog : h->last_chain_joint ? h->joint_cog : h->d_cog;
     hipSetDevice(h->device);
     HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
     std::vector<unsigned int> chk((size_t)(K + 3) * 2);
-    HIPCHK(h, hipMemcpy(chk.data(), check, chk.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(chk.data(), k.check, chk.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
     float worst = 0.f;
     for (int i = 0; i < K + 2 && worst == worst; ++i) {
         float largest, err;
@@ -1531,7 +1430,7 @@ extern "C" int cmdgen_chain_status(cmdgen_handle* h, float* max_rel, float* max_
         if (rel > worst || rel != rel) worst = rel;      // a NaN sticks: the reference's `assert rel_error < 1e-2` fails on it
     }
     if (max_rel) *max_rel = worst;
-    unsigned int cog; HIPCHK(h, hipMemcpy(&cog, cog_slot, 4, hipMemcpyDeviceToHost));
+    unsigned int cog; HIPCHK(h, hipMemcpy(&cog, k.cog, 4, hipMemcpyDeviceToHost));
     if (max_cog) memcpy(max_cog, &cog, 4);
     unsigned long long cnt[8];
     HIPCHK(h, hipMemcpy(cnt, h->work.counters, sizeof cnt, hipMemcpyDeviceToHost));
@@ -1657,11 +1556,7 @@ extern "C" int cmdgen_time_evaluation(cmdgen_handle* h, const float* xh_phar, co
     if (h->dims.joint) return fail(h, CMDGEN_ESTATE, "cmdgen_time_evaluation supports the conditional model only");
     hipStream_t caller = (hipStream_t)stream, s = caller;
     if (caller == nullptr) {                             // the legacy default stream cannot be captured
-        if (!h->own_stream) {
-            HIPCHK(h, hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-            HIPCHK(h, hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
-            HIPCHK(h, hipEventCreateWithFlags(&h->ev_out, hipEventDisableTiming));
-        }
+        rc = own_stream(h); if (rc) return rc;
         HIPCHK(h, hipDeviceSynchronize());
         s = h->own_stream;
     }

@@ -21,6 +21,24 @@ struct DevBuf {
     void* p = nullptr; size_t bytes = 0;
 };
 
+// Host state of one kind of denoising chain (cmdgen_api.hip): its buffers for the current layout, the plan tables they were
+// prepared for, and its captured steps.  Each kind has a slot of its own, so plain and inpainting chains alternate on a
+// handle without re-preparing or re-capturing.
+enum ChainKind { CHAIN_PLAIN, CHAIN_JOINT, CHAIN_INPAINT, CHAIN_KINDS };
+struct ChainSlot {
+    std::vector<void*> allocs;
+    std::vector<float> tables;             // the uploaded plan tables (coef | coef2 | iop bits), compared to decide a re-prepare
+    int n_steps = -1;                      // denoising steps of the prepared plan (-1: nothing prepared)
+    unsigned int* check = nullptr;         // [n_steps+3][2] (cmdgen_chain_status)
+    ChainState* state = nullptr;
+    unsigned int* cog = nullptr;           // CoG drift of the final sample
+    float* pk[7] = {};                     // PocketCache storage (c, P0, Q0, dh, dP, dQ) and the time pair (0, 1) that builds it
+    hipGraphExec_t graph = nullptr;        // G captured steps, valid for the key below
+    const void* key[6] = {};               // noise, z_steps, pocket_steps, phar_fixed, pocket_fixed, stream
+    unsigned long long seed = 0;
+    int graph_steps = 0;
+};
+
 struct cmdgen_handle {
     cmdgen_config cfg{};
     int device = 0;
@@ -52,44 +70,18 @@ struct cmdgen_handle {
     hipEvent_t idx_ev[2] = {nullptr, nullptr};
     int idx_cur = 0;
     int64_t idx_ints = 0;
-    // chain
-    std::vector<void*> chain_allocs;
-    ChainBuf chain{};
-    int chain_K = -1;
-    bool chain_steps_out = false;
-    unsigned int* d_cog = nullptr;
-    float *pk_c = nullptr, *pk_P0 = nullptr, *pk_Q0 = nullptr, *pk_dh = nullptr, *pk_dP = nullptr, *pk_dQ = nullptr, *pk_t01 = nullptr;   // PocketCache storage
+    // chains
+    ChainSlot chains[CHAIN_KINDS];
+    ChainKind last_chain = CHAIN_PLAIN;    // the kind cmdgen_chain_status reports on
+    ChainBuf chain{};                      // the kernel arguments the slots' buffers back: plain chain
+    JointBuf joint{};                      // joint-model chain
+    float* eps_pocket_tmp = nullptr;       // [Np][3+R] evaluation output of the joint chain
+    ChainBuf inp_chain{};                  // conditional RePaint chain: its z, pocket, posterior rows, checks and state
+    InpaintBuf inp{};
     std::vector<float> user_coef;          // optional host-supplied step table
     int user_coef_K = -1;
-    hipGraphExec_t step_graph = nullptr;
     hipStream_t own_stream = nullptr;      // used when the caller's stream is the legacy default stream (not capturable)
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
-    const float* graph_noise = nullptr; float* graph_zsteps = nullptr; float* graph_psteps = nullptr; hipStream_t graph_stream = nullptr;
-    unsigned long long graph_seed = 0;
-    int graph_steps = 0;
-    // joint-model chain
-    std::vector<void*> joint_allocs;
-    JointBuf joint{};
-    float* eps_pocket_tmp = nullptr;       // [Np][3+R] evaluation output of the joint chain
-    unsigned int* joint_cog = nullptr;
-    int joint_steps = -1;                  // denoising steps of the prepared plan
-    std::vector<int> joint_key;            // (K, resamplings, jump, inpaint) of the prepared plan
-    bool last_chain_joint = false;
-    hipGraphExec_t joint_graph = nullptr;
-    const void* jg_key[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    unsigned long long jg_seed = 0; int jg_steps = 0;
-    // conditional RePaint chain (cmdgen_inpaint_chain): buffers of its own, so plain and inpainting chains can alternate on a handle
-    std::vector<void*> inp_allocs;
-    ChainBuf inp_chain{};                  // z, pocket, op tables' posterior rows (coef), checks and state of the inpainting chain
-    InpaintBuf inp{};
-    unsigned int* inp_cog = nullptr;
-    float* inp_pk[7] = {};                 // its PocketCache storage (c, P0, Q0, dh, dP, dQ) and the pinned time pair
-    int inp_steps = -1;                    // ops of the prepared plan (-1: nothing prepared)
-    std::vector<float> inp_tables;         // the uploaded tables (coef | coef2 | iop bits), compared to decide a re-upload
-    bool last_chain_inpaint = false;
-    hipGraphExec_t inpaint_graph = nullptr;
-    const void* ig_key[4] = {nullptr, nullptr, nullptr, nullptr};
-    unsigned long long ig_seed = 0; int ig_steps = 0;
     TrainState* train = nullptr;           // training workspace (cmdgen_train.hip)
     float* h_norm = nullptr; hipEvent_t norm_ev = nullptr; bool norm_pending = false;   // deferred gradient-norm readback (pinned host float)
     int train_E = 0, train_Ec = 0;         // message / coordinate edges of the last cmdgen_train_forward (cmdgen_query)

@@ -85,51 +85,6 @@ __global__ __launch_bounds__(64) void k_chain_init(Layout lay, Dims d, ChainBuf 
     record_com_check(c.check, c.z_phar, ld, pb, nl, 1.0f, lane);
 }
 
-// one posterior step z_t -> z_s (sample_p_zs_given_zt, conditional_model.py:342-374).
-// The sample's z (<= a few hundred floats) and eps are pulled into LDS with all loads in flight, the index-order sums
-// (COM, checks) then walk LDS instead of paying one global round trip per node; every sum keeps its order, so the
-// results are bit-identical to the straightforward version.
-__global__ __launch_bounds__(64) void k_ddpm_step(Layout lay, Dims d, ChainBuf c, Work w,
-                                                  const float* __restrict__ eps) {
-    extern __shared__ float s_z[];                  // [nl * ld] z of this sample
-    const int b = blockIdx.x, lane = threadIdx.x;
-    const int nl = lay.num_phar[b], np = lay.num_pocket[b];
-    const int pb = lay.phar_base[b], qb = lay.pocket_base[b];
-    const int ld = 3 + d.P, ldq = 3 + d.R;
-    const int step = c.state->step - 1;             // 0-based index of this posterior step (k_readout has counted the evaluation)
-    const float4 cf = c.coef[step];
-    const bool nan_reset = *w.nan_flag != 0;
-    float* zg = c.z_phar + (size_t)pb * ld;
-    const float* eg = eps + (size_t)pb * ld;
-    const int cnt = nl * ld;
-    for (int idx = lane; idx < cnt; idx += 64) s_z[idx] = zg[idx];
-    __syncthreads();
-    // the reference checks z_t (the step's input) after the update; same numbers, recorded first
-    if (!d.no_com) record_com_check(c.check + 2 * (1 + step), s_z, ld, 0, nl, 1.0f, lane);
-    __syncthreads();
-    for (int idx = lane; idx < cnt; idx += 64) {
-        const int i = idx / ld, k = idx - i * ld;
-        float e = eg[idx];
-        if (nan_reset && k < 3) e = 0.f;
-        const float mu = s_z[idx] / cf.x - cf.y * e;
-        s_z[idx] = mu + cf.z * draw(c, lay, 1 + step, b, i, pb + i, k, ld);
-    }
-    __syncthreads();
-    if (!d.no_com) remove_com(s_z, ld, 0, nl, c.xh_pocket, ldq, qb, np, lane);
-    __syncthreads();
-    for (int idx = lane; idx < cnt; idx += 64) {
-        const float v = s_z[idx];
-        zg[idx] = v;
-        if (c.z_steps) c.z_steps[(size_t)step * lay.Nl * ld + (size_t)pb * ld + idx] = v;
-    }
-    if (c.pocket_steps)
-        for (int idx = lane; idx < np * 3; idx += 64) {
-            const int i = idx / 3, k = idx - 3 * i;
-            c.pocket_steps[((size_t)step * lay.Np + qb + i) * 3 + k] = c.xh_pocket[(size_t)(qb + i) * ldq + k];
-        }
-    if (b == 0 && lane == 0 && nan_reset) atomicAdd(&w.counters[4], 1ull);
-}
-
 // p(x, h | z_0): sample_p_xh_given_z0 (conditional_model.py:108-131) + unnormalize + one-hot
 __global__ __launch_bounds__(64) void k_chain_final(Layout lay, Dims d, ChainBuf c, Work w,
                                                     const float* __restrict__ eps,
@@ -198,11 +153,12 @@ __global__ __launch_bounds__(64) void k_chain_drift_fix(Layout lay, Dims d, floa
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// k_step_count: the posterior step z_t -> z_s (as k_ddpm_step) FUSED with pass 1 of the next evaluation's radius
-// graph (k_edge_count, kernels_egnn.hip): both are one-workgroup-per-sample, and the new positions are already in
-// LDS when the step is done - one launch and one global round trip of the positions less per denoising step.
-// 256 threads per sample.  Arithmetic and summation order of the step are those of k_ddpm_step (bit-identical
-// results); the count pass is k_edge_count's (same dist2, same ballots).
+// k_step_count: one posterior step z_t -> z_s (sample_p_zs_given_zt, conditional_model.py:342-374) FUSED with pass 1
+// of the next evaluation's radius graph (k_edge_count, kernels_egnn.hip): both are one-workgroup-per-sample, and the
+// new positions are already in LDS when the step is done - one launch and one global round trip of the positions less
+// per denoising step.  256 threads per sample.  The sample's z is pulled into LDS with all loads in flight; the sums of
+// the step (COM check, centre of mass) walk LDS in node index order; the count pass is k_edge_count's (same dist2,
+// same ballots).
 // ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void k_step_count(Layout lay, Dims d, ChainBuf c, Work w,
                                                     const float* __restrict__ eps) {
@@ -319,11 +275,6 @@ __global__ __launch_bounds__(1024) void k_step_count(Layout lay, Dims d, ChainBu
 void cmdgen_launch_chain_init(const Layout& lay, const Dims& d, const ChainBuf& c, const float* px,
                               const float* poh, hipStream_t s) {
     hipLaunchKernelGGL(k_chain_init, dim3(lay.B), dim3(64), 0, s, lay, d, c, px, poh);
-}
-void cmdgen_launch_ddpm_step(const Layout& lay, const Dims& d, const ChainBuf& c, const Work& w,
-                             const float* eps, hipStream_t s) {
-    // dynamic LDS: the largest sample's z.  (max_n bounds nl; 3 + P floats per node)
-    hipLaunchKernelGGL(k_ddpm_step, dim3(lay.B), dim3(64), (size_t)lay.max_n * (3 + d.P) * sizeof(float), s, lay, d, c, w, eps);
 }
 void cmdgen_launch_step_count(const Layout& lay, const Dims& d, const ChainBuf& c, const Work& w,
                               const float* eps, hipStream_t s) {

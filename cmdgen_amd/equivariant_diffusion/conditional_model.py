@@ -176,37 +176,12 @@ class ConditionalDDPM(EnVariationalDiffusion):
             noise = noise.detach().to(device, torch.float32).contiguous()
         if seed is None:
             seed = fresh_seed()
-        want_steps = return_frames > 1
-        # (a NaN reset on the half matrix engine is re-run on the bf16 split engine before it is believed: hip_backend.run_range_guarded)
-        (xh_phar, xh_pocket, z_steps), st = h.run_range_guarded(
-            lambda: h.sample_chain(px, poh, timesteps, noise=noise, seed=seed, pocket_ids=pocket_ids, want_steps=want_steps,
-                                   use_graph=self.use_hip_graph),
-            h.chain_status)
-        # deferred, non-syncing versions of the reference's per-step checks
-        self.last_chain_status = st
-        assert st['max_rel_com_error'] < 1e-2, f"Mean is not zero, relative_error {st['max_rel_com_error']}"
-        if st['nan_resets']:
-            print('Warning: detected nan, resetting EGNN output to zero.')
-        if st['max_cog'] > 5e-2 and return_frames == 1:
-            print(f"Warning CoG drift with error {st['max_cog']:.3f}. Projecting the positions down.")
-        if return_frames == 1:
-            return xh_phar, xh_pocket, phar_mask, pocket['mask']
+        run = lambda: h.sample_chain(px, poh, timesteps, noise=noise, seed=seed, pocket_ids=pocket_ids,
+                                     want_steps=return_frames > 1, use_graph=self.use_hip_graph)
         # frames: idx = s*return_frames//timesteps for steps with (s*return_frames) % timesteps == 0
         # (conditional_model.py:439-442); frame 0 is overwritten by the final sample (:460-461).
-        out_phar = torch.zeros((return_frames,) + tuple(xh_phar.shape), device=device)
-        out_pocket = torch.zeros((return_frames,) + tuple(xh_pocket.shape), device=device)
-        p_steps = h.last_pocket_steps
-        nd = self.n_dims
-        for s in range(timesteps):
-            if (s * return_frames) % timesteps == 0:
-                idx = (s * return_frames) // timesteps
-                zs, ps = z_steps[timesteps - 1 - s], p_steps[timesteps - 1 - s]          # state after the step with index s
-                out_phar[idx] = torch.cat([zs[:, :nd] * self.norm_values[0],
-                                           zs[:, nd:] * self.norm_values[1] + self.norm_biases[1]], dim=1)
-                out_pocket[idx] = torch.cat([ps * self.norm_values[0], xh_pocket[:, nd:]], dim=1)   # unnormalize_z :897-906
-        out_phar[0], out_pocket[0] = xh_phar, xh_pocket
-        return out_phar, out_pocket, phar_mask, pocket['mask']
-
+        out = self._finish_chain(h, run, self.inpaint_frames(1, 1, timesteps, return_frames), return_frames)
+        return out[0], out[1], phar_mask, pocket['mask']
 
     @torch.no_grad()
     def inpaint(self, phar, pocket, phar_fixed, resamplings=1, jump_length=1, return_frames=1, timesteps=None,
@@ -259,45 +234,18 @@ class ConditionalDDPM(EnVariationalDiffusion):
             seed = fresh_seed()
         phar_mask = utils.num_nodes_to_batch_mask(n_samples, torch.as_tensor(nph), device)
         args = (f32(pocket['x']), f32(pocket['one_hot']), f32(phar['x']), f32(phar['one_hot']), fixed.contiguous())
-        want_steps = return_frames > 1
-        (xh_phar, xh_pocket, z_steps), st = h.run_range_guarded(
-            lambda: h.inpaint_chain(*args, timesteps, resamplings=resamplings, jump_length=jump_length, noise=noise, seed=seed,
-                                    pocket_ids=pocket_ids, want_steps=want_steps, use_graph=self.use_hip_graph),
-            h.chain_status)
-        self.last_chain_status = st
-        assert st['max_rel_com_error'] < 1e-2, f"Mean is not zero, relative_error {st['max_rel_com_error']}"
-        if st['nan_resets']:
-            print('Warning: detected nan, resetting EGNN output to zero.')
-        if st['max_cog'] > 5e-2 and return_frames == 1:
-            print(f"Warning CoG drift with error {st['max_cog']:.3f}. Projecting the positions down.")
-        if return_frames == 1:
-            return xh_phar, xh_pocket, phar_mask, pocket['mask']
-        out_phar = torch.zeros((return_frames,) + tuple(xh_phar.shape), device=device)
-        out_pocket = torch.zeros((return_frames,) + tuple(xh_pocket.shape), device=device)
-        p_steps = h.last_pocket_steps
-        nd = self.n_dims
-        for step, idx in self.inpaint_frames(resamplings, jump_length, timesteps, return_frames):
-            zs, ps = z_steps[step], p_steps[step]
-            out_phar[idx] = torch.cat([zs[:, :nd] * self.norm_values[0],
-                                       zs[:, nd:] * self.norm_values[1] + self.norm_biases[1]], dim=1)
-            out_pocket[idx] = torch.cat([ps * self.norm_values[0], xh_pocket[:, nd:]], dim=1)
-        out_phar[0], out_pocket[0] = xh_phar, xh_pocket
-        return out_phar, out_pocket, phar_mask, pocket['mask']
+        run = lambda: h.inpaint_chain(*args, timesteps, resamplings=resamplings, jump_length=jump_length, noise=noise, seed=seed,
+                                      pocket_ids=pocket_ids, want_steps=return_frames > 1, use_graph=self.use_hip_graph)
+        out = self._finish_chain(h, run, self.inpaint_frames(resamplings, jump_length, timesteps, return_frames), return_frames)
+        return out[0], out[1], phar_mask, pocket['mask']
 
-    def inpaint_frames(self, resamplings, jump_length, timesteps, return_frames):
-        """[(op index, frame index)]: the ops after which inpaint records a frame - the schedule walked as
-        en_diffusion.py:723-813 do, a frame at the end of a resample cycle whose s falls on the frame grid."""
-        schedule = self.get_repaint_schedule(resamplings, jump_length, timesteps)
-        frames, s, step = [], timesteps - 1, 0
-        for i, n_denoise_steps in enumerate(schedule):
-            for j in range(n_denoise_steps):
-                if (n_denoise_steps > jump_length or i == len(schedule) - 1) and (s * return_frames) % timesteps == 0:
-                    frames.append((step, (s * return_frames) // timesteps))
-                if j == n_denoise_steps - 1 and i < len(schedule) - 1:
-                    s = s + jump_length
-                s -= 1
-                step += 1
-        return frames
+    def _chain_frame(self, h, z_steps, step, xh_phar, xh_pocket):
+        """The frame of the state after op `step`: unnormalize_z (:897-906) of z and of the pocket the op left; the
+        pocket's features are fixed."""
+        zs, ps = z_steps[step], h.last_pocket_steps[step]
+        nd = self.n_dims
+        return (torch.cat([zs[:, :nd] * self.norm_values[0], zs[:, nd:] * self.norm_values[1] + self.norm_biases[1]], dim=1),
+                torch.cat([ps * self.norm_values[0], xh_pocket[:, nd:]], dim=1))
 
 
 class SimpleConditionalDDPM(ConditionalDDPM):

@@ -460,6 +460,22 @@ class EnVariationalDiffusion(nn.Module):
             t += stride
         return runs[::-1]
 
+    def inpaint_frames(self, resamplings, jump_length, timesteps, return_frames):
+        """[(op index, frame index)]: the ops after which inpaint records a frame - the schedule walked as
+        en_diffusion.py:723-813 do, a frame at the end of a resample cycle whose s falls on the frame grid.
+        (1, 1) is sample's case: every step whose s falls on the frame grid (:619-623)."""
+        schedule = self.get_repaint_schedule(resamplings, jump_length, timesteps)
+        frames, s, step = [], timesteps - 1, 0
+        for i, n_denoise_steps in enumerate(schedule):
+            for j in range(n_denoise_steps):
+                if (n_denoise_steps > jump_length or i == len(schedule) - 1) and (s * return_frames) % timesteps == 0:
+                    frames.append((step, (s * return_frames) // timesteps))
+                if j == n_denoise_steps - 1 and i < len(schedule) - 1:
+                    s = s + jump_length
+                s -= 1
+                step += 1
+        return frames
+
     def _joint_handle(self, nph, npk, timesteps=None):
         if self.learned_schedule and timesteps is not None and self.T % timesteps != 0:
             # the joint chain's op table takes gamma from the network's TABULATION on the T-grid (gamma[round(step / K * T)]); the reference
@@ -474,8 +490,18 @@ class EnVariationalDiffusion(nn.Module):
         h.set_layout(nph, npk)
         return h
 
-    def _finish_joint(self, h, run, frame_of_step, return_frames):
-        (xh_phar, xh_pocket, z_steps), st = h.run_range_guarded(run, h.chain_status)       # (half engine: a NaN reset is re-run on the bf16 split engine first)
+    def _chain_frame(self, h, z_steps, step, xh_phar, xh_pocket):
+        """The frame of the state after denoising step `step`: unnormalize_z of the joint chain's z row."""
+        nl = xh_phar.shape[0] * xh_phar.shape[1]
+        return self.unnormalize_z(z_steps[step, :nl].view_as(xh_phar), z_steps[step, nl:].view_as(xh_pocket))
+
+    def _finish_chain(self, h, run, frame_of_step, return_frames):
+        """run() queues a chain on handle h and returns (xh_phar, xh_pocket, z_steps); a NaN reset on the half matrix engine
+        is re-run on the bf16 split engine before it is believed (hip_backend.run_range_guarded).  Then the deferred,
+        non-syncing versions of the reference's per-step checks.  -> (xh_phar, xh_pocket), or with return_frames > 1 the
+        frames (en_diffusion.py:619-623 / :786-791): slot idx <- the state after step `step` for (step, idx) in frame_of_step,
+        slot 0 <- the result."""
+        (xh_phar, xh_pocket, z_steps), st = h.run_range_guarded(run, h.chain_status)
         self.last_chain_status = st
         assert st['max_rel_com_error'] < 1e-2, f"Mean is not zero, relative_error {st['max_rel_com_error']}"
         if st['nan_resets']:
@@ -484,14 +510,10 @@ class EnVariationalDiffusion(nn.Module):
             print(f"Warning CoG drift with error {st['max_cog']:.3f}. Projecting the positions down.")
         if return_frames == 1:
             return xh_phar, xh_pocket
-        # frames (en_diffusion.py:619-623 / :786-791): slot idx <- unnormalize_z(z after that step); slot 0 <- the result
         out_phar = torch.zeros((return_frames,) + tuple(xh_phar.shape), device=xh_phar.device)
         out_pocket = torch.zeros((return_frames,) + tuple(xh_pocket.shape), device=xh_phar.device)
-        nl = xh_phar.shape[0] * xh_phar.shape[1]
         for step, idx in frame_of_step:
-            zp = z_steps[step, :nl].view_as(xh_phar)
-            zq = z_steps[step, nl:].view_as(xh_pocket)
-            out_phar[idx], out_pocket[idx] = self.unnormalize_z(zp, zq)
+            out_phar[idx], out_pocket[idx] = self._chain_frame(h, z_steps, step, xh_phar, xh_pocket)
         out_phar[0], out_pocket[0] = xh_phar, xh_pocket
         return out_phar, out_pocket
 
@@ -515,9 +537,7 @@ class EnVariationalDiffusion(nn.Module):
         seed = fresh_seed() if seed is None else seed
         run = lambda: h.joint_chain(timesteps, noise=noise, seed=seed, pocket_ids=pocket_ids,
                                     want_steps=return_frames > 1, use_graph=self.use_hip_graph, device=dev)
-        frames = [(timesteps - 1 - s, (s * return_frames) // timesteps) for s in range(timesteps)
-                  if (s * return_frames) % timesteps == 0]
-        out = self._finish_joint(h, run, frames, return_frames)
+        out = self._finish_chain(h, run, self.inpaint_frames(1, 1, timesteps, return_frames), return_frames)
         phar_mask = utils.num_nodes_to_batch_mask(n_samples, torch.as_tensor(nph), dev)
         pocket_mask = utils.num_nodes_to_batch_mask(n_samples, torch.as_tensor(npk), dev)
         return out[0], out[1], phar_mask, pocket_mask
@@ -546,17 +566,5 @@ class EnVariationalDiffusion(nn.Module):
                     phar_fixed=f32(phar_fixed).reshape(-1), pocket_fixed=f32(pocket_fixed).reshape(-1))
         run = lambda: h.joint_chain(timesteps, resamplings=resamplings, jump_length=jump_length, noise=noise, seed=seed, pocket_ids=pocket_ids,
                                     want_steps=return_frames > 1, use_graph=self.use_hip_graph, **args)
-        frames = []
-        if return_frames > 1:       # walk the schedule as :723-813 do, noting which steps write a frame
-            schedule = self.get_repaint_schedule(resamplings, jump_length, timesteps)
-            s, step = timesteps - 1, 0
-            for i, n_denoise_steps in enumerate(schedule):
-                for j in range(n_denoise_steps):
-                    if (n_denoise_steps > jump_length or i == len(schedule) - 1) and (s * return_frames) % timesteps == 0:
-                        frames.append((step, (s * return_frames) // timesteps))
-                    if j == n_denoise_steps - 1 and i < len(schedule) - 1:
-                        s = s + jump_length
-                    s -= 1
-                    step += 1
-        out = self._finish_joint(h, run, frames, return_frames)
+        out = self._finish_chain(h, run, self.inpaint_frames(resamplings, jump_length, timesteps, return_frames), return_frames)
         return out[0], out[1], phar['mask'], pocket['mask']

@@ -300,6 +300,21 @@ class Handle:
         return out
 
     # ---- the chain
+    @staticmethod
+    def _check_dev(t, shape=None):
+        """t: a contiguous float32 device tensor (of `shape`, when given)."""
+        import torch
+        assert t is not None and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), 'need a contiguous float32 device tensor'
+        assert shape is None or tuple(t.shape) == tuple(shape), (tuple(t.shape), tuple(shape))
+
+    def _pocket_ids(self, pocket_ids):
+        """Global pocket ids of the Philox draws as the int64 pointer the chain entries take (None: 0 .. batch - 1)."""
+        if pocket_ids is None:
+            return None
+        ids = np.ascontiguousarray(np.asarray(pocket_ids, dtype=np.int64))
+        assert len(ids) == self.batch
+        return ids.ctypes.data_as(_i64p)          # (the pointer keeps the array alive)
+
     def set_step_table(self, K: int, coef: 'np.ndarray'):
         a = np.ascontiguousarray(coef, dtype=np.float32)
         assert a.shape == (K + 1, 4)
@@ -311,24 +326,18 @@ class Handle:
         import torch
         P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
         dev = pocket_x.device
-        assert pocket_x.is_cuda and pocket_x.dtype == torch.float32 and pocket_x.is_contiguous()
-        assert pocket_onehot.dtype == torch.float32 and pocket_onehot.is_contiguous()
-        assert tuple(pocket_x.shape) == (self.n_pocket, 3) and tuple(pocket_onehot.shape) == (self.n_pocket, R)
+        self._check_dev(pocket_x, (self.n_pocket, 3))
+        self._check_dev(pocket_onehot, (self.n_pocket, R))
         if noise is not None:
-            assert noise.is_cuda and noise.dtype == torch.float32 and noise.is_contiguous()
-            assert tuple(noise.shape) == (timesteps + 2, self.n_phar, 3 + P), noise.shape
+            self._check_dev(noise, (timesteps + 2, self.n_phar, 3 + P))
         xh_phar = torch.empty((self.n_phar, 3 + P), dtype=torch.float32, device=dev)
         xh_pocket = torch.empty((self.n_pocket, 3 + R), dtype=torch.float32, device=dev)
         z_steps = torch.empty((timesteps, self.n_phar, 3 + P), dtype=torch.float32, device=dev) if want_steps else None
         p_steps = torch.empty((timesteps, self.n_pocket, 3), dtype=torch.float32, device=dev) if want_steps else None
         self.last_pocket_steps = p_steps
-        ids = None
-        if pocket_ids is not None:
-            ids = np.ascontiguousarray(np.asarray(pocket_ids, dtype=np.int64))
-            assert len(ids) == self.batch
         self._check(self.lib.cmdgen_sample_chain(
             self.h, _ptr(pocket_x), _ptr(pocket_onehot), int(timesteps), _ptr(noise), C.c_uint64(seed & (2 ** 64 - 1)),
-            ids.ctypes.data_as(_i64p) if ids is not None else None, _ptr(xh_phar), _ptr(xh_pocket),
+            self._pocket_ids(pocket_ids), _ptr(xh_phar), _ptr(xh_pocket),
             _ptr(z_steps), _ptr(p_steps), int(bool(use_graph)), self._stream()), 'cmdgen_sample_chain')
         return xh_phar, xh_pocket, z_steps
 
@@ -355,23 +364,19 @@ class Handle:
             ptrs = [phar[0], phar[1], pocket[0], pocket[1], phar_fixed, pocket_fixed]
             shapes = [(self.n_phar, 3), (self.n_phar, P), (self.n_pocket, 3), (self.n_pocket, R), (self.n_phar,), (self.n_pocket,)]
             for t, sh in zip(ptrs, shapes):
-                assert t is not None and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == sh, sh
+                self._check_dev(t, sh)
             device = ptrs[0].device
         dev = device if device is not None else torch.device('cuda', self.device_index)
         if noise is not None:
-            assert noise.is_cuda and noise.dtype == torch.float32 and noise.is_contiguous()
+            self._check_dev(noise)
             assert noise.dim() == 2 and noise.shape[1] == row and noise.shape[0] >= n_draws, (noise.shape, n_draws, row)
         xh_phar = torch.empty((self.n_phar, 3 + P), dtype=torch.float32, device=dev)
         xh_pocket = torch.empty((self.n_pocket, 3 + R), dtype=torch.float32, device=dev)
         z_steps = torch.empty((n_steps, row), dtype=torch.float32, device=dev) if want_steps else None
-        ids = None
-        if pocket_ids is not None:
-            ids = np.ascontiguousarray(np.asarray(pocket_ids, dtype=np.int64))
-            assert len(ids) == self.batch
         self._check(self.lib.cmdgen_joint_chain(
             self.h, *[_ptr(t) for t in ptrs], int(timesteps), int(resamplings), int(jump_length), _ptr(noise),
             int(noise.shape[0]) if noise is not None else 0, C.c_uint64(seed & (2 ** 64 - 1)),
-            ids.ctypes.data_as(_i64p) if ids is not None else None, _ptr(xh_phar), _ptr(xh_pocket), _ptr(z_steps),
+            self._pocket_ids(pocket_ids), _ptr(xh_phar), _ptr(xh_pocket), _ptr(z_steps),
             int(bool(use_graph)), self._stream()), 'cmdgen_joint_chain')
         return xh_phar, xh_pocket, z_steps
 
@@ -392,10 +397,10 @@ class Handle:
         P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
         shapes = [(self.n_pocket, 3), (self.n_pocket, R), (self.n_phar, 3), (self.n_phar, P), (self.n_phar,)]
         for t, sh in zip((pocket_x, pocket_onehot, phar_x, phar_onehot, phar_fixed), shapes):
-            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == sh, (tuple(t.shape), sh)
+            self._check_dev(t, sh)
         n_steps, n_draws = self.inpaint_plan(timesteps, resamplings, jump_length)
         if noise is not None:
-            assert noise.is_cuda and noise.dtype == torch.float32 and noise.is_contiguous()
+            self._check_dev(noise)
             assert noise.dim() == 3 and tuple(noise.shape[1:]) == (self.n_phar, 3 + P), noise.shape
         dev = pocket_x.device
         xh_phar = torch.empty((self.n_phar, 3 + P), dtype=torch.float32, device=dev)
@@ -403,14 +408,10 @@ class Handle:
         z_steps = torch.empty((n_steps, self.n_phar, 3 + P), dtype=torch.float32, device=dev) if want_steps else None
         p_steps = torch.empty((n_steps, self.n_pocket, 3), dtype=torch.float32, device=dev) if want_steps else None
         self.last_pocket_steps = p_steps
-        ids = None
-        if pocket_ids is not None:
-            ids = np.ascontiguousarray(np.asarray(pocket_ids, dtype=np.int64))
-            assert len(ids) == self.batch
         self._check(self.lib.cmdgen_inpaint_chain(
             self.h, _ptr(pocket_x), _ptr(pocket_onehot), _ptr(phar_x), _ptr(phar_onehot), _ptr(phar_fixed), int(timesteps),
             int(resamplings), int(jump_length), _ptr(noise), int(noise.shape[0]) if noise is not None else 0,
-            C.c_uint64(seed & (2 ** 64 - 1)), ids.ctypes.data_as(_i64p) if ids is not None else None, _ptr(xh_phar),
+            C.c_uint64(seed & (2 ** 64 - 1)), self._pocket_ids(pocket_ids), _ptr(xh_phar),
             _ptr(xh_pocket), _ptr(z_steps), _ptr(p_steps), int(bool(use_graph)), self._stream()), 'cmdgen_inpaint_chain')
         return xh_phar, xh_pocket, z_steps
 

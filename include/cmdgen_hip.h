@@ -477,8 +477,7 @@ int cmdgen_set_gemm_mode(cmdgen_handle* h, int32_t split_bf16);
  *                        kernels_node16w.hip; default 1), "write_embed" 0|1 (graph pass 2 + k_embed in one launch)
  *   dead work            "dead_skip" 0|1|2 (2, default: every block skips tiles beyond L - l hops of a moving node; 1: the
  *                        last block only; 0: off)
- *   chain                "fused_step" 0|1 (posterior step + graph pass 1 in one kernel), "pocket_cache" 0|1, "graph_steps"
- *                        (denoising steps per captured graph, default 8)
+ *   chain                "graph_steps" (denoising steps per captured graph, default 8)
  *   training step        "wgrad_split" -1|0|1 (-1: three-piece weight gradients wherever the handle runs the split engine), "wgrad_tile" 0|64, "wgrad_split_wgs128", "wgrad_split_wgs64", "wgrad_wgs",
  *                        "dgrad_mt" 0|32|64, "dgrad_tail" 0|1   (see TrainTune in csrc/cmdgen_dev.h);
  *                        "wgrad_stream" 0|1|2 (weight / bias gradients and partial-sum reductions on the handle's second stream beside the chain

@@ -182,6 +182,49 @@ def test_plain_and_inpaint_chains_alternate_on_one_handle():
     h.close()
 
 
+def test_graph_runs_equal_eager_runs_as_the_key_changes():
+    """On one conditional handle, graph-mode plain and inpainting chains each equal their eager run bit for bit (outputs,
+    saved steps, chain status) while one input of the captured graph's key changes at a time: the seed, injected noise
+    against Philox draws, want_steps, graph_steps = 5 at K = 17 (three replays, two eager steps) and a caller's own stream."""
+    cfg = bounded_config(20, 1000)
+    h = hip_backend.Handle(cfg.as_dict(), 0)
+    h.load_state_dict(make_state_dict(cfg, seed=0))
+    pb = make_pockets(5, 'CA', ragged=True, first_index=500)
+    px, poh, fixed, _ = _fixed_inputs(pb, 0.25, np.random.default_rng(5))
+    K = 17
+    h.set_layout(pb.num_nodes_phar, pb.size)
+    nl, n_draws = int(pb.num_nodes_phar.sum()), h.inpaint_plan(K)[1]
+    rng = np.random.default_rng(6)
+    noise = {'plain': dev(rng.normal(size=(K + 2, nl, 3 + cfg.phar_nf)).astype(np.float32)),
+             'inpaint': dev(rng.normal(size=(n_draws, nl, 3 + cfg.phar_nf)).astype(np.float32))}
+    args = {'plain': (dev(pb.x), dev(pb.one_hot)),
+            'inpaint': (dev(pb.x), dev(pb.one_hot), dev(px), dev(poh), dev(np.asarray(fixed, np.float32)))}
+    side = torch.cuda.Stream()
+
+    def run(kind, use_graph, seed, inject=False, want_steps=False, on_side=False):
+        chain = h.sample_chain if kind == 'plain' else h.inpaint_chain
+        with torch.cuda.stream(side if on_side else torch.cuda.current_stream()):
+            out = chain(*args[kind], K, noise=noise[kind] if inject else None, seed=seed, want_steps=want_steps, use_graph=use_graph)
+            st = h.chain_status()
+            arrays = [t.cpu().numpy() for t in out + (h.last_pocket_steps,) if t is not None]
+        return arrays, (st['max_rel_com_error'], st['max_cog'], st['nan_resets'])
+
+    variants = [dict(seed=1), dict(seed=2), dict(seed=2, inject=True), dict(seed=2, want_steps=True),
+                dict(seed=2, graph_steps=5), dict(seed=2, graph_steps=5, on_side=True)]
+    for v in variants:
+        v = dict(v)
+        if 'graph_steps' in v:
+            h.set_option('graph_steps', v.pop('graph_steps'))
+        graph = {kind: run(kind, True, **v) for kind in ('plain', 'inpaint')}       # the two kinds alternate on the handle
+        for kind in ('plain', 'inpaint'):
+            eager = run(kind, False, **v)
+            assert len(graph[kind][0]) == len(eager[0]) == (4 if v.get('want_steps') else 2), (kind, v)
+            for a, b in zip(graph[kind][0], eager[0]):
+                assert np.array_equal(a, b), (kind, v)
+            assert graph[kind][1] == eager[1], (kind, v)
+    h.close()
+
+
 def _check_fixed_points_hold(h, pb, K, r, j, rng):
     px, poh, fixed, pm = _fixed_inputs(pb, 0.25, rng)
     (xh_phar, xh_pocket, _), st = run_inpaint(h, pb, px, poh, fixed, K, r, j, seed=21)

@@ -281,6 +281,58 @@ def test_joint_inpaint_full_size_properties_and_sharding():
     assert np.abs(half_p[:, :3] - full_p[sel][:, :3]).max() < 1e-3 * scale              # same draws whatever the sharding
 
 
+def test_joint_graph_runs_equal_eager_runs_as_the_key_changes():
+    """On one joint handle, graph-mode sample and inpaint runs each equal their eager run while one input of the captured
+    graph's key changes at a time: the seed, injected noise against Philox draws, want_steps, graph_steps = 5 at K = 17 (three
+    replays, two eager steps), a caller's own stream, and the fixed masks on and off.  Types exactly; coordinates and saved
+    steps within the same-seed bound of test_joint_inpaint_full_size_properties_and_sharding (float atomics)."""
+    cfg = joint_cfg(64, 2)
+    h = hip_backend.Handle(cfg.as_dict(), 0)
+    h.load_state_dict(make_state_dict(cfg, seed=3, coord_gain=1e-3))
+    pb = make_pockets(5, 'CA', ragged=True, first_index=500)
+    nl = pb.num_nodes_phar
+    K, P, R = 17, cfg.phar_nf, cfg.residue_nf
+    h.set_layout(nl, pb.size)
+    rng = np.random.default_rng(8)
+    n_phar = int(nl.sum())
+    pm = np.repeat(np.arange(len(nl)), nl)
+    com = np.stack([pb.x[pb.mask == b].mean(0) for b in range(len(nl))])
+    phar_x = (com[pm] + rng.normal(size=(n_phar, 3)) * 2.5).astype(np.float32)
+    phar = (dev(phar_x), dev(np.eye(P, dtype=np.float32)[rng.integers(0, P, n_phar)]))
+    masks = dict(phar=phar, pocket=(dev(pb.x), dev(pb.one_hot)), phar_fixed=dev((rng.random(n_phar) < 0.3).astype(np.float32)),
+                 pocket_fixed=dev(np.ones(len(pb.x), np.float32)))
+    row = n_phar * (3 + P) + len(pb.x) * (3 + R)
+    noise = {fix: dev(rng.normal(size=(h.joint_plan(K, inpaint=fix)[1], row)).astype(np.float32)) for fix in (False, True)}
+    side = torch.cuda.Stream()
+
+    def run(fix, use_graph, seed, inject=False, want_steps=False, on_side=False):
+        with torch.cuda.stream(side if on_side else torch.cuda.current_stream()):
+            out = h.joint_chain(K, noise=noise[fix] if inject else None, seed=seed, want_steps=want_steps, use_graph=use_graph,
+                                **(masks if fix else {}))
+            st = h.chain_status()
+            arrays = [t.cpu().numpy() for t in out if t is not None]
+        return arrays, st
+
+    variants = [dict(seed=1), dict(seed=2), dict(seed=2, inject=True), dict(seed=2, want_steps=True),
+                dict(seed=2, graph_steps=5), dict(seed=2, graph_steps=5, on_side=True)]
+    for v in variants:
+        v = dict(v)
+        if 'graph_steps' in v:
+            h.set_option('graph_steps', v.pop('graph_steps'))
+        graph = {fix: run(fix, True, **v) for fix in (False, True)}           # sample and inpaint alternate on the handle
+        for fix in (False, True):
+            eager = run(fix, False, **v)
+            assert len(graph[fix][0]) == len(eager[0]) == (3 if v.get('want_steps') else 2), (fix, v)
+            (gp, gq, *gz), (ep, eq, *ez) = graph[fix][0], eager[0]
+            scale = max(1.0, np.abs(ep[:, :3]).max(), np.abs(eq[:, :3]).max())
+            assert np.array_equal(gp[:, 3:], ep[:, 3:]) and np.array_equal(gq[:, 3:], eq[:, 3:]), (fix, v)
+            for a, b in [(gp[:, :3], ep[:, :3]), (gq[:, :3], eq[:, :3])] + list(zip(gz, ez)):
+                assert np.abs(a - b).max() < 1e-3 * scale, (fix, v)
+            assert graph[fix][1]['nan_resets'] == eager[1]['nan_resets'], (fix, v)
+            assert graph[fix][1]['max_rel_com_error'] < 1e-2 and eager[1]['max_rel_com_error'] < 1e-2, (fix, v)
+    h.close()
+
+
 # ------------------------------------------------------------------ Python API (the reference's classes)
 def small_joint_module(H=64, L=2, hist=None):
     from cmdgen_amd.equivariant_diffusion.dynamics import EGNNDynamics

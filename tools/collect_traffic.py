@@ -25,7 +25,7 @@ sys.path.insert(0, ROOT)
 
 # kernel key -> substrings of the kernel name (the 128-row edge kernels of kernels_edge128.hip are k_edge128<false> = messages, <true> = coordinates)
 KERNELS = {'edge_msg': ('k_edge_msg', 'k_edge128<false>'), 'node': ('k_node',), 'edge_coord': ('k_edge_coord', 'k_edge128<true>'), 'embed': ('k_embed',),
-           'readout': ('k_readout',), 'ddpm_step': ('k_ddpm_step',), 'edge_count': ('k_edge_count',), 'edge_write': ('k_edge_write',),
+           'readout': ('k_readout',), 'edge_count': ('k_edge_count',), 'edge_write': ('k_edge_write',),
            'write_embed': ('k_write_embed',), 'step_count': ('k_step_count',)}
 
 
