@@ -1543,6 +1543,7 @@ extern "C" int cmdgen_query(cmdgen_handle* h, const char* key, int64_t* value) {
     else if (k == "dead_skip") *value = a.dead_skip;
     else if (k == "eval_gen") *value = h->eval_gen;
     else if (k == "train_half_ran") *value = h->train_fwd_half;
+    else if (k == "train_range_event") *value = h->h_norm && !h->norm_pending ? (int64_t)h->h_norm[1] : 0;     // of the last collected norm
     else if (k == "train_edges") *value = h->train_E;
     else if (k == "train_coord_edges") *value = h->train_Ec;
     else return fail(h, CMDGEN_EINVAL, "unknown query '%s'", key);

@@ -67,7 +67,9 @@ void tr_adamw(size_t n, float* theta, const float* grad, float* m, float* v, flo
               float eps, float wd, float bias1, float bias2_sqrt, float clip, hipStream_t s, const float* sqnorm = nullptr,
               float max_norm = 0.f, int skip_nonfinite = 0);
 void tr_sqsum(size_t n, const float* x, float* out, hipStream_t s);
-void tr_norm_guard(float* sq, const int* nan_flag, hipStream_t s);
+void tr_low_snap(const unsigned long long* counters, unsigned* snap, hipStream_t s);
+void tr_range_event(const int* nan_flag, const unsigned long long* counters, const unsigned* snap, float* out, hipStream_t s);
+void tr_norm_guard(float* sq, const float* shared, const int* nan_flag, const unsigned long long* counters, const unsigned* snap, hipStream_t s);
 void tr_noise(const Layout& lay, const Dims& d, const float* px, const float* poh, const float* qx, const float* qoh, const float* tab,
               const float* eps, float* z_t, float* xh_pocket, float* klsum, hipStream_t s);
 void tr_noise_joint(const Layout& lay, const Dims& d, const float* px, const float* poh, const float* qx, const float* qoh, const float* tab,
@@ -135,6 +137,7 @@ struct TrainState {
     bool split_packs_valid = false;     // the last forward re-packed the transposed split fragments (backward may use them)
     int wsilu = 0;                      // which activations the last forward did NOT store (option wgrad_silu)
     bool fwd_on_half = false;           // the last forward's tile kernels ran on the half engine (fp16 range: a non-finite gradient after it skips the update)
+    const float* shared_event = nullptr;    // where cmdgen_train_range_event put the last forward's range event (summed over ranks by the caller's all-reduce)
     bool bf16 = false;                  // GEMM operands in bf16 (fp32 accumulation); default exact fp32
     const float* theta = nullptr;       // parameters used by the last forward (backward reads the same)
     const float* xh_phar = nullptr; const float* xh_pocket = nullptr;
@@ -151,7 +154,7 @@ struct TrainState {
     // backward node level
     float *dh, *dX, *dagg, *dP, *dQ, *dn, *dhfin, *ddec, *ddeca, *dhdyn, *denca_l, *denca_p;
     float *vel, *qdec1, *qdeca, *qdec_out, *dqdec, *dqdeca;     // velocity [N][4]; residue decoder (joint model's pocket output)
-    float* d_scalar;                    // [4] device scalars (sum of squares, ...)
+    float* d_scalar;                    // [4] device scalars: sum of squares, the range event read back with it, the low-range counter at the forward's start (bits)
     // Weight gradients on a second stream (option wgrad_stream, default on): they are off the chain of data gradients, and most of
     // them are launches that cannot fill the chip (256 x 256 outputs over 4k-36k rows, split-K) - beside the data-gradient kernels they
     // cost a fraction of what they cost alone.  What they read must outlive the main stream's next writer of the same buffer, so the
@@ -551,6 +554,8 @@ extern "C" int cmdgen_train_forward(cmdgen_handle* h, const float* theta, const 
     a.save_split = (h->gemm_split && t->split_packs_valid && H == 256) ? 1 : 0;
     if (h->agg_dirty) { HIPCHK(h, hipMemsetAsync(h->work.agg, 0, NH * sizeof(float), s)); h->agg_dirty = false; }
     a.frag_launches = 0;
+    t->shared_event = nullptr;
+    if (fwd_half) tr_low_snap(w.counters, (unsigned*)(t->d_scalar + 2), s);       // the norm guard compares the low-range counter with this
     cmdgen_launch_eval(a, xh_phar, xh_pocket, t_arr, nullptr, nullptr, eps_phar, eps_pocket, s, nullptr);
     if (!d.joint) cmdgen_launch_nan_fix(a, eps_phar, s);                    // dynamics.py:129-131 (joint: inside k_vel_com)
     cmdgen_launch_save_positions(a, t->X, s);
@@ -1025,22 +1030,38 @@ extern "C" int cmdgen_adamw_step_clipped(cmdgen_handle* h, float* theta, const f
     hipStream_t s = (hipStream_t)stream;
     h->last_stream = s;
     float* sq = h->train->d_scalar;
-    HIPCHK(h, hipMemsetAsync(sq, 0, sizeof(float), s));
+    HIPCHK(h, hipMemsetAsync(sq, 0, 2 * sizeof(float), s));
     tr_sqsum((size_t)n, grad, sq, s);
     const float bias1 = 1.0f - powf(beta1, (float)step), bias2 = 1.0f - powf(beta2, (float)step);
     // the update is queued behind the norm without a host round trip: the clipping coefficient is formed on the device
-    // (after a half-engine forward a non-finite norm skips the update on the device: see k_adamw)
+    // (after a half-engine forward a non-finite norm skips the update on the device: see k_adamw; so does a range event of that forward -
+    // a NaN reset, or rows below the half engine's range - this rank's own, or the all-reduced one of cmdgen_train_range_event)
     const bool guard = h->train && h->train->fwd_on_half;
-    if (guard) tr_norm_guard(sq, (const int*)h->work.nan_flag, s);
+    if (guard) tr_norm_guard(sq, h->train->shared_event, (const int*)h->work.nan_flag, h->work.counters, (const unsigned*)(sq + 2), s);
     tr_adamw((size_t)n, theta, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, lr, beta1, beta2, eps, weight_decay, bias1, sqrtf(bias2), 1.0f, s,
              (max_grad_norm > 0.f || guard) ? sq : nullptr, max_grad_norm, guard ? 1 : 0);
     // (the readback state lives in the handle: a later cmdgen_set_layout that outgrows the workspaces frees the training state)
-    if (!h->h_norm) { HIPCHK(h, hipHostMalloc((void**)&h->h_norm, sizeof(float), hipHostMallocDefault)); HIPCHK(h, hipEventCreateWithFlags(&h->norm_ev, hipEventDisableTiming)); }
-    HIPCHK(h, hipMemcpyAsync(h->h_norm, sq, sizeof(float), hipMemcpyDeviceToHost, s));
+    if (!h->h_norm) { HIPCHK(h, hipHostMalloc((void**)&h->h_norm, 2 * sizeof(float), hipHostMallocDefault)); HIPCHK(h, hipEventCreateWithFlags(&h->norm_ev, hipEventDisableTiming)); }
+    HIPCHK(h, hipMemcpyAsync(h->h_norm, sq, 2 * sizeof(float), hipMemcpyDeviceToHost, s));      // the norm and the guard's range event
     HIPCHK(h, hipEventRecord(h->norm_ev, s));
     h->norm_pending = true;
     if (!grad_norm_host) return CMDGEN_OK;          // deferred: cmdgen_last_grad_norm collects it (the host keeps queueing the next step)
     return cmdgen_last_grad_norm(h, grad_norm_host);
+}
+
+// The last forward's range event (include/cmdgen_hip.h) to out[0]; the next cmdgen_adamw_step_clipped's guard reads it from there, so that a
+// caller who sums it over its ranks (the gradient all-reduce: HipTrainer) makes every rank skip the same step.
+extern "C" int cmdgen_train_range_event(cmdgen_handle* h, float* out, cmdgen_stream stream) {
+    if (!h || !out) return CMDGEN_EINVAL;
+    if (!h->train || !h->train->have_forward) return fail(h, CMDGEN_ESTATE, "no training forward to report on (cmdgen_train_forward)");
+    hipSetDevice(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    TrainState* t = h->train;
+    if (t->fwd_on_half) tr_range_event((const int*)h->work.nan_flag, h->work.counters, (const unsigned*)(t->d_scalar + 2), out, s);
+    else HIPCHK(h, hipMemsetAsync(out, 0, sizeof(float), s));
+    t->shared_event = out;
+    HIPCHK(h, hipGetLastError());
+    return CMDGEN_OK;
 }
 
 extern "C" int cmdgen_last_grad_norm(cmdgen_handle* h, float* grad_norm_host) {

@@ -1620,12 +1620,35 @@ __global__ void k_adamw(size_t n, float* __restrict__ theta, const float* __rest
     const float denom = sqrtf(vm) / bias2_sqrt + eps;
     theta[i] = p - (lr / bias1) * (mi / denom);
 }
-// after a forward on the half engine: a NaN reset of that forward (the evaluation's guard zeroed the velocities - the fp32 reference would not have
-// seen a NaN there) makes the step's norm non-finite, so that k_adamw skips the update and the host repeats the batch on the bf16 engine
-__global__ void k_norm_guard(float* __restrict__ sq, const int* __restrict__ nan_flag) {
-    if (*nan_flag) *sq = __int_as_float(0x7fc00000);
+// The half engine's range events of a training forward, as one float that may be summed over ranks: TR_EVENT_RESET for a NaN reset (the
+// evaluation's guard zeroed the velocities - the fp32 reference would not have seen a NaN there), TR_EVENT_LOW when the tile producers counted
+// rows below HALF_LOW_TAU (the counter slot moved since k_low_snap at the forward's start; its low 32 bits suffice: no forward counts 2^32 rows).
+#define TR_EVENT_RESET 1.0f
+#define TR_EVENT_LOW 4096.0f
+__device__ __forceinline__ float range_event(const int* nan_flag, const unsigned long long* counters, const unsigned* snap) {
+    return (*nan_flag ? TR_EVENT_RESET : 0.f) + ((unsigned)counters[HALF_LOW_SLOT] != *snap ? TR_EVENT_LOW : 0.f);
 }
-void tr_norm_guard(float* sq, const int* nan_flag, hipStream_t s) { hipLaunchKernelGGL(k_norm_guard, dim3(1), dim3(1), 0, s, sq, nan_flag); }
+__global__ void k_low_snap(const unsigned long long* __restrict__ counters, unsigned* __restrict__ snap) { *snap = (unsigned)counters[HALF_LOW_SLOT]; }
+__global__ void k_range_event(const int* __restrict__ nan_flag, const unsigned long long* __restrict__ counters, const unsigned* __restrict__ snap,
+                              float* __restrict__ out) {
+    *out = range_event(nan_flag, counters, snap);
+}
+// after a forward on the half engine: a range event (this rank's, or - `shared` - the sum over the ranks that the gradient all-reduce carried)
+// makes the step's norm non-finite, so that k_adamw skips the update and the host repeats the batch on the bf16 engine; sq[1] keeps the event
+// for the host (it reads it with the norm, on the non-finite path only)
+__global__ void k_norm_guard(float* __restrict__ sq, const float* __restrict__ shared, const int* __restrict__ nan_flag,
+                             const unsigned long long* __restrict__ counters, const unsigned* __restrict__ snap) {
+    const float e = shared ? *shared : range_event(nan_flag, counters, snap);
+    sq[1] = e;
+    if (e > 0.f) sq[0] = __int_as_float(0x7fc00000);
+}
+void tr_low_snap(const unsigned long long* counters, unsigned* snap, hipStream_t s) { hipLaunchKernelGGL(k_low_snap, dim3(1), dim3(1), 0, s, counters, snap); }
+void tr_range_event(const int* nan_flag, const unsigned long long* counters, const unsigned* snap, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(k_range_event, dim3(1), dim3(1), 0, s, nan_flag, counters, snap, out);
+}
+void tr_norm_guard(float* sq, const float* shared, const int* nan_flag, const unsigned long long* counters, const unsigned* snap, hipStream_t s) {
+    hipLaunchKernelGGL(k_norm_guard, dim3(1), dim3(1), 0, s, sq, shared, nan_flag, counters, snap);
+}
 __global__ __launch_bounds__(256) void k_sqsum(size_t n, const float* __restrict__ x, float* __restrict__ out) {
     // one atomic per workgroup: thousands of waves adding into the same address serialise (44 us for 3M elements before)
     __shared__ float red[4];

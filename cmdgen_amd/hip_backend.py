@@ -81,6 +81,7 @@ SYMBOLS = [
     ('cmdgen_adamw_step_clipped', C.c_int, [_vp, _fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_float,
                                             C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float), _vp]),
     ('cmdgen_last_grad_norm', C.c_int, [_vp, C.POINTER(C.c_float)]),
+    ('cmdgen_train_range_event', C.c_int, [_vp, _fp, _vp]),
     ('cmdgen_debug_wgrad', C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, C.c_int32, _vp]),
     ('cmdgen_debug_dgrad', C.c_int, [_vp, C.c_int32, _fp, _fp, _fp, _fp, _fp, C.c_int32, C.c_float, _fp, C.c_int32, C.c_int32, _vp]),
     ('cmdgen_debug_sgemm', C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int32, _fp,
@@ -553,6 +554,12 @@ class Handle:
                                                        float(betas[1]), float(eps), float(weight_decay), float(max_grad_norm),
                                                        None if defer else C.byref(out), self._stream()), 'cmdgen_adamw_step_clipped')
         return None if defer else out.value
+
+    def train_range_event(self, out):
+        """The last train_forward's half-engine range event into the one-element device tensor `out` (0 none, +1 NaN reset, +4096 rows below
+        the range); the next adamw_step_clipped skips the update when out[0] > 0 then - sum it over the ranks first to decide for all of them."""
+        self._check_dev(out)
+        self._check(self.lib.cmdgen_train_range_event(self.h, _ptr(out), self._stream()), 'cmdgen_train_range_event')
 
     def last_grad_norm(self) -> float:
         out = C.c_float(0)

@@ -80,7 +80,11 @@ class HipTrainer:
         n = h.param_count()
         dev = next(self.dyn.parameters()).device
         self.theta = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.grad = torch.zeros_like(self.theta)
+        # the flat gradient and, behind it, one slot for the step's half-engine range event (cmdgen_train_range_event): the gradient
+        # all-reduce sums it over the ranks, so that every rank's update guard reads the same value and skips the same step
+        self._grad_ext = torch.zeros(n + 1, dtype=torch.float32, device=dev)
+        self.grad = self._grad_ext[:n]
+        self._range_event = self._grad_ext[n:]
         self.exp_avg = torch.zeros_like(self.theta)
         self.exp_avg_sq = torch.zeros_like(self.theta)
         self.max_exp_avg_sq = torch.zeros_like(self.theta)
@@ -108,6 +112,9 @@ class HipTrainer:
         self.last_grad_norm = None
         self._tab_pinned, self._tab_slot = [None, None], 0
         self._pending = []
+        self._updates_queued = 0            # optimizer_step calls so far (the index dropped_steps refers to)
+        self.dropped_steps = []             # pipelined mode: optimizer_step calls whose update the device skipped (not repeated: see _account)
+        self.half_range_fallbacks = 0       # switches of the training forward from the half engine to the bf16 split engine
 
     # ------------------------------------------------------------------
     def _net(self, z_t, xh_pocket, t, phar_mask, pocket_mask):
@@ -285,14 +292,20 @@ class HipTrainer:
         are queued, so the collective runs behind the remaining differentiation (RCCL on its own stream) and only the
         small head chunk is exposed.  The sum is divided by the world size in ``_allreduce``."""
         self._pending = []
+        # the range event of this rank's forward into the slot behind the gradient, before the first all-reduce (the tail chunk carries it);
+        # one rank alone needs no slot: the update guard then reads the event of its own forward
+        ev = getattr(self, '_range_event', None) if self._dp_active() else None
+        if ev is not None:
+            self.h.train_range_event(ev)
         if not self._dp_active() or not self.overlap_allreduce:
             self.h.train_backward(d_eps, self.grad, d_eps_q)
             return
         import torch.distributed as dist
-        first = 0
+        first, n = 0, self.grad.numel()
         for last, lo, hi in self.grad_chunks():
             self.h.train_backward_stages(d_eps, self.grad, first, last, d_eps_q)
-            self._pending.append(dist.all_reduce(self.grad[lo:hi], group=self.group, async_op=True))
+            buf = self._grad_ext[lo:hi + 1] if ev is not None and hi == n else self.grad[lo:hi]
+            self._pending.append(dist.all_reduce(buf, group=self.group, async_op=True))
             first = last + 1
 
     def _allreduce(self):
@@ -304,8 +317,9 @@ class HipTrainer:
                     work.wait()
                 self._pending = []
             else:
-                wait_collective(dist.all_reduce(self.grad, group=self.group, async_op=True))          # one flat bucket over RCCL
-            self.grad.div_(world)
+                buf = self._grad_ext if getattr(self, '_range_event', None) is not None else self.grad      # (with the event slot)
+                wait_collective(dist.all_reduce(buf, group=self.group, async_op=True))          # one flat bucket over RCCL
+            self.grad.div_(world)                       # (the range event stays a sum)
 
     def broadcast_state(self, src: int = 0):
         """Every replica starts from rank `src`'s parameters and optimizer state (what DDP does at construction,
@@ -320,40 +334,60 @@ class HipTrainer:
     def _collect_norm(self):
         """The deferred gradient norm of the previous step enters the queue of recent norms (pipelined mode)."""
         if self._norm_pending is not None:
-            mx = self._norm_pending
+            mx, on_half, index = self._norm_pending
             self._norm_pending = None
             grad_norm = self.h.last_grad_norm()
             self.last_grad_norm = grad_norm
-            if self._left_half_range(grad_norm):
+            if not self._account(grad_norm, mx, on_half, index):
                 import warnings
-                warnings.warn('the previous training step produced a non-finite gradient on the half matrix engine (an activation beyond fp16\'s 65504): '
-                              'its update was skipped on the device; the forward runs on the bf16 split engine from here on', RuntimeWarning, stacklevel=3)
-                return
-            if self.clip_grad:
-                self.gradnorm_queue.add(float(mx) if grad_norm > mx else grad_norm)
-                if grad_norm > mx:
-                    print(f'Clipped gradient with value {grad_norm:.1f} while allowed {mx:.1f}')
+                self.dropped_steps.append(index)
+                warnings.warn(f'training step {index} (the previous one): {self._event_text()}: its update was skipped on the device and its batch is '
+                              'dropped; the forward runs on the bf16 split engine from here on', RuntimeWarning, stacklevel=3)
 
-    def _left_half_range(self, grad_norm) -> bool:
-        """A non-finite gradient norm after a forward on the half matrix engine (two fp16 pieces per operand: range 65504): the device has skipped
-        the update (k_adamw); switch this handle's training forward to the three-piece bf16 engine (fp32's range).  True when that happened."""
+    def _event_text(self) -> str:
+        """What the guard of the last collected norm saw (cmdgen_train_range_event: +1 NaN reset, +4096 rows below the range; summed over ranks)."""
+        ev = self.h.query('train_range_event')
+        if ev >= 4096 and ev % 4096 == 0:          # low-range rows and no reset (an overflowing model may count low rows too: SiLU of -1e5)
+            return 'activations lay below the half matrix engine\'s precision range (rows with max |a| below 2^-5)'
+        return 'non-finite gradient on the half matrix engine (an activation beyond fp16\'s 65504)'
+
+    def _account(self, grad_norm, mx, on_half: bool, index: int) -> bool:
+        """Book the norm of optimizer_step call `index`, whose forward ran on the half engine when `on_half`; -> False when the device skipped
+        that update.  A non-finite norm never enters the queue of recent norms.  After a half-engine forward it means the update was skipped
+        (k_norm_guard / k_adamw: a range event, or a non-finite gradient): step_count goes back by one - the collect of a pipelined step comes
+        before the next update is queued, so AdamW's bias correction counts applied updates only - and this handle's training forward switches
+        to the three-piece bf16 engine (fp32's range).  A non-finite norm off the half engine is the model's own: the reference carries it on."""
         import math
-        if grad_norm is None or math.isfinite(grad_norm):
+        if not math.isfinite(grad_norm):
+            if not on_half:
+                return True
+            self.step_count -= 1
+            if self.h.get_option('train_half') != 0 and self.h.half_engine_active():
+                self.h.set_option('train_half', 0)
+                self.half_range_fallbacks += 1
             return False
-        if self.h.get_option('train_half') == 0 or not self.h.half_engine_active():
-            return False                    # not the half engine's doing: the reference would carry the NaN on as well
-        self.h.set_option('train_half', 0)
-        self.half_range_fallbacks = getattr(self, 'half_range_fallbacks', 0) + 1
+        if self.clip_grad:
+            self.gradnorm_queue.add(float(mx) if grad_norm > mx else grad_norm)
+            if grad_norm > mx:
+                print(f'Clipped gradient with value {grad_norm:.1f} while allowed {mx:.1f}')
         return True
 
     def optimizer_step(self, max_grad_norm: Optional[float] = None):
         """Adaptive clipping + AdamW(amsgrad) on the flat buffers; returns (grad_norm, max_grad_norm).  With
         ``self.pipelined`` the norm is NOT waited for (returned as None, collected before the next step's bound is formed:
-        ``last_grad_norm`` then holds it), so the host goes on to queue the next step behind this one."""
+        ``last_grad_norm`` then holds it), so the host goes on to queue the next step behind this one.  ``last_skipped``: the device
+        skipped this update (waiting mode; a pipelined step's skip shows one step late, in ``dropped_steps``)."""
+        import math
         self._collect_norm()
         self.step_count += 1
         if self.clip_grad and max_grad_norm is None:                   # 150 % of the recent mean + 2 stdev
             max_grad_norm = 1.5 * self.gradnorm_queue.mean() + 2 * self.gradnorm_queue.std()
+            if not math.isfinite(max_grad_norm):
+                raise RuntimeError(f'non-finite clipping bound {max_grad_norm} from the queue of recent gradient norms')
+        on_half = bool(self.h.query('train_half_ran'))          # this step's forward (read now: the next forward overwrites it)
+        index = self._updates_queued
+        self._updates_queued += 1
+        self.last_skipped = False
         # norm -> clipping coefficient -> update are queued back to back (the coefficient is formed on the device from the
         # bound known beforehand); the norm itself is only read back for the queue of recent norms
         grad_norm = self.h.adamw_step_clipped(self.theta, self.grad, self.exp_avg, self.exp_avg_sq, self.max_exp_avg_sq,
@@ -361,27 +395,22 @@ class HipTrainer:
                                               float(max_grad_norm) if self.clip_grad else 0.0, defer=self.pipelined)
         self.dyn._weights_sig = None            # the sampler's packed copy of the weights is stale now
         if self.pipelined:
-            self._norm_pending = float(max_grad_norm) if self.clip_grad else float('inf')
+            self._norm_pending = (float(max_grad_norm) if self.clip_grad else float('inf'), on_half, index)
             return None, max_grad_norm
         self.last_grad_norm = grad_norm
-        if self._left_half_range(grad_norm):
-            self.step_count -= 1            # the device skipped this update; training_step repeats the batch on the bf16 engine
-            return grad_norm, max_grad_norm
-        if self.clip_grad:
-            self.gradnorm_queue.add(float(max_grad_norm) if grad_norm > max_grad_norm else grad_norm)
-            if grad_norm > max_grad_norm:
-                print(f'Clipped gradient with value {grad_norm:.1f} while allowed {max_grad_norm:.1f}')
+        self.last_skipped = not self._account(grad_norm, max_grad_norm, on_half, index)      # training_step repeats a skipped batch
         return grad_norm, max_grad_norm
 
     def training_step(self, data, t_int=None, eps=None, max_grad_norm: Optional[float] = None):
+        """One step.  Waiting mode: a step the device skipped after a half-engine forward (see _account) is repeated on the bf16 split engine
+        with the same batch and draws, and a warning names the cause.  Pipelined mode: the skip shows when the next step collects the norm -
+        by then that step's forward has run too, on the half engine; both batches are dropped (``dropped_steps``) with a warning each."""
         loss, nll, info = self.loss_and_grad(data, t_int=t_int, eps=eps)
         self._allreduce()
-        before = getattr(self, 'half_range_fallbacks', 0)
         grad_norm, mx = self.optimizer_step(max_grad_norm)
-        if getattr(self, 'half_range_fallbacks', 0) != before and not self.pipelined:
+        if self.last_skipped:
             import warnings
-            warnings.warn('non-finite gradient on the half matrix engine (an activation beyond fp16\'s 65504): the step is repeated on the bf16 split engine',
-                          RuntimeWarning, stacklevel=2)
+            warnings.warn(f'{self._event_text()}: the step is repeated on the bf16 split engine', RuntimeWarning, stacklevel=2)
             loss, nll, info = self.loss_and_grad(data, t_int=t_int, eps=eps)
             self._allreduce()
             grad_norm, mx = self.optimizer_step(max_grad_norm)

@@ -403,6 +403,15 @@ int cmdgen_adamw_step_clipped(cmdgen_handle* h, float* theta, const float* grad,
 /* The norm of the last cmdgen_adamw_step_clipped called with grad_norm_host = NULL (waits for that update only). */
 int cmdgen_last_grad_norm(cmdgen_handle* h, float* grad_norm_host);
 
+/* After a training forward on the half matrix engine, cmdgen_adamw_step_clipped skips the update - its norm comes back
+ * non-finite - when that forward took a NaN reset or counted rows below the engine's range (cmdgen_counters.half_low_range).
+ * This call writes that range event of the last cmdgen_train_forward to dev out[0], stream-ordered: 0 for none, +1 for a NaN
+ * reset, +4096 for low-range rows (0 after a forward off the half engine); the next cmdgen_adamw_step_clipped's guard then
+ * reads out[0] instead of this process's own event.  A data-parallel caller sums the slot over its ranks (with the gradient
+ * all-reduce) before the update, so that every rank skips the same step.  cmdgen_query "train_range_event" returns the
+ * value the guard read, once cmdgen_last_grad_norm (or a waiting update) has brought the norm back. */
+int cmdgen_train_range_event(cmdgen_handle* h, float* out, cmdgen_stream stream);
+
 /* C[M,N] (+)= op(A) op(B) (+ bias) through the training path's exact-fp32 MFMA GEMM (test aid):
  * ta: A stored [K][M]; tb: B stored [N][K] (nn.Linear weight); accumulate bit 0: C += ..., bit 1: bf16 operands. */
 int cmdgen_debug_sgemm(cmdgen_handle* h, int32_t ta, int32_t tb, int32_t M, int32_t N, int32_t K, const float* A,
