@@ -42,6 +42,14 @@ void cmdgen_launch_joint_step(const Layout& lay, const Dims& d, const JointBuf& 
 void cmdgen_launch_joint_final(const Layout& lay, const Dims& d, const JointBuf& c, const float* ep, const float* eq,
                                float* xo, float* po, unsigned int* cog, hipStream_t s);
 
+void cmdgen_launch_score_init(const Layout& lay, const Dims& d, const ChainBuf& c, const ScoreBuf& sc, float alpha_T, const float* phx,
+                              const float* phoh, const float* px, const float* poh, float* kl_sums, hipStream_t s);
+void cmdgen_launch_score_step(const Layout& lay, const Dims& d, const ChainBuf& c, const ScoreBuf& sc, const Work& w, const float* eps,
+                              hipStream_t s);
+void cmdgen_launch_score_final(const Layout& lay, const Dims& d, const ChainBuf& c, const ScoreBuf& sc, const Work& w, const float* eps,
+                               hipStream_t s);
+size_t cmdgen_score_step_lds(const Layout& lay, const Dims& d);
+
 #include "cmdgen_host.h"
 
 std::string g_create_error;
@@ -1410,6 +1418,72 @@ extern "C" int cmdgen_inpaint_chain(cmdgen_handle* h, const float* pocket_x, con
     ChainBuf cf = c;
     if (noise) cf.noise = noise + (size_t)(plan.n_draws - 1 - (1 + n_steps)) * h->lay.Nl * (3 + d.P);
     cmdgen_launch_chain_final(h->lay, d, cf, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, k.cog, s);
+    return end_chain(h, caller, s);
+}
+
+// ---------------------------------------------------------------------------------
+// scoring: ConditionalDDPM.score (kernels_score.hip; the level semantics and the output columns are in include/cmdgen_hip.h)
+// ---------------------------------------------------------------------------------
+// the scoring chain's ChainBuf (coef: one row per level, then the (alpha_T, sigma_T) row) and the clean rows it noises
+static int alloc_score(cmdgen_handle* h, ChainSlot& k, const float* tables, int) {
+    int rc = alloc_chain_buf(h, k, h->score_chain, tables); if (rc) return rc;
+    const Dims& d = h->dims;
+    const Layout& L = h->lay;
+    void* q;
+    rc = dev_alloc(h, k.allocs, &q, (size_t)L.Nl * (3 + d.P) * sizeof(float), true); if (rc) return rc; h->score.xh0 = (const float*)q;
+    rc = dev_alloc(h, k.allocs, &q, (size_t)L.Np * 3 * sizeof(float), true); if (rc) return rc; h->score.pocket0 = (const float*)q;
+    return 0;
+}
+
+extern "C" int cmdgen_score_chain(cmdgen_handle* h, const float* phar_x, const float* phar_onehot,
+                                  const float* pocket_x, const float* pocket_onehot,
+                                  int32_t n_levels, const int32_t* t_levels_host, const float* level_coef_host,
+                                  const float* noise, uint64_t seed, const int64_t* pocket_ids_host,
+                                  float* level_terms_out, float* kl_sums_out, int32_t use_graph, cmdgen_stream stream) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (h->dims.joint) return fail(h, CMDGEN_ESTATE, "scoring is not supported for the joint model (update_pocket_coords=1): its loss has the pocket's own terms");
+    if (h->dims.no_com) return fail(h, CMDGEN_ESTATE, "scoring is not supported for no_com_projection handles (SimpleConditionalDDPM)");
+    if (!phar_x || !phar_onehot || !pocket_x || !pocket_onehot || !t_levels_host || !level_terms_out || !kl_sums_out)
+        return fail(h, CMDGEN_EINVAL, "null pointer");
+    if (n_levels < 1) return fail(h, CMDGEN_EINVAL, "n_levels=%d must be >= 1", n_levels);
+    const int T = h->cfg.timesteps;
+    for (int i = 0; i < n_levels; ++i)
+        if (t_levels_host[i] < 0 || t_levels_host[i] > T)
+            return fail(h, CMDGEN_EINVAL, "level %d is t=%d: levels must be in [0, %d]", i, t_levels_host[i], T);
+    if (cmdgen_score_step_lds(h->lay, h->dims) > 64 * 1024)
+        return fail(h, CMDGEN_EINVAL, "a sample has %d nodes: the scoring step keeps a sample's positions, z and row sums in LDS (64 KiB)", h->lay.max_n);
+    // one row per level: (alpha_t, sigma_t, t == 0, t / T), then (alpha_T, sigma_T, 0, 1) for the prior KL sums; alpha and sigma are the
+    // caller's when it supplies them (its own fp32 evaluation of the schedule, as cmdgen_set_step_table)
+    std::vector<float> tables((size_t)(n_levels + 1) * 4);
+    for (int i = 0; i <= n_levels; ++i) {
+        const int t = i < n_levels ? t_levels_host[i] : T;
+        const float g = h->gamma[(size_t)t];
+        tables[4 * i + 0] = level_coef_host ? level_coef_host[2 * i] : sqrtf(sigmoid_h(-g));
+        tables[4 * i + 1] = level_coef_host ? level_coef_host[2 * i + 1] : sqrtf(sigmoid_h(g));
+        tables[4 * i + 2] = (i < n_levels && t == 0) ? 1.f : 0.f;
+        tables[4 * i + 3] = (float)t / (float)T;
+    }
+    const float alpha_T = tables[4 * (size_t)n_levels];
+    const hipStream_t caller = (hipStream_t)stream;
+    hipStream_t s; EvalLaunch a;
+    rc = begin_chain(h, CHAIN_SCORE, tables, n_levels, alloc_score, pocket_ids_host, use_graph, caller, &s, &a); if (rc) return rc;
+    ChainSlot& k = h->chains[CHAIN_SCORE];
+    const Dims& d = h->dims;
+    ChainBuf c = h->score_chain;
+    c.noise = noise; c.seed = seed; c.z_steps = nullptr; c.pocket_steps = nullptr;
+    ScoreBuf sc = h->score;
+    sc.out = level_terms_out;
+    cmdgen_launch_score_init(h->lay, d, c, sc, alpha_T, phar_x, phar_onehot, pocket_x, pocket_onehot, kl_sums_out, s);
+    build_pocket_cache(h, k, c, a, s);
+    a.skip_count = 1;                                // k_score_step ran pass 1 of the graph
+    // the level rows and the clean rows are slot buffers; the captured steps read the caller's draws and write its output
+    const void* key[6] = {noise, level_terms_out, nullptr, nullptr, nullptr, s};
+    rc = run_steps(h, k, key, seed, n_levels, use_graph, s, [&](hipStream_t ss) {
+        cmdgen_launch_score_step(h->lay, d, c, sc, h->work, h->work.eps_tmp, ss);
+        cmdgen_launch_eval(a, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, ss, nullptr);
+    });
+    if (rc) return rc;
+    cmdgen_launch_score_final(h->lay, d, c, sc, h->work, h->work.eps_tmp, s);
     return end_chain(h, caller, s);
 }
 

@@ -187,6 +187,14 @@ struct InpaintBuf {             // conditional RePaint chain (cmdgen_inpaint_cha
     int n_steps;                // denoising ops of the schedule (Philox: B draws at 2 + n_steps + op, C draws at 2 + 2 n_steps + op)
 };
 
+struct ScoreBuf {               // scoring chain (cmdgen_score_chain), beside a ChainBuf whose coef rows are one per LEVEL:
+                                // (alpha_t, sigma_t, 1 if t = 0 else 0, t / T); ChainBuf::noise is [n_levels][Nl][3+P] or null
+    const float* xh0;           // [Nl][3+P]   clean normalised phar rows, x centred on the phar centre of mass
+    const float* pocket0;       // [Np][3]     normalised pocket positions in the same frame (the features sit in ChainBuf::xh_pocket)
+    float* out;                 // [n_levels][B][CMDGEN_SC_COLS] raw sums per (level, sample): see include/cmdgen_hip.h
+};
+enum { SC_ERR = 0, SC_ERR_X = 1, SC_LOG_PH = 2, SC_RESET = 3, SC_COLS = 4 };     // = CMDGEN_SC_COLS
+
 struct PocketCache {            // chain-invariant part of k_embed's output for POCKET rows (conditional sampler): the pocket's
                                 // features never change during a chain and the embedding is affine in the time feature, so
                                 //   h(t) = c + t dh,  P(t) = P0 + t dP,  Q(t) = Q0 + t dQ   (dh, dP, dQ: one row of H values each)

@@ -1,5 +1,5 @@
-// cmdgen_sampler.h - device helpers of the conditional sampler kernels (kernels_ddpm.hip, kernels_inpaint.hip).
-// Both translation units are built with -ffp-contract=off, so the same helper rounds the same way in each.
+// cmdgen_sampler.h - device helpers of the conditional sampler kernels (kernels_ddpm.hip, kernels_inpaint.hip, kernels_score.hip).
+// These translation units are built with -ffp-contract=off, so the same helper rounds the same way in each.
 #pragma once
 #include "cmdgen_dev.h"
 

@@ -1,0 +1,252 @@
+// kernels_score.hip - the scoring chain (ConditionalDDPM.score, cmdgen_score_chain): the diffusion loss of a GIVEN pharmacophore in
+// its pocket at a list of noise levels, one network evaluation per level.  Level k of the list (conditional_model.py:198-320, eval mode) is
+//   z_k = alpha_k xh0 + sigma_k eps_k, then remove_mean_batch(z_k.x, pocket.x)            (noised_representation, :158-179)
+//   error_k[b] = sum_except_batch((eps_k - net(z_k, t_k))^2)                              (:249-251)
+// and at a level with t = 0 also log p(h | z_0) (log_pxh_given_z0_without_constants, :58-106).  xh0 is the normalised input centred on
+// the phar centre of mass, the pocket a translated copy; both are made once by k_score_init.  The levels do not depend on each other:
+// every z_k is formed from the clean rows and the level's own draw.
+//
+// One step of the chain is k_score_step + the sampler's evaluation.  k_score_step, one workgroup per sample, reads the level index from
+// the device step counter, reduces the PREVIOUS level's (eps - net)^2 from the evaluation's output, forms the NEXT level's z and counts
+// pass 1 of its radius graph from the positions it holds in LDS - k_step_count's shape (kernels_ddpm.hip).  k_score_final reduces the last
+// level.  The draw of a level is used twice, for z and one step later in the reduction: both read the injected row or regenerate the same
+// Philox counter (seed, global pocket id, level, node), so they see the same numbers.
+//
+// Sums: a node's columns are added in column order, the nodes of a sample in index order (sum_except_batch is a row sum followed by
+// index_add_), by one thread - no float atomics, so a level's entry does not depend on the launch shape or on the other levels.
+// Built with -ffp-contract=off; the projection uses k_step_count's expressions and sum orders.
+#include "cmdgen_sampler.h"
+
+namespace {
+
+__device__ __forceinline__ float sdraw(const ChainBuf& c, const Layout& lay, int level, int b, int local, int node, int comp, int ld) {
+    if (c.noise) return c.noise[((size_t)level * lay.Nl + node) * ld + comp];
+    float z[4];
+    philox_normal4(c.seed, (uint32_t)lay.pocket_gid[b], (uint32_t)(lay.pocket_gid[b] >> 32),
+                   (uint32_t)level, (uint32_t)(local * 4 + (comp >> 2)), z);
+    return z[comp & 3];
+}
+
+__device__ __forceinline__ float cdf_std(float x) { return 0.5f * (1.0f + erff(x / 1.41421356237309515f)); }
+
+// Level `lv` of sample b: (eps - net)^2 over all columns and over the x columns, and at a t = 0 level the categorical term, summed
+// per node into s_row and then in node index order into the level's output row.  c.z_phar still holds the level's z.
+__device__ void reduce_level(const Layout& lay, const Dims& d, const ChainBuf& c, const ScoreBuf& sc, const Work& w,
+                             const float* __restrict__ eps, int lv, int b, float* s_row) {
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int nl = lay.num_phar[b], pb = lay.phar_base[b];
+    const int ld = 3 + d.P;
+    const float4 cf = c.coef[lv];
+    const bool zero = cf.z != 0.f;
+    const bool nan_reset = *w.nan_flag != 0;
+    const float s0cat = cf.y * d.norm_h;                 // sigma_0 on the integer scale of the one-hot
+    for (int i = tid; i < nl; i += nt) {
+        const float* o = eps + (size_t)(pb + i) * ld;
+        float sx = 0.f;
+        for (int k = 0; k < 3; ++k) {
+            const float net = nan_reset ? 0.f : o[k];    // the reference's batch-wide reset of the velocity (dynamics.py:129-131)
+            const float df = sdraw(c, lay, lv, b, i, pb + i, k, ld) - net;
+            sx += df * df;
+        }
+        float sa = sx;
+        for (int k = 3; k < ld; ++k) {
+            const float df = sdraw(c, lay, lv, b, i, pb + i, k, ld) - o[k];
+            sa += df * df;
+        }
+        float lph = 0.f;
+        if (zero) {
+            // log p(h | z_0): the normal around each class integrated over the unit bin, normalised over the classes (k_train_loss's expressions)
+            const float* z = c.z_phar + (size_t)(pb + i) * ld + 3;
+            const float* oh0 = sc.xh0 + (size_t)(pb + i) * ld + 3;
+            float mx = -INFINITY;
+            for (int k = 0; k < d.P; ++k) {
+                const float ctr = z[k] * d.norm_h + d.bias_h - 1.0f;
+                const float lp = logf(cdf_std((ctr + 0.5f) / s0cat) - cdf_std((ctr - 0.5f) / s0cat) + 1e-10f);
+                mx = fmaxf(mx, lp);
+            }
+            float se = 0.f, dot = 0.f, ohs = 0.f;
+            for (int k = 0; k < d.P; ++k) {
+                const float ctr = z[k] * d.norm_h + d.bias_h - 1.0f;
+                const float lp = logf(cdf_std((ctr + 0.5f) / s0cat) - cdf_std((ctr - 0.5f) / s0cat) + 1e-10f);
+                se += expf(lp - mx);
+                const float oh = oh0[k] * d.norm_h + d.bias_h;      // the normalised one-hot un-normalised again (:83)
+                dot += lp * oh; ohs += oh;
+            }
+            lph = dot - (mx + logf(se)) * ohs;
+        }
+        s_row[3 * i] = sa; s_row[3 * i + 1] = sx; s_row[3 * i + 2] = lph;
+    }
+    __syncthreads();
+    if (tid < 3) {
+        float s = 0.f;
+        for (int i = 0; i < nl; ++i) s += s_row[3 * i + tid];        // index order, as index_add_
+        sc.out[((size_t)lv * lay.B + b) * SC_COLS + tid] = s;
+    }
+    if (tid == 3) sc.out[((size_t)lv * lay.B + b) * SC_COLS + SC_RESET] = nan_reset ? 1.f : 0.f;
+    if (b == 0 && tid == 0 && nan_reset) atomicAdd(&w.counters[4], 1ull);
+    __syncthreads();
+}
+
+}  // namespace
+
+// normalize (en_diffusion.py:874-889), centre both node sets on the phar centre of mass (:235-238), and the two sums of the prior KL
+// term (mu_T = alpha_T xh0, :20-56).  The slot keeps the clean rows; ChainBuf::xh_pocket gets the pocket (positions rewritten per level).
+__global__ __launch_bounds__(256) void k_score_init(Layout lay, Dims d, ChainBuf c, ScoreBuf sc, float alpha_T,
+                                                    const float* __restrict__ phar_x, const float* __restrict__ phar_onehot,
+                                                    const float* __restrict__ pocket_x, const float* __restrict__ pocket_onehot,
+                                                    float* __restrict__ kl_sums) {
+    __shared__ float s_mean[3];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int nl = lay.num_phar[b], np = lay.num_pocket[b];
+    const int pb = lay.phar_base[b], qb = lay.pocket_base[b];
+    const int ld = 3 + d.P, ldq = 3 + d.R;
+    float* xh0 = const_cast<float*>(sc.xh0);
+    float* p0 = const_cast<float*>(sc.pocket0);
+    if (tid < 3) {
+        float s = 0.f;
+        for (int i = 0; i < nl; ++i) s += phar_x[(size_t)(pb + i) * 3 + tid] / d.norm_x;      // index order
+        s_mean[tid] = s / fmaxf((float)nl, 1.0f);
+    }
+    __syncthreads();
+    const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
+    for (int i = tid; i < nl; i += 256) {
+        const size_t g = (size_t)(pb + i);
+        float* o = xh0 + g * ld;
+        o[0] = phar_x[g * 3 + 0] / d.norm_x - m0; o[1] = phar_x[g * 3 + 1] / d.norm_x - m1; o[2] = phar_x[g * 3 + 2] / d.norm_x - m2;
+        for (int k = 0; k < d.P; ++k) o[3 + k] = (phar_onehot[g * d.P + k] - d.bias_h) / d.norm_h;
+        for (int k = 0; k < ld; ++k) c.z_phar[g * ld + k] = o[k];
+    }
+    for (int i = tid; i < np; i += 256) {
+        const size_t g = (size_t)(qb + i);
+        const float x0 = pocket_x[g * 3 + 0] / d.norm_x - m0, x1 = pocket_x[g * 3 + 1] / d.norm_x - m1, x2 = pocket_x[g * 3 + 2] / d.norm_x - m2;
+        p0[g * 3 + 0] = x0; p0[g * 3 + 1] = x1; p0[g * 3 + 2] = x2;
+        float* q = c.xh_pocket + g * ldq;
+        q[0] = x0; q[1] = x1; q[2] = x2;
+        for (int k = 0; k < d.R; ++k) q[3 + k] = (pocket_onehot[g * d.R + k] - d.bias_h) / d.norm_h;
+    }
+    __syncthreads();
+    if (tid < 2) {              // 0: x columns, 1: feature columns; row sums added in index order
+        float s = 0.f;
+        for (int i = 0; i < nl; ++i) {
+            const float* o = xh0 + (size_t)(pb + i) * ld;
+            float r = 0.f;
+            for (int k = tid ? 3 : 0; k < (tid ? ld : 3); ++k) { const float a = alpha_T * o[k]; r += a * a; }
+            s += r;
+        }
+        kl_sums[2 * b + tid] = s;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// k_score_step: reduce level (step - 1), form level `step` and count pass 1 of its radius graph.  step = ChainState::step is the number of
+// evaluations done, i.e. the index of the level about to be evaluated; FINAL: only the reduction (k_score_final).
+// ------------------------------------------------------------------------------------------------------------
+template <bool FINAL>
+__global__ __launch_bounds__(1024) void k_score_step(Layout lay, Dims d, ChainBuf c, ScoreBuf sc, Work w, const float* __restrict__ eps) {
+    extern __shared__ float4 s_pos[];               // [max_n] positions (phar first), int sdeg[max_n], z [max_n * ld], row sums [3 * max_n]
+    int* sdeg = reinterpret_cast<int*>(s_pos + lay.max_n);
+    float* s_z = reinterpret_cast<float*>(sdeg + lay.max_n);
+    const int ld = 3 + d.P, ldq = 3 + d.R;
+    float* s_row = s_z + (size_t)lay.max_n * ld;
+    __shared__ float s_mean[3];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6, nt = blockDim.x;
+    const int nl = lay.num_phar[b], np = lay.num_pocket[b], n = nl + np;
+    const int pb = lay.phar_base[b], qb = lay.pocket_base[b];
+    const int lv = c.state->step;
+    if (lv > 0) reduce_level(lay, d, c, sc, w, eps, lv - 1, b, s_row);
+    if (FINAL || lv >= c.state->K) return;          // (K = the number of levels: the list is never walked past its end)
+    const float4 cf = c.coef[lv];
+    float* zg = c.z_phar + (size_t)pb * ld;
+    const float* x0g = sc.xh0 + (size_t)pb * ld;
+    const int cnt = nl * ld;
+    for (int idx = tid; idx < cnt; idx += nt) {
+        const int i = idx / ld, k = idx - i * ld;
+        const float a = cf.x * x0g[idx];
+        s_z[idx] = a + cf.y * sdraw(c, lay, lv, b, i, pb + i, k, ld);
+    }
+    for (int i = tid; i < np; i += nt) {
+        const float* q = sc.pocket0 + (size_t)(qb + i) * 3;
+        s_pos[nl + i] = make_float4(q[0], q[1], q[2], 0.f);
+    }
+    __syncthreads();
+    if (tid < 3) {                                  // phar centre of mass, index order (remove_mean_batch :467-475)
+        float sum = 0.f;
+        for (int i = 0; i < nl; ++i) sum += s_z[i * ld + tid];
+        s_mean[tid] = sum / fmaxf((float)nl, 1.0f);
+    }
+    __syncthreads();
+    const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
+    for (int i = tid; i < n; i += nt) {
+        float4 p;
+        if (i < nl) {
+            float* z = s_z + i * ld;
+            z[0] -= m0; z[1] -= m1; z[2] -= m2;
+            p = make_float4(z[0], z[1], z[2], 0.f);
+            w.X0[pb + i] = p;
+            for (int l = 0; l < d.L; ++l) w.ACC[(size_t)l * lay.Nm + pb + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+            p = s_pos[i];
+            p.x -= m0; p.y -= m1; p.z -= m2;
+            float* q = c.xh_pocket + (size_t)(qb + i - nl) * ldq;
+            q[0] = p.x; q[1] = p.y; q[2] = p.z;
+            w.XP[qb + i - nl] = p;
+        }
+        s_pos[i] = p;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < cnt; idx += nt) zg[idx] = s_z[idx];
+    if (wave == 0) record_com_check(c.check + 2 * lv, s_z, ld, 0, nl, 1.0f, lane);        // the level's z (assert_mean_zero_with_mask)
+    // ---- pass 1 of the radius graph of the level's evaluation (as k_edge_count / k_step_count)
+    for (int i = wave; i < n; i += nwaves) {
+        const float4 pi = s_pos[i];
+        int deg = 0, self = 0;
+        for (int j0 = 0; j0 < n; j0 += 64) {
+            const int j = j0 + lane;
+            bool ok = false;
+            if (j < n) {
+                const float r2 = dist2(pi, s_pos[j]);
+                ok = (d.cutoff2 < 0.f) || (r2 <= d.cutoff2);
+            }
+            const unsigned long long m = __ballot(ok);
+            deg += __popcll(m);
+            if (i >= j0 && i < j0 + 64) self = (int)((m >> (i - j0)) & 1ull);
+        }
+        if (lane == 0) { sdeg[i] = deg | (self << 30); w.degL[pb + qb + i] = deg | (self << 30); }
+    }
+    __syncthreads();
+    if (wave == 0) {
+        int e = 0, eph = 0, ens = 0, ensq = 0;
+        for (int i = lane; i < n; i += 64) {
+            const int dg = sdeg[i] & 0x3fffffff; e += dg;
+            if (i < nl) { eph += dg; ens += dg - ((sdeg[i] >> 30) & 1); }
+            else ensq += dg - ((sdeg[i] >> 30) & 1);
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            e += __shfl_xor(e, o); eph += __shfl_xor(eph, o); ens += __shfl_xor(ens, o); ensq += __shfl_xor(ensq, o);
+        }
+        if (lane == 0) { w.pocketE[b] = e; w.pocketEph[b] = eph; w.pocketEns[b] = ens; w.pocketEnsQ[b] = ensq; }
+    }
+    if (b == 0 && tid == 0) {
+        atomicAdd(&w.counters[0], 1ull);                       // evaluations (the one about to run)
+        atomicAdd(&w.counters[3], (unsigned long long)lay.N);  // nodes
+    }
+}
+
+// (The NaN flag read by the reduction was set by the previous level's k_readout; pass 2 of the radius graph of the level formed here
+// clears it after this kernel has read it, as in the sampling chain.)
+
+size_t cmdgen_score_step_lds(const Layout& lay, const Dims& d) {
+    return (size_t)lay.max_n * (sizeof(float4) + sizeof(int)) + (size_t)lay.max_n * (3 + d.P + 3) * sizeof(float);
+}
+void cmdgen_launch_score_init(const Layout& lay, const Dims& d, const ChainBuf& c, const ScoreBuf& sc, float alpha_T, const float* phx,
+                              const float* phoh, const float* px, const float* poh, float* kl_sums, hipStream_t s) {
+    hipLaunchKernelGGL(k_score_init, dim3(lay.B), dim3(256), 0, s, lay, d, c, sc, alpha_T, phx, phoh, px, poh, kl_sums);
+}
+void cmdgen_launch_score_step(const Layout& lay, const Dims& d, const ChainBuf& c, const ScoreBuf& sc, const Work& w, const float* eps,
+                              hipStream_t s) {
+    hipLaunchKernelGGL(k_score_step<false>, dim3(lay.B), dim3(lay.max_n > 128 ? 1024 : 256), cmdgen_score_step_lds(lay, d), s, lay, d, c, sc, w, eps);
+}
+void cmdgen_launch_score_final(const Layout& lay, const Dims& d, const ChainBuf& c, const ScoreBuf& sc, const Work& w, const float* eps,
+                               hipStream_t s) {
+    hipLaunchKernelGGL(k_score_step<true>, dim3(lay.B), dim3(256), cmdgen_score_step_lds(lay, d), s, lay, d, c, sc, w, eps);
+}

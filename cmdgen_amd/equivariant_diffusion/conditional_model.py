@@ -239,6 +239,80 @@ class ConditionalDDPM(EnVariationalDiffusion):
         out = self._finish_chain(h, run, self.inpaint_frames(resamplings, jump_length, timesteps, return_frames), return_frames)
         return out[0], out[1], phar_mask, pocket['mask']
 
+    @torch.no_grad()
+    def score(self, phar, pocket, timesteps=None, repeats=1, noise=None, seed=None, pocket_ids=None, return_levels=False):
+        """How likely the model finds a GIVEN pharmacophore in its pocket: the per-sample negative log-likelihood bound of
+        ``forward`` in eval mode (conditional_model.py:198-320 with lightning_modules.py:211-229), but over a fixed grid of
+        noise levels instead of one random t - the whole level loop runs on the device (cmdgen_score_chain).
+
+        Levels t_k = (k + 1) T / timesteps, k = 0 .. timesteps-1 (``timesteps`` must divide T; default T), each with a draw of
+        its own, plus the t = 0 level:  loss_t = (T / timesteps) sum_k -0.5 w_k error_k.  timesteps = T is the diffusion part of
+        the variational bound itself; smaller values are the reference's estimator on a fixed grid (cmdgen_amd/scoring.py).
+        ``repeats`` evaluates the list that many times with distinct draws and returns the means (and '<name>_repeats' [R, B]).
+
+        phar / pocket: dict(x, one_hot, size, mask) as ``forward`` takes them (raw; not modified).
+        noise [repeats * (timesteps + 1), Nl, 3+phar_nf] (or [repeats, timesteps + 1, Nl, 3+phar_nf]) Gaussian draws to inject: row
+        r (timesteps + 1) + k is level k of repeat r, the last row of a repeat the t = 0 level; seed / pocket_ids as in
+        sample_given_pocket (the draws of a pocket do not depend on how a batch is sharded).
+        -> dict of per-sample tensors [B]: nll, loss_t, loss_0_x, loss_0_h, neg_log_const_0, kl_prior, delta_log_px, log_pN; with
+        return_levels also t_levels [timesteps + 1], level_terms [R, timesteps + 1, B], the weighted terms (the loss profile over t), and
+        level_sums [R, timesteps + 1, B, 4], the raw sums of cmdgen_score_chain (error over all / the x columns, log p(h | z_0), reset flag).
+        A level whose evaluation the NaN guard reset is reported (warning) and makes nll NaN for the whole batch: the reference
+        resets batch-wide, and a reset is never summed in silently."""
+        from .. import scoring
+        K = self.T if timesteps is None else int(timesteps)
+        levels = scoring.level_list(self.T, K)                        # ValueError when K does not divide T
+        R = int(repeats)
+        if R < 1:
+            raise ValueError(f'repeats={repeats} must be >= 1')
+        device = pocket['x'].device
+        n_samples = len(pocket['size'])
+        sizes = pocket['size'].detach().to('cpu', torch.int64).numpy()
+        nph = phar['size'].detach().to('cpu', torch.int64).numpy()
+        if len(nph) != n_samples:
+            raise ValueError(f'phar has {len(nph)} samples, pocket {n_samples}')
+        for m in (phar['mask'], pocket['mask']):
+            if m.numel() > 1 and bool((m[1:] < m[:-1]).any()):
+                raise ValueError('batch masks must be ascending and contiguous')
+        n_phar, ld = int(nph.sum()), self.n_dims + self.phar_nf
+        f32 = lambda t: t.detach().to(device, torch.float32).contiguous()
+        if noise is not None:
+            noise = f32(noise)
+            if noise.dim() == 4:
+                noise = noise.reshape(-1, noise.shape[2], noise.shape[3])
+            if tuple(noise.shape) != (R * (K + 1), n_phar, ld):
+                raise ValueError(f'noise has shape {tuple(noise.shape)}: {R} x {K + 1} levels need [{R * (K + 1)}, {n_phar}, {ld}]')
+        self.refresh_learned_schedule()
+        gamma = np.asarray(self.gamma_table_host(), dtype=np.float32)
+        log_pn = self.size_distribution._table(1, torch.device('cpu')).detach().to(torch.float32).numpy()
+        tab = scoring.level_table(gamma, self.T, self.n_dims, self.norm_values, levels)
+        h = self.dynamics.hip_handle()
+        h.set_layout(nph, sizes)
+        if seed is None:
+            seed = fresh_seed()
+        args = (f32(phar['x']), f32(phar['one_hot']), f32(pocket['x']), f32(pocket['one_hot']))
+        run = lambda: h.score_chain(*args, np.tile(levels, R), level_coef=scoring.level_coef(tab, R), noise=noise, seed=seed,
+                                    pocket_ids=pocket_ids, use_graph=self.use_hip_graph)
+        (terms, kl), st = h.run_range_guarded(run, h.chain_status)
+        self.last_chain_status = st
+        assert st['max_rel_com_error'] < 1e-2, f"Mean is not zero, relative_error {st['max_rel_com_error']}"
+        terms = terms.cpu().numpy().reshape(R, K + 1, n_samples, -1)
+        out = scoring.assemble(terms, kl.cpu().numpy(), gamma, log_pn, self.T, self.n_dims, self.norm_values, levels, nph, sizes)
+        reset = terms[..., scoring.SC_RESET].max(axis=2) > 0             # [R, K + 1]
+        if st['nan_resets'] or reset.any():
+            import warnings
+            bad = sorted({int(levels[k]) for k in np.nonzero(reset.any(axis=0))[0]})
+            warnings.warn(f'score: the NaN guard reset the network output at {int(reset.sum())} level evaluation(s) (t = {bad}): '
+                          'the reference resets the whole batch there, so nll is NaN for this batch', RuntimeWarning, stacklevel=2)
+            out['nll'] = np.full_like(out['nll'], np.nan)
+            out['nll_repeats'][reset.any(axis=1)] = np.nan
+        keep = ['nll', 'loss_t', 'loss_0_x', 'loss_0_h', 'neg_log_const_0', 'kl_prior', 'delta_log_px', 'log_pN']
+        keep += [k for k in out if k.endswith('_repeats')]
+        if return_levels:
+            out['level_sums'] = terms                                       # the raw sums (include/cmdgen_hip.h: CMDGEN_SC_COLS columns)
+            keep += ['t_levels', 'level_terms', 'level_sums']
+        return {k: torch.from_numpy(np.ascontiguousarray(out[k])).to(device) for k in keep}
+
     def _chain_frame(self, h, z_steps, step, xh_phar, xh_pocket):
         """The frame of the state after op `step`: unnormalize_z (:897-906) of z and of the pocket the op left; the
         pocket's features are fixed."""
@@ -287,3 +361,7 @@ class SimpleConditionalDDPM(ConditionalDDPM):
     def inpaint(self, *args, **kwargs):
         raise NotImplementedError('inpainting is not implemented for SimpleConditionalDDPM (no centre-of-mass projection); '
                                   'use ConditionalDDPM')
+
+    def score(self, *args, **kwargs):
+        raise NotImplementedError('score is not implemented for SimpleConditionalDDPM (the scoring chain projects every level to the '
+                                  'centre-of-mass-free subspace); use ConditionalDDPM')

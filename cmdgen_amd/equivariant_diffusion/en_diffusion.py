@@ -542,6 +542,10 @@ class EnVariationalDiffusion(nn.Module):
         pocket_mask = utils.num_nodes_to_batch_mask(n_samples, torch.as_tensor(npk), dev)
         return out[0], out[1], phar_mask, pocket_mask
 
+    def score(self, *args, **kwargs):
+        raise NotImplementedError('score is not implemented for the joint model: its loss has the pocket\'s own terms '
+                                  '(error_t and loss_0_x of the pocket nodes); use ConditionalDDPM')
+
     @torch.no_grad()
     def inpaint(self, phar, pocket, phar_fixed, pocket_fixed, resamplings=1, jump_length=1, return_frames=1,
                 timesteps=None, noise=None, seed=None, pocket_ids=None):

@@ -64,6 +64,7 @@ SYMBOLS = [
     ('cmdgen_inpaint_plan', C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _i64p, _i64p]),
     ('cmdgen_inpaint_chain', C.c_int, [_vp, _fp, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int64,
                                        C.c_uint64, _i64p, _fp, _fp, _fp, _fp, C.c_int32, _vp]),
+    ('cmdgen_score_chain', C.c_int, [_vp, _fp, _fp, _fp, _fp, C.c_int32, _vp, _vp, _fp, C.c_uint64, _i64p, _fp, _fp, C.c_int32, _vp]),
     ('cmdgen_param_count', C.c_int, [_vp, _i64p]),
     ('cmdgen_param_offset', C.c_int, [_vp, C.c_char_p, _i64p, _i64p]),
     ('cmdgen_train_forward', C.c_int, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),
@@ -415,6 +416,36 @@ class Handle:
             C.c_uint64(seed & (2 ** 64 - 1)), self._pocket_ids(pocket_ids), _ptr(xh_phar),
             _ptr(xh_pocket), _ptr(z_steps), _ptr(p_steps), int(bool(use_graph)), self._stream()), 'cmdgen_inpaint_chain')
         return xh_phar, xh_pocket, z_steps
+
+    SC_COLS = 4                      # include/cmdgen_hip.h: CMDGEN_SC_COLS
+
+    def score_chain(self, phar_x, phar_onehot, pocket_x, pocket_onehot, t_levels, level_coef=None, noise=None, seed: int = 0,
+                    pocket_ids: Optional[Sequence[int]] = None, use_graph: bool = True):
+        """ConditionalDDPM.score's device part (cmdgen_score_chain): one evaluation per entry of t_levels (ints in 0 .. T).  Raw phar_x
+        [Nl,3], phar_onehot [Nl,P], pocket_x [Np,3], pocket_onehot [Np,R] device tensors; level_coef host [len(t_levels) + 1, 2] (alpha,
+        sigma per level, then of t = T) or None; noise [len(t_levels), Nl, 3+P] or None (Philox draws, draw counter = index of the level).
+        -> (level_terms [n_levels, batch, SC_COLS], kl_sums [batch, 2]): raw sums, columns as in include/cmdgen_hip.h."""
+        import torch
+        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
+        shapes = [(self.n_phar, 3), (self.n_phar, P), (self.n_pocket, 3), (self.n_pocket, R)]
+        for t, sh in zip((phar_x, phar_onehot, pocket_x, pocket_onehot), shapes):
+            self._check_dev(t, sh)
+        lv = np.ascontiguousarray(np.asarray(t_levels, dtype=np.int32).reshape(-1))
+        n = len(lv)
+        coef = None
+        if level_coef is not None:
+            coef = np.ascontiguousarray(level_coef, dtype=np.float32)
+            assert coef.shape == (n + 1, 2), coef.shape
+        if noise is not None:
+            self._check_dev(noise, (n, self.n_phar, 3 + P))
+        dev = phar_x.device
+        terms = torch.zeros((n, self.batch, self.SC_COLS), dtype=torch.float32, device=dev)
+        kl = torch.zeros((self.batch, 2), dtype=torch.float32, device=dev)
+        self._check(self.lib.cmdgen_score_chain(
+            self.h, _ptr(phar_x), _ptr(phar_onehot), _ptr(pocket_x), _ptr(pocket_onehot), n, lv.ctypes.data_as(C.c_void_p),
+            coef.ctypes.data_as(C.c_void_p) if coef is not None else None, _ptr(noise), C.c_uint64(seed & (2 ** 64 - 1)),
+            self._pocket_ids(pocket_ids), _ptr(terms), _ptr(kl), int(bool(use_graph)), self._stream()), 'cmdgen_score_chain')
+        return terms, kl
 
     # ---- training step (flat parameter / gradient buffers are torch tensors owned by the caller)
     def param_count(self) -> int:

@@ -393,3 +393,50 @@ class PharPocketDDPM(nn.Module):
             for k, (name, coords) in enumerate(zip(names, coords_batch), start=1):
                 phar_to_coords.setdefault(f'Molecule_{k}', {}).setdefault(name, []).append(coords)
         return phar_to_coords
+
+    # ------------------------------------------------------------------ scoring
+    def _score_model(self):
+        if not isinstance(self.ddpm, ConditionalDDPM):
+            raise NotImplementedError('scoring needs the conditional model (mode pocket_conditioning): the joint model\'s loss has the '
+                                      'pocket\'s own terms')
+        return self.ddpm
+
+    @torch.no_grad()
+    def score(self, data, timesteps=None, repeats=1, noise=None, seed=None, pocket_ids=None, return_levels=False):
+        """ConditionalDDPM.score of a collated batch, as ``forward(data)`` takes it: the per-sample NLL bound over a fixed grid of
+        noise levels, evaluated on the device.  -> the dict of per-sample tensors ConditionalDDPM.score returns."""
+        ddpm = self._score_model()
+        phar, pocket = self.get_phar_and_pocket(data)
+        return ddpm.score(phar, pocket, timesteps=timesteps, repeats=repeats, noise=noise, seed=seed, pocket_ids=pocket_ids,
+                          return_levels=return_levels)
+
+    @torch.no_grad()
+    def score_phars(self, pdb_file, candidates, pocket_ids=None, ref_ligand=None, timesteps=None, repeats=1, seed=None):
+        """Score candidate pharmacophores in the pocket of a PDB file (ConditionalDDPM.score): lower nll = the model finds the
+        candidate more likely there.
+
+        candidates: a list of point lists [(type name of dataset_info['phar_decoder'], (x, y, z) in Angstrom in the PDB's frame), ...];
+        every candidate gets a copy of the pocket (pocket_ids / ref_ligand as in generate_phars) and is one sample of the batch.
+        -> the dict of ConditionalDDPM.score, entry i of every tensor belonging to candidates[i].  Sample i draws with global pocket
+        id i, so with the same seed a candidate's draws depend on its position in the list only.
+        The return value of generate_phars cannot be scored: its 'Molecule_k' groups the k-th point of ALL samples (quirk Q9), not
+        the points of one sample.  To rank generated samples go through ddpm.sample_given_pocket -> ddpm.score."""
+        assert (pocket_ids is None) ^ (ref_ligand is None)
+        ddpm = self._score_model()
+        decoder = list(self.dataset_info['phar_decoder'])
+        if len(candidates) < 1:
+            raise ValueError('no candidates')
+        for cand in candidates:
+            if len(cand) < 1:
+                raise ValueError('a candidate needs at least one point')
+            for name, _ in cand:
+                if name not in decoder:
+                    raise ValueError(f'unknown pharmacophore type {name!r}: expected one of {decoder}')
+        n = len(candidates)
+        pocket = self._pdb_pocket(pdb_file, n, pocket_ids, ref_ligand)
+        sizes = torch.tensor([len(c) for c in candidates], device=self.device, dtype=INT_TYPE)
+        x = torch.tensor([list(map(float, xyz)) for c in candidates for _, xyz in c], device=self.device, dtype=FLOAT_TYPE).reshape(-1, 3)
+        types = torch.tensor([decoder.index(name) for c in candidates for name, _ in c], device=self.device, dtype=torch.int64)
+        phar = {'x': x, 'one_hot': F.one_hot(types, self.phar_nf).to(FLOAT_TYPE), 'size': sizes,
+                'mask': utils.num_nodes_to_batch_mask(n, sizes, self.device)}
+        return ddpm.score(phar, pocket, timesteps=timesteps, repeats=repeats, seed=seed)

@@ -273,6 +273,37 @@ int cmdgen_inpaint_chain(cmdgen_handle* h, const float* pocket_x, const float* p
                          float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
                          int32_t use_graph, cmdgen_stream stream);
 
+/* Scoring for the CONDITIONAL model (ConditionalDDPM.score): the diffusion loss of a GIVEN pharmacophore in its pocket at a
+ * list of noise levels, one evaluation per level, all on the device.  In the normalised space, with xh0 the phar rows and P0
+ * the pocket both centred on the phar centre of mass (conditional_model.py:198-320 in eval mode), level k with t = t_levels[k]:
+ *   z_k = alpha(t) xh0 + sigma(t) eps_k; (z_k.x, P.x) = remove_mean_batch(z_k.x, P0.x)      (noised_representation)
+ *   net = dynamics(z_k, P, t / T)
+ *   level_terms_out[k][b][0] = sum over the sample's rows and ALL columns of (eps_k - net)^2   (error_t)
+ *   level_terms_out[k][b][1] = the same over the x columns only                               (2 loss_0_x at a t = 0 level)
+ *   level_terms_out[k][b][2] = log p(h | z_k) summed over the rows at a t = 0 level, else 0   (-loss_0_h)
+ *   level_terms_out[k][b][3] = 1 if the evaluation's velocity was reset by the NaN guard (then net.x = 0 entered the sums), else 0
+ *   kl_sums_out[b][0 / 1]    = sum of (alpha_T xh0)^2 over the x / the feature columns         (the two sums of kl_prior)
+ * Only raw sums leave the device: the weights 1 - SNR(gamma(t - 1/T) - gamma(t)), T / K, the constants and log p(N) are scalars of
+ * (t, n_phar, n_pocket) and the caller assembles nll = loss_t + loss_0 + kl_prior - delta_log_px - log_pN from them
+ * (lightning_modules.py:211-229).  Rows are added column by column and then in node index order by one thread (no float atomics):
+ * an entry depends on its level's t and draw only, never on the other levels or on how the steps were launched.
+ *   phar_x dev [Nl,3], phar_onehot dev [Nl,phar_nf], pocket_x dev [Np,3], pocket_onehot dev [Np,residue_nf]: raw, as
+ *          cmdgen_train_noise takes them; copied (normalised) into the handle's buffers before the steps run
+ *   t_levels_host int32 [n_levels], each in 0 .. timesteps (any order, repeats allowed; others are refused)
+ *   level_coef_host float [n_levels + 1][2] or NULL: (alpha, sigma) of every level and, last, of t = T, as the caller's fp32
+ *          evaluation of the schedule gives them (so that they match the reference's torch ops bit for bit); NULL: the library's
+ *   noise  dev [n_levels][Nl][3+phar_nf] or NULL: eps_k.  NULL: Philox keyed by (seed, global pocket id) as cmdgen_sample_chain,
+ *          with the draw counter k (the index in the list) - cmdgen_debug_noise(seed, id, k, ...) returns the same numbers
+ *   level_terms_out dev [n_levels][batch][CMDGEN_SC_COLS], kl_sums_out dev [batch][2]
+ * The joint model (its loss has the pocket's own terms) and no_com_projection handles are refused.
+ * Asynchronous on `stream`; cmdgen_chain_status reports this run's mean-zero check of every z_k and the levels the NaN guard reset. */
+#define CMDGEN_SC_COLS 4
+int cmdgen_score_chain(cmdgen_handle* h, const float* phar_x, const float* phar_onehot,
+                       const float* pocket_x, const float* pocket_onehot,
+                       int32_t n_levels, const int32_t* t_levels_host, const float* level_coef_host,
+                       const float* noise, uint64_t seed, const int64_t* pocket_ids_host,
+                       float* level_terms_out, float* kl_sums_out, int32_t use_graph, cmdgen_stream stream);
+
 /* ---- training step (conditional model) -------------------------------------------------- */
 /* The trainable tensors of EGNNDynamics live in ONE flat fp32 device buffer owned by the caller, in the
  * reference's registration order (the state_dict order below 'ddpm.dynamics.': weight then bias of every
