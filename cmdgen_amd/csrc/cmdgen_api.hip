@@ -1,56 +1,9 @@
 // cmdgen_api.hip - the C ABI of libcmdgen_hip.so (include/cmdgen_hip.h): handle, weight
 // packing, workspaces, the launch sequence of one evaluation and the denoising loop
 // (eager or replayed as a hipGraph).
-#include "cmdgen_dev.h"
-#include "../../include/cmdgen_hip.h"
-
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-#include <cstdlib>
-#include <map>
-#include <string>
-#include <vector>
-
-// launchers implemented next to the kernels
-void cmdgen_launch_eval(const EvalLaunch& a, const float* xh_phar, const float* xh_pocket,
-                        const float* t_arr, const float4* coef, ChainState* chain, float* eps_phar,
-                        float* eps_pocket, hipStream_t s, hipEvent_t* ev);
-void cmdgen_launch_nan_fix(const EvalLaunch& a, float* eps_phar, hipStream_t s);
-void cmdgen_readout_allow_lds(size_t bytes);      // kernels_egnn.hip: k_readout's dynamic LDS above the 64 KiB default (hidden_nf 512)
-void cmdgen_launch_edges(const EvalLaunch& a, const float* xh_phar, const float* xh_pocket, hipStream_t s);
-void cmdgen_build_pocket_cache(const EvalLaunch& a, const float* xh_phar, const float* xh_pocket, const float* t01,
-                               float* c, float* P0, float* Q0, float* dh, float* dP, float* dQ, hipStream_t s);
-void cmdgen_launch_edge_msg_only(const EvalLaunch& a, int layer, hipStream_t s);
-void cmdgen_launch_chain_init(const Layout& lay, const Dims& d, const ChainBuf& c, const float* px,
-                              const float* poh, hipStream_t s);
-void cmdgen_launch_step_count(const Layout& lay, const Dims& d, const ChainBuf& c, const Work& w,
-                              const float* eps, hipStream_t s);
-void cmdgen_launch_debug_noise(unsigned long long seed, long long pocket_id, int draw, int n_nodes, int width,
-                               float* out, hipStream_t s);
-void cmdgen_launch_chain_final(const Layout& lay, const Dims& d, const ChainBuf& c, const Work& w,
-                               const float* eps, float* xo, float* po, unsigned int* cog, hipStream_t s);
-
-void cmdgen_launch_inpaint_prep(const Layout& lay, const Dims& d, const ChainBuf& c, const InpaintBuf& ip, const float* phx,
-                                const float* phoh, const float* fix, const float* px, hipStream_t s);
-void cmdgen_launch_inpaint_step_count(const Layout& lay, const Dims& d, const ChainBuf& c, const InpaintBuf& ip, const Work& w,
-                                      const float* eps, hipStream_t s);
-void cmdgen_launch_joint_init(const Layout& lay, const Dims& d, const JointBuf& c, const float* phx, const float* phoh,
-                              const float* px, const float* poh, hipStream_t s);
-void cmdgen_launch_joint_step(const Layout& lay, const Dims& d, const JointBuf& c, const float* ep, const float* eq, hipStream_t s);
-void cmdgen_launch_joint_final(const Layout& lay, const Dims& d, const JointBuf& c, const float* ep, const float* eq,
-                               float* xo, float* po, unsigned int* cog, hipStream_t s);
-
-void cmdgen_launch_score_init(const Layout& lay, const Dims& d, const ChainBuf& c, const ScoreBuf& sc, float alpha_T, const float* phx,
-                              const float* phoh, const float* px, const float* poh, float* kl_sums, hipStream_t s);
-void cmdgen_launch_score_step(const Layout& lay, const Dims& d, const ChainBuf& c, const ScoreBuf& sc, const Work& w, const float* eps,
-                              hipStream_t s);
-void cmdgen_launch_score_final(const Layout& lay, const Dims& d, const ChainBuf& c, const ScoreBuf& sc, const Work& w, const float* eps,
-                               hipStream_t s);
-size_t cmdgen_score_step_lds(const Layout& lay, const Dims& d);
-
 #include "cmdgen_host.h"
+#include "cmdgen_launch.h"
+#include "cmdgen_wlayout.h"
 
 std::string g_create_error;
 
@@ -150,37 +103,28 @@ static int get_w(cmdgen_handle* h, const std::string& name, size_t n, const std:
     return 0;
 }
 
-static int upload(cmdgen_handle* h, const std::vector<float>& v, const float** dev) {
-    void* p; int rc = dev_alloc(h, h->weight_allocs, &p, v.size() * sizeof(float), false);
+template <class T, class D>
+static int upload(cmdgen_handle* h, const std::vector<T>& v, D* dev) {
+    void* p; int rc = dev_alloc(h, h->weight_allocs, &p, v.size() * sizeof(T), false);
     if (rc) return rc;
-    if (hipMemcpy(p, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail(h, CMDGEN_EHIP, "hipMemcpy H2D failed");
-    *dev = (const float*)p;
+    if (hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return fail(h, CMDGEN_EHIP, "hipMemcpy H2D failed");
+    *dev = (D)p;
     return 0;
 }
 
-// W[out][ld] rows, columns [c0, c0+in) -> MFMA fragment order (see cmdgen_dev.h)
-static std::vector<float> pack_frag(const float* W, int out, int ld, int c0, int in) {
-    const int NT = out / 32, KB = in / 8;
-    std::vector<float> p((size_t)NT * KB * 64 * 4);
+// W[out][in] in one fragment order (cmdgen_wlayout.h): FR = the order's map, PIECES values of type T per weight, made by split(w, piece[])
+template <class FR, int PIECES, class T, class SPLIT>
+static std::vector<T> pack(const float* W, int out, int in, SPLIT split) {
+    const int NT = out / FR::ROWS, KB = in / FR::KBLK;
+    std::vector<T> p((size_t)NT * KB * PIECES * 64 * FR::PER);
     for (int nt = 0; nt < NT; ++nt)
         for (int kb = 0; kb < KB; ++kb)
             for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 4; ++j)
-                    p[(((size_t)nt * KB + kb) * 64 + lane) * 4 + j] =
-                        W[(size_t)(32 * nt + (lane & 31)) * ld + c0 + 8 * kb + 4 * (lane >> 5) + j];
-    return p;
-}
-
-// same matrix in v_mfma_f32_16x16x4_f32 fragment order (16-row tiles)
-static std::vector<float> pack_frag16(const float* W, int out, int ld, int c0, int in) {
-    const int NT = out / 16, KB = in / 16;
-    std::vector<float> p((size_t)NT * KB * 64 * 4);
-    for (int nt = 0; nt < NT; ++nt)
-        for (int kb = 0; kb < KB; ++kb)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 4; ++j)
-                    p[(((size_t)nt * KB + kb) * 64 + lane) * 4 + j] =
-                        W[(size_t)(16 * nt + (lane & 15)) * ld + c0 + 16 * kb + 4 * (lane >> 4) + j];
+                for (int j = 0; j < FR::PER; ++j) {
+                    T piece[PIECES];
+                    split(W[(size_t)FR::row(nt, lane) * in + FR::k0(kb, lane) + FR::koff(j)], piece);
+                    for (int s = 0; s < PIECES; ++s) p[wfrag_piece(nt * KB + kb, PIECES, s, lane) * FR::PER + j] = piece[s];
+                }
     return p;
 }
 
@@ -191,123 +135,26 @@ static inline unsigned short bf16_rne(float f) {
 }
 static inline float bf16_val(unsigned short b) { const uint32_t u = (uint32_t)b << 16; float f; memcpy(&f, &u, 4); return f; }
 
-// same matrix as three bf16 pieces per weight (w = w0 + w1 + w2 exactly up to 2^-24 |w|) in v_mfma_f32_32x32x16_bf16
-// fragment order, the three pieces of a fragment contiguous (cmdgen_split.h)
-static std::vector<unsigned short> pack_split(const float* W, int out, int ld, int c0, int in) {
-    const int NT = out / 32, KB = in / 16;
-    std::vector<unsigned short> p((size_t)NT * KB * 3 * 64 * 8);
-    for (int nt = 0; nt < NT; ++nt)
-        for (int kb = 0; kb < KB; ++kb)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 8; ++j) {
-                    const float w = W[(size_t)(32 * nt + (lane & 31)) * ld + c0 + 16 * kb + 8 * (lane >> 5) + j];
-                    const unsigned short h0 = bf16_rne(w); const float r1 = w - bf16_val(h0);
-                    const unsigned short h1 = bf16_rne(r1); const float r2 = r1 - bf16_val(h1);
-                    const unsigned short h2 = bf16_rne(r2);
-                    const size_t base = (((size_t)nt * KB + kb) * 3) * 64 * 8;
-                    p[base + (0 * 64 + lane) * 8 + j] = h0; p[base + (1 * 64 + lane) * 8 + j] = h1; p[base + (2 * 64 + lane) * 8 + j] = h2;
-                }
-    return p;
-}
-
-// the same three pieces in v_mfma_f32_16x16x32_bf16 fragment order (16-row tiles; k order inside a block of 32 as the
-// A-side reads it: lane group g holds k = 4g .. 4g+3 and 16+4g .. 16+4g+3, cmdgen_split.h)
-static std::vector<unsigned short> pack_split16(const float* W, int out, int ld, int c0, int in) {
-    const int NT = out / 16, KB = in / 32;
-    std::vector<unsigned short> p((size_t)NT * KB * 3 * 64 * 8);
-    for (int nt = 0; nt < NT; ++nt)
-        for (int kb = 0; kb < KB; ++kb)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 8; ++j) {
-                    const int g = lane >> 4;
-                    const int k = 32 * kb + (j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4));
-                    const float w = W[(size_t)(16 * nt + (lane & 15)) * ld + c0 + k];
-                    const unsigned short h0 = bf16_rne(w); const float r1 = w - bf16_val(h0);
-                    const unsigned short h1 = bf16_rne(r1); const float r2 = r1 - bf16_val(h1);
-                    const unsigned short h2 = bf16_rne(r2);
-                    const size_t base = (((size_t)nt * KB + kb) * 3) * 64 * 8;
-                    p[base + (0 * 64 + lane) * 8 + j] = h0; p[base + (1 * 64 + lane) * 8 + j] = h1; p[base + (2 * 64 + lane) * 8 + j] = h2;
-                }
-    return p;
-}
-
-// same matrix as TWO fp16 pieces of (scale * w) per weight in v_mfma_f32_32x32x16_f16 fragment order, the two pieces of a fragment
-// contiguous: Wh[((nt * KB16 + kb) * 2 + s) * 64 + lane] = 8 halves (cmdgen_split.h, "half" engine).  scale is a power of two chosen
-// so that the largest weight lands in [2^11, 2^12): both pieces of every weight that matters are normal fp16 numbers.
-static std::vector<unsigned short> pack_half(const float* W, int out, int ld, int c0, int in, float* scale) {
-    float mx = 0.f;
-    for (int o = 0; o < out; ++o) for (int k = 0; k < in; ++k) mx = std::max(mx, std::fabs(W[(size_t)o * ld + c0 + k]));
-    int e = 0;
-    if (mx > 0.f && std::isfinite(mx)) { int ex; std::frexp(mx, &ex); e = 12 - ex; }      // mx * 2^e in [2^11, 2^12)
-    e = std::max(-40, std::min(40, e));
-    const float sc = std::ldexp(1.0f, e);
-    *scale = sc;
-    const int NT = out / 32, KB = in / 16;
-    std::vector<unsigned short> p((size_t)NT * KB * 2 * 64 * 8);
-    for (int nt = 0; nt < NT; ++nt)
-        for (int kb = 0; kb < KB; ++kb)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 8; ++j) {
-                    const float w = W[(size_t)(32 * nt + (lane & 31)) * ld + c0 + 16 * kb + 8 * (lane >> 5) + j] * sc;
-                    const _Float16 h0 = (_Float16)w; const float r1 = w - (float)h0;
-                    const _Float16 h1 = (_Float16)r1;
-                    unsigned short u0, u1; memcpy(&u0, &h0, 2); memcpy(&u1, &h1, 2);
-                    const size_t base = (((size_t)nt * KB + kb) * 2) * 64 * 8;
-                    p[base + (0 * 64 + lane) * 8 + j] = u0; p[base + (1 * 64 + lane) * 8 + j] = u1;
-                }
-    return p;
-}
-
-// the same two fp16 pieces of (scale * w) in v_mfma_f32_16x16x32_f16 fragment order (16-row tiles; k order inside a block of 32 as pack_split16)
-static std::vector<unsigned short> pack_half16(const float* W, int out, int ld, int c0, int in, float sc) {
-    const int NT = out / 16, KB = in / 32;
-    std::vector<unsigned short> p((size_t)NT * KB * 2 * 64 * 8);
-    for (int nt = 0; nt < NT; ++nt)
-        for (int kb = 0; kb < KB; ++kb)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 8; ++j) {
-                    const int g = lane >> 4;
-                    const int k = 32 * kb + (j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4));
-                    const float w = W[(size_t)(16 * nt + (lane & 15)) * ld + c0 + k] * sc;
-                    const _Float16 h0 = (_Float16)w; const float r1 = w - (float)h0;
-                    const _Float16 h1 = (_Float16)r1;
-                    unsigned short u0, u1; memcpy(&u0, &h0, 2); memcpy(&u1, &h1, 2);
-                    const size_t base = (((size_t)nt * KB + kb) * 2) * 64 * 8;
-                    p[base + (0 * 64 + lane) * 8 + j] = u0; p[base + (1 * 64 + lane) * 8 + j] = u1;
-                }
-    return p;
-}
-
 static int upload_pack(cmdgen_handle* h, const float* W, int out, int in, WPack* wp) {
-    const float* dp;
-    std::vector<float> p = pack_frag(W, out, in, 0, in);
-    int r = upload(h, p, &dp); if (r) return r; wp->w32 = (const float4*)dp;
-    p = pack_frag16(W, out, in, 0, in);
-    r = upload(h, p, &dp); if (r) return r; wp->w16 = (const float4*)dp;
-    const std::vector<unsigned short> ps = pack_split(W, out, in, 0, in);
-    void* q; r = dev_alloc(h, h->weight_allocs, &q, ps.size() * sizeof(unsigned short), false); if (r) return r;
-    if (hipMemcpy(q, ps.data(), ps.size() * sizeof(unsigned short), hipMemcpyHostToDevice) != hipSuccess) return fail(h, CMDGEN_EHIP, "hipMemcpy H2D failed");
-    wp->ws = q;
-    wp->ws16 = nullptr;
-    {
-        float sc = 1.0f;
-        const std::vector<unsigned short> ph = pack_half(W, out, in, 0, in, &sc);
-        r = dev_alloc(h, h->weight_allocs, &q, ph.size() * sizeof(unsigned short), false); if (r) return r;
-        if (hipMemcpy(q, ph.data(), ph.size() * sizeof(unsigned short), hipMemcpyHostToDevice) != hipSuccess) return fail(h, CMDGEN_EHIP, "hipMemcpy H2D failed");
-        wp->wh = q; wp->wh_scale = sc; wp->wh_inv = 1.0f / sc;
-        wp->wh16 = nullptr;
-        if (in % 128 == 0) {
-            const std::vector<unsigned short> ph16 = pack_half16(W, out, in, 0, in, sc);
-            r = dev_alloc(h, h->weight_allocs, &q, ph16.size() * sizeof(unsigned short), false); if (r) return r;
-            if (hipMemcpy(q, ph16.data(), ph16.size() * sizeof(unsigned short), hipMemcpyHostToDevice) != hipSuccess) return fail(h, CMDGEN_EHIP, "hipMemcpy H2D failed");
-            wp->wh16 = q;
-        }
-    }
-    if (in % 128 == 0) {        // the 16-row split GEMM walks four k-blocks of 32 per iteration
-        const std::vector<unsigned short> p16 = pack_split16(W, out, in, 0, in);
-        r = dev_alloc(h, h->weight_allocs, &q, p16.size() * sizeof(unsigned short), false); if (r) return r;
-        if (hipMemcpy(q, p16.data(), p16.size() * sizeof(unsigned short), hipMemcpyHostToDevice) != hipSuccess) return fail(h, CMDGEN_EHIP, "hipMemcpy H2D failed");
-        wp->ws16 = q;
+    float mx = 0.f;
+    for (size_t i = 0; i < (size_t)out * in; ++i) mx = std::max(mx, std::fabs(W[i]));
+    const int e = whalf_exp(mx);
+    const float sc = whalf_pow2(e);
+    wp->wh_scale = sc; wp->wh_inv = whalf_pow2(-e);
+    auto f32 = [](float w, float* p) { p[0] = w; };
+    auto bf16x3 = [](float w, unsigned short* p) {      // w = p0 + p1 + p2 exactly up to 2^-24 |w| (cmdgen_split.h)
+        p[0] = bf16_rne(w); const float r1 = w - bf16_val(p[0]);
+        p[1] = bf16_rne(r1); p[2] = bf16_rne(r1 - bf16_val(p[1]));
+    };
+    auto f16x2 = [sc](float w, _Float16* p) { const float v = w * sc; p[0] = (_Float16)v; p[1] = (_Float16)(v - (float)p[0]); };
+    int r = upload(h, pack<WFrag<32, 4>, 1, float>(W, out, in, f32), &wp->w32); if (r) return r;
+    r = upload(h, pack<WFrag<16, 4>, 1, float>(W, out, in, f32), &wp->w16); if (r) return r;
+    r = upload(h, pack<WFrag<32, 8>, 3, unsigned short>(W, out, in, bf16x3), &wp->ws); if (r) return r;
+    r = upload(h, pack<WFrag<32, 8>, 2, _Float16>(W, out, in, f16x2), &wp->wh); if (r) return r;
+    wp->wh16 = nullptr; wp->ws16 = nullptr;
+    if (in % 128 == 0) {        // the 16-row split / half GEMMs walk four k-blocks of 32 per iteration
+        r = upload(h, pack<WFrag<16, 8>, 2, _Float16>(W, out, in, f16x2), &wp->wh16); if (r) return r;
+        r = upload(h, pack<WFrag<16, 8>, 3, unsigned short>(W, out, in, bf16x3), &wp->ws16); if (r) return r;
     }
     return 0;
 }
@@ -430,7 +277,6 @@ extern "C" int cmdgen_finalize_weights(cmdgen_handle* h) {
 // dynamic LDS of k_edge_count / k_edge_write: float4 position + two ints per node (kernels_egnn.hip)
 static inline size_t edge_lds_bytes(int max_n) { return (size_t)max_n * (sizeof(float4) + 3 * sizeof(int)); }
 static const size_t kEdgeLdsMax = 156 * 1024;      // 160 KiB per CU minus k_edge_write's small static arrays
-void cmdgen_edge_kernels_allow_lds(size_t bytes);  // kernels_egnn.hip: hipFuncSetAttribute above the 64 KiB default
 
 // Rows per tile and grids of the evaluation's launches for the current layout (cmdgen_set_layout, and again after cmdgen_set_option /
 // cmdgen_set_gemm_mode).

@@ -13,20 +13,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define CMDGEN_MAX_LAYERS 16
 #define CMDGEN_MAX_SMALL 64     // upper bound for phar_nf*2, residue_nf*2, joint_nf+1
 
-// ---------------------------------------------------------------------------------
-// Packed weight layout ("B fragments" of v_mfma_f32_32x32x2_f32)
-//
-// A Linear weight W[out][in] (nn.Linear layout) is stored as float4
-//     Wp[(nt * KB + kb) * 64 + lane] = { W[o][k+0], W[o][k+1], W[o][k+2], W[o][k+3] }
-//     o = 32*nt + (lane & 31),  k = 8*kb + 4*(lane >> 5)
-// with nt over out/32 and kb over in/8 (in padded with zeros to a multiple of 8).
-// One 16-byte load per lane then feeds four MFMA k-steps: in step j lanes 0-31 supply
-// k = 8kb+j and lanes 32-63 supply k = 8kb+4+j, and the A operand is read from LDS with
-// the same pairing (one ds_read_b128 per lane).  The k order inside a block of 8 is thus
-// (0,4),(1,5),(2,6),(3,7): a fixed re-association of the fp32 dot product.
-// ---------------------------------------------------------------------------------
-
-struct WPack {                  // one Linear weight in the MFMA fragment orders (see above / below)
+struct WPack {                  // one Linear weight in the MFMA fragment orders ("B fragments"): the index map of each is in cmdgen_wlayout.h
     const float4* w32;          // v_mfma_f32_32x32x2_f32 order  (64- and 32-row tiles)
     const float4* w16;          // v_mfma_f32_16x16x4_f32 order  (16-row tiles)
     const void*   ws;           // three bf16 pieces per weight in v_mfma_f32_32x32x16_bf16 order (cmdgen_split.h); null in training
@@ -294,10 +281,7 @@ __device__ __forceinline__ float dist2(const float4& a, const float4& b) {
 // Rows of A come from LDS (row stride lda floats, 16-byte aligned), weights stream from L2 in
 // fragment order two k-blocks ahead of their use (pinned with sched_barrier so hipcc cannot
 // sink the prefetches back down to their uses; it still places the counted s_waitcnt).
-//
-// 16x16x4 fragment order: Wp16[(nt*KB16 + kb)*64 + lane] = { W[o][k..k+3] },
-//   o = 16*nt + (lane & 15), k = 16*kb + 4*(lane >> 4): step j pairs k-slot g = lane>>4 with
-//   k = 16kb + 4g + j, and the A row is read with one ds_read_b128 at the same k.
+// (fragment orders w32 / w16: cmdgen_wlayout.h; the A row is read with one ds_read_b128 at the k of the lane's piece.)
 // ---------------------------------------------------------------------------------
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
@@ -384,8 +368,8 @@ __device__ __forceinline__ ColVec<MT> col_load(const float* __restrict__ vec, in
 #define CMDGEN_MFMA32(ACC, A, B) ACC = __builtin_amdgcn_mfma_f32_32x32x2f32(A, B, ACC, 0, 0, 0)
 #define CMDGEN_MFMA16(ACC, A, B) ACC = __builtin_amdgcn_mfma_f32_16x16x4f32(A, B, ACC, 0, 0, 0)
 
-// A wave's view of one packed weight matrix: base of its fragment stream and the stride between
-// its n-tiles (float4 units).  kb0_8 / kb_total8 are in blocks of 8 k; cg = the wave's 64-column group.
+// A wave's view of one packed weight matrix (orders w32 / w16, cmdgen_wlayout.h): base of its fragment stream and the stride
+// between its n-tiles (float4 units).  kb0_8 / kb_total8 are in blocks of 8 k; cg = the wave's 64-column group.
 struct FragPtr { const float4* p; unsigned ns; };
 template <int MT>
 __device__ __forceinline__ FragPtr frag_ptr(const WPack& W, int kb_total8, int kb0_8, int cg) {

@@ -165,7 +165,7 @@ __device__ __forceinline__ void store_half(E128Lds& L, const int tid, const int 
         }
 }
 
-// one 16-byte weight fragment: descriptor base (the wave's first 32-column tile) + lane * 16 + a scalar byte offset: no address arithmetic
+// one 16-byte weight fragment (orders ws / wh, cmdgen_wlayout.h): descriptor base (the wave's first 32-column tile) + lane * 16 + a scalar byte offset: no address arithmetic
 // in vector registers, one register (lane * 16) for every weight address of the kernel
 __device__ __forceinline__ efrag w_frag(const __amdgpu_buffer_rsrc_t rw, const int lane, const int soff) {
     return __builtin_bit_cast(efrag, __builtin_amdgcn_raw_buffer_load_b128(rw, lane << 4, soff, 0));

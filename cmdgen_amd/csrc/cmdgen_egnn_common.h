@@ -1,18 +1,14 @@
 // cmdgen_egnn_common.h - what the translation units of the evaluation's tile kernels share (kernels_egnn.hip: readout + the launch
 // sequence; kernels_egnn_graph.hip: radius graph + k_embed; kernels_egnn_msg.hip / _node.hip / _coord.hip: one kernel family each):
 // the LDS row pad, the LDS-only barrier, the accumulator / projection helpers, positions, the edge-tile builders, the tile walk, the
-// matrix-engine selectors of the edge kernels, and the per-family launch entry points.  One family per translation unit keeps an A/B
+// matrix-engine selectors of the edge kernels (the per-family launch entry points: cmdgen_launch.h).  One family per translation unit keeps an A/B
 // rebuild of one kernel under a minute (round 4: 1 m 50 s for the single file).
 #pragma once
 #include "cmdgen_dev.h"
+#include "cmdgen_launch.h"
 #include <hip/hip_ext.h>
 
 #define LDA(H) ((H) + 4)
-
-bool cmdgen_launch_node64(const EvalLaunch& a, int l, hipStream_t s);         // kernels_node64.hip: k_node for large batches
-bool cmdgen_launch_node16w(const EvalLaunch& a, int l, hipStream_t s);        // kernels_node16w.hip: 16-row tiles on eight waves (small batches)
-bool cmdgen_launch_msg128(const EvalLaunch& a, int l, hipStream_t s);         // kernels_edge128.hip: the edge kernels for long lists (128-row tiles)
-bool cmdgen_launch_coord128(const EvalLaunch& a, int l, hipStream_t s);
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for vmcnt(0), i.e.
 // drains every outstanding global store / atomic of the wave (1-3 us each time); the barriers of
@@ -21,15 +17,6 @@ bool cmdgen_launch_coord128(const EvalLaunch& a, int l, hipStream_t s);
 __device__ __forceinline__ void lds_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
-
-// per-family launch entry points (each picks the instantiation for a.d.H and the launch's tile rows)
-void cmdgen_launch_edge_count(const EvalLaunch& a, const float* xh_phar, const float* xh_pocket, hipStream_t s);                 // kernels_egnn_graph.hip
-void cmdgen_launch_edge_write(const EvalLaunch& a, hipStream_t s);
-void cmdgen_launch_embed_tiles(const EvalLaunch& a, int mt, const float* xp, const float* xq, const float* t, const float4* coef, ChainState* chain, hipStream_t s);
-void cmdgen_launch_write_embed_tiles(const EvalLaunch& a, int mt, const float* xp, const float* xq, const float* t, const float4* coef, ChainState* chain, hipStream_t s);   // H = 256
-void cmdgen_launch_msg_tiles(const EvalLaunch& a, int l, hipStream_t s);                                                         // kernels_egnn_msg.hip
-void cmdgen_launch_node_tiles(const EvalLaunch& a, int l, hipStream_t s);                                                        // kernels_egnn_node.hip
-void cmdgen_launch_coord_tiles(const EvalLaunch& a, int l, hipStream_t s);                                                       // kernels_egnn_coord.hip
 
 // ------------------------------------------------------------------------------------
 // shared pieces of the tile kernels

@@ -1,0 +1,69 @@
+// cmdgen_launch.h - the launchers of the evaluation and of the chains: every function one translation unit defines and another
+// calls, declared once.  The calling file AND the defining file include this header, so a changed signature is a compile error
+// instead of an unresolved (or, with default arguments, a silently different) call.  Declarations only: nothing here beyond
+// cmdgen_dev.h's types.
+#pragma once
+#include "cmdgen_dev.h"
+
+// kernels_egnn.hip: one evaluation (radius graph, k_embed, per block the message / node / coordinate launches, k_readout)
+void cmdgen_launch_eval(const EvalLaunch& a, const float* xh_phar, const float* xh_pocket, const float* t_arr, const float4* coef,
+                        ChainState* chain, float* eps_phar, float* eps_pocket, hipStream_t s, hipEvent_t* ev);
+void cmdgen_launch_nan_fix(const EvalLaunch& a, float* eps_phar, hipStream_t s);
+void cmdgen_launch_save_positions(const EvalLaunch& a, float4* X, hipStream_t s);
+void cmdgen_readout_allow_lds(size_t bytes);            // k_readout's dynamic LDS above the 64 KiB default (hidden_nf 512)
+
+// kernels_egnn_graph.hip: radius graph + k_embed
+void cmdgen_launch_edges(const EvalLaunch& a, const float* xh_phar, const float* xh_pocket, hipStream_t s);
+void cmdgen_build_pocket_cache(const EvalLaunch& a, const float* xh_phar, const float* xh_pocket, const float* t01,
+                               float* c, float* P0, float* Q0, float* dh, float* dP, float* dQ, hipStream_t s);
+void cmdgen_edge_kernels_allow_lds(size_t bytes);       // hipFuncSetAttribute above the 64 KiB default
+void cmdgen_launch_edge_count(const EvalLaunch& a, const float* xh_phar, const float* xh_pocket, hipStream_t s);
+void cmdgen_launch_edge_write(const EvalLaunch& a, hipStream_t s);
+
+// per-family launch entry points (each picks the instantiation for a.d.H and the launch's tile rows); the *_hx forms are the same
+// families at the hidden sizes other than 256, built as translation units of their own (kernels_egnn_*_hx.hip, CMDGEN_H_PART)
+void cmdgen_launch_embed_tiles(const EvalLaunch& a, int mt, const float* xp, const float* xq, const float* t, const float4* coef, ChainState* chain, hipStream_t s);
+void cmdgen_launch_embed_tiles_hx(const EvalLaunch& a, int mt, const float* xp, const float* xq, const float* t, const float4* coef, ChainState* chain, hipStream_t s);
+void cmdgen_launch_write_embed_tiles(const EvalLaunch& a, int mt, const float* xp, const float* xq, const float* t, const float4* coef, ChainState* chain, hipStream_t s);   // H = 256
+void cmdgen_embed_only_hx(const EvalLaunch& a, const float* xp, const float* xq, const float* t, hipStream_t s);
+void cmdgen_launch_msg_tiles(const EvalLaunch& a, int l, hipStream_t s);                   // kernels_egnn_msg.hip
+void cmdgen_launch_msg_tiles_hx(const EvalLaunch& a, int l, hipStream_t s);
+void cmdgen_launch_edge_msg_only(const EvalLaunch& a, int layer, hipStream_t s);
+void cmdgen_launch_edge_msg_only_hx(const EvalLaunch& a, int layer, hipStream_t s);
+void cmdgen_launch_node_tiles(const EvalLaunch& a, int l, hipStream_t s);                  // kernels_egnn_node.hip
+void cmdgen_launch_node_tiles_hx(const EvalLaunch& a, int l, hipStream_t s);
+void cmdgen_launch_coord_tiles(const EvalLaunch& a, int l, hipStream_t s);                 // kernels_egnn_coord.hip
+void cmdgen_launch_coord_tiles_hx(const EvalLaunch& a, int l, hipStream_t s);
+bool cmdgen_launch_node64(const EvalLaunch& a, int l, hipStream_t s);         // kernels_node64.hip: k_node for large batches
+bool cmdgen_launch_node16w(const EvalLaunch& a, int l, hipStream_t s);        // kernels_node16w.hip: 16-row tiles on eight waves (small batches)
+bool cmdgen_launch_msg128(const EvalLaunch& a, int l, hipStream_t s);         // kernels_edge128.hip: the edge kernels for long lists (128-row tiles)
+bool cmdgen_launch_coord128(const EvalLaunch& a, int l, hipStream_t s);
+
+// kernels_ddpm.hip: the conditional chain
+void cmdgen_launch_chain_init(const Layout& lay, const Dims& d, const ChainBuf& c, const float* px, const float* poh, hipStream_t s);
+void cmdgen_launch_step_count(const Layout& lay, const Dims& d, const ChainBuf& c, const Work& w, const float* eps, hipStream_t s);
+void cmdgen_launch_chain_final(const Layout& lay, const Dims& d, const ChainBuf& c, const Work& w, const float* eps, float* xo, float* po,
+                               unsigned int* cog, hipStream_t s);
+void cmdgen_launch_debug_noise(unsigned long long seed, long long pocket_id, int draw, int n_nodes, int width, float* out, hipStream_t s);
+
+// kernels_inpaint.hip: the conditional RePaint chain
+void cmdgen_launch_inpaint_prep(const Layout& lay, const Dims& d, const ChainBuf& c, const InpaintBuf& ip, const float* phx,
+                                const float* phoh, const float* fix, const float* px, hipStream_t s);
+void cmdgen_launch_inpaint_step_count(const Layout& lay, const Dims& d, const ChainBuf& c, const InpaintBuf& ip, const Work& w,
+                                      const float* eps, hipStream_t s);
+
+// kernels_joint.hip: the joint model's chain
+void cmdgen_launch_joint_init(const Layout& lay, const Dims& d, const JointBuf& c, const float* phx, const float* phoh,
+                              const float* px, const float* poh, hipStream_t s);
+void cmdgen_launch_joint_step(const Layout& lay, const Dims& d, const JointBuf& c, const float* ep, const float* eq, hipStream_t s);
+void cmdgen_launch_joint_final(const Layout& lay, const Dims& d, const JointBuf& c, const float* ep, const float* eq,
+                               float* xo, float* po, unsigned int* cog, hipStream_t s);
+
+// kernels_score.hip: the scoring chain
+void cmdgen_launch_score_init(const Layout& lay, const Dims& d, const ChainBuf& c, const ScoreBuf& sc, float alpha_T, const float* phx,
+                              const float* phoh, const float* px, const float* poh, float* kl_sums, hipStream_t s);
+void cmdgen_launch_score_step(const Layout& lay, const Dims& d, const ChainBuf& c, const ScoreBuf& sc, const Work& w, const float* eps,
+                              hipStream_t s);
+void cmdgen_launch_score_final(const Layout& lay, const Dims& d, const ChainBuf& c, const ScoreBuf& sc, const Work& w, const float* eps,
+                               hipStream_t s);
+size_t cmdgen_score_step_lds(const Layout& lay, const Dims& d);

@@ -23,7 +23,7 @@ __device__ __forceinline__ float nw_inv(const WPack& W) { return NPL == 3 ? 1.0f
 
 __device__ __forceinline__ void nw_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-struct NwFrag { const wfrag* p; unsigned ns; };       // a wave's first 16-column tile (k-block kb0); ns = stride between n-tiles (16-byte units)
+struct NwFrag { const wfrag* p; unsigned ns; };       // a wave's first 16-column tile (k-block kb0) of order ws16 / wh16 (cmdgen_wlayout.h); ns = stride between n-tiles (16-byte units)
 __device__ __forceinline__ NwFrag nw_frag(const void* Ws16, int kb32_total, int kb0, int nt0) {
     const int lane = threadIdx.x & 63;
     NwFrag f;

@@ -142,7 +142,7 @@ __device__ __forceinline__ void n64_split_store2(unsigned short* planes, int NPE
 #endif
 }
 
-// a 32-column tile of a packed split weight ([nt][K/16][NPL pieces][64 lanes] x 16 bytes) at k-block kb0: wave-uniform pointer
+// a 32-column tile of a packed split weight (orders ws / wh, cmdgen_wlayout.h: [nt][K/16][NPL pieces][64 lanes] x 16 bytes) at k-block kb0: wave-uniform pointer
 __device__ __forceinline__ const nfrag* n64_tile(const WPack& W, int kb16_total, int nt, int kb0) {
     return reinterpret_cast<const nfrag*>(NPL == 3 ? W.ws : W.wh) + ((size_t)nt * kb16_total + kb0) * KBS;
 }

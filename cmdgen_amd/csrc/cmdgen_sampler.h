@@ -2,6 +2,7 @@
 // These translation units are built with -ffp-contract=off, so the same helper rounds the same way in each.
 #pragma once
 #include "cmdgen_dev.h"
+#include "cmdgen_launch.h"
 
 __device__ __forceinline__ void atomic_max_pos(unsigned int* slot, float v) {
     atomicMax(slot, __float_as_uint(fabsf(v)) & 0x7fffffffu);     // non-negative floats order like their bits (a NaN's sign bit is cleared: any NaN ranks above +Inf)

@@ -23,10 +23,8 @@
 //            splits the fragments it reads in registers (5.5 VALU operations per element, issued in the
 //            shadow of the MFMAs), so producers and epilogues of the tile kernels do not change and a
 //            64-row tile still needs 66 KB (two workgroups per CU).
-//   B (global, L2-resident): per Linear weight W[out][in]
-//            Ws[((nt * KB16 + kb) * 3 + s) * 64 + lane] = 8 bf16 { W_s[o][k .. k+7] },
-//            o = 32 nt + (lane & 31), k = 16 kb + 8 (lane >> 5): one 16-byte load per lane and piece,
-//            the three pieces of a fragment contiguous (3 KiB per (nt, kb)); split once on the host.
+//   B (global, L2-resident): per Linear weight W[out][in], order ws of cmdgen_wlayout.h: one 16-byte load per lane and
+//            piece, the three pieces of a fragment contiguous (3 KiB per (nt, kb)); split once on the host.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -121,7 +119,7 @@ __device__ __forceinline__ void split_store4_half(unsigned short* planes, int pl
     *reinterpret_cast<uint2*>(planes + plane_elems + off) = make_uint2(a1, b1);
 }
 
-struct SFragPtr { const sbf16x8* p; unsigned ns; };     // a wave's first n-tile; ns = stride between n-tiles (16-byte units)
+struct SFragPtr { const sbf16x8* p; unsigned ns; };     // a wave's first n-tile of order ws (cmdgen_wlayout.h); ns = stride between n-tiles (16-byte units)
 
 // cg = the wave's 64-column group; kb16_total = K / 16 of the packed matrix; kb0 = first k-block of this GEMM
 __device__ __forceinline__ SFragPtr sfrag_ptr(const void* Ws, int kb16_total, int kb0, int cg) {
@@ -233,8 +231,7 @@ __device__ __forceinline__ void tile_gemm_rsplit(const float* ldsA, int lda, con
 // 16-row tiles: v_mfma_f32_16x16x32_bf16 (16 cycles per MFMA; six per fp32 product = 96 matrix cycles per 32 k-values
 // and 16x16 tile against 256 for the eight v_mfma_f32_16x16x4_f32 they replace).  Same split, same fp32 LDS image, same
 // accumulator layout as the fp32 16-row path (row = 4 (lane >> 4) + reg, col = lane & 15).
-//   B (global): Ws16[((nt * KB32 + kb) * 3 + s) * 64 + lane] = 8 bf16 { W_s[o][k_j] }, o = 16 nt + (lane & 15), g = lane >> 4,
-//               k_j = 32 kb + 4 g + j (j < 4) and 32 kb + 16 + 4 g + (j - 4) (j >= 4)
+//   B (global): order ws16 (cmdgen_wlayout.h): lane group g = lane >> 4 holds k = 32 kb + 4 g .. + 3 and 32 kb + 16 + 4 g .. + 3 of row 16 nt + (lane & 15)
 //   A (LDS):    the lane reads two float4 of row (lane & 15) at k = 32 kb + 4 g and 32 kb + 16 + 4 g - the conflict-free
 //               ds_read_b128 pattern of the fp32 16-row path, twice (the MFMA's k order inside a block is free as long as A and B agree)
 // The weight stream is what binds a 16-row tile (one workgroup streams every weight of the block for 16 rows: 6 B per
@@ -482,7 +479,7 @@ __device__ __forceinline__ void tile_gemm_planes_swz32(const unsigned short* pla
 
 // ---------------------------------------------------------------------------------------------
 // Half engine (two fp16 pieces per operand, three MFMAs per product; see the top of this file) for the full-K 32-row plane image:
-// two swizzled planes of [32][256] fp16 (32 KB), weight fragments from WPack::wh ([nt][K/16][2 pieces][64 lanes] x 16 bytes).
+// two swizzled planes of [32][256] fp16 (32 KB), weight fragments from WPack::wh (cmdgen_wlayout.h: [nt][K/16][2 pieces][64 lanes] x 16 bytes).
 // Carry contract as tile_gemm_planes_swz32.  The accumulators carry WPack::wh_scale.
 // ---------------------------------------------------------------------------------------------
 struct HFragPtr { const sf16x8* p; unsigned ns; };      // a wave's first n-tile; ns = stride between n-tiles (16-byte units)

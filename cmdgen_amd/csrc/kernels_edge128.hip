@@ -24,6 +24,7 @@
 // Results: the same sums as kernels_egnn.hip up to fp32 re-association (row dots add in another order; receiver sums in list order);
 // deterministic run to run as long as a receiver's edges span at most two tiles (one float atomic each: commutative).
 #include "cmdgen_dev.h"
+#include "cmdgen_launch.h"
 #include <hip/hip_ext.h>
 
 // half engine, twice: the FUSED main loop (the next quarter's build inside the GEMM; long lists) and the plain one (build -> barrier -> GEMM -> barrier;

@@ -177,7 +177,6 @@ template <int H, int MT, bool SP> static void launch_coord(const EvalLaunch& a, 
 }
 template <int H> static void coord_tiles_H(const EvalLaunch& a, int l, hipStream_t s) { MT_DISPATCH(a.coord_mt, launch_coord, a, l, s); }
 #if CMDGEN_H_PART == 0
-void cmdgen_launch_coord_tiles_hx(const EvalLaunch& a, int l, hipStream_t s);     // kernels_egnn_coord_hx.hip
 void cmdgen_launch_coord_tiles(const EvalLaunch& a, int l, hipStream_t s) {
     if (launch_coord_fullk(a, l, s)) return;
     if (a.d.H == 256) coord_tiles_H<256>(a, l, s); else cmdgen_launch_coord_tiles_hx(a, l, s);

@@ -507,7 +507,6 @@ template <int H> static void embed_tiles_H(const EvalLaunch& a, int mt, const fl
     MT_DISPATCH(mt, launch_embed, a, xp, xq, t, coef, chain, s);
 }
 #if CMDGEN_H_PART == 0
-void cmdgen_launch_embed_tiles_hx(const EvalLaunch& a, int mt, const float* xp, const float* xq, const float* t, const float4* coef, ChainState* chain, hipStream_t s);   // kernels_egnn_graph_hx.hip
 void cmdgen_launch_embed_tiles(const EvalLaunch& a, int mt, const float* xp, const float* xq, const float* t, const float4* coef, ChainState* chain, hipStream_t s) {
     if (a.d.H == 256) embed_tiles_H<256>(a, mt, xp, xq, t, coef, chain, s); else cmdgen_launch_embed_tiles_hx(a, mt, xp, xq, t, coef, chain, s);
 }
@@ -548,7 +547,6 @@ __global__ void k_pocket_cache(Layout lay, Work w, int H, float* __restrict__ c,
         dh[i] = w.h[base + i] - c[i]; dP[i] = w.P[base + i] - P0[i]; dQ[i] = w.Q[base + i] - Q0[i];
     }
 }
-void cmdgen_embed_only_hx(const EvalLaunch& a, const float* xp, const float* xq, const float* t, hipStream_t s);     // kernels_egnn_graph_hx.hip
 // builds the cache from two embed-only passes with the time feature pinned to 0 and to 1 (t01: device [2][B])
 void cmdgen_build_pocket_cache(const EvalLaunch& a, const float* xh_phar, const float* xh_pocket, const float* t01,
                                float* c, float* P0, float* Q0, float* dh, float* dP, float* dQ, hipStream_t s) {

@@ -240,7 +240,6 @@ static bool launch_msg_fullk(const EvalLaunch& a, int l, hipStream_t s) {
 template <int H> static void msg_tiles_H(const EvalLaunch& a, int l, hipStream_t s) { MT_DISPATCH(a.edge_mt, launch_msg, a, l, s); }
 // the launch of one block's message kernel on <= 64-row tiles: the full-K 32-row form where it applies, else the generic dispatch
 #if CMDGEN_H_PART == 0
-void cmdgen_launch_msg_tiles_hx(const EvalLaunch& a, int l, hipStream_t s);       // kernels_egnn_msg_hx.hip
 void cmdgen_launch_msg_tiles(const EvalLaunch& a, int l, hipStream_t s) {
     if (launch_msg_fullk(a, l, s)) return;
     if (a.d.H == 256) msg_tiles_H<256>(a, l, s); else cmdgen_launch_msg_tiles_hx(a, l, s);
@@ -264,7 +263,6 @@ template <int H> static void launch_msg_only_H(const EvalLaunch& a, int layer, h
     if (!cmdgen_launch_msg128(a, layer, s) && !launch_msg_fullk(a, layer, s)) MT_DISPATCH(a.edge_mt, launch_msg, a, layer, s);
     a.unit = -1;
 }
-void cmdgen_launch_edge_msg_only_hx(const EvalLaunch& a, int layer, hipStream_t s);       // kernels_egnn_msg_hx.hip
 void cmdgen_launch_edge_msg_only(const EvalLaunch& a, int layer, hipStream_t s) {
     if (a.d.H == 256) launch_msg_only_H<256>(a, layer, s); else cmdgen_launch_edge_msg_only_hx(a, layer, s);
 }

@@ -206,7 +206,6 @@ template <int H, int MT, bool SP> static void launch_node(const EvalLaunch& a, i
 }
 template <int H> static void node_tiles_H(const EvalLaunch& a, int l, hipStream_t s) { MT_DISPATCH(a.node_mt, launch_node, a, l, s); }
 #if CMDGEN_H_PART == 0
-void cmdgen_launch_node_tiles_hx(const EvalLaunch& a, int l, hipStream_t s);      // kernels_egnn_node_hx.hip
 void cmdgen_launch_node_tiles(const EvalLaunch& a, int l, hipStream_t s) {
     if (a.d.H == 256) node_tiles_H<256>(a, l, s); else cmdgen_launch_node_tiles_hx(a, l, s);
 }

@@ -8,6 +8,7 @@
 // order (phar rows, then pocket rows) on three threads, everything element-wise is spread over the workgroup, and a
 // Philox call fills the four columns it generates.  Compiled with -ffp-contract=off (no FMA re-association).
 #include "cmdgen_dev.h"
+#include "cmdgen_launch.h"
 
 namespace {
 

@@ -11,6 +11,7 @@
 // (egnn_new.py:48-58) and the projections of the first edge / coordinate MLP layers; every accumulator sees the MFMAs of k_node<256, 16, false, true>
 // in the same order.
 #include "cmdgen_dev.h"
+#include "cmdgen_launch.h"
 #include "cmdgen_split.h"
 #include <hip/hip_ext.h>
 

@@ -21,6 +21,7 @@
 // k_node64e (64 rows on eight waves: 43 B/clk, GEMM phases at the matrix pipe's rate, no partner - so its stores leave under the next GEMM's
 // MFMAs), k_node64d (lean 64-row tile, two workgroups per CU: both), and k_node64 (the round-3 tile, option node64 = 1).
 #include "cmdgen_dev.h"
+#include "cmdgen_launch.h"
 #include <hip/hip_ext.h>
 
 #define N64_NPL 2

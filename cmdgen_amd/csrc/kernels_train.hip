@@ -9,6 +9,8 @@
 #define CMDGEN_PLANE_PIN 0
 #include "cmdgen_dev.h"
 #include "cmdgen_split.h"
+#include "cmdgen_train_kernels.h"
+#include "cmdgen_wlayout.h"
 
 // ------------------------------------------------------------------------------------
 // C[M,N] (+)= alpha * op(A)[M,K] * op(B)[K,N] (+ bias[N])          exact fp32 on v_mfma_f32_32x32x2_f32
@@ -231,12 +233,6 @@ __global__ __launch_bounds__(256) void k_sgemm_bf16(int M, int N, int K, const f
 // leading dimensions that are multiples of 4; results are added with float atomics (the destination holds the running
 // gradient).  blockIdx.z = problem * zsplit + k-split.
 // ------------------------------------------------------------------------------------
-struct WgradBatch {
-    const float* dy[8]; const float* x[8]; float* dw[8]; float* db[8];
-    int M[8], N[8], lddy[8], ldx[8], ldw[8];
-    int n;
-    int xs[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // 1: X_p holds PRE-activations - SiLU is applied while the operand is staged (the forward then stores pre1 / pre6 only)
-};
 __device__ __forceinline__ float4 silu4(const float4& v) { return make_float4(silu_f(v.x), silu_f(v.y), silu_f(v.z), silu_f(v.w)); }
 
 template <bool BF, bool XS = false>      // XS: some X_p holds pre-activations (WgradBatch::xs) - a separate instantiation: the default one carries no trace of it
@@ -583,7 +579,7 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_split128(WgradBatch g, int K, 
 // that the fp32 instruction (three pieces) and the 64-tile kernel (bf16) stay.  Options (TrainTune, cmdgen_set_option): wgrad_split = 0: never
 // three pieces; = 1: always where the shape allows; wgrad_tile = 64: never the 128-tile kernel.
 thread_local TrainTune g_train_tune;      // set from the handle at every entry of the training step (cmdgen_train.hip)
-void cmdgen_wgrad_group(const WgradBatch& g, int K, bool bf16, hipStream_t s, bool split3 = false, bool force3 = false) {
+void cmdgen_wgrad_group(const WgradBatch& g, int K, bool bf16, hipStream_t s, bool split3, bool force3) {
     if (g.n <= 0 || K <= 0) return;
     bool xs = false;
     for (int p = 0; p < g.n; ++p) xs = xs || g.xs[p] != 0;
@@ -660,31 +656,29 @@ void cmdgen_wgrad_group(const WgradBatch& g, int K, bool bf16, hipStream_t s, bo
 
 // ------------------------------------------------------------------------------------
 // Per-step re-pack of the parameters the optimizer has just updated into the layouts the fused evaluation kernels
-// stream (cmdgen_dev.h): every block's six Linears in both MFMA fragment orders, the transposed embedding tables and
-// the radial / d0 weight columns.  Two table-driven launches; ~36 MB of traffic per step.
+// stream (fragment orders: cmdgen_wlayout.h): every block's six Linears in both fp32 fragment orders, the transposed embedding
+// tables and the radial / d0 weight columns.  Two table-driven launches; ~36 MB of traffic per step.
 // ------------------------------------------------------------------------------------
-struct RepackFrag { int src_off, ld, out, in, row_split, col_shift; float* dst32; float* dst16; };
-struct RepackMisc { int src_off, ld, rows, cols; float* dst; };      // dst[c * rows + r] = theta[src_off + r * ld + c]
-
+// element [row][k] of the matrix a RepackFrag / RepackHalf16 entry packs (row_split / col_shift: cmdgen_train_kernels.h)
+template <class F>
+__device__ __forceinline__ const float* repack_src(const float* theta, const F& f, int row, int k) {
+    int c = k, r = row;
+    if (f.row_split && row >= f.row_split) { c = k + f.col_shift; r = row - f.row_split; }
+    return theta + f.src_off + (size_t)r * f.ld + c;
+}
+template <class FR>     // the piece of thread idx = (nt * KB + kb) * 64 + lane = wfrag_piece(nt * KB + kb, 1, 0, lane) of one fp32 order
+__device__ __forceinline__ float4 repack_frag_f32(const float* theta, const RepackFrag& f, int idx) {
+    const int KB = f.in / FR::KBLK, lane = idx & 63, kb = (idx >> 6) % KB, nt = (idx >> 6) / KB;
+    const float* src = repack_src(theta, f, FR::row(nt, lane), FR::k0(kb, lane));
+    return make_float4(src[0], src[1], src[2], src[3]);
+}
 __global__ void k_repack_frags(const float* __restrict__ theta, const RepackFrag* __restrict__ tab) {
     const RepackFrag f = tab[blockIdx.y];
     const int n4 = f.out * f.in / 4;
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n4) return;
-    auto fetch = [&](int row, int k) {
-        int r = row, c = k;
-        if (f.row_split && row >= f.row_split) { r = row - f.row_split; c = k + f.col_shift; }
-        const float* src = theta + f.src_off + (size_t)r * f.ld + c;
-        return make_float4(src[0], src[1], src[2], src[3]);
-    };
-    {   // v_mfma_f32_32x32x2_f32 order: [(nt * KB + kb) * 64 + lane] = W[32 nt + (lane & 31)][8 kb + 4 (lane >> 5) .. +3]
-        const int KB = f.in / 8, lane = idx & 63, kb = (idx >> 6) % KB, nt = (idx >> 6) / KB;
-        reinterpret_cast<float4*>(f.dst32)[idx] = fetch(32 * nt + (lane & 31), 8 * kb + 4 * (lane >> 5));
-    }
-    {   // v_mfma_f32_16x16x4_f32 order: [(nt * KB16 + kb) * 64 + lane] = W[16 nt + (lane & 15)][16 kb + 4 (lane >> 4) .. +3]
-        const int KB = f.in / 16, lane = idx & 63, kb = (idx >> 6) % KB, nt = (idx >> 6) / KB;
-        reinterpret_cast<float4*>(f.dst16)[idx] = fetch(16 * nt + (lane & 15), 16 * kb + 4 * (lane >> 4));
-    }
+    reinterpret_cast<float4*>(f.dst32)[idx] = repack_frag_f32<WFrag<32, 4>>(theta, f, idx);
+    reinterpret_cast<float4*>(f.dst16)[idx] = repack_frag_f32<WFrag<16, 4>>(theta, f, idx);
 }
 __global__ void k_repack_misc(const float* __restrict__ theta, const RepackMisc* __restrict__ tab) {
     const RepackMisc m = tab[blockIdx.y];
@@ -699,10 +693,9 @@ void tr_repack(const float* theta, const void* frag_tab, int n_frag, int max_fra
     hipLaunchKernelGGL(k_repack_misc, dim3((max_misc + 255) / 256, n_misc), dim3(256), 0, s, theta, (const RepackMisc*)misc_tab);
 }
 
-// split_k: 0 = choose so that the launch fills the chip (wgrad: few output tiles, K = thousands of rows); 1 = none
 void cmdgen_sgemm(bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
                   int ldc, const float* bias, float alpha, bool accumulate, int split_k, hipStream_t s,
-                  int epi = 0, float* aux = nullptr, int ldaux = 0, bool bf16 = false) {
+                  int epi, float* aux, int ldaux, bool bf16) {
     if (M <= 0 || N <= 0 || K <= 0) return;
     const int tiles = ((N + 63) / 64) * ((M + 63) / 64);
     if (split_k == 0) {
@@ -847,33 +840,32 @@ __global__ __launch_bounds__(256, 2) void k_dgrad_split(int M, const float* __re
     }
 }
 
-// split fragment packs of transposed weight sub-blocks: dst = pack of Wt, Wt[o'][k] = theta[src_off + k * ld + o'] (o', k < 256)
-struct RepackSplitT { int src_off, ld; void* dst; int transpose; };      // transpose = 0: the pack of W itself (forward: Y = X W^T)
+// split fragment packs (WPack::ws order, cmdgen_wlayout.h) of 256 x 256 weight sub-blocks or of their transposes (RepackSplitT)
 __global__ void k_repack_split_t(const float* __restrict__ theta, const RepackSplitT* __restrict__ tab) {
+    typedef WFrag<32, 8> FR;
     const RepackSplitT f = tab[blockIdx.y];
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;         // (nt * 16 + kb) * 64 + lane, nt < 8, kb < 16
     if (idx >= 8 * 16 * 64) return;
     const int lane = idx & 63, kb = (idx >> 6) & 15, nt = idx >> 10;
-    const int o = 32 * nt + (lane & 31), k = 16 * kb + 8 * (lane >> 5);
+    const int o = FR::row(nt, lane), k = FR::k0(kb, lane);
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = f.transpose ? theta[f.src_off + (size_t)(k + j) * f.ld + o] : theta[f.src_off + (size_t)o * f.ld + k + j];
     sbf16x8 p0, p1, p2;
     split8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), p0, p1, p2);
-    sbf16x8* d = reinterpret_cast<sbf16x8*>(f.dst) + (size_t)((nt * 16 + kb) * 3) * 64 + lane;
+    sbf16x8* d = reinterpret_cast<sbf16x8*>(f.dst) + wfrag_piece(nt * 16 + kb, 3, 0, lane);
     d[0] = p0; d[64] = p1; d[128] = p2;
 }
 void tr_repack_split_t(const float* theta, const void* tab, int n, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_repack_split_t, dim3(8 * 16 * 64 / 256, n), dim3(256), 0, s, theta, (const RepackSplitT*)tab);
 }
 // Half-engine packs of the training forward's two edge kernels (cmdgen_split.h, "half" engine), re-made every step like the split packs:
-// two fp16 pieces of (w * 2^e) per weight in v_mfma_f32_32x32x16_f16 fragment order (the layout of pack_half, cmdgen_api.hip), e chosen ON
-// THE DEVICE so that the largest |w| of the matrix lands in [2^11, 2^12) - the parameters move every step, no host value can be trusted -
-// and sc = {2^e, 2^-e} left beside the pack for the kernel's epilogue (WPack::wh_dev).  One workgroup of 1024 threads per 256 x 256 matrix:
-// the 64 weights a thread packs stay in its registers between the maximum and the split.
-struct RepackHalf { int src_off, ld; void* dst; float* sc; int transpose; };     // transpose: the pack of W^T (data gradients: dX = dY W)
+// two fp16 pieces of (w * 2^e) per weight (WPack::wh order and whalf_exp, cmdgen_wlayout.h), e chosen ON THE DEVICE - the parameters move
+// every step, no host value can be trusted - and sc = {2^e, 2^-e} left beside the pack for the kernel's epilogue (WPack::wh_dev).  One
+// workgroup of 1024 threads per 256 x 256 matrix: the 64 weights a thread packs stay in its registers between the maximum and the split.
 template <bool TR>      // TR: the entries are transposed blocks (a strided gather; its own instantiation: sharing one cost the plain packs 20 us per step)
 __global__ __launch_bounds__(1024) void k_repack_half(const float* __restrict__ theta, const RepackHalf* __restrict__ tab) {
+    typedef WFrag<32, 8> FR;
     const RepackHalf f = tab[blockIdx.x];
     __shared__ float red[16];
     const int tid = threadIdx.x;
@@ -883,7 +875,7 @@ __global__ __launch_bounds__(1024) void k_repack_half(const float* __restrict__ 
     for (int q = 0; q < 8; ++q) {
         const int idx = q * 1024 + tid;                                // (nt * 16 + kb) * 64 + lane, nt < 8, kb < 16
         const int lane = idx & 63, kb = (idx >> 6) & 15, nt = idx >> 10;
-        const int o = 32 * nt + (lane & 31), k = 16 * kb + 8 * (lane >> 5);
+        const int o = FR::row(nt, lane), k = FR::k0(kb, lane);
         if constexpr (TR) {                                            // Wt[o][k] = W[k][o]
             const float* src = theta + f.src_off + (size_t)k * f.ld + o;
             va[q] = make_float4(src[0], src[(size_t)f.ld], src[2 * (size_t)f.ld], src[3 * (size_t)f.ld]);
@@ -902,11 +894,9 @@ __global__ __launch_bounds__(1024) void k_repack_half(const float* __restrict__ 
     mx = red[0];
 #pragma unroll
     for (int i = 1; i < 16; ++i) mx = fmaxf(mx, red[i]);
-    int e = 0;
-    if (mx > 0.f && mx < 3.0e38f) e = 12 - ((int)((__float_as_uint(mx) >> 23) & 0xffu) - 126);     // mx = m 2^ex, m in [0.5, 1): mx 2^e in [2^11, 2^12)
-    e = max(-40, min(40, e));
-    const float sc = __uint_as_float((unsigned)(127 + e) << 23);
-    if (tid == 0) { f.sc[0] = sc; f.sc[1] = __uint_as_float((unsigned)(127 - e) << 23); }
+    const int e = whalf_exp(mx);
+    const float sc = whalf_pow2(e);
+    if (tid == 0) { f.sc[0] = sc; f.sc[1] = whalf_pow2(-e); }
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
         const int idx = q * 1024 + tid;
@@ -915,7 +905,7 @@ __global__ __launch_bounds__(1024) void k_repack_half(const float* __restrict__ 
         union { _Float16 h[8]; uint4 u; } p0, p1;
 #pragma unroll
         for (int j = 0; j < 8; ++j) { p0.h[j] = (_Float16)w[j]; p1.h[j] = (_Float16)(w[j] - (float)p0.h[j]); }
-        uint4* d = reinterpret_cast<uint4*>(f.dst) + (size_t)((idx >> 6) * 2) * 64 + lane;
+        uint4* d = reinterpret_cast<uint4*>(f.dst) + wfrag_piece(idx >> 6, 2, 0, lane);
         d[0] = p0.u; d[64] = p1.u;
     }
 }
@@ -924,16 +914,10 @@ void tr_repack_half(const float* theta, const void* tab, int n_plain, int n, hip
     if (n_plain) hipLaunchKernelGGL(k_repack_half<false>, dim3(n_plain), dim3(1024), 0, s, theta, (const RepackHalf*)tab);
     if (n > n_plain) hipLaunchKernelGGL(k_repack_half<true>, dim3(n - n_plain), dim3(1024), 0, s, theta, (const RepackHalf*)tab + n_plain);
 }
-// The same for the node kernel of the training forward (k_node16w<true>): the 16-row half packs (v_mfma_f32_16x16x32_f16 fragment order,
-// the layout of pack_half16, cmdgen_api.hip) of node_mlp.0 [H][2H], node_mlp.2 [H][H] and the stacked projections [2H][H] of coord_mlp.0 /
-// edge_mlp.0 (RepackFrag's row_split / col_shift).  A pack has ONE scale (its products share accumulators), so the maximum is a launch of
-// its own: k_wmax16 (one workgroup per pack) leaves {2^e, 2^-e}, k_repack_half16 splits.
-struct RepackHalf16 { int src_off, ld, out, in, row_split, col_shift; void* dst; float* sc; };
-__device__ __forceinline__ const float* rh16_src(const float* theta, const RepackHalf16& f, int row, int k) {
-    int r = row, c = k;
-    if (f.row_split && row >= f.row_split) { r = row - f.row_split; c = k + f.col_shift; }
-    return theta + f.src_off + (size_t)r * f.ld + c;
-}
+// The same for the node kernel of the training forward (k_node16w<true>): the 16-row half packs (WPack::wh16 order, cmdgen_wlayout.h) of
+// node_mlp.0 [H][2H], node_mlp.2 [H][H] and the stacked projections [2H][H] of coord_mlp.0 / edge_mlp.0 (row_split / col_shift).  A pack
+// has ONE scale (its products share accumulators), so the maximum is a launch of its own: k_wmax16 (one workgroup per pack) leaves
+// {2^e, 2^-e}, k_repack_half16 splits.
 __global__ __launch_bounds__(1024) void k_wmax16(const float* __restrict__ theta, const RepackHalf16* __restrict__ tab) {
     const RepackHalf16 f = tab[blockIdx.x];
     __shared__ float red[16];
@@ -942,7 +926,7 @@ __global__ __launch_bounds__(1024) void k_wmax16(const float* __restrict__ theta
     const int sh = 31 - __clz(k4);                                      // in is 256 or 512: k4 a power of two (no integer division per element)
 #pragma unroll 4
     for (int i = tid; i < n4; i += 1024) {
-        const float2* src = reinterpret_cast<const float2*>(rh16_src(theta, f, i >> sh, 4 * (i & (k4 - 1))));      // (every tensor starts 16-byte aligned, rows are an even number of floats)
+        const float2* src = reinterpret_cast<const float2*>(repack_src(theta, f, i >> sh, 4 * (i & (k4 - 1))));      // (every tensor starts 16-byte aligned, rows are an even number of floats)
         const float2 a = src[0], b = src[1];
         mx = fmaxf(mx, fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fmaxf(fabsf(b.x), fabsf(b.y))));
     }
@@ -953,24 +937,25 @@ __global__ __launch_bounds__(1024) void k_wmax16(const float* __restrict__ theta
     if (tid == 0) {
         mx = red[0];
         for (int i = 1; i < 16; ++i) mx = fmaxf(mx, red[i]);
-        int e = 0;
-        if (mx > 0.f && mx < 3.0e38f) e = 12 - ((int)((__float_as_uint(mx) >> 23) & 0xffu) - 126);
-        e = max(-40, min(40, e));
-        f.sc[0] = __uint_as_float((unsigned)(127 + e) << 23); f.sc[1] = __uint_as_float((unsigned)(127 - e) << 23);
+        const int e = whalf_exp(mx);
+        f.sc[0] = whalf_pow2(e); f.sc[1] = whalf_pow2(-e);
     }
 }
 __global__ void k_repack_half16(const float* __restrict__ theta, const RepackHalf16* __restrict__ tab) {
     const RepackHalf16 f = tab[blockIdx.y];
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;         // (nt * KB + kb) * 64 + lane, nt < out / 16, kb < in / 32
     if (idx >= f.out * f.in / 8) return;
-    const int KB = f.in / 32, lane = idx & 63, kb = (idx >> 6) % KB, nt = (idx >> 6) / KB, g = lane >> 4;
+    typedef WFrag<16, 8> FR;
+    const int KB = f.in / FR::KBLK, lane = idx & 63, kb = (idx >> 6) % KB, nt = (idx >> 6) / KB;
     const float sc = f.sc[0];
-    const float* lo = rh16_src(theta, f, 16 * nt + (lane & 15), 32 * kb + 4 * g);           // k = 4g .. 4g + 3, then 16 + 4g .. 16 + 4g + 3
-    const float w[8] = {lo[0] * sc, lo[1] * sc, lo[2] * sc, lo[3] * sc, lo[16] * sc, lo[17] * sc, lo[18] * sc, lo[19] * sc};
+    const float* lo = repack_src(theta, f, FR::row(nt, lane), FR::k0(kb, lane));
+    float w[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) w[j] = lo[FR::koff(j)] * sc;
     union { _Float16 h[8]; uint4 u; } p0, p1;
 #pragma unroll
     for (int j = 0; j < 8; ++j) { p0.h[j] = (_Float16)w[j]; p1.h[j] = (_Float16)(w[j] - (float)p0.h[j]); }
-    uint4* d = reinterpret_cast<uint4*>(f.dst) + (size_t)((idx >> 6) * 2) * 64 + lane;
+    uint4* d = reinterpret_cast<uint4*>(f.dst) + wfrag_piece(idx >> 6, 2, 0, lane);
     d[0] = p0.u; d[64] = p1.u;
 }
 void tr_repack_half16(const float* theta, const void* tab, int n, int max8, hipStream_t s) {
@@ -978,11 +963,9 @@ void tr_repack_half16(const float* theta, const void* tab, int n, int max8, hipS
     hipLaunchKernelGGL(k_wmax16, dim3(n), dim3(1024), 0, s, theta, (const RepackHalf16*)tab);
     hipLaunchKernelGGL(k_repack_half16, dim3((max8 + 255) / 256, n), dim3(256), 0, s, theta, (const RepackHalf16*)tab);
 }
-// pieces = 3: fp32-accurate (split engine); 1: the operands' leading bf16 piece only (= operands rounded to nearest-even
-// bf16, fp32 accumulation: cmdgen_train_set_precision(1))
 void cmdgen_dgrad_split(int M, const float* A0, const void* W0, const float* A1, const void* W1, float* Y, bool accumulate, float div,
-                        const float* pre, hipStream_t s, int pieces = 3, const void* W0b = nullptr, float* Yb = nullptr,
-                        bool accumulate_b = false, float div_b = 1.0f, int force_mt = 0, const float* Yin = nullptr, const float* rowdiv_b = nullptr) {
+                        const float* pre, hipStream_t s, int pieces, const void* W0b, float* Yb,
+                        bool accumulate_b, float div_b, int force_mt, const float* Yin, const float* rowdiv_b) {
     if (M <= 0) return;
     if (!Yin) Yin = Y;
     const int mt = g_train_tune.dgrad_mt;
@@ -1092,9 +1075,6 @@ __global__ __launch_bounds__(256) void k_gate_bwd(int E, int H, const int* __res
     if (threadIdx.x == 0) out[H] = (red[0][256] + red[1][256]) + (red[2][256] + red[3][256]);
 }
 
-// the inputs of k_coord_out_bwd, for the form of k_head_bwd that computes dphi (and writes dcd) itself: one launch less per block
-struct CoordOutArgs { const int* row; const int* col; const float4* X; const float* phi; int use_tanh; float range, norm_constant;
-                      const float* dacc; float dacc_div; const float* adiv; float4* dcd_out; };
 // dpre7[e][c] = dphi_e w5[c] SiLU'(pre7[e][c]) and, in the same pass, the partial sums of d coord_mlp.4.weight[c] =
 // sum_e dphi_e SiLU(pre7[e][c]) (c2 is recomputed, not read); same workgroup shape and scratch layout as k_gate_bwd.
 __global__ __launch_bounds__(256) void k_head_bwd(int E, int H, const float* __restrict__ dphi, const float* __restrict__ w5,
@@ -2070,7 +2050,7 @@ size_t tr_partial_scratch_floats(size_t E, size_t H) { return ((E + 4 * GATE_EPW
 // the attention gate's adjoint with its two parameter gradients (d_wa [H], d_ba [1]; ignored without attention)
 void tr_gate_bwd(int E, int H, const int* row, const float* pre2, const float* wa, const float* z, int attention, const float* dagg,
                  float* dpre2, float* scratch, float* d_wa, float* d_ba, float* zero, size_t zero_floats, hipStream_t s,
-                 bool defer_reduce = false) {       // defer_reduce: the caller adds the partial sums up later (tr_reduce_pair)
+                 bool defer_reduce) {       // defer_reduce: the caller adds the partial sums up later (tr_reduce_pair)
     if (!E) { if (zero_floats) hipMemsetAsync(zero, 0, zero_floats * sizeof(float), s); return; }
     const int nwg = (E + 4 * GATE_EPW - 1) / (4 * GATE_EPW);
     hipLaunchKernelGGL(k_gate_bwd, dim3(nwg), dim3(256), 0, s, E, H, row, pre2, wa, z, attention, dagg, dpre2, scratch, (float4*)zero, zero_floats / 4);
@@ -2078,19 +2058,19 @@ void tr_gate_bwd(int E, int H, const int* row, const float* pre2, const float* w
 }
 // dpre7 from dphi, and d coord_mlp.4.weight
 void tr_head_bwd(int E, int H, const float* dphi, const float* w5, const float* pre7, float* dpre7, float* scratch, float* d_w5,
-                 float* zero, size_t zero_floats, hipStream_t s, bool defer_reduce = false, const CoordOutArgs* co = nullptr) {
+                 float* zero, size_t zero_floats, hipStream_t s, bool defer_reduce, const CoordOutArgs* co) {
     if (!E) { if (zero_floats) hipMemsetAsync(zero, 0, zero_floats * sizeof(float), s); return; }
     const int nwg = (E + 4 * GATE_EPW - 1) / (4 * GATE_EPW);
     hipLaunchKernelGGL(k_head_bwd, dim3(nwg), dim3(256), 0, s, E, H, dphi, w5, pre7, dpre7, scratch, (float4*)zero, zero_floats / 4, co ? *co : CoordOutArgs{});
     if (!defer_reduce) hipLaunchKernelGGL(k_partial_reduce, dim3((H + 63) / 64, min(32, (nwg + 15) / 16)), dim3(256), 0, s, nwg, H, scratch, d_w5, (float*)nullptr);
 }
 void tr_coord_out_bwd(int E, const int* row, const int* col, const float4* X, const float* phi, int use_tanh, float range,
-                      float nc, const float* dacc, float dacc_div, int n_moving, float* dphi, float4* dcd, hipStream_t s, const float* adiv = nullptr) {
+                      float nc, const float* dacc, float dacc_div, int n_moving, float* dphi, float4* dcd, hipStream_t s, const float* adiv) {
     if (E) hipLaunchKernelGGL(k_coord_out_bwd, EW_GRID(E), 0, s, E, row, col, X, phi, use_tanh, range, nc, dacc, dacc_div, n_moving, dphi, dcd, adiv);
 }
 void tr_edge_tail_bwd(int E, int H, const int* row, const int* col, const float* g, const float* d0, const float* Wcol, int ldw,
                       const float4* X, float nc, const float4* dcd, int n_moving, float* dP, float* dQ, float* dWcol, float* dX,
-                      float* scratch, hipStream_t s, const float* Wd = nullptr, float* dd0 = nullptr) {
+                      float* scratch, hipStream_t s, const float* Wd, float* dd0) {
     if (!E) return;
     const int nwg = (E + 4 * TAIL_EPW - 1) / (4 * TAIL_EPW);
     if (dd0) hipLaunchKernelGGL(k_edge_tail_bwd<true>, dim3(nwg), dim3(256), 0, s, E, H, row, col, g, d0, Wcol, ldw, X, nc, dcd, n_moving,
@@ -2102,8 +2082,8 @@ void tr_edge_tail_bwd(int E, int H, const int* row, const int* col, const float*
 // fused: g = (dY W2^T-pack) * SiLU'(pre1) and its whole tail (H = 256; W = split pack of the transposed weight)
 void cmdgen_dgrad_tail(int E, const float* dY, const void* Wt, const float* pre1, const int* row, const int* col, const float* d0,
                        const float* Wcol, int ldw, const float4* X, float nc, const float4* dcd, int n_moving, float* dP, float* dQ,
-                       float* dWcol, float* dX, float* scratch, int pieces, hipStream_t s, bool defer_reduce = false,
-                       const float* Wd = nullptr, float* dd0 = nullptr) {
+                       float* dWcol, float* dX, float* scratch, int pieces, hipStream_t s, bool defer_reduce,
+                       const float* Wd, float* dd0) {
     if (E <= 0) return;
     const int nwg = (E + 31) / 32;
     const TailArgs ta{row, col, d0, Wcol, ldw, X, nc, dcd, n_moving, dP, dQ, scratch, dX, g_train_tune.dbg, Wd, dd0};
@@ -2155,8 +2135,8 @@ void tr_dt(const Layout& lay, const float* dhdyn, int dyn, float* dt, hipStream_
     if (lay.B) hipLaunchKernelGGL(k_dt, dim3(lay.B), dim3(64), 0, s, lay, dhdyn, dyn, dt);
 }
 void tr_adamw(size_t n, float* theta, const float* grad, float* m, float* v, float* vmax, float lr, float b1, float b2,
-              float eps, float wd, float bias1, float bias2_sqrt, float clip, hipStream_t s, const float* sqnorm = nullptr,
-              float max_norm = 0.f, int skip_nonfinite = 0) {
+              float eps, float wd, float bias1, float bias2_sqrt, float clip, hipStream_t s, const float* sqnorm,
+              float max_norm, int skip_nonfinite) {
     if (n) hipLaunchKernelGGL(k_adamw, EW_GRID(n), 0, s, n, theta, grad, m, v, vmax, lr, b1, b2, eps, wd, bias1, bias2_sqrt, clip, sqnorm, max_norm, skip_nonfinite);
 }
 void tr_sqsum(size_t n, const float* x, float* out, hipStream_t s) {

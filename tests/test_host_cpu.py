@@ -55,6 +55,71 @@ def test_library_source_reads_no_environment_variable():
             assert 'getenv' not in open(os.path.join(csrc, f)).read(), f
 
 
+def _file_scope_declarations(code):
+    """(text joined to one line, ';' or '{') of every declaration at brace depth 0 of comment-free code"""
+    out, depth, cur = [], 0, []
+    for ch in code:
+        if ch == '{':
+            if depth == 0:
+                out.append((' '.join(''.join(cur).split()), '{'))
+                cur = []
+            depth += 1
+        elif ch == '}':
+            depth -= 1
+        elif depth == 0 and ch == ';':
+            out.append((' '.join(''.join(cur).split()), ';'))
+            cur = []
+        elif depth == 0:
+            cur.append(ch)
+    assert depth == 0
+    return out
+
+
+def test_library_source_declares_each_struct_and_launcher_once():
+    """What two translation units must agree on is written once, in a header both include: no struct is defined in two files of
+    csrc/ (a table struct copied into the host file and the kernel file can drift apart, and the kernel then indexes the uploaded
+    table with the wrong stride), and no .hip file carries a bare prototype of a cmdgen_* / tr_* function or an extern object
+    declaration (a copied prototype with default arguments silently passes stale defaults)."""
+    csrc = os.path.join(ROOT, 'cmdgen_amd', 'csrc')
+    proto = re.compile(r'^(?:extern C_LINKAGE )?(?:template ?<[^>]*> ?)?(?:[\w:]+[ *&]+)+((?:cmdgen_|tr_)\w+) ?\(')
+    structs, prototypes = {}, []
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith(('.hip', '.h')):
+            continue
+        code = open(os.path.join(csrc, f)).read()
+        code = re.sub(r'/\*.*?\*/', ' ', code, flags=re.S)                      # comments, preprocessor lines, literals
+        code = re.sub(r'//[^\n]*', '', code)
+        code = re.sub(r'(?m)^[ \t]*#(?:[^\n]*\\\n)*[^\n]*', '', code)
+        code = code.replace('"C"', 'C_LINKAGE')
+        code = re.sub(r'"(?:\\.|[^"\\\n])*"', '""', code)
+        code = re.sub(r"'(?:\\.|[^'\\\n])'", "' '", code)
+        for name in set(re.findall(r'\bstruct\s+(\w+)\s*(?::[^;{()]*)?\{', code)):
+            structs.setdefault(name, []).append(f)
+        if not f.endswith('.hip'):
+            continue
+        for text, end in _file_scope_declarations(code):                          # multi-line prototypes arrive joined
+            if end != ';' or text.startswith(('static ', 'typedef ', 'using ')):
+                continue
+            if proto.match(text) or (text.startswith('extern ') and not text.startswith('extern C_LINKAGE ')):
+                prototypes.append((f, text))
+    twice = {name: files for name, files in structs.items() if len(files) > 1}
+    assert not twice, twice
+    assert not prototypes, prototypes
+    assert len(structs) > 30 and 'RepackHalf16' in structs and 'WPack' in structs       # the scan sees the structs it is about
+
+
+def test_half_scale_rule_equals_both_rules_it_replaced(tmp_path):
+    """tests/whalf_exp_check.cpp: whalf_exp (cmdgen_wlayout.h) against the former host and device rules, on the host."""
+    import subprocess
+    exe = str(tmp_path / 'whalf_exp_check')
+    r = subprocess.run(['/opt/rocm/bin/hipcc', '-x', 'hip', '--offload-arch=gfx950', '-O2', '-I' + os.path.join(ROOT, 'cmdgen_amd', 'csrc'),
+                        os.path.join(ROOT, 'tests', 'whalf_exp_check.cpp'), '-o', exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and 'bad 0' in r.stdout, (r.stdout + r.stderr)[-2000:]
+    assert int(r.stdout.split('checked')[1].split()[0]) > 2500
+
+
 def test_product_fails_loudly_without_gpu():
     if torch.cuda.is_available():
         pytest.skip('GPU present')
