@@ -1144,25 +1144,29 @@ extern "C" int cmdgen_joint_chain(cmdgen_handle* h, const float* phar_x, const f
 }
 
 // ---------------------------------------------------------------------------------
-// conditional RePaint: ConditionalDDPM.inpaint (kernels_inpaint.hip; the op semantics and the draw scheme are in
-// include/cmdgen_hip.h)
+// conditional RePaint and the edit chain: ConditionalDDPM.inpaint / .edit (kernels_inpaint.hip; the op semantics and the
+// draw scheme are in include/cmdgen_hip.h).  Inpainting is the edit chain with both masks equal and start = timesteps.
 // ---------------------------------------------------------------------------------
 struct InpaintPlan {
     std::vector<float> coef, coef2;     // [n_steps+1][4] (last: decode row), [n_steps][4]
     std::vector<int> iop;               // [n_steps][4]
     int n_steps = 0, n_draws = 0;
+    float alpha_start = 0.f, sigma_start = 0.f;     // q(z_start | x) of a chain that starts below t = T
 };
 
 // One row per op in execution order.  The posterior rows are the step table's (the caller's, when it supplied one for K:
-// then an op at step s uses exactly the scalars cmdgen_sample_chain uses there).
-static InpaintPlan build_inpaint_plan(const cmdgen_handle* h, int K, int resamplings, int jump) {
+// then an op at step s uses exactly the scalars cmdgen_sample_chain uses there).  The ops walk s = start-1 .. 0 on the K grid
+// with get_repaint_schedule(resamplings, jump, start).
+static InpaintPlan build_inpaint_plan(const cmdgen_handle* h, int K, int start, int resamplings, int jump) {
     InpaintPlan p;
     const std::vector<float> tab = step_table(h, K);
     const int T = h->cfg.timesteps;
     auto g_at = [&](int step) { return h->gamma[(size_t)lrintf(((float)step / (float)K) * (float)T)]; };
-    const std::vector<int> sched = repaint_schedule(resamplings, jump, K);
-    int draw = 1;                       // row 0 = z_T
-    int s = K - 1;
+    const std::vector<int> sched = repaint_schedule(resamplings, jump, start);
+    p.alpha_start = sqrtf(sigmoid_h(-g_at(start)));
+    p.sigma_start = sqrtf(sigmoid_h(g_at(start)));
+    int draw = 1;                       // row 0 = z_T (z_start)
+    int s = start - 1;
     for (size_t i = 0; i < sched.size(); ++i) {
         for (int j = 0; j < sched[i]; ++j) {
             p.coef.insert(p.coef.end(), tab.begin() + (size_t)(K - 1 - s) * 4, tab.begin() + (size_t)(K - s) * 4);
@@ -1187,23 +1191,29 @@ static InpaintPlan build_inpaint_plan(const cmdgen_handle* h, int K, int resampl
     return p;
 }
 
-static int check_inpaint_args(cmdgen_handle* h, int K, int resamplings, int jump) {
+static int check_inpaint_args(cmdgen_handle* h, int K, int start, int resamplings, int jump) {
     if (h->dims.joint) return fail(h, CMDGEN_ESTATE, "this handle is the joint model (update_pocket_coords=1): use cmdgen_joint_chain");
     if (h->dims.no_com) return fail(h, CMDGEN_ESTATE, "inpainting is not supported for no_com_projection handles (SimpleConditionalDDPM)");
     if (K < 1 || K > h->cfg.timesteps) return fail(h, CMDGEN_EINVAL, "timesteps=%d must be in [1, %d]", K, h->cfg.timesteps);
+    if (start < 1 || start > K) return fail(h, CMDGEN_EINVAL, "start=%d must be in [1, timesteps=%d]", start, K);
     if (resamplings < 1 || jump < 1) return fail(h, CMDGEN_EINVAL, "resamplings and jump_length must be >= 1");
     return 0;
 }
 
-extern "C" int cmdgen_inpaint_plan(cmdgen_handle* h, int32_t timesteps, int32_t resamplings, int32_t jump_length,
-                                   int64_t* n_steps, int64_t* n_draws) {
+extern "C" int cmdgen_edit_plan(cmdgen_handle* h, int32_t timesteps, int32_t start, int32_t resamplings, int32_t jump_length,
+                                int64_t* n_steps, int64_t* n_draws) {
     if (!h) return CMDGEN_EINVAL;
     if (!h->finalized) return fail(h, CMDGEN_ESTATE, "weights not finalised (cmdgen_finalize_weights)");
-    int rc = check_inpaint_args(h, timesteps, resamplings, jump_length); if (rc) return rc;
-    const InpaintPlan p = build_inpaint_plan(h, timesteps, resamplings, jump_length);
+    int rc = check_inpaint_args(h, timesteps, start, resamplings, jump_length); if (rc) return rc;
+    const InpaintPlan p = build_inpaint_plan(h, timesteps, start, resamplings, jump_length);
     if (n_steps) *n_steps = p.n_steps;
     if (n_draws) *n_draws = p.n_draws;
     return CMDGEN_OK;
+}
+
+extern "C" int cmdgen_inpaint_plan(cmdgen_handle* h, int32_t timesteps, int32_t resamplings, int32_t jump_length,
+                                   int64_t* n_steps, int64_t* n_draws) {
+    return cmdgen_edit_plan(h, timesteps, timesteps, resamplings, jump_length, n_steps, n_draws);
 }
 
 // the inpainting chain's ChainBuf (posterior rows: coef, n_steps + 1) and InpaintBuf (coef2, iop: n_steps each; the known part)
@@ -1224,17 +1234,17 @@ static int alloc_inpaint(cmdgen_handle* h, ChainSlot& k, const float* tables, in
     return 0;
 }
 
-extern "C" int cmdgen_inpaint_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
-                                    const float* phar_x, const float* phar_onehot, const float* phar_fixed,
-                                    int32_t timesteps, int32_t resamplings, int32_t jump_length,
-                                    const float* noise, int64_t n_draws, uint64_t seed, const int64_t* pocket_ids_host,
-                                    float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
-                                    int32_t use_graph, cmdgen_stream stream) {
+extern "C" int cmdgen_edit_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
+                                 const float* phar_x, const float* phar_onehot, const float* fix_x, const float* fix_h,
+                                 int32_t timesteps, int32_t start, int32_t resamplings, int32_t jump_length,
+                                 const float* noise, int64_t n_draws, uint64_t seed, const int64_t* pocket_ids_host,
+                                 float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                                 int32_t use_graph, cmdgen_stream stream) {
     int rc = check_ready(h); if (rc) return rc;
-    rc = check_inpaint_args(h, timesteps, resamplings, jump_length); if (rc) return rc;
-    if (!pocket_x || !pocket_onehot || !phar_x || !phar_onehot || !phar_fixed || !xh_phar_out || !xh_pocket_out)
+    rc = check_inpaint_args(h, timesteps, start, resamplings, jump_length); if (rc) return rc;
+    if (!pocket_x || !pocket_onehot || !phar_x || !phar_onehot || !fix_x || !fix_h || !xh_phar_out || !xh_pocket_out)
         return fail(h, CMDGEN_EINVAL, "null device pointer");
-    const InpaintPlan plan = build_inpaint_plan(h, timesteps, resamplings, jump_length);
+    const InpaintPlan plan = build_inpaint_plan(h, timesteps, start, resamplings, jump_length);
     if (noise && n_draws < plan.n_draws)
         return fail(h, CMDGEN_EINVAL, "noise holds %lld draws, the schedule needs %lld", (long long)n_draws, (long long)plan.n_draws);
     const int n_steps = plan.n_steps;
@@ -1247,13 +1257,19 @@ extern "C" int cmdgen_inpaint_chain(cmdgen_handle* h, const float* pocket_x, con
     ChainBuf c = h->inp_chain;
     c.noise = noise; c.seed = seed; c.z_steps = z_steps_out; c.pocket_steps = pocket_steps_out;
     const InpaintBuf ip = h->inp;
-    cmdgen_launch_chain_init(h->lay, d, c, pocket_x, pocket_onehot, s);
-    cmdgen_launch_inpaint_prep(h->lay, d, c, ip, phar_x, phar_onehot, phar_fixed, pocket_x, s);
+    if (start == timesteps) {                        // from the prior: z_T around the pocket centre
+        cmdgen_launch_chain_init(h->lay, d, c, pocket_x, pocket_onehot, s);
+        cmdgen_launch_inpaint_prep(h->lay, d, c, ip, phar_x, phar_onehot, fix_x, fix_h, pocket_x, s);
+    } else {                                         // part-way: z ~ q(z_start | the given rows)
+        cmdgen_launch_edit_start(h->lay, d, c, ip, plan.alpha_start, plan.sigma_start, phar_x, phar_onehot, fix_x, fix_h, pocket_x,
+                                 pocket_onehot, s);
+    }
     build_pocket_cache(h, k, c, a, s);
     EvalLaunch a2 = a;
     a2.skip_count = 1;                               // k_inpaint_step_count ran pass 1 of the graph
-    cmdgen_launch_eval(a, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, s, nullptr);   // evaluation 0 (t = 1)
-    // the tables, the known rows and the mask are slot buffers (a new plan prepares the slot again); the caller's pointers are the key
+    cmdgen_launch_eval(a, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, s, nullptr);   // evaluation 0 (t = start / timesteps)
+    // the tables (their rows differ with start and with the plan), the known rows and the masks are slot buffers: a new plan or start
+    // prepares the slot again; the caller's pointers are the key
     const void* key[6] = {noise, z_steps_out, pocket_steps_out, nullptr, nullptr, s};
     rc = run_steps(h, k, key, seed, n_steps, use_graph, s, [&](hipStream_t ss) {
         cmdgen_launch_inpaint_step_count(h->lay, d, c, ip, h->work, h->work.eps_tmp, ss);
@@ -1265,6 +1281,17 @@ extern "C" int cmdgen_inpaint_chain(cmdgen_handle* h, const float* pocket_x, con
     if (noise) cf.noise = noise + (size_t)(plan.n_draws - 1 - (1 + n_steps)) * h->lay.Nl * (3 + d.P);
     cmdgen_launch_chain_final(h->lay, d, cf, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, k.cog, s);
     return end_chain(h, caller, s);
+}
+
+extern "C" int cmdgen_inpaint_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
+                                    const float* phar_x, const float* phar_onehot, const float* phar_fixed,
+                                    int32_t timesteps, int32_t resamplings, int32_t jump_length,
+                                    const float* noise, int64_t n_draws, uint64_t seed, const int64_t* pocket_ids_host,
+                                    float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                                    int32_t use_graph, cmdgen_stream stream) {
+    return cmdgen_edit_chain(h, pocket_x, pocket_onehot, phar_x, phar_onehot, phar_fixed, phar_fixed, timesteps, timesteps, resamplings,
+                             jump_length, noise, n_draws, seed, pocket_ids_host, xh_phar_out, xh_pocket_out, z_steps_out,
+                             pocket_steps_out, use_graph, stream);
 }
 
 // ---------------------------------------------------------------------------------

@@ -165,12 +165,12 @@ struct JointBuf {               // joint-model chain (EnVariationalDiffusion.sam
     ChainState* state;
 };
 
-struct InpaintBuf {             // conditional RePaint chain (cmdgen_inpaint_chain): the op tables and the known part, beside a ChainBuf
+struct InpaintBuf {             // conditional RePaint / edit chain (cmdgen_inpaint_chain, cmdgen_edit_chain): the op tables and the known part, beside a ChainBuf
     const float4* coef2;        // [n_steps]   (alpha_s, sigma_s, jump alpha_t'|s, jump sigma_t'|s); the ChainBuf's coef holds the posterior rows
     const int4* iop;            // [n_steps]   (flags: 1 = jump back after the op, noise row of draw A, of draw B, of draw C)
-    const float* known;         // [Nl][3+P]   normalised input phar rows [x | one_hot] (only fixed rows are read)
-    float* fix;                 // [Nl]        1 = fixed row, else 0 (a copy of the caller's mask)
-    float4* poff;               // [B]         (com(P) - com(P0) of the current translated pocket, number of fixed rows of the sample)
+    const float* known;         // [Nl][3+P]   normalised input phar rows [x | one_hot] (only marked column groups are read)
+    float* fix;                 // [Nl]        two bits per row: 1 = x columns held, 2 = h columns held (0, 1, 2 or 3 as a float)
+    float4* poff;               // [B]         (com(P) - com(P0) of the current translated pocket, number of marked rows of the sample)
     int n_steps;                // denoising ops of the schedule (Philox: B draws at 2 + n_steps + op, C draws at 2 + 2 n_steps + op)
 };
 

@@ -239,6 +239,68 @@ class ConditionalDDPM(EnVariationalDiffusion):
         out = self._finish_chain(h, run, self.inpaint_frames(resamplings, jump_length, timesteps, return_frames), return_frames)
         return out[0], out[1], phar_mask, pocket['mask']
 
+    def _row_mask(self, value, name, n_phar, device):
+        """A per-row mask argument ([Nl] or [Nl,1], bools or floats; None: no row) as float [Nl] on `device`."""
+        if value is None:
+            return torch.zeros(n_phar, dtype=torch.float32, device=device)
+        m = torch.as_tensor(value).detach()
+        shape = tuple(m.shape)
+        if m.dim() == 2 and m.shape[1] == 1:
+            m = m[:, 0]
+        if m.dim() != 1 or m.numel() != n_phar:
+            raise ValueError(f'{name} has shape {shape}: expected [{n_phar}] or [{n_phar}, 1]')
+        return (m != 0).to(device, torch.float32).contiguous()
+
+    @torch.no_grad()
+    def edit(self, phar, pocket, fix_coords=None, fix_types=None, start=None, resamplings=1, jump_length=1, timesteps=None,
+             noise=None, seed=None, pocket_ids=None):
+        """Modify a GIVEN pharmacophore in its pocket: ``inpaint`` with a mask per column group and a start level.
+
+        fix_coords / fix_types ([Nl] or [Nl,1], bools or floats; None: nothing held) hold a row's position / its feature type at
+        the noised copy of the given row, independently: types held and coordinates free re-places the points, the reverse
+        re-types them; both marked is ``inpaint``'s fixed row.  ``start`` in 1 .. timesteps is the level the chain begins at:
+        None or timesteps is the prior (z_T around the pocket centre, as sample_given_pocket); below it the chain begins at
+        q(z_start | phar) as ``forward`` forms it (both node sets centred on the phar centre of mass, noised_representation) and
+        walks s = start-1 .. 0 with get_repaint_schedule(resamplings, jump_length, start) - then every row of phar is read.
+        The whole chain runs on the device (cmdgen_edit_chain; its header gives the ops, the draw layout and the Philox
+        counters).  noise [n_draws, Nl, 3+P] (Handle.edit_plan), seed and pocket_ids as in sample_given_pocket.
+        Returns (xh_phar, xh_pocket, phar_mask, pocket_mask) like sample_given_pocket."""
+        timesteps = self.T if timesteps is None else int(timesteps)
+        start = timesteps if start is None else start
+        if int(start) != start or not 1 <= int(start) <= timesteps:
+            raise ValueError(f'start={start} must be an integer level in [1, timesteps={timesteps}]')
+        start = int(start)
+        device = pocket['x'].device
+        n_samples = len(pocket['size'])
+        sizes = pocket['size'].detach().to('cpu', torch.int64).numpy()
+        nph = phar['size'].detach().to('cpu', torch.int64).numpy()
+        if len(nph) != n_samples:
+            raise ValueError(f'phar has {len(nph)} samples, pocket {n_samples}')
+        for m in (phar['mask'], pocket['mask']):
+            if m.numel() > 1 and bool((m[1:] < m[:-1]).any()):
+                raise ValueError('batch masks must be ascending and contiguous')
+        n_phar = int(nph.sum())
+        fix_x = self._row_mask(fix_coords, 'fix_coords', n_phar, device)
+        fix_h = self._row_mask(fix_types, 'fix_types', n_phar, device)
+        self.refresh_learned_schedule()
+        h = self.dynamics.hip_handle()
+        h.set_layout(nph, sizes)
+        h.set_step_table(timesteps, self.step_table(timesteps))
+        n_steps, n_draws = h.edit_plan(timesteps, start, resamplings, jump_length)
+        f32 = lambda t: t.detach().to(device, torch.float32).contiguous()
+        if noise is not None:
+            noise = f32(noise)
+            if noise.dim() != 3 or noise.shape[0] < n_draws:
+                raise ValueError(f'noise has shape {tuple(noise.shape)}: this schedule needs {n_draws} draws of [{n_phar}, {3 + self.phar_nf}]')
+        if seed is None:
+            seed = fresh_seed()
+        phar_mask = utils.num_nodes_to_batch_mask(n_samples, torch.as_tensor(nph), device)
+        args = (f32(pocket['x']), f32(pocket['one_hot']), f32(phar['x']), f32(phar['one_hot']), fix_x, fix_h)
+        run = lambda: h.edit_chain(*args, timesteps, start=start, resamplings=resamplings, jump_length=jump_length, noise=noise,
+                                   seed=seed, pocket_ids=pocket_ids, use_graph=self.use_hip_graph)
+        out = self._finish_chain(h, run, [], 1)
+        return out[0], out[1], phar_mask, pocket['mask']
+
     @torch.no_grad()
     def score(self, phar, pocket, timesteps=None, repeats=1, noise=None, seed=None, pocket_ids=None, return_levels=False):
         """How likely the model finds a GIVEN pharmacophore in its pocket: the per-sample negative log-likelihood bound of
@@ -360,6 +422,10 @@ class SimpleConditionalDDPM(ConditionalDDPM):
 
     def inpaint(self, *args, **kwargs):
         raise NotImplementedError('inpainting is not implemented for SimpleConditionalDDPM (no centre-of-mass projection); '
+                                  'use ConditionalDDPM')
+
+    def edit(self, *args, **kwargs):
+        raise NotImplementedError('edit is not implemented for SimpleConditionalDDPM (no centre-of-mass projection); '
                                   'use ConditionalDDPM')
 
     def score(self, *args, **kwargs):

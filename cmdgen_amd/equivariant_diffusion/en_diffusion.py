@@ -546,6 +546,10 @@ class EnVariationalDiffusion(nn.Module):
         raise NotImplementedError('score is not implemented for the joint model: its loss has the pocket\'s own terms '
                                   '(error_t and loss_0_x of the pocket nodes); use ConditionalDDPM')
 
+    def edit(self, *args, **kwargs):
+        raise NotImplementedError('edit is not implemented for the joint model (its pocket diffuses too: use inpaint with the '
+                                  'pocket fixed); use ConditionalDDPM')
+
     @torch.no_grad()
     def inpaint(self, phar, pocket, phar_fixed, pocket_fixed, resamplings=1, jump_length=1, return_frames=1,
                 timesteps=None, noise=None, seed=None, pocket_ids=None):

@@ -64,6 +64,9 @@ SYMBOLS = [
     ('cmdgen_inpaint_plan', C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _i64p, _i64p]),
     ('cmdgen_inpaint_chain', C.c_int, [_vp, _fp, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int64,
                                        C.c_uint64, _i64p, _fp, _fp, _fp, _fp, C.c_int32, _vp]),
+    ('cmdgen_edit_plan', C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i64p, _i64p]),
+    ('cmdgen_edit_chain', C.c_int, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int64,
+                                    C.c_uint64, _i64p, _fp, _fp, _fp, _fp, C.c_int32, _vp]),
     ('cmdgen_score_chain', C.c_int, [_vp, _fp, _fp, _fp, _fp, C.c_int32, _vp, _vp, _fp, C.c_uint64, _i64p, _fp, _fp, C.c_int32, _vp]),
     ('cmdgen_param_count', C.c_int, [_vp, _i64p]),
     ('cmdgen_param_offset', C.c_int, [_vp, C.c_char_p, _i64p, _i64p]),
@@ -415,6 +418,43 @@ class Handle:
             int(resamplings), int(jump_length), _ptr(noise), int(noise.shape[0]) if noise is not None else 0,
             C.c_uint64(seed & (2 ** 64 - 1)), self._pocket_ids(pocket_ids), _ptr(xh_phar),
             _ptr(xh_pocket), _ptr(z_steps), _ptr(p_steps), int(bool(use_graph)), self._stream()), 'cmdgen_inpaint_chain')
+        return xh_phar, xh_pocket, z_steps
+
+    def edit_plan(self, timesteps: int, start: Optional[int] = None, resamplings: int = 1, jump_length: int = 1):
+        """(denoising ops, noise draws) of an edit chain that starts at level `start` (None: timesteps) - cmdgen_edit_plan."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        start = timesteps if start is None else start
+        self._check(self.lib.cmdgen_edit_plan(self.h, int(timesteps), int(start), int(resamplings), int(jump_length), C.byref(a),
+                                              C.byref(b)), 'cmdgen_edit_plan')
+        return a.value, b.value
+
+    def edit_chain(self, pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h, timesteps: int, start: Optional[int] = None,
+                   resamplings: int = 1, jump_length: int = 1, noise=None, seed: int = 0, pocket_ids: Optional[Sequence[int]] = None,
+                   want_steps: bool = False, use_graph: bool = True):
+        """ConditionalDDPM.edit on the device (cmdgen_edit_chain): inpaint_chain with a mask for the x columns (fix_x) and one for the
+        feature columns (fix_h), float [Nl] device tensors, and the level the chain starts from (None: timesteps, the prior).
+        -> (xh_phar, xh_pocket, z_steps); with want_steps the pocket after every op is left in last_pocket_steps."""
+        import torch
+        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
+        start = timesteps if start is None else start
+        shapes = [(self.n_pocket, 3), (self.n_pocket, R), (self.n_phar, 3), (self.n_phar, P), (self.n_phar,), (self.n_phar,)]
+        for t, sh in zip((pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h), shapes):
+            self._check_dev(t, sh)
+        n_steps, n_draws = self.edit_plan(timesteps, start, resamplings, jump_length)
+        if noise is not None:
+            self._check_dev(noise)
+            assert noise.dim() == 3 and tuple(noise.shape[1:]) == (self.n_phar, 3 + P), noise.shape
+        dev = pocket_x.device
+        xh_phar = torch.empty((self.n_phar, 3 + P), dtype=torch.float32, device=dev)
+        xh_pocket = torch.empty((self.n_pocket, 3 + R), dtype=torch.float32, device=dev)
+        z_steps = torch.empty((n_steps, self.n_phar, 3 + P), dtype=torch.float32, device=dev) if want_steps else None
+        p_steps = torch.empty((n_steps, self.n_pocket, 3), dtype=torch.float32, device=dev) if want_steps else None
+        self.last_pocket_steps = p_steps
+        self._check(self.lib.cmdgen_edit_chain(
+            self.h, _ptr(pocket_x), _ptr(pocket_onehot), _ptr(phar_x), _ptr(phar_onehot), _ptr(fix_x), _ptr(fix_h), int(timesteps),
+            int(start), int(resamplings), int(jump_length), _ptr(noise), int(noise.shape[0]) if noise is not None else 0,
+            C.c_uint64(seed & (2 ** 64 - 1)), self._pocket_ids(pocket_ids), _ptr(xh_phar),
+            _ptr(xh_pocket), _ptr(z_steps), _ptr(p_steps), int(bool(use_graph)), self._stream()), 'cmdgen_edit_chain')
         return xh_phar, xh_pocket, z_steps
 
     SC_COLS = 4                      # include/cmdgen_hip.h: CMDGEN_SC_COLS

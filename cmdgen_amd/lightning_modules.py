@@ -339,6 +339,36 @@ class PharPocketDDPM(nn.Module):
                 phar_to_coords.setdefault(f'Molecule_{k}', {}).setdefault(name, []).append(coords)
         return phar_to_coords
 
+    def _phar_with_given_rows(self, points, arg, n_samples, num_nodes_phar, pocket):
+        """The phar batch of inpaint_phars / edit_phars: `points` = [(type name, (x, y, z))] are the first rows of every sample, the
+        other rows zero.  num_nodes_phar: points per sample, default the size prior given the pocket, at least len(points).
+        -> (phar dict, the indices of the given rows, sample by sample)."""
+        n_fix = len(points)
+        decoder = list(self.dataset_info['phar_decoder'])
+        for name, _ in points:
+            if name not in decoder:
+                raise ValueError(f'unknown pharmacophore type {name!r}: expected one of {decoder}')
+        if num_nodes_phar is None:
+            num_nodes_phar = self.ddpm.size_distribution.sample_conditional(n1=None, n2=pocket['size'])
+            num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device).clamp(min=n_fix)
+        else:
+            num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device).reshape(-1)
+            if num_nodes_phar.numel() == 1:
+                num_nodes_phar = num_nodes_phar.expand(n_samples)
+            if bool((num_nodes_phar < n_fix).any()):
+                raise ValueError(f'num_nodes_phar must be at least len({arg}) = {n_fix}')
+        num_nodes_phar = num_nodes_phar.to(INT_TYPE)
+        phar_mask = utils.num_nodes_to_batch_mask(n_samples, num_nodes_phar, self.device)
+        first = torch.cumsum(num_nodes_phar, 0) - num_nodes_phar                 # first row of every sample
+        rows = (first[:, None] + torch.arange(n_fix, device=self.device)[None, :]).reshape(-1)
+        fx = torch.tensor([list(map(float, xyz)) for _, xyz in points], device=self.device, dtype=FLOAT_TYPE).reshape(n_fix, 3)
+        ft = torch.tensor([decoder.index(name) for name, _ in points], device=self.device, dtype=torch.int64)
+        x = torch.zeros((len(phar_mask), self.x_dims), device=self.device, dtype=FLOAT_TYPE)
+        one_hot = torch.zeros((len(phar_mask), self.phar_nf), device=self.device, dtype=FLOAT_TYPE)
+        x[rows] = fx.repeat(n_samples, 1)
+        one_hot[rows] = F.one_hot(ft, self.phar_nf).to(FLOAT_TYPE).repeat(n_samples, 1)
+        return {'x': x, 'one_hot': one_hot, 'size': num_nodes_phar, 'mask': phar_mask}, rows
+
     def inpaint_phars(self, pdb_file, n_samples, fixed_phars, pocket_ids=None, ref_ligand=None, num_nodes_phar=None,
                       timesteps=None, resamplings=1, jump_length=1, seed=None):
         """Generate pharmacophores inside a pocket around given points (ConditionalDDPM.inpaint).
@@ -349,35 +379,12 @@ class PharPocketDDPM(nn.Module):
         assert (pocket_ids is None) ^ (ref_ligand is None)
         if not isinstance(self.ddpm, ConditionalDDPM):
             raise NotImplementedError('inpaint_phars needs the conditional model (mode pocket_conditioning)')
-        n_fix = len(fixed_phars)
         decoder = list(self.dataset_info['phar_decoder'])
-        for name, _ in fixed_phars:
-            if name not in decoder:
-                raise ValueError(f'unknown pharmacophore type {name!r}: expected one of {decoder}')
         pocket = self._pdb_pocket(pdb_file, n_samples, pocket_ids, ref_ligand)
         pocket_com_before = _scatter_mean(pocket['x'], pocket['mask'], n_samples)
-        if num_nodes_phar is None:
-            num_nodes_phar = self.ddpm.size_distribution.sample_conditional(n1=None, n2=pocket['size'])
-            num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device).clamp(min=n_fix)
-        else:
-            num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device).reshape(-1)
-            if num_nodes_phar.numel() == 1:
-                num_nodes_phar = num_nodes_phar.expand(n_samples)
-            if bool((num_nodes_phar < n_fix).any()):
-                raise ValueError(f'num_nodes_phar must be at least len(fixed_phars) = {n_fix}')
-        num_nodes_phar = num_nodes_phar.to(INT_TYPE)
-        phar_mask = utils.num_nodes_to_batch_mask(n_samples, num_nodes_phar, self.device)
-        first = torch.cumsum(num_nodes_phar, 0) - num_nodes_phar                 # first row of every sample
-        rows = (first[:, None] + torch.arange(n_fix, device=self.device)[None, :]).reshape(-1)
-        fx = torch.tensor([list(map(float, xyz)) for _, xyz in fixed_phars], device=self.device, dtype=FLOAT_TYPE).reshape(n_fix, 3)
-        ft = torch.tensor([decoder.index(name) for name, _ in fixed_phars], device=self.device, dtype=torch.int64)
-        x = torch.zeros((len(phar_mask), self.x_dims), device=self.device, dtype=FLOAT_TYPE)
-        one_hot = torch.zeros((len(phar_mask), self.phar_nf), device=self.device, dtype=FLOAT_TYPE)
-        fixed = torch.zeros(len(phar_mask), device=self.device, dtype=FLOAT_TYPE)
-        x[rows] = fx.repeat(n_samples, 1)
-        one_hot[rows] = F.one_hot(ft, self.phar_nf).to(FLOAT_TYPE).repeat(n_samples, 1)
+        phar, rows = self._phar_with_given_rows(fixed_phars, 'fixed_phars', n_samples, num_nodes_phar, pocket)
+        fixed = torch.zeros(len(phar['mask']), device=self.device, dtype=FLOAT_TYPE)
         fixed[rows] = 1.0
-        phar = {'x': x, 'one_hot': one_hot, 'size': num_nodes_phar, 'mask': phar_mask}
         xh_phar, xh_pocket, phar_mask, pocket_mask = self.ddpm.inpaint(
             phar, pocket, fixed, resamplings=resamplings, jump_length=jump_length, timesteps=timesteps, seed=seed)
         # move the generated points back to the original pocket position (as generate_phars)
@@ -393,6 +400,61 @@ class PharPocketDDPM(nn.Module):
             for k, (name, coords) in enumerate(zip(names, coords_batch), start=1):
                 phar_to_coords.setdefault(f'Molecule_{k}', {}).setdefault(name, []).append(coords)
         return phar_to_coords
+
+    KEEP = {'types': (False, True), 'coords': (True, False), 'both': (True, True), 'none': (False, False)}
+
+    @torch.no_grad()
+    def edit_phars(self, pdb_file, n_samples, phars, keep='types', strength=None, num_nodes_phar=None, pocket_ids=None,
+                   ref_ligand=None, timesteps=None, resamplings=1, jump_length=1, seed=None):
+        """Modify a given pharmacophore inside a pocket (ConditionalDDPM.edit): n_samples variants of it.
+
+        phars: [(type name of dataset_info['phar_decoder'], (x, y, z) in Angstrom in the PDB's frame)], the first rows of every
+        sample.  keep: what a given point holds - 'types' (the points are re-placed), 'coords' (they are re-typed), 'both' (as
+        inpaint_phars) or 'none' - one word for all points or one per point.  strength in (0, 1]: how far the input is noised
+        before the chain walks back, start = max(1, round(strength * timesteps)); None: from the prior.  num_nodes_phar adds
+        free rows as in inpaint_phars (default: the size prior; with strength < 1 the given points only); with strength < 1 extra
+        free rows are refused (there is nothing to noise for those rows).
+        -> one point list per sample, [(type name, (x, y, z))] back in the PDB's frame: the ``candidates`` of score_phars."""
+        assert (pocket_ids is None) ^ (ref_ligand is None)
+        if not isinstance(self.ddpm, ConditionalDDPM):
+            raise NotImplementedError('edit_phars needs the conditional model (mode pocket_conditioning)')
+        n_given = len(phars)
+        if n_given < 1:
+            raise ValueError('phars needs at least one point')
+        keeps = [keep] * n_given if isinstance(keep, str) else list(keep)
+        if len(keeps) != n_given or any(k not in self.KEEP for k in keeps):
+            raise ValueError(f'keep must be one of {sorted(self.KEEP)}, or one of these per point ({n_given}): got {keep!r}')
+        T = self.ddpm.T if timesteps is None else int(timesteps)
+        start = None
+        if strength is not None:
+            if not 0.0 < float(strength) <= 1.0:
+                raise ValueError(f'strength={strength} must be in (0, 1]')
+            start = max(1, int(round(float(strength) * T)))
+        decoder = list(self.dataset_info['phar_decoder'])
+        pocket = self._pdb_pocket(pdb_file, n_samples, pocket_ids, ref_ligand)
+        pocket_com_before = _scatter_mean(pocket['x'], pocket['mask'], n_samples)
+        if start is not None and start < T and num_nodes_phar is None:
+            num_nodes_phar = n_given                                    # part-way: the given points only (no size prior)
+        phar, rows = self._phar_with_given_rows(phars, 'phars', n_samples, num_nodes_phar, pocket)
+        if start is not None and start < T and bool((phar['size'] > n_given).any()):
+            raise ValueError(f'strength={strength} < 1 noises the given points; the extra free rows of num_nodes_phar have nothing to '
+                             'noise: use strength=None (or 1), or num_nodes_phar = len(phars)')
+        fix_x = torch.zeros(len(phar['mask']), device=self.device, dtype=FLOAT_TYPE)
+        fix_h = torch.zeros_like(fix_x)
+        fix_x[rows] = torch.tensor([float(self.KEEP[k][0]) for k in keeps], device=self.device).repeat(n_samples)
+        fix_h[rows] = torch.tensor([float(self.KEEP[k][1]) for k in keeps], device=self.device).repeat(n_samples)
+        xh_phar, xh_pocket, phar_mask, pocket_mask = self.ddpm.edit(
+            phar, pocket, fix_coords=fix_x, fix_types=fix_h, start=start, resamplings=resamplings, jump_length=jump_length,
+            timesteps=timesteps, seed=seed)
+        # move the points back to the original pocket position (as generate_phars)
+        pocket_com_after = _scatter_mean(xh_pocket[:, :self.x_dims], pocket_mask, n_samples)
+        xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
+        x = xh_phar[:, :self.x_dims].detach().cpu()
+        phar_type = xh_phar[:, self.x_dims:].argmax(1).detach().cpu()
+        # rows in their given order (utils.batch_to_list goes through an unstable argsort, which may permute a sample's rows)
+        sizes = phar['size'].cpu().tolist()
+        return [[(decoder[int(t)], tuple(float(v) for v in c)) for t, c in zip(types, coords)]
+                for coords, types in zip(torch.split(x, sizes), torch.split(phar_type, sizes))]
 
     # ------------------------------------------------------------------ scoring
     def _score_model(self):

@@ -273,6 +273,35 @@ int cmdgen_inpaint_chain(cmdgen_handle* h, const float* pocket_x, const float* p
                          float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
                          int32_t use_graph, cmdgen_stream stream);
 
+/* The edit chain (ConditionalDDPM.edit): cmdgen_inpaint_chain with a mask per column group and a start level, to MODIFY a given
+ * pharmacophore - hold the types and re-place the points, hold the positions and re-type them, or perturb it by a chosen amount.
+ * Notation as above (K the normalised given rows, P0 the normalised input pocket, P its translated copy), timesteps = Kt.
+ *   Ops.  A and C as cmdgen_inpaint_chain.  B forms z_k = alpha_s K + sigma_s eps_B over all rows and z_k.x += com(P_u) - com(P0),
+ *      then merges per column group:  z.x = fix_x ? z_k.x : z_u.x,  z.h = fix_h ? z_k.h : z_u.h,  then
+ *      (z.x, P.x) = remove_mean_batch(z.x, P_u.x).  A sample with no mark in either mask skips B.
+ *   Start.  start == timesteps: z_T around the pocket centre, as cmdgen_sample_chain.  start < timesteps: the forward process of the
+ *      given rows as ConditionalDDPM.forward forms it (conditional_model.py:235-243): K.x and P0.x centred on the phar centre of mass
+ *      of the sample's given rows, z = alpha(start / Kt) xh0 + sigma(start / Kt) eps_0, remove_mean_batch(z.x, P.x) and the mean-zero
+ *      check; then ALL rows of phar_x and phar_onehot are read, not only marked ones.  The ops walk s = start-1 .. 0 on the Kt grid
+ *      with get_repaint_schedule(resamplings, jump_length, start); the posterior rows are those of the Kt step table at the same s.
+ *   fix_x, fix_h dev [Nl]: nonzero = the row's x columns / its phar_nf feature columns are held
+ *   start  in 1 .. timesteps (others are refused)
+ *   noise  dev [n_draws][Nl][3+phar_nf] or NULL, in call order: draw 0 (z_T or eps_0); per op draw A, draw B, and draw C if the op
+ *          jumps back; the decode draw.  n_draws = 2 + 2 n_steps + n_jumps for the schedule actually walked (cmdgen_edit_plan).
+ *   Device draws: the Philox counters of cmdgen_inpaint_chain with that n_steps -
+ *          draw 0: 0, A of op i: 1 + i, decode: 1 + n_steps, B of op i: 2 + n_steps + i, C of op i: 2 + 2 n_steps + i.
+ *   everything else as cmdgen_inpaint_chain, which is this entry with fix_x = fix_h = phar_fixed and start = timesteps, bit for bit
+ *          (the two share one slot of the handle: a changed start or plan prepares it again, the caller's pointers stay the graph key).
+ * One op is one launch (k_inpaint_step_count) plus the evaluation, as for inpainting.  Refusals as cmdgen_inpaint_chain. */
+int cmdgen_edit_plan(cmdgen_handle* h, int32_t timesteps, int32_t start, int32_t resamplings, int32_t jump_length,
+                     int64_t* n_steps, int64_t* n_draws);
+int cmdgen_edit_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
+                      const float* phar_x, const float* phar_onehot, const float* fix_x, const float* fix_h,
+                      int32_t timesteps, int32_t start, int32_t resamplings, int32_t jump_length,
+                      const float* noise, int64_t n_draws, uint64_t seed, const int64_t* pocket_ids_host,
+                      float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                      int32_t use_graph, cmdgen_stream stream);
+
 /* Scoring for the CONDITIONAL model (ConditionalDDPM.score): the diffusion loss of a GIVEN pharmacophore in its pocket at a
  * list of noise levels, one evaluation per level, all on the device.  In the normalised space, with xh0 the phar rows and P0
  * the pocket both centred on the phar centre of mass (conditional_model.py:198-320 in eval mode), level k with t = t_levels[k]:
