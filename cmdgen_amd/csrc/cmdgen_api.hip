@@ -590,6 +590,19 @@ EvalLaunch make_launch(cmdgen_handle* h) {
     }
     // (the node kernel avoids its 64-row register-split tiles on the split engine: 87 vs 132 us at B=256, profiles/r02_o_tile_sweep_split.txt)
     if (a.split && a.node_mt == 64 && !opt_set(h, "node_mt")) a.node_mt = 32;
+    {   // the next block's P | Q projections as column-sliced tiles inside the coordinate launch (kernels_coord_proj.hip) instead of in k_node16w,
+        // whose 16-row tile streams every weight it multiplies: only where k_node16w takes the node launches AND the coordinate list runs on the
+        // 32-row full-K tile (the launch the projection tiles join), one GCL per block, the conditional model, and both roles on the same engine.
+        // Option "proj_in_coord": 0 never, 1 wherever that holds, unset: where it measured faster (profiles/proj_in_coord_ab.txt).
+        bool can = false;
+        if (!h->layers.empty() && a.d.H == 256 && a.d.S == 1 && a.d.L > 1 && !a.d.joint && !a.node64 && a.node_mt == 16 && a.split && a.split16 && a.node16w &&
+            a.edge_fullk && a.coord_mt == 32) {
+            const LayerW& lw = h->layers[0];
+            const bool half_n = a.half_engine && lw.W3.wh16, half_c = a.half_engine && lw.W7.wh;
+            can = lw.W3.ws16 && half_n == half_c && (half_n ? lw.Wpq_e.wh16 != nullptr : lw.Wpq_e.ws16 != nullptr);
+        }
+        a.proj_in_coord = can && opt_of(h, "proj_in_coord", 1) != 0 ? 1 : 0;
+    }
     return a;
 }
 
@@ -598,7 +611,7 @@ EvalLaunch make_launch(cmdgen_handle* h) {
 // ---------------------------------------------------------------------------------
 static const char* const kOptionKeys[] = {
     "node_mt", "edge_mt", "coord_mt", "embed_mt", "edge_wgs_per_cu", "coord_wgs_per_cu", "e128_wgs_per_cu", "e128_fused", "half_engine", "edge_fullk", "node64", "node16_split", "node16w",
-    "dead_skip", "write_embed", "graph_steps",
+    "proj_in_coord", "dead_skip", "write_embed", "graph_steps",
     "wgrad_split", "wgrad_tile", "wgrad_split_wgs128", "wgrad_split_wgs64", "wgrad_wgs", "dgrad_mt", "dgrad_tail", "wgrad_stream", "train_half", "wgrad_silu", "train_node16", "wgrad_k128"};
 
 static void drop_graphs(cmdgen_handle* h) {
@@ -1486,9 +1499,11 @@ extern "C" int cmdgen_query(cmdgen_handle* h, const char* key, int64_t* value) {
     else if (k == "node16_split") *value = a.split16;
     else if (k == "node64") *value = a.node64;
     else if (k == "node16w") *value = a.node16w;
+    else if (k == "proj_in_coord") *value = a.proj_in_coord;
     else if (k == "edge_fullk") *value = a.edge_fullk;
     else if (k == "dead_skip") *value = a.dead_skip;
     else if (k == "eval_gen") *value = h->eval_gen;
+    else if (k == "chain_graphs") { int64_t n = 0; for (const ChainSlot& c : h->chains) n += c.graph != nullptr ? 1 : 0; *value = n; }   // captured step graphs held
     else if (k == "train_half_ran") *value = h->train_fwd_half;
     else if (k == "train_range_event") *value = h->h_norm && !h->norm_pending ? (int64_t)h->h_norm[1] : 0;     // of the last collected norm
     else if (k == "train_edges") *value = h->train_E;

@@ -247,12 +247,15 @@ struct EvalLaunch {             // everything one evaluation's launches need (ho
     int e128_wgs = 2;           // workgroups per CU of the 128-row edge kernels (kernels_edge128.hip)
     int e128_fused = 3;         // bit 0 / 1: the 128-row message / coordinate kernel runs its fused main loop (half engine; lists long enough for more than one tile per workgroup)
     int half_engine = 1;        // 1: split-engine kernels that have a HALF form (two fp16 pieces per operand, three MFMAs per product; cmdgen_split.h) use it
+    int proj_in_coord = 0;      // 1: the next block's P | Q projections run as column-sliced tiles in the coordinate launch instead of in k_node16w (kernels_coord_proj.hip; option "proj_in_coord")
+    mutable int proj_now = 0;   // ... and this evaluation does so (launch_eval: not a training forward, no parity stop, no per-stage events)
 };
 // weight unit of block l's launches (EvalLaunch::unit), and the has_next argument of its node kernel: bit 0 = another unit follows
-// (its P | Q are projected), bits 1..29 = the dead-tile threshold of the plane tiles, bit 30 = no P_c | Q_c (EvalLaunch::skip_pc)
+// (its P | Q are projected), bits 1..28 = the dead-tile threshold of the plane tiles, bit 29 = the coordinate launch projects the next unit's
+// P | Q (EvalLaunch::proj_now: k_node16w leaves them out), bit 30 = no P_c | Q_c (EvalLaunch::skip_pc)
 inline int unit_of(const EvalLaunch& a, int l) { return a.unit >= 0 ? a.unit : l; }
 inline int unit_has_next(const EvalLaunch& a, int l) { return unit_of(a, l) + 1 < a.d.L * a.d.S ? 1 : 0; }
-inline int node_flags(const EvalLaunch& a, int l) { return unit_has_next(a, l) | (a.live_thr << 1) | (a.skip_pc << 30); }
+inline int node_flags(const EvalLaunch& a, int l) { return unit_has_next(a, l) | (a.live_thr << 1) | (a.proj_now << 29) | (a.skip_pc << 30); }
 
 
 // ---------------------------------------------------------------------------------

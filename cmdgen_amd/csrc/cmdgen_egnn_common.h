@@ -269,8 +269,9 @@ __device__ __forceinline__ float tile_row_dot(const float* buf, const float* wv,
 // Giving every XCD group one contiguous range of tiles keeps the P/Q rows it gathers (edges are sorted
 // by sample and receiver) inside that L2 instead of spreading every sample over all eight.
 // Placement only affects speed, never results.  Returns the k-th tile of this workgroup or -1.
-__device__ __forceinline__ int xcd_tile(int k, int ntiles) {
-    const int vb = (int)blockIdx.x, nb = (int)gridDim.x;
+// (nwg: the workgroups that walk the list when they are only the first ones of a launch - k_coord_proj; 0: the whole grid)
+__device__ __forceinline__ int xcd_tile(int k, int ntiles, int nwg = 0) {
+    const int vb = (int)blockIdx.x, nb = nwg ? nwg : (int)gridDim.x;
     const int g = vb & 7;
     const int wg_in_g = vb >> 3;
     const int wgs_in_g = (nb - g + 7) >> 3;                 // workgroups whose blockIdx % 8 == g

@@ -38,6 +38,7 @@ bool cmdgen_launch_node64(const EvalLaunch& a, int l, hipStream_t s);         //
 bool cmdgen_launch_node16w(const EvalLaunch& a, int l, hipStream_t s);        // kernels_node16w.hip: 16-row tiles on eight waves (small batches)
 bool cmdgen_launch_msg128(const EvalLaunch& a, int l, hipStream_t s);         // kernels_edge128.hip: the edge kernels for long lists (128-row tiles)
 bool cmdgen_launch_coord128(const EvalLaunch& a, int l, hipStream_t s);
+bool cmdgen_launch_coord_proj(const EvalLaunch& a, int l, hipStream_t s);     // kernels_coord_proj.hip: the 32-row full-K coordinate tiles + the next block's P | Q tiles in one launch (EvalLaunch::proj_now)
 
 // kernels_ddpm.hip: the conditional chain
 void cmdgen_launch_chain_init(const Layout& lay, const Dims& d, const ChainBuf& c, const float* px, const float* poh, hipStream_t s);

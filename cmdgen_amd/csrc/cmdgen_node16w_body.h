@@ -157,7 +157,9 @@ template <bool SAVE>
 __global__ __launch_bounds__(512) void k_node16w(Layout lay, Work w, Dims d, LayerW lw, LayerW lw_next, int layer, int has_next_arg, TrainSave sv) {
     __shared__ __attribute__((aligned(16))) float buf0[NW_MT * NW_LD];      // h (kept for the residual)
     __shared__ __attribute__((aligned(16))) float buf1[NW_MT * NW_LD];      // agg / nf -> T = SiLU(.) -> h_new
-    const int has_next = has_next_arg & 1;                                   // (bits 1..29: the dead-tile threshold of the plane tiles, unused here)
+    // (bits 1..28: the dead-tile threshold of the plane tiles, unused here; bit 29: the next block's P | Q are projected by the coordinate
+    // launch that follows (kernels_coord_proj.hip) - the tile ends after Q_c like a last block's, and fnp / fnq are never fetched)
+    const int has_next = (has_next_arg & 1) & ~(has_next_arg >> 29);
     const bool skip_pc = ((has_next_arg >> 30) & 1) != 0;                   // not the last GCL of its block (inv_sublayers > 1): no P_c | Q_c
     const int tid = threadIdx.x, wave = tid >> 6;
     const int row0 = (int)blockIdx.x * NW_MT, nvalid = min(NW_MT, lay.N - row0);

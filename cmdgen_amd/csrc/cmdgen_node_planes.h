@@ -190,7 +190,7 @@ __device__ __forceinline__ void node_planes_tile_body(unsigned short* planes, co
     constexpr int H = 256, LPR = H / 4, NMT = NROWS / 32, NPE = NROWS * NPLD;
     constexpr int NW = 8 / NCT, NPASS = NROWS / NW;        // waves = rows per pass of the row-wise phases (64 threads per row)
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int has_next = has_next_arg & 1, live_thr = (has_next_arg >> 1) & 0x1fffffff;       // bits 1..29: only tiles with a node within that many hops of a moving node (see below)
+    const int has_next = has_next_arg & 1, live_thr = (has_next_arg >> 1) & 0x0fffffff;       // bits 1..28: only tiles with a node within that many hops of a moving node (see below)
     const bool skip_pc = ((has_next_arg >> 30) & 1) != 0;                     // not the last GCL of its block (inv_sublayers > 1): no P_c | Q_c
 #if CMDGEN_STAMPS == 5      // diagnostic build: per-phase cycle stamps into w.dbg ([wave][phase] sums, [32 + wave] lifetime, [40] waves)
     unsigned long long nst_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, nst_t = __builtin_amdgcn_s_memtime();

@@ -1,0 +1,45 @@
+// kernels_coord_proj.hip - k_coord_proj: the coordinate update of block l on 32-row full-K tiles (edge_coord_body, kernels_egnn_coord.hip) and the
+// edge-MLP projections P | Q of block l + 1 in ONE launch (conditional sampler, H = 256, small batches).
+//
+// Why.  k_node16w (kernels_node16w.hip) multiplies 16 rows per workgroup and streams every weight of its chain of GEMMs for them: 1.8 MB per tile
+// on the half engine, 236 tiles at 64 C-alpha pockets, ~425 MB per launch out of the L2s - that stream, at what the chip's L2s deliver to one
+// workgroup per CU, IS the launch's time.  Two of the tile's six weight units are the NEXT block's P | Q, which nothing in the
+// node tile reads.  Here they run as independent tiles of 32 rows x 128 columns (a quarter of one projection's weights for twice the rows) beside
+// the coordinate launch, which at this size is the latency chain of a few tiles on mostly idle CUs.  No exchange between workgroups: both roles
+// read what earlier launches wrote.  Every P / Q element sees the MFMAs nw_gemm gave it, in the same order (cmdgen_coord_proj_body.h).
+#define CMDGEN_H_PART 2                 // edge_coord_body and its helpers only, no launchers
+#include "kernels_egnn_coord.hip"
+#include "cmdgen_split.h"
+
+#define NW_NPL 2
+namespace cp_half {
+#include "cmdgen_node16w_body.h"
+#include "cmdgen_coord_proj_body.h"
+}
+#undef NW_NPL
+#undef NW_MFMA
+#define NW_NPL 3
+namespace cp_bf3 {
+#include "cmdgen_node16w_body.h"
+#include "cmdgen_coord_proj_body.h"
+}
+#undef NW_NPL
+#undef NW_MFMA
+
+// launcher: true when the merged kernel took the coordinate launch of block l.  EvalLaunch::proj_now says that this evaluation's k_node16w launches
+// left the next block's P | Q out (make_launch / launch_eval hold the conditions); the last block has no next one and stays with k_edge_coord.
+bool cmdgen_launch_coord_proj(const EvalLaunch& a, int l, hipStream_t s) {
+    if (!a.proj_now || !unit_has_next(a, l)) return false;
+    const LayerW& lw = a.layers[unit_of(a, l)];
+    const LayerW& ln = a.layers[unit_of(a, l) + 1];
+    if (a.half_engine && lw.W7.wh) {
+        const int grid = cp_half::cp_grid(a.coord_grid, a.lay.N);
+        if (a.pe_start) hipExtLaunchKernelGGL(cp_half::k_coord_proj, dim3(grid), dim3(256), 0, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d, lw, ln, l, a.coord_grid);
+        else hipLaunchKernelGGL(cp_half::k_coord_proj, dim3(grid), dim3(256), 0, s, a.lay, a.w, a.d, lw, ln, l, a.coord_grid);
+    } else {
+        const int grid = cp_bf3::cp_grid(a.coord_grid, a.lay.N);
+        if (a.pe_start) hipExtLaunchKernelGGL(cp_bf3::k_coord_proj, dim3(grid), dim3(256), 0, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d, lw, ln, l, a.coord_grid);
+        else hipLaunchKernelGGL(cp_bf3::k_coord_proj, dim3(grid), dim3(256), 0, s, a.lay, a.w, a.d, lw, ln, l, a.coord_grid);
+    }
+    return true;
+}

@@ -161,6 +161,9 @@ static void launch_eval(const EvalLaunch& a, const float* xh_phar, const float* 
 #define PROF_END() do { a.pe_start = nullptr; a.pe_stop = nullptr; } while (0)
     // k_embed's tile: the small one only where the pocket cache serves the pocket rows (inside a conditional chain)
     const int emt = (chain && !t_arr && a.pcache.c) ? a.embed_mt : a.node_mt;
+    // the next block's P | Q in the coordinate launch (EvalLaunch::proj_in_coord): the sampler's whole evaluations only - the training forward, the
+    // parity stops and the per-stage events keep every projection in the node launch
+    a.proj_now = (a.proj_in_coord && !a.save && a.stop_block < 0 && !ev) ? 1 : 0;
     REC();
     // per-sample graph kernels: one wave scans one receiver at a time, so big samples (full-atom pockets: 381 nodes) get 16 waves
     const int gthr = a.lay.max_n > 128 ? 1024 : 256;
@@ -212,6 +215,7 @@ static void launch_eval(const EvalLaunch& a, const float* xh_phar, const float* 
                        eps_phar, eps_pocket, chain, a.save ? *a.save : TrainSave{});
     if (a.d.joint) hipLaunchKernelGGL(k_vel_com, dim3(B), dim3(64), 0, s, a.lay, a.w, a.d, eps_phar, eps_pocket);
     REC();
+    a.proj_now = 0;
 #undef REC
 #undef PROF_BEGIN
 #undef PROF_END

@@ -16,7 +16,7 @@
 // ------------------------------------------------------------------------------------
 template <int H, int MT, bool SAVE, bool SP, int FK = 0>
 __device__ __forceinline__ void edge_coord_body(EdgeLds<H, MT, FK>& L, const Layout& lay, const Work& w, const Dims& d, const LayerW& lw,
-                                                const int layer, const TrainSave& sv) {
+                                                const int layer, const TrainSave& sv, const int nwg = 0 /* xcd_tile */) {
     float* buf = L.buf; int* s_row = L.s_row; int* s_col = L.s_col;
     float* s_r = L.s_r; float* s_d0 = L.s_d0; float* s_w5 = L.s_vec; float* s_wrd = L.s_wrd;
     float (*s_cd)[3] = L.s_cd; float (*s_tr)[3] = L.s_tr;
@@ -40,16 +40,16 @@ __device__ __forceinline__ void edge_coord_body(EdgeLds<H, MT, FK>& L, const Lay
     const int ntiles = (E + MT - 1) / MT;
     int nx_row = -1, nx_col = -1; float nx_d0 = 0.f;           // the next tile's triple, one tile ahead (see edge_msg_body)
     {
-        const int t0 = xcd_tile(0, ntiles);
+        const int t0 = xcd_tile(0, ntiles, nwg);
         if (t0 >= 0 && tid < MT && t0 * MT + tid < E) { nx_row = w.crow[t0 * MT + tid]; nx_col = w.ccol[t0 * MT + tid]; nx_d0 = w.cd0[t0 * MT + tid]; }
     }
-    for (int k = 0, tile; (tile = xcd_tile(k, ntiles)) >= 0; ++k) {
+    for (int k = 0, tile; (tile = xcd_tile(k, ntiles, nwg)) >= 0; ++k) {
         const int e0 = tile * MT;
         const int ne = min(MT, E - e0);
         if (tid < MT) {
             const int row = nx_row, col = nx_col; const float d0 = nx_d0;               // phar receivers, self loops dropped
             nx_row = -1; nx_col = -1; nx_d0 = 0.f;
-            const int tn = xcd_tile(k + 1, ntiles);
+            const int tn = xcd_tile(k + 1, ntiles, nwg);
             if (tn >= 0 && tn * MT + tid < E) { nx_row = w.crow[tn * MT + tid]; nx_col = w.ccol[tn * MT + tid]; nx_d0 = w.cd0[tn * MT + tid]; }
             float r = 0.f, cx = 0.f, cy = 0.f, cz = 0.f;
             if (tid < ne) {
@@ -147,8 +147,9 @@ __global__ __launch_bounds__(H, FK ? 3 : 2) void k_edge_coord(Layout lay, Work w
 }
 
 // ------------------------------------------------------------------------------------
-// host-callable launchers (C++ linkage)
+// host-callable launchers (C++ linkage); kernels_coord_proj.hip includes this file for edge_coord_body alone (CMDGEN_H_PART 2)
 // ------------------------------------------------------------------------------------
+#if CMDGEN_H_PART != 2
 #if CMDGEN_H_PART == 0
 static bool launch_coord_fullk(const EvalLaunch& a, int l, hipStream_t s) {
     if (!a.edge_fullk || (a.save && !a.save_half) || !a.split || a.d.H != 256 || a.coord_mt != 32) return false;
@@ -178,6 +179,7 @@ template <int H, int MT, bool SP> static void launch_coord(const EvalLaunch& a, 
 template <int H> static void coord_tiles_H(const EvalLaunch& a, int l, hipStream_t s) { MT_DISPATCH(a.coord_mt, launch_coord, a, l, s); }
 #if CMDGEN_H_PART == 0
 void cmdgen_launch_coord_tiles(const EvalLaunch& a, int l, hipStream_t s) {
+    if (cmdgen_launch_coord_proj(a, l, s)) return;             // the 32-row full-K tiles + the next block's P | Q (kernels_coord_proj.hip)
     if (launch_coord_fullk(a, l, s)) return;
     if (a.d.H == 256) coord_tiles_H<256>(a, l, s); else cmdgen_launch_coord_tiles_hx(a, l, s);
 }
@@ -191,3 +193,4 @@ void cmdgen_launch_coord_tiles_hx(const EvalLaunch& a, int l, hipStream_t s) {
     }
 }
 #endif
+#endif  // CMDGEN_H_PART != 2

@@ -18,7 +18,7 @@
 template <int H, int MT, bool SAVE, bool SP>
 __device__ __forceinline__ void node_tile_body(float* bufs, const Layout& lay, const Work& w, const Dims& d, const LayerW& lw, const LayerW& lw_next,
                                                const int layer, const int has_next_arg, const TrainSave& sv, const int row0, const int row_end) {
-    const int has_next = has_next_arg & 1;                                     // (bits 1..29 carry the dead-tile threshold of the plane tiles: unused here)
+    const int has_next = has_next_arg & 1;                                     // (bits 1..28 carry the dead-tile threshold of the plane tiles: unused here)
     const bool skip_pc = ((has_next_arg >> 30) & 1) != 0;                     // not the last GCL of its block (inv_sublayers > 1): no P_c | Q_c
     // Tiles of <= 32 rows keep two LDS images: buf0 = h (kept for the residual), buf1 = agg -> T -> h_new,
     // so h and agg are fetched together and the residual needs no second global read.  64-row tiles

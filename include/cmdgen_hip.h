@@ -543,7 +543,12 @@ int cmdgen_set_gemm_mode(cmdgen_handle* h, int32_t split_bf16);
  *                        edge cutoff (the radial features are bounded; fp16 ends at 65504), 2 always, 0 never
  *   kernel variants      "edge_fullk" 0|1 (full-K planes for 32-row edge tiles), "node64" 0|1|32 (64-row planes node kernel;
  *                        32: its 32-row form), "node16_split" 0|1, "node16w" 0|1 (16-row node tiles of H = 256 on eight waves,
- *                        kernels_node16w.hip; default 1), "write_embed" 0|1 (graph pass 2 + k_embed in one launch)
+ *                        kernels_node16w.hip; default 1), "write_embed" 0|1 (graph pass 2 + k_embed in one launch),
+ *                        "proj_in_coord" 0|1 (the next block's P | Q projections as 32-row x 128-column tiles inside the coordinate launch
+ *                        instead of inside k_node16w - kernels_coord_proj.hip; same bits.  It exists only where k_node16w takes the node
+ *                        launches and the coordinate list runs on the 32-row full-K tile, conditional model, inv_sublayers 1, hidden_nf 256:
+ *                        1 = wherever that holds, 0 = never, unset = the library's rule (the same places).  Training forwards,
+ *                        cmdgen_debug_eval_prefix and cmdgen_profile_evaluation always keep the projections in the node launch.)
  *   dead work            "dead_skip" 0|1|2 (2, default: every block skips tiles beyond L - l hops of a moving node; 1: the
  *                        last block only; 0: off)
  *   chain                "graph_steps" (denoising steps per captured graph, default 8)
@@ -569,8 +574,8 @@ int cmdgen_debug_stamps(cmdgen_handle* h, uint64_t* out64, int32_t reset);
 
 /* Launch configuration in force for the current layout (measurement aid): key = "node_mt" | "edge_mt" | "coord_mt"
  * (rows per tile of the three MFMA kernels), "edge_grid" | "coord_grid" (workgroups of the persistent-style edge
- * kernels), "gemm_split" (the mode above), "node16_split", "node16w", "node64", "edge_fullk", "dead_skip" (as resolved from the
- * options and the layout), "half_engine" (the engine option as resolved: 1 = kernels with a half form use it), "msg_mfmas_per_product" |
+ * kernels), "gemm_split" (the mode above), "node16_split", "node16w", "node64", "edge_fullk", "dead_skip", "proj_in_coord" (as resolved from the
+ * options and the layout), "chain_graphs" (captured step graphs the handle holds), "half_engine" (the engine option as resolved: 1 = kernels with a half form use it), "msg_mfmas_per_product" |
  * "node_mfmas_per_product" | "coord_mfmas_per_product" (1: the fp32 matrix instruction, 6: three bf16 pieces per operand, 3: two fp16 pieces - the
  * engine the three tile kernels of the current layout run on), "train_edges" | "train_coord_edges" (edges of the last cmdgen_train_forward). */
 int cmdgen_query(cmdgen_handle* h, const char* key, int64_t* value);
