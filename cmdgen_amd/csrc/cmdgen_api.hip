@@ -51,7 +51,6 @@ extern "C" int cmdgen_create(const cmdgen_config* cfg, int device, cmdgen_handle
     d.norm_x = cfg->norm_x; d.norm_h = cfg->norm_h; d.bias_h = cfg->bias_h;
     h->n_cus = prop.multiProcessorCount;
     if ((size_t)(8 + d.dyn) * H * sizeof(float) > 64 * 1024) cmdgen_readout_allow_lds((size_t)(8 + d.dyn) * H * sizeof(float));
-    h->edge_grid = 2 * prop.multiProcessorCount;      // two 66 KB-LDS workgroups per CU at 64-row tiles
     h->gemm_split = !d.sin;                           // matrix engine of the tiles of >= 32 rows (cmdgen_set_gemm_mode); sin_embedding: the fp32
                                                       // instruction (the split engine's plane builders carry the two scalar distance features only)
     *out = h;
@@ -164,7 +163,9 @@ extern "C" int cmdgen_finalize_weights(cmdgen_handle* h) {
     hipSetDevice(h->device);
     drop_chain_graphs(h);
     free_pool(h->weight_allocs);
-    h->layers.clear();
+    h->layers.clear(); h->finalized = false;   // a failure below leaves no layer, no pack in the plan and nothing that launches
+    if (h->have_layout) replan(h);
+    std::vector<LayerW> layers;
     const Dims& d = h->dims;
     const int H = d.H, T = h->cfg.timesteps;
     const std::vector<float>* v; int rc;
@@ -261,13 +262,15 @@ extern "C" int cmdgen_finalize_weights(cmdgen_handle* h) {
         } else {                       // never multiplied (the node kernel skips the projection); valid pointers for the bias prefetches
             lw.Wpq_c = lw.Wpq_e; lw.b6 = lw.b1; lw.wr_c = lw.wr_e; lw.wd_c = lw.wd_e; lw.we_c = lw.we_e; lw.W7 = lw.W2; lw.b7 = lw.b2; lw.w5 = lw.b2;
         }
-        h->layers.push_back(lw);
+        layers.push_back(lw);
     }
 #undef GET
 #undef UP
+    h->layers = std::move(layers);
     h->finalized = true;
     h->user_coef_K = -1;                       // a new gamma table invalidates any step table
     release_chains(h);
+    if (h->have_layout) replan(h);             // the packs exist now
     return CMDGEN_OK;
 }
 
@@ -278,90 +281,21 @@ extern "C" int cmdgen_finalize_weights(cmdgen_handle* h) {
 static inline size_t edge_lds_bytes(int max_n) { return (size_t)max_n * (sizeof(float4) + 3 * sizeof(int)); }
 static const size_t kEdgeLdsMax = 156 * 1024;      // 160 KiB per CU minus k_edge_write's small static arrays
 
-// Rows per tile and grids of the evaluation's launches for the current layout (cmdgen_set_layout, and again after cmdgen_set_option /
-// cmdgen_set_gemm_mode).
-static void pick_tiles(cmdgen_handle* h) {
-    // Rows per tile: the largest tile that still gives every CU a few workgroups.  Edge counts are only known on
-    // the device, so they are estimated from the layout for the geometry a trained model holds and every chain starts
-    // from - the phar points inside the pocket (measured on CrossDocked-shaped pockets, bench.py's steady_state_evaluation:
-    // C-alpha 9.2 neighbours per node within 6 A and 15 coordinate edges per phar node; full-atom 36 and 54).  A chain of
-    // an untrained model drifts to fewer edges; the persistent edge grids just find fewer tiles then.
-    double e_est = 0.0, ec_est = 0.0;
-    const int B = (int)h->cur_nphar.size();
+// The planner's input for the sampler (cmdgen_plan.h holds every rule).
+PlanInput plan_input(const cmdgen_handle* h) {
+    PlanInput in;
     const Dims& d = h->dims;
-    const int64_t N = (int64_t)h->lay.N;
-    const int64_t* nph = h->cur_nphar.data(); const int64_t* npk = h->cur_npocket.data();
-    for (int b = 0; b < B; ++b) {
-        const double n = (double)(nph[b] + npk[b]);
-        const bool full = h->cfg.edge_cutoff < 0.f;
-        const double deg = full ? n : (n <= 128.0 ? 9.0 : 36.0);
-        const double dnode = deg < n ? deg : n;
-        double dphar = full ? n : 0.6 * (double)nph[b] + (n <= 128.0 ? 0.15 : 0.13) * (double)npk[b];   // receivers that move
-        if (dphar > n) dphar = n;
-        e_est += n * dnode;
-        ec_est += d.joint ? n * dnode : (double)nph[b] * dphar;                   // joint: every receiver moves
+    in.H = d.H; in.L = d.L; in.S = d.S; in.joint = d.joint != 0; in.sin = d.sin != 0; in.cutoff = d.cutoff2 >= 0.f;
+    in.n_cus = h->n_cus; in.gemm_split = h->gemm_split;
+    in.B = (int)h->cur_nphar.size(); in.nph = h->cur_nphar.data(); in.npk = h->cur_npocket.data();
+    in.N = h->lay.N; in.Nl = h->lay.Nl; in.max_n = h->lay.max_n;
+    in.opts = &h->opts;
+    if (!h->layers.empty()) {           // upload_pack's rule (the [2H][H] first-layer stacks and the square layers take H inputs, node_mlp.0 takes 2H)
+        in.W2 = in.W7 = in.Wpq_e = PlanPacks::of_uploaded(d.H); in.W3 = PlanPacks::of_uploaded(2 * d.H);
     }
-    // thresholds from sweeps on MI355X (fp32 engine: profiles/r01_tile_sweep.txt; split engine:
-    // profiles/r02_o_tile_sweep_split.txt, r02_z_tiles_trained_geometry.txt)
-    auto pick = [&](double rows) { return rows / 64.0 >= 3.0 * h->n_cus ? 64 : (rows / 32.0 >= 1.5 * h->n_cus ? 32 : 16); };
-    h->node_mt = pick((double)N); h->edge_mt = pick(e_est); h->coord_mt = pick(ec_est);
-    if (h->gemm_split) {
-        // node kernel: 32-row tiles (two LDS images) as soon as they put a workgroup on 0.6 of the CUs (96 C-alpha pockets),
-        // never 64 rows; coordinate kernel: 64-row tiles only for very long lists - its list shrinks to a few tiles when a
-        // chain drifts, and a lone 64-row tile costs 15 us where a 32-row one costs 10
-        h->node_mt = (double)N / 32.0 >= 0.6 * h->n_cus ? 32 : 16;
-        h->coord_mt = ec_est / 64.0 >= 6.0 * h->n_cus ? 64 : (ec_est / 32.0 >= 1.5 * h->n_cus ? 32 : 16);
-    }
-    // long lists on the split engine: the 128-row kernels of kernels_edge128.hip (every workgroup owns one chunk of the list; same-box
-    // A/B at 256 C-alpha pockets: messages -3 %, coordinate list -14 %; full-atom pockets: level; profiles/r04_d)
-    // (the half engine as make_launch resolves it)
-    const int he_opt = (int)opt_of(h, "half_engine", 1);
-    const bool half = h->gemm_split && d.H == 256 && (he_opt == 2 || (he_opt == 1 && d.cutoff2 >= 0.f));
-    if (h->gemm_split && d.H == 256) {
-        if (e_est / 64.0 >= 4.0 * h->n_cus) h->edge_mt = 128;
-        // on the half engine the chunked 128-row message kernel wins from ~48 C-alpha pockets (64: 29.6 vs 32.4 us per launch for the 32-row full-K
-        // tiles, 96: 37.7 vs 58.7 for the 64-row plane tiles; profiles/r05_t); the coordinate list stays on 32-row tiles until it is long
-        if (half && e_est >= 96.0 * h->n_cus) h->edge_mt = 128;
-        // ... and more 16-row node tiles than CUs means two rounds of k_node16w where 64-row plane tiles need one
-        if (half && (N + 15) / 16 > h->n_cus) h->node_mt = 32;
-        // the 32-row full-K coordinate tiles run on the half engine, 16-row tiles on the fp32 instruction: 32 rows from a quarter of a tile per CU
-        // (48 pockets: 32.9 us per launch on 16-row tiles, 64 pockets: 18.3 on 32-row ones)
-        if (half && h->coord_mt == 16 && ec_est / 32.0 >= 0.25 * h->n_cus) h->coord_mt = 32;
-        if (half && h->edge_mt == 16 && e_est / 32.0 >= 0.25 * h->n_cus) h->edge_mt = 32;        // (16 pockets: 29.0 us on 16-row tiles; 32 pockets: 21.2 on 32-row ones)
-        if (ec_est / 32.0 >= 3.0 * h->n_cus) h->coord_mt = 128;      // (from 128 C-alpha pockets: profiles/r04_h)
-        // dense samples (full-atom pockets: 36 neighbours per node, ~60 coordinate edges per phar point while the points sit at the pocket centre):
-        // a receiver's edges outnumber the rows of a 16- / 32-row tile, its sum would be three or more float-atomic partials whose order the
-        // hardware picks - the 128-row kernels (variable tiles, >= 128-row chunks) keep it at two, so full-atom chains are reproducible run to run
-        if (h->lay.max_n > 128) { h->edge_mt = 128; h->coord_mt = 128; }
-        // joint chains noise the pocket nodes too: over the first steps a C-alpha sample is nearly fully connected (~48 k edges per evaluation
-        // on average at 64 pockets where the layout estimate says 34 k), and over those lists the 32-row full-K message tiles win - same-box
-        // chains at 64 / 128 / 256 pockets: +8.6 / +5.0 / +4.7 % (profiles/r06_m); the coordinate list (the same edges) stays on 128 rows
-        else if (half && d.joint && h->edge_mt == 128) h->edge_mt = 32;
-    }
-    // (the fp32 instruction / other widths have no 128-row kernels: their largest tile keeps most dense receivers at two partials)
-    if (!(h->gemm_split && d.H == 256) && h->lay.max_n > 128) { h->edge_mt = 64; h->coord_mt = 64; }
-    h->node_mt = (int)opt_of(h, "node_mt", h->node_mt);
-    h->edge_mt = (int)opt_of(h, "edge_mt", h->edge_mt);
-    h->coord_mt = (int)opt_of(h, "coord_mt", h->coord_mt);
-    // grids of the persistent-style edge kernels: enough workgroups for the estimated tile count, capped at
-    // what is co-resident per CU (2 at 64-row tiles, 4 below); surplus tiles are picked up by the loop
-    auto grid_for = [&](double rows, int mt) {
-        const double tiles = rows / mt + 1.0;
-        const int cap = (mt >= 64 ? 2 : 4) * h->n_cus;
-        int g = (int)(tiles * 1.25) + 8;
-        return g < h->n_cus / 4 ? h->n_cus / 4 : (g > cap ? cap : g);
-    };
-    h->edge_grid = grid_for(e_est, h->edge_mt);
-    h->coord_grid = grid_for(ec_est, h->coord_mt);
-    // the 128-row kernels' fused main loop pays once a workgroup (two per CU) walks more than one tile: same-box chains, profiles/r06_f
-    // (64 C-alpha pockets, one 96-row tile per workgroup: -1.6 %; 96 pockets, one 128-row tile: +1.2 %; 128 pockets: +2 %; 256: +3 %; full-atom: +8 %)
-    h->e128_fused = (e_est > 160.0 * h->n_cus ? 1 : 0) | (ec_est > 160.0 * h->n_cus ? 2 : 0);
-    if (opt_set(h, "e128_fused")) h->e128_fused = (int)opt_of(h, "e128_fused", 3) & 3;
-    if (opt_set(h, "edge_wgs_per_cu")) h->edge_grid = (int)opt_of(h, "edge_wgs_per_cu", 2) * h->n_cus;
-    if (opt_set(h, "coord_wgs_per_cu")) h->coord_grid = (int)opt_of(h, "coord_wgs_per_cu", 2) * h->n_cus;
-    if (h->node_mt != 64 && h->node_mt != 32 && h->node_mt != 16) h->node_mt = 64;
-    for (int* m : {&h->edge_mt, &h->coord_mt}) if (*m != 128 && *m != 64 && *m != 32 && *m != 16) *m = 64;     // 128: kernels_edge128.hip
+    return in;
 }
+void replan(cmdgen_handle* h) { h->plan = make_plan(plan_input(h)); }
 
 static int set_layout_impl(cmdgen_handle* h, int64_t batch, const int64_t* nph, const int64_t* npk, bool on_stream, hipStream_t stream);
 extern "C" int cmdgen_set_layout(cmdgen_handle* h, int64_t batch, const int64_t* nph, const int64_t* npk) {
@@ -498,7 +432,7 @@ static int set_layout_impl(cmdgen_handle* h, int64_t batch, const int64_t* nph, 
     }
     h->ecap = ecap; h->eccap = eccap;
     h->cur_nphar.assign(nph, nph + B); h->cur_npocket.assign(npk, npk + B);
-    pick_tiles(h);
+    replan(h);
     h->have_layout = true;
     return CMDGEN_OK;
 }
@@ -526,83 +460,12 @@ int begin_work(cmdgen_handle* h, hipStream_t s) {
 
 EvalLaunch make_launch(cmdgen_handle* h) {
     EvalLaunch a; a.lay = h->lay; a.w = h->work; a.d = h->dims; a.sw = h->small; a.layers = h->layers.data();
-    a.edge_grid = h->edge_grid; a.coord_grid = h->coord_grid;
+    a.plan = h->plan;
     a.prof_events = nullptr; a.ablate = 0;
-    a.node_mt = h->node_mt; a.edge_mt = h->edge_mt; a.coord_mt = h->coord_mt;
-    a.split = h->gemm_split ? 1 : 0;
-    a.n_cus = h->n_cus;
-    const bool sp256 = h->dims.H == 256 && h->gemm_split;
-    if (!sp256) { if (a.edge_mt == 128) a.edge_mt = 64; if (a.coord_mt == 128) a.coord_mt = 64; }      // the 128-row kernels are split-engine, H = 256
-    if (h->dims.sin && h->dims.H == 512) { if (a.edge_mt > 32) a.edge_mt = 32; if (a.coord_mt > 32) a.coord_mt = 32; }   // (64-row tiles + the 55 KB of feature columns exceed the LDS)
-    a.edge_fullk = (sp256 && opt_of(h, "edge_fullk", 1) != 0) ? 1 : 0;
-    a.e128_wgs = (int)opt_of(h, "e128_wgs_per_cu", 2);
-    a.e128_fused = h->e128_fused;
-    {   // the half engine's operands end at 65504: by default only where the radial features are bounded by a cutoff (every shipped config);
-        // 2 forces it, 0 keeps the three-piece bf16 split everywhere
-        const int he = (int)opt_of(h, "half_engine", 1);
-        a.half_engine = he == 2 || (he == 1 && h->dims.cutoff2 >= 0.f) ? 1 : 0;
-    }
-    a.write_embed = opt_of(h, "write_embed", 1) != 0 ? 1 : 0;
-    {   // k_node64 (kernels_node64.hip: 64-row node tiles, the A operand as producer-side bf16 planes, one workgroup per CU) against
-        // k_node<H, 32> (register split, two workgroups per CU).  Per launch the 64-row kernel takes ~0.89 of a co-resident pair of
-        // 32-row tiles, a 32-row tile alone on its CU ~0.62 of that 64-row tile (profiles/r03_m_node64.txt), so the choice is a matter
-        // of how the tiles fill the CUs: compare the rounds each needs.  Option "node64" = 0 / 1 (/ 32: the 32-row planes tile) overrides.
-        int on = 0;
-        if (sp256 && h->n_cus > 0 && h->have_layout) {
-            const int ncu = h->n_cus, t64 = (h->lay.N + 63) / 64, t32 = (h->lay.N + 31) / 32;
-            const float cost64 = (float)((t64 + ncu - 1) / ncu);
-            const int full = t32 / (2 * ncu), rem = t32 - full * 2 * ncu;
-            float cost32 = 1.12f * full + (rem == 0 ? 0.f : rem <= ncu ? 0.62f : 1.12f);
-            // half engine: k_node64 has a half form, the register-split 32-row tile has not - measured per launch (profiles/r05_t) 54.0 vs 44.6 us at
-            // 96 pockets (177 32-row tiles, one per CU), 87.5 vs 46.1 at 160 (two per CU)
-            if (a.half_engine) cost32 = 1.9f * full + (rem == 0 ? 0.f : rem <= ncu ? 1.22f : 1.9f);
-            on = cost64 < cost32 && !(a.half_engine && h->node_mt == 16);
-            // Round 6: on the half engine the 32-ROW plane tile (k_node32p: 193 registers, 67 KB of LDS - TWO workgroups per CU, so one's HBM phases run
-            // beside the other's GEMMs) beats both the 64-row tile and the register-split 32-row tile wherever the eight-wave 16-row tile does not apply:
-            // per evaluation -13 % at 80 C-alpha pockets, -10 % at 128, -1.4 % at 256, -2 % / -1.4 % at 64 / 256 full-atom pockets
-            // (profiles/r06_h_node_tile_sweep.txt; the 64-row tile stays behind option node64 = 1)
-            if (a.half_engine && h->node_mt != 16) on = 32;
-            // ... except where the 32-row tiles need both slots of a CU and the 64-row tiles still fit one per CU (8 k < N <= 16 k rows on 256 CUs: 144 - 272
-            // C-alpha pockets, the north star's 256): there the 64-row tile on EIGHT waves (k_node64e) streams the weights once per CU instead of twice and its
-            // GEMM phases run at the matrix pipe's rate (k_node32p's are bound by the 64 B/clk of L1 fill: 85 B/clk asked) - per evaluation -1.4 .. -1.9 %
-            // (profiles/r06_n_node64e.txt)
-            if (on == 32 && t32 > ncu && t64 <= ncu) on = 8;
-            // ... and with more 64-row tiles than CUs the lean 64-row tile, two workgroups per CU (k_node64d: 43 B/clk of weight fragments asked, and a
-            // partner workgroup beside every phase): per launch -5 % at 288 C-alpha pockets, -8 % at 384, -15 % at 512, -7 % / -11 % at 64 / 128 full-atom pockets
-            else if (on == 32 && t64 > ncu) on = 2;
-            if (opt_set(h, "node64")) { const int64_t v = opt_of(h, "node64", 0); on = v == 32 ? 32 : v == 8 ? 8 : v == 2 ? 2 : v != 0; }
-        }
-        a.node64 = on;
-        a.dead_skip = (h->dims.joint || h->dims.S != 1) ? 0 : (int)opt_of(h, "dead_skip", 2);   // (hop levels count blocks of ONE GCL)      // 2 (default): every block by hop level; 1: the last block only; 0: off
-        if (!on && !a.dead_skip) a.w.need_qc = nullptr;
-        a.w.hop_levels = a.dead_skip >= 2 ? h->dims.L : 1;
-        if (!a.dead_skip) a.w.ehop = nullptr;           // the graph pass fills the flags only for the kernels that read them
-    }
-    // 16-row node tiles on the split engine too (v_mfma_f32_16x16x32_bf16; H >= 128): k_node<256,16> 35.0 -> 31.4 us at B=64 -
-    // bound by the 6 B/weight stream of one workgroup per 16 rows, not by the matrix pipe (profiles/r03_b_*); option "node16_split" = 0 opts out
-    a.split16 = (a.split && h->dims.H >= 128 && opt_of(h, "node16_split", 1) != 0) ? 1 : 0;
-    a.node16w = opt_of(h, "node16w", 1) != 0 ? 1 : 0;
-    {   // k_embed: inside a conditional chain only the phar tiles take the full path (the pocket rows come from the per-chain
-        // cache), and they are few: 16-row tiles spread them over twice the CUs and halve the two projection passes of each
-        // (B=256: 120 tiles of 32 rows 38.6 us -> 240 tiles of 16 rows)
-        a.embed_mt = (int)opt_of(h, "embed_mt", (((double)h->lay.Nl / 16.0 <= 2.0 * h->n_cus && !h->dims.joint) ? 16 : a.node_mt));
-        if (a.embed_mt != 16 && a.embed_mt != 32 && a.embed_mt != 64) a.embed_mt = a.node_mt;
-    }
-    // (the node kernel avoids its 64-row register-split tiles on the split engine: 87 vs 132 us at B=256, profiles/r02_o_tile_sweep_split.txt)
-    if (a.split && a.node_mt == 64 && !opt_set(h, "node_mt")) a.node_mt = 32;
-    {   // the next block's P | Q projections as column-sliced tiles inside the coordinate launch (kernels_coord_proj.hip) instead of in k_node16w,
-        // whose 16-row tile streams every weight it multiplies: only where k_node16w takes the node launches AND the coordinate list runs on the
-        // 32-row full-K tile (the launch the projection tiles join), one GCL per block, the conditional model, and both roles on the same engine.
-        // Option "proj_in_coord": 0 never, 1 wherever that holds, unset: where it measured faster (profiles/proj_in_coord_ab.txt).
-        bool can = false;
-        if (!h->layers.empty() && a.d.H == 256 && a.d.S == 1 && a.d.L > 1 && !a.d.joint && !a.node64 && a.node_mt == 16 && a.split && a.split16 && a.node16w &&
-            a.edge_fullk && a.coord_mt == 32) {
-            const LayerW& lw = h->layers[0];
-            const bool half_n = a.half_engine && lw.W3.wh16, half_c = a.half_engine && lw.W7.wh;
-            can = lw.W3.ws16 && half_n == half_c && (half_n ? lw.Wpq_e.wh16 != nullptr : lw.Wpq_e.ws16 != nullptr);
-        }
-        a.proj_in_coord = can && opt_of(h, "proj_in_coord", 1) != 0 ? 1 : 0;
-    }
+    // the graph pass fills the flags only for the kernels that read them
+    if (!a.plan.node64 && !a.plan.dead_skip) a.w.need_qc = nullptr;
+    a.w.hop_levels = a.plan.dead_skip >= 2 ? h->dims.L : 1;
+    if (!a.plan.dead_skip) a.w.ehop = nullptr;
     return a;
 }
 
@@ -638,7 +501,7 @@ extern "C" int cmdgen_set_option(cmdgen_handle* h, const char* key, int64_t valu
     drop_graphs(h);
     if (unset) h->opts.erase(key); else h->opts[key] = value;
     refresh_tune(h);
-    if (h->have_layout) pick_tiles(h);
+    if (h->have_layout) replan(h);
     return CMDGEN_OK;
 }
 
@@ -1456,53 +1319,18 @@ extern "C" int cmdgen_set_gemm_mode(cmdgen_handle* h, int32_t split_bf16) {
     if (h->gemm_split != (split_bf16 != 0)) {
         drop_graphs(h);                 // captured graphs bake the kernel choice in; the pocket cache is rebuilt per chain anyway
         h->gemm_split = split_bf16 != 0;
-        if (h->have_layout) pick_tiles(h);
+        if (h->have_layout) replan(h);
     }
     return CMDGEN_OK;
-}
-
-// MFMAs per fp32 product of the three tile kernels of an evaluation, as the launchers pick them: 1 = the fp32 matrix instruction, 6 = three bf16
-// pieces per operand, 3 = the half engine (two fp16 pieces).  which: 0 messages, 1 node, 2 coordinates.
-static int mfmas_per_product(const EvalLaunch& a, int which) {
-    const LayerW& lw = a.layers[0];
-    const bool sampler = !a.save, h256 = a.d.H == 256;
-    if (which == 1) {
-        if (h256 && a.split && sampler && a.node64 && lw.W3.ws) return a.half_engine && lw.W3.wh ? 3 : 6;
-        if (h256 && a.node_mt == 16 && a.split16 && a.node16w && sampler && lw.W3.ws16) return a.half_engine && lw.W3.wh16 ? 3 : 6;
-        if ((a.split && a.node_mt >= 32) || (a.split16 && a.node_mt == 16)) return 6;
-        return 1;
-    }
-    const int mt = which == 0 ? a.edge_mt : a.coord_mt;
-    const WPack& W = which == 0 ? lw.W2 : lw.W7;
-    if (mt == 128 && h256 && a.split && sampler && W.ws) return a.half_engine && W.wh ? 3 : 6;
-    if (a.edge_fullk && sampler && a.split && h256 && mt == 32) return a.half_engine && W.wh ? 3 : 6;
-    if (a.split && mt >= 32) return 6;
-    return 1;
 }
 
 extern "C" int cmdgen_query(cmdgen_handle* h, const char* key, int64_t* value) {
     if (!h || !key || !value) return CMDGEN_EINVAL;
     if (!h->have_layout) return fail(h, CMDGEN_ESTATE, "no batch layout (cmdgen_set_layout)");
     const std::string k = key;
-    const EvalLaunch a = make_launch(h);
-    if (k == "node_mt") *value = a.node_mt;
-    else if (k == "edge_mt") *value = a.edge_mt;
-    else if (k == "e128_fused") *value = a.e128_fused;
-    else if (k == "coord_mt") *value = a.coord_mt;
-    else if (k == "edge_grid") *value = a.edge_grid;
-    else if (k == "coord_grid") *value = a.coord_grid;
-    else if (k == "gemm_split") *value = a.split;
-    else if (k == "half_engine") *value = a.split ? a.half_engine : 0;
-    else if (k == "msg_mfmas_per_product") *value = mfmas_per_product(a, 0);
-    else if (k == "node_mfmas_per_product") *value = mfmas_per_product(a, 1);
-    else if (k == "coord_mfmas_per_product") *value = mfmas_per_product(a, 2);
-    else if (k == "node16_split") *value = a.split16;
-    else if (k == "node64") *value = a.node64;
-    else if (k == "node16w") *value = a.node16w;
-    else if (k == "proj_in_coord") *value = a.proj_in_coord;
-    else if (k == "edge_fullk") *value = a.edge_fullk;
-    else if (k == "dead_skip") *value = a.dead_skip;
-    else if (k == "eval_gen") *value = h->eval_gen;
+    if (plan_query(h->plan, key, value)) return CMDGEN_OK;      // the launch keys: what the planner resolved (1 = the fp32 matrix instruction, 6 = three bf16
+                                                                // pieces per operand, 3 = the half engine, for the *_mfmas_per_product keys)
+    if (k == "eval_gen") *value = h->eval_gen;
     else if (k == "chain_graphs") { int64_t n = 0; for (const ChainSlot& c : h->chains) n += c.graph != nullptr ? 1 : 0; *value = n; }   // captured step graphs held
     else if (k == "train_half_ran") *value = h->train_fwd_half;
     else if (k == "train_range_event") *value = h->h_norm && !h->norm_pending ? (int64_t)h->h_norm[1] : 0;     // of the last collected norm

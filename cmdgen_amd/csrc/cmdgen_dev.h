@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include <vector>
 #include "cmdgen_split.h"
+#include "cmdgen_plan.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -219,9 +220,7 @@ struct TrainTune {              // launch choices of the training step's gradien
 struct EvalLaunch {             // everything one evaluation's launches need (host side)
     Layout lay; Work w; Dims d; SmallW sw;
     const LayerW* layers;       // host array [L]
-    int edge_grid, coord_grid;  // workgroups of the persistent-style edge kernels (tiles are taken round-robin)
-    int node_mt, edge_mt, coord_mt;   // rows per tile (64, 32 or 16) chosen per launch from the row counts
-    int embed_mt = 16;                // k_embed's tile (its critical path is a phar tile: encoders, embedding, two projections)
+    LaunchPlan plan;            // the kernel of each role, its rows per tile, grid and engine (cmdgen_plan.h)
     std::vector<hipEvent_t>* prof_events;  // when non-null: [3] vectors, (start, stop) event pairs of every msg / node / coord launch
     mutable hipEvent_t pe_start = nullptr, pe_stop = nullptr;   // the pair the next profiled launch carries (hipExtLaunchKernelGGL)
     int ablate;                 // timing-only builds of the edge kernel (cmdgen_time_edge_kernel); 0 in production
@@ -229,26 +228,11 @@ struct EvalLaunch {             // everything one evaluation's launches need (ho
     const TrainSave* save = nullptr;   // training forward: keep the activations (see TrainSave)
     PocketCache pcache{};       // conditional chains: pocket tiles of k_embed are an axpy from the cache
     int skip_count = 0;         // 1: the radius-graph count pass has run (fused step kernel); 2: both passes have (training)
-    int split = 0;              // 1: tiles of >= 32 rows multiply on the bf16 matrix pipe (Eng<MT, true>)
-    int split16 = 0;            // 1: 16-row node tiles too (Eng<16, true>; option "node16_split")
-    int n_cus = 256;
-    int edge_fullk = 0;         // 1: 32-row edge tiles of the sampler build all 256 columns at once (full-K planes; option "edge_fullk")
-    int node16w = 1;            // 1: 16-row node tiles of H = 256 on eight waves (kernels_node16w.hip)
-    int node64 = 0;             // 1: large batches run k_node as 64-row tiles with both images in LDS (kernels_node64.hip)
-    int dead_skip = 0;          // 2: every block of a conditional evaluation skips tiles whose new h nobody reads (by hop level); 1: the last block only; 0: off (option "dead_skip")
     mutable int unit = -1;      // weight unit (GCL) of the launches being issued: block l, sub-layer s -> l * S + s; -1: the block index itself (S = 1)
     mutable int skip_pc = 0;    // 1: the unit is not the last GCL of its block - its node kernel projects no P_c | Q_c
     mutable int frag_launches = 0;   // tile launches of this evaluation that read the fp32 FRAGMENT packs (the generic k_edge_msg / k_node / k_edge_coord forms): the training step re-packs those only when one will run
     mutable int live_thr = 0;   // set around a block's launches when that applies: nodes within this many hops of a moving node are still read
-    int save_half = 0;          // with `save`: W2 / W7 (.wh, .wh_dev) carry half packs re-made this step: the two edge kernels run their 32-row full-K half form
-    int save_half16 = 0;        // with `save`: W3 / W4 / Wpq_c / Wpq_e (.wh16, .wh_dev) carry 16-row half packs re-made this step: k_node16w<true>
-    int save_split = 0;         // with `save`: W2 / W7 carry split packs, the two edge kernels may use them (H = 256)
-    int write_embed = 1;        // 1: pass 2 of the radius graph and k_embed share a launch (k_write_embed) where both fit (option "write_embed")
-    int e128_wgs = 2;           // workgroups per CU of the 128-row edge kernels (kernels_edge128.hip)
-    int e128_fused = 3;         // bit 0 / 1: the 128-row message / coordinate kernel runs its fused main loop (half engine; lists long enough for more than one tile per workgroup)
-    int half_engine = 1;        // 1: split-engine kernels that have a HALF form (two fp16 pieces per operand, three MFMAs per product; cmdgen_split.h) use it
-    int proj_in_coord = 0;      // 1: the next block's P | Q projections run as column-sliced tiles in the coordinate launch instead of in k_node16w (kernels_coord_proj.hip; option "proj_in_coord")
-    mutable int proj_now = 0;   // ... and this evaluation does so (launch_eval: not a training forward, no parity stop, no per-stage events)
+    mutable int proj_now = 0;   // plan.proj_in_coord and this evaluation does so (launch_eval: not a training forward, no parity stop, no per-stage events)
 };
 // weight unit of block l's launches (EvalLaunch::unit), and the has_next argument of its node kernel: bit 0 = another unit follows
 // (its P | Q are projected), bits 1..28 = the dead-tile threshold of the plane tiles, bit 29 = the coordinate launch projects the next unit's

@@ -318,10 +318,9 @@ template <int H, int MT, int FK = 0> struct EdgeLds {       // FK: 0, or the num
     int s_live[2];                          // last block of a conditional evaluation: does the tile hold a receiver whose h is still read?
 };
 
-// tiles of >= 32 rows run on the split-bf16 engine when the launch asks for it (the training forward: only its two edge
-// kernels, and only when the step re-packed split weights for them - save_split); 16-row tiles are always fp32 MFMA
-// (there the L2 weight stream, not the matrix rate, binds)
-#define MT_DISPATCH(mt, FN, ...) do { const bool sp_ = a.split && (!a.save || a.save_split);                                                 \
+// tiles of >= 32 rows run on the split-bf16 engine when `sp` says so (the engine the plan resolved for the role: cmdgen_plan.h);
+// 16-row tiles are always fp32 MFMA (there the L2 weight stream, not the matrix rate, binds)
+#define MT_DISPATCH(mt, sp, FN, ...) do { const bool sp_ = (sp);                                                                             \
         if ((mt) >= 64) { if (sp_) FN<H, 64, true>(__VA_ARGS__); else FN<H, 64, false>(__VA_ARGS__); }                       \
         else if ((mt) == 32) { if (sp_) FN<H, 32, true>(__VA_ARGS__); else FN<H, 32, false>(__VA_ARGS__); }                 \
         else FN<H, 16, false>(__VA_ARGS__); } while (0)

@@ -59,10 +59,8 @@ struct cmdgen_handle {
     Work work{};
     int64_t ecap = 0, eccap = 0;
     int64_t cap_B = 0, cap_Nl = 0, cap_Np = 0, cap_N = 0, cap_e = 0, cap_ec = 0;   // allocated capacities of the workspaces
-    int edge_grid = 512, coord_grid = 256;
-    int e128_fused = 3;                    // bit 0 / 1: fused main loop of the 128-row message / coordinate kernel (pick_tiles)
     int n_cus = 256;
-    int node_mt = 64, edge_mt = 64, coord_mt = 64;   // rows per tile, chosen in cmdgen_set_layout
+    LaunchPlan plan;                       // the sampler's launch plan for the current layout, options, engine and weights (replan)
     bool gemm_split = true;                // tiles of >= 32 rows multiply on the bf16 matrix pipe (cmdgen_set_gemm_mode)
     int64_t* d_gid = nullptr;
     int* idx_blk[2] = {nullptr, nullptr};  // two copies of the index block: a new layout is written to the one the previous layout's kernels do not read
@@ -122,6 +120,8 @@ inline void free_pool(std::vector<void*>& pool) { for (void* p : pool) hipFree(p
 
 int check_ready(cmdgen_handle* h);
 int begin_work(cmdgen_handle* h, hipStream_t s);   // check_ready + device + workspace invariants; remembers the stream
+PlanInput plan_input(const cmdgen_handle* h);      // the sampler's planner input: dims, layout, options, engine, the packs the weights have
+void replan(cmdgen_handle* h);                     // h->plan again: after a new layout, option, engine or set of weights
 EvalLaunch make_launch(cmdgen_handle* h);
 inline int64_t opt_of(const cmdgen_handle* h, const char* key, int64_t dflt) { auto it = h->opts.find(key); return it == h->opts.end() ? dflt : it->second; }
 inline bool opt_set(const cmdgen_handle* h, const char* key) { return h->opts.find(key) != h->opts.end(); }

@@ -26,19 +26,21 @@ void cmdgen_launch_embed_tiles(const EvalLaunch& a, int mt, const float* xp, con
 void cmdgen_launch_embed_tiles_hx(const EvalLaunch& a, int mt, const float* xp, const float* xq, const float* t, const float4* coef, ChainState* chain, hipStream_t s);
 void cmdgen_launch_write_embed_tiles(const EvalLaunch& a, int mt, const float* xp, const float* xq, const float* t, const float4* coef, ChainState* chain, hipStream_t s);   // H = 256
 void cmdgen_embed_only_hx(const EvalLaunch& a, const float* xp, const float* xq, const float* t, hipStream_t s);
-void cmdgen_launch_msg_tiles(const EvalLaunch& a, int l, hipStream_t s);                   // kernels_egnn_msg.hip
+void cmdgen_launch_msg_tiles(const EvalLaunch& a, int l, hipStream_t s);                   // kernels_egnn_msg.hip: the generic tiles
 void cmdgen_launch_msg_tiles_hx(const EvalLaunch& a, int l, hipStream_t s);
-void cmdgen_launch_edge_msg_only(const EvalLaunch& a, int layer, hipStream_t s);
-void cmdgen_launch_edge_msg_only_hx(const EvalLaunch& a, int layer, hipStream_t s);
+void cmdgen_launch_msg_fullk(const EvalLaunch& a, int l, hipStream_t s);                   // ... and the 32-row full-K tiles (H = 256)
+void cmdgen_launch_edge_msg_only(const EvalLaunch& a, int layer, hipStream_t s);           // kernels_egnn.hip: one block's message launch alone
 void cmdgen_launch_node_tiles(const EvalLaunch& a, int l, hipStream_t s);                  // kernels_egnn_node.hip
 void cmdgen_launch_node_tiles_hx(const EvalLaunch& a, int l, hipStream_t s);
-void cmdgen_launch_coord_tiles(const EvalLaunch& a, int l, hipStream_t s);                 // kernels_egnn_coord.hip
+void cmdgen_launch_coord_tiles(const EvalLaunch& a, int l, hipStream_t s);                 // kernels_egnn_coord.hip: the generic tiles
 void cmdgen_launch_coord_tiles_hx(const EvalLaunch& a, int l, hipStream_t s);
-bool cmdgen_launch_node64(const EvalLaunch& a, int l, hipStream_t s);         // kernels_node64.hip: k_node for large batches
-bool cmdgen_launch_node16w(const EvalLaunch& a, int l, hipStream_t s);        // kernels_node16w.hip: 16-row tiles on eight waves (small batches)
-bool cmdgen_launch_msg128(const EvalLaunch& a, int l, hipStream_t s);         // kernels_edge128.hip: the edge kernels for long lists (128-row tiles)
-bool cmdgen_launch_coord128(const EvalLaunch& a, int l, hipStream_t s);
-bool cmdgen_launch_coord_proj(const EvalLaunch& a, int l, hipStream_t s);     // kernels_coord_proj.hip: the 32-row full-K coordinate tiles + the next block's P | Q tiles in one launch (EvalLaunch::proj_now)
+void cmdgen_launch_coord_fullk(const EvalLaunch& a, int l, hipStream_t s);                 // ... and the 32-row full-K tiles (H = 256)
+// one kernel family each, picked by launch_eval's switches on EvalLaunch::plan (kernels_egnn.hip)
+void cmdgen_launch_node64(const EvalLaunch& a, int l, hipStream_t s);         // kernels_node64.hip: k_node for large batches
+void cmdgen_launch_node16w(const EvalLaunch& a, int l, hipStream_t s);        // kernels_node16w.hip: 16-row tiles on eight waves (small batches)
+void cmdgen_launch_msg128(const EvalLaunch& a, int l, hipStream_t s);         // kernels_edge128.hip: the edge kernels for long lists (128-row tiles)
+void cmdgen_launch_coord128(const EvalLaunch& a, int l, hipStream_t s);
+void cmdgen_launch_coord_proj(const EvalLaunch& a, int l, hipStream_t s);     // kernels_coord_proj.hip: the 32-row full-K coordinate tiles + the next block's P | Q tiles in one launch (EvalLaunch::proj_now)
 
 // kernels_ddpm.hip: the conditional chain
 void cmdgen_launch_chain_init(const Layout& lay, const Dims& d, const ChainBuf& c, const float* px, const float* poh, hipStream_t s);

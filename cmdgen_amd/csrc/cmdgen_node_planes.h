@@ -4,7 +4,7 @@
 //   k_node32p  32 rows, four waves, two workgroups per CU
 //   k_node64e  64 rows, EIGHT waves (NCT = 1: one 32-column tile each), one workgroup per CU: two plane images, stores under the next GEMM's MFMAs
 //   k_node64d  64 rows, four waves, LEAN: ring of four, no fp32 h tile, buffer addressing - two workgroups per CU
-// (which one runs: make_launch, cmdgen_api.hip; why: kernels_node64.hip and profiles/r06_n_node64e.txt).
+// (which one runs: make_plan, cmdgen_plan.h; why: kernels_node64.hip and profiles/r06_n_node64e.txt).
 // Included once per matrix engine by kernels_node64.hip (N64_NPL = 3: three bf16 pieces per operand, six MFMAs per product; 2: two fp16
 // pieces, three MFMAs - the "half" engine of cmdgen_split.h; the eight-wave and the lean tile exist on the half engine only) inside a namespace
 // of its own.  No include guard on purpose.

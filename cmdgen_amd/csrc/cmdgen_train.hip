@@ -385,7 +385,15 @@ extern "C" int cmdgen_train_forward(cmdgen_handle* h, const float* theta, const 
     // activation store are sized from them
     EvalLaunch a = make_launch(h);
     ++h->eval_gen;                                                          // the graph pass below rewrites the evaluation workspace
-    a.dead_skip = 0; a.w.need_qc = nullptr; a.w.ehop = nullptr; a.w.hop_levels = 1;       // the training forward skips nothing: no hop levels in its graph pass
+    a.w.need_qc = nullptr; a.w.ehop = nullptr; a.w.hop_levels = 1;       // the training forward skips nothing: no hop levels in its graph pass
+    // its launch plan: the planner's training mode, given the packs this step can re-make on the device.  The list lengths are not known yet
+    // (E = Ec = 0): until the second make_plan below only fwd_half, node_half and reads_frag are read, and none of them depends on E / Ec
+    const bool split_packs = (h->gemm_split || t->bf16) && t->n_split > 0;
+    PlanInput pin = plan_input(h);
+    pin.training = true;
+    pin.W2 = pin.W7 = PlanPacks{split_packs && H == 256, t->n_half > 0, false, false};
+    pin.W3 = pin.Wpq_e = PlanPacks{false, false, false, t->n_half16 > 0};
+    a.plan = make_plan(pin);
     cmdgen_launch_edges(a, xh_phar, xh_pocket, s);
     // the list lengths come to the host through pinned memory and an event of their own: the re-packs below depend on the parameters only
     // and are queued BEHIND the copy, so the device works on them while the host wakes up (a stream synchronize would wait for them too)
@@ -398,18 +406,13 @@ extern "C" int cmdgen_train_forward(cmdgen_handle* h, const float* theta, const 
     // The forward pass IS the sampler's fused evaluation (k_embed, then per block k_edge_msg / k_node / k_edge_coord, then
     // k_readout) with save hooks that keep what the backward pass reads (TrainSave): ~20 launches instead of ~190, GEMMs on
     // the fragment-streaming tile kernels.  The parameters the optimizer has just updated are re-packed on the device.
-    // the forward's two edge kernels on the half engine (two fp16 pieces, three MFMAs per product: cmdgen_split.h) wherever the sampler would use it
-    const bool fwd_half = h->gemm_split && H == 256 && a.half_engine && a.edge_fullk && t->n_half > 0 && opt_of(h, "train_half", 1) != 0;
-    // ... and the node kernel as the sampler's eight-wave 16-row tile (k_node16w)
-    // (option train_node16: 16-row tiles for the node kernel at EVERY size - the save-hook form of the node kernel exists on the half engine
-    // for these tiles only; larger layouts otherwise fall back to the fp32-instruction k_node<H, 32 / 64, SAVE>)
-    if (fwd_half && opt_of(h, "train_node16", 1) != 0) a.node_mt = 16;
-    const bool node_half = fwd_half && a.node_mt == 16 && t->n_half16 > 0 && opt_of(h, "train_half", 1) != 2;
+    // the forward's two edge kernels / its node kernel on the half engine, as the plan says
+    const bool fwd_half = a.plan.fwd_half, node_half = a.plan.node_half;
     // fp32 fragment packs: with every tile kernel on the half engine only k_embed reads one (block 0's P | Q projection: the table's first entry)
-    const bool frag_partial = fwd_half && node_half;
+    const bool frag_partial = !a.plan.reads_frag;
     tr_repack(theta, t->frag_tab, frag_partial ? 1 : t->n_frag, t->max_frag4, t->misc_tab, t->n_misc, t->max_misc, s);
     if (h->gemm_split || t->bf16) tr_repack_split_t(theta, t->split_tab, t->n_split, s);        // data gradients (and the forward's two
-    t->split_packs_valid = (h->gemm_split || t->bf16) && t->n_split > 0;                         // edge kernels) on the bf16 matrix pipe
+    t->split_packs_valid = split_packs;                                                          // edge kernels) on the bf16 matrix pipe
     if (fwd_half) tr_repack_half(theta, t->half_tab, t->n_half_fwd, t->n_half_fwd, s);
     if (node_half) tr_repack_half16(theta, t->half16_tab, t->n_half16, t->max_half16, s);
     HIPCHK(h, hipEventSynchronize(t->tot_ev));
@@ -466,18 +469,8 @@ extern "C" int cmdgen_train_forward(cmdgen_handle* h, const float* theta, const 
     sv.qdec1 = t->qdec1; sv.qdeca = t->qdeca; sv.qdec_out = t->qdec_out;
     sv.ecap = t->ecap; sv.eccap = t->eccap;
     a.layers = t->layers.data(); a.sw = sw; a.save = &sv; a.skip_count = 2;
-    {   // tile rows of the two edge kernels: the training forward knows its lists' lengths (the sampler's pick_tiles estimates them, and its
-        // 128-row kernels have no activation-saving form): 32-row tiles until 64-row ones fill every CU four times over
-        auto rows = [&](int n) { return n / 64 >= 4 * h->n_cus ? 64 : (n / 32 >= h->n_cus / 4 ? 32 : 16); };
-        auto grid = [&](int n, int mt) { const int cap = (mt >= 64 ? 2 : 4) * h->n_cus, g = (int)((n / mt + 1) * 1.25) + 8; return g < h->n_cus / 4 ? h->n_cus / 4 : (g > cap ? cap : g); };
-        if (!opt_set(h, "edge_mt") || a.edge_mt == 128) { a.edge_mt = rows(E); a.edge_grid = grid(E, a.edge_mt); }
-        if (!opt_set(h, "coord_mt") || a.coord_mt == 128) { a.coord_mt = rows(Ec); a.coord_grid = grid(Ec, a.coord_mt); }
-        if (fwd_half) {     // the half form exists for 32-row full-K tiles (three workgroups per CU)
-            a.save_half = 1; a.save_half16 = node_half ? 1 : 0;
-            a.edge_mt = 32; a.edge_grid = grid(E, 32); a.coord_mt = 32; a.coord_grid = grid(Ec, 32);
-        }
-    }
-    a.save_split = (h->gemm_split && t->split_packs_valid && H == 256) ? 1 : 0;
+    pin.E = E; pin.Ec = Ec;                 // tile rows and grids of the two edge kernels from the lists' real lengths
+    a.plan = make_plan(pin);
     if (h->agg_dirty) { HIPCHK(h, hipMemsetAsync(h->work.agg, 0, NH * sizeof(float), s)); h->agg_dirty = false; }
     a.frag_launches = 0;
     t->shared_event = nullptr;
@@ -487,7 +480,7 @@ extern "C" int cmdgen_train_forward(cmdgen_handle* h, const float* theta, const 
     cmdgen_launch_save_positions(a, t->X, s);
     // Only the first fp32 fragment pack was refreshed above when every tile kernel was expected on its half form.  The launchers report what they
     // actually ran: a generic (fragment-reading) tile launch here would have multiplied with the weights of an earlier step - refuse the step
-    // instead of training on them (the conditions above and in launch_msg_fullk / launch_coord_fullk / cmdgen_launch_node16w must agree).
+    // instead of training on them (a backstop: the plan's reads_frag is made from the same kernel choice the launchers switch on).
     t->fwd_on_half = fwd_half;
     h->train_fwd_half = fwd_half ? 1 : 0;
     h->train_gen = h->eval_gen;

@@ -26,20 +26,19 @@ namespace cp_bf3 {
 #undef NW_NPL
 #undef NW_MFMA
 
-// launcher: true when the merged kernel took the coordinate launch of block l.  EvalLaunch::proj_now says that this evaluation's k_node16w launches
-// left the next block's P | Q out (make_launch / launch_eval hold the conditions); the last block has no next one and stays with k_edge_coord.
-bool cmdgen_launch_coord_proj(const EvalLaunch& a, int l, hipStream_t s) {
-    if (!a.proj_now || !unit_has_next(a, l)) return false;
+// launcher of the merged kernel (CoordKernel::fullk32_proj, for a block that has a next one in an evaluation with EvalLaunch::proj_now: this
+// evaluation's k_node16w launches leave the next block's P | Q out - the planner and launch_eval hold the conditions)
+void cmdgen_launch_coord_proj(const EvalLaunch& a, int l, hipStream_t s) {
     const LayerW& lw = a.layers[unit_of(a, l)];
     const LayerW& ln = a.layers[unit_of(a, l) + 1];
-    if (a.half_engine && lw.W7.wh) {
-        const int grid = cp_half::cp_grid(a.coord_grid, a.lay.N);
-        if (a.pe_start) hipExtLaunchKernelGGL(cp_half::k_coord_proj, dim3(grid), dim3(256), 0, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d, lw, ln, l, a.coord_grid);
-        else hipLaunchKernelGGL(cp_half::k_coord_proj, dim3(grid), dim3(256), 0, s, a.lay, a.w, a.d, lw, ln, l, a.coord_grid);
+    const int cg = a.plan.coord_grid;
+    if (a.plan.coord_eng == PlanEngine::half) {
+        const int grid = cp_half::cp_grid(cg, a.lay.N);
+        if (a.pe_start) hipExtLaunchKernelGGL(cp_half::k_coord_proj, dim3(grid), dim3(256), 0, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d, lw, ln, l, cg);
+        else hipLaunchKernelGGL(cp_half::k_coord_proj, dim3(grid), dim3(256), 0, s, a.lay, a.w, a.d, lw, ln, l, cg);
     } else {
-        const int grid = cp_bf3::cp_grid(a.coord_grid, a.lay.N);
-        if (a.pe_start) hipExtLaunchKernelGGL(cp_bf3::k_coord_proj, dim3(grid), dim3(256), 0, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d, lw, ln, l, a.coord_grid);
-        else hipLaunchKernelGGL(cp_bf3::k_coord_proj, dim3(grid), dim3(256), 0, s, a.lay, a.w, a.d, lw, ln, l, a.coord_grid);
+        const int grid = cp_bf3::cp_grid(cg, a.lay.N);
+        if (a.pe_start) hipExtLaunchKernelGGL(cp_bf3::k_coord_proj, dim3(grid), dim3(256), 0, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d, lw, ln, l, cg);
+        else hipLaunchKernelGGL(cp_bf3::k_coord_proj, dim3(grid), dim3(256), 0, s, a.lay, a.w, a.d, lw, ln, l, cg);
     }
-    return true;
 }

@@ -51,29 +51,22 @@ namespace e128_bf3 {
 #undef E128_MFMA
 
 
-// launchers: true when the 128-row kernels took the launch (H = 256, split engine, sampler)
+// launchers of the 128-row kernels (MsgKernel::e128 / CoordKernel::e128: H = 256, split engine, sampler)
 #define E128_LAUNCH(NSP, COORD_, LIVE)                                                                                                              \
     do {                                                                                                                                            \
-        {                                                                                                                                           \
-            const int grid = (a.e128_wgs >= 1 && a.e128_wgs <= 4 ? a.e128_wgs : 2) * a.n_cus;                                                       \
-            static bool lds_set = false;     /* (one flag per expansion = per kernel instantiation) */                                              \
-            if (!lds_set) { hipFuncSetAttribute(reinterpret_cast<const void*>(NSP::k_edge128<COORD_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(NSP::E128Lds)); lds_set = true; } \
-            if (a.pe_start) hipExtLaunchKernelGGL(NSP::k_edge128<COORD_>, dim3(grid), dim3(256), sizeof(NSP::E128Lds), s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d, a.layers[unit_of(a, l)], l, LIVE); \
-            else hipLaunchKernelGGL(NSP::k_edge128<COORD_>, dim3(grid), dim3(256), sizeof(NSP::E128Lds), s, a.lay, a.w, a.d, a.layers[unit_of(a, l)], l, LIVE);         \
-        }                                                                                                                                           \
+        static bool lds_set = false;     /* (one flag per expansion = per kernel instantiation) */                                                  \
+        if (!lds_set) { hipFuncSetAttribute(reinterpret_cast<const void*>(NSP::k_edge128<COORD_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(NSP::E128Lds)); lds_set = true; } \
+        if (a.pe_start) hipExtLaunchKernelGGL(NSP::k_edge128<COORD_>, dim3(a.plan.e128_grid), dim3(256), sizeof(NSP::E128Lds), s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d, a.layers[unit_of(a, l)], l, LIVE); \
+        else hipLaunchKernelGGL(NSP::k_edge128<COORD_>, dim3(a.plan.e128_grid), dim3(256), sizeof(NSP::E128Lds), s, a.lay, a.w, a.d, a.layers[unit_of(a, l)], l, LIVE);         \
     } while (0)
-bool cmdgen_launch_msg128(const EvalLaunch& a, int l, hipStream_t s) {
-    const WPack& W = a.layers[unit_of(a, l)].W2;
-    if (a.edge_mt != 128 || a.d.H != 256 || !a.split || a.save || !W.ws) return false;
-    if (a.half_engine && W.wh) { if (a.e128_fused & 1) E128_LAUNCH(e128_half, false, a.live_thr); else E128_LAUNCH(e128_half_u, false, a.live_thr); }
-    else E128_LAUNCH(e128_bf3, false, a.live_thr);
-    return true;
+void cmdgen_launch_msg128(const EvalLaunch& a, int l, hipStream_t s) {
+    if (a.plan.msg_eng != PlanEngine::half) E128_LAUNCH(e128_bf3, false, a.live_thr);
+    else if (a.plan.e128_fused & 1) E128_LAUNCH(e128_half, false, a.live_thr);
+    else E128_LAUNCH(e128_half_u, false, a.live_thr);
 }
-bool cmdgen_launch_coord128(const EvalLaunch& a, int l, hipStream_t s) {
-    const WPack& W = a.layers[unit_of(a, l)].W7;
-    if (a.coord_mt != 128 || a.d.H != 256 || !a.split || a.save || !W.ws) return false;
-    if (a.half_engine && W.wh) { if (a.e128_fused & 2) E128_LAUNCH(e128_half, true, 0); else E128_LAUNCH(e128_half_u, true, 0); }
-    else E128_LAUNCH(e128_bf3, true, 0);
-    return true;
+void cmdgen_launch_coord128(const EvalLaunch& a, int l, hipStream_t s) {
+    if (a.plan.coord_eng != PlanEngine::half) E128_LAUNCH(e128_bf3, true, 0);
+    else if (a.plan.e128_fused & 2) E128_LAUNCH(e128_half, true, 0);
+    else E128_LAUNCH(e128_half_u, true, 0);
 }
 #undef E128_LAUNCH

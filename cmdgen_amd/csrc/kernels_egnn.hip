@@ -146,6 +146,38 @@ __global__ __launch_bounds__(64) void k_vel_com(Layout lay, Work w, Dims d, floa
 // ------------------------------------------------------------------------------------
 // host-callable launchers (C++ linkage)
 // ------------------------------------------------------------------------------------
+// one launch per role, the kernel the plan names (cmdgen_plan.h)
+static void launch_msg(const EvalLaunch& a, int l, hipStream_t s) {
+    switch (a.plan.msg) {
+        case MsgKernel::e128:    cmdgen_launch_msg128(a, l, s); break;
+        case MsgKernel::fullk32: cmdgen_launch_msg_fullk(a, l, s); break;
+        case MsgKernel::tiles:   cmdgen_launch_msg_tiles(a, l, s); break;
+    }
+}
+static void launch_node(const EvalLaunch& a, int l, hipStream_t s) {
+    switch (a.plan.node) {
+        case NodeKernel::tiles:   cmdgen_launch_node_tiles(a, l, s); break;
+        case NodeKernel::node16w: cmdgen_launch_node16w(a, l, s); break;
+        default:                  cmdgen_launch_node64(a, l, s); break;     // k_node64 and its kin
+    }
+}
+static void launch_coord(const EvalLaunch& a, int l, hipStream_t s) {
+    switch (a.plan.coord) {
+        case CoordKernel::e128:  cmdgen_launch_coord128(a, l, s); break;
+        case CoordKernel::tiles: cmdgen_launch_coord_tiles(a, l, s); break;
+        case CoordKernel::fullk32_proj:      // (the last block has no next one and stays with k_edge_coord)
+            if (a.proj_now && unit_has_next(a, l)) { cmdgen_launch_coord_proj(a, l, s); break; }
+            [[fallthrough]];
+        case CoordKernel::fullk32: cmdgen_launch_coord_fullk(a, l, s); break;
+    }
+}
+// (the kernel the evaluation itself would run for this block's messages; weight unit of the block's first GCL when a block has several)
+void cmdgen_launch_edge_msg_only(const EvalLaunch& a, int layer, hipStream_t s) {
+    a.unit = layer * a.d.S;
+    launch_msg(a, layer, s);
+    a.unit = -1;
+}
+
 static void launch_eval(const EvalLaunch& a, const float* xh_phar, const float* xh_pocket,
                           const float* t_arr, const float4* coef, ChainState* chain,
                           float* eps_phar, float* eps_pocket, hipStream_t s,
@@ -160,10 +192,10 @@ static void launch_eval(const EvalLaunch& a, const float* xh_phar, const float* 
                            a.prof_events[k].push_back(a.pe_start); a.prof_events[k].push_back(a.pe_stop); } } while (0)
 #define PROF_END() do { a.pe_start = nullptr; a.pe_stop = nullptr; } while (0)
     // k_embed's tile: the small one only where the pocket cache serves the pocket rows (inside a conditional chain)
-    const int emt = (chain && !t_arr && a.pcache.c) ? a.embed_mt : a.node_mt;
-    // the next block's P | Q in the coordinate launch (EvalLaunch::proj_in_coord): the sampler's whole evaluations only - the training forward, the
+    const int emt = (chain && !t_arr && a.pcache.c) ? a.plan.embed_mt : a.plan.node_mt;
+    // the next block's P | Q in the coordinate launch (LaunchPlan::proj_in_coord): the sampler's whole evaluations only - the training forward, the
     // parity stops and the per-stage events keep every projection in the node launch
-    a.proj_now = (a.proj_in_coord && !a.save && a.stop_block < 0 && !ev) ? 1 : 0;
+    a.proj_now = (a.plan.proj_in_coord && !a.save && a.stop_block < 0 && !ev) ? 1 : 0;
     REC();
     // per-sample graph kernels: one wave scans one receiver at a time, so big samples (full-atom pockets: 381 nodes) get 16 waves
     const int gthr = a.lay.max_n > 128 ? 1024 : 256;
@@ -172,7 +204,7 @@ static void launch_eval(const EvalLaunch& a, const float* xh_phar, const float* 
         REC(); REC();
         cmdgen_launch_embed_tiles(a, emt, xh_phar, xh_pocket, t_arr, coef, chain, s);
     } else if (a.d.H == 256 && !ev && !a.save && gthr == 256 && shm <= 64 * 1024 && (size_t)emt * 1812 + 1024 + (shm > 12288 ? shm : 12288) <= 160 * 1024 &&
-               a.write_embed) {      // (static LDS of the embedding body is 1812 B per tile row; one launch must hold both bodies' LDS)
+               a.plan.write_embed) {      // (static LDS of the embedding body is 1812 B per tile row; one launch must hold both bodies' LDS)
         cmdgen_launch_write_embed_tiles(a, emt, xh_phar, xh_pocket, t_arr, coef, chain, s);       // both in one launch
     } else {
         cmdgen_launch_edge_write(a, s);
@@ -181,9 +213,9 @@ static void launch_eval(const EvalLaunch& a, const float* xh_phar, const float* 
     }
     REC();
     // dead work (conditional sampler, pocket output not asked for): see edge_msg_body / cmdgen_node_planes.h
-    const bool live_last = a.dead_skip && !eps_pocket && !a.save && !a.d.joint && a.stop_block < 0 && a.w.need_qc != nullptr;
+    const bool live_last = a.plan.dead_skip && !eps_pocket && !a.save && !a.d.joint && a.stop_block < 0 && a.w.need_qc != nullptr;
     for (int l = 0; l < a.d.L; ++l) {
-        a.live_thr = live_last ? (a.dead_skip >= 2 ? a.d.L - l : (l == a.d.L - 1 ? 1 : 0)) : 0;     // dead_skip 1: the last block only; 2: every block (a kernel argument of its own: any n_layers)
+        a.live_thr = live_last ? (a.plan.dead_skip >= 2 ? a.d.L - l : (l == a.d.L - 1 ? 1 : 0)) : 0;     // dead_skip 1: the last block only; 2: every block (a kernel argument of its own: any n_layers)
         const int stop = a.stop_block == l ? a.stop_stage : 0;        // parity aid: leave intermediates in the workspace
         // the block's GCLs (inv_sublayers, egnn_new.py:152-154): message + node kernel per unit; only the last one projects P_c | Q_c.
         // (The per-stage events and the prefix stops belong to the block's last unit; cmdgen_profile_evaluation asks for S = 1.)
@@ -192,18 +224,18 @@ static void launch_eval(const EvalLaunch& a, const float* xh_phar, const float* 
             a.unit = l * a.d.S + sub; a.skip_pc = last ? 0 : 1;
             if (last) REC();
             PROF_BEGIN(0);
-            if (!cmdgen_launch_msg128(a, l, s)) cmdgen_launch_msg_tiles(a, l, s);
+            launch_msg(a, l, s);
             PROF_END();
             if (last) { REC(); REC(); }
             if (last && stop == 1) { a.unit = -1; a.skip_pc = 0; return; }
             PROF_BEGIN(1);
-            if (!(a.node64 && cmdgen_launch_node64(a, l, s)) && !cmdgen_launch_node16w(a, l, s)) cmdgen_launch_node_tiles(a, l, s);
+            launch_node(a, l, s);
             PROF_END();
             if (last) { REC(); REC(); }
             if (last && stop == 2) { a.unit = -1; a.skip_pc = 0; return; }
         }
         PROF_BEGIN(2);
-        if (!cmdgen_launch_coord128(a, l, s)) cmdgen_launch_coord_tiles(a, l, s);
+        launch_coord(a, l, s);
         PROF_END();
         REC();
         a.unit = -1; a.skip_pc = 0;

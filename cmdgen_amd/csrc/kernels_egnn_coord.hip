@@ -151,36 +151,30 @@ __global__ __launch_bounds__(H, FK ? 3 : 2) void k_edge_coord(Layout lay, Work w
 // ------------------------------------------------------------------------------------
 #if CMDGEN_H_PART != 2
 #if CMDGEN_H_PART == 0
-static bool launch_coord_fullk(const EvalLaunch& a, int l, hipStream_t s) {
-    if (!a.edge_fullk || (a.save && !a.save_half) || !a.split || a.d.H != 256 || a.coord_mt != 32) return false;
+// 32-row full-K tiles - CoordKernel::fullk32 (and the last block of CoordKernel::fullk32_proj)
+void cmdgen_launch_coord_fullk(const EvalLaunch& a, int l, hipStream_t s) {
     const LayerW& lw = a.layers[unit_of(a, l)];
-    if (a.save) {
-        hipLaunchKernelGGL((k_edge_coord<256, 32, true, true, 2>), dim3(a.coord_grid), dim3(256), 0, s, a.lay, a.w, a.d, lw, l, *a.save);
-        return true;
-    }
-    if (a.half_engine && lw.W7.wh) {
-        if (a.pe_start) hipExtLaunchKernelGGL((k_edge_coord<256, 32, false, true, 2>), dim3(a.coord_grid), dim3(256), 0, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d, lw, l, TrainSave{});
-        else hipLaunchKernelGGL((k_edge_coord<256, 32, false, true, 2>), dim3(a.coord_grid), dim3(256), 0, s, a.lay, a.w, a.d, lw, l, TrainSave{});
+    if (a.save) hipLaunchKernelGGL((k_edge_coord<256, 32, true, true, 2>), dim3(a.plan.coord_grid), dim3(256), 0, s, a.lay, a.w, a.d, lw, l, *a.save);
+    else if (a.plan.coord_eng == PlanEngine::half) {
+        if (a.pe_start) hipExtLaunchKernelGGL((k_edge_coord<256, 32, false, true, 2>), dim3(a.plan.coord_grid), dim3(256), 0, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d, lw, l, TrainSave{});
+        else hipLaunchKernelGGL((k_edge_coord<256, 32, false, true, 2>), dim3(a.plan.coord_grid), dim3(256), 0, s, a.lay, a.w, a.d, lw, l, TrainSave{});
     } else {
-        if (a.pe_start) hipExtLaunchKernelGGL((k_edge_coord<256, 32, false, true, 3>), dim3(a.coord_grid), dim3(256), 0, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d, lw, l, TrainSave{});
-        else hipLaunchKernelGGL((k_edge_coord<256, 32, false, true, 3>), dim3(a.coord_grid), dim3(256), 0, s, a.lay, a.w, a.d, lw, l, TrainSave{});
+        if (a.pe_start) hipExtLaunchKernelGGL((k_edge_coord<256, 32, false, true, 3>), dim3(a.plan.coord_grid), dim3(256), 0, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d, lw, l, TrainSave{});
+        else hipLaunchKernelGGL((k_edge_coord<256, 32, false, true, 3>), dim3(a.plan.coord_grid), dim3(256), 0, s, a.lay, a.w, a.d, lw, l, TrainSave{});
     }
-    return true;
 }
 #endif
 template <int H, int MT, bool SP> static void launch_coord(const EvalLaunch& a, int l, hipStream_t s) {
     const size_t shm = a.d.sin ? (size_t)(24 * H + 24 * MT) * sizeof(float) : 0;
     ++a.frag_launches;
-    if (a.save) hipLaunchKernelGGL((k_edge_coord<H, MT, true, SP && H == 256>), dim3(a.coord_grid), dim3(H), 0, s, a.lay, a.w, a.d, a.layers[unit_of(a, l)], l, *a.save);
-    else if (a.pe_start) hipExtLaunchKernelGGL((k_edge_coord<H, MT, false, SP>), dim3(a.coord_grid), dim3(H), shm, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d,
+    if (a.save) hipLaunchKernelGGL((k_edge_coord<H, MT, true, SP && H == 256>), dim3(a.plan.coord_grid), dim3(H), 0, s, a.lay, a.w, a.d, a.layers[unit_of(a, l)], l, *a.save);
+    else if (a.pe_start) hipExtLaunchKernelGGL((k_edge_coord<H, MT, false, SP>), dim3(a.plan.coord_grid), dim3(H), shm, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d,
                                                a.layers[unit_of(a, l)], l, TrainSave{});
-    else hipLaunchKernelGGL((k_edge_coord<H, MT, false, SP>), dim3(a.coord_grid), dim3(H), shm, s, a.lay, a.w, a.d, a.layers[unit_of(a, l)], l, TrainSave{});
+    else hipLaunchKernelGGL((k_edge_coord<H, MT, false, SP>), dim3(a.plan.coord_grid), dim3(H), shm, s, a.lay, a.w, a.d, a.layers[unit_of(a, l)], l, TrainSave{});
 }
-template <int H> static void coord_tiles_H(const EvalLaunch& a, int l, hipStream_t s) { MT_DISPATCH(a.coord_mt, launch_coord, a, l, s); }
+template <int H> static void coord_tiles_H(const EvalLaunch& a, int l, hipStream_t s) { MT_DISPATCH(a.plan.coord_mt, a.plan.coord_eng == PlanEngine::bf3, launch_coord, a, l, s); }
 #if CMDGEN_H_PART == 0
 void cmdgen_launch_coord_tiles(const EvalLaunch& a, int l, hipStream_t s) {
-    if (cmdgen_launch_coord_proj(a, l, s)) return;             // the 32-row full-K tiles + the next block's P | Q (kernels_coord_proj.hip)
-    if (launch_coord_fullk(a, l, s)) return;
     if (a.d.H == 256) coord_tiles_H<256>(a, l, s); else cmdgen_launch_coord_tiles_hx(a, l, s);
 }
 #else

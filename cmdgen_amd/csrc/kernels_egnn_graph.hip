@@ -501,10 +501,10 @@ template <int H, int MT, bool SP> static void launch_write_embed(const EvalLaunc
     }
 }
 template <int H> static void embed_only_H(const EvalLaunch& a, const float* xp, const float* xq, const float* t, hipStream_t s) {
-    MT_DISPATCH(a.node_mt, launch_embed, a, xp, xq, t, nullptr, nullptr, s);
+    MT_DISPATCH(a.plan.node_mt, a.plan.gemm_split != 0, launch_embed, a, xp, xq, t, nullptr, nullptr, s);
 }
 template <int H> static void embed_tiles_H(const EvalLaunch& a, int mt, const float* xp, const float* xq, const float* t, const float4* coef, ChainState* chain, hipStream_t s) {
-    MT_DISPATCH(mt, launch_embed, a, xp, xq, t, coef, chain, s);
+    MT_DISPATCH(mt, a.plan.gemm_split != 0, launch_embed, a, xp, xq, t, coef, chain, s);
 }
 #if CMDGEN_H_PART == 0
 void cmdgen_launch_embed_tiles(const EvalLaunch& a, int mt, const float* xp, const float* xq, const float* t, const float4* coef, ChainState* chain, hipStream_t s) {
@@ -523,7 +523,7 @@ void cmdgen_launch_embed_tiles_hx(const EvalLaunch& a, int mt, const float* xp, 
 #if CMDGEN_H_PART == 0
 void cmdgen_launch_write_embed_tiles(const EvalLaunch& a, int mt, const float* xp, const float* xq, const float* t, const float4* coef, ChainState* chain, hipStream_t s) {
     constexpr int H = 256;
-    MT_DISPATCH(mt, launch_write_embed, a, xp, xq, t, coef, chain, s);
+    MT_DISPATCH(mt, a.plan.gemm_split != 0, launch_write_embed, a, xp, xq, t, coef, chain, s);
 }
 void cmdgen_launch_edge_count(const EvalLaunch& a, const float* xh_phar, const float* xh_pocket, hipStream_t s) {
     const size_t shm = (size_t)a.lay.max_n * (sizeof(float4) + 3 * sizeof(int));

@@ -210,38 +210,32 @@ __global__ __launch_bounds__(H, FK ? 3 : 2) void k_edge_msg(Layout lay, Work w, 
 // ------------------------------------------------------------------------------------
 template <int H, int MT, bool SP> static void launch_msg(const EvalLaunch& a, int l, hipStream_t s) {
     const size_t shm = a.d.sin ? (size_t)(24 * H + 24 * MT) * sizeof(float) : 0;      // sin_embedding: feature columns + the tile's features (edge_msg_body)
-    // training forward: the split engine only where the step re-packs split weights (H = 256: edge_mlp.2 / coord_mlp.2)
     ++a.frag_launches;
-    if (a.save) { TrainSave sv = *a.save; sv.slot = unit_of(a, l); hipLaunchKernelGGL((k_edge_msg<H, MT, true, SP && H == 256>), dim3(a.edge_grid), dim3(H), 0, s, a.lay, a.w, a.d, a.layers[unit_of(a, l)], l, a.ablate, sv, 0); }
-    else if (a.pe_start) hipExtLaunchKernelGGL((k_edge_msg<H, MT, false, SP>), dim3(a.edge_grid), dim3(H), shm, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d,
+    if (a.save) { TrainSave sv = *a.save; sv.slot = unit_of(a, l); hipLaunchKernelGGL((k_edge_msg<H, MT, true, SP && H == 256>), dim3(a.plan.edge_grid), dim3(H), 0, s, a.lay, a.w, a.d, a.layers[unit_of(a, l)], l, a.ablate, sv, 0); }
+    else if (a.pe_start) hipExtLaunchKernelGGL((k_edge_msg<H, MT, false, SP>), dim3(a.plan.edge_grid), dim3(H), shm, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d,
                                                a.layers[unit_of(a, l)], l, a.ablate, TrainSave{}, a.live_thr);
-    else hipLaunchKernelGGL((k_edge_msg<H, MT, false, SP>), dim3(a.edge_grid), dim3(H), shm, s, a.lay, a.w, a.d, a.layers[unit_of(a, l)], l, a.ablate, TrainSave{}, a.live_thr);
+    else hipLaunchKernelGGL((k_edge_msg<H, MT, false, SP>), dim3(a.plan.edge_grid), dim3(H), shm, s, a.lay, a.w, a.d, a.layers[unit_of(a, l)], l, a.ablate, TrainSave{}, a.live_thr);
 }
 #if CMDGEN_H_PART == 0
-// 32-row sampler tiles on the split engine: full-K planes (one build, one GEMM per tile; see cmdgen_split.h) unless CMDGEN_EDGE_FULLK=0
-static bool launch_msg_fullk(const EvalLaunch& a, int l, hipStream_t s) {
-    if (!a.edge_fullk || (a.save && !a.save_half) || !a.split || a.d.H != 256 || a.edge_mt != 32) return false;
+// 32-row tiles on the split engine: full-K planes (one build, one GEMM per tile; see cmdgen_split.h) - MsgKernel::fullk32
+void cmdgen_launch_msg_fullk(const EvalLaunch& a, int l, hipStream_t s) {
     const LayerW& lw = a.layers[unit_of(a, l)];
     if (a.save) {       // training forward on the half engine (packs and scale re-made on the device every step: WPack::wh_dev)
         TrainSave sv = *a.save; sv.slot = unit_of(a, l);
-        hipLaunchKernelGGL((k_edge_msg<256, 32, true, true, 2>), dim3(a.edge_grid), dim3(256), 0, s, a.lay, a.w, a.d, lw, l, a.ablate, sv, 0);
-        return true;
-    }
-    if (a.half_engine && lw.W2.wh) {
-        if (a.pe_start) hipExtLaunchKernelGGL((k_edge_msg<256, 32, false, true, 2>), dim3(a.edge_grid), dim3(256), 0, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d, lw, l, a.ablate, TrainSave{}, a.live_thr);
-        else hipLaunchKernelGGL((k_edge_msg<256, 32, false, true, 2>), dim3(a.edge_grid), dim3(256), 0, s, a.lay, a.w, a.d, lw, l, a.ablate, TrainSave{}, a.live_thr);
+        hipLaunchKernelGGL((k_edge_msg<256, 32, true, true, 2>), dim3(a.plan.edge_grid), dim3(256), 0, s, a.lay, a.w, a.d, lw, l, a.ablate, sv, 0);
+    } else if (a.plan.msg_eng == PlanEngine::half) {
+        if (a.pe_start) hipExtLaunchKernelGGL((k_edge_msg<256, 32, false, true, 2>), dim3(a.plan.edge_grid), dim3(256), 0, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d, lw, l, a.ablate, TrainSave{}, a.live_thr);
+        else hipLaunchKernelGGL((k_edge_msg<256, 32, false, true, 2>), dim3(a.plan.edge_grid), dim3(256), 0, s, a.lay, a.w, a.d, lw, l, a.ablate, TrainSave{}, a.live_thr);
     } else {
-        if (a.pe_start) hipExtLaunchKernelGGL((k_edge_msg<256, 32, false, true, 3>), dim3(a.edge_grid), dim3(256), 0, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d, lw, l, a.ablate, TrainSave{}, a.live_thr);
-        else hipLaunchKernelGGL((k_edge_msg<256, 32, false, true, 3>), dim3(a.edge_grid), dim3(256), 0, s, a.lay, a.w, a.d, lw, l, a.ablate, TrainSave{}, a.live_thr);
+        if (a.pe_start) hipExtLaunchKernelGGL((k_edge_msg<256, 32, false, true, 3>), dim3(a.plan.edge_grid), dim3(256), 0, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d, lw, l, a.ablate, TrainSave{}, a.live_thr);
+        else hipLaunchKernelGGL((k_edge_msg<256, 32, false, true, 3>), dim3(a.plan.edge_grid), dim3(256), 0, s, a.lay, a.w, a.d, lw, l, a.ablate, TrainSave{}, a.live_thr);
     }
-    return true;
 }
 #endif
-template <int H> static void msg_tiles_H(const EvalLaunch& a, int l, hipStream_t s) { MT_DISPATCH(a.edge_mt, launch_msg, a, l, s); }
-// the launch of one block's message kernel on <= 64-row tiles: the full-K 32-row form where it applies, else the generic dispatch
+template <int H> static void msg_tiles_H(const EvalLaunch& a, int l, hipStream_t s) { MT_DISPATCH(a.plan.edge_mt, a.plan.msg_eng == PlanEngine::bf3, launch_msg, a, l, s); }
+// the launch of one block's message kernel on the generic <= 64-row tiles - MsgKernel::tiles
 #if CMDGEN_H_PART == 0
 void cmdgen_launch_msg_tiles(const EvalLaunch& a, int l, hipStream_t s) {
-    if (launch_msg_fullk(a, l, s)) return;
     if (a.d.H == 256) msg_tiles_H<256>(a, l, s); else cmdgen_launch_msg_tiles_hx(a, l, s);
 }
 #else
@@ -251,33 +245,6 @@ void cmdgen_launch_msg_tiles_hx(const EvalLaunch& a, int l, hipStream_t s) {
         case 128: msg_tiles_H<128>(a, l, s); break;
         case 64:  msg_tiles_H<64>(a, l, s); break;
         default: break;   // rejected in cmdgen_create
-    }
-}
-#endif
-
-// (the kernel the evaluation itself would run for this block: the 128-row kernel, then the full-K 32-row tiles, then the generic dispatch;
-// weight unit of the block's first GCL when a block has several)
-#if CMDGEN_H_PART == 0
-template <int H> static void launch_msg_only_H(const EvalLaunch& a, int layer, hipStream_t s) {
-    a.unit = layer * a.d.S;
-    if (!cmdgen_launch_msg128(a, layer, s) && !launch_msg_fullk(a, layer, s)) MT_DISPATCH(a.edge_mt, launch_msg, a, layer, s);
-    a.unit = -1;
-}
-void cmdgen_launch_edge_msg_only(const EvalLaunch& a, int layer, hipStream_t s) {
-    if (a.d.H == 256) launch_msg_only_H<256>(a, layer, s); else cmdgen_launch_edge_msg_only_hx(a, layer, s);
-}
-#else
-template <int H> static void launch_msg_only_H(const EvalLaunch& a, int layer, hipStream_t s) {
-    a.unit = layer * a.d.S;
-    MT_DISPATCH(a.edge_mt, launch_msg, a, layer, s);          // (the 128-row and full-K forms are hidden_nf = 256 only)
-    a.unit = -1;
-}
-void cmdgen_launch_edge_msg_only_hx(const EvalLaunch& a, int layer, hipStream_t s) {
-    switch (a.d.H) {
-        case 512: launch_msg_only_H<512>(a, layer, s); break;
-        case 128: launch_msg_only_H<128>(a, layer, s); break;
-        case 64:  launch_msg_only_H<64>(a, layer, s); break;
-        default: break;
     }
 }
 #endif

@@ -188,10 +188,6 @@ __global__ __launch_bounds__(H, (MT == 16 && SP) ? 1 : 2) void k_node(Layout lay
 // ------------------------------------------------------------------------------------
 // SAVE variants (training forward) keep the activations; the sampler's instantiations carry no trace of the stores
 template <int H, int MT, bool SP> static void launch_node(const EvalLaunch& a, int l, hipStream_t s) {
-    if constexpr (MT == 16 && !SP && H >= 128) {
-        // 16-row tiles on the split engine (v_mfma_f32_16x16x32_bf16): opt-in, see DESIGN section 4a for why it is not the default
-        if (a.split16 && !a.save && a.layers[unit_of(a, l)].W3.ws16) { launch_node<H, 16, true>(a, l, s); return; }
-    }
     const int nt = (a.lay.N + MT - 1) / MT;
     ++a.frag_launches;
     if (a.save) {
@@ -204,7 +200,12 @@ template <int H, int MT, bool SP> static void launch_node(const EvalLaunch& a, i
     else hipLaunchKernelGGL((k_node<H, MT, false, SP>), dim3(nt), dim3(H), 0, s, a.lay, a.w, a.d, a.layers[unit_of(a, l)],
                             a.layers[unit_has_next(a, l) ? unit_of(a, l) + 1 : unit_of(a, l)], l, node_flags(a, l), TrainSave{});
 }
-template <int H> static void node_tiles_H(const EvalLaunch& a, int l, hipStream_t s) { MT_DISPATCH(a.node_mt, launch_node, a, l, s); }
+template <int H> static void node_tiles_H(const EvalLaunch& a, int l, hipStream_t s) {
+    const bool sp = a.plan.node_eng == PlanEngine::bf3;
+    // 16-row tiles on the split engine too (v_mfma_f32_16x16x32_bf16; H >= 128, option node16_split): the node kernel alone has that form
+    if constexpr (H >= 128) if (sp && a.plan.node_mt == 16) { launch_node<H, 16, true>(a, l, s); return; }
+    MT_DISPATCH(a.plan.node_mt, sp, launch_node, a, l, s);
+}
 #if CMDGEN_H_PART == 0
 void cmdgen_launch_node_tiles(const EvalLaunch& a, int l, hipStream_t s) {
     if (a.d.H == 256) node_tiles_H<256>(a, l, s); else cmdgen_launch_node_tiles_hx(a, l, s);

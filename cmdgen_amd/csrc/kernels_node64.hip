@@ -17,7 +17,7 @@
 //
 // Round 6: what bounds a node tile is the chain's 1.8 MB of weight fragments through its CU's L1 (64 B/clk; every tile streams all of it,
 // co-resident workgroups share nothing: TCP_TCC_READ_REQ, profiles/r06_n_node64e.txt).  Four tiles of one body, picked by how the layout's
-// tiles fill the CUs (make_launch): k_node32p (two workgroups per CU: a partner beside every phase, but 85 B/clk asked in the GEMM phases),
+// tiles fill the CUs (make_plan, cmdgen_plan.h): k_node32p (two workgroups per CU: a partner beside every phase, but 85 B/clk asked in the GEMM phases),
 // k_node64e (64 rows on eight waves: 43 B/clk, GEMM phases at the matrix pipe's rate, no partner - so its stores leave under the next GEMM's
 // MFMAs), k_node64d (lean 64-row tile, two workgroups per CU: both), and k_node64 (the round-3 tile, option node64 = 1).
 #include "cmdgen_dev.h"
@@ -69,31 +69,22 @@ __global__ __launch_bounds__(256, 1) void k_node32p(Layout lay, Work w, Dims d, 
 }
 }
 
-// launcher: true when the 64-row kernel took the launch (H = 256, split engine, sampler)
-#define N64_LAUNCH(NSP, EIGHT)                                                                                                                              \
+// launcher of the plane kernels: the one the plan names (H = 256, split engine, sampler); k_node64d / k_node64e exist on the half engine
+#define N64_LAUNCH(KERNEL, ROWS, THREADS)                                                                                                            \
     do {                                                                                                                                             \
-        const LayerW& lw_ = a.layers[unit_of(a, l)]; const LayerW& ln_ = a.layers[unit_has_next(a, l) ? unit_of(a, l) + 1 : unit_of(a, l)];          \
-        if (a.node64 == 2 && EIGHT) {                                                                                                                \
-            const int nt = (a.lay.N + 63) / 64;                                                                                                      \
-            if (a.pe_start) hipExtLaunchKernelGGL(n64_half::k_node64d, dim3(nt), dim3(256), 0, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d, lw_, ln_, l, node_flags(a, l)); \
-            else hipLaunchKernelGGL(n64_half::k_node64d, dim3(nt), dim3(256), 0, s, a.lay, a.w, a.d, lw_, ln_, l, node_flags(a, l));                  \
-        } else if (a.node64 == 8 && EIGHT) {                                                                                                         \
-            const int nt = (a.lay.N + 63) / 64;                                                                                                      \
-            if (a.pe_start) hipExtLaunchKernelGGL(n64_half::k_node64e, dim3(nt), dim3(512), 0, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d, lw_, ln_, l, node_flags(a, l)); \
-            else hipLaunchKernelGGL(n64_half::k_node64e, dim3(nt), dim3(512), 0, s, a.lay, a.w, a.d, lw_, ln_, l, node_flags(a, l));                  \
-        } else if (a.node64 == 32) {                                                                                                                 \
-            const int nt32 = (a.lay.N + 31) / 32;                                                                                                    \
-            if (a.pe_start) hipExtLaunchKernelGGL(NSP::k_node32p, dim3(nt32), dim3(256), 0, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d, lw_, ln_, l, node_flags(a, l)); \
-            else hipLaunchKernelGGL(NSP::k_node32p, dim3(nt32), dim3(256), 0, s, a.lay, a.w, a.d, lw_, ln_, l, node_flags(a, l));                     \
-        } else {                                                                                                                                     \
-            const int nt = (a.lay.N + 63) / 64;                                                                                                      \
-            if (a.pe_start) hipExtLaunchKernelGGL(NSP::k_node64, dim3(nt), dim3(256), 0, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d, lw_, ln_, l, node_flags(a, l)); \
-            else hipLaunchKernelGGL(NSP::k_node64, dim3(nt), dim3(256), 0, s, a.lay, a.w, a.d, lw_, ln_, l, node_flags(a, l));                        \
-        }                                                                                                                                            \
+        const int nt = (a.lay.N + ROWS - 1) / ROWS;                                                                                                  \
+        if (a.pe_start) hipExtLaunchKernelGGL(KERNEL, dim3(nt), dim3(THREADS), 0, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d, lw, ln, l, node_flags(a, l)); \
+        else hipLaunchKernelGGL(KERNEL, dim3(nt), dim3(THREADS), 0, s, a.lay, a.w, a.d, lw, ln, l, node_flags(a, l));                                \
     } while (0)
-bool cmdgen_launch_node64(const EvalLaunch& a, int l, hipStream_t s) {
-    if (a.d.H != 256 || !a.split || a.save || !a.node64 || !a.layers[unit_of(a, l)].W3.ws) return false;
-    if (a.half_engine && a.layers[unit_of(a, l)].W3.wh) N64_LAUNCH(n64_half, true); else N64_LAUNCH(n64_bf3, false);
-    return true;
+void cmdgen_launch_node64(const EvalLaunch& a, int l, hipStream_t s) {
+    const LayerW& lw = a.layers[unit_of(a, l)]; const LayerW& ln = a.layers[unit_has_next(a, l) ? unit_of(a, l) + 1 : unit_of(a, l)];
+    const bool half = a.plan.node_eng == PlanEngine::half;
+    switch (a.plan.node) {
+        case NodeKernel::node64d: N64_LAUNCH(n64_half::k_node64d, 64, 256); break;
+        case NodeKernel::node64e: N64_LAUNCH(n64_half::k_node64e, 64, 512); break;
+        case NodeKernel::node32p: if (half) N64_LAUNCH(n64_half::k_node32p, 32, 256); else N64_LAUNCH(n64_bf3::k_node32p, 32, 256); break;
+        case NodeKernel::node64:  if (half) N64_LAUNCH(n64_half::k_node64, 64, 256); else N64_LAUNCH(n64_bf3::k_node64, 64, 256); break;
+        default: break;           // (launch_eval sends the other node kernels elsewhere)
+    }
 }
 #undef N64_LAUNCH

@@ -1,10 +1,10 @@
 """Cases, inputs and oracle results of the tile-rule sweep (test_hip_rule_sweep.py on the GPU, test_rule_sweep_cpu.py without one).
 
-Between 1 and ~300 C-alpha pockets pick_tiles / make_launch (csrc/cmdgen_api.hip) change the kernels of an evaluation about ten times, from the
-layout alone.  Every case below is one layout with NO launch option set, and carries the launch the library resolves for it on a 256-CU device:
-LAUNCH_KEYS read through Handle.query.  The tuples were evaluated on the CPU from a transcription of those functions (which reproduces the
-rule table of uniform 44 + 15 samples: regimes from 1, 4, 9, 47, 70, 78, 106, 139, 176 and 278 pockets); the GPU test asserts them where
-multi_processor_count == 256, so whoever moves a threshold moves these sizes with it.
+Between 1 and ~300 C-alpha pockets the launch planner (make_plan, csrc/cmdgen_plan.h) changes the kernels of an evaluation about ten times, from
+the layout alone.  Every case below is one layout with NO launch option set, and carries the launch the library resolves for it on a 256-CU
+device: LAUNCH_KEYS read through Handle.query (the rule table of uniform 44 + 15 samples: regimes from 1, 4, 9, 47, 70, 78, 106, 139, 176 and
+278 pockets).  test_rule_sweep_cpu.py asserts the tuples against the planner itself on the CPU, the GPU test where multi_processor_count == 256,
+so whoever moves a threshold moves these sizes with it.
 
 Inputs: ragged pockets (make_pockets(B, 'CA', ragged=True, first_index=7000): tile and chunk boundaries fall inside samples, N is rarely a
 multiple of a tile) with the phar points inside the pocket (test_hip_properties.eval_inputs' law) or, geometry 'drifted', as one compact body

@@ -98,7 +98,7 @@ def test_equal_masks_from_the_prior_equal_inpaint_chain_bit_for_bit(use_graph, s
     injected noise, for (r, j) = (1, 1) and (2, 2), on the default and the fp32 instruction engine.
 
     Tile rows on the fp32 instruction engine.  Comparing two runs bit for bit presupposes that one run is reproducible, and the library
-    states when it is (pick_tiles, cmdgen_api.hip): k_edge_msg / k_edge_coord add a receiver's per-tile partial sums with float atomics, so
+    states when it is (make_plan, cmdgen_plan.h): k_edge_msg / k_edge_coord add a receiver's per-tile partial sums with float atomics, so
     a receiver whose edges span three or more tiles is summed in an order the hardware picks.  At this size that engine would choose
     16-row tiles, and a phar point in the pocket's centre has more than the 17 edges two such tiles are sure to hold (measured: two
     inpaint_chain runs of the SAME inputs then differ in the last bit of ~1000 saved h values, max 1.4e-6, outputs equal).  With 64-row

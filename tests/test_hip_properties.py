@@ -157,7 +157,7 @@ def test_a_pockets_chain_does_not_depend_on_its_batch_at_256_pockets():
 def test_chains_are_reproducible_bit_for_bit(rep, B, K):
     """Two fresh handles, the same Philox seed: identical bits, step by step.  Per receiver a segment sum is ordered inside a tile and has at
     most two float-atomic partials across tiles (which commute) as long as the receiver's edges are fewer than a tile's rows: C-alpha layouts
-    have ~20 edges per receiver on 32-row tiles, dense (full-atom) layouts ~60 on the 128-row kernels with >= 128-row chunks (pick_tiles).
+    have ~20 edges per receiver on 32-row tiles, dense (full-atom) layouts ~60 on the 128-row kernels with >= 128-row chunks (make_plan, cmdgen_plan.h).
     The chain starts with every phar point at the pocket centre - the densest graph it sees."""
     cfg = bounded_config(20 if rep == 'CA' else 11, 1000)
     sd = make_state_dict(cfg, seed=0)

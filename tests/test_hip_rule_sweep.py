@@ -1,6 +1,6 @@
 """The library's OWN launches against the oracle on both sides of every boundary of its tile rules, 1 - 278 C-alpha pockets.
 
-pick_tiles / make_launch (csrc/cmdgen_api.hip) choose the kernels of an evaluation from the layout alone, about ten times between 1 and 300
+The launch planner (make_plan, csrc/cmdgen_plan.h) chooses the kernels of an evaluation from the layout alone, about ten times between 1 and 300
 pockets; the other suites compare the library's own choice with the reference in three of those regimes and are self-consistency checks
 (option against option, permutation, reflection) everywhere else, which a mistake shared by both sides passes.  Here no tile option is set:
 
@@ -51,6 +51,27 @@ def resolved(h):
 def table_applies():
     """The case table's launches are those of 256 CUs with every choice left to the library (conftest's CMDGEN_TEST_OPTIONS sets some)."""
     return torch.cuda.get_device_properties(0).multi_processor_count == 256 and not hip_backend.DEFAULT_OPTIONS
+
+
+def test_query_replays_the_recorded_launch_table():
+    """tests/golden/plan_table.npz - every launch key of cmdgen_query over a sweep of configs, engines, options and layouts, recorded from the
+    library before the launch planner (csrc/cmdgen_plan.h) replaced its rules - through Handle.query of this build; no kernel is launched.  And
+    the three *_mfmas_per_product keys answer on a handle that has a layout but no finalized weights."""
+    import plan_table_ref as pt
+    c = rs.EVAL_CASES[3]
+    h = hip_backend.Handle(rs.config_of(c).as_dict(), 0)
+    pb = rs.pockets_of(c)
+    h.set_layout(pb.num_nodes_phar, pb.size)
+    assert [h.query(r + '_mfmas_per_product') for r in ('msg', 'node', 'coord')] == [6, 1, 6] or not table_applies()
+    assert all(h.query(r + '_mfmas_per_product') in (1, 6) for r in ('msg', 'node', 'coord'))      # (the half forms need their packs)
+    h.load_state_dict(rs.state_dict_of(c))
+    assert resolved(h) == c.launch or not table_applies()                  # ... and the plan follows the weights
+    h.close()
+    t = pt.table()
+    if table_applies() and torch.cuda.get_device_properties(0).multi_processor_count == t['n_cus']:
+        got, want = pt.replay_on_gpu(), t['rows'][:, pt.N_IN:]
+        bad = np.flatnonzero((got != want).any(axis=1))
+        assert len(bad) == 0, [(pt.describe(t['rows'][i]), {k: (int(w), int(g)) for k, w, g in zip(pt.QUERY_KEYS, want[i], got[i]) if w != g}) for i in bad[:5]]
 
 
 def evaluate(h, inputs):

@@ -120,6 +120,129 @@ def test_half_scale_rule_equals_both_rules_it_replaced(tmp_path):
     assert int(r.stdout.split('checked')[1].split()[0]) > 2500
 
 
+def test_planner_reproduces_the_recorded_launch_table():
+    """tests/plan_check.cpp: the launch planner (csrc/cmdgen_plan.h) on the host against every row of tests/golden/plan_table.npz - the launch keys
+    cmdgen_query gave BEFORE the planner existed, for a sweep of configs, engines, options and layouts, with n_cus taken from the table."""
+    import plan_table_ref as pt
+    t = pt.table()
+    assert len(t['rows']) > 4000 and t['rows'].shape[1] == pt.N_IN + len(pt.QUERY_KEYS)
+    got = pt.run_planner(t['layouts'], pt.table_plans())
+    want = t['rows'][:, pt.N_IN:]
+    bad = np.flatnonzero((got != want).any(axis=1))
+    assert len(bad) == 0, [(pt.describe(t['rows'][i]), {k: (int(w), int(g)) for k, w, g in zip(pt.QUERY_KEYS, want[i], got[i]) if w != g}) for i in bad[:5]]
+
+
+def test_planner_names_the_kernels_the_former_launchers_took():
+    """The query keys are not what the launchers switch on: the kernel of each role, its engine and the 128-row kernels' grid are.  Before the
+    planner, each launcher tested the launch keys itself and fell through to the next; those guards, applied here to the RECORDED keys of every
+    row of the table (weights uploaded, sampler), must name the kernel the planner names."""
+    import plan_table_ref as pt
+    t = pt.table()
+    plans = pt.table_plans()
+    got = pt.run_planner(t['layouts'], plans, extra=True)[:, len(pt.QUERY_KEYS):]
+    for row, p, g in zip(t['rows'], plans, got):
+        q = dict(zip(pt.QUERY_KEYS, (int(v) for v in row[pt.N_IN:])))
+        H, split, he = p['H'], q['gemm_split'], p['opts'].get('half_engine', 1)
+        half = he == 2 or (he == 1 and not p['no_cutoff'])
+        sp256 = H == 256 and split
+        eng256 = pt.ENG['half'] if half else pt.ENG['bf3']                       # (ws and wh exist for every uploaded matrix)
+
+        def edge_role(mt, e128, fullk, tiles):
+            if mt == 128 and sp256:
+                return e128, eng256
+            if q['edge_fullk'] and sp256 and mt == 32:
+                return fullk, eng256
+            return tiles, pt.ENG['bf3'] if split and mt >= 32 else pt.ENG['fp32']
+        msg = edge_role(q['edge_mt'], pt.MSG['e128'], pt.MSG['fullk32'], pt.MSG['tiles'])
+        coord = edge_role(q['coord_mt'], pt.COORD['e128'], pt.COORD['fullk32'], pt.COORD['tiles'])
+        if q['proj_in_coord']:
+            assert coord[0] == pt.COORD['fullk32']
+            coord = pt.COORD['fullk32_proj'], coord[1]
+        ws16 = (2 * H) % 128 == 0                                                 # node_mlp.0 takes 2H inputs
+        if q['node64'] and sp256:
+            n64 = q['node64']
+            node = (pt.NODE['node64d'] if n64 == 2 and half else pt.NODE['node64e'] if n64 == 8 and half else pt.NODE['node32p'] if n64 == 32
+                    else pt.NODE['node64']), eng256
+        elif H == 256 and q['node_mt'] == 16 and q['node16_split'] and q['node16w'] and ws16:
+            node = pt.NODE['node16w'], eng256
+        elif q['node_mt'] >= 32:
+            node = pt.NODE['tiles'], pt.ENG['bf3'] if split else pt.ENG['fp32']
+        else:
+            node = pt.NODE['tiles'], pt.ENG['bf3'] if q['node16_split'] and ws16 and H >= 128 else pt.ENG['fp32']
+        wgs = p['opts'].get('e128_wgs_per_cu', 2)
+        nph = t['layouts'][p['layout']][0]
+        embed = p['opts'].get('embed_mt', 16 if int(nph.sum()) / 16.0 <= 2.0 * p['n_cus'] and not p['joint'] else q['node_mt'])
+        if embed not in (16, 32, 64):
+            embed = q['node_mt']
+        want = dict(msg=msg[0], node=node[0], coord=coord[0], msg_eng=msg[1], node_eng=node[1], coord_eng=coord[1],
+                    e128_grid=(wgs if 1 <= wgs <= 4 else 2) * p['n_cus'], embed_mt=embed, write_embed=1,
+                    reads_frag=int(pt.MSG['tiles'] == msg[0] or pt.COORD['tiles'] == coord[0] or pt.NODE['tiles'] == node[0]), fwd_half=0, node_half=0)
+        assert dict(zip(pt.EXTRA_KEYS, (int(v) for v in g))) == want, (pt.describe(row), q)
+    # (no row of the table sets write_embed; make_launch read it as `opt_of(h, "write_embed", 1) != 0`)
+    few = [dict(p, opts=dict(p['opts'], write_embed=v)) for p in plans[:3] for v in (0, 1, 5)]
+    assert list(pt.run_planner(t['layouts'], few, extra=True)[:, len(pt.QUERY_KEYS) + pt.EXTRA_KEYS.index('write_embed')]) == [0, 1, 1] * 3
+
+
+def test_planner_training_mode_is_the_former_training_forwards_patches():
+    """cmdgen_train_forward used to patch the sampler's launch after the fact (train_half, train_node16, rows / grids from the real list lengths,
+    the half save forms) and to predict from its own copy of the launchers' guards whether a launch would read the fp32 fragment packs.  Those
+    rules, applied to the planner's sampler answer (pinned by the recorded table), against the planner's training mode."""
+    import plan_table_ref as pt
+    t = pt.table()
+    n_cus, cases = 256, []
+    for layout in (7, 63, 199):                                                                   # 8, 64 and 200 uniform C-alpha pockets
+        for H, split, opts in ((256, 1, {}), (256, 1, {'half_engine': 0}), (256, 0, {}), (128, 1, {})):
+            for extra in ({}, {'train_half': 0}, {'train_half': 2}, {'train_node16': 0}, {'edge_mt': 64}, {'edge_mt': 128}, {'edge_mt': 16, 'coord_mt': 128},
+                          {'edge_fullk': 0}, {'edge_wgs_per_cu': 1, 'edge_mt': 32}):
+                for packs in (7, 3, 1, 0):
+                    for E, Ec in ((100, 50), (34000, 9000), (300000, 70000)):
+                        cases.append(dict(H=H, L=5, S=1, joint=0, sin=0, no_cutoff=0, n_cus=n_cus, gemm_split=split, layout=layout, opts=dict(opts, **extra),
+                                          packs=packs, E=E, Ec=Ec))
+    sampler = pt.run_planner(t['layouts'], [dict(c, packs=1) for c in cases])
+    got = pt.run_planner(t['layouts'], [dict(c, training=1) for c in cases], extra=True)
+    keys = pt.QUERY_KEYS + pt.EXTRA_KEYS
+    seen = set()
+    for c, s, g in zip(cases, sampler, got):
+        q, g = dict(zip(pt.QUERY_KEYS, (int(v) for v in s))), dict(zip(keys, (int(v) for v in g)))
+        o, H, split = c['opts'], c['H'], c['gemm_split']
+        fwd_half = bool(split and H == 256 and q['half_engine'] and q['edge_fullk'] and c['packs'] & 2 and o.get('train_half', 1) != 0)
+        node_mt = 16 if fwd_half and o.get('train_node16', 1) != 0 else q['node_mt']
+        node_half = bool(fwd_half and node_mt == 16 and c['packs'] & 4 and o.get('train_half', 1) != 2)
+        rows = lambda n: 64 if n // 64 >= 4 * n_cus else 32 if n // 32 >= n_cus // 4 else 16
+        grid = lambda n, mt: min(max(int((n // mt + 1) * 1.25) + 8, n_cus // 4), (2 if mt >= 64 else 4) * n_cus)
+        want = {}
+        for role, mt_key, grid_key, n in (('msg', 'edge_mt', 'edge_grid', c['E']), ('coord', 'coord_mt', 'coord_grid', c['Ec'])):
+            mt, gr = q[mt_key], q[grid_key]
+            if mt_key not in o or mt == 128:
+                mt = rows(n); gr = grid(n, mt)
+            if fwd_half:
+                mt, gr = 32, grid(n, 32)
+            sp = split and c['packs'] & 1 and H == 256 and mt >= 32
+            want.update({mt_key: mt, grid_key: gr, role: 1 if fwd_half else 0, role + '_eng': pt.ENG['half'] if fwd_half else pt.ENG['bf3'] if sp else pt.ENG['fp32']})
+        node16w = H == 256 and node_mt == 16 and node_half
+        want.update(node_mt=node_mt, node=pt.NODE['node16w'] if node16w else pt.NODE['tiles'], node_eng=pt.ENG['half'] if node16w else pt.ENG['fp32'],
+                    fwd_half=int(fwd_half), node_half=int(node_half), reads_frag=int(not (fwd_half and node16w)), dead_skip=0, node64=0, proj_in_coord=0)
+        assert {k: g[k] for k in want} == want, (c, q)
+        seen.add((want['fwd_half'], want['node_half'], want['reads_frag'], want['edge_mt']))
+    assert {s[:3] for s in seen} == {(1, 1, 0), (1, 0, 1), (0, 0, 1)} and {s[3] for s in seen} == {16, 32, 64}       # the cases reach every outcome
+
+
+def test_planner_header_is_plain_cpp():
+    """cmdgen_plan.h takes no HIP header and no cmdgen_handle (plan_check.cpp compiles it with -x c++), and before cmdgen_finalize_weights - no
+    packs - every role resolves to a kernel that needs none."""
+    import plan_table_ref as pt
+    src = open(os.path.join(ROOT, 'cmdgen_amd', 'csrc', 'cmdgen_plan.h')).read()
+    assert all(inc.startswith('<') and 'hip' not in inc for inc in re.findall(r'#include\s+(\S+)', src)) and 'cmdgen_handle' not in src
+    t = pt.table()
+    plans = [dict(p, packs=0) for p in pt.table_plans()[:320]]                  # uniform C-alpha layouts of 1 .. 320 pockets, the default engine
+    got = pt.run_planner(t['layouts'], plans)
+    k = {key: i for i, key in enumerate(pt.QUERY_KEYS)}
+    assert (got[:, k['proj_in_coord']] == 0).all()
+    for role in ('msg', 'node', 'coord'):
+        assert np.isin(got[:, k[role + '_mfmas_per_product']], (1, 6)).all()                          # (the half forms need their packs)
+    assert (got[:, k['node_mfmas_per_product']] == np.where(got[:, k['node_mt']] >= 32, 6, 1)).all()
+
+
 def test_product_fails_loudly_without_gpu():
     if torch.cuda.is_available():
         pytest.skip('GPU present')

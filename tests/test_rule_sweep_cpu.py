@@ -22,6 +22,23 @@ def test_case_table_is_consistent():
         assert len({c.launch for c in rs.ENGINE_CASES if c.engine == eng}) >= 4
 
 
+def test_planner_resolves_the_case_tables_launch_at_256_cus():
+    """Every case's expected launch is what the launch planner (csrc/cmdgen_plan.h, on the host through tests/plan_check.cpp) resolves for its
+    layout, engine and model on 256 CUs with no option set - the table test_hip_rule_sweep.py asserts on such a device."""
+    import plan_table_ref as pt
+    cases = rs.ONE_EVALUATION + rs.CHAIN_CASES
+    layouts, plans = [], []
+    for c in cases:
+        cfg, pb = rs.config_of(c), rs.pockets_of(c)
+        layouts.append((pb.num_nodes_phar, pb.size))
+        plans.append(dict(H=cfg.hidden_nf, L=cfg.n_layers, S=cfg.inv_sublayers, joint=int(c.kind == 'joint'), sin=0, no_cutoff=0, n_cus=256,
+                          gemm_split=int(c.engine != 'fp32'), layout=len(layouts) - 1, opts={'half_engine': 0} if c.engine == 'bf3' else {}))
+    got = pt.run_planner(layouts, plans)
+    cols = [pt.QUERY_KEYS.index(k) for k in rs.LAUNCH_KEYS]
+    for c, g in zip(cases, got):
+        assert tuple(int(v) for v in g[cols]) == c.launch, (rs.case_id(c), tuple(g[cols]), c.launch)
+
+
 def test_inside_geometry_is_the_property_tests_input_builder():
     from test_hip_properties import eval_inputs
     case = rs.EVAL_CASES[1]
