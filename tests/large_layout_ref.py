@@ -1,0 +1,432 @@
+"""The full-atom layout of test_large_layout_cpu.py / test_hip_large_layout.py: its builder, the committed seeds of every case, the
+margins of a case recomputed from the oracle's own run, and the searches that found the seeds (test infrastructure, CPU only).
+
+One mixed batch of five samples (pocket nodes, phar points), SAMPLES below: 128 and 129 nodes (the two sides of the planner's and the
+per-sample step kernels' max_n > 128), a ragged full-atom pocket of 250-450 atoms with 15 points (the shipped shape), 300 + 70 (more
+than 64 phar rows, the highest degree) and 257 + 1 (a second trip of the 256-row loops; a single point, which is its own centre of
+mass).  Every sample is a single-sample make_pockets(1, 'full-atom', ...) call at first_index + its position, so a sample alone is the
+same sample as in the batch.  Phar points as test_hip_train.case_inputs places them: centre of mass + normal * spread.
+
+Margins.  The radius graph is a hard threshold; at 300-400 nodes a sample has 45-80 thousand pairs and about one per sample and
+evaluation lies within 1e-4 A of the cutoff, so the CA tests' "margin > 2e-3" searches cannot succeed here.  Instead:
+  single evaluations   first_index chosen so that EVERY sample's margin >= rule_sweep_ref.MARGIN (1e-4); no sample is left out
+  score                an entry (level, sample) inside test_score_cpu.BAND (1e-4) is left out, at most 2 % of a case; the committed
+                       noise seed leaves none out on the oracle
+  chains               a sample is left out from the first evaluation at which one of its pairs is within test_hip_parity_r3.BAND (2e-5 A)
+                       of the cutoff; at most CHAIN_CAP of the samples (one of five); the committed seeds leave none out on the oracle
+The constants below are what the searches at the bottom returned; a test never trusts them: it recomputes the margins with
+RecordedEdges round the oracle's run (test_large_layout_cpu.py asserts the conditions, the GPU tests derive `kept` from them)."""
+import numpy as np
+import torch
+
+import score_ref
+import cond_inpaint_ref
+import edit_ref
+from helpers import JointNoiseTape
+from oracle import ref_cpu
+from cmdgen_amd.synthetic import ModelConfig, PocketBatch, make_pockets, make_state_dict
+from rule_sweep_ref import MARGIN, CHAIN_CAP, CUTOFF
+from test_score_cpu import BAND as SCORE_BAND
+from test_hip_parity_r3 import BAND as CHAIN_BAND
+
+# (pocket nodes, phar points); None: ragged full-atom, 250-450 atoms
+SAMPLES = [(119, 9), (120, 9), (None, 15), (300, 70), (257, 1)]
+B = len(SAMPLES)
+SPREAD = 3.0
+T = 100
+SCORE_CAP = 0.02
+MAX_LEFT_OUT = int(CHAIN_CAP * B)          # one of five
+
+# ----------------------------------------------------------------------------- the committed seeds (searches at the bottom)
+FIRST_INDEX = 5052         # single evaluations: every sample's margin >= MARGIN at spread 3.0
+SEEDS = {                  # case -> noise seed; the layout of every case is build(FIRST_INDEX)
+    'loss_train': 1, 'loss_eval': 1, 'joint_loss_train': 0, 'joint_loss_eval': 16,
+    'score': 19, 'inpaint': 0, 'edit': 3, 'joint_sample': 0, 'joint_inpaint': 161,
+    # the library's own Philox draws (batch independence of the score): chosen on the device, where the draws are made - the first seed
+    # whose draws leave no entry inside the band on the CPU model; test_hip_large_layout.py recomputes the margins
+    'score_device': 11,
+}
+SCORE_K = 5
+INPAINT = dict(K=4, r=2, j=1)
+EDIT = dict(K=6, start=3, r=2, j=1)
+JOINT_SAMPLE_K = 4
+JOINT_INPAINT = dict(K=4, r=2, j=1)
+
+# a size histogram that covers this layout's sizes (helpers.HIST stops at 25 x 65): same law, 0 .. 79 phar points x 0 .. 459 pocket nodes
+HIST = np.zeros((80, 460), dtype=np.float64)
+for _i in range(1, 80):
+    for _j in range(100, 460):
+        HIST[_i, _j] = 1 + ((_i * 7 + _j * 3) % 11)
+
+
+# ----------------------------------------------------------------------------- the layout
+def build(first_index=FIRST_INDEX, samples=None, spread=SPREAD):
+    """-> dict(pb, pm, phar_x, phar_one_hot, ids, samples): the batch of SAMPLES (or of the positions `samples` of it, each the same
+    sample as in the whole batch: pockets and phar points are drawn per global index)."""
+    samples = list(range(B)) if samples is None else list(samples)
+    xs, hs, sizes, nph, px, poh = [], [], [], [], [], []
+    for k in samples:
+        npk, nl = SAMPLES[k]
+        one = (make_pockets(1, 'full-atom', ragged=True, first_index=first_index + k) if npk is None else
+               make_pockets(1, 'full-atom', n_pocket_nodes=npk, n_phar=nl, first_index=first_index + k))
+        rng = np.random.Generator(np.random.PCG64(2_000_003 + first_index + k))
+        com = one.x.mean(0)
+        px.append((com[None] + rng.normal(size=(nl, 3)) * spread).astype(np.float32))
+        poh.append(np.eye(8, dtype=np.float32)[rng.integers(0, 8, size=nl)])
+        xs.append(one.x); hs.append(one.one_hot); sizes.append(int(one.size[0])); nph.append(nl)
+    size, nl = np.asarray(sizes, dtype=np.int64), np.asarray(nph, dtype=np.int64)
+    n = len(samples)
+    pb = PocketBatch(x=np.concatenate(xs), one_hot=np.concatenate(hs), size=size, mask=np.repeat(np.arange(n, dtype=np.int64), size),
+                     num_nodes_phar=nl, pocket_index=np.asarray([first_index + k for k in samples], dtype=np.int64))
+    return dict(pb=pb, pm=np.repeat(np.arange(n, dtype=np.int64), nl), phar_x=np.concatenate(px), phar_one_hot=np.concatenate(poh),
+                ids=pb.pocket_index, samples=samples)
+
+
+def rows_of(lay, sample):
+    """(phar rows, pocket rows) of one sample as slices"""
+    a = np.concatenate([[0], np.cumsum(lay['pb'].num_nodes_phar)])
+    b = np.concatenate([[0], np.cumsum(lay['pb'].size)])
+    return slice(int(a[sample]), int(a[sample + 1])), slice(int(b[sample]), int(b[sample + 1]))
+
+
+def dicts(lay):
+    """(phar, pocket) torch dicts as the oracle and the CPU models take them"""
+    pb = lay['pb']
+    phar = {'x': torch.from_numpy(lay['phar_x'].copy()), 'one_hot': torch.from_numpy(lay['phar_one_hot'].copy()),
+            'size': torch.from_numpy(pb.num_nodes_phar.copy()), 'mask': torch.from_numpy(lay['pm'].copy())}
+    pocket = {'x': torch.from_numpy(pb.x.copy()), 'one_hot': torch.from_numpy(pb.one_hot.copy()),
+              'size': torch.from_numpy(pb.size.copy()), 'mask': torch.from_numpy(pb.mask.copy())}
+    return phar, pocket
+
+
+def eval_inputs(lay, cfg, seed=1):
+    """(xh_phar, xh_pocket, t [B, 1]) of one evaluation on the layout, as test_hip_train.case_inputs forms them"""
+    pb = lay['pb']
+    rng = np.random.Generator(np.random.PCG64(seed))
+    xh_phar = np.concatenate([lay['phar_x'], rng.normal(size=(len(lay['pm']), cfg.phar_nf)).astype(np.float32)], 1)
+    xh_pocket = np.concatenate([pb.x, pb.one_hot / cfg.norm_values[1]], 1).astype(np.float32)
+    t = rng.uniform(size=(len(pb.size), 1)).astype(np.float32)
+    return xh_phar, xh_pocket, t
+
+
+def sample_margins(x, mask, cutoff=CUTOFF):
+    """[B] float64: per sample the smallest | ||x_i - x_j|| - cutoff | over its pairs (synthetic.min_cutoff_margin, per sample);
+    x the rows of all nodes, mask their sample."""
+    x, mask = np.asarray(x, dtype=np.float64), np.asarray(mask)
+    out = []
+    for b in range(int(mask.max()) + 1):
+        p = x[mask == b]
+        d = np.sqrt(((p[:, None, :] - p[None, :, :]) ** 2).sum(-1))
+        g = np.abs(d[np.triu_indices(len(p), k=1)] - cutoff)
+        out.append(g.min() if len(g) else np.inf)
+    return np.asarray(out)
+
+
+def max_degree(x, mask, cutoff=CUTOFF):
+    """the most neighbours one node has inside the cutoff"""
+    x, mask = np.asarray(x, dtype=np.float64), np.asarray(mask)
+    worst = 0
+    for b in range(int(mask.max()) + 1):
+        p = x[mask == b]
+        d = np.sqrt(((p[:, None, :] - p[None, :, :]) ** 2).sum(-1))
+        worst = max(worst, int((d < cutoff).sum(1).max()) - 1)
+    return worst
+
+
+def layout_margins(lay):
+    """[B]: the margins of the layout's own positions (the single evaluations run on them)"""
+    return sample_margins(np.concatenate([lay['phar_x'], lay['pb'].x]), np.concatenate([lay['pm'], lay['pb'].mask]))
+
+
+class RecordedEdges:
+    """with RecordedEdges() as rec: ... - every ref_cpu.get_edges call of the oracle inside leaves its per-sample margins in
+    rec.margins ([evaluations, B] from rec.array()): the margins of the oracle's own run, whatever formed the positions."""
+    def __enter__(self):
+        self.margins, self.orig = [], ref_cpu.get_edges
+
+        def rec(mask, x, cutoff):
+            self.margins.append(sample_margins(x.detach().numpy(), mask.numpy(), cutoff))
+            return self.orig(mask, x, cutoff)
+        ref_cpu.get_edges = rec
+        return self
+
+    def __exit__(self, *exc):
+        ref_cpu.get_edges = self.orig
+
+    def array(self):
+        return np.stack(self.margins)
+
+
+def kept_from(margins, band=CHAIN_BAND):
+    """[B] bool: the samples no evaluation of a chain brings within `band` of the cutoff ([evaluations, B] margins)"""
+    return np.asarray(margins).min(axis=0) >= band
+
+
+# ----------------------------------------------------------------------------- models
+def config(H=64, L=2, joint=False, **kw):
+    return ModelConfig(hidden_nf=H, n_layers=L, residue_nf=11, timesteps=T, update_pocket_coords=joint, **kw)
+
+
+_SD, _P, _ORACLE = {}, {}, {}
+
+
+def state_dict_of(cfg, seed=0):
+    key = (tuple(sorted((k, str(v)) for k, v in cfg.as_dict().items())), seed)
+    if key not in _SD:
+        _SD[key] = make_state_dict(cfg, seed=seed, coord_gain=1.0)
+        _P[key] = ref_cpu.to_torch_params(_SD[key])
+    return _SD[key]
+
+
+def params_of(cfg, seed=0):
+    state_dict_of(cfg, seed)
+    return _P[(tuple(sorted((k, str(v)) for k, v in cfg.as_dict().items())), seed)]
+
+
+def _threads():
+    torch.set_num_threads(min(16, max(1, torch.get_num_threads())))
+
+
+def _cached(key, fn):
+    if key not in _ORACLE:
+        _threads()
+        _ORACLE[key] = fn()
+    return _ORACLE[key]
+
+
+# ----------------------------------------------------------------------------- the cases: inputs and the oracle's run, once per process
+def loss_draws(lay, mode, seed):
+    """(t_int [B, 1] with a 0 and a T in it, [eps_t, eps_0]) of the conditional loss cases"""
+    g = torch.Generator().manual_seed(1000 + seed)
+    t_int = torch.randint(1, T, (B, 1), generator=g).float()
+    t_int[1], t_int[3] = 0.0, float(T)
+    nl = len(lay['pm'])
+    return t_int, [torch.randn((nl, 11), generator=g), torch.randn((nl, 11), generator=g)]
+
+
+def oracle_loss(mode, seed=None, first_index=FIRST_INDEX):
+    """dict(lay, t_int, eps, terms, nll, margins [evaluations, B]) of ref_cpu.ddpm_forward on the layout; mode 'train' | 'eval'"""
+    seed = SEEDS['loss_' + mode] if seed is None else seed
+
+    def run():
+        cfg, lay = config(), build(first_index)
+        phar, pocket = dicts(lay)
+        t_int, eps = loss_draws(lay, mode, seed)
+        with torch.no_grad(), RecordedEdges() as rec:
+            terms = ref_cpu.ddpm_forward(params_of(cfg), cfg.as_dict(), phar, pocket, t_int, eps, mode == 'train', HIST)
+            nll = ref_cpu.nll_from_terms(terms, cfg.as_dict(), phar['size'], pocket['size'], mode == 'train')
+        return dict(cfg=cfg, lay=lay, t_int=t_int, eps=eps, terms=terms, nll=nll, margins=rec.array())
+    return _cached(('loss', mode, seed, first_index), run)
+
+
+def joint_loss_draws(lay, mode, seed):
+    """(t_int, packed combined draws [2, Nl * 11 + Np * 14]) of the joint loss cases (helpers.JointNoiseTape's packing)"""
+    g = torch.Generator().manual_seed(2000 + seed)
+    t_int = torch.randint(1, T, (B, 1), generator=g).float()
+    t_int[1], t_int[3] = 0.0, float(T)
+    return t_int, torch.randn((2, len(lay['pm']) * 11 + len(lay['pb'].mask) * 14), generator=g).numpy()
+
+
+def oracle_joint_loss(mode, seed=None, first_index=FIRST_INDEX):
+    seed = SEEDS['joint_loss_' + mode] if seed is None else seed
+
+    def run():
+        cfg, lay = config(joint=True), build(first_index)
+        phar, pocket = dicts(lay)
+        t_int, noise = joint_loss_draws(lay, mode, seed)
+        tape = JointNoiseTape(noise, len(lay['pm']), len(lay['pb'].mask), R=11)
+        with torch.no_grad(), RecordedEdges() as rec:
+            terms = ref_cpu.joint_ddpm_forward(params_of(cfg), cfg.as_dict(), phar, pocket, t_int, tape, mode == 'train', HIST)
+        return dict(cfg=cfg, lay=lay, t_int=t_int, noise=noise, terms=terms, margins=rec.array())
+    return _cached(('joint_loss', mode, seed, first_index), run)
+
+
+def oracle_score(seed=None, first_index=FIRST_INDEX):
+    """dict(lay, levels, noise [K + 1, Nl, 11], raw (score_ref.score_levels), margins [K + 1, B])"""
+    seed = SEEDS['score'] if seed is None else seed
+
+    def run():
+        cfg, lay = config(), build(first_index)
+        phar, pocket = dicts(lay)
+        levels = score_ref.level_list(T, SCORE_K)
+        noise = torch.randn((SCORE_K + 1, len(lay['pm']), 11), generator=torch.Generator().manual_seed(3000 + seed)).numpy()
+        with torch.no_grad(), RecordedEdges() as rec:
+            raw = score_ref.score_levels(params_of(cfg), cfg.as_dict(), phar, pocket, levels, noise)
+        return dict(cfg=cfg, lay=lay, levels=levels, noise=noise, raw=raw, margins=rec.array())
+    return _cached(('score', seed, first_index), run)
+
+
+def _phar_rows_by_position(lay):
+    """{position in SAMPLES: the phar rows of that sample in `lay`} - a layout of some of the samples marks them as the whole batch does"""
+    return {k: rows_of(lay, i)[0] for i, k in enumerate(lay['samples'])}
+
+
+def fixed_rows(lay):
+    """phar_fixed [Nl] of the inpainting case: none of sample 0, all of sample 1, every other row of sample 2, the first 65 of sample
+    3's 70 (the fixed / free split falls across a wavefront), all of sample 4 (its single point)."""
+    f = np.zeros(len(lay['pm']), dtype=np.float32)
+    for k, s in _phar_rows_by_position(lay).items():
+        if k in (1, 4):
+            f[s] = 1.0
+        elif k == 2:
+            f[s.start:s.stop:2] = 1.0
+        elif k == 3:
+            f[s.start:s.start + 65] = 1.0
+    return f
+
+
+def edit_masks(lay):
+    """(fix_x, fix_h) [Nl] of the edit case, mixed: sample 0 holds types only, sample 1 positions only, sample 2 nothing (no mark),
+    sample 3 positions of its first 65 rows and types of its last 40 (the two overlap on rows 30 .. 64), sample 4 both."""
+    fx, fh = np.zeros(len(lay['pm']), dtype=np.float32), np.zeros(len(lay['pm']), dtype=np.float32)
+    for k, s in _phar_rows_by_position(lay).items():
+        if k == 0:
+            fh[s] = 1.0
+        elif k == 1:
+            fx[s] = 1.0
+        elif k == 3:
+            fx[s.start:s.start + 65] = 1.0
+            fh[s.start + 30:s.stop] = 1.0
+        elif k == 4:
+            fx[s] = 1.0; fh[s] = 1.0
+    return fx, fh
+
+
+def _chain_noise(n_draws, nl, seed):
+    return torch.randn((n_draws, nl, 11), generator=torch.Generator().manual_seed(seed)).numpy()
+
+
+def oracle_inpaint(seed=None, first_index=FIRST_INDEX):
+    """dict(lay, fixed, noise, want (xh_phar, xh_pocket), z_steps, p_steps, margins [evaluations, B]) of cond_inpaint_ref.cond_inpaint"""
+    seed = SEEDS['inpaint'] if seed is None else seed
+
+    def run():
+        cfg, lay = config(), build(first_index)
+        phar, pocket = dicts(lay)
+        K, r, j = INPAINT['K'], INPAINT['r'], INPAINT['j']
+        n_steps, n_draws, _ = cond_inpaint_ref.inpaint_plan(r, j, K)
+        noise = _chain_noise(n_draws, len(lay['pm']), 4000 + seed)
+        tape = iter(torch.from_numpy(noise))
+        fixed = fixed_rows(lay)
+        with torch.no_grad(), RecordedEdges() as rec:
+            out = cond_inpaint_ref.cond_inpaint(params_of(cfg), cfg.as_dict(), phar, pocket, fixed, r, j, K, noise=lambda shape: next(tape),
+                                                return_steps=True)
+        assert len(rec.margins) == n_steps + 1
+        return dict(cfg=cfg, lay=lay, fixed=fixed, noise=noise, want=(out[0].numpy(), out[1].numpy()), z_steps=out[4].numpy(),
+                    p_steps=out[5].numpy(), margins=rec.array(), n_steps=n_steps)
+    return _cached(('inpaint', seed, first_index), run)
+
+
+def oracle_edit(seed=None, first_index=FIRST_INDEX):
+    seed = SEEDS['edit'] if seed is None else seed
+
+    def run():
+        cfg, lay = config(), build(first_index)
+        phar, pocket = dicts(lay)
+        K, start, r, j = EDIT['K'], EDIT['start'], EDIT['r'], EDIT['j']
+        n_steps, n_draws, _ = edit_ref.edit_plan(r, j, K, start)
+        noise = _chain_noise(n_draws, len(lay['pm']), 5000 + seed)
+        tape = iter(torch.from_numpy(noise))
+        fx, fh = edit_masks(lay)
+        with torch.no_grad(), RecordedEdges() as rec:
+            out = edit_ref.cond_edit(params_of(cfg), cfg.as_dict(), phar, pocket, fx, fh, start, r, j, K, noise=lambda shape: next(tape),
+                                     return_steps=True)
+        assert len(rec.margins) == n_steps + 1
+        return dict(cfg=cfg, lay=lay, fix_x=fx, fix_h=fh, noise=noise, want=(out[0].numpy(), out[1].numpy()), z_steps=out[4].numpy(),
+                    p_steps=out[5].numpy(), margins=rec.array(), n_steps=n_steps)
+    return _cached(('edit', seed, first_index), run)
+
+
+def joint_fixed(lay):
+    """(phar_fixed [Nl], pocket_fixed [Np]) of the joint inpainting case: the pocket known (as the driver fixes it), a third of the points"""
+    rng = np.random.Generator(np.random.PCG64(77))
+    fp = (rng.uniform(size=len(lay['pm'])) < 0.3).astype(np.float32)
+    fp[_phar_rows_by_position(lay)[4]] = 0.0          # the single point stays free
+    return fp, np.ones(len(lay['pb'].mask), dtype=np.float32)
+
+
+def oracle_joint(kind, seed=None, first_index=FIRST_INDEX):
+    """kind 'sample' (ref_cpu.joint_sample, K = 4) | 'inpaint' (ref_cpu.joint_inpaint, K = 4, r = 2, j = 1) on the joint model with
+    residue_nf = 11 -> dict(lay, noise [draws, Nl * 11 + Np * 14], want (xh_phar, xh_pocket), chain (the merge states, packed as the device
+    records them), margins [evaluations, B])"""
+    seed = SEEDS['joint_' + kind] if seed is None else seed
+
+    def run():
+        cfg, lay = config(joint=True), build(first_index)
+        pb = lay['pb']
+        phar, pocket = dicts(lay)
+        Nl, Np = len(lay['pm']), len(pb.mask)
+        if kind == 'sample':
+            K, r, j = JOINT_SAMPLE_K, 1, 1
+            n_steps, n_draws = K, K + 2
+        else:
+            K, r, j = JOINT_INPAINT['K'], JOINT_INPAINT['r'], JOINT_INPAINT['j']
+            sched = ref_cpu.get_repaint_schedule(r, j, K)
+            n_steps = sum(sched)
+            n_draws = 2 + 2 * n_steps + len(sched) - 1
+        noise = torch.randn((n_draws, Nl * 11 + Np * 14), generator=torch.Generator().manual_seed(6000 + seed)).numpy()
+        tape = JointNoiseTape(noise, Nl, Np, R=11)
+        fp, fq = joint_fixed(lay)
+        with torch.no_grad(), RecordedEdges() as rec:
+            if kind == 'sample':
+                wp, wq, _, _, chain = ref_cpu.joint_sample(params_of(cfg), cfg.as_dict(), B, pb.num_nodes_phar, pb.size, timesteps=K, noise=tape,
+                                                           return_chain=True)
+                merges = list(range(K))
+            else:
+                wp, wq, _, _, chain = ref_cpu.joint_inpaint(params_of(cfg), cfg.as_dict(), phar, pocket, torch.from_numpy(fp), torch.from_numpy(fq),
+                                                            resamplings=r, jump_length=j, timesteps=K, noise=tape, return_chain=True)
+                # the oracle's chain lists the state after every merge and after every jump back; the device records merges
+                merges, pos = [], 0
+                for i, n in enumerate(sched):
+                    for jj in range(n):
+                        merges.append(pos); pos += 1
+                        if jj == n - 1 and i < len(sched) - 1:
+                            pos += 1
+        assert tape.i == n_draws and len(rec.margins) == n_steps + 1
+        states = np.stack([np.concatenate([chain[ci][0].numpy().ravel(), chain[ci][1].numpy().ravel()]) for ci in merges])
+        return dict(cfg=cfg, lay=lay, noise=noise, fixed=(fp, fq), want=(wp.numpy(), wq.numpy()), chain=states, margins=rec.array(),
+                    n_steps=n_steps, n_draws=n_draws, K=K, r=r, j=j)
+    return _cached(('joint', kind, seed, first_index), run)
+
+
+CHAIN_CASES = {'inpaint': oracle_inpaint, 'edit': oracle_edit, 'joint_sample': lambda **kw: oracle_joint('sample', **kw),
+               'joint_inpaint': lambda **kw: oracle_joint('inpaint', **kw)}
+SINGLE_CASES = {'loss_train': lambda **kw: oracle_loss('train', **kw), 'loss_eval': lambda **kw: oracle_loss('eval', **kw),
+                'joint_loss_train': lambda **kw: oracle_joint_loss('train', **kw), 'joint_loss_eval': lambda **kw: oracle_joint_loss('eval', **kw)}
+
+
+def case_condition(name, margins):
+    """True where the oracle's margins of a committed case meet its condition of "Margins" above (nothing left out)"""
+    m = np.asarray(margins)
+    if name in SINGLE_CASES:
+        return bool((m >= MARGIN).all())
+    if name == 'score':
+        return bool((m >= SCORE_BAND).all())
+    return bool(kept_from(m).all())
+
+
+# ----------------------------------------------------------------------------- the searches that chose the constants
+def search_first_index(start=5048, tries=200):
+    """the first first_index from `start` whose layout keeps every sample's margin >= MARGIN"""
+    for f in range(start, start + tries):
+        if (layout_margins(build(f)) >= MARGIN).all():
+            return f
+    raise RuntimeError('no first_index found')
+
+
+def search_seed(name, tries=200):
+    """the first noise seed of a case whose oracle run meets case_condition"""
+    fn = {**CHAIN_CASES, **SINGLE_CASES, 'score': oracle_score}[name]
+    for s in range(tries):
+        res = fn(seed=s)
+        ok = case_condition(name, res['margins'])
+        for k in [k for k in _ORACLE if k[-2] == s and s != SEEDS.get(name)]:
+            del _ORACLE[k]
+        if ok:
+            return s
+    raise RuntimeError('no seed found for ' + name)
+
+
+if __name__ == '__main__':
+    print('FIRST_INDEX', search_first_index())
+    print({name: search_seed(name) for name in SEEDS if name != 'score_device'})
