@@ -197,6 +197,25 @@ extern "C" int cmdgen_finalize_weights(cmdgen_handle* h) {
         std::vector<float> t((size_t)H * d.dyn);
         for (int c = 0; c < H; ++c) for (int k = 0; k < d.dyn; ++k) t[(size_t)k * H + c] = (*v)[(size_t)c * d.dyn + k];
         rc = upload(h, t, &s.emb_wT); if (rc) return rc;
+        s.emf_pack = nullptr;
+        if (d.P == EMF_P && d.J == EMF_J && d.dyn == EMF_J + 1) {
+            // B operands of the full-path embedding tile's two MFMA products (embed_body, option embed_mfma), v_mfma_f32_16x16x4_f32 with k ASCENDING: step s
+            // of n-tile nt pairs lane l with W[16 nt + l % 16][4 s + l / 16] (WFrag<16, 4> pairs step j with k = 16 kb + 4 g + j, a re-association of the dot
+            // product; here the chain must be the scalar form's).  A lane's steps lie behind one another: encoder layer 2, 2 n-tiles x 4 steps, then the
+            // embedding, 16 n-tiles x EMF_KE steps (k >= dyn: zero) in EMF_KE_LD floats - 16-byte loads.
+            const std::vector<float>* we = v;                       // (both sizes checked by GET)
+            GET(dy + "phar_encoder.2.weight", d.J * 2 * d.P);
+            const std::vector<float>* w2 = v;
+            std::vector<float> pack((size_t)EMF_J * 2 * EMF_P + (size_t)(H / 16) * 64 * EMF_KE_LD, 0.f);
+            for (int nt = 0; nt < EMF_J / 16; ++nt) for (int lane = 0; lane < 64; ++lane) for (int st = 0; st < 2 * EMF_P / 4; ++st)
+                pack[(size_t)(nt * 64 + lane) * (2 * EMF_P / 4) + st] = (*w2)[(size_t)(16 * nt + lane % 16) * 2 * EMF_P + 4 * st + lane / 16];
+            float* pe = pack.data() + EMF_J * 2 * EMF_P;
+            for (int nt = 0; nt < H / 16; ++nt) for (int lane = 0; lane < 64; ++lane) for (int st = 0; st < EMF_KE; ++st) {
+                const int k = 4 * st + lane / 16;
+                pe[(size_t)(nt * 64 + lane) * EMF_KE_LD + st] = k < d.dyn ? (*we)[(size_t)(16 * nt + lane % 16) * d.dyn + k] : 0.f;
+            }
+            rc = upload(h, pack, &s.emf_pack); if (rc) return rc;
+        }
         GET(dy + "egnn.embedding.bias", H); UP(s.emb_b);
     }
     {   // embedding_out [dyn][H] -> transposed [H][dyn]
@@ -292,6 +311,7 @@ PlanInput plan_input(const cmdgen_handle* h) {
     in.opts = &h->opts;
     if (!h->layers.empty()) {           // upload_pack's rule (the [2H][H] first-layer stacks and the square layers take H inputs, node_mlp.0 takes 2H)
         in.W2 = in.W7 = in.Wpq_e = PlanPacks::of_uploaded(d.H); in.W3 = PlanPacks::of_uploaded(2 * d.H);
+        in.embed_pack = h->small.emf_pack != nullptr;
     }
     return in;
 }
@@ -474,7 +494,7 @@ EvalLaunch make_launch(cmdgen_handle* h) {
 // ---------------------------------------------------------------------------------
 static const char* const kOptionKeys[] = {
     "node_mt", "edge_mt", "coord_mt", "embed_mt", "edge_wgs_per_cu", "coord_wgs_per_cu", "e128_wgs_per_cu", "e128_fused", "half_engine", "edge_fullk", "node64", "node16_split", "node16w",
-    "proj_in_coord", "dead_skip", "write_embed", "graph_steps",
+    "proj_in_coord", "embed_mfma", "dead_skip", "write_embed", "graph_steps",
     "wgrad_split", "wgrad_tile", "wgrad_split_wgs128", "wgrad_split_wgs64", "wgrad_wgs", "dgrad_mt", "dgrad_tail", "wgrad_stream", "train_half", "wgrad_silu", "train_node16", "wgrad_k128"};
 
 static void drop_graphs(cmdgen_handle* h) {

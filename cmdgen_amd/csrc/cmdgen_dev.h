@@ -62,7 +62,15 @@ struct SmallW {                 // encoders / decoders / embeddings, plain [out]
     const float *embo_wT, *embo_b;                  // egnn.embedding_out, stored transposed [H][J+1]
     const float *enc_pack;                          // the eight encoder tensors (pe0_w, pe0_b, pe2_w, pe2_b, re0_w, re0_b, re2_w, re2_b)
                                                     // back to back in one buffer (k_embed copies them to LDS); null in training
+    const float *emf_pack;                          // pe2_w and the embedding weight as k-ascending 16x4 MFMA B operands (cmdgen_finalize_weights);
+                                                    // null in training and at other sizes than EMF_P / EMF_J
 };
+// the sizes the MFMA form of the full-path embedding tile is written for (the shipped model's): phar_nf, joint_nf; k-steps of the embedding
+// (joint_nf + 1 padded to a multiple of 4) and a lane's stride in the pack
+#define EMF_P 8
+#define EMF_J 32
+#define EMF_KE 9
+#define EMF_KE_LD 12
 
 struct Dims {
     int P, R, J, H, L;          // phar_nf, residue_nf, joint_nf, hidden_nf, n_layers

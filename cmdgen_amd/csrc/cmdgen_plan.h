@@ -34,6 +34,8 @@ struct PlanInput {
     // training forward (cmdgen_train_forward): the list lengths are known, the packs above are what the step can re-pack
     bool training = false;
     int E = 0, Ec = 0;
+    // the k-ascending 16x4 packs of encoder layer 2 and the embedding exist (SmallW::emf_pack: phar_nf 8, joint_nf 32, the time column)
+    bool embed_pack = false;
 
     int64_t opt(const char* key, int64_t dflt) const { if (!opts) return dflt; auto it = opts->find(key); return it == opts->end() ? dflt : it->second; }
     bool opt_set(const char* key) const { return opts && opts->find(key) != opts->end(); }
@@ -49,6 +51,7 @@ struct LaunchPlan {
     int dead_skip = 0, write_embed = 1;
     // what cmdgen_query reports beside the above
     int gemm_split = 1, half_engine = 0, node16_split = 0, node64 = 0, node16w = 1, edge_fullk = 0, proj_in_coord = 0;
+    int embed_mfma = 0;                                  // full-path 16-row embedding tiles of phar rows on the fp32 matrix instruction (embed_body)
     // training forward
     bool fwd_half = false, node_half = false;            // the two edge kernels / the node kernel run their half save form
     bool reads_frag = false;                             // a tile launch reads the fp32 fragment packs (the generic k_edge_msg / k_node / k_edge_coord forms)
@@ -190,6 +193,11 @@ inline LaunchPlan make_plan(const PlanInput& in) {
         p.embed_mt = (int)in.opt("embed_mt", (((double)in.Nl / 16.0 <= 2.0 * n_cus && !in.joint) ? 16 : node_mt));
         if (p.embed_mt != 16 && p.embed_mt != 32 && p.embed_mt != 64) p.embed_mt = node_mt;
     }
+    // the full-path 16-row tile of phar rows with encoder layer 2 and the embedding as v_mfma_f32_16x16x4_f32 chains (k ascending from the bias: the
+    // scalar form's bits) and every operand requested at kernel start: H = 256, a 16-row tile (k_write_embed's pairs inside a chain, k_embed<256, 16>),
+    // never the training forward.  Option "embed_mfma": 0 never, 1 wherever that holds, unset: where it measured faster in every run - from 30 full-path
+    // tiles (32, 64 and 256 C-alpha pockets of 15 points; at 20 pockets of 3 points, four tiles, the rates overlap: profiles/phar_tiles_ab.txt).
+    p.embed_mfma = H == 256 && in.embed_pack && !in.training && (p.embed_mt == 16 || node_mt == 16) && in.opt("embed_mfma", in.Nl >= 30 * 16 ? 1 : 0) != 0 ? 1 : 0;
     // (the node kernel avoids its 64-row register-split tiles on the split engine: 87 vs 132 us at B=256, profiles/r02_o_tile_sweep_split.txt)
     if (split && node_mt == 64 && !in.opt_set("node_mt")) node_mt = 32;
     p.node_mt = node_mt; p.edge_mt = edge_mt; p.coord_mt = coord_mt;
@@ -264,6 +272,7 @@ inline bool plan_query(const LaunchPlan& p, const char* key, int64_t* value) {
         {"node_mt", p.node_mt}, {"edge_mt", p.edge_mt}, {"coord_mt", p.coord_mt}, {"edge_grid", p.edge_grid}, {"coord_grid", p.coord_grid},
         {"e128_fused", p.e128_fused}, {"gemm_split", p.gemm_split}, {"half_engine", p.half_engine}, {"node16_split", p.node16_split},
         {"node64", p.node64}, {"node16w", p.node16w}, {"proj_in_coord", p.proj_in_coord}, {"edge_fullk", p.edge_fullk}, {"dead_skip", p.dead_skip},
+        {"embed_mfma", p.embed_mfma},
         {"msg_mfmas_per_product", plan_mfmas_per_product(p.msg_eng)}, {"node_mfmas_per_product", plan_mfmas_per_product(p.node_eng)},
         {"coord_mfmas_per_product", plan_mfmas_per_product(p.coord_eng)}};
     for (const auto& k : keys) if (strcmp(k.key, key) == 0) { *value = k.v; return true; }

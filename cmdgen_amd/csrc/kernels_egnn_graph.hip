@@ -266,7 +266,7 @@ __device__ __forceinline__ void embed_body(const Layout& lay, const Work& w, con
                                            const float* __restrict__ xh_pocket,
                                            const float* __restrict__ t_arr,
                                            const float4* __restrict__ coef, const ChainState* chain, const TrainSave& sv,
-                                           const PocketCache& pc, const int blk, const int part = 2) {
+                                           const PocketCache& pc, const int blk, const int part = 2, const int emf = 0) {
     // part: 2 = the whole tile; 0 / 1 = one workgroup of a PAIR that shares a full-path tile inside a chain: both run the
     // encoders and the embedding (cheap), 0 writes h and projects P, 1 projects Q - the two 16-row projection passes were 40 %
     // of the tile's critical path when one workgroup ran them back to back (profiles/r02_b_step_fusion.txt, cycle stamps)
@@ -311,135 +311,219 @@ __device__ __forceinline__ void embed_body(const Layout& lay, const Work& w, con
     G::prefetch(f0, carry);
     const ColVec<MT> b1v = col_load<MT>(lw0.b1, tid >> 6);       // needed by the projection's epilogue four phases later
     const float t_chain = t_arr ? 0.f : coef[chain->step].w;     // two dependent loads: issued now, needed three phases later
-    // The eight encoder tensors (2.8k floats at the shipped sizes) are copied into LDS first, sixteen loads per thread in
-    // flight at a time: the FMA loops below then read them at LDS latency.  Read from global inside those loops they
-    // cost one dependent L2 round trip per unrolled batch (3 passes x up to 10 batches - most of this kernel's time).
-    extern __shared__ float s_enc[];
-    const int seg_n[8] = {2 * d.P * d.P, 2 * d.P, d.J * 2 * d.P, d.J, 2 * d.R * d.R, 2 * d.R, d.J * 2 * d.R, d.J};
-    const float* const seg_p[8] = {sw.pe0_w, sw.pe0_b, sw.pe2_w, sw.pe2_b, sw.re0_w, sw.re0_b, sw.re2_w, sw.re2_b};
-    int seg_o[9];
-    seg_o[0] = 0;
+    // The MFMA form of a full-path tile (LaunchPlan::embed_mfma; H = 256, sixteen PHAR rows, the sampler): encoder layer 2 and the embedding are
+    // v_mfma_f32_16x16x4_f32 chains - C starts from the bias and k ascends, the fmaf chain of the form below bit for bit - instead of one output
+    // per thread fed by broadcast LDS reads (528 ds_read_b32 + 528 FMAs per thread in the embedding alone), and every operand is requested HERE,
+    // in registers, beside the projection's first fragments: one round trip where the form below stages the eight tensors into LDS, waits, and
+    // then reads them.  A tile that holds a pocket row (or ends the list) keeps the form below.
+    bool mf = false;
+    if constexpr (H == 256 && MT == 16) mf = emf != 0 && row0 + MT <= lay.Nl;
+    if (mf) {
+        if constexpr (H == 256 && MT == 16) {
+            const int lane = tid & 63, wv = tid >> 6, l16 = lane & 15, g = lane >> 4;
+            const int r0 = tid >> 4, o0 = tid & 15;                      // layer 0: thread -> (row, output)
+            const float4 w0a = reinterpret_cast<const float4*>(sw.pe0_w)[2 * o0], w0b = reinterpret_cast<const float4*>(sw.pe0_w)[2 * o0 + 1];
+            const float b0 = sw.pe0_b[o0];
+            float xin[EMF_P];
 #pragma unroll
-    for (int q = 0; q < 8; ++q) seg_o[q + 1] = seg_o[q] + seg_n[q];
-    // the tile's input features: requested first (registers), written to LDS after the encoder tensors, so that both sets of
-    // loads are in flight together (written where they were loaded, the second set waited for the first: two round trips)
-    constexpr int NIN = (MT * CMDGEN_MAX_SMALL + H - 1) / H;            // upper bound of (row, feature) pairs per thread
-    float vin[NIN];
+            for (int k = 0; k < EMF_P; ++k) xin[k] = xh_phar[(size_t)(row0 + r0) * ldp + 3 + k];
+            // layer 2 (waves 0 and 1: one 16-column n-tile each; wave 2: the time column and the zero columns up to 4 EMF_KE)
+            float4 w2 = make_float4(0.f, 0.f, 0.f, 0.f);
+            float b2 = 0.f, tcol = 0.f;
+            if (wv < 2) { w2 = reinterpret_cast<const float4*>(sw.emf_pack)[wv * 64 + lane]; b2 = sw.pe2_b[16 * wv + l16]; }
+            else if (wv == 2 && lane < MT) tcol = t_arr ? t_arr[lay.node_sample[row0 + lane]] : t_chain;
+            // embedding: the wave's four n-tiles, three 16-byte pieces (EMF_KE steps) per lane and tile
+            const float4* pe = reinterpret_cast<const float4*>(sw.emf_pack + EMF_J * 2 * EMF_P) + (size_t)(4 * wv * 64 + lane) * (EMF_KE_LD / 4);
+            float we[4][EMF_KE_LD], be[4];
 #pragma unroll
-    for (int q = 0; q < NIN; ++q) {
-        const int idx = tid + q * nthr;
-        vin[q] = 0.f;
-        if (idx < MT * Fmax) {
-            const int r = idx / Fmax, k = idx - r * Fmax, n = row0 + r;
-            if (r < nvalid) {
-                if (n < lay.Nl) { if (k < d.P) vin[q] = xh_phar[(size_t)n * ldp + 3 + k]; }
-                else if (k < d.R) vin[q] = xh_pocket[(size_t)(n - lay.Nl) * ldq + 3 + k];
-            }
-        }
-    }
-    if (sw.enc_pack) {          // sampler: the eight tensors lie contiguous in one device buffer (cmdgen_finalize_weights)
-        for (int i = tid; i < seg_o[8]; i += nthr) s_enc[i] = sw.enc_pack[i];
-    } else
-    for (int base = 0; base < seg_o[8]; base += 16 * nthr) {
-        float v[16];
+            for (int i = 0; i < 4; ++i) {
 #pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int gi = base + q * nthr + tid;
-            v[q] = 0.f;
-            if (gi < seg_o[8]) {
-                int sg = 0;
-#pragma unroll
-                for (int u = 1; u < 8; ++u) sg += gi >= seg_o[u];
-                v[q] = seg_p[sg][gi - seg_o[sg]];
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int gi = base + q * nthr + tid;
-            if (gi < seg_o[8]) s_enc[gi] = v[q];
-        }
-    }
-    const float *pe0w = s_enc + seg_o[0], *pe0b = s_enc + seg_o[1], *pe2w = s_enc + seg_o[2], *pe2b = s_enc + seg_o[3];
-    const float *re0w = s_enc + seg_o[4], *re0b = s_enc + seg_o[5], *re2w = s_enc + seg_o[6], *re2b = s_enc + seg_o[7];
-#pragma unroll
-    for (int q = 0; q < NIN; ++q) {                       // one (row, feature) pair per thread and slot
-        const int idx = tid + q * nthr;
-        if (idx < MT * Fmax) { const int r = idx / Fmax; s_in[r][idx - r * Fmax] = vin[q]; }
-    }
-    lds_barrier();
-    ESTAMP(0);
-    // encoder layer 0 + SiLU: thread -> (row r, output o)
-    for (int idx = tid; idx < MT * F1max; idx += nthr) {
-        const int r = idx / F1max, o = idx - r * F1max;
-        const int n = row0 + r;
-        if (r >= nvalid) continue;
-        const bool ph = n < lay.Nl;
-        const int F = ph ? d.P : d.R;
-        if (o >= 2 * F) continue;
-        const float* W = (ph ? pe0w : re0w) + o * F;
-        float s = (ph ? pe0b : re0b)[o];
-#pragma unroll 4
-        for (int k = 0; k < F; ++k) s = fmaf(s_in[r][k], W[k], s);
-        const float act = silu_f(s);
-        s_h1[r][o] = act;
-        if (sv.enc1_l) {                                   // training: layer-0 pre-activation and activation
-            if (ph) { sv.enc1_l[(size_t)n * 2 * F + o] = s; sv.enca_l[(size_t)n * 2 * F + o] = act; }
-            else { sv.enc1_p[(size_t)(n - lay.Nl) * 2 * F + o] = s; sv.enca_p[(size_t)(n - lay.Nl) * 2 * F + o] = act; }
-        }
-    }
-    lds_barrier();
-    ESTAMP(1);
-    // encoder layer 2 -> joint space, then the time column (dynamics.py:92-99)
-    for (int idx = tid; idx < MT * d.dyn; idx += nthr) {
-        const int r = idx / d.dyn, j = idx - r * d.dyn;
-        const int n = row0 + r;
-        float s = 0.f;
-        if (r < nvalid) {
-            if (j < d.J) {
-                const bool ph = n < lay.Nl;
-                const int F2 = 2 * (ph ? d.P : d.R);
-                const float* W = (ph ? pe2w : re2w) + j * F2;
-                s = (ph ? pe2b : re2b)[j];
-#pragma unroll 4
-                for (int k = 0; k < F2; ++k) s = fmaf(s_h1[r][k], W[k], s);
-            } else {
-                s = t_arr ? t_arr[lay.node_sample[n]] : t_chain;
-            }
-            if (sv.hdyn) sv.hdyn[(size_t)n * d.dyn + j] = s;
-        }
-        s_h2[r][j] = s;
-    }
-    lds_barrier();
-    ESTAMP(2);
-    {   // embedding dyn -> H: one output column per thread, weights transposed [dyn][H] (coalesced)
-        const int c = tid;
-        const float bc = sw.emb_b[c];
-        float accr[MT];
-#pragma unroll
-        for (int r = 0; r < MT; ++r) accr[r] = bc;
-        for (int k0 = 0; k0 < d.dyn; k0 += 16) {       // sixteen weight loads in flight, then their FMAs (k ascending as before)
-            float wk[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) wk[j] = k0 + j < d.dyn ? sw.emb_wT[(size_t)(k0 + j) * H + c] : 0.f;
-#pragma unroll
-            for (int j = 0; j < 16; ++j)
-                if (k0 + j < d.dyn) {
-#pragma unroll
-                    for (int r = 0; r < MT; ++r) accr[r] = fmaf(s_h2[r][k0 + j], wk[j], accr[r]);
+                for (int q = 0; q < EMF_KE_LD / 4; ++q) {
+                    const float4 v = pe[(size_t)i * 64 * (EMF_KE_LD / 4) + q];
+                    we[i][4 * q] = v.x; we[i][4 * q + 1] = v.y; we[i][4 * q + 2] = v.z; we[i][4 * q + 3] = v.w;
                 }
-        }
+                be[i] = sw.emb_b[16 * (4 * wv + i) + l16];
+            }
+            ESTAMP(0);
+            {   // encoder layer 0 + SiLU -> buf (its padded rows keep the A reads below off one bank; the embedding's output replaces it two barriers on)
+                const float w0[EMF_P] = {w0a.x, w0a.y, w0a.z, w0a.w, w0b.x, w0b.y, w0b.z, w0b.w};
+                float s = b0;
 #pragma unroll
-        for (int r = 0; r < MT; ++r) {
-            const float s = r < nvalid ? accr[r] : 0.f;
-            buf[r * LDA(H) + c] = s;
-            if (r < nvalid && part != 1) {
-                w.h[(size_t)(row0 + r) * H + c] = s;
-                if (sv.h) sv.h[(size_t)(row0 + r) * H + c] = s;      // h entering block 0
+                for (int k = 0; k < EMF_P; ++k) s = fmaf(xin[k], w0[k], s);
+                buf[r0 * LDA(H) + o0] = silu_f(s);
+            }
+            lds_barrier();
+            ESTAMP(1);
+            if (wv < 2) {          // encoder layer 2 -> joint space
+                const float w2v[4] = {w2.x, w2.y, w2.z, w2.w};
+                f32x4v c = {b2, b2, b2, b2};
+#pragma unroll
+                for (int st = 0; st < 2 * EMF_P / 4; ++st) CMDGEN_MFMA16(c, buf[l16 * LDA(H) + 4 * st + g], w2v[st]);
+#pragma unroll
+                for (int v = 0; v < 4; ++v) s_h2[4 * g + v][16 * wv + l16] = c[v];
+            } else if (wv == 2 && lane < MT) {
+                s_h2[lane][EMF_J] = tcol;
+#pragma unroll
+                for (int k = EMF_J + 1; k < 4 * EMF_KE; ++k) s_h2[lane][k] = 0.f;
+            }
+            lds_barrier();
+            ESTAMP(2);
+            {   // embedding dyn -> H
+                float a[EMF_KE];
+#pragma unroll
+                for (int st = 0; st < EMF_KE; ++st) a[st] = s_h2[l16][4 * st + g];
+                f32x4v c[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) c[i] = f32x4v{be[i], be[i], be[i], be[i]};
+#pragma unroll
+                for (int st = 0; st < EMF_KE; ++st) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) CMDGEN_MFMA16(c[i], a[st], we[i][st]);
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) {
+                        const int r = 4 * g + v, col = 16 * (4 * wv + i) + l16;
+                        buf[r * LDA(H) + col] = c[i][v];
+                        if (part != 1) w.h[(size_t)(row0 + r) * H + col] = c[i][v];
+                    }
+                }
+            }
+            lds_barrier();
+            ESTAMP(3);
+        }
+    } else {
+        // The eight encoder tensors (2.8k floats at the shipped sizes) are copied into LDS first, sixteen loads per thread in
+        // flight at a time: the FMA loops below then read them at LDS latency.  Read from global inside those loops they
+        // cost one dependent L2 round trip per unrolled batch (3 passes x up to 10 batches - most of this kernel's time).
+        extern __shared__ float s_enc[];
+        const int seg_n[8] = {2 * d.P * d.P, 2 * d.P, d.J * 2 * d.P, d.J, 2 * d.R * d.R, 2 * d.R, d.J * 2 * d.R, d.J};
+        const float* const seg_p[8] = {sw.pe0_w, sw.pe0_b, sw.pe2_w, sw.pe2_b, sw.re0_w, sw.re0_b, sw.re2_w, sw.re2_b};
+        int seg_o[9];
+        seg_o[0] = 0;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) seg_o[q + 1] = seg_o[q] + seg_n[q];
+        // the tile's input features: requested first (registers), written to LDS after the encoder tensors, so that both sets of
+        // loads are in flight together (written where they were loaded, the second set waited for the first: two round trips)
+        constexpr int NIN = (MT * CMDGEN_MAX_SMALL + H - 1) / H;            // upper bound of (row, feature) pairs per thread
+        float vin[NIN];
+#pragma unroll
+        for (int q = 0; q < NIN; ++q) {
+            const int idx = tid + q * nthr;
+            vin[q] = 0.f;
+            if (idx < MT * Fmax) {
+                const int r = idx / Fmax, k = idx - r * Fmax, n = row0 + r;
+                if (r < nvalid) {
+                    if (n < lay.Nl) { if (k < d.P) vin[q] = xh_phar[(size_t)n * ldp + 3 + k]; }
+                    else if (k < d.R) vin[q] = xh_pocket[(size_t)(n - lay.Nl) * ldq + 3 + k];
+                }
             }
         }
+        if (sw.enc_pack) {          // sampler: the eight tensors lie contiguous in one device buffer (cmdgen_finalize_weights)
+            for (int i = tid; i < seg_o[8]; i += nthr) s_enc[i] = sw.enc_pack[i];
+        } else
+        for (int base = 0; base < seg_o[8]; base += 16 * nthr) {
+            float v[16];
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int gi = base + q * nthr + tid;
+                v[q] = 0.f;
+                if (gi < seg_o[8]) {
+                    int sg = 0;
+#pragma unroll
+                    for (int u = 1; u < 8; ++u) sg += gi >= seg_o[u];
+                    v[q] = seg_p[sg][gi - seg_o[sg]];
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int gi = base + q * nthr + tid;
+                if (gi < seg_o[8]) s_enc[gi] = v[q];
+            }
+        }
+        const float *pe0w = s_enc + seg_o[0], *pe0b = s_enc + seg_o[1], *pe2w = s_enc + seg_o[2], *pe2b = s_enc + seg_o[3];
+        const float *re0w = s_enc + seg_o[4], *re0b = s_enc + seg_o[5], *re2w = s_enc + seg_o[6], *re2b = s_enc + seg_o[7];
+#pragma unroll
+        for (int q = 0; q < NIN; ++q) {                       // one (row, feature) pair per thread and slot
+            const int idx = tid + q * nthr;
+            if (idx < MT * Fmax) { const int r = idx / Fmax; s_in[r][idx - r * Fmax] = vin[q]; }
+        }
+        lds_barrier();
+        ESTAMP(0);
+        // encoder layer 0 + SiLU: thread -> (row r, output o)
+        for (int idx = tid; idx < MT * F1max; idx += nthr) {
+            const int r = idx / F1max, o = idx - r * F1max;
+            const int n = row0 + r;
+            if (r >= nvalid) continue;
+            const bool ph = n < lay.Nl;
+            const int F = ph ? d.P : d.R;
+            if (o >= 2 * F) continue;
+            const float* W = (ph ? pe0w : re0w) + o * F;
+            float s = (ph ? pe0b : re0b)[o];
+#pragma unroll 4
+            for (int k = 0; k < F; ++k) s = fmaf(s_in[r][k], W[k], s);
+            const float act = silu_f(s);
+            s_h1[r][o] = act;
+            if (sv.enc1_l) {                                   // training: layer-0 pre-activation and activation
+                if (ph) { sv.enc1_l[(size_t)n * 2 * F + o] = s; sv.enca_l[(size_t)n * 2 * F + o] = act; }
+                else { sv.enc1_p[(size_t)(n - lay.Nl) * 2 * F + o] = s; sv.enca_p[(size_t)(n - lay.Nl) * 2 * F + o] = act; }
+            }
+        }
+        lds_barrier();
+        ESTAMP(1);
+        // encoder layer 2 -> joint space, then the time column (dynamics.py:92-99)
+        for (int idx = tid; idx < MT * d.dyn; idx += nthr) {
+            const int r = idx / d.dyn, j = idx - r * d.dyn;
+            const int n = row0 + r;
+            float s = 0.f;
+            if (r < nvalid) {
+                if (j < d.J) {
+                    const bool ph = n < lay.Nl;
+                    const int F2 = 2 * (ph ? d.P : d.R);
+                    const float* W = (ph ? pe2w : re2w) + j * F2;
+                    s = (ph ? pe2b : re2b)[j];
+#pragma unroll 4
+                    for (int k = 0; k < F2; ++k) s = fmaf(s_h1[r][k], W[k], s);
+                } else {
+                    s = t_arr ? t_arr[lay.node_sample[n]] : t_chain;
+                }
+                if (sv.hdyn) sv.hdyn[(size_t)n * d.dyn + j] = s;
+            }
+            s_h2[r][j] = s;
+        }
+        lds_barrier();
+        ESTAMP(2);
+        {   // embedding dyn -> H: one output column per thread, weights transposed [dyn][H] (coalesced)
+            const int c = tid;
+            const float bc = sw.emb_b[c];
+            float accr[MT];
+#pragma unroll
+            for (int r = 0; r < MT; ++r) accr[r] = bc;
+            for (int k0 = 0; k0 < d.dyn; k0 += 16) {       // sixteen weight loads in flight, then their FMAs (k ascending as before)
+                float wk[16];
+#pragma unroll
+                for (int j = 0; j < 16; ++j) wk[j] = k0 + j < d.dyn ? sw.emb_wT[(size_t)(k0 + j) * H + c] : 0.f;
+#pragma unroll
+                for (int j = 0; j < 16; ++j)
+                    if (k0 + j < d.dyn) {
+#pragma unroll
+                        for (int r = 0; r < MT; ++r) accr[r] = fmaf(s_h2[r][k0 + j], wk[j], accr[r]);
+                    }
+            }
+#pragma unroll
+            for (int r = 0; r < MT; ++r) {
+                const float s = r < nvalid ? accr[r] : 0.f;
+                buf[r * LDA(H) + c] = s;
+                if (r < nvalid && part != 1) {
+                    w.h[(size_t)(row0 + r) * H + c] = s;
+                    if (sv.h) sv.h[(size_t)(row0 + r) * H + c] = s;      // h entering block 0
+                }
+            }
+        }
+        lds_barrier();
+        ESTAMP(3);
     }
-    lds_barrier();
-    ESTAMP(3);
     tile_project_pq<H, MT, SP>(buf, lw0.Wpq_e, b1v, w.P, w.Q, row0, nvalid, part != 1, carry, f0, part != 0);
     ESTAMP(4);
 #if CMDGEN_STAMPS == 3
@@ -451,8 +535,8 @@ __device__ __forceinline__ void embed_body(const Layout& lay, const Work& w, con
 template <int H, int MT, bool SP>
 __global__ __launch_bounds__(H) void k_embed(Layout lay, Work w, Dims d, SmallW sw, LayerW lw0, const float* __restrict__ xh_phar,
                                              const float* __restrict__ xh_pocket, const float* __restrict__ t_arr,
-                                             const float4* __restrict__ coef, const ChainState* chain, TrainSave sv, PocketCache pc) {
-    embed_body<H, MT, SP>(lay, w, d, sw, lw0, xh_phar, xh_pocket, t_arr, coef, chain, sv, pc, (int)blockIdx.x);
+                                             const float4* __restrict__ coef, const ChainState* chain, TrainSave sv, PocketCache pc, int emf) {
+    embed_body<H, MT, SP>(lay, w, d, sw, lw0, xh_phar, xh_pocket, t_arr, coef, chain, sv, pc, (int)blockIdx.x, 2, emf);
 }
 // Pass 2 of the radius graph (one workgroup per sample, reads positions and degrees) and k_embed (node tiles, reads features and
 // the time) do not depend on each other and are both latency chains of a few workgroups per CU: ONE launch runs them side by
@@ -462,18 +546,20 @@ __global__ __launch_bounds__(H) void k_embed(Layout lay, Work w, Dims d, SmallW 
 template <int MT, bool SP>
 __global__ __launch_bounds__(256) void k_write_embed(Layout lay, Work w, Dims d, SmallW sw, LayerW lw0, const float* __restrict__ xh_phar,
                                                      const float* __restrict__ xh_pocket, const float* __restrict__ t_arr,
-                                                     const float4* __restrict__ coef, const ChainState* chain, PocketCache pc, int npair) {
+                                                     const float4* __restrict__ coef, const ChainState* chain, PocketCache pc, int npair, int emf) {
     // workgroups: [0, B) edge lists | [B, B + 2 npair) pairs over the first npair tiles (the full-path tiles of a chain) |
     // the rest: one workgroup per remaining tile
     const int i = (int)blockIdx.x - lay.B;
     if (i < 0) edge_write_body(lay, w, d, (int)blockIdx.x);
-    else if (i < 2 * npair) embed_body<256, MT, SP>(lay, w, d, sw, lw0, xh_phar, xh_pocket, t_arr, coef, chain, TrainSave{}, pc, i >> 1, i & 1);
-    else embed_body<256, MT, SP>(lay, w, d, sw, lw0, xh_phar, xh_pocket, t_arr, coef, chain, TrainSave{}, pc, i - npair, 2);
+    else if (i < 2 * npair) embed_body<256, MT, SP>(lay, w, d, sw, lw0, xh_phar, xh_pocket, t_arr, coef, chain, TrainSave{}, pc, i >> 1, i & 1, emf);
+    else embed_body<256, MT, SP>(lay, w, d, sw, lw0, xh_phar, xh_pocket, t_arr, coef, chain, TrainSave{}, pc, i - npair, 2, emf);
 }
 
 // ------------------------------------------------------------------------------------
 // host-callable launchers (C++ linkage)
 // ------------------------------------------------------------------------------------
+// the MFMA form of the full-path tile (embed_body): where the plan asks for it and its packs exist
+static inline int embed_mfma_arg(const EvalLaunch& a) { return a.plan.embed_mfma && a.sw.emf_pack && !a.save ? 1 : 0; }
 template <int H, int MT, bool SP> static void launch_embed(const EvalLaunch& a, const float* xp, const float* xq, const float* t,
                                                   const float4* coef, ChainState* chain, hipStream_t s) {
     if constexpr (H == 512 && MT == 64) launch_embed<H, 32, SP>(a, xp, xq, t, coef, chain, s);      // (its 64-row tile would need 181 KB of LDS)
@@ -482,9 +568,9 @@ template <int H, int MT, bool SP> static void launch_embed(const EvalLaunch& a, 
         const Dims& d = a.d;
         const size_t shm = sizeof(float) * (size_t)(2 * d.P * d.P + 2 * d.P + d.J * 2 * d.P + d.J + 2 * d.R * d.R + 2 * d.R + d.J * 2 * d.R + d.J);
         if (a.save) hipLaunchKernelGGL((k_embed<H, MT, false>), dim3(nt), dim3(H), shm, s, a.lay, a.w, a.d, a.sw, a.layers[0], xp, xq, t, coef,
-                                       (const ChainState*)chain, *a.save, PocketCache{});          // training packs: fp32 fragments only
+                                       (const ChainState*)chain, *a.save, PocketCache{}, 0);          // training packs: fp32 fragments only
         else hipLaunchKernelGGL((k_embed<H, MT, SP>), dim3(nt), dim3(H), shm, s, a.lay, a.w, a.d, a.sw, a.layers[0], xp, xq, t, coef,
-                                (const ChainState*)chain, TrainSave{}, (chain && !t) ? a.pcache : PocketCache{});
+                                (const ChainState*)chain, TrainSave{}, (chain && !t) ? a.pcache : PocketCache{}, embed_mfma_arg(a));
     }
 }
 template <int H, int MT, bool SP> static void launch_write_embed(const EvalLaunch& a, const float* xp, const float* xq, const float* t,
@@ -497,7 +583,7 @@ template <int H, int MT, bool SP> static void launch_write_embed(const EvalLaunc
         const PocketCache pc = (chain && !t) ? a.pcache : PocketCache{};
         const int npair = pc.c ? (a.lay.Nl + MT - 1) / MT : 0;        // pairs only where the other tiles are cache tiles
         hipLaunchKernelGGL((k_write_embed<MT, SP>), dim3(a.lay.B + nt + npair), dim3(256), shm_e > shm_w ? shm_e : shm_w, s, a.lay, a.w, a.d, a.sw,
-                           a.layers[0], xp, xq, t, coef, (const ChainState*)chain, pc, npair);
+                           a.layers[0], xp, xq, t, coef, (const ChainState*)chain, pc, npair, embed_mfma_arg(a));
     }
 }
 template <int H> static void embed_only_H(const EvalLaunch& a, const float* xp, const float* xq, const float* t, hipStream_t s) {
