@@ -893,6 +893,104 @@ extern "C" int cmdgen_sample_chain(cmdgen_handle* h, const float* pocket_x, cons
 }
 
 // ---------------------------------------------------------------------------------
+// the multi-pocket chain: one latent per GROUP of consecutive samples (kernels_multi.hip; the ops, the draw layout and the
+// Philox counters are in include/cmdgen_hip.h).  The evaluations are the ordinary ones over the member samples.
+// ---------------------------------------------------------------------------------
+static_assert(CMDGEN_MAX_GROUP == MAX_GROUP, "the public bound and the kernels' agree");
+
+// the multi-pocket chain's ChainBuf and, behind the posterior rows (n_steps + 1) of the slot's table block, the group tables:
+// first | size | ubase | weight (one entry per member each), then the groups' first members
+static int alloc_multi(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
+    int rc = alloc_chain_buf(h, k, h->multi_chain, tables); if (rc) return rc;
+    const size_t B = (size_t)h->lay.B;
+    const float* g = tables + (size_t)(n_steps + 1) * 4;
+    GroupTab& gt = h->groups;
+    gt.first = (const int*)g; gt.size = (const int*)(g + B); gt.ubase = (const int*)(g + 2 * B);
+    gt.weight = g + 3 * B; gt.group_first = (const int*)(g + 4 * B);
+    return 0;
+}
+
+extern "C" int cmdgen_multi_pocket_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
+                                         int64_t n_groups, const int64_t* group_size_host, const float* weight_host,
+                                         int32_t timesteps, const float* noise, uint64_t seed, const int64_t* group_ids_host,
+                                         float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                                         int32_t use_graph, cmdgen_stream stream) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (h->dims.joint) return fail(h, CMDGEN_ESTATE, "the multi-pocket chain is not supported for the joint model (update_pocket_coords=1): its pocket nodes diffuse with the latent");
+    if (h->dims.no_com) return fail(h, CMDGEN_ESTATE, "the multi-pocket chain is not supported for no_com_projection handles (SimpleConditionalDDPM)");
+    if (!pocket_x || !pocket_onehot || !group_size_host || !weight_host || !xh_phar_out || !xh_pocket_out)
+        return fail(h, CMDGEN_EINVAL, "null pointer");
+    const int K = timesteps;
+    if (K < 1 || K > h->cfg.timesteps) return fail(h, CMDGEN_EINVAL, "timesteps=%d must be in [1, %d]", K, h->cfg.timesteps);
+    const int B = h->lay.B;
+    if (n_groups < 1 || n_groups > B) return fail(h, CMDGEN_EINVAL, "n_groups=%lld must be in [1, batch=%d]", (long long)n_groups, B);
+    const int G = (int)n_groups;
+    // the group tables, per member (GroupTab)
+    std::vector<int> first(B), size(B), ubase(B), gfirst(G);
+    std::vector<int64_t> gid(B);
+    int64_t members = 0, Nu = 0;
+    for (int g = 0; g < G; ++g) {
+        const int64_t M = group_size_host[g];
+        if (M < 1 || M > CMDGEN_MAX_GROUP) return fail(h, CMDGEN_EINVAL, "group %d has %lld members: sizes must be in [1, %d]", g, (long long)M, CMDGEN_MAX_GROUP);
+        if (members + M > B) { members += M; continue; }                 // (reported below with the sum)
+        gfirst[g] = (int)members;
+        double wsum = 0.0;
+        for (int m = 0; m < (int)M; ++m) {
+            const int b = (int)members + m;
+            if (h->cur_nphar[b] != h->cur_nphar[members])
+                return fail(h, CMDGEN_EINVAL, "group %d: member %d has %lld phar nodes, member 0 has %lld (the members of a group share one latent)",
+                            g, m, (long long)h->cur_nphar[b], (long long)h->cur_nphar[members]);
+            const float w = weight_host[b];
+            if (!std::isfinite(w) || w < 0.f) return fail(h, CMDGEN_EINVAL, "group %d: weight %d is %g (weights must be finite and >= 0)", g, m, (double)w);
+            wsum += (double)w;
+            first[b] = (int)members; size[b] = (int)M; ubase[b] = (int)Nu;
+            gid[b] = group_ids_host ? group_ids_host[g] : g;
+        }
+        if (std::fabs(wsum - 1.0) > 1e-5)
+            return fail(h, CMDGEN_EINVAL, "group %d: its weights sum to %.9g, not 1 (the caller normalises them)", g, wsum);
+        Nu += h->cur_nphar[members];
+        members += M;
+    }
+    if (members != B) return fail(h, CMDGEN_EINVAL, "the group sizes sum to %lld, the layout has %d samples", (long long)members, B);
+    const size_t step_lds = (size_t)h->lay.max_n * (sizeof(float4) + sizeof(int) + (size_t)(3 + h->dims.P) * sizeof(float));
+    if (step_lds > 64 * 1024)
+        return fail(h, CMDGEN_EINVAL, "a sample has %d nodes: the multi-pocket step keeps a sample's positions, degrees and z in LDS (64 KiB)", h->lay.max_n);
+    std::vector<float> tables = step_table(h, K);
+    {
+        const size_t c0 = tables.size();
+        tables.resize(c0 + (size_t)4 * B + G);
+        float* g = tables.data() + c0;
+        memcpy(g, first.data(), (size_t)B * sizeof(int)); memcpy(g + B, size.data(), (size_t)B * sizeof(int));
+        memcpy(g + 2 * (size_t)B, ubase.data(), (size_t)B * sizeof(int)); memcpy(g + 3 * (size_t)B, weight_host, (size_t)B * sizeof(float));
+        memcpy(g + 4 * (size_t)B, gfirst.data(), (size_t)G * sizeof(int));
+    }
+    const hipStream_t caller = (hipStream_t)stream;
+    hipStream_t s; EvalLaunch a;
+    rc = begin_chain(h, CHAIN_MULTI, tables, K, alloc_multi, gid.data(), use_graph, caller, &s, &a); if (rc) return rc;
+    ChainSlot& k = h->chains[CHAIN_MULTI];
+    const Dims& d = h->dims;
+    ChainBuf c = h->multi_chain;
+    c.noise = noise; c.seed = seed; c.z_steps = z_steps_out; c.pocket_steps = pocket_steps_out;
+    GroupTab gt = h->groups;
+    gt.G = G; gt.Nu = (int)Nu;
+    cmdgen_launch_multi_init(h->lay, d, c, gt, pocket_x, pocket_onehot, s);
+    build_pocket_cache(h, k, c, a, s);
+    EvalLaunch a2 = a;
+    a2.skip_count = 1;                               // k_multi_step_count ran pass 1 of the graph
+    cmdgen_launch_eval(a, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, s, nullptr);   // evaluation 0 (t = 1)
+    // the group tables are slot buffers (a changed grouping or weight prepares the slot again and drops its graph); the group ids are
+    // uploaded per call, like the pocket ids of the other chains
+    const void* key[6] = {noise, z_steps_out, pocket_steps_out, nullptr, nullptr, s};
+    rc = run_steps(h, k, key, seed, K, use_graph, s, [&](hipStream_t ss) {
+        cmdgen_launch_multi_step_count(h->lay, d, c, gt, h->work, h->work.eps_tmp, ss);
+        cmdgen_launch_eval(a2, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, ss, nullptr);
+    });
+    if (rc) return rc;
+    cmdgen_launch_multi_final(h->lay, d, c, gt, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, k.cog, s);
+    return end_chain(h, caller, s);
+}
+
+// ---------------------------------------------------------------------------------
 // joint model: EnVariationalDiffusion.sample / .inpaint (en_diffusion.py:576-831)
 // ---------------------------------------------------------------------------------
 // get_repaint_schedule (en_diffusion.py:649-670): denoising steps to run before each jump back

@@ -191,6 +191,18 @@ struct ScoreBuf {               // scoring chain (cmdgen_score_chain), beside a 
 };
 enum { SC_ERR = 0, SC_ERR_X = 1, SC_LOG_PH = 2, SC_RESET = 3, SC_COLS = 4 };     // = CMDGEN_SC_COLS
 
+struct GroupTab {               // multi-pocket chain (cmdgen_multi_pocket_chain), beside a ChainBuf: the M consecutive samples ("members") of a
+                                // group share one latent.  Every member holds its own copy of z in the ChainBuf's z_phar ([Nl] rows); noise, z_steps
+                                // and the phar output hold one copy of the rows per group ([Nu] rows)
+    const int* first;           // [B]  first member of the sample's group
+    const int* size;            // [B]  members of the sample's group (1 .. MAX_GROUP)
+    const int* ubase;           // [B]  first of the group's rows among the Nu unique rows
+    const float* weight;        // [B]  the member's weight (>= 0; a group's weights sum to 1)
+    const int* group_first;     // [G]  first member of every group
+    int G, Nu;                  // groups, unique phar rows
+};
+enum { MAX_GROUP = 8 };         // = CMDGEN_MAX_GROUP
+
 struct PocketCache {            // chain-invariant part of k_embed's output for POCKET rows (conditional sampler): the pocket's
                                 // features never change during a chain and the embedding is affine in the time feature, so
                                 //   h(t) = c + t dh,  P(t) = P0 + t dP,  Q(t) = Q0 + t dQ   (dh, dP, dQ: one row of H values each)

@@ -49,6 +49,14 @@ void cmdgen_launch_chain_final(const Layout& lay, const Dims& d, const ChainBuf&
                                unsigned int* cog, hipStream_t s);
 void cmdgen_launch_debug_noise(unsigned long long seed, long long pocket_id, int draw, int n_nodes, int width, float* out, hipStream_t s);
 
+// kernels_multi.hip: the multi-pocket chain (groups of samples that share one latent)
+void cmdgen_launch_multi_init(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const float* px, const float* poh,
+                              hipStream_t s);
+void cmdgen_launch_multi_step_count(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const Work& w, const float* eps,
+                                    hipStream_t s);
+void cmdgen_launch_multi_final(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const Work& w, const float* eps,
+                               float* xo, float* po, unsigned int* cog, hipStream_t s);
+
 // kernels_inpaint.hip: the conditional RePaint chain and the edit chain
 void cmdgen_launch_inpaint_prep(const Layout& lay, const Dims& d, const ChainBuf& c, const InpaintBuf& ip, const float* phx,
                                 const float* phoh, const float* fix_x, const float* fix_h, const float* px, hipStream_t s);

@@ -1,4 +1,4 @@
-// cmdgen_sampler.h - device helpers of the conditional sampler kernels (kernels_ddpm.hip, kernels_inpaint.hip, kernels_score.hip).
+// cmdgen_sampler.h - device helpers of the conditional sampler kernels (kernels_ddpm.hip, kernels_inpaint.hip, kernels_score.hip, kernels_multi.hip).
 // These translation units are built with -ffp-contract=off, so the same helper rounds the same way in each.
 #pragma once
 #include "cmdgen_dev.h"

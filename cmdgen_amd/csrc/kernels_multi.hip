@@ -1,0 +1,297 @@
+// kernels_multi.hip - the multi-pocket chain (cmdgen_multi_pocket_chain): kernels_ddpm.hip's init, step and decode for groups of
+// M consecutive samples ("members") that share ONE latent z and differ in their pockets.  The evaluation between the ops is the
+// ordinary one over the B member samples; an op combines the members' eps rows with the group's weights,
+//   eps_bar = sum_m w_m eps_m  (m ascending, the first term is not added to a zero),
+// and is sample_given_pocket's op on eps_bar otherwise.  One workgroup per MEMBER: every member keeps its own copy of z, reads
+// the eps rows of all members of its group (nothing writes them in these launches), combines them in member order and draws with
+// the group's key - so the copies stay bit-identical without any synchronisation between workgroups - then translates its own
+// pocket and counts its own edges.  Sums run in index order as in kernels_ddpm.hip; with M = 1 every value is that file's, bit for bit.
+#include "cmdgen_sampler.h"
+
+// one draw per group and op: row ubase + local of the [Nu] unique rows, or Philox keyed by the group's id (Layout::pocket_gid holds it
+// for every member)
+__device__ __forceinline__ float draw_group(const ChainBuf& c, const Layout& lay, const GroupTab& g, int draw_idx, int b,
+                                            int local, int comp, int ld) {
+    if (c.noise) return c.noise[((size_t)draw_idx * g.Nu + g.ubase[b] + local) * ld + comp];
+    float z[4];
+    philox_normal4(c.seed, (uint32_t)lay.pocket_gid[b], (uint32_t)(lay.pocket_gid[b] >> 32),
+                   (uint32_t)draw_idx, (uint32_t)(local * 4 + (comp >> 2)), z);
+    return z[comp & 3];
+}
+
+// eps_bar of element idx of the group's rows (eps: [Nl][ld], a member's rows start at its phar_base)
+__device__ __forceinline__ float combine_eps(const Layout& lay, const GroupTab& g, const float* __restrict__ eps, int first, int M,
+                                             int ld, int idx) {
+    float e = g.weight[first] * eps[(size_t)lay.phar_base[first] * ld + idx];
+    for (int m = 1; m < M; ++m) e = e + g.weight[first + m] * eps[(size_t)lay.phar_base[first + m] * ld + idx];
+    return e;
+}
+
+// subtract the centre of mass of the member's z from its z and its pocket (remove_com of kernels_ddpm.hip)
+__device__ __forceinline__ void remove_com_member(float* zx, int ld, int pb, int nl, float* px, int ldq, int qb, int np, int lane) {
+    float mean = 0.f;
+    if (lane < 3) {
+        float s = 0.f;
+        for (int i = 0; i < nl; ++i) s += zx[(size_t)(pb + i) * ld + lane];
+        mean = s / fmaxf((float)nl, 1.0f);
+    }
+    const float m0 = __shfl(mean, 0), m1 = __shfl(mean, 1), m2 = __shfl(mean, 2);
+    for (int i = lane; i < nl; i += 64) {
+        float* p = zx + (size_t)(pb + i) * ld;
+        p[0] -= m0; p[1] -= m1; p[2] -= m2;
+    }
+    for (int i = lane; i < np; i += 64) {
+        float* p = px + (size_t)(qb + i) * ldq;
+        p[0] -= m0; p[1] -= m1; p[2] -= m2;
+    }
+}
+
+// z_T = [sum_m w_m com(P_m), 0] + noise, then the COM projection of the member's z and pocket.  A member's centre is summed from
+// the RAW input (pocket_x[i] / norm_x in index order: the values k_chain_init stores and sums), never from another member's
+// normalised rows, which that member's workgroup may still be writing.
+__global__ __launch_bounds__(64) void k_multi_init(Layout lay, Dims d, ChainBuf c, GroupTab g,
+                                                   const float* __restrict__ pocket_x,
+                                                   const float* __restrict__ pocket_onehot) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int nl = lay.num_phar[b], np = lay.num_pocket[b];
+    const int pb = lay.phar_base[b], qb = lay.pocket_base[b];
+    const int ld = 3 + d.P, ldq = 3 + d.R;
+    const int first = g.first[b], M = g.size[b];
+    for (int i = lane; i < np; i += 64) {
+        float* o = c.xh_pocket + (size_t)(qb + i) * ldq;
+        for (int k = 0; k < 3; ++k) o[k] = pocket_x[(size_t)(qb + i) * 3 + k] / d.norm_x;
+        for (int k = 0; k < d.R; ++k) o[3 + k] = (pocket_onehot[(size_t)(qb + i) * d.R + k] - d.bias_h) / d.norm_h;
+    }
+    __syncthreads();
+    float mu = 0.f;
+    if (lane < 3) {
+        for (int m = 0; m < M; ++m) {
+            const int qm = lay.pocket_base[first + m], npm = lay.num_pocket[first + m];
+            float s = 0.f;
+            for (int i = 0; i < npm; ++i) s += pocket_x[(size_t)(qm + i) * 3 + lane] / d.norm_x;
+            const float com = s / fmaxf((float)npm, 1.0f);
+            mu = m == 0 ? g.weight[first] * com : mu + g.weight[first + m] * com;
+        }
+    }
+    const float m0 = __shfl(mu, 0), m1 = __shfl(mu, 1), m2 = __shfl(mu, 2);
+    for (int idx = lane; idx < nl * ld; idx += 64) {
+        const int i = idx / ld, k = idx % ld;
+        const float m = k == 0 ? m0 : k == 1 ? m1 : k == 2 ? m2 : 0.f;
+        c.z_phar[(size_t)(pb + i) * ld + k] = m + 1.0f * draw_group(c, lay, g, 0, b, i, k, ld);
+    }
+    __syncthreads();
+    remove_com_member(c.z_phar, ld, pb, nl, c.xh_pocket, ldq, qb, np, lane);
+    __syncthreads();
+    record_com_check(c.check, c.z_phar, ld, pb, nl, 1.0f, lane);
+}
+
+// the decode of k_chain_final on eps_bar.  Every member decodes its own copy of z in place and moves its own pocket; the group's first
+// member writes the group's rows of xh_phar_out.  The checks and the CoG drift are taken from the member's own values (z * norm_x,
+// the bits the output holds), so no workgroup reads rows another one writes.
+__global__ __launch_bounds__(64) void k_multi_final(Layout lay, Dims d, ChainBuf c, GroupTab g, Work w,
+                                                    const float* __restrict__ eps,
+                                                    float* __restrict__ xh_phar_out,
+                                                    float* __restrict__ xh_pocket_out,
+                                                    unsigned int* cog_slot) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int nl = lay.num_phar[b], np = lay.num_pocket[b];
+    const int pb = lay.phar_base[b], qb = lay.pocket_base[b];
+    const int ld = 3 + d.P, ldq = 3 + d.R;
+    const int first = g.first[b], M = g.size[b], ub = g.ubase[b];
+    const bool writer = b == first;
+    const int K = c.state->K;
+    const float4 cf = c.coef[K];                    // (sigma_0, alpha_0, sigma_x = exp(gamma_0/2), 0)
+    const bool nan_reset = *w.nan_flag != 0;
+    if (writer)
+        for (int i = lane; i < nl; i += 64) {       // types: argmax of the un-normalised h of z_0
+            const float* z = c.z_phar + (size_t)(pb + i) * ld;
+            int best = 0; float bv = z[3] * d.norm_h + d.bias_h;
+            for (int k = 1; k < d.P; ++k) { const float v = z[3 + k] * d.norm_h + d.bias_h; if (v > bv) { bv = v; best = k; } }
+            float* o = xh_phar_out + (size_t)(ub + i) * ld;
+            for (int k = 0; k < d.P; ++k) o[3 + k] = (k == best) ? 1.0f : 0.0f;
+        }
+    __syncthreads();
+    for (int idx = lane; idx < nl * ld; idx += 64) {
+        const int i = idx / ld, k = idx % ld;
+        const size_t o = (size_t)(pb + i) * ld + k;
+        float e = combine_eps(lay, g, eps, first, M, ld, idx);
+        if (nan_reset && k < 3) e = 0.f;
+        const float mu = (1.0f / cf.y) * (c.z_phar[o] - cf.x * e);
+        c.z_phar[o] = mu + cf.z * draw_group(c, lay, g, 1 + K, b, i, k, ld);
+    }
+    __syncthreads();
+    remove_com_member(c.z_phar, ld, pb, nl, c.xh_pocket, ldq, qb, np, lane);
+    __syncthreads();
+    if (writer)
+        for (int i = lane; i < nl; i += 64) {
+            const float* z = c.z_phar + (size_t)(pb + i) * ld;
+            float* o = xh_phar_out + (size_t)(ub + i) * ld;
+            o[0] = z[0] * d.norm_x; o[1] = z[1] * d.norm_x; o[2] = z[2] * d.norm_x;
+        }
+    for (int i = lane; i < np; i += 64) {
+        const float* q = c.xh_pocket + (size_t)(qb + i) * ldq;
+        float* o = xh_pocket_out + (size_t)(qb + i) * ldq;
+        o[0] = q[0] * d.norm_x; o[1] = q[1] * d.norm_x; o[2] = q[2] * d.norm_x;
+        for (int k = 0; k < d.R; ++k) o[3 + k] = q[3 + k] * d.norm_h + d.bias_h;
+    }
+    record_com_check(c.check + 2 * (1 + K), c.z_phar, ld, pb, nl, d.norm_x, lane);
+    float s = 0.f;
+    if (lane < 3) for (int i = 0; i < nl; ++i) s += c.z_phar[(size_t)(pb + i) * ld + lane] * d.norm_x;
+    s = fabsf(s);
+    s = max_nan(s, max_nan(__shfl(s, 1), __shfl(s, 2)));
+    if (lane == 0) atomic_max_pos(cog_slot, s);
+    if (b == 0 && lane == 0 && nan_reset) atomicAdd(&w.counters[4], 1ull);
+}
+
+// the batch-wide re-centring of k_chain_drift_fix, one workgroup per GROUP: the group's phar rows and every member's pocket
+__global__ __launch_bounds__(64) void k_multi_drift_fix(Layout lay, Dims d, GroupTab g, float* __restrict__ xh_phar_out,
+                                                        float* __restrict__ xh_pocket_out, const unsigned int* cog_slot) {
+    if (!(__uint_as_float(*cog_slot) > 5e-2f)) return;
+    const int first = g.group_first[blockIdx.x], lane = threadIdx.x;
+    const int nl = lay.num_phar[first], ub = g.ubase[first], M = g.size[first];
+    const int ld = 3 + d.P, ldq = 3 + d.R;
+    float mean = 0.f;
+    if (lane < 3) {
+        float s = 0.f;
+        for (int i = 0; i < nl; ++i) s += xh_phar_out[(size_t)(ub + i) * ld + lane];
+        mean = s / fmaxf((float)nl, 1.0f);
+    }
+    const float m0 = __shfl(mean, 0), m1 = __shfl(mean, 1), m2 = __shfl(mean, 2);
+    __syncthreads();
+    for (int i = lane; i < nl; i += 64) {
+        float* p = xh_phar_out + (size_t)(ub + i) * ld;
+        p[0] -= m0; p[1] -= m1; p[2] -= m2;
+    }
+    for (int m = 0; m < M; ++m) {
+        const int qb = lay.pocket_base[first + m], np = lay.num_pocket[first + m];
+        for (int i = lane; i < np; i += 64) {
+            float* p = xh_pocket_out + (size_t)(qb + i) * ldq;
+            p[0] -= m0; p[1] -= m1; p[2] -= m2;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// k_multi_step_count: k_step_count (kernels_ddpm.hip) on eps_bar - one posterior step of the member's copy of z, fused with pass 1
+// of the radius graph of the member's next evaluation.  Same LDS layout, same sums, same count pass; z_steps (one copy of the
+// rows per group) is written by the group's first member.
+// ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void k_multi_step_count(Layout lay, Dims d, ChainBuf c, GroupTab g, Work w,
+                                                          const float* __restrict__ eps) {
+    extern __shared__ float4 s_pos[];               // [max_n] positions of the sample (phar first), then int sdeg[max_n], then z
+    int* sdeg = reinterpret_cast<int*>(s_pos + lay.max_n);
+    float* s_z = reinterpret_cast<float*>(sdeg + lay.max_n);      // [nl * ld]
+    __shared__ float s_mean[3];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
+    const int nl = lay.num_phar[b], np = lay.num_pocket[b], n = nl + np;
+    const int pb = lay.phar_base[b], qb = lay.pocket_base[b];
+    const int ld = 3 + d.P, ldq = 3 + d.R;
+    const int first = g.first[b], M = g.size[b];
+    const int step = c.state->step - 1;
+    const float4 cf = c.coef[step];
+    const bool nan_reset = *w.nan_flag != 0;
+    float* zg = c.z_phar + (size_t)pb * ld;
+    const int cnt = nl * ld;
+    for (int idx = tid; idx < cnt; idx += blockDim.x) s_z[idx] = zg[idx];
+    for (int i = tid; i < np; i += blockDim.x) {
+        const float* q = c.xh_pocket + (size_t)(qb + i) * ldq;
+        s_pos[nl + i] = make_float4(q[0], q[1], q[2], 0.f);
+    }
+    __syncthreads();
+    if (wave == 0) record_com_check(c.check + 2 * (1 + step), s_z, ld, 0, nl, 1.0f, lane);   // z_t, the step's input
+    __syncthreads();
+    for (int idx = tid; idx < cnt; idx += blockDim.x) {
+        const int i = idx / ld, k = idx - i * ld;
+        float e = combine_eps(lay, g, eps, first, M, ld, idx);
+        if (nan_reset && k < 3) e = 0.f;
+        const float mu = s_z[idx] / cf.x - cf.y * e;
+        s_z[idx] = mu + cf.z * draw_group(c, lay, g, 1 + step, b, i, k, ld);
+    }
+    __syncthreads();
+    if (tid < 3) {                                  // centre of mass of the new z, index order
+        float sum = 0.f;
+        for (int i = 0; i < nl; ++i) sum += s_z[i * ld + tid];
+        s_mean[tid] = sum / fmaxf((float)nl, 1.0f);
+    }
+    __syncthreads();
+    const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
+    for (int i = tid; i < n; i += blockDim.x) {
+        float4 p;
+        if (i < nl) {
+            float* z = s_z + i * ld;
+            z[0] -= m0; z[1] -= m1; z[2] -= m2;
+            p = make_float4(z[0], z[1], z[2], 0.f);
+            w.X0[pb + i] = p;
+            for (int l = 0; l < d.L; ++l) w.ACC[(size_t)l * lay.Nm + pb + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+            p = s_pos[i];
+            p.x -= m0; p.y -= m1; p.z -= m2;
+            float* q = c.xh_pocket + (size_t)(qb + i - nl) * ldq;
+            q[0] = p.x; q[1] = p.y; q[2] = p.z;
+            w.XP[qb + i - nl] = p;
+            if (c.pocket_steps) {
+                float* o = c.pocket_steps + ((size_t)step * lay.Np + qb + i - nl) * 3;
+                o[0] = p.x; o[1] = p.y; o[2] = p.z;
+            }
+        }
+        s_pos[i] = p;
+    }
+    __syncthreads();
+    const bool writer = c.z_steps && b == first;
+    float* zs = writer ? c.z_steps + ((size_t)step * g.Nu + g.ubase[b]) * ld : nullptr;
+    for (int idx = tid; idx < cnt; idx += blockDim.x) {
+        const float v = s_z[idx];
+        zg[idx] = v;
+        if (writer) zs[idx] = v;
+    }
+    // ---- pass 1 of the radius graph of the NEXT evaluation (as k_edge_count)
+    for (int i = wave; i < n; i += nwaves) {
+        const float4 pi = s_pos[i];
+        int deg = 0, self = 0;
+        for (int j0 = 0; j0 < n; j0 += 64) {
+            const int j = j0 + lane;
+            bool ok = false;
+            if (j < n) {
+                const float r2 = dist2(pi, s_pos[j]);
+                ok = (d.cutoff2 < 0.f) || (r2 <= d.cutoff2);
+            }
+            const unsigned long long m = __ballot(ok);
+            deg += __popcll(m);
+            if (i >= j0 && i < j0 + 64) self = (int)((m >> (i - j0)) & 1ull);
+        }
+        if (lane == 0) { sdeg[i] = deg | (self << 30); w.degL[pb + qb + i] = deg | (self << 30); }
+    }
+    __syncthreads();
+    if (wave == 0) {
+        int e = 0, eph = 0, ens = 0, ensq = 0;
+        for (int i = lane; i < n; i += 64) {
+            const int dg = sdeg[i] & 0x3fffffff; e += dg;
+            if (i < nl) { eph += dg; ens += dg - ((sdeg[i] >> 30) & 1); }
+            else ensq += dg - ((sdeg[i] >> 30) & 1);
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            e += __shfl_xor(e, o); eph += __shfl_xor(eph, o); ens += __shfl_xor(ens, o); ensq += __shfl_xor(ensq, o);
+        }
+        if (lane == 0) { w.pocketE[b] = e; w.pocketEph[b] = eph; w.pocketEns[b] = ens; w.pocketEnsQ[b] = ensq; }
+    }
+    if (b == 0 && tid == 0) {
+        if (nan_reset) atomicAdd(&w.counters[4], 1ull);
+        atomicAdd(&w.counters[0], 1ull);                       // evaluations (the one about to run)
+        atomicAdd(&w.counters[3], (unsigned long long)lay.N);  // nodes
+    }
+}
+
+void cmdgen_launch_multi_init(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const float* px,
+                              const float* poh, hipStream_t s) {
+    hipLaunchKernelGGL(k_multi_init, dim3(lay.B), dim3(64), 0, s, lay, d, c, g, px, poh);
+}
+void cmdgen_launch_multi_step_count(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const Work& w,
+                                    const float* eps, hipStream_t s) {
+    const size_t shm = (size_t)lay.max_n * (sizeof(float4) + sizeof(int)) + (size_t)lay.max_n * (3 + d.P) * sizeof(float);
+    hipLaunchKernelGGL(k_multi_step_count, dim3(lay.B), dim3(lay.max_n > 128 ? 1024 : 256), shm, s, lay, d, c, g, w, eps);   // as k_step_count
+}
+void cmdgen_launch_multi_final(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const Work& w,
+                               const float* eps, float* xo, float* po, unsigned int* cog, hipStream_t s) {
+    hipLaunchKernelGGL(k_multi_final, dim3(lay.B), dim3(64), 0, s, lay, d, c, g, w, eps, xo, po, cog);
+    hipLaunchKernelGGL(k_multi_drift_fix, dim3(g.G), dim3(64), 0, s, lay, d, g, xo, po, (const unsigned int*)cog);
+}

@@ -183,6 +183,92 @@ class ConditionalDDPM(EnVariationalDiffusion):
         out = self._finish_chain(h, run, self.inpaint_frames(1, 1, timesteps, return_frames), return_frames)
         return out[0], out[1], phar_mask, pocket['mask']
 
+    @staticmethod
+    def group_weights(weights, n_groups, n_members):
+        """weights None (uniform), [M] or [G, M] -> float32 numpy [G, M], every row normalised to sum 1 in float64."""
+        if weights is None:
+            w = np.ones((n_groups, n_members), dtype=np.float64)
+        else:
+            w = np.asarray(torch.as_tensor(weights).detach().cpu().numpy(), dtype=np.float64)
+            if w.shape == (n_members,):
+                w = np.broadcast_to(w, (n_groups, n_members)).copy()
+            elif w.shape != (n_groups, n_members):
+                raise ValueError(f'weights has shape {tuple(w.shape)}: expected [{n_members}] (one per pocket) or '
+                                 f'[{n_groups}, {n_members}] (per group and pocket)')
+        if not np.isfinite(w).all() or (w < 0).any():
+            raise ValueError('weights must be finite and >= 0')
+        tot = w.sum(axis=1, keepdims=True)
+        if (tot <= 0).any():
+            raise ValueError('the weights of a group sum to zero')
+        return (w / tot).astype(np.float32)
+
+    @torch.no_grad()
+    def sample_given_pockets(self, pockets, num_nodes_phar, weights=None, return_frames=1, timesteps=None,
+                             noise=None, seed=None, group_ids=None):
+        """Draw ONE pharmacophore per group of pockets (dual-target design, or an ensemble of conformations of one receptor): one
+        chain whose latent is shared by the group's pockets.  At every step the eps-predictions of the pocket contexts are combined
+        with the weights - the score of the weighted geometric mixture of the per-pocket distributions - and the step is
+        sample_given_pocket's otherwise; the shared latent stays centre-of-mass free and every pocket carries its own translated copy
+        (cmdgen_multi_pocket_chain: its header gives the ops, the draw layout and the Philox counters).
+
+        pockets: list of M pocket dicts (x, one_hot, size [G], mask) as sample_given_pocket takes one, each batched over the same G
+        groups: group g samples one pharmacophore for pockets[0] .. pockets[M-1] of g.  The pockets of a group must be given in ONE
+        common frame - superposing the structures is the caller's business; sizes and compositions differ freely.
+        num_nodes_phar [G]; weights None (uniform), [M] or [G, M], >= 0, normalised per group in float64 and cast to float32;
+        noise [K+2, Nu, 3+phar_nf] (one draw per group and op, Nu = sum(num_nodes_phar)); seed as in sample_given_pocket; group_ids
+        [G] global group ids of the Philox draws.  With M = 1 this is sample_given_pocket, bit for bit.
+        Returns (xh_phar [Nu, 3+P], [xh_pocket_m], phar_mask, [pocket_mask_m]); with return_frames > 1 the tensors carry the leading
+        frame axis of sample_given_pocket."""
+        pockets = list(pockets)
+        if not pockets:
+            raise ValueError('pockets is empty: expected a list of pocket dicts')
+        M, G = len(pockets), len(pockets[0]['size'])
+        if M > 8:
+            raise ValueError(f'{M} pockets per group: the multi-pocket chain takes at most 8')
+        for m, q in enumerate(pockets):
+            if len(q['size']) != G:
+                raise ValueError(f"pockets[{m}] holds {len(q['size'])} groups, pockets[0] {G}: every dict is batched over the same groups")
+            qm = q['mask']
+            if qm.numel() > 1 and bool((qm[1:] < qm[:-1]).any()):
+                raise ValueError('pocket mask must be ascending and contiguous')
+        nph = torch.as_tensor(num_nodes_phar).detach().to('cpu', torch.int64).numpy().reshape(-1)
+        if len(nph) != G:
+            raise ValueError(f'num_nodes_phar has {len(nph)} entries for {G} groups')
+        w = self.group_weights(weights, G, M)
+        timesteps = self.T if timesteps is None else timesteps
+        assert 0 < return_frames <= timesteps
+        assert timesteps % return_frames == 0
+        device = pockets[0]['x'].device
+        # the member layout: sample g * M + m is pocket m of group g
+        sizes = np.stack([q['size'].detach().to('cpu', torch.int64).numpy() for q in pockets], axis=1)       # [G, M]
+        base = np.concatenate([[0], np.cumsum(sizes.reshape(-1))])                                           # [G * M + 1] first row of every member
+        rows = []                                                                                            # per m: its rows in the member layout
+        for m, q in enumerate(pockets):
+            start = np.concatenate([[0], np.cumsum(sizes[:, m])[:-1]])
+            g_of = np.repeat(np.arange(G), sizes[:, m])
+            rows.append(torch.from_numpy(base[g_of * M + m] + np.arange(len(g_of)) - start[g_of]).to(device))
+        n_rows = int(base[-1])
+        f32 = lambda t: t.detach().to(device, torch.float32)
+        px = torch.empty((n_rows, self.n_dims), dtype=torch.float32, device=device)
+        poh = torch.empty((n_rows, self.residue_nf), dtype=torch.float32, device=device)
+        for r, q in zip(rows, pockets):
+            if len(q['x']) != len(r):
+                raise ValueError("a pocket's x does not have sum(size) rows")
+            px[r], poh[r] = f32(q['x']), f32(q['one_hot'])
+        self.refresh_learned_schedule()
+        h = self.dynamics.hip_handle()
+        h.set_layout(np.repeat(nph, M), sizes.reshape(-1))
+        h.set_step_table(timesteps, self.step_table(timesteps))
+        phar_mask = utils.num_nodes_to_batch_mask(G, torch.as_tensor(nph), device)
+        if noise is not None:
+            noise = noise.detach().to(device, torch.float32).contiguous()
+        if seed is None:
+            seed = fresh_seed()
+        run = lambda: h.multi_pocket_chain(px, poh, [M] * G, w.reshape(-1), timesteps, noise=noise, seed=seed, group_ids=group_ids,
+                                           want_steps=return_frames > 1, use_graph=self.use_hip_graph)
+        out = self._finish_chain(h, run, self.inpaint_frames(1, 1, timesteps, return_frames), return_frames)
+        return out[0], [out[1][..., r, :] for r in rows], phar_mask, [q['mask'] for q in pockets]
+
     @torch.no_grad()
     def inpaint(self, phar, pocket, phar_fixed, resamplings=1, jump_length=1, return_frames=1, timesteps=None,
                 noise=None, seed=None, pocket_ids=None):
@@ -431,3 +517,7 @@ class SimpleConditionalDDPM(ConditionalDDPM):
     def score(self, *args, **kwargs):
         raise NotImplementedError('score is not implemented for SimpleConditionalDDPM (the scoring chain projects every level to the '
                                   'centre-of-mass-free subspace); use ConditionalDDPM')
+
+    def sample_given_pockets(self, *args, **kwargs):
+        raise NotImplementedError('sample_given_pockets is not implemented for SimpleConditionalDDPM (no centre-of-mass projection: the '
+                                  'shared latent has no frame of its own); use ConditionalDDPM')

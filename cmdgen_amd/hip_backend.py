@@ -58,6 +58,8 @@ SYMBOLS = [
     ('cmdgen_debug_noise', C.c_int, [_vp, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _fp, _vp]),
     ('cmdgen_sample_chain', C.c_int, [_vp, _fp, _fp, C.c_int32, _fp, C.c_uint64, _i64p, _fp, _fp, _fp, _fp,
                                       C.c_int32, _vp]),
+    ('cmdgen_multi_pocket_chain', C.c_int, [_vp, _fp, _fp, C.c_int64, _i64p, _vp, C.c_int32, _fp, C.c_uint64, _i64p, _fp, _fp, _fp, _fp,
+                                            C.c_int32, _vp]),
     ('cmdgen_joint_chain', C.c_int, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int64,
                                      C.c_uint64, _i64p, _fp, _fp, _fp, C.c_int32, _vp]),
     ('cmdgen_joint_plan', C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i64p, _i64p]),
@@ -244,6 +246,7 @@ class Handle:
                             'cmdgen_set_layout')
             self._layout_key = key
         self.batch, self.n_phar, self.n_pocket = len(a), int(a.sum()), int(b.sum())
+        self.num_phar_host = a
 
     # ---- one evaluation
     def dynamics_forward(self, xh_phar, xh_pocket, t, want_pocket: bool = True):
@@ -344,6 +347,45 @@ class Handle:
             self.h, _ptr(pocket_x), _ptr(pocket_onehot), int(timesteps), _ptr(noise), C.c_uint64(seed & (2 ** 64 - 1)),
             self._pocket_ids(pocket_ids), _ptr(xh_phar), _ptr(xh_pocket),
             _ptr(z_steps), _ptr(p_steps), int(bool(use_graph)), self._stream()), 'cmdgen_sample_chain')
+        return xh_phar, xh_pocket, z_steps
+
+    MAX_GROUP = 8                    # include/cmdgen_hip.h: CMDGEN_MAX_GROUP
+
+    def multi_pocket_chain(self, pocket_x, pocket_onehot, group_sizes: Sequence[int], weights, timesteps: int, noise=None,
+                           seed: int = 0, group_ids: Optional[Sequence[int]] = None, want_steps: bool = False, use_graph: bool = True):
+        """One pharmacophore per GROUP of pockets (cmdgen_multi_pocket_chain): the layout's samples are the groups' members, group g the
+        next group_sizes[g] consecutive samples (equal n_phar; their pockets in one common frame), weights [batch] one per member (each
+        group's summing to 1).  noise [K+2, Nu, 3+P] or None, Nu = one copy of the phar rows per group; group_ids: the global group ids
+        of the Philox draws (None: 0 .. groups - 1).  -> (xh_phar [Nu, 3+P], xh_pocket [Np, 3+R], z_steps [K, Nu, 3+P] or None) like
+        sample_chain; with want_steps every member's pocket after every op is left in last_pocket_steps."""
+        import torch
+        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
+        dev = pocket_x.device
+        self._check_dev(pocket_x, (self.n_pocket, 3))
+        self._check_dev(pocket_onehot, (self.n_pocket, R))
+        sizes = np.ascontiguousarray(np.asarray(group_sizes, dtype=np.int64))
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32))
+        assert sizes.ndim == 1 and len(sizes) >= 1 and w.shape == (self.batch,), (sizes.shape, w.shape, self.batch)
+        # one copy of the rows per group: n_phar of every group's first member (the library checks the grouping itself; a grouping
+        # it will refuse only has to give SOME buffer size here)
+        firsts = np.minimum(np.concatenate([[0], np.cumsum(sizes)[:-1]]), self.batch - 1)
+        n_unique = int(self.num_phar_host[firsts].sum())
+        if noise is not None:
+            self._check_dev(noise, (timesteps + 2, n_unique, 3 + P))
+        ids = None
+        if group_ids is not None:
+            ids_arr = np.ascontiguousarray(np.asarray(group_ids, dtype=np.int64))
+            assert len(ids_arr) == len(sizes)
+            ids = ids_arr.ctypes.data_as(_i64p)
+        xh_phar = torch.empty((n_unique, 3 + P), dtype=torch.float32, device=dev)
+        xh_pocket = torch.empty((self.n_pocket, 3 + R), dtype=torch.float32, device=dev)
+        z_steps = torch.empty((timesteps, n_unique, 3 + P), dtype=torch.float32, device=dev) if want_steps else None
+        p_steps = torch.empty((timesteps, self.n_pocket, 3), dtype=torch.float32, device=dev) if want_steps else None
+        self.last_pocket_steps = p_steps
+        self._check(self.lib.cmdgen_multi_pocket_chain(
+            self.h, _ptr(pocket_x), _ptr(pocket_onehot), len(sizes), sizes.ctypes.data_as(_i64p), w.ctypes.data_as(C.c_void_p),
+            int(timesteps), _ptr(noise), C.c_uint64(seed & (2 ** 64 - 1)), ids, _ptr(xh_phar), _ptr(xh_pocket),
+            _ptr(z_steps), _ptr(p_steps), int(bool(use_graph)), self._stream()), 'cmdgen_multi_pocket_chain')
         return xh_phar, xh_pocket, z_steps
 
     def joint_plan(self, timesteps: int, resamplings: int = 1, jump_length: int = 1, inpaint: bool = True):

@@ -339,6 +339,48 @@ class PharPocketDDPM(nn.Module):
                 phar_to_coords.setdefault(f'Molecule_{k}', {}).setdefault(name, []).append(coords)
         return phar_to_coords
 
+    def generate_phars_multi(self, pdb_files, n_samples, pocket_ids=None, ref_ligands=None, num_nodes_phar=None, weights=None,
+                             timesteps=None, **kwargs):
+        """Generate pharmacophore point clouds for SEVERAL pockets at once - the two targets of a dual-target design, or
+        conformations of one receptor (ConditionalDDPM.sample_given_pockets): every sample is one point cloud drawn from a chain
+        that sees all the pockets.
+
+        pdb_files: one PDB file per pocket.  The files must ALREADY be superposed into one common frame; nothing here aligns
+        them (the reference's get_phar/point_dultarget*.py scripts superpose their two point clouds with a Kabsch step AFTER
+        sampling each target alone - do that step on the structures first).  pocket_ids: per file a list of residues
+        '<chain>:<resi>', or ref_ligands: per file a '<chain>:<resi>' ligand, as generate_phars takes one of them.
+        num_nodes_phar: points per sample, default the size prior given the FIRST pocket.  weights: None (uniform) or one
+        weight per file, >= 0 (normalised to sum 1).  seed / noise go to the sampler.  Everything is moved back by the first
+        pocket's shift, so the points come out in the common frame.  -> the phar_to_coords dict of generate_phars."""
+        pdb_files = list(pdb_files)
+        M = len(pdb_files)
+        assert (pocket_ids is None) ^ (ref_ligands is None)
+        if len(pocket_ids if pocket_ids is not None else ref_ligands) != M:
+            raise ValueError(f'{M} pdb_files need {M} entries of pocket_ids or ref_ligands (one per file)')
+        if not isinstance(self.ddpm, ConditionalDDPM):
+            raise NotImplementedError('generate_phars_multi needs the conditional model (mode pocket_conditioning)')
+        sampler_kw = {k: kwargs.pop(k) for k in ('noise', 'seed', 'group_ids') if k in kwargs}
+        pockets = [self._pdb_pocket(f, n_samples, pocket_ids[m] if pocket_ids is not None else None,
+                                    ref_ligands[m] if ref_ligands is not None else None) for m, f in enumerate(pdb_files)]
+        first = pockets[0]
+        pocket_com_before = _scatter_mean(first['x'], first['mask'], n_samples)
+        if num_nodes_phar is None:
+            num_nodes_phar = self.ddpm.size_distribution.sample_conditional(n1=None, n2=first['size'])
+        xh_phar, xh_pockets, phar_mask, pocket_masks = self.ddpm.sample_given_pockets(
+            pockets, num_nodes_phar, weights=weights, timesteps=timesteps, **sampler_kw)
+        # move the generated points back by the first pocket's shift (every pocket was translated by the same vector)
+        pocket_com_after = _scatter_mean(xh_pockets[0][:, :self.x_dims], pocket_masks[0], n_samples)
+        xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
+        phar_mask = phar_mask.cpu()
+        x = xh_phar[:, :self.x_dims].detach().cpu()
+        phar_type = xh_phar[:, self.x_dims:].argmax(1).detach().cpu()
+        phar_to_coords = {}
+        for coords_batch, types in zip(utils.batch_to_list(x, phar_mask), utils.batch_to_list(phar_type, phar_mask)):
+            names = [self.dataset_info['phar_decoder'][int(t)] for t in types]
+            for k, (name, coords) in enumerate(zip(names, coords_batch), start=1):
+                phar_to_coords.setdefault(f'Molecule_{k}', {}).setdefault(name, []).append(coords)
+        return phar_to_coords
+
     def _phar_with_given_rows(self, points, arg, n_samples, num_nodes_phar, pocket):
         """The phar batch of inpaint_phars / edit_phars: `points` = [(type name, (x, y, z))] are the first rows of every sample, the
         other rows zero.  num_nodes_phar: points per sample, default the size prior given the pocket, at least len(points).

@@ -212,6 +212,44 @@ int cmdgen_sample_chain(cmdgen_handle* h, const float* pocket_x, const float* po
                         float* xh_phar_out, float* xh_pocket_out, float* z_steps_out,
                         float* pocket_steps_out, int32_t use_graph, cmdgen_stream stream);
 
+/* One pharmacophore for SEVERAL pockets (ConditionalDDPM.sample_given_pockets): cmdgen_sample_chain's chain with one latent z per
+ * GROUP of pocket contexts - two targets of a dual-target design, or several conformations of one receptor.  At every op the
+ * eps-predictions of the group's contexts are combined with weights, the score of the weighted geometric mixture of the per-pocket
+ * distributions.  The layout (cmdgen_set_layout) holds the B = sum_g M_g MEMBER samples: the members of group g are the consecutive
+ * samples first[g] .. first[g] + M_g - 1, all with the same n_phar; their pockets differ freely in size and composition and are
+ * given in ONE common frame (superposing them is the caller's business).  Nu = sum_g n_phar[g] counts one copy of the rows per group.
+ * In the normalised space, with P_m the pocket of member m, w_m its weight and sums over m ascending:
+ *   Init    c = sum_m w_m com(P_m);  z = [c, 0] + xi_0;  shift = com(z.x);  z.x -= shift and every P_m.x -= shift;  the mean-zero check.
+ *   Op t->s eps_m = the phar output of the ordinary evaluation of (z, P_m, t), its x columns zero when the (batch-wide) NaN guard is set;
+ *           eps_bar = sum_m w_m eps_m;  mu = z / alpha_ts - c_eps eps_bar;  z' = mu + sigma xi;  shift = com(z'.x);
+ *           z'.x -= shift and every P_m.x -= shift.  The scalars are the step table's (cmdgen_set_step_table), as cmdgen_sample_chain.
+ *   Final   eps_bar at t = 0;  x = (z - sigma_0 eps_bar) / alpha_0 + sigma_x xi;  the COM is removed from x and every P_m;  types =
+ *           argmax of z_0;  unnormalise;  the CoG-drift re-centring is batch-wide as in cmdgen_sample_chain.
+ * The shared latent stays COM-free and every pocket carries its own translated copy of the frame.  With every M_g = 1 this is
+ * cmdgen_sample_chain, bit for bit.
+ *   pocket_x, pocket_onehot  as cmdgen_sample_chain, the rows of the B member samples in layout order
+ *   n_groups, group_size_host int64 [n_groups]: M_g in 1 .. CMDGEN_MAX_GROUP, summing to the layout's batch
+ *   weight_host   float [batch], one per member: >= 0, finite, each group's summing to 1 within 1e-5 (the caller normalises)
+ *   noise  dev [K+2][Nu][3+phar_nf] or NULL: ONE draw per group and op, in cmdgen_sample_chain's order (draw 0: xi_0, 1 + i: op i,
+ *          1 + K: the decode); all members of a group use the same numbers.
+ *   Device draws (noise == NULL): Philox keyed by (seed, global GROUP id, draw, node of the group) with those draw counters -
+ *          cmdgen_debug_noise(seed, group id, draw, n_phar, ...) returns the same numbers.
+ *   group_ids_host  host [n_groups] global group ids for the Philox key (NULL: 0 .. n_groups-1)
+ *   xh_phar_out dev [Nu][3+phar_nf];  xh_pocket_out dev [Np][3+residue_nf]: every member's translated pocket;
+ *   z_steps_out dev [K][Nu][3+phar_nf] or NULL;  pocket_steps_out dev [K][Np][3] or NULL: as cmdgen_sample_chain
+ * One op is one launch (k_multi_step_count: one workgroup per member, each with its own copy of z - no float atomics, no
+ * synchronisation between workgroups) plus the evaluation; with use_graph the step is captured and replayed like the other chains, and
+ * a changed grouping or weight prepares the chain's slot again.
+ * Refused: n_phar unequal inside a group, sizes that do not sum to the batch or lie outside 1 .. CMDGEN_MAX_GROUP, a negative or
+ * non-finite weight, a group whose weights do not sum to 1, the joint model and no_com_projection handles (SimpleConditionalDDPM).
+ * Asynchronous on `stream`; cmdgen_chain_status reports this run's checks, drift and NaN resets. */
+#define CMDGEN_MAX_GROUP 8
+int cmdgen_multi_pocket_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
+                              int64_t n_groups, const int64_t* group_size_host, const float* weight_host,
+                              int32_t timesteps, const float* noise, uint64_t seed, const int64_t* group_ids_host,
+                              float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                              int32_t use_graph, cmdgen_stream stream);
+
 /* The JOINT model's loops (config.update_pocket_coords = 1), return_frames=1:
  *   phar_fixed == NULL && pocket_fixed == NULL: EnVariationalDiffusion.sample (en_diffusion.py:576-647) -
  *       phar AND pocket nodes start from noise; phar_x/phar_onehot/pocket_x/pocket_onehot are ignored (may be NULL).
