@@ -304,7 +304,7 @@ static const size_t kEdgeLdsMax = 156 * 1024;      // 160 KiB per CU minus k_edg
 PlanInput plan_input(const cmdgen_handle* h) {
     PlanInput in;
     const Dims& d = h->dims;
-    in.H = d.H; in.L = d.L; in.S = d.S; in.joint = d.joint != 0; in.sin = d.sin != 0; in.cutoff = d.cutoff2 >= 0.f;
+    in.H = d.H; in.L = d.L; in.S = d.S; in.dyn = d.dyn; in.joint = d.joint != 0; in.sin = d.sin != 0; in.cutoff = d.cutoff2 >= 0.f;
     in.n_cus = h->n_cus; in.gemm_split = h->gemm_split;
     in.B = (int)h->cur_nphar.size(); in.nph = h->cur_nphar.data(); in.npk = h->cur_npocket.data();
     in.N = h->lay.N; in.Nl = h->lay.Nl; in.max_n = h->lay.max_n;
@@ -494,7 +494,7 @@ EvalLaunch make_launch(cmdgen_handle* h) {
 // ---------------------------------------------------------------------------------
 static const char* const kOptionKeys[] = {
     "node_mt", "edge_mt", "coord_mt", "embed_mt", "edge_wgs_per_cu", "coord_wgs_per_cu", "e128_wgs_per_cu", "e128_fused", "half_engine", "edge_fullk", "node64", "node16_split", "node16w",
-    "proj_in_coord", "embed_mfma", "dead_skip", "write_embed", "graph_steps",
+    "proj_in_coord", "embed_mfma", "readout_in_coord", "dead_skip", "write_embed", "graph_steps",
     "wgrad_split", "wgrad_tile", "wgrad_split_wgs128", "wgrad_split_wgs64", "wgrad_wgs", "dgrad_mt", "dgrad_tail", "wgrad_stream", "train_half", "wgrad_silu", "train_node16", "wgrad_k128"};
 
 static void drop_graphs(cmdgen_handle* h) {
@@ -877,17 +877,26 @@ extern "C" int cmdgen_sample_chain(cmdgen_handle* h, const float* pocket_x, cons
     // One denoising step = the posterior update fused with pass 1 of the next radius graph (k_step_count), then the
     // evaluation at the new state: pass 2 of the graph (k_edge_write), k_embed, the L blocks,
     // k_readout.  The chain is: evaluation 0, K x (step + evaluation), decode.
+    // Where the plan says so (LaunchPlan::readout_in_coord) the evaluations run without k_readout: its feature part rides in the last coordinate
+    // launch, k_step_count forms the velocity and the NaN flag it consumes itself, and k_vel_flag does so once in front of the decode.
+    a.plain_chain = 1;
+    const int own_vel = readout_mode(a, c.state, nullptr, nullptr, nullptr);     // (what the evaluations below are launched with)
     EvalLaunch a2 = a;
     a2.skip_count = 1;                               // (pass 2 of the graph on a side stream was measured and dropped: the fork / join costs ~23 us per
                                                      // step inside the replayed graph, far more than the 10 us it hides; profiles/r02_b_step_fusion.txt)
     cmdgen_launch_eval(a, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, s, nullptr);   // evaluation 0 (t = 1)
+    // (a step kernel that leaves X0 / ACC to an evaluation that does not take them over would leave stale positions without any error)
+    // (evaluation 0 is already queued when this returns: the chain is abandoned half issued, the handle stays usable - the next chain of any
+    // kind starts again from k_chain_init and k_edge_count, which rewrite everything this one left behind)
+    if (a.readout_used != own_vel) return fail(h, CMDGEN_ESTATE, "the evaluation and the step kernel disagree on readout_in_coord (%d, %d)", a.readout_used, own_vel);
     const void* key[6] = {noise, z_steps_out, pocket_steps_out, nullptr, nullptr, s};
     rc = run_steps(h, k, key, seed, K, use_graph, s, [&](hipStream_t ss) {
-        cmdgen_launch_step_count(h->lay, d, c, h->work, h->work.eps_tmp, ss);
+        cmdgen_launch_step_count(h->lay, d, c, h->work, h->work.eps_tmp, own_vel, ss);
         cmdgen_launch_eval(a2, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, ss, nullptr);
     });
     if (rc) return rc;
     // final p(x, h | z0): the last evaluation above ran at t = 0 (coef[K].w); decode
+    if (own_vel) cmdgen_launch_vel_flag(a, h->work.eps_tmp, s);
     cmdgen_launch_chain_final(h->lay, d, c, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, k.cog, s);
     return end_chain(h, caller, s);
 }

@@ -114,3 +114,21 @@ static int cp_grid(int n_coord, int N) {
     }
     return grid;
 }
+
+// k_coord_readout: the LAST block's coordinate launch (no next block to project for) with the feature part of the readout as its second role
+// (LaunchPlan::readout_in_coord).  Workgroups [0, n_coord) are k_edge_coord<256, 32, false, true, NPL>'s, as above; each one behind them owns one
+// readout tile of RO_ROWS phar rows (readout_features, cmdgen_egnn_common.h: k_readout's arithmetic by construction).  The roles share nothing: the
+// readout role reads h as the last node launch left it and writes columns 3 .. 3 + P of the eps rows; the velocity columns and the NaN flag need
+// THIS launch's coordinate sums and are formed by their consumer (k_step_count, k_vel_flag).  The first readout workgroup counts the evaluation
+// (ChainState::step: read by embed_body and the step kernels, never by the last block's launches).
+struct alignas(16) ReadoutLds { float hrow[RO_ROWS * NW_H]; float wT[NW_H * PLAN_READOUT_DYN_MAX]; ReadoutSmall s; };
+__global__ __launch_bounds__(256, 3) void k_coord_readout(Layout lay, Work w, Dims d, LayerW lw, SmallW sw, int layer, int n_coord,
+                                                          float* __restrict__ eps_phar, ChainState* chain) {
+    union alignas(16) Both { EdgeLds<NW_H, 32, NPL> c; ReadoutLds r; };
+    __shared__ Both L;
+    static_assert(sizeof(Both) <= 160 * 1024 / 3, "three workgroups per CU, as k_coord_proj");
+    const int bid = (int)blockIdx.x;
+    if (bid < n_coord) { edge_coord_body<NW_H, 32, false, true, NPL>(L.c, lay, w, d, lw, layer, TrainSave{}, n_coord); return; }
+    if (bid == n_coord && threadIdx.x == 0) chain->step += 1;
+    readout_features(L.r.hrow, L.r.wT, L.r.s, lay, w, d, sw, eps_phar, nullptr, TrainSave{}, bid - n_coord);
+}

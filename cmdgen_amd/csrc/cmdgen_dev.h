@@ -132,9 +132,28 @@ struct Work {                   // per-layout workspace; all pointers device
 // divisor of node n's segment sums (egnn_new.py:277-292): normalization_factor ('sum'), or the receiver's edge count ('mean')
 __device__ __forceinline__ float agg_div(const Work& w, const Dims& d, int n) { return d.agg_mean ? w.adiv[n] : d.norm_factor; }
 
+// velocity of moving node n once the last block's coordinate launch is done (dynamics.py:126-127): x_final = X[L-1] + ACC[L-1] / divisor,
+// vel = x_final - x_input.  ONE expression for every kernel that forms it (k_readout, k_vel_flag and the step kernel that computes it for itself:
+// LaunchPlan::readout_in_coord); only divisions, additions and subtractions, so the translation units' contraction settings cannot tell it apart.
+// (in two halves, so a kernel can request the operands of several rows before it needs the first result)
+struct VelIn { float4 p, a, x0; float dv; };
+__device__ __forceinline__ VelIn readout_vel_in(const Layout& lay, const Work& w, const Dims& d, int n) {
+    VelIn v;
+    v.p = (d.L == 1) ? w.X0[n] : w.XL[(size_t)(d.L - 1) * lay.Nm + n];
+    v.a = w.ACC[(size_t)(d.L - 1) * lay.Nm + n];
+    v.x0 = w.X0[n];
+    v.dv = agg_div(w, d, n);
+    return v;
+}
+__device__ __forceinline__ float4 readout_vel_of(const VelIn& v) {
+    return make_float4((v.p.x + v.a.x / v.dv) - v.x0.x, (v.p.y + v.a.y / v.dv) - v.x0.y, (v.p.z + v.a.z / v.dv) - v.x0.z, 0.f);
+}
+__device__ __forceinline__ float4 readout_vel(const Layout& lay, const Work& w, const Dims& d, int n) { return readout_vel_of(readout_vel_in(lay, w, d, n)); }
+__device__ __forceinline__ bool vel_isnan(const float4& v) { return isnan(v.x) || isnan(v.y) || isnan(v.z); }
+
 struct ChainState {             // device-resident denoising-loop state
     int step;                   // evaluations completed so far = index into coef[] of the NEXT evaluation; bumped by
-                                // k_readout (which does not read it), so no kernel reads it while it changes: the
+                                // k_readout or the readout role of k_coord_readout (which do not read it), so no kernel reads it while it changes: the
                                 // evaluation kernels of step e read e, the sampler kernel that follows reads step - 1
     int K;                      // posterior steps
     int pad0, pad1;
@@ -253,7 +272,17 @@ struct EvalLaunch {             // everything one evaluation's launches need (ho
     mutable int frag_launches = 0;   // tile launches of this evaluation that read the fp32 FRAGMENT packs (the generic k_edge_msg / k_node / k_edge_coord forms): the training step re-packs those only when one will run
     mutable int live_thr = 0;   // set around a block's launches when that applies: nodes within this many hops of a moving node are still read
     mutable int proj_now = 0;   // plan.proj_in_coord and this evaluation does so (launch_eval: not a training forward, no parity stop, no per-stage events)
+    int plain_chain = 0;        // the evaluation belongs to cmdgen_sample_chain: its step kernel can form the velocity itself (readout_mode below)
+    mutable int readout_now = 0;   // readout_mode() of the evaluation being issued (launch_eval)
+    mutable int readout_used = 0;  // ... of the evaluation issued last: the chain driver checks it against the mode it gave its step kernel
 };
+// LaunchPlan::readout_in_coord for this evaluation: the last block's coordinate launch carries the feature part of k_readout, pass 2 of the radius
+// graph takes X0 / ACC over from the step kernel, and the velocity and the NaN flag are formed by their consumer (k_step_count, k_vel_flag).
+// The plain conditional sampling chain's whole evaluations only.  ONE function for launch_eval and for the chain driver that picks the step kernel's
+// form: both pass what the evaluation is launched with (its chain state, time array, pocket output and per-stage events).
+inline int readout_mode(const EvalLaunch& a, const ChainState* chain, const float* t_arr, const float* eps_pocket, const hipEvent_t* ev) {
+    return a.plan.readout_in_coord && a.plain_chain && !a.save && a.stop_block < 0 && chain && !t_arr && !eps_pocket && !ev ? 1 : 0;
+}
 // weight unit of block l's launches (EvalLaunch::unit), and the has_next argument of its node kernel: bit 0 = another unit follows
 // (its P | Q are projected), bits 1..28 = the dead-tile threshold of the plane tiles, bit 29 = the coordinate launch projects the next unit's
 // P | Q (EvalLaunch::proj_now: k_node16w leaves them out), bit 30 = no P_c | Q_c (EvalLaunch::skip_pc)

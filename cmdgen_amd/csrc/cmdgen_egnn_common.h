@@ -72,6 +72,74 @@ __device__ __forceinline__ float4 node_pos(const Layout& lay, const Work& w, con
     return make_float4(p.x + a.x / dv, p.y + a.y / dv, p.z + a.z / dv, 0.f);
 }
 
+// ------------------------------------------------------------------------------------
+// The feature part of the readout for one tile of RO_ROWS nodes (egnn_new.py:205, dynamics.py:110-124): embedding_out (the time column
+// dropped), decoder layer 0 + SiLU, decoder layer 2 into columns 3.. of the eps rows.  32 threads per node; the node's h row is staged in
+// s_hrow [RO_ROWS][H], the transposed weight in s_wT [H][dyn] (read coalesced).  ONE function for k_readout and for the readout role of
+// k_coord_readout (kernels_coord_proj.hip), so both give the same bits: four interleaved accumulators over k combined as (s0 + s1) + (s2 + s3),
+// the decoders one fmaf chain from the bias with k ascending.  256 threads; ends without a barrier (nothing reads its LDS afterwards).
+// ------------------------------------------------------------------------------------
+constexpr int RO_ROWS = 8;
+struct ReadoutSmall { float j[RO_ROWS][CMDGEN_MAX_SMALL + 1]; float h1[RO_ROWS][CMDGEN_MAX_SMALL]; };
+__device__ __forceinline__ void readout_features(float* __restrict__ s_hrow, float* __restrict__ s_wT, ReadoutSmall& S, const Layout& lay, const Work& w,
+                                                 const Dims& d, const SmallW& sw, float* __restrict__ eps_phar, float* __restrict__ eps_pocket,
+                                                 const TrainSave& sv, const int tile) {
+    const int tid = threadIdx.x, g = tid >> 5, l32 = tid & 31;
+    const int nnodes = eps_pocket ? lay.N : lay.Nl;
+    const int n = tile * RO_ROWS + g;
+    const bool live = n < nnodes;
+    const bool ph = n < lay.Nl;
+    const int H = d.H;
+    for (int i = tid; i < H * d.dyn; i += 256) s_wT[i] = sw.embo_wT[i];        // coalesced, all loads in flight
+    if (live) for (int k = l32; k < H; k += 32) s_hrow[g * H + k] = w.h[(size_t)n * H + k];
+    __syncthreads();
+    if (live) {
+        for (int j = l32; j < d.J; j += 32) {
+            float s0 = sw.embo_b[j], s1 = 0.f, s2 = 0.f, s3 = 0.f;
+            const float* hr = s_hrow + g * H;
+            const float* wt = s_wT + j;
+            for (int k = 0; k < H; k += 4) {
+                s0 = fmaf(hr[k], wt[k * d.dyn], s0);
+                s1 = fmaf(hr[k + 1], wt[(k + 1) * d.dyn], s1);
+                s2 = fmaf(hr[k + 2], wt[(k + 2) * d.dyn], s2);
+                s3 = fmaf(hr[k + 3], wt[(k + 3) * d.dyn], s3);
+            }
+            S.j[g][j] = (s0 + s1) + (s2 + s3);
+            if (sv.hfin) sv.hfin[(size_t)n * d.dyn + j] = S.j[g][j];
+        }
+    }
+    __syncthreads();
+    if (live) {
+        const int F = ph ? d.P : d.R;
+        const float* W0 = ph ? sw.pd0_w : sw.rd0_w; const float* B0 = ph ? sw.pd0_b : sw.rd0_b;
+        for (int o = l32; o < 2 * F; o += 32) {
+            float s = B0[o];
+            for (int k = 0; k < d.J; ++k) s = fmaf(S.j[g][k], W0[(size_t)o * d.J + k], s);
+            const float a = silu_f(s);
+            S.h1[g][o] = a;
+            if (sv.dec1) {
+                if (ph) { sv.dec1[(size_t)n * 2 * F + o] = s; sv.deca[(size_t)n * 2 * F + o] = a; }
+                else if (sv.qdec1) { sv.qdec1[(size_t)(n - lay.Nl) * 2 * F + o] = s; sv.qdeca[(size_t)(n - lay.Nl) * 2 * F + o] = a; }
+            }
+        }
+    }
+    __syncthreads();
+    if (live) {
+        const int F = ph ? d.P : d.R;
+        const float* W2 = ph ? sw.pd2_w : sw.rd2_w; const float* B2 = ph ? sw.pd2_b : sw.rd2_b;
+        float* out = ph ? eps_phar + (size_t)n * (3 + d.P) : eps_pocket + (size_t)(n - lay.Nl) * (3 + d.R);
+        for (int o = l32; o < F; o += 32) {
+            float s = B2[o];
+            for (int k = 0; k < 2 * F; ++k) s = fmaf(S.h1[g][k], W2[(size_t)o * 2 * F + k], s);
+            out[3 + o] = s;
+            if (sv.dec_out) {
+                if (ph) sv.dec_out[(size_t)n * F + o] = s;
+                else if (sv.qdec_out) sv.qdec_out[(size_t)(n - lay.Nl) * F + o] = s;
+            }
+        }
+    }
+}
+
 // A-tile generation shared by the two edge kernels:
 //   a1[e][:] = SiLU(P[row_e] + Q[col_e] + w_r * radial_e + w_d * d0_e)     (b folded into P)
 // which equals SiLU(W1 [h_row | h_col | radial | d0] + b1) of egnn_new.py:33-36 / :89-93.

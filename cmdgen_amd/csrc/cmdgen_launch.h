@@ -9,6 +9,7 @@
 void cmdgen_launch_eval(const EvalLaunch& a, const float* xh_phar, const float* xh_pocket, const float* t_arr, const float4* coef,
                         ChainState* chain, float* eps_phar, float* eps_pocket, hipStream_t s, hipEvent_t* ev);
 void cmdgen_launch_nan_fix(const EvalLaunch& a, float* eps_phar, hipStream_t s);
+void cmdgen_launch_vel_flag(const EvalLaunch& a, float* eps_phar, hipStream_t s);     // velocity columns + NaN flag alone, in front of the decode (readout_mode)
 void cmdgen_launch_save_positions(const EvalLaunch& a, float4* X, hipStream_t s);
 void cmdgen_readout_allow_lds(size_t bytes);            // k_readout's dynamic LDS above the 64 KiB default (hidden_nf 512)
 
@@ -18,7 +19,7 @@ void cmdgen_build_pocket_cache(const EvalLaunch& a, const float* xh_phar, const 
                                float* c, float* P0, float* Q0, float* dh, float* dP, float* dQ, hipStream_t s);
 void cmdgen_edge_kernels_allow_lds(size_t bytes);       // hipFuncSetAttribute above the 64 KiB default
 void cmdgen_launch_edge_count(const EvalLaunch& a, const float* xh_phar, const float* xh_pocket, hipStream_t s);
-void cmdgen_launch_edge_write(const EvalLaunch& a, hipStream_t s);
+void cmdgen_launch_edge_write(const EvalLaunch& a, const float* x0_from /* null, or the phar rows pass 2 copies into X0 (readout_mode) */, hipStream_t s);
 
 // per-family launch entry points (each picks the instantiation for a.d.H and the launch's tile rows); the *_hx forms are the same
 // families at the hidden sizes other than 256, built as translation units of their own (kernels_egnn_*_hx.hip, CMDGEN_H_PART)
@@ -42,9 +43,11 @@ void cmdgen_launch_msg128(const EvalLaunch& a, int l, hipStream_t s);         //
 void cmdgen_launch_coord128(const EvalLaunch& a, int l, hipStream_t s);
 void cmdgen_launch_coord_proj(const EvalLaunch& a, int l, hipStream_t s);     // kernels_coord_proj.hip: the 32-row full-K coordinate tiles + the next block's P | Q tiles in one launch (EvalLaunch::proj_now)
 
+void cmdgen_launch_coord_readout(const EvalLaunch& a, int l, float* eps_phar, ChainState* chain, hipStream_t s);   // ... the same tiles + the readout's feature tiles: the LAST block (EvalLaunch::readout_now)
+
 // kernels_ddpm.hip: the conditional chain
 void cmdgen_launch_chain_init(const Layout& lay, const Dims& d, const ChainBuf& c, const float* px, const float* poh, hipStream_t s);
-void cmdgen_launch_step_count(const Layout& lay, const Dims& d, const ChainBuf& c, const Work& w, const float* eps, hipStream_t s);
+void cmdgen_launch_step_count(const Layout& lay, const Dims& d, const ChainBuf& c, const Work& w, const float* eps, int own_vel /* readout_mode */, hipStream_t s);
 void cmdgen_launch_chain_final(const Layout& lay, const Dims& d, const ChainBuf& c, const Work& w, const float* eps, float* xo, float* po,
                                unsigned int* cog, hipStream_t s);
 void cmdgen_launch_debug_noise(unsigned long long seed, long long pocket_id, int draw, int n_nodes, int width, float* out, hipStream_t s);

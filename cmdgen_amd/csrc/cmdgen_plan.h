@@ -21,8 +21,12 @@ struct PlanPacks {
     static PlanPacks of_uploaded(int in) { return PlanPacks{true, true, in % 128 == 0, in % 128 == 0}; }
 };
 
+// k_coord_readout stages embedding_out^T [H][dyn] in static LDS beside 8 node rows: with dyn <= 40 the workgroup stays under a third of a CU's 160 KB
+constexpr int PLAN_READOUT_DYN_MAX = 40;
+
 struct PlanInput {
     int H = 256, L = 1, S = 1;
+    int dyn = 0;                                         // joint_nf + condition_time: the leading dimension of embedding_out^T (0: not known - no readout_in_coord)
     bool joint = false, sin = false, cutoff = true;      // cutoff: a cutoff bounds the radial features
     int n_cus = 256;
     bool gemm_split = true;
@@ -52,6 +56,7 @@ struct LaunchPlan {
     // what cmdgen_query reports beside the above
     int gemm_split = 1, half_engine = 0, node16_split = 0, node64 = 0, node16w = 1, edge_fullk = 0, proj_in_coord = 0;
     int embed_mfma = 0;                                  // full-path 16-row embedding tiles of phar rows on the fp32 matrix instruction (embed_body)
+    int readout_in_coord = 0;                            // the plain sampling chain runs without k_readout: its feature part rides in the last block's coordinate launch (k_coord_readout)
     // training forward
     bool fwd_half = false, node_half = false;            // the two edge kernels / the node kernel run their half save form
     bool reads_frag = false;                             // a tile launch reads the fp32 fragment packs (the generic k_edge_msg / k_node / k_edge_coord forms)
@@ -263,6 +268,14 @@ inline LaunchPlan make_plan(const PlanInput& in) {
                      (p.node_eng == PlanEngine::half ? in.Wpq_e.wh16 : in.Wpq_e.ws16);
     p.proj_in_coord = can && in.opt("proj_in_coord", 1) != 0 ? 1 : 0;
     if (p.proj_in_coord) p.coord = CoordKernel::fullk32_proj;
+    // k_readout's feature part (embedding_out + the decoders of the phar rows) as tiles behind the LAST block's coordinate launch, the velocity and the
+    // batch-global NaN flag formed by their consumer (k_step_count, k_vel_flag): one launch less per step of the plain conditional sampling chain
+    // (launch_eval / readout_mode hold the per-evaluation conditions).  Only where that launch is the 32-row full-K tile (three workgroups per CU, mostly
+    // idle CUs), one GCL per block, the conditional model, samples the per-sample kernels run on four waves.
+    // Option "readout_in_coord": 0 never, 1 wherever that holds, unset: where it measured faster (profiles/readout_in_coord_ab.txt).
+    const bool can_ro = H == 256 && !in.joint && in.S == 1 && (p.coord == CoordKernel::fullk32 || p.coord == CoordKernel::fullk32_proj) &&
+                        in.dyn >= 1 && in.dyn <= PLAN_READOUT_DYN_MAX && in.max_n <= 128;
+    p.readout_in_coord = can_ro && in.opt("readout_in_coord", 1) != 0 ? 1 : 0;
     return p;
 }
 
@@ -272,7 +285,7 @@ inline bool plan_query(const LaunchPlan& p, const char* key, int64_t* value) {
         {"node_mt", p.node_mt}, {"edge_mt", p.edge_mt}, {"coord_mt", p.coord_mt}, {"edge_grid", p.edge_grid}, {"coord_grid", p.coord_grid},
         {"e128_fused", p.e128_fused}, {"gemm_split", p.gemm_split}, {"half_engine", p.half_engine}, {"node16_split", p.node16_split},
         {"node64", p.node64}, {"node16w", p.node16w}, {"proj_in_coord", p.proj_in_coord}, {"edge_fullk", p.edge_fullk}, {"dead_skip", p.dead_skip},
-        {"embed_mfma", p.embed_mfma},
+        {"embed_mfma", p.embed_mfma}, {"readout_in_coord", p.readout_in_coord},
         {"msg_mfmas_per_product", plan_mfmas_per_product(p.msg_eng)}, {"node_mfmas_per_product", plan_mfmas_per_product(p.node_eng)},
         {"coord_mfmas_per_product", plan_mfmas_per_product(p.coord_eng)}};
     for (const auto& k : keys) if (strcmp(k.key, key) == 0) { *value = k.v; return true; }

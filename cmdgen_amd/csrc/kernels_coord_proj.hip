@@ -7,6 +7,9 @@
 // node tile reads.  Here they run as independent tiles of 32 rows x 128 columns (a quarter of one projection's weights for twice the rows) beside
 // the coordinate launch, which at this size is the latency chain of a few tiles on mostly idle CUs.  No exchange between workgroups: both roles
 // read what earlier launches wrote.  Every P / Q element sees the MFMAs nw_gemm gave it, in the same order (cmdgen_coord_proj_body.h).
+//
+// k_coord_readout: the LAST block's coordinate launch has no next block to project for; in the plain sampling chain its second role is the feature
+// part of k_readout (embedding_out + the decoders of the phar rows), which depends on the last node launch alone - one launch less per step.
 #define CMDGEN_H_PART 2                 // edge_coord_body and its helpers only, no launchers
 #include "kernels_egnn_coord.hip"
 #include "cmdgen_split.h"
@@ -40,5 +43,19 @@ void cmdgen_launch_coord_proj(const EvalLaunch& a, int l, hipStream_t s) {
         const int grid = cp_bf3::cp_grid(cg, a.lay.N);
         if (a.pe_start) hipExtLaunchKernelGGL(cp_bf3::k_coord_proj, dim3(grid), dim3(256), 0, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d, lw, ln, l, cg);
         else hipLaunchKernelGGL(cp_bf3::k_coord_proj, dim3(grid), dim3(256), 0, s, a.lay, a.w, a.d, lw, ln, l, cg);
+    }
+}
+
+// launcher of the last block's coordinate launch with the readout tiles behind it (EvalLaunch::readout_now; the planner holds the conditions:
+// H = 256, the 32-row full-K coordinate tile, dyn <= PLAN_READOUT_DYN_MAX)
+void cmdgen_launch_coord_readout(const EvalLaunch& a, int l, float* eps_phar, ChainState* chain, hipStream_t s) {
+    const LayerW& lw = a.layers[unit_of(a, l)];
+    const int cg = a.plan.coord_grid, grid = cg + (a.lay.Nl + RO_ROWS - 1) / RO_ROWS;
+    if (a.plan.coord_eng == PlanEngine::half) {
+        if (a.pe_start) hipExtLaunchKernelGGL(cp_half::k_coord_readout, dim3(grid), dim3(256), 0, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d, lw, a.sw, l, cg, eps_phar, chain);
+        else hipLaunchKernelGGL(cp_half::k_coord_readout, dim3(grid), dim3(256), 0, s, a.lay, a.w, a.d, lw, a.sw, l, cg, eps_phar, chain);
+    } else {
+        if (a.pe_start) hipExtLaunchKernelGGL(cp_bf3::k_coord_readout, dim3(grid), dim3(256), 0, s, a.pe_start, a.pe_stop, 0, a.lay, a.w, a.d, lw, a.sw, l, cg, eps_phar, chain);
+        else hipLaunchKernelGGL(cp_bf3::k_coord_readout, dim3(grid), dim3(256), 0, s, a.lay, a.w, a.d, lw, a.sw, l, cg, eps_phar, chain);
     }
 }

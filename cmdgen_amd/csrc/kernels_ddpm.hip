@@ -159,35 +159,78 @@ __global__ __launch_bounds__(64) void k_chain_drift_fix(Layout lay, Dims d, floa
 // per denoising step.  256 threads per sample.  The sample's z is pulled into LDS with all loads in flight; the sums of
 // the step (COM check, centre of mass) walk LDS in node index order; the count pass is k_edge_count's (same dist2,
 // same ballots).
+// own_vel (readout_mode, cmdgen_dev.h: the evaluation ran without k_readout): nobody wrote the velocity columns of eps or the NaN flag.  The
+// workgroup forms the velocities of its sample's rows itself (readout_vel), and - the flag is batch-global (dynamics.py:129-131) - evaluates
+// the same expression for ALL Nl phar rows and ORs isnan over the workgroup: every workgroup reaches the same flag on its own, none learns
+// anything from another.  So nothing the scan reads (X0, XL, ACC, adiv) may change during this launch: X0 and ACC are left to pass 2 of the
+// radius graph (edge_write_body), the launch behind this one.
 // ------------------------------------------------------------------------------------------------------------
+// (a template parameter: the form without it stays the code it was)
+template <bool own_vel>
 __global__ __launch_bounds__(1024) void k_step_count(Layout lay, Dims d, ChainBuf c, Work w,
                                                     const float* __restrict__ eps) {
     extern __shared__ float4 s_pos[];               // [max_n] positions of the sample (phar first), then int sdeg[max_n], then z
     int* sdeg = reinterpret_cast<int*>(s_pos + lay.max_n);
     float* s_z = reinterpret_cast<float*>(sdeg + lay.max_n);      // [nl * ld]
+    float* s_vel = s_z + (size_t)lay.max_n * (3 + d.P);           // own_vel: [nl][3]
     __shared__ float s_mean[3];
+    __shared__ int s_bad[16];                                      // own_vel: per wave, did a lane see a NaN velocity?
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
     const int nl = lay.num_phar[b], np = lay.num_pocket[b], n = nl + np;
     const int pb = lay.phar_base[b], qb = lay.pocket_base[b];
     const int ld = 3 + d.P, ldq = 3 + d.R;
     const int step = c.state->step - 1;
     const float4 cf = c.coef[step];
-    const bool nan_reset = *w.nan_flag != 0;
     float* zg = c.z_phar + (size_t)pb * ld;
     const float* eg = eps + (size_t)pb * ld;
     const int cnt = nl * ld;
+    const int flag0 = own_vel ? 0 : *w.nan_flag;                  // (requested with the kernel's first scalar loads, as before)
+    // own_vel: the operands of the first four rows of this thread's share of the scan are requested here, in front of the kernel's first loads, and
+    // used behind them - one round trip for all of them (at 64 pockets of 15 points: the whole scan; the compiled kernel issues its 12 global_load_dwordx3
+    // - the w components are never used - back to back in front of the first s_waitcnt: 56 registers)
+    [[maybe_unused]] VelIn vin[4];
+    if constexpr (own_vel) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int r = tid + u * (int)blockDim.x;
+            if (r < lay.Nl) vin[u] = readout_vel_in(lay, w, d, r);
+        }
+    }
     for (int idx = tid; idx < cnt; idx += blockDim.x) s_z[idx] = zg[idx];
     // pocket coordinates of this sample: in flight while the step is computed
     for (int i = tid; i < np; i += blockDim.x) {
         const float* q = c.xh_pocket + (size_t)(qb + i) * ldq;
         s_pos[nl + i] = make_float4(q[0], q[1], q[2], 0.f);
     }
+    if constexpr (own_vel) {
+        int bad = 0;
+        auto take = [&](int r, const float4& v) {
+            bad |= vel_isnan(v) ? 1 : 0;
+            const int i = r - pb;
+            if (i >= 0 && i < nl) { s_vel[3 * i] = v.x; s_vel[3 * i + 1] = v.y; s_vel[3 * i + 2] = v.z; }
+        };
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int r = tid + u * (int)blockDim.x;
+            if (r < lay.Nl) take(r, readout_vel_of(vin[u]));
+        }
+        for (int r = tid + 4 * (int)blockDim.x; r < lay.Nl; r += (int)blockDim.x) take(r, readout_vel(lay, w, d, r));     // (more than 4 rows per thread)
+        const bool any = __ballot(bad != 0) != 0ull;
+        if (lane == 0) s_bad[wave] = any ? 1 : 0;
+    }
     __syncthreads();
+    bool nan_reset;
+    if constexpr (own_vel) {
+        int any = 0;
+        for (int k = 0; k < nwaves; ++k) any |= s_bad[k];
+        nan_reset = any != 0;
+    } else nan_reset = flag0 != 0;
     if (wave == 0 && !d.no_com) record_com_check(c.check + 2 * (1 + step), s_z, ld, 0, nl, 1.0f, lane);   // z_t, the step's input
     __syncthreads();
     for (int idx = tid; idx < cnt; idx += blockDim.x) {
         const int i = idx / ld, k = idx - i * ld;
-        float e = eg[idx];
+        float e = eg[idx];                          // (unconditional, so it is requested ahead of the barriers as before; own_vel: columns 0..2 are stale and unused)
+        if constexpr (own_vel) { if (k < 3) e = s_vel[3 * i + k]; }
         if (nan_reset && k < 3) e = 0.f;
         const float mu = s_z[idx] / cf.x - cf.y * e;
         s_z[idx] = mu + cf.z * draw(c, lay, 1 + step, b, i, pb + i, k, ld);
@@ -209,8 +252,10 @@ __global__ __launch_bounds__(1024) void k_step_count(Layout lay, Dims d, ChainBu
             float* z = s_z + i * ld;
             if (!d.no_com) { z[0] -= m0; z[1] -= m1; z[2] -= m2; }
             p = make_float4(z[0], z[1], z[2], 0.f);
-            w.X0[pb + i] = p;
-            for (int l = 0; l < d.L; ++l) w.ACC[(size_t)l * lay.Nm + pb + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (!own_vel) {         // (own_vel: other workgroups are reading both - pass 2 stores them from z_phar)
+                w.X0[pb + i] = p;
+                for (int l = 0; l < d.L; ++l) w.ACC[(size_t)l * lay.Nm + pb + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
         } else {
             p = s_pos[i];
             if (!d.no_com) {
@@ -270,16 +315,17 @@ __global__ __launch_bounds__(1024) void k_step_count(Layout lay, Dims d, ChainBu
 }
 
 // (The NaN flag this kernel reads is cleared for the next evaluation by k_edge_write, which runs after every reader
-// of the old value and before k_readout can set it again.)
+// of the old value and before k_readout - or k_vel_flag in front of the decode - can set it again.)
 
 void cmdgen_launch_chain_init(const Layout& lay, const Dims& d, const ChainBuf& c, const float* px,
                               const float* poh, hipStream_t s) {
     hipLaunchKernelGGL(k_chain_init, dim3(lay.B), dim3(64), 0, s, lay, d, c, px, poh);
 }
 void cmdgen_launch_step_count(const Layout& lay, const Dims& d, const ChainBuf& c, const Work& w,
-                              const float* eps, hipStream_t s) {
-    const size_t shm = (size_t)lay.max_n * (sizeof(float4) + sizeof(int)) + (size_t)lay.max_n * (3 + d.P) * sizeof(float);
-    hipLaunchKernelGGL(k_step_count, dim3(lay.B), dim3(lay.max_n > 128 ? 1024 : 256), shm, s, lay, d, c, w, eps);     // 16 waves for big samples (one receiver per wave at a time)
+                              const float* eps, int own_vel, hipStream_t s) {
+    const size_t shm = (size_t)lay.max_n * (sizeof(float4) + sizeof(int)) + (size_t)lay.max_n * (3 + d.P + (own_vel ? 3 : 0)) * sizeof(float);
+    if (own_vel) hipLaunchKernelGGL(k_step_count<true>, dim3(lay.B), dim3(lay.max_n > 128 ? 1024 : 256), shm, s, lay, d, c, w, eps);
+    else hipLaunchKernelGGL(k_step_count<false>, dim3(lay.B), dim3(lay.max_n > 128 ? 1024 : 256), shm, s, lay, d, c, w, eps);     // 16 waves for big samples (one receiver per wave at a time)
 }
 void cmdgen_launch_chain_final(const Layout& lay, const Dims& d, const ChainBuf& c, const Work& w,
                                const float* eps, float* xo, float* po, unsigned int* cog, hipStream_t s) {

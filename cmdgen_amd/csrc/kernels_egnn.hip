@@ -10,6 +10,7 @@
 //                  k_node       GCL.node_model, then P/Q for the coord MLP and block l+1
 //                  k_edge_coord EquivariantUpdate.coord_model          (egnn_new.py:87-104)
 //   k_readout      embedding_out, decoders, velocity, NaN flag       (dynamics.py:110-139)
+//                  (the plain sampling chain at small batches runs without it: LaunchPlan::readout_in_coord)
 //
 // Tiling: a workgroup owns MT rows (edges or nodes; MT = 64, 32 or 16, chosen per launch so
 // that even a 64-pocket batch spreads over all 256 CUs) and all H output columns; wave w owns
@@ -29,79 +30,31 @@ __global__ __launch_bounds__(256) void k_readout(Layout lay, Work w, Dims d, Sma
                                                  float* __restrict__ eps_phar, float* __restrict__ eps_pocket,
                                                  ChainState* chain, TrainSave sv) {
     extern __shared__ float s_hrow[];            // [8][H] node rows, then [H][dyn] embedding_out^T
-    __shared__ float s_j[8][CMDGEN_MAX_SMALL + 1];
-    __shared__ float s_h1[8][CMDGEN_MAX_SMALL];
+    __shared__ ReadoutSmall S;
     const int tid = threadIdx.x, g = tid >> 5, l32 = tid & 31;
     if (chain && blockIdx.x == 0 && tid == 0) chain->step += 1;      // this evaluation is done (see ChainState)
-    const int nnodes = eps_pocket ? lay.N : lay.Nl;
-    const int n = blockIdx.x * 8 + g;
-    const bool live = n < nnodes;
-    const bool ph = n < lay.Nl;
-    const int H = d.H;
-    float* s_wT = s_hrow + 8 * H;
-    for (int i = tid; i < H * d.dyn; i += 256) s_wT[i] = sw.embo_wT[i];        // coalesced, all loads in flight
-    if (live) for (int k = l32; k < H; k += 32) s_hrow[g * H + k] = w.h[(size_t)n * H + k];
-    __syncthreads();
-    if (live) {
-        for (int j = l32; j < d.J; j += 32) {
-            float s0 = sw.embo_b[j], s1 = 0.f, s2 = 0.f, s3 = 0.f;
-            const float* hr = s_hrow + g * H;
-            const float* wt = s_wT + j;
-            for (int k = 0; k < H; k += 4) {
-                s0 = fmaf(hr[k], wt[k * d.dyn], s0);
-                s1 = fmaf(hr[k + 1], wt[(k + 1) * d.dyn], s1);
-                s2 = fmaf(hr[k + 2], wt[(k + 2) * d.dyn], s2);
-                s3 = fmaf(hr[k + 3], wt[(k + 3) * d.dyn], s3);
-            }
-            s_j[g][j] = (s0 + s1) + (s2 + s3);
-            if (sv.hfin) sv.hfin[(size_t)n * d.dyn + j] = s_j[g][j];
+    readout_features(s_hrow, s_hrow + RO_ROWS * d.H, S, lay, w, d, sw, eps_phar, eps_pocket, sv, (int)blockIdx.x);
+    const int n = blockIdx.x * RO_ROWS + g;
+    if (n < (eps_pocket ? lay.N : lay.Nl) && l32 == 0) {
+        float* out = n < lay.Nl ? eps_phar + (size_t)n * (3 + d.P) : eps_pocket + (size_t)(n - lay.Nl) * (3 + d.R);
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (n < lay.Nm) {
+            v = readout_vel(lay, w, d, n);
+            if (vel_isnan(v)) atomicOr(w.nan_flag, 1);
         }
+        out[0] = v.x; out[1] = v.y; out[2] = v.z;
     }
-    __syncthreads();
-    if (live) {
-        const int F = ph ? d.P : d.R;
-        const float* W0 = ph ? sw.pd0_w : sw.rd0_w; const float* B0 = ph ? sw.pd0_b : sw.rd0_b;
-        for (int o = l32; o < 2 * F; o += 32) {
-            float s = B0[o];
-            for (int k = 0; k < d.J; ++k) s = fmaf(s_j[g][k], W0[(size_t)o * d.J + k], s);
-            const float a = silu_f(s);
-            s_h1[g][o] = a;
-            if (sv.dec1) {
-                if (ph) { sv.dec1[(size_t)n * 2 * F + o] = s; sv.deca[(size_t)n * 2 * F + o] = a; }
-                else if (sv.qdec1) { sv.qdec1[(size_t)(n - lay.Nl) * 2 * F + o] = s; sv.qdeca[(size_t)(n - lay.Nl) * 2 * F + o] = a; }
-            }
-        }
-    }
-    __syncthreads();
-    if (live) {
-        const int F = ph ? d.P : d.R;
-        const float* W2 = ph ? sw.pd2_w : sw.rd2_w; const float* B2 = ph ? sw.pd2_b : sw.rd2_b;
-        float* out = ph ? eps_phar + (size_t)n * (3 + d.P) : eps_pocket + (size_t)(n - lay.Nl) * (3 + d.R);
-        for (int o = l32; o < F; o += 32) {
-            float s = B2[o];
-            for (int k = 0; k < 2 * F; ++k) s = fmaf(s_h1[g][k], W2[(size_t)o * 2 * F + k], s);
-            out[3 + o] = s;
-            if (sv.dec_out) {
-                if (ph) sv.dec_out[(size_t)n * F + o] = s;
-                else if (sv.qdec_out) sv.qdec_out[(size_t)(n - lay.Nl) * F + o] = s;
-            }
-        }
-        if (l32 == 0) {
-            float vx = 0.f, vy = 0.f, vz = 0.f;
-            if (n < lay.Nm) {
-                // x_final = X[L-1] + ACC[L-1]/nf ; vel = x_final - x_input
-                const float4 p = (d.L == 1) ? w.X0[n] : w.XL[(size_t)(d.L - 1) * lay.Nm + n];
-                const float4 a = w.ACC[(size_t)(d.L - 1) * lay.Nm + n];
-                const float4 x0 = w.X0[n];
-                const float dv = agg_div(w, d, n);
-                vx = (p.x + a.x / dv) - x0.x;
-                vy = (p.y + a.y / dv) - x0.y;
-                vz = (p.z + a.z / dv) - x0.z;
-                if (isnan(vx) || isnan(vy) || isnan(vz)) atomicOr(w.nan_flag, 1);
-            }
-            out[0] = vx; out[1] = vy; out[2] = vz;
-        }
-    }
+}
+
+// The velocity columns and the NaN flag of the phar rows on their own: the evaluation in front of the decode where the evaluation itself ran
+// without them (readout_mode, cmdgen_dev.h).  One thread per phar row; pass 2 of that evaluation cleared the flag.
+__global__ void k_vel_flag(Layout lay, Work w, Dims d, float* __restrict__ eps_phar) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= lay.Nl) return;
+    const float4 v = readout_vel(lay, w, d, n);
+    if (vel_isnan(v)) atomicOr(w.nan_flag, 1);
+    float* out = eps_phar + (size_t)n * (3 + d.P);
+    out[0] = v.x; out[1] = v.y; out[2] = v.z;
 }
 
 // applies the reference's batch-global NaN reset to an evaluation's output (dynamics.py:129-131)
@@ -161,14 +114,17 @@ static void launch_node(const EvalLaunch& a, int l, hipStream_t s) {
         default:                  cmdgen_launch_node64(a, l, s); break;     // k_node64 and its kin
     }
 }
-static void launch_coord(const EvalLaunch& a, int l, hipStream_t s) {
+static void launch_coord(const EvalLaunch& a, int l, hipStream_t s, float* eps_phar, ChainState* chain) {
     switch (a.plan.coord) {
         case CoordKernel::e128:  cmdgen_launch_coord128(a, l, s); break;
         case CoordKernel::tiles: cmdgen_launch_coord_tiles(a, l, s); break;
-        case CoordKernel::fullk32_proj:      // (the last block has no next one and stays with k_edge_coord)
+        case CoordKernel::fullk32_proj:      // (the last block has no next one: k_edge_coord, or k_coord_readout where the readout joins it)
             if (a.proj_now && unit_has_next(a, l)) { cmdgen_launch_coord_proj(a, l, s); break; }
             [[fallthrough]];
-        case CoordKernel::fullk32: cmdgen_launch_coord_fullk(a, l, s); break;
+        case CoordKernel::fullk32:
+            if (a.readout_now && l == a.d.L - 1) cmdgen_launch_coord_readout(a, l, eps_phar, chain, s);
+            else cmdgen_launch_coord_fullk(a, l, s);
+            break;
     }
 }
 // (the kernel the evaluation itself would run for this block's messages; weight unit of the block's first GCL when a block has several)
@@ -196,6 +152,9 @@ static void launch_eval(const EvalLaunch& a, const float* xh_phar, const float* 
     // the next block's P | Q in the coordinate launch (LaunchPlan::proj_in_coord): the sampler's whole evaluations only - the training forward, the
     // parity stops and the per-stage events keep every projection in the node launch
     a.proj_now = (a.plan.proj_in_coord && !a.save && a.stop_block < 0 && !ev) ? 1 : 0;
+    // the feature part of the readout in the last block's coordinate launch (LaunchPlan::readout_in_coord): the plain sampling chain's evaluations
+    a.readout_now = a.readout_used = readout_mode(a, chain, t_arr, eps_pocket, ev);
+    const float* x0_from = a.readout_now ? xh_phar : nullptr;       // pass 2 then takes X0 / ACC of the phar rows over from the step kernel (edge_write_body)
     REC();
     // per-sample graph kernels: one wave scans one receiver at a time, so big samples (full-atom pockets: 381 nodes) get 16 waves
     const int gthr = a.lay.max_n > 128 ? 1024 : 256;
@@ -205,9 +164,9 @@ static void launch_eval(const EvalLaunch& a, const float* xh_phar, const float* 
         cmdgen_launch_embed_tiles(a, emt, xh_phar, xh_pocket, t_arr, coef, chain, s);
     } else if (a.d.H == 256 && !ev && !a.save && gthr == 256 && shm <= 64 * 1024 && (size_t)emt * 1812 + 1024 + (shm > 12288 ? shm : 12288) <= 160 * 1024 &&
                a.plan.write_embed) {      // (static LDS of the embedding body is 1812 B per tile row; one launch must hold both bodies' LDS)
-        cmdgen_launch_write_embed_tiles(a, emt, xh_phar, xh_pocket, t_arr, coef, chain, s);       // both in one launch
+        cmdgen_launch_write_embed_tiles(a, emt, xh_phar, xh_pocket, t_arr, coef, chain, s);       // both in one launch (EvalLaunch::readout_now: see x0_from)
     } else {
-        cmdgen_launch_edge_write(a, s);
+        cmdgen_launch_edge_write(a, x0_from, s);
         REC(); REC();
         cmdgen_launch_embed_tiles(a, emt, xh_phar, xh_pocket, t_arr, coef, chain, s);
     }
@@ -235,7 +194,7 @@ static void launch_eval(const EvalLaunch& a, const float* xh_phar, const float* 
             if (last && stop == 2) { a.unit = -1; a.skip_pc = 0; return; }
         }
         PROF_BEGIN(2);
-        launch_coord(a, l, s);
+        launch_coord(a, l, s, eps_phar, chain);
         PROF_END();
         REC();
         a.unit = -1; a.skip_pc = 0;
@@ -243,11 +202,12 @@ static void launch_eval(const EvalLaunch& a, const float* xh_phar, const float* 
     }
     REC();
     const int nn = eps_pocket ? N : a.lay.Nl;
-    hipLaunchKernelGGL(k_readout, dim3((nn + 7) / 8), dim3(256), (8 + a.d.dyn) * a.d.H * sizeof(float), s, a.lay, a.w, a.d, a.sw,
-                       eps_phar, eps_pocket, chain, a.save ? *a.save : TrainSave{});
+    if (!a.readout_now)      // (else: its feature part ran beside the last coordinate launch, the velocity is formed by its consumer)
+        hipLaunchKernelGGL(k_readout, dim3((nn + RO_ROWS - 1) / RO_ROWS), dim3(256), (RO_ROWS + a.d.dyn) * a.d.H * sizeof(float), s, a.lay, a.w, a.d, a.sw,
+                           eps_phar, eps_pocket, chain, a.save ? *a.save : TrainSave{});
     if (a.d.joint) hipLaunchKernelGGL(k_vel_com, dim3(B), dim3(64), 0, s, a.lay, a.w, a.d, eps_phar, eps_pocket);
     REC();
-    a.proj_now = 0;
+    a.proj_now = 0; a.readout_now = 0;
 #undef REC
 #undef PROF_BEGIN
 #undef PROF_END
@@ -284,6 +244,10 @@ void cmdgen_launch_save_positions(const EvalLaunch& a, float4* X, hipStream_t s)
 // k_readout stages 8 node rows + embedding_out^T in dynamic LDS: above the 64 KiB default (hidden_nf 512) the kernel needs the opt-in
 void cmdgen_readout_allow_lds(size_t bytes) {
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_readout), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+
+void cmdgen_launch_vel_flag(const EvalLaunch& a, float* eps_phar, hipStream_t s) {
+    hipLaunchKernelGGL(k_vel_flag, dim3((a.lay.Nl + 255) / 256), dim3(256), 0, s, a.lay, a.w, a.d, eps_phar);
 }
 
 void cmdgen_launch_nan_fix(const EvalLaunch& a, float* eps_phar, hipStream_t s) {

@@ -83,7 +83,11 @@ __global__ void k_edge_count(Layout lay, Work w, Dims d, const float* __restrict
 #endif
 
 // (a device function: it is also the first B workgroups of k_write_embed)
-__device__ __forceinline__ void edge_write_body(const Layout& lay, const Work& w, const Dims& d, const int b) {
+// x0_from (null: X0 and ACC are ready, as k_edge_count and the step kernels leave them): the [Nl][3 + P] rows whose first three columns are the
+// phar positions of this evaluation.  The workgroup then does k_edge_count's prologue for the phar rows of its sample - stores X0, zeroes the L
+// rows of ACC - because the step kernel in front of it left them alone: every one of its workgroups was reading them for the batch-global
+// NaN flag (k_step_count, readout_mode).  Nothing else in this launch reads X0 or ACC.
+__device__ __forceinline__ void edge_write_body(const Layout& lay, const Work& w, const Dims& d, const int b, const float* __restrict__ x0_from = nullptr) {
     extern __shared__ float4 spos[];
     int* soff = reinterpret_cast<int*>(spos + lay.max_n);
     int* sdg = soff + lay.max_n;                 // the sample's degree words (k_edge_count), read many times below
@@ -94,11 +98,22 @@ __device__ __forceinline__ void edge_write_body(const Layout& lay, const Work& w
     const int nl = lay.num_phar[b], np = lay.num_pocket[b], n = nl + np;
     const int pb = lay.phar_base[b], qb = lay.pocket_base[b];
     const int lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
-    for (int i = tid; i < n; i += blockDim.x) {
-        spos[i] = i < nl ? w.X0[pb + i] : w.XP[qb + i - nl];
-        sdg[i] = w.degL[pb + qb + i];
-        // aggregation_method 'mean' (egnn_new.py:288-292): every segment sum of a node is divided by its edge count, self loop included
-        if (d.agg_mean) w.adiv[flat_node(i, nl, pb, qb, lay.Nl)] = fmaxf((float)(sdg[i] & 0x3fffffff), 1.0f);
+    if (x0_from) {                               // (a loop of its own: the other one stays the code it was)
+        for (int i = tid; i < n; i += blockDim.x) {
+            sdg[i] = w.degL[pb + qb + i];
+            if (i < nl) {
+                const float* z = x0_from + (size_t)(pb + i) * (3 + d.P);
+                spos[i] = make_float4(z[0], z[1], z[2], 0.f);          // (X0 / ACC: in front of the receiver loop)
+            } else spos[i] = w.XP[qb + i - nl];
+            if (d.agg_mean) w.adiv[flat_node(i, nl, pb, qb, lay.Nl)] = fmaxf((float)(sdg[i] & 0x3fffffff), 1.0f);
+        }
+    } else {
+        for (int i = tid; i < n; i += blockDim.x) {
+            spos[i] = i < nl ? w.X0[pb + i] : w.XP[qb + i - nl];
+            sdg[i] = w.degL[pb + qb + i];
+            // aggregation_method 'mean' (egnn_new.py:288-292): every segment sum of a node is divided by its edge count, self loop included
+            if (d.agg_mean) w.adiv[flat_node(i, nl, pb, qb, lay.Nl)] = fmaxf((float)(sdg[i] & 0x3fffffff), 1.0f);
+        }
     }
     // The compact list is ordered like torch.where on the N x N adjacency of the flat node
     // numbering (dynamics.py:146): all phar receivers first (sample by sample), then all pocket
@@ -143,6 +158,12 @@ __device__ __forceinline__ void edge_write_body(const Layout& lay, const Work& w
         }
     }
     __syncthreads();
+    // (X0 / ACC here: the next barrier is the one behind the receiver loop, which waits for that loop's list stores anyway)
+    if (x0_from)
+        for (int i = tid; i < nl; i += blockDim.x) {
+            w.X0[pb + i] = spos[i];
+            for (int l = 0; l < d.L; ++l) w.ACC[(size_t)l * lay.Nm + pb + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
     const int eph_b = w.pocketEph[b];
     // The coordinate update needs the phar-receiver edges WITHOUT the self loops: their coord_diff is
     // exactly (x_i - x_i)/(...) = 0, so they add exactly 0 to the sum (egnn_new.py:91, :265-271).
@@ -243,7 +264,7 @@ __device__ __forceinline__ void edge_write_body(const Layout& lay, const Work& w
             }
         }
     }
-    if (b == 0 && tid == 0) *w.nan_flag = 0;     // after every reader of the previous evaluation's flag, before k_readout sets it
+    if (b == 0 && tid == 0) *w.nan_flag = 0;     // after every reader of the previous evaluation's flag (k_step_count's own scan never reads it), before k_readout - or k_vel_flag in front of the decode - sets it
     if (b == lay.B - 1 && tid == 0) {
         const int E = s_base[1] + (w.pocketE[b] - eph_b);
         const int Ec = d.joint ? s_base[4] + w.pocketEnsQ[b] : s_base[3] + w.pocketEns[b];
@@ -253,7 +274,7 @@ __device__ __forceinline__ void edge_write_body(const Layout& lay, const Work& w
     }
 }
 #if CMDGEN_H_PART == 0
-__global__ void k_edge_write(Layout lay, Work w, Dims d) { edge_write_body(lay, w, d, blockIdx.x); }
+__global__ void k_edge_write(Layout lay, Work w, Dims d, const float* __restrict__ x0_from) { edge_write_body(lay, w, d, blockIdx.x, x0_from); }
 #endif
 
 // ------------------------------------------------------------------------------------
@@ -546,11 +567,12 @@ __global__ __launch_bounds__(H) void k_embed(Layout lay, Work w, Dims d, SmallW 
 template <int MT, bool SP>
 __global__ __launch_bounds__(256) void k_write_embed(Layout lay, Work w, Dims d, SmallW sw, LayerW lw0, const float* __restrict__ xh_phar,
                                                      const float* __restrict__ xh_pocket, const float* __restrict__ t_arr,
-                                                     const float4* __restrict__ coef, const ChainState* chain, PocketCache pc, int npair, int emf) {
+                                                     const float4* __restrict__ coef, const ChainState* chain, PocketCache pc, int npair, int emf,
+                                                     int x0_from_xh /* pass 2 copies the phar positions of xh_phar into X0: edge_write_body */) {
     // workgroups: [0, B) edge lists | [B, B + 2 npair) pairs over the first npair tiles (the full-path tiles of a chain) |
     // the rest: one workgroup per remaining tile
     const int i = (int)blockIdx.x - lay.B;
-    if (i < 0) edge_write_body(lay, w, d, (int)blockIdx.x);
+    if (i < 0) edge_write_body(lay, w, d, (int)blockIdx.x, x0_from_xh ? xh_phar : nullptr);
     else if (i < 2 * npair) embed_body<256, MT, SP>(lay, w, d, sw, lw0, xh_phar, xh_pocket, t_arr, coef, chain, TrainSave{}, pc, i >> 1, i & 1, emf);
     else embed_body<256, MT, SP>(lay, w, d, sw, lw0, xh_phar, xh_pocket, t_arr, coef, chain, TrainSave{}, pc, i - npair, 2, emf);
 }
@@ -583,7 +605,7 @@ template <int H, int MT, bool SP> static void launch_write_embed(const EvalLaunc
         const PocketCache pc = (chain && !t) ? a.pcache : PocketCache{};
         const int npair = pc.c ? (a.lay.Nl + MT - 1) / MT : 0;        // pairs only where the other tiles are cache tiles
         hipLaunchKernelGGL((k_write_embed<MT, SP>), dim3(a.lay.B + nt + npair), dim3(256), shm_e > shm_w ? shm_e : shm_w, s, a.lay, a.w, a.d, a.sw,
-                           a.layers[0], xp, xq, t, coef, (const ChainState*)chain, pc, npair, embed_mfma_arg(a));
+                           a.layers[0], xp, xq, t, coef, (const ChainState*)chain, pc, npair, embed_mfma_arg(a), a.readout_now);
     }
 }
 template <int H> static void embed_only_H(const EvalLaunch& a, const float* xp, const float* xq, const float* t, hipStream_t s) {
@@ -615,9 +637,9 @@ void cmdgen_launch_edge_count(const EvalLaunch& a, const float* xh_phar, const f
     const size_t shm = (size_t)a.lay.max_n * (sizeof(float4) + 3 * sizeof(int));
     hipLaunchKernelGGL(k_edge_count, dim3(a.lay.B), dim3(a.lay.max_n > 128 ? 1024 : 256), shm, s, a.lay, a.w, a.d, xh_phar, xh_pocket);
 }
-void cmdgen_launch_edge_write(const EvalLaunch& a, hipStream_t s) {
+void cmdgen_launch_edge_write(const EvalLaunch& a, const float* x0_from, hipStream_t s) {
     const size_t shm = (size_t)a.lay.max_n * (sizeof(float4) + 3 * sizeof(int));
-    hipLaunchKernelGGL(k_edge_write, dim3(a.lay.B), dim3(a.lay.max_n > 128 ? 1024 : 256), shm, s, a.lay, a.w, a.d);
+    hipLaunchKernelGGL(k_edge_write, dim3(a.lay.B), dim3(a.lay.max_n > 128 ? 1024 : 256), shm, s, a.lay, a.w, a.d, x0_from);
 }
 
 // Chain-start cache of k_embed's pocket rows: stage 0 copies the rows of an evaluation at t = 0, stage 1 turns row 0 of
@@ -651,7 +673,7 @@ void cmdgen_launch_edges(const EvalLaunch& a, const float* xh_phar, const float*
     const size_t shm = (size_t)a.lay.max_n * (sizeof(float4) + 3 * sizeof(int));
     const int gthr = a.lay.max_n > 128 ? 1024 : 256;
     hipLaunchKernelGGL(k_edge_count, dim3(a.lay.B), dim3(gthr), shm, s, a.lay, a.w, a.d, xh_phar, xh_pocket);
-    hipLaunchKernelGGL(k_edge_write, dim3(a.lay.B), dim3(gthr), shm, s, a.lay, a.w, a.d);
+    hipLaunchKernelGGL(k_edge_write, dim3(a.lay.B), dim3(gthr), shm, s, a.lay, a.w, a.d, (const float*)nullptr);
 }
 
 // dynamic LDS above the 64 KiB default needs an explicit opt-in per kernel (samples of more than ~2700 nodes)

@@ -591,6 +591,12 @@ int cmdgen_set_gemm_mode(cmdgen_handle* h, int32_t split_bf16);
  *                        embedding on v_mfma_f32_16x16x4_f32, C = bias and k ascending, with every operand requested at kernel start; same
  *                        bits as the scalar tile.  hidden_nf 256, phar_nf 8, joint_nf 32 with the time column, 16-row tiles, never the training
  *                        forward: 1 = wherever that holds, 0 = never, unset = the library's rule: there, from 30 such tiles - 480 phar rows)
+ *                        "readout_in_coord" 0|1 (cmdgen_sample_chain runs without k_readout: embedding_out and the decoders of the phar rows as
+ *                        tiles of the last block's coordinate launch - kernels_coord_proj.hip -, the velocity and the batch-global NaN flag formed
+ *                        by the step kernel that consumes them, X0 / ACC handed from the step kernel to pass 2 of the radius graph; same bits.
+ *                        It exists only where the coordinate list runs on the 32-row full-K tile, conditional model, inv_sublayers 1, hidden_nf
+ *                        256, joint_nf + 1 <= 40, samples of at most 128 nodes: 1 = wherever that holds, 0 = never, unset = the library's rule
+ *                        (the same places).  Every other chain and entry point keeps k_readout.)
  *   dead work            "dead_skip" 0|1|2 (2, default: every block skips tiles beyond L - l hops of a moving node; 1: the
  *                        last block only; 0: off)
  *   chain                "graph_steps" (denoising steps per captured graph, default 8)
@@ -616,7 +622,7 @@ int cmdgen_debug_stamps(cmdgen_handle* h, uint64_t* out64, int32_t reset);
 
 /* Launch configuration in force for the current layout (measurement aid): key = "node_mt" | "edge_mt" | "coord_mt"
  * (rows per tile of the three MFMA kernels), "edge_grid" | "coord_grid" (workgroups of the persistent-style edge
- * kernels), "gemm_split" (the mode above), "node16_split", "node16w", "node64", "edge_fullk", "dead_skip", "proj_in_coord", "embed_mfma" (as resolved from the
+ * kernels), "gemm_split" (the mode above), "node16_split", "node16w", "node64", "edge_fullk", "dead_skip", "proj_in_coord", "embed_mfma", "readout_in_coord" (as resolved from the
  * options and the layout), "chain_graphs" (captured step graphs the handle holds), "half_engine" (the engine option as resolved: 1 = kernels with a half form use it), "msg_mfmas_per_product" |
  * "node_mfmas_per_product" | "coord_mfmas_per_product" (1: the fp32 matrix instruction, 6: three bf16 pieces per operand, 3: two fp16 pieces - the
  * engine the three tile kernels of the current layout run on), "train_edges" | "train_coord_edges" (edges of the last cmdgen_train_forward). */
