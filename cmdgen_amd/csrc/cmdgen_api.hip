@@ -642,6 +642,12 @@ extern "C" int cmdgen_debug_read(cmdgen_handle* h, const char* what, float* host
     else if (k == "x0") { src = h->work.X0; have = (size_t)h->lay.Nm * 4; }
     else if (k == "xl") { src = h->work.XL; have = (size_t)d.L * h->lay.Nm * 4; }
     else if (k == "acc") { src = h->work.ACC; have = (size_t)d.L * h->lay.Nm * 4; }
+    else if (k == "chain_z") {                       // the last conditional chain's z buffer (the multi-pocket chains: every member's copy)
+        const ChainBuf* cb = h->last_chain == CHAIN_PLAIN ? &h->chain : h->last_chain == CHAIN_INPAINT ? &h->inp_chain :
+                             h->last_chain == CHAIN_MULTI ? &h->multi_chain : h->last_chain == CHAIN_MULTI_EDIT ? &h->medit_chain : nullptr;
+        if (!cb || !cb->z_phar || h->chains[h->last_chain].n_steps < 0) return fail(h, CMDGEN_ESTATE, "no conditional chain has run on this layout");
+        src = cb->z_phar; have = (size_t)h->lay.Nl * (3 + d.P);
+    }
     else return fail(h, CMDGEN_EINVAL, "unknown debug buffer '%s'", k.c_str());
     if (n > have) n = have;
     HIPCHK(h, hipMemcpy(host, src, n * sizeof(float), hipMemcpyDeviceToHost));
@@ -907,15 +913,66 @@ extern "C" int cmdgen_sample_chain(cmdgen_handle* h, const float* pocket_x, cons
 // ---------------------------------------------------------------------------------
 static_assert(CMDGEN_MAX_GROUP == MAX_GROUP, "the public bound and the kernels' agree");
 
-// the multi-pocket chain's ChainBuf and, behind the posterior rows (n_steps + 1) of the slot's table block, the group tables:
-// first | size | ubase | weight (one entry per member each), then the groups' first members
-static int alloc_multi(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
-    int rc = alloc_chain_buf(h, k, h->multi_chain, tables); if (rc) return rc;
-    const size_t B = (size_t)h->lay.B;
-    const float* g = tables + (size_t)(n_steps + 1) * 4;
-    GroupTab& gt = h->groups;
+// the group tables of a call, per member (GroupTab), checked: what cmdgen_multi_pocket_chain and cmdgen_multi_edit_chain refuse alike
+struct GroupPlan {
+    std::vector<int> first, size, ubase, gfirst;
+    std::vector<int64_t> gid;
+    int G = 0; int64_t Nu = 0;
+};
+static int build_group_plan(cmdgen_handle* h, int64_t n_groups, const int64_t* group_size_host, const float* weight_host,
+                            const int64_t* group_ids_host, GroupPlan& p) {
+    const int B = h->lay.B;
+    if (n_groups < 1 || n_groups > B) return fail(h, CMDGEN_EINVAL, "n_groups=%lld must be in [1, batch=%d]", (long long)n_groups, B);
+    const int G = (int)n_groups;
+    p.first.resize(B); p.size.resize(B); p.ubase.resize(B); p.gfirst.resize(G); p.gid.resize(B);
+    int64_t members = 0, Nu = 0;
+    for (int g = 0; g < G; ++g) {
+        const int64_t M = group_size_host[g];
+        if (M < 1 || M > CMDGEN_MAX_GROUP) return fail(h, CMDGEN_EINVAL, "group %d has %lld members: sizes must be in [1, %d]", g, (long long)M, CMDGEN_MAX_GROUP);
+        if (members + M > B) { members += M; continue; }                 // (reported below with the sum)
+        p.gfirst[g] = (int)members;
+        double wsum = 0.0;
+        for (int m = 0; m < (int)M; ++m) {
+            const int b = (int)members + m;
+            if (h->cur_nphar[b] != h->cur_nphar[members])
+                return fail(h, CMDGEN_EINVAL, "group %d: member %d has %lld phar nodes, member 0 has %lld (the members of a group share one latent)",
+                            g, m, (long long)h->cur_nphar[b], (long long)h->cur_nphar[members]);
+            const float w = weight_host[b];
+            if (!std::isfinite(w) || w < 0.f) return fail(h, CMDGEN_EINVAL, "group %d: weight %d is %g (weights must be finite and >= 0)", g, m, (double)w);
+            wsum += (double)w;
+            p.first[b] = (int)members; p.size[b] = (int)M; p.ubase[b] = (int)Nu;
+            p.gid[b] = group_ids_host ? group_ids_host[g] : g;
+        }
+        if (std::fabs(wsum - 1.0) > 1e-5)
+            return fail(h, CMDGEN_EINVAL, "group %d: its weights sum to %.9g, not 1 (the caller normalises them)", g, wsum);
+        Nu += h->cur_nphar[members];
+        members += M;
+    }
+    if (members != B) return fail(h, CMDGEN_EINVAL, "the group sizes sum to %lld, the layout has %d samples", (long long)members, B);
+    const size_t step_lds = (size_t)h->lay.max_n * (sizeof(float4) + sizeof(int) + (size_t)(3 + h->dims.P) * sizeof(float));
+    if (step_lds > 64 * 1024)
+        return fail(h, CMDGEN_EINVAL, "a sample has %d nodes: the multi-pocket step keeps a sample's positions, degrees and z in LDS (64 KiB)", h->lay.max_n);
+    p.G = G; p.Nu = Nu;
+    return 0;
+}
+// ... appended to a plan's tables: first | size | ubase | weight (one entry per member each), then the groups' first members
+static void append_group_tables(std::vector<float>& tables, const GroupPlan& p, const float* weight_host, int B) {
+    const size_t c0 = tables.size();
+    tables.resize(c0 + (size_t)4 * B + p.G);
+    float* g = tables.data() + c0;
+    memcpy(g, p.first.data(), (size_t)B * sizeof(int)); memcpy(g + B, p.size.data(), (size_t)B * sizeof(int));
+    memcpy(g + 2 * (size_t)B, p.ubase.data(), (size_t)B * sizeof(int)); memcpy(g + 3 * (size_t)B, weight_host, (size_t)B * sizeof(float));
+    memcpy(g + 4 * (size_t)B, p.gfirst.data(), (size_t)p.G * sizeof(int));
+}
+static void point_group_tab(GroupTab& gt, const float* g, size_t B) {
     gt.first = (const int*)g; gt.size = (const int*)(g + B); gt.ubase = (const int*)(g + 2 * B);
     gt.weight = g + 3 * B; gt.group_first = (const int*)(g + 4 * B);
+}
+
+// the multi-pocket chain's ChainBuf and, behind the posterior rows (n_steps + 1) of the slot's table block, the group tables
+static int alloc_multi(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
+    int rc = alloc_chain_buf(h, k, h->multi_chain, tables); if (rc) return rc;
+    point_group_tab(h->groups, tables + (size_t)(n_steps + 1) * 4, (size_t)h->lay.B);
     return 0;
 }
 
@@ -932,56 +989,19 @@ extern "C" int cmdgen_multi_pocket_chain(cmdgen_handle* h, const float* pocket_x
     const int K = timesteps;
     if (K < 1 || K > h->cfg.timesteps) return fail(h, CMDGEN_EINVAL, "timesteps=%d must be in [1, %d]", K, h->cfg.timesteps);
     const int B = h->lay.B;
-    if (n_groups < 1 || n_groups > B) return fail(h, CMDGEN_EINVAL, "n_groups=%lld must be in [1, batch=%d]", (long long)n_groups, B);
-    const int G = (int)n_groups;
-    // the group tables, per member (GroupTab)
-    std::vector<int> first(B), size(B), ubase(B), gfirst(G);
-    std::vector<int64_t> gid(B);
-    int64_t members = 0, Nu = 0;
-    for (int g = 0; g < G; ++g) {
-        const int64_t M = group_size_host[g];
-        if (M < 1 || M > CMDGEN_MAX_GROUP) return fail(h, CMDGEN_EINVAL, "group %d has %lld members: sizes must be in [1, %d]", g, (long long)M, CMDGEN_MAX_GROUP);
-        if (members + M > B) { members += M; continue; }                 // (reported below with the sum)
-        gfirst[g] = (int)members;
-        double wsum = 0.0;
-        for (int m = 0; m < (int)M; ++m) {
-            const int b = (int)members + m;
-            if (h->cur_nphar[b] != h->cur_nphar[members])
-                return fail(h, CMDGEN_EINVAL, "group %d: member %d has %lld phar nodes, member 0 has %lld (the members of a group share one latent)",
-                            g, m, (long long)h->cur_nphar[b], (long long)h->cur_nphar[members]);
-            const float w = weight_host[b];
-            if (!std::isfinite(w) || w < 0.f) return fail(h, CMDGEN_EINVAL, "group %d: weight %d is %g (weights must be finite and >= 0)", g, m, (double)w);
-            wsum += (double)w;
-            first[b] = (int)members; size[b] = (int)M; ubase[b] = (int)Nu;
-            gid[b] = group_ids_host ? group_ids_host[g] : g;
-        }
-        if (std::fabs(wsum - 1.0) > 1e-5)
-            return fail(h, CMDGEN_EINVAL, "group %d: its weights sum to %.9g, not 1 (the caller normalises them)", g, wsum);
-        Nu += h->cur_nphar[members];
-        members += M;
-    }
-    if (members != B) return fail(h, CMDGEN_EINVAL, "the group sizes sum to %lld, the layout has %d samples", (long long)members, B);
-    const size_t step_lds = (size_t)h->lay.max_n * (sizeof(float4) + sizeof(int) + (size_t)(3 + h->dims.P) * sizeof(float));
-    if (step_lds > 64 * 1024)
-        return fail(h, CMDGEN_EINVAL, "a sample has %d nodes: the multi-pocket step keeps a sample's positions, degrees and z in LDS (64 KiB)", h->lay.max_n);
+    GroupPlan gp;
+    rc = build_group_plan(h, n_groups, group_size_host, weight_host, group_ids_host, gp); if (rc) return rc;
     std::vector<float> tables = step_table(h, K);
-    {
-        const size_t c0 = tables.size();
-        tables.resize(c0 + (size_t)4 * B + G);
-        float* g = tables.data() + c0;
-        memcpy(g, first.data(), (size_t)B * sizeof(int)); memcpy(g + B, size.data(), (size_t)B * sizeof(int));
-        memcpy(g + 2 * (size_t)B, ubase.data(), (size_t)B * sizeof(int)); memcpy(g + 3 * (size_t)B, weight_host, (size_t)B * sizeof(float));
-        memcpy(g + 4 * (size_t)B, gfirst.data(), (size_t)G * sizeof(int));
-    }
+    append_group_tables(tables, gp, weight_host, B);
     const hipStream_t caller = (hipStream_t)stream;
     hipStream_t s; EvalLaunch a;
-    rc = begin_chain(h, CHAIN_MULTI, tables, K, alloc_multi, gid.data(), use_graph, caller, &s, &a); if (rc) return rc;
+    rc = begin_chain(h, CHAIN_MULTI, tables, K, alloc_multi, gp.gid.data(), use_graph, caller, &s, &a); if (rc) return rc;
     ChainSlot& k = h->chains[CHAIN_MULTI];
     const Dims& d = h->dims;
     ChainBuf c = h->multi_chain;
     c.noise = noise; c.seed = seed; c.z_steps = z_steps_out; c.pocket_steps = pocket_steps_out;
     GroupTab gt = h->groups;
-    gt.G = G; gt.Nu = (int)Nu;
+    gt.G = gp.G; gt.Nu = (int)gp.Nu;
     cmdgen_launch_multi_init(h->lay, d, c, gt, pocket_x, pocket_onehot, s);
     build_pocket_cache(h, k, c, a, s);
     EvalLaunch a2 = a;
@@ -1295,6 +1315,84 @@ extern "C" int cmdgen_inpaint_chain(cmdgen_handle* h, const float* pocket_x, con
     return cmdgen_edit_chain(h, pocket_x, pocket_onehot, phar_x, phar_onehot, phar_fixed, phar_fixed, timesteps, timesteps, resamplings,
                              jump_length, noise, n_draws, seed, pocket_ids_host, xh_phar_out, xh_pocket_out, z_steps_out,
                              pocket_steps_out, use_graph, stream);
+}
+
+// ---------------------------------------------------------------------------------
+// the multi-pocket edit chain: the edit chain's ops on the multi-pocket chain's shared latent (kernels_multi.hip; the ops, the group
+// offset and the draw scheme are in include/cmdgen_hip.h).  The plan is the edit chain's, the group tables the multi-pocket chain's.
+// ---------------------------------------------------------------------------------
+// the slot's table block: coef (n_steps + 1) | coef2 | iop (n_steps each) | the group tables; the known rows and marks once per group
+static int alloc_multi_edit(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
+    int rc = alloc_chain_buf(h, k, h->medit_chain, tables); if (rc) return rc;
+    const Dims& d = h->dims;
+    const Layout& L = h->lay;
+    InpaintBuf& ip = h->medit;
+    ip.coef2 = (const float4*)(tables + (size_t)(n_steps + 1) * 4);
+    ip.iop = (const int4*)(tables + (size_t)(2 * n_steps + 1) * 4);
+    ip.n_steps = n_steps;
+    point_group_tab(h->medit_groups, tables + (size_t)(3 * n_steps + 1) * 4, (size_t)L.B);
+    void* q;                                         // (Nl bounds the unique rows of any grouping of this layout)
+    rc = dev_alloc(h, k.allocs, &q, (size_t)L.Nl * (3 + d.P) * sizeof(float), true); if (rc) return rc; ip.known = (const float*)q;
+    rc = dev_alloc(h, k.allocs, &q, (size_t)L.Nl * sizeof(float), true); if (rc) return rc; ip.fix = (float*)q;
+    rc = dev_alloc(h, k.allocs, &q, (size_t)L.B * sizeof(float4), true); if (rc) return rc; ip.poff = (float4*)q;
+    return 0;
+}
+
+extern "C" int cmdgen_multi_edit_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
+                                       int64_t n_groups, const int64_t* group_size_host, const float* weight_host,
+                                       const float* phar_x, const float* phar_onehot, const float* fix_x, const float* fix_h,
+                                       int32_t timesteps, int32_t start, int32_t resamplings, int32_t jump_length,
+                                       const float* noise, int64_t n_draws, uint64_t seed, const int64_t* group_ids_host,
+                                       float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                                       int32_t use_graph, cmdgen_stream stream) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (h->dims.joint) return fail(h, CMDGEN_ESTATE, "the multi-pocket edit chain is not supported for the joint model (update_pocket_coords=1): its pocket nodes diffuse with the latent");
+    if (h->dims.no_com) return fail(h, CMDGEN_ESTATE, "the multi-pocket edit chain is not supported for no_com_projection handles (SimpleConditionalDDPM)");
+    rc = check_inpaint_args(h, timesteps, start, resamplings, jump_length); if (rc) return rc;
+    if (!pocket_x || !pocket_onehot || !group_size_host || !weight_host || !phar_x || !phar_onehot || !fix_x || !fix_h || !xh_phar_out ||
+        !xh_pocket_out)
+        return fail(h, CMDGEN_EINVAL, "null pointer");
+    GroupPlan gp;
+    rc = build_group_plan(h, n_groups, group_size_host, weight_host, group_ids_host, gp); if (rc) return rc;
+    const InpaintPlan plan = build_inpaint_plan(h, timesteps, start, resamplings, jump_length);
+    if (noise && n_draws < plan.n_draws)
+        return fail(h, CMDGEN_EINVAL, "noise holds %lld draws, the schedule needs %lld", (long long)n_draws, (long long)plan.n_draws);
+    const int n_steps = plan.n_steps;
+    std::vector<float> tables = plan_tables(plan.coef, plan.coef2, plan.iop);
+    append_group_tables(tables, gp, weight_host, h->lay.B);
+    const hipStream_t caller = (hipStream_t)stream;
+    hipStream_t s; EvalLaunch a;
+    rc = begin_chain(h, CHAIN_MULTI_EDIT, tables, n_steps, alloc_multi_edit, gp.gid.data(), use_graph, caller, &s, &a); if (rc) return rc;
+    ChainSlot& k = h->chains[CHAIN_MULTI_EDIT];
+    const Dims& d = h->dims;
+    ChainBuf c = h->medit_chain;
+    c.noise = noise; c.seed = seed; c.z_steps = z_steps_out; c.pocket_steps = pocket_steps_out;
+    const InpaintBuf ip = h->medit;
+    GroupTab gt = h->medit_groups;
+    gt.G = gp.G; gt.Nu = (int)gp.Nu;
+    if (start == timesteps)                          // from the prior: z_T around the weighted pocket centre
+        cmdgen_launch_multi_init(h->lay, d, c, gt, pocket_x, pocket_onehot, s);
+    else                                             // part-way: z ~ q(z_start | the given rows)
+        cmdgen_launch_multi_edit_start(h->lay, d, c, gt, plan.alpha_start, plan.sigma_start, phar_x, phar_onehot, pocket_x, pocket_onehot, s);
+    // a launch of its own after the init: every member reads the projected pocket of its group's FIRST member for the offset
+    cmdgen_launch_multi_edit_prep(h->lay, d, c, gt, ip, phar_x, phar_onehot, fix_x, fix_h, pocket_x, s);
+    build_pocket_cache(h, k, c, a, s);
+    EvalLaunch a2 = a;
+    a2.skip_count = 1;                               // k_multi_edit_step_count ran pass 1 of the graph
+    cmdgen_launch_eval(a, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, s, nullptr);   // evaluation 0 (t = start / timesteps)
+    // the plan's tables and the group tables are slot buffers: a changed plan, start, grouping or weight prepares the slot again and
+    // drops its graph; the caller's pointers are the key
+    const void* key[6] = {noise, z_steps_out, pocket_steps_out, nullptr, nullptr, s};
+    rc = run_steps(h, k, key, seed, n_steps, use_graph, s, [&](hipStream_t ss) {
+        cmdgen_launch_multi_edit_step_count(h->lay, d, c, gt, ip, h->work, h->work.eps_tmp, ss);
+        cmdgen_launch_eval(a2, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, ss, nullptr);
+    });
+    if (rc) return rc;
+    // decode: k_multi_final reads its draw from row 1 + n_steps of `noise`; the decode draw is the plan's last row
+    ChainBuf cf = c;
+    if (noise) cf.noise = noise + (size_t)(plan.n_draws - 1 - (1 + n_steps)) * gt.Nu * (3 + d.P);
+    cmdgen_launch_multi_final(h->lay, d, cf, gt, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, k.cog, s);
+    return end_chain(h, caller, s);
 }
 
 // ---------------------------------------------------------------------------------

@@ -24,7 +24,7 @@ struct DevBuf {
 // Host state of one kind of denoising chain (cmdgen_api.hip): its buffers for the current layout, the plan tables they were
 // prepared for, and its captured steps.  Each kind has a slot of its own, so plain and inpainting chains alternate on a
 // handle without re-preparing or re-capturing.
-enum ChainKind { CHAIN_PLAIN, CHAIN_JOINT, CHAIN_INPAINT, CHAIN_SCORE, CHAIN_MULTI, CHAIN_KINDS };
+enum ChainKind { CHAIN_PLAIN, CHAIN_JOINT, CHAIN_INPAINT, CHAIN_SCORE, CHAIN_MULTI, CHAIN_MULTI_EDIT, CHAIN_KINDS };
 struct ChainSlot {
     std::vector<void*> allocs;
     std::vector<float> tables;             // the uploaded plan tables (coef | coef2 | iop bits), compared to decide a re-prepare
@@ -80,6 +80,9 @@ struct cmdgen_handle {
     ScoreBuf score{};
     ChainBuf multi_chain{};                // multi-pocket chain: every member's copy of z, the pockets, the posterior rows, checks and state
     GroupTab groups{};                     // ... and its group tables (in the slot's table block: a changed grouping prepares the slot again)
+    ChainBuf medit_chain{};                // multi-pocket edit chain: the multi-pocket chain's buffers, ...
+    InpaintBuf medit{};                    // ... the edit chain's op tables, the known rows and marks once per group ([Nu] rows), the group's offset per member
+    GroupTab medit_groups{};               // ... and its own group tables
     std::vector<float> user_coef;          // optional host-supplied step table
     int user_coef_K = -1;
     hipStream_t own_stream = nullptr;      // used when the caller's stream is the legacy default stream (not capturable)

@@ -60,6 +60,15 @@ void cmdgen_launch_multi_step_count(const Layout& lay, const Dims& d, const Chai
 void cmdgen_launch_multi_final(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const Work& w, const float* eps,
                                float* xo, float* po, unsigned int* cog, hipStream_t s);
 
+// ... and the multi-pocket edit chain: the edit chain's ops on a group's shared latent (known rows and marks once per group)
+void cmdgen_launch_multi_edit_start(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, float alpha, float sigma,
+                                    const float* phx, const float* phoh, const float* px, const float* poh, hipStream_t s);
+void cmdgen_launch_multi_edit_prep(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const InpaintBuf& ip,
+                                   const float* phx, const float* phoh, const float* fix_x, const float* fix_h, const float* px,
+                                   hipStream_t s);
+void cmdgen_launch_multi_edit_step_count(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const InpaintBuf& ip,
+                                         const Work& w, const float* eps, hipStream_t s);
+
 // kernels_inpaint.hip: the conditional RePaint chain and the edit chain
 void cmdgen_launch_inpaint_prep(const Layout& lay, const Dims& d, const ChainBuf& c, const InpaintBuf& ip, const float* phx,
                                 const float* phoh, const float* fix_x, const float* fix_h, const float* px, hipStream_t s);

@@ -28,3 +28,58 @@ __device__ __forceinline__ void record_com_check(unsigned int* slot2, const floa
     s = max_nan(s, max_nan(__shfl(s, 1), __shfl(s, 2)));
     if (lane == 0) { atomic_max_pos(slot2, mx); atomic_max_pos(slot2 + 1, s); }
 }
+
+// ---- parts of the op kernels that hold a sample's z and positions in LDS (k_inpaint_step_count, k_multi_edit_step_count)
+// the phar centre of mass of the sample's z (LDS, index order, as index_add_) on threads 0..2 -> s_mean
+__device__ __forceinline__ void phar_mean(const float* s_z, int nl, int ld, int tid, float* s_mean) {
+    if (tid < 3) {
+        float sum = 0.f;
+        for (int i = 0; i < nl; ++i) sum += s_z[i * ld + tid];
+        s_mean[tid] = sum / fmaxf((float)nl, 1.0f);
+    }
+}
+
+// subtract (m0, m1, m2) from the phar x columns in LDS and from the pocket positions in LDS (rows nl .. n-1 of s_pos)
+__device__ __forceinline__ void sub_mean(float* s_z, float4* s_pos, int nl, int n, int ld, int tid, int nt, float m0, float m1, float m2) {
+    for (int i = tid; i < n; i += nt) {
+        if (i < nl) { float* z = s_z + i * ld; z[0] -= m0; z[1] -= m1; z[2] -= m2; }
+        else { float4 p = s_pos[i]; p.x -= m0; p.y -= m1; p.z -= m2; s_pos[i] = p; }
+    }
+}
+
+// pass 1 of the radius graph of the NEXT evaluation from the sample's final positions in LDS (s_pos[0 .. n-1], phar rows first), as
+// k_edge_count and the tail of k_step_count: a row per wave, the degrees in sdeg and degL, the sample's four edge totals.  The whole
+// workgroup calls it after a barrier that follows the last write to s_pos.
+__device__ __forceinline__ void count_next_graph(const Layout& lay, const Dims& d, const Work& w, const float4* s_pos, int* sdeg, int b,
+                                                 int nl, int n, int pb, int qb) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    for (int i = wave; i < n; i += nwaves) {
+        const float4 pi = s_pos[i];
+        int deg = 0, self = 0;
+        for (int j0 = 0; j0 < n; j0 += 64) {
+            const int j = j0 + lane;
+            bool ok = false;
+            if (j < n) {
+                const float r2 = dist2(pi, s_pos[j]);
+                ok = (d.cutoff2 < 0.f) || (r2 <= d.cutoff2);
+            }
+            const unsigned long long m = __ballot(ok);
+            deg += __popcll(m);
+            if (i >= j0 && i < j0 + 64) self = (int)((m >> (i - j0)) & 1ull);
+        }
+        if (lane == 0) { sdeg[i] = deg | (self << 30); w.degL[pb + qb + i] = deg | (self << 30); }
+    }
+    __syncthreads();
+    if (wave == 0) {
+        int e = 0, eph = 0, ens = 0, ensq = 0;
+        for (int i = lane; i < n; i += 64) {
+            const int dg = sdeg[i] & 0x3fffffff; e += dg;
+            if (i < nl) { eph += dg; ens += dg - ((sdeg[i] >> 30) & 1); }
+            else ensq += dg - ((sdeg[i] >> 30) & 1);
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            e += __shfl_xor(e, o); eph += __shfl_xor(eph, o); ens += __shfl_xor(ens, o); ensq += __shfl_xor(ensq, o);
+        }
+        if (lane == 0) { w.pocketE[b] = e; w.pocketEph[b] = eph; w.pocketEns[b] = ens; w.pocketEnsQ[b] = ensq; }
+    }
+}

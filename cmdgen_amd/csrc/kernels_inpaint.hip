@@ -33,23 +33,6 @@ __device__ __forceinline__ float idraw(const ChainBuf& c, const Layout& lay, int
     return z[comp & 3];
 }
 
-// the phar centre of mass of the sample's z (LDS, index order, as index_add_) on threads 0..2 -> s_mean
-__device__ __forceinline__ void phar_mean(const float* s_z, int nl, int ld, int tid, float* s_mean) {
-    if (tid < 3) {
-        float sum = 0.f;
-        for (int i = 0; i < nl; ++i) sum += s_z[i * ld + tid];
-        s_mean[tid] = sum / fmaxf((float)nl, 1.0f);
-    }
-}
-
-// subtract (m0, m1, m2) from the phar x columns in LDS and from the pocket positions in LDS (rows nl .. n-1 of s_pos)
-__device__ __forceinline__ void sub_mean(float* s_z, float4* s_pos, int nl, int n, int ld, int tid, int nt, float m0, float m1, float m2) {
-    for (int i = tid; i < n; i += nt) {
-        if (i < nl) { float* z = s_z + i * ld; z[0] -= m0; z[1] -= m1; z[2] -= m2; }
-        else { float4 p = s_pos[i]; p.x -= m0; p.y -= m1; p.z -= m2; s_pos[i] = p; }
-    }
-}
-
 }  // namespace
 
 // known rows normalised (en_diffusion.py:874-889), the two masks packed as 1 (x held) + 2 (h held), and the pocket offset of

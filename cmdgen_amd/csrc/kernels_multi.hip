@@ -281,6 +281,233 @@ __global__ __launch_bounds__(1024) void k_multi_step_count(Layout lay, Dims d, C
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// The multi-pocket EDIT chain (cmdgen_multi_edit_chain): kernels_inpaint.hip's ops A / B / C on the group's shared latent.  An op
+// is k_inpaint_step_count's with eps_bar in place of the sample's own eps rows, the group's draws, and the known rows and marks
+// held once per group ([Nu] rows, at ubase + i).  The pocket offset of step B is the GROUP's: com(P_first) - com(P0_first) of the
+// group's first member, which every member's workgroup computes for itself after the init launch and keeps in its own slot
+// (InpaintBuf::poff[b]); from then on it only changes by the means subtracted from z.  So z depends on eps_bar, the draws, the
+// known rows and the offset alone, none of which depends on the member that computes them: the copies stay bit-identical, again
+// without a workgroup reading what another one of the same launch writes.  With M = 1 every value is kernels_inpaint.hip's, and
+// without marks and jumps k_multi_step_count's, bit for bit.
+// ------------------------------------------------------------------------------------------------------------
+// draw_group with the noise row and the Philox counter given apart (the edit plan's rows are in call order, its counters are not)
+__device__ __forceinline__ float draw_group_at(const ChainBuf& c, const Layout& lay, const GroupTab& g, int row, int key, int b,
+                                               int local, int comp, int ld) {
+    if (c.noise) return c.noise[((size_t)row * g.Nu + g.ubase[b] + local) * ld + comp];
+    float z[4];
+    philox_normal4(c.seed, (uint32_t)lay.pocket_gid[b], (uint32_t)(lay.pocket_gid[b] >> 32),
+                   (uint32_t)key, (uint32_t)(local * 4 + (comp >> 2)), z);
+    return z[comp & 3];
+}
+
+// what k_inpaint_prep leaves, per group: the known rows normalised and the packed marks (one copy per group, written by its first
+// member from the raw inputs), and in EVERY member's slot the group's offset and its number of marked rows.  Runs after the init
+// launch (k_multi_init or k_multi_edit_start), which has projected the pockets; nothing writes them here.
+__global__ __launch_bounds__(64) void k_multi_edit_prep(Layout lay, Dims d, ChainBuf c, GroupTab g, InpaintBuf ip,
+                                                        const float* __restrict__ phar_x, const float* __restrict__ phar_onehot,
+                                                        const float* __restrict__ fix_x, const float* __restrict__ fix_h,
+                                                        const float* __restrict__ pocket_x) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int nl = lay.num_phar[b];
+    const int first = g.first[b], ub = g.ubase[b];
+    const int qf = lay.pocket_base[first], npf = lay.num_pocket[first];
+    const int ld = 3 + d.P, ldq = 3 + d.R;
+    const bool writer = b == first;
+    float* known = const_cast<float*>(ip.known);
+    int nfix = 0;
+    for (int i = lane; i < nl; i += 64) {
+        const float f = (fix_x[ub + i] != 0.f ? 1.f : 0.f) + (fix_h[ub + i] != 0.f ? 2.f : 0.f);
+        nfix += f != 0.f ? 1 : 0;
+        if (!writer) continue;
+        ip.fix[ub + i] = f;
+        float* o = known + (size_t)(ub + i) * ld;
+        for (int k = 0; k < 3; ++k) o[k] = phar_x[(size_t)(ub + i) * 3 + k] / d.norm_x;
+        for (int k = 0; k < d.P; ++k) o[3 + k] = (phar_onehot[(size_t)(ub + i) * d.P + k] - d.bias_h) / d.norm_h;
+    }
+    for (int o = 32; o > 0; o >>= 1) nfix += __shfl_xor(nfix, o);
+    float off = 0.f;
+    if (lane < 3) {                                 // k_inpaint_prep's expression on the first member's rows
+        float s0 = 0.f, s1 = 0.f;
+        for (int i = 0; i < npf; ++i) {
+            s0 += c.xh_pocket[(size_t)(qf + i) * ldq + lane];
+            s1 += pocket_x[(size_t)(qf + i) * 3 + lane] / d.norm_x;
+        }
+        const float cnt = fmaxf((float)npf, 1.0f);
+        off = s0 / cnt - s1 / cnt;
+    }
+    const float o0 = __shfl(off, 0), o1 = __shfl(off, 1), o2 = __shfl(off, 2);
+    if (lane == 0) ip.poff[b] = make_float4(o0, o1, o2, (float)nfix);
+}
+
+// the start of a chain below t = T, in place of k_multi_init (k_edit_start for a group): every pocket of the group centred on the
+// centre of mass of the group's given rows, z ~ q(z_start | K) on the group's draw 0 over ALL rows, then the COM projection of the
+// member's z and pocket and the mean-zero check.  Reads the raw inputs only; k_multi_edit_prep follows it.
+__global__ __launch_bounds__(256) void k_multi_edit_start(Layout lay, Dims d, ChainBuf c, GroupTab g, float alpha, float sigma,
+                                                          const float* __restrict__ phar_x, const float* __restrict__ phar_onehot,
+                                                          const float* __restrict__ pocket_x, const float* __restrict__ pocket_onehot) {
+    __shared__ float s_mean[3], s_mean2[3];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nl = lay.num_phar[b], np = lay.num_pocket[b];
+    const int pb = lay.phar_base[b], qb = lay.pocket_base[b], ub = g.ubase[b];
+    const int ld = 3 + d.P, ldq = 3 + d.R;
+    if (tid < 3) {
+        float s = 0.f;
+        for (int i = 0; i < nl; ++i) s += phar_x[(size_t)(ub + i) * 3 + tid] / d.norm_x;      // index order
+        s_mean[tid] = s / fmaxf((float)nl, 1.0f);
+    }
+    __syncthreads();
+    const float c0 = s_mean[0], c1 = s_mean[1], c2 = s_mean[2];
+    for (int i = tid; i < nl; i += 256) {
+        const size_t u = (size_t)(ub + i);
+        float* z = c.z_phar + (size_t)(pb + i) * ld;
+        for (int k = 0; k < ld; ++k) {
+            const float x0 = k < 3 ? phar_x[u * 3 + k] / d.norm_x - (k == 0 ? c0 : k == 1 ? c1 : c2)
+                                   : (phar_onehot[u * d.P + k - 3] - d.bias_h) / d.norm_h;
+            const float a = alpha * x0;
+            z[k] = a + sigma * draw_group_at(c, lay, g, 0, 0, b, i, k, ld);
+        }
+    }
+    for (int i = tid; i < np; i += 256) {
+        const size_t q0 = (size_t)(qb + i);
+        float* q = c.xh_pocket + q0 * ldq;
+        q[0] = pocket_x[q0 * 3 + 0] / d.norm_x - c0; q[1] = pocket_x[q0 * 3 + 1] / d.norm_x - c1; q[2] = pocket_x[q0 * 3 + 2] / d.norm_x - c2;
+        for (int k = 0; k < d.R; ++k) q[3 + k] = (pocket_onehot[q0 * d.R + k] - d.bias_h) / d.norm_h;
+    }
+    __syncthreads();
+    if (tid < 3) {                                  // phar centre of mass of z, index order
+        float sum = 0.f;
+        for (int i = 0; i < nl; ++i) sum += c.z_phar[(size_t)(pb + i) * ld + tid];
+        s_mean2[tid] = sum / fmaxf((float)nl, 1.0f);
+    }
+    __syncthreads();
+    const float m0 = s_mean2[0], m1 = s_mean2[1], m2 = s_mean2[2];
+    for (int i = tid; i < nl + np; i += 256) {
+        float* p = i < nl ? c.z_phar + (size_t)(pb + i) * ld : c.xh_pocket + (size_t)(qb + i - nl) * ldq;
+        p[0] -= m0; p[1] -= m1; p[2] -= m2;
+    }
+    __syncthreads();
+    if (wave == 0) record_com_check(c.check, c.z_phar, ld, pb, nl, 1.0f, lane);
+}
+
+// k_inpaint_step_count for a member of a group: same LDS layout, same sums, same count pass as the two step kernels it composes;
+// z_steps (one copy of the rows per group) is written by the group's first member, pocket_steps by every member.
+__global__ __launch_bounds__(1024) void k_multi_edit_step_count(Layout lay, Dims d, ChainBuf c, GroupTab g, InpaintBuf ip, Work w,
+                                                                const float* __restrict__ eps) {
+    extern __shared__ float4 s_pos[];               // [max_n] positions of the sample (phar first), then int sdeg[max_n], then z
+    int* sdeg = reinterpret_cast<int*>(s_pos + lay.max_n);
+    float* s_z = reinterpret_cast<float*>(sdeg + lay.max_n);      // [nl * ld]
+    __shared__ float s_mean[3];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nt = blockDim.x;
+    const int nl = lay.num_phar[b], np = lay.num_pocket[b], n = nl + np;
+    const int pb = lay.phar_base[b], qb = lay.pocket_base[b];
+    const int ld = 3 + d.P, ldq = 3 + d.R;
+    const int first = g.first[b], M = g.size[b], ub = g.ubase[b];
+    const int step = c.state->step - 1;             // index of this op
+    const float4 cf = c.coef[step];
+    const float4 cf2 = ip.coef2[step];
+    const int4 io = ip.iop[step];
+    const float4 off0 = ip.poff[b];                 // this member's copy of the group's offset
+    const bool merge = off0.w > 0.f;
+    const bool nan_reset = *w.nan_flag != 0;
+    float* zg = c.z_phar + (size_t)pb * ld;
+    const int cnt = nl * ld;
+    for (int idx = tid; idx < cnt; idx += nt) s_z[idx] = zg[idx];
+    for (int i = tid; i < np; i += nt) {
+        const float* q = c.xh_pocket + (size_t)(qb + i) * ldq;
+        s_pos[nl + i] = make_float4(q[0], q[1], q[2], 0.f);
+    }
+    __syncthreads();
+    if (wave == 0) record_com_check(c.check + 2 * (1 + step), s_z, ld, 0, nl, 1.0f, lane);   // z_t, the op's input
+    __syncthreads();
+    // A: the posterior step on eps_bar (k_multi_step_count's expressions)
+    for (int idx = tid; idx < cnt; idx += nt) {
+        const int i = idx / ld, k = idx - i * ld;
+        float e = combine_eps(lay, g, eps, first, M, ld, idx);
+        if (nan_reset && k < 3) e = 0.f;
+        const float mu = s_z[idx] / cf.x - cf.y * e;
+        s_z[idx] = mu + cf.z * draw_group_at(c, lay, g, io.y, 1 + step, b, i, k, ld);
+    }
+    __syncthreads();
+    phar_mean(s_z, nl, ld, tid, s_mean);
+    __syncthreads();
+    float o0, o1, o2;                               // the group's offset in the frame of the pocket in LDS
+    {
+        const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
+        sub_mean(s_z, s_pos, nl, n, ld, tid, nt, m0, m1, m2);
+        o0 = off0.x - m0; o1 = off0.y - m1; o2 = off0.z - m2;
+    }
+    __syncthreads();
+    // B: the noised known rows moved into the current frame replace the held column groups; then the phar COM projection
+    if (merge) {
+        const int keyB = 2 + ip.n_steps + step;
+        for (int idx = tid; idx < cnt; idx += nt) {
+            const int i = idx / ld, k = idx - i * ld;
+            if (!((int)ip.fix[ub + i] & (k < 3 ? 1 : 2))) continue;
+            float zk = cf2.x * ip.known[(size_t)ub * ld + idx] + cf2.y * draw_group_at(c, lay, g, io.z, keyB, b, i, k, ld);
+            if (k < 3) zk = zk + (k == 0 ? o0 : k == 1 ? o1 : o2);
+            s_z[idx] = zk;
+        }
+        __syncthreads();
+        phar_mean(s_z, nl, ld, tid, s_mean);
+        __syncthreads();
+        const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
+        sub_mean(s_z, s_pos, nl, n, ld, tid, nt, m0, m1, m2);
+        o0 -= m0; o1 -= m1; o2 -= m2;
+        __syncthreads();
+    }
+    // the state after the op (a frame): the group's z by its first member, every member's pocket
+    if (c.z_steps && b == first)
+        for (int idx = tid; idx < cnt; idx += nt) c.z_steps[((size_t)step * g.Nu + ub) * ld + idx] = s_z[idx];
+    if (c.pocket_steps)
+        for (int i = tid; i < np; i += nt) {
+            const float4 p = s_pos[nl + i];
+            float* o = c.pocket_steps + ((size_t)step * lay.Np + qb + i) * 3;
+            o[0] = p.x; o[1] = p.y; o[2] = p.z;
+        }
+    // C: jump back, z_t' ~ q(z_t' | z_s) (draw, then the phar COM projection)
+    if (io.x & 1) {
+        const int keyC = 2 + 2 * ip.n_steps + step;
+        for (int idx = tid; idx < cnt; idx += nt) {
+            const int i = idx / ld, k = idx - i * ld;
+            const float mu = cf2.z * s_z[idx];
+            s_z[idx] = mu + cf2.w * draw_group_at(c, lay, g, io.w, keyC, b, i, k, ld);
+        }
+        __syncthreads();
+        phar_mean(s_z, nl, ld, tid, s_mean);
+        __syncthreads();
+        const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
+        sub_mean(s_z, s_pos, nl, n, ld, tid, nt, m0, m1, m2);
+        o0 -= m0; o1 -= m1; o2 -= m2;
+        __syncthreads();
+    }
+    // the new state, and the inputs of the next evaluation
+    for (int i = tid; i < n; i += nt) {
+        float4 p;
+        if (i < nl) {
+            const float* z = s_z + i * ld;
+            p = make_float4(z[0], z[1], z[2], 0.f);
+            w.X0[pb + i] = p;
+            for (int l = 0; l < d.L; ++l) w.ACC[(size_t)l * lay.Nm + pb + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            s_pos[i] = p;
+        } else {
+            p = s_pos[i];
+            float* q = c.xh_pocket + (size_t)(qb + i - nl) * ldq;
+            q[0] = p.x; q[1] = p.y; q[2] = p.z;
+            w.XP[qb + i - nl] = p;
+        }
+    }
+    for (int idx = tid; idx < cnt; idx += nt) zg[idx] = s_z[idx];
+    if (tid == 0) ip.poff[b] = make_float4(o0, o1, o2, off0.w);
+    __syncthreads();
+    count_next_graph(lay, d, w, s_pos, sdeg, b, nl, n, pb, qb);
+    if (b == 0 && tid == 0) {
+        if (nan_reset) atomicAdd(&w.counters[4], 1ull);
+        atomicAdd(&w.counters[0], 1ull);                       // evaluations (the one about to run)
+        atomicAdd(&w.counters[3], (unsigned long long)lay.N);  // nodes
+    }
+}
+
 void cmdgen_launch_multi_init(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const float* px,
                               const float* poh, hipStream_t s) {
     hipLaunchKernelGGL(k_multi_init, dim3(lay.B), dim3(64), 0, s, lay, d, c, g, px, poh);
@@ -294,4 +521,18 @@ void cmdgen_launch_multi_final(const Layout& lay, const Dims& d, const ChainBuf&
                                const float* eps, float* xo, float* po, unsigned int* cog, hipStream_t s) {
     hipLaunchKernelGGL(k_multi_final, dim3(lay.B), dim3(64), 0, s, lay, d, c, g, w, eps, xo, po, cog);
     hipLaunchKernelGGL(k_multi_drift_fix, dim3(g.G), dim3(64), 0, s, lay, d, g, xo, po, (const unsigned int*)cog);
+}
+void cmdgen_launch_multi_edit_start(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, float alpha, float sigma,
+                                    const float* phx, const float* phoh, const float* px, const float* poh, hipStream_t s) {
+    hipLaunchKernelGGL(k_multi_edit_start, dim3(lay.B), dim3(256), 0, s, lay, d, c, g, alpha, sigma, phx, phoh, px, poh);
+}
+void cmdgen_launch_multi_edit_prep(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const InpaintBuf& ip,
+                                   const float* phx, const float* phoh, const float* fix_x, const float* fix_h, const float* px,
+                                   hipStream_t s) {
+    hipLaunchKernelGGL(k_multi_edit_prep, dim3(lay.B), dim3(64), 0, s, lay, d, c, g, ip, phx, phoh, fix_x, fix_h, px);
+}
+void cmdgen_launch_multi_edit_step_count(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const InpaintBuf& ip,
+                                         const Work& w, const float* eps, hipStream_t s) {
+    const size_t shm = (size_t)lay.max_n * (sizeof(float4) + sizeof(int)) + (size_t)lay.max_n * (3 + d.P) * sizeof(float);
+    hipLaunchKernelGGL(k_multi_edit_step_count, dim3(lay.B), dim3(lay.max_n > 128 ? 1024 : 256), shm, s, lay, d, c, g, ip, w, eps);   // as its parents
 }

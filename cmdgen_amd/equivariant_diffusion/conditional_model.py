@@ -219,6 +219,33 @@ class ConditionalDDPM(EnVariationalDiffusion):
         [G] global group ids of the Philox draws.  With M = 1 this is sample_given_pocket, bit for bit.
         Returns (xh_phar [Nu, 3+P], [xh_pocket_m], phar_mask, [pocket_mask_m]); with return_frames > 1 the tensors carry the leading
         frame axis of sample_given_pocket."""
+        pockets, M, G = self._checked_pockets(pockets)
+        nph = torch.as_tensor(num_nodes_phar).detach().to('cpu', torch.int64).numpy().reshape(-1)
+        if len(nph) != G:
+            raise ValueError(f'num_nodes_phar has {len(nph)} entries for {G} groups')
+        w = self.group_weights(weights, G, M)
+        timesteps = self.T if timesteps is None else timesteps
+        assert 0 < return_frames <= timesteps
+        assert timesteps % return_frames == 0
+        device = pockets[0]['x'].device
+        sizes, rows, px, poh = self._member_layout(pockets, M, G)
+        self.refresh_learned_schedule()
+        h = self.dynamics.hip_handle()
+        h.set_layout(np.repeat(nph, M), sizes.reshape(-1))
+        h.set_step_table(timesteps, self.step_table(timesteps))
+        phar_mask = utils.num_nodes_to_batch_mask(G, torch.as_tensor(nph), device)
+        if noise is not None:
+            noise = noise.detach().to(device, torch.float32).contiguous()
+        if seed is None:
+            seed = fresh_seed()
+        run = lambda: h.multi_pocket_chain(px, poh, [M] * G, w.reshape(-1), timesteps, noise=noise, seed=seed, group_ids=group_ids,
+                                           want_steps=return_frames > 1, use_graph=self.use_hip_graph)
+        out = self._finish_chain(h, run, self.inpaint_frames(1, 1, timesteps, return_frames), return_frames)
+        return out[0], [out[1][..., r, :] for r in rows], phar_mask, [q['mask'] for q in pockets]
+
+    @staticmethod
+    def _checked_pockets(pockets):
+        """The pocket dicts of sample_given_pockets / edit_given_pockets as a list, with M (pockets per group) and G (groups)."""
         pockets = list(pockets)
         if not pockets:
             raise ValueError('pockets is empty: expected a list of pocket dicts')
@@ -231,15 +258,12 @@ class ConditionalDDPM(EnVariationalDiffusion):
             qm = q['mask']
             if qm.numel() > 1 and bool((qm[1:] < qm[:-1]).any()):
                 raise ValueError('pocket mask must be ascending and contiguous')
-        nph = torch.as_tensor(num_nodes_phar).detach().to('cpu', torch.int64).numpy().reshape(-1)
-        if len(nph) != G:
-            raise ValueError(f'num_nodes_phar has {len(nph)} entries for {G} groups')
-        w = self.group_weights(weights, G, M)
-        timesteps = self.T if timesteps is None else timesteps
-        assert 0 < return_frames <= timesteps
-        assert timesteps % return_frames == 0
+        return pockets, M, G
+
+    def _member_layout(self, pockets, M, G):
+        """The member layout of the multi-pocket chains: sample g * M + m is pocket m of group g.  -> (sizes [G, M], per m its rows in
+        the member layout, pocket x and one_hot of all members in that layout)."""
         device = pockets[0]['x'].device
-        # the member layout: sample g * M + m is pocket m of group g
         sizes = np.stack([q['size'].detach().to('cpu', torch.int64).numpy() for q in pockets], axis=1)       # [G, M]
         base = np.concatenate([[0], np.cumsum(sizes.reshape(-1))])                                           # [G * M + 1] first row of every member
         rows = []                                                                                            # per m: its rows in the member layout
@@ -255,19 +279,7 @@ class ConditionalDDPM(EnVariationalDiffusion):
             if len(q['x']) != len(r):
                 raise ValueError("a pocket's x does not have sum(size) rows")
             px[r], poh[r] = f32(q['x']), f32(q['one_hot'])
-        self.refresh_learned_schedule()
-        h = self.dynamics.hip_handle()
-        h.set_layout(np.repeat(nph, M), sizes.reshape(-1))
-        h.set_step_table(timesteps, self.step_table(timesteps))
-        phar_mask = utils.num_nodes_to_batch_mask(G, torch.as_tensor(nph), device)
-        if noise is not None:
-            noise = noise.detach().to(device, torch.float32).contiguous()
-        if seed is None:
-            seed = fresh_seed()
-        run = lambda: h.multi_pocket_chain(px, poh, [M] * G, w.reshape(-1), timesteps, noise=noise, seed=seed, group_ids=group_ids,
-                                           want_steps=return_frames > 1, use_graph=self.use_hip_graph)
-        out = self._finish_chain(h, run, self.inpaint_frames(1, 1, timesteps, return_frames), return_frames)
-        return out[0], [out[1][..., r, :] for r in rows], phar_mask, [q['mask'] for q in pockets]
+        return sizes, rows, px, poh
 
     @torch.no_grad()
     def inpaint(self, phar, pocket, phar_fixed, resamplings=1, jump_length=1, return_frames=1, timesteps=None,
@@ -386,6 +398,60 @@ class ConditionalDDPM(EnVariationalDiffusion):
                                    seed=seed, pocket_ids=pocket_ids, use_graph=self.use_hip_graph)
         out = self._finish_chain(h, run, [], 1)
         return out[0], out[1], phar_mask, pocket['mask']
+
+    @torch.no_grad()
+    def edit_given_pockets(self, phar, pockets, fix_coords=None, fix_types=None, start=None, resamplings=1, jump_length=1,
+                           weights=None, timesteps=None, noise=None, seed=None, group_ids=None):
+        """Hold or edit GIVEN points while drawing one pharmacophore per group of pockets: ``edit``'s ops on the shared latent of
+        ``sample_given_pockets`` - a dual-target design around a known anchor, a pharmacophore that fits one target adapted to a
+        second one (start below timesteps), points re-typed or re-placed against an ensemble of conformations.
+
+        phar: dict(x [Nu,3], one_hot [Nu,P], size [G], mask [Nu]) batched over the G groups, in the pockets' common frame; pockets,
+        weights and group_ids as in sample_given_pockets; fix_coords, fix_types, start, resamplings and jump_length as in edit (masks
+        [Nu] or [Nu,1]); noise [n_draws, Nu, 3+P] (Handle.edit_plan), one draw per group, op and role.  The offset that moves the
+        given rows into the chain's frame is the group's: the shift of its first pocket, which every pocket of the group shares.
+        The whole chain runs on the device (cmdgen_multi_edit_chain; its header gives the ops, the offset and the Philox counters).
+        With one pocket this is edit, and with nothing held from the prior at resamplings = jump_length = 1 sample_given_pockets,
+        both bit for bit.  Returns what sample_given_pockets returns: (xh_phar [Nu, 3+P], [xh_pocket_m], phar_mask, [pocket_mask_m])."""
+        pockets, M, G = self._checked_pockets(pockets)
+        timesteps = self.T if timesteps is None else int(timesteps)
+        start = timesteps if start is None else start
+        if int(start) != start or not 1 <= int(start) <= timesteps:
+            raise ValueError(f'start={start} must be an integer level in [1, timesteps={timesteps}]')
+        start = int(start)
+        nph = phar['size'].detach().to('cpu', torch.int64).numpy().reshape(-1)
+        if len(nph) != G:
+            raise ValueError(f'phar has {len(nph)} samples, pocket {G}')
+        pm = phar['mask']
+        if pm.numel() > 1 and bool((pm[1:] < pm[:-1]).any()):
+            raise ValueError('batch masks must be ascending and contiguous')
+        w = self.group_weights(weights, G, M)
+        device = pockets[0]['x'].device
+        n_phar = int(nph.sum())
+        fix_x = self._row_mask(fix_coords, 'fix_coords', n_phar, device)
+        fix_h = self._row_mask(fix_types, 'fix_types', n_phar, device)
+        f32 = lambda t: t.detach().to(device, torch.float32).contiguous()
+        if tuple(phar['x'].shape) != (n_phar, self.n_dims) or tuple(phar['one_hot'].shape) != (n_phar, self.phar_nf):
+            raise ValueError(f"phar x / one_hot have shapes {tuple(phar['x'].shape)} / {tuple(phar['one_hot'].shape)}: expected "
+                             f'[{n_phar}, {self.n_dims}] / [{n_phar}, {self.phar_nf}] (sum(size) rows)')
+        sizes, rows, px, poh = self._member_layout(pockets, M, G)
+        self.refresh_learned_schedule()
+        h = self.dynamics.hip_handle()
+        h.set_layout(np.repeat(nph, M), sizes.reshape(-1))
+        h.set_step_table(timesteps, self.step_table(timesteps))
+        n_steps, n_draws = h.edit_plan(timesteps, start, resamplings, jump_length)
+        if noise is not None:
+            noise = f32(noise)
+            if noise.dim() != 3 or noise.shape[0] < n_draws:
+                raise ValueError(f'noise has shape {tuple(noise.shape)}: this schedule needs {n_draws} draws of [{n_phar}, {3 + self.phar_nf}]')
+        if seed is None:
+            seed = fresh_seed()
+        phar_mask = utils.num_nodes_to_batch_mask(G, torch.as_tensor(nph), device)
+        args = (px, poh, [M] * G, w.reshape(-1), f32(phar['x']), f32(phar['one_hot']), fix_x, fix_h)
+        run = lambda: h.multi_edit_chain(*args, timesteps, start=start, resamplings=resamplings, jump_length=jump_length, noise=noise,
+                                         seed=seed, group_ids=group_ids, use_graph=self.use_hip_graph)
+        out = self._finish_chain(h, run, [], 1)
+        return out[0], [out[1][..., r, :] for r in rows], phar_mask, [q['mask'] for q in pockets]
 
     @torch.no_grad()
     def score(self, phar, pocket, timesteps=None, repeats=1, noise=None, seed=None, pocket_ids=None, return_levels=False):
@@ -520,4 +586,8 @@ class SimpleConditionalDDPM(ConditionalDDPM):
 
     def sample_given_pockets(self, *args, **kwargs):
         raise NotImplementedError('sample_given_pockets is not implemented for SimpleConditionalDDPM (no centre-of-mass projection: the '
+                                  'shared latent has no frame of its own); use ConditionalDDPM')
+
+    def edit_given_pockets(self, *args, **kwargs):
+        raise NotImplementedError('edit_given_pockets is not implemented for SimpleConditionalDDPM (no centre-of-mass projection: the '
                                   'shared latent has no frame of its own); use ConditionalDDPM')

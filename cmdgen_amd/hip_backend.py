@@ -69,6 +69,8 @@ SYMBOLS = [
     ('cmdgen_edit_plan', C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i64p, _i64p]),
     ('cmdgen_edit_chain', C.c_int, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int64,
                                     C.c_uint64, _i64p, _fp, _fp, _fp, _fp, C.c_int32, _vp]),
+    ('cmdgen_multi_edit_chain', C.c_int, [_vp, _fp, _fp, C.c_int64, _i64p, _vp, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_int32, _fp, C.c_int64, C.c_uint64, _i64p, _fp, _fp, _fp, _fp, C.c_int32, _vp]),
     ('cmdgen_score_chain', C.c_int, [_vp, _fp, _fp, _fp, _fp, C.c_int32, _vp, _vp, _fp, C.c_uint64, _i64p, _fp, _fp, C.c_int32, _vp]),
     ('cmdgen_param_count', C.c_int, [_vp, _i64p]),
     ('cmdgen_param_offset', C.c_int, [_vp, C.c_char_p, _i64p, _i64p]),
@@ -497,6 +499,47 @@ class Handle:
             int(start), int(resamplings), int(jump_length), _ptr(noise), int(noise.shape[0]) if noise is not None else 0,
             C.c_uint64(seed & (2 ** 64 - 1)), self._pocket_ids(pocket_ids), _ptr(xh_phar),
             _ptr(xh_pocket), _ptr(z_steps), _ptr(p_steps), int(bool(use_graph)), self._stream()), 'cmdgen_edit_chain')
+        return xh_phar, xh_pocket, z_steps
+
+    def multi_edit_chain(self, pocket_x, pocket_onehot, group_sizes: Sequence[int], weights, phar_x, phar_onehot, fix_x, fix_h,
+                         timesteps: int, start: Optional[int] = None, resamplings: int = 1, jump_length: int = 1, noise=None,
+                         seed: int = 0, group_ids: Optional[Sequence[int]] = None, want_steps: bool = False, use_graph: bool = True):
+        """edit_chain on the shared latent of multi_pocket_chain (cmdgen_multi_edit_chain): the layout, group_sizes, weights and
+        group_ids of multi_pocket_chain; phar_x [Nu,3], phar_onehot [Nu,P], fix_x, fix_h [Nu] one row per unique phar row (Nu = one copy
+        of the rows per group), in the pockets' common frame; start, resamplings, jump_length as edit_chain; noise [n_draws, Nu, 3+P]
+        (edit_plan) or None.  -> (xh_phar [Nu, 3+P], xh_pocket [Np, 3+R], z_steps [n_steps, Nu, 3+P] or None); with want_steps every
+        member's pocket after every op is left in last_pocket_steps."""
+        import torch
+        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
+        dev = pocket_x.device
+        start = timesteps if start is None else start
+        sizes = np.ascontiguousarray(np.asarray(group_sizes, dtype=np.int64))
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32))
+        assert sizes.ndim == 1 and len(sizes) >= 1 and w.shape == (self.batch,), (sizes.shape, w.shape, self.batch)
+        firsts = np.minimum(np.concatenate([[0], np.cumsum(sizes)[:-1]]), self.batch - 1)      # (as multi_pocket_chain)
+        n_unique = int(self.num_phar_host[firsts].sum())
+        shapes = [(self.n_pocket, 3), (self.n_pocket, R), (n_unique, 3), (n_unique, P), (n_unique,), (n_unique,)]
+        for t, sh in zip((pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h), shapes):
+            self._check_dev(t, sh)
+        n_steps, n_draws = self.edit_plan(timesteps, start, resamplings, jump_length)
+        if noise is not None:
+            self._check_dev(noise)
+            assert noise.dim() == 3 and tuple(noise.shape[1:]) == (n_unique, 3 + P), noise.shape
+        ids = None
+        if group_ids is not None:
+            ids_arr = np.ascontiguousarray(np.asarray(group_ids, dtype=np.int64))
+            assert len(ids_arr) == len(sizes)
+            ids = ids_arr.ctypes.data_as(_i64p)
+        xh_phar = torch.empty((n_unique, 3 + P), dtype=torch.float32, device=dev)
+        xh_pocket = torch.empty((self.n_pocket, 3 + R), dtype=torch.float32, device=dev)
+        z_steps = torch.empty((n_steps, n_unique, 3 + P), dtype=torch.float32, device=dev) if want_steps else None
+        p_steps = torch.empty((n_steps, self.n_pocket, 3), dtype=torch.float32, device=dev) if want_steps else None
+        self.last_pocket_steps = p_steps
+        self._check(self.lib.cmdgen_multi_edit_chain(
+            self.h, _ptr(pocket_x), _ptr(pocket_onehot), len(sizes), sizes.ctypes.data_as(_i64p), w.ctypes.data_as(C.c_void_p),
+            _ptr(phar_x), _ptr(phar_onehot), _ptr(fix_x), _ptr(fix_h), int(timesteps), int(start), int(resamplings), int(jump_length),
+            _ptr(noise), int(noise.shape[0]) if noise is not None else 0, C.c_uint64(seed & (2 ** 64 - 1)), ids, _ptr(xh_phar),
+            _ptr(xh_pocket), _ptr(z_steps), _ptr(p_steps), int(bool(use_graph)), self._stream()), 'cmdgen_multi_edit_chain')
         return xh_phar, xh_pocket, z_steps
 
     SC_COLS = 4                      # include/cmdgen_hip.h: CMDGEN_SC_COLS

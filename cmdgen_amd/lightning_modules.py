@@ -460,6 +460,20 @@ class PharPocketDDPM(nn.Module):
         assert (pocket_ids is None) ^ (ref_ligand is None)
         if not isinstance(self.ddpm, ConditionalDDPM):
             raise NotImplementedError('edit_phars needs the conditional model (mode pocket_conditioning)')
+        keeps, start = self._edit_keeps_and_start(phars, keep, strength, timesteps)
+        pocket = self._pdb_pocket(pdb_file, n_samples, pocket_ids, ref_ligand)
+        pocket_com_before = _scatter_mean(pocket['x'], pocket['mask'], n_samples)
+        phar, fix_x, fix_h = self._edit_phar_and_masks(phars, keeps, start, strength, timesteps, n_samples, num_nodes_phar, pocket)
+        xh_phar, xh_pocket, phar_mask, pocket_mask = self.ddpm.edit(
+            phar, pocket, fix_coords=fix_x, fix_types=fix_h, start=start, resamplings=resamplings, jump_length=jump_length,
+            timesteps=timesteps, seed=seed)
+        # move the points back to the original pocket position (as generate_phars)
+        pocket_com_after = _scatter_mean(xh_pocket[:, :self.x_dims], pocket_mask, n_samples)
+        xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
+        return self._point_lists(xh_phar, phar)
+
+    def _edit_keeps_and_start(self, phars, keep, strength, timesteps):
+        """edit_phars' argument rules: -> (what every given point holds, the start level or None for the prior)."""
         n_given = len(phars)
         if n_given < 1:
             raise ValueError('phars needs at least one point')
@@ -472,9 +486,13 @@ class PharPocketDDPM(nn.Module):
             if not 0.0 < float(strength) <= 1.0:
                 raise ValueError(f'strength={strength} must be in (0, 1]')
             start = max(1, int(round(float(strength) * T)))
-        decoder = list(self.dataset_info['phar_decoder'])
-        pocket = self._pdb_pocket(pdb_file, n_samples, pocket_ids, ref_ligand)
-        pocket_com_before = _scatter_mean(pocket['x'], pocket['mask'], n_samples)
+        return keeps, start
+
+    def _edit_phar_and_masks(self, phars, keeps, start, strength, timesteps, n_samples, num_nodes_phar, pocket):
+        """-> (the phar batch with the given points as the first rows of every sample, fix_x, fix_h); pocket: the one the size prior
+        is conditioned on."""
+        n_given = len(phars)
+        T = self.ddpm.T if timesteps is None else int(timesteps)
         if start is not None and start < T and num_nodes_phar is None:
             num_nodes_phar = n_given                                    # part-way: the given points only (no size prior)
         phar, rows = self._phar_with_given_rows(phars, 'phars', n_samples, num_nodes_phar, pocket)
@@ -485,18 +503,50 @@ class PharPocketDDPM(nn.Module):
         fix_h = torch.zeros_like(fix_x)
         fix_x[rows] = torch.tensor([float(self.KEEP[k][0]) for k in keeps], device=self.device).repeat(n_samples)
         fix_h[rows] = torch.tensor([float(self.KEEP[k][1]) for k in keeps], device=self.device).repeat(n_samples)
-        xh_phar, xh_pocket, phar_mask, pocket_mask = self.ddpm.edit(
-            phar, pocket, fix_coords=fix_x, fix_types=fix_h, start=start, resamplings=resamplings, jump_length=jump_length,
-            timesteps=timesteps, seed=seed)
-        # move the points back to the original pocket position (as generate_phars)
-        pocket_com_after = _scatter_mean(xh_pocket[:, :self.x_dims], pocket_mask, n_samples)
-        xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
+        return phar, fix_x, fix_h
+
+    def _point_lists(self, xh_phar, phar):
+        """One point list per sample, [(type name, (x, y, z))], rows in their given order (utils.batch_to_list goes through an
+        unstable argsort, which may permute a sample's rows)."""
+        decoder = list(self.dataset_info['phar_decoder'])
         x = xh_phar[:, :self.x_dims].detach().cpu()
         phar_type = xh_phar[:, self.x_dims:].argmax(1).detach().cpu()
-        # rows in their given order (utils.batch_to_list goes through an unstable argsort, which may permute a sample's rows)
         sizes = phar['size'].cpu().tolist()
         return [[(decoder[int(t)], tuple(float(v) for v in c)) for t, c in zip(types, coords)]
                 for coords, types in zip(torch.split(x, sizes), torch.split(phar_type, sizes))]
+
+    @torch.no_grad()
+    def edit_phars_multi(self, pdb_files, n_samples, phars, keep='types', strength=None, num_nodes_phar=None, pocket_ids=None,
+                         ref_ligands=None, weights=None, timesteps=None, resamplings=1, jump_length=1, seed=None):
+        """edit_phars for SEVERAL pockets at once (ConditionalDDPM.edit_given_pockets): n_samples variants of a given pharmacophore,
+        each drawn from a chain that sees all the pockets - a dual-target design around known anchor points, or a pharmacophore of
+        one target adapted to a second (strength < 1).
+
+        pdb_files, pocket_ids / ref_ligands and weights as generate_phars_multi takes them: one entry per pocket, the files ALREADY
+        superposed into one common frame.  phars: [(type name, (x, y, z))] in that common frame; keep, strength and num_nodes_phar
+        follow edit_phars' rules (the size prior is conditioned on the FIRST pocket; with strength < 1 the given points only).
+        The result is moved back by the first pocket's shift.  -> edit_phars' point list per sample; keep='both' from the prior is
+        the multi-pocket inpaint_phars."""
+        pdb_files = list(pdb_files)
+        M = len(pdb_files)
+        assert (pocket_ids is None) ^ (ref_ligands is None)
+        if len(pocket_ids if pocket_ids is not None else ref_ligands) != M:
+            raise ValueError(f'{M} pdb_files need {M} entries of pocket_ids or ref_ligands (one per file)')
+        if not isinstance(self.ddpm, ConditionalDDPM):
+            raise NotImplementedError('edit_phars_multi needs the conditional model (mode pocket_conditioning)')
+        keeps, start = self._edit_keeps_and_start(phars, keep, strength, timesteps)
+        pockets = [self._pdb_pocket(f, n_samples, pocket_ids[m] if pocket_ids is not None else None,
+                                    ref_ligands[m] if ref_ligands is not None else None) for m, f in enumerate(pdb_files)]
+        first = pockets[0]
+        pocket_com_before = _scatter_mean(first['x'], first['mask'], n_samples)
+        phar, fix_x, fix_h = self._edit_phar_and_masks(phars, keeps, start, strength, timesteps, n_samples, num_nodes_phar, first)
+        xh_phar, xh_pockets, phar_mask, pocket_masks = self.ddpm.edit_given_pockets(
+            phar, pockets, fix_coords=fix_x, fix_types=fix_h, start=start, resamplings=resamplings, jump_length=jump_length,
+            weights=weights, timesteps=timesteps, seed=seed)
+        # move the points back by the first pocket's shift (every pocket was translated by the same vector)
+        pocket_com_after = _scatter_mean(xh_pockets[0][:, :self.x_dims], pocket_masks[0], n_samples)
+        xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
+        return self._point_lists(xh_phar, phar)
 
     # ------------------------------------------------------------------ scoring
     def _score_model(self):

@@ -177,7 +177,9 @@ int cmdgen_debug_eval_prefix(cmdgen_handle* h, const float* xh_phar, const float
  * "x0" [Nm, 4], "xl" / "acc" [n_layers, Nm, 4].  After a CONDITIONAL evaluation whose pocket output was not requested
  * (eps_pocket == NULL, every chain) the POCKET rows of h / P / Q are undefined unless option "dead_skip" is 0: blocks skip
  * tiles whose result nobody reads, so those rows hold a mix of earlier blocks.  Phar rows, agg (zero) and the positions are
- * always complete; cmdgen_debug_eval_prefix never skips. */
+ * always complete; cmdgen_debug_eval_prefix never skips.
+ * "chain_z" [Nl, 3 + phar_nf]: the z buffer of the last conditional chain (sample, inpaint / edit, multi-pocket, multi-pocket edit) as
+ * its decode left it - for the multi-pocket chains EVERY member's copy of the group's latent, which are equal bit for bit. */
 int cmdgen_debug_read(cmdgen_handle* h, const char* what, float* host, size_t n, cmdgen_stream stream);
 
 /* Fills out_dev[n_nodes * width] with the standard normals the sampler would draw for draw index
@@ -339,6 +341,49 @@ int cmdgen_edit_chain(cmdgen_handle* h, const float* pocket_x, const float* pock
                       const float* noise, int64_t n_draws, uint64_t seed, const int64_t* pocket_ids_host,
                       float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
                       int32_t use_graph, cmdgen_stream stream);
+
+/* Hold or edit given points while sampling ONE pharmacophore for several pockets (ConditionalDDPM.edit_given_pockets): the ops of
+ * cmdgen_edit_chain on the shared latent of cmdgen_multi_pocket_chain.  Layout, groups, weights, group_ids_host and the outputs are
+ * exactly cmdgen_multi_pocket_chain's (B member samples, Nu = one copy of the phar rows per group); start, resamplings, jump_length and
+ * the draw order are exactly cmdgen_edit_chain's, and cmdgen_edit_plan gives n_steps and n_draws (the plan does not depend on the
+ * grouping).  In the normalised space, with P_m the translated pocket of member m, P0_m its normalised input, K the normalised given
+ * rows of the group, w_m the weights, sums over m ascending and "first" the group's first member:
+ *   Init    start == timesteps: cmdgen_multi_pocket_chain's, on draw 0.  start < timesteps: cK = com(K) over the group's rows;
+ *           xh0 = [K.x - cK, K.h] and every P_m.x = P0_m.x - cK;  z = alpha(start / Kt) xh0 + sigma(start / Kt) eps_0;  shift = com(z.x);
+ *           z.x -= shift and every P_m.x -= shift;  the mean-zero check (cmdgen_edit_chain's expressions).  Then ALL rows of phar_x and
+ *           phar_onehot are read.
+ *   Offset  off = com(P_first) - com(P0_first), the frame offset of the GROUP, taken once after the init from the first member's rows
+ *           as cmdgen_inpaint_chain takes it for its one pocket.  Afterwards it only changes by the means subtracted from z.  All
+ *           pockets of a group sit in one frame and move by the same shifts, so this is com(P_m) - com(P0_m) of every member up to
+ *           rounding - and z depends on eps_bar, the draws, K and off alone, so the members' copies of z stay bit-identical.
+ *   A       cmdgen_multi_pocket_chain's op on eps_bar = sum_m w_m eps_m (x columns zero under the batch-wide NaN guard), then the COM
+ *           projection of z and of every P_m;  off -= shift.
+ *   B       z_k = alpha_s K + sigma_s eps_B over the group's rows; z_k.x += off;  z.x = fix_x ? z_k.x : z_u.x,  z.h = fix_h ? z_k.h : z_u.h;
+ *           shift = com(z.x);  z.x -= shift, every P_m.x -= shift, off -= shift.  A group with no mark in either mask skips B.
+ *   C       before a jump back: z = alpha_t'|s z + sigma_t'|s xi_C, then the same projection; off follows it.
+ *   Final   cmdgen_multi_pocket_chain's decode and CoG-drift re-centring.
+ *   phar_x dev [Nu,3], phar_onehot dev [Nu,phar_nf], fix_x, fix_h dev [Nu]: one row per unique phar row, raw, in the pockets' common
+ *          frame; normalised on the device.  From the prior only marked column groups are read.
+ *   noise  dev [n_draws][Nu][3+phar_nf] or NULL: ONE draw per group, op and role, in cmdgen_edit_chain's call order; fewer rows than
+ *          the plan needs are refused.
+ *   Device draws: Philox keyed by (seed, global GROUP id, counter, node of the group) with cmdgen_edit_chain's counters -
+ *          draw 0: 0, A of op i: 1 + i, decode: 1 + n_steps, B of op i: 2 + n_steps + i, C of op i: 2 + 2 n_steps + i.
+ *   z_steps_out dev [n_steps][Nu][3+phar_nf] or NULL (written by the group's first member), pocket_steps_out dev [n_steps][Np][3] or
+ *          NULL (every member's pocket): the state after B of every op, before a jump back.
+ * With every M_g = 1 this is cmdgen_edit_chain, and with no mark, start = timesteps and resamplings = jump_length = 1 it is
+ * cmdgen_multi_pocket_chain, both bit for bit (same seed, device draws or injected noise).
+ * One op is one launch (k_multi_edit_step_count: one workgroup per member, no float atomics, no synchronisation between workgroups)
+ * plus the evaluation.  The chain has a slot of its own: a changed grouping, weight, start or plan prepares it again.
+ * Refused: whatever cmdgen_multi_pocket_chain or cmdgen_edit_chain refuses - the joint model and no_com_projection handles, group
+ * sizes and weights as above, start outside 1 .. timesteps, too few rows of noise, a sample beyond the step's 64 KiB of LDS.
+ * Asynchronous on `stream`; cmdgen_chain_status reports this run's checks, drift and NaN resets. */
+int cmdgen_multi_edit_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
+                            int64_t n_groups, const int64_t* group_size_host, const float* weight_host,
+                            const float* phar_x, const float* phar_onehot, const float* fix_x, const float* fix_h,
+                            int32_t timesteps, int32_t start, int32_t resamplings, int32_t jump_length,
+                            const float* noise, int64_t n_draws, uint64_t seed, const int64_t* group_ids_host,
+                            float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                            int32_t use_graph, cmdgen_stream stream);
 
 /* Scoring for the CONDITIONAL model (ConditionalDDPM.score): the diffusion loss of a GIVEN pharmacophore in its pocket at a
  * list of noise levels, one evaluation per level, all on the device.  In the normalised space, with xh0 the phar rows and P0
