@@ -644,7 +644,8 @@ extern "C" int cmdgen_debug_read(cmdgen_handle* h, const char* what, float* host
     else if (k == "acc") { src = h->work.ACC; have = (size_t)d.L * h->lay.Nm * 4; }
     else if (k == "chain_z") {                       // the last conditional chain's z buffer (the multi-pocket chains: every member's copy)
         const ChainBuf* cb = h->last_chain == CHAIN_PLAIN ? &h->chain : h->last_chain == CHAIN_INPAINT ? &h->inp_chain :
-                             h->last_chain == CHAIN_MULTI ? &h->multi_chain : h->last_chain == CHAIN_MULTI_EDIT ? &h->medit_chain : nullptr;
+                             h->last_chain == CHAIN_MULTI ? &h->multi_chain : h->last_chain == CHAIN_MULTI_EDIT ? &h->medit_chain :
+                             h->last_chain == CHAIN_MULTI_SCORE ? &h->mscore_chain : nullptr;     // (the last level's z of the multi-pocket scoring chain)
         if (!cb || !cb->z_phar || h->chains[h->last_chain].n_steps < 0) return fail(h, CMDGEN_ESTATE, "no conditional chain has run on this layout");
         src = cb->z_phar; have = (size_t)h->lay.Nl * (3 + d.P);
     }
@@ -913,7 +914,8 @@ extern "C" int cmdgen_sample_chain(cmdgen_handle* h, const float* pocket_x, cons
 // ---------------------------------------------------------------------------------
 static_assert(CMDGEN_MAX_GROUP == MAX_GROUP, "the public bound and the kernels' agree");
 
-// the group tables of a call, per member (GroupTab), checked: what cmdgen_multi_pocket_chain and cmdgen_multi_edit_chain refuse alike
+// the group tables of a call, per member (GroupTab), checked: what cmdgen_multi_pocket_chain, cmdgen_multi_edit_chain and
+// cmdgen_multi_score_chain refuse alike
 struct GroupPlan {
     std::vector<int> first, size, ubase, gfirst;
     std::vector<int64_t> gid;
@@ -1409,6 +1411,30 @@ static int alloc_score(cmdgen_handle* h, ChainSlot& k, const float* tables, int)
     return 0;
 }
 
+// what cmdgen_score_chain and cmdgen_multi_score_chain check of a level list alike, and its rows: one per level
+// (alpha_t, sigma_t, t == 0, t / T), then (alpha_T, sigma_T, 0, 1) for the prior KL sums; alpha and sigma are the caller's when it
+// supplies them (its own fp32 evaluation of the schedule, as cmdgen_set_step_table)
+static int build_level_rows(cmdgen_handle* h, int32_t n_levels, const int32_t* t_levels_host, const float* level_coef_host,
+                            std::vector<float>& tables) {
+    if (n_levels < 1) return fail(h, CMDGEN_EINVAL, "n_levels=%d must be >= 1", n_levels);
+    const int T = h->cfg.timesteps;
+    for (int i = 0; i < n_levels; ++i)
+        if (t_levels_host[i] < 0 || t_levels_host[i] > T)
+            return fail(h, CMDGEN_EINVAL, "level %d is t=%d: levels must be in [0, %d]", i, t_levels_host[i], T);
+    if (cmdgen_score_step_lds(h->lay, h->dims) > 64 * 1024)
+        return fail(h, CMDGEN_EINVAL, "a sample has %d nodes: the scoring step keeps a sample's positions, z and row sums in LDS (64 KiB)", h->lay.max_n);
+    tables.assign((size_t)(n_levels + 1) * 4, 0.f);
+    for (int i = 0; i <= n_levels; ++i) {
+        const int t = i < n_levels ? t_levels_host[i] : T;
+        const float g = h->gamma[(size_t)t];
+        tables[4 * i + 0] = level_coef_host ? level_coef_host[2 * i] : sqrtf(sigmoid_h(-g));
+        tables[4 * i + 1] = level_coef_host ? level_coef_host[2 * i + 1] : sqrtf(sigmoid_h(g));
+        tables[4 * i + 2] = (i < n_levels && t == 0) ? 1.f : 0.f;
+        tables[4 * i + 3] = (float)t / (float)T;
+    }
+    return 0;
+}
+
 extern "C" int cmdgen_score_chain(cmdgen_handle* h, const float* phar_x, const float* phar_onehot,
                                   const float* pocket_x, const float* pocket_onehot,
                                   int32_t n_levels, const int32_t* t_levels_host, const float* level_coef_host,
@@ -1419,24 +1445,8 @@ extern "C" int cmdgen_score_chain(cmdgen_handle* h, const float* phar_x, const f
     if (h->dims.no_com) return fail(h, CMDGEN_ESTATE, "scoring is not supported for no_com_projection handles (SimpleConditionalDDPM)");
     if (!phar_x || !phar_onehot || !pocket_x || !pocket_onehot || !t_levels_host || !level_terms_out || !kl_sums_out)
         return fail(h, CMDGEN_EINVAL, "null pointer");
-    if (n_levels < 1) return fail(h, CMDGEN_EINVAL, "n_levels=%d must be >= 1", n_levels);
-    const int T = h->cfg.timesteps;
-    for (int i = 0; i < n_levels; ++i)
-        if (t_levels_host[i] < 0 || t_levels_host[i] > T)
-            return fail(h, CMDGEN_EINVAL, "level %d is t=%d: levels must be in [0, %d]", i, t_levels_host[i], T);
-    if (cmdgen_score_step_lds(h->lay, h->dims) > 64 * 1024)
-        return fail(h, CMDGEN_EINVAL, "a sample has %d nodes: the scoring step keeps a sample's positions, z and row sums in LDS (64 KiB)", h->lay.max_n);
-    // one row per level: (alpha_t, sigma_t, t == 0, t / T), then (alpha_T, sigma_T, 0, 1) for the prior KL sums; alpha and sigma are the
-    // caller's when it supplies them (its own fp32 evaluation of the schedule, as cmdgen_set_step_table)
-    std::vector<float> tables((size_t)(n_levels + 1) * 4);
-    for (int i = 0; i <= n_levels; ++i) {
-        const int t = i < n_levels ? t_levels_host[i] : T;
-        const float g = h->gamma[(size_t)t];
-        tables[4 * i + 0] = level_coef_host ? level_coef_host[2 * i] : sqrtf(sigmoid_h(-g));
-        tables[4 * i + 1] = level_coef_host ? level_coef_host[2 * i + 1] : sqrtf(sigmoid_h(g));
-        tables[4 * i + 2] = (i < n_levels && t == 0) ? 1.f : 0.f;
-        tables[4 * i + 3] = (float)t / (float)T;
-    }
+    std::vector<float> tables;
+    rc = build_level_rows(h, n_levels, t_levels_host, level_coef_host, tables); if (rc) return rc;
     const float alpha_T = tables[4 * (size_t)n_levels];
     const hipStream_t caller = (hipStream_t)stream;
     hipStream_t s; EvalLaunch a;
@@ -1458,6 +1468,67 @@ extern "C" int cmdgen_score_chain(cmdgen_handle* h, const float* phar_x, const f
     });
     if (rc) return rc;
     cmdgen_launch_score_final(h->lay, d, c, sc, h->work, h->work.eps_tmp, s);
+    return end_chain(h, caller, s);
+}
+
+// ---------------------------------------------------------------------------------
+// scoring for several pockets at once: ConditionalDDPM.score_given_pockets (kernels_score.hip; the definition is in
+// include/cmdgen_hip.h).  The level rows are the scoring chain's, the group tables the multi-pocket chain's.
+// ---------------------------------------------------------------------------------
+// the slot's table block: the level rows (n_levels + 1) | the group tables
+static int alloc_multi_score(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_levels) {
+    int rc = alloc_chain_buf(h, k, h->mscore_chain, tables); if (rc) return rc;
+    const Dims& d = h->dims;
+    const Layout& L = h->lay;
+    void* q;
+    rc = dev_alloc(h, k.allocs, &q, (size_t)L.Nl * (3 + d.P) * sizeof(float), true); if (rc) return rc; h->mscore.xh0 = (const float*)q;
+    rc = dev_alloc(h, k.allocs, &q, (size_t)L.Np * 3 * sizeof(float), true); if (rc) return rc; h->mscore.pocket0 = (const float*)q;
+    point_group_tab(h->mscore_groups, tables + (size_t)(n_levels + 1) * 4, (size_t)L.B);
+    return 0;
+}
+
+extern "C" int cmdgen_multi_score_chain(cmdgen_handle* h, const float* phar_x, const float* phar_onehot,
+                                        const float* pocket_x, const float* pocket_onehot,
+                                        int64_t n_groups, const int64_t* group_size_host, const float* weight_host,
+                                        int32_t n_levels, const int32_t* t_levels_host, const float* level_coef_host,
+                                        const float* noise, uint64_t seed, const int64_t* group_ids_host,
+                                        float* group_terms_out, float* member_terms_out, float* kl_sums_out,
+                                        int32_t use_graph, cmdgen_stream stream) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (h->dims.joint) return fail(h, CMDGEN_ESTATE, "scoring is not supported for the joint model (update_pocket_coords=1): its loss has the pocket's own terms");
+    if (h->dims.no_com) return fail(h, CMDGEN_ESTATE, "scoring is not supported for no_com_projection handles (SimpleConditionalDDPM)");
+    if (!phar_x || !phar_onehot || !pocket_x || !pocket_onehot || !group_size_host || !weight_host || !t_levels_host || !group_terms_out ||
+        !kl_sums_out)
+        return fail(h, CMDGEN_EINVAL, "null pointer");
+    std::vector<float> tables;
+    rc = build_level_rows(h, n_levels, t_levels_host, level_coef_host, tables); if (rc) return rc;
+    GroupPlan gp;
+    rc = build_group_plan(h, n_groups, group_size_host, weight_host, group_ids_host, gp); if (rc) return rc;
+    const float alpha_T = tables[4 * (size_t)n_levels];
+    append_group_tables(tables, gp, weight_host, h->lay.B);
+    const hipStream_t caller = (hipStream_t)stream;
+    hipStream_t s; EvalLaunch a;
+    rc = begin_chain(h, CHAIN_MULTI_SCORE, tables, n_levels, alloc_multi_score, gp.gid.data(), use_graph, caller, &s, &a); if (rc) return rc;
+    ChainSlot& k = h->chains[CHAIN_MULTI_SCORE];
+    const Dims& d = h->dims;
+    ChainBuf c = h->mscore_chain;
+    c.noise = noise; c.seed = seed; c.z_steps = nullptr; c.pocket_steps = nullptr;
+    ScoreBuf sc = h->mscore;
+    sc.out = group_terms_out;
+    GroupTab gt = h->mscore_groups;
+    gt.G = gp.G; gt.Nu = (int)gp.Nu;
+    cmdgen_launch_multi_score_init(h->lay, d, c, sc, gt, alpha_T, phar_x, phar_onehot, pocket_x, pocket_onehot, kl_sums_out, s);
+    build_pocket_cache(h, k, c, a, s);
+    a.skip_count = 1;                                // k_multi_score_step ran pass 1 of the graph
+    // the level rows, the group tables and the clean rows are slot buffers (a changed level list, grouping or weight prepares the slot
+    // again and drops its graph); the captured steps read the caller's draws and write its outputs
+    const void* key[6] = {noise, group_terms_out, member_terms_out, nullptr, nullptr, s};
+    rc = run_steps(h, k, key, seed, n_levels, use_graph, s, [&](hipStream_t ss) {
+        cmdgen_launch_multi_score_step(h->lay, d, c, sc, gt, h->work, h->work.eps_tmp, member_terms_out, ss);
+        cmdgen_launch_eval(a, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, ss, nullptr);
+    });
+    if (rc) return rc;
+    cmdgen_launch_multi_score_final(h->lay, d, c, sc, gt, h->work, h->work.eps_tmp, member_terms_out, s);
     return end_chain(h, caller, s);
 }
 

@@ -207,6 +207,8 @@ struct ScoreBuf {               // scoring chain (cmdgen_score_chain), beside a 
     const float* xh0;           // [Nl][3+P]   clean normalised phar rows, x centred on the phar centre of mass
     const float* pocket0;       // [Np][3]     normalised pocket positions in the same frame (the features sit in ChainBuf::xh_pocket)
     float* out;                 // [n_levels][B][CMDGEN_SC_COLS] raw sums per (level, sample): see include/cmdgen_hip.h
+                                // (cmdgen_multi_score_chain: [n_levels][G] rows, one per GROUP; xh0 holds every member's copy of its group's rows,
+                                // ChainBuf::noise is [n_levels][Nu][3+P])
 };
 enum { SC_ERR = 0, SC_ERR_X = 1, SC_LOG_PH = 2, SC_RESET = 3, SC_COLS = 4 };     // = CMDGEN_SC_COLS
 

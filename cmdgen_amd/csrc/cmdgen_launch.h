@@ -93,3 +93,10 @@ void cmdgen_launch_score_step(const Layout& lay, const Dims& d, const ChainBuf& 
 void cmdgen_launch_score_final(const Layout& lay, const Dims& d, const ChainBuf& c, const ScoreBuf& sc, const Work& w, const float* eps,
                                hipStream_t s);
 size_t cmdgen_score_step_lds(const Layout& lay, const Dims& d);
+// ... and the multi-pocket scoring chain: groups of samples that share the clean rows and the draws (member_out: [n_levels][B][SC_COLS] or null)
+void cmdgen_launch_multi_score_init(const Layout& lay, const Dims& d, const ChainBuf& c, const ScoreBuf& sc, const GroupTab& g, float alpha_T,
+                                    const float* phx, const float* phoh, const float* px, const float* poh, float* kl_sums, hipStream_t s);
+void cmdgen_launch_multi_score_step(const Layout& lay, const Dims& d, const ChainBuf& c, const ScoreBuf& sc, const GroupTab& g, const Work& w,
+                                    const float* eps, float* member_out, hipStream_t s);
+void cmdgen_launch_multi_score_final(const Layout& lay, const Dims& d, const ChainBuf& c, const ScoreBuf& sc, const GroupTab& g, const Work& w,
+                                     const float* eps, float* member_out, hipStream_t s);

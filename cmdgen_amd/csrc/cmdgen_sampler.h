@@ -29,6 +29,26 @@ __device__ __forceinline__ void record_com_check(unsigned int* slot2, const floa
     if (lane == 0) { atomic_max_pos(slot2, mx); atomic_max_pos(slot2 + 1, s); }
 }
 
+// ---- groups of samples that share one latent (kernels_multi.hip, and the multi-pocket scoring chain of kernels_score.hip)
+// one draw per group and op: row ubase + local of the [Nu] unique rows, or Philox keyed by the group's id (Layout::pocket_gid holds it
+// for every member)
+__device__ __forceinline__ float draw_group(const ChainBuf& c, const Layout& lay, const GroupTab& g, int draw_idx, int b,
+                                            int local, int comp, int ld) {
+    if (c.noise) return c.noise[((size_t)draw_idx * g.Nu + g.ubase[b] + local) * ld + comp];
+    float z[4];
+    philox_normal4(c.seed, (uint32_t)lay.pocket_gid[b], (uint32_t)(lay.pocket_gid[b] >> 32),
+                   (uint32_t)draw_idx, (uint32_t)(local * 4 + (comp >> 2)), z);
+    return z[comp & 3];
+}
+
+// eps_bar of element idx of the group's rows (eps: [Nl][ld], a member's rows start at its phar_base)
+__device__ __forceinline__ float combine_eps(const Layout& lay, const GroupTab& g, const float* __restrict__ eps, int first, int M,
+                                             int ld, int idx) {
+    float e = g.weight[first] * eps[(size_t)lay.phar_base[first] * ld + idx];
+    for (int m = 1; m < M; ++m) e = e + g.weight[first + m] * eps[(size_t)lay.phar_base[first + m] * ld + idx];
+    return e;
+}
+
 // ---- parts of the op kernels that hold a sample's z and positions in LDS (k_inpaint_step_count, k_multi_edit_step_count)
 // the phar centre of mass of the sample's z (LDS, index order, as index_add_) on threads 0..2 -> s_mean
 __device__ __forceinline__ void phar_mean(const float* s_z, int nl, int ld, int tid, float* s_mean) {

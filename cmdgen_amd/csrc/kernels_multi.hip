@@ -8,25 +8,6 @@
 // pocket and counts its own edges.  Sums run in index order as in kernels_ddpm.hip; with M = 1 every value is that file's, bit for bit.
 #include "cmdgen_sampler.h"
 
-// one draw per group and op: row ubase + local of the [Nu] unique rows, or Philox keyed by the group's id (Layout::pocket_gid holds it
-// for every member)
-__device__ __forceinline__ float draw_group(const ChainBuf& c, const Layout& lay, const GroupTab& g, int draw_idx, int b,
-                                            int local, int comp, int ld) {
-    if (c.noise) return c.noise[((size_t)draw_idx * g.Nu + g.ubase[b] + local) * ld + comp];
-    float z[4];
-    philox_normal4(c.seed, (uint32_t)lay.pocket_gid[b], (uint32_t)(lay.pocket_gid[b] >> 32),
-                   (uint32_t)draw_idx, (uint32_t)(local * 4 + (comp >> 2)), z);
-    return z[comp & 3];
-}
-
-// eps_bar of element idx of the group's rows (eps: [Nl][ld], a member's rows start at its phar_base)
-__device__ __forceinline__ float combine_eps(const Layout& lay, const GroupTab& g, const float* __restrict__ eps, int first, int M,
-                                             int ld, int idx) {
-    float e = g.weight[first] * eps[(size_t)lay.phar_base[first] * ld + idx];
-    for (int m = 1; m < M; ++m) e = e + g.weight[first + m] * eps[(size_t)lay.phar_base[first + m] * ld + idx];
-    return e;
-}
-
 // subtract the centre of mass of the member's z from its z and its pocket (remove_com of kernels_ddpm.hip)
 __device__ __forceinline__ void remove_com_member(float* zx, int ld, int pb, int nl, float* px, int ldq, int qb, int np, int lane) {
     float mean = 0.f;

@@ -527,6 +527,92 @@ class ConditionalDDPM(EnVariationalDiffusion):
             keep += ['t_levels', 'level_terms', 'level_sums']
         return {k: torch.from_numpy(np.ascontiguousarray(out[k])).to(device) for k in keep}
 
+    @torch.no_grad()
+    def score_given_pockets(self, phar, pockets, weights=None, timesteps=None, repeats=1, noise=None, seed=None, group_ids=None,
+                            return_levels=False, return_members=False):
+        """How likely the model finds a GIVEN pharmacophore under SEVERAL pockets at once: ``score`` for the sampler that
+        ``sample_given_pockets`` runs, whose denoiser is eps_bar = sum_m w_m eps_m - the bound that ranks what sample_given_pockets or
+        edit_given_pockets drew, or compares a known pharmacophore across target and anti-target.  (The sum of per-pocket ``score``s is
+        not this quantity: the error of the combined prediction is not the sum of the members' errors.)
+
+        phar: dict(x [Nu,3], one_hot [Nu,P], size [G], mask [Nu]) batched over the G groups, in the pockets' common frame; pockets,
+        weights and group_ids as in sample_given_pockets; timesteps, repeats, seed and the NaN-reset warning as in score; noise
+        [repeats * (timesteps + 1), Nu, 3+P] (or [repeats, timesteps + 1, Nu, 3+P]): ONE draw per group and level.  The whole level
+        loop runs on the device (cmdgen_multi_score_chain; its header gives the definition and the Philox counters).  With one pocket
+        this is score, bit for bit.
+        -> score's dict per group [G]; log_pN = sum_m w_m log p(N_phar | N_pocket_m), the geometric mixture's term.  With
+        return_members also member_nll, member_loss_t, member_loss_0_x, member_log_pN [G, M]: every pocket's own score on the SAME
+        draws (what score gives for that pocket with the group's draws).  With return_levels also t_levels, level_terms
+        [R, timesteps + 1, G], level_sums [R, timesteps + 1, G, 4] and, with return_members, member_level_sums [R, timesteps + 1, G, M, 4]."""
+        from .. import scoring
+        pockets, M, G = self._checked_pockets(pockets)
+        K = self.T if timesteps is None else int(timesteps)
+        levels = scoring.level_list(self.T, K)                        # ValueError when K does not divide T
+        R = int(repeats)
+        if R < 1:
+            raise ValueError(f'repeats={repeats} must be >= 1')
+        nph = phar['size'].detach().to('cpu', torch.int64).numpy().reshape(-1)
+        if len(nph) != G:
+            raise ValueError(f'phar has {len(nph)} samples, pocket {G}')
+        pm = phar['mask']
+        if pm.numel() > 1 and bool((pm[1:] < pm[:-1]).any()):
+            raise ValueError('batch masks must be ascending and contiguous')
+        w = self.group_weights(weights, G, M)
+        device = pockets[0]['x'].device
+        n_phar, ld = int(nph.sum()), self.n_dims + self.phar_nf
+        f32 = lambda t: t.detach().to(device, torch.float32).contiguous()
+        if tuple(phar['x'].shape) != (n_phar, self.n_dims) or tuple(phar['one_hot'].shape) != (n_phar, self.phar_nf):
+            raise ValueError(f"phar x / one_hot have shapes {tuple(phar['x'].shape)} / {tuple(phar['one_hot'].shape)}: expected "
+                             f'[{n_phar}, {self.n_dims}] / [{n_phar}, {self.phar_nf}] (sum(size) rows)')
+        if noise is not None:
+            noise = f32(noise)
+            if noise.dim() == 4:
+                noise = noise.reshape(-1, noise.shape[2], noise.shape[3])
+            if tuple(noise.shape) != (R * (K + 1), n_phar, ld):
+                raise ValueError(f'noise has shape {tuple(noise.shape)}: {R} x {K + 1} levels need [{R * (K + 1)}, {n_phar}, {ld}]')
+        sizes, rows, px, poh = self._member_layout(pockets, M, G)
+        self.refresh_learned_schedule()
+        gamma = np.asarray(self.gamma_table_host(), dtype=np.float32)
+        log_pn = self.size_distribution._table(1, torch.device('cpu')).detach().to(torch.float32).numpy()
+        tab = scoring.level_table(gamma, self.T, self.n_dims, self.norm_values, levels)
+        h = self.dynamics.hip_handle()
+        h.set_layout(np.repeat(nph, M), sizes.reshape(-1))
+        if seed is None:
+            seed = fresh_seed()
+        args = (f32(phar['x']), f32(phar['one_hot']), px, poh, [M] * G, w.reshape(-1))
+        run = lambda: h.multi_score_chain(*args, np.tile(levels, R), level_coef=scoring.level_coef(tab, R), noise=noise, seed=seed,
+                                          group_ids=group_ids, want_members=return_members, use_graph=self.use_hip_graph)
+        (terms, members, kl), st = h.run_range_guarded(run, h.chain_status)
+        self.last_chain_status = st
+        assert st['max_rel_com_error'] < 1e-2, f"Mean is not zero, relative_error {st['max_rel_com_error']}"
+        terms = terms.cpu().numpy().reshape(R, K + 1, G, -1)
+        if members is not None:
+            members = members.cpu().numpy().reshape(R, K + 1, G, M, -1)
+        out = scoring.assemble_groups(terms, members, kl.cpu().numpy(), w, gamma, log_pn, self.T, self.n_dims, self.norm_values, levels,
+                                      nph, sizes)
+        reset = terms[..., scoring.SC_RESET].max(axis=2) > 0             # [R, K + 1]
+        if st['nan_resets'] or reset.any():
+            import warnings
+            bad = sorted({int(levels[k]) for k in np.nonzero(reset.any(axis=0))[0]})
+            warnings.warn(f'score_given_pockets: the NaN guard reset the network output at {int(reset.sum())} level evaluation(s) '
+                          f'(t = {bad}): the reference resets the whole batch there, so nll is NaN for this batch', RuntimeWarning,
+                          stacklevel=2)
+            out['nll'] = np.full_like(out['nll'], np.nan)
+            out['nll_repeats'][reset.any(axis=1)] = np.nan
+            if members is not None:
+                out['member_nll'] = np.full_like(out['member_nll'], np.nan)
+        keep = ['nll', 'loss_t', 'loss_0_x', 'loss_0_h', 'neg_log_const_0', 'kl_prior', 'delta_log_px', 'log_pN']
+        keep += [k for k in out if k.endswith('_repeats')]
+        if return_members:
+            keep += ['member_nll', 'member_loss_t', 'member_loss_0_x', 'member_log_pN']
+        if return_levels:
+            out['level_sums'] = terms                                       # the raw sums (include/cmdgen_hip.h: CMDGEN_SC_COLS columns)
+            keep += ['t_levels', 'level_terms', 'level_sums']
+            if return_members:
+                out['member_level_sums'] = members
+                keep += ['member_level_sums']
+        return {k: torch.from_numpy(np.ascontiguousarray(out[k])).to(device) for k in keep}
+
     def _chain_frame(self, h, z_steps, step, xh_phar, xh_pocket):
         """The frame of the state after op `step`: unnormalize_z (:897-906) of z and of the pocket the op left; the
         pocket's features are fixed."""
@@ -591,3 +677,7 @@ class SimpleConditionalDDPM(ConditionalDDPM):
     def edit_given_pockets(self, *args, **kwargs):
         raise NotImplementedError('edit_given_pockets is not implemented for SimpleConditionalDDPM (no centre-of-mass projection: the '
                                   'shared latent has no frame of its own); use ConditionalDDPM')
+
+    def score_given_pockets(self, *args, **kwargs):
+        raise NotImplementedError('score_given_pockets is not implemented for SimpleConditionalDDPM (the scoring chain projects every '
+                                  'level to the centre-of-mass-free subspace); use ConditionalDDPM')

@@ -558,6 +558,10 @@ class EnVariationalDiffusion(nn.Module):
         raise NotImplementedError('edit_given_pockets is not implemented for the joint model (its pocket nodes diffuse with the '
                                   'latent, so several pockets cannot share one); use ConditionalDDPM')
 
+    def score_given_pockets(self, *args, **kwargs):
+        raise NotImplementedError('score_given_pockets is not implemented for the joint model: its loss has the pocket\'s own terms, '
+                                  'and its pocket nodes diffuse with the latent; use ConditionalDDPM')
+
     @torch.no_grad()
     def inpaint(self, phar, pocket, phar_fixed, pocket_fixed, resamplings=1, jump_length=1, return_frames=1,
                 timesteps=None, noise=None, seed=None, pocket_ids=None):

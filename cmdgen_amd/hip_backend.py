@@ -72,6 +72,8 @@ SYMBOLS = [
     ('cmdgen_multi_edit_chain', C.c_int, [_vp, _fp, _fp, C.c_int64, _i64p, _vp, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, _fp, C.c_int64, C.c_uint64, _i64p, _fp, _fp, _fp, _fp, C.c_int32, _vp]),
     ('cmdgen_score_chain', C.c_int, [_vp, _fp, _fp, _fp, _fp, C.c_int32, _vp, _vp, _fp, C.c_uint64, _i64p, _fp, _fp, C.c_int32, _vp]),
+    ('cmdgen_multi_score_chain', C.c_int, [_vp, _fp, _fp, _fp, _fp, C.c_int64, _i64p, _vp, C.c_int32, _vp, _vp, _fp, C.c_uint64, _i64p,
+                                           _fp, _fp, _fp, C.c_int32, _vp]),
     ('cmdgen_param_count', C.c_int, [_vp, _i64p]),
     ('cmdgen_param_offset', C.c_int, [_vp, C.c_char_p, _i64p, _i64p]),
     ('cmdgen_train_forward', C.c_int, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),
@@ -571,6 +573,47 @@ class Handle:
             coef.ctypes.data_as(C.c_void_p) if coef is not None else None, _ptr(noise), C.c_uint64(seed & (2 ** 64 - 1)),
             self._pocket_ids(pocket_ids), _ptr(terms), _ptr(kl), int(bool(use_graph)), self._stream()), 'cmdgen_score_chain')
         return terms, kl
+
+    def multi_score_chain(self, phar_x, phar_onehot, pocket_x, pocket_onehot, group_sizes: Sequence[int], weights, t_levels,
+                          level_coef=None, noise=None, seed: int = 0, group_ids: Optional[Sequence[int]] = None,
+                          want_members: bool = False, use_graph: bool = True):
+        """score_chain for groups of pockets (cmdgen_multi_score_chain): the layout, group_sizes, weights and group_ids of
+        multi_pocket_chain; phar_x [Nu,3], phar_onehot [Nu,P] one row per unique phar row (Nu = one copy of the rows per group), in the
+        pockets' common frame; t_levels and level_coef as score_chain; noise [n_levels, Nu, 3+P] or None (one draw per group and level).
+        -> (group_terms [n_levels, groups, SC_COLS], member_terms [n_levels, batch, SC_COLS] or None, kl_sums [groups, 2])."""
+        import torch
+        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
+        sizes = np.ascontiguousarray(np.asarray(group_sizes, dtype=np.int64))
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32))
+        assert sizes.ndim == 1 and len(sizes) >= 1 and w.shape == (self.batch,), (sizes.shape, w.shape, self.batch)
+        firsts = np.minimum(np.concatenate([[0], np.cumsum(sizes)[:-1]]), self.batch - 1)      # (as multi_pocket_chain)
+        n_unique = int(self.num_phar_host[firsts].sum())
+        shapes = [(n_unique, 3), (n_unique, P), (self.n_pocket, 3), (self.n_pocket, R)]
+        for t, sh in zip((phar_x, phar_onehot, pocket_x, pocket_onehot), shapes):
+            self._check_dev(t, sh)
+        lv = np.ascontiguousarray(np.asarray(t_levels, dtype=np.int32).reshape(-1))
+        n = len(lv)
+        coef = None
+        if level_coef is not None:
+            coef = np.ascontiguousarray(level_coef, dtype=np.float32)
+            assert coef.shape == (n + 1, 2), coef.shape
+        if noise is not None:
+            self._check_dev(noise, (n, n_unique, 3 + P))
+        ids = None
+        if group_ids is not None:
+            ids_arr = np.ascontiguousarray(np.asarray(group_ids, dtype=np.int64))
+            assert len(ids_arr) == len(sizes)
+            ids = ids_arr.ctypes.data_as(_i64p)
+        dev = phar_x.device
+        terms = torch.zeros((n, len(sizes), self.SC_COLS), dtype=torch.float32, device=dev)
+        members = torch.zeros((n, self.batch, self.SC_COLS), dtype=torch.float32, device=dev) if want_members else None
+        kl = torch.zeros((len(sizes), 2), dtype=torch.float32, device=dev)
+        self._check(self.lib.cmdgen_multi_score_chain(
+            self.h, _ptr(phar_x), _ptr(phar_onehot), _ptr(pocket_x), _ptr(pocket_onehot), len(sizes), sizes.ctypes.data_as(_i64p),
+            w.ctypes.data_as(C.c_void_p), n, lv.ctypes.data_as(C.c_void_p), coef.ctypes.data_as(C.c_void_p) if coef is not None else None,
+            _ptr(noise), C.c_uint64(seed & (2 ** 64 - 1)), ids, _ptr(terms), _ptr(members), _ptr(kl), int(bool(use_graph)),
+            self._stream()), 'cmdgen_multi_score_chain')
+        return terms, members, kl
 
     # ---- training step (flat parameter / gradient buffers are torch tensors owned by the caller)
     def param_count(self) -> int:

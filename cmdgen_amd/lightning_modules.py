@@ -564,6 +564,24 @@ class PharPocketDDPM(nn.Module):
         return ddpm.score(phar, pocket, timesteps=timesteps, repeats=repeats, noise=noise, seed=seed, pocket_ids=pocket_ids,
                           return_levels=return_levels)
 
+    def _candidate_batch(self, candidates):
+        """The phar batch of score_phars / score_phars_multi: one sample per candidate point list, checked."""
+        decoder = list(self.dataset_info['phar_decoder'])
+        if len(candidates) < 1:
+            raise ValueError('no candidates')
+        for cand in candidates:
+            if len(cand) < 1:
+                raise ValueError('a candidate needs at least one point')
+            for name, _ in cand:
+                if name not in decoder:
+                    raise ValueError(f'unknown pharmacophore type {name!r}: expected one of {decoder}')
+        n = len(candidates)
+        sizes = torch.tensor([len(c) for c in candidates], device=self.device, dtype=INT_TYPE)
+        x = torch.tensor([list(map(float, xyz)) for c in candidates for _, xyz in c], device=self.device, dtype=FLOAT_TYPE).reshape(-1, 3)
+        types = torch.tensor([decoder.index(name) for c in candidates for name, _ in c], device=self.device, dtype=torch.int64)
+        return {'x': x, 'one_hot': F.one_hot(types, self.phar_nf).to(FLOAT_TYPE), 'size': sizes,
+                'mask': utils.num_nodes_to_batch_mask(n, sizes, self.device)}
+
     @torch.no_grad()
     def score_phars(self, pdb_file, candidates, pocket_ids=None, ref_ligand=None, timesteps=None, repeats=1, seed=None):
         """Score candidate pharmacophores in the pocket of a PDB file (ConditionalDDPM.score): lower nll = the model finds the
@@ -577,20 +595,30 @@ class PharPocketDDPM(nn.Module):
         the points of one sample.  To rank generated samples go through ddpm.sample_given_pocket -> ddpm.score."""
         assert (pocket_ids is None) ^ (ref_ligand is None)
         ddpm = self._score_model()
-        decoder = list(self.dataset_info['phar_decoder'])
-        if len(candidates) < 1:
-            raise ValueError('no candidates')
-        for cand in candidates:
-            if len(cand) < 1:
-                raise ValueError('a candidate needs at least one point')
-            for name, _ in cand:
-                if name not in decoder:
-                    raise ValueError(f'unknown pharmacophore type {name!r}: expected one of {decoder}')
-        n = len(candidates)
-        pocket = self._pdb_pocket(pdb_file, n, pocket_ids, ref_ligand)
-        sizes = torch.tensor([len(c) for c in candidates], device=self.device, dtype=INT_TYPE)
-        x = torch.tensor([list(map(float, xyz)) for c in candidates for _, xyz in c], device=self.device, dtype=FLOAT_TYPE).reshape(-1, 3)
-        types = torch.tensor([decoder.index(name) for c in candidates for name, _ in c], device=self.device, dtype=torch.int64)
-        phar = {'x': x, 'one_hot': F.one_hot(types, self.phar_nf).to(FLOAT_TYPE), 'size': sizes,
-                'mask': utils.num_nodes_to_batch_mask(n, sizes, self.device)}
+        phar = self._candidate_batch(candidates)
+        pocket = self._pdb_pocket(pdb_file, len(candidates), pocket_ids, ref_ligand)
         return ddpm.score(phar, pocket, timesteps=timesteps, repeats=repeats, seed=seed)
+
+    @torch.no_grad()
+    def score_phars_multi(self, pdb_files, candidates, pocket_ids=None, ref_ligands=None, weights=None, timesteps=None, repeats=1,
+                          seed=None, return_members=False):
+        """score_phars against SEVERAL pockets at once (ConditionalDDPM.score_given_pockets): how likely the model finds each
+        candidate under all the pockets together - to rank what generate_phars_multi or edit_phars_multi drew, or to compare a
+        known pharmacophore across a target and an anti-target (return_members gives every pocket's own score on the same draws).
+
+        pdb_files, pocket_ids / ref_ligands and weights as generate_phars_multi takes them: one entry per pocket, the files ALREADY
+        superposed into one common frame.  candidates as score_phars takes them, in that common frame; every candidate is one group
+        and candidate i draws with global group id i.  -> the dict of ConditionalDDPM.score_given_pockets, entry i of every tensor
+        belonging to candidates[i]."""
+        pdb_files = list(pdb_files)
+        M = len(pdb_files)
+        assert (pocket_ids is None) ^ (ref_ligands is None)
+        if len(pocket_ids if pocket_ids is not None else ref_ligands) != M:
+            raise ValueError(f'{M} pdb_files need {M} entries of pocket_ids or ref_ligands (one per file)')
+        ddpm = self._score_model()
+        n = len(candidates)
+        phar = self._candidate_batch(candidates)
+        pockets = [self._pdb_pocket(f, n, pocket_ids[m] if pocket_ids is not None else None,
+                                    ref_ligands[m] if ref_ligands is not None else None) for m, f in enumerate(pdb_files)]
+        return ddpm.score_given_pockets(phar, pockets, weights=weights, timesteps=timesteps, repeats=repeats, seed=seed,
+                                        return_members=return_members)

@@ -97,3 +97,43 @@ def assemble(level_terms, kl_sums, gamma, log_pn, T: int, n_dims: int, norm_valu
            'nll_repeats': nll, 'loss_t_repeats': loss_t, 'loss_0_x_repeats': loss_0_x, 'loss_0_h_repeats': loss_0_h,
            'level_terms': weighted, 't_levels': t_levels.astype(np.int64)}
     return out
+
+
+def assemble_groups(group_terms, member_terms, kl_sums, weights, gamma, log_pn, T: int, n_dims: int, norm_values, t_levels, n_phar,
+                    n_pocket) -> Dict[str, np.ndarray]:
+    """The assembly for groups of pockets that share one pharmacophore (cmdgen_multi_score_chain; ConditionalDDPM.score_given_pockets).
+    group_terms [R, n_levels, G, >= 3], member_terms [R, n_levels, G, M, >= 3] or None, kl_sums [G, 2], weights float32 [G, M]
+    (normalised), n_phar [G], n_pocket [G, M] -> ``assemble``'s dict per group [G] on the group's raw sums, with
+        log_pN = sum_m w_m log p(N_phar | N_pocket_m)        (the geometric mixture's term; float64 sum of the fp32 per-member values)
+    and nll taken with it; every other scalar depends on the group's rows alone.  With member_terms also 'member_nll',
+    'member_loss_t', 'member_loss_0_x', 'member_log_pN' [G, M] and 'member_level_terms' [R, n_levels, G, M]: ``assemble`` on member m's
+    columns with the group's kl_sums and that member's pocket size."""
+    f32 = np.float32
+    gt = np.asarray(group_terms, dtype=f32)
+    if gt.ndim == 3:
+        gt = gt[None]
+    w = np.asarray(weights, dtype=f32)
+    n_phar, n_pocket = np.asarray(n_phar, dtype=np.int64), np.asarray(n_pocket, dtype=np.int64)
+    G, M = w.shape
+    assert gt.shape[2] == G and n_pocket.shape == (G, M) and n_phar.shape == (G,)
+    per_m = lambda terms, m: assemble(terms, kl_sums, gamma, log_pn, T, n_dims, norm_values, t_levels, n_phar, n_pocket[:, m])
+    out = per_m(gt, 0)
+    # log p(N_phar | N_pocket_m) by ``assemble``'s expression, per member [G, M]
+    log_pN_m = np.stack([per_sample_table(gamma, log_pn, T, n_dims, norm_values, np.full(G, T, dtype=f32), n_phar, n_pocket[:, m]).numpy()[8]
+                         for m in range(M)], axis=1).astype(f32)
+    log_pN = (w.astype(np.float64) * log_pN_m.astype(np.float64)).sum(1).astype(f32)
+    # ``assemble``'s nll with the group's log_pN in place of the first member's
+    loss_0 = ((out['loss_0_x_repeats'] + f32(0)) + out['loss_0_h_repeats'] + out['neg_log_const_0'][None]).astype(f32)
+    nll = (((out['loss_t_repeats'] + loss_0) + out['kl_prior'][None]) - out['delta_log_px'][None] - log_pN[None]).astype(f32)
+    out['log_pN'], out['nll_repeats'] = log_pN, nll
+    out['nll'] = nll.astype(np.float64).mean(0).astype(f32)
+    if member_terms is not None:
+        mt = np.asarray(member_terms, dtype=f32)
+        if mt.ndim == 4:
+            mt = mt[None]
+        assert mt.shape[2:4] == (G, M)
+        mem = [per_m(mt[:, :, :, m], m) for m in range(M)]
+        for k in ('nll', 'loss_t', 'loss_0_x', 'log_pN'):
+            out['member_' + k] = np.stack([o[k] for o in mem], axis=1)
+        out['member_level_terms'] = np.stack([o['level_terms'] for o in mem], axis=3)
+    return out

@@ -416,6 +416,47 @@ int cmdgen_score_chain(cmdgen_handle* h, const float* phar_x, const float* phar_
                        const float* noise, uint64_t seed, const int64_t* pocket_ids_host,
                        float* level_terms_out, float* kl_sums_out, int32_t use_graph, cmdgen_stream stream);
 
+/* Scoring ONE pharmacophore against SEVERAL pockets (ConditionalDDPM.score_given_pockets): the variational bound of the sampler that
+ * cmdgen_multi_pocket_chain runs, whose denoiser is eps_bar = sum_m w_m eps_m - cmdgen_score_chain's levels with eps_bar in place of
+ * net.  Layout, groups, weights and group_ids_host are exactly cmdgen_multi_pocket_chain's (B member samples, the members of a group
+ * consecutive, Nu = one copy of the phar rows per group, the pockets of a group in ONE common frame); levels, level_coef_host and the
+ * output columns are exactly cmdgen_score_chain's.  In the normalised space, for group g with the clean rows xh0_g and the pockets
+ * P0_m of its members, all centred on the centre of mass of the group's phar rows (summed from the raw input in index order), level
+ * k with t = t_levels[k] and ONE draw eps_k per group:
+ *   z_k = alpha(t) xh0_g + sigma(t) eps_k;  shift = com(z_k.x);  z_k.x -= shift;  P_m.x = P0_m.x - shift for every member
+ *   eps_m = dynamics(z_k, P_m, t / T): the ordinary evaluation over the B member samples (x columns zero under the batch-wide NaN guard)
+ *   eps_bar = sum_m w_m eps_m                (m ascending, the first term not added to a zero)
+ *   group_terms_out[k][g]  = the CMDGEN_SC_COLS columns of cmdgen_score_chain with eps_bar in place of net
+ *   member_terms_out[k][b] = the same columns with member b's own eps_b: what cmdgen_score_chain gives on the member layout when every
+ *                            member gets its group's rows and draws - the per-pocket scores on COMMON draws
+ *   kl_sums_out[g][0 / 1]  = cmdgen_score_chain's two sums on xh0_g
+ * Rows are added column by column and then in node index order by one thread, no float atomics.  With every M_g = 1 every value is
+ * cmdgen_score_chain's, bit for bit.
+ *   phar_x dev [Nu,3], phar_onehot dev [Nu,phar_nf]: raw, one row per unique phar row;  pocket_x dev [Np,3], pocket_onehot dev
+ *          [Np,residue_nf]: raw, the rows of the B member samples in layout order
+ *   n_groups, group_size_host, weight_host  as cmdgen_multi_pocket_chain
+ *   n_levels, t_levels_host, level_coef_host  as cmdgen_score_chain
+ *   noise  dev [n_levels][Nu][3+phar_nf] or NULL: eps_k, one draw per group and level.  NULL: Philox keyed by (seed, global GROUP id,
+ *          level index k, node of the group) - cmdgen_debug_noise(seed, group id, k, n_phar, ...) returns the same numbers
+ *   group_ids_host  host [n_groups] global group ids for the Philox key (NULL: 0 .. n_groups-1)
+ *   group_terms_out dev [n_levels][n_groups][CMDGEN_SC_COLS];  member_terms_out dev [n_levels][batch][CMDGEN_SC_COLS] or NULL;
+ *   kl_sums_out dev [n_groups][2]
+ * One level is one launch (k_multi_score_step: one workgroup per member, each with its own copy of the clean rows and of z - no float
+ * atomics, no synchronisation between workgroups) plus the evaluation.  The chain has a slot of its own: a changed level list,
+ * grouping or weight prepares it again; the caller's pointers are the graph key.
+ * Refused: whatever cmdgen_multi_pocket_chain refuses of a grouping (sizes, unequal n_phar in a group, weights) and cmdgen_score_chain of
+ * a level list (levels outside 0 .. timesteps, n_levels < 1, a sample beyond the step's 64 KiB of LDS), the joint model,
+ * no_com_projection handles and null pointers.
+ * Asynchronous on `stream`; cmdgen_chain_status reports this run's mean-zero check of every z_k and the levels the NaN guard reset;
+ * cmdgen_debug_read("chain_z") gives every member's copy of the last level's z. */
+int cmdgen_multi_score_chain(cmdgen_handle* h, const float* phar_x, const float* phar_onehot,
+                             const float* pocket_x, const float* pocket_onehot,
+                             int64_t n_groups, const int64_t* group_size_host, const float* weight_host,
+                             int32_t n_levels, const int32_t* t_levels_host, const float* level_coef_host,
+                             const float* noise, uint64_t seed, const int64_t* group_ids_host,
+                             float* group_terms_out, float* member_terms_out, float* kl_sums_out,
+                             int32_t use_graph, cmdgen_stream stream);
+
 /* ---- training step (conditional model) -------------------------------------------------- */
 /* The trainable tensors of EGNNDynamics live in ONE flat fp32 device buffer owned by the caller, in the
  * reference's registration order (the state_dict order below 'ddpm.dynamics.': weight then bias of every
