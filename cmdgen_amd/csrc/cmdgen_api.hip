@@ -288,6 +288,7 @@ extern "C" int cmdgen_finalize_weights(cmdgen_handle* h) {
     h->layers = std::move(layers);
     h->finalized = true;
     h->user_coef_K = -1;                       // a new gamma table invalidates any step table
+    h->user_guide_K = -1;                      // ... and any guide table
     release_chains(h);
     if (h->have_layout) replan(h);             // the packs exist now
     return CMDGEN_OK;
@@ -645,7 +646,8 @@ extern "C" int cmdgen_debug_read(cmdgen_handle* h, const char* what, float* host
     else if (k == "chain_z") {                       // the last conditional chain's z buffer (the multi-pocket chains: every member's copy)
         const ChainBuf* cb = h->last_chain == CHAIN_PLAIN ? &h->chain : h->last_chain == CHAIN_INPAINT ? &h->inp_chain :
                              h->last_chain == CHAIN_MULTI ? &h->multi_chain : h->last_chain == CHAIN_MULTI_EDIT ? &h->medit_chain :
-                             h->last_chain == CHAIN_MULTI_SCORE ? &h->mscore_chain : nullptr;     // (the last level's z of the multi-pocket scoring chain)
+                             h->last_chain == CHAIN_MULTI_SCORE ? &h->mscore_chain :               // (the last level's z of the multi-pocket scoring chain)
+                             h->last_chain == CHAIN_RESTRAINED ? &h->restr_chain : nullptr;
         if (!cb || !cb->z_phar || h->chains[h->last_chain].n_steps < 0) return fail(h, CMDGEN_ESTATE, "no conditional chain has run on this layout");
         src = cb->z_phar; have = (size_t)h->lay.Nl * (3 + d.P);
     }
@@ -905,6 +907,150 @@ extern "C" int cmdgen_sample_chain(cmdgen_handle* h, const float* pocket_x, cons
     // final p(x, h | z0): the last evaluation above ran at t = 0 (coef[K].w); decode
     if (own_vel) cmdgen_launch_vel_flag(a, h->work.eps_tmp, s);
     cmdgen_launch_chain_final(h->lay, d, c, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, k.cog, s);
+    return end_chain(h, caller, s);
+}
+
+// ---------------------------------------------------------------------------------
+// the restrained chain: cmdgen_sample_chain's chain with a guidance term in the mean of every posterior op (kernels_restrain.hip holds
+// the definition).  The slot's table block is: the posterior rows | the guide rows (sigma_t, alpha_t, 0, 0; n_steps + 1 of them, the
+// last unused) | r_c, k_c, scale, max_shift, guide_below, 0, 0, 0 | the CSR offsets [B + 1] | the records sorted by sample - so whatever
+// changes the guidance prepares the slot again and drops its captured steps.
+// ---------------------------------------------------------------------------------
+static_assert(sizeof(cmdgen_restraint) == sizeof(RestraintRec) && sizeof(RestraintRec) == 10 * sizeof(float), "the public record is the kernels'");
+static_assert(CMDGEN_RESTRAINT_POSITION == RK_POSITION && CMDGEN_RESTRAINT_DISTANCE == RK_DISTANCE && CMDGEN_RESTRAINT_EXCLUSION == RK_EXCLUSION &&
+              CMDGEN_MAX_RESTRAINTS == MAX_RESTRAINTS, "the public constants and the kernels' agree");
+
+// sigma_t, alpha_t of every posterior op (rows s = K-1 .. 0, t = s + 1), fp32 as build_step_table evaluates its own (en_diffusion.py:859-867)
+static void build_guide_table(const std::vector<float>& gamma, int T, int K, std::vector<float>& sa) {
+    sa.assign((size_t)K * 2, 0.f);
+    for (int i = 0; i < K; ++i) {
+        const float t_arr = (float)(K - i) / (float)K;
+        const float g_t = gamma[(size_t)lrintf(t_arr * (float)T)];
+        sa[i * 2 + 0] = sqrtf(sigmoid_h(g_t));
+        sa[i * 2 + 1] = sqrtf(sigmoid_h(-g_t));
+    }
+}
+
+extern "C" int cmdgen_set_guide_table(cmdgen_handle* h, int32_t K, const float* sigma_alpha_host) {
+    if (!h || K < 1 || !sigma_alpha_host) return fail(h, CMDGEN_EINVAL, "bad guide table");
+    h->user_guide.assign(sigma_alpha_host, sigma_alpha_host + (size_t)K * 2);
+    h->user_guide_K = K;
+    return CMDGEN_OK;
+}
+
+static int alloc_restrained(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
+    int rc = alloc_chain_buf(h, k, h->restr_chain, tables); if (rc) return rc;
+    const size_t B = (size_t)h->lay.B;
+    RestrainBuf& rb = h->restr;
+    const float* sa = tables + (size_t)(n_steps + 1) * 4;
+    const float* par = sa + (size_t)(n_steps + 1) * 4;
+    rb.sa = (const float4*)sa;
+    rb.clash_r = par[0]; rb.clash_k = par[1]; rb.scale = par[2]; rb.max_shift = par[3]; rb.guide_below = par[4];
+    rb.rstart = (const int*)(par + 8);
+    rb.rec = (const RestraintRec*)(par + 8 + B + 1);
+    void* p;
+    rc = dev_alloc(h, k.allocs, &p, B * sizeof(float4), true); if (rc) return rc;
+    rb.pin_com = (float4*)p;
+    rb.op_energy = nullptr;
+    return 0;
+}
+
+extern "C" int cmdgen_restrained_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot, int32_t timesteps,
+                                       const cmdgen_restraint* restraints_host, int64_t n_restraints,
+                                       float clash_radius, float clash_k, float scale, float max_shift, float guide_below,
+                                       const float* noise, uint64_t seed, const int64_t* pocket_ids_host,
+                                       float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                                       float* energy_out, float* op_energy_out, int32_t use_graph, cmdgen_stream stream) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (!pocket_x || !pocket_onehot || !xh_phar_out || !xh_pocket_out || !energy_out) return fail(h, CMDGEN_EINVAL, "null device pointer");
+    const int K = timesteps;
+    if (K < 1 || K > h->cfg.timesteps) return fail(h, CMDGEN_EINVAL, "timesteps=%d must be in [1, %d]", K, h->cfg.timesteps);
+    if (h->dims.joint) return fail(h, CMDGEN_ESTATE, "the restrained chain is not supported for the joint model (update_pocket_coords=1): its pocket nodes diffuse with the latent");
+    if (h->dims.no_com) return fail(h, CMDGEN_EINVAL, "the restrained chain is not supported for no_com_projection handles (SimpleConditionalDDPM): the guidance frame follows the centre-of-mass projections");
+    if (n_restraints < 0 || (n_restraints > 0 && !restraints_host)) return fail(h, CMDGEN_EINVAL, "n_restraints=%lld without a restraint list", (long long)n_restraints);
+    auto ok = [](float v) { return std::isfinite(v) && v >= 0.f; };
+    if (!ok(clash_radius) || !ok(clash_k)) return fail(h, CMDGEN_EINVAL, "clash_radius=%g, clash_k=%g must be finite and >= 0", (double)clash_radius, (double)clash_k);
+    if (!ok(scale)) return fail(h, CMDGEN_EINVAL, "scale=%g must be finite and >= 0", (double)scale);
+    if (!(std::isfinite(max_shift) && max_shift > 0.f)) return fail(h, CMDGEN_EINVAL, "max_shift=%g must be finite and > 0", (double)max_shift);
+    if (!(guide_below >= 0.f && guide_below <= 1.f)) return fail(h, CMDGEN_EINVAL, "guide_below=%g must be in [0, 1]", (double)guide_below);
+    const int B = h->lay.B;
+    std::vector<int> rstart((size_t)B + 1, 0);
+    for (int64_t r = 0; r < n_restraints; ++r) {
+        const cmdgen_restraint& q = restraints_host[r];
+        const long long ri = (long long)r;
+        if (q.kind != RK_POSITION && q.kind != RK_DISTANCE && q.kind != RK_EXCLUSION) return fail(h, CMDGEN_EINVAL, "restraint %lld: unknown kind %d", ri, q.kind);
+        if (q.sample < 0 || q.sample >= B) return fail(h, CMDGEN_EINVAL, "restraint %lld: sample %d outside the layout's %d samples", ri, q.sample, B);
+        const long long nl = (long long)h->cur_nphar[q.sample];
+        if (q.kind != RK_EXCLUSION && (q.i < 0 || q.i >= nl)) return fail(h, CMDGEN_EINVAL, "restraint %lld: point %d, sample %d has %lld points", ri, q.i, q.sample, nl);
+        if (q.kind == RK_DISTANCE) {
+            if (q.j < 0 || q.j >= nl) return fail(h, CMDGEN_EINVAL, "restraint %lld: point %d, sample %d has %lld points", ri, q.j, q.sample, nl);
+            if (q.i == q.j) return fail(h, CMDGEN_EINVAL, "restraint %lld: a distance between point %d and itself (i == j)", ri, q.i);
+            if (!ok(q.a) || !ok(q.b)) return fail(h, CMDGEN_EINVAL, "restraint %lld: lo=%g, hi=%g must be finite and >= 0", ri, (double)q.a, (double)q.b);
+            if (q.a > q.b) return fail(h, CMDGEN_EINVAL, "restraint %lld: lo=%g > hi=%g", ri, (double)q.a, (double)q.b);
+        } else {
+            if (!ok(q.a)) return fail(h, CMDGEN_EINVAL, "restraint %lld: radius=%g must be finite and >= 0", ri, (double)q.a);
+            if (!std::isfinite(q.c[0]) || !std::isfinite(q.c[1]) || !std::isfinite(q.c[2])) return fail(h, CMDGEN_EINVAL, "restraint %lld: a non-finite centre", ri);
+        }
+        if (!ok(q.k)) return fail(h, CMDGEN_EINVAL, "restraint %lld: k=%g must be finite and >= 0", ri, (double)q.k);
+        if (++rstart[(size_t)q.sample + 1] > CMDGEN_MAX_RESTRAINTS)
+            return fail(h, CMDGEN_EINVAL, "sample %d has more than %d restraints", q.sample, CMDGEN_MAX_RESTRAINTS);
+    }
+    if (plan_restrained_step_lds(h->lay.max_n, h->dims.P) > PLAN_RESTRAINED_LDS_MAX)
+        return fail(h, CMDGEN_EINVAL, "a sample has %d nodes: the restrained step keeps a sample's positions, z and guidance terms in LDS (64 KiB)", h->lay.max_n);
+    for (int b = 0; b < B; ++b) rstart[(size_t)b + 1] += rstart[b];
+    std::vector<cmdgen_restraint> rec((size_t)n_restraints);
+    {
+        std::vector<int> at(rstart.begin(), rstart.end() - 1);
+        for (int64_t r = 0; r < n_restraints; ++r) {             // stable: a sample's restraints keep their list order
+            cmdgen_restraint q = restraints_host[r];
+            if (q.kind == RK_EXCLUSION) { q.i = 0; q.j = 0; }
+            if (q.kind == RK_POSITION) q.j = 0;
+            if (q.kind != RK_DISTANCE) q.b = 0.f;
+            if (q.kind == RK_DISTANCE) q.c[0] = q.c[1] = q.c[2] = 0.f;
+            rec[(size_t)at[q.sample]++] = q;                     // (fields a kind does not read are zeroed: they are part of the slot's key)
+        }
+    }
+    std::vector<float> tables = step_table(h, K);
+    {
+        std::vector<float> sa;
+        if (h->user_guide_K == K) sa = h->user_guide; else build_guide_table(h->gamma, h->cfg.timesteps, K, sa);
+        const size_t c0 = tables.size();
+        tables.resize(c0 + (size_t)(K + 1) * 4 + 8 + (size_t)B + 1 + rec.size() * 10, 0.f);
+        float* g = tables.data() + c0;
+        for (int i = 0; i < K; ++i) { g[4 * i] = sa[2 * i]; g[4 * i + 1] = sa[2 * i + 1]; }
+        float* par = g + (size_t)(K + 1) * 4;
+        par[0] = clash_radius; par[1] = clash_k; par[2] = scale; par[3] = max_shift; par[4] = guide_below;
+        memcpy(par + 8, rstart.data(), rstart.size() * sizeof(int));
+        if (!rec.empty()) memcpy(par + 8 + B + 1, rec.data(), rec.size() * sizeof(cmdgen_restraint));
+    }
+    const hipStream_t caller = (hipStream_t)stream;
+    hipStream_t s; EvalLaunch a;
+    rc = begin_chain(h, CHAIN_RESTRAINED, tables, K, alloc_restrained, pocket_ids_host, use_graph, caller, &s, &a); if (rc) return rc;
+    ChainSlot& k = h->chains[CHAIN_RESTRAINED];
+    const Dims& d = h->dims;
+    ChainBuf c = h->restr_chain;
+    c.noise = noise; c.seed = seed; c.z_steps = z_steps_out; c.pocket_steps = pocket_steps_out;
+    RestrainBuf rb = h->restr;
+    rb.op_energy = op_energy_out;
+    cmdgen_launch_chain_init(h->lay, d, c, pocket_x, pocket_onehot, s);
+    cmdgen_launch_restrain_prep(h->lay, d, rb, pocket_x, s);
+    build_pocket_cache(h, k, c, a, s);
+    // the evaluations are the plain chain's, with or without k_readout (cmdgen_sample_chain: readout_mode); the step kernel has both forms
+    a.plain_chain = 1;
+    const int own_vel = readout_mode(a, c.state, nullptr, nullptr, nullptr);
+    EvalLaunch a2 = a;
+    a2.skip_count = 1;
+    cmdgen_launch_eval(a, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, s, nullptr);   // evaluation 0 (t = 1)
+    if (a.readout_used != own_vel) return fail(h, CMDGEN_ESTATE, "the evaluation and the step kernel disagree on readout_in_coord (%d, %d)", a.readout_used, own_vel);
+    const void* key[6] = {noise, z_steps_out, pocket_steps_out, op_energy_out, nullptr, s};
+    rc = run_steps(h, k, key, seed, K, use_graph, s, [&](hipStream_t ss) {
+        cmdgen_launch_restrained_step_count(h->lay, d, c, rb, h->work, h->work.eps_tmp, own_vel, ss);
+        cmdgen_launch_eval(a2, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, ss, nullptr);
+    });
+    if (rc) return rc;
+    if (own_vel) cmdgen_launch_vel_flag(a, h->work.eps_tmp, s);
+    cmdgen_launch_chain_final(h->lay, d, c, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, k.cog, s);
+    cmdgen_launch_restrain_energy(h->lay, d, rb, xh_phar_out, xh_pocket_out, energy_out, s);
     return end_chain(h, caller, s);
 }
 

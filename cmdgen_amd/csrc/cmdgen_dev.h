@@ -224,6 +224,22 @@ struct GroupTab {               // multi-pocket chain (cmdgen_multi_pocket_chain
 };
 enum { MAX_GROUP = 8 };         // = CMDGEN_MAX_GROUP
 
+struct RestraintRec {           // = cmdgen_restraint (include/cmdgen_hip.h), one geometric restraint of one sample
+    int kind, sample, i, j;     // RK_POSITION (point i), RK_DISTANCE (points i, j), RK_EXCLUSION (every point)
+    float c[3], a, b, k;        // centre in the caller's frame; a, b: radius, - | lo, hi | radius, -; k in 1/A^2
+};
+enum { RK_POSITION = 0, RK_DISTANCE = 1, RK_EXCLUSION = 2, MAX_RESTRAINTS = 256 };   // = CMDGEN_RESTRAINT_*, CMDGEN_MAX_RESTRAINTS
+
+struct RestrainBuf {            // restrained chain (cmdgen_restrained_chain), beside a ChainBuf: the guidance tables (kernels_restrain.hip)
+    const float4* sa;           // [K]     (sigma_t, alpha_t, 0, 0) of op i's t: the denoised estimate xhat = n_x (z.x - sigma_t e) / alpha_t
+    const int* rstart;          // [B+1]   a sample's records are rec[rstart[b] .. rstart[b+1] - 1], in the caller's list order
+    const RestraintRec* rec;    // [n]
+    float4* pin_com;            // [B]     com(P_in.x / n_x): the caller's pocket, normalised (k_restrain_prep)
+    float clash_r, clash_k;     // the clash term of every sample (clash_r = 0: off)
+    float scale, max_shift, guide_below;
+    float* op_energy;           // [K][B] E at xhat of every op, or null
+};
+
 struct PocketCache {            // chain-invariant part of k_embed's output for POCKET rows (conditional sampler): the pocket's
                                 // features never change during a chain and the embedding is affine in the time feature, so
                                 //   h(t) = c + t dh,  P(t) = P0 + t dP,  Q(t) = Q0 + t dQ   (dh, dP, dQ: one row of H values each)
@@ -274,7 +290,7 @@ struct EvalLaunch {             // everything one evaluation's launches need (ho
     mutable int frag_launches = 0;   // tile launches of this evaluation that read the fp32 FRAGMENT packs (the generic k_edge_msg / k_node / k_edge_coord forms): the training step re-packs those only when one will run
     mutable int live_thr = 0;   // set around a block's launches when that applies: nodes within this many hops of a moving node are still read
     mutable int proj_now = 0;   // plan.proj_in_coord and this evaluation does so (launch_eval: not a training forward, no parity stop, no per-stage events)
-    int plain_chain = 0;        // the evaluation belongs to cmdgen_sample_chain: its step kernel can form the velocity itself (readout_mode below)
+    int plain_chain = 0;        // the evaluation belongs to cmdgen_sample_chain or cmdgen_restrained_chain: its step kernel can form the velocity itself (readout_mode below)
     mutable int readout_now = 0;   // readout_mode() of the evaluation being issued (launch_eval)
     mutable int readout_used = 0;  // ... of the evaluation issued last: the chain driver checks it against the mode it gave its step kernel
 };

@@ -24,7 +24,7 @@ struct DevBuf {
 // Host state of one kind of denoising chain (cmdgen_api.hip): its buffers for the current layout, the plan tables they were
 // prepared for, and its captured steps.  Each kind has a slot of its own, so plain and inpainting chains alternate on a
 // handle without re-preparing or re-capturing.
-enum ChainKind { CHAIN_PLAIN, CHAIN_JOINT, CHAIN_INPAINT, CHAIN_SCORE, CHAIN_MULTI, CHAIN_MULTI_EDIT, CHAIN_MULTI_SCORE, CHAIN_KINDS };
+enum ChainKind { CHAIN_PLAIN, CHAIN_JOINT, CHAIN_INPAINT, CHAIN_SCORE, CHAIN_MULTI, CHAIN_MULTI_EDIT, CHAIN_MULTI_SCORE, CHAIN_RESTRAINED, CHAIN_KINDS };
 struct ChainSlot {
     std::vector<void*> allocs;
     std::vector<float> tables;             // the uploaded plan tables (coef | coef2 | iop bits), compared to decide a re-prepare
@@ -34,7 +34,7 @@ struct ChainSlot {
     unsigned int* cog = nullptr;           // CoG drift of the final sample
     float* pk[7] = {};                     // PocketCache storage (c, P0, Q0, dh, dP, dQ) and the time pair (0, 1) that builds it
     hipGraphExec_t graph = nullptr;        // G captured steps, valid for the key below
-    const void* key[6] = {};               // noise, z_steps (scoring: the level terms), pocket_steps (multi-pocket scoring: the member terms), phar_fixed, pocket_fixed, stream
+    const void* key[6] = {};               // noise, z_steps (scoring: the level terms), pocket_steps (multi-pocket scoring: the member terms), phar_fixed (restrained: the op energies), pocket_fixed, stream
     unsigned long long seed = 0;
     int graph_steps = 0;
 };
@@ -86,8 +86,12 @@ struct cmdgen_handle {
     ChainBuf mscore_chain{};               // multi-pocket scoring chain: the scoring chain's buffers (every member's copy of the level's z and of the clean rows), ...
     ScoreBuf mscore{};
     GroupTab mscore_groups{};              // ... and its own group tables, behind the level rows of the slot's table block
+    ChainBuf restr_chain{};                // restrained chain: the plain chain's buffers, ...
+    RestrainBuf restr{};                   // ... and the guidance tables behind the posterior rows of the slot's table block (a changed restraint prepares the slot again)
     std::vector<float> user_coef;          // optional host-supplied step table
     int user_coef_K = -1;
+    std::vector<float> user_guide;         // optional host-supplied guide table [K][2] (cmdgen_set_guide_table)
+    int user_guide_K = -1;
     hipStream_t own_stream = nullptr;      // used when the caller's stream is the legacy default stream (not capturable)
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
     TrainState* train = nullptr;           // training workspace (cmdgen_train.hip)

@@ -52,6 +52,13 @@ void cmdgen_launch_chain_final(const Layout& lay, const Dims& d, const ChainBuf&
                                unsigned int* cog, hipStream_t s);
 void cmdgen_launch_debug_noise(unsigned long long seed, long long pocket_id, int draw, int n_nodes, int width, float* out, hipStream_t s);
 
+// kernels_restrain.hip: the restrained chain (the conditional chain with a guidance term in the mean of every posterior op)
+void cmdgen_launch_restrain_prep(const Layout& lay, const Dims& d, const RestrainBuf& rb, const float* px, hipStream_t s);
+void cmdgen_launch_restrained_step_count(const Layout& lay, const Dims& d, const ChainBuf& c, const RestrainBuf& rb, const Work& w,
+                                         const float* eps, int own_vel /* readout_mode */, hipStream_t s);
+void cmdgen_launch_restrain_energy(const Layout& lay, const Dims& d, const RestrainBuf& rb, const float* xo, const float* po,
+                                   float* energy_out, hipStream_t s);
+
 // kernels_multi.hip: the multi-pocket chain (groups of samples that share one latent)
 void cmdgen_launch_multi_init(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const float* px, const float* poh,
                               hipStream_t s);

@@ -1,0 +1,342 @@
+// kernels_restrain.hip - sampling steered by geometric restraints (ConditionalDDPM.sample_restrained, cmdgen_restrained_chain): the
+// ancestral sampler of kernels_ddpm.hip with a guidance term in the mean of every posterior op.  The reference has nothing like it; this
+// is the definition ("Sampling with geometric restraints", repeats it; tests/restraint_ref.py is its CPU model).
+//
+// The chain is sample_given_pocket's: the same ops, the same draws, the same Philox counters; z_T is k_chain_init's and the decode
+// k_chain_final's, which is not guided.  One addition is made to the mean of every posterior op t -> s.  With
+//   z     the op's input latent,
+//   e     the network's x columns after the NaN guard (zero when the guard reset),
+//   P     the current (translated, normalised) pocket,  P_in the caller's pocket,
+//   n_x   norm_values[0],
+//   coef  the op's step-table row (alpha_ts, sigma2_ts/alpha_ts/sigma_t, sigma_ts*sigma_s/sigma_t, t),
+// per sample:
+//   1. Denoised estimate.  xhat_i = n_x * (z.x_i - sigma_t * e_i) / alpha_t, in Angstrom, in the chain's current frame; sigma_t and
+//      alpha_t are those of the op's t, from a second per-op table beside the step table (RestrainBuf::sa: the host's fp32 evaluation,
+//      cmdgen_set_guide_table, or the library's own).
+//   2. Frame.  shift = n_x * (com(P.x) - com(P_in.x / n_x)).  A centre c of the caller's frame becomes c + shift; pocket atoms are used
+//      where they are, q_a = n_x * P.x_a.
+//   3. Energy.  E = sum over restraints of 0.5 * k * v^2, v >= 0 the violation in Angstrom, k >= 0 in 1/Angstrom^2:
+//        position(point i, centre c, radius r, k)   v = max(0, |xhat_i - (c + shift)| - r)
+//        distance(points i, j, lo, hi, k)           v = max(0, lo - d, d - hi),  d = |xhat_i - xhat_j|
+//        exclusion(centre c, radius r, k)           for every point of the sample  v_i = max(0, r - |xhat_i - (c + shift)|)
+//        clash(radius r_c, k_c)                     one pair of scalars per call: for every point and every pocket atom of the sample
+//                                                   v_ia = max(0, r_c - |xhat_i - q_a|); r_c = 0 turns it off
+//      g_i = dE / dxhat_i.  A term whose distance is below 1e-12 A contributes the zero vector.  A point's terms are summed in this
+//      order: position, distance and exclusion in list order, then pocket atoms in index order.
+//   4. Displacement.  d_i = -scale * (n_x * coef.z)^2 * g_i, in Angstrom: the mean shifted by the op's posterior variance times the
+//      gradient (classifier guidance), the gradient taken at xhat with d xhat / d z treated as the identity.  If |d_i| > max_shift,
+//      d_i *= max_shift / |d_i|.  An op whose t / T > guide_below has d = 0.
+//   5. Mean.  mu.x_i = z.x_i / coef.x - coef.y * e_i + d_i / n_x; the h columns as before.  The draw, the COM projection of z and the
+//      pocket, the saved steps and pass 1 of the next radius graph follow exactly as in k_step_count.
+// The energy is C1 and the clip is continuous: the term adds no hard threshold; the radius graph's cutoff remains the only one.
+// Beside the chain's outputs: per sample the energy E of the FINAL output and its largest violation in Angstrom, evaluated on the
+// returned xh_phar / xh_pocket with shift = com(xh_pocket.x) - n_x * com(P_in.x / n_x) (k_restrain_energy); and, when asked for, E at
+// xhat of every op.
+//
+// Reductions that hold bit for bit.  With no restraint on any sample and r_c = 0, or with scale = 0, every output equals
+// cmdgen_sample_chain's.  A sample that no restraint touches, an op above guide_below and a chain with scale = 0 run k_step_count's
+// arithmetic: nothing is added to their mean, not even a zero.
+//
+// Sums.  A wave owns a phar point: its lanes walk the sample's restraint records, then the pocket atoms already in LDS, each lane adding
+// its terms in ascending order, and a butterfly of __shfl_xor adds the lanes - a fixed order, the same on every run (it is not the index
+// order of step 3: the results agree with the CPU model within rounding, not bit for bit).  The pocket's centre of mass is summed the
+// same way.  No float atomics anywhere in the guidance.  IEEE sqrtf and division; built with -ffp-contract=off like kernels_ddpm.hip.
+#include "cmdgen_sampler.h"
+
+namespace {
+
+__device__ __forceinline__ float rdraw(const ChainBuf& c, const Layout& lay, int draw_idx, int b, int local, int node, int comp, int ld) {
+    if (c.noise) return c.noise[((size_t)draw_idx * lay.Nl + node) * ld + comp];
+    float z[4];
+    philox_normal4(c.seed, (uint32_t)lay.pocket_gid[b], (uint32_t)(lay.pocket_gid[b] >> 32),
+                   (uint32_t)draw_idx, (uint32_t)(local * 4 + (comp >> 2)), z);
+    return z[comp & 3];
+}
+
+__device__ __forceinline__ float wave_sum(float v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o); return v; }
+__device__ __forceinline__ float wave_max(float v) { for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o)); return v; }
+
+struct PointTerm { float gx, gy, gz, e, v; };     // dE / dxhat_i, the point's share of E, its largest violation
+
+// one term of point i: (dx, dy, dz) = xhat_i - the other end, v its violation (> 0), sgn = d v / d dist; count: the term's energy is this point's
+__device__ __forceinline__ void add_term(PointTerm& t, float dx, float dy, float dz, float dist, float v, float sgn, float k, bool count) {
+    if (dist >= 1e-12f) {
+        const float c = sgn * (k * v) / dist;
+        t.gx += c * dx; t.gy += c * dy; t.gz += c * dz;
+    }
+    if (count) { t.e += 0.5f * k * (v * v); t.v = fmaxf(t.v, v); }
+}
+
+// Steps 3 of point i, by the whole wave: the sample's records r0 .. r1-1 over the lanes, then its np pocket atoms s_q[0 .. np-1] * qs.
+// s_xh: [nl][3] the points in Angstrom; (sx, sy, sz): shift.  Every lane returns the same sums.
+__device__ __forceinline__ PointTerm point_terms(const RestrainBuf& rb, int r0, int r1, int i, int np, const float* s_xh, const float4* s_q,
+                                                 float qs, float sx, float sy, float sz, int lane) {
+    const float xi = s_xh[3 * i], yi = s_xh[3 * i + 1], zi = s_xh[3 * i + 2];
+    PointTerm t{0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int base = r0; base < r1; base += 64) {
+        const int r = base + lane;
+        if (r >= r1) continue;
+        const RestraintRec q = rb.rec[r];
+        if (q.kind == RK_DISTANCE) {
+            if (q.i != i && q.j != i) continue;
+            const int o = q.i == i ? q.j : q.i;
+            const float dx = xi - s_xh[3 * o], dy = yi - s_xh[3 * o + 1], dz = zi - s_xh[3 * o + 2];
+            const float dist = sqrtf(dx * dx + dy * dy + dz * dz);
+            if (dist < q.a) add_term(t, dx, dy, dz, dist, q.a - dist, -1.f, q.k, q.i == i);
+            else if (dist > q.b) add_term(t, dx, dy, dz, dist, dist - q.b, 1.f, q.k, q.i == i);
+        } else {
+            if (q.kind == RK_POSITION && q.i != i) continue;
+            const float dx = xi - (q.c[0] + sx), dy = yi - (q.c[1] + sy), dz = zi - (q.c[2] + sz);
+            const float dist = sqrtf(dx * dx + dy * dy + dz * dz);
+            if (q.kind == RK_POSITION) { if (dist > q.a) add_term(t, dx, dy, dz, dist, dist - q.a, 1.f, q.k, true); }
+            else if (dist < q.a) add_term(t, dx, dy, dz, dist, q.a - dist, -1.f, q.k, true);
+        }
+    }
+    if (rb.clash_r > 0.f) {
+        for (int a = lane; a < np; a += 64) {
+            const float4 p = s_q[a];
+            const float dx = xi - qs * p.x, dy = yi - qs * p.y, dz = zi - qs * p.z;
+            const float dist = sqrtf(dx * dx + dy * dy + dz * dz);
+            if (dist < rb.clash_r) add_term(t, dx, dy, dz, dist, rb.clash_r - dist, -1.f, rb.clash_k, true);
+        }
+    }
+    t.gx = wave_sum(t.gx); t.gy = wave_sum(t.gy); t.gz = wave_sum(t.gz); t.e = wave_sum(t.e); t.v = wave_max(t.v);
+    return t;
+}
+
+// com of the np positions s_q[0 .. np-1] (one wave; every lane returns it)
+__device__ __forceinline__ void wave_com(const float4* s_q, int np, int lane, float& c0, float& c1, float& c2) {
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+    for (int a = lane; a < np; a += 64) { const float4 p = s_q[a]; a0 += p.x; a1 += p.y; a2 += p.z; }
+    const float cnt = fmaxf((float)np, 1.0f);
+    c0 = wave_sum(a0) / cnt; c1 = wave_sum(a1) / cnt; c2 = wave_sum(a2) / cnt;
+}
+
+}  // namespace
+
+// com(P_in.x / n_x) per sample, index order (scatter_mean of the normalised input pocket)
+__global__ __launch_bounds__(64) void k_restrain_prep(Layout lay, Dims d, RestrainBuf rb, const float* __restrict__ pocket_x) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int np = lay.num_pocket[b], qb = lay.pocket_base[b];
+    if (lane < 3) {
+        float s = 0.f;
+        for (int i = 0; i < np; ++i) s += pocket_x[(size_t)(qb + i) * 3 + lane] / d.norm_x;
+        reinterpret_cast<float*>(rb.pin_com + b)[lane] = s / fmaxf((float)np, 1.0f);
+    }
+    if (lane == 3) reinterpret_cast<float*>(rb.pin_com + b)[3] = 0.f;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// k_restrained_step_count: k_step_count (kernels_ddpm.hip; both of its forms, own_vel as there) with steps 1-5 of the header between the
+// loads and the posterior mean.  xhat, the displacement and the points' energy terms live in LDS behind s_z / s_vel.  A sample-op that is
+// not guided (no restraint on the sample and no clash term, scale = 0, t / T > guide_below) skips all of it: k_step_count's arithmetic.
+// ------------------------------------------------------------------------------------------------------------
+template <bool own_vel>
+__global__ __launch_bounds__(1024) void k_restrained_step_count(Layout lay, Dims d, ChainBuf c, RestrainBuf rb, Work w,
+                                                               const float* __restrict__ eps) {
+    extern __shared__ float4 s_pos[];               // [max_n] positions of the sample (phar first), then int sdeg[max_n], then z, vel, xhat, d, e
+    int* sdeg = reinterpret_cast<int*>(s_pos + lay.max_n);
+    float* s_z = reinterpret_cast<float*>(sdeg + lay.max_n);      // [nl * ld]
+    float* s_vel = s_z + (size_t)lay.max_n * (3 + d.P);           // own_vel: [nl][3]
+    float* s_xh = s_vel + (size_t)lay.max_n * 3;                  // [nl][3] xhat, Angstrom
+    float* s_d = s_xh + (size_t)lay.max_n * 3;                    // [nl][3] displacement, Angstrom
+    float* s_e = s_d + (size_t)lay.max_n * 3;                     // [nl] the points' shares of E
+    __shared__ float s_mean[3], s_shift[3];
+    __shared__ int s_bad[16];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6, nt = blockDim.x;
+    const int nl = lay.num_phar[b], np = lay.num_pocket[b], n = nl + np;
+    const int pb = lay.phar_base[b], qb = lay.pocket_base[b];
+    const int ld = 3 + d.P, ldq = 3 + d.R;
+    const int step = c.state->step - 1;
+    const float4 cf = c.coef[step];
+    const float4 sa = rb.sa[step];
+    const int r0 = rb.rstart[b], r1 = rb.rstart[b + 1];
+    const bool touched = r1 > r0 || rb.clash_r > 0.f;
+    const bool guided = touched && rb.scale > 0.f && cf.w <= rb.guide_below;
+    const bool terms = touched && (guided || rb.op_energy != nullptr);
+    float* zg = c.z_phar + (size_t)pb * ld;
+    const float* eg = eps + (size_t)pb * ld;
+    const int cnt = nl * ld;
+    const int flag0 = own_vel ? 0 : *w.nan_flag;
+    [[maybe_unused]] VelIn vin[4];
+    if constexpr (own_vel) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int r = tid + u * nt;
+            if (r < lay.Nl) vin[u] = readout_vel_in(lay, w, d, r);
+        }
+    }
+    for (int idx = tid; idx < cnt; idx += nt) s_z[idx] = zg[idx];
+    for (int i = tid; i < np; i += nt) {
+        const float* q = c.xh_pocket + (size_t)(qb + i) * ldq;
+        s_pos[nl + i] = make_float4(q[0], q[1], q[2], 0.f);
+    }
+    if constexpr (own_vel) {              // the batch-global NaN flag, formed by every workgroup for itself (k_step_count)
+        int bad = 0;
+        auto take = [&](int r, const float4& v) {
+            bad |= vel_isnan(v) ? 1 : 0;
+            const int i = r - pb;
+            if (i >= 0 && i < nl) { s_vel[3 * i] = v.x; s_vel[3 * i + 1] = v.y; s_vel[3 * i + 2] = v.z; }
+        };
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int r = tid + u * nt;
+            if (r < lay.Nl) take(r, readout_vel_of(vin[u]));
+        }
+        for (int r = tid + 4 * nt; r < lay.Nl; r += nt) take(r, readout_vel(lay, w, d, r));
+        const bool any = __ballot(bad != 0) != 0ull;
+        if (lane == 0) s_bad[wave] = any ? 1 : 0;
+    }
+    __syncthreads();
+    bool nan_reset;
+    if constexpr (own_vel) {
+        int any = 0;
+        for (int k = 0; k < nwaves; ++k) any |= s_bad[k];
+        nan_reset = any != 0;
+    } else nan_reset = flag0 != 0;
+    if (wave == 0) record_com_check(c.check + 2 * (1 + step), s_z, ld, 0, nl, 1.0f, lane);   // z_t, the step's input
+    __syncthreads();
+    // ---- the guidance (steps 1-4): uniform over the workgroup
+    if (terms) {
+        for (int idx = tid; idx < 3 * nl; idx += nt) {          // 1. xhat
+            const int i = idx / 3, k = idx - 3 * i;
+            float e;
+            if constexpr (own_vel) e = s_vel[idx]; else e = eg[i * ld + k];
+            if (nan_reset) e = 0.f;
+            s_xh[idx] = d.norm_x * (s_z[i * ld + k] - sa.x * e) / sa.y;
+        }
+        if (wave == nwaves - 1) {                               // 2. shift
+            float c0, c1, c2;
+            wave_com(s_pos + nl, np, lane, c0, c1, c2);
+            const float4 pin = rb.pin_com[b];
+            if (lane == 0) { s_shift[0] = d.norm_x * (c0 - pin.x); s_shift[1] = d.norm_x * (c1 - pin.y); s_shift[2] = d.norm_x * (c2 - pin.z); }
+        }
+        __syncthreads();
+        const float sx = s_shift[0], sy = s_shift[1], sz = s_shift[2];
+        const float sd = d.norm_x * cf.z, var = sd * sd;
+        for (int i = wave; i < nl; i += nwaves) {               // 3. / 4. a wave per point
+            const PointTerm t = point_terms(rb, r0, r1, i, np, s_xh, s_pos + nl, d.norm_x, sx, sy, sz, lane);
+            float dx = -rb.scale * var * t.gx, dy = -rb.scale * var * t.gy, dz = -rb.scale * var * t.gz;
+            const float len = sqrtf(dx * dx + dy * dy + dz * dz);
+            if (len > rb.max_shift) { const float f = rb.max_shift / len; dx *= f; dy *= f; dz *= f; }
+            if (lane == 0) { s_d[3 * i] = dx; s_d[3 * i + 1] = dy; s_d[3 * i + 2] = dz; s_e[i] = t.e; }
+        }
+        __syncthreads();
+    }
+    if (rb.op_energy && tid == 0) {
+        float e = 0.f;
+        if (terms) for (int i = 0; i < nl; ++i) e += s_e[i];    // index order
+        rb.op_energy[(size_t)step * lay.B + b] = e;
+    }
+    // ---- 5. the posterior mean and the draw (k_step_count's expressions)
+    for (int idx = tid; idx < cnt; idx += nt) {
+        const int i = idx / ld, k = idx - i * ld;
+        float e = eg[idx];
+        if constexpr (own_vel) { if (k < 3) e = s_vel[3 * i + k]; }
+        if (nan_reset && k < 3) e = 0.f;
+        float mu = s_z[idx] / cf.x - cf.y * e;
+        if (guided && k < 3) mu = mu + s_d[3 * i + k] / d.norm_x;
+        s_z[idx] = mu + cf.z * rdraw(c, lay, 1 + step, b, i, pb + i, k, ld);
+    }
+    __syncthreads();
+    phar_mean(s_z, nl, ld, tid, s_mean);
+    __syncthreads();
+    const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
+    for (int i = tid; i < n; i += nt) {
+        float4 p;
+        if (i < nl) {
+            float* z = s_z + i * ld;
+            z[0] -= m0; z[1] -= m1; z[2] -= m2;
+            p = make_float4(z[0], z[1], z[2], 0.f);
+            if constexpr (!own_vel) {         // (own_vel: other workgroups are reading both - pass 2 stores them from z_phar)
+                w.X0[pb + i] = p;
+                for (int l = 0; l < d.L; ++l) w.ACC[(size_t)l * lay.Nm + pb + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        } else {
+            p = s_pos[i];
+            p.x -= m0; p.y -= m1; p.z -= m2;
+            float* q = c.xh_pocket + (size_t)(qb + i - nl) * ldq;
+            q[0] = p.x; q[1] = p.y; q[2] = p.z;
+            w.XP[qb + i - nl] = p;
+            if (c.pocket_steps) {
+                float* o = c.pocket_steps + ((size_t)step * lay.Np + qb + i - nl) * 3;
+                o[0] = p.x; o[1] = p.y; o[2] = p.z;
+            }
+        }
+        s_pos[i] = p;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < cnt; idx += nt) {
+        const float v = s_z[idx];
+        zg[idx] = v;
+        if (c.z_steps) c.z_steps[(size_t)step * lay.Nl * ld + (size_t)pb * ld + idx] = v;
+    }
+    count_next_graph(lay, d, w, s_pos, sdeg, b, nl, n, pb, qb);
+    if (b == 0 && tid == 0) {
+        if (nan_reset) atomicAdd(&w.counters[4], 1ull);
+        atomicAdd(&w.counters[0], 1ull);                       // evaluations (the one about to run)
+        atomicAdd(&w.counters[3], (unsigned long long)lay.N);  // nodes
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// k_restrain_energy: E and the largest violation of the chain's OUTPUT (after the decode and the drift fix), per sample: the terms of
+// step 3 on xh_phar_out / xh_pocket_out (Angstrom), shift = com(xh_pocket_out.x) - n_x * com(P_in.x / n_x).  256 threads per sample.
+// ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_restrain_energy(Layout lay, Dims d, RestrainBuf rb, const float* __restrict__ xh_phar_out,
+                                                         const float* __restrict__ xh_pocket_out, float* __restrict__ energy_out) {
+    extern __shared__ float4 s_q[];                 // [max_n] pocket atoms, then xhat [max_n][3], e [max_n], v [max_n]
+    float* s_xh = reinterpret_cast<float*>(s_q + lay.max_n);
+    float* s_e = s_xh + (size_t)lay.max_n * 3;
+    float* s_v = s_e + lay.max_n;
+    __shared__ float s_shift[3];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6, nt = blockDim.x;
+    const int nl = lay.num_phar[b], np = lay.num_pocket[b];
+    const int pb = lay.phar_base[b], qb = lay.pocket_base[b];
+    const int ld = 3 + d.P, ldq = 3 + d.R;
+    const int r0 = rb.rstart[b], r1 = rb.rstart[b + 1];
+    if (!(r1 > r0 || rb.clash_r > 0.f)) {           // no restraint touches the sample
+        if (tid == 0) { energy_out[2 * b] = 0.f; energy_out[2 * b + 1] = 0.f; }
+        return;
+    }
+    for (int idx = tid; idx < 3 * nl; idx += nt) { const int i = idx / 3, k = idx - 3 * i; s_xh[idx] = xh_phar_out[(size_t)(pb + i) * ld + k]; }
+    for (int i = tid; i < np; i += nt) {
+        const float* q = xh_pocket_out + (size_t)(qb + i) * ldq;
+        s_q[i] = make_float4(q[0], q[1], q[2], 0.f);
+    }
+    __syncthreads();
+    if (wave == 0) {
+        float c0, c1, c2;
+        wave_com(s_q, np, lane, c0, c1, c2);
+        const float4 pin = rb.pin_com[b];
+        if (lane == 0) { s_shift[0] = c0 - d.norm_x * pin.x; s_shift[1] = c1 - d.norm_x * pin.y; s_shift[2] = c2 - d.norm_x * pin.z; }
+    }
+    __syncthreads();
+    const float sx = s_shift[0], sy = s_shift[1], sz = s_shift[2];
+    for (int i = wave; i < nl; i += nwaves) {
+        const PointTerm t = point_terms(rb, r0, r1, i, np, s_xh, s_q, 1.0f, sx, sy, sz, lane);
+        if (lane == 0) { s_e[i] = t.e; s_v[i] = t.v; }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float e = 0.f, v = 0.f;
+        for (int i = 0; i < nl; ++i) { e += s_e[i]; v = fmaxf(v, s_v[i]); }     // index order
+        energy_out[2 * b] = e; energy_out[2 * b + 1] = v;
+    }
+}
+
+void cmdgen_launch_restrain_prep(const Layout& lay, const Dims& d, const RestrainBuf& rb, const float* px, hipStream_t s) {
+    hipLaunchKernelGGL(k_restrain_prep, dim3(lay.B), dim3(64), 0, s, lay, d, rb, px);
+}
+void cmdgen_launch_restrained_step_count(const Layout& lay, const Dims& d, const ChainBuf& c, const RestrainBuf& rb, const Work& w,
+                                         const float* eps, int own_vel, hipStream_t s) {
+    const size_t shm = plan_restrained_step_lds(lay.max_n, d.P);
+    const dim3 block(lay.max_n > 128 ? 1024 : 256);             // as k_step_count
+    if (own_vel) hipLaunchKernelGGL(k_restrained_step_count<true>, dim3(lay.B), block, shm, s, lay, d, c, rb, w, eps);
+    else hipLaunchKernelGGL(k_restrained_step_count<false>, dim3(lay.B), block, shm, s, lay, d, c, rb, w, eps);
+}
+void cmdgen_launch_restrain_energy(const Layout& lay, const Dims& d, const RestrainBuf& rb, const float* xo, const float* po,
+                                   float* energy_out, hipStream_t s) {
+    const size_t shm = (size_t)lay.max_n * (sizeof(float4) + 5 * sizeof(float));
+    hipLaunchKernelGGL(k_restrain_energy, dim3(lay.B), dim3(256), shm, s, lay, d, rb, xo, po, energy_out);
+}

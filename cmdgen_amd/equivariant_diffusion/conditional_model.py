@@ -183,6 +183,64 @@ class ConditionalDDPM(EnVariationalDiffusion):
         out = self._finish_chain(h, run, self.inpaint_frames(1, 1, timesteps, return_frames), return_frames)
         return out[0], out[1], phar_mask, pocket['mask']
 
+    @torch.no_grad()
+    def sample_restrained(self, pocket, num_nodes_phar, restraints, clash=None, scale=1.0, max_shift=None, guide_below=1.0,
+                          return_frames=1, timesteps=None, noise=None, seed=None, pocket_ids=None):
+        """sample_given_pocket BIASED toward a geometric query: the same chain (ops, draws, Philox counters) with a guidance term in
+        the mean of every posterior op - the gradient of a restraint energy at the denoised estimate, times the op's posterior variance
+        (cmdgen_restrained_chain; the header of csrc/kernels_restrain.hip defines every term).  The whole chain runs on the device.
+
+        restraints: list of dicts (cmdgen_amd/restraints.py), centres in the frame of pocket['x'], lengths in Angstrom:
+          {'kind': 'position', 'sample': b, 'point': i, 'center': (x, y, z), 'radius': r, 'k': k}
+          {'kind': 'distance', 'sample': b, 'points': (i, j), 'lo': lo, 'hi': hi, 'k': k}
+          {'kind': 'exclusion', 'sample': b, 'center': (x, y, z), 'radius': r, 'k': k}
+        clash: None, a radius, or (radius, k): no point within the radius of a pocket atom, for every sample.  scale multiplies the
+        guidance (0: sample_given_pocket, bit for bit); max_shift (A, default restraints.DEFAULT_MAX_SHIFT) caps a point's
+        displacement per op; ops with t / T > guide_below are not guided.  The other arguments as sample_given_pocket.
+        Returns sample_given_pocket's tuple plus {'energy': [B], 'max_violation': [B]} of the returned sample (and 'op_energy'
+        [timesteps, B], the energy at every op's denoised estimate, when return_frames > 1)."""
+        from .. import restraints as rs
+        timesteps = self.T if timesteps is None else timesteps
+        assert 0 < return_frames <= timesteps
+        assert timesteps % return_frames == 0
+        n_samples = len(pocket['size'])
+        device = pocket['x'].device
+        nph = torch.as_tensor(num_nodes_phar).detach().to('cpu', torch.int64).numpy()
+        assert len(nph) == n_samples
+        rec = rs.records(restraints, nph)
+        clash_r, clash_k = rs.clash_pair(clash)
+        scale, max_shift, guide_below = rs.check_scalars(scale, rs.DEFAULT_MAX_SHIFT if max_shift is None else max_shift, guide_below)
+        pm = pocket['mask']
+        if pm.numel() > 1 and bool((pm[1:] < pm[:-1]).any()):
+            raise ValueError('pocket mask must be ascending and contiguous')
+        self.refresh_learned_schedule()
+        h = self.dynamics.hip_handle()
+        sizes = pocket['size'].detach().to('cpu', torch.int64).numpy()
+        h.set_layout(nph, sizes)
+        h.set_step_table(timesteps, self.step_table(timesteps))
+        h.set_guide_table(timesteps, self.guide_table(timesteps))
+        phar_mask = utils.num_nodes_to_batch_mask(n_samples, torch.as_tensor(nph), device)
+        px = pocket['x'].detach().to(torch.float32).contiguous()
+        poh = pocket['one_hot'].detach().to(torch.float32).contiguous()
+        if noise is not None:
+            noise = noise.detach().to(device, torch.float32).contiguous()
+        if seed is None:
+            seed = fresh_seed()
+        extra = {}
+
+        def run():
+            out = h.restrained_chain(px, poh, timesteps, rec, clash_radius=clash_r, clash_k=clash_k, scale=scale, max_shift=max_shift,
+                                     guide_below=guide_below, noise=noise, seed=seed, pocket_ids=pocket_ids,
+                                     want_steps=return_frames > 1, use_graph=self.use_hip_graph)
+            extra['energy'], extra['op_energy'] = out[3], out[4]
+            return out[:3]
+
+        out = self._finish_chain(h, run, self.inpaint_frames(1, 1, timesteps, return_frames), return_frames)
+        info = {'energy': extra['energy'][:, 0].clone(), 'max_violation': extra['energy'][:, 1].clone()}
+        if return_frames > 1:
+            info['op_energy'] = extra['op_energy']
+        return out[0], out[1], phar_mask, pocket['mask'], info
+
     @staticmethod
     def group_weights(weights, n_groups, n_members):
         """weights None (uniform), [M] or [G, M] -> float32 numpy [G, M], every row normalised to sum 1 in float64."""
@@ -673,6 +731,10 @@ class SimpleConditionalDDPM(ConditionalDDPM):
     def sample_given_pockets(self, *args, **kwargs):
         raise NotImplementedError('sample_given_pockets is not implemented for SimpleConditionalDDPM (no centre-of-mass projection: the '
                                   'shared latent has no frame of its own); use ConditionalDDPM')
+
+    def sample_restrained(self, *args, **kwargs):
+        raise NotImplementedError('sample_restrained is not implemented for SimpleConditionalDDPM (no centre-of-mass projection: the '
+                                  'guidance frame follows the projections); use ConditionalDDPM')
 
     def edit_given_pockets(self, *args, **kwargs):
         raise NotImplementedError('edit_given_pockets is not implemented for SimpleConditionalDDPM (no centre-of-mass projection: the '

@@ -260,6 +260,29 @@ class EnVariationalDiffusion(nn.Module):
         cache[K] = (table.clone(), out)
         return out
 
+    def guide_table(self, timesteps: int) -> np.ndarray:
+        """[K, 2] sigma_t and alpha_t of every posterior op (rows s = K-1 .. 0, t = (s+1)/K), beside step_table and with its op sequence:
+        the scalars of the restrained chain's denoised estimate (cmdgen_set_guide_table)."""
+        table = torch.from_numpy(self.gamma_table_host())
+        T, K = self.T, timesteps
+        cache = self.__dict__.setdefault('_guide_tables', {})
+        hit = cache.get(K)
+        if hit is not None and torch.equal(hit[0], table):
+            return hit[1]
+        z = torch.zeros(1, 1)
+        if self.learned_schedule:
+            net = self.gamma.cpu_copy()
+            look = lambda t: net(t).detach()
+        else:
+            look = lambda t: table[torch.round(t * T).long()]
+        rows = []
+        for s in reversed(range(K)):
+            g_t = look((torch.full((1, 1), fill_value=s) + 1) / K)
+            rows.append([self.sigma(g_t, z).item(), self.alpha(g_t, z).item()])
+        out = np.asarray(rows, dtype=np.float32)
+        cache[K] = (table.clone(), out)
+        return out
+
     # ---- normalisation (en_diffusion.py:874-906)
     def normalize(self, phar=None, pocket=None):
         if phar is not None:
@@ -553,6 +576,10 @@ class EnVariationalDiffusion(nn.Module):
     def sample_given_pockets(self, *args, **kwargs):
         raise NotImplementedError('sample_given_pockets is not implemented for the joint model (its pocket nodes diffuse with the '
                                   'latent, so several pockets cannot share one); use ConditionalDDPM')
+
+    def sample_restrained(self, *args, **kwargs):
+        raise NotImplementedError('sample_restrained is not implemented for the joint model (its pocket nodes diffuse with the latent: '
+                                  'there is no fixed pocket frame to place the restraints in); use ConditionalDDPM')
 
     def edit_given_pockets(self, *args, **kwargs):
         raise NotImplementedError('edit_given_pockets is not implemented for the joint model (its pocket nodes diffuse with the '

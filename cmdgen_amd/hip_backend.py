@@ -11,6 +11,8 @@ from typing import Dict, Optional, Sequence
 
 import numpy as np
 
+from .restraints import DEFAULT_MAX_SHIFT, RESTRAINT_DTYPE
+
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'libcmdgen_hip.so')
 _lib = None
 
@@ -74,6 +76,9 @@ SYMBOLS = [
     ('cmdgen_score_chain', C.c_int, [_vp, _fp, _fp, _fp, _fp, C.c_int32, _vp, _vp, _fp, C.c_uint64, _i64p, _fp, _fp, C.c_int32, _vp]),
     ('cmdgen_multi_score_chain', C.c_int, [_vp, _fp, _fp, _fp, _fp, C.c_int64, _i64p, _vp, C.c_int32, _vp, _vp, _fp, C.c_uint64, _i64p,
                                            _fp, _fp, _fp, C.c_int32, _vp]),
+    ('cmdgen_restrained_chain', C.c_int, [_vp, _fp, _fp, C.c_int32, _vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                          _fp, C.c_uint64, _i64p, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int32, _vp]),
+    ('cmdgen_set_guide_table', C.c_int, [_vp, C.c_int32, _vp]),
     ('cmdgen_param_count', C.c_int, [_vp, _i64p]),
     ('cmdgen_param_offset', C.c_int, [_vp, C.c_char_p, _i64p, _i64p]),
     ('cmdgen_train_forward', C.c_int, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),
@@ -352,6 +357,40 @@ class Handle:
             self._pocket_ids(pocket_ids), _ptr(xh_phar), _ptr(xh_pocket),
             _ptr(z_steps), _ptr(p_steps), int(bool(use_graph)), self._stream()), 'cmdgen_sample_chain')
         return xh_phar, xh_pocket, z_steps
+
+    def set_guide_table(self, K: int, sigma_alpha: 'np.ndarray'):
+        a = np.ascontiguousarray(sigma_alpha, dtype=np.float32)
+        assert a.shape == (K, 2)
+        self._check(self.lib.cmdgen_set_guide_table(self.h, K, a.ctypes.data_as(C.c_void_p)), 'cmdgen_set_guide_table')
+
+    def restrained_chain(self, pocket_x, pocket_onehot, timesteps: int, restraints=None, clash_radius: float = 0.0, clash_k: float = 0.0,
+                         scale: float = 1.0, max_shift: float = DEFAULT_MAX_SHIFT, guide_below: float = 1.0, noise=None, seed: int = 0,
+                         pocket_ids: Optional[Sequence[int]] = None, want_steps: bool = False, use_graph: bool = True):
+        """cmdgen_restrained_chain: sample_chain with a guidance term from geometric restraints in every posterior op (the header of
+        kernels_restrain.hip defines it).  restraints: a RESTRAINT_DTYPE array (restraint_records) or None.
+        -> (xh_phar, xh_pocket, z_steps, energy [B, 2] (E and the largest violation in A of the output), op_energy [K, B] or None)."""
+        import torch
+        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
+        dev = pocket_x.device
+        self._check_dev(pocket_x, (self.n_pocket, 3))
+        self._check_dev(pocket_onehot, (self.n_pocket, R))
+        if noise is not None:
+            self._check_dev(noise, (timesteps + 2, self.n_phar, 3 + P))
+        rec = np.zeros(0, dtype=RESTRAINT_DTYPE) if restraints is None else np.ascontiguousarray(restraints, dtype=RESTRAINT_DTYPE)
+        assert rec.ndim == 1
+        xh_phar = torch.empty((self.n_phar, 3 + P), dtype=torch.float32, device=dev)
+        xh_pocket = torch.empty((self.n_pocket, 3 + R), dtype=torch.float32, device=dev)
+        z_steps = torch.empty((timesteps, self.n_phar, 3 + P), dtype=torch.float32, device=dev) if want_steps else None
+        p_steps = torch.empty((timesteps, self.n_pocket, 3), dtype=torch.float32, device=dev) if want_steps else None
+        energy = torch.empty((self.batch, 2), dtype=torch.float32, device=dev)
+        op_energy = torch.empty((timesteps, self.batch), dtype=torch.float32, device=dev) if want_steps else None
+        self.last_pocket_steps = p_steps
+        self._check(self.lib.cmdgen_restrained_chain(
+            self.h, _ptr(pocket_x), _ptr(pocket_onehot), int(timesteps), rec.ctypes.data_as(C.c_void_p) if len(rec) else None, len(rec),
+            float(clash_radius), float(clash_k), float(scale), float(max_shift), float(guide_below),
+            _ptr(noise), C.c_uint64(seed & (2 ** 64 - 1)), self._pocket_ids(pocket_ids), _ptr(xh_phar), _ptr(xh_pocket),
+            _ptr(z_steps), _ptr(p_steps), _ptr(energy), _ptr(op_energy), int(bool(use_graph)), self._stream()), 'cmdgen_restrained_chain')
+        return xh_phar, xh_pocket, z_steps, energy, op_energy
 
     MAX_GROUP = 8                    # include/cmdgen_hip.h: CMDGEN_MAX_GROUP
 

@@ -381,6 +381,50 @@ class PharPocketDDPM(nn.Module):
                 phar_to_coords.setdefault(f'Molecule_{k}', {}).setdefault(name, []).append(coords)
         return phar_to_coords
 
+    @torch.no_grad()
+    def generate_phars_restrained(self, pdb_file, n_samples, restraints, pocket_ids=None, ref_ligand=None, num_nodes_phar=None,
+                                  clash=None, scale=1.0, max_shift=None, guide_below=1.0, timesteps=None, seed=None, noise=None):
+        """Generate pharmacophores inside a pocket BIASED toward a geometric query (ConditionalDDPM.sample_restrained): "a feature
+        within 1.5 A of this spot", "two features 5 to 7 A apart", "nothing inside this excluded volume", "no point on a pocket atom".
+
+        restraints: the dicts of cmdgen_amd/restraints.py WITHOUT 'sample', given once in the PDB's frame and applied to every one of
+        the n_samples copies; a point index names a row of every sample.  clash: None, a radius, or (radius, k).  num_nodes_phar:
+        points per sample, default the size prior given the pocket, at least as many as the restraints name.  scale, max_shift,
+        guide_below as sample_restrained; the pocket and the move back to its position as generate_phars.
+        -> (one point list per sample, [(type name, (x, y, z))] in the PDB's frame - edit_phars' format, the ``candidates`` of
+        score_phars - and {'energy': [n_samples], 'max_violation': [n_samples]} of the returned samples, to filter on)."""
+        from . import restraints as rs
+        assert (pocket_ids is None) ^ (ref_ligand is None)
+        if not isinstance(self.ddpm, ConditionalDDPM):
+            raise NotImplementedError('generate_phars_restrained needs the conditional model (mode pocket_conditioning)')
+        restraints = list(restraints)
+        for n, r in enumerate(restraints):
+            if isinstance(r, dict) and 'sample' in r:
+                raise ValueError(f"restraints[{n}] = {r!r}: restraints are given once, without 'sample', and applied to every sample")
+        named = [int(v) for r in restraints if isinstance(r, dict)
+                 for v in ([r['point']] if 'point' in r else list(r.get('points', ()))) if isinstance(v, (int, np.integer))]
+        pocket = self._pdb_pocket(pdb_file, n_samples, pocket_ids, ref_ligand)
+        pocket_com_before = _scatter_mean(pocket['x'], pocket['mask'], n_samples)
+        if num_nodes_phar is None:
+            num_nodes_phar = self.ddpm.size_distribution.sample_conditional(n1=None, n2=pocket['size'])
+            num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device).clamp(min=max(named, default=0) + 1)
+        else:
+            num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device).reshape(-1)
+            if num_nodes_phar.numel() == 1:
+                num_nodes_phar = num_nodes_phar.expand(n_samples)
+        num_nodes_phar = num_nodes_phar.to(INT_TYPE)
+        nph = num_nodes_phar.cpu().numpy()
+        for b in range(n_samples):
+            rs.records(restraints, nph, sample=b)                       # (names the entry of the caller's list)
+        per_sample = [dict(r, sample=b) for b in range(n_samples) for r in restraints]
+        xh_phar, xh_pocket, phar_mask, pocket_mask, info = self.ddpm.sample_restrained(
+            pocket, num_nodes_phar, per_sample, clash=clash, scale=scale, max_shift=max_shift, guide_below=guide_below,
+            timesteps=timesteps, seed=seed, noise=noise)
+        # move the points back to the original pocket position (as generate_phars)
+        pocket_com_after = _scatter_mean(xh_pocket[:, :self.x_dims], pocket_mask, n_samples)
+        xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
+        return self._point_lists(xh_phar, {'size': num_nodes_phar}), info
+
     def _phar_with_given_rows(self, points, arg, n_samples, num_nodes_phar, pocket):
         """The phar batch of inpaint_phars / edit_phars: `points` = [(type name, (x, y, z))] are the first rows of every sample, the
         other rows zero.  num_nodes_phar: points per sample, default the size prior given the pocket, at least len(points).

@@ -457,6 +457,53 @@ int cmdgen_multi_score_chain(cmdgen_handle* h, const float* phar_x, const float*
                              float* group_terms_out, float* member_terms_out, float* kl_sums_out,
                              int32_t use_graph, cmdgen_stream stream);
 
+/* Sampling steered by geometric restraints (ConditionalDDPM.sample_restrained): cmdgen_sample_chain's chain - the same ops, draws and
+ * Philox counters - with one addition to the mean of every posterior op t -> s (classifier guidance); the decode op is not guided.
+ * The definition is the project's own (the reference has nothing like it); kernels_restrain.hip carries it in full.  Per sample and op,
+ * with z the op's input, e the network's x columns after the NaN guard, P the current (translated, normalised) pocket, P_in the caller's
+ * pocket, n_x = norm_values[0] and coef the op's step-table row:
+ *   xhat_i = n_x (z.x_i - sigma_t e_i) / alpha_t             the denoised estimate, in Angstrom, in the chain's current frame
+ *   shift  = n_x (com(P.x) - com(P_in.x / n_x))              centres c of the caller's frame become c + shift; q_a = n_x P.x_a
+ *   E      = sum over restraints of 0.5 k v^2                v >= 0 the violation in Angstrom, k >= 0 in 1/Angstrom^2:
+ *            position(point i, c, r, k)   v = max(0, |xhat_i - (c + shift)| - r)
+ *            distance(points i, j, lo, hi, k)  v = max(0, lo - d, d - hi), d = |xhat_i - xhat_j|
+ *            exclusion(c, r, k)           for every point of the sample  v_i = max(0, r - |xhat_i - (c + shift)|)
+ *            clash(r_c, k_c)              for every point and pocket atom of every sample  v_ia = max(0, r_c - |xhat_i - q_a|)
+ *   g_i    = dE / dxhat_i                                     (a term whose distance is below 1e-12 A contributes the zero vector)
+ *   d_i    = -scale (n_x coef.z)^2 g_i,  scaled down to |d_i| = max_shift when longer;  d = 0 for an op with t / T > guide_below
+ *   mu.x_i = z.x_i / coef.x - coef.y e_i + d_i / n_x          the h columns, the draw, the projection and the saved steps as before
+ * sigma_t and alpha_t come from the guide table (cmdgen_set_guide_table, or the library's own evaluation of the gamma table).
+ * With no restraint on any sample and clash_radius = 0, or with scale = 0, every output equals cmdgen_sample_chain's bit for bit; a
+ * sample that no restraint touches takes k_step_count's arithmetic.  No float atomics: two runs of the same inputs are equal bit for bit.
+ *   restraints_host  host [n_restraints] (or NULL with n_restraints = 0), any order; a sample's restraints keep their list order
+ *   clash_radius, clash_k   r_c in Angstrom (0: off), k_c
+ *   scale, max_shift (Angstrom, > 0), guide_below in [0, 1]
+ *   energy_out     dev [batch][2]: E and the largest violation (Angstrom) of the RETURNED xh_phar / xh_pocket, shift taken from the
+ *                  returned pocket
+ *   op_energy_out  dev [K][batch] E at xhat of every op, or NULL
+ *   the other arguments as cmdgen_sample_chain
+ * The chain has a slot of its own and is captured like the others; the restraint table and the five scalars are part of the slot's
+ * tables, so a change prepares the slot (and its graph) again.
+ * Refused (CMDGEN_EINVAL): an unknown kind, a sample index outside the layout, a point index >= n_phar of its sample, i == j, lo > hi,
+ * a negative or non-finite radius, bound, centre, k, scale or clash value, max_shift <= 0, guide_below outside [0, 1], more than
+ * CMDGEN_MAX_RESTRAINTS restraints on one sample, a sample beyond the step's 64 KiB of LDS, a no_com_projection handle; the joint
+ * model (CMDGEN_ESTATE).
+ * Asynchronous on `stream`; cmdgen_chain_status reports this run's checks, drift and NaN resets. */
+#define CMDGEN_RESTRAINT_POSITION  0
+#define CMDGEN_RESTRAINT_DISTANCE  1
+#define CMDGEN_RESTRAINT_EXCLUSION 2
+#define CMDGEN_MAX_RESTRAINTS 256      /* per sample */
+typedef struct {
+    int32_t kind, sample, i, j;        /* position: point i; distance: points i, j; exclusion: neither */
+    float c[3], a, b, k;               /* centre; a, b: radius, - | lo, hi | radius, -; k */
+} cmdgen_restraint;
+int cmdgen_restrained_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot, int32_t timesteps,
+                            const cmdgen_restraint* restraints_host, int64_t n_restraints,
+                            float clash_radius, float clash_k, float scale, float max_shift, float guide_below,
+                            const float* noise, uint64_t seed, const int64_t* pocket_ids_host,
+                            float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                            float* energy_out, float* op_energy_out, int32_t use_graph, cmdgen_stream stream);
+
 /* ---- training step (conditional model) -------------------------------------------------- */
 /* The trainable tensors of EGNNDynamics live in ONE flat fp32 device buffer owned by the caller, in the
  * reference's registration order (the state_dict order below 'ddpm.dynamics.': weight then bias of every
@@ -610,6 +657,11 @@ int cmdgen_debug_sgemm(cmdgen_handle* h, int32_t ta, int32_t tb, int32_t M, int3
  * (conditional_model.py:345-366, :108-131; en_diffusion.py:79-103).  Used by the next
  * cmdgen_sample_chain whose `timesteps` equals K. */
 int cmdgen_set_step_table(cmdgen_handle* h, int32_t K, const float* coef_host);
+
+/* Optional, beside the step table: sigma_t and alpha_t of every posterior op (rows s = K-1 .. 0, t = (s+1)/K; [K][2]) for the
+ * denoised estimate of cmdgen_restrained_chain, computed by the host with the reference's own fp32 ops.  Used by the next
+ * cmdgen_restrained_chain whose `timesteps` equals K; otherwise the library evaluates both from its gamma table. */
+int cmdgen_set_guide_table(cmdgen_handle* h, int32_t K, const float* sigma_alpha_host);
 
 /* Deferred, non-syncing versions of the reference's in-loop checks, read back after the
  * chain (synchronises the stream):
