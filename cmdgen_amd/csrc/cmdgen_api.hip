@@ -647,7 +647,7 @@ extern "C" int cmdgen_debug_read(cmdgen_handle* h, const char* what, float* host
         const ChainBuf* cb = h->last_chain == CHAIN_PLAIN ? &h->chain : h->last_chain == CHAIN_INPAINT ? &h->inp_chain :
                              h->last_chain == CHAIN_MULTI ? &h->multi_chain : h->last_chain == CHAIN_MULTI_EDIT ? &h->medit_chain :
                              h->last_chain == CHAIN_MULTI_SCORE ? &h->mscore_chain :               // (the last level's z of the multi-pocket scoring chain)
-                             h->last_chain == CHAIN_RESTRAINED ? &h->restr_chain : nullptr;
+                             h->last_chain == CHAIN_RESTRAINED ? &h->restr_chain : h->last_chain == CHAIN_RESTRAINED_EDIT ? &h->redit_chain : nullptr;
         if (!cb || !cb->z_phar || h->chains[h->last_chain].n_steps < 0) return fail(h, CMDGEN_ESTATE, "no conditional chain has run on this layout");
         src = cb->z_phar; have = (size_t)h->lay.Nl * (3 + d.P);
     }
@@ -938,6 +938,57 @@ extern "C" int cmdgen_set_guide_table(cmdgen_handle* h, int32_t K, const float* 
     return CMDGEN_OK;
 }
 
+// the restraint arguments of cmdgen_restrained_chain and cmdgen_restrained_edit_chain, checked (step_lds: the step kernel's LDS for this layout);
+// rstart [B + 1]: the CSR offsets, rec: the records sorted by sample, the fields a kind does not read zeroed
+static int check_restraints(cmdgen_handle* h, const cmdgen_restraint* restraints_host, int64_t n_restraints, float clash_radius, float clash_k,
+                            float scale, float max_shift, float guide_below, size_t step_lds, std::vector<int>& rstart,
+                            std::vector<cmdgen_restraint>& rec) {
+    if (n_restraints < 0 || (n_restraints > 0 && !restraints_host)) return fail(h, CMDGEN_EINVAL, "n_restraints=%lld without a restraint list", (long long)n_restraints);
+    auto ok = [](float v) { return std::isfinite(v) && v >= 0.f; };
+    if (!ok(clash_radius) || !ok(clash_k)) return fail(h, CMDGEN_EINVAL, "clash_radius=%g, clash_k=%g must be finite and >= 0", (double)clash_radius, (double)clash_k);
+    if (!ok(scale)) return fail(h, CMDGEN_EINVAL, "scale=%g must be finite and >= 0", (double)scale);
+    if (!(std::isfinite(max_shift) && max_shift > 0.f)) return fail(h, CMDGEN_EINVAL, "max_shift=%g must be finite and > 0", (double)max_shift);
+    if (!(guide_below >= 0.f && guide_below <= 1.f)) return fail(h, CMDGEN_EINVAL, "guide_below=%g must be in [0, 1]", (double)guide_below);
+    const int B = h->lay.B;
+    rstart.assign((size_t)B + 1, 0);
+    for (int64_t r = 0; r < n_restraints; ++r) {
+        const cmdgen_restraint& q = restraints_host[r];
+        const long long ri = (long long)r;
+        if (q.kind != RK_POSITION && q.kind != RK_DISTANCE && q.kind != RK_EXCLUSION) return fail(h, CMDGEN_EINVAL, "restraint %lld: unknown kind %d", ri, q.kind);
+        if (q.sample < 0 || q.sample >= B) return fail(h, CMDGEN_EINVAL, "restraint %lld: sample %d outside the layout's %d samples", ri, q.sample, B);
+        const long long nl = (long long)h->cur_nphar[q.sample];
+        if (q.kind != RK_EXCLUSION && (q.i < 0 || q.i >= nl)) return fail(h, CMDGEN_EINVAL, "restraint %lld: point %d, sample %d has %lld points", ri, q.i, q.sample, nl);
+        if (q.kind == RK_DISTANCE) {
+            if (q.j < 0 || q.j >= nl) return fail(h, CMDGEN_EINVAL, "restraint %lld: point %d, sample %d has %lld points", ri, q.j, q.sample, nl);
+            if (q.i == q.j) return fail(h, CMDGEN_EINVAL, "restraint %lld: a distance between point %d and itself (i == j)", ri, q.i);
+            if (!ok(q.a) || !ok(q.b)) return fail(h, CMDGEN_EINVAL, "restraint %lld: lo=%g, hi=%g must be finite and >= 0", ri, (double)q.a, (double)q.b);
+            if (q.a > q.b) return fail(h, CMDGEN_EINVAL, "restraint %lld: lo=%g > hi=%g", ri, (double)q.a, (double)q.b);
+        } else {
+            if (!ok(q.a)) return fail(h, CMDGEN_EINVAL, "restraint %lld: radius=%g must be finite and >= 0", ri, (double)q.a);
+            if (!std::isfinite(q.c[0]) || !std::isfinite(q.c[1]) || !std::isfinite(q.c[2])) return fail(h, CMDGEN_EINVAL, "restraint %lld: a non-finite centre", ri);
+        }
+        if (!ok(q.k)) return fail(h, CMDGEN_EINVAL, "restraint %lld: k=%g must be finite and >= 0", ri, (double)q.k);
+        if (++rstart[(size_t)q.sample + 1] > CMDGEN_MAX_RESTRAINTS)
+            return fail(h, CMDGEN_EINVAL, "sample %d has more than %d restraints", q.sample, CMDGEN_MAX_RESTRAINTS);
+    }
+    if (step_lds > PLAN_RESTRAINED_LDS_MAX)
+        return fail(h, CMDGEN_EINVAL, "a sample has %d nodes: the restrained step keeps a sample's positions, z and guidance terms in LDS (64 KiB)", h->lay.max_n);
+    for (int b = 0; b < B; ++b) rstart[(size_t)b + 1] += rstart[b];
+    rec.assign((size_t)n_restraints, cmdgen_restraint{});
+    {
+        std::vector<int> at(rstart.begin(), rstart.end() - 1);
+        for (int64_t r = 0; r < n_restraints; ++r) {             // stable: a sample's restraints keep their list order
+            cmdgen_restraint q = restraints_host[r];
+            if (q.kind == RK_EXCLUSION) { q.i = 0; q.j = 0; }
+            if (q.kind == RK_POSITION) q.j = 0;
+            if (q.kind != RK_DISTANCE) q.b = 0.f;
+            if (q.kind == RK_DISTANCE) q.c[0] = q.c[1] = q.c[2] = 0.f;
+            rec[(size_t)at[q.sample]++] = q;                     // (fields a kind does not read are zeroed: they are part of the slot's key)
+        }
+    }
+    return 0;
+}
+
 static int alloc_restrained(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
     int rc = alloc_chain_buf(h, k, h->restr_chain, tables); if (rc) return rc;
     const size_t B = (size_t)h->lay.B;
@@ -967,49 +1018,11 @@ extern "C" int cmdgen_restrained_chain(cmdgen_handle* h, const float* pocket_x, 
     if (K < 1 || K > h->cfg.timesteps) return fail(h, CMDGEN_EINVAL, "timesteps=%d must be in [1, %d]", K, h->cfg.timesteps);
     if (h->dims.joint) return fail(h, CMDGEN_ESTATE, "the restrained chain is not supported for the joint model (update_pocket_coords=1): its pocket nodes diffuse with the latent");
     if (h->dims.no_com) return fail(h, CMDGEN_EINVAL, "the restrained chain is not supported for no_com_projection handles (SimpleConditionalDDPM): the guidance frame follows the centre-of-mass projections");
-    if (n_restraints < 0 || (n_restraints > 0 && !restraints_host)) return fail(h, CMDGEN_EINVAL, "n_restraints=%lld without a restraint list", (long long)n_restraints);
-    auto ok = [](float v) { return std::isfinite(v) && v >= 0.f; };
-    if (!ok(clash_radius) || !ok(clash_k)) return fail(h, CMDGEN_EINVAL, "clash_radius=%g, clash_k=%g must be finite and >= 0", (double)clash_radius, (double)clash_k);
-    if (!ok(scale)) return fail(h, CMDGEN_EINVAL, "scale=%g must be finite and >= 0", (double)scale);
-    if (!(std::isfinite(max_shift) && max_shift > 0.f)) return fail(h, CMDGEN_EINVAL, "max_shift=%g must be finite and > 0", (double)max_shift);
-    if (!(guide_below >= 0.f && guide_below <= 1.f)) return fail(h, CMDGEN_EINVAL, "guide_below=%g must be in [0, 1]", (double)guide_below);
+    std::vector<int> rstart; std::vector<cmdgen_restraint> rec;
+    rc = check_restraints(h, restraints_host, n_restraints, clash_radius, clash_k, scale, max_shift, guide_below,
+                          plan_restrained_step_lds(h->lay.max_n, h->dims.P), rstart, rec);
+    if (rc) return rc;
     const int B = h->lay.B;
-    std::vector<int> rstart((size_t)B + 1, 0);
-    for (int64_t r = 0; r < n_restraints; ++r) {
-        const cmdgen_restraint& q = restraints_host[r];
-        const long long ri = (long long)r;
-        if (q.kind != RK_POSITION && q.kind != RK_DISTANCE && q.kind != RK_EXCLUSION) return fail(h, CMDGEN_EINVAL, "restraint %lld: unknown kind %d", ri, q.kind);
-        if (q.sample < 0 || q.sample >= B) return fail(h, CMDGEN_EINVAL, "restraint %lld: sample %d outside the layout's %d samples", ri, q.sample, B);
-        const long long nl = (long long)h->cur_nphar[q.sample];
-        if (q.kind != RK_EXCLUSION && (q.i < 0 || q.i >= nl)) return fail(h, CMDGEN_EINVAL, "restraint %lld: point %d, sample %d has %lld points", ri, q.i, q.sample, nl);
-        if (q.kind == RK_DISTANCE) {
-            if (q.j < 0 || q.j >= nl) return fail(h, CMDGEN_EINVAL, "restraint %lld: point %d, sample %d has %lld points", ri, q.j, q.sample, nl);
-            if (q.i == q.j) return fail(h, CMDGEN_EINVAL, "restraint %lld: a distance between point %d and itself (i == j)", ri, q.i);
-            if (!ok(q.a) || !ok(q.b)) return fail(h, CMDGEN_EINVAL, "restraint %lld: lo=%g, hi=%g must be finite and >= 0", ri, (double)q.a, (double)q.b);
-            if (q.a > q.b) return fail(h, CMDGEN_EINVAL, "restraint %lld: lo=%g > hi=%g", ri, (double)q.a, (double)q.b);
-        } else {
-            if (!ok(q.a)) return fail(h, CMDGEN_EINVAL, "restraint %lld: radius=%g must be finite and >= 0", ri, (double)q.a);
-            if (!std::isfinite(q.c[0]) || !std::isfinite(q.c[1]) || !std::isfinite(q.c[2])) return fail(h, CMDGEN_EINVAL, "restraint %lld: a non-finite centre", ri);
-        }
-        if (!ok(q.k)) return fail(h, CMDGEN_EINVAL, "restraint %lld: k=%g must be finite and >= 0", ri, (double)q.k);
-        if (++rstart[(size_t)q.sample + 1] > CMDGEN_MAX_RESTRAINTS)
-            return fail(h, CMDGEN_EINVAL, "sample %d has more than %d restraints", q.sample, CMDGEN_MAX_RESTRAINTS);
-    }
-    if (plan_restrained_step_lds(h->lay.max_n, h->dims.P) > PLAN_RESTRAINED_LDS_MAX)
-        return fail(h, CMDGEN_EINVAL, "a sample has %d nodes: the restrained step keeps a sample's positions, z and guidance terms in LDS (64 KiB)", h->lay.max_n);
-    for (int b = 0; b < B; ++b) rstart[(size_t)b + 1] += rstart[b];
-    std::vector<cmdgen_restraint> rec((size_t)n_restraints);
-    {
-        std::vector<int> at(rstart.begin(), rstart.end() - 1);
-        for (int64_t r = 0; r < n_restraints; ++r) {             // stable: a sample's restraints keep their list order
-            cmdgen_restraint q = restraints_host[r];
-            if (q.kind == RK_EXCLUSION) { q.i = 0; q.j = 0; }
-            if (q.kind == RK_POSITION) q.j = 0;
-            if (q.kind != RK_DISTANCE) q.b = 0.f;
-            if (q.kind == RK_DISTANCE) q.c[0] = q.c[1] = q.c[2] = 0.f;
-            rec[(size_t)at[q.sample]++] = q;                     // (fields a kind does not read are zeroed: they are part of the slot's key)
-        }
-    }
     std::vector<float> tables = step_table(h, K);
     {
         std::vector<float> sa;
@@ -1321,6 +1334,7 @@ extern "C" int cmdgen_joint_chain(cmdgen_handle* h, const float* phar_x, const f
 struct InpaintPlan {
     std::vector<float> coef, coef2;     // [n_steps+1][4] (last: decode row), [n_steps][4]
     std::vector<int> iop;               // [n_steps][4]
+    std::vector<int> s_of;              // [n_steps] the level s every op goes to (t = s + 1)
     int n_steps = 0, n_draws = 0;
     float alpha_start = 0.f, sigma_start = 0.f;     // q(z_start | x) of a chain that starts below t = T
 };
@@ -1343,6 +1357,7 @@ static InpaintPlan build_inpaint_plan(const cmdgen_handle* h, int K, int start, 
             p.coef.insert(p.coef.end(), tab.begin() + (size_t)(K - 1 - s) * 4, tab.begin() + (size_t)(K - s) * 4);
             const float g_s = g_at(s);
             const int rowA = draw++, rowB = draw++;
+            p.s_of.push_back(s);
             float re_a = 0.f, re_s = 0.f; int flags = 0, rowC = 0;
             if (j == sched[i] - 1 && i + 1 < sched.size()) {      // jump back s -> s + jump_length
                 const float g_t2 = g_at(s + jump);
@@ -1463,6 +1478,110 @@ extern "C" int cmdgen_inpaint_chain(cmdgen_handle* h, const float* pocket_x, con
     return cmdgen_edit_chain(h, pocket_x, pocket_onehot, phar_x, phar_onehot, phar_fixed, phar_fixed, timesteps, timesteps, resamplings,
                              jump_length, noise, n_draws, seed, pocket_ids_host, xh_phar_out, xh_pocket_out, z_steps_out,
                              pocket_steps_out, use_graph, stream);
+}
+
+// ---------------------------------------------------------------------------------
+// the restrained edit chain: cmdgen_edit_chain's chain with cmdgen_restrained_chain's guidance in op A (k_restrained_edit_step_count,
+// kernels_restrain.hip, holds the definition).  The slot's table block is the edit plan's tables (coef | coef2 | iop), then one guide row
+// per OP (sigma_t, alpha_t, 0, 0), r_c, k_c, scale, max_shift, guide_below, 0, 0, 0, the CSR offsets [B + 1] and the records sorted by
+// sample - so a changed plan, start, restraint or scalar prepares the slot again and drops its captured steps.
+// ---------------------------------------------------------------------------------
+static int alloc_restrained_edit(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
+    int rc = alloc_chain_buf(h, k, h->redit_chain, tables); if (rc) return rc;
+    const Dims& d = h->dims;
+    const Layout& L = h->lay;
+    InpaintBuf& ip = h->redit;
+    ip.coef2 = (const float4*)(tables + (size_t)(n_steps + 1) * 4);
+    ip.iop = (const int4*)(tables + (size_t)(2 * n_steps + 1) * 4);
+    ip.n_steps = n_steps;
+    RestrainBuf& rb = h->redit_restr;                // (the five scalars are set by the call from its arguments)
+    const float* guide = tables + (size_t)(3 * n_steps + 1) * 4;
+    rb.sa = (const float4*)guide;
+    rb.rstart = (const int*)(guide + (size_t)n_steps * 4 + 8);
+    rb.rec = (const RestraintRec*)(guide + (size_t)n_steps * 4 + 8 + (size_t)L.B + 1);
+    rb.op_energy = nullptr;
+    void* q;
+#define IALLOC(dst, type, bytes) do { rc = dev_alloc(h, k.allocs, &q, bytes, true); if (rc) return rc; dst = (type)q; } while (0)
+    IALLOC(ip.known, const float*, (size_t)L.Nl * (3 + d.P) * sizeof(float));
+    IALLOC(ip.fix, float*, (size_t)L.Nl * sizeof(float));
+    IALLOC(ip.poff, float4*, (size_t)L.B * sizeof(float4));
+    IALLOC(rb.pin_com, float4*, (size_t)L.B * sizeof(float4));
+#undef IALLOC
+    return 0;
+}
+
+extern "C" int cmdgen_restrained_edit_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
+                                            const float* phar_x, const float* phar_onehot, const float* fix_x, const float* fix_h,
+                                            int32_t timesteps, int32_t start, int32_t resamplings, int32_t jump_length,
+                                            const float* noise, int64_t n_draws, uint64_t seed, const int64_t* pocket_ids_host,
+                                            float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                                            const cmdgen_restraint* restraints_host, int64_t n_restraints,
+                                            float clash_radius, float clash_k, float scale, float max_shift, float guide_below,
+                                            float* energy_out, float* op_energy_out, int32_t use_graph, cmdgen_stream stream) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (h->dims.joint) return fail(h, CMDGEN_ESTATE, "the restrained edit chain is not supported for the joint model (update_pocket_coords=1): its pocket nodes diffuse with the latent");
+    if (h->dims.no_com) return fail(h, CMDGEN_ESTATE, "the restrained edit chain is not supported for no_com_projection handles (SimpleConditionalDDPM): the edit chain and the guidance frame follow the centre-of-mass projections");
+    rc = check_inpaint_args(h, timesteps, start, resamplings, jump_length); if (rc) return rc;
+    if (!pocket_x || !pocket_onehot || !phar_x || !phar_onehot || !fix_x || !fix_h || !xh_phar_out || !xh_pocket_out || !energy_out)
+        return fail(h, CMDGEN_EINVAL, "null device pointer");
+    std::vector<int> rstart; std::vector<cmdgen_restraint> rec;
+    rc = check_restraints(h, restraints_host, n_restraints, clash_radius, clash_k, scale, max_shift, guide_below,
+                          plan_restrained_edit_step_lds(h->lay.max_n, h->dims.P), rstart, rec);
+    if (rc) return rc;
+    const InpaintPlan plan = build_inpaint_plan(h, timesteps, start, resamplings, jump_length);
+    if (noise && n_draws < plan.n_draws)
+        return fail(h, CMDGEN_EINVAL, "noise holds %lld draws, the schedule needs %lld", (long long)n_draws, (long long)plan.n_draws);
+    const int n_steps = plan.n_steps, K = timesteps, B = h->lay.B;
+    std::vector<float> tables = plan_tables(plan.coef, plan.coef2, plan.iop);
+    {
+        std::vector<float> sa;                       // [K][2], row K - 1 - s for the op that goes to level s
+        if (h->user_guide_K == K) sa = h->user_guide; else build_guide_table(h->gamma, h->cfg.timesteps, K, sa);
+        const size_t c0 = tables.size();
+        tables.resize(c0 + (size_t)n_steps * 4 + 8 + (size_t)B + 1 + rec.size() * 10, 0.f);
+        float* g = tables.data() + c0;
+        for (int i = 0; i < n_steps; ++i) {
+            const int row = K - 1 - plan.s_of[(size_t)i];
+            g[4 * i] = sa[2 * (size_t)row]; g[4 * i + 1] = sa[2 * (size_t)row + 1];
+        }
+        float* par = g + (size_t)n_steps * 4;
+        par[0] = clash_radius; par[1] = clash_k; par[2] = scale; par[3] = max_shift; par[4] = guide_below;
+        memcpy(par + 8, rstart.data(), rstart.size() * sizeof(int));
+        if (!rec.empty()) memcpy(par + 8 + B + 1, rec.data(), rec.size() * sizeof(cmdgen_restraint));
+    }
+    const hipStream_t caller = (hipStream_t)stream;
+    hipStream_t s; EvalLaunch a;
+    rc = begin_chain(h, CHAIN_RESTRAINED_EDIT, tables, n_steps, alloc_restrained_edit, pocket_ids_host, use_graph, caller, &s, &a); if (rc) return rc;
+    ChainSlot& k = h->chains[CHAIN_RESTRAINED_EDIT];
+    const Dims& d = h->dims;
+    ChainBuf c = h->redit_chain;
+    c.noise = noise; c.seed = seed; c.z_steps = z_steps_out; c.pocket_steps = pocket_steps_out;
+    const InpaintBuf ip = h->redit;
+    RestrainBuf rb = h->redit_restr;
+    rb.clash_r = clash_radius; rb.clash_k = clash_k; rb.scale = scale; rb.max_shift = max_shift; rb.guide_below = guide_below;
+    rb.op_energy = op_energy_out;
+    if (start == timesteps) {                        // from the prior: z_T around the pocket centre
+        cmdgen_launch_chain_init(h->lay, d, c, pocket_x, pocket_onehot, s);
+        cmdgen_launch_inpaint_prep(h->lay, d, c, ip, phar_x, phar_onehot, fix_x, fix_h, pocket_x, s);
+    } else {                                         // part-way: z ~ q(z_start | the given rows)
+        cmdgen_launch_edit_start(h->lay, d, c, ip, plan.alpha_start, plan.sigma_start, phar_x, phar_onehot, fix_x, fix_h, pocket_x,
+                                 pocket_onehot, s);
+    }
+    cmdgen_launch_restrain_prep(h->lay, d, rb, pocket_x, s);
+    build_pocket_cache(h, k, c, a, s);
+    EvalLaunch a2 = a;                               // the evaluations are cmdgen_edit_chain's: every one with its own k_readout
+    a2.skip_count = 1;                               // k_restrained_edit_step_count ran pass 1 of the graph
+    cmdgen_launch_eval(a, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, s, nullptr);   // evaluation 0 (t = start / timesteps)
+    const void* key[6] = {noise, z_steps_out, pocket_steps_out, op_energy_out, nullptr, s};
+    rc = run_steps(h, k, key, seed, n_steps, use_graph, s, [&](hipStream_t ss) {
+        cmdgen_launch_restrained_edit_step_count(h->lay, d, c, ip, rb, h->work, h->work.eps_tmp, ss);
+        cmdgen_launch_eval(a2, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, ss, nullptr);
+    });
+    if (rc) return rc;
+    ChainBuf cf = c;                                 // the decode draw is the plan's last row (cmdgen_edit_chain)
+    if (noise) cf.noise = noise + (size_t)(plan.n_draws - 1 - (1 + n_steps)) * h->lay.Nl * (3 + d.P);
+    cmdgen_launch_chain_final(h->lay, d, cf, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, k.cog, s);
+    cmdgen_launch_restrain_energy(h->lay, d, rb, xh_phar_out, xh_pocket_out, energy_out, s);
+    return end_chain(h, caller, s);
 }
 
 // ---------------------------------------------------------------------------------

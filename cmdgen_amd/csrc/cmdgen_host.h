@@ -24,7 +24,7 @@ struct DevBuf {
 // Host state of one kind of denoising chain (cmdgen_api.hip): its buffers for the current layout, the plan tables they were
 // prepared for, and its captured steps.  Each kind has a slot of its own, so plain and inpainting chains alternate on a
 // handle without re-preparing or re-capturing.
-enum ChainKind { CHAIN_PLAIN, CHAIN_JOINT, CHAIN_INPAINT, CHAIN_SCORE, CHAIN_MULTI, CHAIN_MULTI_EDIT, CHAIN_MULTI_SCORE, CHAIN_RESTRAINED, CHAIN_KINDS };
+enum ChainKind { CHAIN_PLAIN, CHAIN_JOINT, CHAIN_INPAINT, CHAIN_SCORE, CHAIN_MULTI, CHAIN_MULTI_EDIT, CHAIN_MULTI_SCORE, CHAIN_RESTRAINED, CHAIN_RESTRAINED_EDIT, CHAIN_KINDS };
 struct ChainSlot {
     std::vector<void*> allocs;
     std::vector<float> tables;             // the uploaded plan tables (coef | coef2 | iop bits), compared to decide a re-prepare
@@ -88,6 +88,9 @@ struct cmdgen_handle {
     GroupTab mscore_groups{};              // ... and its own group tables, behind the level rows of the slot's table block
     ChainBuf restr_chain{};                // restrained chain: the plain chain's buffers, ...
     RestrainBuf restr{};                   // ... and the guidance tables behind the posterior rows of the slot's table block (a changed restraint prepares the slot again)
+    ChainBuf redit_chain{};                // restrained edit chain: the edit chain's buffers, ...
+    InpaintBuf redit{};                    // ... its op tables, known rows and marks, ...
+    RestrainBuf redit_restr{};             // ... and the guidance tables behind the plan's tables in the slot's table block
     std::vector<float> user_coef;          // optional host-supplied step table
     int user_coef_K = -1;
     std::vector<float> user_guide;         // optional host-supplied guide table [K][2] (cmdgen_set_guide_table)

@@ -56,6 +56,8 @@ void cmdgen_launch_debug_noise(unsigned long long seed, long long pocket_id, int
 void cmdgen_launch_restrain_prep(const Layout& lay, const Dims& d, const RestrainBuf& rb, const float* px, hipStream_t s);
 void cmdgen_launch_restrained_step_count(const Layout& lay, const Dims& d, const ChainBuf& c, const RestrainBuf& rb, const Work& w,
                                          const float* eps, int own_vel /* readout_mode */, hipStream_t s);
+void cmdgen_launch_restrained_edit_step_count(const Layout& lay, const Dims& d, const ChainBuf& c, const InpaintBuf& ip, const RestrainBuf& rb,
+                                              const Work& w, const float* eps, hipStream_t s);   // the edit chain's op with the guidance in op A
 void cmdgen_launch_restrain_energy(const Layout& lay, const Dims& d, const RestrainBuf& rb, const float* xo, const float* po,
                                    float* energy_out, hipStream_t s);
 

@@ -287,6 +287,13 @@ inline size_t plan_restrained_step_lds(int max_n, int P) {
     return (size_t)max_n * (16 + sizeof(int) + (size_t)(3 + P) * sizeof(float) + 3 * sizeof(float) + 7 * sizeof(float));
 }
 
+// The restrained edit chain's step kernel (k_restrained_edit_step_count, kernels_restrain.hip) keeps k_inpaint_step_count's LDS (a float4 position and a
+// degree per node, z per row), then the denoised estimate, the displacement and the energy term of every row; eps comes from eps_tmp, so there is no
+// velocity array.  Bytes per workgroup, at most PLAN_RESTRAINED_LDS_MAX.
+inline size_t plan_restrained_edit_step_lds(int max_n, int P) {
+    return (size_t)max_n * (16 + sizeof(int) + (size_t)(3 + P) * sizeof(float) + 7 * sizeof(float));
+}
+
 // the launch keys of cmdgen_query (include/cmdgen_hip.h); false: not a launch key
 inline bool plan_query(const LaunchPlan& p, const char* key, int64_t* value) {
     const struct { const char* key; int64_t v; } keys[] = {

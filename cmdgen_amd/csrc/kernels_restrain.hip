@@ -41,6 +41,9 @@
 // its terms in ascending order, and a butterfly of __shfl_xor adds the lanes - a fixed order, the same on every run (it is not the index
 // order of step 3: the results agree with the CPU model within rounding, not bit for bit).  The pocket's centre of mass is summed the
 // same way.  No float atomics anywhere in the guidance.  IEEE sqrtf and division; built with -ffp-contract=off like kernels_ddpm.hip.
+//
+// The same guidance inside op A of the edit chain (ConditionalDDPM.edit_restrained, cmdgen_restrained_edit_chain): k_restrained_edit_step_count
+// below, whose header settles what a held row means to the terms.
 #include "cmdgen_sampler.h"
 
 namespace {
@@ -50,6 +53,15 @@ __device__ __forceinline__ float rdraw(const ChainBuf& c, const Layout& lay, int
     float z[4];
     philox_normal4(c.seed, (uint32_t)lay.pocket_gid[b], (uint32_t)(lay.pocket_gid[b] >> 32),
                    (uint32_t)draw_idx, (uint32_t)(local * 4 + (comp >> 2)), z);
+    return z[comp & 3];
+}
+
+// a draw of the edit chain's ops: row `row` of injected noise, or Philox with the counter `key` (idraw of kernels_inpaint.hip)
+__device__ __forceinline__ float edraw(const ChainBuf& c, const Layout& lay, int row, int key, int b, int local, int node, int comp, int ld) {
+    if (c.noise) return c.noise[((size_t)row * lay.Nl + node) * ld + comp];
+    float z[4];
+    philox_normal4(c.seed, (uint32_t)lay.pocket_gid[b], (uint32_t)(lay.pocket_gid[b] >> 32),
+                   (uint32_t)key, (uint32_t)(local * 4 + (comp >> 2)), z);
     return z[comp & 3];
 }
 
@@ -325,6 +337,189 @@ __global__ __launch_bounds__(256) void k_restrain_energy(Layout lay, Dims d, Res
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// k_restrained_edit_step_count: editing under restraints (ConditionalDDPM.edit_restrained, cmdgen_restrained_edit_chain).  The chain is
+// cmdgen_edit_chain's (kernels_inpaint.hip: the same init, op table, draws and Philox counters, B merge, C jump, saved steps and decode);
+// this kernel is k_inpaint_step_count with steps 1-5 of this file's header inside op A of every op t -> s, and three points settled:
+//   1. Denoised estimate.  A row whose x columns are NOT held (bit 1 of InpaintBuf::fix clear) has the restrained chain's xhat_i.  A row
+//      whose x columns ARE held has xhat_i = n_x K_i.x + shift: its given position moved into the current frame, exactly as a restraint
+//      centre is (shift is step 2's, from the pocket in LDS) - so a distance restraint between a free and a held point pulls toward the
+//      true held position, not toward a noisy estimate of it.
+//   2. Displacement.  d_i as in step 4 for rows whose x is not held.  A row whose x is held gets nothing added to its mean, not even a
+//      zero (B replaces it); its energy terms still count in E.  A row with only its types held is a free row here.
+//   3. Tables.  RestrainBuf::sa has one row per op of the edit plan (n_steps, following the plan's s with its repeats after jumps): the op
+//      that goes to level s takes row K - 1 - s of the K-row guide table.  Op C and the decode are never guided.
+// Reductions that hold bit for bit on every output, the chain status and the "chain_z" debug read:
+//   - no restraint on any sample and r_c = 0, or scale = 0: cmdgen_edit_chain's outputs for the same arguments (start < timesteps,
+//     resamplings > 1 and jump_length > 1 included);
+//   - no mark in either mask, start = timesteps, resamplings = jump_length = 1: cmdgen_restrained_chain's outputs on a handle whose
+//     evaluations use their own k_readout (readout_in_coord = 0), energy_out, op_energy_out, z_steps and pocket_steps included;
+//   - a sample that no restraint touches and an op above guide_below run k_inpaint_step_count's arithmetic;
+//   - two runs of the same inputs are equal bit for bit (no float atomics in the guidance).
+// LDS: k_inpaint_step_count's layout (positions, degrees, z), then xhat, d and e as in k_restrained_step_count.  eps comes from eps_tmp:
+// the evaluations are launched as cmdgen_edit_chain launches them (there is no own-velocity form).
+// ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void k_restrained_edit_step_count(Layout lay, Dims d, ChainBuf c, InpaintBuf ip, RestrainBuf rb, Work w,
+                                                                    const float* __restrict__ eps) {
+    extern __shared__ float4 s_pos[];               // [max_n] positions of the sample (phar first), then int sdeg[max_n], then z, xhat, d, e
+    int* sdeg = reinterpret_cast<int*>(s_pos + lay.max_n);
+    float* s_z = reinterpret_cast<float*>(sdeg + lay.max_n);      // [nl * ld]
+    float* s_xh = s_z + (size_t)lay.max_n * (3 + d.P);            // [nl][3] xhat, Angstrom
+    float* s_d = s_xh + (size_t)lay.max_n * 3;                    // [nl][3] displacement, Angstrom
+    float* s_e = s_d + (size_t)lay.max_n * 3;                     // [nl] the points' shares of E
+    __shared__ float s_mean[3], s_shift[3];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6, nt = blockDim.x;
+    const int nl = lay.num_phar[b], np = lay.num_pocket[b], n = nl + np;
+    const int pb = lay.phar_base[b], qb = lay.pocket_base[b];
+    const int ld = 3 + d.P, ldq = 3 + d.R;
+    const int step = c.state->step - 1;             // index of this op (k_readout has counted the evaluation)
+    const float4 cf = c.coef[step];
+    const float4 cf2 = ip.coef2[step];
+    const int4 io = ip.iop[step];
+    const float4 sa = rb.sa[step];
+    const float4 off0 = ip.poff[b];
+    const bool merge = off0.w > 0.f;
+    const bool nan_reset = *w.nan_flag != 0;
+    const int r0 = rb.rstart[b], r1 = rb.rstart[b + 1];
+    const bool touched = r1 > r0 || rb.clash_r > 0.f;
+    const bool guided = touched && rb.scale > 0.f && cf.w <= rb.guide_below;
+    const bool terms = touched && (guided || rb.op_energy != nullptr);
+    float* zg = c.z_phar + (size_t)pb * ld;
+    const float* eg = eps + (size_t)pb * ld;
+    const int cnt = nl * ld;
+    for (int idx = tid; idx < cnt; idx += nt) s_z[idx] = zg[idx];
+    for (int i = tid; i < np; i += nt) {
+        const float* q = c.xh_pocket + (size_t)(qb + i) * ldq;
+        s_pos[nl + i] = make_float4(q[0], q[1], q[2], 0.f);
+    }
+    __syncthreads();
+    if (wave == 0) record_com_check(c.check + 2 * (1 + step), s_z, ld, 0, nl, 1.0f, lane);   // z_t, the op's input
+    __syncthreads();
+    // ---- the guidance (steps 1-4): uniform over the workgroup
+    if (terms) {
+        if (wave == nwaves - 1) {                               // 2. shift
+            float c0, c1, c2;
+            wave_com(s_pos + nl, np, lane, c0, c1, c2);
+            const float4 pin = rb.pin_com[b];
+            if (lane == 0) { s_shift[0] = d.norm_x * (c0 - pin.x); s_shift[1] = d.norm_x * (c1 - pin.y); s_shift[2] = d.norm_x * (c2 - pin.z); }
+        }
+        __syncthreads();                                        // (held rows read the shift)
+        for (int idx = tid; idx < 3 * nl; idx += nt) {          // 1. xhat
+            const int i = idx / 3, k = idx - 3 * i;
+            if ((int)ip.fix[pb + i] & 1) {                      // x held (a marked row: only a sample that merges has one)
+                s_xh[idx] = d.norm_x * ip.known[(size_t)(pb + i) * ld + k] + s_shift[k];
+            } else {
+                float e = eg[i * ld + k];
+                if (nan_reset) e = 0.f;
+                s_xh[idx] = d.norm_x * (s_z[i * ld + k] - sa.x * e) / sa.y;
+            }
+        }
+        __syncthreads();
+        const float sx = s_shift[0], sy = s_shift[1], sz = s_shift[2];
+        const float sd = d.norm_x * cf.z, var = sd * sd;
+        for (int i = wave; i < nl; i += nwaves) {               // 3. / 4. a wave per point
+            const PointTerm t = point_terms(rb, r0, r1, i, np, s_xh, s_pos + nl, d.norm_x, sx, sy, sz, lane);
+            float dx = -rb.scale * var * t.gx, dy = -rb.scale * var * t.gy, dz = -rb.scale * var * t.gz;
+            const float len = sqrtf(dx * dx + dy * dy + dz * dz);
+            if (len > rb.max_shift) { const float f = rb.max_shift / len; dx *= f; dy *= f; dz *= f; }
+            if (lane == 0) { s_d[3 * i] = dx; s_d[3 * i + 1] = dy; s_d[3 * i + 2] = dz; s_e[i] = t.e; }
+        }
+        __syncthreads();
+    }
+    if (rb.op_energy && tid == 0) {
+        float e = 0.f;
+        if (terms) for (int i = 0; i < nl; ++i) e += s_e[i];    // index order
+        rb.op_energy[(size_t)step * lay.B + b] = e;
+    }
+    // A: the posterior step (k_step_count's expressions) with 5. the displacement on the rows whose x is not held
+    for (int idx = tid; idx < cnt; idx += nt) {
+        const int i = idx / ld, k = idx - i * ld;
+        float e = eg[idx];
+        if (nan_reset && k < 3) e = 0.f;
+        float mu = s_z[idx] / cf.x - cf.y * e;
+        if (guided && k < 3 && !((int)ip.fix[pb + i] & 1)) mu = mu + s_d[3 * i + k] / d.norm_x;
+        s_z[idx] = mu + cf.z * edraw(c, lay, io.y, 1 + step, b, i, pb + i, k, ld);
+    }
+    __syncthreads();
+    phar_mean(s_z, nl, ld, tid, s_mean);
+    __syncthreads();
+    float o0, o1, o2;                               // com(P) - com(P0) of the pocket in LDS
+    {
+        const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
+        sub_mean(s_z, s_pos, nl, n, ld, tid, nt, m0, m1, m2);
+        o0 = off0.x - m0; o1 = off0.y - m1; o2 = off0.z - m2;
+    }
+    __syncthreads();
+    // B: the noised known rows moved into the current frame replace the held column groups; then the phar COM projection
+    if (merge) {
+        const int keyB = 2 + ip.n_steps + step;
+        for (int idx = tid; idx < cnt; idx += nt) {
+            const int i = idx / ld, k = idx - i * ld;
+            if (!((int)ip.fix[pb + i] & (k < 3 ? 1 : 2))) continue;
+            float zk = cf2.x * ip.known[(size_t)pb * ld + idx] + cf2.y * edraw(c, lay, io.z, keyB, b, i, pb + i, k, ld);
+            if (k < 3) zk = zk + (k == 0 ? o0 : k == 1 ? o1 : o2);
+            s_z[idx] = zk;
+        }
+        __syncthreads();
+        phar_mean(s_z, nl, ld, tid, s_mean);
+        __syncthreads();
+        const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
+        sub_mean(s_z, s_pos, nl, n, ld, tid, nt, m0, m1, m2);
+        o0 -= m0; o1 -= m1; o2 -= m2;
+        __syncthreads();
+    }
+    // the state after the op (a frame): z and the pocket
+    if (c.z_steps)
+        for (int idx = tid; idx < cnt; idx += nt) c.z_steps[(size_t)step * lay.Nl * ld + (size_t)pb * ld + idx] = s_z[idx];
+    if (c.pocket_steps)
+        for (int i = tid; i < np; i += nt) {
+            const float4 p = s_pos[nl + i];
+            float* o = c.pocket_steps + ((size_t)step * lay.Np + qb + i) * 3;
+            o[0] = p.x; o[1] = p.y; o[2] = p.z;
+        }
+    // C: jump back, z_t' ~ q(z_t' | z_s) (never guided)
+    if (io.x & 1) {
+        const int keyC = 2 + 2 * ip.n_steps + step;
+        for (int idx = tid; idx < cnt; idx += nt) {
+            const int i = idx / ld, k = idx - i * ld;
+            const float mu = cf2.z * s_z[idx];
+            s_z[idx] = mu + cf2.w * edraw(c, lay, io.w, keyC, b, i, pb + i, k, ld);
+        }
+        __syncthreads();
+        phar_mean(s_z, nl, ld, tid, s_mean);
+        __syncthreads();
+        const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
+        sub_mean(s_z, s_pos, nl, n, ld, tid, nt, m0, m1, m2);
+        o0 -= m0; o1 -= m1; o2 -= m2;
+        __syncthreads();
+    }
+    // the new state, and the inputs of the next evaluation
+    for (int i = tid; i < n; i += nt) {
+        float4 p;
+        if (i < nl) {
+            const float* z = s_z + i * ld;
+            p = make_float4(z[0], z[1], z[2], 0.f);
+            w.X0[pb + i] = p;
+            for (int l = 0; l < d.L; ++l) w.ACC[(size_t)l * lay.Nm + pb + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            s_pos[i] = p;
+        } else {
+            p = s_pos[i];
+            float* q = c.xh_pocket + (size_t)(qb + i - nl) * ldq;
+            q[0] = p.x; q[1] = p.y; q[2] = p.z;
+            w.XP[qb + i - nl] = p;
+        }
+    }
+    for (int idx = tid; idx < cnt; idx += nt) zg[idx] = s_z[idx];
+    if (tid == 0) ip.poff[b] = make_float4(o0, o1, o2, off0.w);
+    __syncthreads();
+    count_next_graph(lay, d, w, s_pos, sdeg, b, nl, n, pb, qb);
+    if (b == 0 && tid == 0) {
+        if (nan_reset) atomicAdd(&w.counters[4], 1ull);
+        atomicAdd(&w.counters[0], 1ull);                       // evaluations (the one about to run)
+        atomicAdd(&w.counters[3], (unsigned long long)lay.N);  // nodes
+    }
+}
+
 void cmdgen_launch_restrain_prep(const Layout& lay, const Dims& d, const RestrainBuf& rb, const float* px, hipStream_t s) {
     hipLaunchKernelGGL(k_restrain_prep, dim3(lay.B), dim3(64), 0, s, lay, d, rb, px);
 }
@@ -334,6 +529,11 @@ void cmdgen_launch_restrained_step_count(const Layout& lay, const Dims& d, const
     const dim3 block(lay.max_n > 128 ? 1024 : 256);             // as k_step_count
     if (own_vel) hipLaunchKernelGGL(k_restrained_step_count<true>, dim3(lay.B), block, shm, s, lay, d, c, rb, w, eps);
     else hipLaunchKernelGGL(k_restrained_step_count<false>, dim3(lay.B), block, shm, s, lay, d, c, rb, w, eps);
+}
+void cmdgen_launch_restrained_edit_step_count(const Layout& lay, const Dims& d, const ChainBuf& c, const InpaintBuf& ip, const RestrainBuf& rb,
+                                              const Work& w, const float* eps, hipStream_t s) {
+    const size_t shm = plan_restrained_edit_step_lds(lay.max_n, d.P);
+    hipLaunchKernelGGL(k_restrained_edit_step_count, dim3(lay.B), dim3(lay.max_n > 128 ? 1024 : 256), shm, s, lay, d, c, ip, rb, w, eps);
 }
 void cmdgen_launch_restrain_energy(const Layout& lay, const Dims& d, const RestrainBuf& rb, const float* xo, const float* po,
                                    float* energy_out, hipStream_t s) {

@@ -458,6 +458,71 @@ class ConditionalDDPM(EnVariationalDiffusion):
         return out[0], out[1], phar_mask, pocket['mask']
 
     @torch.no_grad()
+    def edit_restrained(self, phar, pocket, restraints, fix_coords=None, fix_types=None, start=None, resamplings=1, jump_length=1,
+                        clash=None, scale=1.0, max_shift=None, guide_below=1.0, timesteps=None, noise=None, seed=None, pocket_ids=None):
+        """``edit`` STEERED by ``sample_restrained``'s geometric query: keep some given points and grow or re-place the others under
+        position, distance, exclusion and clash terms.  The chain is ``edit``'s (the same start, ops, draws, Philox counters, merge, jumps
+        and decode) with the guidance term of ``sample_restrained`` in the posterior op (op A) of every op; the jump-back op and the decode
+        are not guided (cmdgen_restrained_edit_chain; the header of k_restrained_edit_step_count in csrc/kernels_restrain.hip defines it).
+        A point whose coordinates are held enters the restraint energy at its GIVEN position (moved into the chain's frame) and is not
+        displaced, so a distance window between a held and a free point pulls the free one toward the true held position; a point with
+        only its type held is steered like a free one.
+
+        phar, pocket, fix_coords, fix_types, start, resamplings, jump_length, timesteps, noise, seed, pocket_ids as ``edit``; restraints
+        (list of dicts, centres in the frame of pocket['x']), clash, scale, max_shift, guide_below as ``sample_restrained``.  With no
+        restraint and no clash term, or scale = 0, the result is ``edit``'s bit for bit.
+        Returns (xh_phar, xh_pocket, phar_mask, pocket_mask, {'energy': [B], 'max_violation': [B]}): the energy and the largest violation
+        (A) of the returned sample, held points included at their returned positions."""
+        from .. import restraints as rs
+        timesteps = self.T if timesteps is None else int(timesteps)
+        start = timesteps if start is None else start
+        if int(start) != start or not 1 <= int(start) <= timesteps:
+            raise ValueError(f'start={start} must be an integer level in [1, timesteps={timesteps}]')
+        start = int(start)
+        device = pocket['x'].device
+        n_samples = len(pocket['size'])
+        sizes = pocket['size'].detach().to('cpu', torch.int64).numpy()
+        nph = phar['size'].detach().to('cpu', torch.int64).numpy()
+        if len(nph) != n_samples:
+            raise ValueError(f'phar has {len(nph)} samples, pocket {n_samples}')
+        for m in (phar['mask'], pocket['mask']):
+            if m.numel() > 1 and bool((m[1:] < m[:-1]).any()):
+                raise ValueError('batch masks must be ascending and contiguous')
+        n_phar = int(nph.sum())
+        fix_x = self._row_mask(fix_coords, 'fix_coords', n_phar, device)
+        fix_h = self._row_mask(fix_types, 'fix_types', n_phar, device)
+        rec = rs.records(restraints, nph)
+        clash_r, clash_k = rs.clash_pair(clash)
+        scale, max_shift, guide_below = rs.check_scalars(scale, rs.DEFAULT_MAX_SHIFT if max_shift is None else max_shift, guide_below)
+        self.refresh_learned_schedule()
+        h = self.dynamics.hip_handle()
+        h.set_layout(nph, sizes)
+        h.set_step_table(timesteps, self.step_table(timesteps))
+        h.set_guide_table(timesteps, self.guide_table(timesteps))
+        n_steps, n_draws = h.edit_plan(timesteps, start, resamplings, jump_length)
+        f32 = lambda t: t.detach().to(device, torch.float32).contiguous()
+        if noise is not None:
+            noise = f32(noise)
+            if noise.dim() != 3 or noise.shape[0] < n_draws:
+                raise ValueError(f'noise has shape {tuple(noise.shape)}: this schedule needs {n_draws} draws of [{n_phar}, {3 + self.phar_nf}]')
+        if seed is None:
+            seed = fresh_seed()
+        phar_mask = utils.num_nodes_to_batch_mask(n_samples, torch.as_tensor(nph), device)
+        args = (f32(pocket['x']), f32(pocket['one_hot']), f32(phar['x']), f32(phar['one_hot']), fix_x, fix_h)
+        extra = {}
+
+        def run():
+            out = h.restrained_edit_chain(*args, timesteps, start=start, resamplings=resamplings, jump_length=jump_length, restraints=rec,
+                                          clash_radius=clash_r, clash_k=clash_k, scale=scale, max_shift=max_shift, guide_below=guide_below,
+                                          noise=noise, seed=seed, pocket_ids=pocket_ids, use_graph=self.use_hip_graph)
+            extra['energy'] = out[3]
+            return out[:3]
+
+        out = self._finish_chain(h, run, [], 1)
+        info = {'energy': extra['energy'][:, 0].clone(), 'max_violation': extra['energy'][:, 1].clone()}
+        return out[0], out[1], phar_mask, pocket['mask'], info
+
+    @torch.no_grad()
     def edit_given_pockets(self, phar, pockets, fix_coords=None, fix_types=None, start=None, resamplings=1, jump_length=1,
                            weights=None, timesteps=None, noise=None, seed=None, group_ids=None):
         """Hold or edit GIVEN points while drawing one pharmacophore per group of pockets: ``edit``'s ops on the shared latent of
@@ -735,6 +800,10 @@ class SimpleConditionalDDPM(ConditionalDDPM):
     def sample_restrained(self, *args, **kwargs):
         raise NotImplementedError('sample_restrained is not implemented for SimpleConditionalDDPM (no centre-of-mass projection: the '
                                   'guidance frame follows the projections); use ConditionalDDPM')
+
+    def edit_restrained(self, *args, **kwargs):
+        raise NotImplementedError('edit_restrained is not implemented for SimpleConditionalDDPM (no centre-of-mass projection: the '
+                                  'edit chain and the guidance frame follow the projections); use ConditionalDDPM')
 
     def edit_given_pockets(self, *args, **kwargs):
         raise NotImplementedError('edit_given_pockets is not implemented for SimpleConditionalDDPM (no centre-of-mass projection: the '

@@ -78,6 +78,9 @@ SYMBOLS = [
                                            _fp, _fp, _fp, C.c_int32, _vp]),
     ('cmdgen_restrained_chain', C.c_int, [_vp, _fp, _fp, C.c_int32, _vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                           _fp, C.c_uint64, _i64p, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int32, _vp]),
+    ('cmdgen_restrained_edit_chain', C.c_int, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int64,
+                                               C.c_uint64, _i64p, _fp, _fp, _fp, _fp, _vp, C.c_int64, C.c_float, C.c_float, C.c_float,
+                                               C.c_float, C.c_float, _fp, _fp, C.c_int32, _vp]),
     ('cmdgen_set_guide_table', C.c_int, [_vp, C.c_int32, _vp]),
     ('cmdgen_param_count', C.c_int, [_vp, _i64p]),
     ('cmdgen_param_offset', C.c_int, [_vp, C.c_char_p, _i64p, _i64p]),
@@ -541,6 +544,44 @@ class Handle:
             C.c_uint64(seed & (2 ** 64 - 1)), self._pocket_ids(pocket_ids), _ptr(xh_phar),
             _ptr(xh_pocket), _ptr(z_steps), _ptr(p_steps), int(bool(use_graph)), self._stream()), 'cmdgen_edit_chain')
         return xh_phar, xh_pocket, z_steps
+
+    def restrained_edit_chain(self, pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h, timesteps: int, start: Optional[int] = None,
+                              resamplings: int = 1, jump_length: int = 1, restraints=None, clash_radius: float = 0.0, clash_k: float = 0.0,
+                              scale: float = 1.0, max_shift: float = DEFAULT_MAX_SHIFT, guide_below: float = 1.0, noise=None, seed: int = 0,
+                              pocket_ids: Optional[Sequence[int]] = None, want_steps: bool = False, use_graph: bool = True):
+        """cmdgen_restrained_edit_chain: edit_chain with restrained_chain's guidance term in op A of every op (the header of
+        k_restrained_edit_step_count in kernels_restrain.hip defines it): a held point enters the restraint energy at its given position
+        and is not displaced.  The arguments are edit_chain's, then restrained_chain's.
+        -> (xh_phar, xh_pocket, z_steps, energy [B, 2] (E and the largest violation in A of the output), op_energy [n_steps, B] or None);
+        with want_steps the pocket after every op is left in last_pocket_steps."""
+        import torch
+        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
+        start = timesteps if start is None else start
+        shapes = [(self.n_pocket, 3), (self.n_pocket, R), (self.n_phar, 3), (self.n_phar, P), (self.n_phar,), (self.n_phar,)]
+        for t, sh in zip((pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h), shapes):
+            self._check_dev(t, sh)
+        n_steps, n_draws = self.edit_plan(timesteps, start, resamplings, jump_length)
+        if noise is not None:
+            self._check_dev(noise)
+            assert noise.dim() == 3 and tuple(noise.shape[1:]) == (self.n_phar, 3 + P), noise.shape
+        rec = np.zeros(0, dtype=RESTRAINT_DTYPE) if restraints is None else np.ascontiguousarray(restraints, dtype=RESTRAINT_DTYPE)
+        assert rec.ndim == 1
+        dev = pocket_x.device
+        xh_phar = torch.empty((self.n_phar, 3 + P), dtype=torch.float32, device=dev)
+        xh_pocket = torch.empty((self.n_pocket, 3 + R), dtype=torch.float32, device=dev)
+        z_steps = torch.empty((n_steps, self.n_phar, 3 + P), dtype=torch.float32, device=dev) if want_steps else None
+        p_steps = torch.empty((n_steps, self.n_pocket, 3), dtype=torch.float32, device=dev) if want_steps else None
+        energy = torch.empty((self.batch, 2), dtype=torch.float32, device=dev)
+        op_energy = torch.empty((n_steps, self.batch), dtype=torch.float32, device=dev) if want_steps else None
+        self.last_pocket_steps = p_steps
+        self._check(self.lib.cmdgen_restrained_edit_chain(
+            self.h, _ptr(pocket_x), _ptr(pocket_onehot), _ptr(phar_x), _ptr(phar_onehot), _ptr(fix_x), _ptr(fix_h), int(timesteps),
+            int(start), int(resamplings), int(jump_length), _ptr(noise), int(noise.shape[0]) if noise is not None else 0,
+            C.c_uint64(seed & (2 ** 64 - 1)), self._pocket_ids(pocket_ids), _ptr(xh_phar), _ptr(xh_pocket), _ptr(z_steps), _ptr(p_steps),
+            rec.ctypes.data_as(C.c_void_p) if len(rec) else None, len(rec), float(clash_radius), float(clash_k), float(scale),
+            float(max_shift), float(guide_below), _ptr(energy), _ptr(op_energy), int(bool(use_graph)), self._stream()),
+            'cmdgen_restrained_edit_chain')
+        return xh_phar, xh_pocket, z_steps, energy, op_energy
 
     def multi_edit_chain(self, pocket_x, pocket_onehot, group_sizes: Sequence[int], weights, phar_x, phar_onehot, fix_x, fix_h,
                          timesteps: int, start: Optional[int] = None, resamplings: int = 1, jump_length: int = 1, noise=None,

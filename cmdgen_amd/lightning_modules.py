@@ -516,6 +516,51 @@ class PharPocketDDPM(nn.Module):
         xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
         return self._point_lists(xh_phar, phar)
 
+    @torch.no_grad()
+    def edit_phars_restrained(self, pdb_file, n_samples, phars, restraints, keep='both', strength=None, clash=None, num_nodes_phar=None,
+                              pocket_ids=None, ref_ligand=None, scale=1.0, max_shift=None, guide_below=1.0, timesteps=None,
+                              resamplings=1, jump_length=1, seed=None):
+        """edit_phars STEERED by a geometric query (ConditionalDDPM.edit_restrained): "keep these three points of the known
+        pharmacophore and grow two more, 5 to 7 A from point 0, inside this sub-pocket, off the pocket atoms".
+
+        phars, keep, strength, num_nodes_phar, resamplings, jump_length as edit_phars (keep defaults to 'both': the given points
+        stay); restraints, clash, scale, max_shift, guide_below as generate_phars_restrained: the dicts of cmdgen_amd/restraints.py
+        WITHOUT 'sample', given once in the PDB's frame, and every one of the n_samples copies gets the list.  A point index names a
+        row of every sample: rows 0 .. len(phars) - 1 are the given points, the rows behind them the free ones.  A given point whose
+        coordinates are kept enters the query at its given position and is not moved by it.
+        -> (one point list per sample in the PDB's frame, {'energy': [n_samples], 'max_violation': [n_samples]} of the returned
+        samples, to filter on)."""
+        from . import restraints as rs
+        assert (pocket_ids is None) ^ (ref_ligand is None)
+        if not isinstance(self.ddpm, ConditionalDDPM):
+            raise NotImplementedError('edit_phars_restrained needs the conditional model (mode pocket_conditioning)')
+        restraints = list(restraints)
+        for n, r in enumerate(restraints):
+            if isinstance(r, dict) and 'sample' in r:
+                raise ValueError(f"restraints[{n}] = {r!r}: restraints are given once, without 'sample', and applied to every sample")
+        named = [int(v) for r in restraints if isinstance(r, dict)
+                 for v in ([r['point']] if 'point' in r else list(r.get('points', ()))) if isinstance(v, (int, np.integer))]
+        keeps, start = self._edit_keeps_and_start(phars, keep, strength, timesteps)
+        pocket = self._pdb_pocket(pdb_file, n_samples, pocket_ids, ref_ligand)
+        pocket_com_before = _scatter_mean(pocket['x'], pocket['mask'], n_samples)
+        T = self.ddpm.T if timesteps is None else int(timesteps)
+        if num_nodes_phar is None and not (start is not None and start < T):
+            # from the prior: the size prior given the pocket, at least the given points and the rows the restraints name
+            num_nodes_phar = self.ddpm.size_distribution.sample_conditional(n1=None, n2=pocket['size'])
+            num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device).clamp(min=max(len(phars), max(named, default=0) + 1))
+        phar, fix_x, fix_h = self._edit_phar_and_masks(phars, keeps, start, strength, timesteps, n_samples, num_nodes_phar, pocket)
+        nph = phar['size'].cpu().numpy()
+        for b in range(n_samples):
+            rs.records(restraints, nph, sample=b)                       # (names the entry of the caller's list)
+        per_sample = [dict(r, sample=b) for b in range(n_samples) for r in restraints]
+        xh_phar, xh_pocket, phar_mask, pocket_mask, info = self.ddpm.edit_restrained(
+            phar, pocket, per_sample, fix_coords=fix_x, fix_types=fix_h, start=start, resamplings=resamplings, jump_length=jump_length,
+            clash=clash, scale=scale, max_shift=max_shift, guide_below=guide_below, timesteps=timesteps, seed=seed)
+        # move the points back to the original pocket position (as generate_phars)
+        pocket_com_after = _scatter_mean(xh_pocket[:, :self.x_dims], pocket_mask, n_samples)
+        xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
+        return self._point_lists(xh_phar, phar), info
+
     def _edit_keeps_and_start(self, phars, keep, strength, timesteps):
         """edit_phars' argument rules: -> (what every given point holds, the start level or None for the prior)."""
         n_given = len(phars)

@@ -504,6 +504,41 @@ int cmdgen_restrained_chain(cmdgen_handle* h, const float* pocket_x, const float
                             float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
                             float* energy_out, float* op_energy_out, int32_t use_graph, cmdgen_stream stream);
 
+/* Editing under restraints (ConditionalDDPM.edit_restrained): cmdgen_edit_chain's chain - the same init (from the prior, or z ~ q(z_start | K)
+ * when start < timesteps), op table, draws and Philox counters, B merge, C jump, saved steps and decode - with cmdgen_restrained_chain's
+ * guidance in the mean of op A of every op t -> s.  The definition is the project's own; kernels_restrain.hip (k_restrained_edit_step_count)
+ * carries it in full.  The terms, the shift, g_i, d_i and mu are cmdgen_restrained_chain's, with three points settled:
+ *   xhat_i  of a row whose x columns are not held is the restrained chain's; of a row whose x columns ARE held it is n_x K_i.x + shift, its
+ *           given position moved into the current frame as a restraint centre is (K the normalised given rows) - a distance restraint
+ *           between a free and a held point pulls toward the true held position
+ *   d_i     is added to the mean of rows whose x is not held; a row whose x is held gets nothing added, not even a zero (B replaces it),
+ *           while its energy terms still count in E.  A row with only its types held is a free row here
+ *   sigma_t, alpha_t  one row per op of the edit plan (n_steps, following the plan's s with its repeats after jumps): the op that goes to
+ *           level s takes row K - 1 - s of the guide table (cmdgen_set_guide_table with K = timesteps, or the library's own evaluation).
+ *           Op C and the decode are never guided
+ * Reductions that hold bit for bit on every output, cmdgen_chain_status and cmdgen_debug_read("chain_z"):
+ *   - no restraint on any sample and clash_radius = 0, or scale = 0: cmdgen_edit_chain's outputs for the same arguments (start < timesteps,
+ *     resamplings > 1 and jump_length > 1 included)
+ *   - no mark in either mask, start = timesteps, resamplings = jump_length = 1: cmdgen_restrained_chain's outputs on a handle whose
+ *     evaluations use their own k_readout (option readout_in_coord = 0), energy_out, op_energy_out, z_steps and pocket_steps included
+ *     (noise rows in cmdgen_edit_chain's order)
+ *   - a sample that no restraint touches and an op above guide_below run cmdgen_edit_chain's arithmetic
+ *   - two runs of the same inputs are equal bit for bit (no float atomics)
+ *   energy_out     dev [batch][2]: E and the largest violation (Angstrom) of the RETURNED rows, held points included at their returned positions
+ *   op_energy_out  dev [n_steps][batch] E at xhat of every op (n_steps of cmdgen_edit_plan), or NULL
+ *   the other arguments as cmdgen_edit_chain, then as cmdgen_restrained_chain; cmdgen_edit_plan gives n_steps and n_draws
+ * The chain has a slot of its own; the plan's tables, the guide rows, the five scalars and the restraint table are the slot's tables, so a
+ * changed plan, start, restraint or scalar prepares the slot (and its graph) again.
+ * Refused: whatever cmdgen_edit_chain or cmdgen_restrained_chain refuses, with the same codes. */
+int cmdgen_restrained_edit_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
+                                 const float* phar_x, const float* phar_onehot, const float* fix_x, const float* fix_h,
+                                 int32_t timesteps, int32_t start, int32_t resamplings, int32_t jump_length,
+                                 const float* noise, int64_t n_draws, uint64_t seed, const int64_t* pocket_ids_host,
+                                 float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                                 const cmdgen_restraint* restraints_host, int64_t n_restraints,
+                                 float clash_radius, float clash_k, float scale, float max_shift, float guide_below,
+                                 float* energy_out, float* op_energy_out, int32_t use_graph, cmdgen_stream stream);
+
 /* ---- training step (conditional model) -------------------------------------------------- */
 /* The trainable tensors of EGNNDynamics live in ONE flat fp32 device buffer owned by the caller, in the
  * reference's registration order (the state_dict order below 'ddpm.dynamics.': weight then bias of every
