@@ -644,12 +644,10 @@ extern "C" int cmdgen_debug_read(cmdgen_handle* h, const char* what, float* host
     else if (k == "xl") { src = h->work.XL; have = (size_t)d.L * h->lay.Nm * 4; }
     else if (k == "acc") { src = h->work.ACC; have = (size_t)d.L * h->lay.Nm * 4; }
     else if (k == "chain_z") {                       // the last conditional chain's z buffer (the multi-pocket chains: every member's copy)
-        const ChainBuf* cb = h->last_chain == CHAIN_PLAIN ? &h->chain : h->last_chain == CHAIN_INPAINT ? &h->inp_chain :
-                             h->last_chain == CHAIN_MULTI ? &h->multi_chain : h->last_chain == CHAIN_MULTI_EDIT ? &h->medit_chain :
-                             h->last_chain == CHAIN_MULTI_SCORE ? &h->mscore_chain :               // (the last level's z of the multi-pocket scoring chain)
-                             h->last_chain == CHAIN_RESTRAINED ? &h->restr_chain : h->last_chain == CHAIN_RESTRAINED_EDIT ? &h->redit_chain : nullptr;
-        if (!cb || !cb->z_phar || h->chains[h->last_chain].n_steps < 0) return fail(h, CMDGEN_ESTATE, "no conditional chain has run on this layout");
-        src = cb->z_phar; have = (size_t)h->lay.Nl * (3 + d.P);
+        const ChainSlot& k = h->chains[h->last_chain];   // (the multi-pocket scoring chain: the last level's z; the scoring chain is not served)
+        if (h->last_chain == CHAIN_JOINT || h->last_chain == CHAIN_SCORE || !k.buf.z_phar || k.n_steps < 0)
+            return fail(h, CMDGEN_ESTATE, "no conditional chain has run on this layout");
+        src = k.buf.z_phar; have = (size_t)h->lay.Nl * (3 + d.P);
     }
     else return fail(h, CMDGEN_EINVAL, "unknown debug buffer '%s'", k.c_str());
     if (n > have) n = have;
@@ -704,8 +702,28 @@ static std::vector<float> step_table(const cmdgen_handle* h, int K) {
 }
 
 // ---------------------------------------------------------------------------------
-// the denoising chains: what cmdgen_sample_chain, cmdgen_joint_chain and cmdgen_inpaint_chain share
+// the chains: what the entries of all nine kinds share.  A kind's state lives in its slot (h->chains[kind]); its ChainAlloc composes
+// the parts it uses (alloc_chain_buf, alloc_inpaint_part, point_group_tab, alloc_restrain_part, alloc_score_part); its entry reads top to
+// bottom: checks, tables, Chain::open, its init launches, Chain::start, Chain::steps with its step launch, its final launches, Chain::close.
 // ---------------------------------------------------------------------------------
+static int check_timesteps(cmdgen_handle* h, int K) {
+    if (K < 1 || K > h->cfg.timesteps) return fail(h, CMDGEN_EINVAL, "timesteps=%d must be in [1, %d]", K, h->cfg.timesteps);
+    return 0;
+}
+// the conditional chains that neither the joint model nor a no_com_projection handle runs, each with its reason
+static const char* const kPocketDiffuses = "its pocket nodes diffuse with the latent";
+static const char* const kOwnPocketTerms = "its loss has the pocket's own terms";
+static int refuse_joint_no_com(cmdgen_handle* h, const char* what, const char* joint_why, const char* no_com_why = "", int no_com_code = CMDGEN_ESTATE) {
+    if (h->dims.joint) return fail(h, CMDGEN_ESTATE, "%s is not supported for the joint model (update_pocket_coords=1): %s", what, joint_why);
+    if (h->dims.no_com) return fail(h, no_com_code, "%s is not supported for no_com_projection handles (SimpleConditionalDDPM)%s", what, no_com_why);
+    return 0;
+}
+// injected noise covers the schedule (draws: what the chain calls its rows)
+static int check_draws(cmdgen_handle* h, const float* noise, int64_t n_draws, int need, const char* draws = "draws") {
+    if (noise && n_draws < need) return fail(h, CMDGEN_EINVAL, "noise holds %lld %s, the schedule needs %lld", (long long)n_draws, draws, (long long)need);
+    return 0;
+}
+
 // a plan's tables as one upload: coef | coef2 | iop bits
 static std::vector<float> plan_tables(const std::vector<float>& coef, const std::vector<float>& coef2, const std::vector<int>& iop) {
     std::vector<float> t(coef);
@@ -852,17 +870,87 @@ static int end_chain(cmdgen_handle* h, hipStream_t caller, hipStream_t s) {
     return CMDGEN_OK;
 }
 
+// The parts a kind's ChainAlloc composes; each fills its member of the slot.  slot_alloc: `count` zeroed T in the slot's pool
+template <class T>
+static int slot_alloc(cmdgen_handle* h, ChainSlot& k, T*& dst, size_t count) {
+    void* p; const int rc = dev_alloc(h, k.allocs, &p, count * sizeof(T), true);
+    if (!rc) dst = (T*)p;
+    return rc;
+}
 // a conditional chain's z and pocket (ChainBuf) and its pocket cache; coef: its posterior rows
-static int alloc_chain_buf(cmdgen_handle* h, ChainSlot& k, ChainBuf& c, const float* coef) {
-    const Dims& d = h->dims;
-    void* p; int rc;
+static int alloc_chain_buf(cmdgen_handle* h, ChainSlot& k, const float* coef) {
+    ChainBuf& c = k.buf;
     c.coef = (const float4*)coef; c.check = k.check; c.state = k.state;
-    rc = dev_alloc(h, k.allocs, &p, (size_t)h->lay.Nl * (3 + d.P) * sizeof(float), true); if (rc) return rc; c.z_phar = (float*)p;
-    rc = dev_alloc(h, k.allocs, &p, (size_t)h->lay.Np * (3 + d.R) * sizeof(float), true); if (rc) return rc; c.xh_pocket = (float*)p;
+    int rc = slot_alloc(h, k, c.z_phar, (size_t)h->lay.Nl * (3 + h->dims.P)); if (rc) return rc;
+    rc = slot_alloc(h, k, c.xh_pocket, (size_t)h->lay.Np * (3 + h->dims.R)); if (rc) return rc;
     return alloc_pocket_cache(h, k);
 }
+// the edit kinds' InpaintBuf: coef2 | iop (n_steps rows each) at `coef2` in the table block, the known rows and marks, the offset per sample
+static int alloc_inpaint_part(cmdgen_handle* h, ChainSlot& k, const float* coef2, int n_steps) {
+    InpaintBuf& ip = k.inp;
+    ip.coef2 = (const float4*)coef2;
+    ip.iop = (const int4*)(coef2 + (size_t)n_steps * 4);
+    ip.n_steps = n_steps;
+    int rc = slot_alloc(h, k, ip.known, (size_t)h->lay.Nl * (3 + h->dims.P)); if (rc) return rc;    // (Nl bounds the unique rows of any grouping)
+    rc = slot_alloc(h, k, ip.fix, (size_t)h->lay.Nl); if (rc) return rc;
+    return slot_alloc(h, k, ip.poff, (size_t)h->lay.B);
+}
+// the restrained kinds' RestrainBuf: the guidance tail append_guidance packed at `guide` in the table block (n_rows guide rows), and com(P_in)
+static int alloc_restrain_part(cmdgen_handle* h, ChainSlot& k, const float* guide, int n_rows) {
+    RestrainBuf& rb = k.restr;
+    const float* par = guide + (size_t)n_rows * 4;
+    rb.sa = (const float4*)guide;
+    rb.clash_r = par[0]; rb.clash_k = par[1]; rb.scale = par[2]; rb.max_shift = par[3]; rb.guide_below = par[4];
+    rb.rstart = (const int*)(par + 8);
+    rb.rec = (const RestraintRec*)(par + 8 + (size_t)h->lay.B + 1);
+    rb.op_energy = nullptr;
+    return slot_alloc(h, k, rb.pin_com, (size_t)h->lay.B);
+}
+// the scoring kinds' ScoreBuf: the clean rows the levels noise
+static int alloc_score_part(cmdgen_handle* h, ChainSlot& k) {
+    const int rc = slot_alloc(h, k, k.score.xh0, (size_t)h->lay.Nl * (3 + h->dims.P)); if (rc) return rc;
+    return slot_alloc(h, k, k.score.pocket0, (size_t)h->lay.Np * 3);
+}
 
-static int alloc_plain(cmdgen_handle* h, ChainSlot& k, const float* tables, int) { return alloc_chain_buf(h, k, h->chain, tables); }
+// One chain call between begin_chain and end_chain: the stream it runs on, its slot, the launch description of its evaluations and, for
+// the eight conditional kinds, the slot's ChainBuf completed with the call's pointers.
+struct Chain {
+    cmdgen_handle* h = nullptr;
+    ChainSlot* k = nullptr;
+    hipStream_t caller = nullptr, s = nullptr;
+    bool use_graph = false;
+    EvalLaunch a, a2;                // evaluation 0 | the evaluations behind a step kernel, which ran pass 1 of the radius graph
+    ChainBuf c{};
+
+    int open(cmdgen_handle* h_, ChainKind kind, std::vector<float>& tables, int n_steps, ChainAlloc alloc, const int64_t* ids_host,
+             const float* noise, unsigned long long seed, float* z_steps, float* pocket_steps, bool graph, cmdgen_stream stream) {
+        h = h_; k = &h->chains[kind]; caller = (hipStream_t)stream; use_graph = graph;
+        const int rc = begin_chain(h, kind, tables, n_steps, alloc, ids_host, use_graph, caller, &s, &a); if (rc) return rc;
+        c = k->buf;
+        c.noise = noise; c.seed = seed; c.z_steps = z_steps; c.pocket_steps = pocket_steps;
+        return 0;
+    }
+    void eval(const EvalLaunch& e, hipStream_t ss) const {
+        cmdgen_launch_eval(e, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, ss, nullptr);
+    }
+    // behind the kind's init launches: the pocket cache, then evaluation 0 (t of the chain's first row) - a scoring chain has none
+    void start(bool eval0) {
+        build_pocket_cache(h, *k, c, a, s);
+        a2 = a;
+        a2.skip_count = 1;                           // (pass 2 of the graph on a side stream was measured and dropped: the fork / join costs ~23 us per
+                                                     // step inside the replayed graph, far more than the 10 us it hides; profiles/r02_b_step_fusion.txt)
+        if (eval0) eval(a, s);
+    }
+    // n x (the kind's step launch, the evaluation at the new state); ptrs: the caller's pointers the captured steps bake in
+    template <class Step>
+    int steps(const void* const (&ptrs)[5], int n, Step step) {
+        const void* key[6] = {ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4], s};
+        return run_steps(h, *k, key, c.seed, n, use_graph, s, [&](hipStream_t ss) { step(ss); eval(a2, ss); });
+    }
+    int close() { return end_chain(h, caller, s); }
+};
+
+static int alloc_plain(cmdgen_handle* h, ChainSlot& k, const float* tables, int) { return alloc_chain_buf(h, k, tables); }
 
 extern "C" int cmdgen_sample_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
                                    int32_t timesteps, const float* noise, uint64_t seed,
@@ -871,43 +959,34 @@ extern "C" int cmdgen_sample_chain(cmdgen_handle* h, const float* pocket_x, cons
     int rc = check_ready(h); if (rc) return rc;
     if (!pocket_x || !pocket_onehot || !xh_phar_out || !xh_pocket_out) return fail(h, CMDGEN_EINVAL, "null device pointer");
     const int K = timesteps;
-    if (K < 1 || K > h->cfg.timesteps) return fail(h, CMDGEN_EINVAL, "timesteps=%d must be in [1, %d]", K, h->cfg.timesteps);
+    rc = check_timesteps(h, K); if (rc) return rc;
     if (h->dims.joint) return fail(h, CMDGEN_ESTATE, "this handle is the joint model (update_pocket_coords=1): use cmdgen_joint_chain");
     std::vector<float> tables = step_table(h, K);
-    const hipStream_t caller = (hipStream_t)stream;
-    hipStream_t s; EvalLaunch a;
-    rc = begin_chain(h, CHAIN_PLAIN, tables, K, alloc_plain, pocket_ids_host, use_graph, caller, &s, &a); if (rc) return rc;
-    ChainSlot& k = h->chains[CHAIN_PLAIN];
+    Chain ch;
+    rc = ch.open(h, CHAIN_PLAIN, tables, K, alloc_plain, pocket_ids_host, noise, seed, z_steps_out, pocket_steps_out, use_graph, stream); if (rc) return rc;
     const Dims& d = h->dims;
-    ChainBuf c = h->chain;
-    c.noise = noise; c.seed = seed; c.z_steps = z_steps_out; c.pocket_steps = pocket_steps_out;
-    cmdgen_launch_chain_init(h->lay, d, c, pocket_x, pocket_onehot, s);
-    build_pocket_cache(h, k, c, a, s);
+    const ChainBuf& c = ch.c;
+    cmdgen_launch_chain_init(h->lay, d, c, pocket_x, pocket_onehot, ch.s);
     // One denoising step = the posterior update fused with pass 1 of the next radius graph (k_step_count), then the
     // evaluation at the new state: pass 2 of the graph (k_edge_write), k_embed, the L blocks,
     // k_readout.  The chain is: evaluation 0, K x (step + evaluation), decode.
     // Where the plan says so (LaunchPlan::readout_in_coord) the evaluations run without k_readout: its feature part rides in the last coordinate
     // launch, k_step_count forms the velocity and the NaN flag it consumes itself, and k_vel_flag does so once in front of the decode.
-    a.plain_chain = 1;
-    const int own_vel = readout_mode(a, c.state, nullptr, nullptr, nullptr);     // (what the evaluations below are launched with)
-    EvalLaunch a2 = a;
-    a2.skip_count = 1;                               // (pass 2 of the graph on a side stream was measured and dropped: the fork / join costs ~23 us per
-                                                     // step inside the replayed graph, far more than the 10 us it hides; profiles/r02_b_step_fusion.txt)
-    cmdgen_launch_eval(a, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, s, nullptr);   // evaluation 0 (t = 1)
+    ch.a.plain_chain = 1;
+    const int own_vel = readout_mode(ch.a, c.state, nullptr, nullptr, nullptr);  // (what the evaluations below are launched with)
+    ch.start(true);                                  // evaluation 0 (t = 1)
     // (a step kernel that leaves X0 / ACC to an evaluation that does not take them over would leave stale positions without any error)
     // (evaluation 0 is already queued when this returns: the chain is abandoned half issued, the handle stays usable - the next chain of any
     // kind starts again from k_chain_init and k_edge_count, which rewrite everything this one left behind)
-    if (a.readout_used != own_vel) return fail(h, CMDGEN_ESTATE, "the evaluation and the step kernel disagree on readout_in_coord (%d, %d)", a.readout_used, own_vel);
-    const void* key[6] = {noise, z_steps_out, pocket_steps_out, nullptr, nullptr, s};
-    rc = run_steps(h, k, key, seed, K, use_graph, s, [&](hipStream_t ss) {
+    if (ch.a.readout_used != own_vel) return fail(h, CMDGEN_ESTATE, "the evaluation and the step kernel disagree on readout_in_coord (%d, %d)", ch.a.readout_used, own_vel);
+    rc = ch.steps({noise, z_steps_out, pocket_steps_out, nullptr, nullptr}, K, [&](hipStream_t ss) {
         cmdgen_launch_step_count(h->lay, d, c, h->work, h->work.eps_tmp, own_vel, ss);
-        cmdgen_launch_eval(a2, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, ss, nullptr);
     });
     if (rc) return rc;
     // final p(x, h | z0): the last evaluation above ran at t = 0 (coef[K].w); decode
-    if (own_vel) cmdgen_launch_vel_flag(a, h->work.eps_tmp, s);
-    cmdgen_launch_chain_final(h->lay, d, c, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, k.cog, s);
-    return end_chain(h, caller, s);
+    if (own_vel) cmdgen_launch_vel_flag(ch.a, h->work.eps_tmp, ch.s);
+    cmdgen_launch_chain_final(h->lay, d, c, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, ch.k->cog, ch.s);
+    return ch.close();
 }
 
 // ---------------------------------------------------------------------------------
@@ -989,21 +1068,30 @@ static int check_restraints(cmdgen_handle* h, const cmdgen_restraint* restraints
     return 0;
 }
 
+// The guidance tail of a table block: one guide row (sigma_t, alpha_t, 0, 0) per op, s_of[i] the level op i goes to (t = s + 1), then `spare`
+// unused rows | par: r_c, k_c, scale, max_shift, guide_below, then 0, 0, 0 | rstart | rec.  alloc_restrain_part points a RestrainBuf at it.
+static void append_guidance(const cmdgen_handle* h, std::vector<float>& tables, int K, const std::vector<int>& s_of, int spare, const float (&par5)[5],
+                            const std::vector<int>& rstart, const std::vector<cmdgen_restraint>& rec) {
+    std::vector<float> sa;                           // [K][2], row K - 1 - s for the op that goes to level s
+    if (h->user_guide_K == K) sa = h->user_guide; else build_guide_table(h->gamma, h->cfg.timesteps, K, sa);
+    const size_t c0 = tables.size(), n_rows = s_of.size() + (size_t)spare;
+    tables.resize(c0 + n_rows * 4 + 8 + rstart.size() + rec.size() * 10, 0.f);
+    float* g = tables.data() + c0;
+    for (size_t i = 0; i < s_of.size(); ++i) {
+        const size_t row = (size_t)(K - 1 - s_of[i]);
+        g[4 * i] = sa[2 * row]; g[4 * i + 1] = sa[2 * row + 1];
+    }
+    float* par = g + n_rows * 4;
+    memcpy(par, par5, sizeof par5);
+    float* const csr = par + 8;
+    memcpy(csr, rstart.data(), rstart.size() * sizeof(int));
+    if (!rec.empty()) memcpy(csr + rstart.size(), rec.data(), rec.size() * sizeof(cmdgen_restraint));
+}
+
+// the slot's table block: the posterior rows | the guidance tail, both n_steps + 1 rows
 static int alloc_restrained(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
-    int rc = alloc_chain_buf(h, k, h->restr_chain, tables); if (rc) return rc;
-    const size_t B = (size_t)h->lay.B;
-    RestrainBuf& rb = h->restr;
-    const float* sa = tables + (size_t)(n_steps + 1) * 4;
-    const float* par = sa + (size_t)(n_steps + 1) * 4;
-    rb.sa = (const float4*)sa;
-    rb.clash_r = par[0]; rb.clash_k = par[1]; rb.scale = par[2]; rb.max_shift = par[3]; rb.guide_below = par[4];
-    rb.rstart = (const int*)(par + 8);
-    rb.rec = (const RestraintRec*)(par + 8 + B + 1);
-    void* p;
-    rc = dev_alloc(h, k.allocs, &p, B * sizeof(float4), true); if (rc) return rc;
-    rb.pin_com = (float4*)p;
-    rb.op_energy = nullptr;
-    return 0;
+    const int rc = alloc_chain_buf(h, k, tables); if (rc) return rc;
+    return alloc_restrain_part(h, k, tables + (size_t)(n_steps + 1) * 4, n_steps + 1);
 }
 
 extern "C" int cmdgen_restrained_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot, int32_t timesteps,
@@ -1015,56 +1103,38 @@ extern "C" int cmdgen_restrained_chain(cmdgen_handle* h, const float* pocket_x, 
     int rc = check_ready(h); if (rc) return rc;
     if (!pocket_x || !pocket_onehot || !xh_phar_out || !xh_pocket_out || !energy_out) return fail(h, CMDGEN_EINVAL, "null device pointer");
     const int K = timesteps;
-    if (K < 1 || K > h->cfg.timesteps) return fail(h, CMDGEN_EINVAL, "timesteps=%d must be in [1, %d]", K, h->cfg.timesteps);
-    if (h->dims.joint) return fail(h, CMDGEN_ESTATE, "the restrained chain is not supported for the joint model (update_pocket_coords=1): its pocket nodes diffuse with the latent");
-    if (h->dims.no_com) return fail(h, CMDGEN_EINVAL, "the restrained chain is not supported for no_com_projection handles (SimpleConditionalDDPM): the guidance frame follows the centre-of-mass projections");
+    rc = check_timesteps(h, K); if (rc) return rc;
+    rc = refuse_joint_no_com(h, "the restrained chain", kPocketDiffuses, ": the guidance frame follows the centre-of-mass projections", CMDGEN_EINVAL);
+    if (rc) return rc;
     std::vector<int> rstart; std::vector<cmdgen_restraint> rec;
     rc = check_restraints(h, restraints_host, n_restraints, clash_radius, clash_k, scale, max_shift, guide_below,
                           plan_restrained_step_lds(h->lay.max_n, h->dims.P), rstart, rec);
     if (rc) return rc;
-    const int B = h->lay.B;
     std::vector<float> tables = step_table(h, K);
-    {
-        std::vector<float> sa;
-        if (h->user_guide_K == K) sa = h->user_guide; else build_guide_table(h->gamma, h->cfg.timesteps, K, sa);
-        const size_t c0 = tables.size();
-        tables.resize(c0 + (size_t)(K + 1) * 4 + 8 + (size_t)B + 1 + rec.size() * 10, 0.f);
-        float* g = tables.data() + c0;
-        for (int i = 0; i < K; ++i) { g[4 * i] = sa[2 * i]; g[4 * i + 1] = sa[2 * i + 1]; }
-        float* par = g + (size_t)(K + 1) * 4;
-        par[0] = clash_radius; par[1] = clash_k; par[2] = scale; par[3] = max_shift; par[4] = guide_below;
-        memcpy(par + 8, rstart.data(), rstart.size() * sizeof(int));
-        if (!rec.empty()) memcpy(par + 8 + B + 1, rec.data(), rec.size() * sizeof(cmdgen_restraint));
-    }
-    const hipStream_t caller = (hipStream_t)stream;
-    hipStream_t s; EvalLaunch a;
-    rc = begin_chain(h, CHAIN_RESTRAINED, tables, K, alloc_restrained, pocket_ids_host, use_graph, caller, &s, &a); if (rc) return rc;
-    ChainSlot& k = h->chains[CHAIN_RESTRAINED];
+    std::vector<int> s_of((size_t)K);
+    for (int i = 0; i < K; ++i) s_of[(size_t)i] = K - 1 - i;
+    append_guidance(h, tables, K, s_of, 1, {clash_radius, clash_k, scale, max_shift, guide_below}, rstart, rec);
+    Chain ch;
+    rc = ch.open(h, CHAIN_RESTRAINED, tables, K, alloc_restrained, pocket_ids_host, noise, seed, z_steps_out, pocket_steps_out, use_graph, stream); if (rc) return rc;
     const Dims& d = h->dims;
-    ChainBuf c = h->restr_chain;
-    c.noise = noise; c.seed = seed; c.z_steps = z_steps_out; c.pocket_steps = pocket_steps_out;
-    RestrainBuf rb = h->restr;
+    const ChainBuf& c = ch.c;
+    RestrainBuf rb = ch.k->restr;
     rb.op_energy = op_energy_out;
-    cmdgen_launch_chain_init(h->lay, d, c, pocket_x, pocket_onehot, s);
-    cmdgen_launch_restrain_prep(h->lay, d, rb, pocket_x, s);
-    build_pocket_cache(h, k, c, a, s);
+    cmdgen_launch_chain_init(h->lay, d, c, pocket_x, pocket_onehot, ch.s);
+    cmdgen_launch_restrain_prep(h->lay, d, rb, pocket_x, ch.s);
     // the evaluations are the plain chain's, with or without k_readout (cmdgen_sample_chain: readout_mode); the step kernel has both forms
-    a.plain_chain = 1;
-    const int own_vel = readout_mode(a, c.state, nullptr, nullptr, nullptr);
-    EvalLaunch a2 = a;
-    a2.skip_count = 1;
-    cmdgen_launch_eval(a, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, s, nullptr);   // evaluation 0 (t = 1)
-    if (a.readout_used != own_vel) return fail(h, CMDGEN_ESTATE, "the evaluation and the step kernel disagree on readout_in_coord (%d, %d)", a.readout_used, own_vel);
-    const void* key[6] = {noise, z_steps_out, pocket_steps_out, op_energy_out, nullptr, s};
-    rc = run_steps(h, k, key, seed, K, use_graph, s, [&](hipStream_t ss) {
+    ch.a.plain_chain = 1;
+    const int own_vel = readout_mode(ch.a, c.state, nullptr, nullptr, nullptr);
+    ch.start(true);                                  // evaluation 0 (t = 1)
+    if (ch.a.readout_used != own_vel) return fail(h, CMDGEN_ESTATE, "the evaluation and the step kernel disagree on readout_in_coord (%d, %d)", ch.a.readout_used, own_vel);
+    rc = ch.steps({noise, z_steps_out, pocket_steps_out, op_energy_out, nullptr}, K, [&](hipStream_t ss) {
         cmdgen_launch_restrained_step_count(h->lay, d, c, rb, h->work, h->work.eps_tmp, own_vel, ss);
-        cmdgen_launch_eval(a2, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, ss, nullptr);
     });
     if (rc) return rc;
-    if (own_vel) cmdgen_launch_vel_flag(a, h->work.eps_tmp, s);
-    cmdgen_launch_chain_final(h->lay, d, c, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, k.cog, s);
-    cmdgen_launch_restrain_energy(h->lay, d, rb, xh_phar_out, xh_pocket_out, energy_out, s);
-    return end_chain(h, caller, s);
+    if (own_vel) cmdgen_launch_vel_flag(ch.a, h->work.eps_tmp, ch.s);
+    cmdgen_launch_chain_final(h->lay, d, c, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, ch.k->cog, ch.s);
+    cmdgen_launch_restrain_energy(h->lay, d, rb, xh_phar_out, xh_pocket_out, energy_out, ch.s);
+    return ch.close();
 }
 
 // ---------------------------------------------------------------------------------
@@ -1129,11 +1199,13 @@ static void point_group_tab(GroupTab& gt, const float* g, size_t B) {
     gt.first = (const int*)g; gt.size = (const int*)(g + B); gt.ubase = (const int*)(g + 2 * B);
     gt.weight = g + 3 * B; gt.group_first = (const int*)(g + 4 * B);
 }
+// the slot's group tables with the call's counts
+static GroupTab group_tab(const ChainSlot& k, const GroupPlan& p) { GroupTab gt = k.groups; gt.G = p.G; gt.Nu = (int)p.Nu; return gt; }
 
 // the multi-pocket chain's ChainBuf and, behind the posterior rows (n_steps + 1) of the slot's table block, the group tables
 static int alloc_multi(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
-    int rc = alloc_chain_buf(h, k, h->multi_chain, tables); if (rc) return rc;
-    point_group_tab(h->groups, tables + (size_t)(n_steps + 1) * 4, (size_t)h->lay.B);
+    const int rc = alloc_chain_buf(h, k, tables); if (rc) return rc;
+    point_group_tab(k.groups, tables + (size_t)(n_steps + 1) * 4, (size_t)h->lay.B);
     return 0;
 }
 
@@ -1143,41 +1215,30 @@ extern "C" int cmdgen_multi_pocket_chain(cmdgen_handle* h, const float* pocket_x
                                          float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
                                          int32_t use_graph, cmdgen_stream stream) {
     int rc = check_ready(h); if (rc) return rc;
-    if (h->dims.joint) return fail(h, CMDGEN_ESTATE, "the multi-pocket chain is not supported for the joint model (update_pocket_coords=1): its pocket nodes diffuse with the latent");
-    if (h->dims.no_com) return fail(h, CMDGEN_ESTATE, "the multi-pocket chain is not supported for no_com_projection handles (SimpleConditionalDDPM)");
+    rc = refuse_joint_no_com(h, "the multi-pocket chain", kPocketDiffuses); if (rc) return rc;
     if (!pocket_x || !pocket_onehot || !group_size_host || !weight_host || !xh_phar_out || !xh_pocket_out)
         return fail(h, CMDGEN_EINVAL, "null pointer");
     const int K = timesteps;
-    if (K < 1 || K > h->cfg.timesteps) return fail(h, CMDGEN_EINVAL, "timesteps=%d must be in [1, %d]", K, h->cfg.timesteps);
-    const int B = h->lay.B;
+    rc = check_timesteps(h, K); if (rc) return rc;
     GroupPlan gp;
     rc = build_group_plan(h, n_groups, group_size_host, weight_host, group_ids_host, gp); if (rc) return rc;
     std::vector<float> tables = step_table(h, K);
-    append_group_tables(tables, gp, weight_host, B);
-    const hipStream_t caller = (hipStream_t)stream;
-    hipStream_t s; EvalLaunch a;
-    rc = begin_chain(h, CHAIN_MULTI, tables, K, alloc_multi, gp.gid.data(), use_graph, caller, &s, &a); if (rc) return rc;
-    ChainSlot& k = h->chains[CHAIN_MULTI];
+    append_group_tables(tables, gp, weight_host, h->lay.B);
+    Chain ch;
+    rc = ch.open(h, CHAIN_MULTI, tables, K, alloc_multi, gp.gid.data(), noise, seed, z_steps_out, pocket_steps_out, use_graph, stream); if (rc) return rc;
     const Dims& d = h->dims;
-    ChainBuf c = h->multi_chain;
-    c.noise = noise; c.seed = seed; c.z_steps = z_steps_out; c.pocket_steps = pocket_steps_out;
-    GroupTab gt = h->groups;
-    gt.G = gp.G; gt.Nu = (int)gp.Nu;
-    cmdgen_launch_multi_init(h->lay, d, c, gt, pocket_x, pocket_onehot, s);
-    build_pocket_cache(h, k, c, a, s);
-    EvalLaunch a2 = a;
-    a2.skip_count = 1;                               // k_multi_step_count ran pass 1 of the graph
-    cmdgen_launch_eval(a, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, s, nullptr);   // evaluation 0 (t = 1)
+    const ChainBuf& c = ch.c;
+    const GroupTab gt = group_tab(*ch.k, gp);
+    cmdgen_launch_multi_init(h->lay, d, c, gt, pocket_x, pocket_onehot, ch.s);
+    ch.start(true);                                  // evaluation 0 (t = 1)
     // the group tables are slot buffers (a changed grouping or weight prepares the slot again and drops its graph); the group ids are
     // uploaded per call, like the pocket ids of the other chains
-    const void* key[6] = {noise, z_steps_out, pocket_steps_out, nullptr, nullptr, s};
-    rc = run_steps(h, k, key, seed, K, use_graph, s, [&](hipStream_t ss) {
+    rc = ch.steps({noise, z_steps_out, pocket_steps_out, nullptr, nullptr}, K, [&](hipStream_t ss) {
         cmdgen_launch_multi_step_count(h->lay, d, c, gt, h->work, h->work.eps_tmp, ss);
-        cmdgen_launch_eval(a2, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, ss, nullptr);
     });
     if (rc) return rc;
-    cmdgen_launch_multi_final(h->lay, d, c, gt, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, k.cog, s);
-    return end_chain(h, caller, s);
+    cmdgen_launch_multi_final(h->lay, d, c, gt, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, ch.k->cog, ch.s);
+    return ch.close();
 }
 
 // ---------------------------------------------------------------------------------
@@ -1253,7 +1314,7 @@ static JointPlan build_joint_plan(const std::vector<float>& gamma, int T, int K,
 
 static int check_joint_args(cmdgen_handle* h, int K, int resamplings, int jump) {
     if (!h->dims.joint) return fail(h, CMDGEN_ESTATE, "joint chains need a handle created with update_pocket_coords=1");
-    if (K < 1 || K > h->cfg.timesteps) return fail(h, CMDGEN_EINVAL, "timesteps=%d must be in [1, %d]", K, h->cfg.timesteps);
+    const int rc = check_timesteps(h, K); if (rc) return rc;
     if (resamplings < 1 || jump < 1) return fail(h, CMDGEN_EINVAL, "resamplings and jump_length must be >= 1");
     return 0;
 }
@@ -1271,22 +1332,19 @@ extern "C" int cmdgen_joint_plan(cmdgen_handle* h, int32_t timesteps, int32_t re
 
 // JointBuf: the plan's rows (coef, coef2, iop: n_steps + 1 each), the state, and the scratch of the combined draws
 static int alloc_joint(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
-    const Dims& d = h->dims;
-    JointBuf& c = h->joint;
+    JointBuf& c = k.joint;
     c.coef = (const float4*)tables;
     c.coef2 = (const float4*)(tables + (size_t)(n_steps + 1) * 4);
     c.iop = (const int4*)(tables + (size_t)(n_steps + 1) * 8);
     c.check = k.check; c.state = k.state;
-    const size_t np_ = (size_t)h->lay.Nl * (3 + d.P) * sizeof(float), nq_ = (size_t)h->lay.Np * (3 + d.R) * sizeof(float);
-    void* q; int rc;
-#define JALLOC(dst, bytes) do { rc = dev_alloc(h, k.allocs, &q, bytes, true); if (rc) return rc; dst = (float*)q; } while (0)
-    JALLOC(c.z_phar, np_); JALLOC(c.z_pocket, nq_);
-    JALLOC(c.e_phar, np_); JALLOC(c.e_pocket, nq_);
-    JALLOC(c.zk_phar, np_); JALLOC(c.zk_pocket, nq_);
-    JALLOC(c.x0_phar, np_); JALLOC(c.x0_pocket, nq_);
-    JALLOC(h->eps_pocket_tmp, nq_);
-#undef JALLOC
-    return 0;
+    const size_t np_ = (size_t)h->lay.Nl * (3 + h->dims.P), nq_ = (size_t)h->lay.Np * (3 + h->dims.R);
+    float** const phar[] = {&c.z_phar, &c.e_phar, &c.zk_phar, &c.x0_phar};
+    float** const pocket[] = {&c.z_pocket, &c.e_pocket, &c.zk_pocket, &c.x0_pocket};
+    for (int i = 0; i < 4; ++i) {
+        int rc = slot_alloc(h, k, *phar[i], np_); if (rc) return rc;
+        rc = slot_alloc(h, k, *pocket[i], nq_); if (rc) return rc;
+    }
+    return slot_alloc(h, k, k.eps_pocket, nq_);
 }
 
 extern "C" int cmdgen_joint_chain(cmdgen_handle* h, const float* phar_x, const float* phar_onehot,
@@ -1303,28 +1361,27 @@ extern "C" int cmdgen_joint_chain(cmdgen_handle* h, const float* phar_x, const f
     if (inpaint && (!phar_fixed || !pocket_fixed || !phar_x || !phar_onehot || !pocket_x || !pocket_onehot))
         return fail(h, CMDGEN_EINVAL, "inpainting needs phar_x, phar_onehot, pocket_x, pocket_onehot and both fixed masks");
     const JointPlan plan = build_joint_plan(h->gamma, h->cfg.timesteps, timesteps, resamplings, jump_length, inpaint);
-    if (noise && n_draws < plan.n_draws)
-        return fail(h, CMDGEN_EINVAL, "noise holds %lld combined draws, the schedule needs %lld", (long long)n_draws, (long long)plan.n_draws);
+    rc = check_draws(h, noise, n_draws, plan.n_draws, "combined draws"); if (rc) return rc;
     const int n_steps = plan.n_steps;
     std::vector<float> tables = plan_tables(plan.coef, plan.coef2, plan.iop);
-    const hipStream_t caller = (hipStream_t)stream;
-    hipStream_t s; EvalLaunch a;
-    rc = begin_chain(h, CHAIN_JOINT, tables, n_steps, alloc_joint, pocket_ids_host, use_graph, caller, &s, &a); if (rc) return rc;
-    ChainSlot& k = h->chains[CHAIN_JOINT];
+    Chain ch;                                        // (open and close only: the joint chain has no ChainBuf and evaluates BEFORE its step)
+    rc = ch.open(h, CHAIN_JOINT, tables, n_steps, alloc_joint, pocket_ids_host, noise, seed, z_steps_out, nullptr, use_graph, stream); if (rc) return rc;
     const Dims& d = h->dims;
-    JointBuf c = h->joint;
-    c.fix_phar = phar_fixed; c.fix_pocket = pocket_fixed;
-    c.noise = noise; c.seed = seed; c.z_steps = z_steps_out;
+    const hipStream_t s = ch.s;
+    float* const eps_pocket = ch.k->eps_pocket;
+    JointBuf c = ch.k->joint;
+    c.fix_phar = phar_fixed; c.fix_pocket = pocket_fixed; c.z_steps = z_steps_out;
+    c.seed = seed; c.noise = noise;
     cmdgen_launch_joint_init(h->lay, d, c, phar_x, phar_onehot, pocket_x, pocket_onehot, s);
     const void* key[6] = {noise, z_steps_out, nullptr, phar_fixed, pocket_fixed, s};
-    rc = run_steps(h, k, key, seed, n_steps, use_graph, s, [&](hipStream_t ss) {
-        cmdgen_launch_eval(a, c.z_phar, c.z_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, h->eps_pocket_tmp, ss, nullptr);
-        cmdgen_launch_joint_step(h->lay, d, c, h->work.eps_tmp, h->eps_pocket_tmp, ss);
+    rc = run_steps(h, *ch.k, key, seed, n_steps, use_graph, s, [&](hipStream_t ss) {
+        cmdgen_launch_eval(ch.a, c.z_phar, c.z_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, eps_pocket, ss, nullptr);
+        cmdgen_launch_joint_step(h->lay, d, c, h->work.eps_tmp, eps_pocket, ss);
     });
     if (rc) return rc;
-    cmdgen_launch_eval(a, c.z_phar, c.z_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, h->eps_pocket_tmp, s, nullptr);
-    cmdgen_launch_joint_final(h->lay, d, c, h->work.eps_tmp, h->eps_pocket_tmp, xh_phar_out, xh_pocket_out, k.cog, s);
-    return end_chain(h, caller, s);
+    cmdgen_launch_eval(ch.a, c.z_phar, c.z_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, eps_pocket, s, nullptr);
+    cmdgen_launch_joint_final(h->lay, d, c, h->work.eps_tmp, eps_pocket, xh_phar_out, xh_pocket_out, ch.k->cog, s);
+    return ch.close();
 }
 
 // ---------------------------------------------------------------------------------
@@ -1380,7 +1437,7 @@ static InpaintPlan build_inpaint_plan(const cmdgen_handle* h, int K, int start, 
 static int check_inpaint_args(cmdgen_handle* h, int K, int start, int resamplings, int jump) {
     if (h->dims.joint) return fail(h, CMDGEN_ESTATE, "this handle is the joint model (update_pocket_coords=1): use cmdgen_joint_chain");
     if (h->dims.no_com) return fail(h, CMDGEN_ESTATE, "inpainting is not supported for no_com_projection handles (SimpleConditionalDDPM)");
-    if (K < 1 || K > h->cfg.timesteps) return fail(h, CMDGEN_EINVAL, "timesteps=%d must be in [1, %d]", K, h->cfg.timesteps);
+    const int rc = check_timesteps(h, K); if (rc) return rc;
     if (start < 1 || start > K) return fail(h, CMDGEN_EINVAL, "start=%d must be in [1, timesteps=%d]", start, K);
     if (resamplings < 1 || jump < 1) return fail(h, CMDGEN_EINVAL, "resamplings and jump_length must be >= 1");
     return 0;
@@ -1404,20 +1461,27 @@ extern "C" int cmdgen_inpaint_plan(cmdgen_handle* h, int32_t timesteps, int32_t 
 
 // the inpainting chain's ChainBuf (posterior rows: coef, n_steps + 1) and InpaintBuf (coef2, iop: n_steps each; the known part)
 static int alloc_inpaint(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
-    int rc = alloc_chain_buf(h, k, h->inp_chain, tables); if (rc) return rc;
-    const Dims& d = h->dims;
-    const Layout& L = h->lay;
-    InpaintBuf& ip = h->inp;
-    ip.coef2 = (const float4*)(tables + (size_t)(n_steps + 1) * 4);
-    ip.iop = (const int4*)(tables + (size_t)(2 * n_steps + 1) * 4);
-    ip.n_steps = n_steps;
-    void* q;
-#define IALLOC(dst, type, bytes) do { rc = dev_alloc(h, k.allocs, &q, bytes, true); if (rc) return rc; dst = (type)q; } while (0)
-    IALLOC(ip.known, const float*, (size_t)L.Nl * (3 + d.P) * sizeof(float));
-    IALLOC(ip.fix, float*, (size_t)L.Nl * sizeof(float));
-    IALLOC(ip.poff, float4*, (size_t)L.B * sizeof(float4));
-#undef IALLOC
-    return 0;
+    const int rc = alloc_chain_buf(h, k, tables); if (rc) return rc;
+    return alloc_inpaint_part(h, k, tables + (size_t)(n_steps + 1) * 4, n_steps);
+}
+
+// the init launches of cmdgen_edit_chain and cmdgen_restrained_edit_chain
+static void launch_edit_init(const Chain& ch, const InpaintBuf& ip, const InpaintPlan& plan, bool from_prior, const float* pocket_x, const float* pocket_onehot,
+                             const float* phar_x, const float* phar_onehot, const float* fix_x, const float* fix_h) {
+    const cmdgen_handle* h = ch.h;
+    if (from_prior) {                                // z_T around the pocket centre
+        cmdgen_launch_chain_init(h->lay, h->dims, ch.c, pocket_x, pocket_onehot, ch.s);
+        cmdgen_launch_inpaint_prep(h->lay, h->dims, ch.c, ip, phar_x, phar_onehot, fix_x, fix_h, pocket_x, ch.s);
+    } else {                                         // part-way: z ~ q(z_start | the given rows)
+        cmdgen_launch_edit_start(h->lay, h->dims, ch.c, ip, plan.alpha_start, plan.sigma_start, phar_x, phar_onehot, fix_x, fix_h, pocket_x,
+                                 pocket_onehot, ch.s);
+    }
+}
+// the decode draw of an edit plan is its last row; the final kernels read theirs from row 1 + n_steps of `noise` (rows: phar rows per draw)
+static ChainBuf decode_buf(const ChainBuf& c, const InpaintPlan& plan, size_t rows, int P) {
+    ChainBuf cf = c;
+    if (c.noise) cf.noise = c.noise + (size_t)(plan.n_draws - 1 - (1 + plan.n_steps)) * rows * (3 + P);
+    return cf;
 }
 
 extern "C" int cmdgen_edit_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
@@ -1431,42 +1495,23 @@ extern "C" int cmdgen_edit_chain(cmdgen_handle* h, const float* pocket_x, const 
     if (!pocket_x || !pocket_onehot || !phar_x || !phar_onehot || !fix_x || !fix_h || !xh_phar_out || !xh_pocket_out)
         return fail(h, CMDGEN_EINVAL, "null device pointer");
     const InpaintPlan plan = build_inpaint_plan(h, timesteps, start, resamplings, jump_length);
-    if (noise && n_draws < plan.n_draws)
-        return fail(h, CMDGEN_EINVAL, "noise holds %lld draws, the schedule needs %lld", (long long)n_draws, (long long)plan.n_draws);
-    const int n_steps = plan.n_steps;
+    rc = check_draws(h, noise, n_draws, plan.n_draws); if (rc) return rc;
     std::vector<float> tables = plan_tables(plan.coef, plan.coef2, plan.iop);
-    const hipStream_t caller = (hipStream_t)stream;
-    hipStream_t s; EvalLaunch a;
-    rc = begin_chain(h, CHAIN_INPAINT, tables, n_steps, alloc_inpaint, pocket_ids_host, use_graph, caller, &s, &a); if (rc) return rc;
-    ChainSlot& k = h->chains[CHAIN_INPAINT];
+    Chain ch;
+    rc = ch.open(h, CHAIN_INPAINT, tables, plan.n_steps, alloc_inpaint, pocket_ids_host, noise, seed, z_steps_out, pocket_steps_out, use_graph, stream); if (rc) return rc;
     const Dims& d = h->dims;
-    ChainBuf c = h->inp_chain;
-    c.noise = noise; c.seed = seed; c.z_steps = z_steps_out; c.pocket_steps = pocket_steps_out;
-    const InpaintBuf ip = h->inp;
-    if (start == timesteps) {                        // from the prior: z_T around the pocket centre
-        cmdgen_launch_chain_init(h->lay, d, c, pocket_x, pocket_onehot, s);
-        cmdgen_launch_inpaint_prep(h->lay, d, c, ip, phar_x, phar_onehot, fix_x, fix_h, pocket_x, s);
-    } else {                                         // part-way: z ~ q(z_start | the given rows)
-        cmdgen_launch_edit_start(h->lay, d, c, ip, plan.alpha_start, plan.sigma_start, phar_x, phar_onehot, fix_x, fix_h, pocket_x,
-                                 pocket_onehot, s);
-    }
-    build_pocket_cache(h, k, c, a, s);
-    EvalLaunch a2 = a;
-    a2.skip_count = 1;                               // k_inpaint_step_count ran pass 1 of the graph
-    cmdgen_launch_eval(a, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, s, nullptr);   // evaluation 0 (t = start / timesteps)
+    const ChainBuf& c = ch.c;
+    const InpaintBuf ip = ch.k->inp;
+    launch_edit_init(ch, ip, plan, start == timesteps, pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h);
+    ch.start(true);                                  // evaluation 0 (t = start / timesteps)
     // the tables (their rows differ with start and with the plan), the known rows and the masks are slot buffers: a new plan or start
     // prepares the slot again; the caller's pointers are the key
-    const void* key[6] = {noise, z_steps_out, pocket_steps_out, nullptr, nullptr, s};
-    rc = run_steps(h, k, key, seed, n_steps, use_graph, s, [&](hipStream_t ss) {
+    rc = ch.steps({noise, z_steps_out, pocket_steps_out, nullptr, nullptr}, plan.n_steps, [&](hipStream_t ss) {
         cmdgen_launch_inpaint_step_count(h->lay, d, c, ip, h->work, h->work.eps_tmp, ss);
-        cmdgen_launch_eval(a2, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, ss, nullptr);
     });
     if (rc) return rc;
-    // decode: k_chain_final reads its draw from row 1 + K of `noise` (K = n_steps here); the decode draw is the plan's last row
-    ChainBuf cf = c;
-    if (noise) cf.noise = noise + (size_t)(plan.n_draws - 1 - (1 + n_steps)) * h->lay.Nl * (3 + d.P);
-    cmdgen_launch_chain_final(h->lay, d, cf, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, k.cog, s);
-    return end_chain(h, caller, s);
+    cmdgen_launch_chain_final(h->lay, d, decode_buf(c, plan, (size_t)h->lay.Nl, d.P), h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, ch.k->cog, ch.s);
+    return ch.close();
 }
 
 extern "C" int cmdgen_inpaint_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
@@ -1487,27 +1532,9 @@ extern "C" int cmdgen_inpaint_chain(cmdgen_handle* h, const float* pocket_x, con
 // sample - so a changed plan, start, restraint or scalar prepares the slot again and drops its captured steps.
 // ---------------------------------------------------------------------------------
 static int alloc_restrained_edit(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
-    int rc = alloc_chain_buf(h, k, h->redit_chain, tables); if (rc) return rc;
-    const Dims& d = h->dims;
-    const Layout& L = h->lay;
-    InpaintBuf& ip = h->redit;
-    ip.coef2 = (const float4*)(tables + (size_t)(n_steps + 1) * 4);
-    ip.iop = (const int4*)(tables + (size_t)(2 * n_steps + 1) * 4);
-    ip.n_steps = n_steps;
-    RestrainBuf& rb = h->redit_restr;                // (the five scalars are set by the call from its arguments)
-    const float* guide = tables + (size_t)(3 * n_steps + 1) * 4;
-    rb.sa = (const float4*)guide;
-    rb.rstart = (const int*)(guide + (size_t)n_steps * 4 + 8);
-    rb.rec = (const RestraintRec*)(guide + (size_t)n_steps * 4 + 8 + (size_t)L.B + 1);
-    rb.op_energy = nullptr;
-    void* q;
-#define IALLOC(dst, type, bytes) do { rc = dev_alloc(h, k.allocs, &q, bytes, true); if (rc) return rc; dst = (type)q; } while (0)
-    IALLOC(ip.known, const float*, (size_t)L.Nl * (3 + d.P) * sizeof(float));
-    IALLOC(ip.fix, float*, (size_t)L.Nl * sizeof(float));
-    IALLOC(ip.poff, float4*, (size_t)L.B * sizeof(float4));
-    IALLOC(rb.pin_com, float4*, (size_t)L.B * sizeof(float4));
-#undef IALLOC
-    return 0;
+    int rc = alloc_chain_buf(h, k, tables); if (rc) return rc;
+    rc = alloc_inpaint_part(h, k, tables + (size_t)(n_steps + 1) * 4, n_steps); if (rc) return rc;
+    return alloc_restrain_part(h, k, tables + (size_t)(3 * n_steps + 1) * 4, n_steps);
 }
 
 extern "C" int cmdgen_restrained_edit_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
@@ -1519,8 +1546,8 @@ extern "C" int cmdgen_restrained_edit_chain(cmdgen_handle* h, const float* pocke
                                             float clash_radius, float clash_k, float scale, float max_shift, float guide_below,
                                             float* energy_out, float* op_energy_out, int32_t use_graph, cmdgen_stream stream) {
     int rc = check_ready(h); if (rc) return rc;
-    if (h->dims.joint) return fail(h, CMDGEN_ESTATE, "the restrained edit chain is not supported for the joint model (update_pocket_coords=1): its pocket nodes diffuse with the latent");
-    if (h->dims.no_com) return fail(h, CMDGEN_ESTATE, "the restrained edit chain is not supported for no_com_projection handles (SimpleConditionalDDPM): the edit chain and the guidance frame follow the centre-of-mass projections");
+    rc = refuse_joint_no_com(h, "the restrained edit chain", kPocketDiffuses, ": the edit chain and the guidance frame follow the centre-of-mass projections");
+    if (rc) return rc;
     rc = check_inpaint_args(h, timesteps, start, resamplings, jump_length); if (rc) return rc;
     if (!pocket_x || !pocket_onehot || !phar_x || !phar_onehot || !fix_x || !fix_h || !xh_phar_out || !xh_pocket_out || !energy_out)
         return fail(h, CMDGEN_EINVAL, "null device pointer");
@@ -1529,59 +1556,27 @@ extern "C" int cmdgen_restrained_edit_chain(cmdgen_handle* h, const float* pocke
                           plan_restrained_edit_step_lds(h->lay.max_n, h->dims.P), rstart, rec);
     if (rc) return rc;
     const InpaintPlan plan = build_inpaint_plan(h, timesteps, start, resamplings, jump_length);
-    if (noise && n_draws < plan.n_draws)
-        return fail(h, CMDGEN_EINVAL, "noise holds %lld draws, the schedule needs %lld", (long long)n_draws, (long long)plan.n_draws);
-    const int n_steps = plan.n_steps, K = timesteps, B = h->lay.B;
+    rc = check_draws(h, noise, n_draws, plan.n_draws); if (rc) return rc;
     std::vector<float> tables = plan_tables(plan.coef, plan.coef2, plan.iop);
-    {
-        std::vector<float> sa;                       // [K][2], row K - 1 - s for the op that goes to level s
-        if (h->user_guide_K == K) sa = h->user_guide; else build_guide_table(h->gamma, h->cfg.timesteps, K, sa);
-        const size_t c0 = tables.size();
-        tables.resize(c0 + (size_t)n_steps * 4 + 8 + (size_t)B + 1 + rec.size() * 10, 0.f);
-        float* g = tables.data() + c0;
-        for (int i = 0; i < n_steps; ++i) {
-            const int row = K - 1 - plan.s_of[(size_t)i];
-            g[4 * i] = sa[2 * (size_t)row]; g[4 * i + 1] = sa[2 * (size_t)row + 1];
-        }
-        float* par = g + (size_t)n_steps * 4;
-        par[0] = clash_radius; par[1] = clash_k; par[2] = scale; par[3] = max_shift; par[4] = guide_below;
-        memcpy(par + 8, rstart.data(), rstart.size() * sizeof(int));
-        if (!rec.empty()) memcpy(par + 8 + B + 1, rec.data(), rec.size() * sizeof(cmdgen_restraint));
-    }
-    const hipStream_t caller = (hipStream_t)stream;
-    hipStream_t s; EvalLaunch a;
-    rc = begin_chain(h, CHAIN_RESTRAINED_EDIT, tables, n_steps, alloc_restrained_edit, pocket_ids_host, use_graph, caller, &s, &a); if (rc) return rc;
-    ChainSlot& k = h->chains[CHAIN_RESTRAINED_EDIT];
+    append_guidance(h, tables, timesteps, plan.s_of, 0, {clash_radius, clash_k, scale, max_shift, guide_below}, rstart, rec);
+    Chain ch;
+    rc = ch.open(h, CHAIN_RESTRAINED_EDIT, tables, plan.n_steps, alloc_restrained_edit, pocket_ids_host, noise, seed, z_steps_out, pocket_steps_out, use_graph, stream);
+    if (rc) return rc;
     const Dims& d = h->dims;
-    ChainBuf c = h->redit_chain;
-    c.noise = noise; c.seed = seed; c.z_steps = z_steps_out; c.pocket_steps = pocket_steps_out;
-    const InpaintBuf ip = h->redit;
-    RestrainBuf rb = h->redit_restr;
-    rb.clash_r = clash_radius; rb.clash_k = clash_k; rb.scale = scale; rb.max_shift = max_shift; rb.guide_below = guide_below;
+    const ChainBuf& c = ch.c;
+    const InpaintBuf ip = ch.k->inp;
+    RestrainBuf rb = ch.k->restr;
     rb.op_energy = op_energy_out;
-    if (start == timesteps) {                        // from the prior: z_T around the pocket centre
-        cmdgen_launch_chain_init(h->lay, d, c, pocket_x, pocket_onehot, s);
-        cmdgen_launch_inpaint_prep(h->lay, d, c, ip, phar_x, phar_onehot, fix_x, fix_h, pocket_x, s);
-    } else {                                         // part-way: z ~ q(z_start | the given rows)
-        cmdgen_launch_edit_start(h->lay, d, c, ip, plan.alpha_start, plan.sigma_start, phar_x, phar_onehot, fix_x, fix_h, pocket_x,
-                                 pocket_onehot, s);
-    }
-    cmdgen_launch_restrain_prep(h->lay, d, rb, pocket_x, s);
-    build_pocket_cache(h, k, c, a, s);
-    EvalLaunch a2 = a;                               // the evaluations are cmdgen_edit_chain's: every one with its own k_readout
-    a2.skip_count = 1;                               // k_restrained_edit_step_count ran pass 1 of the graph
-    cmdgen_launch_eval(a, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, s, nullptr);   // evaluation 0 (t = start / timesteps)
-    const void* key[6] = {noise, z_steps_out, pocket_steps_out, op_energy_out, nullptr, s};
-    rc = run_steps(h, k, key, seed, n_steps, use_graph, s, [&](hipStream_t ss) {
+    launch_edit_init(ch, ip, plan, start == timesteps, pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h);
+    cmdgen_launch_restrain_prep(h->lay, d, rb, pocket_x, ch.s);
+    ch.start(true);                                  // evaluation 0 (t = start / timesteps); the evaluations are cmdgen_edit_chain's: every one with its own k_readout
+    rc = ch.steps({noise, z_steps_out, pocket_steps_out, op_energy_out, nullptr}, plan.n_steps, [&](hipStream_t ss) {
         cmdgen_launch_restrained_edit_step_count(h->lay, d, c, ip, rb, h->work, h->work.eps_tmp, ss);
-        cmdgen_launch_eval(a2, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, ss, nullptr);
     });
     if (rc) return rc;
-    ChainBuf cf = c;                                 // the decode draw is the plan's last row (cmdgen_edit_chain)
-    if (noise) cf.noise = noise + (size_t)(plan.n_draws - 1 - (1 + n_steps)) * h->lay.Nl * (3 + d.P);
-    cmdgen_launch_chain_final(h->lay, d, cf, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, k.cog, s);
-    cmdgen_launch_restrain_energy(h->lay, d, rb, xh_phar_out, xh_pocket_out, energy_out, s);
-    return end_chain(h, caller, s);
+    cmdgen_launch_chain_final(h->lay, d, decode_buf(c, plan, (size_t)h->lay.Nl, d.P), h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, ch.k->cog, ch.s);
+    cmdgen_launch_restrain_energy(h->lay, d, rb, xh_phar_out, xh_pocket_out, energy_out, ch.s);
+    return ch.close();
 }
 
 // ---------------------------------------------------------------------------------
@@ -1590,19 +1585,9 @@ extern "C" int cmdgen_restrained_edit_chain(cmdgen_handle* h, const float* pocke
 // ---------------------------------------------------------------------------------
 // the slot's table block: coef (n_steps + 1) | coef2 | iop (n_steps each) | the group tables; the known rows and marks once per group
 static int alloc_multi_edit(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
-    int rc = alloc_chain_buf(h, k, h->medit_chain, tables); if (rc) return rc;
-    const Dims& d = h->dims;
-    const Layout& L = h->lay;
-    InpaintBuf& ip = h->medit;
-    ip.coef2 = (const float4*)(tables + (size_t)(n_steps + 1) * 4);
-    ip.iop = (const int4*)(tables + (size_t)(2 * n_steps + 1) * 4);
-    ip.n_steps = n_steps;
-    point_group_tab(h->medit_groups, tables + (size_t)(3 * n_steps + 1) * 4, (size_t)L.B);
-    void* q;                                         // (Nl bounds the unique rows of any grouping of this layout)
-    rc = dev_alloc(h, k.allocs, &q, (size_t)L.Nl * (3 + d.P) * sizeof(float), true); if (rc) return rc; ip.known = (const float*)q;
-    rc = dev_alloc(h, k.allocs, &q, (size_t)L.Nl * sizeof(float), true); if (rc) return rc; ip.fix = (float*)q;
-    rc = dev_alloc(h, k.allocs, &q, (size_t)L.B * sizeof(float4), true); if (rc) return rc; ip.poff = (float4*)q;
-    return 0;
+    const int rc = alloc_chain_buf(h, k, tables); if (rc) return rc;
+    point_group_tab(k.groups, tables + (size_t)(3 * n_steps + 1) * 4, (size_t)h->lay.B);
+    return alloc_inpaint_part(h, k, tables + (size_t)(n_steps + 1) * 4, n_steps);
 }
 
 extern "C" int cmdgen_multi_edit_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
@@ -1613,8 +1598,7 @@ extern "C" int cmdgen_multi_edit_chain(cmdgen_handle* h, const float* pocket_x, 
                                        float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
                                        int32_t use_graph, cmdgen_stream stream) {
     int rc = check_ready(h); if (rc) return rc;
-    if (h->dims.joint) return fail(h, CMDGEN_ESTATE, "the multi-pocket edit chain is not supported for the joint model (update_pocket_coords=1): its pocket nodes diffuse with the latent");
-    if (h->dims.no_com) return fail(h, CMDGEN_ESTATE, "the multi-pocket edit chain is not supported for no_com_projection handles (SimpleConditionalDDPM)");
+    rc = refuse_joint_no_com(h, "the multi-pocket edit chain", kPocketDiffuses); if (rc) return rc;
     rc = check_inpaint_args(h, timesteps, start, resamplings, jump_length); if (rc) return rc;
     if (!pocket_x || !pocket_onehot || !group_size_host || !weight_host || !phar_x || !phar_onehot || !fix_x || !fix_h || !xh_phar_out ||
         !xh_pocket_out)
@@ -1622,44 +1606,30 @@ extern "C" int cmdgen_multi_edit_chain(cmdgen_handle* h, const float* pocket_x, 
     GroupPlan gp;
     rc = build_group_plan(h, n_groups, group_size_host, weight_host, group_ids_host, gp); if (rc) return rc;
     const InpaintPlan plan = build_inpaint_plan(h, timesteps, start, resamplings, jump_length);
-    if (noise && n_draws < plan.n_draws)
-        return fail(h, CMDGEN_EINVAL, "noise holds %lld draws, the schedule needs %lld", (long long)n_draws, (long long)plan.n_draws);
-    const int n_steps = plan.n_steps;
+    rc = check_draws(h, noise, n_draws, plan.n_draws); if (rc) return rc;
     std::vector<float> tables = plan_tables(plan.coef, plan.coef2, plan.iop);
     append_group_tables(tables, gp, weight_host, h->lay.B);
-    const hipStream_t caller = (hipStream_t)stream;
-    hipStream_t s; EvalLaunch a;
-    rc = begin_chain(h, CHAIN_MULTI_EDIT, tables, n_steps, alloc_multi_edit, gp.gid.data(), use_graph, caller, &s, &a); if (rc) return rc;
-    ChainSlot& k = h->chains[CHAIN_MULTI_EDIT];
+    Chain ch;
+    rc = ch.open(h, CHAIN_MULTI_EDIT, tables, plan.n_steps, alloc_multi_edit, gp.gid.data(), noise, seed, z_steps_out, pocket_steps_out, use_graph, stream); if (rc) return rc;
     const Dims& d = h->dims;
-    ChainBuf c = h->medit_chain;
-    c.noise = noise; c.seed = seed; c.z_steps = z_steps_out; c.pocket_steps = pocket_steps_out;
-    const InpaintBuf ip = h->medit;
-    GroupTab gt = h->medit_groups;
-    gt.G = gp.G; gt.Nu = (int)gp.Nu;
+    const ChainBuf& c = ch.c;
+    const InpaintBuf ip = ch.k->inp;
+    const GroupTab gt = group_tab(*ch.k, gp);
     if (start == timesteps)                          // from the prior: z_T around the weighted pocket centre
-        cmdgen_launch_multi_init(h->lay, d, c, gt, pocket_x, pocket_onehot, s);
+        cmdgen_launch_multi_init(h->lay, d, c, gt, pocket_x, pocket_onehot, ch.s);
     else                                             // part-way: z ~ q(z_start | the given rows)
-        cmdgen_launch_multi_edit_start(h->lay, d, c, gt, plan.alpha_start, plan.sigma_start, phar_x, phar_onehot, pocket_x, pocket_onehot, s);
+        cmdgen_launch_multi_edit_start(h->lay, d, c, gt, plan.alpha_start, plan.sigma_start, phar_x, phar_onehot, pocket_x, pocket_onehot, ch.s);
     // a launch of its own after the init: every member reads the projected pocket of its group's FIRST member for the offset
-    cmdgen_launch_multi_edit_prep(h->lay, d, c, gt, ip, phar_x, phar_onehot, fix_x, fix_h, pocket_x, s);
-    build_pocket_cache(h, k, c, a, s);
-    EvalLaunch a2 = a;
-    a2.skip_count = 1;                               // k_multi_edit_step_count ran pass 1 of the graph
-    cmdgen_launch_eval(a, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, s, nullptr);   // evaluation 0 (t = start / timesteps)
+    cmdgen_launch_multi_edit_prep(h->lay, d, c, gt, ip, phar_x, phar_onehot, fix_x, fix_h, pocket_x, ch.s);
+    ch.start(true);                                  // evaluation 0 (t = start / timesteps)
     // the plan's tables and the group tables are slot buffers: a changed plan, start, grouping or weight prepares the slot again and
     // drops its graph; the caller's pointers are the key
-    const void* key[6] = {noise, z_steps_out, pocket_steps_out, nullptr, nullptr, s};
-    rc = run_steps(h, k, key, seed, n_steps, use_graph, s, [&](hipStream_t ss) {
+    rc = ch.steps({noise, z_steps_out, pocket_steps_out, nullptr, nullptr}, plan.n_steps, [&](hipStream_t ss) {
         cmdgen_launch_multi_edit_step_count(h->lay, d, c, gt, ip, h->work, h->work.eps_tmp, ss);
-        cmdgen_launch_eval(a2, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, ss, nullptr);
     });
     if (rc) return rc;
-    // decode: k_multi_final reads its draw from row 1 + n_steps of `noise`; the decode draw is the plan's last row
-    ChainBuf cf = c;
-    if (noise) cf.noise = noise + (size_t)(plan.n_draws - 1 - (1 + n_steps)) * gt.Nu * (3 + d.P);
-    cmdgen_launch_multi_final(h->lay, d, cf, gt, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, k.cog, s);
-    return end_chain(h, caller, s);
+    cmdgen_launch_multi_final(h->lay, d, decode_buf(c, plan, (size_t)gt.Nu, d.P), gt, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, ch.k->cog, ch.s);
+    return ch.close();
 }
 
 // ---------------------------------------------------------------------------------
@@ -1667,13 +1637,8 @@ extern "C" int cmdgen_multi_edit_chain(cmdgen_handle* h, const float* pocket_x, 
 // ---------------------------------------------------------------------------------
 // the scoring chain's ChainBuf (coef: one row per level, then the (alpha_T, sigma_T) row) and the clean rows it noises
 static int alloc_score(cmdgen_handle* h, ChainSlot& k, const float* tables, int) {
-    int rc = alloc_chain_buf(h, k, h->score_chain, tables); if (rc) return rc;
-    const Dims& d = h->dims;
-    const Layout& L = h->lay;
-    void* q;
-    rc = dev_alloc(h, k.allocs, &q, (size_t)L.Nl * (3 + d.P) * sizeof(float), true); if (rc) return rc; h->score.xh0 = (const float*)q;
-    rc = dev_alloc(h, k.allocs, &q, (size_t)L.Np * 3 * sizeof(float), true); if (rc) return rc; h->score.pocket0 = (const float*)q;
-    return 0;
+    const int rc = alloc_chain_buf(h, k, tables); if (rc) return rc;
+    return alloc_score_part(h, k);
 }
 
 // what cmdgen_score_chain and cmdgen_multi_score_chain check of a level list alike, and its rows: one per level
@@ -1706,34 +1671,27 @@ extern "C" int cmdgen_score_chain(cmdgen_handle* h, const float* phar_x, const f
                                   const float* noise, uint64_t seed, const int64_t* pocket_ids_host,
                                   float* level_terms_out, float* kl_sums_out, int32_t use_graph, cmdgen_stream stream) {
     int rc = check_ready(h); if (rc) return rc;
-    if (h->dims.joint) return fail(h, CMDGEN_ESTATE, "scoring is not supported for the joint model (update_pocket_coords=1): its loss has the pocket's own terms");
-    if (h->dims.no_com) return fail(h, CMDGEN_ESTATE, "scoring is not supported for no_com_projection handles (SimpleConditionalDDPM)");
+    rc = refuse_joint_no_com(h, "scoring", kOwnPocketTerms); if (rc) return rc;
     if (!phar_x || !phar_onehot || !pocket_x || !pocket_onehot || !t_levels_host || !level_terms_out || !kl_sums_out)
         return fail(h, CMDGEN_EINVAL, "null pointer");
     std::vector<float> tables;
     rc = build_level_rows(h, n_levels, t_levels_host, level_coef_host, tables); if (rc) return rc;
     const float alpha_T = tables[4 * (size_t)n_levels];
-    const hipStream_t caller = (hipStream_t)stream;
-    hipStream_t s; EvalLaunch a;
-    rc = begin_chain(h, CHAIN_SCORE, tables, n_levels, alloc_score, pocket_ids_host, use_graph, caller, &s, &a); if (rc) return rc;
-    ChainSlot& k = h->chains[CHAIN_SCORE];
+    Chain ch;
+    rc = ch.open(h, CHAIN_SCORE, tables, n_levels, alloc_score, pocket_ids_host, noise, seed, nullptr, nullptr, use_graph, stream); if (rc) return rc;
     const Dims& d = h->dims;
-    ChainBuf c = h->score_chain;
-    c.noise = noise; c.seed = seed; c.z_steps = nullptr; c.pocket_steps = nullptr;
-    ScoreBuf sc = h->score;
+    const ChainBuf& c = ch.c;
+    ScoreBuf sc = ch.k->score;
     sc.out = level_terms_out;
-    cmdgen_launch_score_init(h->lay, d, c, sc, alpha_T, phar_x, phar_onehot, pocket_x, pocket_onehot, kl_sums_out, s);
-    build_pocket_cache(h, k, c, a, s);
-    a.skip_count = 1;                                // k_score_step ran pass 1 of the graph
+    cmdgen_launch_score_init(h->lay, d, c, sc, alpha_T, phar_x, phar_onehot, pocket_x, pocket_onehot, kl_sums_out, ch.s);
+    ch.start(false);                                 // every evaluation follows a k_score_step
     // the level rows and the clean rows are slot buffers; the captured steps read the caller's draws and write its output
-    const void* key[6] = {noise, level_terms_out, nullptr, nullptr, nullptr, s};
-    rc = run_steps(h, k, key, seed, n_levels, use_graph, s, [&](hipStream_t ss) {
+    rc = ch.steps({noise, level_terms_out, nullptr, nullptr, nullptr}, n_levels, [&](hipStream_t ss) {
         cmdgen_launch_score_step(h->lay, d, c, sc, h->work, h->work.eps_tmp, ss);
-        cmdgen_launch_eval(a, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, ss, nullptr);
     });
     if (rc) return rc;
-    cmdgen_launch_score_final(h->lay, d, c, sc, h->work, h->work.eps_tmp, s);
-    return end_chain(h, caller, s);
+    cmdgen_launch_score_final(h->lay, d, c, sc, h->work, h->work.eps_tmp, ch.s);
+    return ch.close();
 }
 
 // ---------------------------------------------------------------------------------
@@ -1742,14 +1700,9 @@ extern "C" int cmdgen_score_chain(cmdgen_handle* h, const float* phar_x, const f
 // ---------------------------------------------------------------------------------
 // the slot's table block: the level rows (n_levels + 1) | the group tables
 static int alloc_multi_score(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_levels) {
-    int rc = alloc_chain_buf(h, k, h->mscore_chain, tables); if (rc) return rc;
-    const Dims& d = h->dims;
-    const Layout& L = h->lay;
-    void* q;
-    rc = dev_alloc(h, k.allocs, &q, (size_t)L.Nl * (3 + d.P) * sizeof(float), true); if (rc) return rc; h->mscore.xh0 = (const float*)q;
-    rc = dev_alloc(h, k.allocs, &q, (size_t)L.Np * 3 * sizeof(float), true); if (rc) return rc; h->mscore.pocket0 = (const float*)q;
-    point_group_tab(h->mscore_groups, tables + (size_t)(n_levels + 1) * 4, (size_t)L.B);
-    return 0;
+    const int rc = alloc_chain_buf(h, k, tables); if (rc) return rc;
+    point_group_tab(k.groups, tables + (size_t)(n_levels + 1) * 4, (size_t)h->lay.B);
+    return alloc_score_part(h, k);
 }
 
 extern "C" int cmdgen_multi_score_chain(cmdgen_handle* h, const float* phar_x, const float* phar_onehot,
@@ -1760,8 +1713,7 @@ extern "C" int cmdgen_multi_score_chain(cmdgen_handle* h, const float* phar_x, c
                                         float* group_terms_out, float* member_terms_out, float* kl_sums_out,
                                         int32_t use_graph, cmdgen_stream stream) {
     int rc = check_ready(h); if (rc) return rc;
-    if (h->dims.joint) return fail(h, CMDGEN_ESTATE, "scoring is not supported for the joint model (update_pocket_coords=1): its loss has the pocket's own terms");
-    if (h->dims.no_com) return fail(h, CMDGEN_ESTATE, "scoring is not supported for no_com_projection handles (SimpleConditionalDDPM)");
+    rc = refuse_joint_no_com(h, "scoring", kOwnPocketTerms); if (rc) return rc;
     if (!phar_x || !phar_onehot || !pocket_x || !pocket_onehot || !group_size_host || !weight_host || !t_levels_host || !group_terms_out ||
         !kl_sums_out)
         return fail(h, CMDGEN_EINVAL, "null pointer");
@@ -1771,30 +1723,23 @@ extern "C" int cmdgen_multi_score_chain(cmdgen_handle* h, const float* phar_x, c
     rc = build_group_plan(h, n_groups, group_size_host, weight_host, group_ids_host, gp); if (rc) return rc;
     const float alpha_T = tables[4 * (size_t)n_levels];
     append_group_tables(tables, gp, weight_host, h->lay.B);
-    const hipStream_t caller = (hipStream_t)stream;
-    hipStream_t s; EvalLaunch a;
-    rc = begin_chain(h, CHAIN_MULTI_SCORE, tables, n_levels, alloc_multi_score, gp.gid.data(), use_graph, caller, &s, &a); if (rc) return rc;
-    ChainSlot& k = h->chains[CHAIN_MULTI_SCORE];
+    Chain ch;
+    rc = ch.open(h, CHAIN_MULTI_SCORE, tables, n_levels, alloc_multi_score, gp.gid.data(), noise, seed, nullptr, nullptr, use_graph, stream); if (rc) return rc;
     const Dims& d = h->dims;
-    ChainBuf c = h->mscore_chain;
-    c.noise = noise; c.seed = seed; c.z_steps = nullptr; c.pocket_steps = nullptr;
-    ScoreBuf sc = h->mscore;
+    const ChainBuf& c = ch.c;
+    ScoreBuf sc = ch.k->score;
     sc.out = group_terms_out;
-    GroupTab gt = h->mscore_groups;
-    gt.G = gp.G; gt.Nu = (int)gp.Nu;
-    cmdgen_launch_multi_score_init(h->lay, d, c, sc, gt, alpha_T, phar_x, phar_onehot, pocket_x, pocket_onehot, kl_sums_out, s);
-    build_pocket_cache(h, k, c, a, s);
-    a.skip_count = 1;                                // k_multi_score_step ran pass 1 of the graph
+    const GroupTab gt = group_tab(*ch.k, gp);
+    cmdgen_launch_multi_score_init(h->lay, d, c, sc, gt, alpha_T, phar_x, phar_onehot, pocket_x, pocket_onehot, kl_sums_out, ch.s);
+    ch.start(false);                                 // every evaluation follows a k_multi_score_step
     // the level rows, the group tables and the clean rows are slot buffers (a changed level list, grouping or weight prepares the slot
     // again and drops its graph); the captured steps read the caller's draws and write its outputs
-    const void* key[6] = {noise, group_terms_out, member_terms_out, nullptr, nullptr, s};
-    rc = run_steps(h, k, key, seed, n_levels, use_graph, s, [&](hipStream_t ss) {
+    rc = ch.steps({noise, group_terms_out, member_terms_out, nullptr, nullptr}, n_levels, [&](hipStream_t ss) {
         cmdgen_launch_multi_score_step(h->lay, d, c, sc, gt, h->work, h->work.eps_tmp, member_terms_out, ss);
-        cmdgen_launch_eval(a, c.z_phar, c.xh_pocket, nullptr, c.coef, c.state, h->work.eps_tmp, nullptr, ss, nullptr);
     });
     if (rc) return rc;
-    cmdgen_launch_multi_score_final(h->lay, d, c, sc, gt, h->work, h->work.eps_tmp, member_terms_out, s);
-    return end_chain(h, caller, s);
+    cmdgen_launch_multi_score_final(h->lay, d, c, sc, gt, h->work, h->work.eps_tmp, member_terms_out, ch.s);
+    return ch.close();
 }
 
 extern "C" int cmdgen_chain_status(cmdgen_handle* h, float* max_rel, float* max_cog, int64_t* nan_resets, cmdgen_stream stream) {

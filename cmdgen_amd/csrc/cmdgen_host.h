@@ -34,9 +34,17 @@ struct ChainSlot {
     unsigned int* cog = nullptr;           // CoG drift of the final sample
     float* pk[7] = {};                     // PocketCache storage (c, P0, Q0, dh, dP, dQ) and the time pair (0, 1) that builds it
     hipGraphExec_t graph = nullptr;        // G captured steps, valid for the key below
-    const void* key[6] = {};               // noise, z_steps (scoring: the level terms), pocket_steps (multi-pocket scoring: the member terms), phar_fixed (restrained: the op energies), pocket_fixed, stream
+    const void* key[6] = {};               // what the captured steps bake in: five caller pointers and the stream
     unsigned long long seed = 0;
     int graph_steps = 0;
+    // the kernel arguments the buffers above back: filled by the kind's ChainAlloc, copied and completed per call by its entry
+    ChainBuf buf{};                        // every conditional kind: z, the pocket, the posterior (scoring: level) rows, checks and state
+    InpaintBuf inp{};                      // edit kinds: the op tables, the known rows and marks (multi-pocket: once per group), the offset per sample
+    GroupTab groups{};                     // multi-pocket kinds: the group tables in the slot's table block (a changed grouping prepares the slot again)
+    RestrainBuf restr{};                   // restrained kinds: the guidance tables in the slot's table block (a changed restraint prepares the slot again)
+    ScoreBuf score{};                      // scoring kinds: the clean rows the levels noise
+    JointBuf joint{};                      // joint kind: its z, scratch and plan rows ...
+    float* eps_pocket = nullptr;           // ... and the pocket output [Np][3+R] of its evaluations
 };
 
 struct cmdgen_handle {
@@ -71,26 +79,6 @@ struct cmdgen_handle {
     // chains
     ChainSlot chains[CHAIN_KINDS];
     ChainKind last_chain = CHAIN_PLAIN;    // the kind cmdgen_chain_status reports on
-    ChainBuf chain{};                      // the kernel arguments the slots' buffers back: plain chain
-    JointBuf joint{};                      // joint-model chain
-    float* eps_pocket_tmp = nullptr;       // [Np][3+R] evaluation output of the joint chain
-    ChainBuf inp_chain{};                  // conditional RePaint chain: its z, pocket, posterior rows, checks and state
-    InpaintBuf inp{};
-    ChainBuf score_chain{};                // scoring chain: the level's z, the pocket, the level rows, checks and state
-    ScoreBuf score{};
-    ChainBuf multi_chain{};                // multi-pocket chain: every member's copy of z, the pockets, the posterior rows, checks and state
-    GroupTab groups{};                     // ... and its group tables (in the slot's table block: a changed grouping prepares the slot again)
-    ChainBuf medit_chain{};                // multi-pocket edit chain: the multi-pocket chain's buffers, ...
-    InpaintBuf medit{};                    // ... the edit chain's op tables, the known rows and marks once per group ([Nu] rows), the group's offset per member
-    GroupTab medit_groups{};               // ... and its own group tables
-    ChainBuf mscore_chain{};               // multi-pocket scoring chain: the scoring chain's buffers (every member's copy of the level's z and of the clean rows), ...
-    ScoreBuf mscore{};
-    GroupTab mscore_groups{};              // ... and its own group tables, behind the level rows of the slot's table block
-    ChainBuf restr_chain{};                // restrained chain: the plain chain's buffers, ...
-    RestrainBuf restr{};                   // ... and the guidance tables behind the posterior rows of the slot's table block (a changed restraint prepares the slot again)
-    ChainBuf redit_chain{};                // restrained edit chain: the edit chain's buffers, ...
-    InpaintBuf redit{};                    // ... its op tables, known rows and marks, ...
-    RestrainBuf redit_restr{};             // ... and the guidance tables behind the plan's tables in the slot's table block
     std::vector<float> user_coef;          // optional host-supplied step table
     int user_coef_K = -1;
     std::vector<float> user_guide;         // optional host-supplied guide table [K][2] (cmdgen_set_guide_table)

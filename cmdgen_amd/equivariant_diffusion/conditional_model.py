@@ -154,34 +154,123 @@ class ConditionalDDPM(EnVariationalDiffusion):
         Returns (xh_phar, xh_pocket, phar_mask, pocket_mask) like the reference; with
         return_frames > 1 the first two carry a leading frame axis.
         """
-        timesteps = self.T if timesteps is None else timesteps
-        assert 0 < return_frames <= timesteps
-        assert timesteps % return_frames == 0
-        n_samples = len(pocket['size'])
-        device = pocket['x'].device
-        self.refresh_learned_schedule()
-        h = self.dynamics.hip_handle()
-        sizes = pocket['size'].detach().to('cpu', torch.int64).numpy()
-        nph = torch.as_tensor(num_nodes_phar).detach().to('cpu', torch.int64).numpy()
-        assert len(nph) == n_samples
-        pm = pocket['mask']
-        if pm.numel() > 1 and bool((pm[1:] < pm[:-1]).any()):
-            raise ValueError('pocket mask must be ascending and contiguous')
-        h.set_layout(nph, sizes)
-        h.set_step_table(timesteps, self.step_table(timesteps))
-        phar_mask = utils.num_nodes_to_batch_mask(n_samples, torch.as_tensor(nph), device)
-        px = pocket['x'].detach().to(torch.float32).contiguous()
-        poh = pocket['one_hot'].detach().to(torch.float32).contiguous()
-        if noise is not None:
-            noise = noise.detach().to(device, torch.float32).contiguous()
-        if seed is None:
-            seed = fresh_seed()
+        timesteps = self._checked_frames(timesteps, return_frames)
+        sizes, nph, px, poh = self._pocket_inputs(pocket, num_nodes_phar)
+        h, phar_mask, noise, seed = self._prepare_sample(nph, (nph, sizes), pocket['x'].device, timesteps, noise, seed)
         run = lambda: h.sample_chain(px, poh, timesteps, noise=noise, seed=seed, pocket_ids=pocket_ids,
                                      want_steps=return_frames > 1, use_graph=self.use_hip_graph)
         # frames: idx = s*return_frames//timesteps for steps with (s*return_frames) % timesteps == 0
         # (conditional_model.py:439-442); frame 0 is overwritten by the final sample (:460-461).
         out = self._finish_chain(h, run, self.inpaint_frames(1, 1, timesteps, return_frames), return_frames)
         return out[0], out[1], phar_mask, pocket['mask']
+
+    # ---- what the chain methods below share
+    def _checked_frames(self, timesteps, return_frames):
+        timesteps = self.T if timesteps is None else timesteps
+        assert 0 < return_frames <= timesteps
+        assert timesteps % return_frames == 0
+        return timesteps
+
+    @staticmethod
+    def _pocket_inputs(pocket, num_nodes_phar):
+        """sample_given_pocket's arguments, checked -> (pocket sizes, num_nodes_phar as host int64 arrays, pocket x, one_hot as float32)."""
+        sizes = pocket['size'].detach().to('cpu', torch.int64).numpy()
+        nph = torch.as_tensor(num_nodes_phar).detach().to('cpu', torch.int64).numpy()
+        assert len(nph) == len(pocket['size'])
+        pm = pocket['mask']
+        if pm.numel() > 1 and bool((pm[1:] < pm[:-1]).any()):
+            raise ValueError('pocket mask must be ascending and contiguous')
+        return sizes, nph, pocket['x'].detach().to(torch.float32).contiguous(), pocket['one_hot'].detach().to(torch.float32).contiguous()
+
+    def _prepare_sample(self, nph, layout, device, timesteps, noise, seed, guide=False, plan=None):
+        """The sample family's preparation once the arguments are checked: the learned schedule, the handle with `layout` (num_phar and
+        num_pocket of every sample of the device layout), the step table (guide: and the guide table), the phar mask of nph (one entry per
+        sample or group), the noise on the device and a seed.  plan: (start, resamplings, jump_length) of an edit chain, whose draws the
+        noise must cover (_prepare_edit).  -> (h, phar_mask, noise, seed)."""
+        self.refresh_learned_schedule()
+        h = self.dynamics.hip_handle()
+        h.set_layout(*layout)
+        h.set_step_table(timesteps, self.step_table(timesteps))
+        if guide:
+            h.set_guide_table(timesteps, self.guide_table(timesteps))
+        if noise is not None:
+            noise = noise.detach().to(device, torch.float32).contiguous()
+        if plan is not None:
+            n_steps, n_draws = h.edit_plan(timesteps, *plan)
+            if noise is not None and (noise.dim() != 3 or noise.shape[0] < n_draws):
+                raise ValueError(f'noise has shape {tuple(noise.shape)}: this schedule needs {n_draws} draws of '
+                                 f'[{int(nph.sum())}, {3 + self.phar_nf}]')
+        if seed is None:
+            seed = fresh_seed()
+        return h, utils.num_nodes_to_batch_mask(len(nph), torch.as_tensor(nph), device), noise, seed
+
+    def _prepare_edit(self, nph, layout, device, timesteps, start, resamplings, jump_length, noise, seed, guide=False):
+        """The edit family's preparation: _prepare_sample, and the noise covers the draws of the edit plan.  -> (h, phar_mask, noise, seed)."""
+        return self._prepare_sample(nph, layout, device, timesteps, noise, seed, guide, (start, resamplings, jump_length))
+
+    def _checked_start(self, timesteps, start):
+        """edit's timesteps and start level, checked -> (timesteps, start) as ints."""
+        timesteps = self.T if timesteps is None else int(timesteps)
+        start = timesteps if start is None else start
+        if int(start) != start or not 1 <= int(start) <= timesteps:
+            raise ValueError(f'start={start} must be an integer level in [1, timesteps={timesteps}]')
+        return timesteps, int(start)
+
+    @staticmethod
+    def _phar_pocket_sizes(phar, pocket):
+        """The sizes of a given pharmacophore and its pocket, both batched over the same samples with sorted masks -> (pocket sizes, nph)."""
+        n_samples = len(pocket['size'])
+        sizes = pocket['size'].detach().to('cpu', torch.int64).numpy()
+        nph = phar['size'].detach().to('cpu', torch.int64).numpy()
+        if len(nph) != n_samples:
+            raise ValueError(f'phar has {len(nph)} samples, pocket {n_samples}')
+        for m in (phar['mask'], pocket['mask']):
+            if m.numel() > 1 and bool((m[1:] < m[:-1]).any()):
+                raise ValueError('batch masks must be ascending and contiguous')
+        return sizes, nph
+
+    @staticmethod
+    def _group_phar_sizes(phar, G):
+        """... of a pharmacophore given per GROUP of pockets (the pockets: _checked_pockets) -> nph."""
+        nph = phar['size'].detach().to('cpu', torch.int64).numpy().reshape(-1)
+        if len(nph) != G:
+            raise ValueError(f'phar has {len(nph)} samples, pocket {G}')
+        pm = phar['mask']
+        if pm.numel() > 1 and bool((pm[1:] < pm[:-1]).any()):
+            raise ValueError('batch masks must be ascending and contiguous')
+        return nph
+
+    def _check_phar_rows(self, phar, n_phar):
+        if tuple(phar['x'].shape) != (n_phar, self.n_dims) or tuple(phar['one_hot'].shape) != (n_phar, self.phar_nf):
+            raise ValueError(f"phar x / one_hot have shapes {tuple(phar['x'].shape)} / {tuple(phar['one_hot'].shape)}: expected "
+                             f'[{n_phar}, {self.n_dims}] / [{n_phar}, {self.phar_nf}] (sum(size) rows)')
+
+    def _finish_restrained(self, h, run, frame_of_step, return_frames):
+        """_finish_chain for a restrained chain, whose run() returns (xh_phar, xh_pocket, z_steps, energy [B, 2], op_energy).
+        -> (_finish_chain's result, {'energy': [B], 'max_violation': [B]} and, with return_frames > 1, 'op_energy')."""
+        extra = {}
+
+        def run3():
+            out = run()
+            extra['energy'], extra['op_energy'] = out[3], out[4]
+            return out[:3]
+
+        out = self._finish_chain(h, run3, frame_of_step, return_frames)
+        info = {'energy': extra['energy'][:, 0].clone(), 'max_violation': extra['energy'][:, 1].clone()}
+        if return_frames > 1:
+            info['op_energy'] = extra['op_energy']
+        return out, info
+
+    def _level_noise(self, noise, R, K, n_phar, device):
+        """The injected draws of a scoring call (None: device draws) as float32 [R (K + 1), n_phar, 3+P] on `device`, checked."""
+        if noise is None:
+            return None
+        noise, ld = noise.detach().to(device, torch.float32).contiguous(), self.n_dims + self.phar_nf
+        if noise.dim() == 4:
+            noise = noise.reshape(-1, noise.shape[2], noise.shape[3])
+        if tuple(noise.shape) != (R * (K + 1), n_phar, ld):
+            raise ValueError(f'noise has shape {tuple(noise.shape)}: {R} x {K + 1} levels need [{R * (K + 1)}, {n_phar}, {ld}]')
+        return noise
 
     @torch.no_grad()
     def sample_restrained(self, pocket, num_nodes_phar, restraints, clash=None, scale=1.0, max_shift=None, guide_below=1.0,
@@ -200,45 +289,16 @@ class ConditionalDDPM(EnVariationalDiffusion):
         Returns sample_given_pocket's tuple plus {'energy': [B], 'max_violation': [B]} of the returned sample (and 'op_energy'
         [timesteps, B], the energy at every op's denoised estimate, when return_frames > 1)."""
         from .. import restraints as rs
-        timesteps = self.T if timesteps is None else timesteps
-        assert 0 < return_frames <= timesteps
-        assert timesteps % return_frames == 0
-        n_samples = len(pocket['size'])
-        device = pocket['x'].device
-        nph = torch.as_tensor(num_nodes_phar).detach().to('cpu', torch.int64).numpy()
-        assert len(nph) == n_samples
+        timesteps = self._checked_frames(timesteps, return_frames)
+        sizes, nph, px, poh = self._pocket_inputs(pocket, num_nodes_phar)
         rec = rs.records(restraints, nph)
         clash_r, clash_k = rs.clash_pair(clash)
         scale, max_shift, guide_below = rs.check_scalars(scale, rs.DEFAULT_MAX_SHIFT if max_shift is None else max_shift, guide_below)
-        pm = pocket['mask']
-        if pm.numel() > 1 and bool((pm[1:] < pm[:-1]).any()):
-            raise ValueError('pocket mask must be ascending and contiguous')
-        self.refresh_learned_schedule()
-        h = self.dynamics.hip_handle()
-        sizes = pocket['size'].detach().to('cpu', torch.int64).numpy()
-        h.set_layout(nph, sizes)
-        h.set_step_table(timesteps, self.step_table(timesteps))
-        h.set_guide_table(timesteps, self.guide_table(timesteps))
-        phar_mask = utils.num_nodes_to_batch_mask(n_samples, torch.as_tensor(nph), device)
-        px = pocket['x'].detach().to(torch.float32).contiguous()
-        poh = pocket['one_hot'].detach().to(torch.float32).contiguous()
-        if noise is not None:
-            noise = noise.detach().to(device, torch.float32).contiguous()
-        if seed is None:
-            seed = fresh_seed()
-        extra = {}
-
-        def run():
-            out = h.restrained_chain(px, poh, timesteps, rec, clash_radius=clash_r, clash_k=clash_k, scale=scale, max_shift=max_shift,
-                                     guide_below=guide_below, noise=noise, seed=seed, pocket_ids=pocket_ids,
-                                     want_steps=return_frames > 1, use_graph=self.use_hip_graph)
-            extra['energy'], extra['op_energy'] = out[3], out[4]
-            return out[:3]
-
-        out = self._finish_chain(h, run, self.inpaint_frames(1, 1, timesteps, return_frames), return_frames)
-        info = {'energy': extra['energy'][:, 0].clone(), 'max_violation': extra['energy'][:, 1].clone()}
-        if return_frames > 1:
-            info['op_energy'] = extra['op_energy']
+        h, phar_mask, noise, seed = self._prepare_sample(nph, (nph, sizes), pocket['x'].device, timesteps, noise, seed, guide=True)
+        run = lambda: h.restrained_chain(px, poh, timesteps, rec, clash_radius=clash_r, clash_k=clash_k, scale=scale, max_shift=max_shift,
+                                         guide_below=guide_below, noise=noise, seed=seed, pocket_ids=pocket_ids,
+                                         want_steps=return_frames > 1, use_graph=self.use_hip_graph)
+        out, info = self._finish_restrained(h, run, self.inpaint_frames(1, 1, timesteps, return_frames), return_frames)
         return out[0], out[1], phar_mask, pocket['mask'], info
 
     @staticmethod
@@ -282,20 +342,9 @@ class ConditionalDDPM(EnVariationalDiffusion):
         if len(nph) != G:
             raise ValueError(f'num_nodes_phar has {len(nph)} entries for {G} groups')
         w = self.group_weights(weights, G, M)
-        timesteps = self.T if timesteps is None else timesteps
-        assert 0 < return_frames <= timesteps
-        assert timesteps % return_frames == 0
-        device = pockets[0]['x'].device
+        timesteps = self._checked_frames(timesteps, return_frames)
         sizes, rows, px, poh = self._member_layout(pockets, M, G)
-        self.refresh_learned_schedule()
-        h = self.dynamics.hip_handle()
-        h.set_layout(np.repeat(nph, M), sizes.reshape(-1))
-        h.set_step_table(timesteps, self.step_table(timesteps))
-        phar_mask = utils.num_nodes_to_batch_mask(G, torch.as_tensor(nph), device)
-        if noise is not None:
-            noise = noise.detach().to(device, torch.float32).contiguous()
-        if seed is None:
-            seed = fresh_seed()
+        h, phar_mask, noise, seed = self._prepare_sample(nph, (np.repeat(nph, M), sizes.reshape(-1)), pockets[0]['x'].device, timesteps, noise, seed)
         run = lambda: h.multi_pocket_chain(px, poh, [M] * G, w.reshape(-1), timesteps, noise=noise, seed=seed, group_ids=group_ids,
                                            want_steps=return_frames > 1, use_graph=self.use_hip_graph)
         out = self._finish_chain(h, run, self.inpaint_frames(1, 1, timesteps, return_frames), return_frames)
@@ -356,39 +405,19 @@ class ConditionalDDPM(EnVariationalDiffusion):
         Returns (xh_phar, xh_pocket, phar_mask, pocket_mask) like sample_given_pocket; with return_frames > 1
         (jump_length 1 only) the frames are the states at the end of each resample cycle, frame 0 the final sample.
         """
-        timesteps = self.T if timesteps is None else timesteps
-        assert 0 < return_frames <= timesteps
-        assert timesteps % return_frames == 0
+        timesteps = self._checked_frames(timesteps, return_frames)
         if return_frames > 1 and jump_length != 1:
             raise ValueError('return_frames > 1 is only implemented for jump_length=1 (as in the joint model\'s inpaint)')
         device = pocket['x'].device
-        n_samples = len(pocket['size'])
-        sizes = pocket['size'].detach().to('cpu', torch.int64).numpy()
-        nph = phar['size'].detach().to('cpu', torch.int64).numpy()
-        if len(nph) != n_samples:
-            raise ValueError(f'phar has {len(nph)} samples, pocket {n_samples}')
-        for m in (phar['mask'], pocket['mask']):
-            if m.numel() > 1 and bool((m[1:] < m[:-1]).any()):
-                raise ValueError('batch masks must be ascending and contiguous')
+        sizes, nph = self._phar_pocket_sizes(phar, pocket)
         n_phar = int(nph.sum())
         fixed = torch.as_tensor(phar_fixed).detach().to(device, torch.float32)
         if fixed.dim() == 2 and fixed.shape[1] == 1:
             fixed = fixed[:, 0]
         if fixed.dim() != 1 or fixed.numel() != n_phar:
             raise ValueError(f'phar_fixed has shape {tuple(torch.as_tensor(phar_fixed).shape)}: expected [{n_phar}] or [{n_phar}, 1]')
-        self.refresh_learned_schedule()
-        h = self.dynamics.hip_handle()
-        h.set_layout(nph, sizes)
-        h.set_step_table(timesteps, self.step_table(timesteps))
-        n_steps, n_draws = h.inpaint_plan(timesteps, resamplings, jump_length)
+        h, phar_mask, noise, seed = self._prepare_edit(nph, (nph, sizes), device, timesteps, timesteps, resamplings, jump_length, noise, seed)
         f32 = lambda t: t.detach().to(device, torch.float32).contiguous()
-        if noise is not None:
-            noise = f32(noise)
-            if noise.dim() != 3 or noise.shape[0] < n_draws:
-                raise ValueError(f'noise has shape {tuple(noise.shape)}: this schedule needs {n_draws} draws of [{n_phar}, {3 + self.phar_nf}]')
-        if seed is None:
-            seed = fresh_seed()
-        phar_mask = utils.num_nodes_to_batch_mask(n_samples, torch.as_tensor(nph), device)
         args = (f32(pocket['x']), f32(pocket['one_hot']), f32(phar['x']), f32(phar['one_hot']), fixed.contiguous())
         run = lambda: h.inpaint_chain(*args, timesteps, resamplings=resamplings, jump_length=jump_length, noise=noise, seed=seed,
                                       pocket_ids=pocket_ids, want_steps=return_frames > 1, use_graph=self.use_hip_graph)
@@ -421,36 +450,13 @@ class ConditionalDDPM(EnVariationalDiffusion):
         The whole chain runs on the device (cmdgen_edit_chain; its header gives the ops, the draw layout and the Philox
         counters).  noise [n_draws, Nl, 3+P] (Handle.edit_plan), seed and pocket_ids as in sample_given_pocket.
         Returns (xh_phar, xh_pocket, phar_mask, pocket_mask) like sample_given_pocket."""
-        timesteps = self.T if timesteps is None else int(timesteps)
-        start = timesteps if start is None else start
-        if int(start) != start or not 1 <= int(start) <= timesteps:
-            raise ValueError(f'start={start} must be an integer level in [1, timesteps={timesteps}]')
-        start = int(start)
+        timesteps, start = self._checked_start(timesteps, start)
         device = pocket['x'].device
-        n_samples = len(pocket['size'])
-        sizes = pocket['size'].detach().to('cpu', torch.int64).numpy()
-        nph = phar['size'].detach().to('cpu', torch.int64).numpy()
-        if len(nph) != n_samples:
-            raise ValueError(f'phar has {len(nph)} samples, pocket {n_samples}')
-        for m in (phar['mask'], pocket['mask']):
-            if m.numel() > 1 and bool((m[1:] < m[:-1]).any()):
-                raise ValueError('batch masks must be ascending and contiguous')
-        n_phar = int(nph.sum())
-        fix_x = self._row_mask(fix_coords, 'fix_coords', n_phar, device)
-        fix_h = self._row_mask(fix_types, 'fix_types', n_phar, device)
-        self.refresh_learned_schedule()
-        h = self.dynamics.hip_handle()
-        h.set_layout(nph, sizes)
-        h.set_step_table(timesteps, self.step_table(timesteps))
-        n_steps, n_draws = h.edit_plan(timesteps, start, resamplings, jump_length)
+        sizes, nph = self._phar_pocket_sizes(phar, pocket)
+        fix_x = self._row_mask(fix_coords, 'fix_coords', int(nph.sum()), device)
+        fix_h = self._row_mask(fix_types, 'fix_types', int(nph.sum()), device)
+        h, phar_mask, noise, seed = self._prepare_edit(nph, (nph, sizes), device, timesteps, start, resamplings, jump_length, noise, seed)
         f32 = lambda t: t.detach().to(device, torch.float32).contiguous()
-        if noise is not None:
-            noise = f32(noise)
-            if noise.dim() != 3 or noise.shape[0] < n_draws:
-                raise ValueError(f'noise has shape {tuple(noise.shape)}: this schedule needs {n_draws} draws of [{n_phar}, {3 + self.phar_nf}]')
-        if seed is None:
-            seed = fresh_seed()
-        phar_mask = utils.num_nodes_to_batch_mask(n_samples, torch.as_tensor(nph), device)
         args = (f32(pocket['x']), f32(pocket['one_hot']), f32(phar['x']), f32(phar['one_hot']), fix_x, fix_h)
         run = lambda: h.edit_chain(*args, timesteps, start=start, resamplings=resamplings, jump_length=jump_length, noise=noise,
                                    seed=seed, pocket_ids=pocket_ids, use_graph=self.use_hip_graph)
@@ -474,52 +480,23 @@ class ConditionalDDPM(EnVariationalDiffusion):
         Returns (xh_phar, xh_pocket, phar_mask, pocket_mask, {'energy': [B], 'max_violation': [B]}): the energy and the largest violation
         (A) of the returned sample, held points included at their returned positions."""
         from .. import restraints as rs
-        timesteps = self.T if timesteps is None else int(timesteps)
-        start = timesteps if start is None else start
-        if int(start) != start or not 1 <= int(start) <= timesteps:
-            raise ValueError(f'start={start} must be an integer level in [1, timesteps={timesteps}]')
-        start = int(start)
+        timesteps, start = self._checked_start(timesteps, start)
         device = pocket['x'].device
-        n_samples = len(pocket['size'])
-        sizes = pocket['size'].detach().to('cpu', torch.int64).numpy()
-        nph = phar['size'].detach().to('cpu', torch.int64).numpy()
-        if len(nph) != n_samples:
-            raise ValueError(f'phar has {len(nph)} samples, pocket {n_samples}')
-        for m in (phar['mask'], pocket['mask']):
-            if m.numel() > 1 and bool((m[1:] < m[:-1]).any()):
-                raise ValueError('batch masks must be ascending and contiguous')
-        n_phar = int(nph.sum())
-        fix_x = self._row_mask(fix_coords, 'fix_coords', n_phar, device)
-        fix_h = self._row_mask(fix_types, 'fix_types', n_phar, device)
+        sizes, nph = self._phar_pocket_sizes(phar, pocket)
+        fix_x = self._row_mask(fix_coords, 'fix_coords', int(nph.sum()), device)
+        fix_h = self._row_mask(fix_types, 'fix_types', int(nph.sum()), device)
         rec = rs.records(restraints, nph)
         clash_r, clash_k = rs.clash_pair(clash)
         scale, max_shift, guide_below = rs.check_scalars(scale, rs.DEFAULT_MAX_SHIFT if max_shift is None else max_shift, guide_below)
-        self.refresh_learned_schedule()
-        h = self.dynamics.hip_handle()
-        h.set_layout(nph, sizes)
-        h.set_step_table(timesteps, self.step_table(timesteps))
-        h.set_guide_table(timesteps, self.guide_table(timesteps))
-        n_steps, n_draws = h.edit_plan(timesteps, start, resamplings, jump_length)
+        h, phar_mask, noise, seed = self._prepare_edit(nph, (nph, sizes), device, timesteps, start, resamplings, jump_length, noise, seed,
+                                                       guide=True)
         f32 = lambda t: t.detach().to(device, torch.float32).contiguous()
-        if noise is not None:
-            noise = f32(noise)
-            if noise.dim() != 3 or noise.shape[0] < n_draws:
-                raise ValueError(f'noise has shape {tuple(noise.shape)}: this schedule needs {n_draws} draws of [{n_phar}, {3 + self.phar_nf}]')
-        if seed is None:
-            seed = fresh_seed()
-        phar_mask = utils.num_nodes_to_batch_mask(n_samples, torch.as_tensor(nph), device)
         args = (f32(pocket['x']), f32(pocket['one_hot']), f32(phar['x']), f32(phar['one_hot']), fix_x, fix_h)
-        extra = {}
-
-        def run():
-            out = h.restrained_edit_chain(*args, timesteps, start=start, resamplings=resamplings, jump_length=jump_length, restraints=rec,
-                                          clash_radius=clash_r, clash_k=clash_k, scale=scale, max_shift=max_shift, guide_below=guide_below,
-                                          noise=noise, seed=seed, pocket_ids=pocket_ids, use_graph=self.use_hip_graph)
-            extra['energy'] = out[3]
-            return out[:3]
-
-        out = self._finish_chain(h, run, [], 1)
-        info = {'energy': extra['energy'][:, 0].clone(), 'max_violation': extra['energy'][:, 1].clone()}
+        run = lambda: h.restrained_edit_chain(*args, timesteps, start=start, resamplings=resamplings, jump_length=jump_length, restraints=rec,
+                                              clash_radius=clash_r, clash_k=clash_k, scale=scale, max_shift=max_shift,
+                                              guide_below=guide_below, noise=noise, seed=seed, pocket_ids=pocket_ids,
+                                              use_graph=self.use_hip_graph)
+        out, info = self._finish_restrained(h, run, [], 1)
         return out[0], out[1], phar_mask, pocket['mask'], info
 
     @torch.no_grad()
@@ -537,39 +514,18 @@ class ConditionalDDPM(EnVariationalDiffusion):
         With one pocket this is edit, and with nothing held from the prior at resamplings = jump_length = 1 sample_given_pockets,
         both bit for bit.  Returns what sample_given_pockets returns: (xh_phar [Nu, 3+P], [xh_pocket_m], phar_mask, [pocket_mask_m])."""
         pockets, M, G = self._checked_pockets(pockets)
-        timesteps = self.T if timesteps is None else int(timesteps)
-        start = timesteps if start is None else start
-        if int(start) != start or not 1 <= int(start) <= timesteps:
-            raise ValueError(f'start={start} must be an integer level in [1, timesteps={timesteps}]')
-        start = int(start)
-        nph = phar['size'].detach().to('cpu', torch.int64).numpy().reshape(-1)
-        if len(nph) != G:
-            raise ValueError(f'phar has {len(nph)} samples, pocket {G}')
-        pm = phar['mask']
-        if pm.numel() > 1 and bool((pm[1:] < pm[:-1]).any()):
-            raise ValueError('batch masks must be ascending and contiguous')
+        timesteps, start = self._checked_start(timesteps, start)
+        nph = self._group_phar_sizes(phar, G)
         w = self.group_weights(weights, G, M)
         device = pockets[0]['x'].device
         n_phar = int(nph.sum())
         fix_x = self._row_mask(fix_coords, 'fix_coords', n_phar, device)
         fix_h = self._row_mask(fix_types, 'fix_types', n_phar, device)
-        f32 = lambda t: t.detach().to(device, torch.float32).contiguous()
-        if tuple(phar['x'].shape) != (n_phar, self.n_dims) or tuple(phar['one_hot'].shape) != (n_phar, self.phar_nf):
-            raise ValueError(f"phar x / one_hot have shapes {tuple(phar['x'].shape)} / {tuple(phar['one_hot'].shape)}: expected "
-                             f'[{n_phar}, {self.n_dims}] / [{n_phar}, {self.phar_nf}] (sum(size) rows)')
+        self._check_phar_rows(phar, n_phar)
         sizes, rows, px, poh = self._member_layout(pockets, M, G)
-        self.refresh_learned_schedule()
-        h = self.dynamics.hip_handle()
-        h.set_layout(np.repeat(nph, M), sizes.reshape(-1))
-        h.set_step_table(timesteps, self.step_table(timesteps))
-        n_steps, n_draws = h.edit_plan(timesteps, start, resamplings, jump_length)
-        if noise is not None:
-            noise = f32(noise)
-            if noise.dim() != 3 or noise.shape[0] < n_draws:
-                raise ValueError(f'noise has shape {tuple(noise.shape)}: this schedule needs {n_draws} draws of [{n_phar}, {3 + self.phar_nf}]')
-        if seed is None:
-            seed = fresh_seed()
-        phar_mask = utils.num_nodes_to_batch_mask(G, torch.as_tensor(nph), device)
+        h, phar_mask, noise, seed = self._prepare_edit(nph, (np.repeat(nph, M), sizes.reshape(-1)), device, timesteps, start, resamplings,
+                                                       jump_length, noise, seed)
+        f32 = lambda t: t.detach().to(device, torch.float32).contiguous()
         args = (px, poh, [M] * G, w.reshape(-1), f32(phar['x']), f32(phar['one_hot']), fix_x, fix_h)
         run = lambda: h.multi_edit_chain(*args, timesteps, start=start, resamplings=resamplings, jump_length=jump_length, noise=noise,
                                          seed=seed, group_ids=group_ids, use_graph=self.use_hip_graph)
@@ -604,21 +560,9 @@ class ConditionalDDPM(EnVariationalDiffusion):
             raise ValueError(f'repeats={repeats} must be >= 1')
         device = pocket['x'].device
         n_samples = len(pocket['size'])
-        sizes = pocket['size'].detach().to('cpu', torch.int64).numpy()
-        nph = phar['size'].detach().to('cpu', torch.int64).numpy()
-        if len(nph) != n_samples:
-            raise ValueError(f'phar has {len(nph)} samples, pocket {n_samples}')
-        for m in (phar['mask'], pocket['mask']):
-            if m.numel() > 1 and bool((m[1:] < m[:-1]).any()):
-                raise ValueError('batch masks must be ascending and contiguous')
-        n_phar, ld = int(nph.sum()), self.n_dims + self.phar_nf
+        sizes, nph = self._phar_pocket_sizes(phar, pocket)
         f32 = lambda t: t.detach().to(device, torch.float32).contiguous()
-        if noise is not None:
-            noise = f32(noise)
-            if noise.dim() == 4:
-                noise = noise.reshape(-1, noise.shape[2], noise.shape[3])
-            if tuple(noise.shape) != (R * (K + 1), n_phar, ld):
-                raise ValueError(f'noise has shape {tuple(noise.shape)}: {R} x {K + 1} levels need [{R * (K + 1)}, {n_phar}, {ld}]')
+        noise = self._level_noise(noise, R, K, int(nph.sum()), device)
         self.refresh_learned_schedule()
         gamma = np.asarray(self.gamma_table_host(), dtype=np.float32)
         log_pn = self.size_distribution._table(1, torch.device('cpu')).detach().to(torch.float32).numpy()
@@ -674,25 +618,12 @@ class ConditionalDDPM(EnVariationalDiffusion):
         R = int(repeats)
         if R < 1:
             raise ValueError(f'repeats={repeats} must be >= 1')
-        nph = phar['size'].detach().to('cpu', torch.int64).numpy().reshape(-1)
-        if len(nph) != G:
-            raise ValueError(f'phar has {len(nph)} samples, pocket {G}')
-        pm = phar['mask']
-        if pm.numel() > 1 and bool((pm[1:] < pm[:-1]).any()):
-            raise ValueError('batch masks must be ascending and contiguous')
+        nph = self._group_phar_sizes(phar, G)
         w = self.group_weights(weights, G, M)
         device = pockets[0]['x'].device
-        n_phar, ld = int(nph.sum()), self.n_dims + self.phar_nf
         f32 = lambda t: t.detach().to(device, torch.float32).contiguous()
-        if tuple(phar['x'].shape) != (n_phar, self.n_dims) or tuple(phar['one_hot'].shape) != (n_phar, self.phar_nf):
-            raise ValueError(f"phar x / one_hot have shapes {tuple(phar['x'].shape)} / {tuple(phar['one_hot'].shape)}: expected "
-                             f'[{n_phar}, {self.n_dims}] / [{n_phar}, {self.phar_nf}] (sum(size) rows)')
-        if noise is not None:
-            noise = f32(noise)
-            if noise.dim() == 4:
-                noise = noise.reshape(-1, noise.shape[2], noise.shape[3])
-            if tuple(noise.shape) != (R * (K + 1), n_phar, ld):
-                raise ValueError(f'noise has shape {tuple(noise.shape)}: {R} x {K + 1} levels need [{R * (K + 1)}, {n_phar}, {ld}]')
+        self._check_phar_rows(phar, int(nph.sum()))
+        noise = self._level_noise(noise, R, K, int(nph.sum()), device)
         sizes, rows, px, poh = self._member_layout(pockets, M, G)
         self.refresh_learned_schedule()
         gamma = np.asarray(self.gamma_table_host(), dtype=np.float32)

@@ -340,23 +340,78 @@ class Handle:
         assert a.shape == (K + 1, 4)
         self._check(self.lib.cmdgen_set_step_table(self.h, K, a.ctypes.data_as(C.c_void_p)), 'cmdgen_set_step_table')
 
+    # what the *_chain methods below share: each is its shape checks, these helpers, the one lib call and the return tuple
+    @staticmethod
+    def _seed(seed: int):
+        return C.c_uint64(seed & (2 ** 64 - 1))
+
+    @staticmethod
+    def _noise_arg(noise):
+        """(pointer, rows) of an injected noise tensor whose schedule the library checks the rows against (None: device draws)."""
+        return _ptr(noise), int(noise.shape[0]) if noise is not None else 0
+
+    def _check_draws(self, noise, rows: int):
+        """noise: None or a [n_draws, rows, 3+P] device tensor."""
+        if noise is not None:
+            self._check_dev(noise)
+            assert noise.dim() == 3 and tuple(noise.shape[1:]) == (rows, 3 + self.cfg['phar_nf']), noise.shape
+
+    def _chain_outputs(self, rows: int, steps: int, want_steps: bool, dev):
+        """-> xh_phar [rows, 3+P], xh_pocket [Np, 3+R], z_steps [steps, rows, 3+P], p_steps [steps, Np, 3] (the last two None without
+        want_steps; p_steps is also left in last_pocket_steps)."""
+        import torch
+        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
+        xh_phar = torch.empty((rows, 3 + P), dtype=torch.float32, device=dev)
+        xh_pocket = torch.empty((self.n_pocket, 3 + R), dtype=torch.float32, device=dev)
+        z_steps = torch.empty((steps, rows, 3 + P), dtype=torch.float32, device=dev) if want_steps else None
+        p_steps = torch.empty((steps, self.n_pocket, 3), dtype=torch.float32, device=dev) if want_steps else None
+        self.last_pocket_steps = p_steps
+        return xh_phar, xh_pocket, z_steps, p_steps
+
+    def _group_args(self, group_sizes, weights, group_ids):
+        """-> (sizes int64 array, weights float32 array, the group ids' pointer or None, n_unique = one copy of the phar rows per group)."""
+        sizes = np.ascontiguousarray(np.asarray(group_sizes, dtype=np.int64))
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32))
+        assert sizes.ndim == 1 and len(sizes) >= 1 and w.shape == (self.batch,), (sizes.shape, w.shape, self.batch)
+        # one copy of the rows per group: n_phar of every group's first member (the library checks the grouping itself; a grouping
+        # it will refuse only has to give SOME buffer size here)
+        firsts = np.minimum(np.concatenate([[0], np.cumsum(sizes)[:-1]]), self.batch - 1)
+        n_unique = int(self.num_phar_host[firsts].sum())
+        ids = None
+        if group_ids is not None:
+            ids_arr = np.ascontiguousarray(np.asarray(group_ids, dtype=np.int64))
+            assert len(ids_arr) == len(sizes)
+            ids = ids_arr.ctypes.data_as(_i64p)
+        return sizes, w, ids, n_unique
+
+    @staticmethod
+    def _level_args(t_levels, level_coef):
+        """-> (levels int32 array, level_coef float32 array [n + 1, 2] or None)."""
+        lv = np.ascontiguousarray(np.asarray(t_levels, dtype=np.int32).reshape(-1))
+        coef = None
+        if level_coef is not None:
+            coef = np.ascontiguousarray(level_coef, dtype=np.float32)
+            assert coef.shape == (len(lv) + 1, 2), coef.shape
+        return lv, coef
+
+    @staticmethod
+    def _restraint_arg(restraints):
+        """(pointer, count) of a RESTRAINT_DTYPE array (restraint_records) or None."""
+        rec = np.zeros(0, dtype=RESTRAINT_DTYPE) if restraints is None else np.ascontiguousarray(restraints, dtype=RESTRAINT_DTYPE)
+        assert rec.ndim == 1
+        return rec.ctypes.data_as(C.c_void_p) if len(rec) else None, len(rec)
+
     def sample_chain(self, pocket_x, pocket_onehot, timesteps: int, noise=None, seed: int = 0,
                      pocket_ids: Optional[Sequence[int]] = None, want_steps: bool = False,
                      use_graph: bool = True):
-        import torch
         P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
-        dev = pocket_x.device
         self._check_dev(pocket_x, (self.n_pocket, 3))
         self._check_dev(pocket_onehot, (self.n_pocket, R))
         if noise is not None:
             self._check_dev(noise, (timesteps + 2, self.n_phar, 3 + P))
-        xh_phar = torch.empty((self.n_phar, 3 + P), dtype=torch.float32, device=dev)
-        xh_pocket = torch.empty((self.n_pocket, 3 + R), dtype=torch.float32, device=dev)
-        z_steps = torch.empty((timesteps, self.n_phar, 3 + P), dtype=torch.float32, device=dev) if want_steps else None
-        p_steps = torch.empty((timesteps, self.n_pocket, 3), dtype=torch.float32, device=dev) if want_steps else None
-        self.last_pocket_steps = p_steps
+        xh_phar, xh_pocket, z_steps, p_steps = self._chain_outputs(self.n_phar, timesteps, want_steps, pocket_x.device)
         self._check(self.lib.cmdgen_sample_chain(
-            self.h, _ptr(pocket_x), _ptr(pocket_onehot), int(timesteps), _ptr(noise), C.c_uint64(seed & (2 ** 64 - 1)),
+            self.h, _ptr(pocket_x), _ptr(pocket_onehot), int(timesteps), _ptr(noise), self._seed(seed),
             self._pocket_ids(pocket_ids), _ptr(xh_phar), _ptr(xh_pocket),
             _ptr(z_steps), _ptr(p_steps), int(bool(use_graph)), self._stream()), 'cmdgen_sample_chain')
         return xh_phar, xh_pocket, z_steps
@@ -379,19 +434,14 @@ class Handle:
         self._check_dev(pocket_onehot, (self.n_pocket, R))
         if noise is not None:
             self._check_dev(noise, (timesteps + 2, self.n_phar, 3 + P))
-        rec = np.zeros(0, dtype=RESTRAINT_DTYPE) if restraints is None else np.ascontiguousarray(restraints, dtype=RESTRAINT_DTYPE)
-        assert rec.ndim == 1
-        xh_phar = torch.empty((self.n_phar, 3 + P), dtype=torch.float32, device=dev)
-        xh_pocket = torch.empty((self.n_pocket, 3 + R), dtype=torch.float32, device=dev)
-        z_steps = torch.empty((timesteps, self.n_phar, 3 + P), dtype=torch.float32, device=dev) if want_steps else None
-        p_steps = torch.empty((timesteps, self.n_pocket, 3), dtype=torch.float32, device=dev) if want_steps else None
+        rec, n_rec = self._restraint_arg(restraints)
+        xh_phar, xh_pocket, z_steps, p_steps = self._chain_outputs(self.n_phar, timesteps, want_steps, dev)
         energy = torch.empty((self.batch, 2), dtype=torch.float32, device=dev)
         op_energy = torch.empty((timesteps, self.batch), dtype=torch.float32, device=dev) if want_steps else None
-        self.last_pocket_steps = p_steps
         self._check(self.lib.cmdgen_restrained_chain(
-            self.h, _ptr(pocket_x), _ptr(pocket_onehot), int(timesteps), rec.ctypes.data_as(C.c_void_p) if len(rec) else None, len(rec),
+            self.h, _ptr(pocket_x), _ptr(pocket_onehot), int(timesteps), rec, n_rec,
             float(clash_radius), float(clash_k), float(scale), float(max_shift), float(guide_below),
-            _ptr(noise), C.c_uint64(seed & (2 ** 64 - 1)), self._pocket_ids(pocket_ids), _ptr(xh_phar), _ptr(xh_pocket),
+            _ptr(noise), self._seed(seed), self._pocket_ids(pocket_ids), _ptr(xh_phar), _ptr(xh_pocket),
             _ptr(z_steps), _ptr(p_steps), _ptr(energy), _ptr(op_energy), int(bool(use_graph)), self._stream()), 'cmdgen_restrained_chain')
         return xh_phar, xh_pocket, z_steps, energy, op_energy
 
@@ -404,33 +454,16 @@ class Handle:
         group's summing to 1).  noise [K+2, Nu, 3+P] or None, Nu = one copy of the phar rows per group; group_ids: the global group ids
         of the Philox draws (None: 0 .. groups - 1).  -> (xh_phar [Nu, 3+P], xh_pocket [Np, 3+R], z_steps [K, Nu, 3+P] or None) like
         sample_chain; with want_steps every member's pocket after every op is left in last_pocket_steps."""
-        import torch
         P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
-        dev = pocket_x.device
         self._check_dev(pocket_x, (self.n_pocket, 3))
         self._check_dev(pocket_onehot, (self.n_pocket, R))
-        sizes = np.ascontiguousarray(np.asarray(group_sizes, dtype=np.int64))
-        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32))
-        assert sizes.ndim == 1 and len(sizes) >= 1 and w.shape == (self.batch,), (sizes.shape, w.shape, self.batch)
-        # one copy of the rows per group: n_phar of every group's first member (the library checks the grouping itself; a grouping
-        # it will refuse only has to give SOME buffer size here)
-        firsts = np.minimum(np.concatenate([[0], np.cumsum(sizes)[:-1]]), self.batch - 1)
-        n_unique = int(self.num_phar_host[firsts].sum())
+        sizes, w, ids, n_unique = self._group_args(group_sizes, weights, group_ids)
         if noise is not None:
             self._check_dev(noise, (timesteps + 2, n_unique, 3 + P))
-        ids = None
-        if group_ids is not None:
-            ids_arr = np.ascontiguousarray(np.asarray(group_ids, dtype=np.int64))
-            assert len(ids_arr) == len(sizes)
-            ids = ids_arr.ctypes.data_as(_i64p)
-        xh_phar = torch.empty((n_unique, 3 + P), dtype=torch.float32, device=dev)
-        xh_pocket = torch.empty((self.n_pocket, 3 + R), dtype=torch.float32, device=dev)
-        z_steps = torch.empty((timesteps, n_unique, 3 + P), dtype=torch.float32, device=dev) if want_steps else None
-        p_steps = torch.empty((timesteps, self.n_pocket, 3), dtype=torch.float32, device=dev) if want_steps else None
-        self.last_pocket_steps = p_steps
+        xh_phar, xh_pocket, z_steps, p_steps = self._chain_outputs(n_unique, timesteps, want_steps, pocket_x.device)
         self._check(self.lib.cmdgen_multi_pocket_chain(
             self.h, _ptr(pocket_x), _ptr(pocket_onehot), len(sizes), sizes.ctypes.data_as(_i64p), w.ctypes.data_as(C.c_void_p),
-            int(timesteps), _ptr(noise), C.c_uint64(seed & (2 ** 64 - 1)), ids, _ptr(xh_phar), _ptr(xh_pocket),
+            int(timesteps), _ptr(noise), self._seed(seed), ids, _ptr(xh_phar), _ptr(xh_pocket),
             _ptr(z_steps), _ptr(p_steps), int(bool(use_graph)), self._stream()), 'cmdgen_multi_pocket_chain')
         return xh_phar, xh_pocket, z_steps
 
@@ -467,9 +500,8 @@ class Handle:
         xh_pocket = torch.empty((self.n_pocket, 3 + R), dtype=torch.float32, device=dev)
         z_steps = torch.empty((n_steps, row), dtype=torch.float32, device=dev) if want_steps else None
         self._check(self.lib.cmdgen_joint_chain(
-            self.h, *[_ptr(t) for t in ptrs], int(timesteps), int(resamplings), int(jump_length), _ptr(noise),
-            int(noise.shape[0]) if noise is not None else 0, C.c_uint64(seed & (2 ** 64 - 1)),
-            self._pocket_ids(pocket_ids), _ptr(xh_phar), _ptr(xh_pocket), _ptr(z_steps),
+            self.h, *[_ptr(t) for t in ptrs], int(timesteps), int(resamplings), int(jump_length), *self._noise_arg(noise),
+            self._seed(seed), self._pocket_ids(pocket_ids), _ptr(xh_phar), _ptr(xh_pocket), _ptr(z_steps),
             int(bool(use_graph)), self._stream()), 'cmdgen_joint_chain')
         return xh_phar, xh_pocket, z_steps
 
@@ -483,30 +515,12 @@ class Handle:
     def inpaint_chain(self, pocket_x, pocket_onehot, phar_x, phar_onehot, phar_fixed, timesteps: int, resamplings: int = 1,
                       jump_length: int = 1, noise=None, seed: int = 0, pocket_ids: Optional[Sequence[int]] = None,
                       want_steps: bool = False, use_graph: bool = True):
-        """ConditionalDDPM.inpaint on the device (cmdgen_inpaint_chain).  Raw pocket_x [Np,3], pocket_onehot [Np,R], phar_x [Nl,3],
-        phar_onehot [Nl,P] and phar_fixed float [Nl] device tensors; noise [n_draws, Nl, 3+P] or None.  -> (xh_phar, xh_pocket, z_steps);
-        with want_steps the pocket after every op is left in last_pocket_steps, as sample_chain does."""
-        import torch
-        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
-        shapes = [(self.n_pocket, 3), (self.n_pocket, R), (self.n_phar, 3), (self.n_phar, P), (self.n_phar,)]
-        for t, sh in zip((pocket_x, pocket_onehot, phar_x, phar_onehot, phar_fixed), shapes):
-            self._check_dev(t, sh)
-        n_steps, n_draws = self.inpaint_plan(timesteps, resamplings, jump_length)
-        if noise is not None:
-            self._check_dev(noise)
-            assert noise.dim() == 3 and tuple(noise.shape[1:]) == (self.n_phar, 3 + P), noise.shape
-        dev = pocket_x.device
-        xh_phar = torch.empty((self.n_phar, 3 + P), dtype=torch.float32, device=dev)
-        xh_pocket = torch.empty((self.n_pocket, 3 + R), dtype=torch.float32, device=dev)
-        z_steps = torch.empty((n_steps, self.n_phar, 3 + P), dtype=torch.float32, device=dev) if want_steps else None
-        p_steps = torch.empty((n_steps, self.n_pocket, 3), dtype=torch.float32, device=dev) if want_steps else None
-        self.last_pocket_steps = p_steps
-        self._check(self.lib.cmdgen_inpaint_chain(
-            self.h, _ptr(pocket_x), _ptr(pocket_onehot), _ptr(phar_x), _ptr(phar_onehot), _ptr(phar_fixed), int(timesteps),
-            int(resamplings), int(jump_length), _ptr(noise), int(noise.shape[0]) if noise is not None else 0,
-            C.c_uint64(seed & (2 ** 64 - 1)), self._pocket_ids(pocket_ids), _ptr(xh_phar),
-            _ptr(xh_pocket), _ptr(z_steps), _ptr(p_steps), int(bool(use_graph)), self._stream()), 'cmdgen_inpaint_chain')
-        return xh_phar, xh_pocket, z_steps
+        """ConditionalDDPM.inpaint on the device: the edit chain with both masks equal and start = timesteps, as cmdgen_inpaint_chain is
+        in the library.  Raw pocket_x [Np,3], pocket_onehot [Np,R], phar_x [Nl,3], phar_onehot [Nl,P] and phar_fixed float [Nl] device
+        tensors; noise [n_draws, Nl, 3+P] or None.  -> (xh_phar, xh_pocket, z_steps); with want_steps the pocket after every op is left
+        in last_pocket_steps, as sample_chain does."""
+        return self.edit_chain(pocket_x, pocket_onehot, phar_x, phar_onehot, phar_fixed, phar_fixed, timesteps, timesteps, resamplings,
+                               jump_length, noise, seed, pocket_ids, want_steps, use_graph)
 
     def edit_plan(self, timesteps: int, start: Optional[int] = None, resamplings: int = 1, jump_length: int = 1):
         """(denoising ops, noise draws) of an edit chain that starts at level `start` (None: timesteps) - cmdgen_edit_plan."""
@@ -516,33 +530,28 @@ class Handle:
                                               C.byref(b)), 'cmdgen_edit_plan')
         return a.value, b.value
 
+    def _check_edit_inputs(self, pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h, rows: int):
+        """the edit kinds' device inputs: the pocket, then `rows` given phar rows with their two masks"""
+        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
+        shapes = [(self.n_pocket, 3), (self.n_pocket, R), (rows, 3), (rows, P), (rows,), (rows,)]
+        for t, sh in zip((pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h), shapes):
+            self._check_dev(t, sh)
+
     def edit_chain(self, pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h, timesteps: int, start: Optional[int] = None,
                    resamplings: int = 1, jump_length: int = 1, noise=None, seed: int = 0, pocket_ids: Optional[Sequence[int]] = None,
                    want_steps: bool = False, use_graph: bool = True):
         """ConditionalDDPM.edit on the device (cmdgen_edit_chain): inpaint_chain with a mask for the x columns (fix_x) and one for the
         feature columns (fix_h), float [Nl] device tensors, and the level the chain starts from (None: timesteps, the prior).
         -> (xh_phar, xh_pocket, z_steps); with want_steps the pocket after every op is left in last_pocket_steps."""
-        import torch
-        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
         start = timesteps if start is None else start
-        shapes = [(self.n_pocket, 3), (self.n_pocket, R), (self.n_phar, 3), (self.n_phar, P), (self.n_phar,), (self.n_phar,)]
-        for t, sh in zip((pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h), shapes):
-            self._check_dev(t, sh)
+        self._check_edit_inputs(pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h, self.n_phar)
         n_steps, n_draws = self.edit_plan(timesteps, start, resamplings, jump_length)
-        if noise is not None:
-            self._check_dev(noise)
-            assert noise.dim() == 3 and tuple(noise.shape[1:]) == (self.n_phar, 3 + P), noise.shape
-        dev = pocket_x.device
-        xh_phar = torch.empty((self.n_phar, 3 + P), dtype=torch.float32, device=dev)
-        xh_pocket = torch.empty((self.n_pocket, 3 + R), dtype=torch.float32, device=dev)
-        z_steps = torch.empty((n_steps, self.n_phar, 3 + P), dtype=torch.float32, device=dev) if want_steps else None
-        p_steps = torch.empty((n_steps, self.n_pocket, 3), dtype=torch.float32, device=dev) if want_steps else None
-        self.last_pocket_steps = p_steps
+        self._check_draws(noise, self.n_phar)
+        xh_phar, xh_pocket, z_steps, p_steps = self._chain_outputs(self.n_phar, n_steps, want_steps, pocket_x.device)
         self._check(self.lib.cmdgen_edit_chain(
             self.h, _ptr(pocket_x), _ptr(pocket_onehot), _ptr(phar_x), _ptr(phar_onehot), _ptr(fix_x), _ptr(fix_h), int(timesteps),
-            int(start), int(resamplings), int(jump_length), _ptr(noise), int(noise.shape[0]) if noise is not None else 0,
-            C.c_uint64(seed & (2 ** 64 - 1)), self._pocket_ids(pocket_ids), _ptr(xh_phar),
-            _ptr(xh_pocket), _ptr(z_steps), _ptr(p_steps), int(bool(use_graph)), self._stream()), 'cmdgen_edit_chain')
+            int(start), int(resamplings), int(jump_length), *self._noise_arg(noise), self._seed(seed), self._pocket_ids(pocket_ids),
+            _ptr(xh_phar), _ptr(xh_pocket), _ptr(z_steps), _ptr(p_steps), int(bool(use_graph)), self._stream()), 'cmdgen_edit_chain')
         return xh_phar, xh_pocket, z_steps
 
     def restrained_edit_chain(self, pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h, timesteps: int, start: Optional[int] = None,
@@ -555,30 +564,19 @@ class Handle:
         -> (xh_phar, xh_pocket, z_steps, energy [B, 2] (E and the largest violation in A of the output), op_energy [n_steps, B] or None);
         with want_steps the pocket after every op is left in last_pocket_steps."""
         import torch
-        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
         start = timesteps if start is None else start
-        shapes = [(self.n_pocket, 3), (self.n_pocket, R), (self.n_phar, 3), (self.n_phar, P), (self.n_phar,), (self.n_phar,)]
-        for t, sh in zip((pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h), shapes):
-            self._check_dev(t, sh)
+        self._check_edit_inputs(pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h, self.n_phar)
         n_steps, n_draws = self.edit_plan(timesteps, start, resamplings, jump_length)
-        if noise is not None:
-            self._check_dev(noise)
-            assert noise.dim() == 3 and tuple(noise.shape[1:]) == (self.n_phar, 3 + P), noise.shape
-        rec = np.zeros(0, dtype=RESTRAINT_DTYPE) if restraints is None else np.ascontiguousarray(restraints, dtype=RESTRAINT_DTYPE)
-        assert rec.ndim == 1
+        self._check_draws(noise, self.n_phar)
+        rec, n_rec = self._restraint_arg(restraints)
         dev = pocket_x.device
-        xh_phar = torch.empty((self.n_phar, 3 + P), dtype=torch.float32, device=dev)
-        xh_pocket = torch.empty((self.n_pocket, 3 + R), dtype=torch.float32, device=dev)
-        z_steps = torch.empty((n_steps, self.n_phar, 3 + P), dtype=torch.float32, device=dev) if want_steps else None
-        p_steps = torch.empty((n_steps, self.n_pocket, 3), dtype=torch.float32, device=dev) if want_steps else None
+        xh_phar, xh_pocket, z_steps, p_steps = self._chain_outputs(self.n_phar, n_steps, want_steps, dev)
         energy = torch.empty((self.batch, 2), dtype=torch.float32, device=dev)
         op_energy = torch.empty((n_steps, self.batch), dtype=torch.float32, device=dev) if want_steps else None
-        self.last_pocket_steps = p_steps
         self._check(self.lib.cmdgen_restrained_edit_chain(
             self.h, _ptr(pocket_x), _ptr(pocket_onehot), _ptr(phar_x), _ptr(phar_onehot), _ptr(fix_x), _ptr(fix_h), int(timesteps),
-            int(start), int(resamplings), int(jump_length), _ptr(noise), int(noise.shape[0]) if noise is not None else 0,
-            C.c_uint64(seed & (2 ** 64 - 1)), self._pocket_ids(pocket_ids), _ptr(xh_phar), _ptr(xh_pocket), _ptr(z_steps), _ptr(p_steps),
-            rec.ctypes.data_as(C.c_void_p) if len(rec) else None, len(rec), float(clash_radius), float(clash_k), float(scale),
+            int(start), int(resamplings), int(jump_length), *self._noise_arg(noise), self._seed(seed), self._pocket_ids(pocket_ids),
+            _ptr(xh_phar), _ptr(xh_pocket), _ptr(z_steps), _ptr(p_steps), rec, n_rec, float(clash_radius), float(clash_k), float(scale),
             float(max_shift), float(guide_below), _ptr(energy), _ptr(op_energy), int(bool(use_graph)), self._stream()),
             'cmdgen_restrained_edit_chain')
         return xh_phar, xh_pocket, z_steps, energy, op_energy
@@ -591,36 +589,16 @@ class Handle:
         of the rows per group), in the pockets' common frame; start, resamplings, jump_length as edit_chain; noise [n_draws, Nu, 3+P]
         (edit_plan) or None.  -> (xh_phar [Nu, 3+P], xh_pocket [Np, 3+R], z_steps [n_steps, Nu, 3+P] or None); with want_steps every
         member's pocket after every op is left in last_pocket_steps."""
-        import torch
-        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
-        dev = pocket_x.device
         start = timesteps if start is None else start
-        sizes = np.ascontiguousarray(np.asarray(group_sizes, dtype=np.int64))
-        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32))
-        assert sizes.ndim == 1 and len(sizes) >= 1 and w.shape == (self.batch,), (sizes.shape, w.shape, self.batch)
-        firsts = np.minimum(np.concatenate([[0], np.cumsum(sizes)[:-1]]), self.batch - 1)      # (as multi_pocket_chain)
-        n_unique = int(self.num_phar_host[firsts].sum())
-        shapes = [(self.n_pocket, 3), (self.n_pocket, R), (n_unique, 3), (n_unique, P), (n_unique,), (n_unique,)]
-        for t, sh in zip((pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h), shapes):
-            self._check_dev(t, sh)
+        sizes, w, ids, n_unique = self._group_args(group_sizes, weights, group_ids)
+        self._check_edit_inputs(pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h, n_unique)
         n_steps, n_draws = self.edit_plan(timesteps, start, resamplings, jump_length)
-        if noise is not None:
-            self._check_dev(noise)
-            assert noise.dim() == 3 and tuple(noise.shape[1:]) == (n_unique, 3 + P), noise.shape
-        ids = None
-        if group_ids is not None:
-            ids_arr = np.ascontiguousarray(np.asarray(group_ids, dtype=np.int64))
-            assert len(ids_arr) == len(sizes)
-            ids = ids_arr.ctypes.data_as(_i64p)
-        xh_phar = torch.empty((n_unique, 3 + P), dtype=torch.float32, device=dev)
-        xh_pocket = torch.empty((self.n_pocket, 3 + R), dtype=torch.float32, device=dev)
-        z_steps = torch.empty((n_steps, n_unique, 3 + P), dtype=torch.float32, device=dev) if want_steps else None
-        p_steps = torch.empty((n_steps, self.n_pocket, 3), dtype=torch.float32, device=dev) if want_steps else None
-        self.last_pocket_steps = p_steps
+        self._check_draws(noise, n_unique)
+        xh_phar, xh_pocket, z_steps, p_steps = self._chain_outputs(n_unique, n_steps, want_steps, pocket_x.device)
         self._check(self.lib.cmdgen_multi_edit_chain(
             self.h, _ptr(pocket_x), _ptr(pocket_onehot), len(sizes), sizes.ctypes.data_as(_i64p), w.ctypes.data_as(C.c_void_p),
             _ptr(phar_x), _ptr(phar_onehot), _ptr(fix_x), _ptr(fix_h), int(timesteps), int(start), int(resamplings), int(jump_length),
-            _ptr(noise), int(noise.shape[0]) if noise is not None else 0, C.c_uint64(seed & (2 ** 64 - 1)), ids, _ptr(xh_phar),
+            *self._noise_arg(noise), self._seed(seed), ids, _ptr(xh_phar),
             _ptr(xh_pocket), _ptr(z_steps), _ptr(p_steps), int(bool(use_graph)), self._stream()), 'cmdgen_multi_edit_chain')
         return xh_phar, xh_pocket, z_steps
 
@@ -637,12 +615,8 @@ class Handle:
         shapes = [(self.n_phar, 3), (self.n_phar, P), (self.n_pocket, 3), (self.n_pocket, R)]
         for t, sh in zip((phar_x, phar_onehot, pocket_x, pocket_onehot), shapes):
             self._check_dev(t, sh)
-        lv = np.ascontiguousarray(np.asarray(t_levels, dtype=np.int32).reshape(-1))
+        lv, coef = self._level_args(t_levels, level_coef)
         n = len(lv)
-        coef = None
-        if level_coef is not None:
-            coef = np.ascontiguousarray(level_coef, dtype=np.float32)
-            assert coef.shape == (n + 1, 2), coef.shape
         if noise is not None:
             self._check_dev(noise, (n, self.n_phar, 3 + P))
         dev = phar_x.device
@@ -650,7 +624,7 @@ class Handle:
         kl = torch.zeros((self.batch, 2), dtype=torch.float32, device=dev)
         self._check(self.lib.cmdgen_score_chain(
             self.h, _ptr(phar_x), _ptr(phar_onehot), _ptr(pocket_x), _ptr(pocket_onehot), n, lv.ctypes.data_as(C.c_void_p),
-            coef.ctypes.data_as(C.c_void_p) if coef is not None else None, _ptr(noise), C.c_uint64(seed & (2 ** 64 - 1)),
+            coef.ctypes.data_as(C.c_void_p) if coef is not None else None, _ptr(noise), self._seed(seed),
             self._pocket_ids(pocket_ids), _ptr(terms), _ptr(kl), int(bool(use_graph)), self._stream()), 'cmdgen_score_chain')
         return terms, kl
 
@@ -663,27 +637,14 @@ class Handle:
         -> (group_terms [n_levels, groups, SC_COLS], member_terms [n_levels, batch, SC_COLS] or None, kl_sums [groups, 2])."""
         import torch
         P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
-        sizes = np.ascontiguousarray(np.asarray(group_sizes, dtype=np.int64))
-        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32))
-        assert sizes.ndim == 1 and len(sizes) >= 1 and w.shape == (self.batch,), (sizes.shape, w.shape, self.batch)
-        firsts = np.minimum(np.concatenate([[0], np.cumsum(sizes)[:-1]]), self.batch - 1)      # (as multi_pocket_chain)
-        n_unique = int(self.num_phar_host[firsts].sum())
+        sizes, w, ids, n_unique = self._group_args(group_sizes, weights, group_ids)
         shapes = [(n_unique, 3), (n_unique, P), (self.n_pocket, 3), (self.n_pocket, R)]
         for t, sh in zip((phar_x, phar_onehot, pocket_x, pocket_onehot), shapes):
             self._check_dev(t, sh)
-        lv = np.ascontiguousarray(np.asarray(t_levels, dtype=np.int32).reshape(-1))
+        lv, coef = self._level_args(t_levels, level_coef)
         n = len(lv)
-        coef = None
-        if level_coef is not None:
-            coef = np.ascontiguousarray(level_coef, dtype=np.float32)
-            assert coef.shape == (n + 1, 2), coef.shape
         if noise is not None:
             self._check_dev(noise, (n, n_unique, 3 + P))
-        ids = None
-        if group_ids is not None:
-            ids_arr = np.ascontiguousarray(np.asarray(group_ids, dtype=np.int64))
-            assert len(ids_arr) == len(sizes)
-            ids = ids_arr.ctypes.data_as(_i64p)
         dev = phar_x.device
         terms = torch.zeros((n, len(sizes), self.SC_COLS), dtype=torch.float32, device=dev)
         members = torch.zeros((n, self.batch, self.SC_COLS), dtype=torch.float32, device=dev) if want_members else None
@@ -691,7 +652,7 @@ class Handle:
         self._check(self.lib.cmdgen_multi_score_chain(
             self.h, _ptr(phar_x), _ptr(phar_onehot), _ptr(pocket_x), _ptr(pocket_onehot), len(sizes), sizes.ctypes.data_as(_i64p),
             w.ctypes.data_as(C.c_void_p), n, lv.ctypes.data_as(C.c_void_p), coef.ctypes.data_as(C.c_void_p) if coef is not None else None,
-            _ptr(noise), C.c_uint64(seed & (2 ** 64 - 1)), ids, _ptr(terms), _ptr(members), _ptr(kl), int(bool(use_graph)),
+            _ptr(noise), self._seed(seed), ids, _ptr(terms), _ptr(members), _ptr(kl), int(bool(use_graph)),
             self._stream()), 'cmdgen_multi_score_chain')
         return terms, members, kl
 

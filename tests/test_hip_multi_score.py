@@ -342,6 +342,72 @@ def test_the_chain_alternates_with_the_other_chains_on_one_handle():
         assert torch.equal(u, v)
 
 
+def test_all_conditional_chains_alternate_on_one_handle_and_survive_a_layout_change():
+    """Every conditional chain of ConditionalDDPM in turn on one model (the single-pocket ones on the member layout): a second round
+    keeps every captured graph and every bit, the eager round gives the captured bits, and after a round on another layout (one point
+    fewer in group 0) the first layout's round gives its first bits again - every slot was prepared again with nothing stale in it.
+    No evaluation is reset throughout."""
+    K, G, M = 5, 2, 2
+    ddpm = model()
+    ddpm.use_hip_graph = True
+    h = ddpm.dynamics.hip_handle()
+    h.set_option('graph_steps', 2)
+    pb = make_pockets(G * M, 'CA', ragged=True, first_index=9660)
+    pockets = [pocket_dev(pb, [g * M + m for g in range(G)]) for m in range(M)]
+    pocket_m = pocket_dev(pb)
+    centre = [float(v) for v in pb.x[:int(pb.size[0])].mean(axis=0)]
+    position = [{'kind': 'position', 'sample': 0, 'point': 1, 'center': centre, 'radius': 1.0, 'k': 1.0}]
+    distance = [{'kind': 'distance', 'sample': 2, 'points': (0, 3), 'lo': 2.0, 'hi': 4.0, 'k': 1.0}]
+
+    def rounds_for(nph):
+        gr = mp.Groups([M] * G, nph)
+        x, oh = given_for(nph, 9)
+        urow = gr.urow.numpy()
+        phar = {'x': dev(x), 'one_hot': dev(oh), 'size': dev(nph), 'mask': dev(np.repeat(np.arange(G), nph))}
+        phar_m = {'x': dev(x[urow]), 'one_hot': dev(oh[urow]), 'size': dev(gr.member_nph), 'mask': dev(gr.phar_mask.numpy())}
+        nph_m = gr.member_nph
+        fix, fix_m = dev(np.arange(int(nph.sum())) % 2 == 0), dev(np.arange(len(urow)) % 2 == 0)
+
+        def round_():
+            resets = []
+
+            def ran(out):
+                resets.append(ddpm.last_chain_status['nan_resets'])
+                return out
+
+            a = ran(ddpm.sample_given_pocket(pocket_m, nph_m, timesteps=K, seed=31))
+            b = ran(ddpm.sample_restrained(pocket_m, nph_m, position, clash=(2.0, 1.0), timesteps=K, seed=32))
+            c = ran(ddpm.inpaint(phar_m, pocket_m, fix_m, timesteps=K, seed=33))
+            d = ran(ddpm.edit(phar_m, pocket_m, fix_types=fix_m, start=3, timesteps=K, seed=34))
+            e = ran(ddpm.edit_restrained(phar_m, pocket_m, distance, fix_coords=fix_m, start=3, timesteps=K, seed=35))
+            f = ran(ddpm.sample_given_pockets(pockets, nph, weights=[1.0, 3.0], timesteps=K, seed=36))
+            g = ran(ddpm.edit_given_pockets(phar, pockets, fix_types=fix, weights=[1.0, 3.0], timesteps=K, seed=37))
+            s = ran(ddpm.score(phar_m, pocket_m, timesteps=K, seed=38, return_levels=True))
+            t = ran(ddpm.score_given_pockets(phar, pockets, weights=[1.0, 3.0], timesteps=K, seed=39, return_levels=True, return_members=True))
+            assert resets == [0] * 9, resets
+            return [a[0], a[1], b[0], b[4]['energy'], b[4]['max_violation'], c[0], d[0], e[0], e[4]['energy'], f[0], f[1][0], f[1][1], g[0],
+                    s['level_sums'], s['nll'], t['level_sums'], t['member_level_sums'], t['nll']]
+
+        return round_
+
+    round_ = rounds_for(np.array([5, 8], dtype=np.int64))
+    first = round_()
+    graphs = h.query('chain_graphs')
+    assert graphs >= 8
+    second = round_()
+    assert h.query('chain_graphs') == graphs
+    for i, (u, v) in enumerate(zip(first, second)):
+        assert torch.equal(u, v), i
+    ddpm.use_hip_graph = False
+    eager = round_()
+    ddpm.use_hip_graph = True
+    for i, (u, v) in enumerate(zip(first, eager)):
+        assert torch.equal(u, v), i
+    rounds_for(np.array([4, 8], dtype=np.int64))()
+    for i, (u, v) in enumerate(zip(first, round_())):
+        assert torch.equal(u, v), i
+
+
 # ------------------------------------------------------------------------------------------------ 8. the driver
 def test_score_given_pockets_with_repeats_and_members():
     """repeats = 2 is the mean of two single runs with the matching draws; the member entries are score's own for that pocket on the
