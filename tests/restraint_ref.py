@@ -5,184 +5,20 @@ ref_cpu.sample_given_pocket bit for bit given the same draws.
 
 Restraints come as the record array of cmdgen_amd.restraints.records (kind, sample, i, j, c, a, b, k).  A point's gradient terms are
 summed in the definition's order - position, distance and exclusion terms in list order, then pocket atoms in index order - by one
-index_add_ over the term list (ref_cpu.scatter_add walks it in order)."""
-import numpy as np
-import torch
+index_add_ over the term list (ref_cpu.scatter_add walks it in order).
 
-from multi_pocket_ref import pair_margins
-from oracle import ref_cpu
-from oracle.ref_cpu import FLOAT, INT
+It is chain_ref.run_chain with the guide part alone."""
+from chain_ref import (CLASH, DISTANCE, EXCLUSION, KIND_NAMES, POSITION, TINY, _norm, energy_terms, run_chain,      # noqa: F401
+                       touched_samples)
 
-POSITION, DISTANCE, EXCLUSION, CLASH = 0, 1, 2, 3
-KIND_NAMES = ('position', 'distance', 'exclusion', 'clash')
-TINY = 1e-12           # A: a term whose distance is below this contributes the zero vector
-
-
-def _norm(diff):
-    return torch.sqrt((diff ** 2).sum(dim=1))
-
-
-def energy_terms(xhat, q, shift, pm, qm, rec, clash_r, clash_k):
-    """The energy of step 3 at the points xhat [Nl, 3] (A) with pocket atoms q [Np, 3] (A) and the frame shift [B, 3], any float dtype.
-    -> (E [B], g [Nl, 3] = dE / dxhat, largest violation [B], largest violation per kind [4])."""
-    dt = xhat.dtype
-    B, Nl = shift.shape[0], xhat.shape[0]
-    nph = torch.bincount(pm, minlength=B)
-    pbase = torch.cumsum(nph, 0) - nph
-    # one entry per (term, point it acts on): the gradient row, the energy (on one of a distance term's two ends only), the violation
-    t_row, t_g, t_e, t_v, t_kind = [], [], [], [], []
-
-    def push(rows, diff, dist, v, sign, k, count, kind):
-        coef = torch.where(dist >= TINY, sign * (k * v) / dist.clamp(min=TINY), torch.zeros_like(dist))
-        t_row.append(rows); t_g.append(coef[:, None] * diff); t_v.append(v)
-        t_e.append(0.5 * k * (v * v) if count else torch.zeros_like(v))
-        t_kind.append(torch.full_like(rows, kind))
-
-    for r in rec:                                                        # list order
-        b, k = int(r['sample']), float(r['k'])
-        if int(r['kind']) == DISTANCE:
-            i, j = int(pbase[b]) + int(r['i']), int(pbase[b]) + int(r['j'])
-            diff = (xhat[i] - xhat[j])[None, :]
-            dist = _norm(diff)
-            lo, hi = float(r['a']), float(r['b'])
-            v = torch.clamp(torch.maximum(lo - dist, dist - hi), min=0)
-            sign = torch.where(dist < lo, -torch.ones_like(dist), torch.ones_like(dist))
-            push(torch.tensor([i]), diff, dist, v, sign, k, True, DISTANCE)
-            push(torch.tensor([j]), -diff, dist, v, sign, k, False, DISTANCE)
-            continue
-        centre = torch.as_tensor(np.asarray(r['c'], dtype=np.float32)).to(dt) + shift[b]
-        if int(r['kind']) == POSITION:
-            rows = torch.tensor([int(pbase[b]) + int(r['i'])])
-            diff = xhat[rows] - centre
-            dist = _norm(diff)
-            push(rows, diff, dist, torch.clamp(dist - float(r['a']), min=0), torch.ones_like(dist), k, True, POSITION)
-        else:
-            rows = int(pbase[b]) + torch.arange(int(nph[b]))
-            diff = xhat[rows] - centre
-            dist = _norm(diff)
-            push(rows, diff, dist, torch.clamp(float(r['a']) - dist, min=0), -torch.ones_like(dist), k, True, EXCLUSION)
-    if clash_r > 0:                                                      # then the pocket atoms in index order, point by point
-        for b in range(B):
-            rows, atoms = torch.nonzero(pm == b).reshape(-1), torch.nonzero(qm == b).reshape(-1)
-            if len(rows) == 0 or len(atoms) == 0:
-                continue
-            diff = (xhat[rows][:, None, :] - q[atoms][None, :, :]).reshape(-1, 3)
-            dist = _norm(diff)
-            push(rows.repeat_interleave(len(atoms)), diff, dist, torch.clamp(clash_r - dist, min=0), -torch.ones_like(dist), float(clash_k),
-                 True, CLASH)
-    E, g = torch.zeros(B, dtype=dt), torch.zeros((Nl, 3), dtype=dt)
-    vmax, vkind = torch.zeros(B, dtype=dt), torch.zeros(4, dtype=dt)
-    if t_row:
-        rows, kinds, v = torch.cat(t_row), torch.cat(t_kind), torch.cat(t_v)
-        g = ref_cpu.scatter_add(torch.cat(t_g), rows, Nl)
-        E = ref_cpu.scatter_add(torch.cat(t_e), pm[rows], B)
-        for b in range(B):
-            sel = pm[rows] == b
-            if bool(sel.any()):
-                vmax[b] = v[sel].max()
-        for kd in range(4):
-            if bool((kinds == kd).any()):
-                vkind[kd] = v[kinds == kd].max()
-    return E, g, vmax, vkind
-
-
-def touched_samples(rec, B, clash_r):
-    t = np.zeros(B, dtype=bool)
-    if clash_r > 0:
-        t[:] = True
-    for r in rec:
-        t[int(r['sample'])] = True
-    return t
+KEYS = ('xh_phar', 'xh_pocket', 'phar_mask', 'pocket_mask', 'z_steps', 'pocket_steps', 'margins', 'op_energy', 'energy', 'max_violation',
+        'kind_violation', 'clipped', 'unclipped')
 
 
 def restrained_chain(p, cfg, pocket, num_nodes_phar, rec, clash_r=0.0, clash_k=0.0, scale=1.0, max_shift=1.0, guide_below=1.0,
                      timesteps=None, noise=None, checks=True):
     """-> dict(xh_phar, xh_pocket, phar_mask, pocket_mask, z_steps [K, Nl, 3+P], pocket_steps [K, Np, 3], margins [K + 1, B] (A),
     op_energy [K, B], energy [B], max_violation [B], kind_violation [K, 4], clipped, unclipped: counts of displacements)."""
-    T, nd, pnf = cfg['timesteps'], cfg['n_dims'], cfg['phar_nf']
-    nv, nb = cfg['norm_values'], cfg['norm_biases']
-    assert not cfg.get('no_com_projection', False) and not cfg.get('update_pocket_coords', False)
-    table = ref_cpu.gamma_source(p)
-    timesteps = T if timesteps is None else timesteps
-    draw = noise if noise is not None else (lambda shape: torch.randn(shape))
-    B = len(pocket['size'])
-    n_x = nv[0]
-    px = pocket['x'].to(FLOAT) / n_x
-    ph = (pocket['one_hot'].float() - nb[1]) / nv[1]
-    qm = pocket['mask'].to(INT)
-    xh0_pocket = torch.cat([px, ph], dim=1)
-    pm = torch.repeat_interleave(torch.arange(B), torch.as_tensor(num_nodes_phar).to(INT))
-    com_in = ref_cpu.scatter_mean(px, qm, B)                                     # com(P_in.x / n_x)
-    mu_phar = torch.cat((com_in, torch.zeros((B, pnf))), dim=1)[pm]
-    sigma = torch.ones_like(pocket['size']).unsqueeze(1)
-    shape = (len(pm), nd + pnf)
-    z, P = ref_cpu.sample_normal_zero_com(mu_phar, xh0_pocket, sigma, pm, qm, draw(shape), nd)
-    if checks:
-        ref_cpu.assert_mean_zero_with_mask(z[:, :nd], pm)
-    touched = torch.from_numpy(touched_samples(rec, B, clash_r))
-    any_touched = bool(touched.any())
-    z_steps, p_steps, margins, op_energy, kind_v = [], [], [], [], []
-    clipped = unclipped = 0
-    for s in reversed(range(0, timesteps)):
-        s_array = torch.full((B, 1), fill_value=s)
-        t_array = s_array + 1
-        s_array = s_array / timesteps
-        t_array = t_array / timesteps
-        gamma_s = ref_cpu.gamma_lookup(table, s_array, T)
-        gamma_t = ref_cpu.gamma_lookup(table, t_array, T)
-        sigma2_ts, sigma_ts, alpha_ts = ref_cpu.sigma_and_alpha_t_given_s(gamma_t, gamma_s)
-        sigma_s, sigma_t = ref_cpu.sigma_of(gamma_s), ref_cpu.sigma_of(gamma_t)
-        alpha_t = ref_cpu.alpha_of(gamma_t)
-        margins.append(pair_margins(z[:, :nd], P[:, :nd], pm, qm, cfg['edge_cutoff']) * n_x)
-        eps_t, _ = ref_cpu.dynamics_forward(p, cfg, z, P, t_array, pm, qm)      # (its x columns are zero when the NaN guard reset)
-        mu = z / alpha_ts[pm] - (sigma2_ts / alpha_ts / sigma_t)[pm] * eps_t
-        sig = sigma_ts * sigma_s / sigma_t
-        E = torch.zeros(B)
-        vk = torch.zeros(4)
-        if any_touched:
-            xhat = n_x * (z[:, :nd] - sigma_t[pm] * eps_t[:, :nd]) / alpha_t[pm]                  # 1.
-            shift = n_x * (ref_cpu.scatter_mean(P[:, :nd], qm, B) - com_in)                        # 2.
-            E, g, _, vk = energy_terms(xhat, n_x * P[:, :nd], shift, pm, qm, rec, clash_r, clash_k)    # 3.
-            var = (n_x * sig) ** 2
-            d = -scale * var[pm] * g                                                               # 4.
-            length = _norm(d)
-            over = length > max_shift
-            d = torch.where(over[:, None], d * (max_shift / length.clamp(min=1e-30))[:, None], d)
-            active = touched[pm] & (t_array[pm][:, 0] <= guide_below) & (scale > 0)
-            clipped += int((over & active).sum())
-            unclipped += int((~over & active & (length > 0)).sum())
-            rows = torch.nonzero(active).reshape(-1)
-            if len(rows):
-                mu[rows, :nd] = mu[rows, :nd] + d[rows] / n_x                                      # 5.
-        op_energy.append(E)
-        kind_v.append(vk)
-        zt_old = z
-        z, P = ref_cpu.sample_normal_zero_com(mu, P, sig, pm, qm, draw(shape), nd)
-        if checks:
-            ref_cpu.assert_mean_zero_with_mask(zt_old[:, :nd], pm)
-        z_steps.append(z.clone())
-        p_steps.append(P[:, :nd].clone())
-    # the decode, not guided: as ref_cpu.sample_given_pocket
-    t_zeros = torch.zeros((B, 1))
-    gamma_0 = ref_cpu.gamma_lookup(table, t_zeros, T)
-    sigma_x = torch.exp(-(-0.5 * gamma_0))
-    margins.append(pair_margins(z[:, :nd], P[:, :nd], pm, qm, cfg['edge_cutoff']) * n_x)
-    net_out, _ = ref_cpu.dynamics_forward(p, cfg, z, P, t_zeros, pm, qm)
-    sigma_0, alpha_0 = ref_cpu.sigma_of(gamma_0), ref_cpu.alpha_of(gamma_0)
-    mu_x = 1. / alpha_0[pm] * (z - sigma_0[pm] * net_out)
-    xh_phar, xh_pocket = ref_cpu.sample_normal_zero_com(mu_x, P, sigma_x, pm, qm, draw(shape), nd)
-    x_phar = xh_phar[:, :nd] * n_x
-    h_phar = torch.nn.functional.one_hot(torch.argmax(z[:, nd:] * nv[1] + nb[1], dim=1), pnf)
-    x_pocket = xh_pocket[:, :nd] * n_x
-    h_pocket = xh_pocket[:, nd:] * nv[1] + nb[1]
-    if checks:
-        ref_cpu.assert_mean_zero_with_mask(x_phar, pm)
-    if ref_cpu.scatter_add(x_phar, pm).abs().max().item() > 5e-2:
-        x_phar, x_pocket = ref_cpu.remove_mean_batch(x_phar, x_pocket, pm, qm)
-    # the diagnostics of the returned sample: shift from the returned pocket
-    shift = ref_cpu.scatter_mean(x_pocket, qm, B) - n_x * com_in
-    E_fin, _, v_fin, _ = energy_terms(x_phar, x_pocket, shift, pm, qm, rec, clash_r, clash_k)
-    return dict(xh_phar=torch.cat([x_phar, h_phar.to(FLOAT)], dim=1), xh_pocket=torch.cat([x_pocket, h_pocket], dim=1), phar_mask=pm,
-                pocket_mask=qm, z_steps=torch.stack(z_steps), pocket_steps=torch.stack(p_steps), margins=np.stack(margins),
-                op_energy=torch.stack(op_energy), energy=E_fin, max_violation=v_fin, kind_violation=torch.stack(kind_v),
-                clipped=clipped, unclipped=unclipped)
+    guide = dict(rec=rec, clash_r=clash_r, clash_k=clash_k, scale=scale, max_shift=max_shift, guide_below=guide_below)
+    o = run_chain(p, cfg, pocket, num_nodes_phar=num_nodes_phar, guide=guide, timesteps=timesteps, noise=noise, checks=checks)
+    return {k: o[k] for k in KEYS}
