@@ -8,6 +8,7 @@
 #include <vector>
 #include "cmdgen_split.h"
 #include "cmdgen_plan.h"
+#include "cmdgen_train_plan.h"      // TrainTune and the training step's GEMM planners
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -260,18 +261,6 @@ struct TrainSave {              // activation store of the TRAINING forward (cmd
     float *qdec1, *qdeca, *qdec_out;            // residue decoder (joint model) [Np][2R] x2, [Np][R]
     size_t ecap, eccap;                         // row capacities of the per-block edge arrays
     int slot;                                   // index of this launch's GCL in the per-GCL arrays (h, pre1 .. z, aggn .. nact): block * inv_sublayers + sub (set by the launcher; the coordinate arrays are per block)
-};
-
-struct TrainTune {              // launch choices of the training step's gradient kernels (cmdgen_set_option; defaults from sweeps on MI355X)
-    int wgrad_split = -1;       // weight gradients as three-piece split products: -1 = wherever the handle runs the split engine (tile by wgrad_k128), 0 = never (fp32 instruction), 1 = always on 128 x 128 tiles where the shape allows
-    int wgrad_tile = 0;         // 64: never the 128 x 128-tile kernel
-    int wgrad_k128 = 131072;    // rows x 128-tiles of a launch from which a three-piece weight gradient uses 128 x 128 tiles (below: 64 x 64)
-    int wgrad_split_wgs128 = 384, wgrad_split_wgs64 = 512;   // workgroups the split-K factor of the two split kernels aims at
-    int wgrad_wgs = 768;        // ... of the fp32-instruction kernel (3 workgroups of 49 KB LDS per CU; profiles/r02_t3_training_round2.txt)
-    int dgrad_mt = 0;           // rows per tile of the data-gradient kernel: 0 = by row count (64 from 24576 rows), 32, 64
-    int dgrad_tail = 1;         // 1: dpre of an edge list is consumed inside the second-layer data gradient (k_dgrad_tail)
-    unsigned long long* dbg = nullptr;   // Work::dbg for the stamped diagnostic build of k_dgrad_tail (tools/tail_stamps.py)
-    int wgrad_stream = 1;       // 1: weight / bias gradients on the handle's second stream, beside the chain of data gradients (cmdgen_train.hip)
 };
 
 struct EvalLaunch {             // everything one evaluation's launches need (host side)

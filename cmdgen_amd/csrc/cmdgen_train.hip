@@ -325,30 +325,6 @@ static int ensure_edges(cmdgen_handle* h, TrainState* t, int E, int Ec) {
     return 0;
 }
 
-// GEMM operand precision of the call in progress (TrainState::bf16; the tiny encoder / decoder products with K < 64
-// always run in fp32)
-static thread_local bool g_bf16 = false;
-static inline bool use_bf16(int K) { return g_bf16 && K >= 64; }
-
-// y[M, out] = x[M, in(ldx)] W^T + b      (W, b inside the flat buffer)
-static void linear(const float* theta, const PRef& r, int col0, int in, int M, const float* x, int ldx, float* y, int ldy,
-                   bool bias, bool accumulate, hipStream_t s, float* act = nullptr) {
-    cmdgen_sgemm(false, true, M, r.out, in, x, ldx, theta + r.w + col0, r.in, y, ldy, (bias && r.has_bias) ? theta + r.b : nullptr,
-                 1.0f, accumulate, 1, s, act ? 1 : 0, act, ldy, use_bf16(in));      // act: SiLU(y) written alongside y
-}
-// dx[M, in] (+)= dy[M, out] W[:, col0:col0+in]
-static void linear_dgrad(const float* theta, const PRef& r, int col0, int in, int M, const float* dy, int lddy, float* dx,
-                         int lddx, bool accumulate, hipStream_t s, const float* pre = nullptr) {
-    cmdgen_sgemm(false, false, M, in, r.out, dy, lddy, theta + r.w + col0, r.in, dx, lddx, nullptr, 1.0f, accumulate, 1, s,
-                 pre ? 2 : 0, const_cast<float*>(pre), lddx, use_bf16(r.out));   // pre: dx *= SiLU'(pre) (the activation that fed this Linear)
-}
-// dW[:, col0:col0+in] += dy^T x ;  split over the M rows (edges / nodes)
-static void linear_wgrad(float* grad, const PRef& r, int col0, int in, int M, const float* dy, int lddy, const float* x,
-                         int ldx, hipStream_t s) {
-    cmdgen_sgemm(true, false, r.out, in, M, dy, lddy, x, ldx, grad + r.w + col0, r.in, nullptr, 1.0f, true, 0, s, 0, nullptr, 0,
-                 g_bf16 && r.out >= 64 && in >= 64);
-}
-
 extern "C" int cmdgen_param_count(cmdgen_handle* h, int64_t* n) {
     if (!h || !n) return CMDGEN_EINVAL;
     ParamTable t; build_table(h->dims, t);
@@ -418,7 +394,6 @@ extern "C" int cmdgen_train_forward(cmdgen_handle* h, const float* theta, const 
     HIPCHK(h, hipEventSynchronize(t->tot_ev));
     const int E = t->h_tot[0], Ec = t->h_tot[1];
     rc = ensure_edges(h, t, E, Ec); if (rc) return rc;
-    g_bf16 = t->bf16; g_train_tune = h->tune;
     h->train_E = E; h->train_Ec = Ec;
     t->E = E; t->Ec = Ec; t->theta = theta; t->xh_phar = xh_phar; t->xh_pocket = xh_pocket;
     const Work& w = h->work;
@@ -566,7 +541,20 @@ static int train_backward_stages(cmdgen_handle* h, const float* d_eps_phar, cons
     if (!d_eps_phar || !grad) return fail(h, CMDGEN_EINVAL, "null device pointer");
     hipSetDevice(h->device);
     TrainState* t = h->train;
-    g_bf16 = t->bf16; g_train_tune = h->tune; g_train_tune.dbg = h->work.dbg;
+    // GEMM operand precision (TrainState::bf16) and launch tuning of THIS call: locals, which every deferred closure below captures by value
+    const bool bf16 = t->bf16;
+    const TrainTune tune = h->tune;
+    // dx[M, in] (+)= dy[M, out] W[:, col0:col0+in]   (W inside the flat buffer; the tiny encoder / decoder products with K < 64 always run in fp32)
+    auto linear_dgrad = [bf16](const float* theta, const PRef& r, int col0, int in, int M, const float* dy, int lddy, float* dx, int lddx, bool accumulate,
+                               hipStream_t s, const float* pre = nullptr) {
+        cmdgen_sgemm(false, false, M, in, r.out, dy, lddy, theta + r.w + col0, r.in, dx, lddx, nullptr, 1.0f, accumulate, 1, s,
+                     pre ? 2 : 0, const_cast<float*>(pre), lddx, bf16 && r.out >= 64);   // pre: dx *= SiLU'(pre) (the activation that fed this Linear)
+    };
+    // dW[:, col0:col0+in] += dy^T x ;  split over the M rows (edges / nodes)
+    auto linear_wgrad = [bf16](float* grad, const PRef& r, int col0, int in, int M, const float* dy, int lddy, const float* x, int ldx, hipStream_t s) {
+        cmdgen_sgemm(true, false, r.out, in, M, dy, lddy, x, ldx, grad + r.w + col0, r.in, nullptr, 1.0f, true, 0, s, 0, nullptr, 0,
+                     bf16 && r.out >= 64 && in >= 64);
+    };
     hipStream_t s = (hipStream_t)stream;
     h->last_stream = s;
     // The pass forks work onto the handle's side streams and joins them with events.  With the LEGACY DEFAULT stream as the caller's stream that
@@ -577,7 +565,7 @@ static int train_backward_stages(cmdgen_handle* h, const float* d_eps_phar, cons
     // streams share one: 2.7 -> 4.5 ms per step inside bench.py - the pass's main chain takes the handle's first side stream, the weight
     // gradients its second, and the embedding stage's third stream is folded into the second.)
     const hipStream_t caller = s;
-    const bool bridged = caller == nullptr && g_train_tune.wgrad_stream != 0 && g_train_tune.dgrad_tail != 0 && t->ws && t->ws_low;
+    const bool bridged = caller == nullptr && tune.wgrad_stream != 0 && tune.dgrad_tail != 0 && t->ws && t->ws_low;
     if (bridged) {
         if (!t->br_in) {
             HIPCHK(h, hipEventCreateWithFlags(&t->br_in, hipEventDisableTiming));
@@ -597,12 +585,12 @@ static int train_backward_stages(cmdgen_handle* h, const float* d_eps_phar, cons
     const size_t NH = (size_t)N * H;
     const bool w3 = h->gemm_split;                                    // (three-piece weight gradients wherever the handle runs the split engine: cmdgen_wgrad_group)
     const bool sp = t->split_packs_valid && H == 256;                 // [.,256] x [256,256] data gradients on the bf16 matrix pipe:
-    const int pcs = g_bf16 ? 1 : 3;                                   // three pieces per operand (fp32-accurate) or the leading one (bf16 operands)
-    const bool tail_fused = sp && g_train_tune.dgrad_tail != 0;
+    const int pcs = bf16 ? 1 : 3;                                        // three pieces per operand (fp32-accurate) or the leading one (bf16 operands)
+    const bool tail_fused = sp && tune.dgrad_tail != 0;
     // weight / bias gradients leave the chain of data gradients for the second stream (SideStream above) where the buffers they read
     // rotate (the fused-tail path); ss.on = false: everything on the caller's stream, in the order written
-    hipStream_t side = (bridged || (g_train_tune.wgrad_stream == 2 && t->ws_low)) ? t->ws_low : t->ws;
-    SideStream ss{s, side, tail_fused && side != nullptr && g_train_tune.wgrad_stream != 0, &t->evs};
+    hipStream_t side = (bridged || (tune.wgrad_stream == 2 && t->ws_low)) ? t->ws_low : t->ws;
+    SideStream ss{s, side, tail_fused && side != nullptr && tune.wgrad_stream != 0, &t->evs};
     // deferred side work: queued where the serial pass launches it, run on the side stream by flush_side() (serial pass: run at once)
     std::vector<std::function<void(hipStream_t)>> pending;
     auto defer = [&](std::function<void(hipStream_t)> f) { if (ss.on) pending.push_back(std::move(f)); else f(s); };
@@ -620,14 +608,14 @@ static int train_backward_stages(cmdgen_handle* h, const float* d_eps_phar, cons
         wb.dy[q] = dy; wb.x[q] = x; wb.dw[q] = grad + r.w + col0; wb.db[q] = (with_bias && r.has_bias) ? grad + r.b : nullptr;
         wb.M[q] = r.out; wb.N[q] = in; wb.lddy[q] = r.out; wb.ldx[q] = in; wb.ldw[q] = r.in;
     };
-    const bool bf = g_bf16, gs = h->gemm_split;
-    auto flush_wgrads = [&]() { const WgradBatch g = wb; defer([=](hipStream_t q) { cmdgen_wgrad_group(g, N, bf, q, gs); }); wb.n = 0; };
+    const bool gs = h->gemm_split;
+    auto flush_wgrads = [&]() { const WgradBatch g = wb; defer([=](hipStream_t q) { cmdgen_wgrad_group(g, N, bf16, q, tune, gs); }); wb.n = 0; };
     // weight + bias gradient of one edge-level Linear (K = list length) in one launch
     auto edge_wgrad = [&](const PRef& r, const float* dy, const float* x, int K, int x_is_pre) {       // x_is_pre: x is the layer's PRE-activation (its SiLU is formed while the operand is staged)
         WgradBatch one; one.n = 1; one.xs[0] = x_is_pre;
         one.dy[0] = dy; one.x[0] = x; one.dw[0] = grad + r.w; one.db[0] = grad + r.b;
         one.M[0] = H; one.N[0] = H; one.lddy[0] = H; one.ldx[0] = H; one.ldw[0] = r.in;
-        defer([=](hipStream_t q) { cmdgen_wgrad_group(one, K, bf, q, w3); });
+        defer([=](hipStream_t q) { cmdgen_wgrad_group(one, K, bf16, q, tune, w3); });
     };
     // small weight + bias gradients of the readout / embedding stages (encoders, decoders, the two embeddings): a k_sgemm + k_colsum pair per
     // Linear.  Readout stage: with the side stream's first batch.  Embedding stage (the pass's tail): each pair on a third stream as soon as its
@@ -642,7 +630,7 @@ static int train_backward_stages(cmdgen_handle* h, const float* d_eps_phar, cons
             linear_wgrad(grad, *rp, 0, in, M, dy, lddy, x, ldx, q); tr_colsum(M, rp->out, dy, lddy, nullptr, grad + rp->b, 1, q);
             return;
         }
-        defer([=](hipStream_t q) { g_bf16 = bf; linear_wgrad(grad, *rp, 0, in, M, dy, lddy, x, ldx, q); tr_colsum(M, rp->out, dy, lddy, nullptr, grad + rp->b, 1, q); });
+        defer([=](hipStream_t q) { linear_wgrad(grad, *rp, 0, in, M, dy, lddy, x, ldx, q); tr_colsum(M, rp->out, dy, lddy, nullptr, grad + rp->b, 1, q); });
     };
     // rotating buffers (side stream on): block k of the pass (k = 0 for block L-1) reads dL/dh_{l+1} in dhb[k % 3] and leaves dL/dh_l in
     // dhb[(k + 1) % 3]; dpre2 / dpre7 / dn / the two dP | dQ pairs by the parity of k.  Off: one buffer each, updated in place.
@@ -730,17 +718,17 @@ static int train_backward_stages(cmdgen_handle* h, const float* d_eps_phar, cons
         edge_wgrad(bc.c2, actB, (t->wsilu & 2) ? pre6 : t->act6 + (size_t)l * t->eccap * H, Ec, (t->wsilu & 2) ? 1 : 0);      // weight and bias gradient of coord_mlp.2 (c1 = SiLU(pre6))
         if (tail_fused)     // dpre6 = (dpre7 W7) SiLU'(pre6) and everything done with it, in one kernel: it never reaches HBM
             cmdgen_dgrad_tail(Ec, actB, pkc.t_c2, pre6, w.crow, w.ccol, w.cd0, pair ? pkc.rd_c : theta + bc.c0.w + 2 * H /* radial column: the forward's contiguous copy */, pair ? 1 : ld1, Xl,
-                              d.norm_constant, t->dcd, n_rows_dx, dPc, dQc, grad + bc.c0.w + 2 * H, t->dX, tail_c, pcs, s, pair,
+                              d.norm_constant, t->dcd, n_rows_dx, dPc, dQc, grad + bc.c0.w + 2 * H, t->dX, tail_c, pcs, s, w.dbg, pair,
                               pair ? pkc.rd_c + H : theta + bc.c0.w + 2 * H + 1 /* d0 column */, dd0_c);
         if (pair) { float* gw = grad + bc.c4.w; float* gc = grad + bc.c0.w + 2 * H; defer([=](hipStream_t q) { tr_reduce_pair(Ec, H, part_c, gw, nullptr, tail_c, gc, ld1, q); }); }
         else {
-            if (sp) cmdgen_dgrad_split(Ec, actB, pkc.t_c2, nullptr, nullptr, t->actA, false, 1.0f, pre6, s, pcs);
+            if (sp) cmdgen_dgrad_split(Ec, actB, pkc.t_c2, nullptr, nullptr, t->actA, false, 1.0f, pre6, s, tune, pcs);
             else linear_dgrad(theta, bc.c2, 0, H, Ec, actB, H, t->actA, H, false, s, pre6);  // actA <- dc1 * SiLU'(pre6) = dpre6
             // adjoints of the gathers, the radial / d0 column gradients, d radial and the geometry adjoint: one pass over dpre6
             tr_edge_tail_bwd(Ec, H, w.crow, w.ccol, t->actA, w.cd0, theta + bc.c0.w + 2 * H, ld1, Xl, d.norm_constant, t->dcd, n_rows_dx,
                              dPc, dQc, grad + bc.c0.w + 2 * H, t->dX, t->tail_scratch, s, theta + bc.c0.w + 2 * H + 1, dd0_c);
         }
-        if (sp) cmdgen_dgrad_split(N, dPc, pkc.t_c0a, dQc, pkc.t_c0b, dh_in, true, 1.0f, nullptr, s, pcs);
+        if (sp) cmdgen_dgrad_split(N, dPc, pkc.t_c0a, dQc, pkc.t_c0b, dh_in, true, 1.0f, nullptr, s, tune, pcs);
         else {
             linear_dgrad(theta, bc.c0, 0, H, N, dPc, H, dh_in, H, true, s);
             linear_dgrad(theta, bc.c0, H, H, N, dQc, H, dh_in, H, true, s);
@@ -755,8 +743,8 @@ static int train_backward_stages(cmdgen_handle* h, const float* d_eps_phar, cons
         flush_wgrads();
         if (u == 0) flush_side();       // the last GCL of the pass: its side work starts as early as it can (nothing comes after to hide it)
         if (sp) {
-            cmdgen_dgrad_split(N, dh_in, pk.t_n2, nullptr, nullptr, dn, false, 1.0f, pre3, s, pcs);
-            cmdgen_dgrad_split(N, dn, pk.t_n0a, nullptr, nullptr, dh_out, true, 1.0f, nullptr, s, pcs,         // dh_out = dh_in + dpre3 W3[:, :H] and
+            cmdgen_dgrad_split(N, dh_in, pk.t_n2, nullptr, nullptr, dn, false, 1.0f, pre3, s, tune, pcs);
+            cmdgen_dgrad_split(N, dn, pk.t_n0a, nullptr, nullptr, dh_out, true, 1.0f, nullptr, s, tune, pcs,         // dh_out = dh_in + dpre3 W3[:, :H] and
                                pk.t_n0b, t->dagg, false, d.norm_factor, 0, dh_in, rowdiv);                      // dagg = dpre3 W3[:, H:] / nf: one launch
         } else {
             linear_dgrad(theta, b.n2, 0, H, N, dh_in, H, dn, H, false, s, pre3);       // dn <- dn1 * SiLU'(pre3) = dpre3
@@ -771,13 +759,13 @@ static int train_backward_stages(cmdgen_handle* h, const float* d_eps_phar, cons
         edge_wgrad(b.e2, actA, (t->wsilu & 1) ? pre1 : t->act1 + (size_t)u * t->ecap * H, E, (t->wsilu & 1) ? 1 : 0);            // weight and bias gradient of edge_mlp.2 (m1 = SiLU(pre1))
         if (tail_fused)
             cmdgen_dgrad_tail(E, actA, pk.t_e2, pre1, w.erow, w.ecol, w.ed0, pair ? pk.rd_e : theta + b.e0.w + 2 * H, pair ? 1 : ld1, Xl, d.norm_constant, nullptr, n_rows_dx,
-                              dPe, dQe, grad + b.e0.w + 2 * H, t->dX, tail_e, pcs, s, pair, pair ? pk.rd_e + H : theta + b.e0.w + 2 * H + 1, dd0_e);
+                              dPe, dQe, grad + b.e0.w + 2 * H, t->dX, tail_e, pcs, s, w.dbg, pair, pair ? pk.rd_e + H : theta + b.e0.w + 2 * H + 1, dd0_e);
         if (pair) {
             float* gaw = d.attention ? grad + b.att.w : nullptr; float* gab = d.attention ? grad + b.att.b : nullptr; float* ge = grad + b.e0.w + 2 * H;
             defer([=](hipStream_t q) { tr_reduce_pair(E, H, part_e, gaw, gab, tail_e, ge, ld1, q); });
         }
         else {
-            if (sp) cmdgen_dgrad_split(E, actA, pk.t_e2, nullptr, nullptr, t->actB, false, 1.0f, pre1, s, pcs);
+            if (sp) cmdgen_dgrad_split(E, actA, pk.t_e2, nullptr, nullptr, t->actB, false, 1.0f, pre1, s, tune, pcs);
             else linear_dgrad(theta, b.e2, 0, H, E, actA, H, t->actB, H, false, s, pre1);   // actB <- dm1 * SiLU'(pre1) = dpre1
             tr_edge_tail_bwd(E, H, w.erow, w.ecol, t->actB, w.ed0, theta + b.e0.w + 2 * H, ld1, Xl, d.norm_constant, nullptr, n_rows_dx,
                              dPe, dQe, grad + b.e0.w + 2 * H, t->dX, t->tail_scratch, s, theta + b.e0.w + 2 * H + 1, dd0_e);
@@ -789,7 +777,7 @@ static int train_backward_stages(cmdgen_handle* h, const float* d_eps_phar, cons
         defer_wgrad(b.e0, H, H, dQe, hl, false);
         flush_wgrads();
         blk_done[k] = flush_side();                 // the GCL's weight gradients: one fork
-        if (sp) cmdgen_dgrad_split(N, dPe, pk.t_e0a, dQe, pk.t_e0b, dh_out, true, 1.0f, nullptr, s, pcs);       // (dh_out = dh_in when the side stream is off)
+        if (sp) cmdgen_dgrad_split(N, dPe, pk.t_e0a, dQe, pk.t_e0b, dh_out, true, 1.0f, nullptr, s, tune, pcs);       // (dh_out = dh_in when the side stream is off)
         else {
             linear_dgrad(theta, b.e0, 0, H, N, dPe, H, dh_out, H, true, s);
             linear_dgrad(theta, b.e0, H, H, N, dQe, H, dh_out, H, true, s);
@@ -1012,7 +1000,6 @@ extern "C" int cmdgen_debug_dgrad(cmdgen_handle* h, int32_t M, const float* A0, 
                                   cmdgen_stream stream) {
     if (!h || !A0 || !W0 || !Y || (A1 && !W1) || M < 1 || (pieces != 1 && pieces != 3)) return fail(h, CMDGEN_EINVAL, "bad arguments");
     hipSetDevice(h->device);
-    g_train_tune = h->tune;
     hipStream_t s = (hipStream_t)stream;
     void* packs = nullptr; void* tab = nullptr;
     const size_t pack_bytes = (size_t)256 * 256 * 6;
@@ -1023,7 +1010,7 @@ extern "C" int cmdgen_debug_dgrad(cmdgen_handle* h, int32_t M, const float* A0, 
     HIPCHK(h, hipMemcpyAsync(tab, t2, sizeof t2, hipMemcpyHostToDevice, s));
     HIPCHK(h, hipStreamSynchronize(s));
     tr_repack_split_t(W0, tab, A1 ? 2 : 1, s);
-    cmdgen_dgrad_split(M, A0, packs, A1, A1 ? (char*)packs + pack_bytes : nullptr, Y, accumulate != 0, div, pre, s, pieces, nullptr, nullptr,
+    cmdgen_dgrad_split(M, A0, packs, A1, A1 ? (char*)packs + pack_bytes : nullptr, Y, accumulate != 0, div, pre, s, h->tune, pieces, nullptr, nullptr,
                        false, 1.0f, tile_rows == 64 ? 64 : (tile_rows ? 32 : 0));
     hipError_t e = hipStreamSynchronize(s);
     hipFree(packs); hipFree(tab);
@@ -1039,11 +1026,10 @@ extern "C" int cmdgen_debug_wgrad(cmdgen_handle* h, int32_t K, int32_t M, int32_
                                   float* db, int32_t mode, cmdgen_stream stream) {
     if (!h || !dY || !X || !dW || K < 1 || M < 1 || N < 1) return fail(h, CMDGEN_EINVAL, "bad arguments");
     hipSetDevice(h->device);
-    g_train_tune = h->tune;
     WgradBatch one; one.n = 1;
     one.dy[0] = dY; one.x[0] = X; one.dw[0] = dW; one.db[0] = db;
     one.M[0] = M; one.N[0] = N; one.lddy[0] = M; one.ldx[0] = N; one.ldw[0] = N;
-    cmdgen_wgrad_group(one, K, mode == 1, (hipStream_t)stream, mode == 3, mode == 3);
+    cmdgen_wgrad_group(one, K, mode == 1, (hipStream_t)stream, h->tune, mode == 3, mode == 3);
     HIPCHK(h, hipGetLastError());
     return CMDGEN_OK;
 }

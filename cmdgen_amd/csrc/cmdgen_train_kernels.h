@@ -5,8 +5,6 @@
 #pragma once
 #include "cmdgen_dev.h"
 
-extern thread_local TrainTune g_train_tune;      // set from the handle at every entry of the training step (defined in kernels_train.hip)
-
 // ---- per-step re-pack of the parameters into the layouts the evaluation kernels stream (fragment orders: cmdgen_wlayout.h) ----
 // row_split / col_shift: rows >= row_split of the packed matrix are rows - row_split of the source, shifted col_shift columns right
 // (the stacked [2H][H] projections of edge_mlp.0 / coord_mlp.0)
@@ -23,6 +21,7 @@ void tr_repack_half(const float* theta, const void* tab, int n_plain, int n, hip
 void tr_repack_half16(const float* theta, const void* tab, int n, int max8, hipStream_t s);
 
 // ---- GEMMs ----
+// Which kernel, grid and split-K each launcher takes is decided in cmdgen_train_plan.h; tune: the handle's TrainTune (cmdgen_handle::tune)
 // split_k: 0 = choose so that the launch fills the chip (wgrad: few output tiles, K = thousands of rows); 1 = none
 void cmdgen_sgemm(bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
                   int ldc, const float* bias, float alpha, bool accumulate, int split_k, hipStream_t s,
@@ -33,16 +32,16 @@ struct WgradBatch {               // up to 8 weight gradients dW (+)= dY^T X (+ 
     int n;
     int xs[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // 1: X_p holds PRE-activations - SiLU is applied while the operand is staged (the forward then stores pre1 / pre6 only)
 };
-void cmdgen_wgrad_group(const WgradBatch& g, int K, bool bf16, hipStream_t s, bool split3 = false, bool force3 = false);
+void cmdgen_wgrad_group(const WgradBatch& g, int K, bool bf16, hipStream_t s, const TrainTune& tune, bool split3 = false, bool force3 = false);
 // pieces = 3: fp32-accurate (split engine); 1: the operands' leading bf16 piece only (= operands rounded to nearest-even
 // bf16, fp32 accumulation: cmdgen_train_set_precision(1))
 void cmdgen_dgrad_split(int M, const float* A0, const void* W0, const float* A1, const void* W1, float* Y, bool accumulate, float div,
-                        const float* pre, hipStream_t s, int pieces = 3, const void* W0b = nullptr, float* Yb = nullptr,
+                        const float* pre, hipStream_t s, const TrainTune& tune, int pieces = 3, const void* W0b = nullptr, float* Yb = nullptr,
                         bool accumulate_b = false, float div_b = 1.0f, int force_mt = 0, const float* Yin = nullptr, const float* rowdiv_b = nullptr);
 void cmdgen_dgrad_tail(int E, const float* dY, const void* Wt, const float* pre1, const int* row, const int* col, const float* d0,
                        const float* Wcol, int ldw, const float4* X, float nc, const float4* dcd, int n_moving, float* dP, float* dQ,
-                       float* dWcol, float* dX, float* scratch, int pieces, hipStream_t s, bool defer_reduce = false,
-                       const float* Wd = nullptr, float* dd0 = nullptr);
+                       float* dWcol, float* dX, float* scratch, int pieces, hipStream_t s, unsigned long long* dbg, bool defer_reduce = false,
+                       const float* Wd = nullptr, float* dd0 = nullptr);      // dbg: Work::dbg, for the stamped diagnostic build (tools/tail_stamps.py)
 
 // ---- adjoints of the edge models' element-wise parts, with their parameter reductions ----
 size_t tr_partial_scratch_floats(size_t E, size_t H);

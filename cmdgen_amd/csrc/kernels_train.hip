@@ -11,6 +11,7 @@
 #include "cmdgen_split.h"
 #include "cmdgen_train_kernels.h"
 #include "cmdgen_wlayout.h"
+#include <utility>
 
 // ------------------------------------------------------------------------------------
 // C[M,N] (+)= alpha * op(A)[M,K] * op(B)[K,N] (+ bias[N])          exact fp32 on v_mfma_f32_32x32x2_f32
@@ -567,91 +568,20 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_split128(WgradBatch g, int K, 
     }
 }
 
-// split3: the handle runs on the split engine, so three-piece (fp32-accurate) weight gradients are allowed; force3: a test asks for them.
-// Which kernel (tools/bench_wgrad.py, profiles/r03_n_wgrad.txt; one 256 x 256 product, us per launch):
-//     K                fp32 instruction   three pieces 64-tile / 128-tile   bf16 operands 64-tile / 128-tile
-//     3 721 (nodes)          18               14 / 17                               12 / 13
-//    16 127                  32               32 / 35                               23 / 24
-//    36 147                  58               59 / 51                               38 / 37
-//   156 316                 253              227 / 175                             155 / 103
-// These products are tall and skinny (256 x 256 outputs over 1e4-1e5 rows): operand reads and the split-K atomics bind them, not the
-// matrix pipe.  The 128-tile kernel reads each operand row half as often and wins once K >= ~32k (three pieces) / ~64k (bf16); below
-// that the fp32 instruction (three pieces) and the 64-tile kernel (bf16) stay.  Options (TrainTune, cmdgen_set_option): wgrad_split = 0: never
-// three pieces; = 1: always where the shape allows; wgrad_tile = 64: never the 128-tile kernel.
-thread_local TrainTune g_train_tune;      // set from the handle at every entry of the training step (cmdgen_train.hip)
-void cmdgen_wgrad_group(const WgradBatch& g, int K, bool bf16, hipStream_t s, bool split3, bool force3) {
+// the kernel, grid and split-K of a group: plan_wgrad (cmdgen_train_plan.h); here only what needs a pointer - the alignment test and the launch
+void cmdgen_wgrad_group(const WgradBatch& g, int K, bool bf16, hipStream_t s, const TrainTune& tune, bool split3, bool force3) {
     if (g.n <= 0 || K <= 0) return;
-    bool xs = false;
-    for (int p = 0; p < g.n; ++p) xs = xs || g.xs[p] != 0;
-    int tm = 1, tn = 1;
-    for (int p = 0; p < g.n; ++p) { tm = max(tm, (g.M[p] + 63) / 64); tn = max(tn, (g.N[p] + 63) / 64); }
-    {
-        const int env3 = g_train_tune.wgrad_split;
-        const bool tile64 = g_train_tune.wgrad_tile == 64;
-        bool ok64 = true, ok128 = !tile64;
-        for (int p = 0; p < g.n; ++p) {
-            ok64 = ok64 && g.M[p] % 64 == 0 && g.N[p] % 64 == 0 && g.lddy[p] % 4 == 0 && g.ldx[p] % 4 == 0 &&
-                   (reinterpret_cast<uintptr_t>(g.dy[p]) & 15) == 0 && (reinterpret_cast<uintptr_t>(g.x[p]) & 15) == 0;
-            ok128 = ok128 && g.M[p] % 128 == 0 && g.N[p] % 128 == 0;
-        }
-        ok128 = ok128 && ok64;
-        // Round 5: the weight gradients run BESIDE the chain of data gradients (cmdgen_train.hip), where the fp32 instruction's long hold on the
-        // matrix pipe costs the other stream more than its own launch gains: three pieces whenever the handle is on the split engine, 64 x 64
-        // tiles for short products and 128 x 128 from TrainTune::wgrad_k128 rows (same-box sweeps with both streams running: profiles/r05_an, r05_ao)
-        // (the 128-tile kernel splits K over wgrad_split_wgs128 / tiles workgroups: it pays once a workgroup's share is ~500 rows, i.e. from
-        // K x tiles >= TrainTune::wgrad_k128 - a 4-product node-level group at 15k rows, a single product from 49k)
-        long tiles128 = 0;
-        for (int p = 0; p < g.n; ++p) tiles128 += (long)(g.M[p] / 128) * (g.N[p] / 128);
-        const bool three = !bf16 && (force3 || (split3 && env3 != 0 && ok64));
-        const bool sp = ok64 && (bf16 || three);
-        const bool sp128 = sp && ok128 && (force3 || env3 == 1 || (bf16 ? K >= 65536 : (long)K * tiles128 >= (long)g_train_tune.wgrad_k128));
-        if (sp128) {
-            int tm = 1, tn = 1, tiles = 0;
-            for (int p = 0; p < g.n; ++p) { tm = max(tm, g.M[p] / 128); tn = max(tn, g.N[p] / 128); tiles += (g.M[p] / 128) * (g.N[p] / 128); }
-            const int wgs = g_train_tune.wgrad_split_wgs128;
-            int zsplit = (wgs + tiles - 1) / tiles;
-            const int max_split = (K + 127) / 128;
-            if (zsplit > max_split) zsplit = max_split;
-            if (zsplit < 1) zsplit = 1;
-            const int kchunk = ((K + zsplit - 1) / zsplit + 31) / 32 * 32;
-            zsplit = (K + kchunk - 1) / kchunk;
-            const dim3 grid(tn, tm, g.n * zsplit);
-            if (xs) { if (bf16) hipLaunchKernelGGL((k_wgrad_split128<1, true>), grid, dim3(256), 0, s, g, K, kchunk, zsplit);
-                      else hipLaunchKernelGGL((k_wgrad_split128<3, true>), grid, dim3(256), 0, s, g, K, kchunk, zsplit); }
-            else if (bf16) hipLaunchKernelGGL(k_wgrad_split128<1>, grid, dim3(256), 0, s, g, K, kchunk, zsplit);
-            else hipLaunchKernelGGL(k_wgrad_split128<3>, grid, dim3(256), 0, s, g, K, kchunk, zsplit);
-            return;
-        }
-        if (sp) {
-            int tm = 1, tn = 1;
-            for (int p = 0; p < g.n; ++p) { tm = max(tm, g.M[p] / 64); tn = max(tn, g.N[p] / 64); }
-            const int wgs = g_train_tune.wgrad_split_wgs64;
-            int zsplit = (wgs + tm * tn * g.n - 1) / (tm * tn * g.n);
-            const int max_split = (K + 127) / 128;
-            if (zsplit > max_split) zsplit = max_split;
-            if (zsplit < 1) zsplit = 1;
-            const int kchunk = ((K + zsplit - 1) / zsplit + 63) / 64 * 64;
-            zsplit = (K + kchunk - 1) / kchunk;
-            const dim3 grid(tn, tm, g.n * zsplit);
-            if (xs) { if (bf16) hipLaunchKernelGGL((k_wgrad_split<1, true>), grid, dim3(256), 0, s, g, K, kchunk, zsplit);
-                      else hipLaunchKernelGGL((k_wgrad_split<3, true>), grid, dim3(256), 0, s, g, K, kchunk, zsplit); }
-            else if (bf16) hipLaunchKernelGGL(k_wgrad_split<1>, grid, dim3(256), 0, s, g, K, kchunk, zsplit);
-            else hipLaunchKernelGGL(k_wgrad_split<3>, grid, dim3(256), 0, s, g, K, kchunk, zsplit);
-            return;
-        }
-    }
-    const int target_wgs = g_train_tune.wgrad_wgs;      // default 768: 3 workgroups (49 KB of LDS each) per CU; sweep: profiles/r02_t3_training_round2.txt
-    int zsplit = (target_wgs + tm * tn * g.n - 1) / (tm * tn * g.n);
-    const int max_split = (K + 127) / 128;
-    if (zsplit > max_split) zsplit = max_split;
-    if (zsplit < 1) zsplit = 1;
-    const int kchunk = ((K + zsplit - 1) / zsplit + 63) / 64 * 64;
-    zsplit = (K + kchunk - 1) / kchunk;
-    const dim3 grid(tn, tm, g.n * zsplit), block(256);
-    if (xs) { if (bf16) hipLaunchKernelGGL((k_wgrad_group<true, true>), grid, block, 0, s, g, K, kchunk, zsplit);
-              else hipLaunchKernelGGL((k_wgrad_group<false, true>), grid, block, 0, s, g, K, kchunk, zsplit); }
-    else if (bf16) hipLaunchKernelGGL(k_wgrad_group<true>, grid, block, 0, s, g, K, kchunk, zsplit);
-    else hipLaunchKernelGGL(k_wgrad_group<false>, grid, block, 0, s, g, K, kchunk, zsplit);
+    WgradShapes sh; sh.n = g.n;
+    for (int p = 0; p < g.n; ++p)
+        sh.p[p] = WgradShape{g.M[p], g.N[p], g.lddy[p] % 4, g.ldx[p] % 4,
+                             (reinterpret_cast<uintptr_t>(g.dy[p]) & 15) == 0 && (reinterpret_cast<uintptr_t>(g.x[p]) & 15) == 0, g.xs[p]};
+    const WgradPlan pl = plan_wgrad(sh, K, bf16, split3, force3, tune);
+    typedef void (*Kernel)(WgradBatch, int, int, int);
+    static const Kernel tab[3][2][2] = {       // [WgradKernel][bf16 operands][xs]
+        {{k_wgrad_group<false>, k_wgrad_group<false, true>}, {k_wgrad_group<true>, k_wgrad_group<true, true>}},
+        {{k_wgrad_split<3>, k_wgrad_split<3, true>}, {k_wgrad_split<1>, k_wgrad_split<1, true>}},
+        {{k_wgrad_split128<3>, k_wgrad_split128<3, true>}, {k_wgrad_split128<1>, k_wgrad_split128<1, true>}}};
+    hipLaunchKernelGGL(tab[(int)pl.kernel][pl.pieces == 1][pl.xs], dim3(pl.grid[0], pl.grid[1], pl.grid[2]), dim3(256), 0, s, g, K, pl.kchunk, pl.zsplit);
 }
 
 // ------------------------------------------------------------------------------------
@@ -693,38 +623,27 @@ void tr_repack(const float* theta, const void* frag_tab, int n_frag, int max_fra
     hipLaunchKernelGGL(k_repack_misc, dim3((max_misc + 255) / 256, n_misc), dim3(256), 0, s, theta, (const RepackMisc*)misc_tab);
 }
 
+// the 64 instantiations of the training GEMM, indexed by SgemmPlan::slot(): bf16 operands, the 64-wide k tile, ta, tb, VECA, VECB
+typedef void (*SgemmKernel)(int, int, int, const float*, int, const float*, int, float*, int, const float*, float, int, int, int, float*, int);
+template <int I> static SgemmKernel sgemm_kernel() {
+    constexpr int KT = (I & 16) ? 64 : 32;
+    constexpr bool TA = (I & 8) != 0, TB = (I & 4) != 0, VA = (I & 2) != 0, VB = (I & 1) != 0;
+    if constexpr ((I & 32) != 0) return k_sgemm_bf16<KT, TA, TB, VA, VB>; else return k_sgemm<KT, TA, TB, VA, VB>;
+}
+template <int... I> static SgemmKernel sgemm_kernel_of(int slot, std::integer_sequence<int, I...>) {
+    static const SgemmKernel tab[] = {sgemm_kernel<I>()...};
+    return tab[slot];
+}
 void cmdgen_sgemm(bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
                   int ldc, const float* bias, float alpha, bool accumulate, int split_k, hipStream_t s,
                   int epi, float* aux, int ldaux, bool bf16) {
     if (M <= 0 || N <= 0 || K <= 0) return;
-    const int tiles = ((N + 63) / 64) * ((M + 63) / 64);
-    if (split_k == 0) {
-        split_k = (1024 + tiles - 1) / tiles;
-        const int max_split = (K + 127) / 128;
-        if (split_k > max_split) split_k = max_split;
-        if (split_k < 1) split_k = 1;
-    }
-    int kchunk = K, z = 1;
-    if (split_k > 1) {
-        kchunk = ((K + split_k - 1) / split_k + 63) / 64 * 64;
-        z = (K + kchunk - 1) / kchunk;
-    }
-    // split-K partials are combined with atomics: the destination must already hold the value to add to
-    const dim3 grid((N + 63) / 64, (M + 63) / 64, z), block(256);
-    const int acc = accumulate ? 1 : 0;
     auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    const bool va = al(A) && (lda % 4 == 0), vb = al(B) && (ldb % 4 == 0);      // weights inside the flat buffer may be unaligned
-    const bool fat = (long)grid.x * grid.y * grid.z < 1024;      // few workgroups: 64-wide k tiles (see TG_LD)
-#define SGK(KT_, TA_, TB_, VA_, VB_) do { if (bf16) hipLaunchKernelGGL((k_sgemm_bf16<KT_, TA_, TB_, VA_, VB_>), grid, block, 0, s, M, N, K, A, lda, B, ldb, C, ldc, bias, alpha, acc, kchunk, z > 1 ? 0 : epi, aux, ldaux); \
-        else hipLaunchKernelGGL((k_sgemm<KT_, TA_, TB_, VA_, VB_>), grid, block, 0, s, M, N, K, A, lda, B, ldb, C, ldc, bias, alpha, acc, kchunk, z > 1 ? 0 : epi, aux, ldaux); } while (0)
-#define SG(TA_, TB_, VA_, VB_) do { if (fat) SGK(64, TA_, TB_, VA_, VB_); else SGK(32, TA_, TB_, VA_, VB_); } while (0)
-#define SG2(TA_, TB_) do { if (va && vb) SG(TA_, TB_, true, true); else if (va) SG(TA_, TB_, true, false); \
-                           else if (vb) SG(TA_, TB_, false, true); else SG(TA_, TB_, false, false); } while (0)
-    if (!ta && tb) SG2(false, true); else if (!ta && !tb) SG2(false, false);
-    else if (ta && !tb) SG2(true, false); else SG2(true, true);
-#undef SG2
-#undef SG
-#undef SGK
+    // weights inside the flat buffer may be unaligned
+    const SgemmPlan pl = plan_sgemm(ta, tb, M, N, K, al(A) && (lda % 4 == 0), al(B) && (ldb % 4 == 0), split_k, bf16, epi);
+    // split-K partials are combined with atomics: the destination must already hold the value to add to
+    hipLaunchKernelGGL(sgemm_kernel_of(pl.slot(), std::make_integer_sequence<int, 64>{}), dim3(pl.grid[0], pl.grid[1], pl.grid[2]), dim3(256), 0, s,
+                       M, N, K, A, lda, B, ldb, C, ldc, bias, alpha, accumulate ? 1 : 0, pl.kchunk, pl.epi, aux, ldaux);
 }
 
 // ------------------------------------------------------------------------------------
@@ -964,18 +883,16 @@ void tr_repack_half16(const float* theta, const void* tab, int n, int max8, hipS
     hipLaunchKernelGGL(k_repack_half16, dim3((max8 + 255) / 256, n), dim3(256), 0, s, theta, (const RepackHalf16*)tab);
 }
 void cmdgen_dgrad_split(int M, const float* A0, const void* W0, const float* A1, const void* W1, float* Y, bool accumulate, float div,
-                        const float* pre, hipStream_t s, int pieces, const void* W0b, float* Yb,
+                        const float* pre, hipStream_t s, const TrainTune& tune, int pieces, const void* W0b, float* Yb,
                         bool accumulate_b, float div_b, int force_mt, const float* Yin, const float* rowdiv_b) {
     if (M <= 0) return;
     if (!Yin) Yin = Y;
-    const int mt = g_train_tune.dgrad_mt;
-    const bool big = force_mt ? force_mt == 64 : (mt ? mt == 64 : M >= 24576);     // force_mt: cmdgen_debug_dgrad
-    const int acc = accumulate ? 1 : 0, ny = W0b ? 2 : 1;
-#define DG(MT_, NP_) hipLaunchKernelGGL((k_dgrad_split<MT_, NP_>), dim3((M + MT_ - 1) / MT_, ny), dim3(256), 0, s, M, A0, W0, A1, W1, Y, acc, div, pre, \
-                                        W0b, Yb, accumulate_b ? 1 : 0, div_b, Yin, rowdiv_b)
-    if (pieces == 3) { if (big) DG(64, 3); else DG(32, 3); }
-    else { if (big) DG(64, 1); else DG(32, 1); }
-#undef DG
+    const int mt = plan_dgrad(M, tune, force_mt);
+    typedef void (*Kernel)(int, const float*, const void*, const float*, const void*, float*, int, float, const float*, const void*, float*, int, float,
+                           const float*, const float*);
+    static const Kernel tab[2][2] = {{k_dgrad_split<32, 1>, k_dgrad_split<32, 3>}, {k_dgrad_split<64, 1>, k_dgrad_split<64, 3>}};     // [64 rows][three pieces]
+    hipLaunchKernelGGL(tab[mt == 64][pieces == 3], dim3((M + mt - 1) / mt, W0b ? 2 : 1), dim3(256), 0, s, M, A0, W0, A1, W1, Y, accumulate ? 1 : 0, div, pre,
+                       W0b, Yb, accumulate_b ? 1 : 0, div_b, Yin, rowdiv_b);
 }
 
 // g <- g * SiLU'(pre)
@@ -2082,11 +1999,11 @@ void tr_edge_tail_bwd(int E, int H, const int* row, const int* col, const float*
 // fused: g = (dY W2^T-pack) * SiLU'(pre1) and its whole tail (H = 256; W = split pack of the transposed weight)
 void cmdgen_dgrad_tail(int E, const float* dY, const void* Wt, const float* pre1, const int* row, const int* col, const float* d0,
                        const float* Wcol, int ldw, const float4* X, float nc, const float4* dcd, int n_moving, float* dP, float* dQ,
-                       float* dWcol, float* dX, float* scratch, int pieces, hipStream_t s, bool defer_reduce,
+                       float* dWcol, float* dX, float* scratch, int pieces, hipStream_t s, unsigned long long* dbg, bool defer_reduce,
                        const float* Wd, float* dd0) {
     if (E <= 0) return;
     const int nwg = (E + 31) / 32;
-    const TailArgs ta{row, col, d0, Wcol, ldw, X, nc, dcd, n_moving, dP, dQ, scratch, dX, g_train_tune.dbg, Wd, dd0};
+    const TailArgs ta{row, col, d0, Wcol, ldw, X, nc, dcd, n_moving, dP, dQ, scratch, dX, dbg, Wd, dd0};
     if (dd0) {
         if (pieces == 3) hipLaunchKernelGGL((k_dgrad_tail<3, true>), dim3(nwg), dim3(256), 0, s, E, dY, Wt, pre1, ta);
         else hipLaunchKernelGGL((k_dgrad_tail<1, true>), dim3(nwg), dim3(256), 0, s, E, dY, Wt, pre1, ta);

@@ -774,7 +774,7 @@ int cmdgen_set_gemm_mode(cmdgen_handle* h, int32_t split_bf16);
  *                        last block only; 0: off)
  *   chain                "graph_steps" (denoising steps per captured graph, default 8)
  *   training step        "wgrad_split" -1|0|1 (-1: three-piece weight gradients wherever the handle runs the split engine), "wgrad_tile" 0|64, "wgrad_split_wgs128", "wgrad_split_wgs64", "wgrad_wgs",
- *                        "dgrad_mt" 0|32|64, "dgrad_tail" 0|1   (see TrainTune in csrc/cmdgen_dev.h);
+ *                        "dgrad_mt" 0|32|64, "dgrad_tail" 0|1   (see TrainTune in csrc/cmdgen_train_plan.h);
  *                        "wgrad_stream" 0|1|2 (weight / bias gradients and partial-sum reductions on the handle's second stream beside the chain
  *                        of data gradients; 2: at the lowest stream priority; default 1), "train_half" 0|1|2 (the training forward's tile kernels on
  *                        the half engine, packs and scales re-made on the device every step; 2: the two edge kernels only; default 1 where

@@ -64,6 +64,38 @@ def test_training_gemm_all_layouts(ta, tb):
     assert (C.double() - want).abs().max() <= 2e-5 * float(want.abs().max())
 
 
+@pytest.mark.parametrize('M,N,K,kt', [(70, 33, 72, 64), (2048, 2048, 72, 32)])
+def test_training_gemm_dispatch_table(M, N, K, kt):
+    """cmdgen_sgemm picks one of 64 instantiations from a table (SgemmPlan::slot, csrc/cmdgen_train_plan.h): every ta / tb pair, A and B 16-byte
+    aligned or not (a view shifted by one column of a matrix whose leading dimension is a multiple of 4), fp32 and bf16 operands, on the 64-wide
+    k tile (a few workgroups) and on the 32-wide one (2048 x 2048: 1024 workgroups, the smallest count that takes it) - each against the float64
+    product, within the bounds of test_training_gemm_all_layouts (fp32) and test_bf16_gemm_equals_fp32_product_of_rounded_operands (bf16)."""
+    h = make_handle(ModelConfig(hidden_nf=64, n_layers=1))
+    assert ((M + 63) // 64) * ((N + 63) // 64) >= 1024 if kt == 32 else ((M + 63) // 64) * ((N + 63) // 64) < 1024
+    g = torch.Generator().manual_seed(3)
+    A, B = torch.randn(M, K, generator=g).cuda(), torch.randn(K, N, generator=g).cuda()          # the logical operands: C = A B
+    want32 = A.double() @ B.double()
+    want16 = A.to(torch.bfloat16).double() @ B.to(torch.bfloat16).double()
+    scale32, scale16 = max(1.0, float(want32.abs().max())), max(1.0, float(want16.abs().max()))
+
+    def stored(X, transposed, shift):          # X (or its transpose) as a view at column `shift` of a matrix with ld % 4 == 0
+        X = X.t() if transposed else X
+        base = torch.zeros(X.shape[0], (X.shape[1] + 1 + 3) // 4 * 4, device='cuda')
+        view = base[:, shift:shift + X.shape[1]]
+        view.copy_(X)
+        assert base.stride(0) % 4 == 0 and (view.data_ptr() % 16 == 0) == (shift == 0)
+        return view
+    for ta in (False, True):
+        for tb in (False, True):
+            for sa in (0, 1):
+                for sb in (0, 1):
+                    Av, Bv = stored(A, ta, sa), stored(B, tb, sb)              # ta: A is stored [K][M]; tb: B is stored [N][K]
+                    got = h.debug_sgemm(Av, Bv, ta=ta, tb=tb)
+                    assert (got.double() - want32).abs().max() <= 1e-5 * scale32, (ta, tb, sa, sb)
+                    got = h.debug_sgemm(Av, Bv, ta=ta, tb=tb, bf16=True)
+                    assert (got.double() - want16).abs().max() <= 2e-5 * scale16, (ta, tb, sa, sb, 'bf16')
+
+
 # ------------------------------------------------------------------ forward
 def case_inputs(cfg, B, first, rng, spread=3.0):
     while True:

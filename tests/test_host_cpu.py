@@ -243,6 +243,97 @@ def test_planner_header_is_plain_cpp():
     assert (got[:, k['node_mfmas_per_product']] == np.where(got[:, k['node_mt']] >= 32, 6, 1)).all()
 
 
+def _train_plan_sweep():
+    """Every case of the training-step planner sweep: weight-gradient groups, plain GEMMs, data gradients (tests/train_plan_ref.py: run_planner)."""
+    import train_plan_ref as tp
+    Ks = (1, 63, 64, 127, 128, 129, 3721, 8191, 8192, 16127, 32767, 32768, 36147, 65535, 65536, 156316)
+    sq = tp.shape(256, 256)
+    groups = [[sq], [sq] * 3, [sq] * 4, [sq] * 7, [sq] * 8,               # 3 / 4: the two node-level groups of a block (coord_mlp.0's halves + node_mlp.2; node_mlp.0's + edge_mlp.0's)
+              [tp.shape(256, 512), sq],                                   # a whole 256 x 512 first layer beside one of its halves
+              [tp.shape(64, 128)], [tp.shape(40, 24)],                    # 64-tile only; the generic kernel only
+              [tp.shape(256, 256, aligned=0)], [sq, tp.shape(256, 256, lddy_mod4=2)], [tp.shape(256, 256, ldx_mod4=1), sq]]
+    tunes = [dict(tp.TUNE)] + [dict(tp.TUNE, **o) for o in ({'wgrad_split': 0}, {'wgrad_split': 1}, {'wgrad_tile': 64}, {'wgrad_k128': 1},
+                                                           {'wgrad_split_wgs128': 100}, {'wgrad_split_wgs64': 100}, {'wgrad_wgs': 100})]
+    cases = []
+    for tune in tunes:
+        for g in groups:
+            for xs in (0, 1):
+                shapes = [s[:5] + (xs,) if i == 0 else s for i, s in enumerate(g)]
+                for K in Ks:
+                    for flags in range(8):
+                        cases.append(('wgrad', tune, shapes, K, flags & 1, (flags >> 1) & 1, (flags >> 2) & 1))
+    gemm_shapes = [(64, 64, 16), (70, 33, 20), (1, 256, 514), (300, 8, 11), (257, 129, 1000), (5, 5, 3), (24, 64, 5000),      # test_training_gemm_all_layouts
+                   (31 * 64, 33 * 64, 72), (2048, 2048, 72), (256, 256, 36147), (2048, 2048, 1000)]                          # 1023 and 1024 workgroups; long K
+    for M, N, K in gemm_shapes:
+        for split_k in (0, 1, 7):
+            for bits in range(32):
+                for epi in (0, 1, 2):
+                    cases.append(('sgemm', bits & 1, (bits >> 1) & 1, M, N, K, (bits >> 2) & 1, (bits >> 3) & 1, split_k, (bits >> 4) & 1, epi))
+    for mt in (0, 32, 64):
+        tune = dict(tp.TUNE, dgrad_mt=mt)
+        for M in (1, 24575, 24576, 100000):
+            for force in (0, 32, 64):
+                cases.append(('dgrad', tune, M, force))
+    return cases
+
+
+def test_training_planners_are_the_former_launchers_decisions():
+    """tests/train_plan_check.cpp: plan_wgrad, plan_sgemm and plan_dgrad (csrc/cmdgen_train_plan.h) on the host against the rules cmdgen_wgrad_group,
+    cmdgen_sgemm and cmdgen_dgrad_split evaluated themselves before the header existed (tests/train_plan_ref.py, transcribed from that source): every
+    field of every plan, over a sweep that is checked to reach every outcome and both sides of every threshold."""
+    import train_plan_ref as tp
+    cases = _train_plan_sweep()
+    got = tp.run_planner(cases)
+    bad = [(c, g, tp.reference(c)) for c, g in zip(cases, got) if g != tp.reference(c)]
+    assert not bad, (len(bad), bad[:3])
+    w = [(c, g) for c, g in zip(cases, got) if c[0] == 'wgrad']
+    assert {g[:3] for _, g in w} == {(k, p, x) for k in (tp.GROUP, tp.SPLIT64, tp.SPLIT128) for p in (1, 3) for x in (0, 1)}     # kernel x pieces x xs
+    # the threshold K x 128-tiles >= wgrad_k128: default options, three pieces by the engine (not forced), shapes the 128-tile kernel takes
+    fits128 = lambda shapes: all(s[0] % 128 == 0 and s[1] % 128 == 0 and s[2] == 0 and s[3] == 0 and s[4] for s in shapes)
+    by_rule = {(c[3] * sum((s[0] // 128) * (s[1] // 128) for s in c[2]) >= tp.TUNE['wgrad_k128'], g[0]) for c, g in w
+               if c[1] == tp.TUNE and (c[4], c[5], c[6]) == (0, 1, 0) and fits128(c[2])}
+    assert by_rule == {(False, tp.SPLIT64), (True, tp.SPLIT128)}
+    by_k = {(c[3] >= 65536, g[0]) for c, g in w if c[1] == tp.TUNE and (c[4], c[6]) == (1, 0) and fits128(c[2])}                # bf16 operands: K >= 65536
+    assert by_k == {(False, tp.SPLIT64), (True, tp.SPLIT128)} and {c[3] for c, _ in w} >= {65535, 65536}
+    s = [(c, g) for c, g in zip(cases, got) if c[0] == 'sgemm']
+    assert {(g[1] * g[2] * g[3] >= 1024, g[0]) for _, g in s} == {(False, 64), (True, 32)}                                         # 1024 workgroups: the k tile
+    assert {g[1] * g[2] * g[3] for _, g in s} >= {1023, 1024} and {g[7] for _, g in s} == set(range(64))                           # ... and every instantiation
+    assert {g[5] > 1 for _, g in s} == {False, True} and all(g[6] == (0 if g[5] > 1 else c[10]) for c, g in s)
+    d = [(c, g) for c, g in zip(cases, got) if c[0] == 'dgrad']
+    assert {(c[2] >= 24576, g[0]) for c, g in d if c[1]['dgrad_mt'] == 0 and c[3] == 0} == {(False, 32), (True, 64)}               # 24576 rows: the tile
+    assert {c[2] for c, _ in d} >= {24575, 24576} and {g[0] for c, g in d if c[2] == 1} == {32, 64}                                # (an option or a test overrides it)
+
+
+def test_training_planner_fixed_points():
+    """The thresholds of the weight-gradient and data-gradient rules at their defaults, as literals: a 256 x 256 product has four 128 x 128 tiles, so
+    K x tiles >= 131072 is K >= 32768 for one product and K >= 8192 for four; bf16 operands change at 65536 rows; the data gradient at 24576."""
+    import train_plan_ref as tp
+    one, four = [tp.shape(256, 256)], [tp.shape(256, 256)] * 4
+    tune = dict(tp.TUNE)
+    assert tune['wgrad_k128'] == 131072 and tune['wgrad_split'] == -1 and tune['dgrad_mt'] == 0
+    got = tp.run_planner([('wgrad', tune, one, 32767, 0, 1, 0), ('wgrad', tune, one, 32768, 0, 1, 0),
+                          ('wgrad', tune, four, 8191, 0, 1, 0), ('wgrad', tune, four, 8192, 0, 1, 0),
+                          ('wgrad', tune, one, 65535, 1, 1, 0), ('wgrad', tune, one, 65536, 1, 1, 0),
+                          ('dgrad', tune, 24575, 0), ('dgrad', tune, 24576, 0)])
+    assert [g[:2] for g in got[:6]] == [(1, 3), (2, 3), (1, 3), (2, 3), (1, 1), (2, 1)]          # (kernel: 1 = 64-tile split, 2 = 128-tile split; pieces)
+    assert got[6:] == [(32,), (64,)]
+    # one product at K = 32768 on 128 tiles: 4 tiles, 384 / 4 = 96 workgroups each, 32768 / 96 -> chunks of 352 rows, 94 of them
+    assert got[1] == (2, 3, 0, 2, 2, 94, 352, 94)
+
+
+def test_training_planner_header_is_plain_cpp_and_the_globals_are_gone():
+    """cmdgen_train_plan.h takes no HIP header and no cmdgen_handle (train_plan_check.cpp compiles it with -x c++), and no launcher of the training step
+    reads a precision or a tuning that some earlier call left in a global."""
+    csrc = os.path.join(ROOT, 'cmdgen_amd', 'csrc')
+    src = open(os.path.join(csrc, 'cmdgen_train_plan.h')).read()
+    assert all(inc.startswith('<') and 'hip' not in inc for inc in re.findall(r'#include\s+(\S+)', src)) and 'cmdgen_handle' not in src
+    assert 'struct TrainTune' in src and 'dbg' not in src
+    for f in os.listdir(csrc):
+        if f.endswith(('.hip', '.h')):
+            text = open(os.path.join(csrc, f)).read()
+            assert 'g_train_tune' not in text and 'g_bf16' not in text, f
+
+
 def test_product_fails_loudly_without_gpu():
     if torch.cuda.is_available():
         pytest.skip('GPU present')
