@@ -702,7 +702,7 @@ static std::vector<float> step_table(const cmdgen_handle* h, int K) {
 }
 
 // ---------------------------------------------------------------------------------
-// the chains: what the entries of all nine kinds share.  A kind's state lives in its slot (h->chains[kind]); its ChainAlloc composes
+// the chains: what the entries of all ten kinds share.  A kind's state lives in its slot (h->chains[kind]); its ChainAlloc composes
 // the parts it uses (alloc_chain_buf, alloc_inpaint_part, point_group_tab, alloc_restrain_part, alloc_score_part); its entry reads top to
 // bottom: checks, tables, Chain::open, its init launches, Chain::start, Chain::steps with its step launch, its final launches, Chain::close.
 // ---------------------------------------------------------------------------------
@@ -896,13 +896,14 @@ static int alloc_inpaint_part(cmdgen_handle* h, ChainSlot& k, const float* coef2
     return slot_alloc(h, k, ip.poff, (size_t)h->lay.B);
 }
 // the restrained kinds' RestrainBuf: the guidance tail append_guidance packed at `guide` in the table block (n_rows guide rows), and com(P_in)
-static int alloc_restrain_part(cmdgen_handle* h, ChainSlot& k, const float* guide, int n_rows) {
+// (n_owners: the samples of the layout, or the groups of the restrained multi-pocket chain - the CSR offsets are [n_owners + 1])
+static int alloc_restrain_part(cmdgen_handle* h, ChainSlot& k, const float* guide, int n_rows, int n_owners) {
     RestrainBuf& rb = k.restr;
     const float* par = guide + (size_t)n_rows * 4;
     rb.sa = (const float4*)guide;
     rb.clash_r = par[0]; rb.clash_k = par[1]; rb.scale = par[2]; rb.max_shift = par[3]; rb.guide_below = par[4];
     rb.rstart = (const int*)(par + 8);
-    rb.rec = (const RestraintRec*)(par + 8 + (size_t)h->lay.B + 1);
+    rb.rec = (const RestraintRec*)(par + 8 + (size_t)n_owners + 1);
     rb.op_energy = nullptr;
     return slot_alloc(h, k, rb.pin_com, (size_t)h->lay.B);
 }
@@ -913,7 +914,7 @@ static int alloc_score_part(cmdgen_handle* h, ChainSlot& k) {
 }
 
 // One chain call between begin_chain and end_chain: the stream it runs on, its slot, the launch description of its evaluations and, for
-// the eight conditional kinds, the slot's ChainBuf completed with the call's pointers.
+// the nine conditional kinds, the slot's ChainBuf completed with the call's pointers.
 struct Chain {
     cmdgen_handle* h = nullptr;
     ChainSlot* k = nullptr;
@@ -1017,28 +1018,33 @@ extern "C" int cmdgen_set_guide_table(cmdgen_handle* h, int32_t K, const float* 
     return CMDGEN_OK;
 }
 
-// the restraint arguments of cmdgen_restrained_chain and cmdgen_restrained_edit_chain, checked (step_lds: the step kernel's LDS for this layout);
-// rstart [B + 1]: the CSR offsets, rec: the records sorted by sample, the fields a kind does not read zeroed
-static int check_restraints(cmdgen_handle* h, const cmdgen_restraint* restraints_host, int64_t n_restraints, float clash_radius, float clash_k,
-                            float scale, float max_shift, float guide_below, size_t step_lds, std::vector<int>& rstart,
-                            std::vector<cmdgen_restraint>& rec) {
+// who the records of a restraint list belong to (cmdgen_restraint::sample): the layout's samples, or the groups of a multi-pocket call
+struct RestraintOwners {
+    const char* one; const char* whose;              // "sample", "the layout's" | "group", "the call's"
+    std::vector<long long> nphar;                    // points of every owner
+};
+// the restraint arguments of a restrained chain, checked (step_lds: the step kernel's LDS for this layout); rstart [owners + 1]: the CSR
+// offsets, rec: the records sorted by owner, the fields a kind does not read zeroed
+static int check_restraint_list(cmdgen_handle* h, const RestraintOwners& own, const cmdgen_restraint* restraints_host, int64_t n_restraints,
+                                float clash_radius, float clash_k, float scale, float max_shift, float guide_below, size_t step_lds,
+                                std::vector<int>& rstart, std::vector<cmdgen_restraint>& rec) {
     if (n_restraints < 0 || (n_restraints > 0 && !restraints_host)) return fail(h, CMDGEN_EINVAL, "n_restraints=%lld without a restraint list", (long long)n_restraints);
     auto ok = [](float v) { return std::isfinite(v) && v >= 0.f; };
     if (!ok(clash_radius) || !ok(clash_k)) return fail(h, CMDGEN_EINVAL, "clash_radius=%g, clash_k=%g must be finite and >= 0", (double)clash_radius, (double)clash_k);
     if (!ok(scale)) return fail(h, CMDGEN_EINVAL, "scale=%g must be finite and >= 0", (double)scale);
     if (!(std::isfinite(max_shift) && max_shift > 0.f)) return fail(h, CMDGEN_EINVAL, "max_shift=%g must be finite and > 0", (double)max_shift);
     if (!(guide_below >= 0.f && guide_below <= 1.f)) return fail(h, CMDGEN_EINVAL, "guide_below=%g must be in [0, 1]", (double)guide_below);
-    const int B = h->lay.B;
+    const int B = (int)own.nphar.size();
     rstart.assign((size_t)B + 1, 0);
     for (int64_t r = 0; r < n_restraints; ++r) {
         const cmdgen_restraint& q = restraints_host[r];
         const long long ri = (long long)r;
         if (q.kind != RK_POSITION && q.kind != RK_DISTANCE && q.kind != RK_EXCLUSION) return fail(h, CMDGEN_EINVAL, "restraint %lld: unknown kind %d", ri, q.kind);
-        if (q.sample < 0 || q.sample >= B) return fail(h, CMDGEN_EINVAL, "restraint %lld: sample %d outside the layout's %d samples", ri, q.sample, B);
-        const long long nl = (long long)h->cur_nphar[q.sample];
-        if (q.kind != RK_EXCLUSION && (q.i < 0 || q.i >= nl)) return fail(h, CMDGEN_EINVAL, "restraint %lld: point %d, sample %d has %lld points", ri, q.i, q.sample, nl);
+        if (q.sample < 0 || q.sample >= B) return fail(h, CMDGEN_EINVAL, "restraint %lld: %s %d outside %s %d %ss", ri, own.one, q.sample, own.whose, B, own.one);
+        const long long nl = own.nphar[(size_t)q.sample];
+        if (q.kind != RK_EXCLUSION && (q.i < 0 || q.i >= nl)) return fail(h, CMDGEN_EINVAL, "restraint %lld: point %d, %s %d has %lld points", ri, q.i, own.one, q.sample, nl);
         if (q.kind == RK_DISTANCE) {
-            if (q.j < 0 || q.j >= nl) return fail(h, CMDGEN_EINVAL, "restraint %lld: point %d, sample %d has %lld points", ri, q.j, q.sample, nl);
+            if (q.j < 0 || q.j >= nl) return fail(h, CMDGEN_EINVAL, "restraint %lld: point %d, %s %d has %lld points", ri, q.j, own.one, q.sample, nl);
             if (q.i == q.j) return fail(h, CMDGEN_EINVAL, "restraint %lld: a distance between point %d and itself (i == j)", ri, q.i);
             if (!ok(q.a) || !ok(q.b)) return fail(h, CMDGEN_EINVAL, "restraint %lld: lo=%g, hi=%g must be finite and >= 0", ri, (double)q.a, (double)q.b);
             if (q.a > q.b) return fail(h, CMDGEN_EINVAL, "restraint %lld: lo=%g > hi=%g", ri, (double)q.a, (double)q.b);
@@ -1048,7 +1054,7 @@ static int check_restraints(cmdgen_handle* h, const cmdgen_restraint* restraints
         }
         if (!ok(q.k)) return fail(h, CMDGEN_EINVAL, "restraint %lld: k=%g must be finite and >= 0", ri, (double)q.k);
         if (++rstart[(size_t)q.sample + 1] > CMDGEN_MAX_RESTRAINTS)
-            return fail(h, CMDGEN_EINVAL, "sample %d has more than %d restraints", q.sample, CMDGEN_MAX_RESTRAINTS);
+            return fail(h, CMDGEN_EINVAL, "%s %d has more than %d restraints", own.one, q.sample, CMDGEN_MAX_RESTRAINTS);
     }
     if (step_lds > PLAN_RESTRAINED_LDS_MAX)
         return fail(h, CMDGEN_EINVAL, "a sample has %d nodes: the restrained step keeps a sample's positions, z and guidance terms in LDS (64 KiB)", h->lay.max_n);
@@ -1066,6 +1072,13 @@ static int check_restraints(cmdgen_handle* h, const cmdgen_restraint* restraints
         }
     }
     return 0;
+}
+// ... of cmdgen_restrained_chain and cmdgen_restrained_edit_chain: the records belong to the layout's samples
+static int check_restraints(cmdgen_handle* h, const cmdgen_restraint* restraints_host, int64_t n_restraints, float clash_radius, float clash_k,
+                            float scale, float max_shift, float guide_below, size_t step_lds, std::vector<int>& rstart,
+                            std::vector<cmdgen_restraint>& rec) {
+    const RestraintOwners own{"sample", "the layout's", std::vector<long long>(h->cur_nphar.begin(), h->cur_nphar.end())};
+    return check_restraint_list(h, own, restraints_host, n_restraints, clash_radius, clash_k, scale, max_shift, guide_below, step_lds, rstart, rec);
 }
 
 // The guidance tail of a table block: one guide row (sigma_t, alpha_t, 0, 0) per op, s_of[i] the level op i goes to (t = s + 1), then `spare`
@@ -1091,7 +1104,7 @@ static void append_guidance(const cmdgen_handle* h, std::vector<float>& tables, 
 // the slot's table block: the posterior rows | the guidance tail, both n_steps + 1 rows
 static int alloc_restrained(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
     const int rc = alloc_chain_buf(h, k, tables); if (rc) return rc;
-    return alloc_restrain_part(h, k, tables + (size_t)(n_steps + 1) * 4, n_steps + 1);
+    return alloc_restrain_part(h, k, tables + (size_t)(n_steps + 1) * 4, n_steps + 1, h->lay.B);
 }
 
 extern "C" int cmdgen_restrained_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot, int32_t timesteps,
@@ -1238,6 +1251,72 @@ extern "C" int cmdgen_multi_pocket_chain(cmdgen_handle* h, const float* pocket_x
     });
     if (rc) return rc;
     cmdgen_launch_multi_final(h->lay, d, c, gt, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, ch.k->cog, ch.s);
+    return ch.close();
+}
+
+// ---------------------------------------------------------------------------------
+// the restrained multi-pocket chain: cmdgen_multi_pocket_chain's chain with cmdgen_restrained_chain's guidance on the shared latent, once
+// per GROUP (kernels_restrain.hip, "The restrained MULTI-POCKET chain", holds the definition).  The slot's table block is: the posterior
+// rows | the group tables, padded to a multiple of four floats | the guidance tail with CSR offsets [G + 1] and the records sorted by
+// group - so a changed grouping, weight, restraint or scalar prepares the slot again and drops its captured steps.
+// ---------------------------------------------------------------------------------
+static size_t group_tables_floats(int B, int G) { return ((size_t)4 * B + G + 3) / 4 * 4; }
+// (the groups of the call are in the slot before Chain::open: the guidance tail lies behind G group entries)
+static int alloc_multi_restrained(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
+    int rc = alloc_multi(h, k, tables, n_steps); if (rc) return rc;
+    const float* tail = tables + (size_t)(n_steps + 1) * 4 + group_tables_floats(h->lay.B, k.groups.G);
+    rc = alloc_restrain_part(h, k, tail, n_steps + 1, k.groups.G); if (rc) return rc;
+    return slot_alloc(h, k, k.guide_d, (size_t)h->lay.Nl * 3);    // (Nl bounds the unique rows of any grouping)
+}
+
+extern "C" int cmdgen_multi_restrained_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
+                                             int64_t n_groups, const int64_t* group_size_host, const float* weight_host, int32_t timesteps,
+                                             const cmdgen_restraint* restraints_host, int64_t n_restraints,
+                                             float clash_radius, float clash_k, float scale, float max_shift, float guide_below,
+                                             const float* noise, uint64_t seed, const int64_t* group_ids_host,
+                                             float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                                             float* energy_out, float* op_energy_out, int32_t use_graph, cmdgen_stream stream) {
+    int rc = check_ready(h); if (rc) return rc;
+    rc = refuse_joint_no_com(h, "the restrained multi-pocket chain", kPocketDiffuses, ": the guidance frame follows the centre-of-mass projections");
+    if (rc) return rc;
+    if (!pocket_x || !pocket_onehot || !group_size_host || !weight_host || !xh_phar_out || !xh_pocket_out || !energy_out)
+        return fail(h, CMDGEN_EINVAL, "null pointer");
+    const int K = timesteps;
+    rc = check_timesteps(h, K); if (rc) return rc;
+    GroupPlan gp;
+    rc = build_group_plan(h, n_groups, group_size_host, weight_host, group_ids_host, gp); if (rc) return rc;
+    RestraintOwners own{"group", "the call's", {}};
+    for (int g = 0; g < gp.G; ++g) own.nphar.push_back((long long)h->cur_nphar[(size_t)gp.gfirst[g]]);
+    std::vector<int> rstart; std::vector<cmdgen_restraint> rec;
+    // (the step keeps k_multi_step_count's LDS, which build_group_plan has checked, and the guide kernel less)
+    rc = check_restraint_list(h, own, restraints_host, n_restraints, clash_radius, clash_k, scale, max_shift, guide_below, 0, rstart, rec);
+    if (rc) return rc;
+    std::vector<float> tables = step_table(h, K);
+    const size_t t0 = tables.size();
+    append_group_tables(tables, gp, weight_host, h->lay.B);
+    tables.resize(t0 + group_tables_floats(h->lay.B, gp.G), 0.f);
+    std::vector<int> s_of((size_t)K);
+    for (int i = 0; i < K; ++i) s_of[(size_t)i] = K - 1 - i;
+    append_guidance(h, tables, K, s_of, 1, {clash_radius, clash_k, scale, max_shift, guide_below}, rstart, rec);
+    h->chains[CHAIN_MULTI_RESTRAINED].groups.G = gp.G;            // alloc_multi_restrained reads it
+    Chain ch;
+    rc = ch.open(h, CHAIN_MULTI_RESTRAINED, tables, K, alloc_multi_restrained, gp.gid.data(), noise, seed, z_steps_out, pocket_steps_out, use_graph, stream);
+    if (rc) return rc;
+    const Dims& d = h->dims;
+    const ChainBuf& c = ch.c;
+    const GroupTab gt = group_tab(*ch.k, gp);
+    RestrainBuf rb = ch.k->restr;
+    rb.op_energy = op_energy_out;
+    float* const gd = ch.k->guide_d;
+    cmdgen_launch_multi_init(h->lay, d, c, gt, pocket_x, pocket_onehot, ch.s);
+    cmdgen_launch_restrain_prep(h->lay, d, rb, pocket_x, ch.s);  // com(P_in) of every member; the guidance reads the first member's
+    ch.start(true);                                  // evaluation 0 (t = 1)
+    rc = ch.steps({noise, z_steps_out, pocket_steps_out, op_energy_out, nullptr}, K, [&](hipStream_t ss) {
+        cmdgen_launch_multi_restrained_step(h->lay, d, c, gt, rb, h->work, h->work.eps_tmp, gd, ss);
+    });
+    if (rc) return rc;
+    cmdgen_launch_multi_final(h->lay, d, c, gt, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, ch.k->cog, ch.s);
+    cmdgen_launch_multi_restrain_energy(h->lay, d, gt, rb, xh_phar_out, xh_pocket_out, energy_out, ch.s);
     return ch.close();
 }
 
@@ -1534,7 +1613,7 @@ extern "C" int cmdgen_inpaint_chain(cmdgen_handle* h, const float* pocket_x, con
 static int alloc_restrained_edit(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
     int rc = alloc_chain_buf(h, k, tables); if (rc) return rc;
     rc = alloc_inpaint_part(h, k, tables + (size_t)(n_steps + 1) * 4, n_steps); if (rc) return rc;
-    return alloc_restrain_part(h, k, tables + (size_t)(3 * n_steps + 1) * 4, n_steps);
+    return alloc_restrain_part(h, k, tables + (size_t)(3 * n_steps + 1) * 4, n_steps, h->lay.B);
 }
 
 extern "C" int cmdgen_restrained_edit_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,

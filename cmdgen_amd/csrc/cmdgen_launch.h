@@ -60,6 +60,12 @@ void cmdgen_launch_restrained_edit_step_count(const Layout& lay, const Dims& d, 
                                               const Work& w, const float* eps, hipStream_t s);   // the edit chain's op with the guidance in op A
 void cmdgen_launch_restrain_energy(const Layout& lay, const Dims& d, const RestrainBuf& rb, const float* xo, const float* po,
                                    float* energy_out, hipStream_t s);
+// ... and the restrained multi-pocket chain: per op k_multi_guide (one workgroup per group: the displacement gd [Nu][3]) and then
+// k_multi_restrained_step_count (one per member); RestrainBuf::rstart and op_energy are per GROUP, energy_out is [G][2]
+void cmdgen_launch_multi_restrained_step(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const RestrainBuf& rb,
+                                         const Work& w, const float* eps, float* gd, hipStream_t s);
+void cmdgen_launch_multi_restrain_energy(const Layout& lay, const Dims& d, const GroupTab& g, const RestrainBuf& rb, const float* xo,
+                                         const float* po, float* energy_out, hipStream_t s);
 
 // kernels_multi.hip: the multi-pocket chain (groups of samples that share one latent)
 void cmdgen_launch_multi_init(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const float* px, const float* poh,

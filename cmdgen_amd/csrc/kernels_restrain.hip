@@ -520,6 +520,262 @@ __global__ __launch_bounds__(1024) void k_restrained_edit_step_count(Layout lay,
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// The restrained MULTI-POCKET chain (ConditionalDDPM.sample_restrained_given_pockets, cmdgen_multi_restrained_chain): the guidance of this
+// file's header on the shared latent of kernels_multi.hip.  The chain is cmdgen_multi_pocket_chain's - the same layout of B member samples
+// in G groups, the same init, ops, draws, Philox counters (keyed by group id), decode and CoG re-centring - with steps 1-5 of the header
+// in the mean of every posterior op, applied PER GROUP, and these points settled:
+//   Restraints belong to a group: RestraintRec::sample is the group index g, point indices are < n_phar[g], centres are given in the
+//     common frame in which the caller gives the group's pockets.  RestrainBuf::rstart is [G + 1], op_energy [K][G], energy_out [G][2].
+//   1. Denoised estimate.  xhat_i = n_x (z.x_i - sigma_t ebar_i) / alpha_t with ebar = sum_m w_m eps_m, what the step itself uses
+//      (combine_eps: m ascending, the first term not added to a zero); its x columns are zero under the batch-wide NaN guard.
+//   2. Frame.  shift_g = n_x (com(P_first.x) - com(P_first,in.x / n_x)), from the group's FIRST member, its pocket as it stands at the
+//      op's input - the multi-pocket edit chain's precedent (the offset of its step B is the first member's), and what edit_phars_multi
+//      moves results back by.
+//   3. Clash.  The sum runs over every point of the group and every pocket atom of EVERY member, q_{m,a} = n_x P_m.x_a as it stands at the
+//      op's input; unweighted, weight-0 members included: a point must clash with neither pocket.  A point's terms: the group's records and
+//      the first member's atoms (point_terms, exactly k_restrained_step_count's sums), then member by member, ascending, the atoms of each
+//      further member (point_terms again, without records), the members' sums added in that order.  No float atomics.
+//   4. / 5.  d_i, the max_shift clip, guide_below and mu.x_i = z.x_i / coef.x - coef.y ebar_i + d_i / n_x as in the header.  Every member
+//      adds the SAME BITS d_i (one copy per group, read from global memory), so the members' copies of z stay bit-identical.
+//   The decode is not guided.  energy_out: E and the largest violation of the returned rows against every member's returned pocket, the
+//   shift taken from the first member's returned pocket (k_multi_restrain_energy).
+// Two launches per op, because a guidance term computed inside the step launch would read the other members' pocket rows while their
+// workgroups translate them:
+//   k_multi_guide                  one workgroup per GROUP: steps 1-4.  Reads the first member's copy of z, all members' eps rows and all
+//                                  members' pockets - nothing in this launch writes any of them - and writes d [Nu][3] and op_energy.
+//   k_multi_restrained_step_count  one workgroup per MEMBER: k_multi_step_count with d_i / n_x in the mean.  Reads d, which nothing in
+//                                  this launch writes, and otherwise only what k_multi_step_count reads.
+// Reductions that hold bit for bit on every output, the chain status and the "chain_z" debug read:
+//   - no record on any group and r_c = 0, or scale = 0, or guide_below = 0: cmdgen_multi_pocket_chain's outputs.  A group-op that is not
+//     guided (no record on the group while r_c = 0, scale = 0, t / T > guide_below) adds nothing to the mean, not even a zero;
+//   - every M_g = 1: cmdgen_restrained_chain's outputs on a handle whose evaluations use their own k_readout (readout_in_coord = 0),
+//     energy_out and op_energy_out included;
+//   - two runs of the same inputs are equal bit for bit, captured or eager.
+// ------------------------------------------------------------------------------------------------------------
+namespace {
+// the index of the group whose first member is `first` (GroupTab::group_first is ascending)
+__device__ __forceinline__ int group_index(const GroupTab& g, int first) {
+    int lo = 0, hi = g.G - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (g.group_first[mid] <= first) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+}  // namespace
+
+// steps 1-4 for one group.  LDS: one member's pocket atoms [max_n] float4 at a time, then xhat [nl][3], the gradient sums [nl][3], e [nl].
+__global__ __launch_bounds__(1024) void k_multi_guide(Layout lay, Dims d, ChainBuf c, GroupTab g, RestrainBuf rb, Work w,
+                                                     const float* __restrict__ eps, float* __restrict__ gd) {
+    extern __shared__ float4 s_q[];                 // [max_n] pocket atoms of the member at hand
+    float* s_xh = reinterpret_cast<float*>(s_q + lay.max_n);      // [nl][3] xhat, Angstrom
+    float* s_g = s_xh + (size_t)lay.max_n * 3;                    // [nl][3] dE / dxhat
+    float* s_e = s_g + (size_t)lay.max_n * 3;                     // [nl] the points' shares of E
+    __shared__ float s_shift[3];
+    const int grp = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6, nt = blockDim.x;
+    const int first = g.group_first[grp], M = g.size[first], ub = g.ubase[first];
+    const int nl = lay.num_phar[first], pb = lay.phar_base[first];
+    const int ld = 3 + d.P, ldq = 3 + d.R;
+    const int step = c.state->step - 1;
+    const float4 cf = c.coef[step];
+    const float4 sa = rb.sa[step];
+    const int r0 = rb.rstart[grp], r1 = rb.rstart[grp + 1];
+    const bool touched = r1 > r0 || rb.clash_r > 0.f;
+    const bool guided = touched && rb.scale > 0.f && cf.w <= rb.guide_below;
+    const bool terms = touched && (guided || rb.op_energy != nullptr);
+    if (!terms) {                                   // uniform over the workgroup
+        if (rb.op_energy && tid == 0) rb.op_energy[(size_t)step * g.G + grp] = 0.f;
+        return;
+    }
+    const bool nan_reset = *w.nan_flag != 0;
+    const float* zg = c.z_phar + (size_t)pb * ld;   // the first member's copy
+    const int Mq = rb.clash_r > 0.f ? M : 1;        // without the clash term only the first member's pocket is read (the shift)
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    for (int m = 0; m < Mq; ++m) {
+        const int b = first + m, np = lay.num_pocket[b], qb = lay.pocket_base[b];
+        if (m > 0) __syncthreads();                 // every wave is done with the previous member's atoms
+        for (int i = tid; i < np; i += nt) {
+            const float* q = c.xh_pocket + (size_t)(qb + i) * ldq;
+            s_q[i] = make_float4(q[0], q[1], q[2], 0.f);
+        }
+        if (m == 0)
+            for (int idx = tid; idx < 3 * nl; idx += nt) {        // 1. xhat
+                const int i = idx / 3, k = idx - 3 * i;
+                float e = combine_eps(lay, g, eps, first, M, ld, i * ld + k);
+                if (nan_reset) e = 0.f;
+                s_xh[idx] = d.norm_x * (zg[i * ld + k] - sa.x * e) / sa.y;
+            }
+        __syncthreads();
+        if (m == 0) {
+            if (wave == nwaves - 1) {                             // 2. shift, from the first member
+                float c0, c1, c2;
+                wave_com(s_q, np, lane, c0, c1, c2);
+                const float4 pin = rb.pin_com[first];
+                if (lane == 0) { s_shift[0] = d.norm_x * (c0 - pin.x); s_shift[1] = d.norm_x * (c1 - pin.y); s_shift[2] = d.norm_x * (c2 - pin.z); }
+            }
+            __syncthreads();
+            sx = s_shift[0]; sy = s_shift[1]; sz = s_shift[2];
+        }
+        for (int i = wave; i < nl; i += nwaves) {                 // 3. a wave per point; the same wave owns the point for every member
+            const PointTerm t = point_terms(rb, m == 0 ? r0 : 0, m == 0 ? r1 : 0, i, np, s_xh, s_q, d.norm_x, sx, sy, sz, lane);
+            if (lane == 0) {
+                if (m == 0) { s_g[3 * i] = t.gx; s_g[3 * i + 1] = t.gy; s_g[3 * i + 2] = t.gz; s_e[i] = t.e; }
+                else { s_g[3 * i] += t.gx; s_g[3 * i + 1] += t.gy; s_g[3 * i + 2] += t.gz; s_e[i] += t.e; }
+            }
+        }
+    }
+    if (guided && lane == 0) {                                    // 4. by the lane that holds the point's sums
+        const float sd = d.norm_x * cf.z, var = sd * sd;
+        for (int i = wave; i < nl; i += nwaves) {
+            float dx = -rb.scale * var * s_g[3 * i], dy = -rb.scale * var * s_g[3 * i + 1], dz = -rb.scale * var * s_g[3 * i + 2];
+            const float len = sqrtf(dx * dx + dy * dy + dz * dz);
+            if (len > rb.max_shift) { const float f = rb.max_shift / len; dx *= f; dy *= f; dz *= f; }
+            float* o = gd + (size_t)(ub + i) * 3;
+            o[0] = dx; o[1] = dy; o[2] = dz;
+        }
+    }
+    __syncthreads();
+    if (rb.op_energy && tid == 0) {
+        float e = 0.f;
+        for (int i = 0; i < nl; ++i) e += s_e[i];                 // index order
+        rb.op_energy[(size_t)step * g.G + grp] = e;
+    }
+}
+
+// k_multi_step_count (kernels_multi.hip: the same LDS layout, sums and count pass) with 5. the group's displacement in the mean
+__global__ __launch_bounds__(1024) void k_multi_restrained_step_count(Layout lay, Dims d, ChainBuf c, GroupTab g, RestrainBuf rb, Work w,
+                                                                     const float* __restrict__ eps, const float* __restrict__ gd) {
+    extern __shared__ float4 s_pos[];               // [max_n] positions of the sample (phar first), then int sdeg[max_n], then z
+    int* sdeg = reinterpret_cast<int*>(s_pos + lay.max_n);
+    float* s_z = reinterpret_cast<float*>(sdeg + lay.max_n);      // [nl * ld]
+    __shared__ float s_mean[3];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nt = blockDim.x;
+    const int nl = lay.num_phar[b], np = lay.num_pocket[b], n = nl + np;
+    const int pb = lay.phar_base[b], qb = lay.pocket_base[b];
+    const int ld = 3 + d.P, ldq = 3 + d.R;
+    const int first = g.first[b], M = g.size[b], ub = g.ubase[b];
+    const int step = c.state->step - 1;
+    const float4 cf = c.coef[step];
+    const bool nan_reset = *w.nan_flag != 0;
+    const int grp = group_index(g, first);
+    const bool touched = rb.rstart[grp + 1] > rb.rstart[grp] || rb.clash_r > 0.f;
+    const bool guided = touched && rb.scale > 0.f && cf.w <= rb.guide_below;      // k_multi_guide's, which then wrote the group's d
+    float* zg = c.z_phar + (size_t)pb * ld;
+    const int cnt = nl * ld;
+    for (int idx = tid; idx < cnt; idx += nt) s_z[idx] = zg[idx];
+    for (int i = tid; i < np; i += nt) {
+        const float* q = c.xh_pocket + (size_t)(qb + i) * ldq;
+        s_pos[nl + i] = make_float4(q[0], q[1], q[2], 0.f);
+    }
+    __syncthreads();
+    if (wave == 0) record_com_check(c.check + 2 * (1 + step), s_z, ld, 0, nl, 1.0f, lane);   // z_t, the step's input
+    __syncthreads();
+    for (int idx = tid; idx < cnt; idx += nt) {
+        const int i = idx / ld, k = idx - i * ld;
+        float e = combine_eps(lay, g, eps, first, M, ld, idx);
+        if (nan_reset && k < 3) e = 0.f;
+        float mu = s_z[idx] / cf.x - cf.y * e;
+        if (guided && k < 3) mu = mu + gd[(size_t)(ub + i) * 3 + k] / d.norm_x;
+        s_z[idx] = mu + cf.z * draw_group(c, lay, g, 1 + step, b, i, k, ld);
+    }
+    __syncthreads();
+    phar_mean(s_z, nl, ld, tid, s_mean);
+    __syncthreads();
+    const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
+    for (int i = tid; i < n; i += nt) {
+        float4 p;
+        if (i < nl) {
+            float* z = s_z + i * ld;
+            z[0] -= m0; z[1] -= m1; z[2] -= m2;
+            p = make_float4(z[0], z[1], z[2], 0.f);
+            w.X0[pb + i] = p;
+            for (int l = 0; l < d.L; ++l) w.ACC[(size_t)l * lay.Nm + pb + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+            p = s_pos[i];
+            p.x -= m0; p.y -= m1; p.z -= m2;
+            float* q = c.xh_pocket + (size_t)(qb + i - nl) * ldq;
+            q[0] = p.x; q[1] = p.y; q[2] = p.z;
+            w.XP[qb + i - nl] = p;
+            if (c.pocket_steps) {
+                float* o = c.pocket_steps + ((size_t)step * lay.Np + qb + i - nl) * 3;
+                o[0] = p.x; o[1] = p.y; o[2] = p.z;
+            }
+        }
+        s_pos[i] = p;
+    }
+    __syncthreads();
+    const bool writer = c.z_steps && b == first;
+    float* zs = writer ? c.z_steps + ((size_t)step * g.Nu + ub) * ld : nullptr;
+    for (int idx = tid; idx < cnt; idx += nt) {
+        const float v = s_z[idx];
+        zg[idx] = v;
+        if (writer) zs[idx] = v;
+    }
+    count_next_graph(lay, d, w, s_pos, sdeg, b, nl, n, pb, qb);
+    if (b == 0 && tid == 0) {
+        if (nan_reset) atomicAdd(&w.counters[4], 1ull);
+        atomicAdd(&w.counters[0], 1ull);                       // evaluations (the one about to run)
+        atomicAdd(&w.counters[3], (unsigned long long)lay.N);  // nodes
+    }
+}
+
+// k_restrain_energy for a group: the terms of step 3 on the group's returned rows (xh_phar_out, [Nu] rows) against every member's returned
+// pocket, shift = com(xh_pocket_out.x of the first member) - n_x * com(P_first,in.x / n_x).  One workgroup of 256 threads per group.
+__global__ __launch_bounds__(256) void k_multi_restrain_energy(Layout lay, Dims d, GroupTab g, RestrainBuf rb, const float* __restrict__ xh_phar_out,
+                                                               const float* __restrict__ xh_pocket_out, float* __restrict__ energy_out) {
+    extern __shared__ float4 s_q[];                 // [max_n] pocket atoms of the member at hand, then xhat [max_n][3], e [max_n], v [max_n]
+    float* s_xh = reinterpret_cast<float*>(s_q + lay.max_n);
+    float* s_e = s_xh + (size_t)lay.max_n * 3;
+    float* s_v = s_e + lay.max_n;
+    __shared__ float s_shift[3];
+    const int grp = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6, nt = blockDim.x;
+    const int first = g.group_first[grp], M = g.size[first], ub = g.ubase[first];
+    const int nl = lay.num_phar[first];
+    const int ld = 3 + d.P, ldq = 3 + d.R;
+    const int r0 = rb.rstart[grp], r1 = rb.rstart[grp + 1];
+    if (!(r1 > r0 || rb.clash_r > 0.f)) {           // no restraint touches the group
+        if (tid == 0) { energy_out[2 * grp] = 0.f; energy_out[2 * grp + 1] = 0.f; }
+        return;
+    }
+    const int Mq = rb.clash_r > 0.f ? M : 1;
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    for (int m = 0; m < Mq; ++m) {
+        const int b = first + m, np = lay.num_pocket[b], qb = lay.pocket_base[b];
+        if (m > 0) __syncthreads();
+        if (m == 0)
+            for (int idx = tid; idx < 3 * nl; idx += nt) { const int i = idx / 3, k = idx - 3 * i; s_xh[idx] = xh_phar_out[(size_t)(ub + i) * ld + k]; }
+        for (int i = tid; i < np; i += nt) {
+            const float* q = xh_pocket_out + (size_t)(qb + i) * ldq;
+            s_q[i] = make_float4(q[0], q[1], q[2], 0.f);
+        }
+        __syncthreads();
+        if (m == 0) {
+            if (wave == 0) {
+                float c0, c1, c2;
+                wave_com(s_q, np, lane, c0, c1, c2);
+                const float4 pin = rb.pin_com[first];
+                if (lane == 0) { s_shift[0] = c0 - d.norm_x * pin.x; s_shift[1] = c1 - d.norm_x * pin.y; s_shift[2] = c2 - d.norm_x * pin.z; }
+            }
+            __syncthreads();
+            sx = s_shift[0]; sy = s_shift[1]; sz = s_shift[2];
+        }
+        for (int i = wave; i < nl; i += nwaves) {
+            const PointTerm t = point_terms(rb, m == 0 ? r0 : 0, m == 0 ? r1 : 0, i, np, s_xh, s_q, 1.0f, sx, sy, sz, lane);
+            if (lane == 0) {
+                if (m == 0) { s_e[i] = t.e; s_v[i] = t.v; }
+                else { s_e[i] += t.e; s_v[i] = fmaxf(s_v[i], t.v); }
+            }
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float e = 0.f, v = 0.f;
+        for (int i = 0; i < nl; ++i) { e += s_e[i]; v = fmaxf(v, s_v[i]); }     // index order
+        energy_out[2 * grp] = e; energy_out[2 * grp + 1] = v;
+    }
+}
+
 void cmdgen_launch_restrain_prep(const Layout& lay, const Dims& d, const RestrainBuf& rb, const float* px, hipStream_t s) {
     hipLaunchKernelGGL(k_restrain_prep, dim3(lay.B), dim3(64), 0, s, lay, d, rb, px);
 }
@@ -539,4 +795,17 @@ void cmdgen_launch_restrain_energy(const Layout& lay, const Dims& d, const Restr
                                    float* energy_out, hipStream_t s) {
     const size_t shm = (size_t)lay.max_n * (sizeof(float4) + 5 * sizeof(float));
     hipLaunchKernelGGL(k_restrain_energy, dim3(lay.B), dim3(256), shm, s, lay, d, rb, xo, po, energy_out);
+}
+void cmdgen_launch_multi_restrained_step(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const RestrainBuf& rb,
+                                         const Work& w, const float* eps, float* gd, hipStream_t s) {
+    const dim3 block(lay.max_n > 128 ? 1024 : 256);             // as k_multi_step_count
+    const size_t shm_guide = (size_t)lay.max_n * (sizeof(float4) + 7 * sizeof(float));
+    const size_t shm_step = (size_t)lay.max_n * (sizeof(float4) + sizeof(int)) + (size_t)lay.max_n * (3 + d.P) * sizeof(float);
+    hipLaunchKernelGGL(k_multi_guide, dim3(g.G), block, shm_guide, s, lay, d, c, g, rb, w, eps, gd);
+    hipLaunchKernelGGL(k_multi_restrained_step_count, dim3(lay.B), block, shm_step, s, lay, d, c, g, rb, w, eps, (const float*)gd);
+}
+void cmdgen_launch_multi_restrain_energy(const Layout& lay, const Dims& d, const GroupTab& g, const RestrainBuf& rb, const float* xo,
+                                         const float* po, float* energy_out, hipStream_t s) {
+    const size_t shm = (size_t)lay.max_n * (sizeof(float4) + 5 * sizeof(float));
+    hipLaunchKernelGGL(k_multi_restrain_energy, dim3(g.G), dim3(256), shm, s, lay, d, g, rb, xo, po, energy_out);
 }

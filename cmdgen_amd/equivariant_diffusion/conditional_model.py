@@ -350,6 +350,39 @@ class ConditionalDDPM(EnVariationalDiffusion):
         out = self._finish_chain(h, run, self.inpaint_frames(1, 1, timesteps, return_frames), return_frames)
         return out[0], [out[1][..., r, :] for r in rows], phar_mask, [q['mask'] for q in pockets]
 
+    @torch.no_grad()
+    def sample_restrained_given_pockets(self, pockets, num_nodes_phar, restraints, weights=None, clash=None, scale=1.0, max_shift=None,
+                                        guide_below=1.0, return_frames=1, timesteps=None, noise=None, seed=None, group_ids=None):
+        """sample_given_pockets BIASED toward a geometric query, sample_restrained's guidance on the latent the group's pockets share
+        (cmdgen_multi_restrained_chain; the header of csrc/kernels_restrain.hip defines every term): "one pharmacophore for both kinases,
+        a donor at the shared hinge position, a hydrophobe 5-7 A from it, off the atoms of EITHER pocket".
+
+        pockets, num_nodes_phar [G], weights, noise, seed and group_ids as sample_given_pockets.  restraints: the dicts of
+        sample_restrained, each naming its GROUP under 'sample'; point indices are rows of the group's pharmacophore, centres lie in the
+        common frame the group's pockets are given in.  The guidance is computed once per group: the frame shift follows the group's
+        FIRST pocket, the clash term (clash: None, a radius, or (radius, k)) sums over the atoms of EVERY pocket of the group, unweighted.
+        scale, max_shift and guide_below as sample_restrained (scale = 0: sample_given_pockets, bit for bit).
+        Returns sample_given_pockets' tuple plus {'energy': [G], 'max_violation': [G]} of the returned sample against all its pockets
+        (and 'op_energy' [timesteps, G] when return_frames > 1)."""
+        from .. import restraints as rs
+        pockets, M, G = self._checked_pockets(pockets)
+        nph = torch.as_tensor(num_nodes_phar).detach().to('cpu', torch.int64).numpy().reshape(-1)
+        if len(nph) != G:
+            raise ValueError(f'num_nodes_phar has {len(nph)} entries for {G} groups')
+        w = self.group_weights(weights, G, M)
+        timesteps = self._checked_frames(timesteps, return_frames)
+        rec = rs.records(restraints, nph)                                 # per group: 'sample' is the group index
+        clash_r, clash_k = rs.clash_pair(clash)
+        scale, max_shift, guide_below = rs.check_scalars(scale, rs.DEFAULT_MAX_SHIFT if max_shift is None else max_shift, guide_below)
+        sizes, rows, px, poh = self._member_layout(pockets, M, G)
+        h, phar_mask, noise, seed = self._prepare_sample(nph, (np.repeat(nph, M), sizes.reshape(-1)), pockets[0]['x'].device, timesteps, noise,
+                                                         seed, guide=True)
+        run = lambda: h.multi_restrained_chain(px, poh, [M] * G, w.reshape(-1), timesteps, rec, clash_radius=clash_r, clash_k=clash_k,
+                                               scale=scale, max_shift=max_shift, guide_below=guide_below, noise=noise, seed=seed,
+                                               group_ids=group_ids, want_steps=return_frames > 1, use_graph=self.use_hip_graph)
+        out, info = self._finish_restrained(h, run, self.inpaint_frames(1, 1, timesteps, return_frames), return_frames)
+        return out[0], [out[1][..., r, :] for r in rows], phar_mask, [q['mask'] for q in pockets], info
+
     @staticmethod
     def _checked_pockets(pockets):
         """The pocket dicts of sample_given_pockets / edit_given_pockets as a list, with M (pockets per group) and G (groups)."""
@@ -731,6 +764,10 @@ class SimpleConditionalDDPM(ConditionalDDPM):
     def sample_restrained(self, *args, **kwargs):
         raise NotImplementedError('sample_restrained is not implemented for SimpleConditionalDDPM (no centre-of-mass projection: the '
                                   'guidance frame follows the projections); use ConditionalDDPM')
+
+    def sample_restrained_given_pockets(self, *args, **kwargs):
+        raise NotImplementedError('sample_restrained_given_pockets is not implemented for SimpleConditionalDDPM (no centre-of-mass '
+                                  'projection: the shared latent has no frame of its own for the guidance to follow); use ConditionalDDPM')
 
     def edit_restrained(self, *args, **kwargs):
         raise NotImplementedError('edit_restrained is not implemented for SimpleConditionalDDPM (no centre-of-mass projection: the '

@@ -581,6 +581,11 @@ class EnVariationalDiffusion(nn.Module):
         raise NotImplementedError('sample_restrained is not implemented for the joint model (its pocket nodes diffuse with the latent: '
                                   'there is no fixed pocket frame to place the restraints in); use ConditionalDDPM')
 
+    def sample_restrained_given_pockets(self, *args, **kwargs):
+        raise NotImplementedError('sample_restrained_given_pockets is not implemented for the joint model (its pocket nodes diffuse with '
+                                  'the latent, so several pockets cannot share one and there is no fixed frame for the restraints); use '
+                                  'ConditionalDDPM')
+
     def edit_restrained(self, *args, **kwargs):
         raise NotImplementedError('edit_restrained is not implemented for the joint model (its pocket nodes diffuse with the latent: '
                                   'the restraint frame and the clash term would move with them); use the conditional model')

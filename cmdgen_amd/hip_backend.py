@@ -81,6 +81,9 @@ SYMBOLS = [
     ('cmdgen_restrained_edit_chain', C.c_int, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int64,
                                                C.c_uint64, _i64p, _fp, _fp, _fp, _fp, _vp, C.c_int64, C.c_float, C.c_float, C.c_float,
                                                C.c_float, C.c_float, _fp, _fp, C.c_int32, _vp]),
+    ('cmdgen_multi_restrained_chain', C.c_int, [_vp, _fp, _fp, C.c_int64, _i64p, _vp, C.c_int32, _vp, C.c_int64, C.c_float, C.c_float,
+                                                C.c_float, C.c_float, C.c_float, _fp, C.c_uint64, _i64p, _fp, _fp, _fp, _fp, _fp, _fp,
+                                                C.c_int32, _vp]),
     ('cmdgen_set_guide_table', C.c_int, [_vp, C.c_int32, _vp]),
     ('cmdgen_param_count', C.c_int, [_vp, _i64p]),
     ('cmdgen_param_offset', C.c_int, [_vp, C.c_char_p, _i64p, _i64p]),
@@ -466,6 +469,33 @@ class Handle:
             int(timesteps), _ptr(noise), self._seed(seed), ids, _ptr(xh_phar), _ptr(xh_pocket),
             _ptr(z_steps), _ptr(p_steps), int(bool(use_graph)), self._stream()), 'cmdgen_multi_pocket_chain')
         return xh_phar, xh_pocket, z_steps
+
+    def multi_restrained_chain(self, pocket_x, pocket_onehot, group_sizes: Sequence[int], weights, timesteps: int, restraints=None,
+                               clash_radius: float = 0.0, clash_k: float = 0.0, scale: float = 1.0, max_shift: float = DEFAULT_MAX_SHIFT,
+                               guide_below: float = 1.0, noise=None, seed: int = 0, group_ids: Optional[Sequence[int]] = None,
+                               want_steps: bool = False, use_graph: bool = True):
+        """cmdgen_multi_restrained_chain: multi_pocket_chain with restrained_chain's guidance term on the shared latent, once per group (the
+        header of kernels_restrain.hip defines it).  The layout, group_sizes, weights, noise and group_ids of multi_pocket_chain; restraints: a
+        RESTRAINT_DTYPE array whose 'sample' is the GROUP index, or None; the scalars of restrained_chain.
+        -> (xh_phar [Nu, 3+P], xh_pocket, z_steps, energy [G, 2] (E and the largest violation in A of the output), op_energy [K, G] or None)."""
+        import torch
+        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
+        dev = pocket_x.device
+        self._check_dev(pocket_x, (self.n_pocket, 3))
+        self._check_dev(pocket_onehot, (self.n_pocket, R))
+        sizes, w, ids, n_unique = self._group_args(group_sizes, weights, group_ids)
+        if noise is not None:
+            self._check_dev(noise, (timesteps + 2, n_unique, 3 + P))
+        rec, n_rec = self._restraint_arg(restraints)
+        xh_phar, xh_pocket, z_steps, p_steps = self._chain_outputs(n_unique, timesteps, want_steps, dev)
+        energy = torch.empty((len(sizes), 2), dtype=torch.float32, device=dev)
+        op_energy = torch.empty((timesteps, len(sizes)), dtype=torch.float32, device=dev) if want_steps else None
+        self._check(self.lib.cmdgen_multi_restrained_chain(
+            self.h, _ptr(pocket_x), _ptr(pocket_onehot), len(sizes), sizes.ctypes.data_as(_i64p), w.ctypes.data_as(C.c_void_p),
+            int(timesteps), rec, n_rec, float(clash_radius), float(clash_k), float(scale), float(max_shift), float(guide_below),
+            _ptr(noise), self._seed(seed), ids, _ptr(xh_phar), _ptr(xh_pocket), _ptr(z_steps), _ptr(p_steps), _ptr(energy),
+            _ptr(op_energy), int(bool(use_graph)), self._stream()), 'cmdgen_multi_restrained_chain')
+        return xh_phar, xh_pocket, z_steps, energy, op_energy
 
     def joint_plan(self, timesteps: int, resamplings: int = 1, jump_length: int = 1, inpaint: bool = True):
         """(denoising steps, combined noise draws) of a joint chain."""

@@ -425,6 +425,58 @@ class PharPocketDDPM(nn.Module):
         xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
         return self._point_lists(xh_phar, {'size': num_nodes_phar}), info
 
+    @torch.no_grad()
+    def generate_phars_multi_restrained(self, pdb_files, n_samples, restraints, pocket_ids=None, ref_ligands=None, num_nodes_phar=None,
+                                        weights=None, clash=None, scale=1.0, max_shift=None, guide_below=1.0, timesteps=None, seed=None,
+                                        noise=None, group_ids=None):
+        """generate_phars_multi BIASED toward a geometric query (ConditionalDDPM.sample_restrained_given_pockets): one pharmacophore per
+        sample for SEVERAL pockets - "a donor at the shared hinge position, a hydrophobe 5-7 A from it, off the atoms of either pocket".
+
+        pdb_files, pocket_ids / ref_ligands, num_nodes_phar and weights as generate_phars_multi: the files ALREADY superposed into one
+        common frame.  restraints: the dicts of cmdgen_amd/restraints.py WITHOUT 'sample', given once in that common frame and applied to
+        every one of the n_samples copies; clash (None, a radius, or (radius, k)) holds against the atoms of every pocket.  scale,
+        max_shift, guide_below as sample_restrained.  Everything is moved back by the FIRST pocket's shift - the frame the guidance itself
+        follows - so the points come out in the frame the centres were given in.
+        -> (one point list per sample, [(type name, (x, y, z))], and {'energy': [n_samples], 'max_violation': [n_samples]})."""
+        from . import restraints as rs
+        pdb_files = list(pdb_files)
+        M = len(pdb_files)
+        assert (pocket_ids is None) ^ (ref_ligands is None)
+        if len(pocket_ids if pocket_ids is not None else ref_ligands) != M:
+            raise ValueError(f'{M} pdb_files need {M} entries of pocket_ids or ref_ligands (one per file)')
+        if not isinstance(self.ddpm, ConditionalDDPM):
+            raise NotImplementedError('generate_phars_multi_restrained needs the conditional model (mode pocket_conditioning)')
+        restraints = list(restraints)
+        for n, r in enumerate(restraints):
+            if isinstance(r, dict) and 'sample' in r:
+                raise ValueError(f"restraints[{n}] = {r!r}: restraints are given once, without 'sample', and applied to every sample")
+        named = [int(v) for r in restraints if isinstance(r, dict)
+                 for v in ([r['point']] if 'point' in r else list(r.get('points', ()))) if isinstance(v, (int, np.integer))]
+        pockets = [self._pdb_pocket(f, n_samples, pocket_ids[m] if pocket_ids is not None else None,
+                                    ref_ligands[m] if ref_ligands is not None else None) for m, f in enumerate(pdb_files)]
+        first = pockets[0]
+        pocket_com_before = _scatter_mean(first['x'], first['mask'], n_samples)
+        if num_nodes_phar is None:
+            num_nodes_phar = self.ddpm.size_distribution.sample_conditional(n1=None, n2=first['size'])
+            num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device).clamp(min=max(named, default=0) + 1)
+        else:
+            num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device).reshape(-1)
+            if num_nodes_phar.numel() == 1:
+                num_nodes_phar = num_nodes_phar.expand(n_samples)
+        num_nodes_phar = num_nodes_phar.to(INT_TYPE)
+        nph = num_nodes_phar.cpu().numpy()
+        for b in range(n_samples):
+            rs.records(restraints, nph, sample=b)                       # (names the entry of the caller's list)
+        per_sample = [dict(r, sample=b) for b in range(n_samples) for r in restraints]
+        sampler_kw = {} if group_ids is None else {'group_ids': group_ids}
+        xh_phar, xh_pockets, phar_mask, pocket_masks, info = self.ddpm.sample_restrained_given_pockets(
+            pockets, num_nodes_phar, per_sample, weights=weights, clash=clash, scale=scale, max_shift=max_shift, guide_below=guide_below,
+            timesteps=timesteps, seed=seed, noise=noise, **sampler_kw)
+        # move the points back by the first pocket's shift (every pocket was translated by the same vector; the centres never moved)
+        pocket_com_after = _scatter_mean(xh_pockets[0][:, :self.x_dims], pocket_masks[0], n_samples)
+        xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
+        return self._point_lists(xh_phar, {'size': num_nodes_phar}), info
+
     def _phar_with_given_rows(self, points, arg, n_samples, num_nodes_phar, pocket):
         """The phar batch of inpaint_phars / edit_phars: `points` = [(type name, (x, y, z))] are the first rows of every sample, the
         other rows zero.  num_nodes_phar: points per sample, default the size prior given the pocket, at least len(points).

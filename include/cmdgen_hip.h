@@ -539,6 +539,46 @@ int cmdgen_restrained_edit_chain(cmdgen_handle* h, const float* pocket_x, const 
                                  float clash_radius, float clash_k, float scale, float max_shift, float guide_below,
                                  float* energy_out, float* op_energy_out, int32_t use_graph, cmdgen_stream stream);
 
+/* Restraints on the shared latent of several pockets (ConditionalDDPM.sample_restrained_given_pockets): cmdgen_multi_pocket_chain's chain -
+ * the same layout of B member samples in G groups, the same init, ops, draws, Philox counters (keyed by group id), decode and CoG
+ * re-centring - with cmdgen_restrained_chain's addition to the mean of every posterior op t -> s, applied PER GROUP.  The decode is not
+ * guided.  The definition is the project's own; kernels_restrain.hip ("The restrained MULTI-POCKET chain") carries it in full.  The terms,
+ * g_i, d_i, the max_shift clip, guide_below and mu are cmdgen_restrained_chain's, with these points settled:
+ *   restraints  belong to a GROUP: cmdgen_restraint::sample is the group index g, point indices are < n_phar of the group, centres are
+ *               given in the common frame in which the caller gives the group's pockets
+ *   xhat_i      = n_x (z.x_i - sigma_t ebar_i) / alpha_t with ebar = sum_m w_m eps_m, what the step itself uses (m ascending, the first
+ *               term not added to a zero); its x columns are zero under the batch-wide NaN guard
+ *   shift_g     = n_x (com(P_first.x) - com(P_first,in.x / n_x)), from the group's FIRST member, its pocket as it stands at the op's input:
+ *               the precedent of cmdgen_multi_edit_chain, whose offset in step B is the first member's
+ *   clash       the sum runs over every point of the group and every pocket atom of EVERY member, q_{m,a} = n_x P_m.x_a as it stands at the
+ *               op's input; unweighted, weight-0 members included: a point must clash with neither pocket
+ *   sums        a point's terms: the group's records and the first member's atoms as cmdgen_restrained_chain sums them, then the further
+ *               members' atoms, member by member in ascending order; a fixed order, no float atomics
+ *   mu.x_i      = z.x_i / coef.x - coef.y ebar_i + d_i / n_x: every member adds the SAME BITS d_i, so the members' copies of z stay
+ *               bit-identical (cmdgen_debug_read("chain_z"))
+ * Reductions that hold bit for bit on every output and cmdgen_chain_status:
+ *   - no record on any group and clash_radius = 0, or scale = 0, or guide_below = 0: cmdgen_multi_pocket_chain's outputs; a group-op that
+ *     is not guided (no record on the group while clash_radius = 0, scale = 0, t / T > guide_below) adds nothing, not even a zero
+ *   - every group of one member: cmdgen_restrained_chain's outputs on a handle whose evaluations use their own k_readout (option
+ *     readout_in_coord = 0), energy_out and op_energy_out included
+ *   - two runs of the same inputs are equal bit for bit, captured or eager
+ *   energy_out     dev [G][2]: E and the largest violation (Angstrom) of the RETURNED rows against every member's returned pocket, the
+ *                  shift taken from the first member's returned pocket
+ *   op_energy_out  dev [K][G] E at xhat of every op, or NULL
+ *   the leading arguments as cmdgen_multi_pocket_chain, the restraint arguments as cmdgen_restrained_chain, then cmdgen_multi_pocket_chain's
+ * The chain has a slot of its own; its tables are the posterior rows, the group tables and the guidance tail (CSR offsets [G + 1]), so a
+ * changed grouping, weight, restraint or scalar prepares the slot (and its graph) again.
+ * Refused: whatever cmdgen_multi_pocket_chain refuses of a grouping and whatever cmdgen_restrained_chain refuses of a restraint list and
+ * scalars, with the same codes; the messages say "group" where a group is meant.  The joint model and no_com_projection handles
+ * (CMDGEN_ESTATE, as cmdgen_multi_pocket_chain). */
+int cmdgen_multi_restrained_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
+                                  int64_t n_groups, const int64_t* group_size_host, const float* weight_host, int32_t timesteps,
+                                  const cmdgen_restraint* restraints_host, int64_t n_restraints,
+                                  float clash_radius, float clash_k, float scale, float max_shift, float guide_below,
+                                  const float* noise, uint64_t seed, const int64_t* group_ids_host,
+                                  float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                                  float* energy_out, float* op_energy_out, int32_t use_graph, cmdgen_stream stream);
+
 /* ---- training step (conditional model) -------------------------------------------------- */
 /* The trainable tensors of EGNNDynamics live in ONE flat fp32 device buffer owned by the caller, in the
  * reference's registration order (the state_dict order below 'ddpm.dynamics.': weight then bias of every
