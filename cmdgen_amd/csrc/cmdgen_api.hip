@@ -702,7 +702,7 @@ static std::vector<float> step_table(const cmdgen_handle* h, int K) {
 }
 
 // ---------------------------------------------------------------------------------
-// the chains: what the entries of all ten kinds share.  A kind's state lives in its slot (h->chains[kind]); its ChainAlloc composes
+// the chains: what the entries of all eleven kinds share.  A kind's state lives in its slot (h->chains[kind]); its ChainAlloc composes
 // the parts it uses (alloc_chain_buf, alloc_inpaint_part, point_group_tab, alloc_restrain_part, alloc_score_part); its entry reads top to
 // bottom: checks, tables, Chain::open, its init launches, Chain::start, Chain::steps with its step launch, its final launches, Chain::close.
 // ---------------------------------------------------------------------------------
@@ -914,7 +914,7 @@ static int alloc_score_part(cmdgen_handle* h, ChainSlot& k) {
 }
 
 // One chain call between begin_chain and end_chain: the stream it runs on, its slot, the launch description of its evaluations and, for
-// the nine conditional kinds, the slot's ChainBuf completed with the call's pointers.
+// the ten conditional kinds, the slot's ChainBuf completed with the call's pointers.
 struct Chain {
     cmdgen_handle* h = nullptr;
     ChainSlot* k = nullptr;
@@ -1708,6 +1708,79 @@ extern "C" int cmdgen_multi_edit_chain(cmdgen_handle* h, const float* pocket_x, 
     });
     if (rc) return rc;
     cmdgen_launch_multi_final(h->lay, d, decode_buf(c, plan, (size_t)gt.Nu, d.P), gt, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, ch.k->cog, ch.s);
+    return ch.close();
+}
+
+// ---------------------------------------------------------------------------------
+// the restrained multi-pocket edit chain: cmdgen_multi_edit_chain's chain with cmdgen_multi_restrained_chain's guidance in op A, once per
+// GROUP (kernels_restrain.hip, "The restrained MULTI-POCKET EDIT chain", holds the definition).  The slot's table block is: the edit plan's
+// tables (coef | coef2 | iop) | the group tables, padded to a multiple of four floats | the guidance tail with one guide row per OP of the
+// plan, CSR offsets [G + 1] and the records sorted by group - so a changed grouping, weight, plan, start, restraint or scalar prepares the
+// slot again and drops its captured steps.
+// ---------------------------------------------------------------------------------
+// (the groups of the call are in the slot before Chain::open, as for alloc_multi_restrained)
+static int alloc_multi_restrained_edit(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
+    int rc = alloc_multi_edit(h, k, tables, n_steps); if (rc) return rc;
+    const float* tail = tables + (size_t)(3 * n_steps + 1) * 4 + group_tables_floats(h->lay.B, k.groups.G);
+    rc = alloc_restrain_part(h, k, tail, n_steps, k.groups.G); if (rc) return rc;
+    return slot_alloc(h, k, k.guide_d, (size_t)h->lay.Nl * 3);    // (Nl bounds the unique rows of any grouping)
+}
+
+extern "C" int cmdgen_multi_restrained_edit_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
+                                                  int64_t n_groups, const int64_t* group_size_host, const float* weight_host,
+                                                  const float* phar_x, const float* phar_onehot, const float* fix_x, const float* fix_h,
+                                                  int32_t timesteps, int32_t start, int32_t resamplings, int32_t jump_length,
+                                                  const float* noise, int64_t n_draws, uint64_t seed, const int64_t* group_ids_host,
+                                                  float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                                                  const cmdgen_restraint* restraints_host, int64_t n_restraints,
+                                                  float clash_radius, float clash_k, float scale, float max_shift, float guide_below,
+                                                  float* energy_out, float* op_energy_out, int32_t use_graph, cmdgen_stream stream) {
+    int rc = check_ready(h); if (rc) return rc;
+    rc = refuse_joint_no_com(h, "the restrained multi-pocket edit chain", kPocketDiffuses, ": the edit chain and the guidance frame follow the centre-of-mass projections");
+    if (rc) return rc;
+    rc = check_inpaint_args(h, timesteps, start, resamplings, jump_length); if (rc) return rc;
+    if (!pocket_x || !pocket_onehot || !group_size_host || !weight_host || !phar_x || !phar_onehot || !fix_x || !fix_h || !xh_phar_out ||
+        !xh_pocket_out || !energy_out)
+        return fail(h, CMDGEN_EINVAL, "null pointer");
+    GroupPlan gp;
+    rc = build_group_plan(h, n_groups, group_size_host, weight_host, group_ids_host, gp); if (rc) return rc;
+    RestraintOwners own{"group", "the call's", {}};
+    for (int g = 0; g < gp.G; ++g) own.nphar.push_back((long long)h->cur_nphar[(size_t)gp.gfirst[g]]);
+    std::vector<int> rstart; std::vector<cmdgen_restraint> rec;
+    // (the step keeps k_multi_edit_step_count's LDS, which build_group_plan has checked, and the guide kernel less)
+    rc = check_restraint_list(h, own, restraints_host, n_restraints, clash_radius, clash_k, scale, max_shift, guide_below, 0, rstart, rec);
+    if (rc) return rc;
+    const InpaintPlan plan = build_inpaint_plan(h, timesteps, start, resamplings, jump_length);
+    rc = check_draws(h, noise, n_draws, plan.n_draws); if (rc) return rc;
+    std::vector<float> tables = plan_tables(plan.coef, plan.coef2, plan.iop);
+    const size_t t0 = tables.size();
+    append_group_tables(tables, gp, weight_host, h->lay.B);
+    tables.resize(t0 + group_tables_floats(h->lay.B, gp.G), 0.f);
+    append_guidance(h, tables, timesteps, plan.s_of, 0, {clash_radius, clash_k, scale, max_shift, guide_below}, rstart, rec);
+    h->chains[CHAIN_MULTI_RESTRAINED_EDIT].groups.G = gp.G;       // alloc_multi_restrained_edit reads it
+    Chain ch;
+    rc = ch.open(h, CHAIN_MULTI_RESTRAINED_EDIT, tables, plan.n_steps, alloc_multi_restrained_edit, gp.gid.data(), noise, seed, z_steps_out, pocket_steps_out, use_graph, stream);
+    if (rc) return rc;
+    const Dims& d = h->dims;
+    const ChainBuf& c = ch.c;
+    const InpaintBuf ip = ch.k->inp;
+    const GroupTab gt = group_tab(*ch.k, gp);
+    RestrainBuf rb = ch.k->restr;
+    rb.op_energy = op_energy_out;
+    float* const gd = ch.k->guide_d;
+    if (start == timesteps)                          // from the prior: z_T around the weighted pocket centre
+        cmdgen_launch_multi_init(h->lay, d, c, gt, pocket_x, pocket_onehot, ch.s);
+    else                                             // part-way: z ~ q(z_start | the given rows)
+        cmdgen_launch_multi_edit_start(h->lay, d, c, gt, plan.alpha_start, plan.sigma_start, phar_x, phar_onehot, pocket_x, pocket_onehot, ch.s);
+    cmdgen_launch_multi_edit_prep(h->lay, d, c, gt, ip, phar_x, phar_onehot, fix_x, fix_h, pocket_x, ch.s);
+    cmdgen_launch_restrain_prep(h->lay, d, rb, pocket_x, ch.s);  // com(P_in) of every member; the guidance reads the first member's
+    ch.start(true);                                  // evaluation 0 (t = start / timesteps); the evaluations are cmdgen_multi_edit_chain's
+    rc = ch.steps({noise, z_steps_out, pocket_steps_out, op_energy_out, nullptr}, plan.n_steps, [&](hipStream_t ss) {
+        cmdgen_launch_multi_restrained_edit_step(h->lay, d, c, gt, ip, rb, h->work, h->work.eps_tmp, gd, ss);
+    });
+    if (rc) return rc;
+    cmdgen_launch_multi_final(h->lay, d, decode_buf(c, plan, (size_t)gt.Nu, d.P), gt, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, ch.k->cog, ch.s);
+    cmdgen_launch_multi_restrain_energy(h->lay, d, gt, rb, xh_phar_out, xh_pocket_out, energy_out, ch.s);
     return ch.close();
 }
 

@@ -232,7 +232,7 @@ struct RestraintRec {           // = cmdgen_restraint (include/cmdgen_hip.h), on
 enum { RK_POSITION = 0, RK_DISTANCE = 1, RK_EXCLUSION = 2, MAX_RESTRAINTS = 256 };   // = CMDGEN_RESTRAINT_*, CMDGEN_MAX_RESTRAINTS
 
 struct RestrainBuf {            // restrained chain (cmdgen_restrained_chain), beside a ChainBuf: the guidance tables (kernels_restrain.hip)
-                                // (cmdgen_multi_restrained_chain: rstart is [G+1] and RestraintRec::sample a GROUP, op_energy [K][G]; pin_com stays per member)
+                                // (cmdgen_multi_restrained_chain, cmdgen_multi_restrained_edit_chain: rstart is [G+1] and RestraintRec::sample a GROUP, op_energy [K][G]; pin_com stays per member)
     const float4* sa;           // [K]     (sigma_t, alpha_t, 0, 0) of op i's t: the denoised estimate xhat = n_x (z.x - sigma_t e) / alpha_t
     const int* rstart;          // [B+1]   a sample's records are rec[rstart[b] .. rstart[b+1] - 1], in the caller's list order
     const RestraintRec* rec;    // [n]

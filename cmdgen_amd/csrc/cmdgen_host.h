@@ -24,7 +24,7 @@ struct DevBuf {
 // Host state of one kind of denoising chain (cmdgen_api.hip): its buffers for the current layout, the plan tables they were
 // prepared for, and its captured steps.  Each kind has a slot of its own, so plain and inpainting chains alternate on a
 // handle without re-preparing or re-capturing.
-enum ChainKind { CHAIN_PLAIN, CHAIN_JOINT, CHAIN_INPAINT, CHAIN_SCORE, CHAIN_MULTI, CHAIN_MULTI_EDIT, CHAIN_MULTI_SCORE, CHAIN_RESTRAINED, CHAIN_RESTRAINED_EDIT, CHAIN_MULTI_RESTRAINED, CHAIN_KINDS };
+enum ChainKind { CHAIN_PLAIN, CHAIN_JOINT, CHAIN_INPAINT, CHAIN_SCORE, CHAIN_MULTI, CHAIN_MULTI_EDIT, CHAIN_MULTI_SCORE, CHAIN_RESTRAINED, CHAIN_RESTRAINED_EDIT, CHAIN_MULTI_RESTRAINED, CHAIN_MULTI_RESTRAINED_EDIT, CHAIN_KINDS };
 struct ChainSlot {
     std::vector<void*> allocs;
     std::vector<float> tables;             // the uploaded plan tables (coef | coef2 | iop bits), compared to decide a re-prepare
@@ -42,7 +42,7 @@ struct ChainSlot {
     InpaintBuf inp{};                      // edit kinds: the op tables, the known rows and marks (multi-pocket: once per group), the offset per sample
     GroupTab groups{};                     // multi-pocket kinds: the group tables in the slot's table block (a changed grouping prepares the slot again)
     RestrainBuf restr{};                   // restrained kinds: the guidance tables in the slot's table block (a changed restraint prepares the slot again)
-    float* guide_d = nullptr;              // restrained multi-pocket kind: the displacement of every group's rows [Nu][3], written by k_multi_guide for the step launch
+    float* guide_d = nullptr;              // restrained multi-pocket kinds: the displacement of every group's rows [Nu][3], written by the guide launch for the step launch
     ScoreBuf score{};                      // scoring kinds: the clean rows the levels noise
     JointBuf joint{};                      // joint kind: its z, scratch and plan rows ...
     float* eps_pocket = nullptr;           // ... and the pocket output [Np][3+R] of its evaluations

@@ -64,6 +64,10 @@ void cmdgen_launch_restrain_energy(const Layout& lay, const Dims& d, const Restr
 // k_multi_restrained_step_count (one per member); RestrainBuf::rstart and op_energy are per GROUP, energy_out is [G][2]
 void cmdgen_launch_multi_restrained_step(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const RestrainBuf& rb,
                                          const Work& w, const float* eps, float* gd, hipStream_t s);
+// ... and the restrained multi-pocket EDIT chain: per op k_multi_edit_guide (k_multi_guide with the held rows at their given positions) and
+// then k_multi_restrained_edit_step_count (k_multi_edit_step_count with the displacement in op A, on the rows whose x is not held)
+void cmdgen_launch_multi_restrained_edit_step(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const InpaintBuf& ip,
+                                              const RestrainBuf& rb, const Work& w, const float* eps, float* gd, hipStream_t s);
 void cmdgen_launch_multi_restrain_energy(const Layout& lay, const Dims& d, const GroupTab& g, const RestrainBuf& rb, const float* xo,
                                          const float* po, float* energy_out, hipStream_t s);
 

@@ -41,6 +41,17 @@ __device__ __forceinline__ float draw_group(const ChainBuf& c, const Layout& lay
     return z[comp & 3];
 }
 
+// draw_group with the noise row and the Philox counter given apart (the edit plan's rows are in call order, its counters are not):
+// the multi-pocket edit chains (kernels_multi.hip, kernels_restrain.hip)
+__device__ __forceinline__ float draw_group_at(const ChainBuf& c, const Layout& lay, const GroupTab& g, int row, int key, int b,
+                                               int local, int comp, int ld) {
+    if (c.noise) return c.noise[((size_t)row * g.Nu + g.ubase[b] + local) * ld + comp];
+    float z[4];
+    philox_normal4(c.seed, (uint32_t)lay.pocket_gid[b], (uint32_t)(lay.pocket_gid[b] >> 32),
+                   (uint32_t)key, (uint32_t)(local * 4 + (comp >> 2)), z);
+    return z[comp & 3];
+}
+
 // eps_bar of element idx of the group's rows (eps: [Nl][ld], a member's rows start at its phar_base)
 __device__ __forceinline__ float combine_eps(const Layout& lay, const GroupTab& g, const float* __restrict__ eps, int first, int M,
                                              int ld, int idx) {

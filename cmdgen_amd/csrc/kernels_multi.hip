@@ -272,16 +272,6 @@ __global__ __launch_bounds__(1024) void k_multi_step_count(Layout lay, Dims d, C
 // without a workgroup reading what another one of the same launch writes.  With M = 1 every value is kernels_inpaint.hip's, and
 // without marks and jumps k_multi_step_count's, bit for bit.
 // ------------------------------------------------------------------------------------------------------------
-// draw_group with the noise row and the Philox counter given apart (the edit plan's rows are in call order, its counters are not)
-__device__ __forceinline__ float draw_group_at(const ChainBuf& c, const Layout& lay, const GroupTab& g, int row, int key, int b,
-                                               int local, int comp, int ld) {
-    if (c.noise) return c.noise[((size_t)row * g.Nu + g.ubase[b] + local) * ld + comp];
-    float z[4];
-    philox_normal4(c.seed, (uint32_t)lay.pocket_gid[b], (uint32_t)(lay.pocket_gid[b] >> 32),
-                   (uint32_t)key, (uint32_t)(local * 4 + (comp >> 2)), z);
-    return z[comp & 3];
-}
-
 // what k_inpaint_prep leaves, per group: the known rows normalised and the packed marks (one copy per group, written by its first
 // member from the raw inputs), and in EVERY member's slot the group's offset and its number of marked rows.  Runs after the init
 // launch (k_multi_init or k_multi_edit_start), which has projected the pockets; nothing writes them here.

@@ -565,14 +565,16 @@ __device__ __forceinline__ int group_index(const GroupTab& g, int first) {
 }
 }  // namespace
 
-// steps 1-4 for one group.  LDS: one member's pocket atoms [max_n] float4 at a time, then xhat [nl][3], the gradient sums [nl][3], e [nl].
-__global__ __launch_bounds__(1024) void k_multi_guide(Layout lay, Dims d, ChainBuf c, GroupTab g, RestrainBuf rb, Work w,
-                                                     const float* __restrict__ eps, float* __restrict__ gd) {
-    extern __shared__ float4 s_q[];                 // [max_n] pocket atoms of the member at hand
+// steps 1-4 for one group, the body of both guide kernels.  LDS: one member's pocket atoms [max_n] float4 at a time (s_q), then xhat [nl][3],
+// the gradient sums [nl][3], e [nl].  held: the group has known rows and marks (the edit chain: known [Nu][ld], fix [Nu]) and a row whose x
+// columns are held takes its given position in the current frame for xhat; without it the branch is compiled out.
+template <bool held>
+__device__ __forceinline__ void multi_guide_body(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const RestrainBuf& rb,
+                                                 const Work& w, const float* __restrict__ eps, float* __restrict__ gd,
+                                                 const float* __restrict__ known, const float* __restrict__ fix, float4* s_q, float* s_shift) {
     float* s_xh = reinterpret_cast<float*>(s_q + lay.max_n);      // [nl][3] xhat, Angstrom
     float* s_g = s_xh + (size_t)lay.max_n * 3;                    // [nl][3] dE / dxhat
     float* s_e = s_g + (size_t)lay.max_n * 3;                     // [nl] the points' shares of E
-    __shared__ float s_shift[3];
     const int grp = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6, nt = blockDim.x;
     const int first = g.group_first[grp], M = g.size[first], ub = g.ubase[first];
     const int nl = lay.num_phar[first], pb = lay.phar_base[first];
@@ -599,13 +601,15 @@ __global__ __launch_bounds__(1024) void k_multi_guide(Layout lay, Dims d, ChainB
             const float* q = c.xh_pocket + (size_t)(qb + i) * ldq;
             s_q[i] = make_float4(q[0], q[1], q[2], 0.f);
         }
-        if (m == 0)
-            for (int idx = tid; idx < 3 * nl; idx += nt) {        // 1. xhat
-                const int i = idx / 3, k = idx - 3 * i;
-                float e = combine_eps(lay, g, eps, first, M, ld, i * ld + k);
-                if (nan_reset) e = 0.f;
-                s_xh[idx] = d.norm_x * (zg[i * ld + k] - sa.x * e) / sa.y;
-            }
+        if constexpr (!held) {
+            if (m == 0)
+                for (int idx = tid; idx < 3 * nl; idx += nt) {    // 1. xhat
+                    const int i = idx / 3, k = idx - 3 * i;
+                    float e = combine_eps(lay, g, eps, first, M, ld, i * ld + k);
+                    if (nan_reset) e = 0.f;
+                    s_xh[idx] = d.norm_x * (zg[i * ld + k] - sa.x * e) / sa.y;
+                }
+        }
         __syncthreads();
         if (m == 0) {
             if (wave == nwaves - 1) {                             // 2. shift, from the first member
@@ -616,6 +620,19 @@ __global__ __launch_bounds__(1024) void k_multi_guide(Layout lay, Dims d, ChainB
             }
             __syncthreads();
             sx = s_shift[0]; sy = s_shift[1]; sz = s_shift[2];
+            if constexpr (held) {                                 // 1. xhat, behind the shift: a row whose x is held is its given position in the current frame
+                for (int idx = tid; idx < 3 * nl; idx += nt) {
+                    const int i = idx / 3, k = idx - 3 * i;
+                    if ((int)fix[ub + i] & 1) {
+                        s_xh[idx] = d.norm_x * known[(size_t)(ub + i) * ld + k] + s_shift[k];
+                    } else {
+                        float e = combine_eps(lay, g, eps, first, M, ld, i * ld + k);
+                        if (nan_reset) e = 0.f;
+                        s_xh[idx] = d.norm_x * (zg[i * ld + k] - sa.x * e) / sa.y;
+                    }
+                }
+                __syncthreads();
+            }
         }
         for (int i = wave; i < nl; i += nwaves) {                 // 3. a wave per point; the same wave owns the point for every member
             const PointTerm t = point_terms(rb, m == 0 ? r0 : 0, m == 0 ? r1 : 0, i, np, s_xh, s_q, d.norm_x, sx, sy, sz, lane);
@@ -641,6 +658,13 @@ __global__ __launch_bounds__(1024) void k_multi_guide(Layout lay, Dims d, ChainB
         for (int i = 0; i < nl; ++i) e += s_e[i];                 // index order
         rb.op_energy[(size_t)step * g.G + grp] = e;
     }
+}
+
+__global__ __launch_bounds__(1024) void k_multi_guide(Layout lay, Dims d, ChainBuf c, GroupTab g, RestrainBuf rb, Work w,
+                                                     const float* __restrict__ eps, float* __restrict__ gd) {
+    extern __shared__ float4 s_q[];                 // [max_n] pocket atoms of the member at hand, then xhat, the gradient sums, e
+    __shared__ float s_shift[3];
+    multi_guide_body<false>(lay, d, c, g, rb, w, eps, gd, nullptr, nullptr, s_q, s_shift);
 }
 
 // k_multi_step_count (kernels_multi.hip: the same LDS layout, sums and count pass) with 5. the group's displacement in the mean
@@ -776,6 +800,172 @@ __global__ __launch_bounds__(256) void k_multi_restrain_energy(Layout lay, Dims 
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// The restrained MULTI-POCKET EDIT chain (ConditionalDDPM.edit_restrained_given_pockets, cmdgen_multi_restrained_edit_chain): all three
+// modifiers at once.  The chain is cmdgen_multi_edit_chain's (kernels_multi.hip: the same layout of B member samples in G groups, both
+// inits and k_multi_edit_prep, the plan, the op table, the draw rows and the Philox counters keyed by group id, the B merge with the group's
+// offset, the C jump, the saved steps, the decode and the CoG re-centring) with the restrained multi-pocket chain's guidance in the mean of
+// op A of every op t -> s, once per GROUP, and three points settled as k_restrained_edit_step_count settles them:
+//   1. Denoised estimate.  A row of the group whose x columns are NOT held (bit 1 of InpaintBuf::fix[ubase + i] clear) has
+//      xhat_i = n_x (z.x_i - sigma_t ebar_i) / alpha_t, ebar = sum_m w_m eps_m (combine_eps), its x columns zero under the batch-wide NaN
+//      guard.  A row whose x columns ARE held has xhat_i = n_x K_i.x + shift_g: its given position moved into the current frame, the way a
+//      restraint centre is moved.
+//   2. Frame.  shift_g = n_x (com(P_first.x) - pin_com[first]), from the group's first member, its pocket as it stands at the op's input:
+//      exactly k_multi_guide's, which also covers start < timesteps, where the init has re-centred every pocket on com(K).  Step B keeps
+//      using InpaintBuf::poff.
+//   3. Displacement.  d_i (the clash over every member's atoms, the order of the sums, the max_shift clip and the guide_below test are
+//      k_multi_guide's: one body) enters mu.x_i = z.x_i / coef.x - coef.y ebar_i + d_i / n_x only on rows whose x is not held.  A held-x
+//      row gets nothing added, not even a zero (B replaces it); its energy terms still count in E and op_energy.  A row with only its
+//      types held is a free row here.  Every member reads the same bits d_i from global memory: the members' copies of z stay bit-identical.
+//   4. Tables.  RestrainBuf::sa has one row per op of the edit plan (n_steps rows, repeats after jumps included): the op that goes to level
+//      s takes row K - 1 - s of the K-row guide table.  Op C and the decode are never guided.
+// Two launches per op, for k_multi_guide's reason (a member's workgroup translates its own pocket during the step):
+//   k_multi_edit_guide                    one workgroup per GROUP.  Reads the first member's z, every member's eps rows and pockets and the
+//                                         group's known and fix rows - nothing in this launch writes any of them - and writes d [Nu][3]
+//                                         and op_energy [n_steps][G].
+//   k_multi_restrained_edit_step_count    one workgroup per MEMBER: k_multi_edit_step_count with step 5 in op A.
+// k_multi_restrain_energy fills energy_out [G][2] after the decode, unchanged.
+// Reductions that hold bit for bit on every output, the chain status and the "chain_z" debug read:
+//   - no record on any group and r_c = 0, or scale = 0, or guide_below = 0: cmdgen_multi_edit_chain's outputs for the same arguments
+//     (start < timesteps, resamplings > 1 and jump_length > 1 included);
+//   - every M_g = 1: cmdgen_restrained_edit_chain's outputs, energy_out and op_energy_out included, with no option set (both chains'
+//     evaluations run their own k_readout);
+//   - no mark in either mask, start = timesteps, resamplings = jump_length = 1: cmdgen_multi_restrained_chain's outputs;
+//   - two runs of the same inputs are equal bit for bit, captured or eager (no float atomics in the guidance).
+// LDS: 44 B per node for the guide, k_multi_edit_step_count's 64 B per node (phar_nf = 8) for the step.
+// ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void k_multi_edit_guide(Layout lay, Dims d, ChainBuf c, GroupTab g, RestrainBuf rb, Work w,
+                                                          const float* __restrict__ eps, float* __restrict__ gd,
+                                                          const float* __restrict__ known /* InpaintBuf::known */,
+                                                          const float* __restrict__ fix /* InpaintBuf::fix */) {
+    extern __shared__ float4 s_q[];                 // [max_n] pocket atoms of the member at hand, then xhat, the gradient sums, e
+    __shared__ float s_shift[3];
+    multi_guide_body<true>(lay, d, c, g, rb, w, eps, gd, known, fix, s_q, s_shift);
+}
+
+// k_multi_edit_step_count (kernels_multi.hip: the same LDS layout, sums, merge, jump and count pass) with 5. the group's displacement in the
+// mean of op A, on the rows whose x is not held
+__global__ __launch_bounds__(1024) void k_multi_restrained_edit_step_count(Layout lay, Dims d, ChainBuf c, GroupTab g, InpaintBuf ip,
+                                                                          RestrainBuf rb, Work w, const float* __restrict__ eps,
+                                                                          const float* __restrict__ gd) {
+    extern __shared__ float4 s_pos[];               // [max_n] positions of the sample (phar first), then int sdeg[max_n], then z
+    int* sdeg = reinterpret_cast<int*>(s_pos + lay.max_n);
+    float* s_z = reinterpret_cast<float*>(sdeg + lay.max_n);      // [nl * ld]
+    __shared__ float s_mean[3];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nt = blockDim.x;
+    const int nl = lay.num_phar[b], np = lay.num_pocket[b], n = nl + np;
+    const int pb = lay.phar_base[b], qb = lay.pocket_base[b];
+    const int ld = 3 + d.P, ldq = 3 + d.R;
+    const int first = g.first[b], M = g.size[b], ub = g.ubase[b];
+    const int step = c.state->step - 1;             // index of this op
+    const float4 cf = c.coef[step];
+    const float4 cf2 = ip.coef2[step];
+    const int4 io = ip.iop[step];
+    const float4 off0 = ip.poff[b];                 // this member's copy of the group's offset
+    const bool merge = off0.w > 0.f;
+    const bool nan_reset = *w.nan_flag != 0;
+    const int grp = group_index(g, first);
+    const bool touched = rb.rstart[grp + 1] > rb.rstart[grp] || rb.clash_r > 0.f;
+    const bool guided = touched && rb.scale > 0.f && cf.w <= rb.guide_below;      // k_multi_edit_guide's, which then wrote the group's d
+    float* zg = c.z_phar + (size_t)pb * ld;
+    const int cnt = nl * ld;
+    for (int idx = tid; idx < cnt; idx += nt) s_z[idx] = zg[idx];
+    for (int i = tid; i < np; i += nt) {
+        const float* q = c.xh_pocket + (size_t)(qb + i) * ldq;
+        s_pos[nl + i] = make_float4(q[0], q[1], q[2], 0.f);
+    }
+    __syncthreads();
+    if (wave == 0) record_com_check(c.check + 2 * (1 + step), s_z, ld, 0, nl, 1.0f, lane);   // z_t, the op's input
+    __syncthreads();
+    // A: the posterior step on eps_bar (k_multi_step_count's expressions) with 5. the displacement on the rows whose x is not held
+    for (int idx = tid; idx < cnt; idx += nt) {
+        const int i = idx / ld, k = idx - i * ld;
+        float e = combine_eps(lay, g, eps, first, M, ld, idx);
+        if (nan_reset && k < 3) e = 0.f;
+        float mu = s_z[idx] / cf.x - cf.y * e;
+        if (guided && k < 3 && !((int)ip.fix[ub + i] & 1)) mu = mu + gd[(size_t)(ub + i) * 3 + k] / d.norm_x;
+        s_z[idx] = mu + cf.z * draw_group_at(c, lay, g, io.y, 1 + step, b, i, k, ld);
+    }
+    __syncthreads();
+    phar_mean(s_z, nl, ld, tid, s_mean);
+    __syncthreads();
+    float o0, o1, o2;                               // the group's offset in the frame of the pocket in LDS
+    {
+        const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
+        sub_mean(s_z, s_pos, nl, n, ld, tid, nt, m0, m1, m2);
+        o0 = off0.x - m0; o1 = off0.y - m1; o2 = off0.z - m2;
+    }
+    __syncthreads();
+    // B: the noised known rows moved into the current frame replace the held column groups; then the phar COM projection
+    if (merge) {
+        const int keyB = 2 + ip.n_steps + step;
+        for (int idx = tid; idx < cnt; idx += nt) {
+            const int i = idx / ld, k = idx - i * ld;
+            if (!((int)ip.fix[ub + i] & (k < 3 ? 1 : 2))) continue;
+            float zk = cf2.x * ip.known[(size_t)ub * ld + idx] + cf2.y * draw_group_at(c, lay, g, io.z, keyB, b, i, k, ld);
+            if (k < 3) zk = zk + (k == 0 ? o0 : k == 1 ? o1 : o2);
+            s_z[idx] = zk;
+        }
+        __syncthreads();
+        phar_mean(s_z, nl, ld, tid, s_mean);
+        __syncthreads();
+        const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
+        sub_mean(s_z, s_pos, nl, n, ld, tid, nt, m0, m1, m2);
+        o0 -= m0; o1 -= m1; o2 -= m2;
+        __syncthreads();
+    }
+    // the state after the op (a frame): the group's z by its first member, every member's pocket
+    if (c.z_steps && b == first)
+        for (int idx = tid; idx < cnt; idx += nt) c.z_steps[((size_t)step * g.Nu + ub) * ld + idx] = s_z[idx];
+    if (c.pocket_steps)
+        for (int i = tid; i < np; i += nt) {
+            const float4 p = s_pos[nl + i];
+            float* o = c.pocket_steps + ((size_t)step * lay.Np + qb + i) * 3;
+            o[0] = p.x; o[1] = p.y; o[2] = p.z;
+        }
+    // C: jump back, z_t' ~ q(z_t' | z_s) (never guided)
+    if (io.x & 1) {
+        const int keyC = 2 + 2 * ip.n_steps + step;
+        for (int idx = tid; idx < cnt; idx += nt) {
+            const int i = idx / ld, k = idx - i * ld;
+            const float mu = cf2.z * s_z[idx];
+            s_z[idx] = mu + cf2.w * draw_group_at(c, lay, g, io.w, keyC, b, i, k, ld);
+        }
+        __syncthreads();
+        phar_mean(s_z, nl, ld, tid, s_mean);
+        __syncthreads();
+        const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
+        sub_mean(s_z, s_pos, nl, n, ld, tid, nt, m0, m1, m2);
+        o0 -= m0; o1 -= m1; o2 -= m2;
+        __syncthreads();
+    }
+    // the new state, and the inputs of the next evaluation
+    for (int i = tid; i < n; i += nt) {
+        float4 p;
+        if (i < nl) {
+            const float* z = s_z + i * ld;
+            p = make_float4(z[0], z[1], z[2], 0.f);
+            w.X0[pb + i] = p;
+            for (int l = 0; l < d.L; ++l) w.ACC[(size_t)l * lay.Nm + pb + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            s_pos[i] = p;
+        } else {
+            p = s_pos[i];
+            float* q = c.xh_pocket + (size_t)(qb + i - nl) * ldq;
+            q[0] = p.x; q[1] = p.y; q[2] = p.z;
+            w.XP[qb + i - nl] = p;
+        }
+    }
+    for (int idx = tid; idx < cnt; idx += nt) zg[idx] = s_z[idx];
+    if (tid == 0) ip.poff[b] = make_float4(o0, o1, o2, off0.w);
+    __syncthreads();
+    count_next_graph(lay, d, w, s_pos, sdeg, b, nl, n, pb, qb);
+    if (b == 0 && tid == 0) {
+        if (nan_reset) atomicAdd(&w.counters[4], 1ull);
+        atomicAdd(&w.counters[0], 1ull);                       // evaluations (the one about to run)
+        atomicAdd(&w.counters[3], (unsigned long long)lay.N);  // nodes
+    }
+}
+
 void cmdgen_launch_restrain_prep(const Layout& lay, const Dims& d, const RestrainBuf& rb, const float* px, hipStream_t s) {
     hipLaunchKernelGGL(k_restrain_prep, dim3(lay.B), dim3(64), 0, s, lay, d, rb, px);
 }
@@ -803,6 +993,14 @@ void cmdgen_launch_multi_restrained_step(const Layout& lay, const Dims& d, const
     const size_t shm_step = (size_t)lay.max_n * (sizeof(float4) + sizeof(int)) + (size_t)lay.max_n * (3 + d.P) * sizeof(float);
     hipLaunchKernelGGL(k_multi_guide, dim3(g.G), block, shm_guide, s, lay, d, c, g, rb, w, eps, gd);
     hipLaunchKernelGGL(k_multi_restrained_step_count, dim3(lay.B), block, shm_step, s, lay, d, c, g, rb, w, eps, (const float*)gd);
+}
+void cmdgen_launch_multi_restrained_edit_step(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const InpaintBuf& ip,
+                                              const RestrainBuf& rb, const Work& w, const float* eps, float* gd, hipStream_t s) {
+    const dim3 block(lay.max_n > 128 ? 1024 : 256);             // as k_multi_guide and k_multi_edit_step_count
+    const size_t shm_guide = (size_t)lay.max_n * (sizeof(float4) + 7 * sizeof(float));
+    const size_t shm_step = (size_t)lay.max_n * (sizeof(float4) + sizeof(int)) + (size_t)lay.max_n * (3 + d.P) * sizeof(float);
+    hipLaunchKernelGGL(k_multi_edit_guide, dim3(g.G), block, shm_guide, s, lay, d, c, g, rb, w, eps, gd, ip.known, (const float*)ip.fix);
+    hipLaunchKernelGGL(k_multi_restrained_edit_step_count, dim3(lay.B), block, shm_step, s, lay, d, c, g, ip, rb, w, eps, (const float*)gd);
 }
 void cmdgen_launch_multi_restrain_energy(const Layout& lay, const Dims& d, const GroupTab& g, const RestrainBuf& rb, const float* xo,
                                          const float* po, float* energy_out, hipStream_t s) {

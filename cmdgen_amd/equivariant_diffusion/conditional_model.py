@@ -566,6 +566,49 @@ class ConditionalDDPM(EnVariationalDiffusion):
         return out[0], [out[1][..., r, :] for r in rows], phar_mask, [q['mask'] for q in pockets]
 
     @torch.no_grad()
+    def edit_restrained_given_pockets(self, phar, pockets, restraints, fix_coords=None, fix_types=None, start=None, resamplings=1,
+                                      jump_length=1, weights=None, clash=None, scale=1.0, max_shift=None, guide_below=1.0, timesteps=None,
+                                      noise=None, seed=None, group_ids=None):
+        """``edit_given_pockets`` STEERED by ``sample_restrained_given_pockets``' geometric query - all three modifiers at once: keep the
+        points known from one target, grow or re-place the others for every pocket of the group under position, distance, exclusion and
+        clash terms.  The chain is ``edit_given_pockets``' (the same start, ops, draws, Philox counters, merge, jumps and decode) with the
+        guidance of ``sample_restrained_given_pockets`` in the posterior op (op A) of every op, once per group; the jump-back op and the
+        decode are not guided (cmdgen_multi_restrained_edit_chain; the header of k_multi_edit_guide in csrc/kernels_restrain.hip defines
+        it).  A point whose coordinates are held enters the group's restraint energy at its GIVEN position (moved into the chain's frame by
+        the shift of the group's first pocket) and is not displaced; a point with only its type held is steered like a free one.
+
+        phar, pockets, fix_coords, fix_types, start, resamplings, jump_length, weights, timesteps, noise, seed and group_ids as
+        ``edit_given_pockets``; restraints (the dicts name their GROUP under 'sample', centres in the pockets' common frame), clash,
+        scale, max_shift and guide_below as ``sample_restrained_given_pockets``.  With no restraint and no clash term, or scale = 0, the
+        result is ``edit_given_pockets``' bit for bit; with one pocket it is ``edit_restrained``'s.
+        Returns (xh_phar [Nu, 3+P], [xh_pocket_m], phar_mask, [pocket_mask_m], {'energy': [G], 'max_violation': [G]}): the energy and the
+        largest violation (A) of the returned sample against all its pockets, held points included at their returned positions."""
+        from .. import restraints as rs
+        pockets, M, G = self._checked_pockets(pockets)
+        timesteps, start = self._checked_start(timesteps, start)
+        nph = self._group_phar_sizes(phar, G)
+        w = self.group_weights(weights, G, M)
+        device = pockets[0]['x'].device
+        n_phar = int(nph.sum())
+        fix_x = self._row_mask(fix_coords, 'fix_coords', n_phar, device)
+        fix_h = self._row_mask(fix_types, 'fix_types', n_phar, device)
+        self._check_phar_rows(phar, n_phar)
+        rec = rs.records(restraints, nph, owner='group')                  # per group: 'sample' is the group index
+        clash_r, clash_k = rs.clash_pair(clash)
+        scale, max_shift, guide_below = rs.check_scalars(scale, rs.DEFAULT_MAX_SHIFT if max_shift is None else max_shift, guide_below)
+        sizes, rows, px, poh = self._member_layout(pockets, M, G)
+        h, phar_mask, noise, seed = self._prepare_edit(nph, (np.repeat(nph, M), sizes.reshape(-1)), device, timesteps, start, resamplings,
+                                                       jump_length, noise, seed, guide=True)
+        f32 = lambda t: t.detach().to(device, torch.float32).contiguous()
+        args = (px, poh, [M] * G, w.reshape(-1), f32(phar['x']), f32(phar['one_hot']), fix_x, fix_h)
+        run = lambda: h.multi_restrained_edit_chain(*args, timesteps, start=start, resamplings=resamplings, jump_length=jump_length,
+                                                    restraints=rec, clash_radius=clash_r, clash_k=clash_k, scale=scale, max_shift=max_shift,
+                                                    guide_below=guide_below, noise=noise, seed=seed, group_ids=group_ids,
+                                                    use_graph=self.use_hip_graph)
+        out, info = self._finish_restrained(h, run, [], 1)
+        return out[0], [out[1][..., r, :] for r in rows], phar_mask, [q['mask'] for q in pockets], info
+
+    @torch.no_grad()
     def score(self, phar, pocket, timesteps=None, repeats=1, noise=None, seed=None, pocket_ids=None, return_levels=False):
         """How likely the model finds a GIVEN pharmacophore in its pocket: the per-sample negative log-likelihood bound of
         ``forward`` in eval mode (conditional_model.py:198-320 with lightning_modules.py:211-229), but over a fixed grid of
@@ -776,6 +819,11 @@ class SimpleConditionalDDPM(ConditionalDDPM):
     def edit_given_pockets(self, *args, **kwargs):
         raise NotImplementedError('edit_given_pockets is not implemented for SimpleConditionalDDPM (no centre-of-mass projection: the '
                                   'shared latent has no frame of its own); use ConditionalDDPM')
+
+    def edit_restrained_given_pockets(self, *args, **kwargs):
+        raise NotImplementedError('edit_restrained_given_pockets is not implemented for SimpleConditionalDDPM (no centre-of-mass '
+                                  'projection: the shared latent has no frame of its own for the edit chain and the guidance to '
+                                  'follow); use ConditionalDDPM')
 
     def score_given_pockets(self, *args, **kwargs):
         raise NotImplementedError('score_given_pockets is not implemented for SimpleConditionalDDPM (the scoring chain projects every '

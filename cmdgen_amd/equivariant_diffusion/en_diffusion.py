@@ -594,6 +594,11 @@ class EnVariationalDiffusion(nn.Module):
         raise NotImplementedError('edit_given_pockets is not implemented for the joint model (its pocket nodes diffuse with the '
                                   'latent, so several pockets cannot share one); use ConditionalDDPM')
 
+    def edit_restrained_given_pockets(self, *args, **kwargs):
+        raise NotImplementedError('edit_restrained_given_pockets is not implemented for the joint model (its pocket nodes diffuse with '
+                                  'the latent, so several pockets cannot share one and there is no fixed frame for the restraints); use '
+                                  'ConditionalDDPM')
+
     def score_given_pockets(self, *args, **kwargs):
         raise NotImplementedError('score_given_pockets is not implemented for the joint model: its loss has the pocket\'s own terms, '
                                   'and its pocket nodes diffuse with the latent; use ConditionalDDPM')

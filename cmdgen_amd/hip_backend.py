@@ -84,6 +84,9 @@ SYMBOLS = [
     ('cmdgen_multi_restrained_chain', C.c_int, [_vp, _fp, _fp, C.c_int64, _i64p, _vp, C.c_int32, _vp, C.c_int64, C.c_float, C.c_float,
                                                 C.c_float, C.c_float, C.c_float, _fp, C.c_uint64, _i64p, _fp, _fp, _fp, _fp, _fp, _fp,
                                                 C.c_int32, _vp]),
+    ('cmdgen_multi_restrained_edit_chain', C.c_int, [_vp, _fp, _fp, C.c_int64, _i64p, _vp, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32,
+                                                     C.c_int32, _fp, C.c_int64, C.c_uint64, _i64p, _fp, _fp, _fp, _fp, _vp, C.c_int64,
+                                                     C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _fp, _fp, C.c_int32, _vp]),
     ('cmdgen_set_guide_table', C.c_int, [_vp, C.c_int32, _vp]),
     ('cmdgen_param_count', C.c_int, [_vp, _i64p]),
     ('cmdgen_param_offset', C.c_int, [_vp, C.c_char_p, _i64p, _i64p]),
@@ -631,6 +634,36 @@ class Handle:
             *self._noise_arg(noise), self._seed(seed), ids, _ptr(xh_phar),
             _ptr(xh_pocket), _ptr(z_steps), _ptr(p_steps), int(bool(use_graph)), self._stream()), 'cmdgen_multi_edit_chain')
         return xh_phar, xh_pocket, z_steps
+
+    def multi_restrained_edit_chain(self, pocket_x, pocket_onehot, group_sizes: Sequence[int], weights, phar_x, phar_onehot, fix_x, fix_h,
+                                    timesteps: int, start: Optional[int] = None, resamplings: int = 1, jump_length: int = 1, restraints=None,
+                                    clash_radius: float = 0.0, clash_k: float = 0.0, scale: float = 1.0,
+                                    max_shift: float = DEFAULT_MAX_SHIFT, guide_below: float = 1.0, noise=None, seed: int = 0,
+                                    group_ids: Optional[Sequence[int]] = None, want_steps: bool = False, use_graph: bool = True):
+        """cmdgen_multi_restrained_edit_chain: multi_edit_chain with multi_restrained_chain's guidance term in op A of every op, once per
+        group (the header of k_multi_edit_guide in kernels_restrain.hip defines it): a held point enters the group's restraint energy at its
+        given position and is not displaced.  The arguments are multi_edit_chain's, then multi_restrained_chain's (restraints: a
+        RESTRAINT_DTYPE array whose 'sample' is the GROUP index, or None).
+        -> (xh_phar [Nu, 3+P], xh_pocket, z_steps, energy [G, 2] (E and the largest violation in A of the output), op_energy [n_steps, G] or
+        None); with want_steps every member's pocket after every op is left in last_pocket_steps."""
+        import torch
+        start = timesteps if start is None else start
+        sizes, w, ids, n_unique = self._group_args(group_sizes, weights, group_ids)
+        self._check_edit_inputs(pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h, n_unique)
+        n_steps, n_draws = self.edit_plan(timesteps, start, resamplings, jump_length)
+        self._check_draws(noise, n_unique)
+        rec, n_rec = self._restraint_arg(restraints)
+        dev = pocket_x.device
+        xh_phar, xh_pocket, z_steps, p_steps = self._chain_outputs(n_unique, n_steps, want_steps, dev)
+        energy = torch.empty((len(sizes), 2), dtype=torch.float32, device=dev)
+        op_energy = torch.empty((n_steps, len(sizes)), dtype=torch.float32, device=dev) if want_steps else None
+        self._check(self.lib.cmdgen_multi_restrained_edit_chain(
+            self.h, _ptr(pocket_x), _ptr(pocket_onehot), len(sizes), sizes.ctypes.data_as(_i64p), w.ctypes.data_as(C.c_void_p),
+            _ptr(phar_x), _ptr(phar_onehot), _ptr(fix_x), _ptr(fix_h), int(timesteps), int(start), int(resamplings), int(jump_length),
+            *self._noise_arg(noise), self._seed(seed), ids, _ptr(xh_phar), _ptr(xh_pocket), _ptr(z_steps), _ptr(p_steps), rec, n_rec,
+            float(clash_radius), float(clash_k), float(scale), float(max_shift), float(guide_below), _ptr(energy), _ptr(op_energy),
+            int(bool(use_graph)), self._stream()), 'cmdgen_multi_restrained_edit_chain')
+        return xh_phar, xh_pocket, z_steps, energy, op_energy
 
     SC_COLS = 4                      # include/cmdgen_hip.h: CMDGEN_SC_COLS
 

@@ -689,6 +689,58 @@ class PharPocketDDPM(nn.Module):
         xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
         return self._point_lists(xh_phar, phar)
 
+    @torch.no_grad()
+    def edit_phars_multi_restrained(self, pdb_files, n_samples, phars, restraints, keep='both', strength=None, clash=None,
+                                    num_nodes_phar=None, pocket_ids=None, ref_ligands=None, weights=None, scale=1.0, max_shift=None,
+                                    guide_below=1.0, timesteps=None, resamplings=1, jump_length=1, seed=None):
+        """edit_phars_multi STEERED by a geometric query (ConditionalDDPM.edit_restrained_given_pockets): "keep the three points known from
+        kinase A and grow two more for kinases A and B together - a hydrophobe 5 to 7 A from the held donor, one point inside the
+        sub-pocket only B has, none within 3 A of an atom of either pocket".
+
+        pdb_files, pocket_ids / ref_ligands, weights, phars, keep, strength, num_nodes_phar, resamplings and jump_length as
+        edit_phars_multi (keep defaults to 'both': the given points stay); restraints, clash, scale, max_shift and guide_below as
+        generate_phars_multi_restrained: the dicts of cmdgen_amd/restraints.py WITHOUT 'sample', given once in the common frame, and every
+        one of the n_samples copies gets the list; clash holds against the atoms of every pocket.  A point index names a row of every
+        sample: rows 0 .. len(phars) - 1 are the given points, the rows behind them the free ones.  Everything is moved back by the FIRST
+        pocket's shift - the frame the guidance itself follows.
+        -> (one point list per sample in the common frame, {'energy': [n_samples], 'max_violation': [n_samples]} of the returned samples)."""
+        from . import restraints as rs
+        pdb_files = list(pdb_files)
+        M = len(pdb_files)
+        assert (pocket_ids is None) ^ (ref_ligands is None)
+        if len(pocket_ids if pocket_ids is not None else ref_ligands) != M:
+            raise ValueError(f'{M} pdb_files need {M} entries of pocket_ids or ref_ligands (one per file)')
+        if not isinstance(self.ddpm, ConditionalDDPM):
+            raise NotImplementedError('edit_phars_multi_restrained needs the conditional model (mode pocket_conditioning)')
+        restraints = list(restraints)
+        for n, r in enumerate(restraints):
+            if isinstance(r, dict) and 'sample' in r:
+                raise ValueError(f"restraints[{n}] = {r!r}: restraints are given once, without 'sample', and applied to every sample")
+        named = [int(v) for r in restraints if isinstance(r, dict)
+                 for v in ([r['point']] if 'point' in r else list(r.get('points', ()))) if isinstance(v, (int, np.integer))]
+        keeps, start = self._edit_keeps_and_start(phars, keep, strength, timesteps)
+        pockets = [self._pdb_pocket(f, n_samples, pocket_ids[m] if pocket_ids is not None else None,
+                                    ref_ligands[m] if ref_ligands is not None else None) for m, f in enumerate(pdb_files)]
+        first = pockets[0]
+        pocket_com_before = _scatter_mean(first['x'], first['mask'], n_samples)
+        T = self.ddpm.T if timesteps is None else int(timesteps)
+        if num_nodes_phar is None and not (start is not None and start < T):
+            # from the prior: the size prior given the FIRST pocket, at least the given points and the rows the restraints name
+            num_nodes_phar = self.ddpm.size_distribution.sample_conditional(n1=None, n2=first['size'])
+            num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device).clamp(min=max(len(phars), max(named, default=0) + 1))
+        phar, fix_x, fix_h = self._edit_phar_and_masks(phars, keeps, start, strength, timesteps, n_samples, num_nodes_phar, first)
+        nph = phar['size'].cpu().numpy()
+        for b in range(n_samples):
+            rs.records(restraints, nph, sample=b)                       # (names the entry of the caller's list)
+        per_sample = [dict(r, sample=b) for b in range(n_samples) for r in restraints]
+        xh_phar, xh_pockets, phar_mask, pocket_masks, info = self.ddpm.edit_restrained_given_pockets(
+            phar, pockets, per_sample, fix_coords=fix_x, fix_types=fix_h, start=start, resamplings=resamplings, jump_length=jump_length,
+            weights=weights, clash=clash, scale=scale, max_shift=max_shift, guide_below=guide_below, timesteps=timesteps, seed=seed)
+        # move the points back by the first pocket's shift (every pocket was translated by the same vector; the centres never moved)
+        pocket_com_after = _scatter_mean(xh_pockets[0][:, :self.x_dims], pocket_masks[0], n_samples)
+        xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
+        return self._point_lists(xh_phar, phar), info
+
     # ------------------------------------------------------------------ scoring
     def _score_model(self):
         if not isinstance(self.ddpm, ConditionalDDPM):

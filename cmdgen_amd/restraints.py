@@ -50,17 +50,18 @@ def _center(n, r):
     return c
 
 
-def _point(n, r, v, nl, sample):
+def _point(n, r, v, nl, sample, owner='sample'):
     if isinstance(v, bool) or int(v) != v:
         raise _bad(n, r, f'point index {v!r} is not an integer')
     if not 0 <= int(v) < nl:
-        raise _bad(n, r, f'point {int(v)}: sample {sample} has {nl} points')
+        raise _bad(n, r, f'point {int(v)}: {owner} {sample} has {nl} points')
     return int(v)
 
 
-def records(restraints, num_phar, sample=None):
+def records(restraints, num_phar, sample=None, owner='sample'):
     """The checked record array (RESTRAINT_DTYPE) of a list of restraint dicts.  num_phar [B]: points per sample.  sample: None - every
-    dict names its 'sample'; an int - the dicts carry none and all belong to that sample.  ValueError names the offending entry."""
+    dict names its 'sample'; an int - the dicts carry none and all belong to that sample.  owner: what a 'sample' is called in the messages
+    ('group' where the records belong to the groups of a multi-pocket call).  ValueError names the offending entry."""
     nph = np.asarray(num_phar, dtype=np.int64).reshape(-1)
     out = np.zeros(len(restraints), dtype=RESTRAINT_DTYPE)
     per_sample = np.zeros(len(nph), dtype=np.int64)
@@ -77,7 +78,7 @@ def records(restraints, num_phar, sample=None):
                        (f'; not understood {extra}' if extra else ''))
         b = r['sample'] if sample is None else sample
         if isinstance(b, bool) or int(b) != b or not 0 <= int(b) < len(nph):
-            raise _bad(n, r, f'sample {b!r} outside the batch of {len(nph)} samples')
+            raise _bad(n, r, f'{owner} {b!r} outside the batch of {len(nph)} {owner}s')
         b, nl = int(b), int(nph[int(b)])
         rec = out[n]
         rec['kind'], rec['sample'], rec['k'] = KINDS[kind], b, _nonneg(n, r, 'k')
@@ -85,7 +86,7 @@ def records(restraints, num_phar, sample=None):
             pts = r['points']
             if not hasattr(pts, '__len__') or len(pts) != 2:
                 raise _bad(n, r, 'points must be a pair (i, j)')
-            rec['i'], rec['j'] = _point(n, r, pts[0], nl, b), _point(n, r, pts[1], nl, b)
+            rec['i'], rec['j'] = _point(n, r, pts[0], nl, b, owner), _point(n, r, pts[1], nl, b, owner)
             if rec['i'] == rec['j']:
                 raise _bad(n, r, f"a distance between point {int(rec['i'])} and itself (i == j)")
             lo, hi = _nonneg(n, r, 'lo'), _nonneg(n, r, 'hi')
@@ -94,12 +95,12 @@ def records(restraints, num_phar, sample=None):
             rec['a'], rec['b'] = lo, hi
         else:
             if kind == 'position':
-                rec['i'] = _point(n, r, r['point'], nl, b)
+                rec['i'] = _point(n, r, r['point'], nl, b, owner)
             rec['c'] = _center(n, r)
             rec['a'] = _nonneg(n, r, 'radius')
         per_sample[b] += 1
         if per_sample[b] > MAX_RESTRAINTS:
-            raise _bad(n, r, f'sample {b} has more than {MAX_RESTRAINTS} restraints')
+            raise _bad(n, r, f'{owner} {b} has more than {MAX_RESTRAINTS} restraints')
     return out
 
 

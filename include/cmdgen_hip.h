@@ -579,6 +579,54 @@ int cmdgen_multi_restrained_chain(cmdgen_handle* h, const float* pocket_x, const
                                   float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
                                   float* energy_out, float* op_energy_out, int32_t use_graph, cmdgen_stream stream);
 
+/* Editing under restraints for several pockets (ConditionalDDPM.edit_restrained_given_pockets): all three modifiers at once.  The chain is
+ * cmdgen_multi_edit_chain's - the same layout of B member samples in G groups, both inits, the plan, the op table, the draw rows and the
+ * Philox counters keyed by group id, the B merge with the group's offset, the C jump, the saved steps, the decode and the CoG re-centring -
+ * with cmdgen_multi_restrained_chain's guidance in the mean of op A of every op t -> s, once per GROUP.  The definition is the project's
+ * own; kernels_restrain.hip ("The restrained MULTI-POCKET EDIT chain") carries it in full.  The terms, the clash over every member's atoms,
+ * the order of the sums, the max_shift clip and guide_below are cmdgen_multi_restrained_chain's, with three points settled as
+ * cmdgen_restrained_edit_chain settles them:
+ *   xhat_i   of a row of the group whose x columns are not held is n_x (z.x_i - sigma_t ebar_i) / alpha_t, ebar = sum_m w_m eps_m (m ascending,
+ *            the first term not added to a zero; zero x columns under the batch-wide NaN guard); of a row whose x columns ARE held (fix_x of
+ *            the group's row non-zero) it is n_x K_i.x + shift_g, its given position moved into the current frame as a restraint centre is
+ *   shift_g  = n_x (com(P_first.x) - com(P_first,in.x / n_x)), from the group's FIRST member, its pocket as it stands at the op's input -
+ *            which also covers start < timesteps, where the init has re-centred every pocket on the given rows' centre.  Step B keeps its
+ *            own offset, as in cmdgen_multi_edit_chain
+ *   mu.x_i   = z.x_i / coef.x - coef.y ebar_i + d_i / n_x on rows whose x is not held; a row whose x is held gets nothing added, not even a
+ *            zero (B replaces it), while its energy terms still count in E and op_energy.  A row with only its types held is a free row
+ *            here.  Every member adds the SAME BITS d_i, so the members' copies of z stay bit-identical (cmdgen_debug_read("chain_z"))
+ *   sigma_t, alpha_t  one row per op of the edit plan (n_steps, repeats after jumps included): the op that goes to level s takes row
+ *            K - 1 - s of the guide table (cmdgen_set_guide_table with K = timesteps, or the library's own evaluation).  Op C and the
+ *            decode are never guided
+ * Reductions that hold bit for bit on every output, cmdgen_chain_status and cmdgen_debug_read("chain_z"):
+ *   - no record on any group and clash_radius = 0, or scale = 0, or guide_below = 0: cmdgen_multi_edit_chain's outputs for the same
+ *     arguments (start < timesteps, resamplings > 1 and jump_length > 1 included); a group-op that is not guided adds nothing, not even a zero
+ *   - every group of one member: cmdgen_restrained_edit_chain's outputs, energy_out and op_energy_out included, with no option set
+ *   - no mark in either mask, start = timesteps, resamplings = jump_length = 1: cmdgen_multi_restrained_chain's outputs (noise rows in
+ *     cmdgen_multi_edit_chain's order)
+ *   - two runs of the same inputs are equal bit for bit, captured or eager (no float atomics)
+ *   energy_out     dev [G][2]: E and the largest violation (Angstrom) of the RETURNED rows, held points included at their returned positions,
+ *                  against every member's returned pocket, the shift taken from the first member's returned pocket
+ *   op_energy_out  dev [n_steps][G] E at xhat of every op (n_steps of cmdgen_edit_plan), or NULL
+ *   the other arguments as cmdgen_multi_edit_chain, then as cmdgen_multi_restrained_chain (cmdgen_restraint::sample is the GROUP index);
+ *   cmdgen_edit_plan gives n_steps and n_draws; injected noise is [n_draws][Nu][3 + phar_nf]
+ * The chain has a slot of its own; its tables are the edit plan's tables, the group tables and the guidance tail (one guide row per op of
+ * the plan, the five scalars, CSR offsets [G + 1], the records sorted by group), so a changed grouping, weight, plan, start, restraint or
+ * scalar prepares the slot (and its graph) again.
+ * Refused: whatever cmdgen_multi_edit_chain refuses and whatever cmdgen_multi_restrained_chain refuses of a restraint list and scalars,
+ * with the same codes; the messages name the argument and say "group" where a group is meant.  The joint model and no_com_projection
+ * handles (CMDGEN_ESTATE). */
+int cmdgen_multi_restrained_edit_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
+                                       int64_t n_groups, const int64_t* group_size_host, const float* weight_host,
+                                       const float* phar_x, const float* phar_onehot, const float* fix_x, const float* fix_h,
+                                       int32_t timesteps, int32_t start, int32_t resamplings, int32_t jump_length,
+                                       const float* noise, int64_t n_draws, uint64_t seed, const int64_t* group_ids_host,
+                                       float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                                       const cmdgen_restraint* restraints_host, int64_t n_restraints,
+                                       float clash_radius, float clash_k, float scale, float max_shift, float guide_below,
+                                       float* energy_out /* dev [G][2] */, float* op_energy_out /* dev [n_steps][G] or NULL */,
+                                       int32_t use_graph, cmdgen_stream stream);
+
 /* ---- training step (conditional model) -------------------------------------------------- */
 /* The trainable tensors of EGNNDynamics live in ONE flat fp32 device buffer owned by the caller, in the
  * reference's registration order (the state_dict order below 'ddpm.dynamics.': weight then bias of every
