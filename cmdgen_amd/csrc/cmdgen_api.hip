@@ -1193,8 +1193,7 @@ static int build_group_plan(cmdgen_handle* h, int64_t n_groups, const int64_t* g
         members += M;
     }
     if (members != B) return fail(h, CMDGEN_EINVAL, "the group sizes sum to %lld, the layout has %d samples", (long long)members, B);
-    const size_t step_lds = (size_t)h->lay.max_n * (sizeof(float4) + sizeof(int) + (size_t)(3 + h->dims.P) * sizeof(float));
-    if (step_lds > 64 * 1024)
+    if (plan_step_lds(h->lay.max_n, h->dims.P) > 64 * 1024)
         return fail(h, CMDGEN_EINVAL, "a sample has %d nodes: the multi-pocket step keeps a sample's positions, degrees and z in LDS (64 KiB)", h->lay.max_n);
     p.G = G; p.Nu = Nu;
     return 0;

@@ -279,20 +279,19 @@ inline LaunchPlan make_plan(const PlanInput& in) {
     return p;
 }
 
+// The dynamic LDS of a derived chain's step kernel (StepWg, cmdgen_step_parts.h): a float4 position and a degree per node of the largest sample, z per row.
+inline size_t plan_step_lds(int max_n, int P) { return (size_t)max_n * (16 + sizeof(int) + (size_t)(3 + P) * sizeof(float)); }
+
 // The restrained chain's step kernel (k_restrained_step_count, kernels_restrain.hip) runs in the plain chain's place and takes both of its forms: where
 // readout_in_coord holds it forms the velocity and the NaN flag itself (readout_mode).  Beside k_step_count's LDS (a float4 position and a degree per node,
 // z and the velocity per row) it keeps the denoised estimate, the displacement and the energy term of every row: bytes per workgroup, at most 64 KiB.
 constexpr size_t PLAN_RESTRAINED_LDS_MAX = 64 * 1024;
-inline size_t plan_restrained_step_lds(int max_n, int P) {
-    return (size_t)max_n * (16 + sizeof(int) + (size_t)(3 + P) * sizeof(float) + 3 * sizeof(float) + 7 * sizeof(float));
-}
+inline size_t plan_restrained_step_lds(int max_n, int P) { return plan_step_lds(max_n, P) + (size_t)max_n * (3 + 7) * sizeof(float); }
 
 // The restrained edit chain's step kernel (k_restrained_edit_step_count, kernels_restrain.hip) keeps k_inpaint_step_count's LDS (a float4 position and a
 // degree per node, z per row), then the denoised estimate, the displacement and the energy term of every row; eps comes from eps_tmp, so there is no
 // velocity array.  Bytes per workgroup, at most PLAN_RESTRAINED_LDS_MAX.
-inline size_t plan_restrained_edit_step_lds(int max_n, int P) {
-    return (size_t)max_n * (16 + sizeof(int) + (size_t)(3 + P) * sizeof(float) + 7 * sizeof(float));
-}
+inline size_t plan_restrained_edit_step_lds(int max_n, int P) { return plan_step_lds(max_n, P) + (size_t)max_n * 7 * sizeof(float); }
 
 // the launch keys of cmdgen_query (include/cmdgen_hip.h); false: not a launch key
 inline bool plan_query(const LaunchPlan& p, const char* key, int64_t* value) {

@@ -1,4 +1,5 @@
-// cmdgen_sampler.h - device helpers of the conditional sampler kernels (kernels_ddpm.hip, kernels_inpaint.hip, kernels_score.hip, kernels_multi.hip).
+// cmdgen_sampler.h - device helpers of the conditional sampler kernels (kernels_ddpm.hip, kernels_score.hip, and through cmdgen_step_parts.h, which
+// composes the derived chains' step kernels from them, kernels_inpaint.hip, kernels_multi.hip and kernels_restrain.hip).
 // These translation units are built with -ffp-contract=off, so the same helper rounds the same way in each.
 #pragma once
 #include "cmdgen_dev.h"
@@ -29,26 +30,28 @@ __device__ __forceinline__ void record_com_check(unsigned int* slot2, const floa
     if (lane == 0) { atomic_max_pos(slot2, mx); atomic_max_pos(slot2 + 1, s); }
 }
 
+// One draw of a derived chain, component comp of row `local` of sample b's rows: injected noise row `row` ([stride] rows per draw, the sample's first
+// at `base`: Layout::Nl and phar_base[b], or for a group GroupTab::Nu and ubase[b]), or Philox keyed by Layout::pocket_gid[b] (the sample's global
+// pocket id, or its group's id, which every member holds) with the draw counter `key`.  Row and counter are given apart: the edit plan's rows are in
+// call order, its counters are not.
+__device__ __forceinline__ float chain_draw(const ChainBuf& c, const Layout& lay, int stride, int base, int row, int key, int b, int local, int comp,
+                                            int ld) {
+    if (c.noise) return c.noise[((size_t)row * stride + base + local) * ld + comp];
+    float z[4];
+    philox_normal4(c.seed, (uint32_t)lay.pocket_gid[b], (uint32_t)(lay.pocket_gid[b] >> 32),
+                   (uint32_t)key, (uint32_t)(local * 4 + (comp >> 2)), z);
+    return z[comp & 3];
+}
+
 // ---- groups of samples that share one latent (kernels_multi.hip, and the multi-pocket scoring chain of kernels_score.hip)
-// one draw per group and op: row ubase + local of the [Nu] unique rows, or Philox keyed by the group's id (Layout::pocket_gid holds it
-// for every member)
+// one draw per group and op: chain_draw(c, lay, g.Nu, g.ubase[b], draw_idx, draw_idx, ...), written out because the multi-pocket scoring kernels
+// (kernels_score.hip) call it and are scheduled differently through the forwarding call
 __device__ __forceinline__ float draw_group(const ChainBuf& c, const Layout& lay, const GroupTab& g, int draw_idx, int b,
                                             int local, int comp, int ld) {
     if (c.noise) return c.noise[((size_t)draw_idx * g.Nu + g.ubase[b] + local) * ld + comp];
     float z[4];
     philox_normal4(c.seed, (uint32_t)lay.pocket_gid[b], (uint32_t)(lay.pocket_gid[b] >> 32),
                    (uint32_t)draw_idx, (uint32_t)(local * 4 + (comp >> 2)), z);
-    return z[comp & 3];
-}
-
-// draw_group with the noise row and the Philox counter given apart (the edit plan's rows are in call order, its counters are not):
-// the multi-pocket edit chains (kernels_multi.hip, kernels_restrain.hip)
-__device__ __forceinline__ float draw_group_at(const ChainBuf& c, const Layout& lay, const GroupTab& g, int row, int key, int b,
-                                               int local, int comp, int ld) {
-    if (c.noise) return c.noise[((size_t)row * g.Nu + g.ubase[b] + local) * ld + comp];
-    float z[4];
-    philox_normal4(c.seed, (uint32_t)lay.pocket_gid[b], (uint32_t)(lay.pocket_gid[b] >> 32),
-                   (uint32_t)key, (uint32_t)(local * 4 + (comp >> 2)), z);
     return z[comp & 3];
 }
 
@@ -60,7 +63,7 @@ __device__ __forceinline__ float combine_eps(const Layout& lay, const GroupTab& 
     return e;
 }
 
-// ---- parts of the op kernels that hold a sample's z and positions in LDS (k_inpaint_step_count, k_multi_edit_step_count)
+// ---- parts of the kernels that hold a sample's z and positions in LDS (cmdgen_step_parts.h, k_multi_score_step)
 // the phar centre of mass of the sample's z (LDS, index order, as index_add_) on threads 0..2 -> s_mean
 __device__ __forceinline__ void phar_mean(const float* s_z, int nl, int ld, int tid, float* s_mean) {
     if (tid < 3) {

@@ -20,20 +20,7 @@
 // so with resamplings = jump_length = 1 (n_steps = K) z_T, every A draw and the decode draw are those of
 // cmdgen_sample_chain's step with the same index, and a sample without fixed rows follows its trajectory bit for bit.
 // Built with -ffp-contract=off; the posterior update and the projection use k_step_count's expressions and sum orders.
-#include "cmdgen_sampler.h"
-
-namespace {
-
-__device__ __forceinline__ float idraw(const ChainBuf& c, const Layout& lay, int row, int key, int b, int local, int node, int comp,
-                                       int ld) {
-    if (c.noise) return c.noise[((size_t)row * lay.Nl + node) * ld + comp];
-    float z[4];
-    philox_normal4(c.seed, (uint32_t)lay.pocket_gid[b], (uint32_t)(lay.pocket_gid[b] >> 32),
-                   (uint32_t)key, (uint32_t)(local * 4 + (comp >> 2)), z);
-    return z[comp & 3];
-}
-
-}  // namespace
+#include "cmdgen_step_parts.h"
 
 // known rows normalised (en_diffusion.py:874-889), the two masks packed as 1 (x held) + 2 (h held), and the pocket offset of
 // z_T's frame (k_chain_init has run: c.xh_pocket is the projected, normalised pocket)
@@ -111,7 +98,7 @@ __global__ __launch_bounds__(256) void k_edit_start(Layout lay, Dims d, ChainBuf
         for (int k = 0; k < ld; ++k) {
             const float x0 = k < 3 ? phar_x[g * 3 + k] / d.norm_x - (k == 0 ? c0 : k == 1 ? c1 : c2) : o[k];
             const float a = alpha * x0;
-            z[k] = a + sigma * idraw(c, lay, 0, 0, b, i, pb + i, k, ld);
+            z[k] = a + sigma * chain_draw(c, lay, lay.Nl, pb, 0, 0, b, i, k, ld);
         }
     }
     if (nfix) atomicAdd(&s_nfix, nfix);
@@ -156,147 +143,14 @@ __global__ __launch_bounds__(256) void k_edit_start(Layout lay, Dims d, ChainBuf
 // ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void k_inpaint_step_count(Layout lay, Dims d, ChainBuf c, InpaintBuf ip, Work w,
                                                              const float* __restrict__ eps) {
-    extern __shared__ float4 s_pos[];               // [max_n] positions of the sample (phar first), then int sdeg[max_n], then z
-    int* sdeg = reinterpret_cast<int*>(s_pos + lay.max_n);
-    float* s_z = reinterpret_cast<float*>(sdeg + lay.max_n);      // [nl * ld]
+    extern __shared__ float4 s_pos[];               // StepWg's layout: [max_n] positions of the sample (phar first), then int sdeg[max_n], then z
     __shared__ float s_mean[3];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6, nt = blockDim.x;
-    const int nl = lay.num_phar[b], np = lay.num_pocket[b], n = nl + np;
-    const int pb = lay.phar_base[b], qb = lay.pocket_base[b];
-    const int ld = 3 + d.P, ldq = 3 + d.R;
-    const int step = c.state->step - 1;             // index of this op (k_readout has counted the evaluation)
-    const float4 cf = c.coef[step];
-    const float4 cf2 = ip.coef2[step];
-    const int4 io = ip.iop[step];
-    const float4 off0 = ip.poff[b];
-    const bool merge = off0.w > 0.f;
-    const bool nan_reset = *w.nan_flag != 0;
-    float* zg = c.z_phar + (size_t)pb * ld;
-    const float* eg = eps + (size_t)pb * ld;
-    const int cnt = nl * ld;
-    for (int idx = tid; idx < cnt; idx += nt) s_z[idx] = zg[idx];
-    for (int i = tid; i < np; i += nt) {
-        const float* q = c.xh_pocket + (size_t)(qb + i) * ldq;
-        s_pos[nl + i] = make_float4(q[0], q[1], q[2], 0.f);
-    }
-    __syncthreads();
-    if (wave == 0) record_com_check(c.check + 2 * (1 + step), s_z, ld, 0, nl, 1.0f, lane);   // z_t, the op's input
-    __syncthreads();
-    // A: the posterior step (k_step_count's expressions)
-    for (int idx = tid; idx < cnt; idx += nt) {
-        const int i = idx / ld, k = idx - i * ld;
-        float e = eg[idx];
-        if (nan_reset && k < 3) e = 0.f;
-        const float mu = s_z[idx] / cf.x - cf.y * e;
-        s_z[idx] = mu + cf.z * idraw(c, lay, io.y, 1 + step, b, i, pb + i, k, ld);
-    }
-    __syncthreads();
-    phar_mean(s_z, nl, ld, tid, s_mean);
-    __syncthreads();
-    float o0, o1, o2;                               // com(P) - com(P0) of the pocket in LDS
-    {
-        const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
-        sub_mean(s_z, s_pos, nl, n, ld, tid, nt, m0, m1, m2);
-        o0 = off0.x - m0; o1 = off0.y - m1; o2 = off0.z - m2;
-    }
-    __syncthreads();
-    // B: the noised known rows moved into the current frame replace the held column groups; then the phar COM projection
-    if (merge) {
-        const int keyB = 2 + ip.n_steps + step;
-        for (int idx = tid; idx < cnt; idx += nt) {
-            const int i = idx / ld, k = idx - i * ld;
-            if (!((int)ip.fix[pb + i] & (k < 3 ? 1 : 2))) continue;
-            float zk = cf2.x * ip.known[(size_t)pb * ld + idx] + cf2.y * idraw(c, lay, io.z, keyB, b, i, pb + i, k, ld);
-            if (k < 3) zk = zk + (k == 0 ? o0 : k == 1 ? o1 : o2);
-            s_z[idx] = zk;
-        }
-        __syncthreads();
-        phar_mean(s_z, nl, ld, tid, s_mean);
-        __syncthreads();
-        const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
-        sub_mean(s_z, s_pos, nl, n, ld, tid, nt, m0, m1, m2);
-        o0 -= m0; o1 -= m1; o2 -= m2;
-        __syncthreads();
-    }
-    // the state after the op (a frame): z and the pocket
-    if (c.z_steps)
-        for (int idx = tid; idx < cnt; idx += nt) c.z_steps[(size_t)step * lay.Nl * ld + (size_t)pb * ld + idx] = s_z[idx];
-    if (c.pocket_steps)
-        for (int i = tid; i < np; i += nt) {
-            const float4 p = s_pos[nl + i];
-            float* o = c.pocket_steps + ((size_t)step * lay.Np + qb + i) * 3;
-            o[0] = p.x; o[1] = p.y; o[2] = p.z;
-        }
-    // C: jump back, z_t' ~ q(z_t' | z_s) (sample_normal_zero_com: draw, then the phar COM projection)
-    if (io.x & 1) {
-        const int keyC = 2 + 2 * ip.n_steps + step;
-        for (int idx = tid; idx < cnt; idx += nt) {
-            const int i = idx / ld, k = idx - i * ld;
-            const float mu = cf2.z * s_z[idx];
-            s_z[idx] = mu + cf2.w * idraw(c, lay, io.w, keyC, b, i, pb + i, k, ld);
-        }
-        __syncthreads();
-        phar_mean(s_z, nl, ld, tid, s_mean);
-        __syncthreads();
-        const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
-        sub_mean(s_z, s_pos, nl, n, ld, tid, nt, m0, m1, m2);
-        o0 -= m0; o1 -= m1; o2 -= m2;
-        __syncthreads();
-    }
-    // the new state, and the inputs of the next evaluation
-    for (int i = tid; i < n; i += nt) {
-        float4 p;
-        if (i < nl) {
-            const float* z = s_z + i * ld;
-            p = make_float4(z[0], z[1], z[2], 0.f);
-            w.X0[pb + i] = p;
-            for (int l = 0; l < d.L; ++l) w.ACC[(size_t)l * lay.Nm + pb + i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            s_pos[i] = p;
-        } else {
-            p = s_pos[i];
-            float* q = c.xh_pocket + (size_t)(qb + i - nl) * ldq;
-            q[0] = p.x; q[1] = p.y; q[2] = p.z;
-            w.XP[qb + i - nl] = p;
-        }
-    }
-    for (int idx = tid; idx < cnt; idx += nt) zg[idx] = s_z[idx];
-    if (tid == 0) ip.poff[b] = make_float4(o0, o1, o2, off0.w);
-    __syncthreads();
-    // ---- pass 1 of the radius graph of the NEXT evaluation (as k_edge_count / k_step_count)
-    for (int i = wave; i < n; i += nwaves) {
-        const float4 pi = s_pos[i];
-        int deg = 0, self = 0;
-        for (int j0 = 0; j0 < n; j0 += 64) {
-            const int j = j0 + lane;
-            bool ok = false;
-            if (j < n) {
-                const float r2 = dist2(pi, s_pos[j]);
-                ok = (d.cutoff2 < 0.f) || (r2 <= d.cutoff2);
-            }
-            const unsigned long long m = __ballot(ok);
-            deg += __popcll(m);
-            if (i >= j0 && i < j0 + 64) self = (int)((m >> (i - j0)) & 1ull);
-        }
-        if (lane == 0) { sdeg[i] = deg | (self << 30); w.degL[pb + qb + i] = deg | (self << 30); }
-    }
-    __syncthreads();
-    if (wave == 0) {
-        int e = 0, eph = 0, ens = 0, ensq = 0;
-        for (int i = lane; i < n; i += 64) {
-            const int dg = sdeg[i] & 0x3fffffff; e += dg;
-            if (i < nl) { eph += dg; ens += dg - ((sdeg[i] >> 30) & 1); }
-            else ensq += dg - ((sdeg[i] >> 30) & 1);
-        }
-        for (int o = 32; o > 0; o >>= 1) {
-            e += __shfl_xor(e, o); eph += __shfl_xor(eph, o); ens += __shfl_xor(ens, o); ensq += __shfl_xor(ensq, o);
-        }
-        if (lane == 0) { w.pocketE[b] = e; w.pocketEph[b] = eph; w.pocketEns[b] = ens; w.pocketEnsQ[b] = ensq; }
-    }
-    if (b == 0 && tid == 0) {
-        if (nan_reset) atomicAdd(&w.counters[4], 1ull);
-        atomicAdd(&w.counters[0], 1ull);                       // evaluations (the one about to run)
-        atomicAdd(&w.counters[3], (unsigned long long)lay.N);  // nodes
-    }
+    const StepWg s = step_wg(lay, d, c, w, s_pos, s_mean);
+    const EditRow op = edit_row(ip, s);
+    const StepRows r = sample_rows(lay, c, s);
+    const float* eg = eps + (size_t)s.pb * s.ld;
+    load_sample(s, c);
+    edit_op(lay, d, c, ip, w, s, r, op, [&](int idx) { return eg[idx]; }, [](float mu, int, int) { return mu; });
 }
 
 void cmdgen_launch_inpaint_prep(const Layout& lay, const Dims& d, const ChainBuf& c, const InpaintBuf& ip, const float* phx,
@@ -310,6 +164,6 @@ void cmdgen_launch_edit_start(const Layout& lay, const Dims& d, const ChainBuf& 
 }
 void cmdgen_launch_inpaint_step_count(const Layout& lay, const Dims& d, const ChainBuf& c, const InpaintBuf& ip, const Work& w,
                                       const float* eps, hipStream_t s) {
-    const size_t shm = (size_t)lay.max_n * (sizeof(float4) + sizeof(int)) + (size_t)lay.max_n * (3 + d.P) * sizeof(float);
+    const size_t shm = plan_step_lds(lay.max_n, d.P);
     hipLaunchKernelGGL(k_inpaint_step_count, dim3(lay.B), dim3(lay.max_n > 128 ? 1024 : 256), shm, s, lay, d, c, ip, w, eps);
 }

@@ -6,7 +6,7 @@
 // the eps rows of all members of its group (nothing writes them in these launches), combines them in member order and draws with
 // the group's key - so the copies stay bit-identical without any synchronisation between workgroups - then translates its own
 // pocket and counts its own edges.  Sums run in index order as in kernels_ddpm.hip; with M = 1 every value is that file's, bit for bit.
-#include "cmdgen_sampler.h"
+#include "cmdgen_step_parts.h"
 
 // subtract the centre of mass of the member's z from its z and its pocket (remove_com of kernels_ddpm.hip)
 __device__ __forceinline__ void remove_com_member(float* zx, int ld, int pb, int nl, float* px, int ldq, int qb, int np, int lane) {
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(64) void k_multi_init(Layout lay, Dims d, ChainBuf 
     for (int idx = lane; idx < nl * ld; idx += 64) {
         const int i = idx / ld, k = idx % ld;
         const float m = k == 0 ? m0 : k == 1 ? m1 : k == 2 ? m2 : 0.f;
-        c.z_phar[(size_t)(pb + i) * ld + k] = m + 1.0f * draw_group(c, lay, g, 0, b, i, k, ld);
+        c.z_phar[(size_t)(pb + i) * ld + k] = m + 1.0f * chain_draw(c, lay, g.Nu, g.ubase[b], 0, 0, b, i, k, ld);
     }
     __syncthreads();
     remove_com_member(c.z_phar, ld, pb, nl, c.xh_pocket, ldq, qb, np, lane);
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(64) void k_multi_final(Layout lay, Dims d, ChainBuf
         float e = combine_eps(lay, g, eps, first, M, ld, idx);
         if (nan_reset && k < 3) e = 0.f;
         const float mu = (1.0f / cf.y) * (c.z_phar[o] - cf.x * e);
-        c.z_phar[o] = mu + cf.z * draw_group(c, lay, g, 1 + K, b, i, k, ld);
+        c.z_phar[o] = mu + cf.z * chain_draw(c, lay, g.Nu, ub, 1 + K, 1 + K, b, i, k, ld);
     }
     __syncthreads();
     remove_com_member(c.z_phar, ld, pb, nl, c.xh_pocket, ldq, qb, np, lane);
@@ -159,107 +159,13 @@ __global__ __launch_bounds__(64) void k_multi_drift_fix(Layout lay, Dims d, Grou
 // ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void k_multi_step_count(Layout lay, Dims d, ChainBuf c, GroupTab g, Work w,
                                                           const float* __restrict__ eps) {
-    extern __shared__ float4 s_pos[];               // [max_n] positions of the sample (phar first), then int sdeg[max_n], then z
-    int* sdeg = reinterpret_cast<int*>(s_pos + lay.max_n);
-    float* s_z = reinterpret_cast<float*>(sdeg + lay.max_n);      // [nl * ld]
+    extern __shared__ float4 s_pos[];               // StepWg's layout: [max_n] positions of the sample (phar first), then int sdeg[max_n], then z
     __shared__ float s_mean[3];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
-    const int nl = lay.num_phar[b], np = lay.num_pocket[b], n = nl + np;
-    const int pb = lay.phar_base[b], qb = lay.pocket_base[b];
-    const int ld = 3 + d.P, ldq = 3 + d.R;
-    const int first = g.first[b], M = g.size[b];
-    const int step = c.state->step - 1;
-    const float4 cf = c.coef[step];
-    const bool nan_reset = *w.nan_flag != 0;
-    float* zg = c.z_phar + (size_t)pb * ld;
-    const int cnt = nl * ld;
-    for (int idx = tid; idx < cnt; idx += blockDim.x) s_z[idx] = zg[idx];
-    for (int i = tid; i < np; i += blockDim.x) {
-        const float* q = c.xh_pocket + (size_t)(qb + i) * ldq;
-        s_pos[nl + i] = make_float4(q[0], q[1], q[2], 0.f);
-    }
-    __syncthreads();
-    if (wave == 0) record_com_check(c.check + 2 * (1 + step), s_z, ld, 0, nl, 1.0f, lane);   // z_t, the step's input
-    __syncthreads();
-    for (int idx = tid; idx < cnt; idx += blockDim.x) {
-        const int i = idx / ld, k = idx - i * ld;
-        float e = combine_eps(lay, g, eps, first, M, ld, idx);
-        if (nan_reset && k < 3) e = 0.f;
-        const float mu = s_z[idx] / cf.x - cf.y * e;
-        s_z[idx] = mu + cf.z * draw_group(c, lay, g, 1 + step, b, i, k, ld);
-    }
-    __syncthreads();
-    if (tid < 3) {                                  // centre of mass of the new z, index order
-        float sum = 0.f;
-        for (int i = 0; i < nl; ++i) sum += s_z[i * ld + tid];
-        s_mean[tid] = sum / fmaxf((float)nl, 1.0f);
-    }
-    __syncthreads();
-    const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
-    for (int i = tid; i < n; i += blockDim.x) {
-        float4 p;
-        if (i < nl) {
-            float* z = s_z + i * ld;
-            z[0] -= m0; z[1] -= m1; z[2] -= m2;
-            p = make_float4(z[0], z[1], z[2], 0.f);
-            w.X0[pb + i] = p;
-            for (int l = 0; l < d.L; ++l) w.ACC[(size_t)l * lay.Nm + pb + i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        } else {
-            p = s_pos[i];
-            p.x -= m0; p.y -= m1; p.z -= m2;
-            float* q = c.xh_pocket + (size_t)(qb + i - nl) * ldq;
-            q[0] = p.x; q[1] = p.y; q[2] = p.z;
-            w.XP[qb + i - nl] = p;
-            if (c.pocket_steps) {
-                float* o = c.pocket_steps + ((size_t)step * lay.Np + qb + i - nl) * 3;
-                o[0] = p.x; o[1] = p.y; o[2] = p.z;
-            }
-        }
-        s_pos[i] = p;
-    }
-    __syncthreads();
-    const bool writer = c.z_steps && b == first;
-    float* zs = writer ? c.z_steps + ((size_t)step * g.Nu + g.ubase[b]) * ld : nullptr;
-    for (int idx = tid; idx < cnt; idx += blockDim.x) {
-        const float v = s_z[idx];
-        zg[idx] = v;
-        if (writer) zs[idx] = v;
-    }
-    // ---- pass 1 of the radius graph of the NEXT evaluation (as k_edge_count)
-    for (int i = wave; i < n; i += nwaves) {
-        const float4 pi = s_pos[i];
-        int deg = 0, self = 0;
-        for (int j0 = 0; j0 < n; j0 += 64) {
-            const int j = j0 + lane;
-            bool ok = false;
-            if (j < n) {
-                const float r2 = dist2(pi, s_pos[j]);
-                ok = (d.cutoff2 < 0.f) || (r2 <= d.cutoff2);
-            }
-            const unsigned long long m = __ballot(ok);
-            deg += __popcll(m);
-            if (i >= j0 && i < j0 + 64) self = (int)((m >> (i - j0)) & 1ull);
-        }
-        if (lane == 0) { sdeg[i] = deg | (self << 30); w.degL[pb + qb + i] = deg | (self << 30); }
-    }
-    __syncthreads();
-    if (wave == 0) {
-        int e = 0, eph = 0, ens = 0, ensq = 0;
-        for (int i = lane; i < n; i += 64) {
-            const int dg = sdeg[i] & 0x3fffffff; e += dg;
-            if (i < nl) { eph += dg; ens += dg - ((sdeg[i] >> 30) & 1); }
-            else ensq += dg - ((sdeg[i] >> 30) & 1);
-        }
-        for (int o = 32; o > 0; o >>= 1) {
-            e += __shfl_xor(e, o); eph += __shfl_xor(eph, o); ens += __shfl_xor(ens, o); ensq += __shfl_xor(ensq, o);
-        }
-        if (lane == 0) { w.pocketE[b] = e; w.pocketEph[b] = eph; w.pocketEns[b] = ens; w.pocketEnsQ[b] = ensq; }
-    }
-    if (b == 0 && tid == 0) {
-        if (nan_reset) atomicAdd(&w.counters[4], 1ull);
-        atomicAdd(&w.counters[0], 1ull);                       // evaluations (the one about to run)
-        atomicAdd(&w.counters[3], (unsigned long long)lay.N);  // nodes
-    }
+    const StepWg s = step_wg(lay, d, c, w, s_pos, s_mean);
+    const int first = g.first[s.b], M = g.size[s.b];
+    load_sample(s, c);
+    plain_op(lay, d, c, w, s, group_rows(g, c, s), [&](int idx) { return combine_eps(lay, g, eps, first, M, s.ld, idx); },
+             [](float mu, int, int) { return mu; });
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -336,7 +242,7 @@ __global__ __launch_bounds__(256) void k_multi_edit_start(Layout lay, Dims d, Ch
             const float x0 = k < 3 ? phar_x[u * 3 + k] / d.norm_x - (k == 0 ? c0 : k == 1 ? c1 : c2)
                                    : (phar_onehot[u * d.P + k - 3] - d.bias_h) / d.norm_h;
             const float a = alpha * x0;
-            z[k] = a + sigma * draw_group_at(c, lay, g, 0, 0, b, i, k, ld);
+            z[k] = a + sigma * chain_draw(c, lay, g.Nu, ub, 0, 0, b, i, k, ld);
         }
     }
     for (int i = tid; i < np; i += 256) {
@@ -365,118 +271,14 @@ __global__ __launch_bounds__(256) void k_multi_edit_start(Layout lay, Dims d, Ch
 // z_steps (one copy of the rows per group) is written by the group's first member, pocket_steps by every member.
 __global__ __launch_bounds__(1024) void k_multi_edit_step_count(Layout lay, Dims d, ChainBuf c, GroupTab g, InpaintBuf ip, Work w,
                                                                 const float* __restrict__ eps) {
-    extern __shared__ float4 s_pos[];               // [max_n] positions of the sample (phar first), then int sdeg[max_n], then z
-    int* sdeg = reinterpret_cast<int*>(s_pos + lay.max_n);
-    float* s_z = reinterpret_cast<float*>(sdeg + lay.max_n);      // [nl * ld]
+    extern __shared__ float4 s_pos[];               // StepWg's layout: [max_n] positions of the sample (phar first), then int sdeg[max_n], then z
     __shared__ float s_mean[3];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nt = blockDim.x;
-    const int nl = lay.num_phar[b], np = lay.num_pocket[b], n = nl + np;
-    const int pb = lay.phar_base[b], qb = lay.pocket_base[b];
-    const int ld = 3 + d.P, ldq = 3 + d.R;
-    const int first = g.first[b], M = g.size[b], ub = g.ubase[b];
-    const int step = c.state->step - 1;             // index of this op
-    const float4 cf = c.coef[step];
-    const float4 cf2 = ip.coef2[step];
-    const int4 io = ip.iop[step];
-    const float4 off0 = ip.poff[b];                 // this member's copy of the group's offset
-    const bool merge = off0.w > 0.f;
-    const bool nan_reset = *w.nan_flag != 0;
-    float* zg = c.z_phar + (size_t)pb * ld;
-    const int cnt = nl * ld;
-    for (int idx = tid; idx < cnt; idx += nt) s_z[idx] = zg[idx];
-    for (int i = tid; i < np; i += nt) {
-        const float* q = c.xh_pocket + (size_t)(qb + i) * ldq;
-        s_pos[nl + i] = make_float4(q[0], q[1], q[2], 0.f);
-    }
-    __syncthreads();
-    if (wave == 0) record_com_check(c.check + 2 * (1 + step), s_z, ld, 0, nl, 1.0f, lane);   // z_t, the op's input
-    __syncthreads();
-    // A: the posterior step on eps_bar (k_multi_step_count's expressions)
-    for (int idx = tid; idx < cnt; idx += nt) {
-        const int i = idx / ld, k = idx - i * ld;
-        float e = combine_eps(lay, g, eps, first, M, ld, idx);
-        if (nan_reset && k < 3) e = 0.f;
-        const float mu = s_z[idx] / cf.x - cf.y * e;
-        s_z[idx] = mu + cf.z * draw_group_at(c, lay, g, io.y, 1 + step, b, i, k, ld);
-    }
-    __syncthreads();
-    phar_mean(s_z, nl, ld, tid, s_mean);
-    __syncthreads();
-    float o0, o1, o2;                               // the group's offset in the frame of the pocket in LDS
-    {
-        const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
-        sub_mean(s_z, s_pos, nl, n, ld, tid, nt, m0, m1, m2);
-        o0 = off0.x - m0; o1 = off0.y - m1; o2 = off0.z - m2;
-    }
-    __syncthreads();
-    // B: the noised known rows moved into the current frame replace the held column groups; then the phar COM projection
-    if (merge) {
-        const int keyB = 2 + ip.n_steps + step;
-        for (int idx = tid; idx < cnt; idx += nt) {
-            const int i = idx / ld, k = idx - i * ld;
-            if (!((int)ip.fix[ub + i] & (k < 3 ? 1 : 2))) continue;
-            float zk = cf2.x * ip.known[(size_t)ub * ld + idx] + cf2.y * draw_group_at(c, lay, g, io.z, keyB, b, i, k, ld);
-            if (k < 3) zk = zk + (k == 0 ? o0 : k == 1 ? o1 : o2);
-            s_z[idx] = zk;
-        }
-        __syncthreads();
-        phar_mean(s_z, nl, ld, tid, s_mean);
-        __syncthreads();
-        const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
-        sub_mean(s_z, s_pos, nl, n, ld, tid, nt, m0, m1, m2);
-        o0 -= m0; o1 -= m1; o2 -= m2;
-        __syncthreads();
-    }
-    // the state after the op (a frame): the group's z by its first member, every member's pocket
-    if (c.z_steps && b == first)
-        for (int idx = tid; idx < cnt; idx += nt) c.z_steps[((size_t)step * g.Nu + ub) * ld + idx] = s_z[idx];
-    if (c.pocket_steps)
-        for (int i = tid; i < np; i += nt) {
-            const float4 p = s_pos[nl + i];
-            float* o = c.pocket_steps + ((size_t)step * lay.Np + qb + i) * 3;
-            o[0] = p.x; o[1] = p.y; o[2] = p.z;
-        }
-    // C: jump back, z_t' ~ q(z_t' | z_s) (draw, then the phar COM projection)
-    if (io.x & 1) {
-        const int keyC = 2 + 2 * ip.n_steps + step;
-        for (int idx = tid; idx < cnt; idx += nt) {
-            const int i = idx / ld, k = idx - i * ld;
-            const float mu = cf2.z * s_z[idx];
-            s_z[idx] = mu + cf2.w * draw_group_at(c, lay, g, io.w, keyC, b, i, k, ld);
-        }
-        __syncthreads();
-        phar_mean(s_z, nl, ld, tid, s_mean);
-        __syncthreads();
-        const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
-        sub_mean(s_z, s_pos, nl, n, ld, tid, nt, m0, m1, m2);
-        o0 -= m0; o1 -= m1; o2 -= m2;
-        __syncthreads();
-    }
-    // the new state, and the inputs of the next evaluation
-    for (int i = tid; i < n; i += nt) {
-        float4 p;
-        if (i < nl) {
-            const float* z = s_z + i * ld;
-            p = make_float4(z[0], z[1], z[2], 0.f);
-            w.X0[pb + i] = p;
-            for (int l = 0; l < d.L; ++l) w.ACC[(size_t)l * lay.Nm + pb + i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            s_pos[i] = p;
-        } else {
-            p = s_pos[i];
-            float* q = c.xh_pocket + (size_t)(qb + i - nl) * ldq;
-            q[0] = p.x; q[1] = p.y; q[2] = p.z;
-            w.XP[qb + i - nl] = p;
-        }
-    }
-    for (int idx = tid; idx < cnt; idx += nt) zg[idx] = s_z[idx];
-    if (tid == 0) ip.poff[b] = make_float4(o0, o1, o2, off0.w);
-    __syncthreads();
-    count_next_graph(lay, d, w, s_pos, sdeg, b, nl, n, pb, qb);
-    if (b == 0 && tid == 0) {
-        if (nan_reset) atomicAdd(&w.counters[4], 1ull);
-        atomicAdd(&w.counters[0], 1ull);                       // evaluations (the one about to run)
-        atomicAdd(&w.counters[3], (unsigned long long)lay.N);  // nodes
-    }
+    const StepWg s = step_wg(lay, d, c, w, s_pos, s_mean);
+    const EditRow op = edit_row(ip, s);             // op.off: this member's copy of the group's offset
+    const int first = g.first[s.b], M = g.size[s.b];
+    load_sample(s, c);
+    edit_op(lay, d, c, ip, w, s, group_rows(g, c, s), op, [&](int idx) { return combine_eps(lay, g, eps, first, M, s.ld, idx); },
+            [](float mu, int, int) { return mu; });
 }
 
 void cmdgen_launch_multi_init(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const float* px,
@@ -485,7 +287,7 @@ void cmdgen_launch_multi_init(const Layout& lay, const Dims& d, const ChainBuf& 
 }
 void cmdgen_launch_multi_step_count(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const Work& w,
                                     const float* eps, hipStream_t s) {
-    const size_t shm = (size_t)lay.max_n * (sizeof(float4) + sizeof(int)) + (size_t)lay.max_n * (3 + d.P) * sizeof(float);
+    const size_t shm = plan_step_lds(lay.max_n, d.P);
     hipLaunchKernelGGL(k_multi_step_count, dim3(lay.B), dim3(lay.max_n > 128 ? 1024 : 256), shm, s, lay, d, c, g, w, eps);   // as k_step_count
 }
 void cmdgen_launch_multi_final(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const Work& w,
@@ -504,6 +306,6 @@ void cmdgen_launch_multi_edit_prep(const Layout& lay, const Dims& d, const Chain
 }
 void cmdgen_launch_multi_edit_step_count(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const InpaintBuf& ip,
                                          const Work& w, const float* eps, hipStream_t s) {
-    const size_t shm = (size_t)lay.max_n * (sizeof(float4) + sizeof(int)) + (size_t)lay.max_n * (3 + d.P) * sizeof(float);
+    const size_t shm = plan_step_lds(lay.max_n, d.P);
     hipLaunchKernelGGL(k_multi_edit_step_count, dim3(lay.B), dim3(lay.max_n > 128 ? 1024 : 256), shm, s, lay, d, c, g, ip, w, eps);   // as its parents
 }

@@ -44,26 +44,9 @@
 //
 // The same guidance inside op A of the edit chain (ConditionalDDPM.edit_restrained, cmdgen_restrained_edit_chain): k_restrained_edit_step_count
 // below, whose header settles what a held row means to the terms.
-#include "cmdgen_sampler.h"
+#include "cmdgen_step_parts.h"
 
 namespace {
-
-__device__ __forceinline__ float rdraw(const ChainBuf& c, const Layout& lay, int draw_idx, int b, int local, int node, int comp, int ld) {
-    if (c.noise) return c.noise[((size_t)draw_idx * lay.Nl + node) * ld + comp];
-    float z[4];
-    philox_normal4(c.seed, (uint32_t)lay.pocket_gid[b], (uint32_t)(lay.pocket_gid[b] >> 32),
-                   (uint32_t)draw_idx, (uint32_t)(local * 4 + (comp >> 2)), z);
-    return z[comp & 3];
-}
-
-// a draw of the edit chain's ops: row `row` of injected noise, or Philox with the counter `key` (idraw of kernels_inpaint.hip)
-__device__ __forceinline__ float edraw(const ChainBuf& c, const Layout& lay, int row, int key, int b, int local, int node, int comp, int ld) {
-    if (c.noise) return c.noise[((size_t)row * lay.Nl + node) * ld + comp];
-    float z[4];
-    philox_normal4(c.seed, (uint32_t)lay.pocket_gid[b], (uint32_t)(lay.pocket_gid[b] >> 32),
-                   (uint32_t)key, (uint32_t)(local * 4 + (comp >> 2)), z);
-    return z[comp & 3];
-}
 
 __device__ __forceinline__ float wave_sum(float v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o); return v; }
 __device__ __forceinline__ float wave_max(float v) { for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o)); return v; }
@@ -124,6 +107,60 @@ __device__ __forceinline__ void wave_com(const float4* s_q, int np, int lane, fl
     c0 = wave_sum(a0) / cnt; c1 = wave_sum(a1) / cnt; c2 = wave_sum(a2) / cnt;
 }
 
+// which of steps 1-5 an op runs for the owner (sample or group) of the records r0 .. r1-1: guided - the displacement enters the mean; terms - steps 1-4
+// run at all (for the displacement, or for op_energy alone).  Uniform over the workgroup.
+struct GuideOp { int r0, r1; bool guided, terms; };
+__device__ __forceinline__ GuideOp guide_op(const RestrainBuf& rb, int owner, const float4& cf) {
+    const int r0 = rb.rstart[owner], r1 = rb.rstart[owner + 1];
+    const bool touched = r1 > r0 || rb.clash_r > 0.f;
+    const bool guided = touched && rb.scale > 0.f && cf.w <= rb.guide_below;
+    return GuideOp{r0, r1, guided, touched && (guided || rb.op_energy != nullptr)};
+}
+
+// 1. xhat of a row, one x column, in Angstrom: free - the denoised estimate from z and the network's column e (zero when the NaN guard reset);
+// held (the edit chains) - the row's given position K moved into the current frame
+__device__ __forceinline__ float xhat_free(const Dims& d, const float4& sa, float z, float e, bool nan_reset) {
+    if (nan_reset) e = 0.f;
+    return d.norm_x * (z - sa.x * e) / sa.y;
+}
+__device__ __forceinline__ float xhat_held(const Dims& d, float known, float shift) { return d.norm_x * known + shift; }
+
+// 2. shift, by one wave, from member b's np pocket atoms in LDS -> s_shift
+__device__ __forceinline__ void frame_shift(const Dims& d, const RestrainBuf& rb, int b, const float4* s_q, int np, int lane, float* s_shift) {
+    float c0, c1, c2;
+    wave_com(s_q, np, lane, c0, c1, c2);
+    const float4 pin = rb.pin_com[b];
+    if (lane == 0) { s_shift[0] = d.norm_x * (c0 - pin.x); s_shift[1] = d.norm_x * (c1 - pin.y); s_shift[2] = d.norm_x * (c2 - pin.z); }
+}
+
+// 4. the displacement of a point from its gradient sums -> o[0 .. 2]
+__device__ __forceinline__ void point_shift(const RestrainBuf& rb, const Dims& d, const float4& cf, float gx, float gy, float gz, float* o) {
+    const float sd = d.norm_x * cf.z, var = sd * sd;
+    float dx = -rb.scale * var * gx, dy = -rb.scale * var * gy, dz = -rb.scale * var * gz;
+    const float len = sqrtf(dx * dx + dy * dy + dz * dz);
+    if (len > rb.max_shift) { const float f = rb.max_shift / len; dx *= f; dy *= f; dz *= f; }
+    o[0] = dx; o[1] = dy; o[2] = dz;
+}
+
+// 3. / 4. of a sample whose xhat, pocket (s_q) and shift stand in LDS: a wave per point -> s_d [nl][3], s_e [nl]
+__device__ __forceinline__ void sample_points(const RestrainBuf& rb, const Dims& d, const float4& cf, const GuideOp& go, int nl, int np, const float* s_xh,
+                                              const float4* s_q, const float* s_shift, float* s_d, float* s_e) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    const float sx = s_shift[0], sy = s_shift[1], sz = s_shift[2];
+    for (int i = wave; i < nl; i += nwaves) {
+        const PointTerm t = point_terms(rb, go.r0, go.r1, i, np, s_xh, s_q, d.norm_x, sx, sy, sz, lane);
+        if (lane == 0) { point_shift(rb, d, cf, t.gx, t.gy, t.gz, s_d + 3 * i); s_e[i] = t.e; }
+    }
+    __syncthreads();
+}
+
+// E at xhat of this op: the points' shares s_e[0 .. nl-1] in index order (one thread)
+__device__ __forceinline__ void store_op_energy(const RestrainBuf& rb, size_t slot, const float* s_e, int nl) {
+    float e = 0.f;
+    for (int i = 0; i < nl; ++i) e += s_e[i];
+    rb.op_energy[slot] = e;
+}
+
 }  // namespace
 
 // com(P_in.x / n_x) per sample, index order (scatter_mean of the normalised input pocket)
@@ -162,10 +199,7 @@ __global__ __launch_bounds__(1024) void k_restrained_step_count(Layout lay, Dims
     const int step = c.state->step - 1;
     const float4 cf = c.coef[step];
     const float4 sa = rb.sa[step];
-    const int r0 = rb.rstart[b], r1 = rb.rstart[b + 1];
-    const bool touched = r1 > r0 || rb.clash_r > 0.f;
-    const bool guided = touched && rb.scale > 0.f && cf.w <= rb.guide_below;
-    const bool terms = touched && (guided || rb.op_energy != nullptr);
+    const GuideOp go = guide_op(rb, b, cf);
     float* zg = c.z_phar + (size_t)pb * ld;
     const float* eg = eps + (size_t)pb * ld;
     const int cnt = nl * ld;
@@ -209,37 +243,18 @@ __global__ __launch_bounds__(1024) void k_restrained_step_count(Layout lay, Dims
     if (wave == 0) record_com_check(c.check + 2 * (1 + step), s_z, ld, 0, nl, 1.0f, lane);   // z_t, the step's input
     __syncthreads();
     // ---- the guidance (steps 1-4): uniform over the workgroup
-    if (terms) {
+    if (go.terms) {
         for (int idx = tid; idx < 3 * nl; idx += nt) {          // 1. xhat
             const int i = idx / 3, k = idx - 3 * i;
             float e;
             if constexpr (own_vel) e = s_vel[idx]; else e = eg[i * ld + k];
-            if (nan_reset) e = 0.f;
-            s_xh[idx] = d.norm_x * (s_z[i * ld + k] - sa.x * e) / sa.y;
+            s_xh[idx] = xhat_free(d, sa, s_z[i * ld + k], e, nan_reset);
         }
-        if (wave == nwaves - 1) {                               // 2. shift
-            float c0, c1, c2;
-            wave_com(s_pos + nl, np, lane, c0, c1, c2);
-            const float4 pin = rb.pin_com[b];
-            if (lane == 0) { s_shift[0] = d.norm_x * (c0 - pin.x); s_shift[1] = d.norm_x * (c1 - pin.y); s_shift[2] = d.norm_x * (c2 - pin.z); }
-        }
+        if (wave == nwaves - 1) frame_shift(d, rb, b, s_pos + nl, np, lane, s_shift);     // 2. shift
         __syncthreads();
-        const float sx = s_shift[0], sy = s_shift[1], sz = s_shift[2];
-        const float sd = d.norm_x * cf.z, var = sd * sd;
-        for (int i = wave; i < nl; i += nwaves) {               // 3. / 4. a wave per point
-            const PointTerm t = point_terms(rb, r0, r1, i, np, s_xh, s_pos + nl, d.norm_x, sx, sy, sz, lane);
-            float dx = -rb.scale * var * t.gx, dy = -rb.scale * var * t.gy, dz = -rb.scale * var * t.gz;
-            const float len = sqrtf(dx * dx + dy * dy + dz * dz);
-            if (len > rb.max_shift) { const float f = rb.max_shift / len; dx *= f; dy *= f; dz *= f; }
-            if (lane == 0) { s_d[3 * i] = dx; s_d[3 * i + 1] = dy; s_d[3 * i + 2] = dz; s_e[i] = t.e; }
-        }
-        __syncthreads();
+        sample_points(rb, d, cf, go, nl, np, s_xh, s_pos + nl, s_shift, s_d, s_e);      // 3. / 4.
     }
-    if (rb.op_energy && tid == 0) {
-        float e = 0.f;
-        if (terms) for (int i = 0; i < nl; ++i) e += s_e[i];    // index order
-        rb.op_energy[(size_t)step * lay.B + b] = e;
-    }
+    if (rb.op_energy && tid == 0) store_op_energy(rb, (size_t)step * lay.B + b, s_e, go.terms ? nl : 0);
     // ---- 5. the posterior mean and the draw (k_step_count's expressions)
     for (int idx = tid; idx < cnt; idx += nt) {
         const int i = idx / ld, k = idx - i * ld;
@@ -247,8 +262,8 @@ __global__ __launch_bounds__(1024) void k_restrained_step_count(Layout lay, Dims
         if constexpr (own_vel) { if (k < 3) e = s_vel[3 * i + k]; }
         if (nan_reset && k < 3) e = 0.f;
         float mu = s_z[idx] / cf.x - cf.y * e;
-        if (guided && k < 3) mu = mu + s_d[3 * i + k] / d.norm_x;
-        s_z[idx] = mu + cf.z * rdraw(c, lay, 1 + step, b, i, pb + i, k, ld);
+        if (go.guided && k < 3) mu = mu + s_d[3 * i + k] / d.norm_x;
+        s_z[idx] = mu + cf.z * chain_draw(c, lay, lay.Nl, pb, 1 + step, 1 + step, b, i, k, ld);
     }
     __syncthreads();
     phar_mean(s_z, nl, ld, tid, s_mean);
@@ -294,47 +309,78 @@ __global__ __launch_bounds__(1024) void k_restrained_step_count(Layout lay, Dims
 // ------------------------------------------------------------------------------------------------------------
 // k_restrain_energy: E and the largest violation of the chain's OUTPUT (after the decode and the drift fix), per sample: the terms of
 // step 3 on xh_phar_out / xh_pocket_out (Angstrom), shift = com(xh_pocket_out.x) - n_x * com(P_in.x / n_x).  256 threads per sample.
+// k_multi_restrain_energy: the same for a group: the terms of step 3 on the group's returned rows (xh_phar_out, [Nu] rows) against every member's
+// returned pocket, shift = com(xh_pocket_out.x of the first member) - n_x * com(P_first,in.x / n_x).  One workgroup of 256 threads per group.
+// One body: the owner's records rstart[owner] .. , its nl rows from row0 of xh_phar_out, the returned pockets of members first .. first + M - 1 (a
+// sample is its own only member), a member's sums added in member order as k_multi_guide adds them.
+// LDS: [max_n] pocket atoms of the member at hand, then xhat [max_n][3], e [max_n], v [max_n].
 // ------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_restrain_energy(Layout lay, Dims d, RestrainBuf rb, const float* __restrict__ xh_phar_out,
-                                                         const float* __restrict__ xh_pocket_out, float* __restrict__ energy_out) {
-    extern __shared__ float4 s_q[];                 // [max_n] pocket atoms, then xhat [max_n][3], e [max_n], v [max_n]
+__device__ __forceinline__ void restrain_energy_body(const Layout& lay, const Dims& d, const RestrainBuf& rb, const float* __restrict__ xh_phar_out,
+                                                     const float* __restrict__ xh_pocket_out, float* __restrict__ energy_out, int owner, int first,
+                                                     int M, int row0, float4* s_q, float* s_shift) {
     float* s_xh = reinterpret_cast<float*>(s_q + lay.max_n);
     float* s_e = s_xh + (size_t)lay.max_n * 3;
     float* s_v = s_e + lay.max_n;
-    __shared__ float s_shift[3];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6, nt = blockDim.x;
-    const int nl = lay.num_phar[b], np = lay.num_pocket[b];
-    const int pb = lay.phar_base[b], qb = lay.pocket_base[b];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6, nt = blockDim.x;
+    const int nl = lay.num_phar[first];
     const int ld = 3 + d.P, ldq = 3 + d.R;
-    const int r0 = rb.rstart[b], r1 = rb.rstart[b + 1];
-    if (!(r1 > r0 || rb.clash_r > 0.f)) {           // no restraint touches the sample
-        if (tid == 0) { energy_out[2 * b] = 0.f; energy_out[2 * b + 1] = 0.f; }
+    const int r0 = rb.rstart[owner], r1 = rb.rstart[owner + 1];
+    if (!(r1 > r0 || rb.clash_r > 0.f)) {           // no restraint touches the sample or group
+        if (tid == 0) { energy_out[2 * owner] = 0.f; energy_out[2 * owner + 1] = 0.f; }
         return;
     }
-    for (int idx = tid; idx < 3 * nl; idx += nt) { const int i = idx / 3, k = idx - 3 * i; s_xh[idx] = xh_phar_out[(size_t)(pb + i) * ld + k]; }
-    for (int i = tid; i < np; i += nt) {
-        const float* q = xh_pocket_out + (size_t)(qb + i) * ldq;
-        s_q[i] = make_float4(q[0], q[1], q[2], 0.f);
-    }
-    __syncthreads();
-    if (wave == 0) {
-        float c0, c1, c2;
-        wave_com(s_q, np, lane, c0, c1, c2);
-        const float4 pin = rb.pin_com[b];
-        if (lane == 0) { s_shift[0] = c0 - d.norm_x * pin.x; s_shift[1] = c1 - d.norm_x * pin.y; s_shift[2] = c2 - d.norm_x * pin.z; }
-    }
-    __syncthreads();
-    const float sx = s_shift[0], sy = s_shift[1], sz = s_shift[2];
-    for (int i = wave; i < nl; i += nwaves) {
-        const PointTerm t = point_terms(rb, r0, r1, i, np, s_xh, s_q, 1.0f, sx, sy, sz, lane);
-        if (lane == 0) { s_e[i] = t.e; s_v[i] = t.v; }
+    const int Mq = rb.clash_r > 0.f ? M : 1;        // without the clash term only the first member's pocket is read (the shift)
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    for (int m = 0; m < Mq; ++m) {
+        const int b = first + m, np = lay.num_pocket[b], qb = lay.pocket_base[b];
+        if (m > 0) __syncthreads();
+        if (m == 0)
+            for (int idx = tid; idx < 3 * nl; idx += nt) { const int i = idx / 3, k = idx - 3 * i; s_xh[idx] = xh_phar_out[(size_t)(row0 + i) * ld + k]; }
+        for (int i = tid; i < np; i += nt) {
+            const float* q = xh_pocket_out + (size_t)(qb + i) * ldq;
+            s_q[i] = make_float4(q[0], q[1], q[2], 0.f);
+        }
+        __syncthreads();
+        if (m == 0) {
+            if (wave == 0) {
+                float c0, c1, c2;
+                wave_com(s_q, np, lane, c0, c1, c2);
+                const float4 pin = rb.pin_com[first];
+                if (lane == 0) { s_shift[0] = c0 - d.norm_x * pin.x; s_shift[1] = c1 - d.norm_x * pin.y; s_shift[2] = c2 - d.norm_x * pin.z; }
+            }
+            __syncthreads();
+            sx = s_shift[0]; sy = s_shift[1]; sz = s_shift[2];
+        }
+        for (int i = wave; i < nl; i += nwaves) {
+            const PointTerm t = point_terms(rb, m == 0 ? r0 : 0, m == 0 ? r1 : 0, i, np, s_xh, s_q, 1.0f, sx, sy, sz, lane);
+            if (lane == 0) {
+                if (m == 0) { s_e[i] = t.e; s_v[i] = t.v; }
+                else { s_e[i] += t.e; s_v[i] = fmaxf(s_v[i], t.v); }
+            }
+        }
     }
     __syncthreads();
     if (tid == 0) {
         float e = 0.f, v = 0.f;
         for (int i = 0; i < nl; ++i) { e += s_e[i]; v = fmaxf(v, s_v[i]); }     // index order
-        energy_out[2 * b] = e; energy_out[2 * b + 1] = v;
+        energy_out[2 * owner] = e; energy_out[2 * owner + 1] = v;
     }
+}
+
+__global__ __launch_bounds__(256) void k_restrain_energy(Layout lay, Dims d, RestrainBuf rb, const float* __restrict__ xh_phar_out,
+                                                         const float* __restrict__ xh_pocket_out, float* __restrict__ energy_out) {
+    extern __shared__ float4 s_q[];
+    __shared__ float s_shift[3];
+    const int b = blockIdx.x;
+    restrain_energy_body(lay, d, rb, xh_phar_out, xh_pocket_out, energy_out, b, b, 1, lay.phar_base[b], s_q, s_shift);
+}
+
+__global__ __launch_bounds__(256) void k_multi_restrain_energy(Layout lay, Dims d, GroupTab g, RestrainBuf rb, const float* __restrict__ xh_phar_out,
+                                                               const float* __restrict__ xh_pocket_out, float* __restrict__ energy_out) {
+    extern __shared__ float4 s_q[];
+    __shared__ float s_shift[3];
+    const int grp = blockIdx.x, first = g.group_first[grp];
+    restrain_energy_body(lay, d, rb, xh_phar_out, xh_pocket_out, energy_out, grp, first, g.size[first], g.ubase[first], s_q, s_shift);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -361,163 +407,35 @@ __global__ __launch_bounds__(256) void k_restrain_energy(Layout lay, Dims d, Res
 // ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void k_restrained_edit_step_count(Layout lay, Dims d, ChainBuf c, InpaintBuf ip, RestrainBuf rb, Work w,
                                                                     const float* __restrict__ eps) {
-    extern __shared__ float4 s_pos[];               // [max_n] positions of the sample (phar first), then int sdeg[max_n], then z, xhat, d, e
-    int* sdeg = reinterpret_cast<int*>(s_pos + lay.max_n);
-    float* s_z = reinterpret_cast<float*>(sdeg + lay.max_n);      // [nl * ld]
-    float* s_xh = s_z + (size_t)lay.max_n * (3 + d.P);            // [nl][3] xhat, Angstrom
+    extern __shared__ float4 s_pos[];               // StepWg's layout ([max_n] positions, phar first, then int sdeg[max_n], then z), then xhat, d, e
+    __shared__ float s_mean[3], s_shift[3];
+    const StepWg s = step_wg(lay, d, c, w, s_pos, s_mean);
+    float* s_xh = s.s_z + (size_t)lay.max_n * (3 + d.P);          // [nl][3] xhat, Angstrom
     float* s_d = s_xh + (size_t)lay.max_n * 3;                    // [nl][3] displacement, Angstrom
     float* s_e = s_d + (size_t)lay.max_n * 3;                     // [nl] the points' shares of E
-    __shared__ float s_mean[3], s_shift[3];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6, nt = blockDim.x;
-    const int nl = lay.num_phar[b], np = lay.num_pocket[b], n = nl + np;
-    const int pb = lay.phar_base[b], qb = lay.pocket_base[b];
-    const int ld = 3 + d.P, ldq = 3 + d.R;
-    const int step = c.state->step - 1;             // index of this op (k_readout has counted the evaluation)
-    const float4 cf = c.coef[step];
-    const float4 cf2 = ip.coef2[step];
-    const int4 io = ip.iop[step];
-    const float4 sa = rb.sa[step];
-    const float4 off0 = ip.poff[b];
-    const bool merge = off0.w > 0.f;
-    const bool nan_reset = *w.nan_flag != 0;
-    const int r0 = rb.rstart[b], r1 = rb.rstart[b + 1];
-    const bool touched = r1 > r0 || rb.clash_r > 0.f;
-    const bool guided = touched && rb.scale > 0.f && cf.w <= rb.guide_below;
-    const bool terms = touched && (guided || rb.op_energy != nullptr);
-    float* zg = c.z_phar + (size_t)pb * ld;
-    const float* eg = eps + (size_t)pb * ld;
-    const int cnt = nl * ld;
-    for (int idx = tid; idx < cnt; idx += nt) s_z[idx] = zg[idx];
-    for (int i = tid; i < np; i += nt) {
-        const float* q = c.xh_pocket + (size_t)(qb + i) * ldq;
-        s_pos[nl + i] = make_float4(q[0], q[1], q[2], 0.f);
-    }
-    __syncthreads();
-    if (wave == 0) record_com_check(c.check + 2 * (1 + step), s_z, ld, 0, nl, 1.0f, lane);   // z_t, the op's input
-    __syncthreads();
+    const int lane = s.tid & 63, wave = s.tid >> 6, nwaves = s.nt >> 6;
+    const EditRow op = edit_row(ip, s);
+    const float4 sa = rb.sa[s.step];
+    const GuideOp go = guide_op(rb, s.b, s.cf);
+    const float* eg = eps + (size_t)s.pb * s.ld;
+    load_sample(s, c);
     // ---- the guidance (steps 1-4): uniform over the workgroup
-    if (terms) {
-        if (wave == nwaves - 1) {                               // 2. shift
-            float c0, c1, c2;
-            wave_com(s_pos + nl, np, lane, c0, c1, c2);
-            const float4 pin = rb.pin_com[b];
-            if (lane == 0) { s_shift[0] = d.norm_x * (c0 - pin.x); s_shift[1] = d.norm_x * (c1 - pin.y); s_shift[2] = d.norm_x * (c2 - pin.z); }
-        }
+    if (go.terms) {
+        if (wave == nwaves - 1) frame_shift(d, rb, s.b, s_pos + s.nl, s.np, lane, s_shift);      // 2. shift
         __syncthreads();                                        // (held rows read the shift)
-        for (int idx = tid; idx < 3 * nl; idx += nt) {          // 1. xhat
+        for (int idx = s.tid; idx < 3 * s.nl; idx += s.nt) {    // 1. xhat
             const int i = idx / 3, k = idx - 3 * i;
-            if ((int)ip.fix[pb + i] & 1) {                      // x held (a marked row: only a sample that merges has one)
-                s_xh[idx] = d.norm_x * ip.known[(size_t)(pb + i) * ld + k] + s_shift[k];
-            } else {
-                float e = eg[i * ld + k];
-                if (nan_reset) e = 0.f;
-                s_xh[idx] = d.norm_x * (s_z[i * ld + k] - sa.x * e) / sa.y;
-            }
+            s_xh[idx] = ((int)ip.fix[s.pb + i] & 1)             // x held (a marked row: only a sample that merges has one)
+                            ? xhat_held(d, ip.known[(size_t)(s.pb + i) * s.ld + k], s_shift[k])
+                            : xhat_free(d, sa, s.s_z[i * s.ld + k], eg[i * s.ld + k], s.nan_reset);
         }
         __syncthreads();
-        const float sx = s_shift[0], sy = s_shift[1], sz = s_shift[2];
-        const float sd = d.norm_x * cf.z, var = sd * sd;
-        for (int i = wave; i < nl; i += nwaves) {               // 3. / 4. a wave per point
-            const PointTerm t = point_terms(rb, r0, r1, i, np, s_xh, s_pos + nl, d.norm_x, sx, sy, sz, lane);
-            float dx = -rb.scale * var * t.gx, dy = -rb.scale * var * t.gy, dz = -rb.scale * var * t.gz;
-            const float len = sqrtf(dx * dx + dy * dy + dz * dz);
-            if (len > rb.max_shift) { const float f = rb.max_shift / len; dx *= f; dy *= f; dz *= f; }
-            if (lane == 0) { s_d[3 * i] = dx; s_d[3 * i + 1] = dy; s_d[3 * i + 2] = dz; s_e[i] = t.e; }
-        }
-        __syncthreads();
+        sample_points(rb, d, s.cf, go, s.nl, s.np, s_xh, s_pos + s.nl, s_shift, s_d, s_e);      // 3. / 4.
     }
-    if (rb.op_energy && tid == 0) {
-        float e = 0.f;
-        if (terms) for (int i = 0; i < nl; ++i) e += s_e[i];    // index order
-        rb.op_energy[(size_t)step * lay.B + b] = e;
-    }
-    // A: the posterior step (k_step_count's expressions) with 5. the displacement on the rows whose x is not held
-    for (int idx = tid; idx < cnt; idx += nt) {
-        const int i = idx / ld, k = idx - i * ld;
-        float e = eg[idx];
-        if (nan_reset && k < 3) e = 0.f;
-        float mu = s_z[idx] / cf.x - cf.y * e;
-        if (guided && k < 3 && !((int)ip.fix[pb + i] & 1)) mu = mu + s_d[3 * i + k] / d.norm_x;
-        s_z[idx] = mu + cf.z * edraw(c, lay, io.y, 1 + step, b, i, pb + i, k, ld);
-    }
-    __syncthreads();
-    phar_mean(s_z, nl, ld, tid, s_mean);
-    __syncthreads();
-    float o0, o1, o2;                               // com(P) - com(P0) of the pocket in LDS
-    {
-        const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
-        sub_mean(s_z, s_pos, nl, n, ld, tid, nt, m0, m1, m2);
-        o0 = off0.x - m0; o1 = off0.y - m1; o2 = off0.z - m2;
-    }
-    __syncthreads();
-    // B: the noised known rows moved into the current frame replace the held column groups; then the phar COM projection
-    if (merge) {
-        const int keyB = 2 + ip.n_steps + step;
-        for (int idx = tid; idx < cnt; idx += nt) {
-            const int i = idx / ld, k = idx - i * ld;
-            if (!((int)ip.fix[pb + i] & (k < 3 ? 1 : 2))) continue;
-            float zk = cf2.x * ip.known[(size_t)pb * ld + idx] + cf2.y * edraw(c, lay, io.z, keyB, b, i, pb + i, k, ld);
-            if (k < 3) zk = zk + (k == 0 ? o0 : k == 1 ? o1 : o2);
-            s_z[idx] = zk;
-        }
-        __syncthreads();
-        phar_mean(s_z, nl, ld, tid, s_mean);
-        __syncthreads();
-        const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
-        sub_mean(s_z, s_pos, nl, n, ld, tid, nt, m0, m1, m2);
-        o0 -= m0; o1 -= m1; o2 -= m2;
-        __syncthreads();
-    }
-    // the state after the op (a frame): z and the pocket
-    if (c.z_steps)
-        for (int idx = tid; idx < cnt; idx += nt) c.z_steps[(size_t)step * lay.Nl * ld + (size_t)pb * ld + idx] = s_z[idx];
-    if (c.pocket_steps)
-        for (int i = tid; i < np; i += nt) {
-            const float4 p = s_pos[nl + i];
-            float* o = c.pocket_steps + ((size_t)step * lay.Np + qb + i) * 3;
-            o[0] = p.x; o[1] = p.y; o[2] = p.z;
-        }
-    // C: jump back, z_t' ~ q(z_t' | z_s) (never guided)
-    if (io.x & 1) {
-        const int keyC = 2 + 2 * ip.n_steps + step;
-        for (int idx = tid; idx < cnt; idx += nt) {
-            const int i = idx / ld, k = idx - i * ld;
-            const float mu = cf2.z * s_z[idx];
-            s_z[idx] = mu + cf2.w * edraw(c, lay, io.w, keyC, b, i, pb + i, k, ld);
-        }
-        __syncthreads();
-        phar_mean(s_z, nl, ld, tid, s_mean);
-        __syncthreads();
-        const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
-        sub_mean(s_z, s_pos, nl, n, ld, tid, nt, m0, m1, m2);
-        o0 -= m0; o1 -= m1; o2 -= m2;
-        __syncthreads();
-    }
-    // the new state, and the inputs of the next evaluation
-    for (int i = tid; i < n; i += nt) {
-        float4 p;
-        if (i < nl) {
-            const float* z = s_z + i * ld;
-            p = make_float4(z[0], z[1], z[2], 0.f);
-            w.X0[pb + i] = p;
-            for (int l = 0; l < d.L; ++l) w.ACC[(size_t)l * lay.Nm + pb + i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            s_pos[i] = p;
-        } else {
-            p = s_pos[i];
-            float* q = c.xh_pocket + (size_t)(qb + i - nl) * ldq;
-            q[0] = p.x; q[1] = p.y; q[2] = p.z;
-            w.XP[qb + i - nl] = p;
-        }
-    }
-    for (int idx = tid; idx < cnt; idx += nt) zg[idx] = s_z[idx];
-    if (tid == 0) ip.poff[b] = make_float4(o0, o1, o2, off0.w);
-    __syncthreads();
-    count_next_graph(lay, d, w, s_pos, sdeg, b, nl, n, pb, qb);
-    if (b == 0 && tid == 0) {
-        if (nan_reset) atomicAdd(&w.counters[4], 1ull);
-        atomicAdd(&w.counters[0], 1ull);                       // evaluations (the one about to run)
-        atomicAdd(&w.counters[3], (unsigned long long)lay.N);  // nodes
-    }
+    if (rb.op_energy && s.tid == 0) store_op_energy(rb, (size_t)s.step * lay.B + s.b, s_e, go.terms ? s.nl : 0);
+    // op A with 5. the displacement on the rows whose x is not held; B, C (never guided) and the rest as k_inpaint_step_count
+    edit_op(lay, d, c, ip, w, s, sample_rows(lay, c, s), op, [&](int idx) { return eg[idx]; },
+            [&](float mu, int i, int k) { return go.guided && !((int)ip.fix[s.pb + i] & 1) ? mu + s_d[3 * i + k] / d.norm_x : mu; });
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -582,11 +500,8 @@ __device__ __forceinline__ void multi_guide_body(const Layout& lay, const Dims& 
     const int step = c.state->step - 1;
     const float4 cf = c.coef[step];
     const float4 sa = rb.sa[step];
-    const int r0 = rb.rstart[grp], r1 = rb.rstart[grp + 1];
-    const bool touched = r1 > r0 || rb.clash_r > 0.f;
-    const bool guided = touched && rb.scale > 0.f && cf.w <= rb.guide_below;
-    const bool terms = touched && (guided || rb.op_energy != nullptr);
-    if (!terms) {                                   // uniform over the workgroup
+    const GuideOp go = guide_op(rb, grp, cf);
+    if (!go.terms) {                                // uniform over the workgroup
         if (rb.op_energy && tid == 0) rb.op_energy[(size_t)step * g.G + grp] = 0.f;
         return;
     }
@@ -605,59 +520,35 @@ __device__ __forceinline__ void multi_guide_body(const Layout& lay, const Dims& 
             if (m == 0)
                 for (int idx = tid; idx < 3 * nl; idx += nt) {    // 1. xhat
                     const int i = idx / 3, k = idx - 3 * i;
-                    float e = combine_eps(lay, g, eps, first, M, ld, i * ld + k);
-                    if (nan_reset) e = 0.f;
-                    s_xh[idx] = d.norm_x * (zg[i * ld + k] - sa.x * e) / sa.y;
+                    s_xh[idx] = xhat_free(d, sa, zg[i * ld + k], combine_eps(lay, g, eps, first, M, ld, i * ld + k), nan_reset);
                 }
         }
         __syncthreads();
         if (m == 0) {
-            if (wave == nwaves - 1) {                             // 2. shift, from the first member
-                float c0, c1, c2;
-                wave_com(s_q, np, lane, c0, c1, c2);
-                const float4 pin = rb.pin_com[first];
-                if (lane == 0) { s_shift[0] = d.norm_x * (c0 - pin.x); s_shift[1] = d.norm_x * (c1 - pin.y); s_shift[2] = d.norm_x * (c2 - pin.z); }
-            }
+            if (wave == nwaves - 1) frame_shift(d, rb, first, s_q, np, lane, s_shift);     // 2. shift, from the first member
             __syncthreads();
             sx = s_shift[0]; sy = s_shift[1]; sz = s_shift[2];
             if constexpr (held) {                                 // 1. xhat, behind the shift: a row whose x is held is its given position in the current frame
                 for (int idx = tid; idx < 3 * nl; idx += nt) {
                     const int i = idx / 3, k = idx - 3 * i;
-                    if ((int)fix[ub + i] & 1) {
-                        s_xh[idx] = d.norm_x * known[(size_t)(ub + i) * ld + k] + s_shift[k];
-                    } else {
-                        float e = combine_eps(lay, g, eps, first, M, ld, i * ld + k);
-                        if (nan_reset) e = 0.f;
-                        s_xh[idx] = d.norm_x * (zg[i * ld + k] - sa.x * e) / sa.y;
-                    }
+                    s_xh[idx] = ((int)fix[ub + i] & 1) ? xhat_held(d, known[(size_t)(ub + i) * ld + k], s_shift[k])
+                                                       : xhat_free(d, sa, zg[i * ld + k], combine_eps(lay, g, eps, first, M, ld, i * ld + k), nan_reset);
                 }
                 __syncthreads();
             }
         }
         for (int i = wave; i < nl; i += nwaves) {                 // 3. a wave per point; the same wave owns the point for every member
-            const PointTerm t = point_terms(rb, m == 0 ? r0 : 0, m == 0 ? r1 : 0, i, np, s_xh, s_q, d.norm_x, sx, sy, sz, lane);
+            const PointTerm t = point_terms(rb, m == 0 ? go.r0 : 0, m == 0 ? go.r1 : 0, i, np, s_xh, s_q, d.norm_x, sx, sy, sz, lane);
             if (lane == 0) {
                 if (m == 0) { s_g[3 * i] = t.gx; s_g[3 * i + 1] = t.gy; s_g[3 * i + 2] = t.gz; s_e[i] = t.e; }
                 else { s_g[3 * i] += t.gx; s_g[3 * i + 1] += t.gy; s_g[3 * i + 2] += t.gz; s_e[i] += t.e; }
             }
         }
     }
-    if (guided && lane == 0) {                                    // 4. by the lane that holds the point's sums
-        const float sd = d.norm_x * cf.z, var = sd * sd;
-        for (int i = wave; i < nl; i += nwaves) {
-            float dx = -rb.scale * var * s_g[3 * i], dy = -rb.scale * var * s_g[3 * i + 1], dz = -rb.scale * var * s_g[3 * i + 2];
-            const float len = sqrtf(dx * dx + dy * dy + dz * dz);
-            if (len > rb.max_shift) { const float f = rb.max_shift / len; dx *= f; dy *= f; dz *= f; }
-            float* o = gd + (size_t)(ub + i) * 3;
-            o[0] = dx; o[1] = dy; o[2] = dz;
-        }
-    }
+    if (go.guided && lane == 0)                                   // 4. by the lane that holds the point's sums
+        for (int i = wave; i < nl; i += nwaves) point_shift(rb, d, cf, s_g[3 * i], s_g[3 * i + 1], s_g[3 * i + 2], gd + (size_t)(ub + i) * 3);
     __syncthreads();
-    if (rb.op_energy && tid == 0) {
-        float e = 0.f;
-        for (int i = 0; i < nl; ++i) e += s_e[i];                 // index order
-        rb.op_energy[(size_t)step * g.G + grp] = e;
-    }
+    if (rb.op_energy && tid == 0) store_op_energy(rb, (size_t)step * g.G + grp, s_e, nl);
 }
 
 __global__ __launch_bounds__(1024) void k_multi_guide(Layout lay, Dims d, ChainBuf c, GroupTab g, RestrainBuf rb, Work w,
@@ -670,134 +561,15 @@ __global__ __launch_bounds__(1024) void k_multi_guide(Layout lay, Dims d, ChainB
 // k_multi_step_count (kernels_multi.hip: the same LDS layout, sums and count pass) with 5. the group's displacement in the mean
 __global__ __launch_bounds__(1024) void k_multi_restrained_step_count(Layout lay, Dims d, ChainBuf c, GroupTab g, RestrainBuf rb, Work w,
                                                                      const float* __restrict__ eps, const float* __restrict__ gd) {
-    extern __shared__ float4 s_pos[];               // [max_n] positions of the sample (phar first), then int sdeg[max_n], then z
-    int* sdeg = reinterpret_cast<int*>(s_pos + lay.max_n);
-    float* s_z = reinterpret_cast<float*>(sdeg + lay.max_n);      // [nl * ld]
+    extern __shared__ float4 s_pos[];               // StepWg's layout: [max_n] positions of the sample (phar first), then int sdeg[max_n], then z
     __shared__ float s_mean[3];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nt = blockDim.x;
-    const int nl = lay.num_phar[b], np = lay.num_pocket[b], n = nl + np;
-    const int pb = lay.phar_base[b], qb = lay.pocket_base[b];
-    const int ld = 3 + d.P, ldq = 3 + d.R;
-    const int first = g.first[b], M = g.size[b], ub = g.ubase[b];
-    const int step = c.state->step - 1;
-    const float4 cf = c.coef[step];
-    const bool nan_reset = *w.nan_flag != 0;
-    const int grp = group_index(g, first);
-    const bool touched = rb.rstart[grp + 1] > rb.rstart[grp] || rb.clash_r > 0.f;
-    const bool guided = touched && rb.scale > 0.f && cf.w <= rb.guide_below;      // k_multi_guide's, which then wrote the group's d
-    float* zg = c.z_phar + (size_t)pb * ld;
-    const int cnt = nl * ld;
-    for (int idx = tid; idx < cnt; idx += nt) s_z[idx] = zg[idx];
-    for (int i = tid; i < np; i += nt) {
-        const float* q = c.xh_pocket + (size_t)(qb + i) * ldq;
-        s_pos[nl + i] = make_float4(q[0], q[1], q[2], 0.f);
-    }
-    __syncthreads();
-    if (wave == 0) record_com_check(c.check + 2 * (1 + step), s_z, ld, 0, nl, 1.0f, lane);   // z_t, the step's input
-    __syncthreads();
-    for (int idx = tid; idx < cnt; idx += nt) {
-        const int i = idx / ld, k = idx - i * ld;
-        float e = combine_eps(lay, g, eps, first, M, ld, idx);
-        if (nan_reset && k < 3) e = 0.f;
-        float mu = s_z[idx] / cf.x - cf.y * e;
-        if (guided && k < 3) mu = mu + gd[(size_t)(ub + i) * 3 + k] / d.norm_x;
-        s_z[idx] = mu + cf.z * draw_group(c, lay, g, 1 + step, b, i, k, ld);
-    }
-    __syncthreads();
-    phar_mean(s_z, nl, ld, tid, s_mean);
-    __syncthreads();
-    const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
-    for (int i = tid; i < n; i += nt) {
-        float4 p;
-        if (i < nl) {
-            float* z = s_z + i * ld;
-            z[0] -= m0; z[1] -= m1; z[2] -= m2;
-            p = make_float4(z[0], z[1], z[2], 0.f);
-            w.X0[pb + i] = p;
-            for (int l = 0; l < d.L; ++l) w.ACC[(size_t)l * lay.Nm + pb + i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        } else {
-            p = s_pos[i];
-            p.x -= m0; p.y -= m1; p.z -= m2;
-            float* q = c.xh_pocket + (size_t)(qb + i - nl) * ldq;
-            q[0] = p.x; q[1] = p.y; q[2] = p.z;
-            w.XP[qb + i - nl] = p;
-            if (c.pocket_steps) {
-                float* o = c.pocket_steps + ((size_t)step * lay.Np + qb + i - nl) * 3;
-                o[0] = p.x; o[1] = p.y; o[2] = p.z;
-            }
-        }
-        s_pos[i] = p;
-    }
-    __syncthreads();
-    const bool writer = c.z_steps && b == first;
-    float* zs = writer ? c.z_steps + ((size_t)step * g.Nu + ub) * ld : nullptr;
-    for (int idx = tid; idx < cnt; idx += nt) {
-        const float v = s_z[idx];
-        zg[idx] = v;
-        if (writer) zs[idx] = v;
-    }
-    count_next_graph(lay, d, w, s_pos, sdeg, b, nl, n, pb, qb);
-    if (b == 0 && tid == 0) {
-        if (nan_reset) atomicAdd(&w.counters[4], 1ull);
-        atomicAdd(&w.counters[0], 1ull);                       // evaluations (the one about to run)
-        atomicAdd(&w.counters[3], (unsigned long long)lay.N);  // nodes
-    }
-}
-
-// k_restrain_energy for a group: the terms of step 3 on the group's returned rows (xh_phar_out, [Nu] rows) against every member's returned
-// pocket, shift = com(xh_pocket_out.x of the first member) - n_x * com(P_first,in.x / n_x).  One workgroup of 256 threads per group.
-__global__ __launch_bounds__(256) void k_multi_restrain_energy(Layout lay, Dims d, GroupTab g, RestrainBuf rb, const float* __restrict__ xh_phar_out,
-                                                               const float* __restrict__ xh_pocket_out, float* __restrict__ energy_out) {
-    extern __shared__ float4 s_q[];                 // [max_n] pocket atoms of the member at hand, then xhat [max_n][3], e [max_n], v [max_n]
-    float* s_xh = reinterpret_cast<float*>(s_q + lay.max_n);
-    float* s_e = s_xh + (size_t)lay.max_n * 3;
-    float* s_v = s_e + lay.max_n;
-    __shared__ float s_shift[3];
-    const int grp = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6, nt = blockDim.x;
-    const int first = g.group_first[grp], M = g.size[first], ub = g.ubase[first];
-    const int nl = lay.num_phar[first];
-    const int ld = 3 + d.P, ldq = 3 + d.R;
-    const int r0 = rb.rstart[grp], r1 = rb.rstart[grp + 1];
-    if (!(r1 > r0 || rb.clash_r > 0.f)) {           // no restraint touches the group
-        if (tid == 0) { energy_out[2 * grp] = 0.f; energy_out[2 * grp + 1] = 0.f; }
-        return;
-    }
-    const int Mq = rb.clash_r > 0.f ? M : 1;
-    float sx = 0.f, sy = 0.f, sz = 0.f;
-    for (int m = 0; m < Mq; ++m) {
-        const int b = first + m, np = lay.num_pocket[b], qb = lay.pocket_base[b];
-        if (m > 0) __syncthreads();
-        if (m == 0)
-            for (int idx = tid; idx < 3 * nl; idx += nt) { const int i = idx / 3, k = idx - 3 * i; s_xh[idx] = xh_phar_out[(size_t)(ub + i) * ld + k]; }
-        for (int i = tid; i < np; i += nt) {
-            const float* q = xh_pocket_out + (size_t)(qb + i) * ldq;
-            s_q[i] = make_float4(q[0], q[1], q[2], 0.f);
-        }
-        __syncthreads();
-        if (m == 0) {
-            if (wave == 0) {
-                float c0, c1, c2;
-                wave_com(s_q, np, lane, c0, c1, c2);
-                const float4 pin = rb.pin_com[first];
-                if (lane == 0) { s_shift[0] = c0 - d.norm_x * pin.x; s_shift[1] = c1 - d.norm_x * pin.y; s_shift[2] = c2 - d.norm_x * pin.z; }
-            }
-            __syncthreads();
-            sx = s_shift[0]; sy = s_shift[1]; sz = s_shift[2];
-        }
-        for (int i = wave; i < nl; i += nwaves) {
-            const PointTerm t = point_terms(rb, m == 0 ? r0 : 0, m == 0 ? r1 : 0, i, np, s_xh, s_q, 1.0f, sx, sy, sz, lane);
-            if (lane == 0) {
-                if (m == 0) { s_e[i] = t.e; s_v[i] = t.v; }
-                else { s_e[i] += t.e; s_v[i] = fmaxf(s_v[i], t.v); }
-            }
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        float e = 0.f, v = 0.f;
-        for (int i = 0; i < nl; ++i) { e += s_e[i]; v = fmaxf(v, s_v[i]); }     // index order
-        energy_out[2 * grp] = e; energy_out[2 * grp + 1] = v;
-    }
+    const StepWg s = step_wg(lay, d, c, w, s_pos, s_mean);
+    const int first = g.first[s.b], M = g.size[s.b];
+    const StepRows r = group_rows(g, c, s);
+    const bool guided = guide_op(rb, group_index(g, first), s.cf).guided;         // k_multi_guide's, which then wrote the group's d
+    load_sample(s, c);
+    plain_op(lay, d, c, w, s, r, [&](int idx) { return combine_eps(lay, g, eps, first, M, s.ld, idx); },
+             [&](float mu, int i, int k) { return guided ? mu + gd[(size_t)(r.base + i) * 3 + k] / d.norm_x : mu; });
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -848,122 +620,16 @@ __global__ __launch_bounds__(1024) void k_multi_edit_guide(Layout lay, Dims d, C
 __global__ __launch_bounds__(1024) void k_multi_restrained_edit_step_count(Layout lay, Dims d, ChainBuf c, GroupTab g, InpaintBuf ip,
                                                                           RestrainBuf rb, Work w, const float* __restrict__ eps,
                                                                           const float* __restrict__ gd) {
-    extern __shared__ float4 s_pos[];               // [max_n] positions of the sample (phar first), then int sdeg[max_n], then z
-    int* sdeg = reinterpret_cast<int*>(s_pos + lay.max_n);
-    float* s_z = reinterpret_cast<float*>(sdeg + lay.max_n);      // [nl * ld]
+    extern __shared__ float4 s_pos[];               // StepWg's layout: [max_n] positions of the sample (phar first), then int sdeg[max_n], then z
     __shared__ float s_mean[3];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nt = blockDim.x;
-    const int nl = lay.num_phar[b], np = lay.num_pocket[b], n = nl + np;
-    const int pb = lay.phar_base[b], qb = lay.pocket_base[b];
-    const int ld = 3 + d.P, ldq = 3 + d.R;
-    const int first = g.first[b], M = g.size[b], ub = g.ubase[b];
-    const int step = c.state->step - 1;             // index of this op
-    const float4 cf = c.coef[step];
-    const float4 cf2 = ip.coef2[step];
-    const int4 io = ip.iop[step];
-    const float4 off0 = ip.poff[b];                 // this member's copy of the group's offset
-    const bool merge = off0.w > 0.f;
-    const bool nan_reset = *w.nan_flag != 0;
-    const int grp = group_index(g, first);
-    const bool touched = rb.rstart[grp + 1] > rb.rstart[grp] || rb.clash_r > 0.f;
-    const bool guided = touched && rb.scale > 0.f && cf.w <= rb.guide_below;      // k_multi_edit_guide's, which then wrote the group's d
-    float* zg = c.z_phar + (size_t)pb * ld;
-    const int cnt = nl * ld;
-    for (int idx = tid; idx < cnt; idx += nt) s_z[idx] = zg[idx];
-    for (int i = tid; i < np; i += nt) {
-        const float* q = c.xh_pocket + (size_t)(qb + i) * ldq;
-        s_pos[nl + i] = make_float4(q[0], q[1], q[2], 0.f);
-    }
-    __syncthreads();
-    if (wave == 0) record_com_check(c.check + 2 * (1 + step), s_z, ld, 0, nl, 1.0f, lane);   // z_t, the op's input
-    __syncthreads();
-    // A: the posterior step on eps_bar (k_multi_step_count's expressions) with 5. the displacement on the rows whose x is not held
-    for (int idx = tid; idx < cnt; idx += nt) {
-        const int i = idx / ld, k = idx - i * ld;
-        float e = combine_eps(lay, g, eps, first, M, ld, idx);
-        if (nan_reset && k < 3) e = 0.f;
-        float mu = s_z[idx] / cf.x - cf.y * e;
-        if (guided && k < 3 && !((int)ip.fix[ub + i] & 1)) mu = mu + gd[(size_t)(ub + i) * 3 + k] / d.norm_x;
-        s_z[idx] = mu + cf.z * draw_group_at(c, lay, g, io.y, 1 + step, b, i, k, ld);
-    }
-    __syncthreads();
-    phar_mean(s_z, nl, ld, tid, s_mean);
-    __syncthreads();
-    float o0, o1, o2;                               // the group's offset in the frame of the pocket in LDS
-    {
-        const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
-        sub_mean(s_z, s_pos, nl, n, ld, tid, nt, m0, m1, m2);
-        o0 = off0.x - m0; o1 = off0.y - m1; o2 = off0.z - m2;
-    }
-    __syncthreads();
-    // B: the noised known rows moved into the current frame replace the held column groups; then the phar COM projection
-    if (merge) {
-        const int keyB = 2 + ip.n_steps + step;
-        for (int idx = tid; idx < cnt; idx += nt) {
-            const int i = idx / ld, k = idx - i * ld;
-            if (!((int)ip.fix[ub + i] & (k < 3 ? 1 : 2))) continue;
-            float zk = cf2.x * ip.known[(size_t)ub * ld + idx] + cf2.y * draw_group_at(c, lay, g, io.z, keyB, b, i, k, ld);
-            if (k < 3) zk = zk + (k == 0 ? o0 : k == 1 ? o1 : o2);
-            s_z[idx] = zk;
-        }
-        __syncthreads();
-        phar_mean(s_z, nl, ld, tid, s_mean);
-        __syncthreads();
-        const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
-        sub_mean(s_z, s_pos, nl, n, ld, tid, nt, m0, m1, m2);
-        o0 -= m0; o1 -= m1; o2 -= m2;
-        __syncthreads();
-    }
-    // the state after the op (a frame): the group's z by its first member, every member's pocket
-    if (c.z_steps && b == first)
-        for (int idx = tid; idx < cnt; idx += nt) c.z_steps[((size_t)step * g.Nu + ub) * ld + idx] = s_z[idx];
-    if (c.pocket_steps)
-        for (int i = tid; i < np; i += nt) {
-            const float4 p = s_pos[nl + i];
-            float* o = c.pocket_steps + ((size_t)step * lay.Np + qb + i) * 3;
-            o[0] = p.x; o[1] = p.y; o[2] = p.z;
-        }
-    // C: jump back, z_t' ~ q(z_t' | z_s) (never guided)
-    if (io.x & 1) {
-        const int keyC = 2 + 2 * ip.n_steps + step;
-        for (int idx = tid; idx < cnt; idx += nt) {
-            const int i = idx / ld, k = idx - i * ld;
-            const float mu = cf2.z * s_z[idx];
-            s_z[idx] = mu + cf2.w * draw_group_at(c, lay, g, io.w, keyC, b, i, k, ld);
-        }
-        __syncthreads();
-        phar_mean(s_z, nl, ld, tid, s_mean);
-        __syncthreads();
-        const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
-        sub_mean(s_z, s_pos, nl, n, ld, tid, nt, m0, m1, m2);
-        o0 -= m0; o1 -= m1; o2 -= m2;
-        __syncthreads();
-    }
-    // the new state, and the inputs of the next evaluation
-    for (int i = tid; i < n; i += nt) {
-        float4 p;
-        if (i < nl) {
-            const float* z = s_z + i * ld;
-            p = make_float4(z[0], z[1], z[2], 0.f);
-            w.X0[pb + i] = p;
-            for (int l = 0; l < d.L; ++l) w.ACC[(size_t)l * lay.Nm + pb + i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            s_pos[i] = p;
-        } else {
-            p = s_pos[i];
-            float* q = c.xh_pocket + (size_t)(qb + i - nl) * ldq;
-            q[0] = p.x; q[1] = p.y; q[2] = p.z;
-            w.XP[qb + i - nl] = p;
-        }
-    }
-    for (int idx = tid; idx < cnt; idx += nt) zg[idx] = s_z[idx];
-    if (tid == 0) ip.poff[b] = make_float4(o0, o1, o2, off0.w);
-    __syncthreads();
-    count_next_graph(lay, d, w, s_pos, sdeg, b, nl, n, pb, qb);
-    if (b == 0 && tid == 0) {
-        if (nan_reset) atomicAdd(&w.counters[4], 1ull);
-        atomicAdd(&w.counters[0], 1ull);                       // evaluations (the one about to run)
-        atomicAdd(&w.counters[3], (unsigned long long)lay.N);  // nodes
-    }
+    const StepWg s = step_wg(lay, d, c, w, s_pos, s_mean);
+    const EditRow op = edit_row(ip, s);             // op.off: this member's copy of the group's offset
+    const int first = g.first[s.b], M = g.size[s.b];
+    const StepRows r = group_rows(g, c, s);
+    const bool guided = guide_op(rb, group_index(g, first), s.cf).guided;         // k_multi_edit_guide's, which then wrote the group's d
+    load_sample(s, c);
+    edit_op(lay, d, c, ip, w, s, r, op, [&](int idx) { return combine_eps(lay, g, eps, first, M, s.ld, idx); },
+            [&](float mu, int i, int k) { return guided && !((int)ip.fix[r.base + i] & 1) ? mu + gd[(size_t)(r.base + i) * 3 + k] / d.norm_x : mu; });
 }
 
 void cmdgen_launch_restrain_prep(const Layout& lay, const Dims& d, const RestrainBuf& rb, const float* px, hipStream_t s) {
@@ -990,7 +656,7 @@ void cmdgen_launch_multi_restrained_step(const Layout& lay, const Dims& d, const
                                          const Work& w, const float* eps, float* gd, hipStream_t s) {
     const dim3 block(lay.max_n > 128 ? 1024 : 256);             // as k_multi_step_count
     const size_t shm_guide = (size_t)lay.max_n * (sizeof(float4) + 7 * sizeof(float));
-    const size_t shm_step = (size_t)lay.max_n * (sizeof(float4) + sizeof(int)) + (size_t)lay.max_n * (3 + d.P) * sizeof(float);
+    const size_t shm_step = plan_step_lds(lay.max_n, d.P);
     hipLaunchKernelGGL(k_multi_guide, dim3(g.G), block, shm_guide, s, lay, d, c, g, rb, w, eps, gd);
     hipLaunchKernelGGL(k_multi_restrained_step_count, dim3(lay.B), block, shm_step, s, lay, d, c, g, rb, w, eps, (const float*)gd);
 }
@@ -998,7 +664,7 @@ void cmdgen_launch_multi_restrained_edit_step(const Layout& lay, const Dims& d, 
                                               const RestrainBuf& rb, const Work& w, const float* eps, float* gd, hipStream_t s) {
     const dim3 block(lay.max_n > 128 ? 1024 : 256);             // as k_multi_guide and k_multi_edit_step_count
     const size_t shm_guide = (size_t)lay.max_n * (sizeof(float4) + 7 * sizeof(float));
-    const size_t shm_step = (size_t)lay.max_n * (sizeof(float4) + sizeof(int)) + (size_t)lay.max_n * (3 + d.P) * sizeof(float);
+    const size_t shm_step = plan_step_lds(lay.max_n, d.P);
     hipLaunchKernelGGL(k_multi_edit_guide, dim3(g.G), block, shm_guide, s, lay, d, c, g, rb, w, eps, gd, ip.known, (const float*)ip.fix);
     hipLaunchKernelGGL(k_multi_restrained_edit_step_count, dim3(lay.B), block, shm_step, s, lay, d, c, g, ip, rb, w, eps, (const float*)gd);
 }
