@@ -65,7 +65,7 @@ static void drop_chain_graphs(cmdgen_handle* h) {
 
 // every kind's buffers: the next chain of each kind prepares its slot again
 static void release_chains(cmdgen_handle* h) {
-    for (ChainSlot& k : h->chains) { free_pool(k.allocs); k.n_steps = -1; k.tables.clear(); }
+    for (ChainSlot& k : h->chains) { free_pool(k.allocs); k.n_steps = -1; k.tables = TableBlock{}; }
 }
 
 extern "C" void cmdgen_destroy(cmdgen_handle* h) {
@@ -702,9 +702,11 @@ static std::vector<float> step_table(const cmdgen_handle* h, int K) {
 }
 
 // ---------------------------------------------------------------------------------
-// the chains: what the entries of all eleven kinds share.  A kind's state lives in its slot (h->chains[kind]); its ChainAlloc composes
-// the parts it uses (alloc_chain_buf, alloc_inpaint_part, point_group_tab, alloc_restrain_part, alloc_score_part); its entry reads top to
-// bottom: checks, tables, Chain::open, its init launches, Chain::start, Chain::steps with its step launch, its final launches, Chain::close.
+// the chains: what the entries of all eleven kinds share.  A kind's state lives in its slot (h->chains[kind]); its entry lays the slot's
+// table block out with the appenders below (TableBlock, cmdgen_host.h: each records where its section begins) and its ChainAlloc composes
+// the parts (alloc_chain_buf, alloc_inpaint_part, point_group_tab, alloc_restrain_part, alloc_score_part) at those offsets - the eight
+// sampling kinds share one, alloc_sampling.  An entry reads top to bottom: checks, table block, Chain::open, its init launches,
+// Chain::start, Chain::steps with its step launch, its final launches, Chain::close.
 // ---------------------------------------------------------------------------------
 static int check_timesteps(cmdgen_handle* h, int K) {
     if (K < 1 || K > h->cfg.timesteps) return fail(h, CMDGEN_EINVAL, "timesteps=%d must be in [1, %d]", K, h->cfg.timesteps);
@@ -724,38 +726,45 @@ static int check_draws(cmdgen_handle* h, const float* noise, int64_t n_draws, in
     return 0;
 }
 
-// a plan's tables as one upload: coef | coef2 | iop bits
-static std::vector<float> plan_tables(const std::vector<float>& coef, const std::vector<float>& coef2, const std::vector<int>& iop) {
-    std::vector<float> t(coef);
-    t.insert(t.end(), coef2.begin(), coef2.end());
-    t.resize(t.size() + iop.size());
-    memcpy(t.data() + coef.size() + coef2.size(), iop.data(), iop.size() * sizeof(int));
+// a table block that begins with the posterior (scoring: level) rows `coef`.  They are never empty (a chain has at least one op or level and
+// the decode / prior row), so every later section begins at an offset > 0 and 0 can stand for "the block has none" (alloc_sampling)
+static TableBlock posterior_rows(std::vector<float> coef) {
+    TableBlock t;
+    t.f = std::move(coef);
+    return t;
+}
+// ... with a plan's edit tables behind them: coef | coef2 | iop bits
+static TableBlock plan_tables(const std::vector<float>& coef, const std::vector<float>& coef2, const std::vector<int>& iop) {
+    TableBlock t = posterior_rows(coef);
+    t.edit = t.f.size();
+    t.f.insert(t.f.end(), coef2.begin(), coef2.end());
+    t.f.resize(t.f.size() + iop.size());
+    memcpy(t.f.data() + coef.size() + coef2.size(), iop.data(), iop.size() * sizeof(int));
     return t;
 }
 
-// the kind's own buffers in its slot's pool, pointed at the uploaded tables
-typedef int (*ChainAlloc)(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps);
+// the kind's own buffers in its slot's pool, pointed at the uploaded block `dev` by the offsets `t` recorded
+typedef int (*ChainAlloc)(cmdgen_handle* h, ChainSlot& k, const TableBlock& t, const float* dev, int n_steps);
 
-// A slot that holds exactly `tables` for the current layout is used as it is, with its captured graph.  Otherwise it is
-// prepared again: the tables, the check buffer, the loop state and the CoG slot, then the kind's buffers (alloc).
-static int prepare_slot(cmdgen_handle* h, ChainSlot& k, std::vector<float>& tables, int n_steps, ChainAlloc alloc) {
-    if (k.n_steps >= 0 && k.tables.size() == tables.size() &&
-        memcmp(k.tables.data(), tables.data(), tables.size() * sizeof(float)) == 0)
+// A slot that holds exactly `tables`, bytes and offsets, for the current layout is used as it is, with its captured graph.  Otherwise it
+// is prepared again: the tables, the check buffer, the loop state and the CoG slot, then the kind's buffers (alloc).
+static int prepare_slot(cmdgen_handle* h, ChainSlot& k, TableBlock& tables, int n_steps, ChainAlloc alloc) {
+    if (k.n_steps >= 0 && k.tables.same(tables))
         return 0;
     hipDeviceSynchronize();
     if (k.graph) { hipGraphExecDestroy(k.graph); k.graph = nullptr; }
     free_pool(k.allocs);
     k.n_steps = -1;
     void* p; int rc;
-    rc = dev_alloc(h, k.allocs, &p, tables.size() * sizeof(float), false); if (rc) return rc;
-    HIPCHK(h, hipMemcpy(p, tables.data(), tables.size() * sizeof(float), hipMemcpyHostToDevice));
+    rc = dev_alloc(h, k.allocs, &p, tables.f.size() * sizeof(float), false); if (rc) return rc;
+    HIPCHK(h, hipMemcpy(p, tables.f.data(), tables.f.size() * sizeof(float), hipMemcpyHostToDevice));
     const float* tab = (const float*)p;
     rc = dev_alloc(h, k.allocs, &p, (size_t)(n_steps + 3) * 2 * sizeof(unsigned int), true); if (rc) return rc; k.check = (unsigned int*)p;
     rc = dev_alloc(h, k.allocs, &p, sizeof(ChainState), true); if (rc) return rc; k.state = (ChainState*)p;
     rc = dev_alloc(h, k.allocs, &p, 4 * sizeof(unsigned int), true); if (rc) return rc; k.cog = (unsigned int*)p;
-    rc = alloc(h, k, tab, n_steps); if (rc) return rc;
+    rc = alloc(h, k, tables, tab, n_steps); if (rc) return rc;
     k.n_steps = n_steps;
-    k.tables.swap(tables);
+    std::swap(k.tables, tables);
     return 0;
 }
 
@@ -796,7 +805,7 @@ static int own_stream(cmdgen_handle* h) {
 // The start of a chain of `kind` with n_steps denoising steps: the stream it runs on (*s; with use_graph on the legacy default
 // stream, the handle's own stream ordered after the caller's pending work), its slot prepared for `tables`, the per-call reset
 // (pocket ids of the Philox draws, loop state, check buffer, CoG slot) and the launch description of its evaluations (*a).
-static int begin_chain(cmdgen_handle* h, ChainKind kind, std::vector<float>& tables, int n_steps, ChainAlloc alloc,
+static int begin_chain(cmdgen_handle* h, ChainKind kind, TableBlock& tables, int n_steps, ChainAlloc alloc,
                        const int64_t* pocket_ids_host, bool use_graph, hipStream_t caller, hipStream_t* s, EvalLaunch* a) {
     h->last_chain = kind;
     hipSetDevice(h->device);
@@ -912,6 +921,22 @@ static int alloc_score_part(cmdgen_handle* h, ChainSlot& k) {
     const int rc = slot_alloc(h, k, k.score.xh0, (size_t)h->lay.Nl * (3 + h->dims.P)); if (rc) return rc;
     return slot_alloc(h, k, k.score.pocket0, (size_t)h->lay.Np * 3);
 }
+// the multi-pocket kinds' GroupTab: the group tables append_group_tables packed at `g` in the table block (the counts G, Nu come per call: group_tab)
+static void point_group_tab(GroupTab& gt, const float* g, size_t B) {
+    gt.first = (const int*)g; gt.size = (const int*)(g + B); gt.ubase = (const int*)(g + 2 * B);
+    gt.weight = g + 3 * B; gt.group_first = (const int*)(g + 4 * B);
+}
+// The ChainAlloc of the eight sampling kinds ({from the prior, edit} x {one pocket, groups} x {unguided, restrained}): the ChainBuf, then
+// the part of every section the entry appended to its table block; the restrained multi-pocket kinds also get the displacement buffer
+// their guide launch hands to their step launch.
+static int alloc_sampling(cmdgen_handle* h, ChainSlot& k, const TableBlock& t, const float* dev, int n_steps) {
+    int rc = alloc_chain_buf(h, k, dev); if (rc) return rc;
+    if (t.edit) { rc = alloc_inpaint_part(h, k, dev + t.edit, n_steps); if (rc) return rc; }
+    if (t.groups) point_group_tab(k.groups, dev + t.groups, (size_t)h->lay.B);
+    if (t.guide) { rc = alloc_restrain_part(h, k, dev + t.guide, t.guide_rows, t.owners); if (rc) return rc; }
+    if (t.groups && t.guide) return slot_alloc(h, k, k.guide_d, (size_t)h->lay.Nl * 3);    // (Nl bounds the unique rows of any grouping)
+    return 0;
+}
 
 // One chain call between begin_chain and end_chain: the stream it runs on, its slot, the launch description of its evaluations and, for
 // the ten conditional kinds, the slot's ChainBuf completed with the call's pointers.
@@ -923,7 +948,7 @@ struct Chain {
     EvalLaunch a, a2;                // evaluation 0 | the evaluations behind a step kernel, which ran pass 1 of the radius graph
     ChainBuf c{};
 
-    int open(cmdgen_handle* h_, ChainKind kind, std::vector<float>& tables, int n_steps, ChainAlloc alloc, const int64_t* ids_host,
+    int open(cmdgen_handle* h_, ChainKind kind, TableBlock& tables, int n_steps, ChainAlloc alloc, const int64_t* ids_host,
              const float* noise, unsigned long long seed, float* z_steps, float* pocket_steps, bool graph, cmdgen_stream stream) {
         h = h_; k = &h->chains[kind]; caller = (hipStream_t)stream; use_graph = graph;
         const int rc = begin_chain(h, kind, tables, n_steps, alloc, ids_host, use_graph, caller, &s, &a); if (rc) return rc;
@@ -951,8 +976,6 @@ struct Chain {
     int close() { return end_chain(h, caller, s); }
 };
 
-static int alloc_plain(cmdgen_handle* h, ChainSlot& k, const float* tables, int) { return alloc_chain_buf(h, k, tables); }
-
 extern "C" int cmdgen_sample_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
                                    int32_t timesteps, const float* noise, uint64_t seed,
                                    const int64_t* pocket_ids_host, float* xh_phar_out, float* xh_pocket_out,
@@ -962,9 +985,9 @@ extern "C" int cmdgen_sample_chain(cmdgen_handle* h, const float* pocket_x, cons
     const int K = timesteps;
     rc = check_timesteps(h, K); if (rc) return rc;
     if (h->dims.joint) return fail(h, CMDGEN_ESTATE, "this handle is the joint model (update_pocket_coords=1): use cmdgen_joint_chain");
-    std::vector<float> tables = step_table(h, K);
+    TableBlock tables = posterior_rows(step_table(h, K));
     Chain ch;
-    rc = ch.open(h, CHAIN_PLAIN, tables, K, alloc_plain, pocket_ids_host, noise, seed, z_steps_out, pocket_steps_out, use_graph, stream); if (rc) return rc;
+    rc = ch.open(h, CHAIN_PLAIN, tables, K, alloc_sampling, pocket_ids_host, noise, seed, z_steps_out, pocket_steps_out, use_graph, stream); if (rc) return rc;
     const Dims& d = h->dims;
     const ChainBuf& c = ch.c;
     cmdgen_launch_chain_init(h->lay, d, c, pocket_x, pocket_onehot, ch.s);
@@ -1081,13 +1104,16 @@ static int check_restraints(cmdgen_handle* h, const cmdgen_restraint* restraints
     return check_restraint_list(h, own, restraints_host, n_restraints, clash_radius, clash_k, scale, max_shift, guide_below, step_lds, rstart, rec);
 }
 
-// The guidance tail of a table block: one guide row (sigma_t, alpha_t, 0, 0) per op, s_of[i] the level op i goes to (t = s + 1), then `spare`
-// unused rows | par: r_c, k_c, scale, max_shift, guide_below, then 0, 0, 0 | rstart | rec.  alloc_restrain_part points a RestrainBuf at it.
-static void append_guidance(const cmdgen_handle* h, std::vector<float>& tables, int K, const std::vector<int>& s_of, int spare, const float (&par5)[5],
+// The guidance tail of a table block, on a row boundary (group tables in front of it are padded to four floats): one guide row (sigma_t,
+// alpha_t, 0, 0) per op, s_of[i] the level op i goes to (t = s + 1), then `spare` unused rows | par: r_c, k_c, scale, max_shift,
+// guide_below, then 0, 0, 0 | rstart [owners + 1] | rec.  alloc_restrain_part points a RestrainBuf at it.
+static void append_guidance(const cmdgen_handle* h, TableBlock& t, int K, const std::vector<int>& s_of, int spare, const float (&par5)[5],
                             const std::vector<int>& rstart, const std::vector<cmdgen_restraint>& rec) {
     std::vector<float> sa;                           // [K][2], row K - 1 - s for the op that goes to level s
     if (h->user_guide_K == K) sa = h->user_guide; else build_guide_table(h->gamma, h->cfg.timesteps, K, sa);
-    const size_t c0 = tables.size(), n_rows = s_of.size() + (size_t)spare;
+    std::vector<float>& tables = t.f;
+    const size_t c0 = (tables.size() + 3) / 4 * 4, n_rows = s_of.size() + (size_t)spare;
+    t.guide = c0; t.guide_rows = (int)n_rows; t.owners = (int)rstart.size() - 1;
     tables.resize(c0 + n_rows * 4 + 8 + rstart.size() + rec.size() * 10, 0.f);
     float* g = tables.data() + c0;
     for (size_t i = 0; i < s_of.size(); ++i) {
@@ -1101,10 +1127,11 @@ static void append_guidance(const cmdgen_handle* h, std::vector<float>& tables, 
     if (!rec.empty()) memcpy(csr + rstart.size(), rec.data(), rec.size() * sizeof(cmdgen_restraint));
 }
 
-// the slot's table block: the posterior rows | the guidance tail, both n_steps + 1 rows
-static int alloc_restrained(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
-    const int rc = alloc_chain_buf(h, k, tables); if (rc) return rc;
-    return alloc_restrain_part(h, k, tables + (size_t)(n_steps + 1) * 4, n_steps + 1, h->lay.B);
+// the op -> level map of a chain without jumps, for append_guidance: op i of K goes to level K - 1 - i
+static std::vector<int> levels_down(int K) {
+    std::vector<int> s_of((size_t)K);
+    for (int i = 0; i < K; ++i) s_of[(size_t)i] = K - 1 - i;
+    return s_of;
 }
 
 extern "C" int cmdgen_restrained_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot, int32_t timesteps,
@@ -1123,12 +1150,10 @@ extern "C" int cmdgen_restrained_chain(cmdgen_handle* h, const float* pocket_x, 
     rc = check_restraints(h, restraints_host, n_restraints, clash_radius, clash_k, scale, max_shift, guide_below,
                           plan_restrained_step_lds(h->lay.max_n, h->dims.P), rstart, rec);
     if (rc) return rc;
-    std::vector<float> tables = step_table(h, K);
-    std::vector<int> s_of((size_t)K);
-    for (int i = 0; i < K; ++i) s_of[(size_t)i] = K - 1 - i;
-    append_guidance(h, tables, K, s_of, 1, {clash_radius, clash_k, scale, max_shift, guide_below}, rstart, rec);
+    TableBlock tables = posterior_rows(step_table(h, K));
+    append_guidance(h, tables, K, levels_down(K), 1, {clash_radius, clash_k, scale, max_shift, guide_below}, rstart, rec);
     Chain ch;
-    rc = ch.open(h, CHAIN_RESTRAINED, tables, K, alloc_restrained, pocket_ids_host, noise, seed, z_steps_out, pocket_steps_out, use_graph, stream); if (rc) return rc;
+    rc = ch.open(h, CHAIN_RESTRAINED, tables, K, alloc_sampling, pocket_ids_host, noise, seed, z_steps_out, pocket_steps_out, use_graph, stream); if (rc) return rc;
     const Dims& d = h->dims;
     const ChainBuf& c = ch.c;
     RestrainBuf rb = ch.k->restr;
@@ -1199,26 +1224,25 @@ static int build_group_plan(cmdgen_handle* h, int64_t n_groups, const int64_t* g
     return 0;
 }
 // ... appended to a plan's tables: first | size | ubase | weight (one entry per member each), then the groups' first members
-static void append_group_tables(std::vector<float>& tables, const GroupPlan& p, const float* weight_host, int B) {
-    const size_t c0 = tables.size();
-    tables.resize(c0 + (size_t)4 * B + p.G);
-    float* g = tables.data() + c0;
+static void append_group_tables(TableBlock& t, const GroupPlan& p, const float* weight_host, int B) {
+    const size_t c0 = t.f.size();
+    t.groups = c0; t.G = p.G;
+    t.f.resize(c0 + (size_t)4 * B + p.G);
+    float* g = t.f.data() + c0;
     memcpy(g, p.first.data(), (size_t)B * sizeof(int)); memcpy(g + B, p.size.data(), (size_t)B * sizeof(int));
     memcpy(g + 2 * (size_t)B, p.ubase.data(), (size_t)B * sizeof(int)); memcpy(g + 3 * (size_t)B, weight_host, (size_t)B * sizeof(float));
     memcpy(g + 4 * (size_t)B, p.gfirst.data(), (size_t)p.G * sizeof(int));
 }
-static void point_group_tab(GroupTab& gt, const float* g, size_t B) {
-    gt.first = (const int*)g; gt.size = (const int*)(g + B); gt.ubase = (const int*)(g + 2 * B);
-    gt.weight = g + 3 * B; gt.group_first = (const int*)(g + 4 * B);
-}
 // the slot's group tables with the call's counts
 static GroupTab group_tab(const ChainSlot& k, const GroupPlan& p) { GroupTab gt = k.groups; gt.G = p.G; gt.Nu = (int)p.Nu; return gt; }
-
-// the multi-pocket chain's ChainBuf and, behind the posterior rows (n_steps + 1) of the slot's table block, the group tables
-static int alloc_multi(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
-    const int rc = alloc_chain_buf(h, k, tables); if (rc) return rc;
-    point_group_tab(k.groups, tables + (size_t)(n_steps + 1) * 4, (size_t)h->lay.B);
-    return 0;
+// the restraint arguments of the restrained multi-pocket chains, checked as check_restraints does: the records belong to the call's groups
+// (the step keeps its unguided parent's LDS, which build_group_plan has checked, and the guide kernel less)
+static int check_group_restraints(cmdgen_handle* h, const GroupPlan& gp, const cmdgen_restraint* restraints_host, int64_t n_restraints,
+                                  float clash_radius, float clash_k, float scale, float max_shift, float guide_below, std::vector<int>& rstart,
+                                  std::vector<cmdgen_restraint>& rec) {
+    RestraintOwners own{"group", "the call's", {}};
+    for (int g = 0; g < gp.G; ++g) own.nphar.push_back((long long)h->cur_nphar[(size_t)gp.gfirst[g]]);
+    return check_restraint_list(h, own, restraints_host, n_restraints, clash_radius, clash_k, scale, max_shift, guide_below, 0, rstart, rec);
 }
 
 extern "C" int cmdgen_multi_pocket_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
@@ -1234,10 +1258,10 @@ extern "C" int cmdgen_multi_pocket_chain(cmdgen_handle* h, const float* pocket_x
     rc = check_timesteps(h, K); if (rc) return rc;
     GroupPlan gp;
     rc = build_group_plan(h, n_groups, group_size_host, weight_host, group_ids_host, gp); if (rc) return rc;
-    std::vector<float> tables = step_table(h, K);
+    TableBlock tables = posterior_rows(step_table(h, K));
     append_group_tables(tables, gp, weight_host, h->lay.B);
     Chain ch;
-    rc = ch.open(h, CHAIN_MULTI, tables, K, alloc_multi, gp.gid.data(), noise, seed, z_steps_out, pocket_steps_out, use_graph, stream); if (rc) return rc;
+    rc = ch.open(h, CHAIN_MULTI, tables, K, alloc_sampling, gp.gid.data(), noise, seed, z_steps_out, pocket_steps_out, use_graph, stream); if (rc) return rc;
     const Dims& d = h->dims;
     const ChainBuf& c = ch.c;
     const GroupTab gt = group_tab(*ch.k, gp);
@@ -1259,15 +1283,6 @@ extern "C" int cmdgen_multi_pocket_chain(cmdgen_handle* h, const float* pocket_x
 // rows | the group tables, padded to a multiple of four floats | the guidance tail with CSR offsets [G + 1] and the records sorted by
 // group - so a changed grouping, weight, restraint or scalar prepares the slot again and drops its captured steps.
 // ---------------------------------------------------------------------------------
-static size_t group_tables_floats(int B, int G) { return ((size_t)4 * B + G + 3) / 4 * 4; }
-// (the groups of the call are in the slot before Chain::open: the guidance tail lies behind G group entries)
-static int alloc_multi_restrained(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
-    int rc = alloc_multi(h, k, tables, n_steps); if (rc) return rc;
-    const float* tail = tables + (size_t)(n_steps + 1) * 4 + group_tables_floats(h->lay.B, k.groups.G);
-    rc = alloc_restrain_part(h, k, tail, n_steps + 1, k.groups.G); if (rc) return rc;
-    return slot_alloc(h, k, k.guide_d, (size_t)h->lay.Nl * 3);    // (Nl bounds the unique rows of any grouping)
-}
-
 extern "C" int cmdgen_multi_restrained_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
                                              int64_t n_groups, const int64_t* group_size_host, const float* weight_host, int32_t timesteps,
                                              const cmdgen_restraint* restraints_host, int64_t n_restraints,
@@ -1284,22 +1299,14 @@ extern "C" int cmdgen_multi_restrained_chain(cmdgen_handle* h, const float* pock
     rc = check_timesteps(h, K); if (rc) return rc;
     GroupPlan gp;
     rc = build_group_plan(h, n_groups, group_size_host, weight_host, group_ids_host, gp); if (rc) return rc;
-    RestraintOwners own{"group", "the call's", {}};
-    for (int g = 0; g < gp.G; ++g) own.nphar.push_back((long long)h->cur_nphar[(size_t)gp.gfirst[g]]);
     std::vector<int> rstart; std::vector<cmdgen_restraint> rec;
-    // (the step keeps k_multi_step_count's LDS, which build_group_plan has checked, and the guide kernel less)
-    rc = check_restraint_list(h, own, restraints_host, n_restraints, clash_radius, clash_k, scale, max_shift, guide_below, 0, rstart, rec);
+    rc = check_group_restraints(h, gp, restraints_host, n_restraints, clash_radius, clash_k, scale, max_shift, guide_below, rstart, rec);
     if (rc) return rc;
-    std::vector<float> tables = step_table(h, K);
-    const size_t t0 = tables.size();
+    TableBlock tables = posterior_rows(step_table(h, K));
     append_group_tables(tables, gp, weight_host, h->lay.B);
-    tables.resize(t0 + group_tables_floats(h->lay.B, gp.G), 0.f);
-    std::vector<int> s_of((size_t)K);
-    for (int i = 0; i < K; ++i) s_of[(size_t)i] = K - 1 - i;
-    append_guidance(h, tables, K, s_of, 1, {clash_radius, clash_k, scale, max_shift, guide_below}, rstart, rec);
-    h->chains[CHAIN_MULTI_RESTRAINED].groups.G = gp.G;            // alloc_multi_restrained reads it
+    append_guidance(h, tables, K, levels_down(K), 1, {clash_radius, clash_k, scale, max_shift, guide_below}, rstart, rec);
     Chain ch;
-    rc = ch.open(h, CHAIN_MULTI_RESTRAINED, tables, K, alloc_multi_restrained, gp.gid.data(), noise, seed, z_steps_out, pocket_steps_out, use_graph, stream);
+    rc = ch.open(h, CHAIN_MULTI_RESTRAINED, tables, K, alloc_sampling, gp.gid.data(), noise, seed, z_steps_out, pocket_steps_out, use_graph, stream);
     if (rc) return rc;
     const Dims& d = h->dims;
     const ChainBuf& c = ch.c;
@@ -1409,7 +1416,7 @@ extern "C" int cmdgen_joint_plan(cmdgen_handle* h, int32_t timesteps, int32_t re
 }
 
 // JointBuf: the plan's rows (coef, coef2, iop: n_steps + 1 each), the state, and the scratch of the combined draws
-static int alloc_joint(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
+static int alloc_joint(cmdgen_handle* h, ChainSlot& k, const TableBlock&, const float* tables, int n_steps) {
     JointBuf& c = k.joint;
     c.coef = (const float4*)tables;
     c.coef2 = (const float4*)(tables + (size_t)(n_steps + 1) * 4);
@@ -1441,7 +1448,7 @@ extern "C" int cmdgen_joint_chain(cmdgen_handle* h, const float* phar_x, const f
     const JointPlan plan = build_joint_plan(h->gamma, h->cfg.timesteps, timesteps, resamplings, jump_length, inpaint);
     rc = check_draws(h, noise, n_draws, plan.n_draws, "combined draws"); if (rc) return rc;
     const int n_steps = plan.n_steps;
-    std::vector<float> tables = plan_tables(plan.coef, plan.coef2, plan.iop);
+    TableBlock tables = plan_tables(plan.coef, plan.coef2, plan.iop);
     Chain ch;                                        // (open and close only: the joint chain has no ChainBuf and evaluates BEFORE its step)
     rc = ch.open(h, CHAIN_JOINT, tables, n_steps, alloc_joint, pocket_ids_host, noise, seed, z_steps_out, nullptr, use_graph, stream); if (rc) return rc;
     const Dims& d = h->dims;
@@ -1537,12 +1544,6 @@ extern "C" int cmdgen_inpaint_plan(cmdgen_handle* h, int32_t timesteps, int32_t 
     return cmdgen_edit_plan(h, timesteps, timesteps, resamplings, jump_length, n_steps, n_draws);
 }
 
-// the inpainting chain's ChainBuf (posterior rows: coef, n_steps + 1) and InpaintBuf (coef2, iop: n_steps each; the known part)
-static int alloc_inpaint(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
-    const int rc = alloc_chain_buf(h, k, tables); if (rc) return rc;
-    return alloc_inpaint_part(h, k, tables + (size_t)(n_steps + 1) * 4, n_steps);
-}
-
 // the init launches of cmdgen_edit_chain and cmdgen_restrained_edit_chain
 static void launch_edit_init(const Chain& ch, const InpaintBuf& ip, const InpaintPlan& plan, bool from_prior, const float* pocket_x, const float* pocket_onehot,
                              const float* phar_x, const float* phar_onehot, const float* fix_x, const float* fix_h) {
@@ -1574,9 +1575,9 @@ extern "C" int cmdgen_edit_chain(cmdgen_handle* h, const float* pocket_x, const 
         return fail(h, CMDGEN_EINVAL, "null device pointer");
     const InpaintPlan plan = build_inpaint_plan(h, timesteps, start, resamplings, jump_length);
     rc = check_draws(h, noise, n_draws, plan.n_draws); if (rc) return rc;
-    std::vector<float> tables = plan_tables(plan.coef, plan.coef2, plan.iop);
+    TableBlock tables = plan_tables(plan.coef, plan.coef2, plan.iop);   // coef (n_steps + 1 rows) | coef2 | iop (n_steps each)
     Chain ch;
-    rc = ch.open(h, CHAIN_INPAINT, tables, plan.n_steps, alloc_inpaint, pocket_ids_host, noise, seed, z_steps_out, pocket_steps_out, use_graph, stream); if (rc) return rc;
+    rc = ch.open(h, CHAIN_INPAINT, tables, plan.n_steps, alloc_sampling, pocket_ids_host, noise, seed, z_steps_out, pocket_steps_out, use_graph, stream); if (rc) return rc;
     const Dims& d = h->dims;
     const ChainBuf& c = ch.c;
     const InpaintBuf ip = ch.k->inp;
@@ -1609,12 +1610,6 @@ extern "C" int cmdgen_inpaint_chain(cmdgen_handle* h, const float* pocket_x, con
 // per OP (sigma_t, alpha_t, 0, 0), r_c, k_c, scale, max_shift, guide_below, 0, 0, 0, the CSR offsets [B + 1] and the records sorted by
 // sample - so a changed plan, start, restraint or scalar prepares the slot again and drops its captured steps.
 // ---------------------------------------------------------------------------------
-static int alloc_restrained_edit(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
-    int rc = alloc_chain_buf(h, k, tables); if (rc) return rc;
-    rc = alloc_inpaint_part(h, k, tables + (size_t)(n_steps + 1) * 4, n_steps); if (rc) return rc;
-    return alloc_restrain_part(h, k, tables + (size_t)(3 * n_steps + 1) * 4, n_steps, h->lay.B);
-}
-
 extern "C" int cmdgen_restrained_edit_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
                                             const float* phar_x, const float* phar_onehot, const float* fix_x, const float* fix_h,
                                             int32_t timesteps, int32_t start, int32_t resamplings, int32_t jump_length,
@@ -1635,10 +1630,10 @@ extern "C" int cmdgen_restrained_edit_chain(cmdgen_handle* h, const float* pocke
     if (rc) return rc;
     const InpaintPlan plan = build_inpaint_plan(h, timesteps, start, resamplings, jump_length);
     rc = check_draws(h, noise, n_draws, plan.n_draws); if (rc) return rc;
-    std::vector<float> tables = plan_tables(plan.coef, plan.coef2, plan.iop);
+    TableBlock tables = plan_tables(plan.coef, plan.coef2, plan.iop);
     append_guidance(h, tables, timesteps, plan.s_of, 0, {clash_radius, clash_k, scale, max_shift, guide_below}, rstart, rec);
     Chain ch;
-    rc = ch.open(h, CHAIN_RESTRAINED_EDIT, tables, plan.n_steps, alloc_restrained_edit, pocket_ids_host, noise, seed, z_steps_out, pocket_steps_out, use_graph, stream);
+    rc = ch.open(h, CHAIN_RESTRAINED_EDIT, tables, plan.n_steps, alloc_sampling, pocket_ids_host, noise, seed, z_steps_out, pocket_steps_out, use_graph, stream);
     if (rc) return rc;
     const Dims& d = h->dims;
     const ChainBuf& c = ch.c;
@@ -1660,14 +1655,8 @@ extern "C" int cmdgen_restrained_edit_chain(cmdgen_handle* h, const float* pocke
 // ---------------------------------------------------------------------------------
 // the multi-pocket edit chain: the edit chain's ops on the multi-pocket chain's shared latent (kernels_multi.hip; the ops, the group
 // offset and the draw scheme are in include/cmdgen_hip.h).  The plan is the edit chain's, the group tables the multi-pocket chain's.
+// The slot's table block is: the edit plan's tables | the group tables; the known rows and marks are held once per group.
 // ---------------------------------------------------------------------------------
-// the slot's table block: coef (n_steps + 1) | coef2 | iop (n_steps each) | the group tables; the known rows and marks once per group
-static int alloc_multi_edit(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
-    const int rc = alloc_chain_buf(h, k, tables); if (rc) return rc;
-    point_group_tab(k.groups, tables + (size_t)(3 * n_steps + 1) * 4, (size_t)h->lay.B);
-    return alloc_inpaint_part(h, k, tables + (size_t)(n_steps + 1) * 4, n_steps);
-}
-
 extern "C" int cmdgen_multi_edit_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
                                        int64_t n_groups, const int64_t* group_size_host, const float* weight_host,
                                        const float* phar_x, const float* phar_onehot, const float* fix_x, const float* fix_h,
@@ -1685,10 +1674,10 @@ extern "C" int cmdgen_multi_edit_chain(cmdgen_handle* h, const float* pocket_x, 
     rc = build_group_plan(h, n_groups, group_size_host, weight_host, group_ids_host, gp); if (rc) return rc;
     const InpaintPlan plan = build_inpaint_plan(h, timesteps, start, resamplings, jump_length);
     rc = check_draws(h, noise, n_draws, plan.n_draws); if (rc) return rc;
-    std::vector<float> tables = plan_tables(plan.coef, plan.coef2, plan.iop);
+    TableBlock tables = plan_tables(plan.coef, plan.coef2, plan.iop);
     append_group_tables(tables, gp, weight_host, h->lay.B);
     Chain ch;
-    rc = ch.open(h, CHAIN_MULTI_EDIT, tables, plan.n_steps, alloc_multi_edit, gp.gid.data(), noise, seed, z_steps_out, pocket_steps_out, use_graph, stream); if (rc) return rc;
+    rc = ch.open(h, CHAIN_MULTI_EDIT, tables, plan.n_steps, alloc_sampling, gp.gid.data(), noise, seed, z_steps_out, pocket_steps_out, use_graph, stream); if (rc) return rc;
     const Dims& d = h->dims;
     const ChainBuf& c = ch.c;
     const InpaintBuf ip = ch.k->inp;
@@ -1717,14 +1706,6 @@ extern "C" int cmdgen_multi_edit_chain(cmdgen_handle* h, const float* pocket_x, 
 // plan, CSR offsets [G + 1] and the records sorted by group - so a changed grouping, weight, plan, start, restraint or scalar prepares the
 // slot again and drops its captured steps.
 // ---------------------------------------------------------------------------------
-// (the groups of the call are in the slot before Chain::open, as for alloc_multi_restrained)
-static int alloc_multi_restrained_edit(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_steps) {
-    int rc = alloc_multi_edit(h, k, tables, n_steps); if (rc) return rc;
-    const float* tail = tables + (size_t)(3 * n_steps + 1) * 4 + group_tables_floats(h->lay.B, k.groups.G);
-    rc = alloc_restrain_part(h, k, tail, n_steps, k.groups.G); if (rc) return rc;
-    return slot_alloc(h, k, k.guide_d, (size_t)h->lay.Nl * 3);    // (Nl bounds the unique rows of any grouping)
-}
-
 extern "C" int cmdgen_multi_restrained_edit_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
                                                   int64_t n_groups, const int64_t* group_size_host, const float* weight_host,
                                                   const float* phar_x, const float* phar_onehot, const float* fix_x, const float* fix_h,
@@ -1743,22 +1724,16 @@ extern "C" int cmdgen_multi_restrained_edit_chain(cmdgen_handle* h, const float*
         return fail(h, CMDGEN_EINVAL, "null pointer");
     GroupPlan gp;
     rc = build_group_plan(h, n_groups, group_size_host, weight_host, group_ids_host, gp); if (rc) return rc;
-    RestraintOwners own{"group", "the call's", {}};
-    for (int g = 0; g < gp.G; ++g) own.nphar.push_back((long long)h->cur_nphar[(size_t)gp.gfirst[g]]);
     std::vector<int> rstart; std::vector<cmdgen_restraint> rec;
-    // (the step keeps k_multi_edit_step_count's LDS, which build_group_plan has checked, and the guide kernel less)
-    rc = check_restraint_list(h, own, restraints_host, n_restraints, clash_radius, clash_k, scale, max_shift, guide_below, 0, rstart, rec);
+    rc = check_group_restraints(h, gp, restraints_host, n_restraints, clash_radius, clash_k, scale, max_shift, guide_below, rstart, rec);
     if (rc) return rc;
     const InpaintPlan plan = build_inpaint_plan(h, timesteps, start, resamplings, jump_length);
     rc = check_draws(h, noise, n_draws, plan.n_draws); if (rc) return rc;
-    std::vector<float> tables = plan_tables(plan.coef, plan.coef2, plan.iop);
-    const size_t t0 = tables.size();
+    TableBlock tables = plan_tables(plan.coef, plan.coef2, plan.iop);
     append_group_tables(tables, gp, weight_host, h->lay.B);
-    tables.resize(t0 + group_tables_floats(h->lay.B, gp.G), 0.f);
     append_guidance(h, tables, timesteps, plan.s_of, 0, {clash_radius, clash_k, scale, max_shift, guide_below}, rstart, rec);
-    h->chains[CHAIN_MULTI_RESTRAINED_EDIT].groups.G = gp.G;       // alloc_multi_restrained_edit reads it
     Chain ch;
-    rc = ch.open(h, CHAIN_MULTI_RESTRAINED_EDIT, tables, plan.n_steps, alloc_multi_restrained_edit, gp.gid.data(), noise, seed, z_steps_out, pocket_steps_out, use_graph, stream);
+    rc = ch.open(h, CHAIN_MULTI_RESTRAINED_EDIT, tables, plan.n_steps, alloc_sampling, gp.gid.data(), noise, seed, z_steps_out, pocket_steps_out, use_graph, stream);
     if (rc) return rc;
     const Dims& d = h->dims;
     const ChainBuf& c = ch.c;
@@ -1787,7 +1762,7 @@ extern "C" int cmdgen_multi_restrained_edit_chain(cmdgen_handle* h, const float*
 // scoring: ConditionalDDPM.score (kernels_score.hip; the level semantics and the output columns are in include/cmdgen_hip.h)
 // ---------------------------------------------------------------------------------
 // the scoring chain's ChainBuf (coef: one row per level, then the (alpha_T, sigma_T) row) and the clean rows it noises
-static int alloc_score(cmdgen_handle* h, ChainSlot& k, const float* tables, int) {
+static int alloc_score(cmdgen_handle* h, ChainSlot& k, const TableBlock&, const float* tables, int) {
     const int rc = alloc_chain_buf(h, k, tables); if (rc) return rc;
     return alloc_score_part(h, k);
 }
@@ -1825,9 +1800,9 @@ extern "C" int cmdgen_score_chain(cmdgen_handle* h, const float* phar_x, const f
     rc = refuse_joint_no_com(h, "scoring", kOwnPocketTerms); if (rc) return rc;
     if (!phar_x || !phar_onehot || !pocket_x || !pocket_onehot || !t_levels_host || !level_terms_out || !kl_sums_out)
         return fail(h, CMDGEN_EINVAL, "null pointer");
-    std::vector<float> tables;
-    rc = build_level_rows(h, n_levels, t_levels_host, level_coef_host, tables); if (rc) return rc;
-    const float alpha_T = tables[4 * (size_t)n_levels];
+    TableBlock tables;
+    rc = build_level_rows(h, n_levels, t_levels_host, level_coef_host, tables.f); if (rc) return rc;
+    const float alpha_T = tables.f[4 * (size_t)n_levels];
     Chain ch;
     rc = ch.open(h, CHAIN_SCORE, tables, n_levels, alloc_score, pocket_ids_host, noise, seed, nullptr, nullptr, use_graph, stream); if (rc) return rc;
     const Dims& d = h->dims;
@@ -1850,9 +1825,9 @@ extern "C" int cmdgen_score_chain(cmdgen_handle* h, const float* phar_x, const f
 // include/cmdgen_hip.h).  The level rows are the scoring chain's, the group tables the multi-pocket chain's.
 // ---------------------------------------------------------------------------------
 // the slot's table block: the level rows (n_levels + 1) | the group tables
-static int alloc_multi_score(cmdgen_handle* h, ChainSlot& k, const float* tables, int n_levels) {
+static int alloc_multi_score(cmdgen_handle* h, ChainSlot& k, const TableBlock& t, const float* tables, int) {
     const int rc = alloc_chain_buf(h, k, tables); if (rc) return rc;
-    point_group_tab(k.groups, tables + (size_t)(n_levels + 1) * 4, (size_t)h->lay.B);
+    point_group_tab(k.groups, tables + t.groups, (size_t)h->lay.B);
     return alloc_score_part(h, k);
 }
 
@@ -1868,11 +1843,11 @@ extern "C" int cmdgen_multi_score_chain(cmdgen_handle* h, const float* phar_x, c
     if (!phar_x || !phar_onehot || !pocket_x || !pocket_onehot || !group_size_host || !weight_host || !t_levels_host || !group_terms_out ||
         !kl_sums_out)
         return fail(h, CMDGEN_EINVAL, "null pointer");
-    std::vector<float> tables;
-    rc = build_level_rows(h, n_levels, t_levels_host, level_coef_host, tables); if (rc) return rc;
+    TableBlock tables;
+    rc = build_level_rows(h, n_levels, t_levels_host, level_coef_host, tables.f); if (rc) return rc;
     GroupPlan gp;
     rc = build_group_plan(h, n_groups, group_size_host, weight_host, group_ids_host, gp); if (rc) return rc;
-    const float alpha_T = tables[4 * (size_t)n_levels];
+    const float alpha_T = tables.f[4 * (size_t)n_levels];
     append_group_tables(tables, gp, weight_host, h->lay.B);
     Chain ch;
     rc = ch.open(h, CHAIN_MULTI_SCORE, tables, n_levels, alloc_multi_score, gp.gid.data(), noise, seed, nullptr, nullptr, use_graph, stream); if (rc) return rc;

@@ -21,13 +21,28 @@ struct DevBuf {
     void* p = nullptr; size_t bytes = 0;
 };
 
+// A slot's table block as its entry lays it out (cmdgen_api.hip): the posterior (scoring: level) rows | the edit tables | the group tables |
+// the guidance tail - whatever must prepare the slot again when it changes.  Each appender records where its section begins, so nothing
+// derives an offset a second time.
+struct TableBlock {
+    std::vector<float> f;                  // the upload
+    size_t edit = 0, groups = 0, guide = 0; // float offset of the edit tables (coef2 | iop), the group tables, the guidance tail; 0: the block has none
+    int guide_rows = 0;                    // guide rows of the tail
+    int owners = 0;                        // owners of the tail's restraints (the layout's samples, or the groups): its CSR offsets are [owners + 1]
+    int G = 0;                             // groups of the group tables; nothing reads it back (a call's counts come from its GroupPlan) - it is part of the slot's key only
+    bool same(const TableBlock& o) const {
+        return edit == o.edit && groups == o.groups && guide == o.guide && guide_rows == o.guide_rows && owners == o.owners && G == o.G &&
+               f.size() == o.f.size() && memcmp(f.data(), o.f.data(), f.size() * sizeof(float)) == 0;
+    }
+};
+
 // Host state of one kind of denoising chain (cmdgen_api.hip): its buffers for the current layout, the plan tables they were
 // prepared for, and its captured steps.  Each kind has a slot of its own, so plain and inpainting chains alternate on a
 // handle without re-preparing or re-capturing.
 enum ChainKind { CHAIN_PLAIN, CHAIN_JOINT, CHAIN_INPAINT, CHAIN_SCORE, CHAIN_MULTI, CHAIN_MULTI_EDIT, CHAIN_MULTI_SCORE, CHAIN_RESTRAINED, CHAIN_RESTRAINED_EDIT, CHAIN_MULTI_RESTRAINED, CHAIN_MULTI_RESTRAINED_EDIT, CHAIN_KINDS };
 struct ChainSlot {
     std::vector<void*> allocs;
-    std::vector<float> tables;             // the uploaded plan tables (coef | coef2 | iop bits), compared to decide a re-prepare
+    TableBlock tables;                     // the uploaded table block with its offsets, compared to decide a re-prepare
     int n_steps = -1;                      // denoising steps of the prepared plan (-1: nothing prepared)
     unsigned int* check = nullptr;         // [n_steps+3][2] (cmdgen_chain_status)
     ChainState* state = nullptr;

@@ -2,7 +2,8 @@
 ops walked by ref_cpu.get_repaint_schedule, the decode) built only from oracle.ref_cpu primitives in torch fp32, and three optional parts -
 `groups` (the device's GroupTab), `edit` (InpaintBuf) and `guide` (RestrainBuf).  With no part it is ref_cpu.sample_given_pocket's op sequence,
 bit for bit given the same draws.  What a chain IS - layout, frames, what reduces to what - is said in the docstring of its adapter module
-(cond_inpaint_ref, edit_ref, multi_pocket_ref, multi_edit_ref, restraint_ref, restrained_edit_ref); the tables and terms the parts need
+(cond_inpaint_ref, edit_ref, multi_pocket_ref, multi_edit_ref, restraint_ref, restrained_edit_ref, multi_restraint_ref,
+multi_restrained_edit_ref); the tables and terms the parts need
 (Groups, pair_margins, energy_terms, the plans) live here and are imported back by those modules."""
 import numpy as np
 import torch
@@ -191,16 +192,21 @@ def touched_samples(rec, B, clash_r):
     return t
 
 
-def op_terms(z, P, eps_t, known, fx, sigma_t, alpha_t, com_in, pm, qm, rec, clash_r, clash_k, n_x, nd):
-    """Steps 1-3 of one op: -> (xhat [Nl, 3] (A), shift [B, 3] (A), E [B], g [Nl, 3], largest violation per kind [4]).  z, P: the op's input;
-    eps_t: the network's output; known: the normalised given rows (None: no row is given); fx [Nl] bool: the rows whose x columns are held."""
+def op_terms(z, P, eps_t, known, fx, sigma_t, alpha_t, com_in, pm, qm, rec, clash_r, clash_k, n_x, nd, first=None, qg=None):
+    """Steps 1-3 of one op: -> (xhat [rows, 3] (A), shift [owners, 3] (A), E [owners], g [rows, 3], largest violation per kind [4]).  z, P: the
+    op's input; eps_t: the network's output; known: the normalised given rows (None: no row is given); fx [rows] bool: the rows whose x columns
+    are held.  A restraint's OWNER is a sample, or grouped a group: z, eps_t, known and fx then hold one copy of the rows per group, pm is the
+    group of a row, first [G] the member whose pocket gives a group its frame and qg [Np] the group of a pocket atom (qm stays its member).
+    Ungrouped both default to the identities."""
     B = com_in.shape[0]
-    shift = n_x * (ref_cpu.scatter_mean(P[:, :nd], qm, B) - com_in)                               # 2.
-    xhat = n_x * (z[:, :nd] - sigma_t[pm] * eps_t[:, :nd]) / alpha_t[pm]                           # 1. free rows
+    first = torch.arange(B) if first is None else first
+    qg = qm if qg is None else qg
+    shift = (n_x * (ref_cpu.scatter_mean(P[:, :nd], qm, B) - com_in))[first]                      # 2. the owner's first member's
+    xhat = n_x * (z[:, :nd] - sigma_t[first][pm] * eps_t[:, :nd]) / alpha_t[first][pm]            # 1. free rows
     if known is not None:
         held = n_x * known[:, :nd] + shift[pm]                                                     #    held rows: the given position in this frame
         xhat = torch.where(fx[:, None], held, xhat)
-    E, g, _, vk = energy_terms(xhat, n_x * P[:, :nd], shift, pm, qm, rec, clash_r, clash_k)        # 3.
+    E, g, _, vk = energy_terms(xhat, n_x * P[:, :nd], shift, pm, qg, rec, clash_r, clash_k)        # 3. every member's atoms
     return xhat, shift, E, g, vk
 
 
@@ -216,13 +222,14 @@ def run_chain(p, cfg, pocket, phar=None, num_nodes_phar=None, groups=None, edit=
         num_nodes_phar [G], the draws and the reported rows hold one copy of the rows per group.
       edit = dict(fix_x, fix_h [rows], start, resamplings, jump_length): op B and the jumps; start < timesteps begins at q(z_start | given rows).
         Without it there is no op B and no B draw, and the schedule is get_repaint_schedule(1, 1, K) == [K].
-      guide = dict(rec, clash_r, clash_k, scale, max_shift, guide_below): steps 1-5 of csrc/kernels_restrain.hip's header in op A; probe(op
-        index, dict of op_terms' inputs) is called before them.
+      guide = dict(rec, clash_r, clash_k, scale, max_shift, guide_below): steps 1-5 of csrc/kernels_restrain.hip's header in op A, once per
+        OWNER of a restraint - a sample, or with groups a group (rec['sample'] is then the group index): its rows are the reported copy, its
+        frame its first member's pocket, its clash atoms every member's, and every member's copy gets the same displacement.  probe(op index,
+        dict of op_terms' inputs in the owner view, and the op's t [B, 1]) is called before them.
     -> dict(xh_phar, xh_pocket, phar_mask, pocket_mask, z_steps [n_steps, rows, 3+P], pocket_steps [n_steps, Np, 3], margins [n_steps + 1, B]
     (A, one row per evaluation; None unless recorded), known_steps [n_steps, rows, 3] (edit), op_energy [n_steps, B], kind_violation
-    [n_steps, 4], energy [B], max_violation [B], clipped, unclipped: counts of displacements (guide))."""
-    if groups is not None and guide is not None:
-        raise NotImplementedError('groups with a guide part has no device chain, and whose frame shift its energy would see is not defined')
+    [n_steps, 4], energy [B], max_violation [B], clipped, unclipped: counts of displacements per reported row and op (guide; grouped, [B]
+    reads [G]: one entry per owner)."""
     T, nd, pnf = cfg['timesteps'], cfg['n_dims'], cfg['phar_nf']
     nv, nb = cfg['norm_values'], cfg['norm_biases']
     n_x = nv[0]
@@ -244,6 +251,7 @@ def run_chain(p, cfg, pocket, phar=None, num_nodes_phar=None, groups=None, edit=
         pm = phar['mask'].to(INT) if phar is not None else torch.repeat_interleave(torch.arange(B), torch.as_tensor(num_nodes_phar).to(INT))
         n_rows, out_mask, offset_of = len(pm), pm, torch.arange(B)
         spread = report = lambda rows: rows
+        um, qg, first, n_own = pm, qm, torch.arange(B), B           # the owner view of the guide part: a sample owns its restraints
     else:
         gr = Groups(groups['group_sizes'], np.asarray(phar['size']).reshape(-1) if phar is not None else num_nodes_phar)
         B = gr.B
@@ -254,15 +262,18 @@ def run_chain(p, cfg, pocket, phar=None, num_nodes_phar=None, groups=None, edit=
         group_of = torch.from_numpy(gr.group_of)
         offset_of = torch.from_numpy(gr.first)[group_of]            # [B] the first member of a member's group: its pocket shift is the group's
         spread, report = (lambda rows: rows[gr.urow]), (lambda rows: rows[gr.first_rows()])
+        # ... a GROUP owns them: owner of a reported row, of a pocket atom (members ascending, atoms in index order), the member whose frame it uses
+        um, qg, first, n_own = gr.unique_mask, group_of[qm], torch.from_numpy(gr.first), gr.G
     shape = (n_rows, nd + pnf)
     # normalize (en_diffusion.py:874-889)
     px = pocket['x'].to(FLOAT) / n_x
     xh0_pocket = torch.cat([px, (pocket['one_hot'].float() - nb[1]) / nv[1]], dim=1)
     com0 = ref_cpu.scatter_mean(px, qm, B)                          # com(P_in.x / n_x)
-    known, fx = None, torch.zeros(len(pm), dtype=torch.bool)
+    known_u, fx_u = None, torch.zeros(n_rows, dtype=torch.bool)    # (_u: one copy of the rows per group, before spread)
     if edit is not None:
-        known = spread(torch.cat([phar['x'].to(FLOAT) / n_x, (phar['one_hot'].float() - nb[1]) / nv[1]], dim=1))
-        fx = spread(torch.as_tensor(edit['fix_x']).to(FLOAT).reshape(-1) != 0)
+        known_u = torch.cat([phar['x'].to(FLOAT) / n_x, (phar['one_hot'].float() - nb[1]) / nv[1]], dim=1)
+        fx_u = torch.as_tensor(edit['fix_x']).to(FLOAT).reshape(-1) != 0
+        known, fx = spread(known_u), spread(fx_u)
         fh = spread(torch.as_tensor(edit['fix_h']).to(FLOAT).reshape(-1) != 0)
         col_fixed = torch.cat([fx[:, None].expand(-1, nd), fh[:, None].expand(-1, pnf)], dim=1)
         has_mark = torch.zeros(B, dtype=torch.bool)
@@ -270,7 +281,7 @@ def run_chain(p, cfg, pocket, phar=None, num_nodes_phar=None, groups=None, edit=
         rows_m, rows_q = has_mark[pm], has_mark[qm]
     if guide is not None:
         rec, clash_r, clash_k, scale, max_shift = (guide[k] for k in ('rec', 'clash_r', 'clash_k', 'scale', 'max_shift'))
-        touched = torch.from_numpy(touched_samples(rec, B, clash_r))
+        touched = torch.from_numpy(touched_samples(rec, n_own, clash_r))   # [owners]
         any_touched = bool(touched.any())
 
     # init
@@ -341,23 +352,25 @@ def run_chain(p, cfg, pocket, phar=None, num_nodes_phar=None, groups=None, edit=
             sig = sigma_ts * sigma_s / sigma_t
             if guide is not None:
                 alpha_t = ref_cpu.alpha_of(gamma_t)
-                E, vk = torch.zeros(B), torch.zeros(4)
+                E, vk = torch.zeros(n_own), torch.zeros(4)
+                terms_in = dict(z=report(z), P=P, eps_t=report(eps_t), known=known_u, fx=fx_u, sigma_t=sigma_t, alpha_t=alpha_t, com_in=com0,
+                                pm=um, qm=qm, first=first, qg=qg)
                 if probe is not None:
-                    probe(len(op_energy), dict(z=z, P=P, eps_t=eps_t, known=known, fx=fx, sigma_t=sigma_t, alpha_t=alpha_t, com_in=com0, pm=pm,
-                                               qm=qm))
+                    probe(len(op_energy), dict(terms_in, t=t_array))
                 if any_touched:
-                    _, _, E, g, vk = op_terms(z, P, eps_t, known, fx, sigma_t, alpha_t, com0, pm, qm, rec, clash_r, clash_k, n_x, nd)  # 1. - 3.
-                    var = (n_x * sig) ** 2
-                    d = -scale * var[pm] * g                                                       # 4.
+                    _, _, E, g, vk = op_terms(rec=rec, clash_r=clash_r, clash_k=clash_k, n_x=n_x, nd=nd, **terms_in)          # 1. - 3.
+                    var = (n_x * sig[first]) ** 2
+                    d = -scale * var[um] * g                                                       # 4.
                     length = _norm(d)
                     over = length > max_shift
                     d = torch.where(over[:, None], d * (max_shift / length.clamp(min=1e-30))[:, None], d)
-                    active = touched[pm] & (t_array[pm][:, 0] <= guide['guide_below']) & (scale > 0) & ~fx   # a held row gets nothing added
+                    active = touched[um] & (t_array[first][um][:, 0] <= guide['guide_below']) & (scale > 0) & ~fx_u   # a held row gets nothing added
                     clipped += int((over & active).sum())
                     unclipped += int((~over & active & (length > 0)).sum())
-                    rows = torch.nonzero(active).reshape(-1)
+                    d_m = spread(d)                                                                # every member's copy gets the same displacement
+                    rows = torch.nonzero(spread(active)).reshape(-1)
                     if len(rows):
-                        mu[rows, :nd] = mu[rows, :nd] + d[rows] / n_x                              # 5.
+                        mu[rows, :nd] = mu[rows, :nd] + d_m[rows] / n_x                            # 5.
                 op_energy.append(E)
                 kind_v.append(vk)
             if checks:
@@ -409,9 +422,10 @@ def run_chain(p, cfg, pocket, phar=None, num_nodes_phar=None, groups=None, edit=
                phar_mask=out_mask, pocket_mask=qm, z_steps=torch.stack(z_steps), pocket_steps=torch.stack(p_steps),
                margins=np.stack(margins) if record_margins else None, known_steps=torch.stack(k_steps) if edit is not None else None)
     if guide is not None:
-        # the diagnostics of the returned sample (held points at their returned positions): shift from the returned pocket
-        shift = ref_cpu.scatter_mean(x_pocket, qm, B) - n_x * com0
-        E_fin, _, v_fin, _ = energy_terms(x_phar, x_pocket, shift, pm, qm, rec, clash_r, clash_k)
+        # the diagnostics of the returned rows (held points at their returned positions) against every member's returned pocket: shift from
+        # the owner's first member's returned pocket
+        shift = (ref_cpu.scatter_mean(x_pocket, qm, B) - n_x * com0)[first]
+        E_fin, _, v_fin, _ = energy_terms(report(x_phar), x_pocket, shift, um, qg, rec, clash_r, clash_k)
         out.update(op_energy=torch.stack(op_energy), kind_violation=torch.stack(kind_v), energy=E_fin, max_violation=v_fin, clipped=clipped,
                    unclipped=unclipped)
     return out

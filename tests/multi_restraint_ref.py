@@ -12,19 +12,34 @@ GROUP:
 With no record and r_c = 0, or with scale = 0, it reproduces multi_pocket_ref.multi_pocket_chain bit for bit; with every group of one
 member it reproduces restraint_ref.restrained_chain bit for bit (test_multi_restraint_cpu.py asserts both).
 
-Why this module has a loop of its own: chain_ref.run_chain refuses `groups` together with `guide`, and chain_ref.py is a yardstick that
-does not move.  So the loop below repeats run_chain's grouped branch (slot-by-slot evaluation, Groups.combine) and op_terms' five steps,
-composed from the parts chain_ref exports (Groups, energy_terms, touched_samples, pair_margins, kept_groups) and oracle.ref_cpu.  The
-duplication is the price of not moving a yardstick."""
+It is chain_ref.run_chain with the groups and the guide parts."""
 import numpy as np
 import torch
 
-from chain_ref import CHAIN_CAP, MARGIN, Groups, _norm, energy_terms, kept_groups, pair_margins, touched_samples      # noqa: F401
-from oracle import ref_cpu
-from oracle.ref_cpu import FLOAT, INT
+from chain_ref import CHAIN_CAP, MARGIN, Groups, _norm, energy_terms, kept_groups, op_terms, pair_margins, run_chain, touched_samples      # noqa: F401
 
 KEYS = ('xh_phar', 'xh_pocket', 'phar_mask', 'pocket_mask', 'z_steps', 'pocket_steps', 'margins', 'op_energy', 'energy', 'max_violation',
         'kind_violation', 'clipped', 'unclipped', 'other_member_clash')
+
+
+def other_member_clash(a, clash_r, n_x, nd):
+    """A test's diagnostic, no part of the chain: the largest clash violation (A) of one op - `a` is what run_chain hands its probe - against
+    an atom of a member other than its group's first.  Does a member other than the first bite?"""
+    if not clash_r > 0:
+        return 0.0
+    terms_in = {k: v for k, v in a.items() if k != 't'}
+    # the op's xhat, by the loop's own steps 1 and 2 a second time; with no record and r_c = 0 energy_terms pushes no term (both of its loops
+    # are empty: `for r in rec`, `if clash_r > 0`) and returns zeros
+    xhat = op_terms(rec=(), clash_r=0.0, clash_k=0.0, n_x=n_x, nd=nd, **terms_in)[0]
+    q, um, qg = n_x * a['P'][:, :nd], a['pm'], a['qg']
+    other = a['first'][qg] != a['qm']                                  # [Np] atoms of a member that is not its group's first
+    vo = 0.0
+    for k in range(len(a['first'])):
+        pts, atoms = xhat[um == k], q[other & (qg == k)]
+        if len(pts) and len(atoms):
+            dist = _norm((pts[:, None, :] - atoms[None, :, :]).reshape(-1, 3))
+            vo = max(vo, float(torch.clamp(clash_r - dist, min=0).max()))
+    return vo
 
 
 def multi_restrained_chain(p, cfg, pocket, group_sizes, num_nodes_phar, weights, rec, clash_r=0.0, clash_k=0.0, scale=1.0, max_shift=1.0,
@@ -35,133 +50,10 @@ def multi_restrained_chain(p, cfg, pocket, group_sizes, num_nodes_phar, weights,
     margins [K + 1, B] (A), op_energy [K, G], energy [G], max_violation [G], kind_violation [K, 4], clipped, unclipped: counts of
     displacements (per unique row and op), other_member_clash [K]: the largest clash violation (A) against an atom of a member other than its
     group's first)."""
-    T, nd, pnf = cfg['timesteps'], cfg['n_dims'], cfg['phar_nf']
-    nv, nb = cfg['norm_values'], cfg['norm_biases']
-    n_x = nv[0]
-    assert not cfg.get('no_com_projection', False) and not cfg.get('update_pocket_coords', False)
-    table = ref_cpu.gamma_source(p)
-    timesteps = T if timesteps is None else timesteps
-    draw = noise if noise is not None else (lambda shape: torch.randn(shape))
-
-    qm = pocket['mask'].to(INT)
-    gr = Groups(group_sizes, num_nodes_phar)
-    B, G = gr.B, gr.G
-    assert len(pocket['size']) == B
-    w = torch.as_tensor(weights).to(FLOAT).reshape(-1)
-    assert len(w) == B
-    pm, um = gr.phar_mask, gr.unique_mask
-    group_of = torch.from_numpy(gr.group_of)
-    first = torch.from_numpy(gr.first)                                # [G] the first member of a group: the guidance frame is its pocket's
-    qg = group_of[qm]                                                  # [Np] group of a pocket atom: members ascending, atoms in index order
-    spread, report = (lambda rows: rows[gr.urow]), (lambda rows: rows[gr.first_rows()])
-    shape = (gr.Nu, nd + pnf)
-    px = pocket['x'].to(FLOAT) / n_x
-    xh0_pocket = torch.cat([px, (pocket['one_hot'].float() - nb[1]) / nv[1]], dim=1)
-    com0 = ref_cpu.scatter_mean(px, qm, B)                            # com(P_in.x / n_x)
-    touched = torch.from_numpy(touched_samples(rec, G, clash_r))       # [G]
-    any_touched = bool(touched.any())
-    other = (torch.arange(B) != first[group_of])[qm]                   # [Np] atoms of a member that is not its group's first
-
-    # init: c = sum_m w_m com(P_m), every member's copy is [c, 0] + the group's draw
-    c = gr.combine_members(com0, w)[group_of]
-    mu_phar = torch.cat((c, torch.zeros((B, pnf))), dim=1)[pm]
-    sigma = torch.ones_like(pocket['size']).unsqueeze(1)
-    z, P = ref_cpu.sample_normal_zero_com(mu_phar, xh0_pocket, sigma, pm, qm, spread(draw(shape)), nd)
-    if checks:
-        ref_cpu.assert_mean_zero_with_mask(z[:, :nd], pm)
-
-    # evaluation, slot by slot: call j holds the j-th member of every group that has one, as one ordinary batch (chain_ref.run_chain)
-    slots = []
-    for j, (u, r, b) in enumerate(gr.rows_of):
-        members = torch.from_numpy(gr.first[gr.sizes > j] + j)
-        renum = torch.full((B,), -1, dtype=INT)
-        renum[members] = torch.arange(len(members))
-        qrows = torch.nonzero(renum[qm] >= 0).reshape(-1)
-        slots.append((r, members, renum[pm[r]], qrows, renum[qm[qrows]]))
-    margins = []
-
-    def evaluate(t_array):
-        """the members' eps combined per group, one copy of the rows per group [Nu] (the NaN guard is batch-wide)"""
-        margins.append(pair_margins(z[:, :nd], P[:, :nd], pm, qm, cfg['edge_cutoff']) * n_x)
-        eps = torch.empty_like(z)
-        reset = False
-        for r, members, pm_j, qrows, qm_j in slots:
-            eps[r], _ = ref_cpu.dynamics_forward(p, cfg, z[r], P[qrows], t_array[members], pm_j, qm_j)
-            reset = reset or (len(r) > 0 and not bool(eps[r][:, :nd].any()))
-        if reset:
-            eps[:, :nd] = 0.0
-        return gr.combine(eps, w)
-
-    z_steps, p_steps, op_energy, kind_v, other_v = [], [], [], [], []
-    clipped = unclipped = 0
-    for s in range(timesteps - 1, -1, -1):
-        s_array = torch.full((B, 1), fill_value=s)
-        t_array = s_array + 1
-        s_array = s_array / timesteps
-        t_array = t_array / timesteps
-        gamma_s = ref_cpu.gamma_lookup(table, s_array, T)
-        gamma_t = ref_cpu.gamma_lookup(table, t_array, T)
-        sigma2_ts, sigma_ts, alpha_ts = ref_cpu.sigma_and_alpha_t_given_s(gamma_t, gamma_s)
-        sigma_s, sigma_t = ref_cpu.sigma_of(gamma_s), ref_cpu.sigma_of(gamma_t)
-        ebar = evaluate(t_array)                                       # [Nu]
-        eps_t = spread(ebar)
-        mu = z / alpha_ts[pm] - (sigma2_ts / alpha_ts / sigma_t)[pm] * eps_t
-        sig = sigma_ts * sigma_s / sigma_t
-        alpha_t = ref_cpu.alpha_of(gamma_t)
-        E, vk, vo = torch.zeros(G), torch.zeros(4), 0.0
-        if any_touched:
-            z_u = report(z)                                            # the first member's copy of the latent
-            shift = (n_x * (ref_cpu.scatter_mean(P[:, :nd], qm, B) - com0))[first]                      # 2. the first member's
-            xhat = n_x * (z_u[:, :nd] - sigma_t[first][um] * ebar[:, :nd]) / alpha_t[first][um]         # 1.
-            q = n_x * P[:, :nd]
-            E, g, _, vk = energy_terms(xhat, q, shift, um, qg, rec, clash_r, clash_k)                   # 3. every member's atoms
-            if clash_r > 0:                                            # diagnostic only: does a member other than the first bite?
-                for k in range(G):
-                    pts, atoms = xhat[um == k], q[other & (qg == k)]
-                    if len(pts) and len(atoms):
-                        dist = _norm((pts[:, None, :] - atoms[None, :, :]).reshape(-1, 3))
-                        vo = max(vo, float(torch.clamp(clash_r - dist, min=0).max()))
-            var = (n_x * sig[first]) ** 2
-            d = -scale * var[um] * g                                   # 4.
-            length = _norm(d)
-            over = length > max_shift
-            d = torch.where(over[:, None], d * (max_shift / length.clamp(min=1e-30))[:, None], d)
-            active = touched[um] & (t_array[first][um][:, 0] <= guide_below) & (scale > 0)
-            clipped += int((over & active).sum())
-            unclipped += int((~over & active & (length > 0)).sum())
-            d_m, active_m = spread(d), spread(active)                  # every member's copy gets the same displacement
-            rows = torch.nonzero(active_m).reshape(-1)
-            if len(rows):
-                mu[rows, :nd] = mu[rows, :nd] + d_m[rows] / n_x        # 5.
-        op_energy.append(E)
-        kind_v.append(vk)
-        other_v.append(vo)
-        if checks:
-            ref_cpu.assert_mean_zero_with_mask(z[:, :nd], pm)
-        z, P = ref_cpu.sample_normal_zero_com(mu, P, sig, pm, qm, spread(draw(shape)), nd)
-        z_steps.append(report(z).clone())
-        p_steps.append(P[:, :nd].clone())
-
-    # decode, not guided: as ref_cpu.sample_given_pocket on the combined eps
-    t_zeros = torch.zeros((B, 1))
-    gamma_0 = ref_cpu.gamma_lookup(table, t_zeros, T)
-    sigma_x = torch.exp(-(-0.5 * gamma_0))
-    net_out = spread(evaluate(t_zeros))
-    sigma_0, alpha_0 = ref_cpu.sigma_of(gamma_0), ref_cpu.alpha_of(gamma_0)
-    mu_x = 1. / alpha_0[pm] * (z - sigma_0[pm] * net_out)
-    xh_phar, xh_pocket = ref_cpu.sample_normal_zero_com(mu_x, P, sigma_x, pm, qm, spread(draw(shape)), nd)
-    x_phar = xh_phar[:, :nd] * n_x
-    h_phar = torch.nn.functional.one_hot(torch.argmax(z[:, nd:] * nv[1] + nb[1], dim=1), pnf)
-    x_pocket = xh_pocket[:, :nd] * n_x
-    h_pocket = xh_pocket[:, nd:] * nv[1] + nb[1]
-    if checks:
-        ref_cpu.assert_mean_zero_with_mask(x_phar, pm)
-    if ref_cpu.scatter_add(x_phar, pm).abs().max().item() > 5e-2:                                # batch-wide
-        x_phar, x_pocket = ref_cpu.remove_mean_batch(x_phar, x_pocket, pm, qm)
-    # the diagnostics of the returned rows against every member's returned pocket: shift from the first member's returned pocket
-    shift = (ref_cpu.scatter_mean(x_pocket, qm, B) - n_x * com0)[first]
-    E_fin, _, v_fin, _ = energy_terms(report(x_phar), x_pocket, shift, um, qg, rec, clash_r, clash_k)
-    return dict(xh_phar=report(torch.cat([x_phar, h_phar.to(FLOAT)], dim=1)), xh_pocket=torch.cat([x_pocket, h_pocket], dim=1),
-                phar_mask=um, pocket_mask=qm, z_steps=torch.stack(z_steps), pocket_steps=torch.stack(p_steps), margins=np.stack(margins),
-                op_energy=torch.stack(op_energy), kind_violation=torch.stack(kind_v), energy=E_fin, max_violation=v_fin, clipped=clipped,
-                unclipped=unclipped, other_member_clash=np.asarray(other_v))
+    other_v = []
+    groups = dict(group_sizes=group_sizes, weights=weights)
+    guide = dict(rec=rec, clash_r=clash_r, clash_k=clash_k, scale=scale, max_shift=max_shift, guide_below=guide_below)
+    o = run_chain(p, cfg, pocket, num_nodes_phar=num_nodes_phar, groups=groups, guide=guide, timesteps=timesteps, noise=noise, checks=checks,
+                  probe=lambda op, a: other_v.append(other_member_clash(a, clash_r, cfg['norm_values'][0], cfg['n_dims'])))
+    o['other_member_clash'] = np.asarray(other_v)
+    return {k: o[k] for k in KEYS}
