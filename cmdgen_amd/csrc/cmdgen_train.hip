@@ -1,7 +1,7 @@
 // cmdgen_train.hip - the training step behind the C ABI: forward with saved activations,
 // backward to parameter gradients, AdamW(amsgrad) and the gradient norm, all on flat fp32 parameter / gradient
 // buffers owned by the caller (one contiguous bucket: a single RCCL all-reduce per step for data parallelism).
-// Conditional and joint (update_pocket_coords = 1) models.  Kernels: kernels_train.hip.
+// Conditional and joint (update_pocket_coords = 1) models.  Kernels: kernels_train_gemm.hip, kernels_train_dgrad.hip, kernels_train_adjoint.hip, kernels_train_repack.hip, kernels_train_loss.hip.
 #include "cmdgen_host.h"
 #include "cmdgen_launch.h"
 #include "cmdgen_train_kernels.h"

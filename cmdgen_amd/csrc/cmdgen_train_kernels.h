@@ -1,6 +1,6 @@
 // cmdgen_train_kernels.h - the interface between the training step's host side (cmdgen_train.hip) and its kernels
-// (kernels_train.hip): the table structs the host fills and a kernel indexes with tab[blockIdx], the launchers with their default
-// arguments, the scratch-size helpers and the launch tuning.  Both files include this header, so each struct and each default is
+// (kernels_train_gemm.hip, kernels_train_dgrad.hip, kernels_train_adjoint.hip, kernels_train_repack.hip, kernels_train_loss.hip): the table structs the host fills and a kernel indexes with tab[blockIdx], the launchers with their default
+// arguments, the scratch-size helpers and the launch tuning.  Both sides include this header, so each struct and each default is
 // written exactly once.  Declarations only: nothing here beyond cmdgen_dev.h's types.
 #pragma once
 #include "cmdgen_dev.h"
@@ -50,13 +50,11 @@ void tr_reduce_pair(int E, int H, const float* scratch_a, float* out_w, float* o
 void tr_gate_bwd(int E, int H, const int* row, const float* pre2, const float* wa, const float* z, int attention, const float* dagg,
                  float* dpre2, float* scratch, float* d_wa, float* d_ba, float* zero, size_t zero_floats, hipStream_t s,
                  bool defer_reduce = false);
-// the inputs of k_coord_out_bwd, for the form of k_head_bwd that computes dphi (and writes dcd) itself: one launch less per block
+// the inputs of coord_out_edge (cmdgen_train_parts.h), for the form of k_head_bwd that computes dphi (and writes dcd) itself: one launch less per block
 struct CoordOutArgs { const int* row; const int* col; const float4* X; const float* phi; int use_tanh; float range, norm_constant;
                       const float* dacc; float dacc_div; const float* adiv; float4* dcd_out; };
 void tr_head_bwd(int E, int H, const float* dphi, const float* w5, const float* pre7, float* dpre7, float* scratch, float* d_w5,
                  float* zero, size_t zero_floats, hipStream_t s, bool defer_reduce = false, const CoordOutArgs* co = nullptr);
-void tr_coord_out_bwd(int E, const int* row, const int* col, const float4* X, const float* phi, int use_tanh, float range,
-                      float nc, const float* dacc, float dacc_div, int n_moving, float* dphi, float4* dcd, hipStream_t s, const float* adiv = nullptr);
 void tr_edge_tail_bwd(int E, int H, const int* row, const int* col, const float* g, const float* d0, const float* Wcol, int ldw,
                       const float4* X, float nc, const float4* dcd, int n_moving, float* dP, float* dQ, float* dWcol, float* dX,
                       float* scratch, hipStream_t s, const float* Wd = nullptr, float* dd0 = nullptr);

@@ -1,6 +1,6 @@
 // cmdgen_train_plan.h - the launch planner of the training step's GEMMs: which weight-gradient kernel runs a group of products, on which grid and
 // split-K factor; the k tile, grid and split-K of the plain training GEMM; the rows per tile of the data-gradient kernel.  Pure functions of
-// the shapes, the precision and the handle's tuning (TrainTune).  Plain C++17, no HIP: the launchers of kernels_train.hip compute their plan
+// the shapes, the precision and the handle's tuning (TrainTune).  Plain C++17, no HIP: the launchers of kernels_train_gemm.hip and kernels_train_dgrad.hip compute their plan
 // and dispatch on it, and tests/train_plan_check.cpp runs the planners on the CPU.
 #pragma once
 

@@ -1,6 +1,6 @@
 // cmdgen_wlayout.h - the MFMA fragment orders of a packed Linear weight (WPack, cmdgen_dev.h), each written once: the host packs
 // the sampler's weights with these maps (cmdgen_api.hip), the training step re-packs its parameters on the device with the same
-// maps (kernels_train.hip), and the same tile kernels read both.
+// maps (kernels_train_repack.hip), and the same tile kernels read both.
 //
 // A weight W[out][in] (nn.Linear layout, in a multiple of KBLK) is cut into n-tiles of ROWS output rows and k-blocks of KBLK
 // inputs.  Fragment (nt, kb) is 64 lanes x PER values; lane l holds, of row ROWS nt + l % ROWS, the values k0 + koff(j), j < PER,

@@ -967,6 +967,92 @@ def test_training_step_options_leave_the_gradient_where_it_is(opts):
         assert float((a - b).abs().max()) <= GRAD_TOL * max(float(a.abs().max()), 1e-6), (name, opts)
 
 
+def _assert_lists_exercise_the_tail(h, n_phar):
+    """Both edge lists of the handle's last training forward: a ragged last workgroup (32 edges each), at least three workgroups, and a
+    receiver's run longer than a wave's eight edges.  The last by counting: the coordinate list's receivers are the pharmacophore rows, so
+    more than eight edges per row means one row has more than eight - and the message list holds the same row's edges plus its self loop."""
+    E, Ec = h.query('train_edges'), h.query('train_coord_edges')
+    print('message edges %d, coordinate edges %d, phar rows %d' % (E, Ec, n_phar))
+    assert E % 32 != 0 and Ec % 32 != 0, (E, Ec)
+    assert E > 64 and Ec > 64, (E, Ec)
+    assert Ec > 8 * n_phar and E > Ec, (E, Ec, n_phar)
+
+
+def test_unfused_edge_tail_agrees_with_the_fused_one_at_width_256():
+    """dgrad_tail = 0 (k_dgrad_split + k_edge_tail_bwd at width 256) against the default k_dgrad_tail on three ragged complexes, one layer,
+    attention and tanh on: the parameter gradient of loss_and_grad and - through the differentiable module, the INP forms of both kernels -
+    the weight and input gradients of cmdgen_train_backward_inputs, tensor by tensor to GRAD_TOL of the tensor's scale.  Both paths add
+    with float atomics in their own order; they share every other kernel of the step.  (Largest difference observed: 0.7 % of the bound.)"""
+    import importlib.util, os
+    from argparse import Namespace
+    from cmdgen_amd.lightning_modules import PharPocketDDPM
+    from cmdgen_amd.training import HipTrainer
+    from test_hip_autograd import case, make_module, hip_grads
+    spec = importlib.util.spec_from_file_location('bench_train', os.path.join(os.path.dirname(__file__), '..', 'tools', 'bench_train.py'))
+    bt = importlib.util.module_from_spec(spec); spec.loader.exec_module(bt)
+    B, L = 3, 1
+    cfg = ModelConfig(n_layers=L)
+    hp = dict(outdir='out', dataset='crossdock', datadir='data', batch_size=B, lr=1e-3,
+              egnn_params=Namespace(device='cuda', edge_cutoff=6.0, joint_nf=32, hidden_nf=256, n_layers=L, attention=True, tanh=True,
+                                    norm_constant=1, inv_sublayers=1, sin_embedding=False, aggregation_method='sum', normalization_factor=100),
+              diffusion_params=Namespace(diffusion_steps=500, diffusion_noise_schedule='polynomial_2', diffusion_noise_precision=1e-5,
+                                         diffusion_loss_type='l2', normalize_factors=[1, 4]),
+              num_workers=0, augment_noise=0, augment_rotation=False, clip_grad=True, eval_epochs=50,
+              eval_params=Namespace(n_eval_samples=100, eval_batch_size=100), mode='pocket_conditioning',
+              node_histogram=np.ones((30, 500)), pocket_representation='CA')
+    model = PharPocketDDPM(**hp)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in make_state_dict(cfg, seed=0).items()}, strict=True)
+    tr = HipTrainer(model.cuda())
+    batch = bt.synthetic_batch(B, 7300, torch.device('cuda', 0))
+    gen = torch.Generator().manual_seed(14)
+    t_int = torch.randint(0, 501, (B, 1), generator=gen).float()
+    n_phar = int(batch['num_phar_atoms'].sum())
+    eps = [torch.randn((n_phar, 11), generator=gen).cuda()]
+    worst = 0.0
+
+    def same(a, b, what):
+        nonlocal worst
+        err, scale = float((a - b).abs().max()), max(float(a.abs().max()), 1e-6)
+        worst = max(worst, err / (GRAD_TOL * scale))
+        assert err <= GRAD_TOL * scale, (what, err, scale)
+
+    loss_a, _, _ = tr.loss_and_grad(batch, t_int=t_int, eps=eps)
+    grad_a = tr.grad.clone()
+    _assert_lists_exercise_the_tail(tr.h, n_phar)
+    tr.h.set_option('dgrad_tail', 0)
+    loss_b, _, _ = tr.loss_and_grad(batch, t_int=t_int, eps=eps)
+    grad_b = tr.grad.clone()
+    assert abs(float(loss_a) - float(loss_b)) <= 2e-6 * max(1.0, abs(float(loss_a)))
+    for name, p in tr.dyn.named_parameters():
+        off, cnt = tr.h.param_offset(name)
+        same(grad_a[off:off + cnt], grad_b[off:off + cnt], name)
+    print('parameter pass: largest difference / bound %.3f' % worst)
+
+    # the input pass (k_dgrad_tail<., true> against k_edge_tail_bwd<true>)
+    cfg, sd, inp, g, gq = case(256, L, B, 77)
+    dyn = make_module(cfg, sd)
+    _, gi_a, gp_a = hip_grads(dyn, inp, g, gq, False)
+    h = dyn.hip_handle()
+    _assert_lists_exercise_the_tail(h, len(inp['mask_phar']))
+    # here the positions are the inputs, so the lists can be counted: the radius graph of each sample (self loops kept: the message list, every
+    # node a receiver; self loops dropped, pharmacophore receivers: the coordinate list).  The counts must be the device's, and the longest run
+    # of one receiver - its degree, the lists are sorted by receiver - longer than a wave's eight edges in both.
+    x = np.concatenate([inp['xh_phar'][:, :3], inp['xh_pocket'][:, :3]]).astype(np.float64)
+    m = np.concatenate([inp['mask_phar'], inp['mask_pocket']])
+    adj = (m[:, None] == m[None, :]) & (((x[:, None, :] - x[None, :, :]) ** 2).sum(-1) <= cfg.edge_cutoff ** 2)
+    deg_msg, deg_coord = adj.sum(1), adj[:len(inp['mask_phar'])].sum(1) - 1
+    assert (int(deg_msg.sum()), int(deg_coord.sum())) == (h.query('train_edges'), h.query('train_coord_edges'))
+    assert deg_msg.max() > 8 and deg_coord.max() > 8, (deg_msg.max(), deg_coord.max())
+    h.set_option('dgrad_tail', 0)
+    _, gi_b, gp_b = hip_grads(dyn, inp, g, gq, False)
+    for k in ('xh_phar', 'xh_pocket', 't'):
+        same(gi_a[k], gi_b[k], k)
+    for k, v in gp_a.items():
+        if v is not None:
+            same(v, gp_b[k], k)
+    print('with the input pass: largest difference / bound %.3f' % worst)
+
+
 # ------------------------------------------------------------------ round 6: the big-list kernels against the ORACLE, the half engine's range, re-pack hygiene
 def _bench_trainer(B, pipelined=False, sd_edit=None, lr=1e-3):
     """PharPocketDDPM (shipped hyper-parameters, seeded weights) + HipTrainer + one synthetic batch of B ragged C-alpha complexes (tools/bench_train.py)."""

@@ -14,7 +14,7 @@ static int host_rule(float mx) {        // cmdgen_api.hip, pack_half, before the
     if (mx > 0.f && std::isfinite(mx)) { int ex; std::frexp(mx, &ex); e = 12 - ex; }
     return std::max(-40, std::min(40, e));
 }
-static int device_rule(float mx) {      // kernels_train.hip, k_repack_half / k_wmax16, before the rules were merged
+static int device_rule(float mx) {      // kernels_train_repack.hip, k_repack_half / k_wmax16, before the rules were merged
     uint32_t u; memcpy(&u, &mx, 4);
     int e = 0;
     if (mx > 0.f && mx < 3.0e38f) e = 12 - ((int)((u >> 23) & 0xffu) - 126);

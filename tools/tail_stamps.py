@@ -1,5 +1,5 @@
 """Per-phase cycle stamps of k_dgrad_tail<3> over training steps (diagnostic build:
-FILE=kernels_train.hip tools/build_variant.sh tailst -DCMDGEN_TAIL_STAMPS=1; CMDGEN_LIB=build/libcmdgen_hip_tailst.so).
+FILE=kernels_train_dgrad.hip tools/build_variant.sh tailst -DCMDGEN_TAIL_STAMPS=1; CMDGEN_LIB=build/libcmdgen_hip_tailst.so).
 Every 4th workgroup reports; both lists (coordinate and message) of every block are summed.  usage: python tools/tail_stamps.py [B] [steps]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
