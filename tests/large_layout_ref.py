@@ -10,9 +10,9 @@ same sample as in the batch.  Phar points as test_hip_train.case_inputs places t
 Margins.  The radius graph is a hard threshold; at 300-400 nodes a sample has 45-80 thousand pairs and about one per sample and
 evaluation lies within 1e-4 A of the cutoff, so the CA tests' "margin > 2e-3" searches cannot succeed here.  Instead:
   single evaluations   first_index chosen so that EVERY sample's margin >= rule_sweep_ref.MARGIN (1e-4); no sample is left out
-  score                an entry (level, sample) inside test_score_cpu.BAND (1e-4) is left out, at most 2 % of a case; the committed
+  score                an entry (level, sample) inside helpers.SCORE_BAND (1e-4) is left out, at most 2 % of a case; the committed
                        noise seed leaves none out on the oracle
-  chains               a sample is left out from the first evaluation at which one of its pairs is within test_hip_parity_r3.BAND (2e-5 A)
+  chains               a sample is left out from the first evaluation at which one of its pairs is within helpers.CHAIN_BAND (2e-5 A)
                        of the cutoff; at most CHAIN_CAP of the samples (one of five); the committed seeds leave none out on the oracle
 The constants below are what the searches at the bottom returned; a test never trusts them: it recomputes the margins with
 RecordedEdges round the oracle's run (test_large_layout_cpu.py asserts the conditions, the GPU tests derive `kept` from them)."""
@@ -26,8 +26,7 @@ from helpers import JointNoiseTape
 from oracle import ref_cpu
 from cmdgen_amd.synthetic import ModelConfig, PocketBatch, make_pockets, make_state_dict
 from rule_sweep_ref import MARGIN, CHAIN_CAP, CUTOFF
-from test_score_cpu import BAND as SCORE_BAND
-from test_hip_parity_r3 import BAND as CHAIN_BAND
+from helpers import CHAIN_BAND, SCORE_BAND
 
 # (pocket nodes, phar points); None: ragged full-atom, 250-450 atoms
 SAMPLES = [(119, 9), (120, 9), (None, 15), (300, 70), (257, 1)]

@@ -5,28 +5,13 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import load_golden, cases_of, cfg_from_meta, NoiseTape
+from helpers import (NoiseTape, bare_inputs as _inputs, bare_model as _model, cases_of, g20, g20_oracle_case as g20_case,
+                     pocket_dict as pocket_of)
 from cond_inpaint_ref import cond_inpaint, inpaint_plan
 from oracle import ref_cpu
-from cmdgen_amd.synthetic import make_state_dict, make_pockets
+from cmdgen_amd.synthetic import make_pockets
 
-G20 = load_golden('g20_cond_inpaint.npz')
-
-
-def g20_case(name):
-    """-> cfg, oracle params, pocket batch, phar dict, fixed mask, (K, resamplings, jump_length)."""
-    H, L, B, R, seed, K, r, j, first = [int(v) for v in G20[name + '/meta']]
-    cfg = cfg_from_meta(H, L, R)
-    p = ref_cpu.to_torch_params(make_state_dict(cfg, seed=seed, coord_gain=1.0))
-    pb = make_pockets(B, 'CA', ragged=True, n_phar=7, first_index=first)
-    phar = {'x': torch.from_numpy(G20[name + '/phar_x']), 'one_hot': torch.from_numpy(G20[name + '/phar_one_hot']),
-            'size': torch.from_numpy(pb.num_nodes_phar), 'mask': torch.from_numpy(np.repeat(np.arange(B), pb.num_nodes_phar))}
-    return cfg, p, pb, phar, G20[name + '/phar_fixed'], (K, r, j)
-
-
-def pocket_of(pb):
-    return {'x': torch.from_numpy(pb.x), 'one_hot': torch.from_numpy(pb.one_hot), 'size': torch.from_numpy(pb.size),
-            'mask': torch.from_numpy(pb.mask)}
+G20 = g20()
 
 
 def test_g20_covers_the_specified_cases():
@@ -99,20 +84,6 @@ def test_plan_counts(K, r, j):
         assert n_steps == K                              # no resampling: every step once
     # ops = K steps down plus jump_length steps again for every jump back
     assert n_steps == K + n_jumps * j
-
-
-def _model(cls):
-    from cmdgen_amd.equivariant_diffusion.dynamics import EGNNDynamics
-    dyn = EGNNDynamics(phar_nf=8, residue_nf=20, n_dims=3, joint_nf=16, hidden_nf=64, n_layers=1, update_pocket_coords=False)
-    return cls(dynamics=dyn, phar_nf=8, residue_nf=20, n_dims=3, timesteps=50, noise_schedule='polynomial_2',
-               noise_precision=1e-5, loss_type='l2', norm_values=[1, 4], size_histogram=np.ones((30, 70)))
-
-
-def _inputs():
-    phar = {'x': torch.zeros(5, 3), 'one_hot': torch.zeros(5, 8), 'size': torch.tensor([2, 3]), 'mask': torch.tensor([0, 0, 1, 1, 1])}
-    pocket = {'x': torch.randn(7, 3), 'one_hot': torch.zeros(7, 20), 'size': torch.tensor([3, 4]),
-              'mask': torch.tensor([0, 0, 0, 1, 1, 1, 1])}
-    return phar, pocket
 
 
 def test_argument_checks_without_a_device():

@@ -8,7 +8,7 @@ import torch
 from helpers import load_golden, cases_of, cfg_from_meta, NoiseTape
 from cond_inpaint_ref import cond_inpaint, inpaint_plan
 from edit_ref import cond_edit, edit_plan
-from test_cond_inpaint_cpu import g20_case, pocket_of, _model, _inputs
+from helpers import bare_inputs as _inputs, bare_model as _model, g20, g20_oracle_case as g20_case, pocket_dict as pocket_of
 from oracle import ref_cpu
 from cmdgen_amd.synthetic import make_state_dict, make_pockets
 
@@ -97,7 +97,7 @@ def test_held_parts_of_g22_come_out_as_given():
 def test_equal_masks_from_the_prior_equal_the_inpainting_model_bit_for_bit(name):
     cfg, p, pb, phar, fixed, (K, r, j) = g20_case(name)
     assert (r, j) in {(1, 1), (2, 1), (3, 2)}
-    from test_cond_inpaint_cpu import G20
+    G20 = g20()
     noise = G20[name + '/noise']
     with torch.no_grad():
         a = cond_edit(p, cfg.as_dict(), phar, pocket_of(pb), fixed, fixed, K, r, j, K, noise=NoiseTape(noise), return_steps=True)
@@ -156,7 +156,7 @@ def test_edit_phars_builds_the_masks_and_keeps_the_row_order():
     import os
     from helpers import GOLDEN
     from cmdgen_amd.lightning_modules import PharPocketDDPM
-    from test_oracle_golden_r2 import _hparams
+    from helpers import _hparams
     model = PharPocketDDPM(**_hparams('CA', 64, 2))
     names = list(model.dataset_info['phar_decoder'])
     pdb, ids = os.path.join(GOLDEN, 'g7_pocket.pdb'), [f'A:{i}' for i in range(1, 30)]

@@ -100,7 +100,7 @@ def test_hip_dynamics_forward_g16(name, opts, engine):
 @pytest.mark.parametrize('name', CHAINS)
 def test_hip_chain_g16(name, use_graph):
     hip_backend, dev = _gpu()
-    from test_hip_parity_r2 import host_step_table
+    from helpers import host_step_table
     cfg, sd, pb, K = chain_case(name)
     h = hip_backend.Handle(cfg.as_dict(), 0)
     h.load_state_dict(sd)
@@ -306,7 +306,7 @@ def test_hip_sin_embedding_g18(name, mt):
 @pytest.mark.parametrize('use_graph', [False, True])
 def test_hip_sin_embedding_chain_g18(use_graph):
     hip_backend, dev = _gpu()
-    from test_hip_parity_r2 import host_step_table
+    from helpers import host_step_table
     cfg, sd, pb, K = sin_chain_case()
     h = hip_backend.Handle(cfg.as_dict(), 0)
     h.load_state_dict(sd)

@@ -7,21 +7,12 @@ small loses accuracy against its own result, the more the smaller they are.  The
 and runs them on the bf16 split engine; this test restates the split in numpy and checks that rows at or above the threshold stay well
 inside the evaluation tolerance and that rows far below it do not.
 """
-import os
-import re
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from helpers import tau_from_header
+
 K = 256
-EVAL_TOL = 2e-5          # the evaluation tolerance of the GPU tests (test_hip_parity_r2.EVAL_TOL)
-
-
-def tau_from_header():
-    text = open(os.path.join(ROOT, 'cmdgen_amd', 'csrc', 'cmdgen_split.h')).read()
-    m = re.search(r'#define\s+HALF_LOW_TAU\s+([0-9.eE+-]+)f', text)
-    assert m, 'HALF_LOW_TAU not found in cmdgen_split.h'
-    return float(m.group(1))
+EVAL_TOL = 2e-5          # the evaluation tolerance of the GPU tests (helpers.EVAL_TOL)
 
 
 def half_pieces(x):

@@ -9,85 +9,11 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import load_golden, dynamics_case
-from oracle import ref_cpu
-from cmdgen_amd.synthetic import ModelConfig, make_state_dict
-from test_hip_train import GRAD_TOL, case_inputs, build_trainer, dev
+from helpers import (GRAD_TOL, assert_close, autograd_case as case, build_trainer, check_against_oracle, dev, hip_grads, make_module, npy,
+                     oracle_grads)
 
 pytestmark = pytest.mark.gpu
 SAME_TOL = 2e-5
-
-
-def make_module(cfg, sd):
-    from cmdgen_amd.equivariant_diffusion.dynamics import EGNNDynamics
-    c = cfg.as_dict()
-    dyn = EGNNDynamics(phar_nf=c['phar_nf'], residue_nf=c['residue_nf'], n_dims=3, joint_nf=c['joint_nf'], hidden_nf=c['hidden_nf'],
-                       n_layers=c['n_layers'], attention=c['attention'], tanh=c['tanh'], norm_constant=c['norm_constant'],
-                       inv_sublayers=c.get('inv_sublayers', 1), sin_embedding=False, normalization_factor=c['normalization_factor'],
-                       aggregation_method=c.get('aggregation_method', 'sum'), update_pocket_coords=c['update_pocket_coords'],
-                       edge_cutoff=c['edge_cutoff'], condition_time=c['condition_time'])
-    state = {k[len('ddpm.dynamics.'):]: torch.from_numpy(np.asarray(v)) for k, v in sd.items() if k.startswith('ddpm.dynamics.')}
-    dyn.load_state_dict(state)
-    return dyn.cuda()
-
-
-def case(H, L, B, seed, **kw):
-    cfg = ModelConfig(hidden_nf=H, n_layers=L, **kw)
-    sd = make_state_dict(cfg, seed=seed, coord_gain=1.0)
-    rng = np.random.Generator(np.random.PCG64(seed))
-    pb, pm, xh_phar, xh_pocket, t = case_inputs(cfg, B, 700000 + seed, rng)
-    g = rng.normal(size=xh_phar.shape).astype(np.float32)
-    gq = rng.normal(size=xh_pocket.shape).astype(np.float32)
-    return cfg, sd, dict(xh_phar=xh_phar, xh_pocket=xh_pocket, t=t, mask_phar=pm.astype(np.int64), mask_pocket=pb.mask.astype(np.int64)), g, gq
-
-
-def hip_grads(dyn, inp, g, gq, with_pocket):
-    """autograd through the module in differentiable mode -> (eps, {input: grad}, {param name: grad})"""
-    dyn.set_differentiable(True)
-    xp, xq, t = (dev(inp[k]).requires_grad_(True) for k in ('xh_phar', 'xh_pocket', 't'))
-    eps, eps_q = dyn(xp, xq, t, dev(inp['mask_phar']), dev(inp['mask_pocket']))
-    assert eps.grad_fn is not None
-    loss = (eps * dev(g)).sum() + ((eps_q * dev(gq)).sum() if with_pocket else 0.0)
-    names = [n for n, _ in dyn.named_parameters()]
-    gr = torch.autograd.grad(loss, [xp, xq, t] + list(dyn.parameters()), allow_unused=True)
-    return eps.detach(), dict(zip(('xh_phar', 'xh_pocket', 't'), gr[:3])), dict(zip(names, gr[3:]))
-
-
-def oracle_grads(cfg, sd, inp, g, gq, with_pocket):
-    p = ref_cpu.to_torch_params(sd)
-    leaves = {k: v.clone().requires_grad_(True) for k, v in p.items() if k.startswith('dynamics.')}
-    p2 = dict(p); p2.update(leaves)
-    xs = {k: torch.from_numpy(inp[k].copy()).requires_grad_(True) for k in ('xh_phar', 'xh_pocket', 't')}
-    eps, eps_q = ref_cpu.dynamics_forward(p2, cfg.as_dict(), xs['xh_phar'], xs['xh_pocket'], xs['t'],
-                                          torch.from_numpy(inp['mask_phar']), torch.from_numpy(inp['mask_pocket']))
-    loss = (eps * torch.from_numpy(g)).sum() + ((eps_q * torch.from_numpy(gq)).sum() if with_pocket else 0.0)
-    loss.backward()
-    return eps.detach(), {k: v.grad for k, v in xs.items()}, {k[len('dynamics.'):]: v.grad for k, v in leaves.items()}
-
-
-def assert_close(got, want, tol, what):
-    want = np.zeros_like(got) if want is None else np.asarray(want, dtype=np.float64)
-    scale = max(float(np.abs(want).max()), 1e-6)
-    err = float(np.abs(np.asarray(got, dtype=np.float64) - want).max())
-    assert err <= tol * scale, (what, err, scale)
-
-
-def npy(x):
-    return None if x is None else x.detach().cpu().numpy()
-
-
-def check_against_oracle(cfg, sd, inp, g, gq, with_pocket, dyn=None, inputs=True):
-    dyn = make_module(cfg, sd) if dyn is None else dyn
-    eps, gi, gp = hip_grads(dyn, inp, g, gq, with_pocket)
-    want_eps, wi, wp = oracle_grads(cfg, sd, inp, g, gq, with_pocket)
-    assert np.abs(npy(eps) - want_eps.numpy()).max() <= 2e-5 * max(1.0, float(want_eps.abs().max()))
-    for k, v in gp.items():
-        assert_close(npy(v), npy(wp[k]), GRAD_TOL, k)
-    if inputs:
-        for k in ('xh_phar', 'xh_pocket', 't'):
-            assert_close(npy(gi[k]), npy(wi[k]), GRAD_TOL, k)
-        assert float(gi['xh_pocket'][:, :3].abs().max()) > 0          # static pocket rows carry a position gradient too
-    return dyn, gi, gp
 
 
 # ------------------------------------------------------------------ 1 + 2: weights and inputs against the oracle
@@ -344,7 +270,7 @@ def test_switch_off_leaves_the_plain_evaluation():
 
 # ------------------------------------------------------------------ 6: the half engine's range guard
 def test_half_overflow_case_warns_and_equals_the_split_engine():
-    from test_hip_half_range import overflow_case
+    from helpers import overflow_case
     cfg, sd, inp = overflow_case('msg')
     rng = np.random.Generator(np.random.PCG64(9))
     g = rng.normal(size=inp['xh_phar'].shape).astype(np.float32)

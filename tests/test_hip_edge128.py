@@ -12,7 +12,8 @@ import torch
 from helpers import load_golden, cases_of, dynamics_case, rms, bounded_case
 from cmdgen_amd import hip_backend
 from cmdgen_amd.synthetic import ModelConfig, make_state_dict, make_pockets
-from test_hip_parity_r2 import dev, new_handle, host_step_table, EVAL_TOL
+from chain_kit import dev
+from helpers import EVAL_TOL, host_step_table, new_handle
 
 pytestmark = pytest.mark.gpu
 

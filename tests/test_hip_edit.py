@@ -6,6 +6,7 @@ PharPocketDDPM.edit_phars.
 Tolerances are those of test_hip_inpaint.py for G20: coordinate RMS <= 1e-4 * max(1, max|x|), types exact, per-op z and pocket
 max-abs <= 1e-4 * max(1, max|.|) (every G22 fixture keeps its pairs >= 2e-3 A away from the cutoff); reductions bit for bit."""
 import os
+from functools import partial
 
 import numpy as np
 import pytest
@@ -13,7 +14,7 @@ import torch
 
 from helpers import load_golden, cases_of, cfg_from_meta, rms, GOLDEN
 from edit_ref import edit_plan
-from test_hip_inpaint import dev, handle_for, model_for, pocket_dict, run_inpaint, _fixed_inputs
+from chain_kit import dev, fixed_inputs, handle_for, lightning_model, model_for, pocket_dev, run_chain, same, PLAIN
 from cmdgen_amd import hip_backend
 from cmdgen_amd.synthetic import ModelConfig, make_state_dict, make_pockets
 from bench import bounded_config
@@ -21,6 +22,7 @@ from bench import bounded_config
 pytestmark = pytest.mark.gpu
 
 G22 = load_golden('g22_edit.npz')
+run = partial(run_chain, tables=False, want_steps=False)          # as test_hip_inpaint.py
 
 
 def g22_case(name):
@@ -31,14 +33,8 @@ def g22_case(name):
     return cfg, sd, pb, (K, start, r, j)
 
 
-def run_edit(h, pb, phar_x, phar_oh, fix_x, fix_h, K, start=None, r=1, j=1, noise=None, seed=7, ids=None, use_graph=True,
-             want_steps=False):
-    h.set_layout(pb.num_nodes_phar, pb.size)
-    out = h.edit_chain(dev(pb.x), dev(pb.one_hot), dev(phar_x), dev(phar_oh), dev(np.asarray(fix_x, np.float32)),
-                       dev(np.asarray(fix_h, np.float32)), K, start=start, resamplings=r, jump_length=j, noise=noise, seed=seed,
-                       pocket_ids=ids, use_graph=use_graph, want_steps=want_steps)
-    st = h.chain_status()
-    return [o.cpu().numpy() if o is not None else None for o in out], st
+def run_edit(h, pb, phar_x, phar_oh, fix_x, fix_h, K, start=None, r=1, j=1, **kw):
+    return run(h, pb, K, given=(phar_x, phar_oh, fix_x, fix_h), plan=(start, r, j), **kw)
 
 
 @pytest.mark.parametrize('use_graph', [True, False])
@@ -49,10 +45,9 @@ def test_edit_chain_matches_g22(name, use_graph):
     noise = dev(G22[name + '/noise'])
     h.set_layout(pb.num_nodes_phar, pb.size)
     assert h.edit_plan(K, start, r, j) == edit_plan(r, j, K, start)[:2]
-    (xh_phar, xh_pocket, z_steps), st = run_edit(h, pb, G22[name + '/phar_x'], G22[name + '/phar_one_hot'], G22[name + '/fix_x'],
-                                                 G22[name + '/fix_h'], K, start, r, j, noise=noise, use_graph=use_graph,
-                                                 want_steps=True)
-    p_steps = h.last_pocket_steps.cpu().numpy()
+    (xh_phar, xh_pocket, z_steps, p_steps, *_), st = run_edit(h, pb, G22[name + '/phar_x'], G22[name + '/phar_one_hot'], G22[name + '/fix_x'],
+                                                              G22[name + '/fix_h'], K, start, r, j, noise=noise, use_graph=use_graph,
+                                                              want_steps=True)
     want = G22[name + '/xh_phar']
     e = rms(xh_phar[:, :3], want[:, :3])
     print(name, 'graph' if use_graph else 'eager', 'x rms', e, 'scale', float(np.abs(want[:, :3]).max()))
@@ -114,7 +109,7 @@ def test_equal_masks_from_the_prior_equal_inpaint_chain_bit_for_bit(use_graph, s
         h.set_option('coord_mt', 64)
         h.set_layout(pb.num_nodes_phar, pb.size)
         assert h.query('edge_mt') == 64 and h.query('coord_mt') == 64
-    px, poh, fixed, _ = _fixed_inputs(pb, 0.25, np.random.default_rng(8))
+    px, poh, fixed, _ = fixed_inputs(pb, 0.25, np.random.default_rng(8))
     fixed[np.repeat(np.arange(6), pb.num_nodes_phar) == 3] = 0.0          # one sample without a mark
     nl = int(pb.num_nodes_phar.sum())
     K = 20
@@ -123,16 +118,13 @@ def test_equal_masks_from_the_prior_equal_inpaint_chain_bit_for_bit(use_graph, s
         n_draws = h.inpaint_plan(K, r, j)[1]
         noise = dev(np.random.default_rng(9).normal(size=(n_draws, nl, 3 + cfg.phar_nf)).astype(np.float32))
         for inject in (None, noise):
-            (xa, qa, za), sa = run_inpaint(h, pb, px, poh, fixed, K, r, j, noise=inject, seed=11, use_graph=use_graph, want_steps=True)
-            pa = h.last_pocket_steps.cpu().numpy()
-            (xb, qb, zb), sb = run_edit(h, pb, px, poh, fixed, fixed, K, K, r, j, noise=inject, seed=11, use_graph=use_graph,
-                                        want_steps=True)
-            pb_steps = h.last_pocket_steps.cpu().numpy()
-            assert np.array_equal(xa, xb) and np.array_equal(qa, qb) and np.array_equal(za, zb) and np.array_equal(pa, pb_steps)
+            a, sa = run(h, pb, K, given=(px, poh, fixed), plan=(None, r, j), noise=inject, seed=11, use_graph=use_graph, want_steps=True)
+            b, sb = run_edit(h, pb, px, poh, fixed, fixed, K, K, r, j, noise=inject, seed=11, use_graph=use_graph, want_steps=True)
+            same(a, b, PLAIN)
             assert sa == sb
             assert sb['max_rel_com_error'] < 1e-2
             if not split:
-                deg = _max_degree(h, pb, za, pa)
+                deg = _max_degree(h, pb, a.z_steps, a.pocket_steps)
                 print('fp32 engine, r, j =', r, j, 'max edges per receiver over the saved states:', deg)
                 assert deg <= 65
     h.close()
@@ -146,7 +138,7 @@ def test_graph_runs_equal_eager_runs_as_start_seed_and_steps_change():
     h = hip_backend.Handle(cfg.as_dict(), 0)
     h.load_state_dict(make_state_dict(cfg, seed=0))
     pb = make_pockets(5, 'CA', ragged=True, first_index=500)
-    px, poh, fixed, pm = _fixed_inputs(pb, 0.5, np.random.default_rng(5))
+    px, poh, fixed, pm = fixed_inputs(pb, 0.5, np.random.default_rng(5))
     fix_x = fixed * (np.arange(len(fixed)) % 2 == 0)
     fix_h = fixed * (np.arange(len(fixed)) % 3 != 0)
     K = 17
@@ -186,10 +178,10 @@ def test_types_hold_and_coordinates_hold():
     cfg = ModelConfig(timesteps=500)
     h = handle_for(cfg, 'seed0', make_state_dict(cfg, seed=0))
     pb = make_pockets(64, 'CA', ragged=True, first_index=1000)
-    px, poh, marked, pm = _fixed_inputs(pb, 0.25, np.random.default_rng(1))
+    px, poh, marked, pm = fixed_inputs(pb, 0.25, np.random.default_rng(1))
     types_only = (marked != 0) & (pm % 2 == 0)
     coords_only = (marked != 0) & (pm % 2 == 1)
-    (xh_phar, xh_pocket, _), st = run_edit(h, pb, px, poh, coords_only, types_only, 100, seed=21)
+    (xh_phar, xh_pocket, *_), st = run_edit(h, pb, px, poh, coords_only, types_only, 100, seed=21)
     assert st['max_rel_com_error'] < 1e-2 and st['nan_resets'] == 0
     assert np.array_equal(xh_phar[types_only, 3:], poh[types_only])
     B = len(pb.size)
@@ -209,14 +201,14 @@ def test_shards_reproduce_the_full_batch():
     h = handle_for(cfg, 'seed0', make_state_dict(cfg, seed=0))
     K, start = 8, 5
     full = make_pockets(8, 'CA', ragged=True)
-    px, poh, marked, pm = _fixed_inputs(full, 0.25, np.random.default_rng(3))
+    px, poh, marked, pm = fixed_inputs(full, 0.25, np.random.default_rng(3))
     fx, fh = marked * (pm % 2 == 1), marked * (pm % 2 == 0)
-    (xf, _, _), _ = run_edit(h, full, px, poh, fx, fh, K, start, 2, 1, ids=full.pocket_index)
+    (xf, *_), _ = run_edit(h, full, px, poh, fx, fh, K, start, 2, 1, ids=full.pocket_index)
     parts = []
     for first in (0, 4):
         sub = make_pockets(4, 'CA', ragged=True, first_index=first)
         rows = np.isin(pm, np.arange(first, first + 4))
-        (xs, _, _), _ = run_edit(h, sub, px[rows], poh[rows], fx[rows], fh[rows], K, start, 2, 1, ids=sub.pocket_index)
+        (xs, *_), _ = run_edit(h, sub, px[rows], poh[rows], fx[rows], fh[rows], K, start, 2, 1, ids=sub.pocket_index)
         parts.append(xs)
     xs = np.concatenate(parts)
     assert np.abs(xs[:, :3] - xf[:, :3]).max() <= 1e-4 * max(1.0, np.abs(xf[:, :3]).max())
@@ -226,7 +218,7 @@ def test_shards_reproduce_the_full_batch():
 def test_refusals():
     cfg = ModelConfig(hidden_nf=64, n_layers=1, timesteps=500)
     pb = make_pockets(2, 'CA', ragged=True)
-    px, poh, fixed, _ = _fixed_inputs(pb, 0.25, np.random.default_rng(4))
+    px, poh, fixed, _ = fixed_inputs(pb, 0.25, np.random.default_rng(4))
     jcfg = ModelConfig(hidden_nf=64, n_layers=1, update_pocket_coords=True)
     joint = hip_backend.Handle(jcfg.as_dict(), 0)
     joint.load_state_dict(make_state_dict(jcfg, seed=0))
@@ -259,9 +251,9 @@ def test_refusals():
     ddpm = model_for(cfg, make_state_dict(cfg, seed=0))
     phar = {'x': dev(px), 'one_hot': dev(poh), 'size': dev(pb.num_nodes_phar), 'mask': dev(np.repeat(np.arange(2), pb.num_nodes_phar))}
     with pytest.raises(ValueError, match='draws'):
-        ddpm.edit(phar, pocket_dict(pb), fix_types=dev(fixed), start=6, resamplings=2, timesteps=10, noise=short)
+        ddpm.edit(phar, pocket_dev(pb), fix_types=dev(fixed), start=6, resamplings=2, timesteps=10, noise=short)
     with pytest.raises(ValueError, match='start'):
-        ddpm.edit(phar, pocket_dict(pb), fix_types=dev(fixed), start=11, timesteps=10)
+        ddpm.edit(phar, pocket_dev(pb), fix_types=dev(fixed), start=11, timesteps=10)
 
 
 def test_python_edit_matches_g22():
@@ -272,7 +264,7 @@ def test_python_edit_matches_g22():
     nph = torch.from_numpy(pb.num_nodes_phar)
     phar = {'x': dev(G22[name + '/phar_x']), 'one_hot': dev(G22[name + '/phar_one_hot']), 'size': nph.cuda(),
             'mask': dev(np.repeat(np.arange(len(nph)), pb.num_nodes_phar))}
-    out_phar, out_pocket, phar_mask, _ = ddpm.edit(phar, pocket_dict(pb), fix_coords=dev(G22[name + '/fix_x'] != 0)[:, None],
+    out_phar, out_pocket, phar_mask, _ = ddpm.edit(phar, pocket_dev(pb), fix_coords=dev(G22[name + '/fix_x'] != 0)[:, None],
                                                    fix_types=dev(G22[name + '/fix_h'] != 0)[:, None], start=start, resamplings=r,
                                                    jump_length=j, timesteps=K, noise=dev(G22[name + '/noise']))
     want = G22[name + '/xh_phar']
@@ -285,12 +277,7 @@ def test_python_edit_matches_g22():
 def test_edit_phars_end_to_end():
     """PharPocketDDPM.edit_phars on the g7 pocket (30 C-alpha residues): held types come back in every sample, held points within
     0.1 A, the same seed gives the same result, strength with extra free rows is refused, and the result feeds score_phars."""
-    from cmdgen_amd.lightning_modules import PharPocketDDPM
-    from test_oracle_golden_r2 import _hparams
-    model = PharPocketDDPM(**_hparams('CA', 64, 2))
-    sd = make_state_dict(ModelConfig(hidden_nf=64, n_layers=2, timesteps=500), seed=0)
-    model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
-    model = model.cuda()
+    model = lightning_model()
     pdb = os.path.join(GOLDEN, 'g7_pocket.pdb')
     ids = [f'A:{i}' for i in range(1, 30)]
     names = list(model.dataset_info['phar_decoder'])

@@ -9,7 +9,7 @@ import torch
 
 from cmdgen_amd.synthetic import make_state_dict, make_pockets
 from bench import bounded_config
-from test_hip_properties import eval_inputs, handle_for, forward
+from helpers import eval_inputs, forward, handle_with_layout as handle_for
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device('cuda')

@@ -15,13 +15,10 @@ import pytest
 import torch
 
 import f64_ref as fr
+from chain_kit import dev
 from cmdgen_amd import hip_backend
 
 pytestmark = pytest.mark.gpu
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def new_handle(l):

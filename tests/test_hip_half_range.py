@@ -22,22 +22,16 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import load_golden, dynamics_case
+from helpers import dynamics_case
 from cmdgen_amd import hip_backend
-from test_hip_parity_r2 import dev, new_handle, EVAL_TOL, host_step_table
+from chain_kit import dev
+from helpers import (EVAL_TOL, RANGE_NAME as NAME, RANGE_TARGETS as TARGETS, g2, host_step_table, new_handle,
+                     overflow_case, underflow_case)
 
 pytestmark = pytest.mark.gpu
 
-G2 = load_golden('g2_dynamics.npz')
-NAME = 'ca_h256_b8'
-FACTOR = 3.0e6           # first-layer gain: the hidden activation of the targeted MLP reaches ~1e5 ... 1e6 (> 65504, far below fp32's 3e38)
+G2 = g2()
 
-# which first layer is scaled -> which kernel's A operand (the SiLU output feeding the second layer) overflows first
-TARGETS = {
-    'msg': 'ddpm.dynamics.egnn.e_block_1.gcl_0.edge_mlp.0',            # GCL.edge_model           (egnn_new.py:31-42)
-    'coord': 'ddpm.dynamics.egnn.e_block_1.gcl_equiv.coord_mlp.0',     # EquivariantUpdate        (egnn_new.py:87-96)
-    'node': 'ddpm.dynamics.egnn.e_block_1.gcl_0.node_mlp.0',           # GCL.node_model           (egnn_new.py:48-58)
-}
 # launch choices that put the three tile kernels on each half-engine family
 OPTION_SETS = {
     'rows128_node64': dict(edge_mt=128, coord_mt=128, node64=1, e128_fused=0),
@@ -52,27 +46,6 @@ LOW_SCALES = [2.0 ** -6, 2.0 ** -10, 2.0 ** -14]
 # the smallest scale per target at which the raw half-engine call misses the oracle by more than the tolerance: the message MLP's error is
 # diluted by the aggregation (sum / normalization_factor) - at 2^-14 its raw error is 4.8e-7, at the fp32 floor - so it is driven to 2^-22
 SMALLEST = {'msg': 2.0 ** -22, 'coord': 2.0 ** -14, 'node': 2.0 ** -14}
-
-
-def overflow_case(target):
-    cfg, sd, inp = dynamics_case(G2, NAME)
-    sd = dict(sd)
-    for suffix in ('.weight', '.bias'):
-        sd[TARGETS[target] + suffix] = (sd[TARGETS[target] + suffix] * FACTOR).astype(np.float32)
-    return cfg, sd, inp
-
-
-def underflow_case(target, s):
-    """The targeted first layer's weight and bias times s, the matching second layer's weight times 1 / s: the half GEMM's A operand
-    (SiLU of the first layer) sits at scale s, the evaluation's output stays O(1)."""
-    cfg, sd, inp = dynamics_case(G2, NAME)
-    sd = dict(sd)
-    first = TARGETS[target]
-    second = first[:-len('.0')] + '.2.weight'
-    for key in (first + '.weight', first + '.bias'):
-        sd[key] = (sd[key] * np.float32(s)).astype(np.float32)
-    sd[second] = (sd[second] * np.float32(1.0 / s)).astype(np.float32)
-    return cfg, sd, inp
 
 
 def oracle_eps(cfg, sd, inp):
@@ -371,7 +344,7 @@ def test_only_the_low_rows_of_a_mixed_tile_are_counted(monkeypatch):
     row-to-flag mapping (swizzle, slot, row mask) would miss or add rows here, where a uniformly scaled model cannot tell."""
     import torch.nn.functional as F
     from oracle import ref_cpu
-    from test_half_split_range import tau_from_header
+    from helpers import tau_from_header
     tau = tau_from_header()
     cfg, sd, inp = dynamics_case(G2, NAME)
     sd = dict(sd)

@@ -10,8 +10,11 @@ import numpy as np
 import pytest
 import torch
 
+from functools import partial
+
 from helpers import load_golden, cases_of, cfg_from_meta, rms, GOLDEN
 from cond_inpaint_ref import inpaint_plan
+from chain_kit import dev, fixed_inputs, handle_for, lightning_model, model_for, pocket_dev, run_chain, same
 from cmdgen_amd import hip_backend
 from cmdgen_amd.synthetic import ModelConfig, make_state_dict, make_pockets
 from bench import bounded_config
@@ -19,20 +22,8 @@ from bench import bounded_config
 pytestmark = pytest.mark.gpu
 
 G20 = load_golden('g20_cond_inpaint.npz')
-_handles = {}
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def handle_for(cfg, key, sd):
-    k = (tuple(sorted((a, str(b)) for a, b in cfg.as_dict().items())), key)
-    if k not in _handles:
-        h = hip_backend.Handle(cfg.as_dict(), 0)
-        h.load_state_dict(sd)
-        _handles[k] = h
-    return _handles[k]
+# the library's own step table (run_chain's docstring); steps are saved only where a test reads them (want_steps is part of a graph's key)
+run = partial(run_chain, tables=False, want_steps=False)
 
 
 def g20_case(name):
@@ -43,37 +34,8 @@ def g20_case(name):
     return cfg, sd, pb, (K, r, j)
 
 
-def model_for(cfg, sd):
-    from cmdgen_amd.equivariant_diffusion.dynamics import EGNNDynamics
-    from cmdgen_amd.equivariant_diffusion.conditional_model import ConditionalDDPM
-    dyn = EGNNDynamics(phar_nf=cfg.phar_nf, residue_nf=cfg.residue_nf, n_dims=3, joint_nf=cfg.joint_nf, hidden_nf=cfg.hidden_nf,
-                       n_layers=cfg.n_layers, attention=True, tanh=True, norm_constant=1, inv_sublayers=1, sin_embedding=False,
-                       normalization_factor=100, aggregation_method='sum', edge_cutoff=6.0, update_pocket_coords=False)
-    ddpm = ConditionalDDPM(dynamics=dyn, phar_nf=cfg.phar_nf, residue_nf=cfg.residue_nf, n_dims=3, timesteps=cfg.timesteps,
-                           noise_schedule='polynomial_2', noise_precision=1e-5, loss_type='l2', norm_values=[1, 4],
-                           size_histogram=np.ones((30, 70)))
-    ddpm.load_state_dict({k[len('ddpm.'):]: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
-    return ddpm.cuda()
-
-
-def pocket_dict(pb):
-    return {'x': dev(pb.x), 'one_hot': dev(pb.one_hot), 'size': dev(pb.size), 'mask': dev(pb.mask)}
-
-
-def run_inpaint(h, pb, phar_x, phar_oh, fixed, K, r=1, j=1, noise=None, seed=7, ids=None, use_graph=True, want_steps=False):
-    h.set_layout(pb.num_nodes_phar, pb.size)
-    out = h.inpaint_chain(dev(pb.x), dev(pb.one_hot), dev(phar_x), dev(phar_oh), dev(np.asarray(fixed, np.float32)), K,
-                          resamplings=r, jump_length=j, noise=noise, seed=seed, pocket_ids=ids, use_graph=use_graph,
-                          want_steps=want_steps)
-    st = h.chain_status()
-    return [o.cpu().numpy() if o is not None else None for o in out], st
-
-
-def run_plain(h, pb, K, seed=7, ids=None, use_graph=True):
-    h.set_layout(pb.num_nodes_phar, pb.size)
-    out = h.sample_chain(dev(pb.x), dev(pb.one_hot), K, noise=None, seed=seed, pocket_ids=ids, use_graph=use_graph)
-    st = h.chain_status()
-    return [o.cpu().numpy() for o in out[:2]], st
+def run_inpaint(h, pb, phar_x, phar_oh, fixed, K, r=1, j=1, **kw):
+    return run(h, pb, K, given=(phar_x, phar_oh, fixed), plan=(None, r, j), **kw)
 
 
 @pytest.mark.parametrize('use_graph', [True, False])
@@ -83,10 +45,9 @@ def test_inpaint_chain_matches_g20(name, use_graph):
     h = handle_for(cfg, name, sd)
     noise = dev(G20[name + '/noise'])
     assert h.inpaint_plan(K, r, j) == inpaint_plan(r, j, K)[:2]
-    (xh_phar, xh_pocket, z_steps), st = run_inpaint(h, pb, G20[name + '/phar_x'], G20[name + '/phar_one_hot'],
-                                                    G20[name + '/phar_fixed'], K, r, j, noise=noise, use_graph=use_graph,
-                                                    want_steps=True)
-    p_steps = h.last_pocket_steps.cpu().numpy()
+    (xh_phar, xh_pocket, z_steps, p_steps, *_), st = run_inpaint(h, pb, G20[name + '/phar_x'], G20[name + '/phar_one_hot'],
+                                                                 G20[name + '/phar_fixed'], K, r, j, noise=noise, use_graph=use_graph,
+                                                                 want_steps=True)
     want = G20[name + '/xh_phar']
     assert rms(xh_phar[:, :3], want[:, :3]) <= 1e-4 * max(1.0, float(np.abs(want[:, :3]).max()))
     assert np.array_equal(xh_phar[:, 3:], want[:, 3:])
@@ -109,7 +70,7 @@ def test_python_inpaint_frames_match_g20():
     phar = {'x': dev(G20[name + '/phar_x']), 'one_hot': dev(G20[name + '/phar_one_hot']), 'size': nph.cuda(),
             'mask': dev(np.repeat(np.arange(len(nph)), pb.num_nodes_phar))}
     F = 4
-    out_phar, out_pocket, _, _ = ddpm.inpaint(phar, pocket_dict(pb), dev(G20[name + '/phar_fixed'] != 0), resamplings=r,
+    out_phar, out_pocket, _, _ = ddpm.inpaint(phar, pocket_dev(pb), dev(G20[name + '/phar_fixed'] != 0), resamplings=r,
                                               jump_length=j, return_frames=F, timesteps=K, noise=dev(G20[name + '/noise']))
     out_phar, out_pocket = out_phar.cpu().numpy(), out_pocket.cpu().numpy()
     want = G20[name + '/xh_phar']
@@ -141,25 +102,12 @@ def test_without_fixed_rows_equals_sample_chain_bit_for_bit(use_graph, split):
     pb = make_pockets(6, 'CA', ragged=True, first_index=300)
     nl = int(pb.num_nodes_phar.sum())
     K = 20
-    (xa, qa), _ = run_plain(h, pb, K, seed=11, use_graph=use_graph)
-    (xb, qb, _), st = run_inpaint(h, pb, np.ones((nl, 3), np.float32), np.eye(8, dtype=np.float32)[np.zeros(nl, int)],
+    (xa, qa, *_), _ = run(h, pb, K, seed=11, use_graph=use_graph)
+    (xb, qb, *_), st = run_inpaint(h, pb, np.ones((nl, 3), np.float32), np.eye(8, dtype=np.float32)[np.zeros(nl, int)],
                                   np.zeros(nl), K, seed=11, use_graph=use_graph)
     assert np.array_equal(xa, xb) and np.array_equal(qa, qb)
     assert st['max_rel_com_error'] < 1e-2
     h.close()
-
-
-def _fixed_inputs(pb, frac, rng):
-    """Known rows near each pocket's centre, the first `frac` of each sample's rows fixed."""
-    nl = pb.num_nodes_phar
-    pm = np.repeat(np.arange(len(nl)), nl)
-    com = np.stack([pb.x[pb.mask == b].mean(0) for b in range(len(nl))])
-    phar_x = (com[pm] + rng.normal(size=(len(pm), 3)) * 2.5).astype(np.float32)
-    phar_oh = np.eye(8, dtype=np.float32)[rng.integers(0, 8, size=len(pm))]
-    first = np.concatenate([[0], np.cumsum(nl)[:-1]])
-    local = np.arange(len(pm)) - first[pm]
-    fixed = (local < np.maximum(1, (nl[pm] * frac).astype(int))).astype(np.float32)
-    return phar_x, phar_oh, fixed, pm
 
 
 def test_plain_and_inpaint_chains_alternate_on_one_handle():
@@ -169,16 +117,14 @@ def test_plain_and_inpaint_chains_alternate_on_one_handle():
     h = hip_backend.Handle(cfg.as_dict(), 0)
     h.load_state_dict(sd)
     pb = make_pockets(5, 'CA', ragged=True, first_index=500)
-    px, poh, fixed, _ = _fixed_inputs(pb, 0.25, np.random.default_rng(5))
+    px, poh, fixed, _ = fixed_inputs(pb, 0.25, np.random.default_rng(5))
     K = 17
-    ref_plain = [run_plain(h, pb, K, seed=s, use_graph=False)[0] for s in (1, 2)]
+    ref_plain = [run(h, pb, K, seed=s, use_graph=False)[0] for s in (1, 2)]
     ref_inp = [run_inpaint(h, pb, px, poh, fixed, K, seed=s, use_graph=False)[0] for s in (3, 4)]
-    got = [run_plain(h, pb, K, seed=1)[0], run_inpaint(h, pb, px, poh, fixed, K, seed=3)[0],
-           run_plain(h, pb, K, seed=2)[0], run_inpaint(h, pb, px, poh, fixed, K, seed=4)[0]]
+    got = [run(h, pb, K, seed=1)[0], run_inpaint(h, pb, px, poh, fixed, K, seed=3)[0],
+           run(h, pb, K, seed=2)[0], run_inpaint(h, pb, px, poh, fixed, K, seed=4)[0]]
     for g, w in zip(got, [ref_plain[0], ref_inp[0], ref_plain[1], ref_inp[1]]):
-        for a, b in zip(g, w):
-            if b is not None:
-                assert np.array_equal(a, b)
+        same(g, w, ('xh_phar', 'xh_pocket'))
     h.close()
 
 
@@ -190,7 +136,7 @@ def test_graph_runs_equal_eager_runs_as_the_key_changes():
     h = hip_backend.Handle(cfg.as_dict(), 0)
     h.load_state_dict(make_state_dict(cfg, seed=0))
     pb = make_pockets(5, 'CA', ragged=True, first_index=500)
-    px, poh, fixed, _ = _fixed_inputs(pb, 0.25, np.random.default_rng(5))
+    px, poh, fixed, _ = fixed_inputs(pb, 0.25, np.random.default_rng(5))
     K = 17
     h.set_layout(pb.num_nodes_phar, pb.size)
     nl, n_draws = int(pb.num_nodes_phar.sum()), h.inpaint_plan(K)[1]
@@ -226,8 +172,8 @@ def test_graph_runs_equal_eager_runs_as_the_key_changes():
 
 
 def _check_fixed_points_hold(h, pb, K, r, j, rng):
-    px, poh, fixed, pm = _fixed_inputs(pb, 0.25, rng)
-    (xh_phar, xh_pocket, _), st = run_inpaint(h, pb, px, poh, fixed, K, r, j, seed=21)
+    px, poh, fixed, pm = fixed_inputs(pb, 0.25, rng)
+    (xh_phar, xh_pocket, *_), st = run_inpaint(h, pb, px, poh, fixed, K, r, j, seed=21)
     f = fixed != 0
     assert np.array_equal(xh_phar[f, 3:], poh[f])
     B = len(pb.size)
@@ -251,13 +197,13 @@ def test_shards_reproduce_the_full_batch():
     h = handle_for(cfg, 'seed0', make_state_dict(cfg, seed=0))
     K = 8
     full = make_pockets(8, 'CA', ragged=True)
-    px, poh, fixed, pm = _fixed_inputs(full, 0.25, np.random.default_rng(3))
-    (xf, _, _), _ = run_inpaint(h, full, px, poh, fixed, K, 2, 1, ids=full.pocket_index)
+    px, poh, fixed, pm = fixed_inputs(full, 0.25, np.random.default_rng(3))
+    (xf, *_), _ = run_inpaint(h, full, px, poh, fixed, K, 2, 1, ids=full.pocket_index)
     parts = []
     for first in (0, 4):
         sub = make_pockets(4, 'CA', ragged=True, first_index=first)
         rows = np.isin(pm, np.arange(first, first + 4))
-        (xs, _, _), _ = run_inpaint(h, sub, px[rows], poh[rows], fixed[rows], K, 2, 1, ids=sub.pocket_index)
+        (xs, *_), _ = run_inpaint(h, sub, px[rows], poh[rows], fixed[rows], K, 2, 1, ids=sub.pocket_index)
         parts.append(xs)
     xs = np.concatenate(parts)
     assert np.abs(xs[:, :3] - xf[:, :3]).max() <= 1e-4 * max(1.0, np.abs(xf[:, :3]).max())
@@ -267,7 +213,7 @@ def test_shards_reproduce_the_full_batch():
 def test_refusals():
     cfg = ModelConfig(hidden_nf=64, n_layers=1, timesteps=500)
     pb = make_pockets(2, 'CA', ragged=True)
-    px, poh, fixed, _ = _fixed_inputs(pb, 0.25, np.random.default_rng(4))
+    px, poh, fixed, _ = fixed_inputs(pb, 0.25, np.random.default_rng(4))
     joint = hip_backend.Handle(ModelConfig(hidden_nf=64, n_layers=1, update_pocket_coords=True).as_dict(), 0)
     joint.load_state_dict(make_state_dict(ModelConfig(hidden_nf=64, n_layers=1, update_pocket_coords=True), seed=0))
     with pytest.raises(hip_backend.CmdgenError, match='cmdgen_joint_chain'):
@@ -294,22 +240,17 @@ def test_refusals():
     phar = {'x': dev(px), 'one_hot': dev(poh), 'size': dev(pb.num_nodes_phar),
             'mask': dev(np.repeat(np.arange(2), pb.num_nodes_phar))}
     with pytest.raises(ValueError, match='draws'):
-        ddpm.inpaint(phar, pocket_dict(pb), dev(fixed), resamplings=2, timesteps=10, noise=short)
+        ddpm.inpaint(phar, pocket_dev(pb), dev(fixed), resamplings=2, timesteps=10, noise=short)
     with pytest.raises(ValueError, match='phar_fixed'):
-        ddpm.inpaint(phar, pocket_dict(pb), torch.ones(nl + 1, device='cuda'), timesteps=10)
+        ddpm.inpaint(phar, pocket_dev(pb), torch.ones(nl + 1, device='cuda'), timesteps=10)
     with pytest.raises(ValueError, match='jump_length'):
-        ddpm.inpaint(phar, pocket_dict(pb), dev(fixed), jump_length=2, return_frames=2, timesteps=10)
+        ddpm.inpaint(phar, pocket_dev(pb), dev(fixed), jump_length=2, return_frames=2, timesteps=10)
 
 
 def test_inpaint_phars_end_to_end():
     """PharPocketDDPM.inpaint_phars on the g7 pocket (30 C-alpha residues): the given types appear at the given points (back in
     the PDB frame), and the same seed gives the same result."""
-    from cmdgen_amd.lightning_modules import PharPocketDDPM
-    from test_oracle_golden_r2 import _hparams
-    model = PharPocketDDPM(**_hparams('CA', 64, 2))
-    sd = make_state_dict(ModelConfig(hidden_nf=64, n_layers=2, timesteps=500), seed=0)
-    model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
-    model = model.cuda()
+    model = lightning_model()
     pdb = os.path.join(GOLDEN, 'g7_pocket.pdb')
     ids = [f'A:{i}' for i in range(1, 30)]
     names = list(model.dataset_info['phar_decoder'])

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from helpers import (load_golden, rms, JointNoiseTape, joint_cfg, joint_cases, joint_inpaint_case)
+from chain_kit import dev, run_joint_inpaint as run_inpaint
 from oracle import ref_cpu
 from cmdgen_amd import hip_backend
 from cmdgen_amd.synthetic import ModelConfig, make_state_dict, make_pockets, min_cutoff_margin
@@ -28,10 +29,6 @@ def handle_for(cfg, seed, gain=1.0):
         h.load_state_dict(make_state_dict(cfg, seed=seed, coord_gain=gain))
         _handles[key] = h
     return _handles[key]
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def gpu_ok(name):
@@ -148,13 +145,6 @@ def test_joint_sample_matches_reference(name, use_graph):
 
 
 # ------------------------------------------------------------------ EnVariationalDiffusion.inpaint
-def run_inpaint(h, phar, pocket, fp, fq, K, r, j, noise, use_graph, want_steps=False):
-    h.set_layout(phar['size'], pocket['size'])
-    return h.joint_chain(K, phar=(dev(phar['x']), dev(phar['one_hot'])), pocket=(dev(pocket['x']), dev(pocket['one_hot'])),
-                         phar_fixed=dev(fp), pocket_fixed=dev(fq), resamplings=r, jump_length=j,
-                         noise=None if noise is None else dev(noise), use_graph=use_graph, want_steps=want_steps)
-
-
 @pytest.mark.parametrize('use_graph', [False, True])
 @pytest.mark.parametrize('name', [n for n in joint_cases(G9, 'inpaint') if gpu_ok(n)])
 def test_joint_inpaint_matches_reference(name, use_graph):
@@ -384,7 +374,7 @@ def test_generate_phars_joint_mode_end_to_end(tmp_path):
     -> 'Molecule_k' dict, through PharPocketDDPM.generate_phars and the CLI (--resamplings / --jump_length)."""
     import json
     from argparse import Namespace
-    from test_hip_parity import PDB_TEXT
+    from helpers import PDB_TEXT
     from cmdgen_amd.lightning_modules import PharPocketDDPM
     from cmdgen_amd import generate_phars as cli
     hp = dict(outdir='out', dataset='crossdock', datadir='data', batch_size=4, lr=1e-4,

@@ -16,18 +16,14 @@ import torch
 
 import large_layout_ref as L
 import score_ref
-import test_hip_autograd as tha
-from helpers import rms, LOSS_NAMES
+import helpers
+from helpers import GRAD_TOL, LOSS_NAMES, dev, flat_theta, make_handle, rms
 from oracle import ref_cpu
 from cmdgen_amd import hip_backend
 from cmdgen_amd.synthetic import make_state_dict
 from bench import bounded_config
 from rule_sweep_ref import MARGIN
-from test_hip_train import GRAD_TOL, dev, make_handle, flat_theta
-from test_hip_score import model_for, to_dev, entry_ratios, _philox_noise
-from test_hip_inpaint import run_inpaint
-from test_hip_edit import run_edit
-from test_hip_joint import run_inpaint as run_joint_inpaint
+from chain_kit import model_for, philox_noise, run_chain, run_joint_inpaint, score_entry_ratios as entry_ratios, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -120,23 +116,23 @@ def test_training_forward_and_backward_vs_oracle_autograd(H, kw, engine):
 @pytest.mark.parametrize('with_pocket', [False, True])
 def test_input_gradients_match_oracle_autograd(with_pocket, monkeypatch):
     """The differentiable EGNNDynamics on the layout: weights and xh_phar / xh_pocket (about 1 000 position rows) / t against autograd
-    through the oracle, with and without the pocket output in the loss - test_hip_autograd.check_against_oracle itself."""
+    through the oracle, with and without the pocket output in the loss - helpers.check_against_oracle itself."""
     cfg, lay = L.config(64, 2), L.build()
     sd = L.state_dict_of(cfg, seed=41)
     xh_phar, xh_pocket, t = L.eval_inputs(lay, cfg, seed=2)
     rng = np.random.Generator(np.random.PCG64(3))
     g, gq = rng.normal(size=xh_phar.shape).astype(np.float32), rng.normal(size=xh_pocket.shape).astype(np.float32)
     inp = dict(xh_phar=xh_phar, xh_pocket=xh_pocket, t=t, mask_phar=lay['pm'], mask_pocket=lay['pb'].mask)
-    seen, orig = {}, tha.assert_close
+    seen, orig = {}, helpers.assert_close
 
     def recording(got, want, tol, what):
         w = np.zeros_like(got) if want is None else np.asarray(want, dtype=np.float64)
         seen[what] = float(np.abs(np.asarray(got, dtype=np.float64) - w).max()) / (tol * max(float(np.abs(w).max()), 1e-6))
         orig(got, want, tol, what)
-    monkeypatch.setattr(tha, 'assert_close', recording)
+    monkeypatch.setattr(helpers, 'assert_close', recording)
     L._threads()
     try:
-        dyn, gi, gp = tha.check_against_oracle(cfg, sd, inp, g, gq, with_pocket)
+        dyn, gi, gp = helpers.check_against_oracle(cfg, sd, inp, g, gq, with_pocket)
     finally:
         worst = max(seen, key=seen.get) if seen else None
         print(f'input gradients, pocket output {with_pocket}: worst {seen.get(worst, float("nan")):.3f} of GRAD_TOL ({worst}); inputs: '
@@ -321,7 +317,7 @@ def test_score_matches_the_cpu_model(use_graph):
     o = L.oracle_score()
     cfg, lay, raw, K = o['cfg'], o['lay'], o['raw'], L.SCORE_K
     phar, pocket = L.dicts(lay)
-    ddpm = model_for(cfg, L.state_dict_of(cfg), hist=L.HIST)
+    ddpm = model_for(cfg, L.state_dict_of(cfg), hist=L.HIST).eval()
     ddpm.use_hip_graph = use_graph
     out = ddpm.score(to_dev(phar), to_dev(pocket), timesteps=K, noise=dev(o['noise']), return_levels=True)
     out = {k: v.cpu().numpy() for k, v in out.items()}
@@ -377,9 +373,9 @@ def test_inpaint_chain_matches_the_cpu_model(use_graph):
     cfg, lay = o['cfg'], o['lay']
     h = make_handle(cfg)
     h.load_state_dict(L.state_dict_of(cfg))
-    (xh_phar, xh_pocket, z_steps), st = run_inpaint(h, lay['pb'], lay['phar_x'], lay['phar_one_hot'], o['fixed'], L.INPAINT['K'], L.INPAINT['r'],
-                                                    L.INPAINT['j'], noise=dev(o['noise']), use_graph=use_graph, want_steps=True)
-    compare_conditional_chain('inpaint', use_graph, h, o, xh_phar, xh_pocket, z_steps, h.last_pocket_steps.cpu().numpy(), st)
+    got, st = run_chain(h, lay['pb'], L.INPAINT['K'], given=(lay['phar_x'], lay['phar_one_hot'], o['fixed']), plan=(None, L.INPAINT['r'], L.INPAINT['j']),
+                        noise=dev(o['noise']), use_graph=use_graph, tables=False)
+    compare_conditional_chain('inpaint', use_graph, h, o, got.xh_phar, got.xh_pocket, got.z_steps, got.pocket_steps, st)
     h.close()
 
 
@@ -392,9 +388,9 @@ def test_edit_chain_matches_the_cpu_model(use_graph):
     h = make_handle(cfg)
     h.load_state_dict(L.state_dict_of(cfg))
     e = L.EDIT
-    (xh_phar, xh_pocket, z_steps), st = run_edit(h, lay['pb'], lay['phar_x'], lay['phar_one_hot'], o['fix_x'], o['fix_h'], e['K'], e['start'], e['r'],
-                                                 e['j'], noise=dev(o['noise']), use_graph=use_graph, want_steps=True)
-    compare_conditional_chain('edit', use_graph, h, o, xh_phar, xh_pocket, z_steps, h.last_pocket_steps.cpu().numpy(), st)
+    got, st = run_chain(h, lay['pb'], e['K'], given=(lay['phar_x'], lay['phar_one_hot'], o['fix_x'], o['fix_h']), plan=(e['start'], e['r'], e['j']),
+                        noise=dev(o['noise']), use_graph=use_graph, tables=False)
+    compare_conditional_chain('edit', use_graph, h, o, got.xh_phar, got.xh_pocket, got.z_steps, got.pocket_steps, st)
     h.close()
 
 
@@ -535,7 +531,7 @@ def test_a_scored_sample_does_not_depend_on_its_batch():
     other (err and max |net| from the CPU model at the same Philox draws; an entry inside the band is left out, at most 2 %)."""
     cfg, lay = L.config(), L.build()
     sd = L.state_dict_of(cfg)
-    ddpm = model_for(cfg, sd, hist=L.HIST)
+    ddpm = model_for(cfg, sd, hist=L.HIST).eval()
     phar, pocket = L.dicts(lay)
     K, seed, ids = L.SCORE_K, L.SEEDS['score_device'], [int(i) for i in lay['ids']]
     whole = ddpm.score(to_dev(phar), to_dev(pocket), timesteps=K, seed=seed, pocket_ids=ids, return_levels=True)
@@ -543,7 +539,7 @@ def test_a_scored_sample_does_not_depend_on_its_batch():
     assert_large_rule(h, 64)
     rules = [rule(h)]
     nl = lay['pb'].num_nodes_phar
-    noise = _philox_noise(h, seed, ids, nl, K + 1).cpu().numpy()
+    noise = philox_noise(h, seed, ids, nl, range(K + 1)).cpu().numpy()
     L._threads()
     with torch.no_grad(), L.RecordedEdges() as rec:
         raw = score_ref.score_levels(L.params_of(cfg), cfg.as_dict(), phar, pocket, whole['t_levels'].tolist(), noise)

@@ -26,136 +26,63 @@ import torch
 import multi_edit_cases as mec
 import multi_restrained_edit_cases as xc
 import multi_restraint_cases as mrc
-from helpers import rms
+import chain_kit as kit
+from chain_kit import (EINVAL, ESTATE, PLAIN, check_against_ref, dev, given_for, guide, handle, handle_for, model, pocket_dev, record, run_chain, same,
+                       status_key)
 from cmdgen_amd import hip_backend
 from cmdgen_amd import restraints as rs
 from cmdgen_amd.synthetic import ModelConfig, PocketBatch, make_state_dict, make_pockets
-from test_hip_multi_restraint import dev, handle, host_tables, model, status_key
 
 pytestmark = pytest.mark.gpu
 
-EINVAL, ESTATE = -1, -2                                # include/cmdgen_hip.h: CMDGEN_EINVAL, CMDGEN_ESTATE
-NAMES = ('xh_phar', 'xh_pocket', 'z_steps', 'pocket_steps', 'energy', 'op_energy', 'chain_z')
+EDIT = PLAIN + ('chain_z',)                            # what the unguided chains share with the guided ones
 
 
 def given_dev(given):
     return [dev(np.asarray(a, np.float32)) for a in given]
 
 
-def chain_z(h):
-    n = int(np.sum(h.num_phar_host)) * 11
-    return h.debug_read('chain_z', n)
+def run_xedit(h, pb, sizes, w, given, rec, K, start=None, r=1, j=1, noise=None, seed=7, ids=None, use_graph=True, tables=True, **g):
+    """cmdgen_multi_restrained_edit_chain; given = (phar_x, phar_one_hot, fix_x, fix_h) over the unique rows; g: guide()'s clash, scale,
+    max_shift, guide_below"""
+    return run_chain(h, pb, K, groups=(sizes, w), given=given, plan=(start, r, j), guide=guide(rec, **g), noise=noise, seed=seed, ids=ids,
+                     use_graph=use_graph, tables=tables)
 
 
-def run_xedit(h, pb, sizes, w, given, rec, K, start=None, r=1, j=1, clash=xc.CLASH, scale=xc.SCALE, max_shift=xc.MAX_SHIFT, guide_below=1.0,
-              noise=None, seed=7, ids=None, use_graph=True, tables=True):
-    """given = (phar_x, phar_one_hot, fix_x, fix_h) over the unique rows
-    -> [xh_phar, xh_pocket, z_steps, pocket_steps, energy [G, 2], op_energy [n_steps, G], chain_z] as numpy, chain status"""
-    h.set_layout(pb.num_nodes_phar, pb.size)
-    if tables:
-        host_tables(h, K)
-    x, q, zs, en, oe = h.multi_restrained_edit_chain(dev(pb.x), dev(pb.one_hot), sizes, w, *given_dev(given), K, start=start, resamplings=r,
-                                                     jump_length=j, restraints=rec, clash_radius=clash[0], clash_k=clash[1], scale=scale,
-                                                     max_shift=max_shift, guide_below=guide_below, noise=noise, seed=seed, group_ids=ids,
-                                                     want_steps=True, use_graph=use_graph)
-    st = h.chain_status()
-    return [t.cpu().numpy() for t in (x, q, zs, h.last_pocket_steps, en, oe)] + [chain_z(h)], st
-
-
-def run_medit(h, pb, sizes, w, given, K, start=None, r=1, j=1, noise=None, seed=7, ids=None, use_graph=True):
-    h.set_layout(pb.num_nodes_phar, pb.size)
-    host_tables(h, K)
-    x, q, zs = h.multi_edit_chain(dev(pb.x), dev(pb.one_hot), sizes, w, *given_dev(given), K, start=start, resamplings=r, jump_length=j,
-                                  noise=noise, seed=seed, group_ids=ids, want_steps=True, use_graph=use_graph)
-    st = h.chain_status()
-    return [t.cpu().numpy() for t in (x, q, zs, h.last_pocket_steps)] + [chain_z(h)], st
-
-
-def run_redit(h, pb, given, rec, K, start=None, r=1, j=1, clash=xc.CLASH, noise=None, seed=7, ids=None, use_graph=True):
-    h.set_layout(pb.num_nodes_phar, pb.size)
-    host_tables(h, K)
-    x, q, zs, en, oe = h.restrained_edit_chain(dev(pb.x), dev(pb.one_hot), *given_dev(given), K, start=start, resamplings=r, jump_length=j,
-                                               restraints=rec, clash_radius=clash[0], clash_k=clash[1], scale=xc.SCALE, max_shift=xc.MAX_SHIFT,
-                                               noise=noise, seed=seed, pocket_ids=ids, want_steps=True, use_graph=use_graph)
-    st = h.chain_status()
-    return [t.cpu().numpy() for t in (x, q, zs, h.last_pocket_steps, en, oe)] + [chain_z(h)], st
-
-
-def run_mrest(h, pb, sizes, w, rec, K, clash=xc.CLASH, noise=None, seed=7, ids=None, use_graph=True):
-    h.set_layout(pb.num_nodes_phar, pb.size)
-    host_tables(h, K)
-    x, q, zs, en, oe = h.multi_restrained_chain(dev(pb.x), dev(pb.one_hot), sizes, w, K, rec, clash_radius=clash[0], clash_k=clash[1],
-                                                scale=xc.SCALE, max_shift=xc.MAX_SHIFT, noise=noise, seed=seed, group_ids=ids, want_steps=True,
-                                                use_graph=use_graph)
-    st = h.chain_status()
-    return [t.cpu().numpy() for t in (x, q, zs, h.last_pocket_steps, en, oe)] + [chain_z(h)], st
-
-
-def same(a, b, names=NAMES):
-    for name, u, v in zip(names, a, b):
-        assert u.shape == v.shape and np.array_equal(u, v), name
-
-
-def given_for(nph, seed):
-    """Given rows for unique-row counts nph: every kind of mark, and the last group (when there are several) without one."""
-    rng = np.random.default_rng(seed)
-    nu = int(np.sum(nph))
-    um = np.repeat(np.arange(len(nph)), nph)
-    x = (rng.normal(size=(nu, 3)) * 2.5).astype(np.float32)
-    oh = np.eye(8, dtype=np.float32)[rng.integers(0, 8, size=nu)]
-    fx = (np.arange(nu) % 2 == 0).astype(np.float32)
-    fh = (np.arange(nu) % 3 == 0).astype(np.float32)
-    if len(nph) > 1:
-        fx[um == len(nph) - 1] = 0.0
-        fh[um == len(nph) - 1] = 0.0
-    return x, oh, fx, fh
+def run_medit(h, pb, sizes, w, given, K, start=None, r=1, j=1, **kw):
+    """cmdgen_multi_edit_chain, on the host's tables as the guided chain it is compared with bit for bit"""
+    return run_chain(h, pb, K, groups=(sizes, w), given=given, plan=(start, r, j), **kw)
 
 
 # ------------------------------------------------------------------------------------------------ 1. / 2. against the reference
-def check_against_ref(run, engine, use_graph):
+def check_run(run, engine, use_graph):
     r = xc.reference(run)
     case = xc.CASES[run.case]
     pb, gr, want, keep = r['pb'], r['groups'], r['guided'], r['keep']
     n_steps = xc.plan(run)[0]
     h = handle(engine)
     h.set_option('graph_steps', 2)
-    (x, q, zs, ps, en, oe, _), st = run_xedit(h, pb, case.group_sizes, r['weights'], xc.given_rows(case), r['rec'], xc.K, run.start, run.r, run.j,
-                                              noise=r['noise'].cuda(), use_graph=use_graph)
-    rows, rows_q = keep[gr.unique_mask.numpy()], keep[gr.group_of][pb.mask]
-    wx, wq = want['xh_phar'].numpy(), want['xh_pocket'].numpy()
-    wzs, wps = want['z_steps'].numpy(), want['pocket_steps'].numpy()
-    assert zs.shape == wzs.shape and ps.shape == wps.shape and oe.shape == (n_steps, gr.G)
-    ratios = {
-        'z': max(float(np.abs(zs[k][rows] - wzs[k][rows]).max()) / (1e-4 * max(1.0, float(np.abs(wzs[k][rows]).max()))) for k in range(n_steps)),
-        'pocket_steps': max(float(np.abs(ps[k][rows_q] - wps[k][rows_q]).max()) / (1e-4 * max(1.0, float(np.abs(wps[k][rows_q]).max())))
-                            for k in range(n_steps)),
-        'x': rms(x[rows, :3], wx[rows, :3]) / (1e-4 * max(1.0, float(np.abs(wx[rows, :3]).max()))),
-        'pocket': rms(q[rows_q], wq[rows_q]) / (1e-4 * max(1.0, float(np.abs(wq[rows_q]).max()))),
-    }
-    rel = lambda got, w: float((np.abs(got - w) / (1e-4 * np.maximum(1.0, np.abs(w)))).max())
-    ratios['energy'] = rel(en[keep, 0], want['energy'].numpy()[keep])
-    ratios['max_violation'] = rel(en[keep, 1], want['max_violation'].numpy()[keep])
-    ratios['op_energy'] = rel(oe[:, keep], want['op_energy'].numpy()[:, keep])
-    print(f'\n[{xc.run_id(run)} {engine} {"graph" if use_graph else "eager"}] worst ratio to each bound: ' +
-          '  '.join(f'{k} {v:.3f}' for k, v in ratios.items()) + f'  left out {int((~keep).sum())} of {gr.G} groups')
-    assert int((~keep).sum()) <= xc.CHAIN_CAP * gr.G
-    assert all(v <= 1.0 for v in ratios.values()), ratios
-    assert np.array_equal(x[rows, 3:], wx[rows, 3:])
-    assert st['nan_resets'] == 0 and st['max_rel_com_error'] < 1e-2
+    got, st = run_xedit(h, pb, case.group_sizes, r['weights'], xc.given_rows(case), r['rec'], xc.K, run.start, run.r, run.j,
+                        noise=r['noise'].cuda(), use_graph=use_graph)
+    assert got.z_steps.shape == want['z_steps'].shape and got.pocket_steps.shape == want['pocket_steps'].shape
+    assert got.op_energy.shape == (n_steps, gr.G)
+    # test_hip_restraint.py's metric, not test_hip_restrained_edit.py's: the final x and pocket by their RMS, the pocket over its whole row
+    check_against_ref(f'{xc.run_id(run)} {engine} {"graph" if use_graph else "eager"}', got, st, want, keep[gr.unique_mask.numpy()],
+                      keep[gr.group_of][pb.mask], keep, 'groups', final='rms')
     return r
 
 
 @pytest.mark.parametrize('use_graph', [True, False], ids=['graph', 'eager'])
 @pytest.mark.parametrize('run', xc.RUNS, ids=xc.run_id)
 def test_chain_matches_the_reference(run, use_graph):
-    r = check_against_ref(run, 'half', use_graph)
+    r = check_run(run, 'half', use_graph)
     if run.case == 'large':
         assert int((r['pb'].size + r['pb'].num_nodes_phar).max()) > 128           # the 1024-thread path ran
 
 
 @pytest.mark.parametrize('engine', ['bf3', 'fp32'])
 def test_other_engines_match_the_reference(engine):
-    check_against_ref(xc.ENGINE_RUN, engine, True)
+    check_run(xc.ENGINE_RUN, engine, True)
 
 
 # ------------------------------------------------------------------------------------------------ 3. the reductions
@@ -176,9 +103,8 @@ def test_without_guidance_it_is_the_multi_edit_chain_bit_for_bit(run, inject):
     none, s0 = run_xedit(h, pb, case.group_sizes, w, given, None, xc.K, clash=(0.0, 0.0), **kw)
     zero, s1 = run_xedit(h, pb, case.group_sizes, w, given, r['rec'], xc.K, scale=0.0, **kw)
     below, s2 = run_xedit(h, pb, case.group_sizes, w, given, r['rec'], xc.K, guide_below=0.0, **kw)
-    plain = ('xh_phar', 'xh_pocket', 'z_steps', 'pocket_steps', 'chain_z')
     for got in (none, zero, below):
-        same(want, got[:4] + got[6:], plain)
+        same(want, got, EDIT)
     assert status_key(sw) == status_key(s0) == status_key(s1) == status_key(s2) and sw['nan_resets'] == 0
     assert not none[4].any() and not none[5].any()                      # nothing restrains: zero energies
     assert zero[4][:, 0].max() > 0 and zero[5].max() > 0                # scale = 0 still reports them
@@ -210,9 +136,9 @@ def test_groups_of_one_are_the_restrained_edit_chain_bit_for_bit(inject, use_gra
         h.set_layout(pb.num_nodes_phar, pb.size)
         n_draws = h.edit_plan(K, start, r, j)[1]
         noise = dev(np.random.default_rng(10 + start).normal(size=(n_draws, nu, 11)).astype(np.float32)) if inject else None
-        kw = dict(start=start, r=r, j=j, clash=clash, noise=noise, seed=11, ids=pb.pocket_index, use_graph=use_graph)
-        want, sw = run_redit(h, pb, given, rec, K, **kw)
-        got, sg = run_xedit(h, pb, [1] * 6, np.ones(6, np.float32), given, rec, K, **kw)
+        kw = dict(noise=noise, seed=11, ids=pb.pocket_index, use_graph=use_graph)
+        want, sw = run_chain(h, pb, K, given=given, plan=(start, r, j), guide=guide(rec, clash=clash), **kw)
+        got, sg = run_xedit(h, pb, [1] * 6, np.ones(6, np.float32), given, rec, K, start, r, j, clash=clash, **kw)
         same(want, got)
         assert status_key(sw) == status_key(sg) and sw['nan_resets'] == 0
         assert want[4][:, 0].max() > 0 and want[5].max() > 0
@@ -240,7 +166,7 @@ def test_no_marks_from_the_prior_are_the_multi_restrained_chain_bit_for_bit(inje
         spread[[0] + [1 + 2 * i for i in range(K)] + [n_draws - 1]] = noise
         noise, spread = dev(noise), dev(spread)
     ids = 500 + np.arange(len(case.nph))
-    want, sw = run_mrest(h, pb, case.group_sizes, w, rec, K, noise=noise, seed=31, ids=ids, use_graph=use_graph)
+    want, sw = run_chain(h, pb, K, groups=(case.group_sizes, w), guide=guide(rec), noise=noise, seed=31, ids=ids, use_graph=use_graph)
     got, sg = run_xedit(h, pb, case.group_sizes, w, (x, oh, zero, zero), rec, K, noise=spread, seed=31, ids=ids, use_graph=use_graph)
     same(want, got)
     assert status_key(sw) == status_key(sg) and sw['nan_resets'] == 0
@@ -264,7 +190,7 @@ def test_copies_stay_identical_and_runs_repeat_bit_for_bit():
     kw = dict(start=run.start, r=run.r, j=run.j, seed=31, ids=ids)
     a, sa = run_xedit(h, pb, case.group_sizes, w, given, r['rec'], xc.K, use_graph=True, **kw)
     assert h.query('chain_graphs') >= 1
-    z = a[6].reshape(gr.Nl, 11)
+    z = a.chain_z.reshape(gr.Nl, 11)
     first_rows = gr.first_rows().numpy()[gr.urow.numpy()]              # per member row: the same row of the group's first member
     assert gr.max_m == 3 and np.array_equal(z, z[first_rows])
     b, sb = run_xedit(h, pb, case.group_sizes, w, given, r['rec'], xc.K, use_graph=True, **kw)
@@ -293,14 +219,13 @@ def test_held_rows_stay_and_guidance_lowers_the_energy():
     """multi_edit_cases' held-rows case (groups of two, K = 100 on hold_config, device draws) with multi_restraint_cases' recipe of restraints:
     the rows whose coordinates are held come back within HOLD_BOUND of their given points, held types come back, and the touched groups end
     with less energy than with scale = 0 on the same seed."""
-    from test_hip_inpaint import handle_for
     hc = mec.hold_case()
     cfg = mec.hold_config()
     h = handle_for(cfg, 'seed0', make_state_dict(cfg, seed=0))
     case = xc.Case(*hc['case'], None)
     rec = rs.records(mrc.restraints_of(case, hc['pb']), case.nph)
     given = (hc['phar_x'], hc['phar_oh'], hc['coords_only'], hc['types_only'])
-    kw = dict(seed=hc['seed'], tables=False)
+    kw = dict(seed=hc['seed'], tables=False)             # hold_config is another model: host_tables' are the bounded model's
     g, st = run_xedit(h, hc['pb'], hc['sizes'], hc['weights'], given, rec, mec.HOLD_K, **kw)
     u, _ = run_xedit(h, hc['pb'], hc['sizes'], hc['weights'], given, rec, mec.HOLD_K, scale=0.0, **kw)
     assert st['max_rel_com_error'] < 1e-2 and st['nan_resets'] == 0
@@ -342,21 +267,8 @@ def test_refusals_leave_the_handle_usable():
     def args(nu):
         return given_dev(given_for(np.array([nu]), 1))
 
-    def record(kind=0, sample=0, i=0, j=0, c=(0.0, 0.0, 0.0), a=1.0, b=0.0, k=1.0):
-        q = np.zeros(1, dtype=rs.RESTRAINT_DTYPE)
-        q['kind'], q['sample'], q['i'], q['j'], q['c'], q['a'], q['b'], q['k'] = kind, sample, i, j, c, a, b, k
-        return q
-
-    def refused(h, match, rec=None, sizes=(2, 2), w=half, nu=8, K=5, code=EINVAL, **kw):
-        """the message, and the code the entry returned"""
-        codes, check = [], h._check
-        h._check = lambda rc, what: (codes.append(rc), check(rc, what))
-        try:
-            with pytest.raises(hip_backend.CmdgenError, match=match):
-                h.multi_restrained_edit_chain(px, poh, list(sizes), w, *args(nu), K, restraints=rec, **kw)
-        finally:
-            del h._check
-        assert codes[-1] == code, (match, codes)
+    refused = lambda h, match, rec=None, sizes=(2, 2), w=half, nu=8, K=5, code=EINVAL, **kw: kit.refused(      # the message, and the code
+        h, lambda: h.multi_restrained_edit_chain(px, poh, list(sizes), w, *args(nu), K, restraints=rec, **kw), match, code)
 
     def refused_raw(h, match, code, **kw):
         rc = _raw_call(h, px, poh, [2, 2], half, args(8), 5, **kw)
@@ -418,15 +330,9 @@ def test_edit_restrained_given_pockets_returns_the_chains_result():
     case = xc.CASES[run.case]
     r = xc.reference(run)
     pb, gr = r['pb'], r['groups']
-    ddpm = model().cuda()
+    ddpm = model()
     ddpm.use_hip_graph = True
-    xs, hs = np.split(pb.x, np.cumsum(pb.size)[:-1]), np.split(pb.one_hot, np.cumsum(pb.size)[:-1])
-    pockets = []
-    for m in range(2):
-        members = [2 * g + m for g in range(gr.G)]
-        size = pb.size[members]
-        pockets.append({'x': dev(np.concatenate([xs[b] for b in members])), 'one_hot': dev(np.concatenate([hs[b] for b in members])),
-                        'size': dev(size), 'mask': dev(np.repeat(np.arange(gr.G, dtype=np.int64), size))})
+    pockets = [pocket_dev(pb, [2 * g + m for g in range(gr.G)]) for m in range(2)]
     px, poh, fx, fh = xc.given_rows(case)
     nph = np.asarray(case.nph, dtype=np.int64)
     phar = {'x': dev(px), 'one_hot': dev(poh), 'size': dev(nph), 'mask': dev(np.repeat(np.arange(gr.G), nph))}

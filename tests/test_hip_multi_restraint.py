@@ -11,137 +11,50 @@ import pytest
 import torch
 
 import multi_restraint_cases as mrc
-from helpers import rms
+import chain_kit as kit
+from chain_kit import (EINVAL, ESTATE, GUIDED, PLAIN, SMALL, check_against_ref, dev, guide, handle, model, pocket_dev, record, run_chain, same,
+                       status_key)
 from cmdgen_amd import hip_backend
 from cmdgen_amd import restraints as rs
 from cmdgen_amd.synthetic import ModelConfig, PocketBatch, make_state_dict, make_pockets
 
 pytestmark = pytest.mark.gpu
 
-EINVAL, ESTATE = -1, -2                                # include/cmdgen_hip.h: CMDGEN_EINVAL, CMDGEN_ESTATE
-SMALL = dict(node_mt=16, node64=0, coord_mt=32)        # the launches of test_hip_restraint.py's readout_in_coord handles
-_handles, _model = {}, []
+
+def run_guided(h, pb, sizes, w, rec, K, noise=None, seed=7, ids=None, use_graph=True, **g):
+    """cmdgen_multi_restrained_chain; g: guide()'s clash, scale, max_shift, guide_below"""
+    return run_chain(h, pb, K, groups=(sizes, w), guide=guide(rec, **g), noise=noise, seed=seed, ids=ids, use_graph=use_graph)
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def handle(key='half', options=None):
-    """The bounded model of the chain tests; key 'half' (the default engine), 'bf3' (three bf16 pieces), 'fp32', or a name for `options`."""
-    if key not in _handles:
-        h = hip_backend.Handle(mrc.config().as_dict(), 0)
-        h.load_state_dict(mrc.state_dict())
-        if key == 'bf3':
-            h.set_option('half_engine', 0)
-        elif key == 'fp32':
-            h.set_gemm_mode(False)
-        for k, v in (options or {}).items():
-            h.set_option(k, v)
-        _handles[key] = h
-    return _handles[key]
-
-
-def model():
-    if not _model:
-        from cmdgen_amd.equivariant_diffusion.dynamics import EGNNDynamics
-        from cmdgen_amd.equivariant_diffusion.conditional_model import ConditionalDDPM
-        cfg = mrc.config()
-        dyn = EGNNDynamics(phar_nf=cfg.phar_nf, residue_nf=cfg.residue_nf, n_dims=3, joint_nf=cfg.joint_nf, hidden_nf=cfg.hidden_nf,
-                           n_layers=cfg.n_layers, attention=True, tanh=True, norm_constant=1, inv_sublayers=1, sin_embedding=False,
-                           normalization_factor=100, aggregation_method='sum', edge_cutoff=6.0, update_pocket_coords=False)
-        ddpm = ConditionalDDPM(dynamics=dyn, phar_nf=cfg.phar_nf, residue_nf=cfg.residue_nf, n_dims=3, timesteps=cfg.timesteps,
-                               noise_schedule=cfg.noise_schedule, noise_precision=cfg.noise_precision, loss_type='l2',
-                               norm_values=list(cfg.norm_values), size_histogram=np.ones((30, 70)))
-        ddpm.load_state_dict({k[len('ddpm.'):]: torch.from_numpy(v) for k, v in mrc.state_dict().items()}, strict=True)
-        _model.append(ddpm)
-    return _model[0]
-
-
-def host_tables(h, K):
-    """The step table and the guide table in the reference's own fp32 ops, as ConditionalDDPM.sample_restrained_given_pockets supplies them."""
-    ddpm = model()
-    h.set_step_table(K, ddpm.step_table(K))
-    h.set_guide_table(K, ddpm.guide_table(K))
-
-
-def run_guided(h, pb, sizes, w, rec, K, clash=mrc.CLASH, scale=mrc.SCALE, max_shift=mrc.MAX_SHIFT, guide_below=1.0, noise=None, seed=7,
-               ids=None, use_graph=True):
-    """-> [xh_phar, xh_pocket, z_steps, pocket_steps, energy [G, 2], op_energy [K, G]] as numpy, chain status"""
-    h.set_layout(pb.num_nodes_phar, pb.size)
-    host_tables(h, K)
-    x, q, zs, en, oe = h.multi_restrained_chain(dev(pb.x), dev(pb.one_hot), sizes, w, K, rec, clash_radius=clash[0], clash_k=clash[1],
-                                                scale=scale, max_shift=max_shift, guide_below=guide_below, noise=noise, seed=seed,
-                                                group_ids=ids, want_steps=True, use_graph=use_graph)
-    st = h.chain_status()
-    return [t.cpu().numpy() for t in (x, q, zs, h.last_pocket_steps, en, oe)], st
-
-
-def run_multi(h, pb, sizes, w, K, noise=None, seed=7, ids=None, use_graph=True):
-    h.set_layout(pb.num_nodes_phar, pb.size)
-    host_tables(h, K)
-    x, q, zs = h.multi_pocket_chain(dev(pb.x), dev(pb.one_hot), sizes, w, K, noise=noise, seed=seed, group_ids=ids, want_steps=True,
-                                    use_graph=use_graph)
-    st = h.chain_status()
-    return [t.cpu().numpy() for t in (x, q, zs, h.last_pocket_steps)], st
-
-
-def run_restrained(h, pb, rec, K, clash=mrc.CLASH, noise=None, seed=7, ids=None, use_graph=True):
-    h.set_layout(pb.num_nodes_phar, pb.size)
-    host_tables(h, K)
-    x, q, zs, en, oe = h.restrained_chain(dev(pb.x), dev(pb.one_hot), K, rec, clash_radius=clash[0], clash_k=clash[1], scale=mrc.SCALE,
-                                          max_shift=mrc.MAX_SHIFT, noise=noise, seed=seed, pocket_ids=ids, want_steps=True,
-                                          use_graph=use_graph)
-    st = h.chain_status()
-    return [t.cpu().numpy() for t in (x, q, zs, h.last_pocket_steps, en, oe)], st
-
-
-def status_key(st):
-    return (st['max_rel_com_error'], st['max_cog'], st['nan_resets'])
+def run_multi(h, pb, sizes, w, K, **kw):
+    """cmdgen_multi_pocket_chain on the host's tables, as the guided chain it is compared with bit for bit"""
+    return run_chain(h, pb, K, groups=(sizes, w), **kw)
 
 
 # ------------------------------------------------------------------------------------------------ 1. / 5. against the reference
-def check_against_ref(case, engine, use_graph):
+def check_case(case, engine, use_graph):
     r = mrc.reference(case)
-    pb, gr, want, keep = r['pb'], r['groups'], r['guided'], r['keep']
+    pb, gr, keep = r['pb'], r['groups'], r['keep']
     h = handle(engine)
     h.set_option('graph_steps', 2)                                   # K = 5: two replays of two steps, one eager step
-    (x, q, zs, ps, en, oe), st = run_guided(h, pb, case.group_sizes, r['weights'], r['rec'], mrc.K, noise=r['noise'].cuda(),
-                                            use_graph=use_graph)
-    rows, rows_q = keep[gr.unique_mask.numpy()], keep[gr.group_of][pb.mask]
-    wx, wq = want['xh_phar'].numpy(), want['xh_pocket'].numpy()
-    wzs, wps = want['z_steps'].numpy(), want['pocket_steps'].numpy()
-    ratios = {
-        'z': max(float(np.abs(zs[k][rows] - wzs[k][rows]).max()) / (1e-4 * max(1.0, float(np.abs(wzs[k][rows]).max()))) for k in range(mrc.K)),
-        'pocket_steps': max(float(np.abs(ps[k][rows_q] - wps[k][rows_q]).max()) / (1e-4 * max(1.0, float(np.abs(wps[k][rows_q]).max())))
-                            for k in range(mrc.K)),
-        'x': rms(x[rows, :3], wx[rows, :3]) / (1e-4 * max(1.0, float(np.abs(wx[rows, :3]).max()))),
-        'pocket': rms(q[rows_q], wq[rows_q]) / (1e-4 * max(1.0, float(np.abs(wq[rows_q]).max()))),
-    }
-    rel = lambda got, w: float((np.abs(got - w) / (1e-4 * np.maximum(1.0, np.abs(w)))).max())
-    ratios['energy'] = rel(en[keep, 0], want['energy'].numpy()[keep])
-    ratios['max_violation'] = rel(en[keep, 1], want['max_violation'].numpy()[keep])
-    ratios['op_energy'] = rel(oe[:, keep], want['op_energy'].numpy()[:, keep])
-    print(f'\n[{case.name} {engine} {"graph" if use_graph else "eager"}] worst ratio to each bound: ' +
-          '  '.join(f'{k} {v:.3f}' for k, v in ratios.items()) + f'  left out {int((~keep).sum())} of {gr.G} groups')
-    assert int((~keep).sum()) <= mrc.CHAIN_CAP * gr.G
-    assert all(v <= 1.0 for v in ratios.values()), ratios
-    assert np.array_equal(x[rows, 3:], wx[rows, 3:])
-    assert st['nan_resets'] == 0 and st['max_rel_com_error'] < 1e-2
+    got, st = run_guided(h, pb, case.group_sizes, r['weights'], r['rec'], mrc.K, noise=r['noise'].cuda(), use_graph=use_graph)
+    # test_hip_restraint.py's metric: the final x and pocket by their RMS, the pocket over its whole row; at most CHAIN_CAP of the groups left out
+    check_against_ref(f'{case.name} {engine} {"graph" if use_graph else "eager"}', got, st, r['guided'], keep[gr.unique_mask.numpy()],
+                      keep[gr.group_of][pb.mask], keep, 'groups', final='rms')
     return r
 
 
 @pytest.mark.parametrize('use_graph', [True, False], ids=['graph', 'eager'])
 @pytest.mark.parametrize('case', [mrc.MIXED, mrc.LARGE], ids=lambda c: c.name)
 def test_chain_matches_the_reference(case, use_graph):
-    r = check_against_ref(case, 'half', use_graph)
+    r = check_case(case, 'half', use_graph)
     if case.big_member is not None:
         assert int((r['pb'].size + r['pb'].num_nodes_phar).max()) > 128           # the 1024-thread path ran
 
 
 @pytest.mark.parametrize('engine', ['bf3', 'fp32'])
 def test_other_engines_match_the_reference(engine):
-    check_against_ref(mrc.PAIRS, engine, True)
+    check_case(mrc.PAIRS, engine, True)
 
 
 # ------------------------------------------------------------------------------------------------ 2. the reductions
@@ -162,10 +75,8 @@ def test_without_guidance_it_is_the_multi_pocket_chain_bit_for_bit(inject, use_g
     none, s0 = run_guided(h, pb, case.group_sizes, w, None, K, clash=(0.0, 0.0), **kw)
     zero, s1 = run_guided(h, pb, case.group_sizes, w, r['rec'], K, scale=0.0, **kw)
     below, s2 = run_guided(h, pb, case.group_sizes, w, r['rec'], K, guide_below=0.0, **kw)
-    for a, b, c, d in zip(want, none, zero, below):
-        assert np.array_equal(a, b)
-        assert np.array_equal(a, c)
-        assert np.array_equal(a, d)
+    for got in (none, zero, below):
+        same(want, got, PLAIN)
     assert status_key(sw) == status_key(s0) == status_key(s1) == status_key(s2) and sw['nan_resets'] == 0
     assert not none[4].any() and not none[5].any()                      # nothing restrains: zero energies
     assert zero[4][:, 0].max() > 0 and zero[5].max() > 0                # scale = 0 still reports them
@@ -180,7 +91,7 @@ def test_groups_of_one_are_the_restrained_chain_bit_for_bit(inject, use_graph):
     """Every M_g = 1: cmdgen_restrained_chain's outputs on a handle whose evaluations use their own k_readout, energy_out and op_energy_out
     included, and the chain status."""
     K = 10
-    h = handle('readout0', dict(SMALL, readout_in_coord=0))
+    h = handle(options=dict(SMALL, readout_in_coord=0))
     h.set_option('graph_steps', 8)
     pb = make_pockets(6, 'CA', ragged=True, first_index=9500)
     nph = 1 + (np.arange(6, dtype=np.int64) * 3) % 8
@@ -193,11 +104,10 @@ def test_groups_of_one_are_the_restrained_chain_bit_for_bit(inject, use_graph):
                   {'kind': 'exclusion', 'sample': 5, 'center': (0.0, 0.0, 0.0), 'radius': 4.0, 'k': 1.0}]
     rec = rs.records(restraints, nph)
     for clash in (mrc.CLASH, (0.0, 0.0)):                               # with the clash term every group is guided; without it three are
-        want, sw = run_restrained(h, pb, rec, K, clash=clash, noise=noise, seed=11, ids=pb.pocket_index, use_graph=use_graph)
+        want, sw = run_chain(h, pb, K, guide=guide(rec, clash=clash), noise=noise, seed=11, ids=pb.pocket_index, use_graph=use_graph)
         got, sg = run_guided(h, pb, [1] * 6, np.ones(6, np.float32), rec, K, clash=clash, noise=noise, seed=11, ids=pb.pocket_index,
                              use_graph=use_graph)
-        for a, b in zip(want, got):
-            assert np.array_equal(a, b)
+        same(want, got, GUIDED)
         assert status_key(sw) == status_key(sg) and sw['nan_resets'] == 0
         assert want[4][:, 0].max() > 0 and want[5].max() > 0
 
@@ -219,16 +129,14 @@ def test_copies_stay_identical_and_runs_repeat_bit_for_bit():
     assert gr.max_m == 3 and np.array_equal(z, z[first_rows])
     b, sb = run_guided(h, pb, case.group_sizes, w, r['rec'], mrc.K, seed=31, use_graph=True)
     e, se = run_guided(h, pb, case.group_sizes, w, r['rec'], mrc.K, seed=31, use_graph=False)
-    for u, v, x in zip(a, b, e):
-        assert np.array_equal(u, v)
-        assert np.array_equal(u, x)
+    same(a, b, GUIDED)
+    same(a, e, GUIDED)
     assert status_key(sa) == status_key(sb) == status_key(se) and sa['nan_resets'] == 0
     # a changed scalar prepares the slot again; the first arguments give the first result back
     c, _ = run_guided(h, pb, case.group_sizes, w, r['rec'], mrc.K, clash=(mrc.CLASH[0], 2.0), seed=31, use_graph=True)
     assert not np.array_equal(a[0], c[0])
     back, _ = run_guided(h, pb, case.group_sizes, w, r['rec'], mrc.K, seed=31, use_graph=True)
-    for u, v in zip(a, back):
-        assert np.array_equal(u, v)
+    same(a, back, GUIDED)
     # the bare group: no record, r_c = 0
     g = case.bare_group
     rows, rows_q = gr.unique_mask.numpy() == g, gr.group_of[pb.mask] == g
@@ -263,21 +171,8 @@ def test_refusals_leave_the_handle_usable():
     h.set_layout(pb.num_nodes_phar, pb.size)
     half = np.full(4, 0.5, np.float32)
 
-    def record(kind=0, sample=0, i=0, j=0, c=(0.0, 0.0, 0.0), a=1.0, b=0.0, k=1.0):
-        q = np.zeros(1, dtype=rs.RESTRAINT_DTYPE)
-        q['kind'], q['sample'], q['i'], q['j'], q['c'], q['a'], q['b'], q['k'] = kind, sample, i, j, c, a, b, k
-        return q
-
-    def refused(h, match, rec=None, sizes=(2, 2), w=half, code=EINVAL, **kw):
-        """the message, and the code the entry returned"""
-        codes, check = [], h._check
-        h._check = lambda rc, what: (codes.append(rc), check(rc, what))
-        try:
-            with pytest.raises(hip_backend.CmdgenError, match=match):
-                h.multi_restrained_chain(px, poh, list(sizes), w, 5, rec, **kw)
-        finally:
-            del h._check
-        assert codes == [code], (match, codes)
+    refused = lambda h, match, rec=None, sizes=(2, 2), w=half, code=EINVAL, **kw: kit.refused(          # the message, and the code
+        h, lambda: h.multi_restrained_chain(px, poh, list(sizes), w, 5, rec, **kw), match, code)
 
     # of a restraint list and the scalars: cmdgen_restrained_chain's refusals, saying "group"
     refused(h, "group 2 outside the call's 2 groups", record(sample=2))
@@ -328,15 +223,9 @@ def test_sample_restrained_given_pockets_returns_the_chains_result():
     case = mrc.PAIRS
     r = mrc.reference(case)
     pb, gr = r['pb'], r['groups']
-    ddpm = model().cuda()
+    ddpm = model()
     ddpm.use_hip_graph = True
-    xs, hs = np.split(pb.x, np.cumsum(pb.size)[:-1]), np.split(pb.one_hot, np.cumsum(pb.size)[:-1])
-    pockets = []
-    for m in range(2):
-        members = [2 * g + m for g in range(gr.G)]
-        size = pb.size[members]
-        pockets.append({'x': dev(np.concatenate([xs[b] for b in members])), 'one_hot': dev(np.concatenate([hs[b] for b in members])),
-                        'size': dev(size), 'mask': dev(np.repeat(np.arange(gr.G, dtype=np.int64), size))})
+    pockets = [pocket_dev(pb, [2 * g + m for g in range(gr.G)]) for m in range(2)]
     w = r['weights'].reshape(gr.G, 2)
     noise = r['noise'].cuda()
     x, qs, pm, qms, info = ddpm.sample_restrained_given_pockets(pockets, case.nph, r['restraints'], weights=w, clash=mrc.CLASH, scale=mrc.SCALE,

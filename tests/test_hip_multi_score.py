@@ -27,11 +27,11 @@ import multi_pocket_ref as mp
 import multi_score_cases as msc
 import multi_score_ref as ms
 import score_ref
-from helpers import GOLDEN
+import chain_kit as kit
+from chain_kit import dev, handle, lightning_model, model, model_for, philox_noise, pocket_dev, score_entry_ratios, sub_batch
+from helpers import GOLDEN, RANGE_NAME, close, g2, overflow_case
 from cmdgen_amd import hip_backend, scoring
 from cmdgen_amd.synthetic import ModelConfig, make_state_dict, make_pockets
-from test_hip_multi_pocket import dev, handle, model, pocket_dev
-from test_score_cpu import close
 
 pytestmark = pytest.mark.gpu
 
@@ -61,7 +61,7 @@ def run_score(h, pb, x, oh, levels=LEVELS, coef=None, noise=None, seed=7, ids=No
     return [o.cpu().numpy() for o in out], (st['max_rel_com_error'], st['nan_resets'])
 
 
-def given_for(nph, seed):
+def phar_rows_for(nph, seed):
     rng = np.random.default_rng(seed)
     nu = int(np.sum(nph))
     return (rng.normal(size=(nu, 3)) * 2.0).astype(np.float32), np.eye(8, dtype=np.float32)[rng.integers(0, 8, size=nu)]
@@ -75,7 +75,7 @@ def test_groups_of_one_are_the_scoring_chain_bit_for_bit(B, inject, use_graph):
     pb = make_pockets(B, 'CA', ragged=True, first_index=9500)
     nph = 1 + (np.arange(B, dtype=np.int64) * 3) % 8
     pb.num_nodes_phar[:] = nph
-    x, oh = given_for(nph, B)
+    x, oh = phar_rows_for(nph, B)
     noise = dev(np.random.default_rng(B).normal(size=(len(LEVELS), int(nph.sum()), 11)).astype(np.float32)) if inject else None
     h = handle('half')
     h.set_option('graph_steps', 4)                                    # six levels: one replay of four, two eager steps
@@ -133,17 +133,12 @@ def test_every_members_copy_of_z_is_the_first_members(name):
 
 # ------------------------------------------------------------------------------------------------ 5. the reference
 def entry_ratios(sums, want, netmax, n_rows, keep):
-    """|got - want| / bound of every kept entry: error_t of the K levels and loss_0_x of the t = 0 level.  sums [K + 1, n, 4]; want:
-    the reference's dict of err, err_x [K + 1, n]; netmax [K + 1, n]; keep [K + 1, n]."""
+    """score_entry_ratios against the reference's dict of err, err_x [K + 1, n]"""
     K = msc.K
-    err, l0x = want['err'][:K].numpy().astype(np.float64), 0.5 * want['err_x'][K].numpy().astype(np.float64)
-    netmax = np.asarray(netmax)
-    r_t = np.abs(sums[:K, :, 0].astype(np.float64) - err) / score_ref.error_bound(err, netmax[:K], n_rows, 11)
-    r_0 = np.abs(0.5 * sums[K, :, 1].astype(np.float64) - l0x) / (0.5 * score_ref.error_bound(2.0 * l0x, netmax[K], n_rows, 3))
-    return np.concatenate([r_t[keep[:K]], r_0[keep[K]]])
+    return score_entry_ratios(sums, want['err'][:K].numpy().astype(np.float64), 0.5 * want['err_x'][K].numpy().astype(np.float64), netmax, n_rows, keep)
 
 
-def check_against_ref(case, engine, use_graph):
+def check_case(case, engine, use_graph):
     r = msc.reference(case)
     pb, gr, raw = r['pb'], r['groups'], r['raw']
     h = handle(engine)
@@ -168,13 +163,13 @@ def check_against_ref(case, engine, use_graph):
 @pytest.mark.parametrize('use_graph', [True, False], ids=['graph', 'eager'])
 @pytest.mark.parametrize('name', list(msc.CASES))
 def test_matches_the_reference(name, use_graph):
-    check_against_ref(msc.CASES[name], 'half', use_graph)
+    check_case(msc.CASES[name], 'half', use_graph)
 
 
 @pytest.mark.parametrize('engine', ['bf3', 'fp32'])
 @pytest.mark.parametrize('name', ['mixed', 'pairs'])
 def test_other_engines_match_the_reference(name, engine):
-    check_against_ref(msc.CASES[name], engine, True)
+    check_case(msc.CASES[name], engine, True)
 
 
 @pytest.mark.parametrize('name', list(msc.CASES))
@@ -187,7 +182,7 @@ def test_categorical_term_matches_the_reference(name):
     case = msc.CASES[name]
     r = msc.reference(case)
     gr, raw = r['groups'], r['raw']
-    gt, mt = check_against_ref(case, 'half', True)
+    gt, mt = check_case(case, 'half', True)
     K = msc.K
     keep = raw['keep']
     g0, m0 = keep[K], keep[K][gr.group_of]
@@ -213,11 +208,6 @@ def test_levels_are_independent():
     assert np.array_equal(part[0], full[0][pick]) and np.array_equal(part[1], full[1][pick]) and np.array_equal(part[2], full[2])
 
 
-def _philox_noise(h, seed, gids, nph, n_levels):
-    return torch.stack([torch.cat([h.debug_noise(seed, int(i), k, int(n), 11) for i, n in zip(gids, nph)])
-                        for k in range(n_levels)]).contiguous()
-
-
 def test_captured_equals_eager_run_to_run_and_device_draws():
     """Device draws: the captured chain twice and the eager one, bit for bit; the run that injects cmdgen_debug_noise's numbers for
     (seed, group id, level index, node of the group) is the device-draw run; a changed weight, grouping or level list after a captured
@@ -240,7 +230,7 @@ def test_captured_equals_eager_run_to_run_and_device_draws():
     base = both(case.group_sizes, w, x, oh, seed=31, ids=gids)
     assert h.query('chain_graphs') >= 1
     again, _ = run_mscore(h, pb, case.group_sizes, w, x, oh, seed=31, ids=gids)
-    injected, _ = run_mscore(h, pb, case.group_sizes, w, x, oh, noise=_philox_noise(h, 31, gids, case.nph, len(LEVELS)), ids=gids)
+    injected, _ = run_mscore(h, pb, case.group_sizes, w, x, oh, noise=philox_noise(h, 31, gids, case.nph, range(len(LEVELS))), ids=gids)
     for u, v, t in zip(base, again, injected):
         assert np.array_equal(u, v) and np.array_equal(u, t)
     other_seed = both(case.group_sizes, w, x, oh, seed=32, ids=gids)
@@ -249,7 +239,7 @@ def test_captured_equals_eager_run_to_run_and_device_draws():
     other_w = both(case.group_sizes, w2, x, oh, seed=31, ids=gids)
     assert not np.array_equal(other_w[0][:, 0], base[0][:, 0]) and np.array_equal(other_w[0][:, 1:], base[0][:, 1:])
     assert np.array_equal(other_w[1], base[1])                         # the members' own rows do not see the weights
-    x1, oh1 = given_for(pb.num_nodes_phar, 6)
+    x1, oh1 = phar_rows_for(pb.num_nodes_phar, 6)
     singles = both([1] * len(pb.size), np.ones(len(pb.size), np.float32), x1, oh1, seed=31)
     assert singles[0].shape == (len(LEVELS), len(pb.size), 4)
     fewer = both(case.group_sizes, w, x, oh, seed=31, ids=gids, levels=LEVELS[:4])
@@ -272,14 +262,11 @@ def test_a_group_alone_and_inside_a_larger_batch():
     members = list(range(gr.first[g], gr.first[g] + gr.sizes[g]))
     h = handle('half')
     full, st = run_mscore(h, pb, case.group_sizes, w, x, oh, seed=seed, ids=gids)
-    xs, hs = np.split(pb.x, np.cumsum(pb.size)[:-1]), np.split(pb.one_hot, np.cumsum(pb.size)[:-1])
-    size = pb.size[members]
-    sub = msc.mc.PocketBatch(x=np.concatenate([xs[b] for b in members]), one_hot=np.concatenate([hs[b] for b in members]), size=size,
-                             mask=np.repeat(np.arange(len(members), dtype=np.int64), size), num_nodes_phar=pb.num_nodes_phar[members])
+    sub = sub_batch(pb, members)
     u0 = int(np.sum(case.nph[:g])); rows = slice(u0, u0 + case.nph[g])
     alone, st2 = run_mscore(h, sub, [len(members)], w[members], x[rows], oh[rows], seed=seed, ids=gids[g:g + 1])
     # the oracle at these draws, for max |net| and the margins of this group
-    noise = _philox_noise(h, seed, gids[g:g + 1], case.nph[g:g + 1], len(LEVELS)).cpu()
+    noise = philox_noise(h, seed, gids[g:g + 1], case.nph[g:g + 1], range(len(LEVELS))).cpu()
     pocket = {'x': torch.from_numpy(sub.x), 'one_hot': torch.from_numpy(sub.one_hot), 'size': torch.from_numpy(sub.size),
               'mask': torch.from_numpy(sub.mask)}
     with torch.no_grad():
@@ -313,7 +300,7 @@ def test_the_chain_alternates_with_the_other_chains_on_one_handle():
     pb = make_pockets(G * M, 'CA', ragged=True, first_index=9620)
     nph = np.array([5, 8], dtype=np.int64)
     gr = mp.Groups([M] * G, nph)
-    x, oh = given_for(nph, 9)
+    x, oh = phar_rows_for(nph, 9)
     pockets = [pocket_dev(pb, [g * M + m for g in range(G)]) for m in range(M)]
     phar = {'x': dev(x), 'one_hot': dev(oh), 'size': dev(nph), 'mask': dev(np.repeat(np.arange(G), nph))}
     urow = gr.urow.numpy()
@@ -361,7 +348,7 @@ def test_all_conditional_chains_alternate_on_one_handle_and_survive_a_layout_cha
 
     def rounds_for(nph):
         gr = mp.Groups([M] * G, nph)
-        x, oh = given_for(nph, 9)
+        x, oh = phar_rows_for(nph, 9)
         urow = gr.urow.numpy()
         phar = {'x': dev(x), 'one_hot': dev(oh), 'size': dev(nph), 'mask': dev(np.repeat(np.arange(G), nph))}
         phar_m = {'x': dev(x[urow]), 'one_hot': dev(oh[urow]), 'size': dev(gr.member_nph), 'mask': dev(gr.phar_mask.numpy())}
@@ -417,7 +404,7 @@ def test_score_given_pockets_with_repeats_and_members():
     ddpm.use_hip_graph = True
     pb = make_pockets(G * M, 'CA', ragged=True, first_index=9640)
     nph = np.array([5, 8, 3], dtype=np.int64)
-    x, oh = given_for(nph, 12)
+    x, oh = phar_rows_for(nph, 12)
     pockets = [pocket_dev(pb, [g * M + m for g in range(G)]) for m in range(M)]
     phar = {'x': dev(x), 'one_hot': dev(oh), 'size': dev(nph), 'mask': dev(np.repeat(np.arange(G), nph))}
     noise = torch.from_numpy(np.random.default_rng(8).normal(size=(2, K + 1, int(nph.sum()), 11)).astype(np.float32)).cuda()
@@ -445,12 +432,7 @@ def test_score_given_pockets_with_repeats_and_members():
 def test_score_phars_multi_end_to_end():
     """PharPocketDDPM.score_phars_multi on the synthetic PDB given twice, as two different pockets (29 and 20 residues): the same seed
     gives the same result, candidate i draws with group id i, and with weights (1, 0) every entry is the first pocket's own."""
-    from cmdgen_amd.lightning_modules import PharPocketDDPM
-    from test_oracle_golden_r2 import _hparams
-    m = PharPocketDDPM(**_hparams('CA', 64, 2))
-    sd = make_state_dict(ModelConfig(hidden_nf=64, n_layers=2, timesteps=500), seed=0)
-    m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
-    m = m.cuda().eval()
+    m = lightning_model().eval()
     pdb = os.path.join(GOLDEN, 'g7_pocket.pdb')
     ids = [f'A:{i}' for i in range(1, 30)]
     names = list(m.dataset_info['phar_decoder'])
@@ -489,11 +471,10 @@ def test_refusals_leave_the_handle_usable():
     half = np.full(4, 0.5, np.float32)
 
     def args(nu):
-        return [dev(a) for a in given_for(np.array([nu]), 1)]
+        return [dev(a) for a in phar_rows_for(np.array([nu]), 1)]
 
-    def refused(match, sizes, w, nu=8, levels=(250, 0)):
-        with pytest.raises(hip_backend.CmdgenError, match=match):
-            h.multi_score_chain(*args(nu), px, poh, sizes, w, list(levels))
+    refused = lambda match, sizes, w, nu=8, levels=(250, 0): kit.refused(              # the message
+        h, lambda: h.multi_score_chain(*args(nu), px, poh, sizes, w, list(levels)), match, code=None)
 
     refused('share one latent', [1, 2, 1], np.array([1, 0.5, 0.5, 1], np.float32), nu=11)     # members 1 and 2 have 3 and 5 points
     refused('sum to 3', [2, 1], np.array([0.5, 0.5, 1, 1], np.float32))
@@ -530,15 +511,14 @@ def test_range_guard():
     """test_hip_score.py's range-guard recipe on one target, the samples paired into groups of two: the raw chain on the half engine
     reports reset levels in the flag column (nothing is summed in silently); score_given_pockets warns, re-runs on the bf16 engine and
     meets the parity bound against the oracle."""
-    from test_hip_score import G2, NAME, model_for, overflow_case
     cfg, sd, inp = overflow_case('node')
-    nl, npk = G2[NAME + '/num_nodes_phar'].astype(np.int64), G2[NAME + '/pocket_size'].astype(np.int64)
+    nl, npk = g2()[RANGE_NAME + '/num_nodes_phar'].astype(np.int64), g2()[RANGE_NAME + '/pocket_size'].astype(np.int64)
     B = len(nl)
     assert B % 2 == 0
     G, M = B // 2, 2
     nph = np.minimum(nl[0::2], nl[1::2])                               # a group's members share the count: the smaller of the pair
     gr = mp.Groups([M] * G, nph)
-    x, oh = given_for(nph, 13)
+    x, oh = phar_rows_for(nph, 13)
     qm = inp['mask_pocket']
     pocket = {'x': torch.from_numpy(inp['xh_pocket'][:, :3].copy()),
               'one_hot': torch.from_numpy(np.round(inp['xh_pocket'][:, 3:] * cfg.norm_values[1]).astype(np.float32)),
@@ -568,7 +548,7 @@ def test_range_guard():
     assert np.array_equal(gt[:, :, 3], np.repeat(gt[:, :1, 3], G, axis=1)) and np.array_equal(mt[:, :, 3], np.repeat(gt[:, :1, 3], B, axis=1))
     h.close()
     # 2. the mirror: warning, bf16 re-run, oracle-equal entries
-    ddpm = model_for(cfg, sd, hist=np.ones((30, 70)))
+    ddpm = model_for(cfg, sd).eval()
     pockets = [{'x': dev(pocket['x'].numpy()[np.isin(qm, np.arange(m, B, M))]), 'one_hot': dev(pocket['one_hot'].numpy()[np.isin(qm, np.arange(m, B, M))]),
                 'size': dev(npk[m::M]), 'mask': dev(np.repeat(np.arange(G), npk[m::M]))} for m in range(M)]
     phar = {'x': dev(x), 'one_hot': dev(oh), 'size': dev(nph), 'mask': dev(gr.unique_mask.numpy())}
@@ -579,9 +559,6 @@ def test_range_guard():
     sums = out['level_sums'][0].cpu().numpy()
     keep = raw['keep']                                                 # (the original recipe keeps all; an entry at the cutoff proves nothing either way)
     err, l0x = raw['group']['err'][:K].numpy().astype(np.float64), 0.5 * raw['group']['err_x'][K].numpy().astype(np.float64)
-    nm = raw['group']['netmax'].numpy()
-    r_t = np.abs(sums[:K, :, 0].astype(np.float64) - err) / score_ref.error_bound(err, nm[:K], nph, 11)
-    r_0 = np.abs(0.5 * sums[K, :, 1].astype(np.float64) - l0x) / (0.5 * score_ref.error_bound(2.0 * l0x, nm[K], nph, 3))
-    r = np.concatenate([r_t[keep[:K]], r_0[keep[K]]])
+    r = score_entry_ratios(sums, err, l0x, raw['group']['netmax'].numpy(), nph, keep)
     print(f'guarded score_given_pockets against the oracle: worst ratio {r.max():.3e}, {int((~keep).sum())} of {keep.size} entries at the cutoff')
     assert r.max() <= 1.0 and bool(torch.isfinite(out['nll']).all()) and keep.sum() >= 0.8 * keep.size

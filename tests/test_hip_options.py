@@ -7,7 +7,8 @@ import torch
 
 from helpers import load_golden, cases_of, dynamics_case
 from cmdgen_amd import hip_backend
-from test_hip_parity_r2 import dev, new_handle, EVAL_TOL
+from chain_kit import dev
+from helpers import EVAL_TOL, new_handle
 
 pytestmark = pytest.mark.gpu
 G2 = load_golden('g2_dynamics.npz')

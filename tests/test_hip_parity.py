@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import (load_golden, cases_of, dynamics_case, chain_case, rms, NoiseTape)
+from helpers import (PDB_TEXT, load_golden, cases_of, dynamics_case, chain_case, rms, NoiseTape)
+from chain_kit import dev
 from cmdgen_amd import hip_backend
 from cmdgen_amd.synthetic import ModelConfig, make_state_dict, make_pockets, min_cutoff_margin
 
@@ -30,10 +31,6 @@ def handle_for(cfg, sd_key, sd):
         h.load_state_dict(sd)
         _handles[key] = h
     return _handles[key]
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def supported(name):
@@ -148,7 +145,7 @@ def test_dynamics_forward_matches_oracle_other_widths(H, L, rep):
         pocket = {'x': torch.from_numpy(pb.x), 'one_hot': torch.from_numpy(pb.one_hot), 'size': torch.from_numpy(pb.size), 'mask': torch.from_numpy(pb.mask)}
         with torch.no_grad():
             ref = ref_cpu.sample_given_pocket(p, cfg.as_dict(), pocket, pb.num_nodes_phar, timesteps=K, noise=NoiseTape(noise))
-        from test_hip_parity_r2 import host_step_table
+        from helpers import host_step_table
         for use_graph in (False, True):
             h.set_step_table(K, host_step_table(cfg, K))
             x, _, _ = h.sample_chain(dev(pb.x), dev(pb.one_hot), K, noise=dev(noise), use_graph=use_graph)
@@ -294,17 +291,6 @@ def test_errors_are_loud():
     with pytest.raises(hip_backend.CmdgenError):
         h.set_layout([3], [10])
         h.dynamics_forward(torch.zeros(3, 11).cuda(), torch.zeros(10, 23).cuda(), torch.zeros(1).cuda())  # no weights
-
-
-PDB_TEXT = """\
-ATOM      1  CA  ALA A   1      11.639   6.071  -5.147  1.00  0.00           C
-ATOM      2  CA  GLY A   2      14.000   7.500  -3.000  1.00  0.00           C
-ATOM      3  CA  TRP A   3      16.500   9.000  -1.000  1.00  0.00           C
-ATOM      4  CA  LEU A   4      12.500   9.500  -2.000  1.00  0.00           C
-ATOM      5  CA  SER A   5      10.000   8.000   0.500  1.00  0.00           C
-ATOM      6  CA  ASP A   6      13.500   4.000  -1.500  1.00  0.00           C
-END
-"""
 
 
 def test_generate_phars_end_to_end(tmp_path):

@@ -13,39 +13,18 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import (GOLDEN, load_golden, cases_of, dynamics_case, rms, bounded_case, fullsize_chain_case, g5_case,
-                     pocket_dict)
+from helpers import (EVAL_TOL, G7_RUNS, GOLDEN, _hparams, assert_same_result, load_golden, cases_of, dynamics_case, g7_select, rms, bounded_case,
+                     fullsize_chain_case, g5_case, host_step_table, new_handle, pocket_dict)
+from chain_kit import dev
 from cmdgen_amd import hip_backend
 from cmdgen_amd.synthetic import ModelConfig, make_state_dict, make_pockets, min_cutoff_margin
 
 pytestmark = pytest.mark.gpu
-EVAL_TOL = 2e-5
 
 G12 = load_golden('g12_fullsize.npz')
 G13 = load_golden('g13_bounded.npz')
 G5 = load_golden('g5_blocks.npz')
 G7 = load_golden('g7_generate.npz')
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def new_handle(cfg, sd):
-    h = hip_backend.Handle(cfg.as_dict(), 0)
-    h.load_state_dict(sd)
-    return h
-
-
-def host_step_table(cfg, K):
-    """Per-step scalars evaluated exactly as the reference does (bit-identical table, oracle-side helper)."""
-    from oracle import ref_cpu
-    table = ref_cpu.gamma_table(cfg.noise_schedule, cfg.timesteps, cfg.noise_precision)
-    coef = ref_cpu.step_coefficients(table, cfg.timesteps, K).numpy()
-    g0 = table[0]
-    final = np.array([[float(torch.sqrt(torch.sigmoid(g0))), float(torch.sqrt(torch.sigmoid(-g0))),
-                       float(torch.exp(0.5 * g0)), 0.0]], np.float32)
-    return np.concatenate([coef, final])
 
 
 # ----------------------------------------------------------------------------- configs[4] at its real size
@@ -236,7 +215,6 @@ def test_per_block_intermediates_match_reference():
 
 
 # ----------------------------------------------------------------------------- G7: generate_phars end to end
-from test_oracle_golden_r2 import _hparams, G7_RUNS, g7_select, assert_same_result  # noqa: E402
 
 
 @pytest.mark.parametrize('tag,rep,sel', G7_RUNS)

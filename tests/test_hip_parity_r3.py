@@ -12,42 +12,13 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import NoiseTape, load_golden, pocket_dict, rms, cases_of, dynamics_case
+from helpers import (CHAIN_BAND as BAND, EVAL_TOL, NoiseTape, load_golden, pocket_dict, rms, cases_of, dynamics_case, g14, g14_case,
+                     host_step_table, new_handle, per_sample_rms, small_case)
+from chain_kit import dev
 from cmdgen_amd import hip_backend
 from cmdgen_amd.synthetic import ModelConfig, make_state_dict, make_pockets
-from test_hip_parity_r2 import EVAL_TOL
 
 pytestmark = pytest.mark.gpu
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def new_handle(cfg, sd):
-    h = hip_backend.Handle(cfg.as_dict(), 0)
-    h.load_state_dict(sd)
-    return h
-
-
-def host_step_table(cfg, K):
-    """Per-step scalars evaluated exactly as the reference does (bit-identical table, oracle-side helper)."""
-    from oracle import ref_cpu
-    table = ref_cpu.gamma_table(cfg.noise_schedule, cfg.timesteps, cfg.noise_precision)
-    coef = ref_cpu.step_coefficients(table, cfg.timesteps, K).numpy()
-    g0 = table[0]
-    final = np.array([[float(torch.sqrt(torch.sigmoid(g0))), float(torch.sqrt(torch.sigmoid(-g0))),
-                       float(torch.exp(0.5 * g0)), 0.0]], np.float32)
-    return np.concatenate([coef, final])
-
-
-def small_case(seed=91, B=3, K=4):
-    cfg = ModelConfig(hidden_nf=64, n_layers=2, timesteps=500)
-    sd = make_state_dict(cfg, seed=seed, coord_gain=1e-3)
-    pb = make_pockets(B, 'CA', ragged=True, n_phar=8, first_index=100 * seed)
-    Nl = int(pb.num_nodes_phar.sum())
-    noise = np.random.Generator(np.random.PCG64(seed)).normal(size=(K + 2, Nl, 11)).astype(np.float32)
-    return cfg, sd, pb, K, noise
 
 
 def oracle_chain(cfg, sd, pb, K, noise):
@@ -139,29 +110,7 @@ def test_mean_zero_assertion_fires_like_reference():
 
 
 # ----------------------------------------------------------------------------- G14: configs[1] / configs[4] at their literal size
-G14 = load_golden('g14_fullsize_chains.npz')
-BAND = 2e-5         # a pair this close to the cutoff may be decided differently by torch.cdist's matmul form (quirk Q2): its
-                    # rounding at |x| ~ 17 A is ~5e-6 A in d, ours (direct fma chain) ~1e-6 A
-
-
-def g14_case(name):
-    H, L, B, R, seed, K, T, first, nseed, window = [int(v) for v in G14[name + '/meta']]
-    cfg = ModelConfig(hidden_nf=H, n_layers=L, residue_nf=R, timesteps=T, noise_precision=float(G14[name + '/noise_precision']),
-                      norm_values=tuple(float(v) for v in G14[name + '/norm_values']))
-    sd = make_state_dict(cfg, seed=seed, coord_gain=1.0)
-    pb = make_pockets(B, 'CA' if R == 20 else 'full-atom', n_phar=15, first_index=first)
-    Nl = int(pb.num_nodes_phar.sum())
-    gen = torch.Generator().manual_seed(nseed)                       # the reference's draws, regenerated (42 MB for K = 1000: not stored)
-    noise = torch.stack([torch.randn((Nl, 11), generator=gen) for _ in range(K + 2)])
-    probe = G14[name + '/noise_probe']
-    assert np.array_equal(noise[0, :4].numpy(), probe[0]) and np.array_equal(noise[K + 1, :4].numpy(), probe[1]), \
-        'torch.Generator stream differs from the one the golden was made with'
-    return cfg, sd, pb, K, window, noise
-
-
-def per_sample_rms(a, b, B):
-    d = (np.asarray(a, np.float64) - np.asarray(b, np.float64)).reshape(B, -1, a.shape[-1])
-    return np.sqrt((d ** 2).mean((1, 2)))
+G14 = g14()
 
 
 def batch_rms(a, b):

@@ -11,8 +11,8 @@ from helpers import load_golden, cases_of, dynamics_case
 from cmdgen_amd import hip_backend
 from cmdgen_amd.synthetic import make_state_dict, make_pockets
 from bench import bounded_config
-from test_hip_parity_r2 import dev, new_handle, EVAL_TOL
-from test_hip_properties import eval_inputs, handle_for, forward
+from chain_kit import dev
+from helpers import EVAL_TOL, eval_inputs, forward, handle_with_layout as handle_for, new_handle
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device('cuda')

@@ -18,37 +18,10 @@ import torch
 from cmdgen_amd import hip_backend
 from cmdgen_amd.synthetic import ModelConfig, make_state_dict, make_pockets
 from bench import bounded_config
+from helpers import eval_inputs, forward, handle_with_layout as handle_for
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device('cuda')
-
-
-def eval_inputs(pb, cfg, seed=12345):
-    """Phar points inside the pocket (the geometry a trained model holds: every pocket node within a few hops of a moving node)."""
-    B = len(pb.size)
-    rng = np.random.Generator(np.random.PCG64(seed))
-    nl = int(pb.num_nodes_phar.sum())
-    pm = np.repeat(np.arange(B), pb.num_nodes_phar)
-    starts = np.concatenate([[0], np.cumsum(pb.size)[:-1]])
-    com = np.add.reduceat(pb.x.astype(np.float64), starts, axis=0) / pb.size[:, None]
-    v = rng.normal(size=(nl, 3)); v /= np.linalg.norm(v, axis=1, keepdims=True)
-    xin = (com[pm] + v * 5.0 * np.cbrt(rng.uniform(size=(nl, 1)))).astype(np.float32)
-    xh = np.concatenate([xin, rng.normal(size=(nl, cfg.phar_nf)).astype(np.float32)], 1)
-    xq = np.concatenate([pb.x, pb.one_hot / cfg.norm_values[1]], 1).astype(np.float32)
-    t = rng.uniform(0.05, 0.95, size=B).astype(np.float32)
-    return xh, xq, t
-
-
-def handle_for(cfg, sd, pb):
-    h = hip_backend.Handle(cfg.as_dict(), 0)
-    h.load_state_dict(sd)
-    h.set_layout(pb.num_nodes_phar, pb.size)
-    return h
-
-
-def forward(h, xh, xq, t):
-    eps, _ = h.dynamics_forward(torch.from_numpy(xh).to(DEV), torch.from_numpy(xq).to(DEV), torch.from_numpy(t).to(DEV))
-    return eps.cpu().numpy()
 
 
 SHAPES = [('CA', 64), ('CA', 256), ('full-atom', 256)]

@@ -12,17 +12,13 @@ import torch
 from cmdgen_amd import hip_backend
 from cmdgen_amd.synthetic import make_state_dict, make_pockets
 from bench import bounded_config
-from test_hip_parity_r3 import small_case, host_step_table
-from test_hip_properties import handle_for
+from chain_kit import dev
+from helpers import handle_with_layout as handle_for, host_step_table, small_case
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device('cuda')
 SMALL = dict(node_mt=16, node64=0, coord_mt=32)        # the launches the rule asks for at the headline, forced on the small layouts
 _shared = {}
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def model():

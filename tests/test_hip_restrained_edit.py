@@ -13,66 +13,38 @@ import pytest
 import torch
 
 import restrained_edit_cases as ec
+import chain_kit as kit
+from chain_kit import (PARITY, PLAIN, SMALL, check_against_ref, dev, guide, handle, lightning_model, model, pocket_dev, record, run_chain,
+                       same, status_key)
 from helpers import GOLDEN
-from test_hip_restraint import SMALL, dev, handle, host_tables, model, run_restrained, status_key
 from cmdgen_amd import hip_backend
 from cmdgen_amd import restraints as rs
-from cmdgen_amd.synthetic import ModelConfig, PocketBatch, make_state_dict, make_pockets
+from cmdgen_amd.synthetic import ModelConfig, make_state_dict, make_pockets
 
 pytestmark = pytest.mark.gpu
 
-PARITY = 1e-4
 ALL = [ec.MIXED, ec.JUMPS, ec.LARGE]
+EDIT = PLAIN + ('chain_z',)                            # what cmdgen_edit_chain shares with the restrained edit chain
 
 
-def inputs(r):
-    pb, ph = r['pb'], r['phar']
-    return dev(pb.x), dev(pb.one_hot), ph['x'].cuda(), ph['one_hot'].cuda()
+def run_redit(h, case, r, rec, noise=None, seed=7, ids=None, use_graph=True, marked=True, start=None, resamplings=None, jump_length=None, **g):
+    """The case's restrained edit chain (marked=False: with no mark in either mask; start, resamplings, jump_length: another plan; g: guide()'s)."""
+    ph, zero = r['phar'], np.zeros(len(r['fx']), np.float32)
+    plan = (case.start if start is None else start, case.r if resamplings is None else resamplings, case.j if jump_length is None else jump_length)
+    return run_chain(h, r['pb'], case.K, given=(ph['x'], ph['one_hot'], r['fx'] if marked else zero, r['fh'] if marked else zero), plan=plan,
+                     guide=guide(rec, **g), noise=noise, seed=seed, ids=ids, use_graph=use_graph)
 
 
-def run_redit(h, case, r, rec, clash=ec.CLASH, scale=ec.SCALE, max_shift=ec.MAX_SHIFT, guide_below=1.0, noise=None, seed=7, ids=None,
-              use_graph=True, marked=True, start=None, resamplings=None, jump_length=None):
-    """-> [xh_phar, xh_pocket, z_steps, pocket_steps, energy [B, 2], op_energy [n_steps, B], chain_z] as numpy, chain status"""
-    pb = r['pb']
-    h.set_layout(pb.num_nodes_phar, pb.size)
-    host_tables(h, case.K)
-    fx, fh = (dev(r['fx']), dev(r['fh'])) if marked else (torch.zeros(len(r['fx']), device='cuda'), torch.zeros(len(r['fh']), device='cuda'))
-    x, q, zs, en, oe = h.restrained_edit_chain(
-        *inputs(r), fx, fh, case.K, start=case.start if start is None else start, resamplings=case.r if resamplings is None else resamplings,
-        jump_length=case.j if jump_length is None else jump_length, restraints=rec, clash_radius=clash[0], clash_k=clash[1], scale=scale,
-        max_shift=max_shift, guide_below=guide_below, noise=noise, seed=seed, pocket_ids=ids, want_steps=True, use_graph=use_graph)
-    st = h.chain_status()
-    cz = h.debug_read('chain_z', int(sum(case.nph)) * 11)
-    return [t.cpu().numpy() for t in (x, q, zs, h.last_pocket_steps, en, oe)] + [cz], st
-
-
-def run_edit(h, case, r, noise=None, seed=7, ids=None, use_graph=True):
-    """cmdgen_edit_chain on the same arguments -> [xh_phar, xh_pocket, z_steps, pocket_steps, chain_z], chain status"""
-    pb = r['pb']
-    h.set_layout(pb.num_nodes_phar, pb.size)
-    host_tables(h, case.K)
-    x, q, zs = h.edit_chain(*inputs(r), dev(r['fx']), dev(r['fh']), case.K, start=case.start, resamplings=case.r, jump_length=case.j,
-                            noise=noise, seed=seed, pocket_ids=ids, want_steps=True, use_graph=use_graph)
-    st = h.chain_status()
-    cz = h.debug_read('chain_z', int(sum(case.nph)) * 11)
-    return [t.cpu().numpy() for t in (x, q, zs, h.last_pocket_steps)] + [cz], st
-
-
-def same(a, b):
-    assert len(a) == len(b)
-    for u, v in zip(a, b):
-        assert np.array_equal(u, v)
+def run_edit(h, case, r, **kw):
+    """cmdgen_edit_chain on the same arguments"""
+    ph = r['phar']
+    return run_chain(h, r['pb'], case.K, given=(ph['x'], ph['one_hot'], r['fx'], r['fh']), plan=(case.start, case.r, case.j), **kw)
 
 
 def sub_batch(case, r, members):
     """The samples `members` of a case as a batch of their own: (case, inputs dict, restraint records)."""
-    pb = r['pb']
-    xs, hs = np.split(pb.x, np.cumsum(pb.size)[:-1]), np.split(pb.one_hot, np.cumsum(pb.size)[:-1])
-    size = pb.size[members]
     rows = np.isin(np.repeat(np.arange(len(case.nph)), case.nph), members)
-    sub_pb = PocketBatch(x=np.concatenate([xs[b] for b in members]), one_hot=np.concatenate([hs[b] for b in members]), size=size,
-                         mask=np.repeat(np.arange(len(members), dtype=np.int64), size), num_nodes_phar=pb.num_nodes_phar[members],
-                         pocket_index=pb.pocket_index[members])
+    sub_pb = kit.sub_batch(r['pb'], members)
     sub_case = case._replace(nph=tuple(case.nph[b] for b in members))
     sub_r = dict(pb=sub_pb, phar={'x': r['phar']['x'][rows], 'one_hot': r['phar']['one_hot'][rows]}, fx=r['fx'][rows], fh=r['fh'][rows])
     sub_restraints = [dict(q, sample=members.index(q['sample'])) for q in r['restraints'] if q['sample'] in members]
@@ -88,28 +60,14 @@ def test_chain_matches_the_reference(case, use_graph):
     n_steps = ec.plan(case)[0]
     h = handle()
     h.set_option('graph_steps', 2)                                   # replays of two ops and, where n_steps is odd, an eager op
-    (x, q, zs, ps, en, oe, _), st = run_redit(h, case, r, r['rec'], noise=r['noise'].cuda(), use_graph=use_graph)
+    got, st = run_redit(h, case, r, r['rec'], noise=r['noise'].cuda(), use_graph=use_graph)
     rows, rows_q = keep[np.repeat(np.arange(len(case.nph)), case.nph)], keep[pb.mask]
-    wx, wq = want['xh_phar'].numpy(), want['xh_pocket'].numpy()
-    wzs, wps = want['z_steps'].numpy(), want['pocket_steps'].numpy()
-    assert zs.shape == wzs.shape and ps.shape == wps.shape and oe.shape == (n_steps, len(case.nph))
-    top = lambda got, w: float(np.abs(got - w).max()) / (PARITY * max(1.0, float(np.abs(w).max())))
-    ratios = {
-        'z': max(top(zs[k][rows], wzs[k][rows]) for k in range(n_steps)),
-        'pocket_steps': max(top(ps[k][rows_q], wps[k][rows_q]) for k in range(n_steps)),
-        'x': top(x[rows, :3], wx[rows, :3]),
-        'pocket': top(q[rows_q, :3], wq[rows_q, :3]),
-    }
-    rel = lambda got, w: float((np.abs(got - w) / (PARITY * np.maximum(1.0, np.abs(w)))).max())
-    ratios['energy'] = rel(en[keep, 0], want['energy'].numpy()[keep])
-    ratios['max_violation'] = rel(en[keep, 1], want['max_violation'].numpy()[keep])
-    ratios['op_energy'] = rel(oe[:, keep], want['op_energy'].numpy()[:, keep])
-    print(f'\n[{case.name} {"graph" if use_graph else "eager"}] worst ratio to each bound: ' +
-          '  '.join(f'{k} {v:.3f}' for k, v in ratios.items()) + f'  left out {int((~keep).sum())} of {len(keep)} samples')
-    assert int((~keep).sum()) <= ec.CHAIN_CAP * len(keep)
-    assert all(v <= 1.0 for v in ratios.values()), ratios
-    assert np.array_equal(x[rows, 3:], wx[rows, 3:])
-    assert st['nan_resets'] == 0 and st['max_rel_com_error'] < 1e-2
+    assert got.z_steps.shape == want['z_steps'].shape and got.pocket_steps.shape == want['pocket_steps'].shape
+    assert got.op_energy.shape == (n_steps, len(case.nph))
+    # this kind bounds the final x and pocket by their LARGEST difference, not the RMS of test_hip_restraint.py, and compares the pocket's
+    # coordinates alone: the docstring's "within PARITY relative to max(1, max|.|)" for every output
+    check_against_ref(f'{case.name} {"graph" if use_graph else "eager"}', got, st, want, rows, rows_q, keep, 'samples', final='max',
+                      pocket_cols=slice(0, 3))
     if case.big_sample is not None:
         assert int((pb.size + pb.num_nodes_phar).max()) > 128           # the 1024-thread step ran
 
@@ -128,8 +86,8 @@ def test_without_guidance_it_is_edit_chain_bit_for_bit(case, inject):
     want, sw = run_edit(h, case, r, noise=noise, seed=11, ids=ids)
     none, s0 = run_redit(h, case, r, None, clash=(0.0, 0.0), noise=noise, seed=11, ids=ids)
     zero, s1 = run_redit(h, case, r, r['rec'], scale=0.0, noise=noise, seed=11, ids=ids)
-    same(want, none[:4] + none[6:])
-    same(want, zero[:4] + zero[6:])
+    same(want, none, EDIT)
+    same(want, zero, EDIT)
     assert status_key(sw) == status_key(s0) == status_key(s1) and sw['nan_resets'] == 0
     assert not none[4].any() and not none[5].any()                      # nothing restrains: zero energies
     assert zero[4][:, 0].max() > 0 and zero[5].max() > 0                # scale = 0 still reports them
@@ -147,17 +105,15 @@ def test_without_marks_it_is_restrained_chain_bit_for_bit(case, inject):
     pb = r['pb']
     n_steps = ec.plan(case)[0]
     assert n_steps == case.K and case.start == case.K
-    h = handle('readout0', dict(SMALL, readout_in_coord=0))
+    h = handle(options=dict(SMALL, readout_in_coord=0))
     h.set_option('graph_steps', 2)
     h.set_layout(pb.num_nodes_phar, pb.size)
     assert h.query('readout_in_coord') == 0
     noise = r['noise'].cuda() if inject else None
     rows = [0] + [1 + 2 * i for i in range(n_steps)] + [len(r['noise']) - 1]
-    want, sw = run_restrained(h, pb, r['rec'], case.K, clash=ec.CLASH, noise=noise[rows].contiguous() if inject else None, seed=13,
-                              ids=pb.pocket_index)
-    want_z = h.debug_read('chain_z', int(sum(case.nph)) * 11)
+    want, sw = run_chain(h, pb, case.K, guide=guide(r['rec']), noise=noise[rows].contiguous() if inject else None, seed=13, ids=pb.pocket_index)
     got, sg = run_redit(h, case, r, r['rec'], noise=noise, seed=13, ids=pb.pocket_index, marked=False)
-    same(want + [want_z], got)
+    same(want, got)
     assert status_key(sw) == status_key(sg) and sw['nan_resets'] == 0
     assert want[4][:, 0].max() > 0 and want[5].max() > 0
 
@@ -266,7 +222,7 @@ def test_held_rows_follow_the_given_points():
     for inject in (sub_noise, None):
         got, sg = run_redit(h, sub_case, sub_r, sub_rec, clash=(0.0, 0.0), noise=inject, seed=61)
         want, sw = run_edit(h, sub_case, sub_r, noise=inject, seed=61)
-        same(want, got[:4] + got[6:])
+        same(want, got, EDIT)
         assert status_key(sg) == status_key(sw)
         assert np.all(np.abs(got[5][:, 0] - 4.5) <= PARITY * 4.5) and not got[5][:, 1].any()     # 0.5 k v^2 at the held point's given position, op after op
     # the full batch
@@ -314,14 +270,8 @@ def test_refusals_leave_the_handle_usable():
     h.load_state_dict(make_state_dict(cfg, seed=0))
     h.set_layout(pb.num_nodes_phar, pb.size)
 
-    def record(kind=0, sample=0, i=0, j=0, c=(0.0, 0.0, 0.0), a=1.0, b=0.0, k=1.0):
-        q = np.zeros(1, dtype=rs.RESTRAINT_DTYPE)
-        q['kind'], q['sample'], q['i'], q['j'], q['c'], q['a'], q['b'], q['k'] = kind, sample, i, j, c, a, b, k
-        return q
-
-    def refused(match, rec=None, K=5, **kw):
-        with pytest.raises(hip_backend.CmdgenError, match=match):
-            h.restrained_edit_chain(px, poh, phx, phoh, fx, fx, K, restraints=rec, **kw)
+    refused = lambda match, rec=None, K=5, **kw: kit.refused(                          # the message
+        h, lambda: h.restrained_edit_chain(px, poh, phx, phoh, fx, fx, K, restraints=rec, **kw), match, code=None)
 
     # what cmdgen_restrained_chain refuses: one per argument class
     refused('unknown kind', record(kind=3))
@@ -376,7 +326,7 @@ def test_edit_restrained_returns_the_chains_result():
     pb = r['pb']
     ddpm = model()
     ddpm.use_hip_graph = True
-    pocket = {'x': dev(pb.x), 'one_hot': dev(pb.one_hot), 'size': dev(pb.size), 'mask': dev(pb.mask)}
+    pocket = pocket_dev(pb)
     phar = {k: v.cuda() for k, v in r['phar'].items()}
     noise = r['noise'].cuda()
     kw = dict(fix_coords=r['fx'], fix_types=r['fh'], start=case.start, resamplings=case.r, jump_length=case.j, timesteps=case.K, noise=noise)
@@ -396,12 +346,7 @@ def test_edit_phars_restrained_end_to_end():
     """PharPocketDDPM.edit_phars_restrained on the g7 pocket: three given points kept, two grown under a distance window from point 0 and a
     position restraint; per-sample point lists in the PDB's frame with the given points where they were, the two diagnostics, the same seed
     the same result, and less energy than the unguided edit on the same draws."""
-    from cmdgen_amd.lightning_modules import PharPocketDDPM
-    from test_oracle_golden_r2 import _hparams
-    m = PharPocketDDPM(**_hparams('CA', 64, 2))
-    sd = make_state_dict(ModelConfig(hidden_nf=64, n_layers=2, timesteps=500), seed=0)
-    m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
-    m = m.cuda()
+    m = lightning_model()
     pdb = os.path.join(GOLDEN, 'g7_pocket.pdb')
     ids = [f'A:{i}' for i in range(1, 30)]
     names = list(m.dataset_info['phar_decoder'])

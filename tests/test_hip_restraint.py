@@ -12,83 +12,21 @@ import pytest
 import torch
 
 import restraint_cases as rc
-from helpers import rms, GOLDEN
+import chain_kit as kit
+from chain_kit import (GUIDED, PLAIN, SMALL, check_against_ref, dev, guide, handle, lightning_model, model, pocket_dev, record, run_chain, same,
+                       status_key, sub_batch)
+from helpers import GOLDEN
 from cmdgen_amd import hip_backend
 from cmdgen_amd import restraints as rs
 from cmdgen_amd.synthetic import ModelConfig, PocketBatch, make_state_dict, make_pockets
 
 pytestmark = pytest.mark.gpu
 
-SMALL = dict(node_mt=16, node64=0, coord_mt=32)        # the launches readout_in_coord needs, forced on a small layout (test_hip_readout_in_coord.py)
-_handles, _model = {}, []
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def handle(key='default', options=None):
-    """The bounded model of the chain tests on the default engine; one handle per set of options."""
-    if key not in _handles:
-        h = hip_backend.Handle(rc.config().as_dict(), 0)
-        h.load_state_dict(rc.state_dict())
-        for k, v in (options or {}).items():
-            h.set_option(k, v)
-        _handles[key] = h
-    return _handles[key]
-
-
-def model():
-    if not _model:
-        from cmdgen_amd.equivariant_diffusion.dynamics import EGNNDynamics
-        from cmdgen_amd.equivariant_diffusion.conditional_model import ConditionalDDPM
-        cfg = rc.config()
-        dyn = EGNNDynamics(phar_nf=cfg.phar_nf, residue_nf=cfg.residue_nf, n_dims=3, joint_nf=cfg.joint_nf, hidden_nf=cfg.hidden_nf,
-                           n_layers=cfg.n_layers, attention=True, tanh=True, norm_constant=1, inv_sublayers=1, sin_embedding=False,
-                           normalization_factor=100, aggregation_method='sum', edge_cutoff=6.0, update_pocket_coords=False)
-        ddpm = ConditionalDDPM(dynamics=dyn, phar_nf=cfg.phar_nf, residue_nf=cfg.residue_nf, n_dims=3, timesteps=cfg.timesteps,
-                               noise_schedule=cfg.noise_schedule, noise_precision=cfg.noise_precision, loss_type='l2',
-                               norm_values=list(cfg.norm_values), size_histogram=np.ones((30, 70)))
-        ddpm.load_state_dict({k[len('ddpm.'):]: torch.from_numpy(v) for k, v in rc.state_dict().items()}, strict=True)
-        _model.append(ddpm.cuda())
-    return _model[0]
-
-
-def host_tables(h, K):
-    """The step table and the guide table in the reference's own fp32 ops, as ConditionalDDPM.sample_restrained supplies them."""
-    ddpm = model()
-    h.set_step_table(K, ddpm.step_table(K))
-    h.set_guide_table(K, ddpm.guide_table(K))
-
-
-def run_restrained(h, pb, rec, K, clash=rc.CLASH, scale=rc.SCALE, max_shift=rc.MAX_SHIFT, guide_below=1.0, noise=None, seed=7, ids=None,
-                   use_graph=True):
-    """-> [xh_phar, xh_pocket, z_steps, pocket_steps, energy [B, 2], op_energy [K, B]] as numpy, chain status"""
-    h.set_layout(pb.num_nodes_phar, pb.size)
-    host_tables(h, K)
-    out = h.restrained_chain(dev(pb.x), dev(pb.one_hot), K, rec, clash_radius=clash[0], clash_k=clash[1], scale=scale, max_shift=max_shift,
-                             guide_below=guide_below, noise=noise, seed=seed, pocket_ids=ids, want_steps=True, use_graph=use_graph)
-    st = h.chain_status()
-    x, q, zs, en, oe = out
-    return [t.cpu().numpy() for t in (x, q, zs, h.last_pocket_steps, en, oe)], st
-
-
-def run_plain(h, pb, K, noise=None, seed=7, ids=None, use_graph=True):
-    h.set_layout(pb.num_nodes_phar, pb.size)
-    host_tables(h, K)
-    x, q, zs = h.sample_chain(dev(pb.x), dev(pb.one_hot), K, noise=noise, seed=seed, pocket_ids=ids, want_steps=True, use_graph=use_graph)
-    st = h.chain_status()
-    return [t.cpu().numpy() for t in (x, q, zs, h.last_pocket_steps)], st
-
-
-def status_key(st):
-    return (st['max_rel_com_error'], st['max_cog'], st['nan_resets'])
-
 
 # ------------------------------------------------------------------------------------------------ 1. against the reference
 def own_velocity_handle():
     """The launches under which the step kernel forms the velocity and the NaN flag itself (readout_in_coord), forced on a small layout."""
-    return handle('readout1', dict(SMALL, readout_in_coord=1))
+    return handle(options=dict(SMALL, readout_in_coord=1))
 
 
 @pytest.mark.parametrize('use_graph', [True, False], ids=['graph', 'eager'])
@@ -100,27 +38,10 @@ def test_chain_matches_the_reference(case, own_vel, use_graph):
     h.set_option('graph_steps', 2)                                   # K = 5: two replays of two steps, one eager step
     h.set_layout(pb.num_nodes_phar, pb.size)
     assert h.query('readout_in_coord') == int(own_vel)
-    (x, q, zs, ps, en, oe), st = run_restrained(h, pb, r['rec'], rc.K, noise=r['noise'].cuda(), use_graph=use_graph)
+    got, st = run_chain(h, pb, rc.K, guide=guide(r['rec']), noise=r['noise'].cuda(), use_graph=use_graph)
     rows, rows_q = keep[np.repeat(np.arange(len(case.nph)), case.nph)], keep[pb.mask]
-    wx, wq = want['xh_phar'].numpy(), want['xh_pocket'].numpy()
-    wzs, wps = want['z_steps'].numpy(), want['pocket_steps'].numpy()
-    ratios = {
-        'z': max(float(np.abs(zs[k][rows] - wzs[k][rows]).max()) / (1e-4 * max(1.0, float(np.abs(wzs[k][rows]).max()))) for k in range(rc.K)),
-        'pocket_steps': max(float(np.abs(ps[k][rows_q] - wps[k][rows_q]).max()) / (1e-4 * max(1.0, float(np.abs(wps[k][rows_q]).max())))
-                            for k in range(rc.K)),
-        'x': rms(x[rows, :3], wx[rows, :3]) / (1e-4 * max(1.0, float(np.abs(wx[rows, :3]).max()))),
-        'pocket': rms(q[rows_q], wq[rows_q]) / (1e-4 * max(1.0, float(np.abs(wq[rows_q]).max()))),
-    }
-    rel = lambda got, w: float((np.abs(got - w) / (1e-4 * np.maximum(1.0, np.abs(w)))).max())
-    ratios['energy'] = rel(en[keep, 0], want['energy'].numpy()[keep])
-    ratios['max_violation'] = rel(en[keep, 1], want['max_violation'].numpy()[keep])
-    ratios['op_energy'] = rel(oe[:, keep], want['op_energy'].numpy()[:, keep])
-    print(f'\n[{case.name} {"graph" if use_graph else "eager"}] worst ratio to each bound: ' +
-          '  '.join(f'{k} {v:.3f}' for k, v in ratios.items()) + f'  left out {int((~keep).sum())} of {len(keep)} samples')
-    assert int((~keep).sum()) <= rc.CHAIN_CAP * len(keep)
-    assert all(v <= 1.0 for v in ratios.values()), ratios
-    assert np.array_equal(x[rows, 3:], wx[rows, 3:])
-    assert st['nan_resets'] == 0 and st['max_rel_com_error'] < 1e-2
+    # the final x and pocket by their RMS, the pocket over its whole row (test_hip_edit.py's bounds); at most CHAIN_CAP of the samples left out
+    check_against_ref(f'{case.name} {"graph" if use_graph else "eager"}', got, st, want, rows, rows_q, keep, 'samples', final='rms')
     if case.big_sample is not None:
         assert int((pb.size + pb.num_nodes_phar).max()) > 128           # the 1024-thread step ran
 
@@ -133,7 +54,7 @@ def test_without_guidance_it_is_sample_chain_bit_for_bit(readout, inject, use_gr
     """No restraint and r_c = 0, and scale = 0 with restraints and the clash term present: xh_phar, xh_pocket, z_steps, pocket_steps and the
     chain status of cmdgen_sample_chain, with the evaluations' own k_readout and with the step kernel forming the velocity itself."""
     K = 10
-    h = handle(f'readout{readout}', dict(SMALL, readout_in_coord=readout))
+    h = handle(options=dict(SMALL, readout_in_coord=readout))
     h.set_option('graph_steps', 8)
     pb = make_pockets(6, 'CA', ragged=True, first_index=9500)
     nph = 1 + (np.arange(6, dtype=np.int64) * 3) % 8
@@ -145,16 +66,16 @@ def test_without_guidance_it_is_sample_chain_bit_for_bit(readout, inject, use_gr
                   {'kind': 'distance', 'sample': 2, 'points': (0, 3), 'lo': 5.0, 'hi': 7.0, 'k': 1.0},
                   {'kind': 'exclusion', 'sample': 5, 'center': (0.0, 0.0, 0.0), 'radius': 4.0, 'k': 1.0}]
     rec = rs.records(restraints, nph)
-    want, sw = run_plain(h, pb, K, noise=noise, seed=11, ids=pb.pocket_index, use_graph=use_graph)
-    none, s0 = run_restrained(h, pb, None, K, clash=(0.0, 0.0), noise=noise, seed=11, ids=pb.pocket_index, use_graph=use_graph)
-    zero, s1 = run_restrained(h, pb, rec, K, scale=0.0, noise=noise, seed=11, ids=pb.pocket_index, use_graph=use_graph)
-    for a, b, c in zip(want, none, zero):
-        assert np.array_equal(a, b)
-        assert np.array_equal(a, c)
+    kw = dict(noise=noise, seed=11, ids=pb.pocket_index, use_graph=use_graph)
+    want, sw = run_chain(h, pb, K, **kw)
+    none, s0 = run_chain(h, pb, K, guide=guide(None, clash=(0.0, 0.0)), **kw)
+    zero, s1 = run_chain(h, pb, K, guide=guide(rec, scale=0.0), **kw)
+    same(want, none, PLAIN)
+    same(want, zero, PLAIN)
     assert status_key(sw) == status_key(s0) == status_key(s1) and sw['nan_resets'] == 0
     assert not none[4].any() and not none[5].any()                      # nothing restrains: zero energies
     assert zero[4][:, 0].max() > 0 and zero[5].max() > 0                # scale = 0 still reports them
-    guided, _ = run_restrained(h, pb, rec, K, noise=noise, seed=11, ids=pb.pocket_index, use_graph=use_graph)
+    guided, _ = run_chain(h, pb, K, guide=guide(rec), **kw)
     assert not np.array_equal(guided[0], want[0])                       # ... and the guidance is not a no-op here
 
 
@@ -167,29 +88,26 @@ def test_captured_equals_eager_and_a_changed_table_prepares_the_slot_again():
     pb = r['pb']
     h = own_velocity_handle()
     h.set_option('graph_steps', 2)
-    a, sa = run_restrained(h, pb, r['rec'], rc.K, seed=31, use_graph=True)
+    a, sa = run_chain(h, pb, rc.K, guide=guide(r['rec']), seed=31, use_graph=True)
     assert h.query('chain_graphs') >= 1
-    a2, sa2 = run_restrained(h, pb, r['rec'], rc.K, seed=31, use_graph=True)
-    e, se = run_restrained(h, pb, r['rec'], rc.K, seed=31, use_graph=False)
-    for u, v, w in zip(a, a2, e):
-        assert np.array_equal(u, v)
-        assert np.array_equal(u, w)
+    a2, sa2 = run_chain(h, pb, rc.K, guide=guide(r['rec']), seed=31, use_graph=True)
+    e, se = run_chain(h, pb, rc.K, guide=guide(r['rec']), seed=31, use_graph=False)
+    same(a, a2, GUIDED)
+    same(a, e, GUIDED)
     assert status_key(sa) == status_key(sa2) == status_key(se) and sa['nan_resets'] == 0
     other = [dict(q) for q in r['restraints']]
     for q in other:
         if q['kind'] == 'position':
             q['center'] = tuple(v + 2.0 for v in q['center'])
     rec_b = rs.records(other, case.nph)
-    b, _ = run_restrained(h, pb, rec_b, rc.K, seed=31, use_graph=True)
-    b_eager, _ = run_restrained(h, pb, rec_b, rc.K, seed=31, use_graph=False)
+    b, _ = run_chain(h, pb, rc.K, guide=guide(rec_b), seed=31, use_graph=True)
+    b_eager, _ = run_chain(h, pb, rc.K, guide=guide(rec_b), seed=31, use_graph=False)
     assert not np.array_equal(a[0], b[0])
-    for u, v in zip(b, b_eager):
-        assert np.array_equal(u, v)
-    c, _ = run_restrained(h, pb, r['rec'], rc.K, clash=(rc.CLASH[0], 2.0), seed=31, use_graph=True)      # a scalar of the key alone
+    same(b, b_eager, GUIDED)
+    c, _ = run_chain(h, pb, rc.K, guide=guide(r['rec'], clash=(rc.CLASH[0], 2.0)), seed=31, use_graph=True)      # a scalar of the key alone
     assert not np.array_equal(a[0], c[0])
-    back, sb = run_restrained(h, pb, r['rec'], rc.K, seed=31, use_graph=True)
-    for u, v in zip(a, back):
-        assert np.array_equal(u, v)
+    back, sb = run_chain(h, pb, rc.K, guide=guide(r['rec']), seed=31, use_graph=True)
+    same(a, back, GUIDED)
     assert status_key(sa) == status_key(sb)
 
 
@@ -202,14 +120,12 @@ def test_a_shard_gives_the_full_batchs_rows():
     pb = r['pb']
     members = [2, 3, 4]
     h = handle()
-    (xf, _, _, _, ef, _), _ = run_restrained(h, pb, r['rec'], rc.K, seed=41, ids=pb.pocket_index)
-    xs, hs = np.split(pb.x, np.cumsum(pb.size)[:-1]), np.split(pb.one_hot, np.cumsum(pb.size)[:-1])
-    size = pb.size[members]
-    sub = PocketBatch(x=np.concatenate([xs[b] for b in members]), one_hot=np.concatenate([hs[b] for b in members]), size=size,
-                      mask=np.repeat(np.arange(len(members), dtype=np.int64), size), num_nodes_phar=pb.num_nodes_phar[members],
-                      pocket_index=pb.pocket_index[members])
+    full, _ = run_chain(h, pb, rc.K, guide=guide(r['rec']), seed=41, ids=pb.pocket_index)
+    xf, ef = full.xh_phar, full.energy
+    sub = sub_batch(pb, members)
     sub_restraints = [dict(q, sample=members.index(q['sample'])) for q in r['restraints'] if q['sample'] in members]
-    (xsub, _, _, _, esub, _), _ = run_restrained(h, sub, rs.records(sub_restraints, sub.num_nodes_phar), rc.K, seed=41, ids=sub.pocket_index)
+    alone, _ = run_chain(h, sub, rc.K, guide=guide(rs.records(sub_restraints, sub.num_nodes_phar)), seed=41, ids=sub.pocket_index)
+    xsub, esub = alone.xh_phar, alone.energy
     rows = np.isin(np.repeat(np.arange(len(case.nph)), case.nph), members)
     diff = float(np.abs(xsub[:, :3] - xf[rows, :3]).max())
     print(f'\n[shard] max |dx| {diff:.3e} A, bound {1e-4 * max(1.0, float(np.abs(xf[rows, :3]).max())):.3e}; energies {esub[:, 0]} / {ef[members, 0]}')
@@ -223,14 +139,13 @@ def test_guide_below_zero_equals_scale_zero():
     case = rc.MIXED
     r = rc.reference(case)
     h = own_velocity_handle()
-    a, sa = run_restrained(h, r['pb'], r['rec'], rc.K, guide_below=0.0, seed=51)
-    b, sb = run_restrained(h, r['pb'], r['rec'], rc.K, scale=0.0, seed=51)
-    for u, v in zip(a, b):
-        assert np.array_equal(u, v)
+    a, sa = run_chain(h, r['pb'], rc.K, guide=guide(r['rec'], guide_below=0.0), seed=51)
+    b, sb = run_chain(h, r['pb'], rc.K, guide=guide(r['rec'], scale=0.0), seed=51)
+    same(a, b, GUIDED)
     assert status_key(sa) == status_key(sb)
     # ... and a threshold between two ops guides only the ops at or below it: t / T = 1, .8, .6 unguided, .4 and .2 guided
-    part, _ = run_restrained(h, r['pb'], r['rec'], rc.K, guide_below=0.5, seed=51)
-    full, _ = run_restrained(h, r['pb'], r['rec'], rc.K, seed=51)
+    part, _ = run_chain(h, r['pb'], rc.K, guide=guide(r['rec'], guide_below=0.5), seed=51)
+    full, _ = run_chain(h, r['pb'], rc.K, guide=guide(r['rec']), seed=51)
     assert np.array_equal(part[2][:3], b[2][:3]) and not np.array_equal(part[2][3], b[2][3]) and not np.array_equal(part[2][0], full[2][0])
 
 
@@ -240,8 +155,8 @@ def test_guidance_lowers_the_energy_of_every_restrained_sample():
     r = rc.reference(case)
     h = handle()
     noise = r['noise'].cuda()
-    g, _ = run_restrained(h, r['pb'], r['rec'], rc.K, noise=noise)
-    u, _ = run_restrained(h, r['pb'], r['rec'], rc.K, scale=0.0, noise=noise)
+    g, _ = run_chain(h, r['pb'], rc.K, guide=guide(r['rec']), noise=noise)
+    u, _ = run_chain(h, r['pb'], rc.K, guide=guide(r['rec'], scale=0.0), noise=noise)
     restrained = np.isin(np.arange(len(case.nph)), [q['sample'] for q in r['restraints']]) & r['keep']
     print(f'\n[effect] final energy unguided {u[4][:, 0]}\n         guided   {g[4][:, 0]}\n         largest violation (A) unguided {u[4][:, 1]}\n'
           f'         guided   {g[4][:, 1]}')
@@ -259,14 +174,7 @@ def test_refusals_leave_the_handle_usable():
     h.load_state_dict(make_state_dict(cfg, seed=0))
     h.set_layout(pb.num_nodes_phar, pb.size)
 
-    def record(kind=0, sample=0, i=0, j=0, c=(0.0, 0.0, 0.0), a=1.0, b=0.0, k=1.0):
-        q = np.zeros(1, dtype=rs.RESTRAINT_DTYPE)
-        q['kind'], q['sample'], q['i'], q['j'], q['c'], q['a'], q['b'], q['k'] = kind, sample, i, j, c, a, b, k
-        return q
-
-    def refused(match, rec=None, **kw):
-        with pytest.raises(hip_backend.CmdgenError, match=match):
-            h.restrained_chain(px, poh, 5, rec, **kw)
+    refused = lambda match, rec=None, **kw: kit.refused(h, lambda: h.restrained_chain(px, poh, 5, rec, **kw), match, code=None)   # the message
 
     refused('unknown kind', record(kind=3))
     refused('unknown kind', record(kind=-1))
@@ -341,11 +249,11 @@ def test_sample_restrained_returns_the_chains_result():
     pb = r['pb']
     ddpm = model()
     ddpm.use_hip_graph = True
-    pocket = {'x': dev(pb.x), 'one_hot': dev(pb.one_hot), 'size': dev(pb.size), 'mask': dev(pb.mask)}
+    pocket = pocket_dev(pb)
     noise = r['noise'].cuda()
     x, q, pm, qm, info = ddpm.sample_restrained(pocket, case.nph, r['restraints'], clash=rc.CLASH, scale=rc.SCALE, max_shift=rc.MAX_SHIFT,
                                                timesteps=rc.K, noise=noise)
-    want, _ = run_restrained(ddpm.dynamics.hip_handle(), pb, r['rec'], rc.K, noise=noise)
+    want, _ = run_chain(ddpm.dynamics.hip_handle(), pb, rc.K, guide=guide(r['rec']), noise=noise)
     assert np.array_equal(x.cpu().numpy(), want[0]) and np.array_equal(q.cpu().numpy(), want[1])
     assert np.array_equal(info['energy'].cpu().numpy(), want[4][:, 0]) and np.array_equal(info['max_violation'].cpu().numpy(), want[4][:, 1])
     assert 'op_energy' not in info and pm.shape == (sum(case.nph),)
@@ -363,12 +271,7 @@ def test_sample_restrained_returns_the_chains_result():
 def test_generate_phars_restrained_end_to_end():
     """PharPocketDDPM.generate_phars_restrained on the g7 pocket (30 C-alpha residues): per-sample point lists in the PDB's frame, the two
     diagnostics, the same seed the same result, and the guided samples closer to the query than the unguided ones on the same draws."""
-    from cmdgen_amd.lightning_modules import PharPocketDDPM
-    from test_oracle_golden_r2 import _hparams
-    m = PharPocketDDPM(**_hparams('CA', 64, 2))
-    sd = make_state_dict(ModelConfig(hidden_nf=64, n_layers=2, timesteps=500), seed=0)
-    m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
-    m = m.cuda()
+    m = lightning_model()
     pdb = os.path.join(GOLDEN, 'g7_pocket.pdb')
     ids = [f'A:{i}' for i in range(1, 30)]
     spot = (9.0, 2.0, -15.0)

@@ -22,15 +22,11 @@ import pytest
 import torch
 
 import rule_sweep_ref as rs
-from helpers import rms
-from test_hip_parity_r2 import EVAL_TOL
+from helpers import EVAL_TOL, rms
+from chain_kit import dev
 from cmdgen_amd import hip_backend
 
 pytestmark = pytest.mark.gpu
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def new_handle(case):

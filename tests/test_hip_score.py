@@ -15,48 +15,26 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import GOLDEN, HIST, dynamics_case, load_golden
+from helpers import GOLDEN, HIST, RANGE_NAME, RANGE_TARGETS, SCORE_BAND as BAND, SCORE_CASES as CASES, g2, g21, overflow_case, score_case
 import score_ref
+from chain_kit import dev, lightning_model, model_for, philox_noise, score_entry_ratios as entry_ratios, to_dev
 from oracle import ref_cpu
 from cmdgen_amd import hip_backend
 from cmdgen_amd.synthetic import ModelConfig, make_pockets, make_state_dict
 from bench import bounded_config
-from test_score_cpu import BAND, CASES, G21, score_case
 
 pytestmark = pytest.mark.gpu
 
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+G21 = g21()
 
 
-def to_dev(d):
-    return {k: v.cuda() for k, v in d.items()}
-
-
-def model_for(cfg, sd, hist=HIST):
-    from cmdgen_amd.equivariant_diffusion.dynamics import EGNNDynamics
-    from cmdgen_amd.equivariant_diffusion.conditional_model import ConditionalDDPM
-    dyn = EGNNDynamics(phar_nf=cfg.phar_nf, residue_nf=cfg.residue_nf, n_dims=3, joint_nf=cfg.joint_nf, hidden_nf=cfg.hidden_nf,
-                       n_layers=cfg.n_layers, attention=True, tanh=True, norm_constant=1, inv_sublayers=1, sin_embedding=False,
-                       normalization_factor=100, aggregation_method='sum', edge_cutoff=6.0, update_pocket_coords=False)
-    ddpm = ConditionalDDPM(dynamics=dyn, phar_nf=cfg.phar_nf, residue_nf=cfg.residue_nf, n_dims=3, timesteps=cfg.timesteps,
-                           noise_schedule=cfg.noise_schedule, noise_precision=cfg.noise_precision, loss_type='l2',
-                           norm_values=list(cfg.norm_values), size_histogram=hist)
-    ddpm.load_state_dict({k[len('ddpm.'):]: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
-    return ddpm.cuda().eval()
+def score_model(cfg, sd, hist=HIST):
+    """The model as ddpm.forward's comparisons need it: in eval mode, with the goldens' size histogram."""
+    return model_for(cfg, sd, hist).eval()
 
 
 def case_arrays(case):
     return {k[len(case) + 1:]: v for k, v in G21.items() if k.startswith(case + '/')}
-
-
-def entry_ratios(sums, want_err, want_l0x, netmax, n_rows, keep, P=8):
-    """|got - want| / bound of every kept entry: error_t of the K levels and loss_0_x of the t = 0 level.  sums [K + 1, B, 4]."""
-    K = len(want_err)
-    r_t = np.abs(sums[:K, :, 0].astype(np.float64) - want_err) / score_ref.error_bound(want_err, netmax[:K], n_rows, 3 + P)
-    r_0 = np.abs(0.5 * sums[K, :, 1].astype(np.float64) - want_l0x) / (0.5 * score_ref.error_bound(2.0 * want_l0x, netmax[K], n_rows, 3))
-    return np.concatenate([r_t[keep[:K]], r_0[keep[K]]])
 
 
 @pytest.mark.parametrize('use_graph', [True, False])
@@ -66,7 +44,7 @@ def test_score_matches_g21(case, use_graph):
     cfg, sd, phar, pocket = score_case()
     g = case_arrays(case)
     K = int(case[1:])
-    ddpm = model_for(cfg, sd)
+    ddpm = score_model(cfg, sd)
     ddpm.use_hip_graph = use_graph
     out = ddpm.score(to_dev(phar), to_dev(pocket), timesteps=K, noise=dev(g['noise']), return_levels=True)
     out = {k: v.cpu().numpy() for k, v in out.items()}
@@ -101,7 +79,7 @@ def test_score_and_forward_are_two_routes_through_the_same_kernels():
     cfg, sd, phar, pocket = score_case()
     g = case_arrays(case)
     K = 20
-    ddpm = model_for(cfg, sd)
+    ddpm = score_model(cfg, sd)
     ph, pk = to_dev(phar), to_dev(pocket)
     out = ddpm.score(ph, pk, timesteps=K, noise=dev(g['noise']), return_levels=True)
     sums = out['level_sums'][0].cpu().numpy()
@@ -130,7 +108,7 @@ def test_levels_are_independent():
     """3. With injected draws the K = 20 entries are bit-identical to the matching entries of the K = 100 run."""
     cfg, sd, phar, pocket = score_case()
     g = case_arrays('K100')
-    ddpm = model_for(cfg, sd)
+    ddpm = score_model(cfg, sd)
     ph, pk = to_dev(phar), to_dev(pocket)
     full = ddpm.score(ph, pk, timesteps=100, noise=dev(g['noise']), return_levels=True)
     pick = [5 * (j + 1) - 1 for j in range(20)] + [100]
@@ -201,24 +179,17 @@ def test_graph_runs_equal_eager_runs_while_chains_alternate():
     h.close()
 
 
-def _philox_noise(h, seed, ids, nl, n_levels, width=11):
-    rows = []
-    for k in range(n_levels):
-        rows.append(torch.cat([h.debug_noise(seed, int(i), k, int(n), width) for i, n in zip(ids, nl)]))
-    return torch.stack(rows).contiguous()
-
-
 def test_device_draws():
     """5. noise=None equals the run that injects the same Philox draws (cmdgen_debug_noise) bit for bit; two seeds differ; a batch
     scored in two shards with global pocket ids gives the whole batch's entries within item 1's bound."""
     cfg, sd, phar, pocket = score_case()
-    ddpm = model_for(cfg, sd)
+    ddpm = score_model(cfg, sd)
     ph, pk = to_dev(phar), to_dev(pocket)
     K, B = 20, len(phar['size'])
     nl = phar['size'].numpy()
     a = ddpm.score(ph, pk, timesteps=K, seed=11, return_levels=True)
     h = ddpm.dynamics.hip_handle()
-    noise = _philox_noise(h, 11, range(B), nl, K + 1)
+    noise = philox_noise(h, 11, range(B), nl, range(K + 1))
     b = ddpm.score(ph, pk, timesteps=K, noise=noise, return_levels=True)
     assert torch.equal(a['level_sums'], b['level_sums']) and torch.equal(a['nll'], b['nll'])
     c = ddpm.score(ph, pk, timesteps=K, seed=12, return_levels=True)
@@ -256,30 +227,12 @@ def test_device_draws():
 
 
 # ---------------------------------------------------------------- 6. the half engine's range (recipe of tests/test_hip_half_range.py)
-G2 = load_golden('g2_dynamics.npz')
-NAME = 'ca_h256_b8'
-FACTOR = 3.0e6           # first-layer gain: the hidden activation of the targeted MLP passes 65504, far below fp32's 3e38
-TARGETS = {
-    'msg': 'ddpm.dynamics.egnn.e_block_1.gcl_0.edge_mlp.0',
-    'coord': 'ddpm.dynamics.egnn.e_block_1.gcl_equiv.coord_mlp.0',
-    'node': 'ddpm.dynamics.egnn.e_block_1.gcl_0.node_mlp.0',
-}
-
-
-def overflow_case(target):
-    cfg, sd, inp = dynamics_case(G2, NAME)
-    sd = dict(sd)
-    for suffix in ('.weight', '.bias'):
-        sd[TARGETS[target] + suffix] = (sd[TARGETS[target] + suffix] * FACTOR).astype(np.float32)
-    return cfg, sd, inp
-
-
-@pytest.mark.parametrize('target', list(TARGETS))
+@pytest.mark.parametrize('target', list(RANGE_TARGETS))
 def test_range_guard(target):
     """The raw score_chain on the half engine reports reset levels; ddpm.score warns, re-runs on the bf16 engine and meets item 1's
     bound against the oracle.  (The guard's normal path, as in the existing range tests.)"""
     cfg, sd, inp = overflow_case(target)
-    nl, npk = G2[NAME + '/num_nodes_phar'], G2[NAME + '/pocket_size']
+    nl, npk = g2()[RANGE_NAME + '/num_nodes_phar'], g2()[RANGE_NAME + '/pocket_size']
     B = len(nl)
     pm, qm = inp['mask_phar'], inp['mask_pocket']
     phar = {'x': torch.from_numpy(inp['xh_phar'][:, :3].copy()),
@@ -309,7 +262,7 @@ def test_range_guard(target):
     assert st['nan_resets'] >= 1 and st['nan_resets'] == int(terms[:, 0, 3].sum())
     h.close()
     # 2. the mirror: warning, bf16 re-run, oracle-equal entries
-    ddpm = model_for(cfg, sd, hist=np.ones((30, 70)))
+    ddpm = score_model(cfg, sd, hist=np.ones((30, 70)))
     with pytest.warns(RuntimeWarning, match='half matrix engine'):
         out = ddpm.score(to_dev(phar), to_dev(pocket), timesteps=K, noise=dev(noise), return_levels=True)
     st = ddpm.last_chain_status
@@ -324,17 +277,8 @@ def test_range_guard(target):
 
 
 # ---------------------------------------------------------------- 7. the driver
-def _lightning_model():
-    from cmdgen_amd.lightning_modules import PharPocketDDPM
-    from test_oracle_golden_r2 import _hparams
-    model = PharPocketDDPM(**_hparams('CA', 64, 2))
-    sd = make_state_dict(ModelConfig(hidden_nf=64, n_layers=2, timesteps=500), seed=0)
-    model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
-    return model.cuda().eval()
-
-
 def test_driver_entries():
-    model = _lightning_model()
+    model = lightning_model().eval()
     cfg, sd, phar, pocket = score_case()
     data = {'phar_coords': phar['x'], 'phar_one_hot': phar['one_hot'], 'num_phar_atoms': phar['size'], 'phar_mask': phar['mask'],
             'pocket_c_alpha': pocket['x'], 'pocket_one_hot': pocket['one_hot'], 'num_pocket_nodes': pocket['size'],
@@ -381,7 +325,7 @@ def test_driver_entries():
     # the oracle's max |net| at these draws for the bound
     h = model.ddpm.dynamics.hip_handle()
     h.set_layout([3], [int(pocket1['size'][0])])
-    noise1 = _philox_noise(h, 5, [0], [3], 11).cpu().numpy()
+    noise1 = philox_noise(h, 5, [0], [3], range(11)).cpu().numpy()
     cfg500 = ModelConfig(hidden_nf=64, n_layers=2, timesteps=500)
     p = ref_cpu.to_torch_params(make_state_dict(cfg500, seed=0))
     cpu = lambda d: {k: v.cpu() for k, v in d.items()}

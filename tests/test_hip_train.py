@@ -10,33 +10,12 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import load_golden, loss_case, HIST
+from helpers import GRAD_TOL, HIST, _bench_trainer, build_trainer, case_inputs, dev, flat_theta, load_golden, loss_case, make_handle
 from oracle import ref_cpu
 from cmdgen_amd import hip_backend
 from cmdgen_amd.synthetic import ModelConfig, make_state_dict, make_pockets, min_cutoff_margin
 
 pytestmark = pytest.mark.gpu
-GRAD_TOL = 2e-4
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def make_handle(cfg):
-    return hip_backend.Handle(cfg.as_dict(), 0)
-
-
-def flat_theta(h, sd):
-    theta = torch.zeros(h.param_count(), dtype=torch.float32)
-    for k, v in sd.items():
-        name = k[len('ddpm.dynamics.'):] if k.startswith('ddpm.dynamics.') else None
-        if name is None:
-            continue
-        off, cnt = h.param_offset(name)
-        assert cnt == v.size
-        theta[off:off + cnt] = torch.from_numpy(v.reshape(-1))
-    return theta.cuda()
 
 
 # ------------------------------------------------------------------ the GEMM
@@ -97,20 +76,6 @@ def test_training_gemm_dispatch_table(M, N, K, kt):
 
 
 # ------------------------------------------------------------------ forward
-def case_inputs(cfg, B, first, rng, spread=3.0):
-    while True:
-        pb = make_pockets(B, 'CA', ragged=True, first_index=first)
-        nl = pb.num_nodes_phar
-        pm = np.repeat(np.arange(B), nl)
-        com = np.stack([pb.x[pb.mask == b].mean(0) for b in range(B)])
-        xp = (com[pm] + rng.normal(size=(len(pm), 3)) * spread).astype(np.float32)
-        if min_cutoff_margin(np.concatenate([xp, pb.x]), np.concatenate([pm, pb.mask]), 6.0) > 2e-3:
-            break
-        first += 13
-    xh_phar = np.concatenate([xp, rng.normal(size=(len(pm), cfg.phar_nf)).astype(np.float32)], 1)
-    xh_pocket = np.concatenate([pb.x, pb.one_hot / cfg.norm_values[1]], 1).astype(np.float32)
-    t = rng.uniform(size=(B, 1)).astype(np.float32)
-    return pb, pm, xh_phar, xh_pocket, t
 
 
 @pytest.mark.parametrize('H,L,B,kw', [(64, 2, 3, {}), (256, 5, 4, {}), (128, 3, 2, {'attention': False, 'tanh': False}),
@@ -203,33 +168,6 @@ def test_weight_gradient_launch(mode):
 
 
 # ------------------------------------------------------------------ the reference's training step (G11)
-def build_trainer(lr=1e-3, inv_sublayers=1, aggregation_method='sum'):
-    from argparse import Namespace
-    from cmdgen_amd.lightning_modules import PharPocketDDPM
-    from cmdgen_amd.training import HipTrainer
-    g6 = load_golden('g6_loss.npz')
-    cfg, sd, phar, pocket, hist = loss_case(g6)
-    if inv_sublayers != 1 or aggregation_method != 'sum':
-        import dataclasses
-        cfg = dataclasses.replace(cfg, inv_sublayers=inv_sublayers, aggregation_method=aggregation_method)
-        sd = make_state_dict(cfg, seed=int(g6['meta'][4]), coord_gain=1.0)
-    hp = dict(outdir='out', dataset='crossdock', datadir='data', batch_size=4, lr=lr,
-              egnn_params=Namespace(device='cuda', edge_cutoff=6.0, joint_nf=32, hidden_nf=cfg.hidden_nf,
-                                    n_layers=cfg.n_layers, attention=True, tanh=True, norm_constant=1, inv_sublayers=inv_sublayers,
-                                    sin_embedding=False, aggregation_method=aggregation_method, normalization_factor=100),
-              diffusion_params=Namespace(diffusion_steps=500, diffusion_noise_schedule='polynomial_2',
-                                         diffusion_noise_precision=1e-5, diffusion_loss_type='l2',
-                                         normalize_factors=[1, 4]),
-              num_workers=0, augment_noise=0, augment_rotation=False, clip_grad=True, eval_epochs=50,
-              eval_params=Namespace(n_eval_samples=100, eval_batch_size=100), mode='pocket_conditioning',
-              node_histogram=hist, pocket_representation='CA')
-    model = PharPocketDDPM(**hp)
-    model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
-    model = model.cuda()
-    data = {'phar_coords': phar['x'], 'phar_one_hot': phar['one_hot'], 'num_phar_atoms': phar['size'],
-            'phar_mask': phar['mask'], 'pocket_c_alpha': pocket['x'], 'pocket_one_hot': pocket['one_hot'],
-            'num_pocket_nodes': pocket['size'], 'pocket_mask': pocket['mask']}
-    return model, HipTrainer(model), data, g6
 
 
 def test_training_step_matches_reference_gradients_and_optimizer():
@@ -987,7 +925,7 @@ def test_unfused_edge_tail_agrees_with_the_fused_one_at_width_256():
     from argparse import Namespace
     from cmdgen_amd.lightning_modules import PharPocketDDPM
     from cmdgen_amd.training import HipTrainer
-    from test_hip_autograd import case, make_module, hip_grads
+    from helpers import autograd_case as case, make_module, hip_grads
     spec = importlib.util.spec_from_file_location('bench_train', os.path.join(os.path.dirname(__file__), '..', 'tools', 'bench_train.py'))
     bt = importlib.util.module_from_spec(spec); spec.loader.exec_module(bt)
     B, L = 3, 1
@@ -1054,20 +992,6 @@ def test_unfused_edge_tail_agrees_with_the_fused_one_at_width_256():
 
 
 # ------------------------------------------------------------------ round 6: the big-list kernels against the ORACLE, the half engine's range, re-pack hygiene
-def _bench_trainer(B, pipelined=False, sd_edit=None, lr=1e-3):
-    """PharPocketDDPM (shipped hyper-parameters, seeded weights) + HipTrainer + one synthetic batch of B ragged C-alpha complexes (tools/bench_train.py)."""
-    import importlib.util, os
-    spec = importlib.util.spec_from_file_location('bench_train', os.path.join(os.path.dirname(__file__), '..', 'tools', 'bench_train.py'))
-    bt = importlib.util.module_from_spec(spec); spec.loader.exec_module(bt)
-    cfg, model, tr = bt.build_trainer(B, 'CA', 'fp32', torch.device('cuda', 0), pipelined=pipelined)
-    sd = make_state_dict(cfg, seed=0)
-    if sd_edit is not None:
-        sd = sd_edit(dict(sd))
-        model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
-        tr = bt.HipTrainer(model, gemm_dtype='fp32')
-        tr.pipelined = pipelined
-    tr.lr = lr
-    return cfg, sd, model, tr, bt
 
 
 def test_default_step_at_bench_size_matches_oracle_autograd():

@@ -18,8 +18,7 @@ import pytest
 import torch
 
 from oracle import ref_cpu
-from test_hip_half_range import TARGETS, underflow_case
-from test_hip_train import GRAD_TOL, _bench_trainer
+from helpers import GRAD_TOL, RANGE_TARGETS as TARGETS, _bench_trainer, underflow_case
 
 pytestmark = pytest.mark.gpu
 
@@ -181,7 +180,7 @@ def test_pipelined_steps_drop_the_half_engine_batches_and_keep_the_optimizer_sta
 
 @pytest.mark.parametrize('target', list(TARGETS))
 def test_differentiable_dynamics_on_a_low_range_model_warns_and_equals_oracle_autograd(target):
-    from test_hip_autograd import make_module, check_against_oracle
+    from helpers import make_module, check_against_oracle
     cfg, sd, inp = underflow_case(target, 2.0 ** -10)
     g = np.random.Generator(np.random.PCG64(9)).normal(size=inp['xh_phar'].shape).astype(np.float32)
     dyn = make_module(cfg, sd)

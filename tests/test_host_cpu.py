@@ -4,32 +4,21 @@ import ctypes
 import json
 import os
 import re
-from argparse import Namespace
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import load_golden
+from helpers import host_hparams as _hparams, load_golden, small_ddpm
 import cmdgen_amd  # noqa: F401
 from cmdgen_amd import hip_backend, utils
 from cmdgen_amd.constants import dataset_params
 from cmdgen_amd.equivariant_diffusion.en_diffusion import DistributionNodes, PredefinedNoiseSchedule
 from cmdgen_amd.equivariant_diffusion.dynamics import EGNNDynamics
-from cmdgen_amd.equivariant_diffusion.conditional_model import ConditionalDDPM
 from cmdgen_amd.lightning_modules import PharPocketDDPM
 from cmdgen_amd.synthetic import ModelConfig, make_state_dict, linear_specs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def small_ddpm(H=64, L=2, T=500):
-    dyn = EGNNDynamics(phar_nf=8, residue_nf=20, n_dims=3, joint_nf=32, hidden_nf=H, n_layers=L, attention=True,
-                       tanh=True, norm_constant=1, inv_sublayers=1, sin_embedding=False, normalization_factor=100,
-                       aggregation_method='sum', edge_cutoff=6.0, update_pocket_coords=False)
-    return ConditionalDDPM(dynamics=dyn, phar_nf=8, residue_nf=20, n_dims=3, timesteps=T,
-                           noise_schedule='polynomial_2', noise_precision=1e-5, loss_type='l2',
-                           norm_values=[1, 4], size_histogram=np.ones((30, 70)))
 
 
 def test_library_exports_every_declared_symbol():
@@ -428,19 +417,6 @@ def test_pdb_reader_and_pocket_selection(tmp_path):
     assert utils.three_to_one('TRP') == 'W'
     near = utils.get_pocket_from_ligand(m, 'A:101')
     assert [r.get_resname() for r in near] == ['ALA', 'GLY', 'TRP']     # standard amino acids within 8 A
-
-
-def _hparams(H=64, L=1):
-    return dict(outdir='out', dataset='crossdock', datadir='data', batch_size=4, lr=1e-4,
-                egnn_params=Namespace(device='cuda', edge_cutoff=6.0, joint_nf=32, hidden_nf=H, n_layers=L,
-                                      attention=True, tanh=True, norm_constant=1, inv_sublayers=1,
-                                      sin_embedding=False, aggregation_method='sum', normalization_factor=100),
-                diffusion_params=Namespace(diffusion_steps=500, diffusion_noise_schedule='polynomial_2',
-                                           diffusion_noise_precision=1e-5, diffusion_loss_type='l2',
-                                           normalize_factors=[1, 4]),
-                num_workers=0, augment_noise=0, augment_rotation=False, clip_grad=True, eval_epochs=50,
-                eval_params=Namespace(n_eval_samples=100, eval_batch_size=100), mode='pocket_conditioning',
-                node_histogram=np.ones((30, 70)), pocket_representation='CA')
 
 
 def test_checkpoint_round_trip_lightning_format(tmp_path):

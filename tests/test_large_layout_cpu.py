@@ -9,11 +9,10 @@ import large_layout_ref as L
 import score_ref
 from cond_inpaint_ref import cond_inpaint, inpaint_plan
 from edit_ref import cond_edit
+import helpers
 from helpers import NoiseTape
 from oracle import ref_cpu
 from rule_sweep_ref import MARGIN, CHAIN_CAP
-import test_score_cpu
-import test_hip_parity_r3
 
 
 def test_layout_covers_what_it_was_chosen_for():
@@ -49,7 +48,7 @@ def test_layout_covers_what_it_was_chosen_for():
 
 
 def test_the_bands_are_the_owners():
-    assert L.SCORE_BAND == test_score_cpu.BAND == 1e-4 and L.CHAIN_BAND == test_hip_parity_r3.BAND == 2e-5
+    assert L.SCORE_BAND == helpers.SCORE_BAND == 1e-4 and L.CHAIN_BAND == helpers.CHAIN_BAND == 2e-5
     assert MARGIN == 1e-4 and L.MAX_LEFT_OUT == int(CHAIN_CAP * L.B) == 1
 
 

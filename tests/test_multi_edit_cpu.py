@@ -18,7 +18,7 @@ from edit_ref import cond_edit, edit_plan
 from helpers import NoiseTape, GOLDEN
 from oracle import ref_cpu
 from cmdgen_amd.synthetic import make_pockets, make_state_dict
-from test_multi_pocket_cpu import small, sub_pockets
+from helpers import small, sub_pockets
 
 K = 6
 
@@ -142,7 +142,7 @@ def test_held_rows_on_the_reference_alone():
 
 
 def test_argument_checks_without_a_device():
-    from test_cond_inpaint_cpu import _model
+    from helpers import bare_model as _model
     from cmdgen_amd.equivariant_diffusion.conditional_model import ConditionalDDPM, SimpleConditionalDDPM
     from cmdgen_amd.equivariant_diffusion.en_diffusion import EnVariationalDiffusion
 
@@ -193,7 +193,7 @@ def test_edit_phars_multi_builds_the_masks_and_moves_back_by_the_first_pocket():
     vector): the given points are the first rows with the masks `keep` asks for, the result comes back by the FIRST pocket's shift,
     strength sets the start level, and the argument checks raise before the chain is called."""
     from cmdgen_amd.lightning_modules import PharPocketDDPM
-    from test_oracle_golden_r2 import _hparams
+    from helpers import _hparams
     model = PharPocketDDPM(**_hparams('CA', 64, 2))
     names = list(model.dataset_info['phar_decoder'])
     pdb, ids = os.path.join(GOLDEN, 'g7_pocket.pdb'), [f'A:{i}' for i in range(1, 30)]

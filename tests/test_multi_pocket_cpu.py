@@ -1,36 +1,17 @@
 """The multi-pocket chain on the CPU: the oracle-built model (multi_pocket_ref) against ref_cpu.sample_given_pocket where the two must
 coincide, the frame (every pocket of a group carries the same translation), the leave-out cap of the GPU cases, and the argument
 checks of ConditionalDDPM.sample_given_pockets that need no device."""
-from dataclasses import replace
-
 import numpy as np
 import pytest
 import torch
 
 import multi_pocket_cases as mc
 import multi_pocket_ref as mp
-from helpers import NoiseTape
+from helpers import NoiseTape, small, sub_pockets
 from oracle import ref_cpu
-from cmdgen_amd.synthetic import make_pockets, make_state_dict
+from cmdgen_amd.synthetic import make_pockets
 
 K = 6
-_SMALL = {}
-
-
-def small():
-    """A small model of the bounded config (the CPU tests need the chain's arithmetic, not the width)."""
-    if not _SMALL:
-        cfg = replace(mc.config(), hidden_nf=64, n_layers=2)
-        _SMALL.update(cfg=cfg, p=ref_cpu.to_torch_params(make_state_dict(cfg, seed=3)))
-    return _SMALL['cfg'], _SMALL['p']
-
-
-def sub_pockets(pb, members):
-    """The pocket dict of the listed samples of pb, in that order."""
-    xs, hs = np.split(pb.x, np.cumsum(pb.size)[:-1]), np.split(pb.one_hot, np.cumsum(pb.size)[:-1])
-    size = pb.size[list(members)]
-    return {'x': torch.from_numpy(np.concatenate([xs[b] for b in members])), 'one_hot': torch.from_numpy(np.concatenate([hs[b] for b in members])),
-            'size': torch.from_numpy(size), 'mask': torch.from_numpy(np.repeat(np.arange(len(size)), size))}
 
 
 def single_chain(cfg, p, pocket, nph, noise):
@@ -108,7 +89,7 @@ def test_every_pocket_of_a_group_carries_the_same_translation_and_the_cap_holds(
 
 
 def test_argument_checks_without_a_device():
-    from test_cond_inpaint_cpu import _model
+    from helpers import bare_model as _model
     from cmdgen_amd.equivariant_diffusion.conditional_model import ConditionalDDPM, SimpleConditionalDDPM
     from cmdgen_amd.equivariant_diffusion.en_diffusion import EnVariationalDiffusion
 

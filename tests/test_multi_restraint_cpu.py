@@ -89,7 +89,7 @@ def _pocket(sizes):
 
 
 def test_argument_checks_without_a_device():
-    from test_cond_inpaint_cpu import _model
+    from helpers import bare_model as _model
     from cmdgen_amd.equivariant_diffusion.conditional_model import ConditionalDDPM, SimpleConditionalDDPM
     from cmdgen_amd.equivariant_diffusion.en_diffusion import EnVariationalDiffusion
     m = _model(ConditionalDDPM)
@@ -133,7 +133,7 @@ def test_argument_checks_without_a_device():
 def test_the_records_are_made_with_the_group_counts_and_both_tables_are_supplied():
     """sample_restrained_given_pockets up to the chain call, on a stand-in handle: restraints.records sees the per-GROUP counts (a point
     valid for the group but not for a member index passes), the layout is the member layout, and the step and the guide table are set."""
-    from test_cond_inpaint_cpu import _model
+    from helpers import bare_model as _model
     from cmdgen_amd.equivariant_diffusion.conditional_model import ConditionalDDPM
     m = _model(ConditionalDDPM)
     seen = {}
@@ -180,7 +180,7 @@ def test_generate_phars_multi_restrained_moves_back_by_the_first_pocket():
     and moves every pocket by its own vector): every copy gets the list under its own group index, the centres stay where the caller put
     them, the result comes back by the FIRST pocket's shift, and the argument checks raise before the chain is called."""
     from cmdgen_amd.lightning_modules import PharPocketDDPM
-    from test_oracle_golden_r2 import _hparams
+    from helpers import _hparams
     model = PharPocketDDPM(**_hparams('CA', 64, 2))
     pdb, ids = os.path.join(GOLDEN, 'g7_pocket.pdb'), [f'A:{i}' for i in range(1, 30)]
     spot = (9.0, 2.0, -15.0)

@@ -16,7 +16,7 @@ import score_ref
 from helpers import GOLDEN, HIST
 from cmdgen_amd import scoring
 from cmdgen_amd.synthetic import make_pockets
-from test_multi_pocket_cpu import small, sub_pockets
+from helpers import small, sub_pockets
 
 LEVELS = [600, 1000, 0, 200]         # any order; one t = 0 level
 NAMES = ('err', 'err_x', 'log_ph_oracle', 'netmax')      # multi_score_ref's name -> score_ref's: its l0 term is 'log_ph_oracle' there
@@ -122,7 +122,7 @@ def _fake_terms(rng, R, nlev, G, M):
 def test_group_assembly():
     """nll against a float64 sum of the assembly's own entries, log_pN as the weighted sum of assemble's per-member values, the member
     entries as assemble's on the member columns, and M = 1 as assemble itself."""
-    from test_score_cpu import score_case
+    from helpers import score_case
     from cmdgen_amd.equivariant_diffusion.en_diffusion import DistributionNodes
     cfg, sd = score_case()[:2]
     T, nd, nv = cfg.timesteps, 3, list(cfg.norm_values)
@@ -160,7 +160,7 @@ def test_group_assembly():
 
 
 def test_argument_checks_without_a_device():
-    from test_cond_inpaint_cpu import _model
+    from helpers import bare_model as _model
     from cmdgen_amd.equivariant_diffusion.conditional_model import ConditionalDDPM, SimpleConditionalDDPM
     from cmdgen_amd.equivariant_diffusion.en_diffusion import EnVariationalDiffusion
 
@@ -209,7 +209,7 @@ def test_score_phars_multi_builds_the_groups():
     """PharPocketDDPM.score_phars_multi up to the chain (replaced by a recorder): one group per candidate, one pocket dict per file
     batched over the candidates, and the argument checks raise before the chain is called."""
     from cmdgen_amd.lightning_modules import PharPocketDDPM
-    from test_oracle_golden_r2 import _hparams
+    from helpers import _hparams
     model = PharPocketDDPM(**_hparams('CA', 64, 2))
     names = list(model.dataset_info['phar_decoder'])
     pdb, ids = os.path.join(GOLDEN, 'g7_pocket.pdb'), [f'A:{i}' for i in range(1, 30)]
@@ -217,10 +217,10 @@ def test_score_phars_multi_builds_the_groups():
     c1 = [(names[2], (10.0, 3.0, -14.0)), (names[2], (12.0, 1.0, -16.0))]
     seen = {}
 
-    def record(phar, pockets, **kw):
+    def recorder(phar, pockets, **kw):
         seen.update(kw, phar=phar, pockets=pockets)
         return {'nll': torch.zeros(len(phar['size']))}
-    model.ddpm.score_given_pockets = record
+    model.ddpm.score_given_pockets = recorder
     out = model.score_phars_multi([pdb, pdb], [c0, c1], pocket_ids=[ids, ids[:20]], weights=[0.25, 0.75], timesteps=10, seed=5,
                                   return_members=True)
     assert out['nll'].shape == (2,)

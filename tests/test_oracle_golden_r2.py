@@ -2,14 +2,13 @@
 G5 per-block intermediates, G7 generate_phars bookkeeping, G12 the full-atom shape of BASELINE configs[4],
 G13 chains in a regime where an ABSOLUTE 1e-4 RMS bound is meaningful.  They pin the oracle (and, for G7, the
 host layer); tests/test_hip_parity_r2.py then checks the HIP path against the same vectors."""
-import json
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import (GOLDEN, load_golden, cases_of, NoiseTape, rms, bounded_case, fullsize_chain_case, g5_case,
+from helpers import (GOLDEN, G7_RUNS, _hparams, assert_same_result, g7_select, load_golden, cases_of, NoiseTape, rms, bounded_case, fullsize_chain_case, g5_case,
                      dynamics_case, pocket_dict)
 from oracle import ref_cpu
 from cmdgen_amd.synthetic import ModelConfig, make_state_dict, make_pockets
@@ -127,37 +126,6 @@ def test_g15_shipped_schedule_chain_per_step():
 
 
 # ------------------------------------------------------------------------------------------------ G7
-def _hparams(rep, H, L):
-    from argparse import Namespace
-    from helpers import HIST
-    return dict(outdir='out', dataset='crossdock' if rep == 'CA' else 'crossdock_full', datadir='data', batch_size=4, lr=1e-4,
-                egnn_params=Namespace(device='cpu', edge_cutoff=6.0, joint_nf=32, hidden_nf=H, n_layers=L, attention=True,
-                                      tanh=True, norm_constant=1, inv_sublayers=1, sin_embedding=False,
-                                      aggregation_method='sum', normalization_factor=100),
-                diffusion_params=Namespace(diffusion_steps=500, diffusion_noise_schedule='polynomial_2',
-                                           diffusion_noise_precision=1e-5, diffusion_loss_type='l2', normalize_factors=[1, 4]),
-                num_workers=0, augment_noise=0, augment_rotation=False, clip_grad=True, eval_epochs=50,
-                eval_params=Namespace(n_eval_samples=100, eval_batch_size=100), mode='pocket_conditioning',
-                node_histogram=HIST, pocket_representation=rep)
-
-
-G7_RUNS = [('ca_ids', 'CA', dict(pocket_ids=True)), ('ca_lig', 'CA', dict(ref_ligand='B:501')),
-           ('ca_pep', 'CA', dict(ref_ligand='B:601')), ('fa_ids', 'full-atom', dict(pocket_ids=True))]
-
-
-def g7_select(g, tag, sel):
-    return {'pocket_ids': [str(s) for s in g[tag + '/pocket_ids']]} if sel.get('pocket_ids') else dict(sel)
-
-
-def assert_same_result(out, want_json, atol):
-    want = json.loads(want_json)
-    assert list(out) == list(want)                                     # Molecule_k keys in creation order (Q9)
-    for m in want:
-        assert list(out[m]) == list(want[m]), m                        # type names in first-seen order
-        for t in want[m]:
-            a = np.asarray([[float(v) for v in c] for c in out[m][t]])
-            b = np.asarray(want[m][t])
-            assert a.shape == b.shape and np.abs(a - b).max() <= atol, (m, t)
 
 
 @pytest.mark.parametrize('tag,rep,sel', G7_RUNS)

@@ -203,7 +203,7 @@ GOOD = {'kind': 'position', 'sample': 1, 'point': 2, 'center': (1.0, 2.0, 3.0), 
 
 
 def test_argument_checks_without_a_device():
-    from test_cond_inpaint_cpu import _model, _inputs
+    from helpers import bare_inputs as _inputs, bare_model as _model
     from cmdgen_amd.equivariant_diffusion.conditional_model import ConditionalDDPM, SimpleConditionalDDPM
     from cmdgen_amd.equivariant_diffusion.en_diffusion import EnVariationalDiffusion
     phar, pocket = _inputs()                                              # samples of 2 and 3 points
@@ -244,7 +244,7 @@ def test_edit_phars_restrained_builds_the_masks_and_gives_every_copy_the_list():
     """PharPocketDDPM.edit_phars_restrained up to the chain and back (the chain replaced by the identity)."""
     from helpers import GOLDEN
     from cmdgen_amd.lightning_modules import PharPocketDDPM
-    from test_oracle_golden_r2 import _hparams
+    from helpers import _hparams
     model = PharPocketDDPM(**_hparams('CA', 64, 2))
     names = list(model.dataset_info['phar_decoder'])
     pdb, ids = os.path.join(GOLDEN, 'g7_pocket.pdb'), [f'A:{i}' for i in range(1, 30)]

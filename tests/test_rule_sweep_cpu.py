@@ -40,7 +40,7 @@ def test_planner_resolves_the_case_tables_launch_at_256_cus():
 
 
 def test_inside_geometry_is_the_property_tests_input_builder():
-    from test_hip_properties import eval_inputs
+    from helpers import eval_inputs
     case = rs.EVAL_CASES[1]
     pb, cfg = rs.pockets_of(case), rs.config_of(case)
     for a, b in zip(rs.eval_inputs(pb, cfg), eval_inputs(pb, cfg)):

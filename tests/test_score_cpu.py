@@ -8,36 +8,13 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import HIST, load_golden
+from helpers import HIST, SCORE_BAND as BAND, SCORE_CASES as CASES, close, g21, score_case
 import score_ref
 from oracle import ref_cpu
 import cmdgen_amd  # noqa: F401
 from cmdgen_amd import hip_backend, scoring
-from cmdgen_amd.synthetic import ModelConfig, make_pockets, make_state_dict
 
-G21 = load_golden('g21_score.npz')
-CASES = ['K100', 'K20']
-BAND = 1e-4
-
-
-def score_case(g=G21):
-    """-> cfg, numpy state dict, phar, pocket (torch dicts) of the G21 complexes (those of G6, timesteps = 100)."""
-    H, L, B, R, seed, first, T = [int(v) for v in g['meta']]
-    g6 = load_golden('g6_loss.npz')
-    cfg = ModelConfig(hidden_nf=H, n_layers=L, residue_nf=R, timesteps=T)
-    sd = make_state_dict(cfg, seed=seed, coord_gain=1.0)
-    pb = make_pockets(B, 'CA', ragged=True, first_index=first)
-    nl = g6['num_nodes_phar']
-    phar = {'x': torch.from_numpy(g6['phar_x'].copy()), 'one_hot': torch.from_numpy(g6['phar_one_hot'].copy()),
-            'size': torch.from_numpy(nl.copy()), 'mask': torch.from_numpy(np.repeat(np.arange(B), nl))}
-    pocket = {'x': torch.from_numpy(pb.x.copy()), 'one_hot': torch.from_numpy(pb.one_hot.copy()),
-              'size': torch.from_numpy(pb.size.copy()), 'mask': torch.from_numpy(pb.mask.copy())}
-    return cfg, sd, phar, pocket
-
-
-def close(got, want):
-    got, want = np.asarray(got, dtype=np.float32), np.asarray(want, dtype=np.float32)
-    return np.allclose(got, want, rtol=2e-5, atol=2e-5 * max(1.0, float(np.abs(want).max())))
+G21 = g21()
 
 
 @pytest.mark.parametrize('case', CASES)
@@ -156,7 +133,7 @@ def test_library_exports_and_binds_score_chain():
 
 
 def test_score_entries_exist_and_refuse_on_the_host():
-    from test_host_cpu import small_ddpm, _hparams
+    from helpers import small_ddpm, host_hparams as _hparams
     from cmdgen_amd.equivariant_diffusion.conditional_model import ConditionalDDPM, SimpleConditionalDDPM
     from cmdgen_amd.equivariant_diffusion.en_diffusion import EnVariationalDiffusion
     from cmdgen_amd.lightning_modules import PharPocketDDPM

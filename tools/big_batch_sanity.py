@@ -8,7 +8,7 @@ import numpy as np, torch
 from cmdgen_amd import hip_backend
 from cmdgen_amd.synthetic import ModelConfig, make_state_dict, make_pockets
 from bench import bounded_config
-from test_hip_properties import eval_inputs, handle_for, forward
+from helpers import eval_inputs, handle_with_layout as handle_for, forward
 out = {}
 cfg = ModelConfig(residue_nf=11, timesteps=1000); sd = make_state_dict(cfg, seed=0)
 pb = make_pockets(1024, 'full-atom'); xh, xq, t = eval_inputs(pb, cfg)

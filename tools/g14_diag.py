@@ -1,10 +1,10 @@
 import sys, numpy as np, torch
 sys.path.insert(0,'tests'); sys.path.insert(0,'.')
-import test_hip_parity_r3 as t
+import helpers as t
 name='ca_b64_K1000'
 cfg, sd, pb, K, window, noise = t.g14_case(name)
 B=len(pb.size)
-G=t.G14
+G=t.g14()
 margins=G[name+'/margins']; steps=G[name+'/ckpt_steps']; ck_z=G[name+'/ckpt_z']
 want=G[name+'/xh_phar']
 for engine in ['split','fp32']:
