@@ -702,7 +702,7 @@ static std::vector<float> step_table(const cmdgen_handle* h, int K) {
 }
 
 // ---------------------------------------------------------------------------------
-// the chains: what the entries of all eleven kinds share.  A kind's state lives in its slot (h->chains[kind]); its entry lays the slot's
+// the chains: what the entries of all twelve kinds share.  A kind's state lives in its slot (h->chains[kind]); its entry lays the slot's
 // table block out with the appenders below (TableBlock, cmdgen_host.h: each records where its section begins) and its ChainAlloc composes
 // the parts (alloc_chain_buf, alloc_inpaint_part, point_group_tab, alloc_restrain_part, alloc_score_part) at those offsets - the eight
 // sampling kinds share one, alloc_sampling.  An entry reads top to bottom: checks, table block, Chain::open, its init launches,
@@ -939,7 +939,7 @@ static int alloc_sampling(cmdgen_handle* h, ChainSlot& k, const TableBlock& t, c
 }
 
 // One chain call between begin_chain and end_chain: the stream it runs on, its slot, the launch description of its evaluations and, for
-// the ten conditional kinds, the slot's ChainBuf completed with the call's pointers.
+// the eleven conditional kinds, the slot's ChainBuf completed with the call's pointers.
 struct Chain {
     cmdgen_handle* h = nullptr;
     ChainSlot* k = nullptr;
@@ -1323,6 +1323,116 @@ extern "C" int cmdgen_multi_restrained_chain(cmdgen_handle* h, const float* pock
     if (rc) return rc;
     cmdgen_launch_multi_final(h->lay, d, c, gt, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, ch.k->cog, ch.s);
     cmdgen_launch_multi_restrain_energy(h->lay, d, gt, rb, xh_phar_out, xh_pocket_out, energy_out, ch.s);
+    return ch.close();
+}
+
+// ---------------------------------------------------------------------------------
+// the diverse chain: cmdgen_sample_chain's chain with a term in the mean of every posterior op that pushes the samples of a SET (consecutive
+// samples: the draws for one pocket) apart (kernels_diverse.hip holds the definition).  The slot's table block is: the posterior rows | the
+// guide rows (sigma_t, alpha_t, 0, 0; n_steps + 1 of them, the last unused) | strength, width, 1 / (2 w^2), max_shift, guide_below, 0, 0, 0 |
+// per sample set_first, set_size, set_row0, set_rows - so a changed partition or scalar prepares the slot again and drops its captured steps.
+// ---------------------------------------------------------------------------------
+static_assert(CMDGEN_MAX_SET_ROWS == MAX_SET_ROWS, "the public bound and the kernels' agree");
+
+// the set tables of a call, per sample (DiverseBuf), checked
+struct SetPlan { std::vector<int> first, size, row0, rows; };
+static int build_set_plan(cmdgen_handle* h, int64_t n_sets, const int64_t* set_size_host, SetPlan& p) {
+    const int B = h->lay.B;
+    if (n_sets < 1 || n_sets > B) return fail(h, CMDGEN_EINVAL, "n_sets=%lld must be in [1, batch=%d]", (long long)n_sets, B);
+    p.first.resize(B); p.size.resize(B); p.row0.resize(B); p.rows.resize(B);
+    int64_t members = 0, row = 0;
+    for (int64_t g = 0; g < n_sets; ++g) {
+        const int64_t M = set_size_host[g];
+        if (M < 1) return fail(h, CMDGEN_EINVAL, "set_size[%lld]=%lld: every set has at least one sample", (long long)g, (long long)M);
+        if (members + M > B) { members += M; continue; }                 // (reported below with the sum)
+        int64_t rows = 0;
+        for (int64_t m = 0; m < M; ++m) rows += h->cur_nphar[(size_t)(members + m)];
+        if (rows > CMDGEN_MAX_SET_ROWS)
+            return fail(h, CMDGEN_EINVAL, "set_size[%lld]: the set has %lld phar rows, at most %d (the pair launch costs rows^2)", (long long)g,
+                        (long long)rows, CMDGEN_MAX_SET_ROWS);
+        for (int64_t m = 0; m < M; ++m) {
+            const size_t b = (size_t)(members + m);
+            p.first[b] = (int)members; p.size[b] = (int)M; p.row0[b] = (int)row; p.rows[b] = (int)rows;
+        }
+        members += M; row += rows;
+    }
+    if (members != B) return fail(h, CMDGEN_EINVAL, "set_size sums to %lld, the layout has %d samples", (long long)members, B);
+    if (plan_step_lds(h->lay.max_n, h->dims.P) > 64 * 1024)
+        return fail(h, CMDGEN_EINVAL, "a sample has %d nodes: the diverse step keeps a sample's positions, degrees and z in LDS (64 KiB)", h->lay.max_n);
+    return 0;
+}
+// The diverse tail of a table block, on a row boundary, laid out as append_guidance lays its own: K guide rows and one unused | par5, then
+// 0, 0, 0 | the four set tables, B entries each.  alloc_diverse points a DiverseBuf at it.
+static void append_sets(const cmdgen_handle* h, TableBlock& t, int K, const float (&par5)[5], const SetPlan& p) {
+    std::vector<float> sa;                           // [K][2], row i for op i (t = K - i)
+    if (h->user_guide_K == K) sa = h->user_guide; else build_guide_table(h->gamma, h->cfg.timesteps, K, sa);
+    const size_t B = p.first.size(), c0 = (t.f.size() + 3) / 4 * 4, n_rows = (size_t)K + 1;
+    t.sets = c0; t.guide_rows = (int)n_rows;
+    t.f.resize(c0 + n_rows * 4 + 8 + 4 * B, 0.f);
+    float* g = t.f.data() + c0;
+    for (int i = 0; i < K; ++i) { g[4 * i] = sa[2 * (size_t)i]; g[4 * i + 1] = sa[2 * (size_t)i + 1]; }
+    float* par = g + n_rows * 4;
+    memcpy(par, par5, sizeof par5);
+    float* tab = par + 8;
+    memcpy(tab, p.first.data(), B * sizeof(int)); memcpy(tab + B, p.size.data(), B * sizeof(int));
+    memcpy(tab + 2 * B, p.row0.data(), B * sizeof(int)); memcpy(tab + 3 * B, p.rows.data(), B * sizeof(int));
+}
+// the diverse kind's ChainAlloc: the ChainBuf, then the DiverseBuf at the tail append_sets packed and the buffers its launches hand on
+static int alloc_diverse(cmdgen_handle* h, ChainSlot& k, const TableBlock& t, const float* dev, int n_steps) {
+    int rc = alloc_chain_buf(h, k, dev); if (rc) return rc;
+    DiverseBuf& db = k.div;
+    const size_t B = (size_t)h->lay.B;
+    const float* g = dev + t.sets;
+    const float* par = g + (size_t)t.guide_rows * 4;
+    db.sa = (const float4*)g;
+    db.strength = par[0]; db.width = par[1]; db.inv2w2 = par[2]; db.max_shift = par[3]; db.guide_below = par[4];
+    const int* tab = (const int*)(par + 8);
+    db.set_first = tab; db.set_size = tab + B; db.set_row0 = tab + 2 * B; db.set_rows = tab + 3 * B;
+    db.op_overlap = nullptr;
+    rc = slot_alloc(h, k, db.pin_com, B); if (rc) return rc;
+    rc = slot_alloc(h, k, db.y, (size_t)h->lay.Nl * 3); if (rc) return rc;
+    rc = slot_alloc(h, k, db.gd, (size_t)h->lay.Nl * 3); if (rc) return rc;
+    return slot_alloc(h, k, db.po, (size_t)h->lay.Nl);
+}
+
+extern "C" int cmdgen_diverse_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot, int32_t timesteps,
+                                    int64_t n_sets, const int64_t* set_size_host,
+                                    float strength, float width, float max_shift, float guide_below,
+                                    const float* noise, uint64_t seed, const int64_t* pocket_ids_host,
+                                    float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                                    float* overlap_out, float* op_overlap_out, int32_t use_graph, cmdgen_stream stream) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (!pocket_x || !pocket_onehot || !set_size_host || !xh_phar_out || !xh_pocket_out || !overlap_out)
+        return fail(h, CMDGEN_EINVAL, "null pointer (pocket_x, pocket_onehot, set_size_host, xh_phar_out, xh_pocket_out and overlap_out are required)");
+    const int K = timesteps;
+    rc = check_timesteps(h, K); if (rc) return rc;
+    rc = refuse_joint_no_com(h, "the diverse chain", kPocketDiffuses, ": the guidance frame follows the centre-of-mass projections", CMDGEN_EINVAL);
+    if (rc) return rc;
+    if (!(std::isfinite(strength) && strength >= 0.f)) return fail(h, CMDGEN_EINVAL, "strength=%g must be finite and >= 0", (double)strength);
+    if (!(std::isfinite(width) && width > 0.f)) return fail(h, CMDGEN_EINVAL, "width=%g must be finite and > 0", (double)width);
+    if (!(std::isfinite(max_shift) && max_shift > 0.f)) return fail(h, CMDGEN_EINVAL, "max_shift=%g must be finite and > 0", (double)max_shift);
+    if (!(guide_below >= 0.f && guide_below <= 1.f)) return fail(h, CMDGEN_EINVAL, "guide_below=%g must be in [0, 1]", (double)guide_below);
+    SetPlan sp;
+    rc = build_set_plan(h, n_sets, set_size_host, sp); if (rc) return rc;
+    TableBlock tables = posterior_rows(step_table(h, K));
+    append_sets(h, tables, K, {strength, width, 1.0f / (2.0f * (width * width)), max_shift, guide_below}, sp);
+    Chain ch;
+    rc = ch.open(h, CHAIN_DIVERSE, tables, K, alloc_diverse, pocket_ids_host, noise, seed, z_steps_out, pocket_steps_out, use_graph, stream); if (rc) return rc;
+    const Dims& d = h->dims;
+    const ChainBuf& c = ch.c;
+    DiverseBuf db = ch.k->div;
+    db.op_overlap = op_overlap_out;
+    RestrainBuf prep{};                              // k_restrain_prep fills pin_com and reads nothing else of it
+    prep.pin_com = db.pin_com;
+    cmdgen_launch_chain_init(h->lay, d, c, pocket_x, pocket_onehot, ch.s);
+    cmdgen_launch_restrain_prep(h->lay, d, prep, pocket_x, ch.s);
+    ch.start(true);                                  // evaluation 0 (t = 1); the evaluations run their own k_readout (no plain_chain)
+    rc = ch.steps({noise, z_steps_out, pocket_steps_out, op_overlap_out, nullptr}, K, [&](hipStream_t ss) {
+        cmdgen_launch_diverse_step(h->lay, d, c, db, h->work, h->work.eps_tmp, ss);
+    });
+    if (rc) return rc;
+    cmdgen_launch_chain_final(h->lay, d, c, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, ch.k->cog, ch.s);
+    cmdgen_launch_diverse_overlap(h->lay, d, db, xh_phar_out, xh_pocket_out, overlap_out, ch.s);
     return ch.close();
 }
 

@@ -242,6 +242,24 @@ struct RestrainBuf {            // restrained chain (cmdgen_restrained_chain), b
     float* op_energy;           // [K][B] E at xhat of every op, or null
 };
 
+struct DiverseBuf {             // diverse chain (cmdgen_diverse_chain), beside a ChainBuf: the set tables and the buffers its three launches per op
+                                // hand to each other (kernels_diverse.hip).  A set is a run of consecutive samples: "the draws for one pocket"
+    const float4* sa;           // [K]     (sigma_t, alpha_t, 0, 0) of op i's t, as RestrainBuf::sa
+    float4* pin_com;            // [B]     com(P_in.x / n_x) (k_restrain_prep)
+    float strength, width;      // k >= 0 (dimensionless), w > 0 in A
+    float inv2w2;               // 1 / (2 w^2), the host's fp32 evaluation
+    float max_shift, guide_below;
+    const int* set_first;       // [B]     first sample of the sample's set
+    const int* set_size;        // [B]     samples of the sample's set, M
+    const int* set_row0;        // [B]     first phar row of the sample's set
+    const int* set_rows;        // [B]     phar rows of the sample's set (at most MAX_SET_ROWS)
+    float* y;                   // [Nl][3] the points of every sample in its caller's frame, A (k_diverse_frame)
+    float* gd;                  // [Nl][3] the displacement of every row, A (k_diverse_pair, for k_diverse_step_count)
+    float* po;                  // [Nl]    o_ai, a point's share of its sample's overlap (k_diverse_pair's own scratch)
+    float* op_overlap;          // [K][B]  overlap at every op's estimate, or null
+};
+enum { MAX_SET_ROWS = 8192 };   // = CMDGEN_MAX_SET_ROWS
+
 struct PocketCache {            // chain-invariant part of k_embed's output for POCKET rows (conditional sampler): the pocket's
                                 // features never change during a chain and the embedding is affine in the time feature, so
                                 //   h(t) = c + t dh,  P(t) = P0 + t dP,  Q(t) = Q0 + t dQ   (dh, dP, dQ: one row of H values each)

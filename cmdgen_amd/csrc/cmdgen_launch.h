@@ -71,6 +71,15 @@ void cmdgen_launch_multi_restrained_edit_step(const Layout& lay, const Dims& d, 
 void cmdgen_launch_multi_restrain_energy(const Layout& lay, const Dims& d, const GroupTab& g, const RestrainBuf& rb, const float* xo,
                                          const float* po, float* energy_out, hipStream_t s);
 
+// kernels_diverse.hip: the diverse chain (the conditional chain with a term that pushes the samples of a set apart).  Per op k_diverse_frame
+// (the points of every sample in its caller's frame, DiverseBuf::y), k_diverse_pair (the displacement gd and op_overlap) and then
+// k_diverse_step_count (k_step_count with the displacement in the mean)
+void cmdgen_launch_diverse_step(const Layout& lay, const Dims& d, const ChainBuf& c, const DiverseBuf& db, const Work& w, const float* eps,
+                                hipStream_t s);
+// ... and the same two guide launches over the chain's output xo / po (A): overlap_out [B]
+void cmdgen_launch_diverse_overlap(const Layout& lay, const Dims& d, const DiverseBuf& db, const float* xo, const float* po, float* overlap_out,
+                                   hipStream_t s);
+
 // kernels_multi.hip: the multi-pocket chain (groups of samples that share one latent)
 void cmdgen_launch_multi_init(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const float* px, const float* poh,
                               hipStream_t s);

@@ -293,6 +293,10 @@ inline size_t plan_restrained_step_lds(int max_n, int P) { return plan_step_lds(
 // velocity array.  Bytes per workgroup, at most PLAN_RESTRAINED_LDS_MAX.
 inline size_t plan_restrained_edit_step_lds(int max_n, int P) { return plan_step_lds(max_n, P) + (size_t)max_n * 7 * sizeof(float); }
 
+// The diverse chain (kernels_diverse.hip): its step kernel keeps plan_step_lds; k_diverse_frame keeps a float4 per pocket atom of the largest sample
+// (less, so the step's check covers it); k_diverse_pair's LDS is static.
+inline size_t plan_diverse_frame_lds(int max_n) { return (size_t)max_n * 16; }
+
 // the launch keys of cmdgen_query (include/cmdgen_hip.h); false: not a launch key
 inline bool plan_query(const LaunchPlan& p, const char* key, int64_t* value) {
     const struct { const char* key; int64_t v; } keys[] = {

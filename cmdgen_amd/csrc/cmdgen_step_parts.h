@@ -1,4 +1,4 @@
-// cmdgen_step_parts.h - the parts the derived chains' step kernels are composed of (kernels_inpaint.hip, kernels_multi.hip, kernels_restrain.hip):
+// cmdgen_step_parts.h - the parts the derived chains' step kernels are composed of (kernels_inpaint.hip, kernels_multi.hip, kernels_restrain.hip, kernels_diverse.hip):
 // one workgroup per sample, the sample's z and positions in LDS as in k_step_count (kernels_ddpm.hip).  Device code only.  Every part is
 // straight-line code that the whole workgroup calls; what differs between the chain kinds enters as arguments:
 //   StepRows        the rows the workgroup draws for and where its known rows, marks, displacements and saved z live (per sample, or per group);

@@ -44,12 +44,9 @@
 //
 // The same guidance inside op A of the edit chain (ConditionalDDPM.edit_restrained, cmdgen_restrained_edit_chain): k_restrained_edit_step_count
 // below, whose header settles what a held row means to the terms.
-#include "cmdgen_step_parts.h"
+#include "cmdgen_guide_parts.h"    // wave_sum, wave_max, wave_com, xhat_free, frame_shift, clip_shift: shared with kernels_diverse.hip
 
 namespace {
-
-__device__ __forceinline__ float wave_sum(float v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o); return v; }
-__device__ __forceinline__ float wave_max(float v) { for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o)); return v; }
 
 struct PointTerm { float gx, gy, gz, e, v; };     // dE / dxhat_i, the point's share of E, its largest violation
 
@@ -99,14 +96,6 @@ __device__ __forceinline__ PointTerm point_terms(const RestrainBuf& rb, int r0, 
     return t;
 }
 
-// com of the np positions s_q[0 .. np-1] (one wave; every lane returns it)
-__device__ __forceinline__ void wave_com(const float4* s_q, int np, int lane, float& c0, float& c1, float& c2) {
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-    for (int a = lane; a < np; a += 64) { const float4 p = s_q[a]; a0 += p.x; a1 += p.y; a2 += p.z; }
-    const float cnt = fmaxf((float)np, 1.0f);
-    c0 = wave_sum(a0) / cnt; c1 = wave_sum(a1) / cnt; c2 = wave_sum(a2) / cnt;
-}
-
 // which of steps 1-5 an op runs for the owner (sample or group) of the records r0 .. r1-1: guided - the displacement enters the mean; terms - steps 1-4
 // run at all (for the displacement, or for op_energy alone).  Uniform over the workgroup.
 struct GuideOp { int r0, r1; bool guided, terms; };
@@ -117,28 +106,17 @@ __device__ __forceinline__ GuideOp guide_op(const RestrainBuf& rb, int owner, co
     return GuideOp{r0, r1, guided, touched && (guided || rb.op_energy != nullptr)};
 }
 
-// 1. xhat of a row, one x column, in Angstrom: free - the denoised estimate from z and the network's column e (zero when the NaN guard reset);
-// held (the edit chains) - the row's given position K moved into the current frame
-__device__ __forceinline__ float xhat_free(const Dims& d, const float4& sa, float z, float e, bool nan_reset) {
-    if (nan_reset) e = 0.f;
-    return d.norm_x * (z - sa.x * e) / sa.y;
-}
+// 1. xhat of a row, one x column, in Angstrom: free - xhat_free (cmdgen_guide_parts.h); held (the edit chains) - the row's given position K
+// moved into the current frame
 __device__ __forceinline__ float xhat_held(const Dims& d, float known, float shift) { return d.norm_x * known + shift; }
 
-// 2. shift, by one wave, from member b's np pocket atoms in LDS -> s_shift
-__device__ __forceinline__ void frame_shift(const Dims& d, const RestrainBuf& rb, int b, const float4* s_q, int np, int lane, float* s_shift) {
-    float c0, c1, c2;
-    wave_com(s_q, np, lane, c0, c1, c2);
-    const float4 pin = rb.pin_com[b];
-    if (lane == 0) { s_shift[0] = d.norm_x * (c0 - pin.x); s_shift[1] = d.norm_x * (c1 - pin.y); s_shift[2] = d.norm_x * (c2 - pin.z); }
-}
+// 2. shift: frame_shift (cmdgen_guide_parts.h)
 
 // 4. the displacement of a point from its gradient sums -> o[0 .. 2]
 __device__ __forceinline__ void point_shift(const RestrainBuf& rb, const Dims& d, const float4& cf, float gx, float gy, float gz, float* o) {
     const float sd = d.norm_x * cf.z, var = sd * sd;
     float dx = -rb.scale * var * gx, dy = -rb.scale * var * gy, dz = -rb.scale * var * gz;
-    const float len = sqrtf(dx * dx + dy * dy + dz * dz);
-    if (len > rb.max_shift) { const float f = rb.max_shift / len; dx *= f; dy *= f; dz *= f; }
+    clip_shift(rb.max_shift, dx, dy, dz);
     o[0] = dx; o[1] = dy; o[2] = dz;
 }
 

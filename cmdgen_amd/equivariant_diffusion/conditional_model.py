@@ -301,6 +301,50 @@ class ConditionalDDPM(EnVariationalDiffusion):
         out, info = self._finish_restrained(h, run, self.inpaint_frames(1, 1, timesteps, return_frames), return_frames)
         return out[0], out[1], phar_mask, pocket['mask'], info
 
+    def _finish_diverse(self, h, run, frame_of_step, return_frames):
+        """_finish_chain for the diverse chain, whose run() returns (xh_phar, xh_pocket, z_steps, overlap [B], op_overlap).
+        -> (_finish_chain's result, {'overlap': [B]} and, with return_frames > 1, 'op_overlap')."""
+        extra = {}
+
+        def run3():
+            out = run()
+            extra['overlap'], extra['op_overlap'] = out[3], out[4]
+            return out[:3]
+
+        out = self._finish_chain(h, run3, frame_of_step, return_frames)
+        info = {'overlap': extra['overlap']}
+        if return_frames > 1:
+            info['op_overlap'] = extra['op_overlap']
+        return out, info
+
+    @torch.no_grad()
+    def sample_diverse(self, pocket, num_nodes_phar, set_sizes, strength=1.0, width=2.0, max_shift=None, guide_below=1.0,
+                       return_frames=1, timesteps=None, noise=None, seed=None, pocket_ids=None):
+        """sample_given_pocket with the samples drawn for one pocket PUSHED APART: the same chain (ops, draws, Philox counters) with a
+        term in the mean of every posterior op that couples the samples of a set - the gradient of their Gaussian overlap at the denoised
+        estimates, times the op's posterior variance: particle guidance (cmdgen_diverse_chain; the header of csrc/kernels_diverse.hip
+        defines every term).  The whole chain runs on the device, on one handle: a set is never split.
+
+        set_sizes: the batch partitioned into sets of consecutive samples, "the draws for one pocket" (a set's pockets are normally
+        copies of one pocket, given in one frame; that is not checked, and the members' numbers of points differ freely).  strength
+        (dimensionless; 0: sample_given_pocket, bit for bit) and width (A) shape the overlap exp(-r^2 / (2 width^2)) between points of
+        different samples of a set; max_shift (A, default restraints.DEFAULT_MAX_SHIFT) caps a point's displacement per op; ops with
+        t / T > guide_below are not guided.  The other arguments as sample_given_pocket.
+        Returns sample_given_pocket's tuple plus {'overlap': [B]}, the mean overlap of every returned sample with the others of its set
+        (0 for a set of one) - and 'op_overlap' [timesteps, B], the same at every op's denoised estimate, when return_frames > 1."""
+        from .. import restraints as rs
+        timesteps = self._checked_frames(timesteps, return_frames)
+        sizes, nph, px, poh = self._pocket_inputs(pocket, num_nodes_phar)
+        sets = rs.check_set_sizes(set_sizes, nph)
+        strength, width, max_shift, guide_below = rs.check_diverse_scalars(strength, width, rs.DEFAULT_MAX_SHIFT if max_shift is None else max_shift,
+                                                                           guide_below)
+        h, phar_mask, noise, seed = self._prepare_sample(nph, (nph, sizes), pocket['x'].device, timesteps, noise, seed, guide=True)
+        run = lambda: h.diverse_chain(px, poh, timesteps, sets, strength=strength, width=width, max_shift=max_shift, guide_below=guide_below,
+                                      noise=noise, seed=seed, pocket_ids=pocket_ids, want_steps=return_frames > 1,
+                                      use_graph=self.use_hip_graph)
+        out, info = self._finish_diverse(h, run, self.inpaint_frames(1, 1, timesteps, return_frames), return_frames)
+        return out[0], out[1], phar_mask, pocket['mask'], info
+
     @staticmethod
     def group_weights(weights, n_groups, n_members):
         """weights None (uniform), [M] or [G, M] -> float32 numpy [G, M], every row normalised to sum 1 in float64."""
@@ -807,6 +851,10 @@ class SimpleConditionalDDPM(ConditionalDDPM):
     def sample_restrained(self, *args, **kwargs):
         raise NotImplementedError('sample_restrained is not implemented for SimpleConditionalDDPM (no centre-of-mass projection: the '
                                   'guidance frame follows the projections); use ConditionalDDPM')
+
+    def sample_diverse(self, *args, **kwargs):
+        raise NotImplementedError('sample_diverse is not implemented for SimpleConditionalDDPM (no centre-of-mass projection: the '
+                                  'frame in which the samples of a set are compared follows the projections); use ConditionalDDPM')
 
     def sample_restrained_given_pockets(self, *args, **kwargs):
         raise NotImplementedError('sample_restrained_given_pockets is not implemented for SimpleConditionalDDPM (no centre-of-mass '

@@ -87,6 +87,8 @@ SYMBOLS = [
     ('cmdgen_multi_restrained_edit_chain', C.c_int, [_vp, _fp, _fp, C.c_int64, _i64p, _vp, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32,
                                                      C.c_int32, _fp, C.c_int64, C.c_uint64, _i64p, _fp, _fp, _fp, _fp, _vp, C.c_int64,
                                                      C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _fp, _fp, C.c_int32, _vp]),
+    ('cmdgen_diverse_chain', C.c_int, [_vp, _fp, _fp, C.c_int32, C.c_int64, _i64p, C.c_float, C.c_float, C.c_float, C.c_float,
+                                       _fp, C.c_uint64, _i64p, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int32, _vp]),
     ('cmdgen_set_guide_table', C.c_int, [_vp, C.c_int32, _vp]),
     ('cmdgen_param_count', C.c_int, [_vp, _i64p]),
     ('cmdgen_param_offset', C.c_int, [_vp, C.c_char_p, _i64p, _i64p]),
@@ -450,6 +452,33 @@ class Handle:
             _ptr(noise), self._seed(seed), self._pocket_ids(pocket_ids), _ptr(xh_phar), _ptr(xh_pocket),
             _ptr(z_steps), _ptr(p_steps), _ptr(energy), _ptr(op_energy), int(bool(use_graph)), self._stream()), 'cmdgen_restrained_chain')
         return xh_phar, xh_pocket, z_steps, energy, op_energy
+
+    MAX_SET_ROWS = 8192              # include/cmdgen_hip.h: CMDGEN_MAX_SET_ROWS
+
+    def diverse_chain(self, pocket_x, pocket_onehot, timesteps: int, set_sizes: Sequence[int], strength: float = 1.0, width: float = 2.0,
+                      max_shift: float = DEFAULT_MAX_SHIFT, guide_below: float = 1.0, noise=None, seed: int = 0,
+                      pocket_ids: Optional[Sequence[int]] = None, want_steps: bool = False, use_graph: bool = True):
+        """cmdgen_diverse_chain: sample_chain with a term in every posterior op that pushes the samples of a set apart (the header of
+        kernels_diverse.hip defines it).  set_sizes: the layout's samples partitioned into sets of consecutive samples, "the draws for one
+        pocket"; strength (dimensionless), width (A), max_shift (A per op and point), guide_below as restrained_chain's.
+        -> (xh_phar, xh_pocket, z_steps, overlap [B] of the output, op_overlap [K, B] or None)."""
+        import torch
+        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
+        dev = pocket_x.device
+        self._check_dev(pocket_x, (self.n_pocket, 3))
+        self._check_dev(pocket_onehot, (self.n_pocket, R))
+        if noise is not None:
+            self._check_dev(noise, (timesteps + 2, self.n_phar, 3 + P))
+        sizes = np.ascontiguousarray(np.asarray(set_sizes, dtype=np.int64).reshape(-1))
+        xh_phar, xh_pocket, z_steps, p_steps = self._chain_outputs(self.n_phar, timesteps, want_steps, dev)
+        overlap = torch.empty((self.batch,), dtype=torch.float32, device=dev)
+        op_overlap = torch.empty((timesteps, self.batch), dtype=torch.float32, device=dev) if want_steps else None
+        self._check(self.lib.cmdgen_diverse_chain(
+            self.h, _ptr(pocket_x), _ptr(pocket_onehot), int(timesteps), len(sizes), sizes.ctypes.data_as(_i64p),
+            float(strength), float(width), float(max_shift), float(guide_below),
+            _ptr(noise), self._seed(seed), self._pocket_ids(pocket_ids), _ptr(xh_phar), _ptr(xh_pocket),
+            _ptr(z_steps), _ptr(p_steps), _ptr(overlap), _ptr(op_overlap), int(bool(use_graph)), self._stream()), 'cmdgen_diverse_chain')
+        return xh_phar, xh_pocket, z_steps, overlap, op_overlap
 
     MAX_GROUP = 8                    # include/cmdgen_hip.h: CMDGEN_MAX_GROUP
 

@@ -426,6 +426,36 @@ class PharPocketDDPM(nn.Module):
         return self._point_lists(xh_phar, {'size': num_nodes_phar}), info
 
     @torch.no_grad()
+    def generate_phars_diverse(self, pdb_file, n_samples, pocket_ids=None, ref_ligand=None, num_nodes_phar=None, strength=1.0, width=2.0,
+                               max_shift=None, guide_below=1.0, timesteps=None, seed=None, noise=None):
+        """Generate n_samples DIFFERENT pharmacophores inside a pocket (ConditionalDDPM.sample_diverse): the n_samples copies of the
+        pocket form one set, and at every denoising step each sample is pushed away from the others where their points overlap.
+
+        strength (0: independent draws, generate_phars' chain), width (A), max_shift and guide_below as sample_diverse.  The pocket,
+        num_nodes_phar (default the size prior given the pocket) and the move back to the pocket's position as generate_phars_restrained.
+        -> (one point list per sample, [(type name, (x, y, z))] in the PDB's frame - edit_phars' format, the ``candidates`` of
+        score_phars - and {'overlap': [n_samples]}, the mean overlap of every returned sample with the others, to rank on)."""
+        assert (pocket_ids is None) ^ (ref_ligand is None)
+        if not isinstance(self.ddpm, ConditionalDDPM):
+            raise NotImplementedError('generate_phars_diverse needs the conditional model (mode pocket_conditioning)')
+        pocket = self._pdb_pocket(pdb_file, n_samples, pocket_ids, ref_ligand)
+        pocket_com_before = _scatter_mean(pocket['x'], pocket['mask'], n_samples)
+        if num_nodes_phar is None:
+            num_nodes_phar = torch.as_tensor(self.ddpm.size_distribution.sample_conditional(n1=None, n2=pocket['size']), device=self.device)
+        else:
+            num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device).reshape(-1)
+            if num_nodes_phar.numel() == 1:
+                num_nodes_phar = num_nodes_phar.expand(n_samples)
+        num_nodes_phar = num_nodes_phar.to(INT_TYPE)
+        xh_phar, xh_pocket, phar_mask, pocket_mask, info = self.ddpm.sample_diverse(
+            pocket, num_nodes_phar, [n_samples], strength=strength, width=width, max_shift=max_shift, guide_below=guide_below,
+            timesteps=timesteps, seed=seed, noise=noise)
+        # move the points back to the original pocket position (as generate_phars)
+        pocket_com_after = _scatter_mean(xh_pocket[:, :self.x_dims], pocket_mask, n_samples)
+        xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
+        return self._point_lists(xh_phar, {'size': num_nodes_phar}), info
+
+    @torch.no_grad()
     def generate_phars_multi_restrained(self, pdb_files, n_samples, restraints, pocket_ids=None, ref_ligands=None, num_nodes_phar=None,
                                         weights=None, clash=None, scale=1.0, max_shift=None, guide_below=1.0, timesteps=None, seed=None,
                                         noise=None, group_ids=None):

@@ -124,3 +124,35 @@ def check_scalars(scale, max_shift, guide_below):
     if not 0.0 <= guide_below <= 1.0:
         raise ValueError(f'guide_below={guide_below} must be in [0, 1]')
     return scale, max_shift, guide_below
+
+
+# ---- diverse sampling (ConditionalDDPM.sample_diverse): its scalar and partition checks live beside check_scalars
+MAX_SET_ROWS = 8192                  # = CMDGEN_MAX_SET_ROWS (include/cmdgen_hip.h): phar rows of one set
+
+
+def check_diverse_scalars(strength, width, max_shift, guide_below):
+    """The scalars of diverse sampling (ConditionalDDPM.sample_diverse, cmdgen_diverse_chain), checked as check_scalars checks its own."""
+    strength, width = float(strength), float(width)
+    if not math.isfinite(strength) or strength < 0.0:
+        raise ValueError(f'strength={strength} must be finite and >= 0')
+    if not math.isfinite(width) or width <= 0.0:
+        raise ValueError(f'width={width} must be finite and > 0')
+    _, max_shift, guide_below = check_scalars(0.0, max_shift, guide_below)
+    return strength, width, max_shift, guide_below
+
+
+def check_set_sizes(set_sizes, num_nodes_phar):
+    """set_sizes: the samples partitioned into sets of consecutive samples -> int64 array [S], checked against num_nodes_phar [B]."""
+    nph = np.asarray(num_nodes_phar, dtype=np.int64).reshape(-1)
+    raw = np.asarray(set_sizes).reshape(-1)
+    if len(raw) < 1 or not np.all(np.isfinite(raw.astype(np.float64))) or np.any(raw != np.floor(raw)):
+        raise ValueError(f'set_sizes={list(raw)}: expected at least one integer size')
+    sizes = raw.astype(np.int64)
+    if np.any(sizes < 1):
+        raise ValueError(f'set_sizes={sizes.tolist()}: every set has at least one sample')
+    if int(sizes.sum()) != len(nph):
+        raise ValueError(f'set_sizes sums to {int(sizes.sum())}, the batch has {len(nph)} samples')
+    rows = np.add.reduceat(nph, np.concatenate([[0], np.cumsum(sizes)[:-1]]))
+    if np.any(rows > MAX_SET_ROWS):
+        raise ValueError(f'set_sizes: set {int(np.argmax(rows))} has {int(rows.max())} phar rows, at most {MAX_SET_ROWS}')
+    return sizes

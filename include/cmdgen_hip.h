@@ -627,6 +627,42 @@ int cmdgen_multi_restrained_edit_chain(cmdgen_handle* h, const float* pocket_x, 
                                        float* energy_out /* dev [G][2] */, float* op_energy_out /* dev [n_steps][G] or NULL */,
                                        int32_t use_graph, cmdgen_stream stream);
 
+/* ---- diverse sampling: push apart the samples drawn for one pocket ---------------------- */
+/* cmdgen_sample_chain's chain (the same init, ops, draws, Philox counters keyed by pocket_ids, saved steps, decode and CoG fix; the
+ * evaluations run their own k_readout) with a term in the mean of every posterior op that couples the samples of a SET: particle guidance
+ * (Corso et al., 2023).  The reference draws independently and has nothing like it; the definition is the project's (the header of
+ * csrc/kernels_diverse.hip; INTEGRATION.md, "Diverse sampling").
+ *   Sets.  The layout's B samples are partitioned into n_sets sets of consecutive samples (set_size_host, every size >= 1, summing to B): "the
+ *     draws for one pocket".  Members may have different numbers of points.  The library does not check that the members' pockets are copies
+ *     of each other: positions are compared in the frame in which the caller gives each sample's pocket.
+ *   With z, e (zero under the NaN guard), P, P_in, n_x, coef and the guide row (sigma_t, alpha_t) as for cmdgen_restrained_chain, w = width
+ *   (A), k = strength (dimensionless) and M_a the size of sample a's set, at every posterior op t -> s:
+ *   1. xhat_ai = n_x (z.x_ai - sigma_t e_ai) / alpha_t;  shift_a = n_x (com(P_a.x) - com(P_a,in.x / n_x));  y_ai = xhat_ai - shift_a.
+ *   2. o_ai = (1 / (M_a - 1)) sum_{b != a, same set} sum_j exp(-|y_ai - y_bj|^2 / (2 w^2)), overlap_a = sum_i o_ai.  The set's energy is
+ *      E = k / (M - 1) sum_{a < b} sum_{i, j} exp(.) and g_ai = -(k / ((M_a - 1) w^2)) sum_{b != a} sum_j exp(.) (y_ai - y_bj).
+ *   3. d_ai = -(n_x coef.z)^2 g_ai (A), scaled back to max_shift when longer.  An op with t / T > guide_below, a sample with M_a = 1 and a
+ *      call with k = 0 have no displacement: nothing is added, not even a zero.
+ *   4. mu.x_ai = z.x_ai / coef.x - coef.y e_ai + d_ai / n_x; everything else is the plain step's.  The decode is not guided.
+ *   overlap_out  dev [B]: step 2 on the RETURNED rows, shift_a = com(xh_pocket_out_a.x) - n_x com(P_a,in.x / n_x); 0 where M_a = 1.
+ *   op_overlap_out  dev [K][B] or NULL: step 2 at every op's estimate, also when k = 0 or the op is above guide_below.
+ *   the other arguments as cmdgen_sample_chain; cmdgen_set_guide_table supplies (sigma_t, alpha_t) as for cmdgen_restrained_chain.
+ * Sums run in a fixed order without float atomics: two runs are equal bit for bit, captured or eager.  k = 0, guide_below = 0 and sets of one
+ * member each give cmdgen_sample_chain's outputs bit for bit (on a handle with readout_in_coord = 0); overlap_out is still reported under k = 0.
+ * The chain has a slot of its own; the guide rows, the scalars and the set tables are part of its table block, so a changed partition or
+ * scalar prepares the slot (and its graph) again.
+ * Refused with CMDGEN_EINVAL, nothing launched: null pointers, n_sets outside [1, B], a set size below 1, sizes that do not sum to B, strength
+ * non-finite or negative, width non-finite or <= 0, max_shift <= 0, guide_below outside [0, 1], a set with more than CMDGEN_MAX_SET_ROWS phar
+ * rows (a capacity cap: the pair launch costs rows^2), a sample beyond the step's 64 KiB of LDS, a no_com_projection handle; the joint model
+ * (CMDGEN_ESTATE). */
+#define CMDGEN_MAX_SET_ROWS 8192
+int cmdgen_diverse_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot, int32_t timesteps,
+                         int64_t n_sets, const int64_t* set_size_host,
+                         float strength, float width, float max_shift, float guide_below,
+                         const float* noise, uint64_t seed, const int64_t* pocket_ids_host,
+                         float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                         float* overlap_out /* dev [B] */, float* op_overlap_out /* dev [K][B] or NULL */,
+                         int32_t use_graph, cmdgen_stream stream);
+
 /* ---- training step (conditional model) -------------------------------------------------- */
 /* The trainable tensors of EGNNDynamics live in ONE flat fp32 device buffer owned by the caller, in the
  * reference's registration order (the state_dict order below 'ddpm.dynamics.': weight then bias of every
