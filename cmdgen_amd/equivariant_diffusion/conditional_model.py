@@ -9,6 +9,7 @@ scalar table and reads the deferred checks afterwards.
 from __future__ import annotations
 
 import math
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -155,14 +156,9 @@ class ConditionalDDPM(EnVariationalDiffusion):
         return_frames > 1 the first two carry a leading frame axis.
         """
         timesteps = self._checked_frames(timesteps, return_frames)
-        sizes, nph, px, poh = self._pocket_inputs(pocket, num_nodes_phar)
-        h, phar_mask, noise, seed = self._prepare_sample(nph, (nph, sizes), pocket['x'].device, timesteps, noise, seed)
-        run = lambda: h.sample_chain(px, poh, timesteps, noise=noise, seed=seed, pocket_ids=pocket_ids,
-                                     want_steps=return_frames > 1, use_graph=self.use_hip_graph)
-        # frames: idx = s*return_frames//timesteps for steps with (s*return_frames) % timesteps == 0
-        # (conditional_model.py:439-442); frame 0 is overwritten by the final sample (:460-461).
-        out = self._finish_chain(h, run, self.inpaint_frames(1, 1, timesteps, return_frames), return_frames)
-        return out[0], out[1], phar_mask, pocket['mask']
+        ps = self._one_pocket(pocket)
+        nph = self._prior_sizes(num_nodes_phar, ps)
+        return self._run_chain('sample_chain', ps, nph, timesteps, return_frames=return_frames, noise=noise, seed=seed, ids=pocket_ids)
 
     # ---- what the chain methods below share
     def _checked_frames(self, timesteps, return_frames):
@@ -172,21 +168,97 @@ class ConditionalDDPM(EnVariationalDiffusion):
         return timesteps
 
     @staticmethod
-    def _pocket_inputs(pocket, num_nodes_phar):
-        """sample_given_pocket's arguments, checked -> (pocket sizes, num_nodes_phar as host int64 arrays, pocket x, one_hot as float32)."""
+    def _check_mask_order(mask, what):
+        if mask.numel() > 1 and bool((mask[1:] < mask[:-1]).any()):
+            raise ValueError(f'{what} must be ascending and contiguous')
+
+    # The pocket side of an entry - one pocket per sample, or a group of pockets per sample - is what the run and the epilogue need of it:
+    # n owners (samples or groups), sizes, device, layout(nph) for set_layout, args (the leading arguments of the Handle's chain method), ids
+    # (the name of its Philox-id keyword), split (xh_pocket back per pocket) and masks (as the entry returns them).
+    def _one_pocket(self, pocket, masks='pocket mask'):
+        """The pocket side of the single-pocket entries (masks: what the mask is called in the refusal)."""
+        self._check_mask_order(pocket['mask'], masks)
         sizes = pocket['size'].detach().to('cpu', torch.int64).numpy()
+        f32 = lambda t: t.detach().to(torch.float32).contiguous()
+        return SimpleNamespace(grouped=False, n=len(sizes), sizes=sizes, device=pocket['x'].device, layout=lambda nph: (nph, sizes),
+                               args=(f32(pocket['x']), f32(pocket['one_hot'])), ids='pocket_ids', split=lambda xh_pocket: xh_pocket,
+                               masks=pocket['mask'])
+
+    def _pocket_groups(self, pockets, weights):
+        """The pocket side of the *_given_pockets entries: M pocket dicts batched over the same G groups, in the member layout."""
+        pockets, M, G = self._checked_pockets(pockets)
+        w = self.group_weights(weights, G, M)
+        sizes, rows, px, poh = self._member_layout(pockets, M, G)
+        return SimpleNamespace(grouped=True, n=G, M=M, w=w, sizes=sizes, device=pockets[0]['x'].device,
+                               layout=lambda nph: (np.repeat(nph, M), sizes.reshape(-1)), args=(px, poh, [M] * G, w.reshape(-1)), ids='group_ids',
+                               split=lambda xh_pocket: [xh_pocket[..., r, :] for r in rows], masks=[q['mask'] for q in pockets])
+
+    @staticmethod
+    def _prior_sizes(num_nodes_phar, ps):
+        """num_nodes_phar of an entry that starts from the prior, one per owner of the pocket side -> host int64 array."""
         nph = torch.as_tensor(num_nodes_phar).detach().to('cpu', torch.int64).numpy()
-        assert len(nph) == len(pocket['size'])
-        pm = pocket['mask']
-        if pm.numel() > 1 and bool((pm[1:] < pm[:-1]).any()):
-            raise ValueError('pocket mask must be ascending and contiguous')
-        return sizes, nph, pocket['x'].detach().to(torch.float32).contiguous(), pocket['one_hot'].detach().to(torch.float32).contiguous()
+        if not ps.grouped:
+            assert len(nph) == ps.n
+            return nph
+        if len(nph.reshape(-1)) != ps.n:
+            raise ValueError(f'num_nodes_phar has {len(nph.reshape(-1))} entries for {ps.n} groups')
+        return nph.reshape(-1)
+
+    def _given_sizes(self, phar, ps):
+        """The sizes of a GIVEN pharmacophore, batched over the owners of the pocket side with a sorted mask -> host int64 array.  (Per
+        group its rows are checked here; per sample the Handle checks them.)"""
+        nph = phar['size'].detach().to('cpu', torch.int64).numpy().reshape(-1)
+        if len(nph) != ps.n:
+            raise ValueError(f'phar has {len(nph)} samples, pocket {ps.n}')
+        self._check_mask_order(phar['mask'], 'batch masks')
+        if ps.grouped:
+            self._check_phar_rows(phar, int(nph.sum()))
+        return nph
+
+    def _given_rows(self, phar, ps, fix_coords, fix_types):
+        """The given side of the edit entries -> (nph, the device tensors the Handle takes behind the pocket side's: x, one_hot, fix_x, fix_h)."""
+        nph = self._given_sizes(phar, ps)
+        f32 = lambda t: t.detach().to(ps.device, torch.float32).contiguous()
+        masks = [self._row_mask(v, name, int(nph.sum()), ps.device) for v, name in ((fix_coords, 'fix_coords'), (fix_types, 'fix_types'))]
+        return nph, (f32(phar['x']), f32(phar['one_hot']), *masks)
+
+    @staticmethod
+    def _guide_kw(restraints, nph, clash, scale, max_shift, guide_below, owner='sample'):
+        """The guidance arguments of the restrained entries, checked -> (the records, the scalar keyword arguments of the Handle's
+        restrained chains).  owner: what a restraint's 'sample' is called in the refusals ('group' where the records belong to the groups)."""
+        from .. import restraints as rs
+        rec = rs.records(restraints, nph, owner=owner)
+        clash_r, clash_k = rs.clash_pair(clash)
+        scale, max_shift, guide_below = rs.check_scalars(scale, rs.DEFAULT_MAX_SHIFT if max_shift is None else max_shift, guide_below)
+        return rec, dict(clash_radius=clash_r, clash_k=clash_k, scale=scale, max_shift=max_shift, guide_below=guide_below)
+
+    def _run_chain(self, method, ps, nph, timesteps, *, given=(), plan=None, behind=(), steer=None, info=None, frames=(1, 1), return_frames=1,
+                   noise, seed, ids):
+        """What the sampling entries share once their arguments are checked: prepare the handle, run the Handle's `method` on the pocket
+        side ps, finish, split the pockets back.  given: the device tensors of _given_rows, with plan: dict(start, resamplings,
+        jump_length) as that method takes them (the noise must cover the plan's draws); steer: the keyword arguments of a guided or diverse
+        chain (behind: what a from-prior one takes by position behind timesteps, its records or set sizes), with info: the names
+        _finish_with_info reports its side outputs under; frames: (resamplings, jump_length) of the frame schedule.
+        -> (xh_phar, xh_pocket as ps splits it, phar_mask, ps.masks) and the info dict, if any."""
+        edit_plan = None if plan is None else (plan.get('start', timesteps), plan['resamplings'], plan['jump_length'])
+        h, phar_mask, noise, seed = self._prepare_sample(nph, ps.layout(nph), ps.device, timesteps, noise, seed, steer is not None, edit_plan)
+        kw = {**(plan or {}), **(steer or {}), 'noise': noise, 'seed': seed, ps.ids: ids, 'want_steps': return_frames > 1,
+              'use_graph': self.use_hip_graph}
+        run = lambda: getattr(h, method)(*ps.args, *given, timesteps, *behind, **kw)
+        # frames: idx = s*return_frames//timesteps for steps with (s*return_frames) % timesteps == 0
+        # (conditional_model.py:439-442); frame 0 is overwritten by the final sample (:460-461).
+        frame_of_step = self.inpaint_frames(*frames, timesteps, return_frames)
+        if info is None:
+            out = self._finish_chain(h, run, frame_of_step, return_frames)
+            return out[0], ps.split(out[1]), phar_mask, ps.masks
+        out, info = self._finish_with_info(h, run, frame_of_step, return_frames, info)
+        return out[0], ps.split(out[1]), phar_mask, ps.masks, info
 
     def _prepare_sample(self, nph, layout, device, timesteps, noise, seed, guide=False, plan=None):
         """The sample family's preparation once the arguments are checked: the learned schedule, the handle with `layout` (num_phar and
         num_pocket of every sample of the device layout), the step table (guide: and the guide table), the phar mask of nph (one entry per
         sample or group), the noise on the device and a seed.  plan: (start, resamplings, jump_length) of an edit chain, whose draws the
-        noise must cover (_prepare_edit).  -> (h, phar_mask, noise, seed)."""
+        noise must cover.  -> (h, phar_mask, noise, seed)."""
         self.refresh_learned_schedule()
         h = self.dynamics.hip_handle()
         h.set_layout(*layout)
@@ -204,10 +276,6 @@ class ConditionalDDPM(EnVariationalDiffusion):
             seed = fresh_seed()
         return h, utils.num_nodes_to_batch_mask(len(nph), torch.as_tensor(nph), device), noise, seed
 
-    def _prepare_edit(self, nph, layout, device, timesteps, start, resamplings, jump_length, noise, seed, guide=False):
-        """The edit family's preparation: _prepare_sample, and the noise covers the draws of the edit plan.  -> (h, phar_mask, noise, seed)."""
-        return self._prepare_sample(nph, layout, device, timesteps, noise, seed, guide, (start, resamplings, jump_length))
-
     def _checked_start(self, timesteps, start):
         """edit's timesteps and start level, checked -> (timesteps, start) as ints."""
         timesteps = self.T if timesteps is None else int(timesteps)
@@ -216,49 +284,30 @@ class ConditionalDDPM(EnVariationalDiffusion):
             raise ValueError(f'start={start} must be an integer level in [1, timesteps={timesteps}]')
         return timesteps, int(start)
 
-    @staticmethod
-    def _phar_pocket_sizes(phar, pocket):
-        """The sizes of a given pharmacophore and its pocket, both batched over the same samples with sorted masks -> (pocket sizes, nph)."""
-        n_samples = len(pocket['size'])
-        sizes = pocket['size'].detach().to('cpu', torch.int64).numpy()
-        nph = phar['size'].detach().to('cpu', torch.int64).numpy()
-        if len(nph) != n_samples:
-            raise ValueError(f'phar has {len(nph)} samples, pocket {n_samples}')
-        for m in (phar['mask'], pocket['mask']):
-            if m.numel() > 1 and bool((m[1:] < m[:-1]).any()):
-                raise ValueError('batch masks must be ascending and contiguous')
-        return sizes, nph
-
-    @staticmethod
-    def _group_phar_sizes(phar, G):
-        """... of a pharmacophore given per GROUP of pockets (the pockets: _checked_pockets) -> nph."""
-        nph = phar['size'].detach().to('cpu', torch.int64).numpy().reshape(-1)
-        if len(nph) != G:
-            raise ValueError(f'phar has {len(nph)} samples, pocket {G}')
-        pm = phar['mask']
-        if pm.numel() > 1 and bool((pm[1:] < pm[:-1]).any()):
-            raise ValueError('batch masks must be ascending and contiguous')
-        return nph
-
     def _check_phar_rows(self, phar, n_phar):
         if tuple(phar['x'].shape) != (n_phar, self.n_dims) or tuple(phar['one_hot'].shape) != (n_phar, self.phar_nf):
             raise ValueError(f"phar x / one_hot have shapes {tuple(phar['x'].shape)} / {tuple(phar['one_hot'].shape)}: expected "
                              f'[{n_phar}, {self.n_dims}] / [{n_phar}, {self.phar_nf}] (sum(size) rows)')
 
-    def _finish_restrained(self, h, run, frame_of_step, return_frames):
-        """_finish_chain for a restrained chain, whose run() returns (xh_phar, xh_pocket, z_steps, energy [B, 2], op_energy).
-        -> (_finish_chain's result, {'energy': [B], 'max_violation': [B]} and, with return_frames > 1, 'op_energy')."""
-        extra = {}
+    ENERGY_INFO = ('energy', 'max_violation', 'op_energy')          # of the restrained chains: energy [owners, 2], op_energy
+    OVERLAP_INFO = ('overlap', 'op_overlap')                        # of the diverse chain: overlap [B], op_overlap
+
+    def _finish_with_info(self, h, run, frame_of_step, return_frames, names):
+        """_finish_chain for a chain with side outputs, whose run() returns (xh_phar, xh_pocket, z_steps, per owner, per op and owner).
+        names: the info key of every column of the per-owner output (one name: of the output itself), then the per-op output's.
+        -> (_finish_chain's result, the info dict - the per-op entry only with return_frames > 1)."""
+        extra = []
 
         def run3():
             out = run()
-            extra['energy'], extra['op_energy'] = out[3], out[4]
+            extra[:] = out[3:]
             return out[:3]
 
         out = self._finish_chain(h, run3, frame_of_step, return_frames)
-        info = {'energy': extra['energy'][:, 0].clone(), 'max_violation': extra['energy'][:, 1].clone()}
+        *cols, per_op = names
+        info = {cols[0]: extra[0]} if len(cols) == 1 else {name: extra[0][:, c].clone() for c, name in enumerate(cols)}
         if return_frames > 1:
-            info['op_energy'] = extra['op_energy']
+            info[per_op] = extra[1]
         return out, info
 
     def _level_noise(self, noise, R, K, n_phar, device):
@@ -288,34 +337,12 @@ class ConditionalDDPM(EnVariationalDiffusion):
         displacement per op; ops with t / T > guide_below are not guided.  The other arguments as sample_given_pocket.
         Returns sample_given_pocket's tuple plus {'energy': [B], 'max_violation': [B]} of the returned sample (and 'op_energy'
         [timesteps, B], the energy at every op's denoised estimate, when return_frames > 1)."""
-        from .. import restraints as rs
         timesteps = self._checked_frames(timesteps, return_frames)
-        sizes, nph, px, poh = self._pocket_inputs(pocket, num_nodes_phar)
-        rec = rs.records(restraints, nph)
-        clash_r, clash_k = rs.clash_pair(clash)
-        scale, max_shift, guide_below = rs.check_scalars(scale, rs.DEFAULT_MAX_SHIFT if max_shift is None else max_shift, guide_below)
-        h, phar_mask, noise, seed = self._prepare_sample(nph, (nph, sizes), pocket['x'].device, timesteps, noise, seed, guide=True)
-        run = lambda: h.restrained_chain(px, poh, timesteps, rec, clash_radius=clash_r, clash_k=clash_k, scale=scale, max_shift=max_shift,
-                                         guide_below=guide_below, noise=noise, seed=seed, pocket_ids=pocket_ids,
-                                         want_steps=return_frames > 1, use_graph=self.use_hip_graph)
-        out, info = self._finish_restrained(h, run, self.inpaint_frames(1, 1, timesteps, return_frames), return_frames)
-        return out[0], out[1], phar_mask, pocket['mask'], info
-
-    def _finish_diverse(self, h, run, frame_of_step, return_frames):
-        """_finish_chain for the diverse chain, whose run() returns (xh_phar, xh_pocket, z_steps, overlap [B], op_overlap).
-        -> (_finish_chain's result, {'overlap': [B]} and, with return_frames > 1, 'op_overlap')."""
-        extra = {}
-
-        def run3():
-            out = run()
-            extra['overlap'], extra['op_overlap'] = out[3], out[4]
-            return out[:3]
-
-        out = self._finish_chain(h, run3, frame_of_step, return_frames)
-        info = {'overlap': extra['overlap']}
-        if return_frames > 1:
-            info['op_overlap'] = extra['op_overlap']
-        return out, info
+        ps = self._one_pocket(pocket)
+        nph = self._prior_sizes(num_nodes_phar, ps)
+        rec, steer = self._guide_kw(restraints, nph, clash, scale, max_shift, guide_below)
+        return self._run_chain('restrained_chain', ps, nph, timesteps, behind=(rec,), steer=steer, info=self.ENERGY_INFO, return_frames=return_frames,
+                               noise=noise, seed=seed, ids=pocket_ids)
 
     @torch.no_grad()
     def sample_diverse(self, pocket, num_nodes_phar, set_sizes, strength=1.0, width=2.0, max_shift=None, guide_below=1.0,
@@ -334,16 +361,14 @@ class ConditionalDDPM(EnVariationalDiffusion):
         (0 for a set of one) - and 'op_overlap' [timesteps, B], the same at every op's denoised estimate, when return_frames > 1."""
         from .. import restraints as rs
         timesteps = self._checked_frames(timesteps, return_frames)
-        sizes, nph, px, poh = self._pocket_inputs(pocket, num_nodes_phar)
+        ps = self._one_pocket(pocket)
+        nph = self._prior_sizes(num_nodes_phar, ps)
         sets = rs.check_set_sizes(set_sizes, nph)
         strength, width, max_shift, guide_below = rs.check_diverse_scalars(strength, width, rs.DEFAULT_MAX_SHIFT if max_shift is None else max_shift,
                                                                            guide_below)
-        h, phar_mask, noise, seed = self._prepare_sample(nph, (nph, sizes), pocket['x'].device, timesteps, noise, seed, guide=True)
-        run = lambda: h.diverse_chain(px, poh, timesteps, sets, strength=strength, width=width, max_shift=max_shift, guide_below=guide_below,
-                                      noise=noise, seed=seed, pocket_ids=pocket_ids, want_steps=return_frames > 1,
-                                      use_graph=self.use_hip_graph)
-        out, info = self._finish_diverse(h, run, self.inpaint_frames(1, 1, timesteps, return_frames), return_frames)
-        return out[0], out[1], phar_mask, pocket['mask'], info
+        steer = dict(strength=strength, width=width, max_shift=max_shift, guide_below=guide_below)
+        return self._run_chain('diverse_chain', ps, nph, timesteps, behind=(sets,), steer=steer, info=self.OVERLAP_INFO, return_frames=return_frames,
+                               noise=noise, seed=seed, ids=pocket_ids)
 
     @staticmethod
     def group_weights(weights, n_groups, n_members):
@@ -381,18 +406,10 @@ class ConditionalDDPM(EnVariationalDiffusion):
         [G] global group ids of the Philox draws.  With M = 1 this is sample_given_pocket, bit for bit.
         Returns (xh_phar [Nu, 3+P], [xh_pocket_m], phar_mask, [pocket_mask_m]); with return_frames > 1 the tensors carry the leading
         frame axis of sample_given_pocket."""
-        pockets, M, G = self._checked_pockets(pockets)
-        nph = torch.as_tensor(num_nodes_phar).detach().to('cpu', torch.int64).numpy().reshape(-1)
-        if len(nph) != G:
-            raise ValueError(f'num_nodes_phar has {len(nph)} entries for {G} groups')
-        w = self.group_weights(weights, G, M)
+        ps = self._pocket_groups(pockets, weights)
+        nph = self._prior_sizes(num_nodes_phar, ps)
         timesteps = self._checked_frames(timesteps, return_frames)
-        sizes, rows, px, poh = self._member_layout(pockets, M, G)
-        h, phar_mask, noise, seed = self._prepare_sample(nph, (np.repeat(nph, M), sizes.reshape(-1)), pockets[0]['x'].device, timesteps, noise, seed)
-        run = lambda: h.multi_pocket_chain(px, poh, [M] * G, w.reshape(-1), timesteps, noise=noise, seed=seed, group_ids=group_ids,
-                                           want_steps=return_frames > 1, use_graph=self.use_hip_graph)
-        out = self._finish_chain(h, run, self.inpaint_frames(1, 1, timesteps, return_frames), return_frames)
-        return out[0], [out[1][..., r, :] for r in rows], phar_mask, [q['mask'] for q in pockets]
+        return self._run_chain('multi_pocket_chain', ps, nph, timesteps, return_frames=return_frames, noise=noise, seed=seed, ids=group_ids)
 
     @torch.no_grad()
     def sample_restrained_given_pockets(self, pockets, num_nodes_phar, restraints, weights=None, clash=None, scale=1.0, max_shift=None,
@@ -408,24 +425,12 @@ class ConditionalDDPM(EnVariationalDiffusion):
         scale, max_shift and guide_below as sample_restrained (scale = 0: sample_given_pockets, bit for bit).
         Returns sample_given_pockets' tuple plus {'energy': [G], 'max_violation': [G]} of the returned sample against all its pockets
         (and 'op_energy' [timesteps, G] when return_frames > 1)."""
-        from .. import restraints as rs
-        pockets, M, G = self._checked_pockets(pockets)
-        nph = torch.as_tensor(num_nodes_phar).detach().to('cpu', torch.int64).numpy().reshape(-1)
-        if len(nph) != G:
-            raise ValueError(f'num_nodes_phar has {len(nph)} entries for {G} groups')
-        w = self.group_weights(weights, G, M)
+        ps = self._pocket_groups(pockets, weights)
+        nph = self._prior_sizes(num_nodes_phar, ps)
         timesteps = self._checked_frames(timesteps, return_frames)
-        rec = rs.records(restraints, nph)                                 # per group: 'sample' is the group index
-        clash_r, clash_k = rs.clash_pair(clash)
-        scale, max_shift, guide_below = rs.check_scalars(scale, rs.DEFAULT_MAX_SHIFT if max_shift is None else max_shift, guide_below)
-        sizes, rows, px, poh = self._member_layout(pockets, M, G)
-        h, phar_mask, noise, seed = self._prepare_sample(nph, (np.repeat(nph, M), sizes.reshape(-1)), pockets[0]['x'].device, timesteps, noise,
-                                                         seed, guide=True)
-        run = lambda: h.multi_restrained_chain(px, poh, [M] * G, w.reshape(-1), timesteps, rec, clash_radius=clash_r, clash_k=clash_k,
-                                               scale=scale, max_shift=max_shift, guide_below=guide_below, noise=noise, seed=seed,
-                                               group_ids=group_ids, want_steps=return_frames > 1, use_graph=self.use_hip_graph)
-        out, info = self._finish_restrained(h, run, self.inpaint_frames(1, 1, timesteps, return_frames), return_frames)
-        return out[0], [out[1][..., r, :] for r in rows], phar_mask, [q['mask'] for q in pockets], info
+        rec, steer = self._guide_kw(restraints, nph, clash, scale, max_shift, guide_below)  # per group: 'sample' is the group index
+        return self._run_chain('multi_restrained_chain', ps, nph, timesteps, behind=(rec,), steer=steer, info=self.ENERGY_INFO,
+                               return_frames=return_frames, noise=noise, seed=seed, ids=group_ids)
 
     @staticmethod
     def _checked_pockets(pockets):
@@ -439,9 +444,7 @@ class ConditionalDDPM(EnVariationalDiffusion):
         for m, q in enumerate(pockets):
             if len(q['size']) != G:
                 raise ValueError(f"pockets[{m}] holds {len(q['size'])} groups, pockets[0] {G}: every dict is batched over the same groups")
-            qm = q['mask']
-            if qm.numel() > 1 and bool((qm[1:] < qm[:-1]).any()):
-                raise ValueError('pocket mask must be ascending and contiguous')
+            ConditionalDDPM._check_mask_order(q['mask'], 'pocket mask')
         return pockets, M, G
 
     def _member_layout(self, pockets, M, G):
@@ -485,21 +488,18 @@ class ConditionalDDPM(EnVariationalDiffusion):
         timesteps = self._checked_frames(timesteps, return_frames)
         if return_frames > 1 and jump_length != 1:
             raise ValueError('return_frames > 1 is only implemented for jump_length=1 (as in the joint model\'s inpaint)')
-        device = pocket['x'].device
-        sizes, nph = self._phar_pocket_sizes(phar, pocket)
+        ps = self._one_pocket(pocket, masks='batch masks')
+        nph = self._given_sizes(phar, ps)
         n_phar = int(nph.sum())
-        fixed = torch.as_tensor(phar_fixed).detach().to(device, torch.float32)
+        fixed = torch.as_tensor(phar_fixed).detach().to(ps.device, torch.float32)
         if fixed.dim() == 2 and fixed.shape[1] == 1:
             fixed = fixed[:, 0]
         if fixed.dim() != 1 or fixed.numel() != n_phar:
             raise ValueError(f'phar_fixed has shape {tuple(torch.as_tensor(phar_fixed).shape)}: expected [{n_phar}] or [{n_phar}, 1]')
-        h, phar_mask, noise, seed = self._prepare_edit(nph, (nph, sizes), device, timesteps, timesteps, resamplings, jump_length, noise, seed)
-        f32 = lambda t: t.detach().to(device, torch.float32).contiguous()
-        args = (f32(pocket['x']), f32(pocket['one_hot']), f32(phar['x']), f32(phar['one_hot']), fixed.contiguous())
-        run = lambda: h.inpaint_chain(*args, timesteps, resamplings=resamplings, jump_length=jump_length, noise=noise, seed=seed,
-                                      pocket_ids=pocket_ids, want_steps=return_frames > 1, use_graph=self.use_hip_graph)
-        out = self._finish_chain(h, run, self.inpaint_frames(resamplings, jump_length, timesteps, return_frames), return_frames)
-        return out[0], out[1], phar_mask, pocket['mask']
+        f32 = lambda t: t.detach().to(ps.device, torch.float32).contiguous()
+        return self._run_chain('inpaint_chain', ps, nph, timesteps, given=(f32(phar['x']), f32(phar['one_hot']), fixed.contiguous()),
+                               plan=dict(resamplings=resamplings, jump_length=jump_length), frames=(resamplings, jump_length),
+                               return_frames=return_frames, noise=noise, seed=seed, ids=pocket_ids)
 
     def _row_mask(self, value, name, n_phar, device):
         """A per-row mask argument ([Nl] or [Nl,1], bools or floats; None: no row) as float [Nl] on `device`."""
@@ -528,17 +528,10 @@ class ConditionalDDPM(EnVariationalDiffusion):
         counters).  noise [n_draws, Nl, 3+P] (Handle.edit_plan), seed and pocket_ids as in sample_given_pocket.
         Returns (xh_phar, xh_pocket, phar_mask, pocket_mask) like sample_given_pocket."""
         timesteps, start = self._checked_start(timesteps, start)
-        device = pocket['x'].device
-        sizes, nph = self._phar_pocket_sizes(phar, pocket)
-        fix_x = self._row_mask(fix_coords, 'fix_coords', int(nph.sum()), device)
-        fix_h = self._row_mask(fix_types, 'fix_types', int(nph.sum()), device)
-        h, phar_mask, noise, seed = self._prepare_edit(nph, (nph, sizes), device, timesteps, start, resamplings, jump_length, noise, seed)
-        f32 = lambda t: t.detach().to(device, torch.float32).contiguous()
-        args = (f32(pocket['x']), f32(pocket['one_hot']), f32(phar['x']), f32(phar['one_hot']), fix_x, fix_h)
-        run = lambda: h.edit_chain(*args, timesteps, start=start, resamplings=resamplings, jump_length=jump_length, noise=noise,
-                                   seed=seed, pocket_ids=pocket_ids, use_graph=self.use_hip_graph)
-        out = self._finish_chain(h, run, [], 1)
-        return out[0], out[1], phar_mask, pocket['mask']
+        ps = self._one_pocket(pocket, masks='batch masks')
+        nph, given = self._given_rows(phar, ps, fix_coords, fix_types)
+        return self._run_chain('edit_chain', ps, nph, timesteps, given=given,
+                               plan=dict(start=start, resamplings=resamplings, jump_length=jump_length), noise=noise, seed=seed, ids=pocket_ids)
 
     @torch.no_grad()
     def edit_restrained(self, phar, pocket, restraints, fix_coords=None, fix_types=None, start=None, resamplings=1, jump_length=1,
@@ -556,25 +549,13 @@ class ConditionalDDPM(EnVariationalDiffusion):
         restraint and no clash term, or scale = 0, the result is ``edit``'s bit for bit.
         Returns (xh_phar, xh_pocket, phar_mask, pocket_mask, {'energy': [B], 'max_violation': [B]}): the energy and the largest violation
         (A) of the returned sample, held points included at their returned positions."""
-        from .. import restraints as rs
         timesteps, start = self._checked_start(timesteps, start)
-        device = pocket['x'].device
-        sizes, nph = self._phar_pocket_sizes(phar, pocket)
-        fix_x = self._row_mask(fix_coords, 'fix_coords', int(nph.sum()), device)
-        fix_h = self._row_mask(fix_types, 'fix_types', int(nph.sum()), device)
-        rec = rs.records(restraints, nph)
-        clash_r, clash_k = rs.clash_pair(clash)
-        scale, max_shift, guide_below = rs.check_scalars(scale, rs.DEFAULT_MAX_SHIFT if max_shift is None else max_shift, guide_below)
-        h, phar_mask, noise, seed = self._prepare_edit(nph, (nph, sizes), device, timesteps, start, resamplings, jump_length, noise, seed,
-                                                       guide=True)
-        f32 = lambda t: t.detach().to(device, torch.float32).contiguous()
-        args = (f32(pocket['x']), f32(pocket['one_hot']), f32(phar['x']), f32(phar['one_hot']), fix_x, fix_h)
-        run = lambda: h.restrained_edit_chain(*args, timesteps, start=start, resamplings=resamplings, jump_length=jump_length, restraints=rec,
-                                              clash_radius=clash_r, clash_k=clash_k, scale=scale, max_shift=max_shift,
-                                              guide_below=guide_below, noise=noise, seed=seed, pocket_ids=pocket_ids,
-                                              use_graph=self.use_hip_graph)
-        out, info = self._finish_restrained(h, run, [], 1)
-        return out[0], out[1], phar_mask, pocket['mask'], info
+        ps = self._one_pocket(pocket, masks='batch masks')
+        nph, given = self._given_rows(phar, ps, fix_coords, fix_types)
+        rec, steer = self._guide_kw(restraints, nph, clash, scale, max_shift, guide_below)
+        return self._run_chain('restrained_edit_chain', ps, nph, timesteps, given=given,
+                               plan=dict(start=start, resamplings=resamplings, jump_length=jump_length), steer=dict(steer, restraints=rec),
+                               info=self.ENERGY_INFO, noise=noise, seed=seed, ids=pocket_ids)
 
     @torch.no_grad()
     def edit_given_pockets(self, phar, pockets, fix_coords=None, fix_types=None, start=None, resamplings=1, jump_length=1,
@@ -590,24 +571,11 @@ class ConditionalDDPM(EnVariationalDiffusion):
         The whole chain runs on the device (cmdgen_multi_edit_chain; its header gives the ops, the offset and the Philox counters).
         With one pocket this is edit, and with nothing held from the prior at resamplings = jump_length = 1 sample_given_pockets,
         both bit for bit.  Returns what sample_given_pockets returns: (xh_phar [Nu, 3+P], [xh_pocket_m], phar_mask, [pocket_mask_m])."""
-        pockets, M, G = self._checked_pockets(pockets)
+        ps = self._pocket_groups(pockets, weights)
         timesteps, start = self._checked_start(timesteps, start)
-        nph = self._group_phar_sizes(phar, G)
-        w = self.group_weights(weights, G, M)
-        device = pockets[0]['x'].device
-        n_phar = int(nph.sum())
-        fix_x = self._row_mask(fix_coords, 'fix_coords', n_phar, device)
-        fix_h = self._row_mask(fix_types, 'fix_types', n_phar, device)
-        self._check_phar_rows(phar, n_phar)
-        sizes, rows, px, poh = self._member_layout(pockets, M, G)
-        h, phar_mask, noise, seed = self._prepare_edit(nph, (np.repeat(nph, M), sizes.reshape(-1)), device, timesteps, start, resamplings,
-                                                       jump_length, noise, seed)
-        f32 = lambda t: t.detach().to(device, torch.float32).contiguous()
-        args = (px, poh, [M] * G, w.reshape(-1), f32(phar['x']), f32(phar['one_hot']), fix_x, fix_h)
-        run = lambda: h.multi_edit_chain(*args, timesteps, start=start, resamplings=resamplings, jump_length=jump_length, noise=noise,
-                                         seed=seed, group_ids=group_ids, use_graph=self.use_hip_graph)
-        out = self._finish_chain(h, run, [], 1)
-        return out[0], [out[1][..., r, :] for r in rows], phar_mask, [q['mask'] for q in pockets]
+        nph, given = self._given_rows(phar, ps, fix_coords, fix_types)
+        return self._run_chain('multi_edit_chain', ps, nph, timesteps, given=given,
+                               plan=dict(start=start, resamplings=resamplings, jump_length=jump_length), noise=noise, seed=seed, ids=group_ids)
 
     @torch.no_grad()
     def edit_restrained_given_pockets(self, phar, pockets, restraints, fix_coords=None, fix_types=None, start=None, resamplings=1,
@@ -627,30 +595,13 @@ class ConditionalDDPM(EnVariationalDiffusion):
         result is ``edit_given_pockets``' bit for bit; with one pocket it is ``edit_restrained``'s.
         Returns (xh_phar [Nu, 3+P], [xh_pocket_m], phar_mask, [pocket_mask_m], {'energy': [G], 'max_violation': [G]}): the energy and the
         largest violation (A) of the returned sample against all its pockets, held points included at their returned positions."""
-        from .. import restraints as rs
-        pockets, M, G = self._checked_pockets(pockets)
+        ps = self._pocket_groups(pockets, weights)
         timesteps, start = self._checked_start(timesteps, start)
-        nph = self._group_phar_sizes(phar, G)
-        w = self.group_weights(weights, G, M)
-        device = pockets[0]['x'].device
-        n_phar = int(nph.sum())
-        fix_x = self._row_mask(fix_coords, 'fix_coords', n_phar, device)
-        fix_h = self._row_mask(fix_types, 'fix_types', n_phar, device)
-        self._check_phar_rows(phar, n_phar)
-        rec = rs.records(restraints, nph, owner='group')                  # per group: 'sample' is the group index
-        clash_r, clash_k = rs.clash_pair(clash)
-        scale, max_shift, guide_below = rs.check_scalars(scale, rs.DEFAULT_MAX_SHIFT if max_shift is None else max_shift, guide_below)
-        sizes, rows, px, poh = self._member_layout(pockets, M, G)
-        h, phar_mask, noise, seed = self._prepare_edit(nph, (np.repeat(nph, M), sizes.reshape(-1)), device, timesteps, start, resamplings,
-                                                       jump_length, noise, seed, guide=True)
-        f32 = lambda t: t.detach().to(device, torch.float32).contiguous()
-        args = (px, poh, [M] * G, w.reshape(-1), f32(phar['x']), f32(phar['one_hot']), fix_x, fix_h)
-        run = lambda: h.multi_restrained_edit_chain(*args, timesteps, start=start, resamplings=resamplings, jump_length=jump_length,
-                                                    restraints=rec, clash_radius=clash_r, clash_k=clash_k, scale=scale, max_shift=max_shift,
-                                                    guide_below=guide_below, noise=noise, seed=seed, group_ids=group_ids,
-                                                    use_graph=self.use_hip_graph)
-        out, info = self._finish_restrained(h, run, [], 1)
-        return out[0], [out[1][..., r, :] for r in rows], phar_mask, [q['mask'] for q in pockets], info
+        nph, given = self._given_rows(phar, ps, fix_coords, fix_types)
+        rec, steer = self._guide_kw(restraints, nph, clash, scale, max_shift, guide_below, owner='group')  # per group: 'sample' is the group index
+        return self._run_chain('multi_restrained_edit_chain', ps, nph, timesteps, given=given,
+                               plan=dict(start=start, resamplings=resamplings, jump_length=jump_length), steer=dict(steer, restraints=rec),
+                               info=self.ENERGY_INFO, noise=noise, seed=seed, ids=group_ids)
 
     @torch.no_grad()
     def score(self, phar, pocket, timesteps=None, repeats=1, noise=None, seed=None, pocket_ids=None, return_levels=False):
@@ -672,47 +623,8 @@ class ConditionalDDPM(EnVariationalDiffusion):
         level_sums [R, timesteps + 1, B, 4], the raw sums of cmdgen_score_chain (error over all / the x columns, log p(h | z_0), reset flag).
         A level whose evaluation the NaN guard reset is reported (warning) and makes nll NaN for the whole batch: the reference
         resets batch-wide, and a reset is never summed in silently."""
-        from .. import scoring
-        K = self.T if timesteps is None else int(timesteps)
-        levels = scoring.level_list(self.T, K)                        # ValueError when K does not divide T
-        R = int(repeats)
-        if R < 1:
-            raise ValueError(f'repeats={repeats} must be >= 1')
-        device = pocket['x'].device
-        n_samples = len(pocket['size'])
-        sizes, nph = self._phar_pocket_sizes(phar, pocket)
-        f32 = lambda t: t.detach().to(device, torch.float32).contiguous()
-        noise = self._level_noise(noise, R, K, int(nph.sum()), device)
-        self.refresh_learned_schedule()
-        gamma = np.asarray(self.gamma_table_host(), dtype=np.float32)
-        log_pn = self.size_distribution._table(1, torch.device('cpu')).detach().to(torch.float32).numpy()
-        tab = scoring.level_table(gamma, self.T, self.n_dims, self.norm_values, levels)
-        h = self.dynamics.hip_handle()
-        h.set_layout(nph, sizes)
-        if seed is None:
-            seed = fresh_seed()
-        args = (f32(phar['x']), f32(phar['one_hot']), f32(pocket['x']), f32(pocket['one_hot']))
-        run = lambda: h.score_chain(*args, np.tile(levels, R), level_coef=scoring.level_coef(tab, R), noise=noise, seed=seed,
-                                    pocket_ids=pocket_ids, use_graph=self.use_hip_graph)
-        (terms, kl), st = h.run_range_guarded(run, h.chain_status)
-        self.last_chain_status = st
-        assert st['max_rel_com_error'] < 1e-2, f"Mean is not zero, relative_error {st['max_rel_com_error']}"
-        terms = terms.cpu().numpy().reshape(R, K + 1, n_samples, -1)
-        out = scoring.assemble(terms, kl.cpu().numpy(), gamma, log_pn, self.T, self.n_dims, self.norm_values, levels, nph, sizes)
-        reset = terms[..., scoring.SC_RESET].max(axis=2) > 0             # [R, K + 1]
-        if st['nan_resets'] or reset.any():
-            import warnings
-            bad = sorted({int(levels[k]) for k in np.nonzero(reset.any(axis=0))[0]})
-            warnings.warn(f'score: the NaN guard reset the network output at {int(reset.sum())} level evaluation(s) (t = {bad}): '
-                          'the reference resets the whole batch there, so nll is NaN for this batch', RuntimeWarning, stacklevel=2)
-            out['nll'] = np.full_like(out['nll'], np.nan)
-            out['nll_repeats'][reset.any(axis=1)] = np.nan
-        keep = ['nll', 'loss_t', 'loss_0_x', 'loss_0_h', 'neg_log_const_0', 'kl_prior', 'delta_log_px', 'log_pN']
-        keep += [k for k in out if k.endswith('_repeats')]
-        if return_levels:
-            out['level_sums'] = terms                                       # the raw sums (include/cmdgen_hip.h: CMDGEN_SC_COLS columns)
-            keep += ['t_levels', 'level_terms', 'level_sums']
-        return {k: torch.from_numpy(np.ascontiguousarray(out[k])).to(device) for k in keep}
+        return self._score_with('score', self._one_pocket(pocket, masks='batch masks'), phar, timesteps, repeats, noise, seed, pocket_ids,
+                                return_levels)
 
     @torch.no_grad()
     def score_given_pockets(self, phar, pockets, weights=None, timesteps=None, repeats=1, noise=None, seed=None, group_ids=None,
@@ -731,46 +643,49 @@ class ConditionalDDPM(EnVariationalDiffusion):
         return_members also member_nll, member_loss_t, member_loss_0_x, member_log_pN [G, M]: every pocket's own score on the SAME
         draws (what score gives for that pocket with the group's draws).  With return_levels also t_levels, level_terms
         [R, timesteps + 1, G], level_sums [R, timesteps + 1, G, 4] and, with return_members, member_level_sums [R, timesteps + 1, G, M, 4]."""
+        return self._score_with('score_given_pockets', self._pocket_groups(pockets, weights), phar, timesteps, repeats, noise, seed, group_ids,
+                                return_levels, return_members)
+
+    def _score_with(self, entry, ps, phar, timesteps, repeats, noise, seed, ids, return_levels, return_members=False):
+        """What score and score_given_pockets share: the level grid, the draws, the Handle's scoring chain on the pocket side ps, the
+        assembly of the terms and the NaN-reset report (entry: the name it is reported under)."""
         from .. import scoring
-        pockets, M, G = self._checked_pockets(pockets)
         K = self.T if timesteps is None else int(timesteps)
         levels = scoring.level_list(self.T, K)                        # ValueError when K does not divide T
         R = int(repeats)
         if R < 1:
             raise ValueError(f'repeats={repeats} must be >= 1')
-        nph = self._group_phar_sizes(phar, G)
-        w = self.group_weights(weights, G, M)
-        device = pockets[0]['x'].device
-        f32 = lambda t: t.detach().to(device, torch.float32).contiguous()
-        self._check_phar_rows(phar, int(nph.sum()))
-        noise = self._level_noise(noise, R, K, int(nph.sum()), device)
-        sizes, rows, px, poh = self._member_layout(pockets, M, G)
+        nph = self._given_sizes(phar, ps)
+        f32 = lambda t: t.detach().to(ps.device, torch.float32).contiguous()
+        noise = self._level_noise(noise, R, K, int(nph.sum()), ps.device)
         self.refresh_learned_schedule()
         gamma = np.asarray(self.gamma_table_host(), dtype=np.float32)
         log_pn = self.size_distribution._table(1, torch.device('cpu')).detach().to(torch.float32).numpy()
         tab = scoring.level_table(gamma, self.T, self.n_dims, self.norm_values, levels)
         h = self.dynamics.hip_handle()
-        h.set_layout(np.repeat(nph, M), sizes.reshape(-1))
+        h.set_layout(*ps.layout(nph))
         if seed is None:
             seed = fresh_seed()
-        args = (f32(phar['x']), f32(phar['one_hot']), px, poh, [M] * G, w.reshape(-1))
-        run = lambda: h.multi_score_chain(*args, np.tile(levels, R), level_coef=scoring.level_coef(tab, R), noise=noise, seed=seed,
-                                          group_ids=group_ids, want_members=return_members, use_graph=self.use_hip_graph)
-        (terms, members, kl), st = h.run_range_guarded(run, h.chain_status)
+        args = (f32(phar['x']), f32(phar['one_hot']), *ps.args)
+        kw = {'noise': noise, 'seed': seed, ps.ids: ids, 'use_graph': self.use_hip_graph, **({'want_members': return_members} if ps.grouped else {})}
+        run = lambda: getattr(h, 'multi_score_chain' if ps.grouped else 'score_chain')(*args, np.tile(levels, R),
+                                                                                        level_coef=scoring.level_coef(tab, R), **kw)
+        (terms, *members, kl), st = h.run_range_guarded(run, h.chain_status)
         self.last_chain_status = st
         assert st['max_rel_com_error'] < 1e-2, f"Mean is not zero, relative_error {st['max_rel_com_error']}"
-        terms = terms.cpu().numpy().reshape(R, K + 1, G, -1)
-        if members is not None:
-            members = members.cpu().numpy().reshape(R, K + 1, G, M, -1)
-        out = scoring.assemble_groups(terms, members, kl.cpu().numpy(), w, gamma, log_pn, self.T, self.n_dims, self.norm_values, levels,
-                                      nph, sizes)
+        terms = terms.cpu().numpy().reshape(R, K + 1, ps.n, -1)
+        shared = (gamma, log_pn, self.T, self.n_dims, self.norm_values, levels, nph, ps.sizes)
+        if ps.grouped:
+            members = members[0].cpu().numpy().reshape(R, K + 1, ps.n, ps.M, -1) if members[0] is not None else None
+            out = scoring.assemble_groups(terms, members, kl.cpu().numpy(), ps.w, *shared)
+        else:
+            members, out = None, scoring.assemble(terms, kl.cpu().numpy(), *shared)
         reset = terms[..., scoring.SC_RESET].max(axis=2) > 0             # [R, K + 1]
         if st['nan_resets'] or reset.any():
             import warnings
             bad = sorted({int(levels[k]) for k in np.nonzero(reset.any(axis=0))[0]})
-            warnings.warn(f'score_given_pockets: the NaN guard reset the network output at {int(reset.sum())} level evaluation(s) '
-                          f'(t = {bad}): the reference resets the whole batch there, so nll is NaN for this batch', RuntimeWarning,
-                          stacklevel=2)
+            warnings.warn(f'{entry}: the NaN guard reset the network output at {int(reset.sum())} level evaluation(s) (t = {bad}): '
+                          'the reference resets the whole batch there, so nll is NaN for this batch', RuntimeWarning, stacklevel=3)
             out['nll'] = np.full_like(out['nll'], np.nan)
             out['nll_repeats'][reset.any(axis=1)] = np.nan
             if members is not None:
@@ -785,7 +700,7 @@ class ConditionalDDPM(EnVariationalDiffusion):
             if return_members:
                 out['member_level_sums'] = members
                 keep += ['member_level_sums']
-        return {k: torch.from_numpy(np.ascontiguousarray(out[k])).to(device) for k in keep}
+        return {k: torch.from_numpy(np.ascontiguousarray(out[k])).to(ps.device) for k in keep}
 
     def _chain_frame(self, h, z_steps, step, xh_phar, xh_pocket):
         """The frame of the state after op `step`: unnormalize_z (:897-906) of z and of the pocket the op left; the

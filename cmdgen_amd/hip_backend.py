@@ -412,17 +412,8 @@ class Handle:
     def sample_chain(self, pocket_x, pocket_onehot, timesteps: int, noise=None, seed: int = 0,
                      pocket_ids: Optional[Sequence[int]] = None, want_steps: bool = False,
                      use_graph: bool = True):
-        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
-        self._check_dev(pocket_x, (self.n_pocket, 3))
-        self._check_dev(pocket_onehot, (self.n_pocket, R))
-        if noise is not None:
-            self._check_dev(noise, (timesteps + 2, self.n_phar, 3 + P))
-        xh_phar, xh_pocket, z_steps, p_steps = self._chain_outputs(self.n_phar, timesteps, want_steps, pocket_x.device)
-        self._check(self.lib.cmdgen_sample_chain(
-            self.h, _ptr(pocket_x), _ptr(pocket_onehot), int(timesteps), _ptr(noise), self._seed(seed),
-            self._pocket_ids(pocket_ids), _ptr(xh_phar), _ptr(xh_pocket),
-            _ptr(z_steps), _ptr(p_steps), int(bool(use_graph)), self._stream()), 'cmdgen_sample_chain')
-        return xh_phar, xh_pocket, z_steps
+        return self._sampling_chain(pocket_x, pocket_onehot, timesteps,
+                                    noise=noise, seed=seed, ids=pocket_ids, want_steps=want_steps, use_graph=use_graph)
 
     def set_guide_table(self, K: int, sigma_alpha: 'np.ndarray'):
         a = np.ascontiguousarray(sigma_alpha, dtype=np.float32)
@@ -435,23 +426,8 @@ class Handle:
         """cmdgen_restrained_chain: sample_chain with a guidance term from geometric restraints in every posterior op (the header of
         kernels_restrain.hip defines it).  restraints: a RESTRAINT_DTYPE array (restraint_records) or None.
         -> (xh_phar, xh_pocket, z_steps, energy [B, 2] (E and the largest violation in A of the output), op_energy [K, B] or None)."""
-        import torch
-        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
-        dev = pocket_x.device
-        self._check_dev(pocket_x, (self.n_pocket, 3))
-        self._check_dev(pocket_onehot, (self.n_pocket, R))
-        if noise is not None:
-            self._check_dev(noise, (timesteps + 2, self.n_phar, 3 + P))
-        rec, n_rec = self._restraint_arg(restraints)
-        xh_phar, xh_pocket, z_steps, p_steps = self._chain_outputs(self.n_phar, timesteps, want_steps, dev)
-        energy = torch.empty((self.batch, 2), dtype=torch.float32, device=dev)
-        op_energy = torch.empty((timesteps, self.batch), dtype=torch.float32, device=dev) if want_steps else None
-        self._check(self.lib.cmdgen_restrained_chain(
-            self.h, _ptr(pocket_x), _ptr(pocket_onehot), int(timesteps), rec, n_rec,
-            float(clash_radius), float(clash_k), float(scale), float(max_shift), float(guide_below),
-            _ptr(noise), self._seed(seed), self._pocket_ids(pocket_ids), _ptr(xh_phar), _ptr(xh_pocket),
-            _ptr(z_steps), _ptr(p_steps), _ptr(energy), _ptr(op_energy), int(bool(use_graph)), self._stream()), 'cmdgen_restrained_chain')
-        return xh_phar, xh_pocket, z_steps, energy, op_energy
+        return self._sampling_chain(pocket_x, pocket_onehot, timesteps, guide=(restraints, clash_radius, clash_k, scale, max_shift, guide_below),
+                                    noise=noise, seed=seed, ids=pocket_ids, want_steps=want_steps, use_graph=use_graph)
 
     MAX_SET_ROWS = 8192              # include/cmdgen_hip.h: CMDGEN_MAX_SET_ROWS
 
@@ -462,23 +438,8 @@ class Handle:
         kernels_diverse.hip defines it).  set_sizes: the layout's samples partitioned into sets of consecutive samples, "the draws for one
         pocket"; strength (dimensionless), width (A), max_shift (A per op and point), guide_below as restrained_chain's.
         -> (xh_phar, xh_pocket, z_steps, overlap [B] of the output, op_overlap [K, B] or None)."""
-        import torch
-        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
-        dev = pocket_x.device
-        self._check_dev(pocket_x, (self.n_pocket, 3))
-        self._check_dev(pocket_onehot, (self.n_pocket, R))
-        if noise is not None:
-            self._check_dev(noise, (timesteps + 2, self.n_phar, 3 + P))
-        sizes = np.ascontiguousarray(np.asarray(set_sizes, dtype=np.int64).reshape(-1))
-        xh_phar, xh_pocket, z_steps, p_steps = self._chain_outputs(self.n_phar, timesteps, want_steps, dev)
-        overlap = torch.empty((self.batch,), dtype=torch.float32, device=dev)
-        op_overlap = torch.empty((timesteps, self.batch), dtype=torch.float32, device=dev) if want_steps else None
-        self._check(self.lib.cmdgen_diverse_chain(
-            self.h, _ptr(pocket_x), _ptr(pocket_onehot), int(timesteps), len(sizes), sizes.ctypes.data_as(_i64p),
-            float(strength), float(width), float(max_shift), float(guide_below),
-            _ptr(noise), self._seed(seed), self._pocket_ids(pocket_ids), _ptr(xh_phar), _ptr(xh_pocket),
-            _ptr(z_steps), _ptr(p_steps), _ptr(overlap), _ptr(op_overlap), int(bool(use_graph)), self._stream()), 'cmdgen_diverse_chain')
-        return xh_phar, xh_pocket, z_steps, overlap, op_overlap
+        return self._sampling_chain(pocket_x, pocket_onehot, timesteps, sets=(set_sizes, strength, width, max_shift, guide_below),
+                                    noise=noise, seed=seed, ids=pocket_ids, want_steps=want_steps, use_graph=use_graph)
 
     MAX_GROUP = 8                    # include/cmdgen_hip.h: CMDGEN_MAX_GROUP
 
@@ -489,18 +450,8 @@ class Handle:
         group's summing to 1).  noise [K+2, Nu, 3+P] or None, Nu = one copy of the phar rows per group; group_ids: the global group ids
         of the Philox draws (None: 0 .. groups - 1).  -> (xh_phar [Nu, 3+P], xh_pocket [Np, 3+R], z_steps [K, Nu, 3+P] or None) like
         sample_chain; with want_steps every member's pocket after every op is left in last_pocket_steps."""
-        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
-        self._check_dev(pocket_x, (self.n_pocket, 3))
-        self._check_dev(pocket_onehot, (self.n_pocket, R))
-        sizes, w, ids, n_unique = self._group_args(group_sizes, weights, group_ids)
-        if noise is not None:
-            self._check_dev(noise, (timesteps + 2, n_unique, 3 + P))
-        xh_phar, xh_pocket, z_steps, p_steps = self._chain_outputs(n_unique, timesteps, want_steps, pocket_x.device)
-        self._check(self.lib.cmdgen_multi_pocket_chain(
-            self.h, _ptr(pocket_x), _ptr(pocket_onehot), len(sizes), sizes.ctypes.data_as(_i64p), w.ctypes.data_as(C.c_void_p),
-            int(timesteps), _ptr(noise), self._seed(seed), ids, _ptr(xh_phar), _ptr(xh_pocket),
-            _ptr(z_steps), _ptr(p_steps), int(bool(use_graph)), self._stream()), 'cmdgen_multi_pocket_chain')
-        return xh_phar, xh_pocket, z_steps
+        return self._sampling_chain(pocket_x, pocket_onehot, timesteps, groups=(group_sizes, weights),
+                                    noise=noise, seed=seed, ids=group_ids, want_steps=want_steps, use_graph=use_graph)
 
     def multi_restrained_chain(self, pocket_x, pocket_onehot, group_sizes: Sequence[int], weights, timesteps: int, restraints=None,
                                clash_radius: float = 0.0, clash_k: float = 0.0, scale: float = 1.0, max_shift: float = DEFAULT_MAX_SHIFT,
@@ -510,24 +461,9 @@ class Handle:
         header of kernels_restrain.hip defines it).  The layout, group_sizes, weights, noise and group_ids of multi_pocket_chain; restraints: a
         RESTRAINT_DTYPE array whose 'sample' is the GROUP index, or None; the scalars of restrained_chain.
         -> (xh_phar [Nu, 3+P], xh_pocket, z_steps, energy [G, 2] (E and the largest violation in A of the output), op_energy [K, G] or None)."""
-        import torch
-        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
-        dev = pocket_x.device
-        self._check_dev(pocket_x, (self.n_pocket, 3))
-        self._check_dev(pocket_onehot, (self.n_pocket, R))
-        sizes, w, ids, n_unique = self._group_args(group_sizes, weights, group_ids)
-        if noise is not None:
-            self._check_dev(noise, (timesteps + 2, n_unique, 3 + P))
-        rec, n_rec = self._restraint_arg(restraints)
-        xh_phar, xh_pocket, z_steps, p_steps = self._chain_outputs(n_unique, timesteps, want_steps, dev)
-        energy = torch.empty((len(sizes), 2), dtype=torch.float32, device=dev)
-        op_energy = torch.empty((timesteps, len(sizes)), dtype=torch.float32, device=dev) if want_steps else None
-        self._check(self.lib.cmdgen_multi_restrained_chain(
-            self.h, _ptr(pocket_x), _ptr(pocket_onehot), len(sizes), sizes.ctypes.data_as(_i64p), w.ctypes.data_as(C.c_void_p),
-            int(timesteps), rec, n_rec, float(clash_radius), float(clash_k), float(scale), float(max_shift), float(guide_below),
-            _ptr(noise), self._seed(seed), ids, _ptr(xh_phar), _ptr(xh_pocket), _ptr(z_steps), _ptr(p_steps), _ptr(energy),
-            _ptr(op_energy), int(bool(use_graph)), self._stream()), 'cmdgen_multi_restrained_chain')
-        return xh_phar, xh_pocket, z_steps, energy, op_energy
+        return self._sampling_chain(pocket_x, pocket_onehot, timesteps, groups=(group_sizes, weights),
+                                    guide=(restraints, clash_radius, clash_k, scale, max_shift, guide_below),
+                                    noise=noise, seed=seed, ids=group_ids, want_steps=want_steps, use_graph=use_graph)
 
     def joint_plan(self, timesteps: int, resamplings: int = 1, jump_length: int = 1, inpaint: bool = True):
         """(denoising steps, combined noise draws) of a joint chain."""
@@ -592,12 +528,96 @@ class Handle:
                                               C.byref(b)), 'cmdgen_edit_plan')
         return a.value, b.value
 
-    def _check_edit_inputs(self, pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h, rows: int):
-        """the edit kinds' device inputs: the pocket, then `rows` given phar rows with their two masks"""
+    # the C entry of a sampling chain, by the parts present: (groups, 'guide' / 'sets' / None, given)
+    _CHAIN_ENTRY = {(False, None, False): 'sample_chain', (False, 'guide', False): 'restrained_chain', (False, 'sets', False): 'diverse_chain',
+                    (True, None, False): 'multi_pocket_chain', (True, 'guide', False): 'multi_restrained_chain',
+                    (False, None, True): 'edit_chain', (False, 'guide', True): 'restrained_edit_chain',
+                    (True, None, True): 'multi_edit_chain', (True, 'guide', True): 'multi_restrained_edit_chain'}
+
+    def _sampling_chain(self, pocket_x, pocket_onehot, timesteps, *, groups=None, given=None, plan=None, guide=None, sets=None,
+                        noise, seed, ids, want_steps, use_graph):
+        """What the public sampling *_chain methods share; the C entry follows from the parts passed (the part names of
+        tests/chain_kit.run_chain).  groups: (group_sizes, weights) - the multi kinds, ids are then the group ids; given: (phar_x,
+        phar_onehot, fix_x, fix_h) with plan: (start, resamplings, jump_length) - the edit kinds; guide: (restraints, clash_radius, clash_k,
+        scale, max_shift, guide_below) - the restrained kinds, with energy [owners, 2] and op_energy [steps, owners] behind the three
+        outputs (an owner is a sample, or a group); sets: (set_sizes, strength, width, max_shift, guide_below) - the diverse chain, with
+        overlap [B] and op_overlap [K, B].  -> (xh_phar, xh_pocket, z_steps) and the side outputs of guide or sets."""
+        import torch
         P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
-        shapes = [(self.n_pocket, 3), (self.n_pocket, R), (rows, 3), (rows, P), (rows,), (rows,)]
-        for t, sh in zip((pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h), shapes):
+        steer = 'guide' if guide is not None else 'sets' if sets is not None else None
+        key = (groups is not None, steer, given is not None)
+        if key not in self._CHAIN_ENTRY or (guide is not None and sets is not None):
+            raise CmdgenError(f'no chain entry for groups, steering, given = {key}')
+        name = 'cmdgen_' + self._CHAIN_ENTRY[key]
+        rows, owners, group_seg = self.n_phar, self.batch, []
+        if groups is not None:
+            sizes, w, ids, rows = self._group_args(*groups, ids)
+            owners, group_seg = len(sizes), [len(sizes), sizes.ctypes.data_as(_i64p), w.ctypes.data_as(C.c_void_p)]
+        else:
+            ids = self._pocket_ids(ids)
+        self._check_dev(pocket_x, (self.n_pocket, 3))
+        self._check_dev(pocket_onehot, (self.n_pocket, R))
+        if given is None:                                   # from the prior: one draw per op, the initial state and the decode
+            steps, given_seg, sched = timesteps, [], [int(timesteps)]
+            if noise is not None:
+                self._check_dev(noise, (timesteps + 2, rows, 3 + P))
+            noise_seg = [_ptr(noise)]
+        else:                                               # `rows` given phar rows with their two masks; the plan sets the ops and draws
+            for t, sh in zip(given, [(rows, 3), (rows, P), (rows,), (rows,)]):
+                self._check_dev(t, sh)
+            start, resamplings, jump_length = plan
+            start = timesteps if start is None else start
+            steps, n_draws = self.edit_plan(timesteps, start, resamplings, jump_length)
+            self._check_draws(noise, rows)
+            given_seg, sched = [_ptr(t) for t in given], [int(timesteps), int(start), int(resamplings), int(jump_length)]
+            noise_seg = [*self._noise_arg(noise)]
+        steer_seg, side = [], ()
+        if guide is not None:
+            rec, n_rec = self._restraint_arg(guide[0])
+            steer_seg = [rec, n_rec, *[float(v) for v in guide[1:]]]
+        elif sets is not None:
+            set_sizes = np.ascontiguousarray(np.asarray(sets[0], dtype=np.int64).reshape(-1))
+            steer_seg = [len(set_sizes), set_sizes.ctypes.data_as(_i64p), *[float(v) for v in sets[1:]]]
+        dev = pocket_x.device
+        outs = self._chain_outputs(rows, steps, want_steps, dev)
+        if steer is not None:                               # per owner: (E, largest violation) of a guided chain, the overlap of a diverse one
+            side = (torch.empty((owners, 2) if guide is not None else (owners,), dtype=torch.float32, device=dev),
+                    torch.empty((steps, owners), dtype=torch.float32, device=dev) if want_steps else None)
+        # every entry's own order: the steering scalars sit before the noise in the from-prior entries, behind the four outputs in the edit ones
+        args = [_ptr(pocket_x), _ptr(pocket_onehot), *group_seg, *given_seg, *sched, *([] if given is not None else steer_seg), *noise_seg,
+                self._seed(seed), ids, *[_ptr(t) for t in outs], *(steer_seg if given is not None else []), *[_ptr(t) for t in side]]
+        self._check(getattr(self.lib, name)(self.h, *args, int(bool(use_graph)), self._stream()), name)
+        return (*outs[:3], *side)
+
+    def _scoring_chain(self, phar_x, phar_onehot, pocket_x, pocket_onehot, t_levels, level_coef, *, groups=None, noise, seed, ids,
+                       want_members=False, use_graph):
+        """What score_chain and multi_score_chain (groups: (group_sizes, weights); ids are then the group ids) share.
+        -> (terms [n_levels, owners, SC_COLS], kl_sums [owners, 2]), with groups member_terms between the two."""
+        import torch
+        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
+        rows, owners, group_seg, members = self.n_phar, self.batch, [], ()
+        if groups is not None:
+            sizes, w, ids, rows = self._group_args(*groups, ids)
+            owners, group_seg = len(sizes), [len(sizes), sizes.ctypes.data_as(_i64p), w.ctypes.data_as(C.c_void_p)]
+        else:
+            ids = self._pocket_ids(ids)
+        for t, sh in zip((phar_x, phar_onehot, pocket_x, pocket_onehot), [(rows, 3), (rows, P), (self.n_pocket, 3), (self.n_pocket, R)]):
             self._check_dev(t, sh)
+        lv, coef = self._level_args(t_levels, level_coef)
+        n = len(lv)
+        if noise is not None:
+            self._check_dev(noise, (n, rows, 3 + P))
+        dev = phar_x.device
+        terms = torch.zeros((n, owners, self.SC_COLS), dtype=torch.float32, device=dev)
+        if groups is not None:
+            members = (torch.zeros((n, self.batch, self.SC_COLS), dtype=torch.float32, device=dev) if want_members else None,)
+        kl = torch.zeros((owners, 2), dtype=torch.float32, device=dev)
+        name = 'cmdgen_multi_score_chain' if groups is not None else 'cmdgen_score_chain'
+        self._check(getattr(self.lib, name)(
+            self.h, _ptr(phar_x), _ptr(phar_onehot), _ptr(pocket_x), _ptr(pocket_onehot), *group_seg, n, lv.ctypes.data_as(C.c_void_p),
+            coef.ctypes.data_as(C.c_void_p) if coef is not None else None, _ptr(noise), self._seed(seed), ids, _ptr(terms),
+            *[_ptr(t) for t in members], _ptr(kl), int(bool(use_graph)), self._stream()), name)
+        return (terms, *members, kl)
 
     def edit_chain(self, pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h, timesteps: int, start: Optional[int] = None,
                    resamplings: int = 1, jump_length: int = 1, noise=None, seed: int = 0, pocket_ids: Optional[Sequence[int]] = None,
@@ -605,16 +625,9 @@ class Handle:
         """ConditionalDDPM.edit on the device (cmdgen_edit_chain): inpaint_chain with a mask for the x columns (fix_x) and one for the
         feature columns (fix_h), float [Nl] device tensors, and the level the chain starts from (None: timesteps, the prior).
         -> (xh_phar, xh_pocket, z_steps); with want_steps the pocket after every op is left in last_pocket_steps."""
-        start = timesteps if start is None else start
-        self._check_edit_inputs(pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h, self.n_phar)
-        n_steps, n_draws = self.edit_plan(timesteps, start, resamplings, jump_length)
-        self._check_draws(noise, self.n_phar)
-        xh_phar, xh_pocket, z_steps, p_steps = self._chain_outputs(self.n_phar, n_steps, want_steps, pocket_x.device)
-        self._check(self.lib.cmdgen_edit_chain(
-            self.h, _ptr(pocket_x), _ptr(pocket_onehot), _ptr(phar_x), _ptr(phar_onehot), _ptr(fix_x), _ptr(fix_h), int(timesteps),
-            int(start), int(resamplings), int(jump_length), *self._noise_arg(noise), self._seed(seed), self._pocket_ids(pocket_ids),
-            _ptr(xh_phar), _ptr(xh_pocket), _ptr(z_steps), _ptr(p_steps), int(bool(use_graph)), self._stream()), 'cmdgen_edit_chain')
-        return xh_phar, xh_pocket, z_steps
+        return self._sampling_chain(pocket_x, pocket_onehot, timesteps,
+                                    given=(phar_x, phar_onehot, fix_x, fix_h), plan=(start, resamplings, jump_length),
+                                    noise=noise, seed=seed, ids=pocket_ids, want_steps=want_steps, use_graph=use_graph)
 
     def restrained_edit_chain(self, pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h, timesteps: int, start: Optional[int] = None,
                               resamplings: int = 1, jump_length: int = 1, restraints=None, clash_radius: float = 0.0, clash_k: float = 0.0,
@@ -625,23 +638,10 @@ class Handle:
         and is not displaced.  The arguments are edit_chain's, then restrained_chain's.
         -> (xh_phar, xh_pocket, z_steps, energy [B, 2] (E and the largest violation in A of the output), op_energy [n_steps, B] or None);
         with want_steps the pocket after every op is left in last_pocket_steps."""
-        import torch
-        start = timesteps if start is None else start
-        self._check_edit_inputs(pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h, self.n_phar)
-        n_steps, n_draws = self.edit_plan(timesteps, start, resamplings, jump_length)
-        self._check_draws(noise, self.n_phar)
-        rec, n_rec = self._restraint_arg(restraints)
-        dev = pocket_x.device
-        xh_phar, xh_pocket, z_steps, p_steps = self._chain_outputs(self.n_phar, n_steps, want_steps, dev)
-        energy = torch.empty((self.batch, 2), dtype=torch.float32, device=dev)
-        op_energy = torch.empty((n_steps, self.batch), dtype=torch.float32, device=dev) if want_steps else None
-        self._check(self.lib.cmdgen_restrained_edit_chain(
-            self.h, _ptr(pocket_x), _ptr(pocket_onehot), _ptr(phar_x), _ptr(phar_onehot), _ptr(fix_x), _ptr(fix_h), int(timesteps),
-            int(start), int(resamplings), int(jump_length), *self._noise_arg(noise), self._seed(seed), self._pocket_ids(pocket_ids),
-            _ptr(xh_phar), _ptr(xh_pocket), _ptr(z_steps), _ptr(p_steps), rec, n_rec, float(clash_radius), float(clash_k), float(scale),
-            float(max_shift), float(guide_below), _ptr(energy), _ptr(op_energy), int(bool(use_graph)), self._stream()),
-            'cmdgen_restrained_edit_chain')
-        return xh_phar, xh_pocket, z_steps, energy, op_energy
+        return self._sampling_chain(pocket_x, pocket_onehot, timesteps,
+                                    given=(phar_x, phar_onehot, fix_x, fix_h), plan=(start, resamplings, jump_length),
+                                    guide=(restraints, clash_radius, clash_k, scale, max_shift, guide_below),
+                                    noise=noise, seed=seed, ids=pocket_ids, want_steps=want_steps, use_graph=use_graph)
 
     def multi_edit_chain(self, pocket_x, pocket_onehot, group_sizes: Sequence[int], weights, phar_x, phar_onehot, fix_x, fix_h,
                          timesteps: int, start: Optional[int] = None, resamplings: int = 1, jump_length: int = 1, noise=None,
@@ -651,18 +651,9 @@ class Handle:
         of the rows per group), in the pockets' common frame; start, resamplings, jump_length as edit_chain; noise [n_draws, Nu, 3+P]
         (edit_plan) or None.  -> (xh_phar [Nu, 3+P], xh_pocket [Np, 3+R], z_steps [n_steps, Nu, 3+P] or None); with want_steps every
         member's pocket after every op is left in last_pocket_steps."""
-        start = timesteps if start is None else start
-        sizes, w, ids, n_unique = self._group_args(group_sizes, weights, group_ids)
-        self._check_edit_inputs(pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h, n_unique)
-        n_steps, n_draws = self.edit_plan(timesteps, start, resamplings, jump_length)
-        self._check_draws(noise, n_unique)
-        xh_phar, xh_pocket, z_steps, p_steps = self._chain_outputs(n_unique, n_steps, want_steps, pocket_x.device)
-        self._check(self.lib.cmdgen_multi_edit_chain(
-            self.h, _ptr(pocket_x), _ptr(pocket_onehot), len(sizes), sizes.ctypes.data_as(_i64p), w.ctypes.data_as(C.c_void_p),
-            _ptr(phar_x), _ptr(phar_onehot), _ptr(fix_x), _ptr(fix_h), int(timesteps), int(start), int(resamplings), int(jump_length),
-            *self._noise_arg(noise), self._seed(seed), ids, _ptr(xh_phar),
-            _ptr(xh_pocket), _ptr(z_steps), _ptr(p_steps), int(bool(use_graph)), self._stream()), 'cmdgen_multi_edit_chain')
-        return xh_phar, xh_pocket, z_steps
+        return self._sampling_chain(pocket_x, pocket_onehot, timesteps, groups=(group_sizes, weights),
+                                    given=(phar_x, phar_onehot, fix_x, fix_h), plan=(start, resamplings, jump_length),
+                                    noise=noise, seed=seed, ids=group_ids, want_steps=want_steps, use_graph=use_graph)
 
     def multi_restrained_edit_chain(self, pocket_x, pocket_onehot, group_sizes: Sequence[int], weights, phar_x, phar_onehot, fix_x, fix_h,
                                     timesteps: int, start: Optional[int] = None, resamplings: int = 1, jump_length: int = 1, restraints=None,
@@ -675,24 +666,10 @@ class Handle:
         RESTRAINT_DTYPE array whose 'sample' is the GROUP index, or None).
         -> (xh_phar [Nu, 3+P], xh_pocket, z_steps, energy [G, 2] (E and the largest violation in A of the output), op_energy [n_steps, G] or
         None); with want_steps every member's pocket after every op is left in last_pocket_steps."""
-        import torch
-        start = timesteps if start is None else start
-        sizes, w, ids, n_unique = self._group_args(group_sizes, weights, group_ids)
-        self._check_edit_inputs(pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h, n_unique)
-        n_steps, n_draws = self.edit_plan(timesteps, start, resamplings, jump_length)
-        self._check_draws(noise, n_unique)
-        rec, n_rec = self._restraint_arg(restraints)
-        dev = pocket_x.device
-        xh_phar, xh_pocket, z_steps, p_steps = self._chain_outputs(n_unique, n_steps, want_steps, dev)
-        energy = torch.empty((len(sizes), 2), dtype=torch.float32, device=dev)
-        op_energy = torch.empty((n_steps, len(sizes)), dtype=torch.float32, device=dev) if want_steps else None
-        self._check(self.lib.cmdgen_multi_restrained_edit_chain(
-            self.h, _ptr(pocket_x), _ptr(pocket_onehot), len(sizes), sizes.ctypes.data_as(_i64p), w.ctypes.data_as(C.c_void_p),
-            _ptr(phar_x), _ptr(phar_onehot), _ptr(fix_x), _ptr(fix_h), int(timesteps), int(start), int(resamplings), int(jump_length),
-            *self._noise_arg(noise), self._seed(seed), ids, _ptr(xh_phar), _ptr(xh_pocket), _ptr(z_steps), _ptr(p_steps), rec, n_rec,
-            float(clash_radius), float(clash_k), float(scale), float(max_shift), float(guide_below), _ptr(energy), _ptr(op_energy),
-            int(bool(use_graph)), self._stream()), 'cmdgen_multi_restrained_edit_chain')
-        return xh_phar, xh_pocket, z_steps, energy, op_energy
+        return self._sampling_chain(pocket_x, pocket_onehot, timesteps, groups=(group_sizes, weights),
+                                    given=(phar_x, phar_onehot, fix_x, fix_h), plan=(start, resamplings, jump_length),
+                                    guide=(restraints, clash_radius, clash_k, scale, max_shift, guide_below),
+                                    noise=noise, seed=seed, ids=group_ids, want_steps=want_steps, use_graph=use_graph)
 
     SC_COLS = 4                      # include/cmdgen_hip.h: CMDGEN_SC_COLS
 
@@ -702,23 +679,8 @@ class Handle:
         [Nl,3], phar_onehot [Nl,P], pocket_x [Np,3], pocket_onehot [Np,R] device tensors; level_coef host [len(t_levels) + 1, 2] (alpha,
         sigma per level, then of t = T) or None; noise [len(t_levels), Nl, 3+P] or None (Philox draws, draw counter = index of the level).
         -> (level_terms [n_levels, batch, SC_COLS], kl_sums [batch, 2]): raw sums, columns as in include/cmdgen_hip.h."""
-        import torch
-        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
-        shapes = [(self.n_phar, 3), (self.n_phar, P), (self.n_pocket, 3), (self.n_pocket, R)]
-        for t, sh in zip((phar_x, phar_onehot, pocket_x, pocket_onehot), shapes):
-            self._check_dev(t, sh)
-        lv, coef = self._level_args(t_levels, level_coef)
-        n = len(lv)
-        if noise is not None:
-            self._check_dev(noise, (n, self.n_phar, 3 + P))
-        dev = phar_x.device
-        terms = torch.zeros((n, self.batch, self.SC_COLS), dtype=torch.float32, device=dev)
-        kl = torch.zeros((self.batch, 2), dtype=torch.float32, device=dev)
-        self._check(self.lib.cmdgen_score_chain(
-            self.h, _ptr(phar_x), _ptr(phar_onehot), _ptr(pocket_x), _ptr(pocket_onehot), n, lv.ctypes.data_as(C.c_void_p),
-            coef.ctypes.data_as(C.c_void_p) if coef is not None else None, _ptr(noise), self._seed(seed),
-            self._pocket_ids(pocket_ids), _ptr(terms), _ptr(kl), int(bool(use_graph)), self._stream()), 'cmdgen_score_chain')
-        return terms, kl
+        return self._scoring_chain(phar_x, phar_onehot, pocket_x, pocket_onehot, t_levels, level_coef, noise=noise, seed=seed, ids=pocket_ids,
+                                   use_graph=use_graph)
 
     def multi_score_chain(self, phar_x, phar_onehot, pocket_x, pocket_onehot, group_sizes: Sequence[int], weights, t_levels,
                           level_coef=None, noise=None, seed: int = 0, group_ids: Optional[Sequence[int]] = None,
@@ -727,26 +689,8 @@ class Handle:
         multi_pocket_chain; phar_x [Nu,3], phar_onehot [Nu,P] one row per unique phar row (Nu = one copy of the rows per group), in the
         pockets' common frame; t_levels and level_coef as score_chain; noise [n_levels, Nu, 3+P] or None (one draw per group and level).
         -> (group_terms [n_levels, groups, SC_COLS], member_terms [n_levels, batch, SC_COLS] or None, kl_sums [groups, 2])."""
-        import torch
-        P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
-        sizes, w, ids, n_unique = self._group_args(group_sizes, weights, group_ids)
-        shapes = [(n_unique, 3), (n_unique, P), (self.n_pocket, 3), (self.n_pocket, R)]
-        for t, sh in zip((phar_x, phar_onehot, pocket_x, pocket_onehot), shapes):
-            self._check_dev(t, sh)
-        lv, coef = self._level_args(t_levels, level_coef)
-        n = len(lv)
-        if noise is not None:
-            self._check_dev(noise, (n, n_unique, 3 + P))
-        dev = phar_x.device
-        terms = torch.zeros((n, len(sizes), self.SC_COLS), dtype=torch.float32, device=dev)
-        members = torch.zeros((n, self.batch, self.SC_COLS), dtype=torch.float32, device=dev) if want_members else None
-        kl = torch.zeros((len(sizes), 2), dtype=torch.float32, device=dev)
-        self._check(self.lib.cmdgen_multi_score_chain(
-            self.h, _ptr(phar_x), _ptr(phar_onehot), _ptr(pocket_x), _ptr(pocket_onehot), len(sizes), sizes.ctypes.data_as(_i64p),
-            w.ctypes.data_as(C.c_void_p), n, lv.ctypes.data_as(C.c_void_p), coef.ctypes.data_as(C.c_void_p) if coef is not None else None,
-            _ptr(noise), self._seed(seed), ids, _ptr(terms), _ptr(members), _ptr(kl), int(bool(use_graph)),
-            self._stream()), 'cmdgen_multi_score_chain')
-        return terms, members, kl
+        return self._scoring_chain(phar_x, phar_onehot, pocket_x, pocket_onehot, t_levels, level_coef, groups=(group_sizes, weights),
+                                   noise=noise, seed=seed, ids=group_ids, want_members=want_members, use_graph=use_graph)
 
     # ---- training step (flat parameter / gradient buffers are torch tensors owned by the caller)
     def param_count(self) -> int:

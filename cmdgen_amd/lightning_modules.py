@@ -293,6 +293,81 @@ class PharPocketDDPM(nn.Module):
                   'size': pocket_size, 'mask': pocket_mask}
         return pocket
 
+    # ---- the parts the PDB-level entries below are composed of
+    def _pocket_request(self, caller, pdb_files, pocket_ids, ref_ligands, many=False):
+        """The pocket(s) an entry names, checked before any file is read: one PDB file with pocket_ids or ref_ligand, or (many) a list of
+        files with one entry of either per file.  caller: the entry's name for the refusal of another model than the conditional one
+        (None: the entry runs on any model, or refuses on its own).  -> load(n_samples): the pocket batch dicts, one per file."""
+        assert (pocket_ids is None) ^ (ref_ligands is None)
+        if many:
+            pdb_files = list(pdb_files)
+            if len(pocket_ids if pocket_ids is not None else ref_ligands) != len(pdb_files):
+                raise ValueError(f'{len(pdb_files)} pdb_files need {len(pdb_files)} entries of pocket_ids or ref_ligands (one per file)')
+        else:
+            pdb_files, pocket_ids, ref_ligands = [pdb_files], [pocket_ids], [ref_ligands]
+        if caller is not None and not isinstance(self.ddpm, ConditionalDDPM):
+            raise NotImplementedError(f'{caller} needs the conditional model (mode pocket_conditioning)')
+        return lambda n_samples: [self._pdb_pocket(f, n_samples, pocket_ids[m] if pocket_ids is not None else None,
+                                                   ref_ligands[m] if ref_ligands is not None else None) for m, f in enumerate(pdb_files)]
+
+    def _num_nodes(self, num_nodes_phar, pocket, n_samples, at_least=0):
+        """Points per sample: by default the size prior given `pocket` (the first one of several), raised to at_least; a given scalar holds
+        for every sample.  -> INT_TYPE [n_samples] on the device."""
+        if num_nodes_phar is None:
+            num_nodes_phar = self.ddpm.size_distribution.sample_conditional(n1=None, n2=pocket['size'])
+            num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device).clamp(min=at_least)
+        else:
+            num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device).reshape(-1)
+            if num_nodes_phar.numel() == 1:
+                num_nodes_phar = num_nodes_phar.expand(n_samples)
+        return num_nodes_phar.to(INT_TYPE)
+
+    @staticmethod
+    def _restraints_for_all(restraints):
+        """Restraints given ONCE, without 'sample', and applied to every sample.  -> (the rows they name: a lower bound of num_nodes_phar,
+        per_sample(num_nodes_phar, n_samples): the checked list for the sampler, every dict once per sample)."""
+        from . import restraints as rs
+        restraints = list(restraints)
+        for n, r in enumerate(restraints):
+            if isinstance(r, dict) and 'sample' in r:
+                raise ValueError(f"restraints[{n}] = {r!r}: restraints are given once, without 'sample', and applied to every sample")
+        named = [int(v) for r in restraints if isinstance(r, dict)
+                 for v in ([r['point']] if 'point' in r else list(r.get('points', ()))) if isinstance(v, (int, np.integer))]
+
+        def per_sample(num_nodes_phar, n_samples):
+            nph = num_nodes_phar.cpu().numpy()
+            for b in range(n_samples):
+                rs.records(restraints, nph, sample=b)                       # (names the entry of the caller's list)
+            return [dict(r, sample=b) for b in range(n_samples) for r in restraints]
+        return max(named, default=0) + 1, per_sample
+
+    def _moved_back(self, first, n_samples, sample, pocket_too=False):
+        """sample() -> a ConditionalDDPM entry's tuple for `first`, the pocket as given (of several: the first one, every pocket was
+        translated by the same vector).  Moves the points back to the original pocket position by that pocket's shift (pocket_too: and
+        the pocket the sampler returned).  -> (xh_phar, phar_mask, what the entry returned behind its four: [] or [info])."""
+        pocket_com_before = _scatter_mean(first['x'], first['mask'], n_samples)
+        xh_phar, xh_pocket, phar_mask, pocket_mask, *info = sample()
+        if isinstance(xh_pocket, list):
+            xh_pocket, pocket_mask = xh_pocket[0], pocket_mask[0]
+        pocket_com_after = _scatter_mean(xh_pocket[:, :self.x_dims], pocket_mask, n_samples)
+        if pocket_too:
+            xh_pocket[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[pocket_mask]
+        xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
+        return xh_phar, phar_mask, info
+
+    def _molecule_dict(self, xh_phar, phar_mask):
+        """generate_phars' output format.  Quirk Q9 kept: the counter restarts for every sample and advances per POINT, so 'Molecule_k'
+        collects the k-th point of all samples, grouped by predicted type."""
+        phar_mask = phar_mask.cpu()
+        x = xh_phar[:, :self.x_dims].detach().cpu()
+        phar_type = xh_phar[:, self.x_dims:].argmax(1).detach().cpu()
+        phar_to_coords = {}
+        for coords_batch, types in zip(utils.batch_to_list(x, phar_mask), utils.batch_to_list(phar_type, phar_mask)):
+            names = [self.dataset_info['phar_decoder'][int(t)] for t in types]
+            for k, (name, coords) in enumerate(zip(names, coords_batch), start=1):
+                phar_to_coords.setdefault(f'Molecule_{k}', {}).setdefault(name, []).append(coords)
+        return phar_to_coords
+
     def generate_phars(self, pdb_file, n_samples, pocket_ids=None, ref_ligand=None, num_nodes_phar=None,
                        sanitize=False, largest_frag=False, relax_iter=0, timesteps=None, **kwargs):
         """Generate pharmacophore point clouds inside a pocket (lightning_modules.py:385-541).
@@ -301,12 +376,11 @@ class PharPocketDDPM(nn.Module):
         sanitize / largest_frag / relax_iter and the inpainting kwargs are accepted and have no
         effect in conditional mode, as in the reference (quirk Q10); in mode 'joint' the kwargs
         (resamplings, jump_length) go to EnVariationalDiffusion.inpaint (lightning_modules.py:466-486)."""
-        assert (pocket_ids is None) ^ (ref_ligand is None)
+        load = self._pocket_request(None, pdb_file, pocket_ids, ref_ligand)
         sampler_kw = {k: kwargs.pop(k) for k in ('noise', 'seed') if k in kwargs}
-        pocket = self._pdb_pocket(pdb_file, n_samples, pocket_ids, ref_ligand)
-        pocket_com_before = _scatter_mean(pocket['x'], pocket['mask'], n_samples)
+        pocket, = load(n_samples)
         if num_nodes_phar is None:
-            num_nodes_phar = self.ddpm.size_distribution.sample_conditional(n1=None, n2=pocket['size'])
+            num_nodes_phar = self._num_nodes(None, pocket, n_samples)
         if type(self.ddpm) == EnVariationalDiffusion:
             # inpainting: every pocket node is fixed, every phar node is generated (lightning_modules.py:466-486)
             num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device)
@@ -316,28 +390,13 @@ class PharPocketDDPM(nn.Module):
                     'size': num_nodes_phar, 'mask': phar_mask}
             phar_mask_fixed = torch.zeros(len(phar_mask), device=self.device)
             pocket_mask_fixed = torch.ones(len(pocket['mask']), device=self.device)
-            xh_phar, xh_pocket, phar_mask, pocket_mask = self.ddpm.inpaint(
-                phar, pocket, phar_mask_fixed, pocket_mask_fixed, timesteps=timesteps, **sampler_kw, **kwargs)
+            sample = lambda: self.ddpm.inpaint(phar, pocket, phar_mask_fixed, pocket_mask_fixed, timesteps=timesteps, **sampler_kw, **kwargs)
         elif isinstance(self.ddpm, ConditionalDDPM):
-            xh_phar, xh_pocket, phar_mask, pocket_mask = self.ddpm.sample_given_pocket(
-                pocket, num_nodes_phar, timesteps=timesteps, **sampler_kw)
+            sample = lambda: self.ddpm.sample_given_pocket(pocket, num_nodes_phar, timesteps=timesteps, **sampler_kw)
         else:
             raise NotImplementedError
-        # move the generated points back to the original pocket position
-        pocket_com_after = _scatter_mean(xh_pocket[:, :self.x_dims], pocket_mask, n_samples)
-        xh_pocket[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[pocket_mask]
-        xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
-        phar_mask = phar_mask.cpu()
-        x = xh_phar[:, :self.x_dims].detach().cpu()
-        phar_type = xh_phar[:, self.x_dims:].argmax(1).detach().cpu()
-        # Quirk Q9 kept: the counter restarts for every sample and advances per POINT, so
-        # 'Molecule_k' collects the k-th point of all samples, grouped by predicted type.
-        phar_to_coords = {}
-        for coords_batch, types in zip(utils.batch_to_list(x, phar_mask), utils.batch_to_list(phar_type, phar_mask)):
-            names = [self.dataset_info['phar_decoder'][int(t)] for t in types]
-            for k, (name, coords) in enumerate(zip(names, coords_batch), start=1):
-                phar_to_coords.setdefault(f'Molecule_{k}', {}).setdefault(name, []).append(coords)
-        return phar_to_coords
+        xh_phar, phar_mask, _ = self._moved_back(pocket, n_samples, sample, pocket_too=True)
+        return self._molecule_dict(xh_phar, phar_mask)
 
     def generate_phars_multi(self, pdb_files, n_samples, pocket_ids=None, ref_ligands=None, num_nodes_phar=None, weights=None,
                              timesteps=None, **kwargs):
@@ -352,34 +411,14 @@ class PharPocketDDPM(nn.Module):
         num_nodes_phar: points per sample, default the size prior given the FIRST pocket.  weights: None (uniform) or one
         weight per file, >= 0 (normalised to sum 1).  seed / noise go to the sampler.  Everything is moved back by the first
         pocket's shift, so the points come out in the common frame.  -> the phar_to_coords dict of generate_phars."""
-        pdb_files = list(pdb_files)
-        M = len(pdb_files)
-        assert (pocket_ids is None) ^ (ref_ligands is None)
-        if len(pocket_ids if pocket_ids is not None else ref_ligands) != M:
-            raise ValueError(f'{M} pdb_files need {M} entries of pocket_ids or ref_ligands (one per file)')
-        if not isinstance(self.ddpm, ConditionalDDPM):
-            raise NotImplementedError('generate_phars_multi needs the conditional model (mode pocket_conditioning)')
+        load = self._pocket_request('generate_phars_multi', pdb_files, pocket_ids, ref_ligands, many=True)
         sampler_kw = {k: kwargs.pop(k) for k in ('noise', 'seed', 'group_ids') if k in kwargs}
-        pockets = [self._pdb_pocket(f, n_samples, pocket_ids[m] if pocket_ids is not None else None,
-                                    ref_ligands[m] if ref_ligands is not None else None) for m, f in enumerate(pdb_files)]
-        first = pockets[0]
-        pocket_com_before = _scatter_mean(first['x'], first['mask'], n_samples)
+        pockets = load(n_samples)
         if num_nodes_phar is None:
-            num_nodes_phar = self.ddpm.size_distribution.sample_conditional(n1=None, n2=first['size'])
-        xh_phar, xh_pockets, phar_mask, pocket_masks = self.ddpm.sample_given_pockets(
-            pockets, num_nodes_phar, weights=weights, timesteps=timesteps, **sampler_kw)
-        # move the generated points back by the first pocket's shift (every pocket was translated by the same vector)
-        pocket_com_after = _scatter_mean(xh_pockets[0][:, :self.x_dims], pocket_masks[0], n_samples)
-        xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
-        phar_mask = phar_mask.cpu()
-        x = xh_phar[:, :self.x_dims].detach().cpu()
-        phar_type = xh_phar[:, self.x_dims:].argmax(1).detach().cpu()
-        phar_to_coords = {}
-        for coords_batch, types in zip(utils.batch_to_list(x, phar_mask), utils.batch_to_list(phar_type, phar_mask)):
-            names = [self.dataset_info['phar_decoder'][int(t)] for t in types]
-            for k, (name, coords) in enumerate(zip(names, coords_batch), start=1):
-                phar_to_coords.setdefault(f'Molecule_{k}', {}).setdefault(name, []).append(coords)
-        return phar_to_coords
+            num_nodes_phar = self._num_nodes(None, pockets[0], n_samples)
+        xh_phar, phar_mask, _ = self._moved_back(pockets[0], n_samples, lambda: self.ddpm.sample_given_pockets(
+            pockets, num_nodes_phar, weights=weights, timesteps=timesteps, **sampler_kw))
+        return self._molecule_dict(xh_phar, phar_mask)
 
     @torch.no_grad()
     def generate_phars_restrained(self, pdb_file, n_samples, restraints, pocket_ids=None, ref_ligand=None, num_nodes_phar=None,
@@ -393,37 +432,15 @@ class PharPocketDDPM(nn.Module):
         guide_below as sample_restrained; the pocket and the move back to its position as generate_phars.
         -> (one point list per sample, [(type name, (x, y, z))] in the PDB's frame - edit_phars' format, the ``candidates`` of
         score_phars - and {'energy': [n_samples], 'max_violation': [n_samples]} of the returned samples, to filter on)."""
-        from . import restraints as rs
-        assert (pocket_ids is None) ^ (ref_ligand is None)
-        if not isinstance(self.ddpm, ConditionalDDPM):
-            raise NotImplementedError('generate_phars_restrained needs the conditional model (mode pocket_conditioning)')
-        restraints = list(restraints)
-        for n, r in enumerate(restraints):
-            if isinstance(r, dict) and 'sample' in r:
-                raise ValueError(f"restraints[{n}] = {r!r}: restraints are given once, without 'sample', and applied to every sample")
-        named = [int(v) for r in restraints if isinstance(r, dict)
-                 for v in ([r['point']] if 'point' in r else list(r.get('points', ()))) if isinstance(v, (int, np.integer))]
-        pocket = self._pdb_pocket(pdb_file, n_samples, pocket_ids, ref_ligand)
-        pocket_com_before = _scatter_mean(pocket['x'], pocket['mask'], n_samples)
-        if num_nodes_phar is None:
-            num_nodes_phar = self.ddpm.size_distribution.sample_conditional(n1=None, n2=pocket['size'])
-            num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device).clamp(min=max(named, default=0) + 1)
-        else:
-            num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device).reshape(-1)
-            if num_nodes_phar.numel() == 1:
-                num_nodes_phar = num_nodes_phar.expand(n_samples)
-        num_nodes_phar = num_nodes_phar.to(INT_TYPE)
-        nph = num_nodes_phar.cpu().numpy()
-        for b in range(n_samples):
-            rs.records(restraints, nph, sample=b)                       # (names the entry of the caller's list)
-        per_sample = [dict(r, sample=b) for b in range(n_samples) for r in restraints]
-        xh_phar, xh_pocket, phar_mask, pocket_mask, info = self.ddpm.sample_restrained(
-            pocket, num_nodes_phar, per_sample, clash=clash, scale=scale, max_shift=max_shift, guide_below=guide_below,
-            timesteps=timesteps, seed=seed, noise=noise)
-        # move the points back to the original pocket position (as generate_phars)
-        pocket_com_after = _scatter_mean(xh_pocket[:, :self.x_dims], pocket_mask, n_samples)
-        xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
-        return self._point_lists(xh_phar, {'size': num_nodes_phar}), info
+        load = self._pocket_request('generate_phars_restrained', pdb_file, pocket_ids, ref_ligand)
+        at_least, per_sample = self._restraints_for_all(restraints)
+        pocket, = load(n_samples)
+        num_nodes_phar = self._num_nodes(num_nodes_phar, pocket, n_samples, at_least)
+        restraints = per_sample(num_nodes_phar, n_samples)
+        xh_phar, _, info = self._moved_back(pocket, n_samples, lambda: self.ddpm.sample_restrained(
+            pocket, num_nodes_phar, restraints, clash=clash, scale=scale, max_shift=max_shift, guide_below=guide_below, timesteps=timesteps,
+            seed=seed, noise=noise))
+        return self._point_lists(xh_phar, {'size': num_nodes_phar}), info[0]
 
     @torch.no_grad()
     def generate_phars_diverse(self, pdb_file, n_samples, pocket_ids=None, ref_ligand=None, num_nodes_phar=None, strength=1.0, width=2.0,
@@ -435,25 +452,13 @@ class PharPocketDDPM(nn.Module):
         num_nodes_phar (default the size prior given the pocket) and the move back to the pocket's position as generate_phars_restrained.
         -> (one point list per sample, [(type name, (x, y, z))] in the PDB's frame - edit_phars' format, the ``candidates`` of
         score_phars - and {'overlap': [n_samples]}, the mean overlap of every returned sample with the others, to rank on)."""
-        assert (pocket_ids is None) ^ (ref_ligand is None)
-        if not isinstance(self.ddpm, ConditionalDDPM):
-            raise NotImplementedError('generate_phars_diverse needs the conditional model (mode pocket_conditioning)')
-        pocket = self._pdb_pocket(pdb_file, n_samples, pocket_ids, ref_ligand)
-        pocket_com_before = _scatter_mean(pocket['x'], pocket['mask'], n_samples)
-        if num_nodes_phar is None:
-            num_nodes_phar = torch.as_tensor(self.ddpm.size_distribution.sample_conditional(n1=None, n2=pocket['size']), device=self.device)
-        else:
-            num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device).reshape(-1)
-            if num_nodes_phar.numel() == 1:
-                num_nodes_phar = num_nodes_phar.expand(n_samples)
-        num_nodes_phar = num_nodes_phar.to(INT_TYPE)
-        xh_phar, xh_pocket, phar_mask, pocket_mask, info = self.ddpm.sample_diverse(
+        load = self._pocket_request('generate_phars_diverse', pdb_file, pocket_ids, ref_ligand)
+        pocket, = load(n_samples)
+        num_nodes_phar = self._num_nodes(num_nodes_phar, pocket, n_samples)
+        xh_phar, _, info = self._moved_back(pocket, n_samples, lambda: self.ddpm.sample_diverse(
             pocket, num_nodes_phar, [n_samples], strength=strength, width=width, max_shift=max_shift, guide_below=guide_below,
-            timesteps=timesteps, seed=seed, noise=noise)
-        # move the points back to the original pocket position (as generate_phars)
-        pocket_com_after = _scatter_mean(xh_pocket[:, :self.x_dims], pocket_mask, n_samples)
-        xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
-        return self._point_lists(xh_phar, {'size': num_nodes_phar}), info
+            timesteps=timesteps, seed=seed, noise=noise))
+        return self._point_lists(xh_phar, {'size': num_nodes_phar}), info[0]
 
     @torch.no_grad()
     def generate_phars_multi_restrained(self, pdb_files, n_samples, restraints, pocket_ids=None, ref_ligands=None, num_nodes_phar=None,
@@ -468,64 +473,29 @@ class PharPocketDDPM(nn.Module):
         max_shift, guide_below as sample_restrained.  Everything is moved back by the FIRST pocket's shift - the frame the guidance itself
         follows - so the points come out in the frame the centres were given in.
         -> (one point list per sample, [(type name, (x, y, z))], and {'energy': [n_samples], 'max_violation': [n_samples]})."""
-        from . import restraints as rs
-        pdb_files = list(pdb_files)
-        M = len(pdb_files)
-        assert (pocket_ids is None) ^ (ref_ligands is None)
-        if len(pocket_ids if pocket_ids is not None else ref_ligands) != M:
-            raise ValueError(f'{M} pdb_files need {M} entries of pocket_ids or ref_ligands (one per file)')
-        if not isinstance(self.ddpm, ConditionalDDPM):
-            raise NotImplementedError('generate_phars_multi_restrained needs the conditional model (mode pocket_conditioning)')
-        restraints = list(restraints)
-        for n, r in enumerate(restraints):
-            if isinstance(r, dict) and 'sample' in r:
-                raise ValueError(f"restraints[{n}] = {r!r}: restraints are given once, without 'sample', and applied to every sample")
-        named = [int(v) for r in restraints if isinstance(r, dict)
-                 for v in ([r['point']] if 'point' in r else list(r.get('points', ()))) if isinstance(v, (int, np.integer))]
-        pockets = [self._pdb_pocket(f, n_samples, pocket_ids[m] if pocket_ids is not None else None,
-                                    ref_ligands[m] if ref_ligands is not None else None) for m, f in enumerate(pdb_files)]
-        first = pockets[0]
-        pocket_com_before = _scatter_mean(first['x'], first['mask'], n_samples)
-        if num_nodes_phar is None:
-            num_nodes_phar = self.ddpm.size_distribution.sample_conditional(n1=None, n2=first['size'])
-            num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device).clamp(min=max(named, default=0) + 1)
-        else:
-            num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device).reshape(-1)
-            if num_nodes_phar.numel() == 1:
-                num_nodes_phar = num_nodes_phar.expand(n_samples)
-        num_nodes_phar = num_nodes_phar.to(INT_TYPE)
-        nph = num_nodes_phar.cpu().numpy()
-        for b in range(n_samples):
-            rs.records(restraints, nph, sample=b)                       # (names the entry of the caller's list)
-        per_sample = [dict(r, sample=b) for b in range(n_samples) for r in restraints]
+        load = self._pocket_request('generate_phars_multi_restrained', pdb_files, pocket_ids, ref_ligands, many=True)
+        at_least, per_sample = self._restraints_for_all(restraints)
+        pockets = load(n_samples)
+        num_nodes_phar = self._num_nodes(num_nodes_phar, pockets[0], n_samples, at_least)
+        restraints = per_sample(num_nodes_phar, n_samples)
         sampler_kw = {} if group_ids is None else {'group_ids': group_ids}
-        xh_phar, xh_pockets, phar_mask, pocket_masks, info = self.ddpm.sample_restrained_given_pockets(
-            pockets, num_nodes_phar, per_sample, weights=weights, clash=clash, scale=scale, max_shift=max_shift, guide_below=guide_below,
-            timesteps=timesteps, seed=seed, noise=noise, **sampler_kw)
-        # move the points back by the first pocket's shift (every pocket was translated by the same vector; the centres never moved)
-        pocket_com_after = _scatter_mean(xh_pockets[0][:, :self.x_dims], pocket_masks[0], n_samples)
-        xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
-        return self._point_lists(xh_phar, {'size': num_nodes_phar}), info
+        xh_phar, _, info = self._moved_back(pockets[0], n_samples, lambda: self.ddpm.sample_restrained_given_pockets(
+            pockets, num_nodes_phar, restraints, weights=weights, clash=clash, scale=scale, max_shift=max_shift, guide_below=guide_below,
+            timesteps=timesteps, seed=seed, noise=noise, **sampler_kw))
+        return self._point_lists(xh_phar, {'size': num_nodes_phar}), info[0]
 
-    def _phar_with_given_rows(self, points, arg, n_samples, num_nodes_phar, pocket):
+    def _phar_with_given_rows(self, points, arg, n_samples, num_nodes_phar, pocket, at_least=0):
         """The phar batch of inpaint_phars / edit_phars: `points` = [(type name, (x, y, z))] are the first rows of every sample, the
-        other rows zero.  num_nodes_phar: points per sample, default the size prior given the pocket, at least len(points).
-        -> (phar dict, the indices of the given rows, sample by sample)."""
+        other rows zero.  num_nodes_phar: points per sample, default the size prior given the pocket, at least len(points) (and at_least,
+        the rows a caller's restraints name).  -> (phar dict, the indices of the given rows, sample by sample)."""
         n_fix = len(points)
         decoder = list(self.dataset_info['phar_decoder'])
         for name, _ in points:
             if name not in decoder:
                 raise ValueError(f'unknown pharmacophore type {name!r}: expected one of {decoder}')
-        if num_nodes_phar is None:
-            num_nodes_phar = self.ddpm.size_distribution.sample_conditional(n1=None, n2=pocket['size'])
-            num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device).clamp(min=n_fix)
-        else:
-            num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device).reshape(-1)
-            if num_nodes_phar.numel() == 1:
-                num_nodes_phar = num_nodes_phar.expand(n_samples)
-            if bool((num_nodes_phar < n_fix).any()):
-                raise ValueError(f'num_nodes_phar must be at least len({arg}) = {n_fix}')
-        num_nodes_phar = num_nodes_phar.to(INT_TYPE)
+        num_nodes_phar = self._num_nodes(num_nodes_phar, pocket, n_samples, at_least=max(n_fix, at_least))
+        if bool((num_nodes_phar < n_fix).any()):
+            raise ValueError(f'num_nodes_phar must be at least len({arg}) = {n_fix}')
         phar_mask = utils.num_nodes_to_batch_mask(n_samples, num_nodes_phar, self.device)
         first = torch.cumsum(num_nodes_phar, 0) - num_nodes_phar                 # first row of every sample
         rows = (first[:, None] + torch.arange(n_fix, device=self.device)[None, :]).reshape(-1)
@@ -544,30 +514,14 @@ class PharPocketDDPM(nn.Module):
         fixed_phars: [(type name of dataset_info['phar_decoder'], (x, y, z) in Angstrom in the PDB's frame)]; they are the
         first rows of every sample.  num_nodes_phar: points per sample, default the size prior given the pocket, at least
         len(fixed_phars).  The pocket, the output format and the move back to the pocket's position are generate_phars'."""
-        assert (pocket_ids is None) ^ (ref_ligand is None)
-        if not isinstance(self.ddpm, ConditionalDDPM):
-            raise NotImplementedError('inpaint_phars needs the conditional model (mode pocket_conditioning)')
-        decoder = list(self.dataset_info['phar_decoder'])
-        pocket = self._pdb_pocket(pdb_file, n_samples, pocket_ids, ref_ligand)
-        pocket_com_before = _scatter_mean(pocket['x'], pocket['mask'], n_samples)
+        load = self._pocket_request('inpaint_phars', pdb_file, pocket_ids, ref_ligand)
+        pocket, = load(n_samples)
         phar, rows = self._phar_with_given_rows(fixed_phars, 'fixed_phars', n_samples, num_nodes_phar, pocket)
         fixed = torch.zeros(len(phar['mask']), device=self.device, dtype=FLOAT_TYPE)
         fixed[rows] = 1.0
-        xh_phar, xh_pocket, phar_mask, pocket_mask = self.ddpm.inpaint(
-            phar, pocket, fixed, resamplings=resamplings, jump_length=jump_length, timesteps=timesteps, seed=seed)
-        # move the generated points back to the original pocket position (as generate_phars)
-        pocket_com_after = _scatter_mean(xh_pocket[:, :self.x_dims], pocket_mask, n_samples)
-        xh_pocket[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[pocket_mask]
-        xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
-        phar_mask = phar_mask.cpu()
-        x = xh_phar[:, :self.x_dims].detach().cpu()
-        phar_type = xh_phar[:, self.x_dims:].argmax(1).detach().cpu()
-        phar_to_coords = {}
-        for coords_batch, types in zip(utils.batch_to_list(x, phar_mask), utils.batch_to_list(phar_type, phar_mask)):
-            names = [decoder[int(t)] for t in types]
-            for k, (name, coords) in enumerate(zip(names, coords_batch), start=1):
-                phar_to_coords.setdefault(f'Molecule_{k}', {}).setdefault(name, []).append(coords)
-        return phar_to_coords
+        xh_phar, phar_mask, _ = self._moved_back(pocket, n_samples, lambda: self.ddpm.inpaint(
+            phar, pocket, fixed, resamplings=resamplings, jump_length=jump_length, timesteps=timesteps, seed=seed), pocket_too=True)
+        return self._molecule_dict(xh_phar, phar_mask)
 
     KEEP = {'types': (False, True), 'coords': (True, False), 'both': (True, True), 'none': (False, False)}
 
@@ -583,19 +537,13 @@ class PharPocketDDPM(nn.Module):
         free rows as in inpaint_phars (default: the size prior; with strength < 1 the given points only); with strength < 1 extra
         free rows are refused (there is nothing to noise for those rows).
         -> one point list per sample, [(type name, (x, y, z))] back in the PDB's frame: the ``candidates`` of score_phars."""
-        assert (pocket_ids is None) ^ (ref_ligand is None)
-        if not isinstance(self.ddpm, ConditionalDDPM):
-            raise NotImplementedError('edit_phars needs the conditional model (mode pocket_conditioning)')
+        load = self._pocket_request('edit_phars', pdb_file, pocket_ids, ref_ligand)
         keeps, start = self._edit_keeps_and_start(phars, keep, strength, timesteps)
-        pocket = self._pdb_pocket(pdb_file, n_samples, pocket_ids, ref_ligand)
-        pocket_com_before = _scatter_mean(pocket['x'], pocket['mask'], n_samples)
+        pocket, = load(n_samples)
         phar, fix_x, fix_h = self._edit_phar_and_masks(phars, keeps, start, strength, timesteps, n_samples, num_nodes_phar, pocket)
-        xh_phar, xh_pocket, phar_mask, pocket_mask = self.ddpm.edit(
+        xh_phar, _, _ = self._moved_back(pocket, n_samples, lambda: self.ddpm.edit(
             phar, pocket, fix_coords=fix_x, fix_types=fix_h, start=start, resamplings=resamplings, jump_length=jump_length,
-            timesteps=timesteps, seed=seed)
-        # move the points back to the original pocket position (as generate_phars)
-        pocket_com_after = _scatter_mean(xh_pocket[:, :self.x_dims], pocket_mask, n_samples)
-        xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
+            timesteps=timesteps, seed=seed))
         return self._point_lists(xh_phar, phar)
 
     @torch.no_grad()
@@ -612,36 +560,16 @@ class PharPocketDDPM(nn.Module):
         coordinates are kept enters the query at its given position and is not moved by it.
         -> (one point list per sample in the PDB's frame, {'energy': [n_samples], 'max_violation': [n_samples]} of the returned
         samples, to filter on)."""
-        from . import restraints as rs
-        assert (pocket_ids is None) ^ (ref_ligand is None)
-        if not isinstance(self.ddpm, ConditionalDDPM):
-            raise NotImplementedError('edit_phars_restrained needs the conditional model (mode pocket_conditioning)')
-        restraints = list(restraints)
-        for n, r in enumerate(restraints):
-            if isinstance(r, dict) and 'sample' in r:
-                raise ValueError(f"restraints[{n}] = {r!r}: restraints are given once, without 'sample', and applied to every sample")
-        named = [int(v) for r in restraints if isinstance(r, dict)
-                 for v in ([r['point']] if 'point' in r else list(r.get('points', ()))) if isinstance(v, (int, np.integer))]
+        load = self._pocket_request('edit_phars_restrained', pdb_file, pocket_ids, ref_ligand)
+        at_least, per_sample = self._restraints_for_all(restraints)
         keeps, start = self._edit_keeps_and_start(phars, keep, strength, timesteps)
-        pocket = self._pdb_pocket(pdb_file, n_samples, pocket_ids, ref_ligand)
-        pocket_com_before = _scatter_mean(pocket['x'], pocket['mask'], n_samples)
-        T = self.ddpm.T if timesteps is None else int(timesteps)
-        if num_nodes_phar is None and not (start is not None and start < T):
-            # from the prior: the size prior given the pocket, at least the given points and the rows the restraints name
-            num_nodes_phar = self.ddpm.size_distribution.sample_conditional(n1=None, n2=pocket['size'])
-            num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device).clamp(min=max(len(phars), max(named, default=0) + 1))
-        phar, fix_x, fix_h = self._edit_phar_and_masks(phars, keeps, start, strength, timesteps, n_samples, num_nodes_phar, pocket)
-        nph = phar['size'].cpu().numpy()
-        for b in range(n_samples):
-            rs.records(restraints, nph, sample=b)                       # (names the entry of the caller's list)
-        per_sample = [dict(r, sample=b) for b in range(n_samples) for r in restraints]
-        xh_phar, xh_pocket, phar_mask, pocket_mask, info = self.ddpm.edit_restrained(
-            phar, pocket, per_sample, fix_coords=fix_x, fix_types=fix_h, start=start, resamplings=resamplings, jump_length=jump_length,
-            clash=clash, scale=scale, max_shift=max_shift, guide_below=guide_below, timesteps=timesteps, seed=seed)
-        # move the points back to the original pocket position (as generate_phars)
-        pocket_com_after = _scatter_mean(xh_pocket[:, :self.x_dims], pocket_mask, n_samples)
-        xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
-        return self._point_lists(xh_phar, phar), info
+        pocket, = load(n_samples)
+        phar, fix_x, fix_h = self._edit_phar_and_masks(phars, keeps, start, strength, timesteps, n_samples, num_nodes_phar, pocket, at_least)
+        restraints = per_sample(phar['size'], n_samples)
+        xh_phar, _, info = self._moved_back(pocket, n_samples, lambda: self.ddpm.edit_restrained(
+            phar, pocket, restraints, fix_coords=fix_x, fix_types=fix_h, start=start, resamplings=resamplings, jump_length=jump_length,
+            clash=clash, scale=scale, max_shift=max_shift, guide_below=guide_below, timesteps=timesteps, seed=seed))
+        return self._point_lists(xh_phar, phar), info[0]
 
     def _edit_keeps_and_start(self, phars, keep, strength, timesteps):
         """edit_phars' argument rules: -> (what every given point holds, the start level or None for the prior)."""
@@ -659,14 +587,14 @@ class PharPocketDDPM(nn.Module):
             start = max(1, int(round(float(strength) * T)))
         return keeps, start
 
-    def _edit_phar_and_masks(self, phars, keeps, start, strength, timesteps, n_samples, num_nodes_phar, pocket):
+    def _edit_phar_and_masks(self, phars, keeps, start, strength, timesteps, n_samples, num_nodes_phar, pocket, at_least=0):
         """-> (the phar batch with the given points as the first rows of every sample, fix_x, fix_h); pocket: the one the size prior
-        is conditioned on."""
+        is conditioned on; at_least: the rows the restraints name, which the size prior's draw is raised to."""
         n_given = len(phars)
         T = self.ddpm.T if timesteps is None else int(timesteps)
         if start is not None and start < T and num_nodes_phar is None:
             num_nodes_phar = n_given                                    # part-way: the given points only (no size prior)
-        phar, rows = self._phar_with_given_rows(phars, 'phars', n_samples, num_nodes_phar, pocket)
+        phar, rows = self._phar_with_given_rows(phars, 'phars', n_samples, num_nodes_phar, pocket, at_least)
         if start is not None and start < T and bool((phar['size'] > n_given).any()):
             raise ValueError(f'strength={strength} < 1 noises the given points; the extra free rows of num_nodes_phar have nothing to '
                              'noise: use strength=None (or 1), or num_nodes_phar = len(phars)')
@@ -698,25 +626,13 @@ class PharPocketDDPM(nn.Module):
         follow edit_phars' rules (the size prior is conditioned on the FIRST pocket; with strength < 1 the given points only).
         The result is moved back by the first pocket's shift.  -> edit_phars' point list per sample; keep='both' from the prior is
         the multi-pocket inpaint_phars."""
-        pdb_files = list(pdb_files)
-        M = len(pdb_files)
-        assert (pocket_ids is None) ^ (ref_ligands is None)
-        if len(pocket_ids if pocket_ids is not None else ref_ligands) != M:
-            raise ValueError(f'{M} pdb_files need {M} entries of pocket_ids or ref_ligands (one per file)')
-        if not isinstance(self.ddpm, ConditionalDDPM):
-            raise NotImplementedError('edit_phars_multi needs the conditional model (mode pocket_conditioning)')
+        load = self._pocket_request('edit_phars_multi', pdb_files, pocket_ids, ref_ligands, many=True)
         keeps, start = self._edit_keeps_and_start(phars, keep, strength, timesteps)
-        pockets = [self._pdb_pocket(f, n_samples, pocket_ids[m] if pocket_ids is not None else None,
-                                    ref_ligands[m] if ref_ligands is not None else None) for m, f in enumerate(pdb_files)]
-        first = pockets[0]
-        pocket_com_before = _scatter_mean(first['x'], first['mask'], n_samples)
-        phar, fix_x, fix_h = self._edit_phar_and_masks(phars, keeps, start, strength, timesteps, n_samples, num_nodes_phar, first)
-        xh_phar, xh_pockets, phar_mask, pocket_masks = self.ddpm.edit_given_pockets(
+        pockets = load(n_samples)
+        phar, fix_x, fix_h = self._edit_phar_and_masks(phars, keeps, start, strength, timesteps, n_samples, num_nodes_phar, pockets[0])
+        xh_phar, _, _ = self._moved_back(pockets[0], n_samples, lambda: self.ddpm.edit_given_pockets(
             phar, pockets, fix_coords=fix_x, fix_types=fix_h, start=start, resamplings=resamplings, jump_length=jump_length,
-            weights=weights, timesteps=timesteps, seed=seed)
-        # move the points back by the first pocket's shift (every pocket was translated by the same vector)
-        pocket_com_after = _scatter_mean(xh_pockets[0][:, :self.x_dims], pocket_masks[0], n_samples)
-        xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
+            weights=weights, timesteps=timesteps, seed=seed))
         return self._point_lists(xh_phar, phar)
 
     @torch.no_grad()
@@ -734,42 +650,16 @@ class PharPocketDDPM(nn.Module):
         sample: rows 0 .. len(phars) - 1 are the given points, the rows behind them the free ones.  Everything is moved back by the FIRST
         pocket's shift - the frame the guidance itself follows.
         -> (one point list per sample in the common frame, {'energy': [n_samples], 'max_violation': [n_samples]} of the returned samples)."""
-        from . import restraints as rs
-        pdb_files = list(pdb_files)
-        M = len(pdb_files)
-        assert (pocket_ids is None) ^ (ref_ligands is None)
-        if len(pocket_ids if pocket_ids is not None else ref_ligands) != M:
-            raise ValueError(f'{M} pdb_files need {M} entries of pocket_ids or ref_ligands (one per file)')
-        if not isinstance(self.ddpm, ConditionalDDPM):
-            raise NotImplementedError('edit_phars_multi_restrained needs the conditional model (mode pocket_conditioning)')
-        restraints = list(restraints)
-        for n, r in enumerate(restraints):
-            if isinstance(r, dict) and 'sample' in r:
-                raise ValueError(f"restraints[{n}] = {r!r}: restraints are given once, without 'sample', and applied to every sample")
-        named = [int(v) for r in restraints if isinstance(r, dict)
-                 for v in ([r['point']] if 'point' in r else list(r.get('points', ()))) if isinstance(v, (int, np.integer))]
+        load = self._pocket_request('edit_phars_multi_restrained', pdb_files, pocket_ids, ref_ligands, many=True)
+        at_least, per_sample = self._restraints_for_all(restraints)
         keeps, start = self._edit_keeps_and_start(phars, keep, strength, timesteps)
-        pockets = [self._pdb_pocket(f, n_samples, pocket_ids[m] if pocket_ids is not None else None,
-                                    ref_ligands[m] if ref_ligands is not None else None) for m, f in enumerate(pdb_files)]
-        first = pockets[0]
-        pocket_com_before = _scatter_mean(first['x'], first['mask'], n_samples)
-        T = self.ddpm.T if timesteps is None else int(timesteps)
-        if num_nodes_phar is None and not (start is not None and start < T):
-            # from the prior: the size prior given the FIRST pocket, at least the given points and the rows the restraints name
-            num_nodes_phar = self.ddpm.size_distribution.sample_conditional(n1=None, n2=first['size'])
-            num_nodes_phar = torch.as_tensor(num_nodes_phar, device=self.device).clamp(min=max(len(phars), max(named, default=0) + 1))
-        phar, fix_x, fix_h = self._edit_phar_and_masks(phars, keeps, start, strength, timesteps, n_samples, num_nodes_phar, first)
-        nph = phar['size'].cpu().numpy()
-        for b in range(n_samples):
-            rs.records(restraints, nph, sample=b)                       # (names the entry of the caller's list)
-        per_sample = [dict(r, sample=b) for b in range(n_samples) for r in restraints]
-        xh_phar, xh_pockets, phar_mask, pocket_masks, info = self.ddpm.edit_restrained_given_pockets(
-            phar, pockets, per_sample, fix_coords=fix_x, fix_types=fix_h, start=start, resamplings=resamplings, jump_length=jump_length,
-            weights=weights, clash=clash, scale=scale, max_shift=max_shift, guide_below=guide_below, timesteps=timesteps, seed=seed)
-        # move the points back by the first pocket's shift (every pocket was translated by the same vector; the centres never moved)
-        pocket_com_after = _scatter_mean(xh_pockets[0][:, :self.x_dims], pocket_masks[0], n_samples)
-        xh_phar[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[phar_mask]
-        return self._point_lists(xh_phar, phar), info
+        pockets = load(n_samples)
+        phar, fix_x, fix_h = self._edit_phar_and_masks(phars, keeps, start, strength, timesteps, n_samples, num_nodes_phar, pockets[0], at_least)
+        restraints = per_sample(phar['size'], n_samples)
+        xh_phar, _, info = self._moved_back(pockets[0], n_samples, lambda: self.ddpm.edit_restrained_given_pockets(
+            phar, pockets, restraints, fix_coords=fix_x, fix_types=fix_h, start=start, resamplings=resamplings, jump_length=jump_length,
+            weights=weights, clash=clash, scale=scale, max_shift=max_shift, guide_below=guide_below, timesteps=timesteps, seed=seed))
+        return self._point_lists(xh_phar, phar), info[0]
 
     # ------------------------------------------------------------------ scoring
     def _score_model(self):
@@ -816,10 +706,10 @@ class PharPocketDDPM(nn.Module):
         id i, so with the same seed a candidate's draws depend on its position in the list only.
         The return value of generate_phars cannot be scored: its 'Molecule_k' groups the k-th point of ALL samples (quirk Q9), not
         the points of one sample.  To rank generated samples go through ddpm.sample_given_pocket -> ddpm.score."""
-        assert (pocket_ids is None) ^ (ref_ligand is None)
+        load = self._pocket_request(None, pdb_file, pocket_ids, ref_ligand)
         ddpm = self._score_model()
         phar = self._candidate_batch(candidates)
-        pocket = self._pdb_pocket(pdb_file, len(candidates), pocket_ids, ref_ligand)
+        pocket, = load(len(candidates))
         return ddpm.score(phar, pocket, timesteps=timesteps, repeats=repeats, seed=seed)
 
     @torch.no_grad()
@@ -833,15 +723,8 @@ class PharPocketDDPM(nn.Module):
         superposed into one common frame.  candidates as score_phars takes them, in that common frame; every candidate is one group
         and candidate i draws with global group id i.  -> the dict of ConditionalDDPM.score_given_pockets, entry i of every tensor
         belonging to candidates[i]."""
-        pdb_files = list(pdb_files)
-        M = len(pdb_files)
-        assert (pocket_ids is None) ^ (ref_ligands is None)
-        if len(pocket_ids if pocket_ids is not None else ref_ligands) != M:
-            raise ValueError(f'{M} pdb_files need {M} entries of pocket_ids or ref_ligands (one per file)')
+        load = self._pocket_request(None, pdb_files, pocket_ids, ref_ligands, many=True)
         ddpm = self._score_model()
-        n = len(candidates)
         phar = self._candidate_batch(candidates)
-        pockets = [self._pdb_pocket(f, n, pocket_ids[m] if pocket_ids is not None else None,
-                                    ref_ligands[m] if ref_ligands is not None else None) for m, f in enumerate(pdb_files)]
-        return ddpm.score_given_pockets(phar, pockets, weights=weights, timesteps=timesteps, repeats=repeats, seed=seed,
+        return ddpm.score_given_pockets(phar, load(len(candidates)), weights=weights, timesteps=timesteps, repeats=repeats, seed=seed,
                                         return_members=return_members)
