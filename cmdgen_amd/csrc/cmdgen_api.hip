@@ -702,11 +702,15 @@ static std::vector<float> step_table(const cmdgen_handle* h, int K) {
 }
 
 // ---------------------------------------------------------------------------------
-// the chains: what the entries of all twelve kinds share.  A kind's state lives in its slot (h->chains[kind]); its entry lays the slot's
-// table block out with the appenders below (TableBlock, cmdgen_host.h: each records where its section begins) and its ChainAlloc composes
-// the parts (alloc_chain_buf, alloc_inpaint_part, point_group_tab, alloc_restrain_part, alloc_score_part) at those offsets - the eight
-// sampling kinds share one, alloc_sampling.  An entry reads top to bottom: checks, table block, Chain::open, its init launches,
-// Chain::start, Chain::steps with its step launch, its final launches, Chain::close.
+// the chains.  The twelve kinds have three host bodies: sampling_chain (nine kinds: a cube of parts - from the prior or from GIVEN rows,
+// one pocket per sample or GROUPS of pockets, unsteered, GUIDEd by restraints or pushed apart within SETS), scoring_chain (two kinds: with
+// or without groups) and cmdgen_joint_chain.  An extern "C" entry of the first two only packs its arguments (SamplingCall, ScoringCall: a
+// part the kind lacks is null) and calls its body; a body branches on the presence of a part, never on the kind.
+// A kind's state lives in its slot (h->chains[kind]).  A body reads top to bottom: refusals, the plans of the parts present, the slot's
+// table block laid out with the appenders below (TableBlock, cmdgen_host.h: each records where its section begins), Chain::open - whose
+// ChainAlloc (alloc_sampling, alloc_scoring, alloc_joint) composes the parts (alloc_chain_buf, alloc_inpaint_part, point_group_tab,
+// alloc_restrain_part, alloc_diverse_part, alloc_score_part) at those offsets - the init launches, Chain::start, Chain::steps with the
+// corner's step launch, the final launches, Chain::close.
 // ---------------------------------------------------------------------------------
 static int check_timesteps(cmdgen_handle* h, int K) {
     if (K < 1 || K > h->cfg.timesteps) return fail(h, CMDGEN_EINVAL, "timesteps=%d must be in [1, %d]", K, h->cfg.timesteps);
@@ -926,16 +930,39 @@ static void point_group_tab(GroupTab& gt, const float* g, size_t B) {
     gt.first = (const int*)g; gt.size = (const int*)(g + B); gt.ubase = (const int*)(g + 2 * B);
     gt.weight = g + 3 * B; gt.group_first = (const int*)(g + 4 * B);
 }
-// The ChainAlloc of the eight sampling kinds ({from the prior, edit} x {one pocket, groups} x {unguided, restrained}): the ChainBuf, then
-// the part of every section the entry appended to its table block; the restrained multi-pocket kinds also get the displacement buffer
-// their guide launch hands to their step launch.
+// the diverse kind's DiverseBuf: the tail append_sets packed at `g` in the table block (n_rows guide rows), com(P_in) and the buffers its
+// launches hand on
+static int alloc_diverse_part(cmdgen_handle* h, ChainSlot& k, const float* g, int n_rows) {
+    DiverseBuf& db = k.div;
+    const size_t B = (size_t)h->lay.B;
+    const float* par = g + (size_t)n_rows * 4;
+    db.sa = (const float4*)g;
+    db.strength = par[0]; db.width = par[1]; db.inv2w2 = par[2]; db.max_shift = par[3]; db.guide_below = par[4];
+    const int* tab = (const int*)(par + 8);
+    db.set_first = tab; db.set_size = tab + B; db.set_row0 = tab + 2 * B; db.set_rows = tab + 3 * B;
+    db.op_overlap = nullptr;
+    int rc = slot_alloc(h, k, db.pin_com, B); if (rc) return rc;
+    rc = slot_alloc(h, k, db.y, (size_t)h->lay.Nl * 3); if (rc) return rc;
+    rc = slot_alloc(h, k, db.gd, (size_t)h->lay.Nl * 3); if (rc) return rc;
+    return slot_alloc(h, k, db.po, (size_t)h->lay.Nl);
+}
+// The ChainAlloc of the nine sampling kinds: the ChainBuf, then the part of every section the body appended to its table block; the
+// restrained multi-pocket kinds also get the displacement buffer their guide launch hands to their step launch.
 static int alloc_sampling(cmdgen_handle* h, ChainSlot& k, const TableBlock& t, const float* dev, int n_steps) {
     int rc = alloc_chain_buf(h, k, dev); if (rc) return rc;
     if (t.edit) { rc = alloc_inpaint_part(h, k, dev + t.edit, n_steps); if (rc) return rc; }
     if (t.groups) point_group_tab(k.groups, dev + t.groups, (size_t)h->lay.B);
     if (t.guide) { rc = alloc_restrain_part(h, k, dev + t.guide, t.guide_rows, t.owners); if (rc) return rc; }
+    if (t.sets) { rc = alloc_diverse_part(h, k, dev + t.sets, t.guide_rows); if (rc) return rc; }
     if (t.groups && t.guide) return slot_alloc(h, k, k.guide_d, (size_t)h->lay.Nl * 3);    // (Nl bounds the unique rows of any grouping)
     return 0;
+}
+// The ChainAlloc of the two scoring kinds: the ChainBuf (coef: one row per level, then the (alpha_T, sigma_T) row), the group tables where
+// the block has them, the clean rows
+static int alloc_scoring(cmdgen_handle* h, ChainSlot& k, const TableBlock& t, const float* dev, int) {
+    const int rc = alloc_chain_buf(h, k, dev); if (rc) return rc;
+    if (t.groups) point_group_tab(k.groups, dev + t.groups, (size_t)h->lay.B);
+    return alloc_score_part(h, k);
 }
 
 // One chain call between begin_chain and end_chain: the stream it runs on, its slot, the launch description of its evaluations and, for
@@ -976,48 +1003,12 @@ struct Chain {
     int close() { return end_chain(h, caller, s); }
 };
 
-extern "C" int cmdgen_sample_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
-                                   int32_t timesteps, const float* noise, uint64_t seed,
-                                   const int64_t* pocket_ids_host, float* xh_phar_out, float* xh_pocket_out,
-                                   float* z_steps_out, float* pocket_steps_out, int32_t use_graph, cmdgen_stream stream) {
-    int rc = check_ready(h); if (rc) return rc;
-    if (!pocket_x || !pocket_onehot || !xh_phar_out || !xh_pocket_out) return fail(h, CMDGEN_EINVAL, "null device pointer");
-    const int K = timesteps;
-    rc = check_timesteps(h, K); if (rc) return rc;
-    if (h->dims.joint) return fail(h, CMDGEN_ESTATE, "this handle is the joint model (update_pocket_coords=1): use cmdgen_joint_chain");
-    TableBlock tables = posterior_rows(step_table(h, K));
-    Chain ch;
-    rc = ch.open(h, CHAIN_PLAIN, tables, K, alloc_sampling, pocket_ids_host, noise, seed, z_steps_out, pocket_steps_out, use_graph, stream); if (rc) return rc;
-    const Dims& d = h->dims;
-    const ChainBuf& c = ch.c;
-    cmdgen_launch_chain_init(h->lay, d, c, pocket_x, pocket_onehot, ch.s);
-    // One denoising step = the posterior update fused with pass 1 of the next radius graph (k_step_count), then the
-    // evaluation at the new state: pass 2 of the graph (k_edge_write), k_embed, the L blocks,
-    // k_readout.  The chain is: evaluation 0, K x (step + evaluation), decode.
-    // Where the plan says so (LaunchPlan::readout_in_coord) the evaluations run without k_readout: its feature part rides in the last coordinate
-    // launch, k_step_count forms the velocity and the NaN flag it consumes itself, and k_vel_flag does so once in front of the decode.
-    ch.a.plain_chain = 1;
-    const int own_vel = readout_mode(ch.a, c.state, nullptr, nullptr, nullptr);  // (what the evaluations below are launched with)
-    ch.start(true);                                  // evaluation 0 (t = 1)
-    // (a step kernel that leaves X0 / ACC to an evaluation that does not take them over would leave stale positions without any error)
-    // (evaluation 0 is already queued when this returns: the chain is abandoned half issued, the handle stays usable - the next chain of any
-    // kind starts again from k_chain_init and k_edge_count, which rewrite everything this one left behind)
-    if (ch.a.readout_used != own_vel) return fail(h, CMDGEN_ESTATE, "the evaluation and the step kernel disagree on readout_in_coord (%d, %d)", ch.a.readout_used, own_vel);
-    rc = ch.steps({noise, z_steps_out, pocket_steps_out, nullptr, nullptr}, K, [&](hipStream_t ss) {
-        cmdgen_launch_step_count(h->lay, d, c, h->work, h->work.eps_tmp, own_vel, ss);
-    });
-    if (rc) return rc;
-    // final p(x, h | z0): the last evaluation above ran at t = 0 (coef[K].w); decode
-    if (own_vel) cmdgen_launch_vel_flag(ch.a, h->work.eps_tmp, ch.s);
-    cmdgen_launch_chain_final(h->lay, d, c, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, ch.k->cog, ch.s);
-    return ch.close();
-}
-
 // ---------------------------------------------------------------------------------
-// the restrained chain: cmdgen_sample_chain's chain with a guidance term in the mean of every posterior op (kernels_restrain.hip holds
-// the definition).  The slot's table block is: the posterior rows | the guide rows (sigma_t, alpha_t, 0, 0; n_steps + 1 of them, the
-// last unused) | r_c, k_c, scale, max_shift, guide_below, 0, 0, 0 | the CSR offsets [B + 1] | the records sorted by sample - so whatever
-// changes the guidance prepares the slot again and drops its captured steps.
+// the parts of the sampling chains, each with its plan (checked) and its section of the slot's table block.  The block of a kind is: the
+// posterior rows, or with GIVEN rows the edit plan's tables (coef | coef2 | iop) | with GROUPS the group tables | the tail of the steering
+// part, on a row boundary: the GUIDE's (kernels_restrain.hip holds the definition: a guidance term in the mean of every posterior op, or
+// with given rows in op A; once per sample, or with groups once per group on the shared latent) or the SETS' (kernels_diverse.hip: a term
+// that pushes the samples of a set apart).  Whatever changes a part therefore prepares the slot again and drops its captured steps.
 // ---------------------------------------------------------------------------------
 static_assert(sizeof(cmdgen_restraint) == sizeof(RestraintRec) && sizeof(RestraintRec) == 10 * sizeof(float), "the public record is the kernels'");
 static_assert(CMDGEN_RESTRAINT_POSITION == RK_POSITION && CMDGEN_RESTRAINT_DISTANCE == RK_DISTANCE && CMDGEN_RESTRAINT_EXCLUSION == RK_EXCLUSION &&
@@ -1041,148 +1032,38 @@ extern "C" int cmdgen_set_guide_table(cmdgen_handle* h, int32_t K, const float* 
     return CMDGEN_OK;
 }
 
-// who the records of a restraint list belong to (cmdgen_restraint::sample): the layout's samples, or the groups of a multi-pocket call
-struct RestraintOwners {
-    const char* one; const char* whose;              // "sample", "the layout's" | "group", "the call's"
-    std::vector<long long> nphar;                    // points of every owner
-};
-// the restraint arguments of a restrained chain, checked (step_lds: the step kernel's LDS for this layout); rstart [owners + 1]: the CSR
-// offsets, rec: the records sorted by owner, the fields a kind does not read zeroed
-static int check_restraint_list(cmdgen_handle* h, const RestraintOwners& own, const cmdgen_restraint* restraints_host, int64_t n_restraints,
-                                float clash_radius, float clash_k, float scale, float max_shift, float guide_below, size_t step_lds,
-                                std::vector<int>& rstart, std::vector<cmdgen_restraint>& rec) {
-    if (n_restraints < 0 || (n_restraints > 0 && !restraints_host)) return fail(h, CMDGEN_EINVAL, "n_restraints=%lld without a restraint list", (long long)n_restraints);
-    auto ok = [](float v) { return std::isfinite(v) && v >= 0.f; };
-    if (!ok(clash_radius) || !ok(clash_k)) return fail(h, CMDGEN_EINVAL, "clash_radius=%g, clash_k=%g must be finite and >= 0", (double)clash_radius, (double)clash_k);
-    if (!ok(scale)) return fail(h, CMDGEN_EINVAL, "scale=%g must be finite and >= 0", (double)scale);
-    if (!(std::isfinite(max_shift) && max_shift > 0.f)) return fail(h, CMDGEN_EINVAL, "max_shift=%g must be finite and > 0", (double)max_shift);
-    if (!(guide_below >= 0.f && guide_below <= 1.f)) return fail(h, CMDGEN_EINVAL, "guide_below=%g must be in [0, 1]", (double)guide_below);
-    const int B = (int)own.nphar.size();
-    rstart.assign((size_t)B + 1, 0);
-    for (int64_t r = 0; r < n_restraints; ++r) {
-        const cmdgen_restraint& q = restraints_host[r];
-        const long long ri = (long long)r;
-        if (q.kind != RK_POSITION && q.kind != RK_DISTANCE && q.kind != RK_EXCLUSION) return fail(h, CMDGEN_EINVAL, "restraint %lld: unknown kind %d", ri, q.kind);
-        if (q.sample < 0 || q.sample >= B) return fail(h, CMDGEN_EINVAL, "restraint %lld: %s %d outside %s %d %ss", ri, own.one, q.sample, own.whose, B, own.one);
-        const long long nl = own.nphar[(size_t)q.sample];
-        if (q.kind != RK_EXCLUSION && (q.i < 0 || q.i >= nl)) return fail(h, CMDGEN_EINVAL, "restraint %lld: point %d, %s %d has %lld points", ri, q.i, own.one, q.sample, nl);
-        if (q.kind == RK_DISTANCE) {
-            if (q.j < 0 || q.j >= nl) return fail(h, CMDGEN_EINVAL, "restraint %lld: point %d, %s %d has %lld points", ri, q.j, own.one, q.sample, nl);
-            if (q.i == q.j) return fail(h, CMDGEN_EINVAL, "restraint %lld: a distance between point %d and itself (i == j)", ri, q.i);
-            if (!ok(q.a) || !ok(q.b)) return fail(h, CMDGEN_EINVAL, "restraint %lld: lo=%g, hi=%g must be finite and >= 0", ri, (double)q.a, (double)q.b);
-            if (q.a > q.b) return fail(h, CMDGEN_EINVAL, "restraint %lld: lo=%g > hi=%g", ri, (double)q.a, (double)q.b);
-        } else {
-            if (!ok(q.a)) return fail(h, CMDGEN_EINVAL, "restraint %lld: radius=%g must be finite and >= 0", ri, (double)q.a);
-            if (!std::isfinite(q.c[0]) || !std::isfinite(q.c[1]) || !std::isfinite(q.c[2])) return fail(h, CMDGEN_EINVAL, "restraint %lld: a non-finite centre", ri);
-        }
-        if (!ok(q.k)) return fail(h, CMDGEN_EINVAL, "restraint %lld: k=%g must be finite and >= 0", ri, (double)q.k);
-        if (++rstart[(size_t)q.sample + 1] > CMDGEN_MAX_RESTRAINTS)
-            return fail(h, CMDGEN_EINVAL, "%s %d has more than %d restraints", own.one, q.sample, CMDGEN_MAX_RESTRAINTS);
-    }
-    if (step_lds > PLAN_RESTRAINED_LDS_MAX)
-        return fail(h, CMDGEN_EINVAL, "a sample has %d nodes: the restrained step keeps a sample's positions, z and guidance terms in LDS (64 KiB)", h->lay.max_n);
-    for (int b = 0; b < B; ++b) rstart[(size_t)b + 1] += rstart[b];
-    rec.assign((size_t)n_restraints, cmdgen_restraint{});
-    {
-        std::vector<int> at(rstart.begin(), rstart.end() - 1);
-        for (int64_t r = 0; r < n_restraints; ++r) {             // stable: a sample's restraints keep their list order
-            cmdgen_restraint q = restraints_host[r];
-            if (q.kind == RK_EXCLUSION) { q.i = 0; q.j = 0; }
-            if (q.kind == RK_POSITION) q.j = 0;
-            if (q.kind != RK_DISTANCE) q.b = 0.f;
-            if (q.kind == RK_DISTANCE) q.c[0] = q.c[1] = q.c[2] = 0.f;
-            rec[(size_t)at[q.sample]++] = q;                     // (fields a kind does not read are zeroed: they are part of the slot's key)
-        }
-    }
-    return 0;
-}
-// ... of cmdgen_restrained_chain and cmdgen_restrained_edit_chain: the records belong to the layout's samples
-static int check_restraints(cmdgen_handle* h, const cmdgen_restraint* restraints_host, int64_t n_restraints, float clash_radius, float clash_k,
-                            float scale, float max_shift, float guide_below, size_t step_lds, std::vector<int>& rstart,
-                            std::vector<cmdgen_restraint>& rec) {
-    const RestraintOwners own{"sample", "the layout's", std::vector<long long>(h->cur_nphar.begin(), h->cur_nphar.end())};
-    return check_restraint_list(h, own, restraints_host, n_restraints, clash_radius, clash_k, scale, max_shift, guide_below, step_lds, rstart, rec);
-}
-
-// The guidance tail of a table block, on a row boundary (group tables in front of it are padded to four floats): one guide row (sigma_t,
-// alpha_t, 0, 0) per op, s_of[i] the level op i goes to (t = s + 1), then `spare` unused rows | par: r_c, k_c, scale, max_shift,
-// guide_below, then 0, 0, 0 | rstart [owners + 1] | rec.  alloc_restrain_part points a RestrainBuf at it.
-static void append_guidance(const cmdgen_handle* h, TableBlock& t, int K, const std::vector<int>& s_of, int spare, const float (&par5)[5],
-                            const std::vector<int>& rstart, const std::vector<cmdgen_restraint>& rec) {
-    std::vector<float> sa;                           // [K][2], row K - 1 - s for the op that goes to level s
-    if (h->user_guide_K == K) sa = h->user_guide; else build_guide_table(h->gamma, h->cfg.timesteps, K, sa);
-    std::vector<float>& tables = t.f;
-    const size_t c0 = (tables.size() + 3) / 4 * 4, n_rows = s_of.size() + (size_t)spare;
-    t.guide = c0; t.guide_rows = (int)n_rows; t.owners = (int)rstart.size() - 1;
-    tables.resize(c0 + n_rows * 4 + 8 + rstart.size() + rec.size() * 10, 0.f);
-    float* g = tables.data() + c0;
-    for (size_t i = 0; i < s_of.size(); ++i) {
-        const size_t row = (size_t)(K - 1 - s_of[i]);
-        g[4 * i] = sa[2 * row]; g[4 * i + 1] = sa[2 * row + 1];
-    }
-    float* par = g + n_rows * 4;
-    memcpy(par, par5, sizeof par5);
-    float* const csr = par + 8;
-    memcpy(csr, rstart.data(), rstart.size() * sizeof(int));
-    if (!rec.empty()) memcpy(csr + rstart.size(), rec.data(), rec.size() * sizeof(cmdgen_restraint));
-}
-
-// the op -> level map of a chain without jumps, for append_guidance: op i of K goes to level K - 1 - i
+// the op -> level map of a chain without jumps, for append_guide_rows: op i of K goes to level K - 1 - i
 static std::vector<int> levels_down(int K) {
     std::vector<int> s_of((size_t)K);
     for (int i = 0; i < K; ++i) s_of[(size_t)i] = K - 1 - i;
     return s_of;
 }
 
-extern "C" int cmdgen_restrained_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot, int32_t timesteps,
-                                       const cmdgen_restraint* restraints_host, int64_t n_restraints,
-                                       float clash_radius, float clash_k, float scale, float max_shift, float guide_below,
-                                       const float* noise, uint64_t seed, const int64_t* pocket_ids_host,
-                                       float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
-                                       float* energy_out, float* op_energy_out, int32_t use_graph, cmdgen_stream stream) {
-    int rc = check_ready(h); if (rc) return rc;
-    if (!pocket_x || !pocket_onehot || !xh_phar_out || !xh_pocket_out || !energy_out) return fail(h, CMDGEN_EINVAL, "null device pointer");
-    const int K = timesteps;
-    rc = check_timesteps(h, K); if (rc) return rc;
-    rc = refuse_joint_no_com(h, "the restrained chain", kPocketDiffuses, ": the guidance frame follows the centre-of-mass projections", CMDGEN_EINVAL);
-    if (rc) return rc;
-    std::vector<int> rstart; std::vector<cmdgen_restraint> rec;
-    rc = check_restraints(h, restraints_host, n_restraints, clash_radius, clash_k, scale, max_shift, guide_below,
-                          plan_restrained_step_lds(h->lay.max_n, h->dims.P), rstart, rec);
-    if (rc) return rc;
-    TableBlock tables = posterior_rows(step_table(h, K));
-    append_guidance(h, tables, K, levels_down(K), 1, {clash_radius, clash_k, scale, max_shift, guide_below}, rstart, rec);
-    Chain ch;
-    rc = ch.open(h, CHAIN_RESTRAINED, tables, K, alloc_sampling, pocket_ids_host, noise, seed, z_steps_out, pocket_steps_out, use_graph, stream); if (rc) return rc;
-    const Dims& d = h->dims;
-    const ChainBuf& c = ch.c;
-    RestrainBuf rb = ch.k->restr;
-    rb.op_energy = op_energy_out;
-    cmdgen_launch_chain_init(h->lay, d, c, pocket_x, pocket_onehot, ch.s);
-    cmdgen_launch_restrain_prep(h->lay, d, rb, pocket_x, ch.s);
-    // the evaluations are the plain chain's, with or without k_readout (cmdgen_sample_chain: readout_mode); the step kernel has both forms
-    ch.a.plain_chain = 1;
-    const int own_vel = readout_mode(ch.a, c.state, nullptr, nullptr, nullptr);
-    ch.start(true);                                  // evaluation 0 (t = 1)
-    if (ch.a.readout_used != own_vel) return fail(h, CMDGEN_ESTATE, "the evaluation and the step kernel disagree on readout_in_coord (%d, %d)", ch.a.readout_used, own_vel);
-    rc = ch.steps({noise, z_steps_out, pocket_steps_out, op_energy_out, nullptr}, K, [&](hipStream_t ss) {
-        cmdgen_launch_restrained_step_count(h->lay, d, c, rb, h->work, h->work.eps_tmp, own_vel, ss);
-    });
-    if (rc) return rc;
-    if (own_vel) cmdgen_launch_vel_flag(ch.a, h->work.eps_tmp, ch.s);
-    cmdgen_launch_chain_final(h->lay, d, c, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, ch.k->cog, ch.s);
-    cmdgen_launch_restrain_energy(h->lay, d, rb, xh_phar_out, xh_pocket_out, energy_out, ch.s);
-    return ch.close();
+// The head of a steering tail (the guide's or the sets'), on a row boundary (group tables in front of it are padded to four floats): one
+// guide row (sigma_t, alpha_t, 0, 0) per op, s_of[i] the level op i goes to (t = s + 1), then `spare` unused rows | par5, then 0, 0, 0 |
+// `behind` zeroed floats for the part's own tables.  Records the rows in t.guide_rows -> the offset of the tail, and of what lies behind
+static size_t append_guide_rows(const cmdgen_handle* h, TableBlock& t, int K, const std::vector<int>& s_of, int spare, const float (&par5)[5],
+                                size_t behind, size_t* own) {
+    std::vector<float> sa;                           // [K][2], row K - 1 - s for the op that goes to level s
+    if (h->user_guide_K == K) sa = h->user_guide; else build_guide_table(h->gamma, h->cfg.timesteps, K, sa);
+    const size_t c0 = (t.f.size() + 3) / 4 * 4, n_rows = s_of.size() + (size_t)spare;
+    t.guide_rows = (int)n_rows;
+    t.f.resize(c0 + n_rows * 4 + 8 + behind, 0.f);
+    float* g = t.f.data() + c0;
+    for (size_t i = 0; i < s_of.size(); ++i) {
+        const size_t row = (size_t)(K - 1 - s_of[i]);
+        g[4 * i] = sa[2 * row]; g[4 * i + 1] = sa[2 * row + 1];
+    }
+    memcpy(g + n_rows * 4, par5, sizeof par5);
+    *own = c0 + n_rows * 4 + 8;
+    return c0;
 }
 
-// ---------------------------------------------------------------------------------
-// the multi-pocket chain: one latent per GROUP of consecutive samples (kernels_multi.hip; the ops, the draw layout and the
-// Philox counters are in include/cmdgen_hip.h).  The evaluations are the ordinary ones over the member samples.
-// ---------------------------------------------------------------------------------
+// ---- the groups part: one latent per GROUP of consecutive samples (kernels_multi.hip; the ops, the draw layout and the Philox counters
+// are in include/cmdgen_hip.h).  The evaluations are the ordinary ones over the member samples.
 static_assert(CMDGEN_MAX_GROUP == MAX_GROUP, "the public bound and the kernels' agree");
 
-// the group tables of a call, per member (GroupTab), checked: what cmdgen_multi_pocket_chain, cmdgen_multi_edit_chain and
-// cmdgen_multi_score_chain refuse alike
+// the group tables of a call, per member (GroupTab), checked: what the sampling and the scoring chains with groups refuse alike
 struct GroupPlan {
     std::vector<int> first, size, ubase, gfirst;
     std::vector<int64_t> gid;
@@ -1235,108 +1116,91 @@ static void append_group_tables(TableBlock& t, const GroupPlan& p, const float* 
 }
 // the slot's group tables with the call's counts
 static GroupTab group_tab(const ChainSlot& k, const GroupPlan& p) { GroupTab gt = k.groups; gt.G = p.G; gt.Nu = (int)p.Nu; return gt; }
-// the restraint arguments of the restrained multi-pocket chains, checked as check_restraints does: the records belong to the call's groups
-// (the step keeps its unguided parent's LDS, which build_group_plan has checked, and the guide kernel less)
-static int check_group_restraints(cmdgen_handle* h, const GroupPlan& gp, const cmdgen_restraint* restraints_host, int64_t n_restraints,
-                                  float clash_radius, float clash_k, float scale, float max_shift, float guide_below, std::vector<int>& rstart,
-                                  std::vector<cmdgen_restraint>& rec) {
-    RestraintOwners own{"group", "the call's", {}};
-    for (int g = 0; g < gp.G; ++g) own.nphar.push_back((long long)h->cur_nphar[(size_t)gp.gfirst[g]]);
-    return check_restraint_list(h, own, restraints_host, n_restraints, clash_radius, clash_k, scale, max_shift, guide_below, 0, rstart, rec);
+
+// ---- the guide part: restraints, owned (cmdgen_restraint::sample) by the layout's samples or, in a call with groups, by its groups
+// The restraint arguments of a restrained chain, checked (gp: the call's groups, or null; par5: clash_radius, clash_k, scale, max_shift,
+// guide_below; step_lds: the step kernel's LDS for this layout - 0 with groups, where the step keeps its unguided parent's LDS, which
+// build_group_plan has checked, and the guide kernel less).  rstart [owners + 1]: the CSR offsets, rec: the records sorted by owner, the
+// fields a kind does not read zeroed
+static int check_restraints(cmdgen_handle* h, const GroupPlan* gp, const cmdgen_restraint* restraints_host, int64_t n_restraints,
+                            const float (&par5)[5], size_t step_lds, std::vector<int>& rstart, std::vector<cmdgen_restraint>& rec) {
+    const float clash_radius = par5[0], clash_k = par5[1], scale = par5[2], max_shift = par5[3], guide_below = par5[4];
+    const char *one = "sample", *whose = "the layout's";
+    std::vector<long long> nphar(h->cur_nphar.begin(), h->cur_nphar.end());          // points of every owner
+    if (gp) {
+        one = "group"; whose = "the call's";
+        nphar.clear();
+        for (int g = 0; g < gp->G; ++g) nphar.push_back((long long)h->cur_nphar[(size_t)gp->gfirst[g]]);
+    }
+    if (n_restraints < 0 || (n_restraints > 0 && !restraints_host)) return fail(h, CMDGEN_EINVAL, "n_restraints=%lld without a restraint list", (long long)n_restraints);
+    auto ok = [](float v) { return std::isfinite(v) && v >= 0.f; };
+    if (!ok(clash_radius) || !ok(clash_k)) return fail(h, CMDGEN_EINVAL, "clash_radius=%g, clash_k=%g must be finite and >= 0", (double)clash_radius, (double)clash_k);
+    if (!ok(scale)) return fail(h, CMDGEN_EINVAL, "scale=%g must be finite and >= 0", (double)scale);
+    if (!(std::isfinite(max_shift) && max_shift > 0.f)) return fail(h, CMDGEN_EINVAL, "max_shift=%g must be finite and > 0", (double)max_shift);
+    if (!(guide_below >= 0.f && guide_below <= 1.f)) return fail(h, CMDGEN_EINVAL, "guide_below=%g must be in [0, 1]", (double)guide_below);
+    const int B = (int)nphar.size();
+    rstart.assign((size_t)B + 1, 0);
+    for (int64_t r = 0; r < n_restraints; ++r) {
+        const cmdgen_restraint& q = restraints_host[r];
+        const long long ri = (long long)r;
+        if (q.kind != RK_POSITION && q.kind != RK_DISTANCE && q.kind != RK_EXCLUSION) return fail(h, CMDGEN_EINVAL, "restraint %lld: unknown kind %d", ri, q.kind);
+        if (q.sample < 0 || q.sample >= B) return fail(h, CMDGEN_EINVAL, "restraint %lld: %s %d outside %s %d %ss", ri, one, q.sample, whose, B, one);
+        const long long nl = nphar[(size_t)q.sample];
+        if (q.kind != RK_EXCLUSION && (q.i < 0 || q.i >= nl)) return fail(h, CMDGEN_EINVAL, "restraint %lld: point %d, %s %d has %lld points", ri, q.i, one, q.sample, nl);
+        if (q.kind == RK_DISTANCE) {
+            if (q.j < 0 || q.j >= nl) return fail(h, CMDGEN_EINVAL, "restraint %lld: point %d, %s %d has %lld points", ri, q.j, one, q.sample, nl);
+            if (q.i == q.j) return fail(h, CMDGEN_EINVAL, "restraint %lld: a distance between point %d and itself (i == j)", ri, q.i);
+            if (!ok(q.a) || !ok(q.b)) return fail(h, CMDGEN_EINVAL, "restraint %lld: lo=%g, hi=%g must be finite and >= 0", ri, (double)q.a, (double)q.b);
+            if (q.a > q.b) return fail(h, CMDGEN_EINVAL, "restraint %lld: lo=%g > hi=%g", ri, (double)q.a, (double)q.b);
+        } else {
+            if (!ok(q.a)) return fail(h, CMDGEN_EINVAL, "restraint %lld: radius=%g must be finite and >= 0", ri, (double)q.a);
+            if (!std::isfinite(q.c[0]) || !std::isfinite(q.c[1]) || !std::isfinite(q.c[2])) return fail(h, CMDGEN_EINVAL, "restraint %lld: a non-finite centre", ri);
+        }
+        if (!ok(q.k)) return fail(h, CMDGEN_EINVAL, "restraint %lld: k=%g must be finite and >= 0", ri, (double)q.k);
+        if (++rstart[(size_t)q.sample + 1] > CMDGEN_MAX_RESTRAINTS)
+            return fail(h, CMDGEN_EINVAL, "%s %d has more than %d restraints", one, q.sample, CMDGEN_MAX_RESTRAINTS);
+    }
+    if (step_lds > PLAN_RESTRAINED_LDS_MAX)
+        return fail(h, CMDGEN_EINVAL, "a sample has %d nodes: the restrained step keeps a sample's positions, z and guidance terms in LDS (64 KiB)", h->lay.max_n);
+    for (int b = 0; b < B; ++b) rstart[(size_t)b + 1] += rstart[b];
+    rec.assign((size_t)n_restraints, cmdgen_restraint{});
+    {
+        std::vector<int> at(rstart.begin(), rstart.end() - 1);
+        for (int64_t r = 0; r < n_restraints; ++r) {             // stable: an owner's restraints keep their list order
+            cmdgen_restraint q = restraints_host[r];
+            if (q.kind == RK_EXCLUSION) { q.i = 0; q.j = 0; }
+            if (q.kind == RK_POSITION) q.j = 0;
+            if (q.kind != RK_DISTANCE) q.b = 0.f;
+            if (q.kind == RK_DISTANCE) q.c[0] = q.c[1] = q.c[2] = 0.f;
+            rec[(size_t)at[q.sample]++] = q;                     // (fields a kind does not read are zeroed: they are part of the slot's key)
+        }
+    }
+    return 0;
+}
+// The guidance tail of a table block: append_guide_rows' head | rstart [owners + 1] | rec.  alloc_restrain_part points a RestrainBuf at it.
+static void append_guidance(const cmdgen_handle* h, TableBlock& t, int K, const std::vector<int>& s_of, int spare, const float (&par5)[5],
+                            const std::vector<int>& rstart, const std::vector<cmdgen_restraint>& rec) {
+    size_t own;
+    t.guide = append_guide_rows(h, t, K, s_of, spare, par5, rstart.size() + rec.size() * 10, &own);
+    t.owners = (int)rstart.size() - 1;
+    float* const csr = t.f.data() + own;
+    memcpy(csr, rstart.data(), rstart.size() * sizeof(int));
+    if (!rec.empty()) memcpy(csr + rstart.size(), rec.data(), rec.size() * sizeof(cmdgen_restraint));
 }
 
-extern "C" int cmdgen_multi_pocket_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
-                                         int64_t n_groups, const int64_t* group_size_host, const float* weight_host,
-                                         int32_t timesteps, const float* noise, uint64_t seed, const int64_t* group_ids_host,
-                                         float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
-                                         int32_t use_graph, cmdgen_stream stream) {
-    int rc = check_ready(h); if (rc) return rc;
-    rc = refuse_joint_no_com(h, "the multi-pocket chain", kPocketDiffuses); if (rc) return rc;
-    if (!pocket_x || !pocket_onehot || !group_size_host || !weight_host || !xh_phar_out || !xh_pocket_out)
-        return fail(h, CMDGEN_EINVAL, "null pointer");
-    const int K = timesteps;
-    rc = check_timesteps(h, K); if (rc) return rc;
-    GroupPlan gp;
-    rc = build_group_plan(h, n_groups, group_size_host, weight_host, group_ids_host, gp); if (rc) return rc;
-    TableBlock tables = posterior_rows(step_table(h, K));
-    append_group_tables(tables, gp, weight_host, h->lay.B);
-    Chain ch;
-    rc = ch.open(h, CHAIN_MULTI, tables, K, alloc_sampling, gp.gid.data(), noise, seed, z_steps_out, pocket_steps_out, use_graph, stream); if (rc) return rc;
-    const Dims& d = h->dims;
-    const ChainBuf& c = ch.c;
-    const GroupTab gt = group_tab(*ch.k, gp);
-    cmdgen_launch_multi_init(h->lay, d, c, gt, pocket_x, pocket_onehot, ch.s);
-    ch.start(true);                                  // evaluation 0 (t = 1)
-    // the group tables are slot buffers (a changed grouping or weight prepares the slot again and drops its graph); the group ids are
-    // uploaded per call, like the pocket ids of the other chains
-    rc = ch.steps({noise, z_steps_out, pocket_steps_out, nullptr, nullptr}, K, [&](hipStream_t ss) {
-        cmdgen_launch_multi_step_count(h->lay, d, c, gt, h->work, h->work.eps_tmp, ss);
-    });
-    if (rc) return rc;
-    cmdgen_launch_multi_final(h->lay, d, c, gt, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, ch.k->cog, ch.s);
-    return ch.close();
-}
-
-// ---------------------------------------------------------------------------------
-// the restrained multi-pocket chain: cmdgen_multi_pocket_chain's chain with cmdgen_restrained_chain's guidance on the shared latent, once
-// per GROUP (kernels_restrain.hip, "The restrained MULTI-POCKET chain", holds the definition).  The slot's table block is: the posterior
-// rows | the group tables, padded to a multiple of four floats | the guidance tail with CSR offsets [G + 1] and the records sorted by
-// group - so a changed grouping, weight, restraint or scalar prepares the slot again and drops its captured steps.
-// ---------------------------------------------------------------------------------
-extern "C" int cmdgen_multi_restrained_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
-                                             int64_t n_groups, const int64_t* group_size_host, const float* weight_host, int32_t timesteps,
-                                             const cmdgen_restraint* restraints_host, int64_t n_restraints,
-                                             float clash_radius, float clash_k, float scale, float max_shift, float guide_below,
-                                             const float* noise, uint64_t seed, const int64_t* group_ids_host,
-                                             float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
-                                             float* energy_out, float* op_energy_out, int32_t use_graph, cmdgen_stream stream) {
-    int rc = check_ready(h); if (rc) return rc;
-    rc = refuse_joint_no_com(h, "the restrained multi-pocket chain", kPocketDiffuses, ": the guidance frame follows the centre-of-mass projections");
-    if (rc) return rc;
-    if (!pocket_x || !pocket_onehot || !group_size_host || !weight_host || !xh_phar_out || !xh_pocket_out || !energy_out)
-        return fail(h, CMDGEN_EINVAL, "null pointer");
-    const int K = timesteps;
-    rc = check_timesteps(h, K); if (rc) return rc;
-    GroupPlan gp;
-    rc = build_group_plan(h, n_groups, group_size_host, weight_host, group_ids_host, gp); if (rc) return rc;
-    std::vector<int> rstart; std::vector<cmdgen_restraint> rec;
-    rc = check_group_restraints(h, gp, restraints_host, n_restraints, clash_radius, clash_k, scale, max_shift, guide_below, rstart, rec);
-    if (rc) return rc;
-    TableBlock tables = posterior_rows(step_table(h, K));
-    append_group_tables(tables, gp, weight_host, h->lay.B);
-    append_guidance(h, tables, K, levels_down(K), 1, {clash_radius, clash_k, scale, max_shift, guide_below}, rstart, rec);
-    Chain ch;
-    rc = ch.open(h, CHAIN_MULTI_RESTRAINED, tables, K, alloc_sampling, gp.gid.data(), noise, seed, z_steps_out, pocket_steps_out, use_graph, stream);
-    if (rc) return rc;
-    const Dims& d = h->dims;
-    const ChainBuf& c = ch.c;
-    const GroupTab gt = group_tab(*ch.k, gp);
-    RestrainBuf rb = ch.k->restr;
-    rb.op_energy = op_energy_out;
-    float* const gd = ch.k->guide_d;
-    cmdgen_launch_multi_init(h->lay, d, c, gt, pocket_x, pocket_onehot, ch.s);
-    cmdgen_launch_restrain_prep(h->lay, d, rb, pocket_x, ch.s);  // com(P_in) of every member; the guidance reads the first member's
-    ch.start(true);                                  // evaluation 0 (t = 1)
-    rc = ch.steps({noise, z_steps_out, pocket_steps_out, op_energy_out, nullptr}, K, [&](hipStream_t ss) {
-        cmdgen_launch_multi_restrained_step(h->lay, d, c, gt, rb, h->work, h->work.eps_tmp, gd, ss);
-    });
-    if (rc) return rc;
-    cmdgen_launch_multi_final(h->lay, d, c, gt, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, ch.k->cog, ch.s);
-    cmdgen_launch_multi_restrain_energy(h->lay, d, gt, rb, xh_phar_out, xh_pocket_out, energy_out, ch.s);
-    return ch.close();
-}
-
-// ---------------------------------------------------------------------------------
-// the diverse chain: cmdgen_sample_chain's chain with a term in the mean of every posterior op that pushes the samples of a SET (consecutive
-// samples: the draws for one pocket) apart (kernels_diverse.hip holds the definition).  The slot's table block is: the posterior rows | the
-// guide rows (sigma_t, alpha_t, 0, 0; n_steps + 1 of them, the last unused) | strength, width, 1 / (2 w^2), max_shift, guide_below, 0, 0, 0 |
-// per sample set_first, set_size, set_row0, set_rows - so a changed partition or scalar prepares the slot again and drops its captured steps.
-// ---------------------------------------------------------------------------------
+// ---- the sets part: the layout's samples partitioned into SETS of consecutive samples, "the draws for one pocket" (DiverseBuf).  The tail is:
+// the guide rows (sigma_t, alpha_t, 0, 0; K + 1 of them, the last unused) | strength, width, 1 / (2 w^2), max_shift, guide_below, 0, 0, 0 |
+// per sample set_first, set_size, set_row0, set_rows
 static_assert(CMDGEN_MAX_SET_ROWS == MAX_SET_ROWS, "the public bound and the kernels' agree");
 
-// the set tables of a call, per sample (DiverseBuf), checked
+// the scalars and the set tables of a call, per sample, checked
 struct SetPlan { std::vector<int> first, size, row0, rows; };
-static int build_set_plan(cmdgen_handle* h, int64_t n_sets, const int64_t* set_size_host, SetPlan& p) {
+static int build_set_plan(cmdgen_handle* h, int64_t n_sets, const int64_t* set_size_host, float strength, float width, float max_shift,
+                          float guide_below, SetPlan& p) {
+    if (!(std::isfinite(strength) && strength >= 0.f)) return fail(h, CMDGEN_EINVAL, "strength=%g must be finite and >= 0", (double)strength);
+    if (!(std::isfinite(width) && width > 0.f)) return fail(h, CMDGEN_EINVAL, "width=%g must be finite and > 0", (double)width);
+    if (!(std::isfinite(max_shift) && max_shift > 0.f)) return fail(h, CMDGEN_EINVAL, "max_shift=%g must be finite and > 0", (double)max_shift);
+    if (!(guide_below >= 0.f && guide_below <= 1.f)) return fail(h, CMDGEN_EINVAL, "guide_below=%g must be in [0, 1]", (double)guide_below);
     const int B = h->lay.B;
     if (n_sets < 1 || n_sets > B) return fail(h, CMDGEN_EINVAL, "n_sets=%lld must be in [1, batch=%d]", (long long)n_sets, B);
     p.first.resize(B); p.size.resize(B); p.row0.resize(B); p.rows.resize(B);
@@ -1361,79 +1225,15 @@ static int build_set_plan(cmdgen_handle* h, int64_t n_sets, const int64_t* set_s
         return fail(h, CMDGEN_EINVAL, "a sample has %d nodes: the diverse step keeps a sample's positions, degrees and z in LDS (64 KiB)", h->lay.max_n);
     return 0;
 }
-// The diverse tail of a table block, on a row boundary, laid out as append_guidance lays its own: K guide rows and one unused | par5, then
-// 0, 0, 0 | the four set tables, B entries each.  alloc_diverse points a DiverseBuf at it.
+// The sets' tail of a table block: append_guide_rows' head (K guide rows and one unused) | the four set tables, B entries each.
+// alloc_diverse_part points a DiverseBuf at it.
 static void append_sets(const cmdgen_handle* h, TableBlock& t, int K, const float (&par5)[5], const SetPlan& p) {
-    std::vector<float> sa;                           // [K][2], row i for op i (t = K - i)
-    if (h->user_guide_K == K) sa = h->user_guide; else build_guide_table(h->gamma, h->cfg.timesteps, K, sa);
-    const size_t B = p.first.size(), c0 = (t.f.size() + 3) / 4 * 4, n_rows = (size_t)K + 1;
-    t.sets = c0; t.guide_rows = (int)n_rows;
-    t.f.resize(c0 + n_rows * 4 + 8 + 4 * B, 0.f);
-    float* g = t.f.data() + c0;
-    for (int i = 0; i < K; ++i) { g[4 * i] = sa[2 * (size_t)i]; g[4 * i + 1] = sa[2 * (size_t)i + 1]; }
-    float* par = g + n_rows * 4;
-    memcpy(par, par5, sizeof par5);
-    float* tab = par + 8;
+    const size_t B = p.first.size();
+    size_t own;
+    t.sets = append_guide_rows(h, t, K, levels_down(K), 1, par5, 4 * B, &own);
+    float* tab = t.f.data() + own;
     memcpy(tab, p.first.data(), B * sizeof(int)); memcpy(tab + B, p.size.data(), B * sizeof(int));
     memcpy(tab + 2 * B, p.row0.data(), B * sizeof(int)); memcpy(tab + 3 * B, p.rows.data(), B * sizeof(int));
-}
-// the diverse kind's ChainAlloc: the ChainBuf, then the DiverseBuf at the tail append_sets packed and the buffers its launches hand on
-static int alloc_diverse(cmdgen_handle* h, ChainSlot& k, const TableBlock& t, const float* dev, int n_steps) {
-    int rc = alloc_chain_buf(h, k, dev); if (rc) return rc;
-    DiverseBuf& db = k.div;
-    const size_t B = (size_t)h->lay.B;
-    const float* g = dev + t.sets;
-    const float* par = g + (size_t)t.guide_rows * 4;
-    db.sa = (const float4*)g;
-    db.strength = par[0]; db.width = par[1]; db.inv2w2 = par[2]; db.max_shift = par[3]; db.guide_below = par[4];
-    const int* tab = (const int*)(par + 8);
-    db.set_first = tab; db.set_size = tab + B; db.set_row0 = tab + 2 * B; db.set_rows = tab + 3 * B;
-    db.op_overlap = nullptr;
-    rc = slot_alloc(h, k, db.pin_com, B); if (rc) return rc;
-    rc = slot_alloc(h, k, db.y, (size_t)h->lay.Nl * 3); if (rc) return rc;
-    rc = slot_alloc(h, k, db.gd, (size_t)h->lay.Nl * 3); if (rc) return rc;
-    return slot_alloc(h, k, db.po, (size_t)h->lay.Nl);
-}
-
-extern "C" int cmdgen_diverse_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot, int32_t timesteps,
-                                    int64_t n_sets, const int64_t* set_size_host,
-                                    float strength, float width, float max_shift, float guide_below,
-                                    const float* noise, uint64_t seed, const int64_t* pocket_ids_host,
-                                    float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
-                                    float* overlap_out, float* op_overlap_out, int32_t use_graph, cmdgen_stream stream) {
-    int rc = check_ready(h); if (rc) return rc;
-    if (!pocket_x || !pocket_onehot || !set_size_host || !xh_phar_out || !xh_pocket_out || !overlap_out)
-        return fail(h, CMDGEN_EINVAL, "null pointer (pocket_x, pocket_onehot, set_size_host, xh_phar_out, xh_pocket_out and overlap_out are required)");
-    const int K = timesteps;
-    rc = check_timesteps(h, K); if (rc) return rc;
-    rc = refuse_joint_no_com(h, "the diverse chain", kPocketDiffuses, ": the guidance frame follows the centre-of-mass projections", CMDGEN_EINVAL);
-    if (rc) return rc;
-    if (!(std::isfinite(strength) && strength >= 0.f)) return fail(h, CMDGEN_EINVAL, "strength=%g must be finite and >= 0", (double)strength);
-    if (!(std::isfinite(width) && width > 0.f)) return fail(h, CMDGEN_EINVAL, "width=%g must be finite and > 0", (double)width);
-    if (!(std::isfinite(max_shift) && max_shift > 0.f)) return fail(h, CMDGEN_EINVAL, "max_shift=%g must be finite and > 0", (double)max_shift);
-    if (!(guide_below >= 0.f && guide_below <= 1.f)) return fail(h, CMDGEN_EINVAL, "guide_below=%g must be in [0, 1]", (double)guide_below);
-    SetPlan sp;
-    rc = build_set_plan(h, n_sets, set_size_host, sp); if (rc) return rc;
-    TableBlock tables = posterior_rows(step_table(h, K));
-    append_sets(h, tables, K, {strength, width, 1.0f / (2.0f * (width * width)), max_shift, guide_below}, sp);
-    Chain ch;
-    rc = ch.open(h, CHAIN_DIVERSE, tables, K, alloc_diverse, pocket_ids_host, noise, seed, z_steps_out, pocket_steps_out, use_graph, stream); if (rc) return rc;
-    const Dims& d = h->dims;
-    const ChainBuf& c = ch.c;
-    DiverseBuf db = ch.k->div;
-    db.op_overlap = op_overlap_out;
-    RestrainBuf prep{};                              // k_restrain_prep fills pin_com and reads nothing else of it
-    prep.pin_com = db.pin_com;
-    cmdgen_launch_chain_init(h->lay, d, c, pocket_x, pocket_onehot, ch.s);
-    cmdgen_launch_restrain_prep(h->lay, d, prep, pocket_x, ch.s);
-    ch.start(true);                                  // evaluation 0 (t = 1); the evaluations run their own k_readout (no plain_chain)
-    rc = ch.steps({noise, z_steps_out, pocket_steps_out, op_overlap_out, nullptr}, K, [&](hipStream_t ss) {
-        cmdgen_launch_diverse_step(h->lay, d, c, db, h->work, h->work.eps_tmp, ss);
-    });
-    if (rc) return rc;
-    cmdgen_launch_chain_final(h->lay, d, c, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, ch.k->cog, ch.s);
-    cmdgen_launch_diverse_overlap(h->lay, d, db, xh_phar_out, xh_pocket_out, overlap_out, ch.s);
-    return ch.close();
 }
 
 // ---------------------------------------------------------------------------------
@@ -1580,8 +1380,9 @@ extern "C" int cmdgen_joint_chain(cmdgen_handle* h, const float* phar_x, const f
 }
 
 // ---------------------------------------------------------------------------------
-// conditional RePaint and the edit chain: ConditionalDDPM.inpaint / .edit (kernels_inpaint.hip; the op semantics and the
-// draw scheme are in include/cmdgen_hip.h).  Inpainting is the edit chain with both masks equal and start = timesteps.
+// the given part of the sampling chains, with its plan: conditional RePaint and the edit chain, ConditionalDDPM.inpaint / .edit
+// (kernels_inpaint.hip; the op semantics and the draw scheme are in include/cmdgen_hip.h; with groups the ops run on the shared latent,
+// kernels_multi.hip, the known rows and marks held once per group).  Inpainting is the edit chain with both masks equal and start = timesteps.
 // ---------------------------------------------------------------------------------
 struct InpaintPlan {
     std::vector<float> coef, coef2;     // [n_steps+1][4] (last: decode row), [n_steps][4]
@@ -1654,23 +1455,222 @@ extern "C" int cmdgen_inpaint_plan(cmdgen_handle* h, int32_t timesteps, int32_t 
     return cmdgen_edit_plan(h, timesteps, timesteps, resamplings, jump_length, n_steps, n_draws);
 }
 
-// the init launches of cmdgen_edit_chain and cmdgen_restrained_edit_chain
-static void launch_edit_init(const Chain& ch, const InpaintBuf& ip, const InpaintPlan& plan, bool from_prior, const float* pocket_x, const float* pocket_onehot,
-                             const float* phar_x, const float* phar_onehot, const float* fix_x, const float* fix_h) {
-    const cmdgen_handle* h = ch.h;
-    if (from_prior) {                                // z_T around the pocket centre
-        cmdgen_launch_chain_init(h->lay, h->dims, ch.c, pocket_x, pocket_onehot, ch.s);
-        cmdgen_launch_inpaint_prep(h->lay, h->dims, ch.c, ip, phar_x, phar_onehot, fix_x, fix_h, pocket_x, ch.s);
-    } else {                                         // part-way: z ~ q(z_start | the given rows)
-        cmdgen_launch_edit_start(h->lay, h->dims, ch.c, ip, plan.alpha_start, plan.sigma_start, phar_x, phar_onehot, fix_x, fix_h, pocket_x,
-                                 pocket_onehot, ch.s);
-    }
-}
-// the decode draw of an edit plan is its last row; the final kernels read theirs from row 1 + n_steps of `noise` (rows: phar rows per draw)
-static ChainBuf decode_buf(const ChainBuf& c, const InpaintPlan& plan, size_t rows, int P) {
+// the decode draw of a plan is its last row; the final kernels read theirs from row 1 + n_steps of `noise`: `skip` rows further with an edit
+// plan, 0 without one (rows: phar rows per draw)
+static ChainBuf decode_buf(const ChainBuf& c, int skip, size_t rows, int P) {
     ChainBuf cf = c;
-    if (c.noise) cf.noise = c.noise + (size_t)(plan.n_draws - 1 - (1 + plan.n_steps)) * rows * (3 + P);
+    if (c.noise) cf.noise = c.noise + (size_t)skip * rows * (3 + P);
     return cf;
+}
+
+// ---------------------------------------------------------------------------------
+// the nine sampling chains: what an entry received (the part names are Handle._sampling_chain's and tests/chain_kit.run_chain's; a part
+// the kind lacks is null), and their one body
+// ---------------------------------------------------------------------------------
+struct GroupsPart { int64_t n; const int64_t* size_host; const float* weight_host; };
+struct GivenPart { const float *phar_x, *phar_onehot, *fix_x, *fix_h; int start, resamplings, jump_length; };      // the rows and their plan
+struct GuidePart {
+    const cmdgen_restraint* restraints_host; int64_t n;
+    float par[5];                                    // clash_radius, clash_k, scale, max_shift, guide_below
+    float *energy_out, *op_energy_out;
+};
+struct SetsPart { int64_t n; const int64_t* size_host; float strength, width, max_shift, guide_below; float *overlap_out, *op_overlap_out; };
+struct SamplingCall {
+    ChainKind kind;
+    const char* name;                                // the kind's name as its refusal of a joint or no_com handle words it; null: the kind refuses the
+                                                     // joint model alone, by pointing at cmdgen_joint_chain (with given rows check_inpaint_args refuses both)
+    const char* no_com_why; int no_com_code;         // ... and what the kind adds for a no_com handle, with the code it returns
+    const float *pocket_x, *pocket_onehot;
+    int timesteps;
+    const float* noise; int64_t n_draws;             // (n_draws is read with given rows only: without them the schedule has timesteps + 2 draws)
+    uint64_t seed; const int64_t* ids_host;          // ids: of the pockets, or with groups of the groups
+    float *xh_phar_out, *xh_pocket_out, *z_steps_out, *pocket_steps_out;
+    int32_t use_graph; cmdgen_stream stream;
+    const GroupsPart* groups; const GivenPart* given; const GuidePart* guide; const SetsPart* sets;
+};
+static const char* const kGuideFrame = ": the guidance frame follows the centre-of-mass projections";
+static const char* const kEditGuideFrame = ": the edit chain and the guidance frame follow the centre-of-mass projections";
+
+static int sampling_chain(cmdgen_handle* h, const SamplingCall& q) {
+    const GroupsPart* const gr = q.groups; const GivenPart* const gv = q.given; const GuidePart* const gu = q.guide; const SetsPart* const se = q.sets;
+    // ---- refusals: the handle, the pointers
+    int rc = check_ready(h); if (rc) return rc;
+    if (q.name) { rc = refuse_joint_no_com(h, q.name, kPocketDiffuses, q.no_com_why, q.no_com_code); if (rc) return rc; }
+    else if (h->dims.joint) return fail(h, CMDGEN_ESTATE, "this handle is the joint model (update_pocket_coords=1): use cmdgen_joint_chain");
+    bool missing = !q.pocket_x || !q.pocket_onehot || !q.xh_phar_out || !q.xh_pocket_out;
+    const char* null_text = "null device pointer";
+    if (gr) { missing |= !gr->size_host || !gr->weight_host; null_text = "null pointer"; }
+    if (gv) missing |= !gv->phar_x || !gv->phar_onehot || !gv->fix_x || !gv->fix_h;
+    if (gu) missing |= !gu->energy_out;
+    if (se) {
+        missing |= !se->size_host || !se->overlap_out;
+        null_text = "null pointer (pocket_x, pocket_onehot, set_size_host, xh_phar_out, xh_pocket_out and overlap_out are required)";
+    }
+    if (missing) return fail(h, CMDGEN_EINVAL, "%s", null_text);
+    // ---- the plans of the parts present.  Without given rows the ops go down the K levels one by one, with one spare guide row; with them the
+    // plan says where every op goes, how many there are and where the decode draw lies
+    const int K = q.timesteps, P = h->dims.P;
+    InpaintPlan plan; GroupPlan gp; SetPlan sp;
+    std::vector<int> s_of, rstart; std::vector<cmdgen_restraint> rec;
+    int n_steps = K, spare = 1, decode_skip = 0;
+    size_t guide_lds;                                // the LDS of the guided step of this corner (check_restraints)
+    if (gv) {
+        rc = check_inpaint_args(h, K, gv->start, gv->resamplings, gv->jump_length); if (rc) return rc;
+        plan = build_inpaint_plan(h, K, gv->start, gv->resamplings, gv->jump_length);
+        rc = check_draws(h, q.noise, q.n_draws, plan.n_draws); if (rc) return rc;
+        n_steps = plan.n_steps; s_of = plan.s_of; spare = 0; decode_skip = plan.n_draws - 1 - (1 + plan.n_steps);
+        guide_lds = plan_restrained_edit_step_lds(h->lay.max_n, P);
+    } else {
+        rc = check_timesteps(h, K); if (rc) return rc;
+        s_of = levels_down(K);
+        guide_lds = plan_restrained_step_lds(h->lay.max_n, P);
+    }
+    if (gr) {
+        rc = build_group_plan(h, gr->n, gr->size_host, gr->weight_host, q.ids_host, gp); if (rc) return rc;
+        guide_lds = 0;
+    }
+    if (gu) { rc = check_restraints(h, gr ? &gp : nullptr, gu->restraints_host, gu->n, gu->par, guide_lds, rstart, rec); if (rc) return rc; }
+    if (se) { rc = build_set_plan(h, se->n, se->size_host, se->strength, se->width, se->max_shift, se->guide_below, sp); if (rc) return rc; }
+    // ---- the table block: its tables, the known rows and the marks are slot buffers (a changed plan, start, grouping, weight, restraint,
+    // partition or scalar prepares the slot again and drops its graph); the ids are uploaded per call, the caller's pointers are the graph's key
+    TableBlock tables = gv ? plan_tables(plan.coef, plan.coef2, plan.iop) : posterior_rows(step_table(h, K));
+    if (gr) append_group_tables(tables, gp, gr->weight_host, h->lay.B);
+    if (gu) append_guidance(h, tables, K, s_of, spare, gu->par, rstart, rec);
+    if (se) append_sets(h, tables, K, {se->strength, se->width, 1.0f / (2.0f * (se->width * se->width)), se->max_shift, se->guide_below}, sp);
+    Chain ch;
+    rc = ch.open(h, q.kind, tables, n_steps, alloc_sampling, gr ? gp.gid.data() : q.ids_host, q.noise, q.seed, q.z_steps_out, q.pocket_steps_out,
+                 q.use_graph, q.stream);
+    if (rc) return rc;
+    const Layout& lay = h->lay; const Dims& d = h->dims; const Work& w = h->work;
+    const ChainBuf& c = ch.c;
+    float* const eps = w.eps_tmp;
+    const hipStream_t s = ch.s;
+    // the slot's buffer of every part, completed with the call's pointers (a part the kind lacks: its empty buffer, which nothing reads)
+    const InpaintBuf ip = ch.k->inp;
+    const GroupTab gt = group_tab(*ch.k, gp);
+    RestrainBuf rb = ch.k->restr;
+    DiverseBuf db = ch.k->div;
+    float* const gd = ch.k->guide_d;
+    float* op_side = nullptr;                        // the steering part's output per op: the fourth pointer of the graph's key
+    if (gu) op_side = rb.op_energy = gu->op_energy_out;
+    if (se) { op_side = db.op_overlap = se->op_overlap_out; rb.pin_com = db.pin_com; }    // (k_restrain_prep fills pin_com and reads nothing else of rb)
+    // ---- init: z_T around the (weighted) pocket centre, or part-way z ~ q(z_start | the given rows); the known rows and marks; com(P_in)
+    const bool from_prior = !gv || gv->start == K;
+    if (gr) {
+        if (from_prior) cmdgen_launch_multi_init(lay, d, c, gt, q.pocket_x, q.pocket_onehot, s);
+        else cmdgen_launch_multi_edit_start(lay, d, c, gt, plan.alpha_start, plan.sigma_start, gv->phar_x, gv->phar_onehot, q.pocket_x, q.pocket_onehot, s);
+        // a launch of its own after the init: every member reads the projected pocket of its group's FIRST member for the offset
+        if (gv) cmdgen_launch_multi_edit_prep(lay, d, c, gt, ip, gv->phar_x, gv->phar_onehot, gv->fix_x, gv->fix_h, q.pocket_x, s);
+    } else {
+        if (from_prior) cmdgen_launch_chain_init(lay, d, c, q.pocket_x, q.pocket_onehot, s);
+        else cmdgen_launch_edit_start(lay, d, c, ip, plan.alpha_start, plan.sigma_start, gv->phar_x, gv->phar_onehot, gv->fix_x, gv->fix_h, q.pocket_x,
+                                      q.pocket_onehot, s);
+        if (gv && from_prior) cmdgen_launch_inpaint_prep(lay, d, c, ip, gv->phar_x, gv->phar_onehot, gv->fix_x, gv->fix_h, q.pocket_x, s);
+    }
+    if (gu || se) cmdgen_launch_restrain_prep(lay, d, rb, q.pocket_x, s);     // (with groups: of every member; the guidance reads the first member's)
+    // One denoising step = the posterior update fused with pass 1 of the next radius graph (the corner's step launch), then the evaluation
+    // at the new state: pass 2 of the graph (k_edge_write), k_embed, the L blocks, k_readout.  The chain is: evaluation 0, n_steps x (step +
+    // evaluation), decode.
+    // The plain and the restrained chain run their evaluations without k_readout where the plan says so (LaunchPlan::readout_in_coord): its
+    // feature part rides in the last coordinate launch, the step kernel (it has both forms) makes the velocity and the NaN flag it consumes
+    // itself, and k_vel_flag does so once in front of the decode.  Every other kind's evaluations run their own k_readout.
+    const bool plain_evals = !gr && !gv && !se;
+    int own_vel = 0;
+    if (plain_evals) {
+        ch.a.plain_chain = 1;
+        own_vel = readout_mode(ch.a, c.state, nullptr, nullptr, nullptr);     // (what the evaluations below are launched with)
+    }
+    ch.start(true);                                  // evaluation 0 (t = 1, or start / timesteps)
+    // (a step kernel that leaves X0 / ACC to an evaluation that does not take them over would leave stale positions without any error)
+    // (evaluation 0 is already queued when this returns: the chain is abandoned half issued, the handle stays usable - the next chain of any
+    // kind starts again from its init launch and k_edge_count, which rewrite everything this one left behind)
+    if (plain_evals && ch.a.readout_used != own_vel)
+        return fail(h, CMDGEN_ESTATE, "the evaluation and the step kernel disagree on readout_in_coord (%d, %d)", ch.a.readout_used, own_vel);
+    // ---- the steps: the one launcher of the corner (the adapters build no other)
+    const int corner = (se ? 8 : 0) | (gr ? 4 : 0) | (gv ? 2 : 0) | (gu ? 1 : 0);
+    rc = ch.steps({q.noise, q.z_steps_out, q.pocket_steps_out, op_side, nullptr}, n_steps, [&](hipStream_t ss) {
+        switch (corner) {
+        case 0: cmdgen_launch_step_count(lay, d, c, w, eps, own_vel, ss); break;
+        case 1: cmdgen_launch_restrained_step_count(lay, d, c, rb, w, eps, own_vel, ss); break;
+        case 2: cmdgen_launch_inpaint_step_count(lay, d, c, ip, w, eps, ss); break;
+        case 3: cmdgen_launch_restrained_edit_step_count(lay, d, c, ip, rb, w, eps, ss); break;
+        case 4: cmdgen_launch_multi_step_count(lay, d, c, gt, w, eps, ss); break;
+        case 5: cmdgen_launch_multi_restrained_step(lay, d, c, gt, rb, w, eps, gd, ss); break;
+        case 6: cmdgen_launch_multi_edit_step_count(lay, d, c, gt, ip, w, eps, ss); break;
+        case 7: cmdgen_launch_multi_restrained_edit_step(lay, d, c, gt, ip, rb, w, eps, gd, ss); break;
+        case 8: cmdgen_launch_diverse_step(lay, d, c, db, w, eps, ss); break;
+        }
+    });
+    if (rc) return rc;
+    // ---- final p(x, h | z0): the last evaluation above ran at t = 0 (the decode row's w); decode, then the steering part's report on the output
+    if (own_vel) cmdgen_launch_vel_flag(ch.a, eps, s);
+    if (gr) {
+        cmdgen_launch_multi_final(lay, d, decode_buf(c, decode_skip, (size_t)gt.Nu, P), gt, w, eps, q.xh_phar_out, q.xh_pocket_out, ch.k->cog, s);
+        if (gu) cmdgen_launch_multi_restrain_energy(lay, d, gt, rb, q.xh_phar_out, q.xh_pocket_out, gu->energy_out, s);
+    } else {
+        cmdgen_launch_chain_final(lay, d, decode_buf(c, decode_skip, (size_t)lay.Nl, P), w, eps, q.xh_phar_out, q.xh_pocket_out, ch.k->cog, s);
+        if (gu) cmdgen_launch_restrain_energy(lay, d, rb, q.xh_phar_out, q.xh_pocket_out, gu->energy_out, s);
+    }
+    if (se) cmdgen_launch_diverse_overlap(lay, d, db, q.xh_phar_out, q.xh_pocket_out, se->overlap_out, s);
+    return ch.close();
+}
+
+// the nine entries (and the inpainting alias): each packs what it received
+extern "C" int cmdgen_sample_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
+                                   int32_t timesteps, const float* noise, uint64_t seed,
+                                   const int64_t* pocket_ids_host, float* xh_phar_out, float* xh_pocket_out,
+                                   float* z_steps_out, float* pocket_steps_out, int32_t use_graph, cmdgen_stream stream) {
+    return sampling_chain(h, {CHAIN_PLAIN, nullptr, "", CMDGEN_ESTATE, pocket_x, pocket_onehot, timesteps, noise, 0, seed, pocket_ids_host, xh_phar_out,
+                              xh_pocket_out, z_steps_out, pocket_steps_out, use_graph, stream, nullptr, nullptr, nullptr, nullptr});
+}
+
+extern "C" int cmdgen_restrained_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot, int32_t timesteps,
+                                       const cmdgen_restraint* restraints_host, int64_t n_restraints,
+                                       float clash_radius, float clash_k, float scale, float max_shift, float guide_below,
+                                       const float* noise, uint64_t seed, const int64_t* pocket_ids_host,
+                                       float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                                       float* energy_out, float* op_energy_out, int32_t use_graph, cmdgen_stream stream) {
+    const GuidePart guide{restraints_host, n_restraints, {clash_radius, clash_k, scale, max_shift, guide_below}, energy_out, op_energy_out};
+    return sampling_chain(h, {CHAIN_RESTRAINED, "the restrained chain", kGuideFrame, CMDGEN_EINVAL, pocket_x, pocket_onehot, timesteps, noise, 0, seed,
+                              pocket_ids_host, xh_phar_out, xh_pocket_out, z_steps_out, pocket_steps_out, use_graph, stream, nullptr, nullptr, &guide,
+                              nullptr});
+}
+
+extern "C" int cmdgen_diverse_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot, int32_t timesteps,
+                                    int64_t n_sets, const int64_t* set_size_host,
+                                    float strength, float width, float max_shift, float guide_below,
+                                    const float* noise, uint64_t seed, const int64_t* pocket_ids_host,
+                                    float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                                    float* overlap_out, float* op_overlap_out, int32_t use_graph, cmdgen_stream stream) {
+    const SetsPart sets{n_sets, set_size_host, strength, width, max_shift, guide_below, overlap_out, op_overlap_out};
+    return sampling_chain(h, {CHAIN_DIVERSE, "the diverse chain", kGuideFrame, CMDGEN_EINVAL, pocket_x, pocket_onehot, timesteps, noise, 0, seed,
+                              pocket_ids_host, xh_phar_out, xh_pocket_out, z_steps_out, pocket_steps_out, use_graph, stream, nullptr, nullptr, nullptr,
+                              &sets});
+}
+
+extern "C" int cmdgen_multi_pocket_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
+                                         int64_t n_groups, const int64_t* group_size_host, const float* weight_host,
+                                         int32_t timesteps, const float* noise, uint64_t seed, const int64_t* group_ids_host,
+                                         float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                                         int32_t use_graph, cmdgen_stream stream) {
+    const GroupsPart groups{n_groups, group_size_host, weight_host};
+    return sampling_chain(h, {CHAIN_MULTI, "the multi-pocket chain", "", CMDGEN_ESTATE, pocket_x, pocket_onehot, timesteps, noise, 0, seed,
+                              group_ids_host, xh_phar_out, xh_pocket_out, z_steps_out, pocket_steps_out, use_graph, stream, &groups, nullptr, nullptr,
+                              nullptr});
+}
+
+extern "C" int cmdgen_multi_restrained_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
+                                             int64_t n_groups, const int64_t* group_size_host, const float* weight_host, int32_t timesteps,
+                                             const cmdgen_restraint* restraints_host, int64_t n_restraints,
+                                             float clash_radius, float clash_k, float scale, float max_shift, float guide_below,
+                                             const float* noise, uint64_t seed, const int64_t* group_ids_host,
+                                             float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                                             float* energy_out, float* op_energy_out, int32_t use_graph, cmdgen_stream stream) {
+    const GroupsPart groups{n_groups, group_size_host, weight_host};
+    const GuidePart guide{restraints_host, n_restraints, {clash_radius, clash_k, scale, max_shift, guide_below}, energy_out, op_energy_out};
+    return sampling_chain(h, {CHAIN_MULTI_RESTRAINED, "the restrained multi-pocket chain", kGuideFrame, CMDGEN_ESTATE, pocket_x, pocket_onehot, timesteps,
+                              noise, 0, seed, group_ids_host, xh_phar_out, xh_pocket_out, z_steps_out, pocket_steps_out, use_graph, stream, &groups,
+                              nullptr, &guide, nullptr});
 }
 
 extern "C" int cmdgen_edit_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
@@ -1679,28 +1679,9 @@ extern "C" int cmdgen_edit_chain(cmdgen_handle* h, const float* pocket_x, const 
                                  const float* noise, int64_t n_draws, uint64_t seed, const int64_t* pocket_ids_host,
                                  float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
                                  int32_t use_graph, cmdgen_stream stream) {
-    int rc = check_ready(h); if (rc) return rc;
-    rc = check_inpaint_args(h, timesteps, start, resamplings, jump_length); if (rc) return rc;
-    if (!pocket_x || !pocket_onehot || !phar_x || !phar_onehot || !fix_x || !fix_h || !xh_phar_out || !xh_pocket_out)
-        return fail(h, CMDGEN_EINVAL, "null device pointer");
-    const InpaintPlan plan = build_inpaint_plan(h, timesteps, start, resamplings, jump_length);
-    rc = check_draws(h, noise, n_draws, plan.n_draws); if (rc) return rc;
-    TableBlock tables = plan_tables(plan.coef, plan.coef2, plan.iop);   // coef (n_steps + 1 rows) | coef2 | iop (n_steps each)
-    Chain ch;
-    rc = ch.open(h, CHAIN_INPAINT, tables, plan.n_steps, alloc_sampling, pocket_ids_host, noise, seed, z_steps_out, pocket_steps_out, use_graph, stream); if (rc) return rc;
-    const Dims& d = h->dims;
-    const ChainBuf& c = ch.c;
-    const InpaintBuf ip = ch.k->inp;
-    launch_edit_init(ch, ip, plan, start == timesteps, pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h);
-    ch.start(true);                                  // evaluation 0 (t = start / timesteps)
-    // the tables (their rows differ with start and with the plan), the known rows and the masks are slot buffers: a new plan or start
-    // prepares the slot again; the caller's pointers are the key
-    rc = ch.steps({noise, z_steps_out, pocket_steps_out, nullptr, nullptr}, plan.n_steps, [&](hipStream_t ss) {
-        cmdgen_launch_inpaint_step_count(h->lay, d, c, ip, h->work, h->work.eps_tmp, ss);
-    });
-    if (rc) return rc;
-    cmdgen_launch_chain_final(h->lay, d, decode_buf(c, plan, (size_t)h->lay.Nl, d.P), h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, ch.k->cog, ch.s);
-    return ch.close();
+    const GivenPart given{phar_x, phar_onehot, fix_x, fix_h, start, resamplings, jump_length};
+    return sampling_chain(h, {CHAIN_INPAINT, nullptr, "", CMDGEN_ESTATE, pocket_x, pocket_onehot, timesteps, noise, n_draws, seed, pocket_ids_host,
+                              xh_phar_out, xh_pocket_out, z_steps_out, pocket_steps_out, use_graph, stream, nullptr, &given, nullptr, nullptr});
 }
 
 extern "C" int cmdgen_inpaint_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
@@ -1714,12 +1695,6 @@ extern "C" int cmdgen_inpaint_chain(cmdgen_handle* h, const float* pocket_x, con
                              pocket_steps_out, use_graph, stream);
 }
 
-// ---------------------------------------------------------------------------------
-// the restrained edit chain: cmdgen_edit_chain's chain with cmdgen_restrained_chain's guidance in op A (k_restrained_edit_step_count,
-// kernels_restrain.hip, holds the definition).  The slot's table block is the edit plan's tables (coef | coef2 | iop), then one guide row
-// per OP (sigma_t, alpha_t, 0, 0), r_c, k_c, scale, max_shift, guide_below, 0, 0, 0, the CSR offsets [B + 1] and the records sorted by
-// sample - so a changed plan, start, restraint or scalar prepares the slot again and drops its captured steps.
-// ---------------------------------------------------------------------------------
 extern "C" int cmdgen_restrained_edit_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
                                             const float* phar_x, const float* phar_onehot, const float* fix_x, const float* fix_h,
                                             int32_t timesteps, int32_t start, int32_t resamplings, int32_t jump_length,
@@ -1728,45 +1703,13 @@ extern "C" int cmdgen_restrained_edit_chain(cmdgen_handle* h, const float* pocke
                                             const cmdgen_restraint* restraints_host, int64_t n_restraints,
                                             float clash_radius, float clash_k, float scale, float max_shift, float guide_below,
                                             float* energy_out, float* op_energy_out, int32_t use_graph, cmdgen_stream stream) {
-    int rc = check_ready(h); if (rc) return rc;
-    rc = refuse_joint_no_com(h, "the restrained edit chain", kPocketDiffuses, ": the edit chain and the guidance frame follow the centre-of-mass projections");
-    if (rc) return rc;
-    rc = check_inpaint_args(h, timesteps, start, resamplings, jump_length); if (rc) return rc;
-    if (!pocket_x || !pocket_onehot || !phar_x || !phar_onehot || !fix_x || !fix_h || !xh_phar_out || !xh_pocket_out || !energy_out)
-        return fail(h, CMDGEN_EINVAL, "null device pointer");
-    std::vector<int> rstart; std::vector<cmdgen_restraint> rec;
-    rc = check_restraints(h, restraints_host, n_restraints, clash_radius, clash_k, scale, max_shift, guide_below,
-                          plan_restrained_edit_step_lds(h->lay.max_n, h->dims.P), rstart, rec);
-    if (rc) return rc;
-    const InpaintPlan plan = build_inpaint_plan(h, timesteps, start, resamplings, jump_length);
-    rc = check_draws(h, noise, n_draws, plan.n_draws); if (rc) return rc;
-    TableBlock tables = plan_tables(plan.coef, plan.coef2, plan.iop);
-    append_guidance(h, tables, timesteps, plan.s_of, 0, {clash_radius, clash_k, scale, max_shift, guide_below}, rstart, rec);
-    Chain ch;
-    rc = ch.open(h, CHAIN_RESTRAINED_EDIT, tables, plan.n_steps, alloc_sampling, pocket_ids_host, noise, seed, z_steps_out, pocket_steps_out, use_graph, stream);
-    if (rc) return rc;
-    const Dims& d = h->dims;
-    const ChainBuf& c = ch.c;
-    const InpaintBuf ip = ch.k->inp;
-    RestrainBuf rb = ch.k->restr;
-    rb.op_energy = op_energy_out;
-    launch_edit_init(ch, ip, plan, start == timesteps, pocket_x, pocket_onehot, phar_x, phar_onehot, fix_x, fix_h);
-    cmdgen_launch_restrain_prep(h->lay, d, rb, pocket_x, ch.s);
-    ch.start(true);                                  // evaluation 0 (t = start / timesteps); the evaluations are cmdgen_edit_chain's: every one with its own k_readout
-    rc = ch.steps({noise, z_steps_out, pocket_steps_out, op_energy_out, nullptr}, plan.n_steps, [&](hipStream_t ss) {
-        cmdgen_launch_restrained_edit_step_count(h->lay, d, c, ip, rb, h->work, h->work.eps_tmp, ss);
-    });
-    if (rc) return rc;
-    cmdgen_launch_chain_final(h->lay, d, decode_buf(c, plan, (size_t)h->lay.Nl, d.P), h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, ch.k->cog, ch.s);
-    cmdgen_launch_restrain_energy(h->lay, d, rb, xh_phar_out, xh_pocket_out, energy_out, ch.s);
-    return ch.close();
+    const GivenPart given{phar_x, phar_onehot, fix_x, fix_h, start, resamplings, jump_length};
+    const GuidePart guide{restraints_host, n_restraints, {clash_radius, clash_k, scale, max_shift, guide_below}, energy_out, op_energy_out};
+    return sampling_chain(h, {CHAIN_RESTRAINED_EDIT, "the restrained edit chain", kEditGuideFrame, CMDGEN_ESTATE, pocket_x, pocket_onehot, timesteps, noise,
+                              n_draws, seed, pocket_ids_host, xh_phar_out, xh_pocket_out, z_steps_out, pocket_steps_out, use_graph, stream, nullptr,
+                              &given, &guide, nullptr});
 }
 
-// ---------------------------------------------------------------------------------
-// the multi-pocket edit chain: the edit chain's ops on the multi-pocket chain's shared latent (kernels_multi.hip; the ops, the group
-// offset and the draw scheme are in include/cmdgen_hip.h).  The plan is the edit chain's, the group tables the multi-pocket chain's.
-// The slot's table block is: the edit plan's tables | the group tables; the known rows and marks are held once per group.
-// ---------------------------------------------------------------------------------
 extern "C" int cmdgen_multi_edit_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
                                        int64_t n_groups, const int64_t* group_size_host, const float* weight_host,
                                        const float* phar_x, const float* phar_onehot, const float* fix_x, const float* fix_h,
@@ -1774,48 +1717,13 @@ extern "C" int cmdgen_multi_edit_chain(cmdgen_handle* h, const float* pocket_x, 
                                        const float* noise, int64_t n_draws, uint64_t seed, const int64_t* group_ids_host,
                                        float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
                                        int32_t use_graph, cmdgen_stream stream) {
-    int rc = check_ready(h); if (rc) return rc;
-    rc = refuse_joint_no_com(h, "the multi-pocket edit chain", kPocketDiffuses); if (rc) return rc;
-    rc = check_inpaint_args(h, timesteps, start, resamplings, jump_length); if (rc) return rc;
-    if (!pocket_x || !pocket_onehot || !group_size_host || !weight_host || !phar_x || !phar_onehot || !fix_x || !fix_h || !xh_phar_out ||
-        !xh_pocket_out)
-        return fail(h, CMDGEN_EINVAL, "null pointer");
-    GroupPlan gp;
-    rc = build_group_plan(h, n_groups, group_size_host, weight_host, group_ids_host, gp); if (rc) return rc;
-    const InpaintPlan plan = build_inpaint_plan(h, timesteps, start, resamplings, jump_length);
-    rc = check_draws(h, noise, n_draws, plan.n_draws); if (rc) return rc;
-    TableBlock tables = plan_tables(plan.coef, plan.coef2, plan.iop);
-    append_group_tables(tables, gp, weight_host, h->lay.B);
-    Chain ch;
-    rc = ch.open(h, CHAIN_MULTI_EDIT, tables, plan.n_steps, alloc_sampling, gp.gid.data(), noise, seed, z_steps_out, pocket_steps_out, use_graph, stream); if (rc) return rc;
-    const Dims& d = h->dims;
-    const ChainBuf& c = ch.c;
-    const InpaintBuf ip = ch.k->inp;
-    const GroupTab gt = group_tab(*ch.k, gp);
-    if (start == timesteps)                          // from the prior: z_T around the weighted pocket centre
-        cmdgen_launch_multi_init(h->lay, d, c, gt, pocket_x, pocket_onehot, ch.s);
-    else                                             // part-way: z ~ q(z_start | the given rows)
-        cmdgen_launch_multi_edit_start(h->lay, d, c, gt, plan.alpha_start, plan.sigma_start, phar_x, phar_onehot, pocket_x, pocket_onehot, ch.s);
-    // a launch of its own after the init: every member reads the projected pocket of its group's FIRST member for the offset
-    cmdgen_launch_multi_edit_prep(h->lay, d, c, gt, ip, phar_x, phar_onehot, fix_x, fix_h, pocket_x, ch.s);
-    ch.start(true);                                  // evaluation 0 (t = start / timesteps)
-    // the plan's tables and the group tables are slot buffers: a changed plan, start, grouping or weight prepares the slot again and
-    // drops its graph; the caller's pointers are the key
-    rc = ch.steps({noise, z_steps_out, pocket_steps_out, nullptr, nullptr}, plan.n_steps, [&](hipStream_t ss) {
-        cmdgen_launch_multi_edit_step_count(h->lay, d, c, gt, ip, h->work, h->work.eps_tmp, ss);
-    });
-    if (rc) return rc;
-    cmdgen_launch_multi_final(h->lay, d, decode_buf(c, plan, (size_t)gt.Nu, d.P), gt, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, ch.k->cog, ch.s);
-    return ch.close();
+    const GroupsPart groups{n_groups, group_size_host, weight_host};
+    const GivenPart given{phar_x, phar_onehot, fix_x, fix_h, start, resamplings, jump_length};
+    return sampling_chain(h, {CHAIN_MULTI_EDIT, "the multi-pocket edit chain", "", CMDGEN_ESTATE, pocket_x, pocket_onehot, timesteps, noise, n_draws, seed,
+                              group_ids_host, xh_phar_out, xh_pocket_out, z_steps_out, pocket_steps_out, use_graph, stream, &groups, &given, nullptr,
+                              nullptr});
 }
 
-// ---------------------------------------------------------------------------------
-// the restrained multi-pocket edit chain: cmdgen_multi_edit_chain's chain with cmdgen_multi_restrained_chain's guidance in op A, once per
-// GROUP (kernels_restrain.hip, "The restrained MULTI-POCKET EDIT chain", holds the definition).  The slot's table block is: the edit plan's
-// tables (coef | coef2 | iop) | the group tables, padded to a multiple of four floats | the guidance tail with one guide row per OP of the
-// plan, CSR offsets [G + 1] and the records sorted by group - so a changed grouping, weight, plan, start, restraint or scalar prepares the
-// slot again and drops its captured steps.
-// ---------------------------------------------------------------------------------
 extern "C" int cmdgen_multi_restrained_edit_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
                                                   int64_t n_groups, const int64_t* group_size_host, const float* weight_host,
                                                   const float* phar_x, const float* phar_onehot, const float* fix_x, const float* fix_h,
@@ -1825,58 +1733,17 @@ extern "C" int cmdgen_multi_restrained_edit_chain(cmdgen_handle* h, const float*
                                                   const cmdgen_restraint* restraints_host, int64_t n_restraints,
                                                   float clash_radius, float clash_k, float scale, float max_shift, float guide_below,
                                                   float* energy_out, float* op_energy_out, int32_t use_graph, cmdgen_stream stream) {
-    int rc = check_ready(h); if (rc) return rc;
-    rc = refuse_joint_no_com(h, "the restrained multi-pocket edit chain", kPocketDiffuses, ": the edit chain and the guidance frame follow the centre-of-mass projections");
-    if (rc) return rc;
-    rc = check_inpaint_args(h, timesteps, start, resamplings, jump_length); if (rc) return rc;
-    if (!pocket_x || !pocket_onehot || !group_size_host || !weight_host || !phar_x || !phar_onehot || !fix_x || !fix_h || !xh_phar_out ||
-        !xh_pocket_out || !energy_out)
-        return fail(h, CMDGEN_EINVAL, "null pointer");
-    GroupPlan gp;
-    rc = build_group_plan(h, n_groups, group_size_host, weight_host, group_ids_host, gp); if (rc) return rc;
-    std::vector<int> rstart; std::vector<cmdgen_restraint> rec;
-    rc = check_group_restraints(h, gp, restraints_host, n_restraints, clash_radius, clash_k, scale, max_shift, guide_below, rstart, rec);
-    if (rc) return rc;
-    const InpaintPlan plan = build_inpaint_plan(h, timesteps, start, resamplings, jump_length);
-    rc = check_draws(h, noise, n_draws, plan.n_draws); if (rc) return rc;
-    TableBlock tables = plan_tables(plan.coef, plan.coef2, plan.iop);
-    append_group_tables(tables, gp, weight_host, h->lay.B);
-    append_guidance(h, tables, timesteps, plan.s_of, 0, {clash_radius, clash_k, scale, max_shift, guide_below}, rstart, rec);
-    Chain ch;
-    rc = ch.open(h, CHAIN_MULTI_RESTRAINED_EDIT, tables, plan.n_steps, alloc_sampling, gp.gid.data(), noise, seed, z_steps_out, pocket_steps_out, use_graph, stream);
-    if (rc) return rc;
-    const Dims& d = h->dims;
-    const ChainBuf& c = ch.c;
-    const InpaintBuf ip = ch.k->inp;
-    const GroupTab gt = group_tab(*ch.k, gp);
-    RestrainBuf rb = ch.k->restr;
-    rb.op_energy = op_energy_out;
-    float* const gd = ch.k->guide_d;
-    if (start == timesteps)                          // from the prior: z_T around the weighted pocket centre
-        cmdgen_launch_multi_init(h->lay, d, c, gt, pocket_x, pocket_onehot, ch.s);
-    else                                             // part-way: z ~ q(z_start | the given rows)
-        cmdgen_launch_multi_edit_start(h->lay, d, c, gt, plan.alpha_start, plan.sigma_start, phar_x, phar_onehot, pocket_x, pocket_onehot, ch.s);
-    cmdgen_launch_multi_edit_prep(h->lay, d, c, gt, ip, phar_x, phar_onehot, fix_x, fix_h, pocket_x, ch.s);
-    cmdgen_launch_restrain_prep(h->lay, d, rb, pocket_x, ch.s);  // com(P_in) of every member; the guidance reads the first member's
-    ch.start(true);                                  // evaluation 0 (t = start / timesteps); the evaluations are cmdgen_multi_edit_chain's
-    rc = ch.steps({noise, z_steps_out, pocket_steps_out, op_energy_out, nullptr}, plan.n_steps, [&](hipStream_t ss) {
-        cmdgen_launch_multi_restrained_edit_step(h->lay, d, c, gt, ip, rb, h->work, h->work.eps_tmp, gd, ss);
-    });
-    if (rc) return rc;
-    cmdgen_launch_multi_final(h->lay, d, decode_buf(c, plan, (size_t)gt.Nu, d.P), gt, h->work, h->work.eps_tmp, xh_phar_out, xh_pocket_out, ch.k->cog, ch.s);
-    cmdgen_launch_multi_restrain_energy(h->lay, d, gt, rb, xh_phar_out, xh_pocket_out, energy_out, ch.s);
-    return ch.close();
+    const GroupsPart groups{n_groups, group_size_host, weight_host};
+    const GivenPart given{phar_x, phar_onehot, fix_x, fix_h, start, resamplings, jump_length};
+    const GuidePart guide{restraints_host, n_restraints, {clash_radius, clash_k, scale, max_shift, guide_below}, energy_out, op_energy_out};
+    return sampling_chain(h, {CHAIN_MULTI_RESTRAINED_EDIT, "the restrained multi-pocket edit chain", kEditGuideFrame, CMDGEN_ESTATE, pocket_x, pocket_onehot,
+                              timesteps, noise, n_draws, seed, group_ids_host, xh_phar_out, xh_pocket_out, z_steps_out, pocket_steps_out, use_graph, stream,
+                              &groups, &given, &guide, nullptr});
 }
 
 // ---------------------------------------------------------------------------------
 // scoring: ConditionalDDPM.score (kernels_score.hip; the level semantics and the output columns are in include/cmdgen_hip.h)
 // ---------------------------------------------------------------------------------
-// the scoring chain's ChainBuf (coef: one row per level, then the (alpha_T, sigma_T) row) and the clean rows it noises
-static int alloc_score(cmdgen_handle* h, ChainSlot& k, const TableBlock&, const float* tables, int) {
-    const int rc = alloc_chain_buf(h, k, tables); if (rc) return rc;
-    return alloc_score_part(h, k);
-}
-
 // what cmdgen_score_chain and cmdgen_multi_score_chain check of a level list alike, and its rows: one per level
 // (alpha_t, sigma_t, t == 0, t / T), then (alpha_T, sigma_T, 0, 1) for the prior KL sums; alpha and sigma are the caller's when it
 // supplies them (its own fp32 evaluation of the schedule, as cmdgen_set_step_table)
@@ -1901,44 +1768,62 @@ static int build_level_rows(cmdgen_handle* h, int32_t n_levels, const int32_t* t
     return 0;
 }
 
+// the two scoring chains: what an entry received (groups: ConditionalDDPM.score_given_pockets, the definition is in include/cmdgen_hip.h -
+// the level rows are the same, the group tables the multi-pocket chain's, behind them in the slot's table block), and their one body
+struct ScoringCall {
+    ChainKind kind;
+    const float *phar_x, *phar_onehot, *pocket_x, *pocket_onehot;
+    int32_t n_levels; const int32_t* t_levels_host; const float* level_coef_host;
+    const float* noise; uint64_t seed; const int64_t* ids_host;          // ids: of the pockets, or with groups of the groups
+    float *terms_out, *member_terms_out, *kl_sums_out;                  // terms: per level and sample, or with groups per level and group (then member_terms: per member, or null)
+    int32_t use_graph; cmdgen_stream stream;
+    const GroupsPart* groups;
+};
+static int scoring_chain(cmdgen_handle* h, const ScoringCall& q) {
+    const GroupsPart* const gr = q.groups;
+    int rc = check_ready(h); if (rc) return rc;
+    rc = refuse_joint_no_com(h, "scoring", kOwnPocketTerms); if (rc) return rc;
+    bool missing = !q.phar_x || !q.phar_onehot || !q.pocket_x || !q.pocket_onehot || !q.t_levels_host || !q.terms_out || !q.kl_sums_out;
+    if (gr) missing |= !gr->size_host || !gr->weight_host;
+    if (missing) return fail(h, CMDGEN_EINVAL, "null pointer");
+    TableBlock tables;
+    rc = build_level_rows(h, q.n_levels, q.t_levels_host, q.level_coef_host, tables.f); if (rc) return rc;
+    const float alpha_T = tables.f[4 * (size_t)q.n_levels];
+    GroupPlan gp;
+    if (gr) {
+        rc = build_group_plan(h, gr->n, gr->size_host, gr->weight_host, q.ids_host, gp); if (rc) return rc;
+        append_group_tables(tables, gp, gr->weight_host, h->lay.B);
+    }
+    Chain ch;
+    rc = ch.open(h, q.kind, tables, q.n_levels, alloc_scoring, gr ? gp.gid.data() : q.ids_host, q.noise, q.seed, nullptr, nullptr, q.use_graph, q.stream);
+    if (rc) return rc;
+    const Layout& lay = h->lay; const Dims& d = h->dims; const Work& w = h->work;
+    const ChainBuf& c = ch.c;
+    ScoreBuf sc = ch.k->score;
+    sc.out = q.terms_out;
+    const GroupTab gt = group_tab(*ch.k, gp);
+    if (gr) cmdgen_launch_multi_score_init(lay, d, c, sc, gt, alpha_T, q.phar_x, q.phar_onehot, q.pocket_x, q.pocket_onehot, q.kl_sums_out, ch.s);
+    else cmdgen_launch_score_init(lay, d, c, sc, alpha_T, q.phar_x, q.phar_onehot, q.pocket_x, q.pocket_onehot, q.kl_sums_out, ch.s);
+    ch.start(false);                                 // every evaluation follows a step launch
+    // the level rows, the group tables and the clean rows are slot buffers (a changed level list, grouping or weight prepares the slot again
+    // and drops its graph); the captured steps read the caller's draws and write its outputs
+    rc = ch.steps({q.noise, q.terms_out, q.member_terms_out, nullptr, nullptr}, q.n_levels, [&](hipStream_t ss) {
+        if (gr) cmdgen_launch_multi_score_step(lay, d, c, sc, gt, w, w.eps_tmp, q.member_terms_out, ss);
+        else cmdgen_launch_score_step(lay, d, c, sc, w, w.eps_tmp, ss);
+    });
+    if (rc) return rc;
+    if (gr) cmdgen_launch_multi_score_final(lay, d, c, sc, gt, w, w.eps_tmp, q.member_terms_out, ch.s);
+    else cmdgen_launch_score_final(lay, d, c, sc, w, w.eps_tmp, ch.s);
+    return ch.close();
+}
+
 extern "C" int cmdgen_score_chain(cmdgen_handle* h, const float* phar_x, const float* phar_onehot,
                                   const float* pocket_x, const float* pocket_onehot,
                                   int32_t n_levels, const int32_t* t_levels_host, const float* level_coef_host,
                                   const float* noise, uint64_t seed, const int64_t* pocket_ids_host,
                                   float* level_terms_out, float* kl_sums_out, int32_t use_graph, cmdgen_stream stream) {
-    int rc = check_ready(h); if (rc) return rc;
-    rc = refuse_joint_no_com(h, "scoring", kOwnPocketTerms); if (rc) return rc;
-    if (!phar_x || !phar_onehot || !pocket_x || !pocket_onehot || !t_levels_host || !level_terms_out || !kl_sums_out)
-        return fail(h, CMDGEN_EINVAL, "null pointer");
-    TableBlock tables;
-    rc = build_level_rows(h, n_levels, t_levels_host, level_coef_host, tables.f); if (rc) return rc;
-    const float alpha_T = tables.f[4 * (size_t)n_levels];
-    Chain ch;
-    rc = ch.open(h, CHAIN_SCORE, tables, n_levels, alloc_score, pocket_ids_host, noise, seed, nullptr, nullptr, use_graph, stream); if (rc) return rc;
-    const Dims& d = h->dims;
-    const ChainBuf& c = ch.c;
-    ScoreBuf sc = ch.k->score;
-    sc.out = level_terms_out;
-    cmdgen_launch_score_init(h->lay, d, c, sc, alpha_T, phar_x, phar_onehot, pocket_x, pocket_onehot, kl_sums_out, ch.s);
-    ch.start(false);                                 // every evaluation follows a k_score_step
-    // the level rows and the clean rows are slot buffers; the captured steps read the caller's draws and write its output
-    rc = ch.steps({noise, level_terms_out, nullptr, nullptr, nullptr}, n_levels, [&](hipStream_t ss) {
-        cmdgen_launch_score_step(h->lay, d, c, sc, h->work, h->work.eps_tmp, ss);
-    });
-    if (rc) return rc;
-    cmdgen_launch_score_final(h->lay, d, c, sc, h->work, h->work.eps_tmp, ch.s);
-    return ch.close();
-}
-
-// ---------------------------------------------------------------------------------
-// scoring for several pockets at once: ConditionalDDPM.score_given_pockets (kernels_score.hip; the definition is in
-// include/cmdgen_hip.h).  The level rows are the scoring chain's, the group tables the multi-pocket chain's.
-// ---------------------------------------------------------------------------------
-// the slot's table block: the level rows (n_levels + 1) | the group tables
-static int alloc_multi_score(cmdgen_handle* h, ChainSlot& k, const TableBlock& t, const float* tables, int) {
-    const int rc = alloc_chain_buf(h, k, tables); if (rc) return rc;
-    point_group_tab(k.groups, tables + t.groups, (size_t)h->lay.B);
-    return alloc_score_part(h, k);
+    return scoring_chain(h, {CHAIN_SCORE, phar_x, phar_onehot, pocket_x, pocket_onehot, n_levels, t_levels_host, level_coef_host, noise, seed,
+                             pocket_ids_host, level_terms_out, nullptr, kl_sums_out, use_graph, stream, nullptr});
 }
 
 extern "C" int cmdgen_multi_score_chain(cmdgen_handle* h, const float* phar_x, const float* phar_onehot,
@@ -1948,34 +1833,9 @@ extern "C" int cmdgen_multi_score_chain(cmdgen_handle* h, const float* phar_x, c
                                         const float* noise, uint64_t seed, const int64_t* group_ids_host,
                                         float* group_terms_out, float* member_terms_out, float* kl_sums_out,
                                         int32_t use_graph, cmdgen_stream stream) {
-    int rc = check_ready(h); if (rc) return rc;
-    rc = refuse_joint_no_com(h, "scoring", kOwnPocketTerms); if (rc) return rc;
-    if (!phar_x || !phar_onehot || !pocket_x || !pocket_onehot || !group_size_host || !weight_host || !t_levels_host || !group_terms_out ||
-        !kl_sums_out)
-        return fail(h, CMDGEN_EINVAL, "null pointer");
-    TableBlock tables;
-    rc = build_level_rows(h, n_levels, t_levels_host, level_coef_host, tables.f); if (rc) return rc;
-    GroupPlan gp;
-    rc = build_group_plan(h, n_groups, group_size_host, weight_host, group_ids_host, gp); if (rc) return rc;
-    const float alpha_T = tables.f[4 * (size_t)n_levels];
-    append_group_tables(tables, gp, weight_host, h->lay.B);
-    Chain ch;
-    rc = ch.open(h, CHAIN_MULTI_SCORE, tables, n_levels, alloc_multi_score, gp.gid.data(), noise, seed, nullptr, nullptr, use_graph, stream); if (rc) return rc;
-    const Dims& d = h->dims;
-    const ChainBuf& c = ch.c;
-    ScoreBuf sc = ch.k->score;
-    sc.out = group_terms_out;
-    const GroupTab gt = group_tab(*ch.k, gp);
-    cmdgen_launch_multi_score_init(h->lay, d, c, sc, gt, alpha_T, phar_x, phar_onehot, pocket_x, pocket_onehot, kl_sums_out, ch.s);
-    ch.start(false);                                 // every evaluation follows a k_multi_score_step
-    // the level rows, the group tables and the clean rows are slot buffers (a changed level list, grouping or weight prepares the slot
-    // again and drops its graph); the captured steps read the caller's draws and write its outputs
-    rc = ch.steps({noise, group_terms_out, member_terms_out, nullptr, nullptr}, n_levels, [&](hipStream_t ss) {
-        cmdgen_launch_multi_score_step(h->lay, d, c, sc, gt, h->work, h->work.eps_tmp, member_terms_out, ss);
-    });
-    if (rc) return rc;
-    cmdgen_launch_multi_score_final(h->lay, d, c, sc, gt, h->work, h->work.eps_tmp, member_terms_out, ch.s);
-    return ch.close();
+    const GroupsPart groups{n_groups, group_size_host, weight_host};
+    return scoring_chain(h, {CHAIN_MULTI_SCORE, phar_x, phar_onehot, pocket_x, pocket_onehot, n_levels, t_levels_host, level_coef_host, noise, seed,
+                             group_ids_host, group_terms_out, member_terms_out, kl_sums_out, use_graph, stream, &groups});
 }
 
 extern "C" int cmdgen_chain_status(cmdgen_handle* h, float* max_rel, float* max_cog, int64_t* nan_resets, cmdgen_stream stream) {
