@@ -702,8 +702,8 @@ static std::vector<float> step_table(const cmdgen_handle* h, int K) {
 }
 
 // ---------------------------------------------------------------------------------
-// the chains.  The twelve kinds have three host bodies: sampling_chain (nine kinds: a cube of parts - from the prior or from GIVEN rows,
-// one pocket per sample or GROUPS of pockets, unsteered, GUIDEd by restraints or pushed apart within SETS), scoring_chain (two kinds: with
+// the chains.  The thirteen kinds have three host bodies: sampling_chain (ten kinds: a cube of parts - from the prior or from GIVEN rows,
+// one pocket per sample or GROUPS of pockets, unsteered, GUIDEd by restraints, pushed apart within SETS or both), scoring_chain (two kinds: with
 // or without groups) and cmdgen_joint_chain.  An extern "C" entry of the first two only packs its arguments (SamplingCall, ScoringCall: a
 // part the kind lacks is null) and calls its body; a body branches on the presence of a part, never on the kind.
 // A kind's state lives in its slot (h->chains[kind]).  A body reads top to bottom: refusals, the plans of the parts present, the slot's
@@ -946,7 +946,7 @@ static int alloc_diverse_part(cmdgen_handle* h, ChainSlot& k, const float* g, in
     rc = slot_alloc(h, k, db.gd, (size_t)h->lay.Nl * 3); if (rc) return rc;
     return slot_alloc(h, k, db.po, (size_t)h->lay.Nl);
 }
-// The ChainAlloc of the nine sampling kinds: the ChainBuf, then the part of every section the body appended to its table block; the
+// The ChainAlloc of the ten sampling kinds: the ChainBuf, then the part of every section the body appended to its table block; the
 // restrained multi-pocket kinds also get the displacement buffer their guide launch hands to their step launch.
 static int alloc_sampling(cmdgen_handle* h, ChainSlot& k, const TableBlock& t, const float* dev, int n_steps) {
     int rc = alloc_chain_buf(h, k, dev); if (rc) return rc;
@@ -1008,7 +1008,7 @@ struct Chain {
 // posterior rows, or with GIVEN rows the edit plan's tables (coef | coef2 | iop) | with GROUPS the group tables | the tail of the steering
 // part, on a row boundary: the GUIDE's (kernels_restrain.hip holds the definition: a guidance term in the mean of every posterior op, or
 // with given rows in op A; once per sample, or with groups once per group on the shared latent) or the SETS' (kernels_diverse.hip: a term
-// that pushes the samples of a set apart).  Whatever changes a part therefore prepares the slot again and drops its captured steps.
+// that pushes the samples of a set apart), or the guide's and then the sets' (both heads hold the same guide rows).  Whatever changes a part therefore prepares the slot again and drops its captured steps.
 // ---------------------------------------------------------------------------------
 static_assert(sizeof(cmdgen_restraint) == sizeof(RestraintRec) && sizeof(RestraintRec) == 10 * sizeof(float), "the public record is the kernels'");
 static_assert(CMDGEN_RESTRAINT_POSITION == RK_POSITION && CMDGEN_RESTRAINT_DISTANCE == RK_DISTANCE && CMDGEN_RESTRAINT_EXCLUSION == RK_EXCLUSION &&
@@ -1464,7 +1464,7 @@ static ChainBuf decode_buf(const ChainBuf& c, int skip, size_t rows, int P) {
 }
 
 // ---------------------------------------------------------------------------------
-// the nine sampling chains: what an entry received (the part names are Handle._sampling_chain's and tests/chain_kit.run_chain's; a part
+// the ten sampling chains: what an entry received (the part names are Handle._sampling_chain's and tests/chain_kit.run_chain's; a part
 // the kind lacks is null), and their one body
 // ---------------------------------------------------------------------------------
 struct GroupsPart { int64_t n; const int64_t* size_host; const float* weight_host; };
@@ -1504,7 +1504,8 @@ static int sampling_chain(cmdgen_handle* h, const SamplingCall& q) {
     if (gu) missing |= !gu->energy_out;
     if (se) {
         missing |= !se->size_host || !se->overlap_out;
-        null_text = "null pointer (pocket_x, pocket_onehot, set_size_host, xh_phar_out, xh_pocket_out and overlap_out are required)";
+        null_text = gu ? "null pointer (pocket_x, pocket_onehot, set_size_host, xh_phar_out, xh_pocket_out, energy_out and overlap_out are required)"
+                       : "null pointer (pocket_x, pocket_onehot, set_size_host, xh_phar_out, xh_pocket_out and overlap_out are required)";
     }
     if (missing) return fail(h, CMDGEN_EINVAL, "%s", null_text);
     // ---- the plans of the parts present.  Without given rows the ops go down the K levels one by one, with one spare guide row; with them the
@@ -1523,7 +1524,7 @@ static int sampling_chain(cmdgen_handle* h, const SamplingCall& q) {
     } else {
         rc = check_timesteps(h, K); if (rc) return rc;
         s_of = levels_down(K);
-        guide_lds = plan_restrained_step_lds(h->lay.max_n, P);
+        guide_lds = se ? plan_diverse_restrained_step_lds(h->lay.max_n, P) : plan_restrained_step_lds(h->lay.max_n, P);
     }
     if (gr) {
         rc = build_group_plan(h, gr->n, gr->size_host, gr->weight_host, q.ids_host, gp); if (rc) return rc;
@@ -1551,9 +1552,10 @@ static int sampling_chain(cmdgen_handle* h, const SamplingCall& q) {
     RestrainBuf rb = ch.k->restr;
     DiverseBuf db = ch.k->div;
     float* const gd = ch.k->guide_d;
-    float* op_side = nullptr;                        // the steering part's output per op: the fourth pointer of the graph's key
+    float *op_side = nullptr, *op_side2 = nullptr;   // the steering parts' outputs per op: the fourth and the fifth pointer of the graph's key
     if (gu) op_side = rb.op_energy = gu->op_energy_out;
-    if (se) { op_side = db.op_overlap = se->op_overlap_out; rb.pin_com = db.pin_com; }    // (k_restrain_prep fills pin_com and reads nothing else of rb)
+    if (se) { (gu ? op_side2 : op_side) = db.op_overlap = se->op_overlap_out; rb.pin_com = db.pin_com; }   // (k_restrain_prep fills pin_com and reads nothing else
+                                                                                                           // of rb; with both parts they read the one buffer)
     // ---- init: z_T around the (weighted) pocket centre, or part-way z ~ q(z_start | the given rows); the known rows and marks; com(P_in)
     const bool from_prior = !gv || gv->start == K;
     if (gr) {
@@ -1588,7 +1590,7 @@ static int sampling_chain(cmdgen_handle* h, const SamplingCall& q) {
         return fail(h, CMDGEN_ESTATE, "the evaluation and the step kernel disagree on readout_in_coord (%d, %d)", ch.a.readout_used, own_vel);
     // ---- the steps: the one launcher of the corner (the adapters build no other)
     const int corner = (se ? 8 : 0) | (gr ? 4 : 0) | (gv ? 2 : 0) | (gu ? 1 : 0);
-    rc = ch.steps({q.noise, q.z_steps_out, q.pocket_steps_out, op_side, nullptr}, n_steps, [&](hipStream_t ss) {
+    rc = ch.steps({q.noise, q.z_steps_out, q.pocket_steps_out, op_side, op_side2}, n_steps, [&](hipStream_t ss) {
         switch (corner) {
         case 0: cmdgen_launch_step_count(lay, d, c, w, eps, own_vel, ss); break;
         case 1: cmdgen_launch_restrained_step_count(lay, d, c, rb, w, eps, own_vel, ss); break;
@@ -1599,6 +1601,7 @@ static int sampling_chain(cmdgen_handle* h, const SamplingCall& q) {
         case 6: cmdgen_launch_multi_edit_step_count(lay, d, c, gt, ip, w, eps, ss); break;
         case 7: cmdgen_launch_multi_restrained_edit_step(lay, d, c, gt, ip, rb, w, eps, gd, ss); break;
         case 8: cmdgen_launch_diverse_step(lay, d, c, db, w, eps, ss); break;
+        case 9: cmdgen_launch_diverse_restrained_step(lay, d, c, rb, db, w, eps, ss); break;
         }
     });
     if (rc) return rc;
@@ -1615,7 +1618,7 @@ static int sampling_chain(cmdgen_handle* h, const SamplingCall& q) {
     return ch.close();
 }
 
-// the nine entries (and the inpainting alias): each packs what it received
+// the ten entries (and the inpainting alias): each packs what it received
 extern "C" int cmdgen_sample_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,
                                    int32_t timesteps, const float* noise, uint64_t seed,
                                    const int64_t* pocket_ids_host, float* xh_phar_out, float* xh_pocket_out,
@@ -1646,6 +1649,22 @@ extern "C" int cmdgen_diverse_chain(cmdgen_handle* h, const float* pocket_x, con
     return sampling_chain(h, {CHAIN_DIVERSE, "the diverse chain", kGuideFrame, CMDGEN_EINVAL, pocket_x, pocket_onehot, timesteps, noise, 0, seed,
                               pocket_ids_host, xh_phar_out, xh_pocket_out, z_steps_out, pocket_steps_out, use_graph, stream, nullptr, nullptr, nullptr,
                               &sets});
+}
+
+extern "C" int cmdgen_diverse_restrained_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot, int32_t timesteps,
+                                               const cmdgen_restraint* restraints_host, int64_t n_restraints,
+                                               float clash_radius, float clash_k, float scale, float max_shift, float guide_below,
+                                               int64_t n_sets, const int64_t* set_size_host,
+                                               float strength, float width, float diverse_max_shift, float diverse_guide_below,
+                                               const float* noise, uint64_t seed, const int64_t* pocket_ids_host,
+                                               float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                                               float* energy_out, float* op_energy_out, float* overlap_out, float* op_overlap_out,
+                                               int32_t use_graph, cmdgen_stream stream) {
+    const GuidePart guide{restraints_host, n_restraints, {clash_radius, clash_k, scale, max_shift, guide_below}, energy_out, op_energy_out};
+    const SetsPart sets{n_sets, set_size_host, strength, width, diverse_max_shift, diverse_guide_below, overlap_out, op_overlap_out};
+    return sampling_chain(h, {CHAIN_DIVERSE_RESTRAINED, "the restrained diverse chain", kGuideFrame, CMDGEN_EINVAL, pocket_x, pocket_onehot, timesteps,
+                              noise, 0, seed, pocket_ids_host, xh_phar_out, xh_pocket_out, z_steps_out, pocket_steps_out, use_graph, stream, nullptr,
+                              nullptr, &guide, &sets});
 }
 
 extern "C" int cmdgen_multi_pocket_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot,

@@ -1,5 +1,5 @@
 // cmdgen_guide_parts.h - the parts the guided chains' kernels share (kernels_restrain.hip, kernels_diverse.hip): the wave reductions, the
-// denoised estimate, the frame shift and the clip of a displacement.  Device code only; every unit that includes this is built with
+// denoised estimate, the frame shift, the clip of a displacement and what an op of the diverse chain runs for a sample.  Device code only; every unit that includes this is built with
 // -ffp-contract=off.  The expressions and sum orders are those the restrained chains' bit-for-bit tests pin.
 #pragma once
 #include "cmdgen_step_parts.h"
@@ -36,4 +36,13 @@ __device__ __forceinline__ void frame_shift(const Dims& d, const GuideBuf& gb, i
 __device__ __forceinline__ void clip_shift(float max_shift, float& dx, float& dy, float& dz) {
     const float len = sqrtf(dx * dx + dy * dy + dz * dz);
     if (len > max_shift) { const float f = max_shift / len; dx *= f; dy *= f; dz *= f; }
+}
+
+// what an op of the diverse chain runs for sample b: guided - the displacement enters the mean; terms - steps 1-3 of kernels_diverse.hip run at all
+// (for the displacement, or for op_overlap alone).  Uniform over the workgroup, and the same in all three launches of the op.
+struct DiverseOp { bool guided, terms; };
+__device__ __forceinline__ DiverseOp diverse_op(const DiverseBuf& db, int b, const float4& cf) {
+    const bool coupled = db.set_size[b] > 1;
+    const bool guided = coupled && db.strength > 0.f && cf.w <= db.guide_below;
+    return DiverseOp{guided, coupled && (guided || db.op_overlap != nullptr)};
 }

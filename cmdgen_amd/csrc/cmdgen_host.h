@@ -22,7 +22,7 @@ struct DevBuf {
 };
 
 // A slot's table block as its entry lays it out (cmdgen_api.hip): the posterior (scoring: level) rows | the edit tables | the group tables |
-// the guidance tail, or the diverse chain's tail - whatever must prepare the slot again when it changes.  Each appender records where its section begins, so nothing
+// the guidance tail | the sets' tail (the diverse kinds; the restrained diverse kind has both) - whatever must prepare the slot again when it changes.  Each appender records where its section begins, so nothing
 // derives an offset a second time.
 struct TableBlock {
     std::vector<float> f;                  // the upload
@@ -40,7 +40,7 @@ struct TableBlock {
 // Host state of one kind of denoising chain (cmdgen_api.hip): its buffers for the current layout, the plan tables they were
 // prepared for, and its captured steps.  Each kind has a slot of its own, so plain and inpainting chains alternate on a
 // handle without re-preparing or re-capturing.
-enum ChainKind { CHAIN_PLAIN, CHAIN_JOINT, CHAIN_INPAINT, CHAIN_SCORE, CHAIN_MULTI, CHAIN_MULTI_EDIT, CHAIN_MULTI_SCORE, CHAIN_RESTRAINED, CHAIN_RESTRAINED_EDIT, CHAIN_MULTI_RESTRAINED, CHAIN_MULTI_RESTRAINED_EDIT, CHAIN_DIVERSE, CHAIN_KINDS };
+enum ChainKind { CHAIN_PLAIN, CHAIN_JOINT, CHAIN_INPAINT, CHAIN_SCORE, CHAIN_MULTI, CHAIN_MULTI_EDIT, CHAIN_MULTI_SCORE, CHAIN_RESTRAINED, CHAIN_RESTRAINED_EDIT, CHAIN_MULTI_RESTRAINED, CHAIN_MULTI_RESTRAINED_EDIT, CHAIN_DIVERSE, CHAIN_DIVERSE_RESTRAINED, CHAIN_KINDS };
 struct ChainSlot {
     std::vector<void*> allocs;
     TableBlock tables;                     // the uploaded table block with its offsets, compared to decide a re-prepare
@@ -57,9 +57,9 @@ struct ChainSlot {
     ChainBuf buf{};                        // every conditional kind: z, the pocket, the posterior (scoring: level) rows, checks and state
     InpaintBuf inp{};                      // edit kinds: the op tables, the known rows and marks (multi-pocket: once per group), the offset per sample
     GroupTab groups{};                     // multi-pocket kinds: the group tables in the slot's table block (a changed grouping prepares the slot again)
-    RestrainBuf restr{};                   // restrained kinds: the guidance tables in the slot's table block (a changed restraint prepares the slot again)
+    RestrainBuf restr{};                   // restrained kinds (the restrained diverse kind among them): the guidance tables in the slot's table block (a changed restraint prepares the slot again)
     float* guide_d = nullptr;              // restrained multi-pocket kinds: the displacement of every group's rows [Nu][3], written by the guide launch for the step launch
-    DiverseBuf div{};                      // diverse kind: the guide rows, scalars and set tables in the slot's table block (a changed partition or scalar prepares the slot again), y, gd, po
+    DiverseBuf div{};                      // diverse kinds: the guide rows, scalars and set tables in the slot's table block (a changed partition or scalar prepares the slot again), y, gd, po
     ScoreBuf score{};                      // scoring kinds: the clean rows the levels noise
     JointBuf joint{};                      // joint kind: its z, scratch and plan rows ...
     float* eps_pocket = nullptr;           // ... and the pocket output [Np][3+R] of its evaluations

@@ -60,6 +60,10 @@ void cmdgen_launch_restrained_edit_step_count(const Layout& lay, const Dims& d, 
                                               const Work& w, const float* eps, hipStream_t s);   // the edit chain's op with the guidance in op A
 void cmdgen_launch_restrain_energy(const Layout& lay, const Dims& d, const RestrainBuf& rb, const float* xo, const float* po,
                                    float* energy_out, hipStream_t s);
+// ... and the restrained diverse chain's op: cmdgen_launch_diverse_terms (kernels_diverse.hip), then k_diverse_restrained_step_count (k_step_count
+// with the restraint displacement and then the sets' displacement in the mean)
+void cmdgen_launch_diverse_restrained_step(const Layout& lay, const Dims& d, const ChainBuf& c, const RestrainBuf& rb, const DiverseBuf& db,
+                                           const Work& w, const float* eps, hipStream_t s);
 // ... and the restrained multi-pocket chain: per op k_multi_guide (one workgroup per group: the displacement gd [Nu][3]) and then
 // k_multi_restrained_step_count (one per member); RestrainBuf::rstart and op_energy are per GROUP, energy_out is [G][2]
 void cmdgen_launch_multi_restrained_step(const Layout& lay, const Dims& d, const ChainBuf& c, const GroupTab& g, const RestrainBuf& rb,
@@ -76,6 +80,9 @@ void cmdgen_launch_multi_restrain_energy(const Layout& lay, const Dims& d, const
 // k_diverse_step_count (k_step_count with the displacement in the mean)
 void cmdgen_launch_diverse_step(const Layout& lay, const Dims& d, const ChainBuf& c, const DiverseBuf& db, const Work& w, const float* eps,
                                 hipStream_t s);
+// ... its first two launches alone (what the restrained diverse chain's step runs in front of its own step kernel)
+void cmdgen_launch_diverse_terms(const Layout& lay, const Dims& d, const ChainBuf& c, const DiverseBuf& db, const Work& w, const float* eps,
+                                 hipStream_t s);
 // ... and the same two guide launches over the chain's output xo / po (A): overlap_out [B]
 void cmdgen_launch_diverse_overlap(const Layout& lay, const Dims& d, const DiverseBuf& db, const float* xo, const float* po, float* overlap_out,
                                    hipStream_t s);

@@ -293,6 +293,11 @@ inline size_t plan_restrained_step_lds(int max_n, int P) { return plan_step_lds(
 // velocity array.  Bytes per workgroup, at most PLAN_RESTRAINED_LDS_MAX.
 inline size_t plan_restrained_edit_step_lds(int max_n, int P) { return plan_step_lds(max_n, P) + (size_t)max_n * 7 * sizeof(float); }
 
+// The restrained diverse chain's step kernel (k_diverse_restrained_step_count, kernels_restrain.hip) keeps the same: the plain step's LDS, then the
+// denoised estimate, the restraint displacement and the energy term of every row (the overlap displacement comes from global memory).  92 B per node at
+// phar_nf 8: bytes per workgroup, at most PLAN_RESTRAINED_LDS_MAX - 712 nodes, where the diverse chain alone takes 1024.
+inline size_t plan_diverse_restrained_step_lds(int max_n, int P) { return plan_step_lds(max_n, P) + (size_t)max_n * 7 * sizeof(float); }
+
 // The diverse chain (kernels_diverse.hip): its step kernel keeps plan_step_lds; k_diverse_frame keeps a float4 per pocket atom of the largest sample
 // (less, so the step's check covers it); k_diverse_pair's LDS is static.
 inline size_t plan_diverse_frame_lds(int max_n) { return (size_t)max_n * 16; }

@@ -49,14 +49,7 @@ namespace {
 
 enum { PAIR_TILE = 256, PAIR_THREADS = 1024 };      // rows of y per LDS tile (a multiple of 64: a lane keeps its stride over the tiles); one wave per own point, 16 per pass
 
-// what an op runs for sample b: guided - the displacement enters the mean; terms - steps 1-3 run at all (for the displacement, or for op_overlap
-// alone).  Uniform over the workgroup, and the same in all three launches of the op.
-struct DiverseOp { bool guided, terms; };
-__device__ __forceinline__ DiverseOp diverse_op(const DiverseBuf& db, int b, const float4& cf) {
-    const bool coupled = db.set_size[b] > 1;
-    const bool guided = coupled && db.strength > 0.f && cf.w <= db.guide_below;
-    return DiverseOp{guided, coupled && (guided || db.op_overlap != nullptr)};
-}
+// (DiverseOp, diverse_op - what an op runs for a sample - are in cmdgen_guide_parts.h: k_diverse_restrained_step_count of kernels_restrain.hip asks too)
 
 // Step 1 for sample b.  output = false: at the op's input (z, eps, the chain's pocket); output = true: on the returned rows xo [Nl][3+P] and
 // po [Np][3+R], which are in Angstrom already.  s_q: [max_n] float4 of dynamic LDS.
@@ -208,11 +201,15 @@ __global__ __launch_bounds__(1024) void k_diverse_step_count(Layout lay, Dims d,
              [&](float mu, int i, int k) { return guided ? mu + gd[(size_t)(s.pb + i) * 3 + k] / d.norm_x : mu; });
 }
 
-void cmdgen_launch_diverse_step(const Layout& lay, const Dims& d, const ChainBuf& c, const DiverseBuf& db, const Work& w, const float* eps,
-                                hipStream_t s) {
+void cmdgen_launch_diverse_terms(const Layout& lay, const Dims& d, const ChainBuf& c, const DiverseBuf& db, const Work& w, const float* eps,
+                                 hipStream_t s) {
     const size_t shm_frame = plan_diverse_frame_lds(lay.max_n);
     hipLaunchKernelGGL(k_diverse_frame, dim3(lay.B), dim3(256), shm_frame, s, lay, d, c, db, w, eps);
     hipLaunchKernelGGL(k_diverse_pair, dim3(lay.B), dim3(PAIR_THREADS), 0, s, lay, d, c, db);
+}
+void cmdgen_launch_diverse_step(const Layout& lay, const Dims& d, const ChainBuf& c, const DiverseBuf& db, const Work& w, const float* eps,
+                                hipStream_t s) {
+    cmdgen_launch_diverse_terms(lay, d, c, db, w, eps, s);
     hipLaunchKernelGGL(k_diverse_step_count, dim3(lay.B), dim3(lay.max_n > 128 ? 1024 : 256), plan_step_lds(lay.max_n, d.P), s, lay, d, c, db, w,
                        eps, (const float*)db.gd);                   // the block as k_step_count
 }

@@ -417,6 +417,72 @@ __global__ __launch_bounds__(1024) void k_restrained_edit_step_count(Layout lay,
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// k_diverse_restrained_step_count: diverse sampling UNDER restraints (ConditionalDDPM.sample_diverse_restrained,
+// cmdgen_diverse_restrained_chain): both steering terms in one chain.  This is the definition (include/cmdgen_hip.h and INTEGRATION.md,
+// "Diverse sampling under restraints", repeat it; tests/diverse_restrained_ref.py is its CPU model).
+// What is unchanged.  The chain is cmdgen_sample_chain's: the same init, ops, draws, Philox counters (keyed by pocket_ids), saved steps and
+// CoG fix.  The decode is unguided.  The evaluations run their own k_readout, as the diverse chain's do (there is no own-velocity form).
+// Per posterior op t -> s both terms are taken at the same point, the denoised estimate of the op's input, and each keeps the definition and
+// the scalars of its own chain:
+//   1. Restraint term.  Steps 1-4 of this file's header give d^r_i: xhat, the frame shift, E and g from the sample's records and the clash
+//      pair, d^r_i = -scale (n_x coef.z)^2 g_i, clipped at the restraint max_shift.  Active for a touched sample (a record on it, or
+//      r_c > 0) when scale > 0 and t / T <= guide_below.
+//   2. Overlap term.  Steps 1-3 of kernels_diverse.hip's header give d^v_ai from the set's y = xhat - shift, with strength and width, clipped
+//      at its own diverse_max_shift.  Active for a sample of a set with M > 1 when strength > 0 and t / T <= diverse_guide_below.
+//   3. Mean.  mu.x_i = ((z.x_i / coef.x - coef.y e_i) + d^r_i / n_x) + d^v_i / n_x: the two additions in that order, each made only where its
+//      term is active; nothing is added for an inactive term, not even a zero.  The h columns, the draw, the projection, the saved steps and
+//      pass 1 of the next radius graph are the plain step's.
+// Side outputs, from the parents' own code: energy_out [B][2] and op_energy_out [K][B] exactly as the restrained chain reports them
+// (k_restrain_energy; sample_points and store_op_energy below), overlap_out [B] and op_overlap_out [K][B] exactly as the diverse chain reports
+// them (k_diverse_frame_out / k_diverse_pair_out; k_diverse_pair).  A per-op output is still computed where its term is inactive but defined.
+// Reductions that hold bit for bit on every output, the chain status and the "chain_z" debug read, on a handle whose evaluations run their
+// own k_readout (readout_in_coord = 0):
+//   - strength = 0, or diverse_guide_below = 0, or every set of one member: cmdgen_restrained_chain's outputs, energy and op_energy included;
+//   - scale = 0, or no record on any sample and r_c = 0: cmdgen_diverse_chain's outputs, overlap and op_overlap included;
+//   - both at once: cmdgen_sample_chain's outputs.
+// Two runs of the same inputs are equal bit for bit, captured or eager (no float atomics in either term; -ffp-contract=off).
+// Three launches per op: k_diverse_frame and k_diverse_pair as they are (the pair term stays out of the step launch, whose other workgroups
+// rewrite z and the pockets), then this kernel, one workgroup per sample: the restraint term exactly as k_restrained_step_count<false> forms
+// it (xhat_free, frame_shift, sample_points), then plain_op with both displacements in the mean.
+// LDS: StepWg's layout, then xhat, d and e as in k_restrained_edit_step_count (plan_diverse_restrained_step_lds: 92 B per node at phar_nf 8,
+// so a sample of more than 712 nodes is refused).
+// ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void k_diverse_restrained_step_count(Layout lay, Dims d, ChainBuf c, RestrainBuf rb, DiverseBuf db, Work w,
+                                                                       const float* __restrict__ eps, const float* __restrict__ gd) {
+    extern __shared__ float4 s_pos[];               // StepWg's layout ([max_n] positions, phar first, then int sdeg[max_n], then z), then xhat, d, e
+    __shared__ float s_mean[3], s_shift[3];
+    const StepWg s = step_wg(lay, d, c, w, s_pos, s_mean);
+    float* s_xh = s.s_z + (size_t)lay.max_n * (3 + d.P);          // [nl][3] xhat, Angstrom
+    float* s_d = s_xh + (size_t)lay.max_n * 3;                    // [nl][3] the restraint displacement, Angstrom
+    float* s_e = s_d + (size_t)lay.max_n * 3;                     // [nl] the points' shares of E
+    const int lane = s.tid & 63, wave = s.tid >> 6, nwaves = s.nt >> 6;
+    const StepRows r = sample_rows(lay, c, s);
+    const float4 sa = rb.sa[s.step];
+    const GuideOp go = guide_op(rb, s.b, s.cf);
+    const bool pushed = diverse_op(db, s.b, s.cf).guided;          // k_diverse_pair's, which then wrote the sample's d^v
+    const float* eg = eps + (size_t)s.pb * s.ld;
+    load_sample(s, c);
+    // ---- the restraint term (steps 1-4): uniform over the workgroup
+    if (go.terms) {
+        for (int idx = s.tid; idx < 3 * s.nl; idx += s.nt) {    // 1. xhat
+            const int i = idx / 3, k = idx - 3 * i;
+            s_xh[idx] = xhat_free(d, sa, s.s_z[i * s.ld + k], eg[i * s.ld + k], s.nan_reset);
+        }
+        if (wave == nwaves - 1) frame_shift(d, rb, s.b, s_pos + s.nl, s.np, lane, s_shift);      // 2. shift
+        __syncthreads();
+        sample_points(rb, d, s.cf, go, s.nl, s.np, s_xh, s_pos + s.nl, s_shift, s_d, s_e);      // 3. / 4.
+    }
+    if (rb.op_energy && s.tid == 0) store_op_energy(rb, (size_t)s.step * lay.B + s.b, s_e, go.terms ? s.nl : 0);
+    // ---- 3. the mean: the restraint displacement, then the overlap displacement, each only where its term is active
+    plain_op(lay, d, c, w, s, r, [&](int idx) { return eg[idx]; },
+             [&](float mu, int i, int k) {
+                 if (go.guided) mu = mu + s_d[3 * i + k] / d.norm_x;
+                 if (pushed) mu = mu + gd[(size_t)(s.pb + i) * 3 + k] / d.norm_x;
+                 return mu;
+             });
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // The restrained MULTI-POCKET chain (ConditionalDDPM.sample_restrained_given_pockets, cmdgen_multi_restrained_chain): the guidance of this
 // file's header on the shared latent of kernels_multi.hip.  The chain is cmdgen_multi_pocket_chain's - the same layout of B member samples
 // in G groups, the same init, ops, draws, Philox counters (keyed by group id), decode and CoG re-centring - with steps 1-5 of the header
@@ -624,6 +690,13 @@ void cmdgen_launch_restrained_edit_step_count(const Layout& lay, const Dims& d, 
                                               const Work& w, const float* eps, hipStream_t s) {
     const size_t shm = plan_restrained_edit_step_lds(lay.max_n, d.P);
     hipLaunchKernelGGL(k_restrained_edit_step_count, dim3(lay.B), dim3(lay.max_n > 128 ? 1024 : 256), shm, s, lay, d, c, ip, rb, w, eps);
+}
+void cmdgen_launch_diverse_restrained_step(const Layout& lay, const Dims& d, const ChainBuf& c, const RestrainBuf& rb, const DiverseBuf& db,
+                                           const Work& w, const float* eps, hipStream_t s) {
+    cmdgen_launch_diverse_terms(lay, d, c, db, w, eps, s);      // k_diverse_frame, k_diverse_pair: gd and op_overlap
+    const size_t shm = plan_diverse_restrained_step_lds(lay.max_n, d.P);
+    hipLaunchKernelGGL(k_diverse_restrained_step_count, dim3(lay.B), dim3(lay.max_n > 128 ? 1024 : 256), shm, s, lay, d, c, rb, db, w, eps,
+                       (const float*)db.gd);                    // the block as k_step_count
 }
 void cmdgen_launch_restrain_energy(const Layout& lay, const Dims& d, const RestrainBuf& rb, const float* xo, const float* po,
                                    float* energy_out, hipStream_t s) {

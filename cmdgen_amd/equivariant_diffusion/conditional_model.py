@@ -293,9 +293,10 @@ class ConditionalDDPM(EnVariationalDiffusion):
     OVERLAP_INFO = ('overlap', 'op_overlap')                        # of the diverse chain: overlap [B], op_overlap
 
     def _finish_with_info(self, h, run, frame_of_step, return_frames, names):
-        """_finish_chain for a chain with side outputs, whose run() returns (xh_phar, xh_pocket, z_steps, per owner, per op and owner).
-        names: the info key of every column of the per-owner output (one name: of the output itself), then the per-op output's.
-        -> (_finish_chain's result, the info dict - the per-op entry only with return_frames > 1)."""
+        """_finish_chain for a chain with side outputs, whose run() returns (xh_phar, xh_pocket, z_steps) and then one pair (per owner,
+        per op and owner) for every steering part.  names: the info key of every column of the per-owner output (one name: of the output
+        itself), then the per-op output's - or, for a chain with several parts, a tuple of such tuples, one per pair.
+        -> (_finish_chain's result, the info dict - the per-op entries only with return_frames > 1)."""
         extra = []
 
         def run3():
@@ -304,10 +305,12 @@ class ConditionalDDPM(EnVariationalDiffusion):
             return out[:3]
 
         out = self._finish_chain(h, run3, frame_of_step, return_frames)
-        *cols, per_op = names
-        info = {cols[0]: extra[0]} if len(cols) == 1 else {name: extra[0][:, c].clone() for c, name in enumerate(cols)}
-        if return_frames > 1:
-            info[per_op] = extra[1]
+        info = {}
+        for pair, (*cols, per_op) in enumerate(names if isinstance(names[0], tuple) else (names,)):
+            per_owner, per_op_out = extra[2 * pair], extra[2 * pair + 1]
+            info.update({cols[0]: per_owner} if len(cols) == 1 else {name: per_owner[:, c].clone() for c, name in enumerate(cols)})
+            if return_frames > 1:
+                info[per_op] = per_op_out
         return out, info
 
     def _level_noise(self, noise, R, K, n_phar, device):
@@ -369,6 +372,34 @@ class ConditionalDDPM(EnVariationalDiffusion):
         steer = dict(strength=strength, width=width, max_shift=max_shift, guide_below=guide_below)
         return self._run_chain('diverse_chain', ps, nph, timesteps, behind=(sets,), steer=steer, info=self.OVERLAP_INFO, return_frames=return_frames,
                                noise=noise, seed=seed, ids=pocket_ids)
+
+    @torch.no_grad()
+    def sample_diverse_restrained(self, pocket, num_nodes_phar, set_sizes, restraints, clash=None, scale=1.0, strength=1.0, width=2.0,
+                                  max_shift=None, guide_below=1.0, diverse_max_shift=None, diverse_guide_below=None, return_frames=1,
+                                  timesteps=None, noise=None, seed=None, pocket_ids=None):
+        """sample_diverse UNDER sample_restrained's restraints: different samples for one pocket that all keep a geometric query.  The same
+        chain (ops, draws, Philox counters) with both terms in the mean of every posterior op, both taken at the op's denoised estimate:
+        first the restraint term of sample_restrained, then the overlap term of sample_diverse, each with the definition and the scalars of
+        its own method (cmdgen_diverse_restrained_chain; the header of k_diverse_restrained_step_count in csrc/kernels_restrain.hip).  The
+        whole chain runs on the device, on one handle.
+
+        set_sizes, strength and width as sample_diverse; restraints, clash and scale as sample_restrained.  max_shift and guide_below
+        belong to the restraint term; the overlap term has its own diverse_max_shift and diverse_guide_below (None: the restraint
+        side's values).  strength = 0 is sample_restrained and scale = 0 is sample_diverse, bit for bit.
+        Returns sample_given_pocket's tuple plus {'energy': [B], 'max_violation': [B], 'overlap': [B]} of the returned sample (and
+        'op_energy', 'op_overlap' [timesteps, B] at every op's denoised estimate when return_frames > 1)."""
+        from .. import restraints as rs
+        timesteps = self._checked_frames(timesteps, return_frames)
+        ps = self._one_pocket(pocket)
+        nph = self._prior_sizes(num_nodes_phar, ps)
+        rec, steer = self._guide_kw(restraints, nph, clash, scale, max_shift, guide_below)
+        sets = rs.check_set_sizes(set_sizes, nph)
+        strength, width, diverse_max_shift, diverse_guide_below = rs.check_diverse_scalars(
+            strength, width, steer['max_shift'] if diverse_max_shift is None else diverse_max_shift,
+            steer['guide_below'] if diverse_guide_below is None else diverse_guide_below)
+        steer.update(strength=strength, width=width, diverse_max_shift=diverse_max_shift, diverse_guide_below=diverse_guide_below)
+        return self._run_chain('diverse_restrained_chain', ps, nph, timesteps, behind=(sets, rec), steer=steer,
+                               info=(self.ENERGY_INFO, self.OVERLAP_INFO), return_frames=return_frames, noise=noise, seed=seed, ids=pocket_ids)
 
     @staticmethod
     def group_weights(weights, n_groups, n_members):
@@ -766,6 +797,10 @@ class SimpleConditionalDDPM(ConditionalDDPM):
     def sample_restrained(self, *args, **kwargs):
         raise NotImplementedError('sample_restrained is not implemented for SimpleConditionalDDPM (no centre-of-mass projection: the '
                                   'guidance frame follows the projections); use ConditionalDDPM')
+
+    def sample_diverse_restrained(self, *args, **kwargs):
+        raise NotImplementedError('sample_diverse_restrained is not implemented for SimpleConditionalDDPM (no centre-of-mass projection: '
+                                  'both terms compare positions in a frame that follows the projections)')
 
     def sample_diverse(self, *args, **kwargs):
         raise NotImplementedError('sample_diverse is not implemented for SimpleConditionalDDPM (no centre-of-mass projection: the '

@@ -585,6 +585,10 @@ class EnVariationalDiffusion(nn.Module):
         raise NotImplementedError('sample_diverse is not implemented for the joint model (its pocket nodes diffuse with the latent: '
                                   'there is no fixed pocket frame in which to compare the samples of a set); use ConditionalDDPM')
 
+    def sample_diverse_restrained(self, *args, **kwargs):
+        raise NotImplementedError('sample_diverse_restrained is not implemented for the joint model (its pocket nodes diffuse with the '
+                                  'latent: there is no fixed pocket frame for the restraints or the samples of a set); use ConditionalDDPM')
+
     def sample_restrained_given_pockets(self, *args, **kwargs):
         raise NotImplementedError('sample_restrained_given_pockets is not implemented for the joint model (its pocket nodes diffuse with '
                                   'the latent, so several pockets cannot share one and there is no fixed frame for the restraints); use '

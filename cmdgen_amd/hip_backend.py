@@ -89,6 +89,9 @@ SYMBOLS = [
                                                      C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _fp, _fp, C.c_int32, _vp]),
     ('cmdgen_diverse_chain', C.c_int, [_vp, _fp, _fp, C.c_int32, C.c_int64, _i64p, C.c_float, C.c_float, C.c_float, C.c_float,
                                        _fp, C.c_uint64, _i64p, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int32, _vp]),
+    ('cmdgen_diverse_restrained_chain', C.c_int, [_vp, _fp, _fp, C.c_int32, _vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
+                                                  C.c_float, C.c_int64, _i64p, C.c_float, C.c_float, C.c_float, C.c_float,
+                                                  _fp, C.c_uint64, _i64p, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int32, _vp]),
     ('cmdgen_set_guide_table', C.c_int, [_vp, C.c_int32, _vp]),
     ('cmdgen_param_count', C.c_int, [_vp, _i64p]),
     ('cmdgen_param_offset', C.c_int, [_vp, C.c_char_p, _i64p, _i64p]),
@@ -441,6 +444,20 @@ class Handle:
         return self._sampling_chain(pocket_x, pocket_onehot, timesteps, sets=(set_sizes, strength, width, max_shift, guide_below),
                                     noise=noise, seed=seed, ids=pocket_ids, want_steps=want_steps, use_graph=use_graph)
 
+    def diverse_restrained_chain(self, pocket_x, pocket_onehot, timesteps: int, set_sizes: Sequence[int], restraints=None,
+                                 clash_radius: float = 0.0, clash_k: float = 0.0, scale: float = 1.0, max_shift: float = DEFAULT_MAX_SHIFT,
+                                 guide_below: float = 1.0, strength: float = 1.0, width: float = 2.0,
+                                 diverse_max_shift: float = DEFAULT_MAX_SHIFT, diverse_guide_below: float = 1.0, noise=None, seed: int = 0,
+                                 pocket_ids: Optional[Sequence[int]] = None, want_steps: bool = False, use_graph: bool = True):
+        """cmdgen_diverse_restrained_chain: sample_chain with restrained_chain's guidance term and then diverse_chain's term in the mean of
+        every posterior op (the header of k_diverse_restrained_step_count in kernels_restrain.hip defines it).  set_sizes, strength, width
+        as diverse_chain, with a max_shift and a guide_below of their own (diverse_max_shift, diverse_guide_below); restraints and the other
+        scalars as restrained_chain.
+        -> (xh_phar, xh_pocket, z_steps, energy [B, 2], op_energy [K, B] or None, overlap [B], op_overlap [K, B] or None)."""
+        return self._sampling_chain(pocket_x, pocket_onehot, timesteps, guide=(restraints, clash_radius, clash_k, scale, max_shift, guide_below),
+                                    sets=(set_sizes, strength, width, diverse_max_shift, diverse_guide_below),
+                                    noise=noise, seed=seed, ids=pocket_ids, want_steps=want_steps, use_graph=use_graph)
+
     MAX_GROUP = 8                    # include/cmdgen_hip.h: CMDGEN_MAX_GROUP
 
     def multi_pocket_chain(self, pocket_x, pocket_onehot, group_sizes: Sequence[int], weights, timesteps: int, noise=None,
@@ -528,8 +545,9 @@ class Handle:
                                               C.byref(b)), 'cmdgen_edit_plan')
         return a.value, b.value
 
-    # the C entry of a sampling chain, by the parts present: (groups, 'guide' / 'sets' / None, given)
+    # the C entry of a sampling chain, by the parts present: (groups, 'guide' / 'sets' / 'guide+sets' / None, given)
     _CHAIN_ENTRY = {(False, None, False): 'sample_chain', (False, 'guide', False): 'restrained_chain', (False, 'sets', False): 'diverse_chain',
+                    (False, 'guide+sets', False): 'diverse_restrained_chain',
                     (True, None, False): 'multi_pocket_chain', (True, 'guide', False): 'multi_restrained_chain',
                     (False, None, True): 'edit_chain', (False, 'guide', True): 'restrained_edit_chain',
                     (True, None, True): 'multi_edit_chain', (True, 'guide', True): 'multi_restrained_edit_chain'}
@@ -541,12 +559,13 @@ class Handle:
         phar_onehot, fix_x, fix_h) with plan: (start, resamplings, jump_length) - the edit kinds; guide: (restraints, clash_radius, clash_k,
         scale, max_shift, guide_below) - the restrained kinds, with energy [owners, 2] and op_energy [steps, owners] behind the three
         outputs (an owner is a sample, or a group); sets: (set_sizes, strength, width, max_shift, guide_below) - the diverse chain, with
-        overlap [B] and op_overlap [K, B].  -> (xh_phar, xh_pocket, z_steps) and the side outputs of guide or sets."""
+        overlap [B] and op_overlap [K, B]; both (without groups or given rows) - the restrained diverse chain, the guide's arguments and
+        outputs in front of the sets'.  -> (xh_phar, xh_pocket, z_steps) and the side outputs of guide, then of sets."""
         import torch
         P, R = self.cfg['phar_nf'], self.cfg['residue_nf']
-        steer = 'guide' if guide is not None else 'sets' if sets is not None else None
+        steer = '+'.join(n for n, part in (('guide', guide), ('sets', sets)) if part is not None) or None
         key = (groups is not None, steer, given is not None)
-        if key not in self._CHAIN_ENTRY or (guide is not None and sets is not None):
+        if key not in self._CHAIN_ENTRY:
             raise CmdgenError(f'no chain entry for groups, steering, given = {key}')
         name = 'cmdgen_' + self._CHAIN_ENTRY[key]
         rows, owners, group_seg = self.n_phar, self.batch, []
@@ -572,17 +591,19 @@ class Handle:
             given_seg, sched = [_ptr(t) for t in given], [int(timesteps), int(start), int(resamplings), int(jump_length)]
             noise_seg = [*self._noise_arg(noise)]
         steer_seg, side = [], ()
-        if guide is not None:
-            rec, n_rec = self._restraint_arg(guide[0])
-            steer_seg = [rec, n_rec, *[float(v) for v in guide[1:]]]
-        elif sets is not None:
-            set_sizes = np.ascontiguousarray(np.asarray(sets[0], dtype=np.int64).reshape(-1))
-            steer_seg = [len(set_sizes), set_sizes.ctypes.data_as(_i64p), *[float(v) for v in sets[1:]]]
         dev = pocket_x.device
         outs = self._chain_outputs(rows, steps, want_steps, dev)
-        if steer is not None:                               # per owner: (E, largest violation) of a guided chain, the overlap of a diverse one
-            side = (torch.empty((owners, 2) if guide is not None else (owners,), dtype=torch.float32, device=dev),
-                    torch.empty((steps, owners), dtype=torch.float32, device=dev) if want_steps else None)
+        # per owner: (E, largest violation) of a guided chain, the overlap of a diverse one - each with its output per op
+        side_of = lambda shape: (torch.empty(shape, dtype=torch.float32, device=dev),
+                                 torch.empty((steps, owners), dtype=torch.float32, device=dev) if want_steps else None)
+        if guide is not None:
+            rec, n_rec = self._restraint_arg(guide[0])
+            steer_seg += [rec, n_rec, *[float(v) for v in guide[1:]]]
+            side += side_of((owners, 2))
+        if sets is not None:
+            set_sizes = np.ascontiguousarray(np.asarray(sets[0], dtype=np.int64).reshape(-1))
+            steer_seg += [len(set_sizes), set_sizes.ctypes.data_as(_i64p), *[float(v) for v in sets[1:]]]
+            side += side_of((owners,))
         # every entry's own order: the steering scalars sit before the noise in the from-prior entries, behind the four outputs in the edit ones
         args = [_ptr(pocket_x), _ptr(pocket_onehot), *group_seg, *given_seg, *sched, *([] if given is not None else steer_seg), *noise_seg,
                 self._seed(seed), ids, *[_ptr(t) for t in outs], *(steer_seg if given is not None else []), *[_ptr(t) for t in side]]

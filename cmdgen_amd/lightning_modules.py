@@ -461,6 +461,30 @@ class PharPocketDDPM(nn.Module):
         return self._point_lists(xh_phar, {'size': num_nodes_phar}), info[0]
 
     @torch.no_grad()
+    def generate_phars_diverse_restrained(self, pdb_file, n_samples, restraints, pocket_ids=None, ref_ligand=None, num_nodes_phar=None,
+                                          clash=None, scale=1.0, strength=1.0, width=2.0, max_shift=None, guide_below=1.0,
+                                          diverse_max_shift=None, diverse_guide_below=None, timesteps=None, seed=None, noise=None):
+        """Generate n_samples DIFFERENT pharmacophores inside a pocket that ALL keep a geometric query
+        (ConditionalDDPM.sample_diverse_restrained): generate_phars_restrained's restraints and generate_phars_diverse's push in one chain.
+
+        restraints: the dicts of cmdgen_amd/restraints.py WITHOUT 'sample', given once in the PDB's frame and applied to every one of the
+        n_samples copies, which form one set.  clash, scale, max_shift, guide_below as generate_phars_restrained; strength (0:
+        generate_phars_restrained's chain) and width as generate_phars_diverse, with diverse_max_shift and diverse_guide_below of the
+        overlap term's own (None: the restraint side's values).  The pocket, num_nodes_phar and the move back as generate_phars_restrained.
+        -> (one point list per sample, [(type name, (x, y, z))] in the PDB's frame, and {'energy': [n_samples], 'max_violation':
+        [n_samples], 'overlap': [n_samples]} of the returned samples, to filter and rank on)."""
+        load = self._pocket_request('generate_phars_diverse_restrained', pdb_file, pocket_ids, ref_ligand)
+        at_least, per_sample = self._restraints_for_all(restraints)
+        pocket, = load(n_samples)
+        num_nodes_phar = self._num_nodes(num_nodes_phar, pocket, n_samples, at_least)
+        restraints = per_sample(num_nodes_phar, n_samples)
+        xh_phar, _, info = self._moved_back(pocket, n_samples, lambda: self.ddpm.sample_diverse_restrained(
+            pocket, num_nodes_phar, [n_samples], restraints, clash=clash, scale=scale, strength=strength, width=width, max_shift=max_shift,
+            guide_below=guide_below, diverse_max_shift=diverse_max_shift, diverse_guide_below=diverse_guide_below, timesteps=timesteps,
+            seed=seed, noise=noise))
+        return self._point_lists(xh_phar, {'size': num_nodes_phar}), info[0]
+
+    @torch.no_grad()
     def generate_phars_multi_restrained(self, pdb_files, n_samples, restraints, pocket_ids=None, ref_ligands=None, num_nodes_phar=None,
                                         weights=None, clash=None, scale=1.0, max_shift=None, guide_below=1.0, timesteps=None, seed=None,
                                         noise=None, group_ids=None):

@@ -663,6 +663,42 @@ int cmdgen_diverse_chain(cmdgen_handle* h, const float* pocket_x, const float* p
                          float* overlap_out /* dev [B] */, float* op_overlap_out /* dev [K][B] or NULL */,
                          int32_t use_graph, cmdgen_stream stream);
 
+/* ---- diverse sampling under restraints: both terms in one chain ------------------------- */
+/* cmdgen_sample_chain's chain (the same init, ops, draws, Philox counters keyed by pocket_ids, saved steps and CoG fix; the decode is
+ * unguided; the evaluations run their own k_readout, there is no own-velocity form) with BOTH steering terms in the mean of every posterior
+ * op t -> s (the header of k_diverse_restrained_step_count in csrc/kernels_restrain.hip; INTEGRATION.md, "Diverse sampling under
+ * restraints").  Both are taken at the same point, the denoised estimate of the op's input; each keeps the definition and the scalars of its
+ * own chain:
+ *   1. Restraint term.  Steps 1-4 of cmdgen_restrained_chain give d^r_i = -scale (n_x coef.z)^2 g_i from the sample's records and the clash
+ *      pair, clipped at max_shift.  Active for a touched sample (a record on it, or clash_radius > 0) when scale > 0 and t / T <= guide_below.
+ *   2. Overlap term.  Steps 1-3 of cmdgen_diverse_chain give d^v_ai from the set's y = xhat - shift with strength and width, clipped at its
+ *      own diverse_max_shift.  Active for a sample of a set with M > 1 when strength > 0 and t / T <= diverse_guide_below.
+ *   3. mu.x_i = ((z.x_i / coef.x - coef.y e_i) + d^r_i / n_x) + d^v_i / n_x: the two additions in that order, each made only where its term
+ *      is active; nothing is added for an inactive term, not even a zero.  Everything else is the plain step's.
+ *   energy_out dev [B][2] and op_energy_out dev [K][B] or NULL exactly as cmdgen_restrained_chain reports them; overlap_out dev [B] and
+ *   op_overlap_out dev [K][B] or NULL exactly as cmdgen_diverse_chain reports them (a per-op output is still computed where its term is
+ *   inactive but defined).  The other arguments as the two parents'; cmdgen_set_guide_table supplies (sigma_t, alpha_t) for both terms.
+ * Reductions that hold bit for bit on every output and the chain status, on a handle with readout_in_coord = 0:
+ *   strength = 0, or diverse_guide_below = 0, or every set of one member: cmdgen_restrained_chain's outputs, energy and op_energy included;
+ *   scale = 0, or no record and clash_radius = 0: cmdgen_diverse_chain's outputs, overlap and op_overlap included;
+ *   both at once: cmdgen_sample_chain's outputs.
+ * Sums are the parents' (a fixed order, no float atomics): two runs are equal bit for bit, captured or eager.  The chain has a slot of its
+ * own; the records, the partition and the scalars of both parts are part of its table block, so a change of any prepares the slot (and its
+ * graph) again.
+ * Refused with CMDGEN_EINVAL, nothing launched: what either parent refuses of its own arguments, in the parent's words; a sample beyond the
+ * step's 64 KiB of LDS (92 B per node at phar_nf 8: more than 712 nodes, where cmdgen_diverse_chain takes 1024); a no_com_projection handle;
+ * the joint model (CMDGEN_ESTATE).  Not combined with groups or given rows. */
+int cmdgen_diverse_restrained_chain(cmdgen_handle* h, const float* pocket_x, const float* pocket_onehot, int32_t timesteps,
+                                    const cmdgen_restraint* restraints_host, int64_t n_restraints,
+                                    float clash_radius, float clash_k, float scale, float max_shift, float guide_below,
+                                    int64_t n_sets, const int64_t* set_size_host,
+                                    float strength, float width, float diverse_max_shift, float diverse_guide_below,
+                                    const float* noise, uint64_t seed, const int64_t* pocket_ids_host,
+                                    float* xh_phar_out, float* xh_pocket_out, float* z_steps_out, float* pocket_steps_out,
+                                    float* energy_out /* dev [B][2] */, float* op_energy_out /* dev [K][B] or NULL */,
+                                    float* overlap_out /* dev [B] */, float* op_overlap_out /* dev [K][B] or NULL */,
+                                    int32_t use_graph, cmdgen_stream stream);
+
 /* ---- training step (conditional model) -------------------------------------------------- */
 /* The trainable tensors of EGNNDynamics live in ONE flat fp32 device buffer owned by the caller, in the
  * reference's registration order (the state_dict order below 'ddpm.dynamics.': weight then bias of every
